@@ -28,6 +28,8 @@ of the side file that holds everything else (per-launch table, unfused per-stage
   stages_frac   {stage: [ms, frac of 8 TB/s, frac of the MFMA peak]} of the default configuration and of the one-launch-per-layer pass.
   configs_alt   {name: [images/sec, roofline frac, parity ok]}: BASELINE.json configs[4] (bf16, batch 512) and configs[1] (batch 1).
   ranks         N > 1: per rank [rank, device ordinal, PCI bus id, images per step, seconds], `collective_world_size`, `backend`.
+--dump-outputs DIR writes DIR/logits.npy after the timed steps: the float32 [batch, 1000] logits the last timed step left on rank 0's
+device (a seeded row sample beyond 64 MB). Images and weights are seeded, so equal arguments give equal inputs on every run.
 """
 import argparse
 import json
@@ -253,7 +255,12 @@ def parse_args(argv=None):
                          "the evidence behind `roofline` and `stages_frac`. Never inside the region `value` comes from")
     ap.add_argument("--no-power", action="store_true", help="skip the untimed ~1.5 s loop that samples package power / core clock with rocm-smi")
     ap.add_argument("--record", default="", help="path of the full record (default: gpurun_out/bench_full_<workload>.json under the repo)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0's logits, float32) as DIR/<name>.npy; "
+                         "inputs and weights are seeded, so two builds run with the same arguments can be compared output for output")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.streams <= 0:
         # bf16 (round 6, profiles/r06/v_bf16_streams.txt): two streams +3.2 % at 1.0x224 batch 512 (282-284 k -> 291-293 k), equal at 0.5x160 (its step is
         # 0.5 ms of short launches), three lose 8-20 %: two from 1e7 batch * alpha^2 * res^2 up (1.0x224 at batch 512: 2.6e7; 0.5x160: 3.3e6)
@@ -377,6 +384,35 @@ def write_record(args, out):
     return os.path.relpath(name, ROOT) if os.path.abspath(name).startswith(ROOT + os.sep) else name
 
 
+DUMP_LIMIT = 64 << 20      # bytes written by --dump-outputs in all
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT):
+    """--dump-outputs: each array as dirname/<name>.npy in float32 (float64 stays float64). When the arrays together exceed `limit`
+    bytes, each array keeps a fixed, seeded sample of its leading-axis rows, in order, and `<name>_rows.npy` (float64) names those
+    rows; the files then stay under `limit` in all. Returns {name: path} of the files written. Pure host code: tests/test_host_cpu.py
+    drives it with synthetic arrays."""
+    import numpy as np
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > limit:       # the row-index files (8 B per row kept) and the .npy headers come out of the same budget
+        total += sum(8 * v.shape[0] for v in arrays.values() if v.ndim >= 1)
+        limit -= 1024 * 2 * len(arrays)
+    os.makedirs(dirname, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        if total > limit and a.ndim >= 1 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * limit // total))
+            rows = np.sort(np.random.default_rng(0x5EED).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+            written[name + "_rows"] = os.path.join(dirname, name + "_rows.npy")
+            np.save(written[name + "_rows"], rows.astype(np.float64))
+        written[name] = os.path.join(dirname, name + ".npy")
+        np.save(written[name], np.ascontiguousarray(a))
+    return written
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -446,6 +482,7 @@ def configs_alt(args, env):
         a.steps, a.warmup = (200, 20) if a.batch == 1 else (60, 8)
         a.profile_steps = 5                      # after the timed region, like the headline's
         a.no_cpu_variants = a.no_unfused_stages = a.no_pw_emul_alt = True
+        a.dump_outputs = ""                       # --dump-outputs holds the headline workload's outputs only
         a.cpu_images = 1 if a.batch == 1 else 8
         o = run_one(a, env)
         keep = ("value", "unit", "ms_per_step", "steps", "warmup", "dtype", "config", "roofline", "stages", "sum_kernel_ms",
@@ -546,6 +583,8 @@ def run_one(args, env):
     logits = d_out.download((args.batch, 1000), np.float32)      # what the timed steps left on the device
     if not np.isfinite(logits).all():
         sys.exit("non-finite logits")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logits": logits})
 
     # ---- after the region: `profile_steps` forwards on ONE stream with a HIP event pair around every launch (roofline, stages_frac),
     # the pw_gemm launches also accumulating the core clock they held (tune key pw_clock)

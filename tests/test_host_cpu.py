@@ -635,6 +635,36 @@ def test_bench_line_is_compact_parseable_and_keeps_the_contract(tmp_path):
     assert json.load(open(path))["layers"][0]["stage"] == "pointwise"
 
 
+def test_bench_dump_outputs_writes_float_npy_under_the_limit(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float32 / float64; above the byte limit a fixed, seeded sample of rows (the same on
+    every call) plus <name>_rows.npy naming them, all files together under the limit. --steps below 1 is refused."""
+    import importlib
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    bench = importlib.import_module("bench")
+    assert bench.DUMP_LIMIT == 64 << 20
+    logits = np.random.default_rng(1).standard_normal((256, 1000)).astype(np.float32)
+    files = bench.dump_outputs(str(tmp_path / "small"), {"logits": logits, "ids": np.arange(256, dtype=np.int32)})
+    assert sorted(files) == ["ids", "logits"]
+    got = np.load(files["logits"])
+    assert got.dtype == np.float32 and np.array_equal(got, logits)
+    assert np.load(files["ids"]).dtype == np.float32 and np.array_equal(np.load(files["ids"]), np.arange(256))
+    limit = 100 * 1000 * 4
+    big = {"logits": logits, "x64": logits.astype(np.float64)}
+    files = bench.dump_outputs(str(tmp_path / "big"), big, limit=limit)
+    assert sorted(files) == ["logits", "logits_rows", "x64", "x64_rows"]
+    assert sum(os.path.getsize(p) for p in files.values()) <= limit
+    rows = np.load(files["logits_rows"])
+    assert rows.dtype == np.float64 and 0 < len(rows) < 256 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(files["logits"]), logits[rows.astype(np.int64)]) and np.load(files["x64"]).dtype == np.float64
+    again = bench.dump_outputs(str(tmp_path / "again"), big, limit=limit)
+    assert np.array_equal(np.load(again["logits_rows"]), rows)
+    assert bench.parse_args(["--steps", "7", "--dump-outputs", "d"]).steps == 7
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
 def test_bench_power_sampler_parses_rocm_smi_json(monkeypatch):
     """bench.py's sample_power (round 5: package power and core clock while the step runs back to back, AFTER the timed region) against a canned rocm-smi: the JSON
     shapes of `--showpower --showclocks --json` and `--showmaxpower --json` as the MI355X boxes print them; a missing rocm-smi gives None, never an exception."""

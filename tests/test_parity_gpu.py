@@ -2146,6 +2146,33 @@ def test_bench_rccl_collectives_rehearsed_with_one_rank(pkg):
     assert out["collective_world_size"] == 1 and out["backend"] == "nccl" and len(out["ranks"]) == 1 and out["ranks"][0][2].count(":") == 2
 
 
+def test_bench_dump_outputs_repeat_run_for_run(pkg, tmp_path):
+    """bench.py --dump-outputs DIR: after exactly --steps timed steps the logits the last one left on the device land in DIR/logits.npy
+    (float32, [batch, 1000], finite), the line's ms_per_step covers those steps, and a second run with the same arguments (seeded images
+    and weights) dumps the same logits bit for bit."""
+    import json
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        cmd = [sys.executable, os.path.join(pkg.REPO_ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "16", "--alpha", "0.5",
+               "--res", "96", "--no-configs-alt", "--no-cpu-baseline", "--no-unfused-stages", "--no-pw-emul-alt", "--no-power",
+               "--record", str(tmp_path / ("full%d.json" % i)), "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = json.loads(r.stdout.splitlines()[-1])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+        full = json.load(open(tmp_path / ("full%d.json" % i)))         # unrounded: value = batch / the time one timed step took
+        assert full["steps"] == 3 and abs(full["value"] * full["ms_per_step"] * 1e-3 - 16) < 1e-6
+        assert sorted(os.listdir(d)) == ["logits.npy"]
+        got = np.load(d / "logits.npy")
+        assert got.dtype == np.float32 and got.shape == (16, 1000) and np.isfinite(got).all() and np.abs(got).max() > 0
+        dumps.append(got)
+    assert np.array_equal(dumps[0], dumps[1])
+
+
 def _lab(ctx):
     return ctx.lib.mbn_lab_build() == 1
 
