@@ -530,6 +530,9 @@ int mbn_f32_dwpw3_eligible(const mbn_context *ctx, int batch, int in_rows, int i
     if (4.0 * batch * in_rows * in_cols * cin + 4.0 * (pad_left + 1) * cin > (double)0x70000000u) return 0;
     if ((double)batch * in_rows >= 8388000.0 || in_cols >= 32768 || out_cols >= 16384 || out_rows >= 32768 || pad_left > 1 || pad_top > 1) return 0;
     if ((double)batch * out_rows >= 2000000.0 || (double)batch * out_rows * out_cols >= 2147483000.0) return 0;
+    // a pixel pair past the end of a ragged last tile stores at PO_INVALID + its channel offset: dropped only while the whole output (+ one
+    // wave tile) stays below PO_INVALID; beyond it those stores would land inside the output (outputs of 2 .. 4 GiB run on dwpw2 / dwpw)
+    if (4.0 * ((double)batch * out_rows * out_cols + WT) * cout > (double)PO_INVALID) return 0;
     const int nh = cout / BN3;
     if (ctx->num_cus / (8 * nh) < 1) return 0;
     return 1;
