@@ -191,37 +191,46 @@ int mbn_net_set_streams(mbn_net *net, int n)
     return MBN_OK;
 }
 
+/* The fused kernels load their parameters with 16-byte accesses and answer MBN_EUNSUPPORTED otherwise: the filter, scale and
+ * shift segments of layer i must exist and start on 16 bytes. The plan's own segments are 256-byte aligned in the blob; a
+ * caller's plan or device blob need not be. */
+static int seg_aligned(const mbn_net *net, int64_t off)
+{
+    return off >= 0 && ((uintptr_t)blob_at(net, off) % 16) == 0;
+}
+
+static int layer_aligned(const mbn_net *net, int i)
+{
+    const mbn_layer_desc *l = &net->plan.layer[i];
+    return seg_aligned(net, l->w_offset) && seg_aligned(net, l->scale_offset) && seg_aligned(net, l->shift_offset);
+}
+
 /* layers 1-3 can go through mbn_stem_fused: conv 3x3 s2 -> dw s1 -> pw with 32 -> 32 -> 64 channels, fp32, nothing kept */
 static int stem_fusable(const mbn_net *net, int last_layer)
 {
     const mbn_layer_desc *l = net->plan.layer;
-    /* the fused kernels load with 16-byte accesses: a caller-provided device blob must be aligned (the plan's segments are
-     * 256-byte aligned inside it); mbn_net_launches and the forward both decide here, so they cannot disagree */
-    if (((uintptr_t)net->dev_blob % 16) != 0) return 0;
     return net->fuse_stem && !net->keep && last_layer >= 3 && net->plan.n_layers >= 3 &&
            (net->dtype == MBN_DT_F32 || (net->dtype == MBN_DT_BF16 && net->bf16_filt[2])) &&
            l[0].kind == MBN_L_CONV && l[1].kind == MBN_L_DW && l[2].kind == MBN_L_PW && l[0].in_ch == 3 &&
            ((l[0].out_ch == 32 && l[2].out_ch == 64) || (l[0].out_ch == 16 && l[2].out_ch == 32)) && l[1].stride == 1 &&
-           (net->plan.res % 32) == 0;
+           (net->plan.res % 32) == 0 && layer_aligned(net, 0) && layer_aligned(net, 1) && layer_aligned(net, 2);
+}
+
+/* a captured graph bakes the launch list in: drop it when the fusion settings change */
+static void drop_graph(mbn_net *net)
+{
+    if (net->graph) {
+        mbn_sync(net->ctx);
+        mbn_graph_destroy(net->ctx, net->graph);
+        net->graph = NULL;
+    }
 }
 
 int mbn_net_set_fuse_stem(mbn_net *net, int enabled)
 {
     if (!net) return MBN_EINVAL;
-    if (net->fuse_stem != (enabled != 0) && net->graph) {
-        mbn_sync(net->ctx);
-        mbn_graph_destroy(net->ctx, net->graph);
-        net->graph = NULL;
-    }
+    if (net->fuse_stem != (enabled != 0)) drop_graph(net);
     net->fuse_stem = enabled != 0;
-    return MBN_OK;
-}
-
-int mbn_net_fused_layers(const mbn_net *net, int last_layer, int *count)
-{
-    if (!net || !count) return MBN_EINVAL;
-    if (last_layer <= 0 || last_layer > net->plan.n_layers) last_layer = net->plan.n_layers;
-    *count = stem_fusable(net, last_layer) ? 3 : 0;
     return MBN_OK;
 }
 
@@ -254,15 +263,16 @@ static int block_fusable(const mbn_net *net, int i, int count, int last_layer)
         const long tiles = (((long)count * q->out_rows * q->out_cols + 127) / 128) * ((q->out_ch + 127) / 128);
         if (tiles * 2 < net->num_cus) return 0;
     }
-    if (((uintptr_t)net->dev_blob % 16) != 0) return 0;            /* see stem_fusable */
     const mbn_layer_desc *d = &net->plan.layer[i], *p = &net->plan.layer[i + 1];
     if (d->kind != MBN_L_DW || p->kind != MBN_L_PW || (d->stride != 1 && d->stride != 2)) return 0;
+    if (!layer_aligned(net, i) || !layer_aligned(net, i + 1)) return 0;
     if (d->in_ch < 32 || (d->in_ch % 32) != 0 || d->in_ch > 1024 || p->out_ch > 1024) return 0;
     if (bf ? (p->out_ch < 64 || (p->out_ch % 64) != 0) : (p->out_ch < 128 || (p->out_ch % 128) != 0)) return 0;   /* bf16 (round 5): 64-column remainders on a padded tile */
     if ((d->out_cols & 1) || p->in_ch != d->out_ch) return 0;
+    /* the 32-bit offset bounds of mbn_f32_dwpw_check / mbn_bf16_dwpw_check: the output keeps a row tile of head room */
     const double es = bf ? 2.0 : 4.0;
     if (es * count * d->in_rows * d->in_cols * d->in_ch >= 4026531840.0) return 0;
-    if (es * count * p->out_rows * p->out_cols * p->out_ch >= 4294967296.0) return 0;
+    if (es * ((double)count * d->out_rows * d->out_cols + 256.0) * p->out_ch >= 4294967296.0) return 0;
     return 1;
 }
 
@@ -286,10 +296,10 @@ static int resident_run(const mbn_net *net, int i, int count, int last_layer)
 
 /* Layers i+1 ... i+5 (0-based index i) are the network's last two blocks and the global pool in the shape mbn_tail_resident_bf16 takes (round 6): bf16, nothing
  * kept, resident launches enabled, both blocks enabled in the mask in force; depthwise stride 2 without top / left padding on an even map of at most 10 x 10 x 256,
- * pointwise 256 -> 512, depthwise stride 1 with pad 1, pointwise 512 -> 512, pool over the whole map (layers 24-28 of the 0.5x160 network). */
+ * pointwise 256 -> 512, depthwise stride 1 with pad 1, pointwise 512 -> 512, pool over the whole map (layers 24-28 of the 0.5x160 network).
+ * The kernel takes only (rows, cols, 256, 512) and assumes the rest, so every other shape of the five layers is checked here. */
 static int tail_run(const mbn_net *net, int i, int count, int last_layer)
 {
-    (void)count;
     if (net->dtype != MBN_DT_BF16 || !net->fuse_resident || net->keep || i + 5 > last_layer || i + 5 > net->plan.n_layers || i + 4 >= 32) return 0;
     const mbn_layer_desc *d0 = &net->plan.layer[i], *p0 = &net->plan.layer[i + 1], *d1 = &net->plan.layer[i + 2], *p1 = &net->plan.layer[i + 3],
                          *po = &net->plan.layer[i + 4];
@@ -297,14 +307,16 @@ static int tail_run(const mbn_net *net, int i, int count, int last_layer)
     if (!net->bf16_filt[i + 1] || !net->bf16_filt[i + 3]) return 0;
     const unsigned mask = fuse_mask(net);
     if (!((mask >> (i + 1)) & 1u) || !((mask >> (i + 3)) & 1u)) return 0;
-    if (((uintptr_t)net->dev_blob % 16) != 0) return 0;
+    for (int k = i; k < i + 4; k++)
+        if (!layer_aligned(net, k)) return 0;
     if (d0->stride != 2 || d0->pad_top != 0 || d0->pad_left != 0 || d0->in_ch != 256 || p0->out_ch != 512 || (d0->in_rows & 1) || (d0->in_cols & 1) ||
-        d0->in_rows > 10 || d0->in_cols > 10 || d0->out_rows != d0->in_rows / 2 || d0->out_cols != d0->in_cols / 2)
+        d0->in_rows > 10 || d0->in_cols > 10 || d0->out_rows != d0->in_rows / 2 || d0->out_cols != d0->in_cols / 2 || p0->in_ch != d0->out_ch)
         return 0;
     if (d1->stride != 1 || d1->pad_top != 1 || d1->pad_left != 1 || d1->in_ch != 512 || p1->out_ch != 512 || d1->out_rows != d0->out_rows ||
-        d1->out_cols != d0->out_cols)
+        d1->out_cols != d0->out_cols || d1->in_rows != d0->out_rows || d1->in_cols != d0->out_cols || p1->in_ch != d1->out_ch)
         return 0;
-    if (po->in_rows != d0->out_rows || po->in_cols != d0->out_cols || po->out_ch != 512) return 0;
+    if (po->in_rows != d0->out_rows || po->in_cols != d0->out_cols || po->out_ch != 512 || po->out_rows != 1 || po->out_cols != 1) return 0;
+    if (2.0 * count * d0->in_rows * d0->in_cols * d0->in_ch >= 4294967296.0) return 0;     /* the input's 32-bit offsets (mbn_launch_bf16_tail) */
     return 1;
 }
 
@@ -313,17 +325,46 @@ static int tail_fusable(const mbn_net *net, int i, int count, int last_layer)
 {
     if (!net->fuse_tail || !net->poolfc_ws || net->dtype != MBN_DT_F32 || net->keep || count < 1 || count > 4) return 0;
     if (i + 2 != last_layer || last_layer != net->plan.n_layers) return 0;
-    return net->plan.layer[i].kind == MBN_L_POOL && net->plan.layer[i + 1].kind == MBN_L_FC;
+    return net->plan.layer[i].kind == MBN_L_POOL && net->plan.layer[i + 1].kind == MBN_L_FC && seg_aligned(net, net->plan.layer[i + 1].w_offset);
 }
 
-/* a captured graph bakes the launch list in: drop it when the fusion settings change */
-static void drop_graph(mbn_net *net)
+/* Launch kinds, in the order next_launch tries them */
+enum { K_STEM, K_RESIDENT, K_TAIL, K_BLOCK, K_POOLFC, K_SINGLE };
+
+/* The launch that starts at 0-based layer i for `count` images: returns its kind, *span = the layers it covers (stem 3, resident
+ * run 2k, resident tail 5, block 2, pool + FC 2, single 1). Kinds in the bit set `excluded` are skipped (the forward excludes a
+ * fused kind whose call answered MBN_EUNSUPPORTED); fused_ok = 0 (per-layer timing) = single layers only. The forward, the
+ * launch list and the fused-stem report all decide here, so they cannot disagree. */
+static int next_launch(const mbn_net *net, int i, int count, int last_layer, int fused_ok, unsigned excluded, int *span)
 {
-    if (net->graph) {
-        mbn_sync(net->ctx);
-        mbn_graph_destroy(net->ctx, net->graph);
-        net->graph = NULL;
+    int k = 0;
+    *span = 2;
+    if (fused_ok) {
+        if (i == 0 && !(excluded & (1u << K_STEM)) && stem_fusable(net, last_layer)) { *span = 3; return K_STEM; }
+        if (!(excluded & (1u << K_RESIDENT)) && (k = resident_run(net, i, count, last_layer))) { *span = 2 * k; return K_RESIDENT; }
+        if (!(excluded & (1u << K_TAIL)) && tail_run(net, i, count, last_layer)) { *span = 5; return K_TAIL; }
+        if (!(excluded & (1u << K_BLOCK)) && block_fusable(net, i, count, last_layer)) return K_BLOCK;
+        if (!(excluded & (1u << K_POOLFC)) && tail_fusable(net, i, count, last_layer)) return K_POOLFC;
     }
+    *span = 1;
+    return K_SINGLE;
+}
+
+/* the sub-batch streams a forward of `batch` images uses: per-layer timing serialises; sub-batches of fewer than 5 images are not
+ * forked: they would take the 1..4-image kernels (mbn_f32_pw_splitk.hip), whose summation order differs from the single-stream
+ * forward of the whole batch */
+static int streams_used(const mbn_net *net, int batch, int timed)
+{
+    return (timed || batch < 5 * net->nstreams) ? 1 : net->nstreams;
+}
+
+int mbn_net_fused_layers(const mbn_net *net, int last_layer, int *count)
+{
+    if (!net || !count) return MBN_EINVAL;
+    if (last_layer <= 0 || last_layer > net->plan.n_layers) last_layer = net->plan.n_layers;
+    int span;
+    *count = next_launch(net, 0, net->max_batch, last_layer, 1, 0, &span) == K_STEM ? 3 : 0;
+    return MBN_OK;
 }
 
 int mbn_net_set_input_u8(mbn_net *net, int enabled)
@@ -381,20 +422,12 @@ int mbn_net_launches(const mbn_net *net, int batch, int last_layer, int *first_l
 {
     if (!net || !count || batch <= 0) return MBN_EINVAL;
     if (last_layer <= 0 || last_layer > net->plan.n_layers) last_layer = net->plan.n_layers;
-    int ns = net->nstreams;
-    if (batch < 5 * ns) ns = 1;                        /* as forward_impl */
-    const int sub = ns > 1 ? batch / ns + (batch % ns ? 1 : 0) : batch;      /* the largest sub-batch decides the envelope */
-    int n = 0, i = 0;
-    while (i < last_layer) {
-        int span = 1;
-        if (i == 0 && stem_fusable(net, last_layer)) span = 3;
-        else if (resident_run(net, i, sub, last_layer)) span = 2 * resident_run(net, i, sub, last_layer);
-        else if (tail_run(net, i, sub, last_layer)) span = 5;
-        else if (block_fusable(net, i, sub, last_layer)) span = 2;
-        else if (tail_fusable(net, i, sub, last_layer)) span = 2;
+    const int ns = streams_used(net, batch, 0);
+    const int sub = batch / ns + (batch % ns ? 1 : 0);      /* the largest sub-batch decides the envelope */
+    int n = 0, span;
+    for (int i = 0; i < last_layer; i += span, n++) {
+        (void)next_launch(net, i, sub, last_layer, 1, 0, &span);
         if (first_layer && n_layers && n < capacity) { first_layer[n] = i + 1; n_layers[n] = span; }
-        n++;
-        i += span;
     }
     *count = n;
     return MBN_OK;
@@ -404,11 +437,7 @@ int mbn_net_set_graph(mbn_net *net, int enabled)
 {
     if (!net) return MBN_EINVAL;
     net->use_graph = enabled != 0;
-    if (!enabled && net->graph) {
-        mbn_sync(net->ctx);
-        mbn_graph_destroy(net->ctx, net->graph);
-        net->graph = NULL;
-    }
+    if (!enabled) drop_graph(net);
     return MBN_OK;
 }
 
@@ -485,6 +514,24 @@ static size_t out_esize(const mbn_net *net, const mbn_layer_desc *l)
     return (net->dtype == MBN_DT_BF16 && l->kind != MBN_L_FC) ? 2 : 4;
 }
 
+/* the parameters of the `nblocks` blocks from layer i on (depthwise i + 2k, pointwise i + 2k + 1) for the bf16 resident kernels */
+static void block_params(const mbn_net *net, int i, int nblocks, mbn_block_params *bp)
+{
+    for (int k = 0; k < nblocks; k++) {
+        const mbn_layer_desc *d = &net->plan.layer[i + 2 * k], *p = d + 1;
+        bp[k].wd = blob_at(net, d->w_offset); bp[k].s2 = blob_at(net, d->scale_offset); bp[k].b2 = blob_at(net, d->shift_offset);
+        bp[k].wp_bf16 = net->bf16_filt[i + 2 * k + 1]; bp[k].s3 = blob_at(net, p->scale_offset); bp[k].b3 = blob_at(net, p->shift_offset);
+    }
+}
+
+/* layer i's buffer for kept activations (max_batch images at fp32 size), allocated on first use */
+static int alloc_keep(mbn_net *net, int i)
+{
+    const mbn_layer_desc *l = &net->plan.layer[i];
+    if (net->keep_buf[i]) return MBN_OK;
+    return mbn_alloc(net->ctx, (size_t)l->out_rows * l->out_cols * l->out_ch * sizeof(float) * (size_t)net->max_batch, &net->keep_buf[i]);
+}
+
 /* Layers 1..last_layer for images [first, first+count) on `stream` (NULL = the context's stream). Sub-batches use
  * disjoint slices of the two ping-pong buffers, so several of them can be in flight on different streams. */
 static int forward_range(mbn_net *net, const void *images, void *logits, int first, int count, int last_layer,
@@ -493,151 +540,75 @@ static int forward_range(mbn_net *net, const void *images, void *logits, int fir
     const size_t img_floats = (size_t)net->plan.res * net->plan.res * 3;
     const char *src = (const char *)images + (size_t)first * img_floats * (net->input_u8 ? 1 : sizeof(float));
     const size_t slot = (size_t)first * (size_t)net->plan.max_act_floats * sizeof(float);
-    int which = 0, i0 = 0;
-    if (!layer_ms && stem_fusable(net, last_layer)) {
-        /* layers 1-3 in one kernel; the 112x112x32 intermediates stay on chip */
-        const mbn_layer_desc *l = net->plan.layer;
-        const int bf = net->dtype == MBN_DT_BF16;
-        const size_t per_img = (size_t)l[2].out_rows * l[2].out_cols * l[2].out_ch * (bf ? 2 : sizeof(float));
-        char *dst = last_layer == 3 ? (char *)logits + (size_t)first * per_img : (char *)net->act[which] + slot;
-        int rc = mbn_stem_fused_ex(net->ctx, dst, src, blob_at(net, l[0].w_offset), blob_at(net, l[0].scale_offset),
-                                   blob_at(net, l[0].shift_offset), blob_at(net, l[1].w_offset), blob_at(net, l[1].scale_offset),
-                                   blob_at(net, l[1].shift_offset), bf ? net->bf16_filt[2] : blob_at(net, l[2].w_offset),
-                                   blob_at(net, l[2].scale_offset), blob_at(net, l[2].shift_offset), count, net->plan.res,
-                                   l[0].out_ch, l[2].out_ch, (net->input_u8 ? MBN_STEM_IN_U8 : 0) | (bf ? MBN_STEM_BF16 : 0), stream);
-        if (rc == MBN_OK) {
-            if (last_layer != 3) which ^= 1;
-            if (first == 0) { net->last_out[0] = net->last_out[1] = NULL; net->last_out[2] = dst; }
-            src = dst;
-            i0 = 3;
-            if (next_stream && stagger >= 1 && stagger <= 3) {
-                rc = mbn_stream_wait(net->ctx, next_stream, stream);
-                if (rc != MBN_OK) return rc;
-            }
-        } else if (rc != MBN_EUNSUPPORTED) return rc;
-    }
-    for (int i = i0; i < last_layer; i++) {
-        const mbn_layer_desc *l = &net->plan.layer[i];
-        const int rr = layer_ms ? 0 : resident_run(net, i, count, last_layer);
-        if (rr) {
-            /* rr blocks in one launch, the map resident in LDS from the first block's input to the last block's output */
-            mbn_block_params bp[8];
-            for (int k = 0; k < rr; k++) {
-                const mbn_layer_desc *d = &net->plan.layer[i + 2 * k], *p = &net->plan.layer[i + 2 * k + 1];
-                bp[k].wd = blob_at(net, d->w_offset); bp[k].s2 = blob_at(net, d->scale_offset); bp[k].b2 = blob_at(net, d->shift_offset);
-                bp[k].wp_bf16 = net->bf16_filt[i + 2 * k + 1]; bp[k].s3 = blob_at(net, p->scale_offset); bp[k].b3 = blob_at(net, p->shift_offset);
-            }
-            const int lastl = i + 2 * rr - 1;                      /* index of the run's last (pointwise) layer */
-            const mbn_layer_desc *lp = &net->plan.layer[lastl];
-            const size_t per_img2 = (size_t)lp->out_rows * lp->out_cols * lp->out_ch * 2;
-            char *dst2 = (lastl == last_layer - 1) ? (char *)logits + (size_t)first * per_img2 : (char *)net->act[which] + slot;
-            int rc = mbn_blocks_resident_bf16(net->ctx, dst2, src, bp, rr, count, l->in_rows, l->in_cols, l->in_ch, stream);
-            if (rc == MBN_OK) {
-                if (lastl != last_layer - 1) which ^= 1;
-                if (first == 0) {
-                    for (int k = i; k < lastl; k++) net->last_out[k] = NULL;
-                    net->last_out[lastl] = dst2;
-                }
-                src = dst2;
-                if (next_stream && stagger > i && stagger <= lastl + 1) {
-                    rc = mbn_stream_wait(net->ctx, next_stream, stream);
-                    if (rc != MBN_OK) return rc;
-                }
-                i = lastl;
-                continue;
-            }
-            if (rc != MBN_EUNSUPPORTED) return rc;
-        }
-        if (!layer_ms && tail_run(net, i, count, last_layer)) {
-            /* the last two blocks and the pool in one launch, an image's maps resident in LDS */
-            mbn_block_params bp[2];
-            for (int k = 0; k < 2; k++) {
-                const mbn_layer_desc *d = &net->plan.layer[i + 2 * k], *p = &net->plan.layer[i + 2 * k + 1];
-                bp[k].wd = blob_at(net, d->w_offset); bp[k].s2 = blob_at(net, d->scale_offset); bp[k].b2 = blob_at(net, d->shift_offset);
-                bp[k].wp_bf16 = net->bf16_filt[i + 2 * k + 1]; bp[k].s3 = blob_at(net, p->scale_offset); bp[k].b3 = blob_at(net, p->shift_offset);
-            }
-            const int lastl = i + 4;                               /* the pool */
-            const mbn_layer_desc *lp = &net->plan.layer[lastl];
-            const size_t per_img2 = (size_t)lp->out_ch * 2;
-            char *dst2 = (lastl == last_layer - 1) ? (char *)logits + (size_t)first * per_img2 : (char *)net->act[which] + slot;
-            int rc = mbn_tail_resident_bf16(net->ctx, dst2, src, bp, count, l->in_rows, l->in_cols, l->in_ch, lp->out_ch, stream);
-            if (rc == MBN_OK) {
-                if (lastl != last_layer - 1) which ^= 1;
-                if (first == 0) {
-                    for (int k = i; k < lastl; k++) net->last_out[k] = NULL;
-                    net->last_out[lastl] = dst2;
-                }
-                src = dst2;
-                if (next_stream && stagger > i && stagger <= lastl + 1) {
-                    rc = mbn_stream_wait(net->ctx, next_stream, stream);
-                    if (rc != MBN_OK) return rc;
-                }
-                i = lastl;
-                continue;
-            }
-            if (rc != MBN_EUNSUPPORTED) return rc;
-        }
-        if (!layer_ms && block_fusable(net, i, count, last_layer)) {
-            /* depthwise + pointwise in one kernel; the depthwise output stays in LDS */
-            const mbn_layer_desc *lp = &net->plan.layer[i + 1];
-            const int bf = net->dtype == MBN_DT_BF16;
-            const size_t per_img2 = (size_t)lp->out_rows * lp->out_cols * lp->out_ch * (bf ? 2 : sizeof(float));
-            char *dst2 = (i + 1 == last_layer - 1) ? (char *)logits + (size_t)first * per_img2 : (char *)net->act[which] + slot;
-            int rc = (bf ? mbn_dwpw_fused_bf16 : mbn_dwpw_fused)(
-                net->ctx, dst2, src, blob_at(net, l->w_offset), blob_at(net, l->scale_offset), blob_at(net, l->shift_offset),
-                bf ? net->bf16_filt[i + 1] : blob_at(net, lp->w_offset), blob_at(net, lp->scale_offset),
-                blob_at(net, lp->shift_offset), count, l->in_rows, l->in_cols, l->out_rows, l->out_cols, l->in_ch, lp->out_ch,
-                l->stride, l->pad_top, l->pad_left, stream);
-            if (rc == MBN_OK) {
-                if (i + 1 != last_layer - 1) which ^= 1;
-                if (first == 0) { net->last_out[i] = NULL; net->last_out[i + 1] = dst2; }
-                src = dst2;
-                if (next_stream && (i + 1 == stagger || i + 2 == stagger)) {
-                    rc = mbn_stream_wait(net->ctx, next_stream, stream);
-                    if (rc != MBN_OK) return rc;
-                }
-                i++;
-                continue;
-            }
-            if (rc != MBN_EUNSUPPORTED) return rc;
-        }
-        if (!layer_ms && tail_fusable(net, i, count, last_layer)) {
-            /* pool + FC in one launch (1...4 images: the forward is launch-bound there) */
-            const mbn_layer_desc *fc = &net->plan.layer[i + 1];
-            char *dst2 = (char *)logits + (size_t)first * fc->out_ch * sizeof(float);
-            int rc = mbn_pool_fc(net->ctx, dst2, src, blob_at(net, fc->w_offset), blob_at(net, fc->shift_offset), count, l->in_rows,
-                                 l->in_cols, l->out_ch, fc->out_ch, net->poolfc_ws, net->poolfc_ws_bytes, stream);
-            if (rc == MBN_OK) {
-                if (first == 0) { net->last_out[i] = NULL; net->last_out[i + 1] = dst2; }
-                break;
-            }
-            if (rc != MBN_EUNSUPPORTED) return rc;
-        }
-        const size_t per_img = (size_t)l->out_rows * l->out_cols * l->out_ch * out_esize(net, l);
+    const int bf = net->dtype == MBN_DT_BF16;
+    const mbn_layer_desc *L = net->plan.layer;
+    int which = 0, span;
+    unsigned excluded = 0;
+    for (int i = 0; i < last_layer; i += span) {
+        const int kind = next_launch(net, i, count, last_layer, !layer_ms, excluded, &span);
+        const int last = i + span - 1;                      /* the launch's last layer: its output is the launch's */
+        const mbn_layer_desc *l = &L[i], *lp = &L[last];
+        const size_t per_img = (size_t)lp->out_rows * lp->out_cols * lp->out_ch * out_esize(net, lp);
         char *dst;
-        if (i == last_layer - 1) dst = (char *)logits + (size_t)first * per_img;
-        else if (net->keep) {
-            if (!net->keep_buf[i]) {
-                size_t bytes = (size_t)l->out_rows * l->out_cols * l->out_ch * sizeof(float) * (size_t)net->max_batch;
-                int rc = mbn_alloc(net->ctx, bytes, &net->keep_buf[i]);
-                if (rc != MBN_OK) return rc;
-            }
+        int flip = 0;
+        if (last == last_layer - 1) dst = (char *)logits + (size_t)first * per_img;
+        else if (net->keep) {                               /* single layers only: every fused kind refuses kept activations */
+            int rc = alloc_keep(net, i);
+            if (rc != MBN_OK) return rc;
             dst = (char *)net->keep_buf[i] + (size_t)first * per_img;
         } else {
             dst = (char *)net->act[which] + slot;
-            which ^= 1;
+            flip = 1;
         }
-        int rc = run_layer(net, l, src, dst, count, stream);
+        mbn_block_params bp[8];
+        int rc;
+        switch (kind) {
+        case K_STEM:            /* layers 1-3 in one kernel; the 112x112x32 intermediates stay on chip */
+            rc = mbn_stem_fused_ex(net->ctx, dst, src, blob_at(net, L[0].w_offset), blob_at(net, L[0].scale_offset),
+                                   blob_at(net, L[0].shift_offset), blob_at(net, L[1].w_offset), blob_at(net, L[1].scale_offset),
+                                   blob_at(net, L[1].shift_offset), bf ? net->bf16_filt[2] : blob_at(net, L[2].w_offset),
+                                   blob_at(net, L[2].scale_offset), blob_at(net, L[2].shift_offset), count, net->plan.res,
+                                   L[0].out_ch, L[2].out_ch, (net->input_u8 ? MBN_STEM_IN_U8 : 0) | (bf ? MBN_STEM_BF16 : 0), stream);
+            break;
+        case K_RESIDENT:        /* span / 2 blocks in one launch, the map resident in LDS from the first block's input to the last block's output */
+            block_params(net, i, span / 2, bp);
+            rc = mbn_blocks_resident_bf16(net->ctx, dst, src, bp, span / 2, count, l->in_rows, l->in_cols, l->in_ch, stream);
+            break;
+        case K_TAIL:            /* the last two blocks and the pool in one launch, an image's maps resident in LDS */
+            block_params(net, i, 2, bp);
+            rc = mbn_tail_resident_bf16(net->ctx, dst, src, bp, count, l->in_rows, l->in_cols, l->in_ch, lp->out_ch, stream);
+            break;
+        case K_BLOCK:           /* depthwise + pointwise in one kernel; the depthwise output stays in LDS */
+            rc = (bf ? mbn_dwpw_fused_bf16 : mbn_dwpw_fused)(
+                net->ctx, dst, src, blob_at(net, l->w_offset), blob_at(net, l->scale_offset), blob_at(net, l->shift_offset),
+                bf ? net->bf16_filt[i + 1] : blob_at(net, lp->w_offset), blob_at(net, lp->scale_offset),
+                blob_at(net, lp->shift_offset), count, l->in_rows, l->in_cols, l->out_rows, l->out_cols, l->in_ch, lp->out_ch,
+                l->stride, l->pad_top, l->pad_left, stream);
+            break;
+        case K_POOLFC:          /* pool + FC in one launch (1...4 images: the forward is launch-bound there) */
+            rc = mbn_pool_fc(net->ctx, dst, src, blob_at(net, lp->w_offset), blob_at(net, lp->shift_offset), count, l->in_rows,
+                             l->in_cols, l->out_ch, lp->out_ch, net->poolfc_ws, net->poolfc_ws_bytes, stream);
+            break;
+        default:
+            rc = run_layer(net, l, src, dst, count, stream);
+            if (rc == MBN_OK && layer_ms && i < n_layer_ms) rc = mbn_last_kernel_ms(net->ctx, &layer_ms[i]);
+        }
+        if (rc == MBN_EUNSUPPORTED && kind != K_SINGLE) {   /* outside the kernel's envelope: the next kind at the same layer */
+            excluded |= 1u << kind;
+            span = 0;
+            continue;
+        }
         if (rc != MBN_OK) return rc;
-        if (layer_ms && i < n_layer_ms) {
-            rc = mbn_last_kernel_ms(net->ctx, &layer_ms[i]);
-            if (rc != MBN_OK) return rc;
+        excluded = 0;
+        which ^= flip;
+        if (first == 0) {
+            for (int k = i; k < last; k++) net->last_out[k] = NULL;
+            net->last_out[last] = dst;
         }
-        if (first == 0) net->last_out[i] = dst;
         src = dst;
         /* stagger: the next sub-batch's stream may start only when this one has finished `stagger` layers, so the
          * streams run a layer or two apart and unlike kernels (HBM-bound vs MFMA-bound) meet each other */
-        if (next_stream && i + 1 == stagger) {
+        if (next_stream && i < stagger && stagger <= i + span) {
             rc = mbn_stream_wait(net->ctx, next_stream, stream);
             if (rc != MBN_OK) return rc;
         }
@@ -651,32 +622,18 @@ static int forward_impl(mbn_net *net, const void *images, void *logits, int batc
     if (!net || !images || !logits || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
     const int n = net->plan.n_layers;
     if (last_layer <= 0 || last_layer > n) last_layer = n;
-    int ns = net->nstreams;
-    if (layer_ms || batch < 5 * ns) ns = 1;            /* per-layer timing serialises; sub-batches of fewer than 5 images are not
-                                                        * forked: they would take the 1..4-image kernels (mbn_f32_pw_splitk.hip), whose
-                                                        * summation order differs from the single-stream forward of the whole batch */
+    const int ns = streams_used(net, batch, layer_ms != NULL);
     if (ns <= 1) net->fr_images = NULL;                /* a single-stream forward in between: the next multi-stream one forks again */
     if (ns <= 1 && net->use_graph && !layer_ms) {
         /* launch-bound batches: replay the 29 launches as one hipGraph; re-capture when the call's key changes */
         int emul = 0;
         (void)mbn_tune_get("pw_emul", &emul);              /* the arithmetic form of the pointwise layers is baked into the capture */
-        if (net->graph && (net->g_images != images || net->g_logits != logits || net->g_batch != batch ||
-                           net->g_last != last_layer || net->g_dtype != net->dtype || net->g_keep != net->keep || net->g_emul != emul)) {
-            mbn_sync(net->ctx);
-            mbn_graph_destroy(net->ctx, net->graph);
-            net->graph = NULL;
-        }
+        if (net->g_images != images || net->g_logits != logits || net->g_batch != batch || net->g_last != last_layer ||
+            net->g_dtype != net->dtype || net->g_keep != net->keep || net->g_emul != emul)
+            drop_graph(net);
         if (!net->graph) {
-            if (net->keep)                                   /* allocations are not allowed inside a capture */
-                for (int i = 0; i < last_layer - 1; i++)
-                    if (!net->keep_buf[i]) {
-                        const mbn_layer_desc *l = &net->plan.layer[i];
-                        size_t bytes = (size_t)l->out_rows * l->out_cols * l->out_ch * sizeof(float) * (size_t)net->max_batch;
-                        int rc = mbn_alloc(net->ctx, bytes, &net->keep_buf[i]);
-                        if (rc != MBN_OK) return rc;
-                    }
-            /* one eager pass first: kernels that allocate a workspace on first use (the pre-split filter images of pw_emul) must
-             * have done so before the capture, inside which nothing may be allocated */
+            /* one eager pass first: kernels that allocate a workspace on first use (the pre-split filter images of pw_emul) and
+             * the kept-activation buffers must have been allocated before the capture, inside which nothing may be allocated */
             int rc = forward_range(net, images, logits, 0, batch, last_layer, NULL, NULL, 0, NULL, 0);
             if (rc != MBN_OK) return rc;
             rc = mbn_graph_begin(net->ctx, NULL);

@@ -882,7 +882,7 @@ def test_net_multi_stream_equals_single_stream(pkg, ctx, tmp_path, ns):
 
 def test_net_graph_replay_equals_eager(pkg, ctx, tmp_path):
     """mbn_net_set_graph: the captured hipGraph replays bit-identically, follows changed INPUT CONTENTS (same
-    pointers), and is re-captured when the batch or a pointer changes."""
+    pointers), and is re-captured when the batch, a pointer or the kept-activations switch changes."""
     hw, net = _make_net(pkg, ctx, tmp_path, 0.25, 64, 30, 4)
     rng = np.random.default_rng(8)
     a, b = (rng.uniform(-1, 1, (4, 64, 64, 3)).astype(np.float32) for _ in range(2))
@@ -903,6 +903,12 @@ def test_net_graph_replay_equals_eager(pkg, ctx, tmp_path):
     net.forward(d_in.ptr, d_out2.ptr, 2)                 # other batch + other output pointer -> re-capture
     ctx.sync()
     assert np.array_equal(d_out2.download((2, 30), np.float32), got_b[:2])
+    net.keep_activations(True)                           # kept buffers are allocated before the capture, never inside it
+    net.forward(d_in.ptr, d_out.ptr, 4)
+    ctx.sync()
+    assert np.array_equal(d_out.download((4, 30), np.float32), got_b)
+    assert net.layer_output(13, 4).shape[0] == 4
+    net.keep_activations(False)
     net.set_graph(False)
     net.forward(d_in.ptr, d_out.ptr, 4)
     ctx.sync()
@@ -1229,6 +1235,103 @@ def test_net_fused_blocks_equal_separate_layers(pkg, orc, ctx, tmp_path):
     net.set_fuse_blocks(0xFFFFFFFE)
     net.keep_activations(True)
     assert net.launches(n) == [(l, 1) for l in range(1, 30)]
+    net.destroy()
+
+
+def _launches_run(ctx, net, plan, d_in, batch, last):
+    """Number of launches one single-stream forward(batch, last) records in the profiling scope."""
+    l = plan.layer[(last or plan.n_layers) - 1]
+    d_out = ctx.alloc(batch * l.out_rows * l.out_cols * l.out_ch * 4)
+    ctx.profile_begin(64)
+    try:
+        net.forward(d_in.ptr, d_out.ptr, batch, last)
+    finally:
+        ran = ctx.profile_end(64)
+        d_out.free()
+    return len(ran)
+
+
+def test_net_launch_list_is_what_runs(pkg, ctx, tmp_path):
+    """mbn_net_launches lists exactly the launches one forward issues (bench.py sizes its per-launch profile from it): the count a
+    profiled single-stream forward records equals the list's length, in fp32 and bf16, under the default and an explicit mask, with
+    kept activations, the stem unfused, pool + FC fused, the resident launches on and off, and last_layer values inside fused launches."""
+    hw, net = _make_net(pkg, ctx, tmp_path, 1.0, 64, 20, 64)
+    d_in = ctx.to_device(np.random.default_rng(21).uniform(-1, 1, (64, 64, 64, 3)).astype(np.float32))
+    cases = [("default mask", n, last) for n in (1, 5, 64) for last in (0, 3, 5, 13, 27)]
+    cases += [("mask 0xFFFFFFFE", n, last) for n in (1, 5, 64) for last in (0, 3, 5, 13, 27)]
+    cases += [("kept", 5, last) for last in (0, 5, 13)] + [("stem unfused", 5, last) for last in (0, 3, 5)] + [("pool + FC", 2, 0)]
+    for what, n, last in cases:
+        if what == "mask 0xFFFFFFFE":
+            net.set_fuse_blocks(0xFFFFFFFE)
+        net.keep_activations(what == "kept")
+        net.set_fuse_stem(what != "stem unfused")
+        net.set_fuse_tail(what == "pool + FC")
+        if what == "pool + FC":
+            assert net.launches(n)[-1] == (28, 2), net.launches(n)
+        listed = net.launches(n, last)
+        assert _launches_run(ctx, net, hw.plan, d_in, n, last) == len(listed), (what, n, last, listed)
+    net.destroy()
+
+    hw, net = _make_net(pkg, ctx, tmp_path, 0.5, 160, 20, 16)
+    net.set_dtype(pkg.DT_BF16)
+    d_in = ctx.to_device(np.random.default_rng(22).uniform(-1, 1, (16, 160, 160, 3)).astype(np.float32))
+    for resident in (True, False):
+        net.set_fuse_resident(resident)
+        for n in (1, 16):
+            if resident:
+                assert (14, 10) in net.launches(n) and (24, 5) in net.launches(n), net.launches(n)
+            for last in (0, 15, 18, 23, 26, 28):      # cut into the resident run (layers 14-23) and the resident tail (24-28)
+                listed = net.launches(n, last)
+                assert _launches_run(ctx, net, hw.plan, d_in, n, last) == len(listed), (resident, n, last, listed)
+    net.destroy()
+
+
+def test_net_misaligned_blob_segments_run_unfused(pkg, orc, ctx, tmp_path):
+    """A caller's plan whose blob segments are not 16-byte aligned (one leading float in the device blob, every offset one float further):
+    the fused kernels cannot take them, so the launch list holds single layers only, the forward issues exactly those, and the logits
+    match the oracle. fp32 only: mbn_net_set_dtype(bf16) refuses misaligned pointwise segments."""
+    n, res = 5, 64
+    hw, aligned = _make_net(pkg, ctx, tmp_path, 1.0, res, 20, n)
+    aligned.destroy()
+    plan = pkg.Plan.from_buffer_copy(hw.plan)
+    for i in range(plan.n_layers):
+        l = plan.layer[i]
+        for f in ("w_offset", "scale_offset", "shift_offset"):
+            if getattr(l, f) >= 0:
+                setattr(l, f, getattr(l, f) + 1)
+    plan.blob_floats += 1
+    net = pkg.Net(ctx, plan, np.concatenate([np.zeros(1, np.float32), hw.blob]), n)
+    assert [c for _, c in net.launches(n)] == [1] * 29                   # the default would fuse the stem
+    net.set_fuse_blocks(0xFFFFFFFE)
+    assert [c for _, c in net.launches(n)] == [1] * 29                   # ... and this mask every block
+    imgs = np.random.default_rng(23).uniform(-1, 1, (n, res, res, 3)).astype(np.float32)
+    d_in, d_out = ctx.to_device(imgs), ctx.alloc(n * 20 * 4)
+    assert _launches_run(ctx, net, plan, d_in, n, 0) == 29
+    net.forward(d_in.ptr, d_out.ptr, n)
+    ctx.sync()
+    want, _ = orc.net_forward(orc.plan_build(1.0, res, 20), hw.blob, imgs, threads=orc.num_threads())
+    assert_close(d_out.download((n, 20), np.float32), np.asarray(want).reshape(n, 20), TOL_NET, "misaligned-segment net vs oracle")
+    net.destroy()
+
+
+@pytest.mark.parametrize("broken", ["pool_not_global", "d1_map", "p0_in_ch"])
+def test_net_inconsistent_tail_plan_is_not_fused(pkg, ctx, tmp_path, broken):
+    """mbn_tail_resident_bf16 takes only (rows, cols, 256, 512) and assumes the rest of layers 24-28: a plan that breaks one of those
+    assumptions is not listed as the resident tail. The launch list only: no forward runs on a broken geometry."""
+    hw, net = _make_net(pkg, ctx, tmp_path, 0.5, 160, 20, 16)
+    net.set_dtype(pkg.DT_BF16)
+    assert (24, 5) in net.launches(16)
+    net.destroy()
+    plan = pkg.Plan.from_buffer_copy(hw.plan)
+    if broken == "pool_not_global":
+        plan.layer[27].out_rows = plan.layer[27].out_cols = 2
+    elif broken == "d1_map":
+        plan.layer[25].in_rows = plan.layer[25].in_cols = 6
+    else:
+        plan.layer[24].in_ch = 512
+    net = pkg.Net(ctx, plan, hw.blob.copy(), 16)
+    net.set_dtype(pkg.DT_BF16)
+    assert 5 not in [c for _, c in net.launches(16)], net.launches(16)
     net.destroy()
 
 
