@@ -5,6 +5,7 @@
 // No CPU fallback exists: without a HIP device mbn_init returns MBN_ENODEVICE and nothing computes.
 #include "mbn_internal.h"
 
+#include <initializer_list>
 #include <new>
 
 mbn_tunables g_mbn_tune;
@@ -44,6 +45,18 @@ int span_check(mbn_context *ctx, const Span *sp, int n)
         const int _rc = span_check((ctx), _sp, (int)(sizeof(_sp) / sizeof(_sp[0])));   \
         if (_rc != MBN_OK) return _rc;                                                 \
     } while (0)
+
+// Pointers of a fused launch: MBN_EINVAL when one is null, else MBN_EUNSUPPORTED when one is not on 16 bytes (the fused kernels
+// load and store with 16-byte accesses), else MBN_OK
+int check_ptrs(std::initializer_list<const void *> ptrs)
+{
+    for (const void *p : ptrs)
+        if (!p) return MBN_EINVAL;
+    for (const void *p : ptrs)
+        if ((uintptr_t)p % 16) return MBN_EUNSUPPORTED;
+    return MBN_OK;
+}
+int check_ptrs(const mbn_block_params &b) { return check_ptrs({ b.wd, b.s2, b.b2, b.wp_bf16, b.s3, b.b3 }); }
 
 // element size of an activation tensor of the call: bf16 mode stores 2 bytes unless the io flag says fp32
 inline double esz_in(const mbn_call &c) { return c.dtype == MBN_DT_BF16 && !(c.io_flags & MBN_IO_IN_F32) ? 2.0 : 4.0; }
@@ -798,9 +811,12 @@ static int stem_fused_impl(mbn_context *ctx, void *out, const void *image, const
     if (!ctx || !out || !image) return MBN_EINVAL;
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     // decide before opening the profiling scope so an unsupported shape does not consume an event slot
-    if (!((c1 == 32 && c3 == 64) || (c1 == 16 && c3 == 32)) || res < 32 || (res % 32) != 0 || batch <= 0) return MBN_EUNSUPPORTED;
+    if (mbn_stem_envelope(batch, res, c1, c3) != MBN_OK) return MBN_EUNSUPPORTED;
     MBN_SPANS(ctx, { image, (in_u8 ? 1.0 : 4.0) * batch * res * res * 3, "stem image" },
               { out, (bf16 ? 2.0 : 4.0) * batch * (res / 2) * (res / 2) * c3, "stem output" });
+    // parameters the kernel cannot load (null or off 16 bytes) are unsupported; an output off 16 bytes or an image off its load width is invalid
+    if (check_ptrs({ w1, s1, b1, wd, s2, b2, wp, s3, b3 }) != MBN_OK) return MBN_EUNSUPPORTED;
+    if (((uintptr_t)out % 16) != 0 || ((uintptr_t)image % (in_u8 ? 2 : 8)) != 0) return MBN_EINVAL;
     Scope sc(ctx, s);
     return sc.finish(mbn_launch_f32_stem(ctx, s, (float *)out, (const float *)image, (const float *)w1, (const float *)s1,
                                          (const float *)b1, (const float *)wd, (const float *)s2, (const float *)b2,
@@ -836,10 +852,11 @@ int mbn_dwpw_fused(mbn_context *ctx, void *out, const void *in, const void *wd, 
 {
     if (!ctx) return MBN_EINVAL;
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    const mbn_block_shape sh = { batch, in_rows, in_cols, out_rows, out_cols, cin, cout, stride, pad_top, pad_left };
+    const mbn_block_params p = { wd, s2, b2, wp, s3, b3 };
     // decide before opening the profiling scope so an unsupported shape does not consume an event slot
-    const int rc = mbn_f32_dwpw_check((const float *)out, (const float *)in, (const float *)wd, (const float *)s2,
-                                      (const float *)b2, (const float *)wp, (const float *)s3, (const float *)b3, batch,
-                                      in_rows, in_cols, out_rows, out_cols, cin, cout, stride, pad_top, pad_left);
+    int rc = check_ptrs({ in, wd, s2, b2, wp, s3, b3, out });
+    if (rc == MBN_OK) rc = mbn_block_envelope(&sh, MBN_DT_F32);
     if (rc != MBN_OK) return rc;
     MBN_SPANS(ctx, { in, 4.0 * batch * in_rows * in_cols * cin, "dwpw input" },
               { out, 4.0 * batch * out_rows * out_cols * cout, "dwpw output" }, { wd, 36.0 * cin, "dwpw depthwise filter" },
@@ -852,38 +869,29 @@ int mbn_dwpw_fused(mbn_context *ctx, void *out, const void *in, const void *wd, 
     // batch 1, block 10-11: 40 us fused against 24 us as two launches — so below one 256-wide tile per CU the block runs
     // on 128-column tiles (twice the workgroups, half the MFMA work per step), i.e. on the unified kernel
     // opt-in: pointwise products on the bf16 matrix cores from exact operand splits (mbn_f32_dwpw2_x6.hip; pw_emul = 6 | 9)
-    if (g_mbn_tune.pw_emul != 0 && g_mbn_tune.dwpw_variant == 0 &&
-        mbn_launch_f32_dwpw2_x6(ctx, s, (float *)out, (const float *)in, (const float *)wd, (const float *)s2, (const float *)b2,
-                                (const float *)wp, (const float *)s3, (const float *)b3, batch, in_rows, in_cols, out_rows, out_cols,
-                                cin, cout, stride, pad_top, pad_left) == MBN_OK)
+    if (g_mbn_tune.pw_emul != 0 && g_mbn_tune.dwpw_variant == 0 && mbn_launch_f32_dwpw2_x6(ctx, s, sh, out, in, p) == MBN_OK)
         return sc.finish(MBN_OK);
     const int dv = g_mbn_tune.dwpw_variant;
     // round 6: the wave-private form (mbn_f32_dwpw3.hip: no barrier in the loop, filter slice resident in LDS) where it applies
     // (Cin 64 / 128 / 256). Lab A/B: dwpw_variant 11 = always where eligible, 12 = never, 300 + bits = its ablation build.
-    if ((dv == 11 || dv >= 300 || (dv == 0 && MBN_DWPW3_DEFAULT(stride, cin))) &&
-        mbn_f32_dwpw3_eligible(ctx, batch, in_rows, in_cols, out_rows, out_cols, cin, cout, stride, pad_top, pad_left))
-        return sc.finish(mbn_launch_f32_dwpw3(ctx, s, (float *)out, (const float *)in, (const float *)wd, (const float *)s2,
-                                              (const float *)b2, (const float *)wp, (const float *)s3, (const float *)b3, batch,
-                                              in_rows, in_cols, out_rows, out_cols, cin, cout, stride, pad_top, pad_left));
+    if ((dv == 11 || dv >= 300 || (dv == 0 && MBN_DWPW3_DEFAULT(stride, cin))) && mbn_f32_dwpw3_eligible(ctx, sh))
+        return sc.finish(mbn_launch_f32_dwpw3(ctx, s, sh, out, in, p));
     const long tiles256 = (((long)batch * out_rows * out_cols + 127) / 128) * (cout / 256);
     const bool small = tiles256 < ctx->num_cus;
     // stride-2 blocks (15 x-window loads per lane and step): with the loads spread under the MFMA groups the unified kernel also wins at
     // 256 columns (block 8-9: 0.1967 / 0.1964 -> 0.1931 / 0.1893 ms, profiles/r02/b_block_kernel_variants.txt); stride 1 at 256 columns
     // stays on the round-1 kernel (block 10-11: 0.291 vs 0.308 ms)
     if (dv != 1 && (dv >= 2 || (cout % 256) != 0 || small || stride == 2))
-        return sc.finish(mbn_launch_f32_dwpw2(ctx, s, (float *)out, (const float *)in, (const float *)wd, (const float *)s2,
-                                              (const float *)b2, (const float *)wp, (const float *)s3, (const float *)b3, batch,
-                                              in_rows, in_cols, out_rows, out_cols, cin, cout, stride, pad_top, pad_left));
-    return sc.finish(mbn_launch_f32_dwpw(ctx, s, (float *)out, (const float *)in, (const float *)wd, (const float *)s2,
-                                         (const float *)b2, (const float *)wp, (const float *)s3, (const float *)b3, batch,
-                                         in_rows, in_cols, out_rows, out_cols, cin, cout, stride, pad_top, pad_left));
+        return sc.finish(mbn_launch_f32_dwpw2(ctx, s, sh, out, in, p));
+    return sc.finish(mbn_launch_f32_dwpw(ctx, s, sh, out, in, p));
 }
 
 int mbn_blocks_resident_bf16(mbn_context *ctx, void *out, const void *in, const mbn_block_params *blocks, int nblocks, int batch,
                              int rows, int cols, int channels, void *stream)
 {
     if (!ctx || !out || !in || !blocks || batch <= 0) return MBN_EINVAL;
-    if (!mbn_bf16_res_eligible(rows, cols, channels, nblocks)) return MBN_EUNSUPPORTED;
+    const mbn_block_shape sh = { batch, rows, cols, rows, cols, channels, channels, 1, 1, 1 };
+    if (mbn_resident_envelope(&sh, nblocks) != MBN_OK) return MBN_EUNSUPPORTED;
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     const double act = 2.0 * batch * rows * cols * channels;
     MBN_SPANS(ctx, { in, act, "resident blocks input" }, { out, act, "resident blocks output" });
@@ -892,15 +900,20 @@ int mbn_blocks_resident_bf16(mbn_context *ctx, void *out, const void *in, const 
         MBN_SPANS(ctx, { blocks[i].wd, 36.0 * channels, "resident blocks depthwise filter" }, { blocks[i].wp_bf16, 2.0 * channels * channels, "resident blocks pointwise filter" },
                   { blocks[i].s2, 4.0 * channels, "resident blocks scale" }, { blocks[i].b3, 4.0 * channels, "resident blocks shift" });
     }
+    int rc = check_ptrs({ out, in });
+    for (int i = 0; i < nblocks && rc == MBN_OK; i++) rc = check_ptrs(blocks[i]);
+    if (rc != MBN_OK) return rc;
     Scope sc(ctx, s);
-    return sc.finish(mbn_launch_bf16_res_blocks(ctx, s, out, in, blocks, nblocks, batch, rows, cols, channels));
+    return sc.finish(mbn_launch_bf16_res_blocks(ctx, s, out, in, blocks, nblocks, batch, rows, cols));
 }
 
 int mbn_tail_resident_bf16(mbn_context *ctx, void *out, const void *in, const mbn_block_params *blocks, int batch, int rows, int cols, int c0, int c1,
                            void *stream)
 {
     if (!ctx || !out || !in || !blocks || batch <= 0) return MBN_EINVAL;
-    if (!mbn_bf16_tail_eligible(rows, cols, c0, c1)) return MBN_EUNSUPPORTED;
+    const mbn_block_shape b0 = { batch, rows, cols, rows / 2, cols / 2, c0, c1, 2, 0, 0 };
+    const mbn_block_shape b1 = { batch, rows / 2, cols / 2, rows / 2, cols / 2, c1, c1, 1, 1, 1 };
+    if (mbn_tail_envelope(&b0, &b1) != MBN_OK) return MBN_EUNSUPPORTED;
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     MBN_SPANS(ctx, { in, 2.0 * batch * rows * cols * c0, "resident tail input" }, { out, 2.0 * batch * c1, "resident tail output" });
     for (int i = 0; i < 2; i++) {
@@ -910,8 +923,11 @@ int mbn_tail_resident_bf16(mbn_context *ctx, void *out, const void *in, const mb
                   { blocks[i].s2, 4.0 * ci, "resident tail scale" }, { blocks[i].b2, 4.0 * ci, "resident tail shift" },
                   { blocks[i].s3, 4.0 * c1, "resident tail scale" }, { blocks[i].b3, 4.0 * c1, "resident tail shift" });
     }
+    int rc = ((uintptr_t)out % 2) ? MBN_EUNSUPPORTED : check_ptrs({ in });      // the pooled output is stored per bf16 element
+    for (int i = 0; i < 2 && rc == MBN_OK; i++) rc = check_ptrs(blocks[i]);
+    if (rc != MBN_OK) return rc;
     Scope sc(ctx, s);
-    return sc.finish(mbn_launch_bf16_tail(ctx, s, out, in, blocks, batch, rows, cols, c0, c1));
+    return sc.finish(mbn_launch_bf16_tail(ctx, s, out, in, blocks, batch, rows, cols));
 }
 
 int mbn_dwpw_fused_bf16(mbn_context *ctx, void *out, const void *in, const void *wd, const void *s2, const void *b2,
@@ -920,9 +936,10 @@ int mbn_dwpw_fused_bf16(mbn_context *ctx, void *out, const void *in, const void 
 {
     if (!ctx) return MBN_EINVAL;
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    const int rc = mbn_bf16_dwpw_check(out, in, (const float *)wd, (const float *)s2, (const float *)b2, wp_bf16,
-                                       (const float *)s3, (const float *)b3, batch, in_rows, in_cols, out_rows, out_cols, cin,
-                                       cout, stride, pad_top, pad_left);
+    const mbn_block_shape sh = { batch, in_rows, in_cols, out_rows, out_cols, cin, cout, stride, pad_top, pad_left };
+    const mbn_block_params p = { wd, s2, b2, wp_bf16, s3, b3 };
+    int rc = check_ptrs({ in, wd, s2, b2, wp_bf16, s3, b3, out });
+    if (rc == MBN_OK) rc = mbn_block_envelope(&sh, MBN_DT_BF16);
     if (rc != MBN_OK) return rc;
     MBN_SPANS(ctx, { in, 2.0 * batch * in_rows * in_cols * cin, "dwpw input" },
               { out, 2.0 * batch * out_rows * out_cols * cout, "dwpw output" }, { wd, 36.0 * cin, "dwpw depthwise filter" },
@@ -930,14 +947,10 @@ int mbn_dwpw_fused_bf16(mbn_context *ctx, void *out, const void *in, const void 
     Scope sc(ctx, s);
 #ifdef MBN_LAB
     if (g_mbn_tune.dwpw_variant == 1 && (cout % 128) == 0 && (cin % 64) == 0)      // the round-1 producer/consumer kernel (A/B hook; mbn_bf16_dwpw.hip's kernels are lab-only; whole 128-column tiles only)
-        return sc.finish(mbn_launch_bf16_dwpw(ctx, s, out, in, (const float *)wd, (const float *)s2, (const float *)b2, wp_bf16,
-                                              (const float *)s3, (const float *)b3, batch, in_rows, in_cols, out_rows, out_cols,
-                                              cin, cout, stride, pad_top, pad_left));
+        return sc.finish(mbn_launch_bf16_dwpw(ctx, s, sh, out, in, p));
 #endif
     // unified-wave kernel (mbn_bf16_dwpw2.hip)
-    return sc.finish(mbn_launch_bf16_dwpw2(ctx, s, out, in, (const float *)wd, (const float *)s2, (const float *)b2, wp_bf16,
-                                           (const float *)s3, (const float *)b3, batch, in_rows, in_cols, out_rows, out_cols,
-                                           cin, cout, stride, pad_top, pad_left));
+    return sc.finish(mbn_launch_bf16_dwpw2(ctx, s, sh, out, in, p));
 }
 
 int mbn_convert_f32_to_bf16(mbn_context *ctx, void *dst_bf16, const void *src_f32, size_t count, void *stream)

@@ -28,8 +28,8 @@ typedef mbn_f16v f16v;
 constexpr int BM = 128, BKF = 32;              // LDS rows are 128 bytes = 32 words = 64 bf16
 constexpr int NCW = 4, NPW = 8;                // consumer / producer waves
 constexpr int NT = 64 * (NCW + NPW);
-constexpr int CMAX = 1024;
-constexpr unsigned OOB = 0xF0000000u;
+constexpr int CMAX = MBN_CMAX;
+constexpr unsigned OOB = MBN_OOB;
 
 struct BArgs {
     __bf16 *out;
@@ -255,44 +255,14 @@ void launch(BArgs &a, hipStream_t s, int num_cus)
 
 }   // namespace
 
-// Envelope: as the fp32 kernel's, with Cin a multiple of 64 (one K chunk) and bf16 element sizes.
-int mbn_bf16_dwpw_check(const void *out, const void *in, const float *wd, const float *s2, const float *b2, const void *wp,
-                        const float *s3, const float *b3, int batch, int in_rows, int in_cols, int out_rows, int out_cols,
-                        int cin, int cout, int stride, int pad_top, int pad_left)
+// The round-1 producer/consumer kernel in bf16 (lab build A/B hook): whole 128-column tiles and Cin a multiple of 64 only.
+int mbn_launch_bf16_dwpw(mbn_context *ctx, hipStream_t stream, const mbn_block_shape &s, void *out, const void *in, const mbn_block_params &p)
 {
-    const void *ptrs[] = { in, wd, s2, b2, wp, s3, b3, out };
-    for (const void *p : ptrs)
-        if (!p) return MBN_EINVAL;
-    if (batch <= 0 || (stride != 1 && stride != 2) || (cin != 32 && (cin < 64 || (cin % 64) != 0)) || cin > CMAX || cout < 64 || cout > 1024 ||
-        (cout % 64) != 0 || (out_cols & 1) || out_rows <= 0 || out_cols <= 0 || in_rows <= 0 || in_cols <= 0 ||
-        pad_top < 0 || pad_left < 0)
-        return MBN_EUNSUPPORTED;
-    if (2.0 * batch * in_rows * in_cols * cin >= (double)OOB) return MBN_EUNSUPPORTED;
-    if ((long)batch * out_rows * out_cols > 0x7fffff00L) return MBN_EUNSUPPORTED;
-    if (2.0 * ((double)batch * out_rows * out_cols + 256.0) * cout >= 4294967296.0) return MBN_EUNSUPPORTED;   // + a row tile of head room: ragged rows must not wrap (32-bit offsets)
-    for (const void *p : ptrs)
-        if (((uintptr_t)p % 16) != 0) return MBN_EUNSUPPORTED;
-    return MBN_OK;
-}
-
-int mbn_launch_bf16_dwpw(mbn_context *ctx, hipStream_t stream, void *out, const void *in, const float *wd, const float *s2,
-                         const float *b2, const void *wp, const float *s3, const float *b3, int batch, int in_rows,
-                         int in_cols, int out_rows, int out_cols, int cin, int cout, int stride, int pad_top, int pad_left)
-{
-    const int rc = mbn_bf16_dwpw_check(out, in, wd, s2, b2, wp, s3, b3, batch, in_rows, in_cols, out_rows, out_cols, cin, cout,
-                                       stride, pad_top, pad_left);
-    if (rc != MBN_OK) return rc;
     BArgs a;
-    a.out = (__bf16 *)out; a.in = (const __bf16 *)in; a.wp = (const __bf16 *)wp;
-    a.wd = wd; a.s2 = s2; a.b2 = b2; a.s3 = s3; a.b3 = b3;
-    a.m = (long)batch * out_rows * out_cols;
-    a.h = in_rows; a.w = in_cols; a.ho = out_rows; a.wo = out_cols;
-    a.cin = cin; a.cout = cout; a.pad_top = pad_top; a.pad_left = pad_left;
-    mbn_udiv_magic((unsigned)out_cols, &a.wo_m, &a.wo_s);
-    mbn_udiv_magic((unsigned)out_rows, &a.ho_m, &a.ho_s);
-    a.in_bytes = (unsigned)(2.0 * batch * in_rows * in_cols * cin);
-    const bool wide = (cout % 256) == 0 && g_mbn_tune.pw_tile != 1;
-    if (stride == 1) {
+    mbn_block_args(a, s, out, in, p, 2.0);
+    a.wp = (const __bf16 *)p.wp_bf16;
+    const bool wide = (s.cout % 256) == 0 && g_mbn_tune.pw_tile != 1;
+    if (s.stride == 1) {
         if (wide) launch<1, 256>(a, stream, ctx->num_cus);
         else launch<1, 128>(a, stream, ctx->num_cus);
     } else {

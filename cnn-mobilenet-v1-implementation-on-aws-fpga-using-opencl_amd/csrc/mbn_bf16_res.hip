@@ -38,8 +38,8 @@ typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
 typedef mbn_f16v f16v;
 
-constexpr int RES_MAXBLK = 8;
-constexpr int XPIX = 144, YPIX = 128, YROWS = 104;   // pixel rows of the two LDS images (Y holds 104 — a map inside the envelope has at most 100 pixels; the GEMM's reads of
+constexpr int RES_MAXBLK = MBN_RES_MAXBLK;
+constexpr int XPIX = MBN_RES_XPIX, YPIX = 128, YROWS = MBN_RES_YROWS;   // pixel rows of the two LDS images (Y holds 104 — a map inside the envelope has at most 100 pixels; the GEMM's reads of
                                                      // pixel rows up to 127 run on into the constants behind it: inside the allocation, results unused)
 
 struct ResArgs {
@@ -292,27 +292,16 @@ __global__ __launch_bounds__(512) void res_blocks_bf16(ResArgs a)
 
 }   // namespace
 
-// 1 when a run of blocks can stay resident: C = 256, stride 1 with pad 1 (TF-SAME), a map of at most 128 pixels whose bordered form fits 144
-int mbn_bf16_res_eligible(int rows, int cols, int channels, int nblocks)
-{
-    return channels == 256 && rows >= 1 && cols >= 1 && rows * cols <= YROWS && (rows + 2) * (cols + 2) <= XPIX && nblocks >= 1 && nblocks <= RES_MAXBLK;
-}
-
+// The caller has checked the shape (mbn_resident_envelope) and the pointers.
 int mbn_launch_bf16_res_blocks(mbn_context *ctx, hipStream_t stream, void *out, const void *in, const mbn_block_params *blocks, int nblocks, int batch,
-                               int rows, int cols, int channels)
+                               int rows, int cols)
 {
-    if (!mbn_bf16_res_eligible(rows, cols, channels, nblocks)) return MBN_EUNSUPPORTED;
-    if (!out || !in || !blocks || batch <= 0) return MBN_EINVAL;
-    if (((uintptr_t)out % 16) || ((uintptr_t)in % 16)) return MBN_EUNSUPPORTED;
     ResArgs a;
     a.out = (__bf16 *)out; a.in = (const __bf16 *)in;
     a.batch = batch; a.h = rows; a.w = cols; a.nblk = nblocks;
     a.dbg = g_mbn_tune.exp0 >= 900 ? g_mbn_tune.exp0 - 900 : 0;
     for (int i = 0; i < nblocks; i++) {
         const mbn_block_params &b = blocks[i];
-        const void *ptrs[] = { b.wd, b.s2, b.b2, b.wp_bf16, b.s3, b.b3 };
-        for (const void *p : ptrs)
-            if (!p || ((uintptr_t)p % 16)) return p ? MBN_EUNSUPPORTED : MBN_EINVAL;
         a.wd[i] = (const float *)b.wd; a.s2[i] = (const float *)b.s2; a.b2[i] = (const float *)b.b2;
         a.wp[i] = (const __bf16 *)b.wp_bf16; a.s3[i] = (const float *)b.s3; a.b3[i] = (const float *)b.b3;
     }

@@ -71,6 +71,7 @@ __global__ __launch_bounds__(512) void tail_bf16(TailArgs a)
     constexpr int G0 = C0 / 8, G1 = C1 / 8;            // 8-channel groups per pixel
     constexpr int KS0 = C0 / 32, KS1 = C1 / 32;        // k steps of v_mfma_f32_16x16x32_bf16 (8, 16)
     constexpr int NIMG = 2, QMAX = NIMG * 25;          // images per pass; their pixels are rows img * P1 + p of Y and X1
+    static_assert(QMAX == NIMG * (MBN_TAIL_MAXSIDE / 2) * (MBN_TAIL_MAXSIDE / 2), "X1 holds the largest stride-2 output of the envelope");
     constexpr int YB = 64 * RSB1, X1B = QMAX * RSB1;   // Y: 64 rows (four 16-pixel column blocks are read; rows past the pass's pixels hold garbage that only reaches unused columns)
     __shared__ __attribute__((aligned(16))) char lds[YB + X1B + (11 * C0 + 11 * C1 + 4 * C1) * 4];      // 160,544 bytes
     char *const yb = lds, *const x1 = lds + YB;
@@ -294,21 +295,9 @@ __global__ __launch_bounds__(512) void tail_bf16(TailArgs a)
 
 }   // namespace
 
-int mbn_bf16_tail_eligible(int rows, int cols, int c0, int c1)
+// The caller has checked the shape (mbn_tail_envelope) and the pointers.
+int mbn_launch_bf16_tail(mbn_context *ctx, hipStream_t stream, void *out, const void *in, const mbn_block_params *blocks, int batch, int rows, int cols)
 {
-    return c0 == 256 && c1 == 512 && rows >= 2 && cols >= 2 && rows <= 10 && cols <= 10 && !(rows & 1) && !(cols & 1);
-}
-
-int mbn_launch_bf16_tail(mbn_context *ctx, hipStream_t stream, void *out, const void *in, const mbn_block_params *blocks, int batch, int rows, int cols, int c0, int c1)
-{
-    if (!mbn_bf16_tail_eligible(rows, cols, c0, c1)) return MBN_EUNSUPPORTED;
-    if (!out || !in || !blocks || batch <= 0) return MBN_EINVAL;
-    if (((uintptr_t)out % 2) || ((uintptr_t)in % 16) || (double)batch * rows * cols * c0 * 2 >= 4294967296.0) return MBN_EUNSUPPORTED;
-    for (int i = 0; i < 2; i++) {
-        const void *ptrs[] = { blocks[i].wd, blocks[i].s2, blocks[i].b2, blocks[i].wp_bf16, blocks[i].s3, blocks[i].b3 };
-        for (const void *p : ptrs)
-            if (!p || ((uintptr_t)p % 16)) return p ? MBN_EUNSUPPORTED : MBN_EINVAL;
-    }
     TailArgs a;
     a.out = (__bf16 *)out; a.in = (const __bf16 *)in; a.batch = batch; a.h0 = rows; a.w0 = cols;
     a.wd0 = (const float *)blocks[0].wd; a.s0 = (const float *)blocks[0].s2; a.b0 = (const float *)blocks[0].b2;

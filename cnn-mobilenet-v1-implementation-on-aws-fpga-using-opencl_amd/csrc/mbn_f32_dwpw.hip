@@ -35,8 +35,8 @@ typedef unsigned u4 __attribute__((ext_vector_type(4)));
 constexpr int BM = 128, BKF = 32;
 constexpr int NCW = 8, NPW = 8;                // consumer / producer waves: waves land on SIMD (wave % 4), so every SIMD
 constexpr int NT = 64 * (NCW + NPW);           // hosts two MFMA-issuing waves and two VALU/memory waves (128 VGPRs each)
-constexpr int CMAX = 1024;                     // largest Cin (depthwise constants resident in LDS: 44 KB)
-constexpr unsigned OOB = 0xF0000000u;          // byte offset beyond any supported tensor: the load returns zeros
+constexpr int CMAX = MBN_CMAX;                 // largest Cin (depthwise constants resident in LDS: 44 KB)
+constexpr unsigned OOB = MBN_OOB;              // byte offset beyond any supported tensor: the load returns zeros
 
 struct DwPwArgs {
     float *out;
@@ -261,47 +261,15 @@ void launch(DwPwArgs &a, hipStream_t s, int num_cus)
 
 }   // namespace
 
-// Shape/alignment envelope of the fused block kernel: MBN_OK, MBN_EUNSUPPORTED (run the two layers separately) or
-// MBN_EINVAL (null pointer).
-int mbn_f32_dwpw_check(const float *out, const float *in, const float *wd, const float *s2, const float *b2,
-                       const float *wp, const float *s3, const float *b3, int batch, int in_rows, int in_cols,
-                       int out_rows, int out_cols, int cin, int cout, int stride, int pad_top, int pad_left)
-{
-    const float *ptrs[] = { in, wd, s2, b2, wp, s3, b3, out };
-    for (const float *p : ptrs)
-        if (!p) return MBN_EINVAL;
-    if (batch <= 0 || (stride != 1 && stride != 2) || cin < 32 || (cin % 32) != 0 || cin > CMAX || cout < 128 || cout > 1024 ||
-        (cout % 128) != 0 || (out_cols & 1) || out_rows <= 0 || out_cols <= 0 || in_rows <= 0 || in_cols <= 0 ||
-        pad_top < 0 || pad_left < 0)
-        return MBN_EUNSUPPORTED;
-    if (4.0 * batch * in_rows * in_cols * cin >= (double)OOB) return MBN_EUNSUPPORTED;
-    if ((long)batch * out_rows * out_cols > 0x7fffff00L) return MBN_EUNSUPPORTED;                 // 32-bit pixel index
-    if (4.0 * ((double)batch * out_rows * out_cols + 256.0) * cout >= 4294967296.0) return MBN_EUNSUPPORTED;          // buffer stores; + a row tile of head room: ragged rows must not wrap (32-bit offsets)
-    for (const float *p : ptrs)
-        if (((uintptr_t)p % 16) != 0) return MBN_EUNSUPPORTED;
-    return MBN_OK;
-}
-
 // Fused depthwise 3x3 (stride 1 or 2, zero padding pad_top/pad_left, none needed explicitly on the high side) ->
 // pointwise 1x1, both with BN scale/shift + ReLU6.
-int mbn_launch_f32_dwpw(mbn_context *ctx, hipStream_t stream, float *out, const float *in, const float *wd,
-                        const float *s2, const float *b2, const float *wp, const float *s3, const float *b3, int batch,
-                        int in_rows, int in_cols, int out_rows, int out_cols, int cin, int cout, int stride, int pad_top,
-                        int pad_left)
+int mbn_launch_f32_dwpw(mbn_context *ctx, hipStream_t stream, const mbn_block_shape &s, void *out, const void *in, const mbn_block_params &p)
 {
-    const int rc = mbn_f32_dwpw_check(out, in, wd, s2, b2, wp, s3, b3, batch, in_rows, in_cols, out_rows, out_cols, cin,
-                                      cout, stride, pad_top, pad_left);
-    if (rc != MBN_OK) return rc;
     DwPwArgs a;
-    a.out = out; a.in = in; a.wd = wd; a.s2 = s2; a.b2 = b2; a.wp = wp; a.s3 = s3; a.b3 = b3;
-    a.m = (long)batch * out_rows * out_cols;
-    a.h = in_rows; a.w = in_cols; a.ho = out_rows; a.wo = out_cols;
-    a.cin = cin; a.cout = cout; a.pad_top = pad_top; a.pad_left = pad_left;
-    mbn_udiv_magic((unsigned)out_cols, &a.wo_m, &a.wo_s);
-    mbn_udiv_magic((unsigned)out_rows, &a.ho_m, &a.ho_s);
-    a.in_bytes = (unsigned)(4.0 * batch * in_rows * in_cols * cin);
-    const bool wide = (cout % 256) == 0 && g_mbn_tune.pw_tile != 1;      // pw_tile=1: force the 128-column tile (A/B hook)
-    if (stride == 1) {
+    mbn_block_args(a, s, out, in, p, 4.0);
+    a.wp = (const float *)p.wp_bf16;
+    const bool wide = (s.cout % 256) == 0 && g_mbn_tune.pw_tile != 1;    // pw_tile=1: force the 128-column tile (A/B hook)
+    if (s.stride == 1) {
         if (wide) launch<1, 256>(a, stream, ctx->num_cus);
         else launch<1, 128>(a, stream, ctx->num_cus);
     } else {

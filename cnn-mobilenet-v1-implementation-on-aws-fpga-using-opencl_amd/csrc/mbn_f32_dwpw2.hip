@@ -43,10 +43,10 @@ typedef mbn_f16v f16v;
 
 constexpr int BKF = 32;
 constexpr int BM8 = 128;                       // rows of the shipped 8-wave tile (2 waves per SIMD, 256 VGPRs each); the 16-wave lab form: 256
-constexpr int NOUT = 1024;                     // widest pointwise output whose scale/shift the LDS copy holds
-constexpr int CMAX = 1024;                     // largest Cin (depthwise constants resident in LDS: 44 KB)
+constexpr int NOUT = MBN_COUT_MAX;             // widest pointwise output whose scale/shift the LDS copy holds
+constexpr int CMAX = MBN_CMAX;                 // largest Cin (depthwise constants resident in LDS: 44 KB)
 constexpr int CMAX4 = 256, NOUT4 = 256;        // ... of the 4-wave form (two workgroups per CU: 66 KB of LDS each)
-constexpr unsigned OOB = 0xF0000000u;          // byte offset beyond any supported tensor: the load returns zeros
+constexpr unsigned OOB = MBN_OOB;              // byte offset beyond any supported tensor: the load returns zeros
 
 // In-kernel stamps (diagnostic: dwpw_variant = 100 + 64): workgroup 0 records s_memtime at five points of its first 96 steps,
 // per wave; read back with mbn_debug_dwpw2_stamps (tools/stamp_dwpw2.py). No output value depends on them.
@@ -708,39 +708,31 @@ void launch2(DwPw2Args &a, hipStream_t s, int num_cus, bool pre)
 
 }   // namespace
 
-// Unified-wave form of mbn_launch_f32_dwpw (same envelope: mbn_f32_dwpw_check has been passed by the caller).
-int mbn_launch_f32_dwpw2(mbn_context *ctx, hipStream_t stream, float *out, const float *in, const float *wd,
-                         const float *s2, const float *b2, const float *wp, const float *s3, const float *b3, int batch,
-                         int in_rows, int in_cols, int out_rows, int out_cols, int cin, int cout, int stride, int pad_top,
-                         int pad_left)
+// Unified-wave form of mbn_launch_f32_dwpw (same envelope).
+int mbn_launch_f32_dwpw2(mbn_context *ctx, hipStream_t stream, const mbn_block_shape &s, void *out, const void *in, const mbn_block_params &p)
 {
     DwPw2Args a;
-    a.out = out; a.in = in; a.wd = wd; a.s2 = s2; a.b2 = b2; a.wp = wp; a.s3 = s3; a.b3 = b3;
-    a.m = (long)batch * out_rows * out_cols;
-    a.h = in_rows; a.w = in_cols; a.ho = out_rows; a.wo = out_cols;
-    a.cin = cin; a.cout = cout; a.pad_top = pad_top; a.pad_left = pad_left;
-    mbn_udiv_magic((unsigned)out_cols, &a.wo_m, &a.wo_s);
-    mbn_udiv_magic((unsigned)out_rows, &a.ho_m, &a.ho_s);
+    mbn_block_args(a, s, out, in, p, 4.0);
+    a.wp = (const float *)p.wp_bf16;
     const int variant = g_mbn_tune.dwpw_variant;
-    a.in_bytes = (unsigned)(4.0 * batch * in_rows * in_cols * cin);
-    a.wp_bytes = (unsigned)(4.0 * cin * cout);
+    a.wp_bytes = (unsigned)(4.0 * s.cin * s.cout);
     a.dbg = variant >= 100 ? variant - 100 : 0;
-    a.inv_wo = 1.0f / (float)out_cols;
-    a.inv_ho = 1.0f / (float)out_rows;
+    a.inv_wo = 1.0f / (float)s.out_cols;
+    a.inv_ho = 1.0f / (float)s.out_rows;
     // the full-rate offsets need every input byte offset below the invalid-column constant, and (n h + iy0) in mul24 range
     //  ... PLUS a left-pad column: a left-pad tap of image 0 / row 0 has base = -pad_left * cs, and its sum with the invalid-column
     // constant must stay beyond num_records without wrapping; out_rows bounded so the row quotient stays in exact float range
-    const double cs_b = 4.0 * cin;
-    a.fast_off = (4.0 * batch * in_rows * in_cols * cin + (pad_left + 1) * cs_b <= (double)0x70000000u && (double)batch * in_rows < 8388000.0 &&
-                  in_cols < 32768 && out_cols < 32768 && out_rows < 32768 && pad_left <= 1) ? 1 : 0;
+    const double cs_b = 4.0 * s.cin;
+    a.fast_off = (4.0 * s.batch * s.in_rows * s.in_cols * s.cin + (s.pad_left + 1) * cs_b <= (double)0x70000000u && (double)s.batch * s.in_rows < 8388000.0 &&
+                  s.in_cols < 32768 && s.out_cols < 32768 && s.out_rows < 32768 && s.pad_left <= 1) ? 1 : 0;
 #ifdef MBN_LAB
     if (g_mbn_tune.exp0 == 51) a.fast_off = 0;                                     // lab A/B: the general offsets
 #endif
     a.stagger = g_mbn_tune.exp2;                                             // lab: start stagger of the workgroups in kcycles per phase
     const bool pre = variant != 3;                                       // 3: taps read from LDS inside the step (A/B hook)
     // 256-column tiles only when they alone fill the chip (see mbn_dwpw_fused); pw_tile=1: force the 128-column tile (A/B hook)
-    const bool wide = (cout % 256) == 0 && g_mbn_tune.pw_tile != 1 && ((a.m + BM8 - 1) / BM8) * (cout / 256) >= ctx->num_cus;
-    if (stride == 1) {
+    const bool wide = (s.cout % 256) == 0 && g_mbn_tune.pw_tile != 1 && ((a.m + BM8 - 1) / BM8) * (s.cout / 256) >= ctx->num_cus;
+    if (s.stride == 1) {
         if (wide) launch2<1, 256>(a, stream, ctx->num_cus, pre);
         else launch2<1, 128>(a, stream, ctx->num_cus, pre);
     } else {

@@ -33,7 +33,7 @@ typedef unsigned u2 __attribute__((ext_vector_type(2)));
 constexpr int BM = 128;
 constexpr int PW = 16;                         // words per plane row (32 bf16)
 constexpr int NW = 8, NT = 64 * NW;
-constexpr unsigned OOB = 0xF0000000u;
+constexpr unsigned OOB = MBN_OOB;
 
 struct XbArgs {
     float *out;
@@ -341,36 +341,28 @@ void launch_x6(XbArgs &a, hipStream_t s, int num_cus)
 }   // namespace
 
 // MBN_OK if launched, MBN_EUNSUPPORTED if pw_emul is off or the block is outside this kernel's envelope (the caller then takes the
-// fp32-MFMA kernels). The caller has passed mbn_f32_dwpw_check.
-int mbn_launch_f32_dwpw2_x6(mbn_context *ctx, hipStream_t stream, float *out, const float *in, const float *wd, const float *s2,
-                            const float *b2, const float *wp, const float *s3, const float *b3, int batch, int in_rows, int in_cols,
-                            int out_rows, int out_cols, int cin, int cout, int stride, int pad_top, int pad_left)
+// fp32-MFMA kernels).
+int mbn_launch_f32_dwpw2_x6(mbn_context *ctx, hipStream_t stream, const mbn_block_shape &s, void *out, const void *in, const mbn_block_params &p)
 {
     const int np = g_mbn_tune.pw_emul;
     if (np != 6 && np != 9) return MBN_EUNSUPPORTED;
-    if (cin > 512 || cout > 1024) return MBN_EUNSUPPORTED;
+    if (s.cin > 512) return MBN_EUNSUPPORTED;
     XbArgs a;
-    a.out = out; a.in = in; a.wd = wd; a.s2 = s2; a.b2 = b2; a.s3 = s3; a.b3 = b3;
-    a.m = (long)batch * out_rows * out_cols;
-    a.h = in_rows; a.w = in_cols; a.ho = out_rows; a.wo = out_cols;
-    a.cin = cin; a.cout = cout; a.pad_top = pad_top; a.pad_left = pad_left;
-    mbn_udiv_magic((unsigned)out_cols, &a.wo_m, &a.wo_s);
-    mbn_udiv_magic((unsigned)out_rows, &a.ho_m, &a.ho_s);
-    a.in_bytes = (unsigned)(4.0 * batch * in_rows * in_cols * cin);
+    mbn_block_args(a, s, out, in, p, 4.0);
     // 256-column tile: Cin <= 256 and Cout == 256 (LDS), and only when those tiles alone fill the chip (as dwpw2_f32)
-    const bool wide = cout == 256 && cin <= 256 && g_mbn_tune.pw_tile != 1 && ((a.m + BM - 1) / BM) >= ctx->num_cus;
+    const bool wide = s.cout == 256 && s.cin <= 256 && g_mbn_tune.pw_tile != 1 && ((a.m + BM - 1) / BM) >= ctx->num_cus;
     const int bn = wide ? 256 : 128;
     const unsigned *img = nullptr;
     unsigned img_bytes = 0;
-    const int rc = mbn_pw_emul_filter_image(ctx, stream, wp, cout, cin, bn, 1, &img, &img_bytes);
+    const int rc = mbn_pw_emul_filter_image(ctx, stream, (const float *)p.wp_bf16, s.cout, s.cin, bn, 1, &img, &img_bytes);
     if (rc != MBN_OK) return rc;
     a.wimg = img; a.wimg_bytes = img_bytes;
     const int cus = ctx->num_cus;
     if (np == 6) {
-        if (stride == 1) { if (wide) launch_x6<1, 256, 6, 256, 256, false>(a, stream, cus); else launch_x6<1, 128, 6, 512, 1024, true>(a, stream, cus); }
+        if (s.stride == 1) { if (wide) launch_x6<1, 256, 6, 256, 256, false>(a, stream, cus); else launch_x6<1, 128, 6, 512, 1024, true>(a, stream, cus); }
         else { if (wide) launch_x6<2, 256, 6, 256, 256, false>(a, stream, cus); else launch_x6<2, 128, 6, 512, 1024, true>(a, stream, cus); }
     } else {
-        if (stride == 1) { if (wide) launch_x6<1, 256, 9, 256, 256, false>(a, stream, cus); else launch_x6<1, 128, 9, 512, 1024, true>(a, stream, cus); }
+        if (s.stride == 1) { if (wide) launch_x6<1, 256, 9, 256, 256, false>(a, stream, cus); else launch_x6<1, 128, 9, 512, 1024, true>(a, stream, cus); }
         else { if (wide) launch_x6<2, 256, 9, 256, 256, false>(a, stream, cus); else launch_x6<2, 128, 9, 512, 1024, true>(a, stream, cus); }
     }
     return MBN_OK;

@@ -516,40 +516,39 @@ void launch3(const DwPw3Args &a, hipStream_t s, int grid)
 
 }   // namespace
 
-// 1 when the wave-private form takes this block (the caller has passed mbn_f32_dwpw_check): Cin 64 / 128 / 256 (filter slice resident in LDS,
+// 1 when the wave-private form takes this block (inside mbn_block_envelope): Cin 64 / 128 / 256 (filter slice resident in LDS,
 // substeps unrolled), the full-rate window offsets' range (every input byte offset + a left-pad column below the invalid-column constant; n h + iy0
 // in mul24 range; the band / image quotients' numerators below 2^21: exact float-reciprocal division), at least one workgroup per XCD and slice.
-int mbn_f32_dwpw3_eligible(const mbn_context *ctx, int batch, int in_rows, int in_cols, int out_rows, int out_cols, int cin, int cout, int stride,
-                           int pad_top, int pad_left)
+int mbn_f32_dwpw3_eligible(const mbn_context *ctx, const mbn_block_shape &s)
 {
-    if (cin != 64 && cin != 128 && cin != 256) return 0;
+    if (s.cin != 64 && s.cin != 128 && s.cin != 256) return 0;
 #ifndef MBN_LAB
-    if (!MBN_DWPW3_DEFAULT(stride, cin)) return 0;      // the shipped library holds only the instantiations its dispatch rule reaches (stride 1, Cin 128 / 256)
+    if (!MBN_DWPW3_DEFAULT(s.stride, s.cin)) return 0;      // the shipped library holds only the instantiations its dispatch rule reaches (stride 1, Cin 128 / 256)
 #endif
-    if ((cout % BN3) != 0 || cout > 1024 || (out_cols & 1) || (stride != 1 && stride != 2)) return 0;
-    if (4.0 * batch * in_rows * in_cols * cin + 4.0 * (pad_left + 1) * cin > (double)0x70000000u) return 0;
-    if ((double)batch * in_rows >= 8388000.0 || in_cols >= 32768 || out_cols >= 16384 || out_rows >= 32768 || pad_left > 1 || pad_top > 1) return 0;
-    if ((double)batch * out_rows >= 2000000.0 || (double)batch * out_rows * out_cols >= 2147483000.0) return 0;
+    if ((s.cout % BN3) != 0) return 0;
+    if (4.0 * s.batch * s.in_rows * s.in_cols * s.cin + 4.0 * (s.pad_left + 1) * s.cin > (double)0x70000000u) return 0;
+    if ((double)s.batch * s.in_rows >= 8388000.0 || s.in_cols >= 32768 || s.out_cols >= 16384 || s.out_rows >= 32768 || s.pad_left > 1 || s.pad_top > 1) return 0;
+    if ((double)s.batch * s.out_rows >= 2000000.0 || (double)s.batch * s.out_rows * s.out_cols >= 2147483000.0) return 0;
     // a pixel pair past the end of a ragged last tile stores at PO_INVALID + its channel offset: dropped only while the whole output (+ one
     // wave tile) stays below PO_INVALID; beyond it those stores would land inside the output (outputs of 2 .. 4 GiB run on dwpw2 / dwpw)
-    if (4.0 * ((double)batch * out_rows * out_cols + WT) * cout > (double)PO_INVALID) return 0;
-    const int nh = cout / BN3;
+    if (4.0 * ((double)s.batch * s.out_rows * s.out_cols + WT) * s.cout > (double)PO_INVALID) return 0;
+    const int nh = s.cout / BN3;
     if (ctx->num_cus / (8 * nh) < 1) return 0;
     return 1;
 }
 
-int mbn_launch_f32_dwpw3(mbn_context *ctx, hipStream_t stream, float *out, const float *in, const float *wd,
-                         const float *s2, const float *b2, const float *wp, const float *s3, const float *b3, int batch,
-                         int in_rows, int in_cols, int out_rows, int out_cols, int cin, int cout, int stride, int pad_top,
-                         int pad_left)
+// The caller has checked mbn_f32_dwpw3_eligible.
+int mbn_launch_f32_dwpw3(mbn_context *ctx, hipStream_t stream, const mbn_block_shape &s, void *out, const void *in, const mbn_block_params &p)
 {
-    if (!mbn_f32_dwpw3_eligible(ctx, batch, in_rows, in_cols, out_rows, out_cols, cin, cout, stride, pad_top, pad_left)) return MBN_EUNSUPPORTED;
     DwPw3Args a;
-    a.out = out; a.in = in; a.wd = wd; a.s2 = s2; a.b2 = b2; a.wp = wp; a.s3 = s3; a.b3 = b3;
-    a.m = (long)batch * out_rows * out_cols;
-    a.h = in_rows; a.w = in_cols; a.ho = out_rows; a.wo = out_cols;
-    a.cout = cout; a.pad_top = pad_top; a.pad_left = pad_left;
-    a.nh = cout / BN3;
+    a.out = (float *)out; a.in = (const float *)in; a.wd = (const float *)p.wd; a.s2 = (const float *)p.s2; a.b2 = (const float *)p.b2;
+    a.wp = (const float *)p.wp_bf16; a.s3 = (const float *)p.s3; a.b3 = (const float *)p.b3;
+    a.m = (long)s.batch * s.out_rows * s.out_cols;
+    a.h = s.in_rows; a.w = s.in_cols; a.ho = s.out_rows; a.wo = s.out_cols;
+    a.cout = s.cout; a.pad_top = s.pad_top; a.pad_left = s.pad_left;
+    const int cin = s.cin, out_rows = s.out_rows, out_cols = s.out_cols;
+    [[maybe_unused]] const int stride = s.stride;                        // the shipped library has stride-1 instantiations only
+    a.nh = s.cout / BN3;
     a.tiles = (int)((a.m + WT - 1) / WT);
     // bands of 4 output rows where the map's height allows (2, then 1 otherwise); lab: exp1 = 1 | 2 | 3 forces R = 1 | 2 | 4 where it divides
     a.rsh = (out_rows % 4) == 0 ? 2 : (out_rows % 2) == 0 ? 1 : 0;
@@ -562,7 +561,7 @@ int mbn_launch_f32_dwpw3(mbn_context *ctx, hipStream_t stream, float *out, const
     mbn_udiv_magic(a.bi, &a.bi_m, &a.bi_s);
     a.inv_pb = 1.0f / (float)a.pb;
     a.inv_bi = 1.0f / (float)a.bi;
-    a.in_bytes = (unsigned)(4.0 * batch * in_rows * in_cols * cin);
+    a.in_bytes = (unsigned)(4.0 * s.batch * s.in_rows * s.in_cols * s.cin);
     const int variant = g_mbn_tune.dwpw_variant;
     a.dbg = variant >= 300 ? variant - 300 : 0;
     // whole slice groups per XCD; no more workgroups per slice than the XCD has tiles (small problems: the remainder round hands out its tiles

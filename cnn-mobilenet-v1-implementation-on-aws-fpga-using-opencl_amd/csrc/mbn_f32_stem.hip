@@ -33,7 +33,7 @@ typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
 
-constexpr int TH = 8, TW = 16;                 // output tile (pixels of the 112x112 map)
+constexpr int TH = MBN_STEM_TH, TW = MBN_STEM_TW;   // output tile (pixels of the 112x112 map)
 constexpr int CR = TH + 2, CC = TW + 2;        // conv1 region incl. the depthwise halo: 10 x 18
 constexpr int PR = 2 * CR + 1;                     // input patch: 21 rows x 37 pixels
 constexpr int PROW = 112;                      // floats per patch row in LDS (37*3 = 111, padded)
@@ -46,7 +46,7 @@ struct StemArgs {
     const uint8_t *in8;         // raw uint8 HWC image instead of `in`: normalised at load, x/127.5 - 1 (MBN_IO_IN_U8)
     int batch, res, h;          // input side, conv1/dw/pw side (res/2)
     int tiles_y, tiles_x;
-    unsigned ntiles;        // < 2^31 (launcher checks): tile indices stay 32-bit, the per-tile index math is scalar and cheap
+    unsigned ntiles;        // < 2^31 (mbn_stem_envelope): tile indices stay 32-bit, the per-tile index math is scalar and cheap
 };
 
 // fp32 A/B tiles [rows][C1]: 16-byte slots XOR-swizzled so the ds_read_b128 of 16 consecutive rows hit 16 distinct bank
@@ -599,23 +599,16 @@ __global__ __launch_bounds__(256, WPE) void stem_fused_f32(StemArgs a)
 
 }   // namespace
 
-// Fused layers 1-3. Returns MBN_EUNSUPPORTED when the shapes are not the alpha = 1 stem (the caller then runs the three
-// layers separately).
+// Fused layers 1-3 (the caller has checked mbn_stem_envelope and the pointers).
 int mbn_launch_f32_stem(mbn_context *ctx, hipStream_t stream, float *out, const float *in, const float *w1,
                         const float *s1, const float *b1, const float *wd, const float *s2, const float *b2,
                         const float *wp, const float *s3, const float *b3, int batch, int res, int c1, int c3, int in_u8, int bf16)
 {
-    if (!((c1 == 32 && c3 == 64) || (c1 == 16 && c3 == 32)) || res < 32 || (res % 32) != 0 || batch <= 0) return MBN_EUNSUPPORTED;
-    const float *ptrs[] = { w1, s1, b1, wd, s2, b2, wp, s3, b3 };
-    for (const float *p : ptrs)
-        if (!p || ((uintptr_t)p % 16) != 0) return MBN_EUNSUPPORTED;
-    if (!out || !in || ((uintptr_t)out % 16) != 0 || ((uintptr_t)in % (in_u8 ? 2 : 8)) != 0) return MBN_EINVAL;
     StemArgs a;
     a.in8 = in_u8 ? (const uint8_t *)in : nullptr;
     a.out = out; a.in = in; a.w1 = w1; a.s1 = s1; a.b1 = b1; a.wd = wd; a.s2 = s2; a.b2 = b2; a.wp = wp; a.s3 = s3; a.b3 = b3;
     a.batch = batch; a.res = res; a.h = res / 2;
     a.tiles_y = a.h / TH; a.tiles_x = a.h / TW;
-    if ((long)batch * a.tiles_y * a.tiles_x >= 0x7fffffffL) return MBN_EUNSUPPORTED;
     a.ntiles = (unsigned)((long)batch * a.tiles_y * a.tiles_x);
     // alpha = 1 bf16: three workgroups per CU (taps from LDS) 0.448-0.455 ms against 0.472-0.480 with two (taps in registers), same run
     const int wpe_bf = g_mbn_tune.misc == 2 ? 2 : 3;                                  // A/B hook: misc = 2

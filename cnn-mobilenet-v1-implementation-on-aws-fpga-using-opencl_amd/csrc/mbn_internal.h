@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "mbn.h"
+#include "mbn_envelope.h"
 
 struct mbn_emul_img {
     void *p = nullptr;           // the image (device)
@@ -135,9 +136,6 @@ int mbn_launch_f32_pw_emul(const mbn_call &c, float *out, const float *in, const
 int mbn_pw_emul_filter_image(mbn_context *ctx, hipStream_t stream, const float *filt, int n, int k, int bn, int paired,
                              const unsigned **img, unsigned *bytes);
 void mbn_pw_emul_invalidate(mbn_context *ctx, const void *dst, size_t bytes);   // caller holds no lock
-int mbn_launch_f32_dwpw2_x6(mbn_context *ctx, hipStream_t stream, float *out, const float *in, const float *wd, const float *s2,
-                            const float *b2, const float *wp, const float *s3, const float *b3, int batch, int in_rows, int in_cols,
-                            int out_rows, int out_cols, int cin, int cout, int stride, int pad_top, int pad_left);
 int mbn_launch_bf16_pw_ring(const mbn_call &c, void *out, const void *in, const void *filt, long m, int cin, int op_size);      // lab build only
 int mbn_launch_bf16_pw_wide(const mbn_call &c, void *out, const void *in, const void *fpk, long m, int cin, int op_size);
 int mbn_launch_pack_filter_bf16(mbn_context *ctx, hipStream_t s, void *dst, const void *src, int n, int k);
@@ -160,46 +158,45 @@ static inline void mbn_udiv_magic(unsigned d, unsigned *m, unsigned *s)
     *s = l - 1;
 }
 
-int mbn_f32_dwpw_check(const float *out, const float *in, const float *wd, const float *s2, const float *b2,
-                       const float *wp, const float *s3, const float *b3, int batch, int in_rows, int in_cols,
-                       int out_rows, int out_cols, int cin, int cout, int stride, int pad_top, int pad_left);
-int mbn_launch_f32_dwpw(mbn_context *ctx, hipStream_t stream, float *out, const float *in, const float *wd,
-                        const float *s2, const float *b2, const float *wp, const float *s3, const float *b3, int batch,
-                        int in_rows, int in_cols, int out_rows, int out_cols, int cin, int cout, int stride, int pad_top,
-                        int pad_left);
-int mbn_launch_f32_dwpw2(mbn_context *ctx, hipStream_t stream, float *out, const float *in, const float *wd,
-                         const float *s2, const float *b2, const float *wp, const float *s3, const float *b3, int batch,
-                         int in_rows, int in_cols, int out_rows, int out_cols, int cin, int cout, int stride, int pad_top,
-                         int pad_left);
+// The fused depthwise -> pointwise block (mbn_dwpw_fused / mbn_dwpw_fused_bf16). Each launcher takes a shape inside
+// mbn_block_envelope (the caller has checked it and the pointers) and the block's parameters as the C-ABI's mbn_block_params;
+// an fp32 block carries its fp32 pointwise filter in wp_bf16. dwpw2_x6 is the opt-in form on the bf16 matrix cores (pw_emul = 6 | 9):
+// MBN_EUNSUPPORTED outside its own limits.
+int mbn_launch_f32_dwpw(mbn_context *ctx, hipStream_t stream, const mbn_block_shape &s, void *out, const void *in, const mbn_block_params &p);
+int mbn_launch_f32_dwpw2(mbn_context *ctx, hipStream_t stream, const mbn_block_shape &s, void *out, const void *in, const mbn_block_params &p);
+int mbn_launch_f32_dwpw2_x6(mbn_context *ctx, hipStream_t stream, const mbn_block_shape &s, void *out, const void *in, const mbn_block_params &p);
+int mbn_launch_bf16_dwpw(mbn_context *ctx, hipStream_t stream, const mbn_block_shape &s, void *out, const void *in, const mbn_block_params &p);
+int mbn_launch_bf16_dwpw2(mbn_context *ctx, hipStream_t stream, const mbn_block_shape &s, void *out, const void *in, const mbn_block_params &p);
+// The kernel-argument fields every block form shares (the structs differ, the names agree): the shape, the activations, the depthwise
+// parameters and the pointwise scale / shift. esize = bytes per activation element. The pointwise filter is the caller's (wp, or dwpw2_x6's image).
+template <typename Args>
+static inline void mbn_block_args(Args &a, const mbn_block_shape &s, void *out, const void *in, const mbn_block_params &p, double esize)
+{
+    a.out = (decltype(a.out))out; a.in = (decltype(a.in))in;
+    a.wd = (const float *)p.wd; a.s2 = (const float *)p.s2; a.b2 = (const float *)p.b2; a.s3 = (const float *)p.s3; a.b3 = (const float *)p.b3;
+    a.m = (long)s.batch * s.out_rows * s.out_cols;
+    a.h = s.in_rows; a.w = s.in_cols; a.ho = s.out_rows; a.wo = s.out_cols;
+    a.cin = s.cin; a.cout = s.cout; a.pad_top = s.pad_top; a.pad_left = s.pad_left;
+    mbn_udiv_magic((unsigned)s.out_cols, &a.wo_m, &a.wo_s);
+    mbn_udiv_magic((unsigned)s.out_rows, &a.ho_m, &a.ho_s);
+    a.in_bytes = (unsigned)(esize * s.batch * s.in_rows * s.in_cols * s.cin);
+}
 // short-K pointwise GEMM with the filter slice resident in LDS (mbn_f32_pw3.hip, round 6). Taken where it measured faster than pw_gemm (profiles/r06/l_*:
 // layers 5 / 7 / 9 / 11 at batch 256: -22 / -12 / -12 / -7 %, batch 64: -17 / -8 / -9 / -2 %, batch 16: equal; layer 13 (N = 512, four slices): +2 ... +40 %):
 // Cin <= 256, Cout <= 256, at least 128 pixels per CU. Same bits as pw_gemm, so the rule may depend on M.
 #define MBN_PW3_DEFAULT(m, cin, n, cus) ((cin) <= 256 && (n) <= 256 && (m) >= 128L * (cus))
 int mbn_launch_f32_pw3(const mbn_call &c, float *out, const float *in, const float *filt, long m, int cin, int op_size);
-// a run of equal bf16 blocks with the activations resident in LDS (mbn_bf16_res.hip, round 6)
-int mbn_bf16_res_eligible(int rows, int cols, int channels, int nblocks);
-int mbn_bf16_tail_eligible(int rows, int cols, int c0, int c1);                      // round 6: the last two blocks + the pool in one launch (mbn_bf16_tail.hip)
-int mbn_launch_bf16_tail(mbn_context *ctx, hipStream_t stream, void *out, const void *in, const mbn_block_params *blocks, int batch, int rows, int cols, int c0, int c1);
+// round 6: a run of equal bf16 blocks with the activations resident in LDS (mbn_bf16_res.hip), and the last two blocks + the pool in one launch
+// (mbn_bf16_tail.hip). Both take a shape inside their envelope (mbn_envelope.h) and pointers the caller has checked.
+int mbn_launch_bf16_tail(mbn_context *ctx, hipStream_t stream, void *out, const void *in, const mbn_block_params *blocks, int batch, int rows, int cols);
 int mbn_launch_bf16_res_blocks(mbn_context *ctx, hipStream_t stream, void *out, const void *in, const mbn_block_params *blocks, int nblocks, int batch,
-                               int rows, int cols, int channels);
+                               int rows, int cols);
 // wave-private form of the fp32 block (mbn_f32_dwpw3.hip, round 6): the default for stride-1 blocks with Cin >= 128 (blocks 6-7 and 10-11 of the
 // 1.0x network: -9...-12 % and -4...-6 % against dwpw2 in alternating runs, profiles/r06/f_*; equal on 8-9, 8 % slower on 4-5: those stay on dwpw2)
 #define MBN_DWPW3_DEFAULT(stride, cin) ((stride) == 1 && (cin) >= 128)
-int mbn_f32_dwpw3_eligible(const mbn_context *ctx, int batch, int in_rows, int in_cols, int out_rows, int out_cols, int cin, int cout, int stride,
-                           int pad_top, int pad_left);
-int mbn_launch_f32_dwpw3(mbn_context *ctx, hipStream_t stream, float *out, const float *in, const float *wd,
-                         const float *s2, const float *b2, const float *wp, const float *s3, const float *b3, int batch,
-                         int in_rows, int in_cols, int out_rows, int out_cols, int cin, int cout, int stride, int pad_top,
-                         int pad_left);
-int mbn_bf16_dwpw_check(const void *out, const void *in, const float *wd, const float *s2, const float *b2, const void *wp,
-                        const float *s3, const float *b3, int batch, int in_rows, int in_cols, int out_rows, int out_cols,
-                        int cin, int cout, int stride, int pad_top, int pad_left);
-int mbn_launch_bf16_dwpw(mbn_context *ctx, hipStream_t stream, void *out, const void *in, const float *wd, const float *s2,
-                         const float *b2, const void *wp, const float *s3, const float *b3, int batch, int in_rows,
-                         int in_cols, int out_rows, int out_cols, int cin, int cout, int stride, int pad_top, int pad_left);
-int mbn_launch_bf16_dwpw2(mbn_context *ctx, hipStream_t stream, void *out, const void *in, const float *wd, const float *s2,
-                          const float *b2, const void *wp, const float *s3, const float *b3, int batch, int in_rows,
-                          int in_cols, int out_rows, int out_cols, int cin, int cout, int stride, int pad_top, int pad_left);
+int mbn_f32_dwpw3_eligible(const mbn_context *ctx, const mbn_block_shape &s);      // inside mbn_block_envelope: the form's own limits
+int mbn_launch_f32_dwpw3(mbn_context *ctx, hipStream_t stream, const mbn_block_shape &s, void *out, const void *in, const mbn_block_params &p);
+// the fused stem: the shape is inside mbn_stem_envelope and the pointers are checked by the caller
 int mbn_launch_f32_stem(mbn_context *ctx, hipStream_t stream, float *out, const float *in, const float *w1,
                         const float *s1, const float *b1, const float *wd, const float *s2, const float *b2,
                         const float *wp, const float *s3, const float *b3, int batch, int res, int c1, int c3, int in_u8, int bf16);

@@ -1,0 +1,53 @@
+/* mbn_envelope.c — the shape envelopes of the fused kernels (mbn_envelope.h). The byte bounds are the kernels' 32-bit buffer
+ * offsets: tests/test_large_tensors_gpu.py runs each on both sides. */
+#include "mbn_envelope.h"
+#include "mbn.h"
+
+int mbn_block_envelope(const mbn_block_shape *s, int dtype)
+{
+    const int bf = dtype == MBN_DT_BF16;
+    if (!bf && dtype != MBN_DT_F32) return MBN_EUNSUPPORTED;
+    if (s->batch <= 0 || (s->stride != 1 && s->stride != 2) || s->cin > MBN_CMAX || s->cout > MBN_COUT_MAX || (s->out_cols & 1) ||
+        s->out_rows <= 0 || s->out_cols <= 0 || s->in_rows <= 0 || s->in_cols <= 0 || s->pad_top < 0 || s->pad_left < 0)
+        return MBN_EUNSUPPORTED;
+    /* fp32: whole 32-channel depthwise chunks, whole 128-column tiles; bf16: whole 64-channel K chunks (or one half chunk, padded),
+     * 64-column remainders on a padded tile */
+    if (bf ? (s->cin != 32 && (s->cin < 64 || (s->cin % 64) != 0)) || s->cout < 64 || (s->cout % 64) != 0
+           : s->cin < 32 || (s->cin % 32) != 0 || s->cout < 128 || (s->cout % 128) != 0)
+        return MBN_EUNSUPPORTED;
+    const double es = bf ? 2.0 : 4.0;
+    if (es * s->batch * s->in_rows * s->in_cols * s->cin >= (double)MBN_OOB) return MBN_EUNSUPPORTED;          /* input offsets below the zero-load offset */
+    if ((long)s->batch * s->out_rows * s->out_cols > 0x7fffff00L) return MBN_EUNSUPPORTED;                    /* 32-bit pixel index */
+    /* buffer stores; + a row tile of head room: ragged rows must not wrap (32-bit offsets) */
+    if (es * ((double)s->batch * s->out_rows * s->out_cols + 256.0) * s->cout >= 4294967296.0) return MBN_EUNSUPPORTED;
+    return MBN_OK;
+}
+
+int mbn_resident_envelope(const mbn_block_shape *s, int nblocks)
+{
+    if (s->cin != 256 || s->cout != 256 || s->stride != 1 || s->pad_top != 1 || s->pad_left != 1 || s->in_rows < 1 || s->in_cols < 1 ||
+        s->out_rows != s->in_rows || s->out_cols != s->in_cols || nblocks < 1 || nblocks > MBN_RES_MAXBLK)
+        return MBN_EUNSUPPORTED;
+    if (s->in_rows * s->in_cols > MBN_RES_YROWS || (s->in_rows + 2) * (s->in_cols + 2) > MBN_RES_XPIX) return MBN_EUNSUPPORTED;
+    return MBN_OK;
+}
+
+int mbn_tail_envelope(const mbn_block_shape *b0, const mbn_block_shape *b1)
+{
+    const int h = b0->in_rows, w = b0->in_cols;
+    if (b0->cin != 256 || b0->cout != 512 || h < 2 || w < 2 || h > MBN_TAIL_MAXSIDE || w > MBN_TAIL_MAXSIDE || (h & 1) || (w & 1))
+        return MBN_EUNSUPPORTED;
+    if (b0->stride != 2 || b0->pad_top != 0 || b0->pad_left != 0 || b0->out_rows != h / 2 || b0->out_cols != w / 2) return MBN_EUNSUPPORTED;
+    if (b1->batch != b0->batch || b1->cin != b0->cout || b1->cout != b0->cout || b1->stride != 1 || b1->pad_top != 1 || b1->pad_left != 1 ||
+        b1->in_rows != b0->out_rows || b1->in_cols != b0->out_cols || b1->out_rows != b1->in_rows || b1->out_cols != b1->in_cols)
+        return MBN_EUNSUPPORTED;
+    if (2.0 * b0->batch * h * w * b0->cin >= 4294967296.0) return MBN_EUNSUPPORTED;                              /* the input's 32-bit offsets */
+    return MBN_OK;
+}
+
+int mbn_stem_envelope(int batch, int res, int c1, int c3)
+{
+    if (!((c1 == 32 && c3 == 64) || (c1 == 16 && c3 == 32)) || res < 32 || (res % 32) != 0 || batch <= 0) return MBN_EUNSUPPORTED;
+    if ((long)batch * (res / 2 / MBN_STEM_TH) * (res / 2 / MBN_STEM_TW) >= 0x7fffffffL) return MBN_EUNSUPPORTED;   /* 32-bit tile index */
+    return MBN_OK;
+}

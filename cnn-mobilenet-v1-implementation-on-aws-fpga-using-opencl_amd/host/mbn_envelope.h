@@ -1,0 +1,41 @@
+/*
+ * mbn_envelope.h — the shapes each fused kernel accepts, written down once. Pure predicates: no pointers, no context, no HIP;
+ * each returns MBN_OK or MBN_EUNSUPPORTED. The C-ABI (csrc/mbn_abi.hip) asks them before it launches a fused kernel and the net
+ * runner (host/mbn_net.c) when it plans, so the launches it lists are the ones that run. Pointer rules, the batch and tile
+ * heuristics and the consistency between layers stay with the callers. Exported by libmbn.so and libmbn_host.so, not in mbn.h.
+ */
+#pragma once
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* fused depthwise -> pointwise block (mbn_f32_dwpw*.hip, mbn_bf16_dwpw*.hip) */
+#define MBN_CMAX 1024                /* largest Cin: the depthwise constants stay resident in LDS (44 KB) */
+#define MBN_COUT_MAX 1024            /* largest Cout: its scale / shift stay resident in LDS */
+#define MBN_OOB 0xF0000000u          /* byte offset beyond any supported tensor: a buffer load there returns zeros, so inputs stay below it */
+/* bf16 resident run (mbn_bf16_res.hip): pixel rows of its two LDS images, the map with its border and the map, and blocks per launch */
+#define MBN_RES_XPIX 144
+#define MBN_RES_YROWS 104
+#define MBN_RES_MAXBLK 8
+#define MBN_TAIL_MAXSIDE 10          /* bf16 resident tail (mbn_bf16_tail.hip): largest side of its input map */
+#define MBN_STEM_TH 8                /* fused stem (mbn_f32_stem.hip): output tile of a workgroup */
+#define MBN_STEM_TW 16
+
+/* one 3x3 depthwise (stride, zero padding pad_top / pad_left) -> 1x1 pointwise block on `batch` NHWC images */
+typedef struct mbn_block_shape {
+    int batch, in_rows, in_cols, out_rows, out_cols, cin, cout, stride, pad_top, pad_left;
+} mbn_block_shape;
+
+/* mbn_dwpw_fused (dtype MBN_DT_F32) and mbn_dwpw_fused_bf16 (MBN_DT_BF16) */
+int mbn_block_envelope(const mbn_block_shape *s, int dtype);
+/* one block of a run of `nblocks` (mbn_blocks_resident_bf16): stride 1, pad 1, the map and the channels unchanged */
+int mbn_resident_envelope(const mbn_block_shape *s, int nblocks);
+/* the two blocks of mbn_tail_resident_bf16: b0 stride 2 without top / left padding on an even map, b1 stride 1 with pad 1 on b0's output */
+int mbn_tail_envelope(const mbn_block_shape *b0, const mbn_block_shape *b1);
+/* mbn_stem_fused*: c1 -> c1 -> c3 channels on res x res images */
+int mbn_stem_envelope(int batch, int res, int c1, int c3);
+
+#ifdef __cplusplus
+}
+#endif

@@ -7,13 +7,14 @@
  * layer order is a loop over the plan; weights are uploaded once, activations ping-pong between two buffers
  * that stay in HBM, every call is asynchronous on the context's stream, and nothing crosses PCIe between layers.
  *
- * Plain C: this file uses nothing but the functions declared in mbn.h.
+ * Plain C: this file uses nothing but the functions declared in mbn.h and the kernels' shape envelopes (mbn_envelope.h).
  */
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include "mbn.h"
+#include "mbn_envelope.h"
 
 struct mbn_net {
     mbn_context *ctx;
@@ -205,15 +206,15 @@ static int layer_aligned(const mbn_net *net, int i)
     return seg_aligned(net, l->w_offset) && seg_aligned(net, l->scale_offset) && seg_aligned(net, l->shift_offset);
 }
 
-/* layers 1-3 can go through mbn_stem_fused: conv 3x3 s2 -> dw s1 -> pw with 32 -> 32 -> 64 channels, fp32, nothing kept */
-static int stem_fusable(const mbn_net *net, int last_layer)
+/* layers 1-3 can go through mbn_stem_fused: conv 3x3 s2 -> dw s1 -> pw inside the kernel's envelope, fp32 or bf16, nothing kept */
+static int stem_fusable(const mbn_net *net, int count, int last_layer)
 {
     const mbn_layer_desc *l = net->plan.layer;
     return net->fuse_stem && !net->keep && last_layer >= 3 && net->plan.n_layers >= 3 &&
            (net->dtype == MBN_DT_F32 || (net->dtype == MBN_DT_BF16 && net->bf16_filt[2])) &&
-           l[0].kind == MBN_L_CONV && l[1].kind == MBN_L_DW && l[2].kind == MBN_L_PW && l[0].in_ch == 3 &&
-           ((l[0].out_ch == 32 && l[2].out_ch == 64) || (l[0].out_ch == 16 && l[2].out_ch == 32)) && l[1].stride == 1 &&
-           (net->plan.res % 32) == 0 && layer_aligned(net, 0) && layer_aligned(net, 1) && layer_aligned(net, 2);
+           l[0].kind == MBN_L_CONV && l[1].kind == MBN_L_DW && l[2].kind == MBN_L_PW && l[0].in_ch == 3 && l[1].stride == 1 &&
+           mbn_stem_envelope(count, net->plan.res, l[0].out_ch, l[2].out_ch) == MBN_OK &&
+           layer_aligned(net, 0) && layer_aligned(net, 1) && layer_aligned(net, 2);
 }
 
 /* a captured graph bakes the launch list in: drop it when the fusion settings change */
@@ -241,13 +242,21 @@ static unsigned fuse_mask(const mbn_net *net)
     return net->dtype == MBN_DT_BF16 ? MBN_FUSE_BLOCKS_DEFAULT_BF16 : MBN_FUSE_BLOCKS_DEFAULT;
 }
 
-/* layers i+1 (depthwise) and i+2 (pointwise), 0-based index i, can go through mbn_dwpw_fused for `count` images: fp32,
- * nothing kept, enabled in the mask, and inside the kernel's envelope (mbn.h: mbn_dwpw_fused) */
+/* the block of depthwise layer i (0-based) and pointwise layer i+1 on `count` images */
+static mbn_block_shape block_shape(const mbn_net *net, int i, int count)
+{
+    const mbn_layer_desc *d = &net->plan.layer[i], *p = d + 1;
+    const mbn_block_shape s = { count, d->in_rows, d->in_cols, d->out_rows, d->out_cols, d->in_ch, p->out_ch, d->stride, d->pad_top, d->pad_left };
+    return s;
+}
+
+/* layers i+1 (depthwise) and i+2 (pointwise), 0-based index i, can go through mbn_dwpw_fused(_bf16) for `count` images: fp32
+ * or bf16, nothing kept, enabled in the mask, and inside the kernel's envelope (mbn_block_envelope) */
 static int block_fusable(const mbn_net *net, int i, int count, int last_layer)
 {
     const int bf = net->dtype == MBN_DT_BF16;
     if ((net->dtype != MBN_DT_F32 && !bf) || net->keep || i + 2 > last_layer || i + 1 >= net->plan.n_layers || i + 1 >= 32) return 0;
-    if (bf && (!net->bf16_filt[i + 1] || ((net->plan.layer[i].in_ch % 64) != 0 && net->plan.layer[i].in_ch != 32))) return 0;   /* 32: half a chunk, padded (round 5) */
+    if (bf && !net->bf16_filt[i + 1]) return 0;
     if (!((fuse_mask(net) >> (i + 1)) & 1u)) return 0;
     /* bf16 default: the block kernel recomputes the depthwise chunk once per 256-column tile and is bound by that VALU work,
      * so a block wider than one tile measures slower fused than as two launches; an explicit mask overrides */
@@ -264,40 +273,32 @@ static int block_fusable(const mbn_net *net, int i, int count, int last_layer)
         if (tiles * 2 < net->num_cus) return 0;
     }
     const mbn_layer_desc *d = &net->plan.layer[i], *p = &net->plan.layer[i + 1];
-    if (d->kind != MBN_L_DW || p->kind != MBN_L_PW || (d->stride != 1 && d->stride != 2)) return 0;
+    if (d->kind != MBN_L_DW || p->kind != MBN_L_PW || p->in_ch != d->out_ch) return 0;
     if (!layer_aligned(net, i) || !layer_aligned(net, i + 1)) return 0;
-    if (d->in_ch < 32 || (d->in_ch % 32) != 0 || d->in_ch > 1024 || p->out_ch > 1024) return 0;
-    if (bf ? (p->out_ch < 64 || (p->out_ch % 64) != 0) : (p->out_ch < 128 || (p->out_ch % 128) != 0)) return 0;   /* bf16 (round 5): 64-column remainders on a padded tile */
-    if ((d->out_cols & 1) || p->in_ch != d->out_ch) return 0;
-    /* the 32-bit offset bounds of mbn_f32_dwpw_check / mbn_bf16_dwpw_check: the output keeps a row tile of head room */
-    const double es = bf ? 2.0 : 4.0;
-    if (es * count * d->in_rows * d->in_cols * d->in_ch >= 4026531840.0) return 0;
-    if (es * ((double)count * d->out_rows * d->out_cols + 256.0) * p->out_ch >= 4294967296.0) return 0;
-    return 1;
+    const mbn_block_shape s = block_shape(net, i, count);
+    return mbn_block_envelope(&s, net->dtype) == MBN_OK;
 }
 
 /* Blocks starting at layer index i (0-based; depthwise, pointwise, depthwise, ...) that can run as ONE launch with the map resident in LDS
- * (mbn_blocks_resident_bf16, round 6): bf16, each of them fusable under the mask in force, stride 1 with pad 1, 256 channels in and out, equal small maps.
- * Returns the number of blocks (2 ... 8) or 0. The five 256 -> 256 blocks on the 10 x 10 map of the 0.5x160 network (layers 14-23). */
+ * (mbn_blocks_resident_bf16, round 6): bf16, each of them fusable under the mask in force and inside mbn_resident_envelope, all on the first
+ * block's map. Returns the number of blocks (2 or more) or 0. The five 256 -> 256 blocks on the 10 x 10 map of the 0.5x160 network (layers 14-23). */
 static int resident_run(const mbn_net *net, int i, int count, int last_layer)
 {
     if (net->dtype != MBN_DT_BF16 || !net->fuse_resident || net->keep) return 0;
+    const mbn_layer_desc *d0 = &net->plan.layer[i];
     int k = 0;
-    while (k < 8 && block_fusable(net, i + 2 * k, count, last_layer)) {
-        const mbn_layer_desc *d = &net->plan.layer[i + 2 * k], *p = &net->plan.layer[i + 2 * k + 1], *d0 = &net->plan.layer[i];
-        if (d->stride != 1 || d->pad_top != 1 || d->pad_left != 1 || d->in_ch != 256 || p->out_ch != 256 || d->out_rows != d->in_rows ||
-            d->out_cols != d->in_cols || d->in_rows != d0->in_rows || d->in_cols != d0->in_cols || d->in_rows * d->in_cols > 104 ||
-            (d->in_rows + 2) * (d->in_cols + 2) > 144)
-            break;
+    while (block_fusable(net, i + 2 * k, count, last_layer)) {
+        const mbn_layer_desc *d = &net->plan.layer[i + 2 * k];
+        const mbn_block_shape s = block_shape(net, i + 2 * k, count);
+        if (d->in_rows != d0->in_rows || d->in_cols != d0->in_cols || mbn_resident_envelope(&s, k + 1) != MBN_OK) break;
         k++;
     }
     return k >= 2 ? k : 0;
 }
 
 /* Layers i+1 ... i+5 (0-based index i) are the network's last two blocks and the global pool in the shape mbn_tail_resident_bf16 takes (round 6): bf16, nothing
- * kept, resident launches enabled, both blocks enabled in the mask in force; depthwise stride 2 without top / left padding on an even map of at most 10 x 10 x 256,
- * pointwise 256 -> 512, depthwise stride 1 with pad 1, pointwise 512 -> 512, pool over the whole map (layers 24-28 of the 0.5x160 network).
- * The kernel takes only (rows, cols, 256, 512) and assumes the rest, so every other shape of the five layers is checked here. */
+ * kept, resident launches enabled, both blocks enabled in the mask in force and inside mbn_tail_envelope, the pool over the whole map of the second block
+ * (layers 24-28 of the 0.5x160 network). The kernel takes only (rows, cols, c0, c1) and assumes the rest, so the layers' chain is checked here. */
 static int tail_run(const mbn_net *net, int i, int count, int last_layer)
 {
     if (net->dtype != MBN_DT_BF16 || !net->fuse_resident || net->keep || i + 5 > last_layer || i + 5 > net->plan.n_layers || i + 4 >= 32) return 0;
@@ -309,15 +310,10 @@ static int tail_run(const mbn_net *net, int i, int count, int last_layer)
     if (!((mask >> (i + 1)) & 1u) || !((mask >> (i + 3)) & 1u)) return 0;
     for (int k = i; k < i + 4; k++)
         if (!layer_aligned(net, k)) return 0;
-    if (d0->stride != 2 || d0->pad_top != 0 || d0->pad_left != 0 || d0->in_ch != 256 || p0->out_ch != 512 || (d0->in_rows & 1) || (d0->in_cols & 1) ||
-        d0->in_rows > 10 || d0->in_cols > 10 || d0->out_rows != d0->in_rows / 2 || d0->out_cols != d0->in_cols / 2 || p0->in_ch != d0->out_ch)
-        return 0;
-    if (d1->stride != 1 || d1->pad_top != 1 || d1->pad_left != 1 || d1->in_ch != 512 || p1->out_ch != 512 || d1->out_rows != d0->out_rows ||
-        d1->out_cols != d0->out_cols || d1->in_rows != d0->out_rows || d1->in_cols != d0->out_cols || p1->in_ch != d1->out_ch)
-        return 0;
-    if (po->in_rows != d0->out_rows || po->in_cols != d0->out_cols || po->out_ch != 512 || po->out_rows != 1 || po->out_cols != 1) return 0;
-    if (2.0 * count * d0->in_rows * d0->in_cols * d0->in_ch >= 4294967296.0) return 0;     /* the input's 32-bit offsets (mbn_launch_bf16_tail) */
-    return 1;
+    if (p0->in_ch != d0->out_ch || p1->in_ch != d1->out_ch) return 0;
+    if (po->in_rows != d1->out_rows || po->in_cols != d1->out_cols || po->out_ch != p1->out_ch || po->out_rows != 1 || po->out_cols != 1) return 0;
+    const mbn_block_shape b0 = block_shape(net, i, count), b1 = block_shape(net, i + 2, count);
+    return mbn_tail_envelope(&b0, &b1) == MBN_OK;
 }
 
 /* layers i+1 (pool) and i+2 (FC), 0-based index i, as one launch: fp32, 1...4 images, nothing kept, the last two layers of the call */
@@ -340,7 +336,7 @@ static int next_launch(const mbn_net *net, int i, int count, int last_layer, int
     int k = 0;
     *span = 2;
     if (fused_ok) {
-        if (i == 0 && !(excluded & (1u << K_STEM)) && stem_fusable(net, last_layer)) { *span = 3; return K_STEM; }
+        if (i == 0 && !(excluded & (1u << K_STEM)) && stem_fusable(net, count, last_layer)) { *span = 3; return K_STEM; }
         if (!(excluded & (1u << K_RESIDENT)) && (k = resident_run(net, i, count, last_layer))) { *span = 2 * k; return K_RESIDENT; }
         if (!(excluded & (1u << K_TAIL)) && tail_run(net, i, count, last_layer)) { *span = 5; return K_TAIL; }
         if (!(excluded & (1u << K_BLOCK)) && block_fusable(net, i, count, last_layer)) return K_BLOCK;
@@ -560,7 +556,7 @@ static int forward_range(mbn_net *net, const void *images, void *logits, int fir
             dst = (char *)net->act[which] + slot;
             flip = 1;
         }
-        mbn_block_params bp[8];
+        mbn_block_params bp[MBN_RES_MAXBLK];
         int rc;
         switch (kind) {
         case K_STEM:            /* layers 1-3 in one kernel; the 112x112x32 intermediates stay on chip */

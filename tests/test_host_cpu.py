@@ -545,6 +545,67 @@ def test_udiv_magic_formula():
                 assert ((v * m) >> 32) >> s == v // d, (v, d)
 
 
+class _BlockShape(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("batch", "in_rows", "in_cols", "out_rows", "out_cols", "cin", "cout", "stride", "pad_top", "pad_left")]
+
+
+def test_fused_kernel_envelopes(pkg):
+    """The shape envelopes of the fused kernels (host/mbn_envelope.c), which the C-ABI and the net runner both ask, at the boundaries the GPU
+    tests run (test_large_tensors_gpu.py, test_parity_gpu.py): the fused block in fp32 and bf16, the bf16 resident run and tail, the fused stem."""
+    host = pkg.host_lib()
+    ok, no = pkg.OK, pkg.EUNSUPPORTED
+
+    def block(dtype, n, h, oh, cin, cout, stride, pad):
+        return host.mbn_block_envelope(C.byref(_BlockShape(n, h, h, oh, oh, cin, cout, stride, pad, pad)), dtype)
+
+    for dt, k in ((pkg.DT_F32, 1), (pkg.DT_BF16, 2)):                   # bf16: the same byte limits at twice the images
+        assert block(dt, 1348 * k, 108, 54, 64, 128, 2, 0) == ok         # input 4 025 106 432 bytes < 0xF0000000
+        assert block(dt, 1349 * k, 108, 54, 64, 128, 2, 0) == no
+        assert block(dt, 359 * k, 54, 54, 128, 1024, 1, 1) == ok         # (m + 256) * 4096 = 4 288 921 600 < 2^32
+        assert block(dt, 360 * k, 54, 54, 128, 1024, 1, 1) == no
+    assert block(pkg.DT_BF16, 2697, 108, 54, 64, 128, 2, 0) == no        # 4 026 599 424 bytes
+    assert block(pkg.DT_BF16, 719, 54, 54, 128, 1024, 1, 1) == ok        # (m + 256) * 2048 = 4 294 369 280
+    f32 = lambda *a: host.mbn_block_envelope(C.byref(_BlockShape(*a)), pkg.DT_F32)
+    assert f32(1, 8, 8, 8, 8, 64, 128, 1, 1, 1) == ok
+    assert f32(1, 14, 14, 7, 7, 64, 128, 2, 0, 0) == no                 # odd output width
+    assert f32(1, 8, 8, 8, 8, 48, 128, 1, 1, 1) == no                   # Cin not a multiple of 32
+    assert f32(1, 8, 8, 8, 8, 2048, 512, 1, 1, 1) == no                 # Cin beyond the LDS-resident filter
+    assert f32(1, 8, 8, 8, 8, 64, 64, 1, 1, 1) == no                    # Cout < 128
+    assert f32(1, 8, 8, 8, 8, 64, 128, 3, 1, 1) == no                   # stride 3
+    assert f32(0, 8, 8, 8, 8, 64, 128, 1, 1, 1) == no
+    assert block(pkg.DT_BF16, 1, 8, 8, 32, 64, 1, 1) == ok               # bf16: half a K chunk (padded), 64-column tiles
+    assert block(pkg.DT_BF16, 1, 8, 8, 96, 128, 1, 1) == no              # ... but not one and a half
+    assert block(pkg.DT_U8, 1, 8, 8, 64, 128, 1, 1) == no
+
+    def resident(h, w, c, nblocks):
+        return host.mbn_resident_envelope(C.byref(_BlockShape(4, h, w, h, w, c, c, 1, 1, 1)), nblocks)
+
+    assert resident(10, 10, 256, 5) == ok and resident(10, 10, 256, 8) == ok
+    assert resident(12, 12, 256, 5) == no                                # 144 pixels: more than the LDS image holds
+    assert resident(10, 10, 256, 9) == no and resident(10, 10, 256, 0) == no and resident(10, 10, 128, 5) == no
+    assert host.mbn_resident_envelope(C.byref(_BlockShape(4, 10, 10, 5, 5, 256, 256, 2, 0, 0)), 2) == no
+
+    def tail(n, h, w, c0=256, c1=512):
+        b0 = _BlockShape(n, h, w, h // 2, w // 2, c0, c1, 2, 0, 0)
+        b1 = _BlockShape(n, h // 2, w // 2, h // 2, w // 2, c1, c1, 1, 1, 1)
+        return host.mbn_tail_envelope(C.byref(b0), C.byref(b1))
+
+    assert tail(83885, 10, 10) == ok                                     # input 4 294 912 000 bytes
+    assert tail(83887, 10, 10) == no                                     # 4 295 014 400 >= 2^32
+    assert tail(4, 12, 12) == no and tail(4, 9, 10) == no and tail(4, 10, 10, 128, 256) == no
+    b0, b1 = _BlockShape(4, 10, 10, 5, 5, 256, 512, 2, 0, 0), _BlockShape(4, 5, 5, 5, 5, 512, 512, 1, 0, 0)
+    assert host.mbn_tail_envelope(C.byref(b0), C.byref(b1)) == no       # the second block without its padding
+
+    for c1, c3 in ((32, 64), (16, 32)):
+        assert host.mbn_stem_envelope(1, 224, c1, c3) == ok and host.mbn_stem_envelope(7, 64, c1, c3) == ok
+        assert host.mbn_stem_envelope(1, 48, c1, c3) == no and host.mbn_stem_envelope(1, 240, c1, c3) == no   # res % 32 != 0
+    for c1, c3 in ((8, 16), (16, 64), (32, 32), (64, 128)):
+        assert host.mbn_stem_envelope(1, 64, c1, c3) == no
+    assert host.mbn_stem_envelope(0, 64, 32, 64) == no
+    assert host.mbn_stem_envelope(21913098, 224, 32, 64) == ok           # 98 tiles per image: 2 147 483 604 tiles
+    assert host.mbn_stem_envelope(21913099, 224, 32, 64) == no           # 2 147 483 702 >= 2^31 - 1: no 32-bit tile index
+
+
 def test_pw_gemm_counted_waits_match_the_isa():
     """`s_waitcnt vmcnt(NSTF); s_barrier` at the top of a pw_gemm tile is right only if the previous tile's fast epilogue is
     EXACTLY NSTF buffer stores, all behind the next tile's first LDS-DMA, in the instruction stream the compiler produced. The source
