@@ -27,7 +27,7 @@ HEADER = os.path.join(REPO_ROOT, "include", "mbn.h")
 
 RANK_FN = C.CFUNCTYPE(C.c_int, C.c_int, C.c_void_p, C.c_void_p)     # mbn_rank_fn(rank, arg, sync)
 OK, EINVAL, ENOMEM, EDEVICE, EIO, EFORMAT, ENOTFOUND, ESHAPE, EUNSUPPORTED, ENODEVICE = 0, -1, -2, -3, -4, -5, -6, -7, -8, -9
-DT_U8, DT_F32, DT_BF16 = 0, 1, 2
+DT_U8, DT_F32, DT_BF16, DT_I8 = 0, 1, 2, 3
 LAYOUT_NCHW_PLANAR, LAYOUT_NHWC = 0, 1
 IO_IN_F32, IO_OUT_F32, IO_IN_U8, IO_FILT_PACKED = 1, 2, 4, 8
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
@@ -71,6 +71,16 @@ class Weights(C.Structure):
     _fields_ = [("plan", Plan), ("blob", C.POINTER(C.c_float))]
 
 
+class I8Layer(C.Structure):
+    """mbn_i8_layer (include/mbn.h): byte offsets of one layer's segments in the i8 blob, and its activation scales"""
+    _fields_ = [("w_offset", C.c_int64), ("mult_offset", C.c_int64), ("bias_offset", C.c_int64), ("in_scale", C.c_float),
+                ("out_scale", C.c_float)]
+
+
+class I8Params(C.Structure):
+    _fields_ = [("n_layers", C.c_int32), ("blob_bytes", C.c_int64), ("layer", I8Layer * MAX_LAYERS)]
+
+
 def build(force: bool = False) -> None:
     """Compile the HIP kernels for gfx950 + the C host (make; hipcc cross-compiles without a GPU): the shipped library and
     the lab build beside it (`all lab`)."""
@@ -112,6 +122,7 @@ def _declare_host(lib):
     lib.mbn_run_ranks.argtypes = [C.c_int, RANK_FN, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     lib.mbn_rank_barrier.argtypes = [C.c_void_p]
     lib.mbn_rank_fail.argtypes = [C.c_void_p]
+    lib.mbn_quantize_i8.argtypes = [C.POINTER(Plan), C.c_void_p, C.c_void_p, C.POINTER(I8Params), C.c_void_p]
     return lib
 
 
@@ -180,6 +191,9 @@ def load():
         lib.mbn_pack_filter_bf16.argtypes = [vp, vp, ci, ci, vp]
         lib.mbn_convert_bf16_to_f32.argtypes = [vp, vp, vp, C.c_size_t, vp]
         lib.mbn_net_set_dtype.argtypes = [vp, ci]
+        lib.mbn_net_set_act_scales_i8.argtypes = [vp, C.POINTER(C.c_float), ci]
+        lib.mbn_net_get_act_scales_i8.argtypes = [vp, C.POINTER(C.c_float), ci]
+        lib.mbn_net_calibrate_i8.argtypes = [vp, vp, ci]
         lib.mbn_tune_set.argtypes = [C.c_char_p, ci]
         lib.mbn_tune_get.argtypes = [C.c_char_p, C.POINTER(ci)]
         lib.mbn_net_set_streams.argtypes = [vp, ci]
@@ -431,6 +445,21 @@ def plan_build(alpha=1.0, res=224, classes=1000, lib=None) -> Plan:
     return p
 
 
+def quantize_i8(plan, blob, scales=None, lib=None):
+    """mbn_quantize_i8: the I8 parameters of `plan` from its fp32 blob with activation scales `scales` (plan.n_layers values, None = the
+    defaults 6/255). Returns (I8Params, i8 blob as a uint8 array of params.blob_bytes)."""
+    lib = lib or host_lib()
+    blob = np.ascontiguousarray(blob, np.float32)
+    sc = None if scales is None else np.ascontiguousarray(scales, np.float32)
+    if sc is not None and sc.size != plan.n_layers:
+        raise ValueError("need %d scales" % plan.n_layers)
+    p = I8Params()
+    _chk(lib.mbn_quantize_i8(C.byref(plan), None, None if sc is None else sc.ctypes.data, C.byref(p), None))
+    out = np.zeros(max(1, p.blob_bytes), np.uint8)
+    _chk(lib.mbn_quantize_i8(C.byref(plan), blob.ctypes.data, None if sc is None else sc.ctypes.data, C.byref(p), out.ctypes.data))
+    return p, out[:p.blob_bytes]
+
+
 class HostWeights:
     """mbn_weights_from_h5 result; .blob is a numpy view of the packed fp32 parameters."""
 
@@ -518,8 +547,22 @@ class Net:
         _chk(self.ctx.lib.mbn_net_set_graph(self.h, int(enabled)), self.ctx.last_error())
 
     def set_dtype(self, dtype):
-        self.dtype = dtype
         _chk(self.ctx.lib.mbn_net_set_dtype(self.h, dtype), self.ctx.last_error())
+        self.dtype = dtype                # only once the net has switched (I8 can refuse a plan)
+
+    def set_act_scales_i8(self, scales):
+        """I8 activation scales s_l, one per layer (pool / FC entries ignored); re-quantizes in I8 mode."""
+        a = (C.c_float * self.plan.n_layers)(*[float(x) for x in scales])
+        _chk(self.ctx.lib.mbn_net_set_act_scales_i8(self.h, a, self.plan.n_layers), self.ctx.last_error())
+
+    def get_act_scales_i8(self) -> np.ndarray:
+        a = (C.c_float * self.plan.n_layers)()
+        _chk(self.ctx.lib.mbn_net_get_act_scales_i8(self.h, a, self.plan.n_layers))
+        return np.array(a[:], np.float32)
+
+    def calibrate_i8(self, images_ptr, batch):
+        """s_l = min(6, max_l) / 255 from an fp32 forward of `batch` device images; the dtype and other settings stay."""
+        _chk(self.ctx.lib.mbn_net_calibrate_i8(self.h, images_ptr, batch), self.ctx.last_error())
 
     def keep_activations(self, keep=True):
         _chk(self.ctx.lib.mbn_net_set_keep_activations(self.h, int(keep)))
@@ -530,9 +573,11 @@ class Net:
         p, n = C.c_void_p(), C.c_size_t()
         _chk(self.ctx.lib.mbn_net_layer_output(self.h, index, C.byref(p), C.byref(n)))
         l = self.plan.layer[index - 1]
-        bf = getattr(self, "dtype", DT_F32) == DT_BF16 and l.kind != L_FC
+        dt = getattr(self, "dtype", DT_F32)
+        bf = dt == DT_BF16 and l.kind != L_FC
         per = (l.out_rows, l.out_cols, l.out_ch)
-        raw = np.empty((batch if images is None else len(images),) + per, np.uint16 if bf else np.float32)
+        et = np.uint16 if bf else np.uint8 if (dt == DT_I8 and l.kind != L_FC) else np.float32
+        raw = np.empty((batch if images is None else len(images),) + per, et)
         if images is None:
             _chk(self.ctx.lib.mbn_download(self.ctx.h, raw.ctypes.data, p, raw.nbytes))
         else:

@@ -562,13 +562,16 @@ int resolve(mbn_context *ctx, const mbn_layer_ext *ext, mbn_call *c, int *dtype)
     if (!ext) return MBN_OK;
     if (ext->struct_size != sizeof(mbn_layer_ext)) return MBN_EINVAL;
     *dtype = ext->dtype;
-    if (ext->dtype != MBN_DT_U8 && ext->dtype != MBN_DT_F32 && ext->dtype != MBN_DT_BF16) return MBN_EINVAL;
+    if (ext->dtype != MBN_DT_U8 && ext->dtype != MBN_DT_F32 && ext->dtype != MBN_DT_BF16 && ext->dtype != MBN_DT_I8) return MBN_EINVAL;
     if (ext->dtype == MBN_DT_U8 && ext->layout != MBN_LAYOUT_NCHW_PLANAR) return MBN_EUNSUPPORTED;
     if (ext->dtype != MBN_DT_U8 && ext->layout != MBN_LAYOUT_NHWC) return MBN_EUNSUPPORTED;
     if (ext->io_flags & ~(MBN_IO_IN_F32 | MBN_IO_OUT_F32 | MBN_IO_IN_U8 | MBN_IO_FILT_PACKED)) return MBN_EINVAL;
     c->dtype = ext->dtype;
-    // IN_F32 / OUT_F32 only mean something in bf16 mode; IN_U8 (raw image into convolute) applies to fp32 and bf16
-    c->io_flags = ext->dtype == MBN_DT_BF16 ? ext->io_flags : (ext->io_flags & MBN_IO_IN_U8);
+    // IN_F32 / OUT_F32 only mean something in bf16 mode, and OUT_F32 in I8 mode (the FC's logits); IN_U8 (raw image into convolute)
+    // applies to fp32, bf16 and I8
+    c->io_flags = ext->dtype == MBN_DT_BF16 ? ext->io_flags
+                : ext->dtype == MBN_DT_I8   ? (ext->io_flags & (MBN_IO_IN_U8 | MBN_IO_OUT_F32))
+                                            : (ext->io_flags & MBN_IO_IN_U8);
     if (ext->batch < 0) return MBN_EINVAL;
     c->batch = ext->batch > 0 ? ext->batch : 1;
     if (ext->act < MBN_ACT_NONE || ext->act > MBN_ACT_RELU6) return MBN_EINVAL;
@@ -587,6 +590,17 @@ int resolve(mbn_context *ctx, const mbn_layer_ext *ext, mbn_call *c, int *dtype)
     c->scale = (const float *)ext->scale;
     c->shift = (const float *)ext->shift;
     if (ext->stream) c->stream = (hipStream_t)ext->stream;
+    return MBN_OK;
+}
+
+// I8 mode (mbn.h, "int8 inference mode"): the checks every I8 layer call shares. Activations and filters are read and written in 4- to
+// 16-byte pieces, so their pointers must be on 8 bytes; channel counts are multiples of 8; mult / bias are required.
+int i8_check(const mbn_call &c, std::initializer_list<const void *> ptrs, bool need_params)
+{
+    if (need_params && (!c.scale || !c.shift)) return MBN_EINVAL;
+    if (c.act == MBN_ACT_NONE && !(c.io_flags & MBN_IO_OUT_F32)) return MBN_EINVAL;
+    for (const void *p : ptrs)
+        if ((uintptr_t)p % 8) return MBN_EUNSUPPORTED;
     return MBN_OK;
 }
 
@@ -629,6 +643,19 @@ int mbn_convolute(mbn_context *ctx, void *output, const void *inp_r, const void 
                                                   filtersize, stride, op_size));
     }
     if (c.cin <= 0) c.cin = 3;
+    if (dtype == MBN_DT_I8) {
+        if (filtersize != 3 || stride > 2 || c.cin != 3 || (c.io_flags & MBN_IO_OUT_F32)) return MBN_EUNSUPPORTED;
+        if ((rc = i8_check(c, { output }, true)) != MBN_OK) return rc;
+        if (op_size % 8) return MBN_EUNSUPPORTED;
+        const double orow = (rows + stride - 1) / stride, ocol = (cols + stride - 1) / stride;
+        const double in_es = (c.io_flags & MBN_IO_IN_U8) ? 1.0 : 4.0;
+        MBN_SPANS(ctx, { inp_r, in_es * c.batch * rows * cols * c.cin, "convolute image" },
+                  { output, 1.0 * c.batch * orow * ocol * op_size, "convolute output" },
+                  { filter_k, 4.0 * 9 * c.cin * op_size, "convolute filter" },
+                  { c.scale, 4.0 * op_size, "convolute mult" }, { c.shift, 4.0 * op_size, "convolute bias" });
+        Scope sc(ctx, c.stream);
+        return sc.finish(mbn_launch_i8_conv(c, (uint8_t *)output, inp_r, (const float *)filter_k, rows, cols, stride, op_size));
+    }
     {
         const double orow = (rows + stride - 1) / stride, ocol = (cols + stride - 1) / stride;
         const double in_es = (c.io_flags & MBN_IO_IN_U8) ? 1.0 : esz_in(c);
@@ -653,6 +680,17 @@ int mbn_depthwise(mbn_context *ctx, void *output, const void *inp_image, const v
         return MBN_EINVAL;
     if (c.in_rows <= 0) c.in_rows = rows * stride;
     if (c.in_cols <= 0) c.in_cols = cols * stride;
+    if (dtype == MBN_DT_I8) {
+        if (filtersize != 3 || stride > 2 || (c.io_flags & MBN_IO_OUT_F32)) return MBN_EUNSUPPORTED;
+        if ((rc = i8_check(c, { output, inp_image, filter_k }, true)) != MBN_OK) return rc;
+        if (op_size % 8) return MBN_EUNSUPPORTED;
+        MBN_SPANS(ctx, { inp_image, 1.0 * c.batch * c.in_rows * c.in_cols * op_size, "depthwise input" },
+                  { output, 1.0 * c.batch * rows * cols * op_size, "depthwise output" }, { filter_k, 9.0 * op_size, "depthwise filter" },
+                  { c.scale, 4.0 * op_size, "depthwise mult" }, { c.shift, 4.0 * op_size, "depthwise bias" });
+        Scope sc(ctx, c.stream);
+        return sc.finish(mbn_launch_i8_depthwise(c, (uint8_t *)output, (const uint8_t *)inp_image, (const int8_t *)filter_k, rows, cols, stride,
+                                                 op_size));
+    }
     {
         const double es = dtype == MBN_DT_U8 ? 1.0 : esz_in(c), fes = 4.0 * filtersize * filtersize * op_size;
         MBN_SPANS(ctx, { inp_image, es * c.batch * c.in_rows * c.in_cols * op_size, "depthwise input" },
@@ -677,6 +715,19 @@ int mbn_pointwise(mbn_context *ctx, void *output, const void *inp_image, const v
     if (rc != MBN_OK) return rc;
     if (!output || !inp_image || !filter_k) return MBN_EINVAL;
     if (rows <= 0 || cols <= 0 || op_size <= 0 || filtersize <= 0) return MBN_EINVAL;
+    if (dtype == MBN_DT_I8) {
+        const bool f32 = (c.io_flags & MBN_IO_OUT_F32) != 0;
+        if ((rc = i8_check(c, { output, inp_image, filter_k }, true)) != MBN_OK) return rc;
+        if (f32 && c.act != MBN_ACT_NONE) return MBN_EINVAL;                  // fp32 logits are y itself: no activation applies
+        if (filtersize % 8 || filtersize > 65536 || (!f32 && op_size % 8)) return MBN_EUNSUPPORTED;   // |acc| < 2^31 needs K <= 65536
+        const double px = (double)c.batch * rows * cols;
+        MBN_SPANS(ctx, { inp_image, px * filtersize, "pointwise input" }, { output, (f32 ? 4.0 : 1.0) * px * op_size, "pointwise output" },
+                  { filter_k, 1.0 * op_size * filtersize, "pointwise filter" },
+                  { c.scale, 4.0 * op_size, "pointwise mult" }, { c.shift, 4.0 * op_size, "pointwise bias" });
+        Scope sc(ctx, c.stream);
+        return sc.finish(mbn_launch_i8_pointwise(c, output, (const uint8_t *)inp_image, (const int8_t *)filter_k, (long)c.batch * rows * cols,
+                                                 filtersize, op_size));
+    }
     {
         const double px = (double)c.batch * rows * cols, lit = dtype == MBN_DT_U8;
         MBN_SPANS(ctx, { inp_image, (lit ? 1.0 : esz_in(c)) * px * filtersize, "pointwise input" },
@@ -704,6 +755,13 @@ int mbn_pool(mbn_context *ctx, void *output, const void *inp_image, int rows, in
     if (!output || !inp_image) return MBN_EINVAL;
     if (rows <= 0 || cols <= 0 || op_size <= 0 || filtersize <= 0) return MBN_EINVAL;
     if (dtype == MBN_DT_U8 && (long)filtersize * filtersize > (long)rows * cols) return MBN_EINVAL;   // kernel.cl:126 would run past the plane
+    if (dtype == MBN_DT_I8) {
+        if (c.io_flags & MBN_IO_OUT_F32) return MBN_EUNSUPPORTED;
+        if (op_size % 8 || (uintptr_t)output % 8 || (uintptr_t)inp_image % 8) return MBN_EUNSUPPORTED;   // no mult / bias, any act
+        MBN_SPANS(ctx, { inp_image, 1.0 * c.batch * rows * cols * op_size, "pool input" }, { output, 1.0 * c.batch * op_size, "pool output" });
+        Scope sc(ctx, c.stream);
+        return sc.finish(mbn_launch_i8_pool(c, (uint8_t *)output, (const uint8_t *)inp_image, rows, cols, filtersize, op_size));
+    }
     {
         const double lit = dtype == MBN_DT_U8;
         MBN_SPANS(ctx, { inp_image, (lit ? 1.0 : esz_in(c)) * c.batch * rows * cols * op_size, "pool input" },

@@ -110,8 +110,8 @@ struct mbn_call {
     int g0, g1;
     uint32_t quirks;
     const float *scale, *shift;
-    int dtype;        // MBN_DT_F32 or MBN_DT_BF16 for the NHWC launchers (storage type of activations)
-    int io_flags;     // MBN_IO_IN_F32 / MBN_IO_OUT_F32 (bf16 mode only), MBN_IO_IN_U8 (convolute)
+    int dtype;        // MBN_DT_F32, MBN_DT_BF16 or MBN_DT_I8 for the NHWC launchers (storage type of activations)
+    int io_flags;     // MBN_IO_IN_F32 / MBN_IO_OUT_F32 (bf16 mode; OUT_F32 also I8), MBN_IO_IN_U8 (convolute)
 };
 
 // ---- launchers implemented in the kernel files; each returns MBN_* and launches on c.stream ----
@@ -144,6 +144,12 @@ int mbn_launch_bf16_pw_rf(const mbn_call &c, void *out, const void *in, const vo
 int mbn_launch_bf16_pw_stream(const mbn_call &c, void *out, const void *in, const void *filt, long m, int cin, int op_size, bool m16 = false);
 int mbn_launch_bf16_pw_big(const mbn_call &c, void *out, const void *in, const void *filt, long m, int cin, int op_size, long *rows_done);
 int mbn_launch_f32_pool(const mbn_call &c, void *out, const void *in, int rows, int cols, int fs, int channels);
+// int8 inference mode (MBN_DT_I8: uint8 NHWC activations, int8 filters, mult / bias in c.scale / c.shift) — mbn_i8.hip. The caller has checked
+// the shapes (channel counts multiples of 8, K <= 65536) and that every activation / filter pointer is on 8 bytes.
+int mbn_launch_i8_conv(const mbn_call &c, uint8_t *out, const void *in, const float *filt, int rows, int cols, int stride, int op_size);
+int mbn_launch_i8_depthwise(const mbn_call &c, uint8_t *out, const uint8_t *in, const int8_t *filt, int rows, int cols, int stride, int channels);
+int mbn_launch_i8_pointwise(const mbn_call &c, void *out, const uint8_t *in, const int8_t *filt, long m, int cin, int op_size);
+int mbn_launch_i8_pool(const mbn_call &c, uint8_t *out, const uint8_t *in, int rows, int cols, int fs, int channels);
 size_t mbn_pool_fc_ws_bytes(int channels, int classes);
 int mbn_launch_f32_pool_fc(mbn_context *ctx, hipStream_t s, float *out, const float *in, const float *w, const float *bias, void *ws,
                            int batch, int pix, int channels, int classes, int k, float *probs, int32_t *topk_idx, float *topk_prob);

@@ -9,6 +9,7 @@
  *
  * Plain C: this file uses nothing but the functions declared in mbn.h and the kernels' shape envelopes (mbn_envelope.h).
  */
+#include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -25,7 +26,7 @@ struct mbn_net {
     int own_blob;
     void *act[2];
     int keep;
-    int dtype;                 /* MBN_DT_F32 or MBN_DT_BF16 */
+    int dtype;                 /* MBN_DT_F32, MBN_DT_BF16 or MBN_DT_I8 */
     int fuse_stem;             /* mbn_net_set_fuse_stem (default 1) */
     int input_u8;              /* mbn_net_set_input_u8: images are raw uint8 HWC */
     unsigned fuse_blocks;      /* mbn_net_set_fuse_blocks: bit L = run the depthwise layer L and the pointwise layer L+1 as one launch */
@@ -51,6 +52,12 @@ struct mbn_net {
     int fuse_tail;             /* mbn_net_set_fuse_tail (default 0) */
     int fuse_resident;         /* mbn_net_set_fuse_resident (default 1): runs of equal bf16 blocks on a small map as one launch, the map resident in LDS */
     void *last_out[MBN_MAX_LAYERS];
+    /* I8 mode (mbn_quantize_i8): the quantized blob on the device, its layout, the activation scales it was made with, and the
+     * host copy of the fp32 blob it is quantized from (downloaded once) */
+    void *i8_blob;
+    mbn_i8_params i8;
+    float act_scale[MBN_MAX_LAYERS];
+    float *host_blob;
 };
 
 static const float *blob_at(const mbn_net *net, int64_t off)
@@ -78,6 +85,7 @@ static int net_alloc_common(mbn_context *ctx, const mbn_plan *plan, int max_batc
     if (rc == MBN_OK) rc = mbn_alloc(ctx, bytes, &net->act[1]);
     net->fuse_tail = 0;            /* measured slower than the two launches (mbn.h: mbn_net_set_fuse_tail): opt-in */
     net->fuse_resident = 1;
+    for (int i = 0; i < MBN_MAX_LAYERS; i++) net->act_scale[i] = 6.0f / 255.0f;
     if (rc == MBN_OK && plan->n_layers >= 2 && plan->layer[plan->n_layers - 2].kind == MBN_L_POOL &&
         plan->layer[plan->n_layers - 1].kind == MBN_L_FC) {
         const mbn_layer_desc *fc = &plan->layer[plan->n_layers - 1];
@@ -134,6 +142,8 @@ int mbn_net_destroy(mbn_net *net)
         if (net->keep_buf[i]) mbn_free(net->ctx, net->keep_buf[i]);
         if (net->bf16_filt[i]) mbn_free(net->ctx, net->bf16_filt[i]);
     }
+    if (net->i8_blob) mbn_free(net->ctx, net->i8_blob);
+    free(net->host_blob);
     if (net->act[0]) mbn_free(net->ctx, net->act[0]);
     if (net->act[1]) mbn_free(net->ctx, net->act[1]);
     if (net->own_blob && net->dev_blob) mbn_free(net->ctx, net->dev_blob);
@@ -149,9 +159,43 @@ int mbn_net_plan(const mbn_net *net, mbn_plan *plan)
     return MBN_OK;
 }
 
+/* I8: quantize the fp32 blob with the current activation scales and upload the result (mbn_quantize_i8). The fp32 blob is downloaded
+ * once; the device blob is allocated once (its size does not depend on the scales) and rewritten after the device has gone idle. */
+static int i8_quantize(mbn_net *net)
+{
+    mbn_i8_params p;
+    int rc = mbn_quantize_i8(&net->plan, NULL, net->act_scale, &p, NULL);
+    if (rc != MBN_OK) return rc;
+    const size_t fbytes = (size_t)net->plan.blob_floats * sizeof(float);
+    if (!net->host_blob) {
+        net->host_blob = (float *)malloc(fbytes ? fbytes : 1);
+        if (!net->host_blob) return MBN_ENOMEM;
+        rc = mbn_download(net->ctx, net->host_blob, net->dev_blob, fbytes);
+        if (rc != MBN_OK) { free(net->host_blob); net->host_blob = NULL; return rc; }
+    }
+    void *h = calloc(1, (size_t)p.blob_bytes ? (size_t)p.blob_bytes : 1);
+    if (!h) return MBN_ENOMEM;
+    rc = mbn_quantize_i8(&net->plan, net->host_blob, net->act_scale, &p, h);
+    if (rc == MBN_OK) rc = mbn_sync(net->ctx);          /* no forward still reads the previous blob */
+    if (rc == MBN_OK && !net->i8_blob) rc = mbn_alloc(net->ctx, (size_t)p.blob_bytes, &net->i8_blob);
+    if (rc == MBN_OK) rc = mbn_upload(net->ctx, net->i8_blob, h, (size_t)p.blob_bytes);
+    free(h);
+    if (rc == MBN_OK) net->i8 = p;
+    return rc;
+}
+
+static const void *i8_at(const mbn_net *net, int64_t off)
+{
+    return off < 0 ? NULL : (const char *)net->i8_blob + off;
+}
+
 int mbn_net_set_dtype(mbn_net *net, int dtype)
 {
-    if (!net || (dtype != MBN_DT_F32 && dtype != MBN_DT_BF16)) return MBN_EINVAL;
+    if (!net || (dtype != MBN_DT_F32 && dtype != MBN_DT_BF16 && dtype != MBN_DT_I8)) return MBN_EINVAL;
+    if (dtype == MBN_DT_I8) {
+        int rc = i8_quantize(net);
+        if (rc != MBN_OK) return rc;
+    }
     if (dtype == MBN_DT_BF16) {
         for (int i = 0; i < net->plan.n_layers; i++) {
             const mbn_layer_desc *l = &net->plan.layer[i];
@@ -177,6 +221,85 @@ int mbn_net_set_dtype(mbn_net *net, int dtype)
     }
     net->dtype = dtype;
     return MBN_OK;
+}
+
+int mbn_net_set_act_scales_i8(mbn_net *net, const float *scales, int n)
+{
+    if (!net || !scales || n != net->plan.n_layers) return MBN_EINVAL;
+    for (int i = 0; i < n; i++) {
+        const int k = net->plan.layer[i].kind;
+        if (k != MBN_L_POOL && k != MBN_L_FC && !(scales[i] > 0.f && isfinite(scales[i]))) return MBN_EINVAL;
+    }
+    float prev[MBN_MAX_LAYERS];
+    memcpy(prev, net->act_scale, sizeof(prev));
+    memcpy(net->act_scale, scales, (size_t)n * sizeof(float));
+    if (net->dtype != MBN_DT_I8) return MBN_OK;
+    const int rc = i8_quantize(net);
+    if (rc != MBN_OK) memcpy(net->act_scale, prev, sizeof(prev));
+    return rc;
+}
+
+int mbn_net_get_act_scales_i8(const mbn_net *net, float *scales, int n)
+{
+    if (!net || !scales || n != net->plan.n_layers) return MBN_EINVAL;
+    memcpy(scales, net->act_scale, (size_t)n * sizeof(float));
+    return MBN_OK;
+}
+
+static int forward_impl(mbn_net *net, const void *images, void *logits, int batch, int last_layer, float *layer_ms, int n_layer_ms);
+static void drop_graph(mbn_net *net);
+
+/* max of n fp32 values (activations after ReLU6: finite, >= 0) */
+static float max_f32(const float *x, size_t n)
+{
+    float m = 0.f;
+    for (size_t i = 0; i < n; i++)
+        if (x[i] > m) m = x[i];
+    return m;
+}
+
+int mbn_net_calibrate_i8(mbn_net *net, const void *images, int batch)
+{
+    if (!net || !images || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
+    const int n = net->plan.n_layers;
+    /* an fp32 forward with every layer's output kept, one stream, no graph; the settings are put back afterwards */
+    const int dtype = net->dtype, keep = net->keep, ns = net->nstreams, graph = net->use_graph;
+    drop_graph(net);                                    /* a captured forward may hold kept buffers this pass frees */
+    int rc = mbn_sync(net->ctx);
+    if (rc != MBN_OK) return rc;
+    const mbn_layer_desc *fc = &net->plan.layer[n - 1];
+    if (!net->logits_buf) rc = mbn_alloc(net->ctx, (size_t)net->max_batch * fc->out_ch * sizeof(float), &net->logits_buf);
+    net->dtype = MBN_DT_F32; net->keep = 1; net->nstreams = 1; net->use_graph = 0;
+    if (rc == MBN_OK) rc = forward_impl(net, images, net->logits_buf, batch, 0, NULL, 0);
+    if (rc == MBN_OK) rc = mbn_sync(net->ctx);
+    float scales[MBN_MAX_LAYERS];
+    float *h = NULL;
+    size_t cap = 0;
+    for (int i = 0; i < n && rc == MBN_OK; i++) {
+        const mbn_layer_desc *l = &net->plan.layer[i];
+        scales[i] = net->act_scale[i];
+        if (l->kind == MBN_L_POOL || l->kind == MBN_L_FC) continue;
+        const size_t cnt = (size_t)l->out_rows * l->out_cols * l->out_ch * (size_t)batch;
+        if (cnt > cap) {
+            free(h);
+            h = (float *)malloc(cnt * sizeof(float));
+            cap = h ? cnt : 0;
+            if (!h) { rc = MBN_ENOMEM; break; }
+        }
+        rc = mbn_download(net->ctx, h, net->last_out[i], cnt * sizeof(float));
+        if (rc != MBN_OK) break;
+        const float mx = max_f32(h, cnt);
+        scales[i] = (mx > 0.f ? (mx < 6.f ? mx : 6.f) : 6.f) / 255.0f;
+    }
+    free(h);
+    /* the kept fp32 buffers were made for this pass only */
+    if (!keep || dtype != MBN_DT_F32)
+        for (int i = 0; i < MBN_MAX_LAYERS; i++)
+            if (net->keep_buf[i]) { mbn_free(net->ctx, net->keep_buf[i]); net->keep_buf[i] = NULL; }
+    for (int i = 0; i < MBN_MAX_LAYERS; i++) net->last_out[i] = NULL;
+    net->dtype = dtype; net->keep = keep; net->nstreams = ns; net->use_graph = graph;
+    if (rc != MBN_OK) return rc;
+    return mbn_net_set_act_scales_i8(net, scales, n);
 }
 
 int mbn_net_set_streams(mbn_net *net, int n)
@@ -464,7 +587,7 @@ int mbn_net_layer_output(mbn_net *net, int index, void **dptr, size_t *floats_pe
 /* One layer through the C-ABI: the positional arguments are kernel.cl's (see mbn.h). */
 static int run_layer(mbn_net *net, const mbn_layer_desc *l, const void *src, void *dst, int batch, void *stream)
 {
-    const int bf = net->dtype == MBN_DT_BF16;
+    const int bf = net->dtype == MBN_DT_BF16, i8 = net->dtype == MBN_DT_I8;
     mbn_layer_ext ext;
     memset(&ext, 0, sizeof(ext));
     ext.struct_size = sizeof(ext);
@@ -479,6 +602,12 @@ static int run_layer(mbn_net *net, const mbn_layer_desc *l, const void *src, voi
     ext.stream = stream;
     const void *filt = blob_at(net, l->w_offset);
     if (bf && (l->kind == MBN_L_PW || l->kind == MBN_L_FC)) filt = net->bf16_filt[l->index - 1];
+    if (i8) {                              /* int8 filters, mult / bias from the i8 blob; conv1 keeps its fp32 filter */
+        const mbn_i8_layer *q = &net->i8.layer[l->index - 1];
+        if (l->kind != MBN_L_CONV) filt = i8_at(net, q->w_offset);
+        ext.scale = i8_at(net, q->mult_offset);
+        ext.shift = i8_at(net, q->bias_offset);
+    }
     switch (l->kind) {
     case MBN_L_CONV:                       /* MobileNet.c:268-292: rows/cols = input size, stride 2 */
         ext.cin = l->in_ch;
@@ -497,17 +626,18 @@ static int run_layer(mbn_net *net, const mbn_layer_desc *l, const void *src, voi
         return mbn_pool(net->ctx, dst, src, l->in_rows, l->in_cols, l->in_rows, l->out_ch, &ext);
     case MBN_L_FC:                         /* MobileNet.c:2682-2739: pointwise with rows = cols = 1; bias, no ReLU (B15) */
         ext.act = MBN_ACT_NONE;
-        if (bf) ext.io_flags = MBN_IO_OUT_F32;         /* logits stay fp32 */
+        if (bf || i8) ext.io_flags = MBN_IO_OUT_F32;   /* logits stay fp32 */
         return mbn_pointwise(net->ctx, dst, src, filt, 1, 1, l->in_ch, l->out_ch, &ext);
     default:
         return MBN_EINVAL;
     }
 }
 
-/* bytes per element of layer i's output in the current mode (FC logits are fp32 in both) */
+/* bytes per element of layer i's output in the current mode (FC logits are fp32 in every mode) */
 static size_t out_esize(const mbn_net *net, const mbn_layer_desc *l)
 {
-    return (net->dtype == MBN_DT_BF16 && l->kind != MBN_L_FC) ? 2 : 4;
+    if (l->kind == MBN_L_FC) return 4;
+    return net->dtype == MBN_DT_BF16 ? 2 : net->dtype == MBN_DT_I8 ? 1 : 4;
 }
 
 /* the parameters of the `nblocks` blocks from layer i on (depthwise i + 2k, pointwise i + 2k + 1) for the bf16 resident kernels */
@@ -612,8 +742,7 @@ static int forward_range(mbn_net *net, const void *images, void *logits, int fir
     return MBN_OK;
 }
 
-static int forward_impl(mbn_net *net, const void *images, void *logits, int batch, int last_layer, float *layer_ms,
-                        int n_layer_ms)
+static int forward_impl(mbn_net *net, const void *images, void *logits, int batch, int last_layer, float *layer_ms, int n_layer_ms)
 {
     if (!net || !images || !logits || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
     const int n = net->plan.n_layers;

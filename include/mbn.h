@@ -44,6 +44,9 @@
  *   F32 (ext->dtype == MBN_DT_F32): what BASELINE.json's metric measures — fp32,
  *     NHWC, conv -> per-channel scale/shift (folded BatchNorm) -> ReLU/ReLU6,
  *     TF-"SAME" padding. Tolerances: tests/test_parity_gpu.py.
+ *   I8 (ext->dtype == MBN_DT_I8): a quantized network — uint8 NHWC activations with one fp32 scale per layer,
+ *     int8 filters with one scale per output channel, exact int32 sums, one fp32 requantization per output.
+ *     Normative arithmetic: the "int8 inference mode" block below. Bit-exact vs tests/test_int8_gpu.py.
  */
 #ifndef MBN_H
 #define MBN_H
@@ -72,7 +75,8 @@ const char *mbn_strerror(int code);
 /* ------------------------------------------------------------- enumerations */
 enum { MBN_DT_U8 = 0,   /* LITERAL: uint8 act / int32 filter / int32 acc (kernel.cl) */
        MBN_DT_F32 = 1,  /* fp32 act / fp32 filter / fp32 acc                         */
-       MBN_DT_BF16 = 2  /* bf16 act / bf16 pointwise filter / fp32 acc (config 5)    */ };
+       MBN_DT_BF16 = 2, /* bf16 act / bf16 pointwise filter / fp32 acc (config 5)    */
+       MBN_DT_I8 = 3    /* uint8 act (scaled) / int8 per-channel filter / int32 acc  */ };
 
 enum { MBN_LAYOUT_NCHW_PLANAR = 0,  /* plane c at offset c*rows*cols (kernel.cl:73,107) */
        MBN_LAYOUT_NHWC = 1 };
@@ -438,6 +442,43 @@ typedef struct mbn_plan {
 /* MobileNet.c:13-26 + SURVEY §2.1 table, parameterised: channels = max(8, int(c*alpha)), sizes from res. */
 int  mbn_plan_build(float alpha, int res, int classes, mbn_plan *plan);
 
+/* int8 inference mode (MBN_DT_I8). The arithmetic, normative (tests/test_int8_*.py reproduce it bit for bit):
+ *   activations  uint8 NHWC, zero point 0, real value = q * s_l with one fp32 scale per layer. Every conv / depthwise / pointwise layer
+ *                ends in ReLU6, so s_l = min(6, clip_l) / 255 (default clip_l = 6) and clamping q to [0, 255] IS the ReLU6. The pool
+ *                output keeps its input's scale.
+ *   weights      int8, symmetric, one scale per output channel (pointwise / FC: per row [Cout][Cin]; depthwise: per channel over its 9
+ *                taps). absmax = max |w| of the channel; inv = 127.0f / absmax (float); q = clamp(rintf(w * inv), -127, 127) (float
+ *                product, round half to even); s_w = absmax / 127 (double). An all-zero channel: q = 0, s_w = 1.
+ *                conv1 keeps its fp32 filter and fp32 arithmetic; only its output is quantized.
+ *   requantize   per output channel c, in double, rounded once to float:
+ *                  mult[c] = (float)(s_w[c] * s_in * bn_scale[c] / s_out),  bias[c] = (float)(bn_shift[c] / s_out)
+ *                (conv1: s_w * s_in = 1; FC: bn_scale = 1, s_out = 1). The kernel forms acc = sum x * w exactly in int32 and
+ *                  y = fadd_rn(fmul_rn((float)acc, mult[c]), bias[c])        (no FMA: numpy float32 reproduces it)
+ *                uint8 outputs store clamp(rintf(y), 0, 255); the FC (MBN_IO_OUT_F32) stores y, the fp32 logit. conv1's acc is its fp32
+ *                convolution sum instead. |acc| <= 255 * 127 * K < 2^31 needs K <= 65536: a larger K answers MBN_EUNSUPPORTED.
+ *   pool         global average: q = clamp(rintf(fmul_rn((float)sum, 1.0f / (rows * cols))), 0, 255), sum exact.
+ * C-ABI in this mode (ext->dtype = MBN_DT_I8, layout NHWC only; NCHW answers MBN_EUNSUPPORTED): ext->scale / ext->shift are mult / bias
+ * above, both required except for the pool; filters are int8 (1 byte) in the layouts of the fp32 mode, conv1's stays fp32 [3][3][cin][C];
+ * activations are 1 byte; mbn_convolute reads the fp32 image or, with MBN_IO_IN_U8, the raw uint8 image (x/127.5 - 1 at load).
+ * mbn_pointwise with MBN_IO_OUT_F32 writes fp32 (the FC) and requires MBN_ACT_NONE; MBN_ACT_NONE is accepted only there, every uint8
+ * output clamps to [0, 255].
+ * conv1: 3x3, 3 input channels. Depthwise: 3x3, stride 1 or 2. Channel counts (conv1 / depthwise / pointwise outputs, pointwise / pool inputs) must be multiples
+ * of 8, otherwise MBN_EUNSUPPORTED. The fused entry points (stem, blocks, resident, pool + FC) have no I8 form. */
+typedef struct mbn_i8_layer {
+    int64_t w_offset;        /* byte offset of the int8 filter in the i8 blob (element order of the fp32 blob's filter); -1: conv1 keeps fp32, pool */
+    int64_t mult_offset;     /* byte offset of out_ch fp32 multipliers; -1 for pool */
+    int64_t bias_offset;     /* byte offset of out_ch fp32 offsets;     -1 for pool */
+    float   in_scale, out_scale;   /* activation scales; FC out_scale = 0 (fp32 logits); conv1 in_scale = 1 (fp32 image) */
+} mbn_i8_layer;
+typedef struct mbn_i8_params { int32_t n_layers; int64_t blob_bytes; mbn_i8_layer layer[MBN_MAX_LAYERS]; } mbn_i8_params;
+
+/* Quantize a plan's fp32 blob (BN folded) for the I8 mode. act_scales: plan->n_layers entries s_l (NULL = the defaults 6/255; pool and
+ * FC entries are ignored; each used one must be finite and > 0). Fills *p; i8_blob NULL = fill *p only, else p->blob_bytes bytes are
+ * written there. Layout: per layer, in order, [int8 filter][mult (out_ch fp32)][bias (out_ch fp32)], each segment 256-byte aligned;
+ * conv1 has no filter segment (its fp32 filter is read from the fp32 blob at plan->layer[0].w_offset), the pool has none at all.
+ * MBN_EUNSUPPORTED for a plan whose channel counts the I8 kernels do not cover (see above). Host code only: also in libmbn_host.so. */
+int  mbn_quantize_i8(const mbn_plan *plan, const float *blob, const float *act_scales, mbn_i8_params *p, void *i8_blob);
+
 /* Host-side packed weights: one contiguous fp32 blob (this is what is broadcast over RCCL). */
 typedef struct mbn_weights {
     mbn_plan plan;
@@ -464,8 +505,19 @@ int  mbn_net_create_from_device_blob(mbn_context *ctx, const mbn_plan *plan, con
                                      int max_batch, mbn_net **net);
 int  mbn_net_destroy(mbn_net *net);
 /* MBN_DT_F32 (default) or MBN_DT_BF16: in bf16 mode the net keeps a bf16 copy of the pointwise/FC filters (made on
- * the device from the fp32 blob), activations are bf16, images stay fp32 [batch][res][res][3], logits stay fp32. */
+ * the device from the fp32 blob), activations are bf16, images stay fp32 [batch][res][res][3], logits stay fp32.
+ * MBN_DT_I8: the net quantizes the fp32 blob with its current activation scales (mbn_quantize_i8; the device blob is downloaded
+ * once for that) and uploads the i8 blob; activations are uint8 (layer_output: 1 byte per element), logits stay fp32. Every layer
+ * runs as its own launch (no stem, block, resident or pool + FC fusion: mbn_net_launches lists 29 single layers). */
 int  mbn_net_set_dtype(mbn_net *net, int dtype);
+/* I8 activation scales s_l (n = plan.n_layers entries; pool / FC entries ignored). Setting them re-quantizes when the net is in I8
+ * mode. Default 6/255 everywhere. */
+int  mbn_net_set_act_scales_i8(mbn_net *net, const float *scales, int n);
+int  mbn_net_get_act_scales_i8(const mbn_net *net, float *scales, int n);
+/* Calibration: an fp32 forward of `batch` device images (the net's input format) records every conv / depthwise / pointwise layer's
+ * output maximum max_l and sets s_l = min(6, max_l) / 255 (6/255 where max_l = 0); re-quantizes in I8 mode. The dtype and every
+ * other setting are left as they were. Synchronous. */
+int  mbn_net_calibrate_i8(mbn_net *net, const void *images, int batch);
 /* Pipeline every forward over `n` contiguous sub-batches on n streams (1 <= n <= 8; default 1). The HBM-bound
  * depthwise kernels of one sub-batch then overlap the MFMA-bound pointwise kernels of another and fill their tails
  * (fp32 1.0x224 batch 256 with the round-2 kernels: +4.7 % at n = 2, -5 % at n = 3, -3 % at n = 4 — smaller sub-batches
@@ -543,7 +595,7 @@ int  mbn_net_plan(const mbn_net *net, mbn_plan *plan);
 /* Device pointer of layer `index`'s output from the most recent forward (valid until the next forward that
  * overwrites the ping-pong buffer; with keep_activations every layer has its own buffer). */
 int  mbn_net_set_keep_activations(mbn_net *net, int keep);
-int  mbn_net_layer_output(mbn_net *net, int index, void **dptr, size_t *floats_per_image);
+int  mbn_net_layer_output(mbn_net *net, int index, void **dptr, size_t *floats_per_image);   /* count: per-image ELEMENTS (fp32, bf16 or uint8) */
 
 /* ------------------------------------------------------------------ multi-GPU (north_star: "batched images
  * shard naturally across the 8 GPUs of one node with an RCCL broadcast of weights over xGMI and no cross-GPU reduction").
