@@ -98,7 +98,9 @@ def _declare_host(lib):
     lib.mbn_strerror.restype = C.c_char_p
     lib.mbn_strerror.argtypes = [C.c_int]
     lib.mbn_plan_build.argtypes = [C.c_float, C.c_int, C.c_int, C.POINTER(Plan)]
+    lib.mbn_plan_build_hw.argtypes = [C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(Plan)]
     lib.mbn_weights_from_h5.argtypes = [C.c_char_p, C.c_float, C.c_int, C.POINTER(Weights)]
+    lib.mbn_weights_from_h5_hw.argtypes = [C.c_char_p, C.c_float, C.c_int, C.c_int, C.POINTER(Weights)]
     lib.mbn_weights_synthetic_h5.argtypes = [C.c_char_p, C.c_float, C.c_int, C.c_uint64]
     lib.mbn_weights_free.argtypes = [C.POINTER(Weights)]
     lib.mbn_h5_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
@@ -215,6 +217,7 @@ def load():
         lib.mbn_stem_fused.argtypes = [vp] + [vp] * 11 + [ci, ci, ci, ci, vp]
         lib.mbn_stem_fused_u8.argtypes = [vp] + [vp] * 11 + [ci, ci, ci, ci, vp]
         lib.mbn_stem_fused_ex.argtypes = [vp] + [vp] * 11 + [ci, ci, ci, ci, ci, vp]
+        lib.mbn_stem_fused_hw.argtypes = [vp] + [vp] * 11 + [ci, ci, ci, ci, ci, ci, vp]
         lib.mbn_net_set_input_u8.argtypes = [vp, ci]
         lib.mbn_net_set_fuse_resident.argtypes = [vp, ci]
         lib.mbn_dwpw_fused.argtypes = [vp] + [vp] * 8 + [ci] * 10 + [vp]
@@ -439,9 +442,22 @@ class Context:
         self.close()
 
 
+def input_hw(res):
+    """(rows, cols) of a `res` argument: an int is a square side, a pair is (rows, cols)."""
+    if isinstance(res, (tuple, list)):
+        rows, cols = res
+        return int(rows), int(cols)
+    return int(res), int(res)
+
+
 def plan_build(alpha=1.0, res=224, classes=1000, lib=None) -> Plan:
+    """mbn_plan_build; res = (rows, cols) builds a rows x cols plan (mbn_plan_build_hw)."""
     p = Plan()
-    _chk((lib or host_lib()).mbn_plan_build(alpha, res, classes, C.byref(p)))
+    lib = lib or host_lib()
+    if isinstance(res, (tuple, list)):
+        _chk(lib.mbn_plan_build_hw(alpha, *input_hw(res), classes, C.byref(p)))
+    else:
+        _chk(lib.mbn_plan_build(alpha, res, classes, C.byref(p)))
     return p
 
 
@@ -461,12 +477,16 @@ def quantize_i8(plan, blob, scales=None, lib=None):
 
 
 class HostWeights:
-    """mbn_weights_from_h5 result; .blob is a numpy view of the packed fp32 parameters."""
+    """mbn_weights_from_h5 result; .blob is a numpy view of the packed fp32 parameters. res = (rows, cols): a rows x cols plan
+    (mbn_weights_from_h5_hw), the same blob."""
 
     def __init__(self, path, alpha=0.0, res=224, lib=None):
         self.lib = lib or host_lib()
         self.w = Weights()
-        _chk(self.lib.mbn_weights_from_h5(path.encode(), alpha, res, C.byref(self.w)), path)
+        if isinstance(res, (tuple, list)):
+            _chk(self.lib.mbn_weights_from_h5_hw(path.encode(), alpha, *input_hw(res), C.byref(self.w)), path)
+        else:
+            _chk(self.lib.mbn_weights_from_h5(path.encode(), alpha, res, C.byref(self.w)), path)
         self.plan = self.w.plan
         self.blob = np.ctypeslib.as_array(self.w.blob, shape=(self.plan.blob_floats,))
 

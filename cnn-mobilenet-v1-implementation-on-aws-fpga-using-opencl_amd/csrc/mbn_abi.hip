@@ -864,44 +864,51 @@ int mbn_classifier_tail_fused(mbn_context *ctx, void *topk_idx_i32, void *topk_p
 
 static int stem_fused_impl(mbn_context *ctx, void *out, const void *image, const void *w1, const void *s1, const void *b1,
                            const void *wd, const void *s2, const void *b2, const void *wp, const void *s3, const void *b3,
-                           int batch, int res, int c1, int c3, void *stream, int in_u8, int bf16)
+                           int batch, int rows, int cols, int c1, int c3, void *stream, int in_u8, int bf16)
 {
     if (!ctx || !out || !image) return MBN_EINVAL;
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     // decide before opening the profiling scope so an unsupported shape does not consume an event slot
-    if (mbn_stem_envelope(batch, res, c1, c3) != MBN_OK) return MBN_EUNSUPPORTED;
-    MBN_SPANS(ctx, { image, (in_u8 ? 1.0 : 4.0) * batch * res * res * 3, "stem image" },
-              { out, (bf16 ? 2.0 : 4.0) * batch * (res / 2) * (res / 2) * c3, "stem output" });
+    if (mbn_stem_envelope_hw(batch, rows, cols, c1, c3) != MBN_OK) return MBN_EUNSUPPORTED;
+    MBN_SPANS(ctx, { image, (in_u8 ? 1.0 : 4.0) * batch * rows * cols * 3, "stem image" },
+              { out, (bf16 ? 2.0 : 4.0) * batch * (rows / 2) * (cols / 2) * c3, "stem output" });
     // parameters the kernel cannot load (null or off 16 bytes) are unsupported; an output off 16 bytes or an image off its load width is invalid
     if (check_ptrs({ w1, s1, b1, wd, s2, b2, wp, s3, b3 }) != MBN_OK) return MBN_EUNSUPPORTED;
     if (((uintptr_t)out % 16) != 0 || ((uintptr_t)image % (in_u8 ? 2 : 8)) != 0) return MBN_EINVAL;
     Scope sc(ctx, s);
     return sc.finish(mbn_launch_f32_stem(ctx, s, (float *)out, (const float *)image, (const float *)w1, (const float *)s1,
                                          (const float *)b1, (const float *)wd, (const float *)s2, (const float *)b2,
-                                         (const float *)wp, (const float *)s3, (const float *)b3, batch, res, c1, c3, in_u8, bf16));
+                                         (const float *)wp, (const float *)s3, (const float *)b3, batch, rows, cols, c1, c3, in_u8, bf16));
+}
+
+int mbn_stem_fused_hw(mbn_context *ctx, void *out, const void *image, const void *w1, const void *s1, const void *b1,
+                      const void *wd, const void *s2, const void *b2, const void *wp, const void *s3, const void *b3,
+                      int batch, int rows, int cols, int c1, int c3, int flags, void *stream)
+{
+    if (flags & ~(MBN_STEM_IN_U8 | MBN_STEM_BF16)) return MBN_EINVAL;
+    return stem_fused_impl(ctx, out, image, w1, s1, b1, wd, s2, b2, wp, s3, b3, batch, rows, cols, c1, c3, stream,
+                           (flags & MBN_STEM_IN_U8) != 0, (flags & MBN_STEM_BF16) != 0);
 }
 
 int mbn_stem_fused(mbn_context *ctx, void *out, const void *image, const void *w1, const void *s1, const void *b1,
                    const void *wd, const void *s2, const void *b2, const void *wp, const void *s3, const void *b3,
                    int batch, int res, int c1, int c3, void *stream)
 {
-    return stem_fused_impl(ctx, out, image, w1, s1, b1, wd, s2, b2, wp, s3, b3, batch, res, c1, c3, stream, 0, 0);
+    return mbn_stem_fused_hw(ctx, out, image, w1, s1, b1, wd, s2, b2, wp, s3, b3, batch, res, res, c1, c3, 0, stream);
 }
 
 int mbn_stem_fused_u8(mbn_context *ctx, void *out, const void *image_u8, const void *w1, const void *s1, const void *b1,
                       const void *wd, const void *s2, const void *b2, const void *wp, const void *s3, const void *b3,
                       int batch, int res, int c1, int c3, void *stream)
 {
-    return stem_fused_impl(ctx, out, image_u8, w1, s1, b1, wd, s2, b2, wp, s3, b3, batch, res, c1, c3, stream, 1, 0);
+    return mbn_stem_fused_hw(ctx, out, image_u8, w1, s1, b1, wd, s2, b2, wp, s3, b3, batch, res, res, c1, c3, MBN_STEM_IN_U8, stream);
 }
 
 int mbn_stem_fused_ex(mbn_context *ctx, void *out, const void *image, const void *w1, const void *s1, const void *b1,
                       const void *wd, const void *s2, const void *b2, const void *wp, const void *s3, const void *b3,
                       int batch, int res, int c1, int c3, int flags, void *stream)
 {
-    if (flags & ~(MBN_STEM_IN_U8 | MBN_STEM_BF16)) return MBN_EINVAL;
-    return stem_fused_impl(ctx, out, image, w1, s1, b1, wd, s2, b2, wp, s3, b3, batch, res, c1, c3, stream,
-                           (flags & MBN_STEM_IN_U8) != 0, (flags & MBN_STEM_BF16) != 0);
+    return mbn_stem_fused_hw(ctx, out, image, w1, s1, b1, wd, s2, b2, wp, s3, b3, batch, res, res, c1, c3, flags, stream);
 }
 
 int mbn_dwpw_fused(mbn_context *ctx, void *out, const void *in, const void *wd, const void *s2, const void *b2,

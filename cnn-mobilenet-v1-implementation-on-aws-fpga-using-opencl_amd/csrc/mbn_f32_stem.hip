@@ -17,7 +17,7 @@
 //      stored as whole 128-byte lines.
 // The three filters and their scale/shift vectors stay in LDS / registers for the workgroup's lifetime.
 // Shapes: Cin 3; conv1 -> C1, pointwise -> C3 with (C1, C3) = (32, 64) (alpha = 1) or (16, 32) (alpha = 0.5: BASELINE
-// config 5's 0.5x160, where the three layers were 40 % of the step as separate launches); input side a multiple of 32.
+// config 5's 0.5x160, where the three layers were 40 % of the step as separate launches); input rows and cols multiples of 32.
 // The kernel is a template over (C1, C3): with 16 channels a lane still owns 4 of them, so there are 4 channel quads per
 // pixel instead of 8 and every phase hands a lane half as many pixels (3 instead of 6 in conv1, 2 instead of 4 in the
 // depthwise) to keep all 256 lanes busy; A/B tile rows are 64 instead of 128 bytes (four 16-byte slots, their own swizzle).
@@ -44,7 +44,8 @@ struct StemArgs {
     float *out;
     const float *in, *w1, *s1, *b1, *wd, *s2, *b2, *wp, *s3, *b3;
     const uint8_t *in8;         // raw uint8 HWC image instead of `in`: normalised at load, x/127.5 - 1 (MBN_IO_IN_U8)
-    int batch, res, h;          // input side, conv1/dw/pw side (res/2)
+    int batch, rows, cols;      // input image rows x cols
+    int oh, ow;                 // conv1/dw/pw map: rows/2 x cols/2
     int tiles_y, tiles_x;
     unsigned ntiles;        // < 2^31 (mbn_stem_envelope): tile indices stay 32-bit, the per-tile index math is scalar and cheap
 };
@@ -80,7 +81,7 @@ constexpr int PAIRS = PROW / 2;                // float2 per patch row (56)
 constexpr int NPF = (PR * PAIRS + 255) / 256;  // float2 prefetch registers per lane (5)
 
 // Phase A, first half: this lane's float2 pieces of tile t's input patch (rows 16ty-2 .. 16ty+18, floats 96tx-6 ..
-// 96tx+105 of each row), zero outside the image. Pair boundaries never straddle the image edge (96tx-6 and 3*res even).
+// 96tx+105 of each row), zero outside the image. Pair boundaries never straddle the image edge (96tx-6 and 3*cols even).
 // Branch-free: buffer loads against this image's descriptor; a piece outside the image (or past the patch) carries an out-of-range
 // offset and the hardware returns zeros (the exec-masked form compiled to two branches per load and a vmcnt(0) drain behind them).
 __device__ __forceinline__ void patch_load(const StemArgs &a, unsigned t, int tid, f2 (&pf)[NPF])
@@ -89,17 +90,17 @@ __device__ __forceinline__ void patch_load(const StemArgs &a, unsigned t, int ti
     const unsigned q0 = t / (unsigned)a.tiles_x;
     const int ty = (int)(q0 % (unsigned)a.tiles_y);
     const long n = q0 / (unsigned)a.tiles_y;
-    const long img = n * a.res * a.res * 3;
-    const int iy0 = 2 * (TH * ty - 1), fx0 = 6 * (TW * tx - 1), rowf = a.res * 3;
+    const long img = n * a.rows * a.cols * 3;
+    const int iy0 = 2 * (TH * ty - 1), fx0 = 6 * (TW * tx - 1), rowf = a.cols * 3;
     constexpr unsigned OOB = 0xF0000000u;
-    const unsigned img_elems = (unsigned)(a.res * a.res * 3);
+    const unsigned img_elems = (unsigned)(a.rows * a.cols * 3);
     if (a.in8) {
         const __amdgpu_buffer_rsrc_t rsrc = mbn_make_rsrc(a.in8 + img, img_elems);
 #pragma unroll
         for (int k = 0; k < NPF; k++) {
             const int i = tid + k * 256, r = i / PAIRS, j = i % PAIRS;
             const int iy = iy0 + r, fx = fx0 + 2 * j;
-            const bool ok = i < PR * PAIRS && iy >= 0 && iy < a.res && fx >= 0 && fx < rowf;
+            const bool ok = i < PR * PAIRS && iy >= 0 && iy < a.rows && fx >= 0 && fx < rowf;
             const unsigned u = (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rsrc, ok ? (unsigned)(iy * rowf + fx) : OOB, 0, 0);
             // same fmaf as normalize_u8_f32: bit-identical; the zero padding is zero AFTER normalisation
             pf[k] = ok ? f2{ fmaf((float)(u & 0xff), 1.0f / 127.5f, -1.0f), fmaf((float)(u >> 8), 1.0f / 127.5f, -1.0f) } : f2{ 0.f, 0.f };
@@ -110,7 +111,7 @@ __device__ __forceinline__ void patch_load(const StemArgs &a, unsigned t, int ti
         for (int k = 0; k < NPF; k++) {
             const int i = tid + k * 256, r = i / PAIRS, j = i % PAIRS;
             const int iy = iy0 + r, fx = fx0 + 2 * j;
-            const bool ok = i < PR * PAIRS && iy >= 0 && iy < a.res && fx >= 0 && fx < rowf;
+            const bool ok = i < PR * PAIRS && iy >= 0 && iy < a.rows && fx >= 0 && fx < rowf;
             pf[k] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, ok ? (unsigned)(iy * rowf + fx) * 4u : OOB, 0, 0));
         }
     }
@@ -358,7 +359,7 @@ __global__ __launch_bounds__(256, WPE) void stem_fused_f32(StemArgs a)
                 for (int t = 0; t < 7; t++) xv[t] = src[mcf_dl[t]];
                 if (kg == 3) xv[6] = 0.f;                                 // k = 27 does not exist (its weight is 0 too)
                 const int oy = TH * ty - 1 + r, ox = TW * tx - 1 + c;     // position of THIS lane's pixel in the conv1 map
-                const bool inside = oy >= 0 && oy < a.h && ox >= 0 && ox < a.h;
+                const bool inside = oy >= 0 && oy < a.oh && ox >= 0 && ox < a.ow;
 #pragma unroll
                 for (int h = 0; h < 2; h++) {
                     f4 acc = f4{ 0.f, 0.f, 0.f, 0.f };                    // same instruction, same k order as conv1_mfma_f32 (mbn_f32_misc.hip): same bits
@@ -393,7 +394,7 @@ __global__ __launch_bounds__(256, WPE) void stem_fused_f32(StemArgs a)
                 }
                 const bf8 xh = __builtin_bit_cast(bf8, ph), xl = __builtin_bit_cast(bf8, pl);
                 const int oy = TH * ty - 1 + r, ox = TW * tx - 1 + c;     // position of THIS lane's pixel in the conv1 map
-                const bool inside = oy >= 0 && oy < a.h && ox >= 0 && ox < a.h;
+                const bool inside = oy >= 0 && oy < a.oh && ox >= 0 && ox < a.ow;
 #pragma unroll
                 for (int h = 0; h < MH; h++) {
                     // weights as the A operand (rows = channels), pixels as B (columns): C/D puts channels 16h + 4kg .. +3 of
@@ -440,11 +441,11 @@ __global__ __launch_bounds__(256, WPE) void stem_fused_f32(StemArgs a)
                     }
             }
             const int oy = TH * ty - 1 + br, ox = TW * tx - 1 + bc;      // position in the 112x112 conv1 map
-            const bool rowok = oy >= 0 && oy < a.h;
+            const bool rowok = oy >= 0 && oy < a.oh;
             const f4 s1 = *reinterpret_cast<const f4 *>(sb_s + c4 * 4), b1 = *reinterpret_cast<const f4 *>(sb_s + C1 + c4 * 4);
 #pragma unroll
             for (int p = 0; p < PB; p++) {                                // outside the map: the depthwise zero padding
-                f4 v = (rowok && ox + p >= 0 && ox + p < a.h) ? bn_relu6(acc[p], s1, b1) : f4{ 0.f, 0.f, 0.f, 0.f };
+                f4 v = (rowok && ox + p >= 0 && ox + p < a.ow) ? bn_relu6(acc[p], s1, b1) : f4{ 0.f, 0.f, 0.f, 0.f };
                 if (BF) v = rbf4(v);
                 *reinterpret_cast<f4 *>(c1_s + (br * CC + bc + p) * C1 + c4 * 4) = v;
             }
@@ -515,12 +516,12 @@ __global__ __launch_bounds__(256, WPE) void stem_fused_f32(StemArgs a)
             // byte offset is ONE VGPR for all 16 stores (the lane's half lh shifts the pixel by 4 columns: row q = 32 wave + (r & 3) +
             // 8 (r >> 2) + 4 lh sits at y = 2 wave + (r >> 3), x = (r & 3) + 8 ((r >> 2) & 1) + 4 lh of the 8 x 16 tile), the
             // wave-uniform rest is the scalar offset: no 64-bit address arithmetic per store.
-            const __amdgpu_buffer_rsrc_t orsrc = mbn_make_rsrc(reinterpret_cast<__bf16 *>(a.out) + n * a.h * a.h * C3, (unsigned)(a.h * a.h * C3 * 2));
+            const __amdgpu_buffer_rsrc_t orsrc = mbn_make_rsrc(reinterpret_cast<__bf16 *>(a.out) + n * a.oh * a.ow * C3, (unsigned)(a.oh * a.ow * C3 * 2));
             const unsigned lane_off = (unsigned)(4 * lh * C3) * 2u + (unsigned)li * (NI == 2 ? 4u : 2u);
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 const int y = TH * ty + 2 * __builtin_amdgcn_readfirstlane(wave) + (r >> 3), x = TW * tx + (r & 3) + 8 * ((r >> 2) & 1);
-                const unsigned soff = (unsigned)((y * a.h + x) * C3) * 2u;
+                const unsigned soff = (unsigned)((y * a.ow + x) * C3) * 2u;
                 if constexpr (NI == 2) {
                     // channel-paired store: lane li holds channels 2li (acc[0]) and 2li+1 (acc[1]) of pixel row q: one dword per
                     // row, 32 lanes = the pixel's whole 128-byte line
@@ -570,24 +571,24 @@ __global__ __launch_bounds__(256, WPE) void stem_fused_f32(StemArgs a)
         if constexpr (C1 == 32 && !BREG) {
             // alpha = 1 in fp32 keeps plain global stores: the buffer-store form below measured 1.2 % SLOWER here (0.3077 against 0.3040 ms,
             // same call, three repetitions) although it drops ~80 address instructions and 32 VGPRs; it wins at alpha = 0.5 (-6 %) and in bf16
-            float *obase = a.out + ((n * a.h + TH * ty) * a.h + TW * tx) * C3;
+            float *obase = a.out + ((n * a.oh + TH * ty) * a.ow + TW * tx) * C3;
 #pragma unroll
             for (int ni = 0; ni < NI; ni++)
 #pragma unroll
                 for (int r = 0; r < 16; r++) {
                     const int q = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                     const int y = q >> 4, x = q & 15;
-                    obase[((long)y * a.h + x) * C3 + ni * 32 + li] = relu6(fmaf(acc[ni][r], s3[ni], b3[ni]));
+                    obase[((long)y * a.ow + x) * C3 + ni * 32 + li] = relu6(fmaf(acc[ni][r], s3[ni], b3[ni]));
                 }
         } else {
-        const __amdgpu_buffer_rsrc_t orsrc = mbn_make_rsrc(a.out + n * a.h * a.h * C3, (unsigned)(a.h * a.h * C3 * 4));   // see the bf16 branch
+        const __amdgpu_buffer_rsrc_t orsrc = mbn_make_rsrc(a.out + n * a.oh * a.ow * C3, (unsigned)(a.oh * a.ow * C3 * 4));   // see the bf16 branch
         const unsigned lane_off = (unsigned)(4 * lh * C3 + li) * 4u;
 #pragma unroll
         for (int ni = 0; ni < NI; ni++)
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 const int y = TH * ty + 2 * __builtin_amdgcn_readfirstlane(wave) + (r >> 3), x = TW * tx + (r & 3) + 8 * ((r >> 2) & 1);
-                const unsigned soff = (unsigned)((y * a.h + x) * C3 + ni * 32) * 4u;
+                const unsigned soff = (unsigned)((y * a.ow + x) * C3 + ni * 32) * 4u;
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, relu6(fmaf(acc[ni][r], s3[ni], b3[ni]))), orsrc, lane_off, soff, 0);
             }
         }
@@ -602,13 +603,13 @@ __global__ __launch_bounds__(256, WPE) void stem_fused_f32(StemArgs a)
 // Fused layers 1-3 (the caller has checked mbn_stem_envelope and the pointers).
 int mbn_launch_f32_stem(mbn_context *ctx, hipStream_t stream, float *out, const float *in, const float *w1,
                         const float *s1, const float *b1, const float *wd, const float *s2, const float *b2,
-                        const float *wp, const float *s3, const float *b3, int batch, int res, int c1, int c3, int in_u8, int bf16)
+                        const float *wp, const float *s3, const float *b3, int batch, int rows, int cols, int c1, int c3, int in_u8, int bf16)
 {
     StemArgs a;
     a.in8 = in_u8 ? (const uint8_t *)in : nullptr;
     a.out = out; a.in = in; a.w1 = w1; a.s1 = s1; a.b1 = b1; a.wd = wd; a.s2 = s2; a.b2 = b2; a.wp = wp; a.s3 = s3; a.b3 = b3;
-    a.batch = batch; a.res = res; a.h = res / 2;
-    a.tiles_y = a.h / TH; a.tiles_x = a.h / TW;
+    a.batch = batch; a.rows = rows; a.cols = cols; a.oh = rows / 2; a.ow = cols / 2;
+    a.tiles_y = a.oh / TH; a.tiles_x = a.ow / TW;      // both sides multiples of 32 (mbn_stem_envelope_hw): whole tiles
     a.ntiles = (unsigned)((long)batch * a.tiles_y * a.tiles_x);
     // alpha = 1 bf16: three workgroups per CU (taps from LDS) 0.448-0.455 ms against 0.472-0.480 with two (taps in registers), same run
     const int wpe_bf = g_mbn_tune.misc == 2 ? 2 : 3;                                  // A/B hook: misc = 2

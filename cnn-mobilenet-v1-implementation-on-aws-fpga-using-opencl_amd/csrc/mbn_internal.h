@@ -202,10 +202,10 @@ int mbn_launch_bf16_res_blocks(mbn_context *ctx, hipStream_t stream, void *out, 
 #define MBN_DWPW3_DEFAULT(stride, cin) ((stride) == 1 && (cin) >= 128)
 int mbn_f32_dwpw3_eligible(const mbn_context *ctx, const mbn_block_shape &s);      // inside mbn_block_envelope: the form's own limits
 int mbn_launch_f32_dwpw3(mbn_context *ctx, hipStream_t stream, const mbn_block_shape &s, void *out, const void *in, const mbn_block_params &p);
-// the fused stem: the shape is inside mbn_stem_envelope and the pointers are checked by the caller
+// the fused stem: the shape is inside mbn_stem_envelope_hw and the pointers are checked by the caller
 int mbn_launch_f32_stem(mbn_context *ctx, hipStream_t stream, float *out, const float *in, const float *w1,
                         const float *s1, const float *b1, const float *wd, const float *s2, const float *b2,
-                        const float *wp, const float *s3, const float *b3, int batch, int res, int c1, int c3, int in_u8, int bf16);
+                        const float *wp, const float *s3, const float *b3, int batch, int rows, int cols, int c1, int c3, int in_u8, int bf16);
 int mbn_launch_convert(mbn_context *ctx, hipStream_t s, void *dst, const void *src, size_t count, int to_bf16);
 int mbn_launch_f32_softmax(mbn_context *ctx, hipStream_t s, float *probs, int32_t *argmax, const float *logits,
                            int batch, int classes);

@@ -47,7 +47,15 @@ int mbn_tail_envelope(const mbn_block_shape *b0, const mbn_block_shape *b1)
 
 int mbn_stem_envelope(int batch, int res, int c1, int c3)
 {
-    if (!((c1 == 32 && c3 == 64) || (c1 == 16 && c3 == 32)) || res < 32 || (res % 32) != 0 || batch <= 0) return MBN_EUNSUPPORTED;
-    if ((long)batch * (res / 2 / MBN_STEM_TH) * (res / 2 / MBN_STEM_TW) >= 0x7fffffffL) return MBN_EUNSUPPORTED;   /* 32-bit tile index */
+    return mbn_stem_envelope_hw(batch, res, res, c1, c3);
+}
+
+int mbn_stem_envelope_hw(int batch, int rows, int cols, int c1, int c3)
+{
+    if (!((c1 == 32 && c3 == 64) || (c1 == 16 && c3 == 32)) || rows < 32 || (rows % 32) != 0 || cols < 32 || (cols % 32) != 0 || batch <= 0)
+        return MBN_EUNSUPPORTED;
+    if ((long)batch * (rows / 2 / MBN_STEM_TH) * (cols / 2 / MBN_STEM_TW) >= 0x7fffffffL) return MBN_EUNSUPPORTED;   /* 32-bit tile index */
+    /* per-image buffer offsets (input loads and output stores) are 32-bit */
+    if (4.0 * rows * cols * 3 >= (double)MBN_OOB || 4.0 * (rows / 2) * (cols / 2) * c3 >= 4294967296.0) return MBN_EUNSUPPORTED;
     return MBN_OK;
 }

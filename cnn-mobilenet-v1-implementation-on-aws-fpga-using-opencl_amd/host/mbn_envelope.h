@@ -33,7 +33,8 @@ int mbn_block_envelope(const mbn_block_shape *s, int dtype);
 int mbn_resident_envelope(const mbn_block_shape *s, int nblocks);
 /* the two blocks of mbn_tail_resident_bf16: b0 stride 2 without top / left padding on an even map, b1 stride 1 with pad 1 on b0's output */
 int mbn_tail_envelope(const mbn_block_shape *b0, const mbn_block_shape *b1);
-/* mbn_stem_fused*: c1 -> c1 -> c3 channels on res x res images */
+/* mbn_stem_fused_hw: c1 -> c1 -> c3 channels on rows x cols images; mbn_stem_envelope is the square form (mbn_stem_fused, _u8, _ex) */
+int mbn_stem_envelope_hw(int batch, int rows, int cols, int c1, int c3);
 int mbn_stem_envelope(int batch, int res, int c1, int c3);
 
 #ifdef __cplusplus

@@ -336,7 +336,7 @@ static int stem_fusable(const mbn_net *net, int count, int last_layer)
     return net->fuse_stem && !net->keep && last_layer >= 3 && net->plan.n_layers >= 3 &&
            (net->dtype == MBN_DT_F32 || (net->dtype == MBN_DT_BF16 && net->bf16_filt[2])) &&
            l[0].kind == MBN_L_CONV && l[1].kind == MBN_L_DW && l[2].kind == MBN_L_PW && l[0].in_ch == 3 && l[1].stride == 1 &&
-           mbn_stem_envelope(count, net->plan.res, l[0].out_ch, l[2].out_ch) == MBN_OK &&
+           mbn_stem_envelope_hw(count, l[0].in_rows, l[0].in_cols, l[0].out_ch, l[2].out_ch) == MBN_OK &&
            layer_aligned(net, 0) && layer_aligned(net, 1) && layer_aligned(net, 2);
 }
 
@@ -621,9 +621,9 @@ static int run_layer(mbn_net *net, const mbn_layer_desc *l, const void *src, voi
     case MBN_L_PW:                         /* MobileNet.c:417-470, with filtersize = true Cin (B3) */
         if (bf && net->bf16_packed[l->index - 1]) ext.io_flags |= MBN_IO_FILT_PACKED;
         return mbn_pointwise(net->ctx, dst, src, filt, l->out_rows, l->out_cols, l->in_ch, l->out_ch, &ext);
-    case MBN_L_POOL:                       /* MobileNet.c:2603-2656 */
+    case MBN_L_POOL:                       /* MobileNet.c:2603-2656; the window is clamped per side: the whole rows x cols plane */
         ext.act = MBN_ACT_NONE;
-        return mbn_pool(net->ctx, dst, src, l->in_rows, l->in_cols, l->in_rows, l->out_ch, &ext);
+        return mbn_pool(net->ctx, dst, src, l->in_rows, l->in_cols, l->in_rows > l->in_cols ? l->in_rows : l->in_cols, l->out_ch, &ext);
     case MBN_L_FC:                         /* MobileNet.c:2682-2739: pointwise with rows = cols = 1; bias, no ReLU (B15) */
         ext.act = MBN_ACT_NONE;
         if (bf || i8) ext.io_flags = MBN_IO_OUT_F32;   /* logits stay fp32 */
@@ -663,7 +663,7 @@ static int alloc_keep(mbn_net *net, int i)
 static int forward_range(mbn_net *net, const void *images, void *logits, int first, int count, int last_layer,
                          void *stream, float *layer_ms, int n_layer_ms, void *next_stream, int stagger)
 {
-    const size_t img_floats = (size_t)net->plan.res * net->plan.res * 3;
+    const size_t img_floats = (size_t)net->plan.layer[0].in_rows * net->plan.layer[0].in_cols * 3;   /* [rows][cols][3] per image */
     const char *src = (const char *)images + (size_t)first * img_floats * (net->input_u8 ? 1 : sizeof(float));
     const size_t slot = (size_t)first * (size_t)net->plan.max_act_floats * sizeof(float);
     const int bf = net->dtype == MBN_DT_BF16;
@@ -690,10 +690,10 @@ static int forward_range(mbn_net *net, const void *images, void *logits, int fir
         int rc;
         switch (kind) {
         case K_STEM:            /* layers 1-3 in one kernel; the 112x112x32 intermediates stay on chip */
-            rc = mbn_stem_fused_ex(net->ctx, dst, src, blob_at(net, L[0].w_offset), blob_at(net, L[0].scale_offset),
+            rc = mbn_stem_fused_hw(net->ctx, dst, src, blob_at(net, L[0].w_offset), blob_at(net, L[0].scale_offset),
                                    blob_at(net, L[0].shift_offset), blob_at(net, L[1].w_offset), blob_at(net, L[1].scale_offset),
                                    blob_at(net, L[1].shift_offset), bf ? net->bf16_filt[2] : blob_at(net, L[2].w_offset),
-                                   blob_at(net, L[2].scale_offset), blob_at(net, L[2].shift_offset), count, net->plan.res,
+                                   blob_at(net, L[2].scale_offset), blob_at(net, L[2].shift_offset), count, L[0].in_rows, L[0].in_cols,
                                    L[0].out_ch, L[2].out_ch, (net->input_u8 ? MBN_STEM_IN_U8 : 0) | (bf ? MBN_STEM_BF16 : 0), stream);
             break;
         case K_RESIDENT:        /* span / 2 blocks in one launch, the map resident in LDS from the first block's input to the last block's output */

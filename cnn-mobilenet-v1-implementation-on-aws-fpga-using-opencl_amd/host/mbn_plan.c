@@ -29,72 +29,89 @@ static int same_pad(int in, int out, int k, int stride)
 
 int mbn_plan_build(float alpha, int res, int classes, mbn_plan *plan)
 {
+    return mbn_plan_build_hw(alpha, res, res, classes, plan);
+}
+
+/* rows x cols input: every layer tracks its height h and width w separately; the pads follow each side (pad_top from the rows,
+ * pad_left from the cols), and the blob layout depends on neither. */
+int mbn_plan_build_hw(float alpha, int rows, int cols, int classes, mbn_plan *plan)
+{
     /* output channels of conv1 and of the 13 pointwise layers at alpha = 1 (MobileNet.c:16-25) */
     static const int width[14] = { 32, 64, 128, 128, 256, 256, 512, 512, 512, 512, 512, 512, 1024, 1024 };
     /* strides of the 13 depthwise layers (MobileNet.c: L4 :503, L8 :865, L12 :1219, L24 :2264 are 2) */
     static const int dstride[13] = { 1, 2, 1, 2, 1, 2, 1, 1, 1, 1, 1, 2, 1 };
 
     if (!plan) return MBN_EINVAL;
-    if (!(alpha > 0.f) || alpha > 4.f || res < 32 || res > 4096 || classes <= 0) return MBN_EINVAL;
+    if (!(alpha > 0.f) || alpha > 4.f || rows < 32 || rows > 4096 || cols < 32 || cols > 4096 || classes <= 0) return MBN_EINVAL;
     /* Odd feature maps are where TF-"SAME" (out = ceil(h/2), pad_top = total/2: what this table computes) and Keras
      * MobileNet (ZeroPadding2D(((0,1),(0,1))) + 'valid': pad_top = 0, out = floor((h-2)/2)+1) disagree — 25 -> 13 vs 12.
-     * With res a multiple of 32 every stride-2 layer sees an even map and the two coincide, so that is the supported set. */
-    if (res % 32) return MBN_EUNSUPPORTED;
+     * With both sides multiples of 32 every stride-2 layer sees an even map and the two coincide, so that is the supported set. */
+    if ((rows % 32) || (cols % 32)) return MBN_EUNSUPPORTED;
     memset(plan, 0, sizeof(*plan));
     plan->alpha = alpha;
-    plan->res = res;
+    plan->res = rows == cols ? rows : 0;          /* non-square: the input size is layer[0].in_rows x in_cols */
     plan->classes = classes;
 
-    int64_t off = 0, max_act = (int64_t)res * res * 3;
-    int n = 0, h = res, ch = 3;
+    int64_t off = 0, max_act = (int64_t)rows * cols * 3;
+    int n = 0, h = rows, w = cols, ch = 3;
 
     for (int blk = -1; blk < 13; blk++) {
         if (blk >= 0) {                                   /* depthwise half of block blk */
             mbn_layer_desc *d = &plan->layer[n++];
             d->index = n;
             d->kind = MBN_L_DW;
-            d->in_rows = d->in_cols = h;
+            d->in_rows = h;
+            d->in_cols = w;
             d->in_ch = d->out_ch = ch;
             d->stride = dstride[blk];
-            d->out_rows = d->out_cols = (h + d->stride - 1) / d->stride;
-            d->pad_top = d->pad_left = same_pad(h, d->out_rows, 3, d->stride);
+            d->out_rows = (h + d->stride - 1) / d->stride;
+            d->out_cols = (w + d->stride - 1) / d->stride;
+            d->pad_top = same_pad(h, d->out_rows, 3, d->stride);
+            d->pad_left = same_pad(w, d->out_cols, 3, d->stride);
             d->w_offset = off; d->w_count = 9 * (int64_t)ch; off = align_seg(off + d->w_count);
             d->scale_offset = off; off = align_seg(off + ch);
             d->shift_offset = off; off = align_seg(off + ch);
             h = d->out_rows;
-            if ((int64_t)h * h * ch > max_act) max_act = (int64_t)h * h * ch;
+            w = d->out_cols;
+            if ((int64_t)h * w * ch > max_act) max_act = (int64_t)h * w * ch;
         }
         int oc = (int)(width[blk + 1] * alpha);           /* Keras: int(filters * alpha) */
         if (oc < 1) return MBN_EINVAL;
         mbn_layer_desc *l = &plan->layer[n++];
         l->index = n;
-        l->in_rows = l->in_cols = h;
+        l->in_rows = h;
+        l->in_cols = w;
         l->in_ch = ch;
         l->out_ch = oc;
         if (blk < 0) {                                    /* conv1: 3x3x3, stride 2 (MobileNet.c:123-124,268-292) */
             l->kind = MBN_L_CONV;
             l->stride = 2;
-            l->out_rows = l->out_cols = (h + 1) / 2;
-            l->pad_top = l->pad_left = same_pad(h, l->out_rows, 3, 2);
+            l->out_rows = (h + 1) / 2;
+            l->out_cols = (w + 1) / 2;
+            l->pad_top = same_pad(h, l->out_rows, 3, 2);
+            l->pad_left = same_pad(w, l->out_cols, 3, 2);
             l->w_count = 27 * (int64_t)oc;
         } else {                                          /* pointwise half */
             l->kind = MBN_L_PW;
             l->stride = 1;
-            l->out_rows = l->out_cols = h;
+            l->out_rows = h;
+            l->out_cols = w;
             l->w_count = (int64_t)oc * ch;
         }
         l->w_offset = off; off = align_seg(off + l->w_count);
         l->scale_offset = off; off = align_seg(off + oc);
         l->shift_offset = off; off = align_seg(off + oc);
         h = l->out_rows;
+        w = l->out_cols;
         ch = oc;
-        if ((int64_t)h * h * ch > max_act) max_act = (int64_t)h * h * ch;
+        if ((int64_t)h * w * ch > max_act) max_act = (int64_t)h * w * ch;
     }
 
     mbn_layer_desc *p = &plan->layer[n++];                /* L28 global average pool (MobileNet.c:2601-2679) */
     p->index = n;
     p->kind = MBN_L_POOL;
-    p->in_rows = p->in_cols = h;
+    p->in_rows = h;
+    p->in_cols = w;
     p->in_ch = p->out_ch = ch;
     p->stride = 1;
     p->out_rows = p->out_cols = 1;

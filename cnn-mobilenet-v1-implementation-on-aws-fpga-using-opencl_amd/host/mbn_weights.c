@@ -68,12 +68,19 @@ int mbn_weights_free(mbn_weights *w)
 
 int mbn_weights_from_h5(const char *path, float alpha, int res, mbn_weights *w)
 {
+    return mbn_weights_from_h5_hw(path, alpha, res, res, w);
+}
+
+/* the blob layout does not depend on the input size: only the plan's map sizes differ from a square load */
+int mbn_weights_from_h5_hw(const char *path, float alpha, int rows, int cols, mbn_weights *w)
+{
     if (!path || !w) return MBN_EINVAL;
     memset(w, 0, sizeof(*w));
     mbn_h5 *h5 = NULL;
     int rc = mbn_h5_open(path, &h5);
     if (rc != MBN_OK) return rc;
-    if (res <= 0) res = 224;
+    if (rows <= 0) rows = 224;
+    if (cols <= 0) cols = rows;
 
     int ndim;
     int64_t shape[8];
@@ -86,7 +93,7 @@ int mbn_weights_from_h5(const char *path, float alpha, int res, mbn_weights *w)
         rc = mbn_h5_get(h5, "/conv_preds/conv_preds/bias:0", &ndim, shape, &p);
         if (rc == MBN_OK) classes = (int)shape_count(ndim, shape);
     }
-    if (rc == MBN_OK) rc = mbn_plan_build(alpha, res, classes, &w->plan);
+    if (rc == MBN_OK) rc = mbn_plan_build_hw(alpha, rows, cols, classes, &w->plan);
     if (rc == MBN_OK) {
         w->blob = (float *)calloc((size_t)w->plan.blob_floats, sizeof(float));
         if (!w->blob) rc = MBN_ENOMEM;

@@ -3,6 +3,7 @@
  *
  *   mobilenet --h5 weights.h5 [--ppm image.ppm] [--batch N] [--res 224] [--alpha 1.0]      fp32 path
  *   mobilenet --synthetic SEED [--alpha A] [--res R] [--batch N]                              fp32, synthetic weights
+ *   --res R = R x R images; --res RxC = R rows by C columns (a P6 image C wide and R high), both multiples of 32
  *   mobilenet --literal [--weights weights_c.txt] [--image Cat_Image0.ppm] [--ref-args]      the reference's own mode
  *   mobilenet --gpus G --batch N [--steps K --warmup W --streams S --pw-emul 6] (--h5 F | --synthetic SEED)  N images sharded over G GPUs
  *   mobilenet --inspect weights.h5                                                             list the datasets of a .h5
@@ -149,7 +150,7 @@ static int convert_h5(const char *path, const char *out)
  * collective on the data path. Timing: W untimed steps, a thread barrier, K steps, device sync, barrier; the job's time
  * is the slowest GPU's (MAX), images/s = K * N / that. The reference drives exactly one device (MobileNet.c:155). */
 typedef struct {
-    int rank, world, batch, first, count, res, steps, warmup;
+    int rank, world, batch, first, count, steps, warmup;
     mbn_dist *dist;
     const mbn_plan *plan;
     void *dev_blob;
@@ -189,14 +190,14 @@ static unsigned long long fnv1a(const void *p, size_t n)
 
 /* the forward of images [first, first + n) on `ctx`, exactly as a rank runs it (same net settings, same call sizes): used by the
  * ranks and by --verify, which replays every shard on GPU 0 */
-static int shard_forward(mbn_context *ctx, const mbn_plan *plan, void *dev_blob, int res, int first, int n, int warmup, int steps,
+static int shard_forward(mbn_context *ctx, const mbn_plan *plan, void *dev_blob, int first, int n, int warmup, int steps,
                          float *host_logits, int *top1, double *seconds, mbn_rank_sync *sync)
 {
     mbn_net *net = NULL;
     void *d_u8 = NULL, *d_logits = NULL, *d_idx = NULL, *d_prob = NULL;
     unsigned char *u8 = NULL;
     const int nn = n > 0 ? n : 1;                             /* a rank without images still takes part in the barriers */
-    const size_t img = (size_t)res * res * 3;
+    const size_t img = (size_t)plan->layer[0].in_rows * plan->layer[0].in_cols * 3;     /* [rows][cols][3] uint8 */
     int rc = mbn_net_create_from_device_blob(ctx, plan, dev_blob, nn, &net);
     if (rc == MBN_OK) rc = mbn_net_set_input_u8(net, 1);
     if (rc == MBN_OK && g_streams > 1) {
@@ -242,14 +243,14 @@ static int gpu_rank(int rank, void *arg, mbn_rank_sync *sync)
     mbn_context *ctx = NULL;
     int rc = mbn_dist_context(j->dist, j->rank, &ctx);
     if (rc == MBN_OK)
-        rc = shard_forward(ctx, j->plan, j->dev_blob, j->res, j->first, j->count, j->warmup, j->steps, j->logits, &j->top1, &j->seconds, sync);
+        rc = shard_forward(ctx, j->plan, j->dev_blob, j->first, j->count, j->warmup, j->steps, j->logits, &j->top1, &j->seconds, sync);
     if (rc == MBN_OK && j->count > 0) j->fnv = fnv1a(j->logits, (size_t)j->count * j->plan->classes * sizeof(float));
     if (rc != MBN_OK) fprintf(stderr, "Error: GPU %d: %s (%s)\n", j->rank, mbn_strerror(rc), ctx ? mbn_last_device_error(ctx) : "");
     return rc;
 }
 
 /* --gpus G [--verify]. Every failure leaves through `done`, which shuts the communicators and contexts down. */
-static int run_multi(int gpus, int batch, int res, int steps, int warmup, const mbn_weights *w, int verify)
+static int run_multi(int gpus, int batch, int steps, int warmup, const mbn_weights *w, int verify)
 {
     mbn_context *ctx = NULL;
     mbn_dist *dist = NULL;
@@ -275,7 +276,7 @@ static int run_multi(int gpus, int batch, int res, int steps, int warmup, const 
     if (rc != MBN_OK) { fprintf(stderr, "Error: mbn_dist_broadcast -> %s (%s)\n", mbn_strerror(rc), mbn_dist_last_error(dist)); goto done; }
     for (int r = 0; r < gpus; r++) {
         gpu_job *j = &jobs[r];
-        j->rank = r; j->world = gpus; j->batch = batch; j->res = res; j->steps = steps; j->warmup = warmup;
+        j->rank = r; j->world = gpus; j->batch = batch; j->steps = steps; j->warmup = warmup;
         j->dist = dist; j->plan = &w->plan; j->dev_blob = blobs[r];
         TRY(mbn_shard_range(batch, gpus, r, &j->first, &j->count));
         j->logits = malloc((size_t)(j->count > 0 ? j->count : 1) * w->plan.classes * sizeof(float));
@@ -304,7 +305,7 @@ static int run_multi(int gpus, int batch, int res, int steps, int warmup, const 
             const size_t nb = (size_t)jobs[r].count * w->plan.classes * sizeof(float);
             float *again = malloc(nb);
             if (!again) goto done;
-            rc = shard_forward(ctx, &w->plan, blobs[0], res, jobs[r].first, jobs[r].count, 0, 1, again, NULL, NULL, NULL);
+            rc = shard_forward(ctx, &w->plan, blobs[0], jobs[r].first, jobs[r].count, 0, 1, again, NULL, NULL, NULL);
             const int same = rc == MBN_OK && memcmp(again, jobs[r].logits, nb) == 0;
             printf("verify: shard %d (GPU %d) vs the same images on GPU 0: %s (fnv1a %016llx)\n", r, r,
                    rc != MBN_OK ? mbn_strerror(rc) : same ? "identical" : "DIFFERENT", rc == MBN_OK ? fnv1a(again, nb) : 0ULL);
@@ -327,7 +328,7 @@ int main(int argc, char **argv)
     if (argc == 3 && !strcmp(argv[1], "--inspect")) return inspect_h5(argv[2]);
     if (argc == 4 && !strcmp(argv[1], "--convert")) return convert_h5(argv[2], argv[3]);
     const char *h5 = NULL, *ppm = NULL, *wfile = "weights_c.txt", *image = "Cat_Image0.ppm";
-    int literal = 0, ref_args = 0, batch = 1, res = 224, have_seed = 0, gpus = 0, steps = 20, warmup = 3, verify = 0;
+    int literal = 0, ref_args = 0, batch = 1, rows = 224, cols = 224, have_seed = 0, gpus = 0, steps = 20, warmup = 3, verify = 0;
     unsigned long long seed = 0;
     float alpha = 0.f;
     for (int i = 1; i < argc; i++) {
@@ -336,7 +337,12 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--weights") && i + 1 < argc) wfile = argv[++i];
         else if (!strcmp(argv[i], "--image") && i + 1 < argc) image = argv[++i];
         else if (!strcmp(argv[i], "--batch") && i + 1 < argc) batch = atoi(argv[++i]);
-        else if (!strcmp(argv[i], "--res") && i + 1 < argc) res = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--res") && i + 1 < argc) {          /* R or RxC, rows first */
+            const char *r = argv[++i];
+            char *end = NULL;
+            rows = cols = (int)strtol(r, &end, 10);
+            if (end && (*end == 'x' || *end == 'X')) cols = atoi(end + 1);
+        }
         else if (!strcmp(argv[i], "--alpha") && i + 1 < argc) alpha = (float)atof(argv[++i]);
         else if (!strcmp(argv[i], "--synthetic") && i + 1 < argc) { seed = strtoull(argv[++i], NULL, 0); have_seed = 1; }
         else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = atoi(argv[++i]);
@@ -350,7 +356,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--literal")) literal = 1;
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
-            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F] [--batch N] [--res R] [--alpha A] "
+            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F] [--batch N] [--res R | RxC] [--alpha A] "
                             "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n", argv[0]);
             return 2;
         }
@@ -368,9 +374,9 @@ int main(int argc, char **argv)
             h5 = tmpm;
         }
         mbn_weights wm;
-        CHECK(mbn_weights_from_h5(h5, alpha, res, &wm));
+        CHECK(mbn_weights_from_h5_hw(h5, alpha, rows, cols, &wm));
         if (h5 == tmpm) remove(tmpm);
-        int rc = run_multi(gpus, batch, res, steps, warmup, &wm, verify);
+        int rc = run_multi(gpus, batch, steps, warmup, &wm, verify);
         mbn_weights_free(&wm);
         return rc;
     }
@@ -394,19 +400,20 @@ int main(int argc, char **argv)
         h5 = tmp;
     }
     mbn_weights w;
-    CHECK(mbn_weights_from_h5(h5, alpha, res, &w));
+    CHECK(mbn_weights_from_h5_hw(h5, alpha, rows, cols, &w));
     if (have_seed) remove(tmp);
     mbn_net *net = NULL;
     CHECK(mbn_net_create(ctx, &w, batch, &net));
     const int classes = w.plan.classes;
-    size_t img_count = (size_t)batch * res * res * 3;
+    const size_t img = (size_t)rows * cols * 3;          /* [rows][cols][3]: a P6 image cols wide and rows high */
+    size_t img_count = (size_t)batch * img;
     unsigned char *u8 = malloc(img_count);
     if (!u8) return 1;
     int pw = 0, ph = 0;
-    if (ppm && mbn_read_ppm(ppm, u8, &pw, &ph, res * res) == MBN_OK && pw == res && ph == res) {
-        for (int n = 1; n < batch; n++) memcpy(u8 + (size_t)n * res * res * 3, u8, (size_t)res * res * 3);
+    if (ppm && mbn_read_ppm(ppm, u8, &pw, &ph, rows * cols) == MBN_OK && pw == cols && ph == rows) {
+        for (int n = 1; n < batch; n++) memcpy(u8 + (size_t)n * img, u8, img);
     } else {
-        if (ppm) fprintf(stderr, "warning: %s is not a %dx%d P6 image; using a synthetic one\n", ppm, res, res);
+        if (ppm) fprintf(stderr, "warning: %s is not a %d wide, %d high P6 image; using a synthetic one\n", ppm, cols, rows);
         unsigned long long s = 0xC0FFEEULL;
         for (size_t i = 0; i < img_count; i++) { s = s * 6364136223846793005ULL + 1442695040888963407ULL; u8[i] = (unsigned char)(s >> 56); }
     }

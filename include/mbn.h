@@ -240,7 +240,9 @@ int mbn_pointwise(mbn_context *ctx, void *output, const void *inp_image, const v
                   int rows, int cols, int filtersize, int op_size, const mbn_layer_ext *ext);
 
 /* pool (kernel.cl:116): global filtersize x filtersize average per channel -> [op_size].
- *   rows, cols = input plane size. LITERAL: integer division (by 49 under MBN_Q_POOL_DIV49).
+ *   rows, cols = input plane size. F32, BF16 and I8: the window is min(filtersize, rows) x min(filtersize, cols), clamped per side,
+ *   so filtersize = max(rows, cols) averages the whole plane of a non-square map (what the net runner passes). LITERAL: integer
+ *   division (by 49 under MBN_Q_POOL_DIV49).
  */
 int mbn_pool(mbn_context *ctx, void *output, const void *inp_image, int rows, int cols, int filtersize,
              int op_size, const mbn_layer_ext *ext);
@@ -250,7 +252,8 @@ int mbn_pool(mbn_context *ctx, void *output, const void *inp_image, int rows, in
  * the two 112x112x32 intermediates never reach HBM (MobileNet.c:240-498 does three launches and six PCIe copies).
  * fp32 NHWC only; image [batch][res][res][3], out [batch][res/2][res/2][c3]; filters in the layouts of the separate
  * calls (w1 [3][3][3][c1], wd [3][3][c1], wp [c3][c1]). Returns MBN_EUNSUPPORTED unless (c1, c3) = (32, 64) (alpha = 1) or
- * (16, 32) (alpha = 0.5) and res is a multiple of 32 — callers then issue the three layer calls instead. */
+ * (16, 32) (alpha = 0.5) and res is a multiple of 32 — callers then issue the three layer calls instead.
+ * mbn_stem_fused, _u8 and _ex are mbn_stem_fused_hw with rows = cols = res. */
 int mbn_stem_fused(mbn_context *ctx, void *out, const void *image, const void *w1, const void *s1, const void *b1,
                    const void *wd, const void *s2, const void *b2, const void *wp, const void *s3, const void *b3,
                    int batch, int res, int c1, int c3, void *stream);
@@ -269,6 +272,11 @@ int mbn_stem_fused_u8(mbn_context *ctx, void *out, const void *image_u8, const v
 int mbn_stem_fused_ex(mbn_context *ctx, void *out, const void *image, const void *w1, const void *s1, const void *b1,
                       const void *wd, const void *s2, const void *b2, const void *wp, const void *s3, const void *b3,
                       int batch, int res, int c1, int c3, int flags, void *stream);
+/* rows x cols images: image [batch][rows][cols][3] (fp32, or uint8 with MBN_STEM_IN_U8), out [batch][rows/2][cols/2][c3]; both sides
+ * multiples of 32, otherwise as mbn_stem_fused_ex (MBN_EUNSUPPORTED outside the envelope). */
+int mbn_stem_fused_hw(mbn_context *ctx, void *out, const void *image, const void *w1, const void *s1, const void *b1,
+                      const void *wd, const void *s2, const void *b2, const void *wp, const void *s3, const void *b3,
+                      int batch, int rows, int cols, int c1, int c3, int flags, void *stream);
 
 /* Fused block: a depthwise 3x3 (stride 1 or 2) + pointwise 1x1 pair of the sequence (the pairs L4-5 ...
  * L26-27, MobileNet.c:322-2599; kernel.cl:62-92 + 94-114) in one kernel, each stage followed by its folded-BN
@@ -431,7 +439,8 @@ typedef struct mbn_layer_desc {
 #define MBN_MAX_LAYERS 32
 typedef struct mbn_plan {
     int32_t  n_layers;          /* 29 */
-    int32_t  res;               /* input resolution (224, 192, 160, 128 or any multiple of 32) */
+    int32_t  res;               /* input side of a square plan (224, 192, 160, 128 or any multiple of 32); 0 for a non-square plan:
+                                 * the input is always layer[0].in_rows x layer[0].in_cols */
     float    alpha;             /* width multiplier */
     int32_t  classes;           /* 1000 */
     int64_t  blob_floats;       /* size of the packed, BN-folded parameter blob */
@@ -441,6 +450,11 @@ typedef struct mbn_plan {
 
 /* MobileNet.c:13-26 + SURVEY §2.1 table, parameterised: channels = max(8, int(c*alpha)), sizes from res. */
 int  mbn_plan_build(float alpha, int res, int classes, mbn_plan *plan);
+/* The same for rows x cols images (Keras input_shape = (rows, cols, 3)): every layer's height and width follow their own side, pad_top
+ * from the rows, pad_left from the cols, max_act_floats from h * w. Both sides must be multiples of 32 in [32, 4096] (MBN_EUNSUPPORTED /
+ * MBN_EINVAL as mbn_plan_build). The blob layout and every offset do not depend on the input size. plan->res = rows when rows == cols
+ * (mbn_plan_build(a, r, c) is mbn_plan_build_hw(a, r, r, c), byte for byte), 0 otherwise. */
+int  mbn_plan_build_hw(float alpha, int rows, int cols, int classes, mbn_plan *plan);
 
 /* int8 inference mode (MBN_DT_I8). The arithmetic, normative (tests/test_int8_*.py reproduce it bit for bit):
  *   activations  uint8 NHWC, zero point 0, real value = q * s_l with one fp32 scale per layer. Every conv / depthwise / pointwise layer
@@ -489,6 +503,8 @@ typedef struct mbn_weights {
  * conv_preds by name, checks every shape against the plan, folds BatchNorm (eps = 1e-3) into per-channel
  * scale/shift, repacks HWIO -> kernel layouts (pointwise -> [Cout][Cin]). alpha <= 0 => infer from conv1. */
 int  mbn_weights_from_h5(const char *path, float alpha, int res, mbn_weights *w);
+/* The same with a rows x cols plan (mbn_plan_build_hw); rows <= 0 => 224, cols <= 0 => rows. The blob is that of any square load. */
+int  mbn_weights_from_h5_hw(const char *path, float alpha, int rows, int cols, mbn_weights *w);
 /* Deterministic synthetic weights: N(0, 2/fan_in) kernels, BN gamma U[.5,1.5], beta N(0,.1),
  * mean N(0,.1), var U[.5,1.5]; written in Keras layout so the same reader path loads them. */
 int  mbn_weights_synthetic_h5(const char *path, float alpha, int classes, uint64_t seed);
@@ -505,7 +521,7 @@ int  mbn_net_create_from_device_blob(mbn_context *ctx, const mbn_plan *plan, con
                                      int max_batch, mbn_net **net);
 int  mbn_net_destroy(mbn_net *net);
 /* MBN_DT_F32 (default) or MBN_DT_BF16: in bf16 mode the net keeps a bf16 copy of the pointwise/FC filters (made on
- * the device from the fp32 blob), activations are bf16, images stay fp32 [batch][res][res][3], logits stay fp32.
+ * the device from the fp32 blob), activations are bf16, images stay fp32 [batch][rows][cols][3], logits stay fp32.
  * MBN_DT_I8: the net quantizes the fp32 blob with its current activation scales (mbn_quantize_i8; the device blob is downloaded
  * once for that) and uploads the i8 blob; activations are uint8 (layer_output: 1 byte per element), logits stay fp32. Every layer
  * runs as its own launch (no stem, block, resident or pool + FC fusion: mbn_net_launches lists 29 single layers). */
@@ -539,7 +555,7 @@ int  mbn_net_set_graph(mbn_net *net, int enabled);
  * kept, at least 3 layers requested); 0 = always issue the 29 separate layer calls. mbn_net_fused_layers reports how
  * many leading layers the next forward(batch, last_layer) would fuse (0 or 3). */
 int  mbn_net_set_fuse_stem(mbn_net *net, int enabled);
-/* 1 = the `images` handed to mbn_net_forward / _timed / _classify are raw uint8 HWC [batch][res][res][3] (device);
+/* 1 = the `images` handed to mbn_net_forward / _timed / _classify are raw uint8 HWC [batch][rows][cols][3] (device);
  * layer 1 (or the fused stem) normalises them at load (MBN_IO_IN_U8). 0 (default) = fp32 NHWC, already normalised. */
 int  mbn_net_set_input_u8(mbn_net *net, int enabled);
 int  mbn_net_fused_layers(const mbn_net *net, int last_layer, int *count);
