@@ -19,17 +19,10 @@
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f8 __attribute__((ext_vector_type(8)));
-typedef unsigned u4v __attribute__((ext_vector_type(4)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef mbn_f16v f16v;
-
 constexpr int BM = 128, BKF = 32;              // LDS rows are 128 bytes = 32 words = 64 bf16
 constexpr int NCW = 4, NPW = 8;                // consumer / producer waves
 constexpr int NT = 64 * (NCW + NPW);
 constexpr int CMAX = MBN_CMAX;
-constexpr unsigned OOB = MBN_OOB;
 
 struct BArgs {
     __bf16 *out;
@@ -40,28 +33,6 @@ struct BArgs {
     unsigned in_bytes;
     unsigned wo_m, wo_s, ho_m, ho_s;   // floor(v / wo) = umulhi(v, wo_m) >> wo_s for v < 2^31 (m == 0: the divisor is 1)
 };
-
-__device__ __forceinline__ int swz(int row, int chunk) { return (row << 5) + (((chunk ^ (row >> 1)) & 7) << 2); }
-__device__ __forceinline__ int xcd_remap(int vb, int nwg)
-{
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = vb & 7;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (vb >> 3);
-}
-__device__ __forceinline__ f8 widen8(u4v p)
-{
-    f8 r;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        r[2 * i] = __builtin_bit_cast(float, p[i] << 16);
-        r[2 * i + 1] = __builtin_bit_cast(float, p[i] & 0xffff0000u);
-    }
-    return r;
-}
-__device__ __forceinline__ f8 ld8(const float *p)
-{
-    const f4 a = *reinterpret_cast<const f4 *>(p), b = *reinterpret_cast<const f4 *>(p + 4);
-    return f8{ a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
-}
 
 template <int S, int BN>
 __global__ __launch_bounds__(NT) void dwpw_bf16(BArgs a)
@@ -96,7 +67,7 @@ __global__ __launch_bounds__(NT) void dwpw_bf16(BArgs a)
         unsigned off[3][XC];
         const __bf16 *b_src[B_LD];
         auto set_tile = [&](int v) __attribute__((always_inline)) {
-            const int lid = xcd_remap(v, nwg);
+            const int lid = mbn_xcd_remap(v, nwg);
             const int n0 = (lid % a.nt) * BN;
             const unsigned m = (unsigned)(lid / a.nt) * BM + 2 * pair;
             const bool mok = m < mtot;
@@ -116,7 +87,7 @@ __global__ __launch_bounds__(NT) void dwpw_bf16(BArgs a)
 #pragma unroll
                 for (int j = 0; j < XC; j++) {
                     const bool ok = rok && (unsigned)(ix0 + j) < (unsigned)a.w;
-                    off[dy][j] = ok ? base + dy * rs + j * cs : OOB;
+                    off[dy][j] = ok ? base + dy * rs + j * cs : MBN_OOB;
                 }
             }
 #pragma unroll
@@ -125,7 +96,7 @@ __global__ __launch_bounds__(NT) void dwpw_bf16(BArgs a)
                 b_src[p] = a.wp + (long)(n0 + row) * a.cin + ((c8 ^ (row >> 1)) & 7) * 8;
             }
         };
-        u4v xr[3][XC];                                                    // the window stays packed (4 VGPRs per vector) ...
+        u4 xr[3][XC];                                                     // the window stays packed (4 VGPRs per vector) ...
         auto ldx = [&](int kc) __attribute__((always_inline)) {
 #pragma unroll
             for (int dy = 0; dy < 3; dy++)
@@ -148,23 +119,23 @@ __global__ __launch_bounds__(NT) void dwpw_bf16(BArgs a)
             for (int dy = 0; dy < 3; dy++) {
                 f8 row[XC];                                               // ... and is widened one row at a time, each vector once
 #pragma unroll
-                for (int j = 0; j < XC; j++) row[j] = widen8(xr[dy][j]);
+                for (int j = 0; j < XC; j++) row[j] = mbn_widen8(xr[dy][j]);
 #pragma unroll
                 for (int dx = 0; dx < 3; dx++) {
-                    const f8 w = ld8(wk + (dy * 3 + dx) * a.cin);
+                    const f8 w = mbn_ld8(wk + (dy * 3 + dx) * a.cin);
                     acc0 = __builtin_elementwise_fma(row[dx], w, acc0);
                     acc1 = __builtin_elementwise_fma(row[dx + S], w, acc1);
                 }
             }
-            const f8 s = ld8(sb_s + kc * 64 + c8 * 8), b = ld8(sb_s + a.cin + kc * 64 + c8 * 8);
+            const f8 s = mbn_ld8(sb_s + kc * 64 + c8 * 8), b = mbn_ld8(sb_s + a.cin + kc * 64 + c8 * 8);
             bf8 o0, o1;
 #pragma unroll
             for (int i = 0; i < 8; i++) {
                 o0[i] = (__bf16)fminf(fmaxf(fmaf(acc0[i], s[i], b[i]), 0.f), 6.f);      // the layer output is rounded to bf16 here
                 o1[i] = (__bf16)fminf(fmaxf(fmaf(acc1[i], s[i], b[i]), 0.f), 6.f);
             }
-            *reinterpret_cast<bf8 *>(a_s0 + buf * BM * BKF + swz(2 * pair, c8)) = o0;
-            *reinterpret_cast<bf8 *>(a_s0 + buf * BM * BKF + swz(2 * pair + 1, c8)) = o1;
+            *reinterpret_cast<bf8 *>(a_s0 + buf * BM * BKF + mbn_swz(2 * pair, c8)) = o0;
+            *reinterpret_cast<bf8 *>(a_s0 + buf * BM * BKF + mbn_swz(2 * pair + 1, c8)) = o1;
         };
 
         int cvb = blockIdx.x, ckc = 0;                 // cursor = the chunk whose input loads are in flight
@@ -207,7 +178,7 @@ __global__ __launch_bounds__(NT) void dwpw_bf16(BArgs a)
     __syncthreads();                                                      // chunk 0 is in buffer 0
     int p = 0;
     for (int vb = blockIdx.x; vb < nwg; vb += gridDim.x) {
-        const int lid = xcd_remap(vb, nwg);
+        const int lid = mbn_xcd_remap(vb, nwg);
         const int n0 = (lid % a.nt) * BN;
         const unsigned m0 = (unsigned)(lid / a.nt) * BM;
         f16v acc[MI][NI];
@@ -224,9 +195,9 @@ __global__ __launch_bounds__(NT) void dwpw_bf16(BArgs a)
                 const int chunk = 2 * g + lh;                             // lane half h holds k = 16g + 8h .. +7 of the 64-wide chunk
                 f4 av[MI], bv[NI];
 #pragma unroll
-                for (int mi = 0; mi < MI; mi++) av[mi] = *reinterpret_cast<const f4 *>(As + swz(wm + mi * 32 + li, chunk));
+                for (int mi = 0; mi < MI; mi++) av[mi] = *reinterpret_cast<const f4 *>(As + mbn_swz(wm + mi * 32 + li, chunk));
 #pragma unroll
-                for (int ni = 0; ni < NI; ni++) bv[ni] = *reinterpret_cast<const f4 *>(Bs + swz(wn + ni * 32 + li, chunk));
+                for (int ni = 0; ni < NI; ni++) bv[ni] = *reinterpret_cast<const f4 *>(Bs + mbn_swz(wn + ni * 32 + li, chunk));
 #pragma unroll
                 for (int mi = 0; mi < MI; mi++)
 #pragma unroll

@@ -20,19 +20,12 @@
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f8 __attribute__((ext_vector_type(8)));
-typedef unsigned u4v __attribute__((ext_vector_type(4)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef mbn_f16v f16v;
-
 constexpr int BKF = 32;                        // LDS rows are 128 bytes = 32 words = 64 bf16
 constexpr int BM8 = 128;                       // rows of the 8-wave tile (2 waves per SIMD, 256 VGPRs each); the 4-wave form (two workgroups per CU): 64
 constexpr int BM_H32 = 256;                    // rows of the Cin = 32 tile (H32: four lanes per pixel pair): shared by the kernel and its launcher
 constexpr int CMAX4 = 256, NOUT4 = 256;        // LDS-resident constants of the 4-wave form (61 KB per workgroup)
 constexpr int NOUT_G = MBN_COUT_MAX;           // widest pointwise output whose scale/shift the LDS copy holds
 constexpr int CMAX_G = MBN_CMAX;               // largest Cin (depthwise constants resident in LDS: 44 KB)
-constexpr unsigned OOB = MBN_OOB;              // byte offset beyond any supported tensor: the load returns zeros
 
 struct DwPw2Args {
     __bf16 *out;
@@ -50,40 +43,6 @@ struct DwPw2Args {
     int fast_off;           // launcher: 1 = the FO instantiation (tile offsets in their full-rate form, as in mbn_f32_dwpw2.hip: input < 0x70000000 bytes)
     float inv_wo, inv_ho;   // 1 / wo, 1 / ho
 };
-
-__device__ __forceinline__ int swz(int row, int chunk) { return (row << 5) + (((chunk ^ (row >> 1)) & 7) << 2); }
-__device__ __forceinline__ f8 widen8(u4v p)
-{
-    f8 r;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        r[2 * i] = __builtin_bit_cast(float, p[i] << 16);
-        r[2 * i + 1] = __builtin_bit_cast(float, p[i] & 0xffff0000u);
-    }
-    return r;
-}
-__device__ __forceinline__ f8 ld8(const float *p)
-{
-    const f4 a = *reinterpret_cast<const f4 *>(p), b = *reinterpret_cast<const f4 *>(p + 4);
-    return f8{ a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
-}
-__device__ __forceinline__ int xcd_remap(int vb, int nwg)
-{
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = vb & 7;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (vb >> 3);
-}
-
-// Workgroup barrier with the waits spelled out. __syncthreads() is a workgroup-scope fence over every address space: with
-// global loads in flight for the NEXT chunk the waitcnt pass drains them (s_waitcnt vmcnt(0)) in front of every barrier
-// (also with the "local"-only fence form), which serialises the prefetch with the hand-over. Here: wait until all but
-// the VM_LEFT youngest vector-memory operations are done (= the LDS-DMA of the filter chunk has landed, the x-window
-// loads issued after it may still fly), until this wave's own LDS writes are done (lgkmcnt(0)), then s_barrier. The asm
-// is volatile with a memory clobber, so the compiler moves no LDS or global access across it.
-template <int VM_LEFT>
-__device__ __forceinline__ void lds_barrier()
-{
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(VM_LEFT) : "memory");
-}
 
 // pointwise filter chunk -> LDS, buffer form (a __device__ function: see mbn_f32_pw.hip lds_dma_rows)
 template <int B_LD, int NT>
@@ -157,12 +116,12 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_bf16(DwPw2Args a)
     const __amdgpu_buffer_rsrc_t irsrc = mbn_make_rsrc(a.in, a.in_bytes);
     const __amdgpu_buffer_rsrc_t wrsrc = mbn_make_rsrc(a.wp, a.wp_bytes);
     const __amdgpu_buffer_rsrc_t orsrc = mbn_make_rsrc(a.out, (unsigned)(a.m * a.cout * 2));
-    const int aw0 = swz(2 * pair, c4), aw1 = swz(2 * pair + 1, c4);           // A-tile slots this lane writes
+    const int aw0 = mbn_swz(2 * pair, c4), aw1 = mbn_swz(2 * pair + 1, c4);   // A-tile slots this lane writes
     int fr_a[4], fr_b[4];                                                       // fragment slots this lane reads
 #pragma unroll
     for (int g = 0; g < 4; g++) {
-        fr_a[g] = swz(wm + li, 2 * g + lh);
-        fr_b[g] = swz(wn + li, 2 * g + lh);
+        fr_a[g] = mbn_swz(wm + li, 2 * g + lh);
+        fr_b[g] = mbn_swz(wn + li, 2 * g + lh);
     }
     unsigned b_vo[B_LD];                                                        // filter piece offsets: fixed for the kernel, the tile's
 #pragma unroll                                                                  // column origin and the chunk go into the scalar offset
@@ -170,7 +129,7 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_bf16(DwPw2Args a)
         const int row = (p * NT + tid) >> 3;
         // channel-paired column blocks (mbn_epilogue.h): LDS filter row `row` holds output channel mbn_pair_channel(row)
         const unsigned kch = (unsigned)(((c8 ^ (row >> 1)) & 7) * 8);                   // first k of this 16-byte piece
-        b_vo[p] = kch < (unsigned)a.cin ? ((unsigned)mbn_pair_channel(row) * (unsigned)a.cin + kch) * 2u : OOB;
+        b_vo[p] = kch < (unsigned)a.cin ? ((unsigned)mbn_pair_channel(row) * (unsigned)a.cin + kch) * 2u : MBN_OOB;
     }
     const bool cok = H32 || c4 * 8 < a.cin;                                            // this lane's 8 channels exist (false only for Cin = 32, c4 >= 4)
     const float *wk = wd_s + c4 * 8;                                           // depthwise taps of this lane's 8 channels (+ kc*64 + tap*cin)
@@ -193,7 +152,7 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_bf16(DwPw2Args a)
 #pragma unroll
             for (int j = 0; j < XC; j++) {
                 const bool ok = rok && (unsigned)(ix0 + j) < (unsigned)a.w;
-                off[dy][j] = ok ? base + dy * rs + j * cs : OOB;
+                off[dy][j] = ok ? base + dy * rs + j * cs : MBN_OOB;
             }
         }
     };
@@ -228,7 +187,7 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_bf16(DwPw2Args a)
         if constexpr (FO) set_offsets_fast(m0);
         else set_offsets_general(m0);
     };
-    u4v xr[3][XC];                                                            // the window stays packed (4 VGPRs per vector)
+    u4 xr[3][XC];                                                             // the window stays packed (4 VGPRs per vector)
     auto ldx = [&](int kc) __attribute__((always_inline)) {
 #pragma unroll
         for (int dy = 0; dy < 3; dy++)
@@ -246,15 +205,15 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_bf16(DwPw2Args a)
         for (int dy = 0; dy < 3; dy++) {
             f8 row[XC];
 #pragma unroll
-            for (int j = 0; j < XC; j++) row[j] = widen8(xr[dy][j]);
+            for (int j = 0; j < XC; j++) row[j] = mbn_widen8(xr[dy][j]);
 #pragma unroll
             for (int dx = 0; dx < 3; dx++) {
-                const f8 w = ld8(wk + kc * 64 + (dy * 3 + dx) * a.cin);
+                const f8 w = mbn_ld8(wk + kc * 64 + (dy * 3 + dx) * a.cin);
                 acc0 = __builtin_elementwise_fma(row[dx], w, acc0);
                 acc1 = __builtin_elementwise_fma(row[dx + S], w, acc1);
             }
         }
-        const f8 sc = ld8(sk + kc * 64), sh = ld8(sk + a.cin + kc * 64);
+        const f8 sc = mbn_ld8(sk + kc * 64), sh = mbn_ld8(sk + a.cin + kc * 64);
         bf8 o0, o1;
 #pragma unroll
         for (int i = 0; i < 8; i++) {
@@ -262,7 +221,7 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_bf16(DwPw2Args a)
             o1[i] = (__bf16)fminf(fmaxf(fmaf(acc1[i], sc[i], sh[i]), 0.f), 6.f);
         }
         if (!cok) {                               // padded channels (Cin = 32): exact zeros, whatever the LDS words behind the taps held
-            const u4v z = { 0u, 0u, 0u, 0u };
+            const u4 z = { 0u, 0u, 0u, 0u };
             o0 = __builtin_bit_cast(bf8, z);
             o1 = o0;
         }
@@ -280,8 +239,8 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_bf16(DwPw2Args a)
     [[maybe_unused]] int fr16_a[2], fr16_b[2];
 #pragma unroll
     for (int kg = 0; kg < 2; kg++) {
-        fr16_a[kg] = swz(wm + (lane & 15), 4 * kg + (lane >> 4));
-        fr16_b[kg] = swz(wn + (lane & 15), 4 * kg + (lane >> 4));
+        fr16_a[kg] = mbn_swz(wm + (lane & 15), 4 * kg + (lane >> 4));
+        fr16_b[kg] = mbn_swz(wn + (lane & 15), 4 * kg + (lane >> 4));
     }
     auto ldfrag = [&](const int buf, int g, int slot) __attribute__((always_inline)) {
         if constexpr (M16) {
@@ -363,7 +322,7 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_bf16(DwPw2Args a)
     int vbD, kD, n0D; unsigned m0D;
     bool validD;
     auto origin = [&](int vb, unsigned &m0, int &n0) __attribute__((always_inline)) {
-        const int lid = xcd_remap(vb, nwg);
+        const int lid = mbn_xcd_remap(vb, nwg);
         n0 = (lid % a.nt) * BN;
         m0 = (unsigned)(lid / a.nt) * BM;
     };
@@ -385,8 +344,8 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_bf16(DwPw2Args a)
         ldx(kD);
     }
     zero_acc();
-    if (validD) lds_barrier<NX>();        // filter chunk 0 landed; the NX newer loads may fly
-    else lds_barrier<0>();
+    if (validD) mbn_waitcnt<NX>();        // filter chunk 0 landed; the NX newer loads may fly
+    else mbn_waitcnt<0>();
 
     // One chunk step with the MFMA chunk in buffer P (a literal at both call sites).
     // Returns false when the sequence is finished.
@@ -425,8 +384,8 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_bf16(DwPw2Args a)
         mfma_group(1);                                                                                                  \
         }                                                                                                               \
         }                                                                                                               \
-        if (validL) lds_barrier<NX>();                                                                                  \
-        else lds_barrier<0>();                                                                                          \
+        if (validL) mbn_waitcnt<NX>();                                                                                  \
+        else mbn_waitcnt<0>();                                                                                          \
         /* Cout = 64 (mod 128), round 5: a wave whose 64-column group lies past Cout multiplied zeros (its filter rows are beyond the descriptor: the  */ \
         /* LDS-DMA wrote zeros) and stores nothing. Block 6-7 of the 0.5x network (64 -> 64 channels) is inside the envelope with it.               */ \
         if (kM == nk - 1 && !(dbg & 4) && n0M + wn < a.cout) {                                                        \

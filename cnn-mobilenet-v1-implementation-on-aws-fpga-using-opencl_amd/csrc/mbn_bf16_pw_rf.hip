@@ -23,16 +23,9 @@
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef unsigned u4v __attribute__((ext_vector_type(4)));
-typedef unsigned u2v __attribute__((ext_vector_type(2)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-
 constexpr int RF_TP = 32;                      // pixels per stage
 constexpr int RF_ST = 4;                       // stages in the ring
 constexpr int RF_CW = 256;                     // output channels per workgroup (8 waves x 32)
-constexpr unsigned OOB = 0xF0000000u;          // a buffer offset past every tensor in the envelope: the load writes zeros into LDS
 
 struct RfArgs {
     __bf16 *out;
@@ -42,15 +35,6 @@ struct RfArgs {
     int n, mt, nh, gq;      // output channels; 32-pixel tiles; channel slices (N / 256); pixel streams per XCD
     int dbg;                // lab ablations (exp0 = 700 + bits): 1 no LDS-DMA after the prologue, 2 no fragment reads / MFMAs, 4 no stores (timing only)
 };
-
-__device__ __forceinline__ float relu6(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
-
-// all but the VM_LEFT youngest vector-memory operations of this wave are done, its LDS reads are done, then s_barrier (asm: nothing moves across it)
-template <int VM_LEFT>
-__device__ __forceinline__ void rf_barrier()
-{
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(VM_LEFT) : "memory");
-}
 
 template <int K>
 __global__ __launch_bounds__(512) void pw_rf_bf16(RfArgs a)
@@ -89,7 +73,7 @@ __global__ __launch_bounds__(512) void pw_rf_bf16(RfArgs a)
         const long p0 = (long)(t0 + ti * tstep) * RF_TP + wave_u * RPW;
 #pragma unroll
         for (int p = 0; p < RPW; p++) {
-            const unsigned vo = (ti < nt && p0 + p < a.m) ? (unsigned)(p0 + p) * (unsigned)(K * 2) + (unsigned)lane * 16u : OOB;
+            const unsigned vo = (ti < nt && p0 + p < a.m) ? (unsigned)(p0 + p) * (unsigned)(K * 2) + (unsigned)lane * 16u : MBN_OOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(irsrc, (__attribute__((address_space(3))) void *)(st + (wave_u * RPW + p) * ROWB), 16, vo, 0, 0, 0);
         }
     };
@@ -101,13 +85,13 @@ __global__ __launch_bounds__(512) void pw_rf_bf16(RfArgs a)
 
     // ---- the wave's filter rows: channels c0 + 16 blk + j16, k = 32 g + 8 q .. + 7 (the A operand of step g, block blk)
     const int c0 = half * RF_CW + 32 * wave_u;
-    u4v wfr[KG][2];
+    u4 wfr[KG][2];
     {
         const __bf16 *wrow = a.filt + (size_t)(c0 + j16) * K + 8 * q;
 #pragma unroll
         for (int g = 0; g < KG; g++)
 #pragma unroll
-            for (int b = 0; b < 2; b++) wfr[g][b] = *reinterpret_cast<const u4v *>(wrow + (size_t)(16 * b) * K + 32 * g);
+            for (int b = 0; b < 2; b++) wfr[g][b] = *reinterpret_cast<const u4 *>(wrow + (size_t)(16 * b) * K + 32 * g);
     }
     // C/D: register r of block (blk, pb) = channel c0 + 16 blk + 4 q + r of pixel 16 pb + j16
     f4 sc[2], sh[2];
@@ -124,17 +108,17 @@ __global__ __launch_bounds__(512) void pw_rf_bf16(RfArgs a)
 
     // BN + ReLU6 + rounding of one 16-pixel block of the PREVIOUS tile and its store: issued between the matrix instructions of the current one
     auto epilogue = [&](const f4 (&pacc)[2][2], int pb, long pix0) __attribute__((always_inline)) {
-        u2v d[2];
+        u2 d[2];
 #pragma unroll
         for (int b = 0; b < 2; b++) {
             const f4 v = pacc[b][pb];
-            d[b] = __builtin_bit_cast(u2v, bf4{ (__bf16)relu6(fmaf(v.x, sc[b].x, sh[b].x)), (__bf16)relu6(fmaf(v.y, sc[b].y, sh[b].y)),
-                                                 (__bf16)relu6(fmaf(v.z, sc[b].z, sh[b].z)), (__bf16)relu6(fmaf(v.w, sc[b].w, sh[b].w)) });
+            d[b] = __builtin_bit_cast(u2, bf4{ (__bf16)mbn_relu6(fmaf(v.x, sc[b].x, sh[b].x)), (__bf16)mbn_relu6(fmaf(v.y, sc[b].y, sh[b].y)),
+                                                 (__bf16)mbn_relu6(fmaf(v.z, sc[b].z, sh[b].z)), (__bf16)mbn_relu6(fmaf(v.w, sc[b].w, sh[b].w)) });
         }
         const auto lo = __builtin_amdgcn_permlane16_swap(d[0].x, d[1].x, false, false);
         const auto hi = __builtin_amdgcn_permlane16_swap(d[0].y, d[1].y, false, false);
         const unsigned po = (unsigned)(pix0 + 16 * pb) * (unsigned)(a.n * 2) + obase;          // past M: beyond the buffer's range, the store is dropped
-        if (!(dbg & 4)) __builtin_amdgcn_raw_buffer_store_b128(u4v{ lo[0], hi[0], lo[1], hi[1] }, orsrc, po, 0, 0);
+        if (!(dbg & 4)) __builtin_amdgcn_raw_buffer_store_b128(u4{ lo[0], hi[0], lo[1], hi[1] }, orsrc, po, 0, 0);
     };
 
     f4 pacc[2][2];                                                       // the previous tile's sums, waiting for their epilogue
@@ -148,9 +132,9 @@ __global__ __launch_bounds__(512) void pw_rf_bf16(RfArgs a)
         // tile ti has landed for every wave, and every wave is done reading tile ti - 1 (whose stage the DMA below refills).
         // Issued behind DMA(ti), steady state: stores(ti-4), DMA(ti+1), stores(ti-3), DMA(ti+2), stores(ti-2) = 3 x NSTORE + 2 x RPW; fewer in the first four
         // steps (the first waits for everything: the filter rows were requested behind the first three stages)
-        if (ti == 0) rf_barrier<0>();
-        else if (ti < 4) rf_barrier<2 * RPW>();
-        else rf_barrier<3 * NSTORE + 2 * RPW>();
+        if (ti == 0) mbn_waitcnt<0>();
+        else if (ti < 4) mbn_waitcnt<2 * RPW>();
+        else mbn_waitcnt<3 * NSTORE + 2 * RPW>();
         if (!(dbg & 1)) dma(ti + 3);
 
         const char *st = lds + (ti & (RF_ST - 1)) * STB;
@@ -162,9 +146,9 @@ __global__ __launch_bounds__(512) void pw_rf_bf16(RfArgs a)
 #pragma unroll
         for (int g = 0; g < KG; g++) {
             if (!(dbg & 2)) {
-                u4v yf[2];
+                u4 yf[2];
 #pragma unroll
-                for (int pb = 0; pb < 2; pb++) yf[pb] = *reinterpret_cast<const u4v *>(st + bfrag + (unsigned)(pb * 16 * ROWB + g * 64));
+                for (int pb = 0; pb < 2; pb++) yf[pb] = *reinterpret_cast<const u4 *>(st + bfrag + (unsigned)(pb * 16 * ROWB + g * 64));
 #pragma unroll
                 for (int b = 0; b < 2; b++)
 #pragma unroll
@@ -196,7 +180,7 @@ static int mbn_bf16_pw_rf_eligible(const mbn_call &c, const void *out, const voi
     if (cin != 512 || op_size < RF_CW || (op_size % RF_CW) != 0 || m < 1) return 0;
     if (((uintptr_t)in % 16) || ((uintptr_t)filt % 16) || ((uintptr_t)out % 8) || ((uintptr_t)c.scale % 16) || ((uintptr_t)c.shift % 16)) return 0;
     // 32-bit byte offsets: the input below the out-of-range marker, the output with a tile of head room below 4 GiB (a ragged last tile's rows past M must not wrap)
-    if ((double)m * cin * 2 >= (double)OOB || ((double)m + 64.0) * op_size * 2 >= 4294967296.0) return 0;
+    if ((double)m * cin * 2 >= (double)MBN_OOB || ((double)m + 64.0) * op_size * 2 >= 4294967296.0) return 0;
     const int nh = op_size / RF_CW;
     if (c.ctx->num_cus < 8 * nh) return 0;
     return 1;

@@ -21,10 +21,6 @@
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef mbn_f16v f16v;
-
 constexpr int BN = 128, BKE = 64, BKF = 32;                // k-tile: 64 bf16 = 128-byte rows = 32 LDS words
 constexpr int NT = 512;
 constexpr int WN = 64, NI = 2, WAVES_N = BN / WN;
@@ -49,46 +45,32 @@ struct RingArgs {
     int k, n, mt, nt;
 };
 
-__device__ __forceinline__ int swz(int row, int chunk) { return (row << 5) + (((chunk ^ (row >> 1)) & 7) << 2); }
-__device__ __forceinline__ int xcd_remap(int vb, int nwg)
-{
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = vb & 7;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (vb >> 3);
-}
-
-// wait until all but the VM_LEFT youngest vector-memory operations of this wave are done and its LDS traffic is done, then
-// s_barrier (asm: no LDS or global access is moved across it; __syncthreads would drain vmcnt(0), see mbn_f32_dwpw2.hip)
-template <int VM_LEFT>
-__device__ __forceinline__ void ring_barrier()
-{
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(VM_LEFT) : "memory");
-}
 // nd = k-tiles issued after the awaited one (0..2), ne = epilogues issued after it (0..3)
 template <int NDMA, int NST>
 __device__ __forceinline__ void ring_barrier_dyn(int nd, int ne)
 {
     if constexpr (3 * NST + 2 * NDMA > 63) {               // the 64x64 shape: nk >= AHEAD = 2, so nd <= 1 and ne <= 1
         switch (ne * 2 + nd) {
-        case 0: ring_barrier<0>(); break;
-        case 1: ring_barrier<NDMA>(); break;
-        case 2: ring_barrier<NST>(); break;
-        default: ring_barrier<NST + NDMA>(); break;
+        case 0: mbn_waitcnt<0>(); break;
+        case 1: mbn_waitcnt<NDMA>(); break;
+        case 2: mbn_waitcnt<NST>(); break;
+        default: mbn_waitcnt<NST + NDMA>(); break;
         }
         return;
     } else
     switch (ne * 3 + nd) {
-    case 0: ring_barrier<0>(); break;
-    case 1: ring_barrier<NDMA>(); break;
-    case 2: ring_barrier<2 * NDMA>(); break;
-    case 3: ring_barrier<NST>(); break;
-    case 4: ring_barrier<NST + NDMA>(); break;
-    case 5: ring_barrier<NST + 2 * NDMA>(); break;
-    case 6: ring_barrier<2 * NST>(); break;
-    case 7: ring_barrier<2 * NST + NDMA>(); break;
-    case 8: ring_barrier<2 * NST + 2 * NDMA>(); break;
-    case 9: ring_barrier<3 * NST>(); break;
-    case 10: ring_barrier<3 * NST + NDMA>(); break;
-    default: ring_barrier<3 * NST + 2 * NDMA>(); break;
+    case 0: mbn_waitcnt<0>(); break;
+    case 1: mbn_waitcnt<NDMA>(); break;
+    case 2: mbn_waitcnt<2 * NDMA>(); break;
+    case 3: mbn_waitcnt<NST>(); break;
+    case 4: mbn_waitcnt<NST + NDMA>(); break;
+    case 5: mbn_waitcnt<NST + 2 * NDMA>(); break;
+    case 6: mbn_waitcnt<2 * NST>(); break;
+    case 7: mbn_waitcnt<2 * NST + NDMA>(); break;
+    case 8: mbn_waitcnt<2 * NST + 2 * NDMA>(); break;
+    case 9: mbn_waitcnt<3 * NST>(); break;
+    case 10: mbn_waitcnt<3 * NST + NDMA>(); break;
+    default: mbn_waitcnt<3 * NST + 2 * NDMA>(); break;
     }
 }
 
@@ -136,8 +118,8 @@ __global__ __launch_bounds__(NT) void pw_ring_bf16(RingArgs a)
     int fr_a[4], fr_b[4];
 #pragma unroll
     for (int g = 0; g < 4; g++) {
-        fr_a[g] = swz(wm + li, 2 * g + lh);
-        fr_b[g] = swz(wn + li, 2 * g + lh);
+        fr_a[g] = mbn_swz(wm + li, 2 * g + lh);
+        fr_b[g] = mbn_swz(wn + li, 2 * g + lh);
     }
 
     // ---- issue cursor (runs AHEAD k-tiles in front of the compute cursor)
@@ -145,7 +127,7 @@ __global__ __launch_bounds__(NT) void pw_ring_bf16(RingArgs a)
     int islot = 0;                                                       // ring slot of the next k-tile to issue
     unsigned a_vo[LDA], b_vo[LDB];
     auto set_issue_tile = [&](int vb) __attribute__((always_inline)) {
-        const int lid = xcd_remap(vb, nwg);
+        const int lid = mbn_xcd_remap(vb, nwg);
         const int n0 = (lid % a.nt) * BN;
         const long m0 = (long)(lid / a.nt) * BM;
 #pragma unroll
@@ -230,7 +212,7 @@ __global__ __launch_bounds__(NT) void pw_ring_bf16(RingArgs a)
         }
         epi_age++;
         if (++ckt == nk) {
-            const int lid = xcd_remap(cvb, nwg);
+            const int lid = mbn_xcd_remap(cvb, nwg);
             const int n0 = (lid % a.nt) * BN;
             const unsigned m0 = (unsigned)(lid / a.nt) * BM;
             if ((long)m0 + BM <= a.m) mbn_store_relu6_bf16_pair<MI, NI, 0>(orsrc, (unsigned)a.n, m0 + wm, n0 + wn, lane, acc, sc_s, sh_s);

@@ -32,15 +32,8 @@
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2e __attribute__((ext_vector_type(2)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf2e __attribute__((ext_vector_type(2)));
-typedef mbn_f16v f16v;
-
 constexpr int BKE = 64, BKF = 32;                          // k-tile: 64 bf16 = 128-byte rows = 32 LDS words
 constexpr int LDP = 2;                                     // 16-byte pieces per lane per operand per k-tile (both tile shapes)
-constexpr unsigned OOB = 0xF0000000u;                      // a buffer offset past every tensor in the envelope (< 3.75 GiB): the load is dropped
 
 // Two shapes of the same kernel:
 //   <128,128,32,64,3,4>  the form described above: 8 waves, 80 KB, two workgroups per CU
@@ -74,22 +67,6 @@ struct StreamArgs {
     int delay;      // lab (exp0 >= 100): start delay of a workgroup, (exp0 - 100) x 1024 cycles x its phase ((blockIdx / 8) & 3): de-phases the tiles' store bursts
     int stag;       // lab (exp2): 1 = odd waves issue their LDS-DMA behind the second MFMA group instead of ahead of the first, 2 = all waves
 };
-
-__device__ __forceinline__ int swz(int row, int chunk) { return (row << 5) + (((chunk ^ (row >> 1)) & 7) << 2); }
-__device__ __forceinline__ int xcd_remap(int vb, int nwg)
-{
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = vb & 7;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (vb >> 3);
-}
-
-// all but the VM_LEFT youngest vector-memory operations of this wave are done, its LDS reads are done, then s_barrier
-// (asm: nothing is moved across it; __syncthreads() would drain vmcnt(0) while an LDS-DMA is pending)
-template <int VM_LEFT, bool BAR = true>
-__device__ __forceinline__ void stream_barrier()
-{
-    if (BAR) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(VM_LEFT) : "memory");
-    else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(VM_LEFT) : "memory");
-}
 
 template <int NT>
 __device__ __forceinline__ void dma2(__amdgpu_buffer_rsrc_t rsrc, float *slot, const unsigned (&voff)[LDP], int soff, int wave_u)
@@ -139,15 +116,15 @@ __global__ __launch_bounds__(SH::NT, 4) void pw_stream_bf16(StreamArgs a)
     int fr_a[4], fr_b[4];
 #pragma unroll
     for (int g = 0; g < 4; g++) {
-        fr_a[g] = swz(wm + li, 2 * g + lh);
-        fr_b[g] = swz(wn + li, 2 * g + lh);
+        fr_a[g] = mbn_swz(wm + li, 2 * g + lh);
+        fr_b[g] = mbn_swz(wn + li, 2 * g + lh);
     }
     // M16: lane (r = l & 15, q = l >> 4) holds k = 32 kg + 8 q .. + 7 of row r of a 16-row block: chunk 4 kg + q of the 128-byte row
     [[maybe_unused]] int fr16_a[2], fr16_b[2];
 #pragma unroll
     for (int kg = 0; kg < 2; kg++) {
-        fr16_a[kg] = swz(wm + (lane & 15), 4 * kg + (lane >> 4));
-        fr16_b[kg] = swz(wn + (lane & 15), 4 * kg + (lane >> 4));
+        fr16_a[kg] = mbn_swz(wm + (lane & 15), 4 * kg + (lane >> 4));
+        fr16_b[kg] = mbn_swz(wn + (lane & 15), 4 * kg + (lane >> 4));
     }
 
     // ---- issue cursors: the filter runs one k-tile ahead of the compute cursor, the activations two
@@ -161,10 +138,10 @@ __global__ __launch_bounds__(SH::NT, 4) void pw_stream_bf16(StreamArgs a)
     auto set_a_tile = [&](int vb) __attribute__((always_inline)) {
         if (vb >= nwg) {
 #pragma unroll
-            for (int p = 0; p < LDP; p++) a_vo[p] = OOB;
+            for (int p = 0; p < LDP; p++) a_vo[p] = MBN_OOB;
             return;
         }
-        const long m0 = (long)(xcd_remap(vb, nwg) / a.nt) * BM;
+        const long m0 = (long)(mbn_xcd_remap(vb, nwg) / a.nt) * BM;
 #pragma unroll
         for (int p = 0; p < LDP; p++) {
             const int row = (p * NT + tid) >> 3;
@@ -176,10 +153,10 @@ __global__ __launch_bounds__(SH::NT, 4) void pw_stream_bf16(StreamArgs a)
     auto set_b_tile = [&](int vb) __attribute__((always_inline)) {
         if (vb >= nwg) {
 #pragma unroll
-            for (int p = 0; p < LDP; p++) b_vo[p] = OOB;
+            for (int p = 0; p < LDP; p++) b_vo[p] = MBN_OOB;
             return;
         }
-        const int n0 = (xcd_remap(vb, nwg) % a.nt) * BN;
+        const int n0 = (mbn_xcd_remap(vb, nwg) % a.nt) * BN;
 #pragma unroll
         for (int p = 0; p < LDP; p++) {
             const int row = (p * NT + tid) >> 3;
@@ -229,7 +206,7 @@ __global__ __launch_bounds__(SH::NT, 4) void pw_stream_bf16(StreamArgs a)
     }
     int cvb = blockIdx.x, cas = 0, cbs = 0;
     f4 fa_fix = f4{ 0.f, 0.f, 0.f, 0.f };
-    if (ABL & 2) { stream_barrier<0>(); fa_fix = *reinterpret_cast<const f4 *>(lds + fr_a[0]); }
+    if (ABL & 2) { mbn_waitcnt<0>(); fa_fix = *reinterpret_cast<const f4 *>(lds + fr_a[0]); }
     bool prev_end = false;                         // step i-1 ended a tile: its 16 stores were issued after A(i+1)
     // One step. LAST (compile time) = the tile's last k-step: scale/shift loads ahead of the DMA, epilogue behind the MFMAs. The
     // sequence is written as tiles x (nk-1 plain steps + one LAST step) so that the scale/shift registers are defined and
@@ -239,28 +216,28 @@ __global__ __launch_bounds__(SH::NT, 4) void pw_stream_bf16(StreamArgs a)
         constexpr bool LAST = decltype(last_tag)::value;
         constexpr bool LATE = decltype(late_tag)::value;     // this wave issues the step's LDS-DMA behind MFMA group 1 (see the launcher)
         // younger than B(i) at this point: A(i+1) (issued behind B(i) in step i-1 / the prologue), then step i-1's stores
-        if (ABL & 1) stream_barrier<0, !(ABL & 8)>();
-        else if (prev_end && !(ABL & 16)) stream_barrier<LDP * (AHEAD - 1) + NST, !(ABL & 8)>();
-        else stream_barrier<LDP * (AHEAD - 1), !(ABL & 8)>();
-        f2e sc, sh;
-        [[maybe_unused]] f2e sc16[2], sh16[2];
+        if (ABL & 1) mbn_waitcnt<0, !(ABL & 8)>();
+        else if (prev_end && !(ABL & 16)) mbn_waitcnt<LDP * (AHEAD - 1) + NST, !(ABL & 8)>();
+        else mbn_waitcnt<LDP * (AHEAD - 1), !(ABL & 8)>();
+        f2 sc, sh;
+        [[maybe_unused]] f2 sc16[2], sh16[2];
         int n0 = 0;
         unsigned m0 = 0;
         if constexpr (LAST) {                                            // ahead of this step's DMA: see the header
-            const int lid = xcd_remap(cvb, nwg);
+            const int lid = mbn_xcd_remap(cvb, nwg);
             n0 = (lid % a.nt) * BN;
             m0 = (unsigned)(lid / a.nt) * BM;
             if constexpr (M16) {
 #pragma unroll
                 for (int jp = 0; jp < 2; jp++) {
                     const unsigned co16 = (unsigned)(n0 + wn + 32 * jp + 2 * (lane & 15)) * 4u;
-                    sc16[jp] = __builtin_bit_cast(f2e, __builtin_amdgcn_raw_buffer_load_b64(scrsrc, co16, 0, 0));
-                    sh16[jp] = __builtin_bit_cast(f2e, __builtin_amdgcn_raw_buffer_load_b64(shrsrc, co16, 0, 0));
+                    sc16[jp] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(scrsrc, co16, 0, 0));
+                    sh16[jp] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(shrsrc, co16, 0, 0));
                 }
             } else {
             const unsigned co = (unsigned)(n0 + wn + 2 * li) * 4u;
-            sc = __builtin_bit_cast(f2e, __builtin_amdgcn_raw_buffer_load_b64(scrsrc, co, 0, 0));
-            sh = __builtin_bit_cast(f2e, __builtin_amdgcn_raw_buffer_load_b64(shrsrc, co, 0, 0));
+            sc = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(scrsrc, co, 0, 0));
+            sh = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(shrsrc, co, 0, 0));
             }
         }
         if (!(ABL & 1) && !LATE) {
@@ -340,7 +317,7 @@ __global__ __launch_bounds__(SH::NT, 4) void pw_stream_bf16(StreamArgs a)
                 const int c16 = lane & 15, q16 = lane >> 4;
 #pragma unroll
                 for (int jp = 0; jp < NI16 / 2; jp++) {
-                    const f2e s2 = sc16[jp], h2 = sh16[jp];
+                    const f2 s2 = sc16[jp], h2 = sh16[jp];
 #pragma unroll
                     for (int i = 0; i < MI16; i++)
 #pragma unroll
@@ -348,7 +325,7 @@ __global__ __launch_bounds__(SH::NT, 4) void pw_stream_bf16(StreamArgs a)
                             const unsigned ro = m0 + wm + 16 * i + 4 * q16 + r;
                             const float v0 = fminf(fmaxf(fmaf(acc16[i][jp][r], s2.x, h2.x), 0.f), 6.f);
                             const float v1 = fminf(fmaxf(fmaf(acc16[i][jp + NI16 / 2][r], s2.y, h2.y), 0.f), 6.f);
-                            const unsigned v = __builtin_bit_cast(unsigned, bf2e{ (__bf16)v0, (__bf16)v1 });
+                            const unsigned v = __builtin_bit_cast(unsigned, bf2{ (__bf16)v0, (__bf16)v1 });
                             const unsigned off = (ro * (unsigned)a.n + (unsigned)(n0 + wn + 32 * jp + 2 * c16)) * 2u;
                             __builtin_amdgcn_raw_buffer_store_b32(v, orsrc, off, 0, 0);
                         }
@@ -369,7 +346,7 @@ __global__ __launch_bounds__(SH::NT, 4) void pw_stream_bf16(StreamArgs a)
                 const unsigned ro = m0 + wm + mi * 32 + (r & 3) + 8 * (r >> 2);
                 const float v0 = fminf(fmaxf(fmaf(acc[mi][0][r], sc.x, sh.x), 0.f), 6.f);
                 const float v1 = fminf(fmaxf(fmaf(acc[mi][1][r], sc.y, sh.y), 0.f), 6.f);
-                const unsigned v = __builtin_bit_cast(unsigned, bf2e{ (__bf16)v0, (__bf16)v1 });
+                const unsigned v = __builtin_bit_cast(unsigned, bf2{ (__bf16)v0, (__bf16)v1 });
                 const unsigned soff = (ro * (unsigned)a.n + (unsigned)(n0 + wn)) * 2u;
                 if (ABL & 16) asm volatile("" ::"v"(v));
                 else if (inside) __builtin_amdgcn_raw_buffer_store_b32(v, orsrc, lane_off, soff, 0);
@@ -418,7 +395,7 @@ static bool stream_common_ok(const mbn_call &c, const void *out, const void *in,
         return false;
     // the output bound leaves a whole 256-row tile of head room: a ragged last tile's rows past M reach the range check as 32-bit byte offsets
     // (row * N + col) * 2, which must not wrap into the first rows of the output
-    if ((double)m * cin * 2 >= (double)OOB || ((double)m + 256.0) * op_size * 2 >= 4294967296.0 || (double)op_size * cin * 2 >= (double)OOB) return false;
+    if ((double)m * cin * 2 >= (double)MBN_OOB || ((double)m + 256.0) * op_size * 2 >= 4294967296.0 || (double)op_size * cin * 2 >= (double)MBN_OOB) return false;
     return true;
 }
 

@@ -37,12 +37,6 @@
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef unsigned u4v __attribute__((ext_vector_type(4)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf2e __attribute__((ext_vector_type(2)));
-typedef mbn_f16v f16v;
-
 constexpr int TM = 196;                 // rows of a tile that are stored
 constexpr int MI = 7;                   // MFMA row blocks computed (224 rows)
 constexpr int BN = 256;                 // 8 waves x 32 columns
@@ -51,7 +45,6 @@ constexpr int NT = 512;
 constexpr int SLOT_ROWS = 256;          // 32 pieces of 8 rows per slot; pieces of rows >= 224 are issued out of range (dropped)
 constexpr int AF = SLOT_ROWS * BKF;     // floats per slot (32 KB)
 constexpr int ASLOTS = 3;                 // ring slots: the activations run 2 k-tiles ahead of the compute cursor, the filter 1 (two register sets)
-constexpr unsigned OOB = 0xF0000000u;   // past every tensor in the envelope (< 3.75 GiB): the buffer unit drops the access
 
 struct WideArgs {
     __bf16 *out;
@@ -62,23 +55,9 @@ struct WideArgs {
     int k, n, mt, nt;
 };
 
-__device__ __forceinline__ int swz(int row, int chunk) { return (row << 5) + (((chunk ^ (row >> 1)) & 7) << 2); }
-__device__ __forceinline__ int xcd_remap(int vb, int nwg)
-{
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = vb & 7;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (vb >> 3);
-}
-
-template <int VM_LEFT, bool BAR = true>
-__device__ __forceinline__ void wide_barrier()
-{
-    if (BAR) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(VM_LEFT) : "memory");
-    else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(VM_LEFT) : "memory");
-}
-
 // ---- filter packing: [N][K] bf16 -> [N/256][K/64][wave 8][k16 step 4][lane 64][8 bf16]; lane (c = l & 31, h = l >> 5) holds
 // filt[n0 + 32 w + c][k0 + 16 s + 8 h + j], j = 0..7: the B operand of v_mfma_f32_32x32x16_bf16 for the wave's 32 columns.
-__global__ __launch_bounds__(256) void pack_filter_bf16(u4v *__restrict__ dst, const __bf16 *__restrict__ src, int n, int k)
+__global__ __launch_bounds__(256) void pack_filter_bf16(u4 *__restrict__ dst, const __bf16 *__restrict__ src, int n, int k)
 {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;          // one 16-byte chunk per thread
     const long total = (long)n * k / 8;
@@ -92,7 +71,7 @@ __global__ __launch_bounds__(256) void pack_filter_bf16(u4v *__restrict__ dst, c
     const int nk = k / BKE;
     const int kt = (int)(q % nk), nt = (int)(q / nk);
     const int col = nt * BN + w * 32 + (lane & 31), kk = kt * BKE + s * 16 + (lane >> 5) * 8;
-    dst[t] = *reinterpret_cast<const u4v *>(src + (long)col * k + kk);
+    dst[t] = *reinterpret_cast<const u4 *>(src + (long)col * k + kk);
 }
 
 // ABL (lab build; 0 in the shipped kernel): timing ablations, results are wrong with any bit set —
@@ -118,7 +97,7 @@ __global__ __launch_bounds__(NT, 2) void pw_wide_bf16(WideArgs a)
     // fragment addresses: row = mi * 32 + li, chunk = 2 s + lh; (row >> 1) & 7 does not depend on mi
     int fr[4];
 #pragma unroll
-    for (int s = 0; s < 4; s++) fr[s] = swz(li, 2 * s + lh);
+    for (int s = 0; s < 4; s++) fr[s] = mbn_swz(li, 2 * s + lh);
 
     // ---- tile descriptors of the issue cursors. Piece q of wave w covers slot rows 8 (w + 8 q) .. + 7: lane l loads row
     // 8 p + (l >> 3), source chunk (l & 7) ^ ((row >> 1) & 7) (the swizzle goes on the source: the LDS image is lane-linear).
@@ -129,16 +108,16 @@ __global__ __launch_bounds__(NT, 2) void pw_wide_bf16(WideArgs a)
     int b_vb = blockIdx.x, b_kt = 0;
     unsigned b_so = 0;                      // byte offset of (n-tile, k-tile 0, this wave) in the packed image
     auto set_a_tile = [&](int vb) __attribute__((always_inline)) {
-        const long m0 = vb < nwg ? (long)(xcd_remap(vb, nwg) / a.nt) * TM : 0;
+        const long m0 = vb < nwg ? (long)(mbn_xcd_remap(vb, nwg) / a.nt) * TM : 0;
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const int row = 8 * (wave_u + 8 * q) + (lane >> 3);
             const long gm = m0 + row;
-            a_vo[q] = (vb < nwg && row < 32 * MI && gm < a.m) ? ((unsigned)gm * (unsigned)a.k + (unsigned)((((lane & 7) ^ (row >> 1)) & 7) * 8)) * 2u : OOB;
+            a_vo[q] = (vb < nwg && row < 32 * MI && gm < a.m) ? ((unsigned)gm * (unsigned)a.k + (unsigned)((((lane & 7) ^ (row >> 1)) & 7) * 8)) * 2u : MBN_OOB;
         }
     };
     auto set_b_tile = [&](int vb) __attribute__((always_inline)) {
-        b_so = vb < nwg ? (unsigned)(((xcd_remap(vb, nwg) % a.nt) * NK * 8 + wave_u) * 4096) : OOB;
+        b_so = vb < nwg ? (unsigned)(((mbn_xcd_remap(vb, nwg) % a.nt) * NK * 8 + wave_u) * 4096) : MBN_OOB;
     };
     auto issue_a = [&]() __attribute__((always_inline)) {
         float *slot = lds + a_slot * AF;
@@ -153,12 +132,12 @@ __global__ __launch_bounds__(NT, 2) void pw_wide_bf16(WideArgs a)
             set_a_tile(a_vb);
         }
     };
-    auto load_b = [&](u4v (&b)[4]) __attribute__((always_inline)) {
-        // the range check sees the VGPR offset only: a dropped load carries OOB there
-        const unsigned so = b_so == OOB ? 0u : b_so + (unsigned)b_kt * 8u * 4096u;
-        const unsigned vo = b_so == OOB ? OOB : (unsigned)lane * 16u;
+    auto load_b = [&](u4 (&b)[4]) __attribute__((always_inline)) {
+        // the range check sees the VGPR offset only: a dropped load carries MBN_OOB there
+        const unsigned so = b_so == MBN_OOB ? 0u : b_so + (unsigned)b_kt * 8u * 4096u;
+        const unsigned vo = b_so == MBN_OOB ? MBN_OOB : (unsigned)lane * 16u;
 #pragma unroll
-        for (int s = 0; s < 4; s++) b[s] = __builtin_bit_cast(u4v, __builtin_amdgcn_raw_buffer_load_b128(brsrc, vo + s * 1024u, so, 0));
+        for (int s = 0; s < 4; s++) b[s] = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(brsrc, vo + s * 1024u, so, 0));
         if (++b_kt == NK) {
             b_kt = 0;
             b_vb += gridDim.x;
@@ -167,7 +146,7 @@ __global__ __launch_bounds__(NT, 2) void pw_wide_bf16(WideArgs a)
     };
     set_a_tile(a_vb);
     set_b_tile(b_vb);
-    u4v b0[4], b1[4];
+    u4 b0[4], b1[4];
     load_b(b0);                                  // B(0), then A(0), A(1): "everything up to B(i)" is one counted wait from step 0 on
     issue_a();
     issue_a();
@@ -196,7 +175,7 @@ __global__ __launch_bounds__(NT, 2) void pw_wide_bf16(WideArgs a)
     // per-lane byte offset of a store, the same for every tile: (lane's row, lane's channel pair inside the 256-column tile); tile,
     // block and j go through the scalar offset. Block 6 holds tile rows 192..223 of which 192..195 exist: lanes with row_l == 0 only.
     const unsigned lane_c = row_l * ldc2 + (unsigned)(wave_u * 32 + (li & ~1)) * 2u;
-    unsigned o_lc = OOB, o_lc6 = OOB;            // lane offsets of the pending tile (OOB: nothing pending)
+    unsigned o_lc = MBN_OOB, o_lc6 = MBN_OOB;            // lane offsets of the pending tile (MBN_OOB: nothing pending)
     unsigned o_m0 = 0, o_nb = 0;                 // its first row, byte offset of its first column
     bool o_ragged = false;
     auto store_block = [&](int mi) __attribute__((always_inline)) {
@@ -208,8 +187,8 @@ __global__ __launch_bounds__(NT, 2) void pw_wide_bf16(WideArgs a)
             if (ABL & 16) asm volatile("" ::"v"(outp[mi][jj]), "v"(lb));
             else if (!o_ragged) __builtin_amdgcn_raw_buffer_store_b32(outp[mi][jj], orsrc, lb, rt * ldc2 + o_nb, 0);
             else {                                                                           // rows past M: whole offset through the VGPR, range-checked
-                const bool keep = lb != OOB && (long)rt + row_l < a.m;
-                __builtin_amdgcn_raw_buffer_store_b32(outp[mi][jj], orsrc, keep ? lb + rt * ldc2 + o_nb : OOB, 0, 0);
+                const bool keep = lb != MBN_OOB && (long)rt + row_l < a.m;
+                __builtin_amdgcn_raw_buffer_store_b32(outp[mi][jj], orsrc, keep ? lb + rt * ldc2 + o_nb : MBN_OOB, 0, 0);
             }
         }
     };
@@ -221,16 +200,16 @@ __global__ __launch_bounds__(NT, 2) void pw_wide_bf16(WideArgs a)
 
     int cvb = blockIdx.x, cas = 0;
     f4 fa_fix = f4{ 0.f, 0.f, 0.f, 0.f };
-    if (ABL & 8) { wide_barrier<0>(); fa_fix = *reinterpret_cast<const f4 *>(lds + fr[0]); }
+    if (ABL & 8) { mbn_waitcnt<0>(); fa_fix = *reinterpret_cast<const f4 *>(lds + fr[0]); }
     // one k-step on filter set bc, loading the next k-tile's filter into bn; KT = the step's index inside its tile
-    auto step = [&](auto kt_tag, u4v (&bc)[4], u4v (&bn)[4]) __attribute__((always_inline)) {
+    auto step = [&](auto kt_tag, u4 (&bc)[4], u4 (&bn)[4]) __attribute__((always_inline)) {
         constexpr int KT = decltype(kt_tag)::value;
         constexpr bool LAST = KT == NK - 1;
         // younger than B(i) at this point: the 4 pieces of A(i+1) and the deferred stores of step i-1
         constexpr int PKT = (KT + NK - 1) % NK;
         constexpr int PST = NK == 4 ? (PKT == 3 ? 4 : 16) : (PKT < MI - 1 ? 8 : PKT == MI - 1 ? 4 : 0);
-        if (ABL & 3) wide_barrier<0, !(ABL & 32)>();
-        else wide_barrier<4 + ((ABL & 16) ? 0 : PST), !(ABL & 32)>();
+        if (ABL & 3) mbn_waitcnt<0, !(ABL & 32)>();
+        else mbn_waitcnt<4 + ((ABL & 16) ? 0 : PST), !(ABL & 32)>();
         const float *As = lds + cas * AF;
         if (++cas == ASLOTS) cas = 0;
         // fragment f = (k16 step s, row block mi) = 7 s + mi, read FD fragments ahead of its MFMA through a 4-deep register
@@ -247,7 +226,7 @@ __global__ __launch_bounds__(NT, 2) void pw_wide_bf16(WideArgs a)
         int n0 = 0;
         unsigned m0 = 0;
         if constexpr (LAST) {                            // ahead of this step's loads, so that waiting for them drains nothing younger
-            const int lid = xcd_remap(cvb, nwg);
+            const int lid = mbn_xcd_remap(cvb, nwg);
             n0 = (lid % a.nt) * BN;
             m0 = (unsigned)(lid / a.nt) * TM;
             const unsigned co = (unsigned)(n0 + wave_u * 32 + li) * 4u;
@@ -286,7 +265,7 @@ __global__ __launch_bounds__(NT, 2) void pw_wide_bf16(WideArgs a)
                     const float y = fminf(fmaxf(fmaf(acc[mi][jj + 8], sc, sh), 0.f), 6.f);
                     const float tx = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));
                     const float ty = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, y), 0xB1, 0xF, 0xF, true));
-                    outp[mi][jj] = __builtin_bit_cast(unsigned, odd ? bf2e{ (__bf16)ty, (__bf16)y } : bf2e{ (__bf16)x, (__bf16)tx });
+                    outp[mi][jj] = __builtin_bit_cast(unsigned, odd ? bf2{ (__bf16)ty, (__bf16)y } : bf2{ (__bf16)x, (__bf16)tx });
                 }
             }
 #pragma unroll
@@ -294,7 +273,7 @@ __global__ __launch_bounds__(NT, 2) void pw_wide_bf16(WideArgs a)
 #pragma unroll
                 for (int r = 0; r < 16; r++) acc[mi][r] = 0.f;
             o_lc = lane_c;
-            o_lc6 = row_l == 0 ? lane_c : OOB;
+            o_lc6 = row_l == 0 ? lane_c : MBN_OOB;
             o_m0 = m0;
             o_nb = (unsigned)n0 * 2u;
             o_ragged = (long)m0 + TM > a.m;                                                  // the last row tile when M % 196 != 0
@@ -322,7 +301,7 @@ __global__ __launch_bounds__(NT, 2) void pw_wide_bf16(WideArgs a)
 static bool wide_shape_ok(long m, int cin, int op_size)
 {
     return (cin == 256 || cin == 512 || cin == 1024) && op_size >= 256 && (op_size % BN) == 0 && m >= 4 * TM &&
-           (double)m * cin * 2 < (double)OOB && (double)m * op_size * 2 < (double)OOB && (double)op_size * cin * 2 < (double)OOB;
+           (double)m * cin * 2 < (double)MBN_OOB && (double)m * op_size * 2 < (double)MBN_OOB && (double)op_size * cin * 2 < (double)MBN_OOB;
 }
 
 int mbn_launch_pack_filter_bf16(mbn_context *ctx, hipStream_t s, void *dst, const void *src, int n, int k)
@@ -330,7 +309,7 @@ int mbn_launch_pack_filter_bf16(mbn_context *ctx, hipStream_t s, void *dst, cons
     (void)ctx;
     if (n <= 0 || k <= 0 || (n % BN) != 0 || (k % BKE) != 0 || ((uintptr_t)dst % 16) != 0 || ((uintptr_t)src % 16) != 0) return MBN_EUNSUPPORTED;
     const long total = (long)n * k / 8;
-    hipLaunchKernelGGL(pack_filter_bf16, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (u4v *)dst, (const __bf16 *)src, n, k);
+    hipLaunchKernelGGL(pack_filter_bf16, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (u4 *)dst, (const __bf16 *)src, n, k);
     return MBN_OK;
 }
 

@@ -30,14 +30,6 @@
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f8 __attribute__((ext_vector_type(8)));
-typedef unsigned u4v __attribute__((ext_vector_type(4)));
-typedef unsigned u2v __attribute__((ext_vector_type(2)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-typedef mbn_f16v f16v;
-
 constexpr int RES_MAXBLK = MBN_RES_MAXBLK;
 constexpr int XPIX = MBN_RES_XPIX, YPIX = 128, YROWS = MBN_RES_YROWS;   // pixel rows of the two LDS images (Y holds 104 — a map inside the envelope has at most 100 pixels; the GEMM's reads of
                                                      // pixel rows up to 127 run on into the constants behind it: inside the allocation, results unused)
@@ -50,23 +42,6 @@ struct ResArgs {
     const float *wd[RES_MAXBLK], *s2[RES_MAXBLK], *b2[RES_MAXBLK], *s3[RES_MAXBLK], *b3[RES_MAXBLK];
     const __bf16 *wp[RES_MAXBLK];
 };
-
-__device__ __forceinline__ f8 widen8(u4v p)
-{
-    f8 r;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        r[2 * i] = __builtin_bit_cast(float, p[i] << 16);
-        r[2 * i + 1] = __builtin_bit_cast(float, p[i] & 0xffff0000u);
-    }
-    return r;
-}
-__device__ __forceinline__ f8 ld8g(const float *p)
-{
-    const f4 a = *reinterpret_cast<const f4 *>(p), b = *reinterpret_cast<const f4 *>(p + 4);
-    return f8{ a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
-}
-__device__ __forceinline__ float relu6(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
 
 template <int C>
 __global__ __launch_bounds__(512) void res_blocks_bf16(ResArgs a)
@@ -97,7 +72,7 @@ __global__ __launch_bounds__(512) void res_blocks_bf16(ResArgs a)
     char *const xb = reinterpret_cast<char *>(x_s), *const yb = reinterpret_cast<char *>(y_s);
 
     // zero X once: the border is never written again
-    for (int i = tid; i < XPIX * RS / 8; i += 512) reinterpret_cast<u4v *>(x_s)[i] = u4v{ 0u, 0u, 0u, 0u };
+    for (int i = tid; i < XPIX * RS / 8; i += 512) reinterpret_cast<u4 *>(x_s)[i] = u4{ 0u, 0u, 0u, 0u };
     for (int i = tid; i < a.nblk * C; i += 512) {
         const int blk = i / C, ch = i % C;
         sb3_s[blk * 2 * C + ch] = a.s3[blk][ch];
@@ -130,13 +105,13 @@ __global__ __launch_bounds__(512) void res_blocks_bf16(ResArgs a)
         if (tp2) *reinterpret_cast<f4 *>(tp_s + 4 * (tid + 512)) = p1;
     }
 
-    u4v wfr[KG];                                                          // this wave's filter rows of the coming block: k = 16 g + 8 lh .. + 7 of output channel 32 wave + li
+    u4 wfr[KG];                                                           // this wave's filter rows of the coming block: k = 16 g + 8 lh .. + 7 of output channel 32 wave + li
     {
         const __bf16 *wrow = a.wp[0] + (size_t)(32 * wave_u + li) * C + 8 * lh;
 #pragma unroll
-        for (int g = 0; g < KG / 2; g++) wfr[g] = *reinterpret_cast<const u4v *>(wrow + 16 * g);
+        for (int g = 0; g < KG / 2; g++) wfr[g] = *reinterpret_cast<const u4 *>(wrow + 16 * g);
 #pragma unroll
-        for (int g = KG / 2; g < KG; g++) wfr[g] = u4v{ 0u, 0u, 0u, 0u };
+        for (int g = KG / 2; g < KG; g++) wfr[g] = u4{ 0u, 0u, 0u, 0u };
     }
 
     for (int n = blockIdx.x; n < a.batch; n += gridDim.x) {
@@ -146,16 +121,16 @@ __global__ __launch_bounds__(512) void res_blocks_bf16(ResArgs a)
             const __bf16 *src = a.in + (size_t)n * P * C;
             int prow_n = prow;                                            // laundered: the eight X offsets are recomputed per image instead of living (spilled) across the block loop
             asm volatile("" : "+v"(prow_n));
-            u4v pc[NIT];
+            u4 pc[NIT];
 #pragma unroll
             for (int k = 0; k < NIT; k++) {
                 const int q = prow_n + PSTEP * k;
-                pc[k] = q < P ? *reinterpret_cast<const u4v *>(reinterpret_cast<const char *>(src) + (unsigned)((q * C + cg * 8) * 2)) : u4v{ 0u, 0u, 0u, 0u };   // (uniform base + 32-bit lane offset)
+                pc[k] = q < P ? *reinterpret_cast<const u4 *>(reinterpret_cast<const char *>(src) + (unsigned)((q * C + cg * 8) * 2)) : u4{ 0u, 0u, 0u, 0u };     // (uniform base + 32-bit lane offset)
             }
 #pragma unroll
             for (int k = 0; k < NIT; k++) {
                 const int q = prow_n + PSTEP * k;
-                if (q < P) *reinterpret_cast<u4v *>(xb + xint(q) + cg * 16) = pc[k];
+                if (q < P) *reinterpret_cast<u4 *>(xb + xint(q) + cg * 16) = pc[k];
             }
         }
         __syncthreads();
@@ -191,8 +166,8 @@ __global__ __launch_bounds__(512) void res_blocks_bf16(ResArgs a)
                 // input row i of the job: dy = 0 for output i (starts its sum), dy = 1 for output i - 1, dy = 2 for output i - 2 (completes it)
 #define RES_DW_ROW(I, SA, SB, SC)                                                                                             \
                 if ((I) < nr + 2) {                                                                                           \
-                    const f8 x0 = widen8(*reinterpret_cast<const u4v *>(xb + xa)), x1 = widen8(*reinterpret_cast<const u4v *>(xb + xa + RSB)), \
-                             x2 = widen8(*reinterpret_cast<const u4v *>(xb + xa + 2 * RSB));                                    \
+                    const f8 x0 = mbn_widen8(*reinterpret_cast<const u4 *>(xb + xa)), x1 = mbn_widen8(*reinterpret_cast<const u4 *>(xb + xa + RSB)), \
+                             x2 = mbn_widen8(*reinterpret_cast<const u4 *>(xb + xa + 2 * RSB));                                 \
                     f8 z;                                                                                                     \
                     _Pragma("unroll") for (int i_ = 0; i_ < 8; i_++) z[i_] = 0.f;                                             \
                     SA = __builtin_elementwise_fma(x0, tap[0], z);                                                            \
@@ -207,7 +182,7 @@ __global__ __launch_bounds__(512) void res_blocks_bf16(ResArgs a)
                     if ((I) >= 2 && cok) {                                                                                    \
                         bf8 o;                                                                                                \
                         const f8 v_ = __builtin_elementwise_fma(SC, sc, sh);                                                  \
-                        _Pragma("unroll") for (int i_ = 0; i_ < 8; i_++) o[i_] = (__bf16)relu6(v_[i_]);                       \
+                        _Pragma("unroll") for (int i_ = 0; i_ < 8; i_++) o[i_] = (__bf16)mbn_relu6(v_[i_]);                   \
                         *reinterpret_cast<bf8 *>(yb + ya) = o;                                                                \
                     }                                                                                                         \
                     xa += (unsigned)(WB * RSB);                                                                               \
@@ -225,7 +200,7 @@ __global__ __launch_bounds__(512) void res_blocks_bf16(ResArgs a)
             if (!(dbg & 8)) {
                 const __bf16 *wrow = a.wp[blk] + (size_t)(32 * wave_u + li) * C + 8 * lh;
 #pragma unroll
-                for (int g = KG / 2; g < KG; g++) wfr[g] = *reinterpret_cast<const u4v *>(wrow + 16 * g);
+                for (int g = KG / 2; g < KG; g++) wfr[g] = *reinterpret_cast<const u4 *>(wrow + 16 * g);
             }
             __syncthreads();
             f4 tq0 = f4{ 0.f, 0.f, 0.f, 0.f }, tq1 = tq0;                 // the next block's depthwise constants, on their way from memory to LDS
@@ -239,9 +214,9 @@ __global__ __launch_bounds__(512) void res_blocks_bf16(ResArgs a)
                 if (!(dbg & 2))
 #pragma unroll
                 for (int g = 0; g < KG; g++) {
-                    u4v yf[4];
+                    u4 yf[4];
 #pragma unroll
-                    for (int b = 0; b < 4; b++) yf[b] = *reinterpret_cast<const u4v *>(yb + yfrag + (unsigned)(b * 32 * RSB + g * 32));
+                    for (int b = 0; b < 4; b++) yf[b] = *reinterpret_cast<const u4 *>(yb + yfrag + (unsigned)(b * 32 * RSB + g * 32));
 #pragma unroll
                     for (int b = 0; b < 4; b++)
                         acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8, wfr[g]), __builtin_bit_cast(bf8, yf[b]), acc[b], 0, 0, 0);
@@ -251,7 +226,7 @@ __global__ __launch_bounds__(512) void res_blocks_bf16(ResArgs a)
                     const int nb = blk + 1 < a.nblk ? blk + 1 : 0;
                     const __bf16 *wrow = a.wp[nb] + (size_t)(32 * wave_u + li) * C + 8 * lh;
 #pragma unroll
-                    for (int g = 0; g < KG / 2; g++) wfr[g] = *reinterpret_cast<const u4v *>(wrow + 16 * g);       // (the first half; the second behind the next depthwise phase: registers)
+                    for (int g = 0; g < KG / 2; g++) wfr[g] = *reinterpret_cast<const u4 *>(wrow + 16 * g);        // (the first half; the second behind the next depthwise phase: registers)
                     tq0 = tap_piece(nb, 0);                                // and this thread's two pieces of its depthwise constants, written into LDS behind the epilogue
                     if (tp2) tq1 = tap_piece(nb, 1);
                 }
@@ -266,8 +241,8 @@ __global__ __launch_bounds__(512) void res_blocks_bf16(ResArgs a)
                     const f4 sc = *reinterpret_cast<const f4 *>(s3p + 8 * j), sh = *reinterpret_cast<const f4 *>(b3p + 8 * j);
 #pragma unroll
                     for (int b = 0; b < 4; b++) {
-                        const bf4 o = bf4{ (__bf16)relu6(fmaf(acc[b][4 * j], sc.x, sh.x)), (__bf16)relu6(fmaf(acc[b][4 * j + 1], sc.y, sh.y)),
-                                           (__bf16)relu6(fmaf(acc[b][4 * j + 2], sc.z, sh.z)), (__bf16)relu6(fmaf(acc[b][4 * j + 3], sc.w, sh.w)) };
+                        const bf4 o = bf4{ (__bf16)mbn_relu6(fmaf(acc[b][4 * j], sc.x, sh.x)), (__bf16)mbn_relu6(fmaf(acc[b][4 * j + 1], sc.y, sh.y)),
+                                           (__bf16)mbn_relu6(fmaf(acc[b][4 * j + 2], sc.z, sh.z)), (__bf16)mbn_relu6(fmaf(acc[b][4 * j + 3], sc.w, sh.w)) };
                         if (32 * b + li < P) *reinterpret_cast<bf4 *>(xb + xi[b] + (unsigned)(16 * j)) = o;
                     }
                 }
@@ -284,7 +259,7 @@ __global__ __launch_bounds__(512) void res_blocks_bf16(ResArgs a)
 #pragma unroll
             for (int k = 0; k < NIT; k++) {
                 const int q = prow_n + PSTEP * k;
-                if (q < P) *reinterpret_cast<u4v *>(reinterpret_cast<char *>(dst) + (unsigned)((q * C + cg * 8) * 2)) = *reinterpret_cast<const u4v *>(xb + xint(q) + cg * 16);
+                if (q < P) *reinterpret_cast<u4 *>(reinterpret_cast<char *>(dst) + (unsigned)((q * C + cg * 8) * 2)) = *reinterpret_cast<const u4 *>(xb + xint(q) + cg * 16);
             }
         }
     }

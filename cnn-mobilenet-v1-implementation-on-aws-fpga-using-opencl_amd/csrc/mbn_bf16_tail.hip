@@ -25,13 +25,6 @@
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f8 __attribute__((ext_vector_type(8)));
-typedef unsigned u4v __attribute__((ext_vector_type(4)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-typedef mbn_f16v f16v;
-
 struct TailArgs {
     __bf16 *out;                 // [batch][C1]
     const __bf16 *in;            // [batch][h0][w0][C0]
@@ -44,23 +37,6 @@ struct TailArgs {
     const float *s3, *b3;
     int dbg;                     // lab ablations (exp0 = 800 + bits): 1 no depthwise phases, 2 no MFMAs, 4 no filter loads, 8 no image load, 16 no pool (timing only)
 };
-
-__device__ __forceinline__ f8 widen8(u4v p)
-{
-    f8 r;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        r[2 * i] = __builtin_bit_cast(float, p[i] << 16);
-        r[2 * i + 1] = __builtin_bit_cast(float, p[i] & 0xffff0000u);
-    }
-    return r;
-}
-__device__ __forceinline__ f8 ld8s(const float *p)
-{
-    const f4 a = *reinterpret_cast<const f4 *>(p), b = *reinterpret_cast<const f4 *>(p + 4);
-    return f8{ a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
-}
-__device__ __forceinline__ float relu6(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
 
 template <int C0, int C1>
 __global__ __launch_bounds__(512) void tail_bf16(TailArgs a)
@@ -96,7 +72,7 @@ __global__ __launch_bounds__(512) void tail_bf16(TailArgs a)
     // the wave's filter rows as A operands of v_mfma_f32_16x16x32_bf16: lane (j16, q4) holds k = 32 g + 8 q4 .. + 7 of row 16 blk16 + j16 — four lanes read 64 contiguous
     // bytes of a row (the 32x32x16 layout: two lanes, 32 bytes; the filter fetch is bound by the lines the L1 handles per instruction, not by bytes).
     // pointwise 1 (K = 256): both 32-channel blocks of the wave, index (blk * KS0 + g) * 2 + half; pointwise 2 (K = 512): one block at a time, index g * 2 + half
-    u4v wf[2 * KS1];                                   // 128 VGPRs
+    u4 wf[2 * KS1];                                    // 128 VGPRs
     auto load_pw0 = [&]() __attribute__((always_inline)) {
         if (dbg & 4) return;
 #pragma unroll
@@ -105,7 +81,7 @@ __global__ __launch_bounds__(512) void tail_bf16(TailArgs a)
             for (int hf = 0; hf < 2; hf++) {
                 const __bf16 *wrow = a.wp0 + (size_t)(32 * (wave_u + 8 * blk) + 16 * hf + j16) * C0 + 8 * q4;
 #pragma unroll
-                for (int g = 0; g < KS0; g++) wf[(blk * KS0 + g) * 2 + hf] = *reinterpret_cast<const u4v *>(wrow + 32 * g);
+                for (int g = 0; g < KS0; g++) wf[(blk * KS0 + g) * 2 + hf] = *reinterpret_cast<const u4 *>(wrow + 32 * g);
             }
     };
     auto load_pw1 = [&](int blk, int g0, int g1) __attribute__((always_inline)) {       // k steps g0 ... g1 - 1 of the block's rows
@@ -115,7 +91,7 @@ __global__ __launch_bounds__(512) void tail_bf16(TailArgs a)
             const __bf16 *wrow = a.wp1 + (size_t)(32 * (wave_u + 8 * blk) + 16 * hf + j16) * C1 + 8 * q4;
 #pragma unroll
             for (int g = 0; g < KS1; g++)
-                if (g >= g0 && g < g1) wf[g * 2 + hf] = *reinterpret_cast<const u4v *>(wrow + 32 * g);
+                if (g >= g0 && g < g1) wf[g * 2 + hf] = *reinterpret_cast<const u4 *>(wrow + 32 * g);
         }
     };
     load_pw0();
@@ -151,8 +127,8 @@ __global__ __launch_bounds__(512) void tail_bf16(TailArgs a)
 #pragma unroll
             for (int b = 0; b < 4; b++) {
                 const f4 v = acc[hf][b];
-                const bf4 o = bf4{ (__bf16)relu6(fmaf(v.x, sc.x, sh.x)), (__bf16)relu6(fmaf(v.y, sc.y, sh.y)),
-                                   (__bf16)relu6(fmaf(v.z, sc.z, sh.z)), (__bf16)relu6(fmaf(v.w, sc.w, sh.w)) };
+                const bf4 o = bf4{ (__bf16)mbn_relu6(fmaf(v.x, sc.x, sh.x)), (__bf16)mbn_relu6(fmaf(v.y, sc.y, sh.y)),
+                                   (__bf16)mbn_relu6(fmaf(v.z, sc.z, sh.z)), (__bf16)mbn_relu6(fmaf(v.w, sc.w, sh.w)) };
                 if (16 * b + j16 < Q) *reinterpret_cast<bf4 *>(x1 + (16 * b + j16) * RSB1 + cb * 2) = o;
             }
         }
@@ -171,23 +147,23 @@ __global__ __launch_bounds__(512) void tail_bf16(TailArgs a)
                 const int oy = p / w1, ox = p - oy * w1;
                 const char *src = reinterpret_cast<const char *>(a.in + (size_t)(n0 + img) * P0 * C0) + cg * 16;
                 const float *tl = tp0 + cg * 8;
-                u4v xr[9];
+                u4 xr[9];
 #pragma unroll
                 for (int dy = 0; dy < 3; dy++)
 #pragma unroll
                     for (int dx = 0; dx < 3; dx++) {
                         const int iy = 2 * oy + dy, ix = 2 * ox + dx;
-                        xr[dy * 3 + dx] = (iy < a.h0 && ix < a.w0) ? *reinterpret_cast<const u4v *>(src + (unsigned)((iy * a.w0 + ix) * (C0 * 2))) : u4v{ 0u, 0u, 0u, 0u };
+                        xr[dy * 3 + dx] = (iy < a.h0 && ix < a.w0) ? *reinterpret_cast<const u4 *>(src + (unsigned)((iy * a.w0 + ix) * (C0 * 2))) : u4{ 0u, 0u, 0u, 0u };
                     }
                 f8 acc;
 #pragma unroll
                 for (int i = 0; i < 8; i++) acc[i] = 0.f;
 #pragma unroll
-                for (int t = 0; t < 9; t++) acc = __builtin_elementwise_fma(widen8(xr[t]), ld8s(tl + t * C0), acc);      // (a tap outside the map multiplies zero: the same sum)
-                const f8 v = __builtin_elementwise_fma(acc, ld8s(tl + 9 * C0), ld8s(tl + 10 * C0));
+                for (int t = 0; t < 9; t++) acc = __builtin_elementwise_fma(mbn_widen8(xr[t]), mbn_ld8(tl + t * C0), acc);  // (a tap outside the map multiplies zero: the same sum)
+                const f8 v = __builtin_elementwise_fma(acc, mbn_ld8(tl + 9 * C0), mbn_ld8(tl + 10 * C0));
                 bf8 o;
 #pragma unroll
-                for (int i = 0; i < 8; i++) o[i] = (__bf16)relu6(v[i]);
+                for (int i = 0; i < 8; i++) o[i] = (__bf16)mbn_relu6(v[i]);
                 *reinterpret_cast<bf8 *>(yb + q * RSB0 + cg * 16) = o;
             }
         }
@@ -205,9 +181,9 @@ __global__ __launch_bounds__(512) void tail_bf16(TailArgs a)
             if (!(dbg & 2))
 #pragma unroll
             for (int g = 0; g < KS0; g++) {
-                u4v yf[4];
+                u4 yf[4];
 #pragma unroll
-                for (int b = 0; b < 4; b++) yf[b] = *reinterpret_cast<const u4v *>(yb + (16 * b + jc_) * RSB0 + g * 64 + qc_ * 16);
+                for (int b = 0; b < 4; b++) yf[b] = *reinterpret_cast<const u4 *>(yb + (16 * b + jc_) * RSB0 + g * 64 + qc_ * 16);
 #pragma unroll
                 for (int hf = 0; hf < 2; hf++)
 #pragma unroll
@@ -239,12 +215,12 @@ __global__ __launch_bounds__(512) void tail_bf16(TailArgs a)
                         const int iy = oy + dy - 1, ix = ox + dx - 1;
                         // (a wave's 64 lanes are the 64 channel groups of ONE pixel: the test is uniform, a tap outside the map is skipped by a scalar branch)
                         if (iy >= 0 && iy < h1 && ix >= 0 && ix < w1)
-                            acc = __builtin_elementwise_fma(widen8(*reinterpret_cast<const u4v *>(xi + (iy * w1 + ix) * RSB1)), ld8s(tl + (dy * 3 + dx) * C1), acc);
+                            acc = __builtin_elementwise_fma(mbn_widen8(*reinterpret_cast<const u4 *>(xi + (iy * w1 + ix) * RSB1)), mbn_ld8(tl + (dy * 3 + dx) * C1), acc);
                     }
-                const f8 v = __builtin_elementwise_fma(acc, ld8s(tl + 9 * C1), ld8s(tl + 10 * C1));
+                const f8 v = __builtin_elementwise_fma(acc, mbn_ld8(tl + 9 * C1), mbn_ld8(tl + 10 * C1));
                 bf8 o;
 #pragma unroll
-                for (int i = 0; i < 8; i++) o[i] = (__bf16)relu6(v[i]);
+                for (int i = 0; i < 8; i++) o[i] = (__bf16)mbn_relu6(v[i]);
                 *reinterpret_cast<bf8 *>(yb + q * RSB1 + cg * 16) = o;
             }
         }
@@ -263,9 +239,9 @@ __global__ __launch_bounds__(512) void tail_bf16(TailArgs a)
 #pragma unroll
             for (int g = 0; g < KS1; g++) {
                 if (!(dbg & 2)) {
-                    u4v yf[4];
+                    u4 yf[4];
 #pragma unroll
-                    for (int b = 0; b < 4; b++) yf[b] = *reinterpret_cast<const u4v *>(yb + (16 * b + je_) * RSB1 + g * 64 + qe_ * 16);
+                    for (int b = 0; b < 4; b++) yf[b] = *reinterpret_cast<const u4 *>(yb + (16 * b + je_) * RSB1 + g * 64 + qe_ * 16);
 #pragma unroll
                     for (int hf = 0; hf < 2; hf++)
 #pragma unroll

@@ -7,12 +7,7 @@
 // when tried with flat stores) and no bounds branches. The output must be smaller than 4 GiB.
 #pragma once
 
-typedef float mbn_f16v __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mbn_make_rsrc(const void *base, unsigned bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, bytes, 0x00020000);
-}
+#include "mbn_device.h"
 
 // MODE 0: the MI*32 x NI*32 block lies inside the matrix, no checks. MODE 1: columns inside, rows may run past m — the
 // descriptor (num_records = m*ldc*4 bytes) drops them: the whole offset goes through the VGPR so the hardware range
@@ -20,7 +15,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t mbn_make_rsrc(const void *base
 // TO = float or __bf16 (the element type of `out`; bf16 is rounded to nearest-even like the plain cast).
 template <int MI, int NI, int MODE, typename TO = float>
 __device__ __forceinline__ void mbn_store_relu6_f32(__amdgpu_buffer_rsrc_t out, unsigned ldc, unsigned row0, int col0,
-                                                    int lane, const mbn_f16v (&acc)[MI][NI],
+                                                    int lane, const f16v (&acc)[MI][NI],
                                                     const float *__restrict__ scale, const float *__restrict__ shift,
                                                     unsigned m, int n)
 {
@@ -71,35 +66,33 @@ __device__ __forceinline__ int mbn_pair_channel(int rho) { return (rho & ~63) | 
 // for bit (same fma, same clamp). Used by the fused block kernels, where the epilogue stores measured 13 % of a step.
 template <int MI, int NI, int MODE>
 __device__ __forceinline__ void mbn_store_relu6_f32_pair(__amdgpu_buffer_rsrc_t out, unsigned ldc, unsigned row0, int col0, int lane,
-                                                         const mbn_f16v (&acc)[MI][NI], const float *__restrict__ scale,
+                                                         const f16v (&acc)[MI][NI], const float *__restrict__ scale,
                                                          const float *__restrict__ shift)
 {
     static_assert((NI & 1) == 0, "channel-paired epilogue needs an even number of 32-column blocks");
-    typedef float f2e __attribute__((ext_vector_type(2)));
-    typedef unsigned u2e __attribute__((ext_vector_type(2)));
     const int li = lane & 31, lh = lane >> 5;
     const unsigned lane_off = ((unsigned)(4 * lh) * ldc + (unsigned)(2 * li)) * 4u;        // bytes
 #pragma unroll
     for (int t = 0; t < NI / 2; t++) {
-        const f2e sc = *reinterpret_cast<const f2e *>(scale + col0 + 64 * t + 2 * li);
-        const f2e sh = *reinterpret_cast<const f2e *>(shift + col0 + 64 * t + 2 * li);
-        const f2e scx = f2e{ sc.x, sc.x }, scy = f2e{ sc.y, sc.y }, shx = f2e{ sh.x, sh.x }, shy = f2e{ sh.y, sh.y };
+        const f2 sc = *reinterpret_cast<const f2 *>(scale + col0 + 64 * t + 2 * li);
+        const f2 sh = *reinterpret_cast<const f2 *>(shift + col0 + 64 * t + 2 * li);
+        const f2 scx = f2{ sc.x, sc.x }, scy = f2{ sc.y, sc.y }, shx = f2{ sh.x, sh.x }, shy = f2{ sh.y, sh.y };
 #pragma unroll
         for (int mi = 0; mi < MI; mi++)
 #pragma unroll
             for (int r = 0; r < 16; r += 2) {
                 // round 5: the BN of rows r, r + 1 of one channel is ONE v_pk_fma_f32 (the two accumulators are adjacent registers, scale and shift
                 // broadcast); the clamps write each value where its store wants it, so the channel pairing costs nothing. Same fma, same clamp: same bits.
-                const f2e p0 = __builtin_elementwise_fma(f2e{ acc[mi][2 * t][r], acc[mi][2 * t][r + 1] }, scx, shx);
-                const f2e p1 = __builtin_elementwise_fma(f2e{ acc[mi][2 * t + 1][r], acc[mi][2 * t + 1][r + 1] }, scy, shy);
+                const f2 p0 = __builtin_elementwise_fma(f2{ acc[mi][2 * t][r], acc[mi][2 * t][r + 1] }, scx, shx);
+                const f2 p1 = __builtin_elementwise_fma(f2{ acc[mi][2 * t + 1][r], acc[mi][2 * t + 1][r + 1] }, scy, shy);
 #pragma unroll
                 for (int h = 0; h < 2; h++) {
                     const int rr = r + h;
                     const unsigned ro = row0 + mi * 32 + (rr & 3) + 8 * (rr >> 2);         // + 4*lh per lane
-                    const f2e v = f2e{ fminf(fmaxf(h ? p0.y : p0.x, 0.f), 6.f), fminf(fmaxf(h ? p1.y : p1.x, 0.f), 6.f) };
+                    const f2 v = f2{ fminf(fmaxf(h ? p0.y : p0.x, 0.f), 6.f), fminf(fmaxf(h ? p1.y : p1.x, 0.f), 6.f) };
                     const unsigned soff = (ro * ldc + (unsigned)(col0 + 64 * t)) * 4u;     // wave-uniform bytes
-                    if (MODE == 0) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2e, v), out, lane_off, soff, 0);
-                    else __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2e, v), out, lane_off + soff, 0, 0);
+                    if (MODE == 0) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, v), out, lane_off, soff, 0);
+                    else __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, v), out, lane_off + soff, 0, 0);
                 }
             }
     }
@@ -107,18 +100,16 @@ __device__ __forceinline__ void mbn_store_relu6_f32_pair(__amdgpu_buffer_rsrc_t 
 
 template <int MI, int NI, int MODE>
 __device__ __forceinline__ void mbn_store_relu6_bf16_pair(__amdgpu_buffer_rsrc_t out, unsigned ldc, unsigned row0, int col0, int lane,
-                                                          const mbn_f16v (&acc)[MI][NI], const float *__restrict__ scale,
+                                                          const f16v (&acc)[MI][NI], const float *__restrict__ scale,
                                                           const float *__restrict__ shift)
 {
     static_assert((NI & 1) == 0, "channel-paired epilogue needs an even number of 32-column blocks");
-    typedef float f2e __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf2e __attribute__((ext_vector_type(2)));
     const int li = lane & 31, lh = lane >> 5;
     const unsigned lane_off = ((unsigned)(4 * lh) * ldc + (unsigned)(2 * li)) * 2u;        // bytes
 #pragma unroll
     for (int t = 0; t < NI / 2; t++) {
-        const f2e sc = *reinterpret_cast<const f2e *>(scale + col0 + 64 * t + 2 * li);
-        const f2e sh = *reinterpret_cast<const f2e *>(shift + col0 + 64 * t + 2 * li);
+        const f2 sc = *reinterpret_cast<const f2 *>(scale + col0 + 64 * t + 2 * li);
+        const f2 sh = *reinterpret_cast<const f2 *>(shift + col0 + 64 * t + 2 * li);
 #pragma unroll
         for (int mi = 0; mi < MI; mi++)
 #pragma unroll
@@ -126,7 +117,7 @@ __device__ __forceinline__ void mbn_store_relu6_bf16_pair(__amdgpu_buffer_rsrc_t
                 const unsigned ro = row0 + mi * 32 + (r & 3) + 8 * (r >> 2);               // + 4*lh per lane
                 const float v0 = fminf(fmaxf(fmaf(acc[mi][2 * t][r], sc.x, sh.x), 0.f), 6.f);
                 const float v1 = fminf(fmaxf(fmaf(acc[mi][2 * t + 1][r], sc.y, sh.y), 0.f), 6.f);
-                const unsigned v = __builtin_bit_cast(unsigned, bf2e{ (__bf16)v0, (__bf16)v1 });   // RNE (v_cvt_pk_bf16_f32)
+                const unsigned v = __builtin_bit_cast(unsigned, bf2{ (__bf16)v0, (__bf16)v1 });    // RNE (v_cvt_pk_bf16_f32)
                 const unsigned soff = (ro * ldc + (unsigned)(col0 + 64 * t)) * 2u;         // wave-uniform bytes
                 if (MODE == 0) __builtin_amdgcn_raw_buffer_store_b32(v, out, lane_off, soff, 0);
                 else __builtin_amdgcn_raw_buffer_store_b32(v, out, lane_off + soff, 0, 0);
@@ -139,23 +130,20 @@ __device__ __forceinline__ void mbn_store_relu6_bf16_pair(__amdgpu_buffer_rsrc_t
 // rows staged channel-paired (mbn_pair_channel), the 16-row LDS blocks j and j + 2 of a 64-column group hold channels 2 (16 j + c) and
 // 2 (16 j + c) + 1 (j = 0, 1): packed 4-byte stores, 64 contiguous bytes per pixel row and instruction, four rows per instruction.
 // acc[i][j]: i = 16-row block of the wave tile (MI16 of them), j = 16-column LDS block (NI16 = 4 per 64-column group, NI16 % 4 == 0).
-typedef float mbn_f4v __attribute__((ext_vector_type(4)));
 template <int MI16, int NI16, int MODE>
 __device__ __forceinline__ void mbn_store_relu6_bf16_pair16(__amdgpu_buffer_rsrc_t out, unsigned ldc, unsigned row0, int col0, int lane,
-                                                            const mbn_f4v (&acc)[MI16][NI16], const float *__restrict__ scale,
+                                                            const f4 (&acc)[MI16][NI16], const float *__restrict__ scale,
                                                             const float *__restrict__ shift)
 {
     static_assert((NI16 & 3) == 0, "channel-paired 16x16 epilogue needs whole 64-column groups");
-    typedef float f2e __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf2e __attribute__((ext_vector_type(2)));
     const int c16 = lane & 15, q16 = lane >> 4;
     const unsigned lane_off = ((unsigned)(4 * q16) * ldc + (unsigned)(2 * c16)) * 2u;      // bytes
 #pragma unroll
     for (int t = 0; t < NI16 / 4; t++)
 #pragma unroll
         for (int jp = 0; jp < 2; jp++) {
-            const f2e sc = *reinterpret_cast<const f2e *>(scale + col0 + 64 * t + 32 * jp + 2 * c16);
-            const f2e sh = *reinterpret_cast<const f2e *>(shift + col0 + 64 * t + 32 * jp + 2 * c16);
+            const f2 sc = *reinterpret_cast<const f2 *>(scale + col0 + 64 * t + 32 * jp + 2 * c16);
+            const f2 sh = *reinterpret_cast<const f2 *>(shift + col0 + 64 * t + 32 * jp + 2 * c16);
 #pragma unroll
             for (int i = 0; i < MI16; i++)
 #pragma unroll
@@ -163,7 +151,7 @@ __device__ __forceinline__ void mbn_store_relu6_bf16_pair16(__amdgpu_buffer_rsrc
                     const unsigned ro = row0 + 16 * i + r;                                 // + 4 * q16 per lane
                     const float v0 = fminf(fmaxf(fmaf(acc[i][4 * t + jp][r], sc.x, sh.x), 0.f), 6.f);
                     const float v1 = fminf(fmaxf(fmaf(acc[i][4 * t + jp + 2][r], sc.y, sh.y), 0.f), 6.f);
-                    const unsigned v = __builtin_bit_cast(unsigned, bf2e{ (__bf16)v0, (__bf16)v1 });
+                    const unsigned v = __builtin_bit_cast(unsigned, bf2{ (__bf16)v0, (__bf16)v1 });
                     const unsigned soff = (ro * ldc + (unsigned)(col0 + 64 * t + 32 * jp)) * 2u;   // wave-uniform bytes
                     if (MODE == 0) __builtin_amdgcn_raw_buffer_store_b32(v, out, lane_off, soff, 0);
                     else __builtin_amdgcn_raw_buffer_store_b32(v, out, lane_off + soff, 0, 0);

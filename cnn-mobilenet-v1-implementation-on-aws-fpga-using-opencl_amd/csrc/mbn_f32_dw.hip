@@ -15,22 +15,15 @@
 // Measured and rejected (profiles/r01): non-temporal output stores (-5..-22 %), one column per lane (TW=1, -10 %),
 // channel-fastest lanes across the full C (-15..-40 % on the 512/1024-channel layers).
 #include "mbn_internal.h"
+#include "mbn_device.h"
 
 namespace {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ f4 ld4(const float *p) { return *reinterpret_cast<const f4 *>(p); }
 __device__ __forceinline__ f4 ld4(const __bf16 *p)
 {
     const bf4 v = *reinterpret_cast<const bf4 *>(p);
     return f4{ (float)v.x, (float)v.y, (float)v.z, (float)v.w };
-}
-__device__ __forceinline__ void st4(float *p, f4 v) { *reinterpret_cast<f4 *>(p) = v; }
-__device__ __forceinline__ void st4(__bf16 *p, f4 v)
-{
-    *reinterpret_cast<bf4 *>(p) = bf4{ (__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w };   // RNE
 }
 __device__ __forceinline__ f4 fma4(f4 a, f4 b, f4 c)
 {
@@ -121,7 +114,7 @@ __global__ __launch_bounds__(256) void dw3x3_nhwc(DwArgs a)
             acc = fma4(r1[j], w[3], acc); acc = fma4(r1[j + 1], w[4], acc); acc = fma4(r1[j + 2], w[5], acc);
             acc = fma4(r2[j], w[6], acc); acc = fma4(r2[j + 1], w[7], acc); acc = fma4(r2[j + 2], w[8], acc);
             acc = act4(fma4(acc, sc, sh), a.act);
-            if (TW == 1 || ox0 + p < a.cols) st4(op + ((long)oy * a.cols + p) * a.ch, acc);
+            if (TW == 1 || ox0 + p < a.cols) mbn_st4(op + ((long)oy * a.cols + p) * a.ch, acc);
         }
 #pragma unroll
         for (int j = 0; j < NC; j++) {
@@ -192,8 +185,7 @@ __global__ __launch_bounds__(256) void dw3x3_nhwc_b(DwArgs a)
             const unsigned off = ro + coff[j];
             if constexpr (sizeof(T) == 4) r[j] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(irs, off, 0, 0));
             else {
-                typedef unsigned u2v __attribute__((ext_vector_type(2)));
-                const u2v p = __builtin_bit_cast(u2v, __builtin_amdgcn_raw_buffer_load_b64(irs, off, 0, 0));
+                const u2 p = __builtin_bit_cast(u2, __builtin_amdgcn_raw_buffer_load_b64(irs, off, 0, 0));
                 r[j] = f4{ __builtin_bit_cast(float, p.x << 16), __builtin_bit_cast(float, p.x & 0xffff0000u),
                            __builtin_bit_cast(float, p.y << 16), __builtin_bit_cast(float, p.y & 0xffff0000u) };
             }
@@ -230,7 +222,7 @@ __global__ __launch_bounds__(256) void dw3x3_nhwc_b(DwArgs a)
             acc = fma4(r1[j], w[3], acc); acc = fma4(r1[j + 1], w[4], acc); acc = fma4(r1[j + 2], w[5], acc);
             acc = fma4(r2[j], w[6], acc); acc = fma4(r2[j + 1], w[7], acc); acc = fma4(r2[j + 2], w[8], acc);
             acc = act4(fma4(acc, sc, sh), a.act);
-            if (TW == 1 || ox0 + p < a.cols) st4(op + ((long)oy * a.cols + p) * a.ch, acc);
+            if (TW == 1 || ox0 + p < a.cols) mbn_st4(op + ((long)oy * a.cols + p) * a.ch, acc);
         }
 #pragma unroll
         for (int j = 0; j < NC; j++) {
@@ -243,50 +235,31 @@ __global__ __launch_bounds__(256) void dw3x3_nhwc_b(DwArgs a)
 // bf16 storage, 8 channels (16 bytes) per lane: the fp32 kernel's decomposition with 4-channel lanes moves 8 bytes per
 // lane-load in bf16 and is instruction-bound at ~2.2 TB/s (27 % of HBM); here a lane loads whole 16-byte vectors, widens
 // them to fp32 once (a shift / a mask per element) and keeps the 3 x NC window in fp32 registers. Weights, scale, shift stay fp32 in registers; arithmetic and rounding are the 4-channel kernel's.
-typedef unsigned u4v __attribute__((ext_vector_type(4)));
-typedef float f8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f8 widen8(u4v p)
-{
-    f8 r;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        r[2 * i] = __builtin_bit_cast(float, p[i] << 16);
-        r[2 * i + 1] = __builtin_bit_cast(float, p[i] & 0xffff0000u);
-    }
-    return r;
-}
-__device__ __forceinline__ f8 ld8f(const float *p)
-{
-    const f4 a = *reinterpret_cast<const f4 *>(p), b = *reinterpret_cast<const f4 *>(p + 4);
-    return f8{ a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
-}
-
 template <int NC>
 __device__ __forceinline__ void load_row8(const DwArgs &a, const __bf16 *img, int iy, int ix0, int c, f8 (&rf)[NC])
 {
-    u4v r[NC];
+    u4 r[NC];
     const bool rowok = iy >= 0 && iy < a.in_rows;
     const __bf16 *row = img + ((long)iy * a.in_cols) * a.ch + c;
 #pragma unroll
     for (int j = 0; j < NC; j++) {
         const int ix = ix0 + j;
-        r[j] = (rowok && ix >= 0 && ix < a.in_cols) ? *reinterpret_cast<const u4v *>(row + (long)ix * a.ch) : u4v{ 0u, 0u, 0u, 0u };
+        r[j] = (rowok && ix >= 0 && ix < a.in_cols) ? *reinterpret_cast<const u4 *>(row + (long)ix * a.ch) : u4{ 0u, 0u, 0u, 0u };
     }
 #pragma unroll
-    for (int j = 0; j < NC; j++) rf[j] = widen8(r[j]);          // each element is widened once, not once per tap
+    for (int j = 0; j < NC; j++) rf[j] = mbn_widen8(r[j]);      // each element is widened once, not once per tap
 }
 
 // the packed half of load_row8: issue the loads of one input row, widen later (row prefetch, stride 1)
 template <int NC>
-__device__ __forceinline__ void load_row8_packed(const DwArgs &a, const __bf16 *img, int iy, int ix0, int c, u4v (&r)[NC])
+__device__ __forceinline__ void load_row8_packed(const DwArgs &a, const __bf16 *img, int iy, int ix0, int c, u4 (&r)[NC])
 {
     const bool rowok = iy >= 0 && iy < a.in_rows;
     const __bf16 *row = img + ((long)iy * a.in_cols) * a.ch + c;
 #pragma unroll
     for (int j = 0; j < NC; j++) {
         const int ix = ix0 + j;
-        r[j] = (rowok && ix >= 0 && ix < a.in_cols) ? *reinterpret_cast<const u4v *>(row + (long)ix * a.ch) : u4v{ 0u, 0u, 0u, 0u };
+        r[j] = (rowok && ix >= 0 && ix < a.in_cols) ? *reinterpret_cast<const u4 *>(row + (long)ix * a.ch) : u4{ 0u, 0u, 0u, 0u };
     }
 }
 
@@ -310,10 +283,10 @@ __global__ __launch_bounds__(256) void dw3x3_nhwc_bf16x8(DwArgs a)
 
     f8 w[9];
 #pragma unroll
-    for (int k = 0; k < 9; k++) w[k] = ld8f(a.filt + (long)k * a.ch + c);
+    for (int k = 0; k < 9; k++) w[k] = mbn_ld8(a.filt + (long)k * a.ch + c);
     const f8 one = f8{ 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f }, zero = one - one;
-    const f8 sc = a.scale ? ld8f(a.scale + c) : one;
-    const f8 sh = a.shift ? ld8f(a.shift + c) : zero;
+    const f8 sc = a.scale ? mbn_ld8(a.scale + c) : one;
+    const f8 sh = a.shift ? mbn_ld8(a.shift + c) : zero;
 
     const __bf16 *img = reinterpret_cast<const __bf16 *>(a.in) + (long)n * a.in_rows * a.in_cols * a.ch;
     __bf16 *op = reinterpret_cast<__bf16 *>(a.out) + (((long)n * a.rows) * a.cols + ox0) * a.ch + c;
@@ -329,7 +302,7 @@ __global__ __launch_bounds__(256) void dw3x3_nhwc_bf16x8(DwArgs a)
     // lane has two rows of loads in flight instead of one. With the fp32 window, nine fp32 tap vectors and scale/shift this
     // kernel sits at ~190 VGPRs = 2 waves per SIMD, and with one row (4 KB per wave) in flight the stride-1 layers were
     // latency-bound at 3.7-4.3 TB/s (the stride-2 lanes request twice the bytes per step and reach 4.9-5.6).
-    u4v pk[NC];
+    u4 pk[NC];
     if (STRIDE == 1) load_row8_packed<NC>(a, img, iy + 2, ix0, c, pk);
 
     for (int oy = oy0; oy < oy1; oy++) {
@@ -338,10 +311,10 @@ __global__ __launch_bounds__(256) void dw3x3_nhwc_bf16x8(DwArgs a)
             load_row8<NC>(a, img, iy + 1, ix0, c, r1);
             load_row8<NC>(a, img, iy + 2, ix0, c, r2);
         } else {
-            u4v nx[NC];
+            u4 nx[NC];
             if (oy + 1 < oy1) load_row8_packed<NC>(a, img, iy + 3, ix0, c, nx);       // next output row's new input row
 #pragma unroll
-            for (int j = 0; j < NC; j++) r2[j] = widen8(pk[j]);
+            for (int j = 0; j < NC; j++) r2[j] = mbn_widen8(pk[j]);
 #pragma unroll
             for (int j = 0; j < NC; j++) pk[j] = nx[j];
         }
@@ -362,8 +335,7 @@ __global__ __launch_bounds__(256) void dw3x3_nhwc_bf16x8(DwArgs a)
             if (TW == 1 || ox0 + p < a.cols) {
                 __bf16 *o = op + ((long)oy * a.cols + p) * a.ch;
                 const f4 lo = act4(f4{ acc[0], acc[1], acc[2], acc[3] }, a.act), hi = act4(f4{ acc[4], acc[5], acc[6], acc[7] }, a.act);
-                typedef __bf16 bf8v __attribute__((ext_vector_type(8)));
-                *reinterpret_cast<bf8v *>(o) = bf8v{ (__bf16)lo.x, (__bf16)lo.y, (__bf16)lo.z, (__bf16)lo.w,
+                *reinterpret_cast<bf8 *>(o) = bf8{ (__bf16)lo.x, (__bf16)lo.y, (__bf16)lo.z, (__bf16)lo.w,
                                                     (__bf16)hi.x, (__bf16)hi.y, (__bf16)hi.z, (__bf16)hi.w };   // RNE
             }
         }
@@ -399,7 +371,6 @@ __global__ __launch_bounds__(256) void dw3x3_lds_bf16(DwLdsBfArgs a)
 {
     constexpr int RING = LAO + 3;
     constexpr int ROWF = 2048;                          // floats per ring row (8 KB): 64 pixels x 32 words (64 bf16)
-    constexpr unsigned OOB = 0xF0000000u;
     __shared__ __attribute__((aligned(16))) float ring[RING * ROWF];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -420,7 +391,7 @@ __global__ __launch_bounds__(256) void dw3x3_lds_bf16(DwLdsBfArgs a)
         const int sp = (wave_u * 2 + k) * 8 + (lane >> 3);
         const int g = sp / a.SW, ix = sp % a.SW - a.pad_left;
         const bool ok = g < a.G && n0 + g < a.batch && ix >= 0 && ix < a.w;
-        col_off[k] = ok ? (unsigned)(n0 + g) * img_bytes + (unsigned)((ix * a.ch + c0 + (lane & 7) * 8) * 2) : OOB;
+        col_off[k] = ok ? (unsigned)(n0 + g) * img_bytes + (unsigned)((ix * a.ch + c0 + (lane & 7) * 8) * 2) : MBN_OOB;
     }
     auto issue_row = [&](int iy) __attribute__((always_inline)) {
         const int slot = (iy + 2 * RING) % RING;                                    // iy >= -1
@@ -429,21 +400,21 @@ __global__ __launch_bounds__(256) void dw3x3_lds_bf16(DwLdsBfArgs a)
 #pragma unroll
         for (int k = 0; k < 2; k++)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(irsrc, (__attribute__((address_space(3))) void *)(ring + slot * ROWF + (wave_u * 2 + k) * 256),
-                                                     16, rok ? col_off[k] : OOB, soff, 0, 0);
+                                                     16, rok ? col_off[k] : MBN_OOB, soff, 0, 0);
     };
     f8 w[9];
 #pragma unroll
-    for (int k = 0; k < 9; k++) w[k] = ld8f(a.filt + (long)k * a.ch + c0 + q * 8);
+    for (int k = 0; k < 9; k++) w[k] = mbn_ld8(a.filt + (long)k * a.ch + c0 + q * 8);
     const f8 one = f8{ 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f }, zero = one - one;
-    const f8 sc = a.scale ? ld8f(a.scale + c0 + q * 8) : one;
-    const f8 sh = a.shift ? ld8f(a.shift + c0 + q * 8) : zero;
+    const f8 sc = a.scale ? mbn_ld8(a.scale + c0 + q * 8) : one;
+    const f8 sh = a.shift ? mbn_ld8(a.shift + c0 + q * 8) : zero;
     // outputs of this lane: centre pixels 2 pi + p (p = 0, 1); window columns 2 pi - 1 .. 2 pi + 2 (clamped: the clamped ones feed invalid outputs only)
     unsigned st_off[2];
 #pragma unroll
     for (int p = 0; p < 2; p++) {
         const int sp = 2 * pi + p, g = sp / a.SW, ox = sp % a.SW - a.pad_left;
         const bool ok = g < a.G && n0 + g < a.batch && ox >= 0 && ox < a.w;
-        st_off[p] = ok ? (unsigned)(n0 + g) * img_bytes + (unsigned)((ox * a.ch + c0 + q * 8) * 2) : OOB;
+        st_off[p] = ok ? (unsigned)(n0 + g) * img_bytes + (unsigned)((ox * a.ch + c0 + q * 8) * 2) : MBN_OOB;
     }
     int rd[4];                                                                      // word offsets of the four window columns inside a ring row
 #pragma unroll
@@ -451,7 +422,7 @@ __global__ __launch_bounds__(256) void dw3x3_lds_bf16(DwLdsBfArgs a)
     auto read_row = [&](int iy, f8 (&r)[4]) __attribute__((always_inline)) {
         const float *rp = ring + ((iy + 2 * RING) % RING) * ROWF;
 #pragma unroll
-        for (int j = 0; j < 4; j++) r[j] = widen8(*reinterpret_cast<const u4v *>(rp + rd[j]));
+        for (int j = 0; j < 4; j++) r[j] = mbn_widen8(*reinterpret_cast<const u4 *>(rp + rd[j]));
     };
     const int iy_first = oy0 - a.pad_top;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                // the tap / scale loads: keep the counted waits exact
@@ -460,13 +431,11 @@ __global__ __launch_bounds__(256) void dw3x3_lds_bf16(DwLdsBfArgs a)
     for (int oy = oy0; oy < oy1; oy++) {
         const int iy = oy - a.pad_top;
         const int t = oy - oy0;
-#define MBN_DWB_WAIT(N) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((N) > 63 ? 63 : (N)) : "memory")
-        if (t >= LAO) MBN_DWB_WAIT(2 + (LAO - 1) * 4);
-        else if (t == 0) MBN_DWB_WAIT((LAO - 1) * 2);
-        else if (t == 1) MBN_DWB_WAIT((LAO - 1) * 2 + 2);
-        else if (t == 2) MBN_DWB_WAIT((LAO - 1) * 2 + 4);
-        else MBN_DWB_WAIT((LAO - 1) * 2 + 6);
-#undef MBN_DWB_WAIT
+        if (t >= LAO) mbn_waitcnt<2 + (LAO - 1) * 4, true, false>();
+        else if (t == 0) mbn_waitcnt<(LAO - 1) * 2, true, false>();
+        else if (t == 1) mbn_waitcnt<(LAO - 1) * 2 + 2, true, false>();
+        else if (t == 2) mbn_waitcnt<(LAO - 1) * 2 + 4, true, false>();
+        else mbn_waitcnt<(LAO - 1) * 2 + 6, true, false>();
         static_assert(LAO <= 4, "the chain above covers t < LAO <= 4");
         issue_row(iy + 2 + LAO);                                                    // the new row of output row oy + LAO
         if (t == 0) { read_row(iy, r0); read_row(iy + 1, r1); }
@@ -486,9 +455,8 @@ __global__ __launch_bounds__(256) void dw3x3_lds_bf16(DwLdsBfArgs a)
             acc = __builtin_elementwise_fma(r2[p + 2], w[8], acc);
             acc = __builtin_elementwise_fma(acc, sc, sh);
             const f4 lo = act4(f4{ acc[0], acc[1], acc[2], acc[3] }, a.act), hi = act4(f4{ acc[4], acc[5], acc[6], acc[7] }, a.act);
-            typedef __bf16 bf8v __attribute__((ext_vector_type(8)));
-            const bf8v o = bf8v{ (__bf16)lo.x, (__bf16)lo.y, (__bf16)lo.z, (__bf16)lo.w, (__bf16)hi.x, (__bf16)hi.y, (__bf16)hi.z, (__bf16)hi.w };   // RNE
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, o), orsrc, st_off[p] == OOB ? OOB : st_off[p] + orow, 0, 0);
+            const bf8 o = bf8{ (__bf16)lo.x, (__bf16)lo.y, (__bf16)lo.z, (__bf16)lo.w, (__bf16)hi.x, (__bf16)hi.y, (__bf16)hi.z, (__bf16)hi.w };   // RNE
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, o), orsrc, st_off[p] == MBN_OOB ? MBN_OOB : st_off[p] + orow, 0, 0);
         }
 #pragma unroll
         for (int j = 0; j < 4; j++) { r0[j] = r1[j]; r1[j] = r2[j]; }
@@ -584,7 +552,6 @@ __global__ __launch_bounds__(256) void dw3x3_lds(DwLdsArgs a)
     constexpr int QL = CH / 4;                          // lanes per pixel (8 / 16)
     constexpr int PP = 256 / QL;                        // pixels per pass (32 / 16): two passes per row
     constexpr int PPC = 64 / QL;                        // pixels per DMA piece (8 / 4)
-    constexpr unsigned OOB = 0xF0000000u;
     __shared__ __attribute__((aligned(16))) float ring[RING * ROWF];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -600,7 +567,7 @@ __global__ __launch_bounds__(256) void dw3x3_lds(DwLdsArgs a)
     const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.in) + (size_t)n * a.in_rows * a.in_cols * a.ch, 0, a.in_img_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(a.out + (size_t)n * a.rows * a.cols * a.ch, 0, a.out_img_bytes, 0x00020000);
 
-    // the two DMA pieces of this wave per input row: ring pixels (2 wave + k) * PPC + lane / QL; column part of the source offset, or OOB
+    // the two DMA pieces of this wave per input row: ring pixels (2 wave + k) * PPC + lane / QL; column part of the source offset, or MBN_OOB
     unsigned col_off[2];
 #pragma unroll
     for (int k = 0; k < 2; k++) {
@@ -608,7 +575,7 @@ __global__ __launch_bounds__(256) void dw3x3_lds(DwLdsArgs a)
         const int rel = S == 1 ? sp : (sp < PX / 2 ? 2 * sp : 2 * (sp - PX / 2) + 1); // relative input column held in that slot
         const int ix = ix0 + rel;
         const bool ok = ix >= 0 && ix < a.in_cols && rel < a.tw * S + 2;
-        col_off[k] = ok ? (unsigned)((ix * a.ch + c0 + (lane % QL) * 4) * 4) : OOB;
+        col_off[k] = ok ? (unsigned)((ix * a.ch + c0 + (lane % QL) * 4) * 4) : MBN_OOB;
     }
     const unsigned row_bytes = (unsigned)(a.in_cols * a.ch * 4);
     auto issue_row = [&](int iy) __attribute__((always_inline)) {                 // input row iy -> ring slot iy mod RING (iy may be outside: zeros)
@@ -618,7 +585,7 @@ __global__ __launch_bounds__(256) void dw3x3_lds(DwLdsArgs a)
 #pragma unroll
         for (int k = 0; k < 2; k++)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(irsrc, (__attribute__((address_space(3))) void *)(ring + slot * ROWF + (wave_u * 2 + k) * 256),
-                                                     16, rok ? col_off[k] : OOB, soff, 0, 0);
+                                                     16, rok ? col_off[k] : MBN_OOB, soff, 0, 0);
     };
     f4 w[9];
 #pragma unroll
@@ -632,7 +599,7 @@ __global__ __launch_bounds__(256) void dw3x3_lds(DwLdsArgs a)
     for (int ps = 0; ps < 2; ps++) {
         px[ps] = tid / QL + PP * ps;
         const bool ok = px[ps] < a.tw && ox0 + px[ps] < a.cols;
-        st_off[ps] = ok ? (unsigned)(((ox0 + px[ps]) * a.ch + c0 + q * 4) * 4) : OOB;
+        st_off[ps] = ok ? (unsigned)(((ox0 + px[ps]) * a.ch + c0 + q * 4) * 4) : MBN_OOB;
         if (!ok) px[ps] = 0;                                                        // reads stay inside the ring row
     }
     auto tap_slot = [&](int p, int dx) __attribute__((always_inline)) {
@@ -649,15 +616,13 @@ __global__ __launch_bounds__(256) void dw3x3_lds(DwLdsArgs a)
         // (LAO - 1) x (S rows x 2 pieces + 2 stores); iterations t < LAO still wait for rows of the prologue: 2 S (LAO - 1 - t) younger
         // pieces of it + t x (2 S pieces + 2 stores) = 2 S (LAO - 1) + 2 t
         const int t = oy - oy0;
-#define MBN_DWL_WAIT(N) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((N) > 63 ? 63 : (N)) : "memory")
-        if (t >= LAO) MBN_DWL_WAIT(2 + (LAO - 1) * (2 * S + 2));
-        else if (t == 0) MBN_DWL_WAIT((LAO - 1) * 2 * S);
-        else if (t == 1) MBN_DWL_WAIT((LAO - 1) * 2 * S + 2);
-        else if (t == 2) MBN_DWL_WAIT((LAO - 1) * 2 * S + 4);
-        else if (t == 3) MBN_DWL_WAIT((LAO - 1) * 2 * S + 6);
-        else if (t == 4) MBN_DWL_WAIT((LAO - 1) * 2 * S + 8);
-        else MBN_DWL_WAIT((LAO - 1) * 2 * S + 10);
-#undef MBN_DWL_WAIT
+        if (t >= LAO) mbn_waitcnt<2 + (LAO - 1) * (2 * S + 2), true, false>();
+        else if (t == 0) mbn_waitcnt<(LAO - 1) * 2 * S, true, false>();
+        else if (t == 1) mbn_waitcnt<(LAO - 1) * 2 * S + 2, true, false>();
+        else if (t == 2) mbn_waitcnt<(LAO - 1) * 2 * S + 4, true, false>();
+        else if (t == 3) mbn_waitcnt<(LAO - 1) * 2 * S + 6, true, false>();
+        else if (t == 4) mbn_waitcnt<(LAO - 1) * 2 * S + 8, true, false>();
+        else mbn_waitcnt<(LAO - 1) * 2 * S + 10, true, false>();
         static_assert(LAO <= 6, "the chain above covers t < LAO <= 6");
         // rows of output row oy + LAO (their ring slots held rows of output row oy - 1 and older: every wave is past them)
 #pragma unroll
@@ -673,8 +638,7 @@ __global__ __launch_bounds__(256) void dw3x3_lds(DwLdsArgs a)
                 for (int dx = 0; dx < 3; dx++) acc = fma4(*reinterpret_cast<const f4 *>(rp + tap_slot(px[ps], dx) * CH), w[dy * 3 + dx], acc);
             }
             acc = act4(fma4(acc, sc, sh), a.act);
-            typedef unsigned u4e __attribute__((ext_vector_type(4)));
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4e, acc), orsrc, st_off[ps] == OOB ? OOB : st_off[ps] + orow, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, acc), orsrc, st_off[ps] == MBN_OOB ? MBN_OOB : st_off[ps] + orow, 0, 0);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }

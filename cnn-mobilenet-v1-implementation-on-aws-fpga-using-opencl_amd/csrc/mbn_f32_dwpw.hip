@@ -28,15 +28,10 @@
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef mbn_f16v f16v;
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
-
 constexpr int BM = 128, BKF = 32;
 constexpr int NCW = 8, NPW = 8;                // consumer / producer waves: waves land on SIMD (wave % 4), so every SIMD
 constexpr int NT = 64 * (NCW + NPW);           // hosts two MFMA-issuing waves and two VALU/memory waves (128 VGPRs each)
 constexpr int CMAX = MBN_CMAX;                 // largest Cin (depthwise constants resident in LDS: 44 KB)
-constexpr unsigned OOB = MBN_OOB;              // byte offset beyond any supported tensor: the load returns zeros
 
 struct DwPwArgs {
     float *out;
@@ -49,18 +44,6 @@ struct DwPwArgs {
     unsigned in_bytes;
     unsigned wo_m, wo_s, ho_m, ho_s;   // floor(v / wo) = umulhi(v, wo_m) >> wo_s for v < 2^31 (m == 0: the divisor is 1)
 };
-
-__device__ __forceinline__ int swz(int row, int chunk) { return (row << 5) + (((chunk ^ (row >> 1)) & 7) << 2); }
-__device__ __forceinline__ float relu6(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
-__device__ __forceinline__ f4 bn_relu6(f4 a, f4 s, f4 b)
-{
-    return f4{ relu6(fmaf(a.x, s.x, b.x)), relu6(fmaf(a.y, s.y, b.y)), relu6(fmaf(a.z, s.z, b.z)), relu6(fmaf(a.w, s.w, b.w)) };
-}
-__device__ __forceinline__ int xcd_remap(int vb, int nwg)
-{
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = vb & 7;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (vb >> 3);
-}
 
 template <int S, int BN>
 __global__ __launch_bounds__(NT) void dwpw_f32(DwPwArgs a)
@@ -99,7 +82,7 @@ __global__ __launch_bounds__(NT) void dwpw_f32(DwPwArgs a)
         unsigned off[3][XC];
         const float *b_src[B_LD];
         auto set_tile = [&](int v) __attribute__((always_inline)) {
-            const int lid = xcd_remap(v, nwg);
+            const int lid = mbn_xcd_remap(v, nwg);
             const int n0 = (lid % a.nt) * BN;
             const unsigned m = (unsigned)(lid / a.nt) * BM + 2 * pair;
             const bool mok = m < mtot;
@@ -119,7 +102,7 @@ __global__ __launch_bounds__(NT) void dwpw_f32(DwPwArgs a)
 #pragma unroll
                 for (int j = 0; j < XC; j++) {
                     const bool ok = rok && (unsigned)(ix0 + j) < (unsigned)a.w;
-                    off[dy][j] = ok ? base + dy * rs + j * cs : OOB;
+                    off[dy][j] = ok ? base + dy * rs + j * cs : MBN_OOB;
                 }
             }
 #pragma unroll
@@ -156,8 +139,8 @@ __global__ __launch_bounds__(NT) void dwpw_f32(DwPwArgs a)
                 }
             const f4 s = *reinterpret_cast<const f4 *>(sb_s + kc * 32 + c4 * 4);
             const f4 b = *reinterpret_cast<const f4 *>(sb_s + a.cin + kc * 32 + c4 * 4);
-            *reinterpret_cast<f4 *>(a_s0 + buf * BM * BKF + swz(2 * pair, c4)) = bn_relu6(acc0, s, b);
-            *reinterpret_cast<f4 *>(a_s0 + buf * BM * BKF + swz(2 * pair + 1, c4)) = bn_relu6(acc1, s, b);
+            *reinterpret_cast<f4 *>(a_s0 + buf * BM * BKF + mbn_swz(2 * pair, c4)) = mbn_bn_relu6(acc0, s, b);
+            *reinterpret_cast<f4 *>(a_s0 + buf * BM * BKF + mbn_swz(2 * pair + 1, c4)) = mbn_bn_relu6(acc1, s, b);
         };
 
         // cursor = the chunk whose input loads are in flight: (tile cvb, chunk ckc)
@@ -177,9 +160,9 @@ __global__ __launch_bounds__(NT) void dwpw_f32(DwPwArgs a)
         bool have = advance();
         if (have) {
             ldx(ckc);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NX) : "memory");     // filter chunk 0 landed; the NX newer loads may fly
+            mbn_waitcnt<NX, false, false>();                              // filter chunk 0 landed; the NX newer loads may fly
         } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            mbn_waitcnt<0, false, false>();
         }
         __syncthreads();                                                  // chunk 0 handed to the consumers
         int p = 0;
@@ -191,9 +174,9 @@ __global__ __launch_bounds__(NT) void dwpw_f32(DwPwArgs a)
             have = advance();
             if (have) {
                 ldx(ckc);
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NX) : "memory");
+                mbn_waitcnt<NX, false, false>();
             } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                mbn_waitcnt<0, false, false>();
             }
             __syncthreads();
             p ^= 1;
@@ -210,7 +193,7 @@ __global__ __launch_bounds__(NT) void dwpw_f32(DwPwArgs a)
     __syncthreads();                                                      // chunk 0 is in buffer 0
     int p = 0;
     for (int vb = blockIdx.x; vb < nwg; vb += gridDim.x) {
-        const int lid = xcd_remap(vb, nwg);
+        const int lid = mbn_xcd_remap(vb, nwg);
         const int n0 = (lid % a.nt) * BN;
         const unsigned m0 = (unsigned)(lid / a.nt) * BM;
         f16v acc[MI][NI];
@@ -227,9 +210,9 @@ __global__ __launch_bounds__(NT) void dwpw_f32(DwPwArgs a)
                 const int chunk = 2 * g + lh;
                 f4 av[MI], bv[NI];
 #pragma unroll
-                for (int mi = 0; mi < MI; mi++) av[mi] = *reinterpret_cast<const f4 *>(As + swz(wm + mi * 32 + li, chunk));
+                for (int mi = 0; mi < MI; mi++) av[mi] = *reinterpret_cast<const f4 *>(As + mbn_swz(wm + mi * 32 + li, chunk));
 #pragma unroll
-                for (int ni = 0; ni < NI; ni++) bv[ni] = *reinterpret_cast<const f4 *>(Bs + swz(wn + ni * 32 + li, chunk));
+                for (int ni = 0; ni < NI; ni++) bv[ni] = *reinterpret_cast<const f4 *>(Bs + mbn_swz(wn + ni * 32 + li, chunk));
 #pragma unroll
                 for (int s = 0; s < 4; s++)
 #pragma unroll

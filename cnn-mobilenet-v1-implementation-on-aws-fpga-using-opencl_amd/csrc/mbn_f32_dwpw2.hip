@@ -38,15 +38,11 @@
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef mbn_f16v f16v;
-
 constexpr int BKF = 32;
 constexpr int BM8 = 128;                       // rows of the shipped 8-wave tile (2 waves per SIMD, 256 VGPRs each); the 16-wave lab form: 256
 constexpr int NOUT = MBN_COUT_MAX;             // widest pointwise output whose scale/shift the LDS copy holds
 constexpr int CMAX = MBN_CMAX;                 // largest Cin (depthwise constants resident in LDS: 44 KB)
 constexpr int CMAX4 = 256, NOUT4 = 256;        // ... of the 4-wave form (two workgroups per CU: 66 KB of LDS each)
-constexpr unsigned OOB = MBN_OOB;              // byte offset beyond any supported tensor: the load returns zeros
 
 // In-kernel stamps (diagnostic: dwpw_variant = 100 + 64): workgroup 0 records s_memtime at five points of its first 96 steps,
 // per wave; read back with mbn_debug_dwpw2_stamps (tools/stamp_dwpw2.py). No output value depends on them.
@@ -69,30 +65,6 @@ struct DwPw2Args {
     int fast_off;           // launcher: 1 = the FO instantiation (set_offsets in its full-rate form: input < 0x70000000 bytes); 0 = the general form (rounds 2-4; lab A/B: exp0 = 51)
     float inv_wo, inv_ho;   // 1 / wo, 1 / ho
 };
-
-__device__ __forceinline__ int swz(int row, int chunk) { return (row << 5) + (((chunk ^ (row >> 1)) & 7) << 2); }
-__device__ __forceinline__ float relu6(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
-__device__ __forceinline__ f4 bn_relu6(f4 a, f4 s, f4 b)
-{
-    return f4{ relu6(fmaf(a.x, s.x, b.x)), relu6(fmaf(a.y, s.y, b.y)), relu6(fmaf(a.z, s.z, b.z)), relu6(fmaf(a.w, s.w, b.w)) };
-}
-__device__ __forceinline__ int xcd_remap(int vb, int nwg)
-{
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = vb & 7;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (vb >> 3);
-}
-
-// Workgroup barrier with the waits spelled out. __syncthreads() is a workgroup-scope fence over every address space: with
-// global loads in flight for the NEXT chunk the waitcnt pass drains them (s_waitcnt vmcnt(0)) in front of every barrier
-// (also with the "local"-only fence form), which serialises the prefetch with the hand-over. Here: wait until all but
-// the VM_LEFT youngest vector-memory operations are done (= the LDS-DMA of the filter chunk has landed, the x-window
-// loads issued after it may still fly), until this wave's own LDS writes are done (lgkmcnt(0)), then s_barrier. The asm
-// is volatile with a memory clobber, so the compiler moves no LDS or global access across it.
-template <int VM_LEFT>
-__device__ __forceinline__ void lds_barrier()
-{
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(VM_LEFT) : "memory");
-}
 
 // pointwise filter chunk -> LDS, buffer form (a __device__ function: see mbn_f32_pw.hip lds_dma_rows)
 template <int B_LD, int NT, int BN>
@@ -178,12 +150,12 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_f32(DwPw2Args a)
     const __amdgpu_buffer_rsrc_t irsrc = mbn_make_rsrc(a.in, a.in_bytes);
     const __amdgpu_buffer_rsrc_t wrsrc = mbn_make_rsrc(a.wp, a.wp_bytes);
     const __amdgpu_buffer_rsrc_t orsrc = mbn_make_rsrc(a.out, (unsigned)(a.m * a.cout * 4));
-    const int aw0 = swz(2 * pair, c4), aw1 = swz(2 * pair + 1, c4);           // A-tile slots this lane writes
+    const int aw0 = mbn_swz(2 * pair, c4), aw1 = mbn_swz(2 * pair + 1, c4);   // A-tile slots this lane writes
     int fr_a[4], fr_b[4];                                                       // fragment slots this lane reads
 #pragma unroll
     for (int g = 0; g < 4; g++) {
-        fr_a[g] = swz(wm + li, 2 * g + lh);
-        fr_b[g] = swz(wn + li, 2 * g + lh);
+        fr_a[g] = mbn_swz(wm + li, 2 * g + lh);
+        fr_b[g] = mbn_swz(wn + li, 2 * g + lh);
     }
     const bool paired = !(dbg & 32);
     unsigned b_vo[B_LD];                                                        // filter piece offsets: fixed for the kernel, the tile's
@@ -214,7 +186,7 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_f32(DwPw2Args a)
 #pragma unroll
             for (int j = 0; j < XC; j++) {
                 const bool ok = rok && (unsigned)(ix0 + j) < (unsigned)a.w;
-                off[dy][j] = ok ? base + dy * rs + j * cs : OOB;
+                off[dy][j] = ok ? base + dy * rs + j * cs : MBN_OOB;
             }
         }
     };
@@ -300,8 +272,8 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_f32(DwPw2Args a)
                 }
             }
             const f4 sc2 = *reinterpret_cast<const f4 *>(sk + kc * 32), sh2 = *reinterpret_cast<const f4 *>(sk + a.cin + kc * 32);
-            *reinterpret_cast<f4 *>(a_s0 + buf * ABUF + aw0) = bn_relu6(acc0, sc2, sh2);
-            *reinterpret_cast<f4 *>(a_s0 + buf * ABUF + aw1) = bn_relu6(acc1, sc2, sh2);
+            *reinterpret_cast<f4 *>(a_s0 + buf * ABUF + aw0) = mbn_bn_relu6(acc0, sc2, sh2);
+            *reinterpret_cast<f4 *>(a_s0 + buf * ABUF + aw1) = mbn_bn_relu6(acc1, sc2, sh2);
             return;
         }
         if (!PRE) ldw(kc);
@@ -312,8 +284,8 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_f32(DwPw2Args a)
                 acc0 = __builtin_elementwise_fma(xr[set][dy][dx], wreg[dy * 3 + dx], acc0);
                 acc1 = __builtin_elementwise_fma(xr[set][dy][dx + S], wreg[dy * 3 + dx], acc1);
             }
-        *reinterpret_cast<f4 *>(a_s0 + buf * ABUF + aw0) = bn_relu6(acc0, wreg[9], wreg[10]);
-        *reinterpret_cast<f4 *>(a_s0 + buf * ABUF + aw1) = bn_relu6(acc1, wreg[9], wreg[10]);
+        *reinterpret_cast<f4 *>(a_s0 + buf * ABUF + aw0) = mbn_bn_relu6(acc0, wreg[9], wreg[10]);
+        *reinterpret_cast<f4 *>(a_s0 + buf * ABUF + aw1) = mbn_bn_relu6(acc1, wreg[9], wreg[10]);
     };
     auto dw = [&](int kc, const int buf) __attribute__((always_inline)) { dw_set(kc, buf, 0); };
     // IL: the same arithmetic in pieces. ldx_row: the XC loads of one window row; dw_row: that row's taps into the two running sums (dy = 0 starts them);
@@ -350,8 +322,8 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_f32(DwPw2Args a)
         else ldw_ss(kc);
     };
     auto dw_fin = [&](const int buf) __attribute__((always_inline)) {
-        *reinterpret_cast<f4 *>(a_s0 + buf * ABUF + aw0) = bn_relu6(dacc0, wss[0], wss[1]);
-        *reinterpret_cast<f4 *>(a_s0 + buf * ABUF + aw1) = bn_relu6(dacc1, wss[0], wss[1]);
+        *reinterpret_cast<f4 *>(a_s0 + buf * ABUF + aw0) = mbn_bn_relu6(dacc0, wss[0], wss[1]);
+        *reinterpret_cast<f4 *>(a_s0 + buf * ABUF + aw1) = mbn_bn_relu6(dacc1, wss[0], wss[1]);
     };
 
     f16v acc[MI][NI];
@@ -386,7 +358,7 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_f32(DwPw2Args a)
     int vbD, kD, n0D; unsigned m0D;
     bool validD;
     auto origin = [&](int vb, unsigned &m0, int &n0) __attribute__((always_inline)) {
-        const int lid = xcd_remap(vb, nwg);
+        const int lid = mbn_xcd_remap(vb, nwg);
         n0 = (lid % a.nt) * BN;
         m0 = (unsigned)(lid / a.nt) * BM;
     };
@@ -424,18 +396,18 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_f32(DwPw2Args a)
     }
     zero_acc();
     if constexpr (XA2) {
-        if (validL1) lds_barrier<2 * NX>();   // filter chunk 0 landed; the two newer windows may fly
-        else if (validD) lds_barrier<NX>();
-        else lds_barrier<0>();
+        if (validL1) mbn_waitcnt<2 * NX>();   // filter chunk 0 landed; the two newer windows may fly
+        else if (validD) mbn_waitcnt<NX>();
+        else mbn_waitcnt<0>();
     } else {
-    if (validD) lds_barrier<NX>();        // filter chunk 0 landed; the NX newer loads may fly
-    else lds_barrier<0>();
+    if (validD) mbn_waitcnt<NX>();        // filter chunk 0 landed; the NX newer loads may fly
+    else mbn_waitcnt<0>();
     }
 
     // The finished tile's epilogue is issued in the NEXT step, behind that step's depthwise part and filter DMA and ahead of its MFMAs
     // (round 3). vmcnt retires in order: with the 16 / 32 stores issued right behind the barrier — ahead of the next step's filter DMA —
     // the counted wait in front of the next barrier (filter landed) also waited for every store to be acknowledged, once per tile.
-    // Behind the DMA they are YOUNGER than what that wait needs and stay in flight (lds_barrier<NX + NST>). The accumulators are not
+    // Behind the DMA they are YOUNGER than what that wait needs and stay in flight (mbn_waitcnt<NX + NST>). The accumulators are not
     // touched by the depthwise part, so no second set is needed (the r2 attempt deferred the stores behind the x loads too, i.e. under
     // the MFMAs, and paid for it in registers). Measured (profiles/r03/q_block_more_waves.txt, second table): block 6-7 -0.7 %, blocks
     // 4-5 and 8-9 unchanged — like r2's three-slot experiment it says the "-13 % without the stores" of the ablation is the store
@@ -507,8 +479,8 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_f32(DwPw2Args a)
         STAMP(3);                                                                                                       \
         if (PRE && validL && !(dbg & 1024)) ldw(kL);                                                                    \
         if (dbg & 4096) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }                                 \
-        else if (validL) { if (didE) lds_barrier<NX + NST>(); else lds_barrier<NX>(); }                                 \
-        else { if (didE) lds_barrier<NST>(); else lds_barrier<0>(); }                                                   \
+        else if (validL) { if (didE) mbn_waitcnt<NX + NST>(); else mbn_waitcnt<NX>(); }                                 \
+        else { if (didE) mbn_waitcnt<NST>(); else mbn_waitcnt<0>(); }                                                   \
         STAMP(4);                                                                                                       \
         if (kM == nk - 1) { pendE = true; m0E = m0M; n0E = n0M; }      /* stored in the next step (or behind the loop) */ \
         STAMP(5);                                                                                                       \
@@ -559,8 +531,8 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_f32(DwPw2Args a)
         __builtin_amdgcn_sched_barrier(0);                                                                              \
         mfma_group(1);                                                                                                  \
         if (PRE && validL1) ldw(kL);                                                                                    \
-        if (validL2) { if (didE) lds_barrier<NX + NST>(); else lds_barrier<NX>(); }                                     \
-        else { if (didE) lds_barrier<NST>(); else lds_barrier<0>(); }                                                   \
+        if (validL2) { if (didE) mbn_waitcnt<NX + NST>(); else mbn_waitcnt<NX>(); }                                     \
+        else { if (didE) mbn_waitcnt<NST>(); else mbn_waitcnt<0>(); }                                                   \
         if (kM == nk - 1) { pendE = true; m0E = m0M; n0E = n0M; }                                                       \
         if (!validD) break;                                                                                             \
         vbM = vbD; kM = kD; m0M = m0D; n0M = n0D;                                                                       \
@@ -614,7 +586,7 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_f32(DwPw2Args a)
         __builtin_amdgcn_sched_barrier(0);                                                                              \
         mfma_group(1);                                                                                                  \
         STAMP(3);                                                                                                       \
-        if (didE) lds_barrier<NX + NST>(); else lds_barrier<NX>();                                                      \
+        if (didE) mbn_waitcnt<NX + NST>(); else mbn_waitcnt<NX>();                                                      \
         STAMP(4);                                                                                                       \
         if (kM == nk - 1) { pendE = true; m0E = m0M; n0E = n0M; }      /* stored in the next step (or behind the loop) */ \
         STAMP(5);                                                                                                       \

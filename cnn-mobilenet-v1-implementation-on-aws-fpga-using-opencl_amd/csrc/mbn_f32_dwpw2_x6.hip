@@ -22,18 +22,9 @@
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef mbn_f16v f16v;
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
-typedef unsigned u2 __attribute__((ext_vector_type(2)));
-
 constexpr int BM = 128;
 constexpr int PW = 16;                         // words per plane row (32 bf16)
 constexpr int NW = 8, NT = 64 * NW;
-constexpr unsigned OOB = MBN_OOB;
 
 struct XbArgs {
     float *out;
@@ -48,17 +39,6 @@ struct XbArgs {
     unsigned wo_m, wo_s, ho_m, ho_s;
 };
 
-__device__ __forceinline__ int pswz(int row, int c) { return row * PW + (((c ^ (row >> 2)) & 3) << 2); }
-__device__ __forceinline__ float relu6(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
-__device__ __forceinline__ f4 bn_relu6(f4 a, f4 s, f4 b)
-{
-    return f4{ relu6(fmaf(a.x, s.x, b.x)), relu6(fmaf(a.y, s.y, b.y)), relu6(fmaf(a.z, s.z, b.z)), relu6(fmaf(a.w, s.w, b.w)) };
-}
-__device__ __forceinline__ int xcd_remap(int vb, int nwg)
-{
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = vb & 7;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (vb >> 3);
-}
 // 4 consecutive channels of one pixel -> the three bf16 planes (exact: h + m + l == v)
 __device__ __forceinline__ void split4(const f4 &v, u2 &H, u2 &M, u2 &L)
 {
@@ -74,12 +54,6 @@ __device__ __forceinline__ void split4(const f4 &v, u2 &H, u2 &M, u2 &L)
         M[j] = __builtin_bit_cast(unsigned, m);
         L[j] = __builtin_bit_cast(unsigned, lo);
     }
-}
-
-template <int VM_LEFT>
-__device__ __forceinline__ void lds_barrier()
-{
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(VM_LEFT) : "memory");
 }
 
 template <int NPC>
@@ -135,12 +109,12 @@ __global__ __launch_bounds__(NT) void dwpw2_x6(XbArgs a)
     const __amdgpu_buffer_rsrc_t wrsrc = mbn_make_rsrc(a.wimg, a.wimg_bytes);
     const __amdgpu_buffer_rsrc_t orsrc = mbn_make_rsrc(a.out, (unsigned)(a.m * a.cout * 4));
     // plane slots this lane writes: 8 bytes (4 channels) at chunk c4 >> 1, half c4 & 1 of rows 2*pair and 2*pair + 1
-    const int aw0 = pswz(2 * pair, c4 >> 1) + (c4 & 1) * 2, aw1 = pswz(2 * pair + 1, c4 >> 1) + (c4 & 1) * 2;
+    const int aw0 = mbn_pswz(2 * pair, c4 >> 1) + (c4 & 1) * 2, aw1 = mbn_pswz(2 * pair + 1, c4 >> 1) + (c4 & 1) * 2;
     int fr_a[2], fr_b[2];
 #pragma unroll
     for (int s = 0; s < 2; s++) {
-        fr_a[s] = pswz(wm + li, 2 * s + lh);
-        fr_b[s] = pswz(wn + li, 2 * s + lh);
+        fr_a[s] = mbn_pswz(wm + li, 2 * s + lh);
+        fr_b[s] = mbn_pswz(wn + li, 2 * s + lh);
     }
     unsigned b_vo[NPC];
 #pragma unroll
@@ -165,7 +139,7 @@ __global__ __launch_bounds__(NT) void dwpw2_x6(XbArgs a)
 #pragma unroll
             for (int j = 0; j < XC; j++) {
                 const bool ok = rok && (unsigned)(ix0 + j) < (unsigned)a.w;
-                off[dy][j] = ok ? base + dy * rs + j * cs : OOB;
+                off[dy][j] = ok ? base + dy * rs + j * cs : MBN_OOB;
             }
         }
     };
@@ -202,11 +176,11 @@ __global__ __launch_bounds__(NT) void dwpw2_x6(XbArgs a)
             }
         u2 H, M, L;
         unsigned *const ab = a_s0 + buf * ABUF;
-        split4(bn_relu6(acc0, wreg[9], wreg[10]), H, M, L);
+        split4(mbn_bn_relu6(acc0, wreg[9], wreg[10]), H, M, L);
         *reinterpret_cast<u2 *>(ab + aw0) = H;
         *reinterpret_cast<u2 *>(ab + PLANE_A + aw0) = M;
         *reinterpret_cast<u2 *>(ab + 2 * PLANE_A + aw0) = L;
-        split4(bn_relu6(acc1, wreg[9], wreg[10]), H, M, L);
+        split4(mbn_bn_relu6(acc1, wreg[9], wreg[10]), H, M, L);
         *reinterpret_cast<u2 *>(ab + aw1) = H;
         *reinterpret_cast<u2 *>(ab + PLANE_A + aw1) = M;
         *reinterpret_cast<u2 *>(ab + 2 * PLANE_A + aw1) = L;
@@ -247,7 +221,7 @@ __global__ __launch_bounds__(NT) void dwpw2_x6(XbArgs a)
     int vbD, kD, n0D; unsigned m0D;
     bool validD;
     auto origin = [&](int vb, unsigned &m0, int &n0) __attribute__((always_inline)) {
-        const int lid = xcd_remap(vb, nwg);
+        const int lid = mbn_xcd_remap(vb, nwg);
         n0 = (lid % a.nt) * BN;
         m0 = (unsigned)(lid / a.nt) * BM;
     };
@@ -270,8 +244,8 @@ __global__ __launch_bounds__(NT) void dwpw2_x6(XbArgs a)
         if (PRE) ldw(kD);
     }
     zero_acc();
-    if (validD) lds_barrier<NX>();
-    else lds_barrier<0>();
+    if (validD) mbn_waitcnt<NX>();
+    else mbn_waitcnt<0>();
 
 #define MBN_X6_STEP(P)                                                                                                  \
     {                                                                                                                   \
@@ -308,8 +282,8 @@ __global__ __launch_bounds__(NT) void dwpw2_x6(XbArgs a)
         mfma_part(NPH, NP);                                                                                             \
         __builtin_amdgcn_sched_barrier(0);                                                                              \
         if (PRE && validL) ldw(kL);                                                                                     \
-        if (validL) lds_barrier<NX>();                                                                                  \
-        else lds_barrier<0>();                                                                                          \
+        if (validL) mbn_waitcnt<NX>();                                                                                  \
+        else mbn_waitcnt<0>();                                                                                          \
         if (kM == nk - 1) {                                                                                             \
             if (m0M + BM <= mtot) mbn_store_relu6_f32_pair<MI, NI, 0>(orsrc, (unsigned)a.cout, m0M + wm, n0M + wn, lane, acc, sc3_s, sh3_s); \
             else mbn_store_relu6_f32_pair<MI, NI, 1>(orsrc, (unsigned)a.cout, m0M + wm, n0M + wn, lane, acc, sc3_s, sh3_s); \

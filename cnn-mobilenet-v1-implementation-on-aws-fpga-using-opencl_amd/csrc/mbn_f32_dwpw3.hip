@@ -34,18 +34,12 @@
 // (row >> 1) & 7 (KS 32): the ds_write_b128 of the depthwise lanes and the fragment ds_read_b128 are conflict-free (MI355X_MICROARCH.md
 // §LDS lane groups). Epilogue: LDS filter row 32 t + l holds output channel 4 l + t, so lane l's four accumulator blocks are 4 adjacent
 // channels: one buffer_store_dwordx4 per lane and row pair = 512 contiguous bytes per pixel.
-// gfx950 hazard found here (profiles/r06/a_*): a buffer_store_dwordx4 followed directly by a VALU write of its first data register stores
-// the NEW value in lanes 12-15 of every 16 (the ">64-bit store data" hazard; the compiler pads only the immediate-soffset form): the
-// epilogue issues its stores in pairs and waits two states behind each pair, pinned by sched_barriers.
+// The epilogue issues its stores in pairs, each pair followed by mbn_store_hazard_wait: the gfx950 store-data hazard of 16-byte buffer
+// stores (mbn_device.h) was found here (profiles/r06/a_*).
 #include "mbn_internal.h"
 #include "mbn_epilogue.h"
 
 namespace {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
-typedef mbn_f16v f16v;
 
 constexpr int BN3 = 128;                       // output channels per workgroup slice
 constexpr int WT = 32;                         // output pixels per wave tile (16 pixel pairs)
@@ -70,11 +64,10 @@ struct DwPw3Args {
                             // 32 no tap reads, 64 no BN / clamp / A-tile writes, 128 no fragment reads, 256 no per-tile window offsets (timing only)
 };
 
-__device__ __forceinline__ float relu6(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
-__device__ __forceinline__ f4 bn_relu6(f4 a, f4 s, f4 b)
+__device__ __forceinline__ f4 bn_relu6_pk(f4 a, f4 s, f4 b)
 {
     const f4 v = __builtin_elementwise_fma(a, s, b);          // two v_pk_fma_f32: the same single-rounding fma per component
-    return f4{ relu6(v.x), relu6(v.y), relu6(v.z), relu6(v.w) };
+    return f4{ mbn_relu6(v.x), mbn_relu6(v.y), mbn_relu6(v.z), mbn_relu6(v.w) };
 }
 
 // S = depthwise stride (1, 2), CIN = input channels (64, 128, 256), KS = channels per depthwise half-round and lane group (16: 4 lanes per
@@ -281,8 +274,8 @@ __global__ __launch_bounds__(512) void dwpw3_f32(DwPw3Args a)
     auto dw_fin = [&](const int u) __attribute__((always_inline)) {
         if (dbg & 64) return;
         const int hh = AH == 2 ? (u & 1) : 0, buf = AH == 2 ? ((u >> 1) & 1) * ABUF : 0;
-        *reinterpret_cast<f4 *>(a_w + buf + aw[hh]) = bn_relu6(dacc0, wss[0], wss[1]);
-        *reinterpret_cast<f4 *>(a_w + buf + aw[hh] + 16 * KS) = bn_relu6(dacc1, wss[0], wss[1]);
+        *reinterpret_cast<f4 *>(a_w + buf + aw[hh]) = bn_relu6_pk(dacc0, wss[0], wss[1]);
+        *reinterpret_cast<f4 *>(a_w + buf + aw[hh] + 16 * KS) = bn_relu6_pk(dacc1, wss[0], wss[1]);
     };
 
     f16v acc[4];
@@ -343,16 +336,15 @@ __global__ __launch_bounds__(512) void dwpw3_f32(DwPw3Args a)
             f4 o[2];
 #pragma unroll
             for (int hh = 0; hh < 2; hh++)
-                o[hh] = f4{ relu6(hh ? p[0].y : p[0].x), relu6(hh ? p[1].y : p[1].x), relu6(hh ? p[2].y : p[2].x), relu6(hh ? p[3].y : p[3].x) };
-            // the two stores back to back, then two wait states before any VALU instruction may write their data registers (see the header)
+                o[hh] = f4{ mbn_relu6(hh ? p[0].y : p[0].x), mbn_relu6(hh ? p[1].y : p[1].x), mbn_relu6(hh ? p[2].y : p[2].x), mbn_relu6(hh ? p[3].y : p[3].x) };
+            // the two stores back to back, then two wait states before any VALU instruction may write their data registers (mbn_store_hazard_wait)
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int hh = 0; hh < 2; hh++) {
                 const int rr = r + hh;
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, o[hh]), orsrc, vo[(rr >> 2) & 1][rr & 3], (rr >> 3) ? rowb : 0u, 0);
             }
-            asm volatile("s_nop 1" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
+            mbn_store_hazard_wait();
         }
     };
 

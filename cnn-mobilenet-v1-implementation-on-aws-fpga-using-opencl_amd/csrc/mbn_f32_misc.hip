@@ -4,17 +4,9 @@
 //   softmax (MobileNet.c:2771-2792, host loop in the reference)           classifier tail on device
 //   u8->f32 normalise (front-end for MobileNet.c:215-238's uint8 image)   HBM-bound
 #include "mbn_internal.h"
+#include "mbn_device.h"
 
 namespace {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void st4(float *p, f4 v) { *reinterpret_cast<f4 *>(p) = v; }
-__device__ __forceinline__ void st4(__bf16 *p, f4 v)
-{
-    *reinterpret_cast<bf4 *>(p) = bf4{ (__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w };   // RNE
-}
 
 struct ConvArgs {
     void *out;
@@ -78,7 +70,7 @@ __global__ __launch_bounds__(256) void conv_f32_nhwc(ConvArgs a)
     } else if (a.act == MBN_ACT_RELU) {
         v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
     }
-    st4(reinterpret_cast<TO *>(a.out) + t * 4, v);
+    mbn_st4(reinterpret_cast<TO *>(a.out) + t * 4, v);
 }
 
 // Specialisation for the network's first layer (3x3, Cin = 3, stride 2): one lane = 4 consecutive output channels of
@@ -168,7 +160,7 @@ __global__ __launch_bounds__(256) void conv3x3s2c3_f32_nhwc(ConvArgs a)
         } else if (a.act == MBN_ACT_RELU) {
             r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f);
         }
-        st4(op + (long)p * a.cout, r);
+        mbn_st4(op + (long)p * a.cout, r);
     }
 }
 
@@ -374,7 +366,6 @@ __global__ __launch_bounds__(256) void poolfc_f32(PoolFcArgs a)
         pooled[b][c] = acc;
     }
     __syncthreads();
-    typedef float f4 __attribute__((ext_vector_type(4)));
     const int r = tid >> 4, q = tid & 15;                       // 16 class rows per pass, 16 float4 per 64-channel slice
     f4 pv[4];
 #pragma unroll
@@ -608,7 +599,7 @@ __global__ __launch_bounds__(256) void normalize_u8_f32(float *__restrict__ out,
 __global__ __launch_bounds__(256) void convert_f32_bf16(__bf16 *__restrict__ dst, const float *__restrict__ src, size_t count)
 {
     const size_t t = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (t + 3 < count) st4(dst + t, *reinterpret_cast<const f4 *>(src + t));
+    if (t + 3 < count) mbn_st4(dst + t, *reinterpret_cast<const f4 *>(src + t));
     else for (size_t i = t; i < count; i++) dst[i] = (__bf16)src[i];
 }
 __global__ __launch_bounds__(256) void convert_bf16_f32(float *__restrict__ dst, const __bf16 *__restrict__ src, size_t count)

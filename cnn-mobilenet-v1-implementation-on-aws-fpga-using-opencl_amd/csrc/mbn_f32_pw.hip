@@ -39,10 +39,6 @@
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef mbn_f16v f16v;
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-
 #ifdef MBN_LAB
 // lab: workgroups 0..7 (one per XCD) of the last pw_gemm launch: { s_memtime at start, at end (core clock cycles), s_memrealtime at start, at end (100 MHz) }
 __device__ unsigned long long g_pw_clk[8][4];
@@ -71,16 +67,6 @@ struct PwArgs {
 constexpr int BKB = 128;            // k-tile in BYTES per row (32 fp32 / 64 bf16)
 constexpr int SSMAX = 1024;         // widest output whose scale/shift are staged in LDS for the epilogue (8 KB)
 constexpr int BKF = BKB / 4;        // ... in 4-byte LDS words
-
-__device__ __forceinline__ int swz(int row, int chunk) { return (row << 5) + (((chunk ^ (row >> 1)) & 7) << 2); }
-
-// virtual block id -> logical tile id: ids that share vb%8 (one XCD) get a contiguous range of tiles (bijective for
-// any tile count, cdna guide T1)
-__device__ __forceinline__ int xcd_remap(int vb, int nwg)
-{
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = vb & 7;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (vb >> 3);
-}
 
 // LD pieces of 8 rows x 128 B per wave: buffer_load_dwordx4 ... lds writes 1 KiB linearly at the wave-uniform LDS
 // address in M0; piece p of wave w covers tile rows p*(NT/8) + 8w .. +7. (A __device__ function, not a lambda: the host pass
@@ -141,8 +127,8 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void pw_gemm(PwArgs a)
     int fr_a[4], fr_b[4];
 #pragma unroll
     for (int g = 0; g < 4; g++) {
-        fr_a[g] = swz(wm + li, 2 * g + lh);
-        fr_b[g] = swz(wn + li, 2 * g + lh);
+        fr_a[g] = mbn_swz(wm + li, 2 * g + lh);
+        fr_b[g] = mbn_swz(wn + li, 2 * g + lh);
     }
 
     const T *a_src[A_LD];
@@ -167,7 +153,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void pw_gemm(PwArgs a)
             mtile = mlo + j / nn;
             ntile = nlo + j % nn;
         } else {
-            const int lid = xcd_remap(vb, nwg);
+            const int lid = mbn_xcd_remap(vb, nwg);
             mtile = lid / a.nt;
             ntile = lid % a.nt;
         }
@@ -199,9 +185,9 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void pw_gemm(PwArgs a)
     auto stage_store = [&](int buf) {
         float *base = lds + buf * (BM + BN) * BKF;
 #pragma unroll
-        for (int p = 0; p < A_LD; p++) *reinterpret_cast<f4 *>(base + swz(st_row[p], st_ch)) = a_reg[p];
+        for (int p = 0; p < A_LD; p++) *reinterpret_cast<f4 *>(base + mbn_swz(st_row[p], st_ch)) = a_reg[p];
 #pragma unroll
-        for (int p = 0; p < B_LD; p++) *reinterpret_cast<f4 *>(base + BM * BKF + swz(st_row[p], st_ch)) = b_reg[p];
+        for (int p = 0; p < B_LD; p++) *reinterpret_cast<f4 *>(base + BM * BKF + mbn_swz(st_row[p], st_ch)) = b_reg[p];
     };
 
     // Direct-to-LDS staging (global_load_lds_dwordx4): one wave-instruction writes 1 KiB = 8 rows x 128 B linearly
@@ -280,9 +266,9 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void pw_gemm(PwArgs a)
                 const int chunk = 2 * g + lh;
                 f4 av[MI], bv[NI];
 #pragma unroll
-                for (int mi = 0; mi < MI; mi++) av[mi] = *reinterpret_cast<const f4 *>(As + swz(wm + mi * 32 + li, chunk));
+                for (int mi = 0; mi < MI; mi++) av[mi] = *reinterpret_cast<const f4 *>(As + mbn_swz(wm + mi * 32 + li, chunk));
 #pragma unroll
-                for (int ni = 0; ni < NI; ni++) bv[ni] = *reinterpret_cast<const f4 *>(Bs + swz(wn + ni * 32 + li, chunk));
+                for (int ni = 0; ni < NI; ni++) bv[ni] = *reinterpret_cast<const f4 *>(Bs + mbn_swz(wn + ni * 32 + li, chunk));
                 if constexpr (BF) {
 #pragma unroll
                     for (int mi = 0; mi < MI; mi++)
@@ -307,7 +293,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void pw_gemm(PwArgs a)
         // with a glds outstanding hipcc emits s_waitcnt vmcnt(0) ahead of __syncthreads(): behind a tile's epilogue that also waits for every
         // store of it to be acknowledged. The fast epilogue issues exactly NSTF stores, all YOUNGER than this tile's first LDS-DMA (issued ahead of
         // them, below): a counted wait leaves them in flight for one more k-tile (vmcnt retires in order)
-        if (GLDS && prev_fast) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(NSTF) : "memory");
+        if (GLDS && prev_fast) mbn_waitcnt<NSTF>();
         else __syncthreads();
         if (GLDS && a.loop2) {
             // Software-pipelined form (default): the LDS fragments of group g+1 are requested before the MFMAs of group g

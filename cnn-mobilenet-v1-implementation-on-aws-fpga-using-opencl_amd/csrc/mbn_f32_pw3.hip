@@ -12,17 +12,12 @@
 // bit-identical to it (tests: test_f32_pointwise with pw_tile = 9), so the dispatch may depend on M.
 // LDS images as in mbn_f32_dwpw3.hip: filter rows padded to K + 4 floats, row 32 t + l = output channel 4 l + t of the slice (a lane's four
 // accumulator blocks are 4 adjacent channels: 16-byte stores, 512 contiguous bytes per pixel); A tile row = 16 (pixel & 1) + (pixel >> 1),
-// 16-byte units XORed by (row >> 2) & 3 (KS 16) / (row >> 1) & 7 (KS 32). The store-data hazard of 16-byte buffer stores found there is
-// padded here the same way (two stores, two wait states, pinned).
+// 16-byte units XORed by (row >> 2) & 3 (KS 16) / (row >> 1) & 7 (KS 32). The 16-byte stores go out in pairs behind
+// mbn_store_hazard_wait, as there (mbn_device.h: the gfx950 store-data hazard).
 #include "mbn_internal.h"
 #include "mbn_epilogue.h"
 
 namespace {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
-typedef mbn_f16v f16v;
 
 constexpr int WT = 32;
 
@@ -35,8 +30,6 @@ struct Pw3Args {
     int tiles;              // ceil(m / 32)
     unsigned in_bytes;
 };
-
-__device__ __forceinline__ float relu6(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
 
 // K = input channels; KS = channels per half-round (16: 4 lanes per pixel pair, 32: 8 lanes = a whole 128-byte line per pixel and load);
 // PD = half-rounds the loads run ahead of the half-round that writes them into the A tile (up to two tiles ahead: the short-K layers are the
@@ -158,7 +151,7 @@ __global__ __launch_bounds__(64 * NW) void pw3_f32(Pw3Args a)
 #pragma unroll
             for (int hh = 0; hh < 2; hh++)
 #pragma unroll
-                for (int t = 0; t < NB; t++) o[hh][t] = relu6(hh ? p[t].y : p[t].x);
+                for (int t = 0; t < NB; t++) o[hh][t] = mbn_relu6(hh ? p[t].y : p[t].x);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int hh = 0; hh < 2; hh++) {
@@ -170,14 +163,13 @@ __global__ __launch_bounds__(64 * NW) void pw3_f32(Pw3Args a)
                     if (inside) __builtin_amdgcn_raw_buffer_store_b128(v, orsrc, lane_off, soff, 0);
                     else __builtin_amdgcn_raw_buffer_store_b128(v, orsrc, lane_off + soff, 0, 0);
                 } else {
-                    typedef unsigned u2e __attribute__((ext_vector_type(2)));
-                    const u2e v = __builtin_bit_cast(u2e, f2{ o[hh][0], o[hh][1] });
+                    const u2 v = __builtin_bit_cast(u2, f2{ o[hh][0], o[hh][1] });
                     if (inside) __builtin_amdgcn_raw_buffer_store_b64(v, orsrc, lane_off, soff, 0);
                     else __builtin_amdgcn_raw_buffer_store_b64(v, orsrc, lane_off + soff, 0, 0);
                 }
             }
-            if constexpr (NB == 4) asm volatile("s_nop 1" ::: "memory");      // store-data hazard of 16-byte buffer stores (mbn_f32_dwpw3.hip)
-            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (NB == 4) mbn_store_hazard_wait();
+            else __builtin_amdgcn_sched_barrier(0);
         }
     };
     auto epilogue = [&](unsigned m0) __attribute__((always_inline)) {

@@ -25,10 +25,9 @@
 // not fork sub-batches of fewer than 5 images (mbn_net_set_streams).
 // A/B hook: mbn_tune_set("pw_splitk", 1) disables this kernel, 2 forces it wherever the shape allows.
 #include "mbn_internal.h"
+#include "mbn_device.h"
 
 namespace {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 struct SkArgs {
     float *out;

@@ -42,13 +42,6 @@
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef mbn_f16v f16v;
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
-
 struct XArgs {
     float *out;
     const float *in, *filt, *scale, *shift;
@@ -63,14 +56,6 @@ struct XArgs {
 
 constexpr int KT = 32;            // k per k-tile
 constexpr int PW = 16;            // 4-byte words per plane row (32 bf16)
-
-__device__ __forceinline__ int pswz(int row, int c) { return row * PW + (((c ^ (row >> 2)) & 3) << 2); }
-
-__device__ __forceinline__ int x_remap(int vb, int nwg)
-{
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = vb & 7;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (vb >> 3);
-}
 
 // 8 consecutive k of one row -> the three bf16 planes (exact: h + m + l == x)
 __device__ __forceinline__ void split8(const f4 &x0, const f4 &x1, u4 &H, u4 &M, u4 &L)
@@ -127,10 +112,10 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) __attribute__((amdgpu_w
     f4 a_reg[A_LD][2], b_reg[B_LD][2];
     int st_off[A_LD > B_LD ? A_LD : B_LD];
 #pragma unroll
-    for (int p = 0; p < (A_LD > B_LD ? A_LD : B_LD); p++) st_off[p] = pswz(p * RP + st_r, st_c);
+    for (int p = 0; p < (A_LD > B_LD ? A_LD : B_LD); p++) st_off[p] = mbn_pswz(p * RP + st_r, st_c);
 
     auto set_tile = [&](int vb, long &m0, int &n0) {
-        const int lid = x_remap(vb, nwg);
+        const int lid = mbn_xcd_remap(vb, nwg);
         m0 = (long)(lid / a.nt) * BM;
         n0 = (lid % a.nt) * BN;
 #pragma unroll
@@ -183,8 +168,8 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) __attribute__((amdgpu_w
     int fr_a[2], fr_b[2];
 #pragma unroll
     for (int s = 0; s < 2; s++) {
-        fr_a[s] = pswz(wm + li, 2 * s + lh);
-        fr_b[s] = pswz(wn + li, 2 * s + lh);
+        fr_a[s] = mbn_pswz(wm + li, 2 * s + lh);
+        fr_b[s] = mbn_pswz(wn + li, 2 * s + lh);
     }
 
     long m0;
@@ -292,19 +277,10 @@ __global__ __launch_bounds__(4 * BN) void split_filter(unsigned *ws, const float
     const float *src = filt + (long)gn * k + kt * KT + c * 8;
     u4 H, M, L;
     split8(*reinterpret_cast<const f4 *>(src), *reinterpret_cast<const f4 *>(src + 4), H, M, L);
-    unsigned *dst = ws + (size_t)(ntile * nk + kt) * 3 * BN * PW + pswz(row, c);
+    unsigned *dst = ws + (size_t)(ntile * nk + kt) * 3 * BN * PW + mbn_pswz(row, c);
     *reinterpret_cast<u4 *>(dst) = H;
     *reinterpret_cast<u4 *>(dst + BN * PW) = M;
     *reinterpret_cast<u4 *>(dst + 2 * BN * PW) = L;
-}
-
-// s_barrier with explicit counters (as in mbn_bf16_pw_ring.hip): __syncthreads would drain vmcnt(0) — the A loads issued two
-// k-tiles ahead included — at every barrier while an LDS-DMA is outstanding. VM_LEFT < 0: vector memory is not waited for.
-template <int VM_LEFT>
-__device__ __forceinline__ void xb_barrier()
-{
-    if constexpr (VM_LEFT < 0) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(VM_LEFT) : "memory");
 }
 
 __device__ __forceinline__ void dma_pieces(const __amdgpu_buffer_rsrc_t rsrc, unsigned *lds_dst, const unsigned *voff, unsigned soff, int wave_u,
@@ -350,13 +326,13 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) __attribute__((amdgpu_w
     int st_off[A_LD];
     unsigned b_vo[NPC];
 #pragma unroll
-    for (int p = 0; p < A_LD; p++) st_off[p] = pswz(p * RP + st_r, st_c);
+    for (int p = 0; p < A_LD; p++) st_off[p] = mbn_pswz(p * RP + st_r, st_c);
 #pragma unroll
     for (int p = 0; p < NPC; p++) b_vo[p] = (unsigned)((p * NW + wave) * 1024 + lane * 16);
 
     int ntile_cur = 0;
     auto set_tile = [&](int vb, long &m0, int &n0) {
-        const int lid = x_remap(vb, nwg);
+        const int lid = mbn_xcd_remap(vb, nwg);
         m0 = (long)(lid / a.nt) * BM;
         ntile_cur = lid % a.nt;
         n0 = ntile_cur * BN;
@@ -391,8 +367,8 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) __attribute__((amdgpu_w
     int fr_a[2], fr_b[2];
 #pragma unroll
     for (int s = 0; s < 2; s++) {
-        fr_a[s] = pswz(wm + li, 2 * s + lh);
-        fr_b[s] = pswz(wn + li, 2 * s + lh);
+        fr_a[s] = mbn_pswz(wm + li, 2 * s + lh);
+        fr_b[s] = mbn_pswz(wn + li, 2 * s + lh);
     }
 
     long m0;
@@ -457,7 +433,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) __attribute__((amdgpu_w
             if (ASETS == 2 && NBB == 2 && HAS2) stage_load(FRESH, (kt_ + 2) * KT);                                         \
             __builtin_amdgcn_sched_barrier(0);                /* loads in flight before the first MFMA */                  \
             compute(Bbuf + (NBB == 2 ? (kt_ & 1) : 0) * IMG_B);                                                            \
-            xb_barrier<-1>();                                 /* everyone has read the A planes (and the filter image) of k-tile kt */ \
+            mbn_waitcnt<-1>();                                /* everyone has read the A planes (and the filter image) of k-tile kt */ \
             __builtin_amdgcn_sched_barrier(0);                /* keep the split (and the wait for its loads) behind the MFMAs */ \
             if (NBB == 1 && HAS1) dma_b(kt_ + 1, 0);                                                                       \
             if (ASETS == 2 && NBB == 1 && HAS2) stage_load(FRESH, (kt_ + 2) * KT);                                         \
@@ -465,8 +441,8 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) __attribute__((amdgpu_w
             if (HAS1) stage_store(PEND);                                                                                   \
             if (a.prio) __builtin_amdgcn_s_setprio(0);                                                                     \
             if (ASETS == 1 && HAS2) stage_load(PEND, (kt_ + 2) * KT);                                                      \
-            if (HAS2) xb_barrier<2 * A_LD>();                 /* A planes of kt + 1 written, filter image kt + 1 landed */ \
-            else xb_barrier<0>();                                                                                          \
+            if (HAS2) mbn_waitcnt<2 * A_LD>();                /* A planes of kt + 1 written, filter image kt + 1 landed */ \
+            else mbn_waitcnt<0>();                                                                                         \
         }
         int kt = 0;
 #define XB_R1 (ASETS == 2 ? a_r1 : a_r0)

@@ -26,13 +26,6 @@
 
 namespace {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f16v __attribute__((ext_vector_type(16)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-
 constexpr int TH = MBN_STEM_TH, TW = MBN_STEM_TW;   // output tile (pixels of the 112x112 map)
 constexpr int CR = TH + 2, CC = TW + 2;        // conv1 region incl. the depthwise halo: 10 x 18
 constexpr int PR = 2 * CR + 1;                     // input patch: 21 rows x 37 pixels
@@ -67,11 +60,6 @@ __device__ __forceinline__ int swzb(int row, int slot)
     if (C1 == 32) return (row << 4) + (((slot ^ (row >> 2)) & 3) << 2);
     return (row << 3) + (((slot ^ (row >> 3)) & 1) << 2);
 }
-__device__ __forceinline__ float relu6(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
-__device__ __forceinline__ f4 bn_relu6(f4 a, f4 s, f4 b)
-{
-    return f4{ relu6(fmaf(a.x, s.x, b.x)), relu6(fmaf(a.y, s.y, b.y)), relu6(fmaf(a.z, s.z, b.z)), relu6(fmaf(a.w, s.w, b.w)) };
-}
 // acc += x * w on four channels: one fused multiply-add per channel (same rounding as the unfused kernels' fmaf), written
 // on vectors so the compiler can pair channels into v_pk_fma_f32
 __device__ __forceinline__ f4 fma4(float x, f4 w, f4 acc) { return __builtin_elementwise_fma(f4{ x, x, x, x }, w, acc); }
@@ -92,7 +80,6 @@ __device__ __forceinline__ void patch_load(const StemArgs &a, unsigned t, int ti
     const long n = q0 / (unsigned)a.tiles_y;
     const long img = n * a.rows * a.cols * 3;
     const int iy0 = 2 * (TH * ty - 1), fx0 = 6 * (TW * tx - 1), rowf = a.cols * 3;
-    constexpr unsigned OOB = 0xF0000000u;
     const unsigned img_elems = (unsigned)(a.rows * a.cols * 3);
     if (a.in8) {
         const __amdgpu_buffer_rsrc_t rsrc = mbn_make_rsrc(a.in8 + img, img_elems);
@@ -101,7 +88,7 @@ __device__ __forceinline__ void patch_load(const StemArgs &a, unsigned t, int ti
             const int i = tid + k * 256, r = i / PAIRS, j = i % PAIRS;
             const int iy = iy0 + r, fx = fx0 + 2 * j;
             const bool ok = i < PR * PAIRS && iy >= 0 && iy < a.rows && fx >= 0 && fx < rowf;
-            const unsigned u = (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rsrc, ok ? (unsigned)(iy * rowf + fx) : OOB, 0, 0);
+            const unsigned u = (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rsrc, ok ? (unsigned)(iy * rowf + fx) : MBN_OOB, 0, 0);
             // same fmaf as normalize_u8_f32: bit-identical; the zero padding is zero AFTER normalisation
             pf[k] = ok ? f2{ fmaf((float)(u & 0xff), 1.0f / 127.5f, -1.0f), fmaf((float)(u >> 8), 1.0f / 127.5f, -1.0f) } : f2{ 0.f, 0.f };
         }
@@ -112,7 +99,7 @@ __device__ __forceinline__ void patch_load(const StemArgs &a, unsigned t, int ti
             const int i = tid + k * 256, r = i / PAIRS, j = i % PAIRS;
             const int iy = iy0 + r, fx = fx0 + 2 * j;
             const bool ok = i < PR * PAIRS && iy >= 0 && iy < a.rows && fx >= 0 && fx < rowf;
-            pf[k] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, ok ? (unsigned)(iy * rowf + fx) * 4u : OOB, 0, 0));
+            pf[k] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, ok ? (unsigned)(iy * rowf + fx) * 4u : MBN_OOB, 0, 0));
         }
     }
 }
@@ -133,16 +120,14 @@ __device__ __forceinline__ f4 rbf4(f4 v) { return f4{ rbf(v.x), rbf(v.y), rbf(v.
 // exact three-way bf16 split of fp32 values (mbn_f32_pw_x6.hip: h = bf16(x), m = bf16(x - h), l = x - h - m), packed two per word
 __device__ __forceinline__ void x6_split2(float x0, float x1, unsigned &h, unsigned &m, unsigned &l)
 {
-    typedef float f2e __attribute__((ext_vector_type(2)));
-    typedef __bf16 b2e __attribute__((ext_vector_type(2)));
-    const f2e v = f2e{ x0, x1 };
-    const b2e hh = __builtin_convertvector(v, b2e);
-    const f2e r = v - __builtin_convertvector(hh, f2e);
-    const b2e mm = __builtin_convertvector(r, b2e);
-    const f2e lo = r - __builtin_convertvector(mm, f2e);
+    const f2 v = f2{ x0, x1 };
+    const bf2 hh = __builtin_convertvector(v, bf2);
+    const f2 r = v - __builtin_convertvector(hh, f2);
+    const bf2 mm = __builtin_convertvector(r, bf2);
+    const f2 lo = r - __builtin_convertvector(mm, f2);
     h = __builtin_bit_cast(unsigned, hh);
     m = __builtin_bit_cast(unsigned, mm);
-    l = __builtin_bit_cast(unsigned, __builtin_convertvector(lo, b2e));
+    l = __builtin_bit_cast(unsigned, __builtin_convertvector(lo, bf2));
 }
 __device__ __forceinline__ void x6_split4(f4 v, unsigned (&h)[2], unsigned (&m)[2], unsigned (&l)[2])
 {
@@ -220,10 +205,9 @@ __global__ __launch_bounds__(256, WPE) void stem_fused_f32(StemArgs a)
             const float *src = a.wp + row * C1 + slot * 8;
             unsigned hw[4], mw[4], lw[4];
             x6_split8(*reinterpret_cast<const f4 *>(src), *reinterpret_cast<const f4 *>(src + 4), hw, mw, lw);
-            typedef unsigned u4e __attribute__((ext_vector_type(4)));
-            *reinterpret_cast<u4e *>(b_s + swzb<C1>(row, slot)) = u4e{ hw[0], hw[1], hw[2], hw[3] };
-            *reinterpret_cast<u4e *>(b_s + BPL + swzb<C1>(row, slot)) = u4e{ mw[0], mw[1], mw[2], mw[3] };
-            *reinterpret_cast<u4e *>(b_s + 2 * BPL + swzb<C1>(row, slot)) = u4e{ lw[0], lw[1], lw[2], lw[3] };
+            *reinterpret_cast<u4 *>(b_s + swzb<C1>(row, slot)) = u4{ hw[0], hw[1], hw[2], hw[3] };
+            *reinterpret_cast<u4 *>(b_s + BPL + swzb<C1>(row, slot)) = u4{ mw[0], mw[1], mw[2], mw[3] };
+            *reinterpret_cast<u4 *>(b_s + 2 * BPL + swzb<C1>(row, slot)) = u4{ lw[0], lw[1], lw[2], lw[3] };
         }
     } else if constexpr (!BREG)
     for (int i = tid; i < C3 * Q1; i += 256) {                            // pointwise filter [C3][C1] -> swizzled B tile
@@ -315,7 +299,6 @@ __global__ __launch_bounds__(256, WPE) void stem_fused_f32(StemArgs a)
         }
 #pragma unroll
         for (int h = 0; h < MH; h++) {
-            typedef unsigned u4 __attribute__((ext_vector_type(4)));
             u4 ph, pl;
 #pragma unroll
             for (int i = 0; i < 4; i++) {
@@ -365,13 +348,12 @@ __global__ __launch_bounds__(256, WPE) void stem_fused_f32(StemArgs a)
                     f4 acc = f4{ 0.f, 0.f, 0.f, 0.f };                    // same instruction, same k order as conv1_mfma_f32 (mbn_f32_misc.hip): same bits
 #pragma unroll
                     for (int t = 0; t < 7; t++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(mcf_w[h][t], xv[t], acc, 0, 0, 0);
-                    const f4 v = inside ? bn_relu6(acc, mcf_s1[h], mcf_b1[h]) : f4{ 0.f, 0.f, 0.f, 0.f };   // outside: the depthwise zero padding
+                    const f4 v = inside ? mbn_bn_relu6(acc, mcf_s1[h], mcf_b1[h]) : f4{ 0.f, 0.f, 0.f, 0.f };  // outside: the depthwise zero padding
                     if (q < CR * CC) *reinterpret_cast<f4 *>(c1_s + q * C1P + 16 * h + 4 * kg) = v;
                 }
             }
         } else
         if constexpr (MC) {
-            typedef unsigned u4 __attribute__((ext_vector_type(4)));
             const int kg = lane >> 4, pc = lane & 15;
 #pragma unroll 1
             for (int bi = 0; bi < 3; bi++) {
@@ -403,7 +385,7 @@ __global__ __launch_bounds__(256, WPE) void stem_fused_f32(StemArgs a)
                     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(mc_wl[h], xh, acc, 0, 0, 0);      // smallest terms first
                     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(mc_wh[h], xl, acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(mc_wh[h], xh, acc, 0, 0, 0);
-                    const f4 v = inside ? rbf4(bn_relu6(acc, mc_s1[h], mc_b1[h])) : f4{ 0.f, 0.f, 0.f, 0.f };   // outside: the depthwise zero padding
+                    const f4 v = inside ? rbf4(mbn_bn_relu6(acc, mc_s1[h], mc_b1[h])) : f4{ 0.f, 0.f, 0.f, 0.f };  // outside: the depthwise zero padding
                     if (q < CR * CC) *reinterpret_cast<f4 *>(c1_s + q * C1 + 16 * h + 4 * kg) = v;
                 }
             }
@@ -445,7 +427,7 @@ __global__ __launch_bounds__(256, WPE) void stem_fused_f32(StemArgs a)
             const f4 s1 = *reinterpret_cast<const f4 *>(sb_s + c4 * 4), b1 = *reinterpret_cast<const f4 *>(sb_s + C1 + c4 * 4);
 #pragma unroll
             for (int p = 0; p < PB; p++) {                                // outside the map: the depthwise zero padding
-                f4 v = (rowok && ox + p >= 0 && ox + p < a.ow) ? bn_relu6(acc[p], s1, b1) : f4{ 0.f, 0.f, 0.f, 0.f };
+                f4 v = (rowok && ox + p >= 0 && ox + p < a.ow) ? mbn_bn_relu6(acc[p], s1, b1) : f4{ 0.f, 0.f, 0.f, 0.f };
                 if (BF) v = rbf4(v);
                 *reinterpret_cast<f4 *>(c1_s + (br * CC + bc + p) * C1 + c4 * 4) = v;
             }
@@ -475,7 +457,7 @@ __global__ __launch_bounds__(256, WPE) void stem_fused_f32(StemArgs a)
             const f4 s2 = *reinterpret_cast<const f4 *>(sb_s + 2 * C1 + c4 * 4), b2 = *reinterpret_cast<const f4 *>(sb_s + 3 * C1 + c4 * 4);
 #pragma unroll
             for (int p = 0; p < PC; p++) {
-                const f4 v = bn_relu6(acc[p], s2, b2);
+                const f4 v = mbn_bn_relu6(acc[p], s2, b2);
                 if (BF) {                                                 // the layer output, rounded to bf16 (RNE): 8 bytes per lane
                     const int row = cy * TW + cx + p;
                     *reinterpret_cast<bf4 *>(a_s + swzb<C1>(row, c4 >> 1) + 2 * (c4 & 1)) = bf4{ (__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w };
@@ -483,10 +465,9 @@ __global__ __launch_bounds__(256, WPE) void stem_fused_f32(StemArgs a)
                     const int o = swzb<C1>(cy * TW + cx + p, c4 >> 1) + 2 * (c4 & 1);
                     unsigned hw[2], mw[2], lw[2];
                     x6_split4(v, hw, mw, lw);
-                    typedef unsigned u2e __attribute__((ext_vector_type(2)));
-                    *reinterpret_cast<u2e *>(a_s + o) = u2e{ hw[0], hw[1] };
-                    *reinterpret_cast<u2e *>(a_s + APL + o) = u2e{ mw[0], mw[1] };
-                    *reinterpret_cast<u2e *>(a_s + 2 * APL + o) = u2e{ lw[0], lw[1] };
+                    *reinterpret_cast<u2 *>(a_s + o) = u2{ hw[0], hw[1] };
+                    *reinterpret_cast<u2 *>(a_s + APL + o) = u2{ mw[0], mw[1] };
+                    *reinterpret_cast<u2 *>(a_s + 2 * APL + o) = u2{ lw[0], lw[1] };
                 } else *reinterpret_cast<f4 *>(a_s + swz<C1>(cy * TW + cx + p, c4)) = v;
             }
         }
@@ -525,10 +506,10 @@ __global__ __launch_bounds__(256, WPE) void stem_fused_f32(StemArgs a)
                 if constexpr (NI == 2) {
                     // channel-paired store: lane li holds channels 2li (acc[0]) and 2li+1 (acc[1]) of pixel row q: one dword per
                     // row, 32 lanes = the pixel's whole 128-byte line
-                    const float v0 = relu6(fmaf(acc[0][r], s3[0], b3[0])), v1 = relu6(fmaf(acc[1][r], s3[1], b3[1]));
+                    const float v0 = mbn_relu6(fmaf(acc[0][r], s3[0], b3[0])), v1 = mbn_relu6(fmaf(acc[1][r], s3[1], b3[1]));
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, bf2{ (__bf16)v0, (__bf16)v1 }), orsrc, lane_off, soff, 0);
                 } else {
-                    __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (__bf16)relu6(fmaf(acc[0][r], s3[0], b3[0]))), orsrc, lane_off, soff, 0);
+                    __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (__bf16)mbn_relu6(fmaf(acc[0][r], s3[0], b3[0]))), orsrc, lane_off, soff, 0);
                 }
             }
         } else {
@@ -578,7 +559,7 @@ __global__ __launch_bounds__(256, WPE) void stem_fused_f32(StemArgs a)
                 for (int r = 0; r < 16; r++) {
                     const int q = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                     const int y = q >> 4, x = q & 15;
-                    obase[((long)y * a.ow + x) * C3 + ni * 32 + li] = relu6(fmaf(acc[ni][r], s3[ni], b3[ni]));
+                    obase[((long)y * a.ow + x) * C3 + ni * 32 + li] = mbn_relu6(fmaf(acc[ni][r], s3[ni], b3[ni]));
                 }
         } else {
         const __amdgpu_buffer_rsrc_t orsrc = mbn_make_rsrc(a.out + n * a.oh * a.ow * C3, (unsigned)(a.oh * a.ow * C3 * 4));   // see the bf16 branch
@@ -589,7 +570,7 @@ __global__ __launch_bounds__(256, WPE) void stem_fused_f32(StemArgs a)
             for (int r = 0; r < 16; r++) {
                 const int y = TH * ty + 2 * __builtin_amdgcn_readfirstlane(wave) + (r >> 3), x = TW * tx + (r & 3) + 8 * ((r >> 2) & 1);
                 const unsigned soff = (unsigned)((y * a.ow + x) * C3 + ni * 32) * 4u;
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, relu6(fmaf(acc[ni][r], s3[ni], b3[ni]))), orsrc, lane_off, soff, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, mbn_relu6(fmaf(acc[ni][r], s3[ni], b3[ni]))), orsrc, lane_off, soff, 0);
             }
         }
         }

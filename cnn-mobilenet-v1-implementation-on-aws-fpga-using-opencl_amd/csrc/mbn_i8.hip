@@ -15,14 +15,11 @@
 //   pool       global average: exact int32 sums of four channels per lane, one fp32 multiply by 1 / (rows * cols).
 // Every index is 64-bit (plain global loads and stores, no buffer descriptors): no 32-bit offset limit.
 #include "mbn_internal.h"
+#include "mbn_device.h"
 
 #include <algorithm>
 
 namespace {
-
-typedef float i8_f2 __attribute__((ext_vector_type(2)));
-typedef int i8_v4i __attribute__((ext_vector_type(4)));
-typedef int i8_v16i __attribute__((ext_vector_type(16)));
 
 constexpr float I8_NORM_SCALE = 1.0f / 127.5f, I8_NORM_BIAS = -1.0f;
 
@@ -76,15 +73,15 @@ __global__ __launch_bounds__(256) void i8_conv_k(uint8_t *__restrict__ out, cons
             }
         }
     }
-    i8_f2 acc[4 * NG];
+    f2 acc[4 * NG];
 #pragma unroll
-    for (int j = 0; j < 4 * NG; j++) acc[j] = i8_f2{ 0.f, 0.f };
+    for (int j = 0; j < 4 * NG; j++) acc[j] = f2{ 0.f, 0.f };
 #pragma unroll
     for (int tp = 0; tp < 27; tp++) {
-        const i8_f2 xx = { x[tp], x[tp] };
+        const f2 xx = { x[tp], x[tp] };
         const float *wr = w + (long)tp * cout + c0;
 #pragma unroll
-        for (int j = 0; j < 4 * NG; j++) acc[j] = __builtin_elementwise_fma(xx, i8_f2{ wr[2 * j], wr[2 * j + 1] }, acc[j]);
+        for (int j = 0; j < 4 * NG; j++) acc[j] = __builtin_elementwise_fma(xx, f2{ wr[2 * j], wr[2 * j + 1] }, acc[j]);
     }
 #pragma unroll
     for (int g = 0; g < NG; g++) {
@@ -92,7 +89,7 @@ __global__ __launch_bounds__(256) void i8_conv_k(uint8_t *__restrict__ out, cons
 #pragma unroll
         for (int h2 = 0; h2 < 2; h2++) {
             const int cb = c0 + 8 * g + 4 * h2;
-            const i8_f2 p0 = acc[4 * g + 2 * h2], p1 = acc[4 * g + 2 * h2 + 1];
+            const f2 p0 = acc[4 * g + 2 * h2], p1 = acc[4 * g + 2 * h2 + 1];
             q[h2] = i8_requant(p0.x, mult[cb], bias[cb]) | (i8_requant(p0.y, mult[cb + 1], bias[cb + 1]) << 8) |
                     (i8_requant(p1.x, mult[cb + 2], bias[cb + 2]) << 16) | (i8_requant(p1.y, mult[cb + 3], bias[cb + 3]) << 24);
         }
@@ -121,19 +118,19 @@ __device__ __forceinline__ void dw_fetch(unsigned (&v)[3], const DwArgs &a, cons
     for (int kx = 0; kx < 3; kx++) v[kx] = (oky && okx[kx]) ? r[kx * a.c4] : 0u;
 }
 // ... and converted to fp32 pairs (v_cvt_f32_ubyte0..3) once the row before has been computed
-__device__ __forceinline__ void dw_cvt(i8_f2 (&r)[6], const unsigned (&v)[3])
+__device__ __forceinline__ void dw_cvt(f2 (&r)[6], const unsigned (&v)[3])
 {
 #pragma unroll
     for (int kx = 0; kx < 3; kx++) {
-        r[2 * kx] = i8_f2{ (float)(v[kx] & 0xffu), (float)((v[kx] >> 8) & 0xffu) };
-        r[2 * kx + 1] = i8_f2{ (float)((v[kx] >> 16) & 0xffu), (float)(v[kx] >> 24) };
+        r[2 * kx] = f2{ (float)(v[kx] & 0xffu), (float)((v[kx] >> 8) & 0xffu) };
+        r[2 * kx + 1] = f2{ (float)((v[kx] >> 16) & 0xffu), (float)(v[kx] >> 24) };
     }
 }
 
-__device__ __forceinline__ void dw_emit(const i8_f2 (&r0)[6], const i8_f2 (&r1)[6], const i8_f2 (&r2)[6], const i8_f2 (&wf)[18],
+__device__ __forceinline__ void dw_emit(const f2 (&r0)[6], const f2 (&r1)[6], const f2 (&r2)[6], const f2 (&wf)[18],
                                         const float (&m)[4], const float (&b)[4], uint8_t *dst)
 {
-    i8_f2 lo = { 0.f, 0.f }, hi = { 0.f, 0.f };
+    f2 lo = { 0.f, 0.f }, hi = { 0.f, 0.f };
 #pragma unroll
     for (int kx = 0; kx < 3; kx++) {
         lo = __builtin_elementwise_fma(r0[2 * kx], wf[2 * kx], lo);
@@ -162,12 +159,12 @@ __global__ __launch_bounds__(256) void i8_dw_k(DwArgs a)
     if (oy1 > a.ho) oy1 = a.ho;
     if (oy0 >= oy1) return;
     const int C = 4 * a.c4;
-    i8_f2 wf[18];                         // [ky][kx][channel pair]
+    f2 wf[18];                            // [ky][kx][channel pair]
 #pragma unroll
     for (int k = 0; k < 9; k++) {
         const unsigned v = reinterpret_cast<const unsigned *>(a.w + (long)k * C)[cg];
-        wf[2 * k] = i8_f2{ (float)(int8_t)(v & 0xffu), (float)(int8_t)((v >> 8) & 0xffu) };
-        wf[2 * k + 1] = i8_f2{ (float)(int8_t)((v >> 16) & 0xffu), (float)(int8_t)(v >> 24) };
+        wf[2 * k] = f2{ (float)(int8_t)(v & 0xffu), (float)(int8_t)((v >> 8) & 0xffu) };
+        wf[2 * k + 1] = f2{ (float)(int8_t)((v >> 16) & 0xffu), (float)(int8_t)(v >> 24) };
     }
     float m[4], b[4];
 #pragma unroll
@@ -177,7 +174,7 @@ __global__ __launch_bounds__(256) void i8_dw_k(DwArgs a)
     const bool okx[3] = { ix0 >= 0 && ix0 < a.wd, ix0 + 1 >= 0 && ix0 + 1 < a.wd, ix0 + 2 >= 0 && ix0 + 2 < a.wd };
     uint8_t *dst = a.out + ((n * a.ho + oy0) * (long)a.wo + ox) * C + 4 * cg;
     const long row_step = (long)a.wo * C;
-    i8_f2 A[6], B[6], Cr[6];
+    f2 A[6], B[6], Cr[6];
     unsigned v0[3], v1[3];
     int iy = oy0 * S - a.pad_top;         // first input row of the window
     dw_fetch(v0, a, col, okx, iy); dw_cvt(A, v0);
@@ -228,11 +225,11 @@ struct PwArgs {
 
 // 8 or 16 bytes of a row at byte offset o (< limit), zero past the row; G = granule (16 when K % 16 == 0, else 8)
 template <int G>
-__device__ __forceinline__ i8_v4i pw_load(const uint8_t *row, int o, int limit)
+__device__ __forceinline__ i4v pw_load(const uint8_t *row, int o, int limit)
 {
-    i8_v4i v = { 0, 0, 0, 0 };
+    i4v v = { 0, 0, 0, 0 };
     if (G == 16) {
-        if (o < limit) v = *reinterpret_cast<const i8_v4i *>(row + o);
+        if (o < limit) v = *reinterpret_cast<const i4v *>(row + o);
     } else {
         if (o < limit) { const uint2 x = *reinterpret_cast<const uint2 *>(row + o); v[0] = (int)x.x; v[1] = (int)x.y; }
         if (o + 8 < limit) { const uint2 x = *reinterpret_cast<const uint2 *>(row + o + 8); v[2] = (int)x.x; v[3] = (int)x.y; }
@@ -240,7 +237,7 @@ __device__ __forceinline__ i8_v4i pw_load(const uint8_t *row, int o, int limit)
     return v;
 }
 
-__device__ __forceinline__ int pw_bytesum(i8_v4i v)
+__device__ __forceinline__ int pw_bytesum(i4v v)
 {
     int s = 0;
 #pragma unroll
@@ -263,12 +260,12 @@ __global__ __launch_bounds__(64 * PW_WAVES) void i8_pw_k(PwArgs a)
     const bool pok = p < a.m;
     const uint8_t *xrow = a.in + (pok ? p : 0) * (long)a.k;
     const int nkb = (a.k + KB - 1) / KB;
-    i8_v4i bx[KS];
+    i4v bx[KS];
     auto load_b = [&](int kb) {
         const int lim = pok ? a.k - kb * KB : 0;
 #pragma unroll
         for (int s = 0; s < KS; s++) {
-            const i8_v4i v = pw_load<G>(xrow + kb * KB, 32 * s + 16 * lh, lim);
+            const i4v v = pw_load<G>(xrow + kb * KB, 32 * s + 16 * lh, lim);
 #pragma unroll
             for (int j = 0; j < 4; j++) bx[s][j] = v[j] ^ (int)0x80808080u;
         }
@@ -279,7 +276,7 @@ __global__ __launch_bounds__(64 * PW_WAVES) void i8_pw_k(PwArgs a)
         const int oc0 = 32 * ch, oc = oc0 + li;
         const bool ook = oc < a.n;
         const uint8_t *wr = reinterpret_cast<const uint8_t *>(a.w) + (long)(ook ? oc : 0) * a.k;
-        i8_v16i acc;
+        i16v acc;
 #pragma unroll
         for (int r = 0; r < 16; r++) acc[r] = 0;
         int ws = 0;
@@ -290,7 +287,7 @@ __global__ __launch_bounds__(64 * PW_WAVES) void i8_pw_k(PwArgs a)
 #pragma unroll
             for (int s = 0; s < KS; s++)
                 if (s < ksteps) {
-                    const i8_v4i av = pw_load<G>(wr + (long)kb * KB, 32 * s + 16 * lh, lim);
+                    const i4v av = pw_load<G>(wr + (long)kb * KB, 32 * s + 16 * lh, lim);
                     ws = __builtin_amdgcn_sdot4(av[0], 0x01010101, ws, false);
                     ws = __builtin_amdgcn_sdot4(av[1], 0x01010101, ws, false);
                     ws = __builtin_amdgcn_sdot4(av[2], 0x01010101, ws, false);
@@ -357,17 +354,17 @@ __global__ __launch_bounds__(MAXT) void i8_pw2_k(Pw2Args a)
     // staging: granules of 16 (8) bytes of the tile's [pt][k] activations, row by row
     const int gb = g16 ? 16 : 8, gpr = a.k / gb, ngr = a.pt * gpr;
     constexpr int MAXG = KS <= 4 ? 8 : 4;            // granules per thread and tile (the launcher sizes pt for it)
-    i8_v4i pre[MAXG];
+    i4v pre[MAXG];
     auto fetch = [&](long t) {
 #pragma unroll
         for (int i = 0; i < MAXG; i++) {
             const int g = tid + i * nthr;
-            pre[i] = i8_v4i{ 0, 0, 0, 0 };
+            pre[i] = i4v{ 0, 0, 0, 0 };
             if (g < ngr) {
                 const long px = t * a.pt + g / gpr;
                 if (px < a.m) {
                     const uint8_t *src = a.in + px * a.k + (long)(g % gpr) * gb;
-                    if (g16) pre[i] = *reinterpret_cast<const i8_v4i *>(src);
+                    if (g16) pre[i] = *reinterpret_cast<const i4v *>(src);
                     else { const uint2 x = *reinterpret_cast<const uint2 *>(src); pre[i][0] = (int)x.x; pre[i][1] = (int)x.y; }
                 }
             }
@@ -375,7 +372,7 @@ __global__ __launch_bounds__(MAXT) void i8_pw2_k(Pw2Args a)
     };
     fetch(tile);                                     // the first tile's loads overlap the filter's
     // the chunk's filter rows: lane (li, lh) holds row oc, bytes 32 s + 16 lh .. + 15 of every k step s
-    i8_v4i av[KS];
+    i4v av[KS];
     int ws = 0;
     {
         const uint8_t *wr = reinterpret_cast<const uint8_t *>(a.w) + (long)(ook ? oc : 0) * a.k;
@@ -413,8 +410,8 @@ __global__ __launch_bounds__(MAXT) void i8_pw2_k(Pw2Args a)
             const int g = tid + i * nthr;
             if (g < ngr) {
                 uint8_t *d = base + (g / gpr) * str + (g % gpr) * gb;
-                const i8_v4i v = pre[i] ^ (int)0x80808080u;
-                if (g16) *reinterpret_cast<i8_v4i *>(d) = v;
+                const i4v v = pre[i] ^ (int)0x80808080u;
+                if (g16) *reinterpret_cast<i4v *>(d) = v;
                 else *reinterpret_cast<uint2 *>(d) = make_uint2((unsigned)v[0], (unsigned)v[1]);
             }
         }
@@ -427,13 +424,13 @@ __global__ __launch_bounds__(MAXT) void i8_pw2_k(Pw2Args a)
         __syncthreads();
         const uint8_t *xb = xs + (long)cur * a.pt * str;
         for (int sub = sub0; sub < a.pt; sub += 32 * nrep) {
-            i8_v16i acc;
+            i16v acc;
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[r] = 0;
             const uint8_t *brow = xb + (sub + li) * str + 16 * lh;
 #pragma unroll
             for (int s = 0; s < KS; s++)
-                if (s < ksteps) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[s], *reinterpret_cast<const i8_v4i *>(brow + 32 * s), acc, 0, 0, 0);
+                if (s < ksteps) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[s], *reinterpret_cast<const i4v *>(brow + 32 * s), acc, 0, 0, 0);
             const long p = tile * a.pt + sub + li;
             uint8_t *orow = OUTF32 ? nullptr : reinterpret_cast<uint8_t *>(a.out) + p * (long)a.n + oc0;
             if (!OUTF32 && full16) {

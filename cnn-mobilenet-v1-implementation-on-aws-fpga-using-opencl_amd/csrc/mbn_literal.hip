@@ -9,6 +9,7 @@
 // Filters are wave-uniform and come through the scalar cache. This path is HBM/latency-light integer work;
 // the fp32 NHWC kernels (mbn_f32_*.hip) are the performance path.
 #include "mbn_internal.h"
+#include "mbn_device.h"
 
 namespace {
 
@@ -248,8 +249,6 @@ __global__ __launch_bounds__(64 * LD_WAVES) void lit_pointwise_dot_k(uint8_t *__
 //             sums do not depend on the order, so any such assignment gives the exact dot product.
 //   C/D       lane l holds pixel l % 32 and output channels (r & 3) + 8 * (r >> 2) + 4 * (l / 32), r = 0..15: 32 lanes store 32 consecutive bytes of a plane.
 constexpr int LM_PIX = 64, LM_WAVES = 8;
-typedef int lit_v4i __attribute__((ext_vector_type(4)));
-typedef int lit_v16i __attribute__((ext_vector_type(16)));
 
 __global__ __launch_bounds__(256) void lit_pack_filter_rows_k(unsigned *__restrict__ w8r, int *__restrict__ wsum, int *__restrict__ bad,
                                                               const int *__restrict__ filt, int cin, int op_size, int cin32, int ocp32)
@@ -315,14 +314,14 @@ __global__ __launch_bounds__(64 * LM_WAVES) void lit_pointwise_mfma_k(uint8_t *_
     const int ntile = (ocp32 / 32) * (LM_PIX / 32);
     for (int t = wave; t < ntile; t += LM_WAVES) {
         const int oc0 = (t >> 1) * 32, px0 = (t & 1) * 32;
-        lit_v16i acc;
+        i16v acc;
 #pragma unroll
         for (int r = 0; r < 16; r++) acc[r] = 0;
-        const lit_v4i *arow = reinterpret_cast<const lit_v4i *>(w8r + ((long)(oc0 + li) * cin32 + 16 * lh) / 4);
+        const i4v *arow = reinterpret_cast<const i4v *>(w8r + ((long)(oc0 + li) * cin32 + 16 * lh) / 4);
         const unsigned *brow = xs + (4 * lh) * LM_PIX + px0 + li;
         for (int ks = 0; ks < cin32 / 32; ks++) {
-            const lit_v4i a = arow[2 * ks];                                    // 32 input channels = two 16-byte pieces per row: this lane's half
-            lit_v4i b;
+            const i4v a = arow[2 * ks];                                        // 32 input channels = two 16-byte pieces per row: this lane's half
+            i4v b;
 #pragma unroll
             for (int j = 0; j < 4; j++) b[j] = (int)brow[(8 * ks + j) * LM_PIX];
             acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc, 0, 0, 0);
