@@ -53,12 +53,12 @@ class LayerExt(C.Structure):
                 ("act", C.c_int32), ("pad_top", C.c_int32), ("pad_left", C.c_int32), ("in_rows", C.c_int32),
                 ("in_cols", C.c_int32), ("cin", C.c_int32), ("gsize0", C.c_int32), ("gsize1", C.c_int32),
                 ("quirks", C.c_uint32), ("quirks_valid", C.c_int32), ("scale", C.c_void_p), ("shift", C.c_void_p),
-                ("stream", C.c_void_p), ("io_flags", C.c_int32), ("reserved", C.c_int32)]
+                ("stream", C.c_void_p), ("io_flags", C.c_int32), ("dilation", C.c_int32)]
 
 
 class LayerDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("index", "kind", "in_rows", "in_cols", "in_ch", "out_rows", "out_cols",
-                                        "out_ch", "stride", "pad_top", "pad_left")] + \
+                                        "out_ch", "stride", "pad_top", "pad_left", "dilation")] + \
                [(n, C.c_int64) for n in ("w_offset", "w_count", "scale_offset", "shift_offset")]
 
 
@@ -99,8 +99,10 @@ def _declare_host(lib):
     lib.mbn_strerror.argtypes = [C.c_int]
     lib.mbn_plan_build.argtypes = [C.c_float, C.c_int, C.c_int, C.POINTER(Plan)]
     lib.mbn_plan_build_hw.argtypes = [C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(Plan)]
+    lib.mbn_plan_build_os.argtypes = [C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Plan)]
     lib.mbn_weights_from_h5.argtypes = [C.c_char_p, C.c_float, C.c_int, C.POINTER(Weights)]
     lib.mbn_weights_from_h5_hw.argtypes = [C.c_char_p, C.c_float, C.c_int, C.c_int, C.POINTER(Weights)]
+    lib.mbn_weights_from_h5_os.argtypes = [C.c_char_p, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(Weights)]
     lib.mbn_weights_synthetic_h5.argtypes = [C.c_char_p, C.c_float, C.c_int, C.c_uint64]
     lib.mbn_weights_free.argtypes = [C.POINTER(Weights)]
     lib.mbn_h5_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
@@ -267,7 +269,7 @@ def declared_symbols():
 
 
 def make_ext(batch=1, dtype=DT_F32, act=ACT_RELU6, pad_top=-1, pad_left=-1, in_rows=0, in_cols=0, cin=0, scale=None,
-             shift=None, quirks=None, gsize=(0, 0), stream=None, io_flags=0) -> LayerExt:
+             shift=None, quirks=None, gsize=(0, 0), stream=None, io_flags=0, dilation=0) -> LayerExt:
     e = LayerExt()
     e.struct_size = C.sizeof(LayerExt)
     e.batch = batch
@@ -277,6 +279,7 @@ def make_ext(batch=1, dtype=DT_F32, act=ACT_RELU6, pad_top=-1, pad_left=-1, in_r
     e.act = act
     e.pad_top, e.pad_left = pad_top, pad_left
     e.in_rows, e.in_cols, e.cin = in_rows, in_cols, cin
+    e.dilation = dilation                 # depthwise only: 0 / 1 = none
     e.gsize0, e.gsize1 = gsize
     if quirks is not None:
         e.quirks, e.quirks_valid = quirks, 1
@@ -450,11 +453,14 @@ def input_hw(res):
     return int(res), int(res)
 
 
-def plan_build(alpha=1.0, res=224, classes=1000, lib=None) -> Plan:
-    """mbn_plan_build; res = (rows, cols) builds a rows x cols plan (mbn_plan_build_hw)."""
+def plan_build(alpha=1.0, res=224, classes=1000, lib=None, output_stride=32) -> Plan:
+    """mbn_plan_build; res = (rows, cols) builds a rows x cols plan (mbn_plan_build_hw); output_stride 16 / 8 (or anything but 32)
+    goes through mbn_plan_build_os: the late stride-2 depthwise layers stop subsampling, the ones behind them are dilated."""
     p = Plan()
     lib = lib or host_lib()
-    if isinstance(res, (tuple, list)):
+    if output_stride != 32:
+        _chk(lib.mbn_plan_build_os(alpha, *input_hw(res), classes, output_stride, C.byref(p)))
+    elif isinstance(res, (tuple, list)):
         _chk(lib.mbn_plan_build_hw(alpha, *input_hw(res), classes, C.byref(p)))
     else:
         _chk(lib.mbn_plan_build(alpha, res, classes, C.byref(p)))
@@ -478,12 +484,14 @@ def quantize_i8(plan, blob, scales=None, lib=None):
 
 class HostWeights:
     """mbn_weights_from_h5 result; .blob is a numpy view of the packed fp32 parameters. res = (rows, cols): a rows x cols plan
-    (mbn_weights_from_h5_hw), the same blob."""
+    (mbn_weights_from_h5_hw), the same blob; output_stride 16 / 8: the plan of mbn_plan_build_os (mbn_weights_from_h5_os), the same blob."""
 
-    def __init__(self, path, alpha=0.0, res=224, lib=None):
+    def __init__(self, path, alpha=0.0, res=224, lib=None, output_stride=32):
         self.lib = lib or host_lib()
         self.w = Weights()
-        if isinstance(res, (tuple, list)):
+        if output_stride != 32:
+            _chk(self.lib.mbn_weights_from_h5_os(path.encode(), alpha, *input_hw(res), output_stride, C.byref(self.w)), path)
+        elif isinstance(res, (tuple, list)):
             _chk(self.lib.mbn_weights_from_h5_hw(path.encode(), alpha, *input_hw(res), C.byref(self.w)), path)
         else:
             _chk(self.lib.mbn_weights_from_h5(path.encode(), alpha, res, C.byref(self.w)), path)

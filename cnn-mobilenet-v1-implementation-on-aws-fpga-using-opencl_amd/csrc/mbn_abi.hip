@@ -680,6 +680,13 @@ int mbn_depthwise(mbn_context *ctx, void *output, const void *inp_image, const v
         return MBN_EINVAL;
     if (c.in_rows <= 0) c.in_rows = rows * stride;
     if (c.in_cols <= 0) c.in_cols = cols * stride;
+    // ext->dilation (read here only): 0 or 1 = none; fp32 and bf16 honour it, LITERAL and I8 have no dilated form
+    c.dilation = 1;
+    if (ext) {
+        if (ext->dilation < 0) return MBN_EINVAL;
+        if (ext->dilation > 1) c.dilation = ext->dilation;
+    }
+    if (c.dilation > 1 && (dtype == MBN_DT_U8 || dtype == MBN_DT_I8)) return MBN_EUNSUPPORTED;
     if (dtype == MBN_DT_I8) {
         if (filtersize != 3 || stride > 2 || (c.io_flags & MBN_IO_OUT_F32)) return MBN_EUNSUPPORTED;
         if ((rc = i8_check(c, { output, inp_image, filter_k }, true)) != MBN_OK) return rc;

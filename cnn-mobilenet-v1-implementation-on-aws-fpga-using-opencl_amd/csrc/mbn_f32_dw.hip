@@ -14,44 +14,9 @@
 // The 9 filter taps and scale/shift of the lane's 4 channels stay in registers for the whole march.
 // Measured and rejected (profiles/r01): non-temporal output stores (-5..-22 %), one column per lane (TW=1, -10 %),
 // channel-fastest lanes across the full C (-15..-40 % on the 512/1024-channel layers).
-#include "mbn_internal.h"
-#include "mbn_device.h"
+#include "mbn_f32_dw.h"
 
 namespace {
-
-__device__ __forceinline__ f4 ld4(const float *p) { return *reinterpret_cast<const f4 *>(p); }
-__device__ __forceinline__ f4 ld4(const __bf16 *p)
-{
-    const bf4 v = *reinterpret_cast<const bf4 *>(p);
-    return f4{ (float)v.x, (float)v.y, (float)v.z, (float)v.w };
-}
-__device__ __forceinline__ f4 fma4(f4 a, f4 b, f4 c)
-{
-    return f4{ fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y), fmaf(a.z, b.z, c.z), fmaf(a.w, b.w, c.w) };
-}
-__device__ __forceinline__ f4 act4(f4 v, int act)
-{
-    if (act == MBN_ACT_RELU6) {
-        v.x = fminf(fmaxf(v.x, 0.f), 6.f); v.y = fminf(fmaxf(v.y, 0.f), 6.f);
-        v.z = fminf(fmaxf(v.z, 0.f), 6.f); v.w = fminf(fmaxf(v.w, 0.f), 6.f);
-    } else if (act == MBN_ACT_RELU) {
-        v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-    }
-    return v;
-}
-
-struct DwArgs {
-    void *out;
-    const void *in;
-    const float *filt, *scale, *shift;
-    int batch, in_rows, in_cols, rows, cols, ch, pad_top, pad_left, act;
-    int seg_rows, nseg;     // output rows per segment / segments per image
-    int prio;               // wave priority of the whole kernel (3: a memory-bound kernel beside another stream's MFMA-streaming GEMM gets its few VALU slots)
-    int cw;                 // lanes along channels inside a slab (channels per slab = 4*cw)
-    int nslab;              // ch / (4*cw)
-    int lcols;              // lane-columns per row = ceil(cols / TW)
-    long total;             // lanes with work
-};
 
 // One input row for a lane: NC = TW*STRIDE+2 channel-quads at columns ix0 .. ix0+NC-1; zero outside the image.
 template <int NC, typename T>
@@ -492,9 +457,9 @@ static int launch_dw_lds_bf16(const mbn_call &c, const DwArgs &a, int channels, 
 }
 #endif
 
-// Generic fallback (any stride / filtersize / channel count): one lane per output element.
+// Generic fallback (any stride / filtersize / dilation / channel count): one lane per output element.
 template <typename T>
-__global__ __launch_bounds__(256) void dw_generic_nhwc(DwArgs a, int fs, int stride)
+__global__ __launch_bounds__(256) void dw_generic_nhwc(DwArgs a, int fs, int stride, int dil)
 {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long total = (long)a.batch * a.rows * a.cols * a.ch;
@@ -508,10 +473,10 @@ __global__ __launch_bounds__(256) void dw_generic_nhwc(DwArgs a, int fs, int str
     const T *img = reinterpret_cast<const T *>(a.in) + (long)n * a.in_rows * a.in_cols * a.ch;
     float acc = 0.f;
     for (int ky = 0; ky < fs; ky++) {
-        int iy = oy * stride + ky - a.pad_top;
+        int iy = oy * stride + ky * dil - a.pad_top;
         if (iy < 0 || iy >= a.in_rows) continue;
         for (int kx = 0; kx < fs; kx++) {
-            int ix = ox * stride + kx - a.pad_left;
+            int ix = ox * stride + kx * dil - a.pad_left;
             if (ix < 0 || ix >= a.in_cols) continue;
             acc = fmaf((float)img[((long)iy * a.in_cols + ix) * a.ch + c], a.filt[(long)(ky * fs + kx) * a.ch + c], acc);
         }
@@ -701,14 +666,20 @@ template <typename T>
 int launch_dw(const mbn_call &c, DwArgs &a, int rows, int cols, int fs, int stride, int channels)
 {
     const size_t io_align = sizeof(T) * 4;             // one channel-quad
+    const int dil = c.dilation > 1 ? c.dilation : 1;
     const bool fast = fs == 3 && (stride == 1 || stride == 2) && (channels % 4) == 0 &&
                       ((uintptr_t)a.in % io_align) == 0 && ((uintptr_t)a.out % io_align) == 0 &&
                       ((uintptr_t)a.filt % 16) == 0 && (!c.scale || ((uintptr_t)c.scale % 16) == 0) &&
                       (!c.shift || ((uintptr_t)c.shift % 16) == 0);
-    if (!fast) {
+    // dilated (atrous) 3x3, stride 1, rate 2 or 4: the polyphase column march of mbn_f32_dw_dil.hip; any other dilated call: generic
+    if (fast && stride == 1 && (dil == 2 || dil == 4)) {
+        const int rc = mbn_launch_dw_dilated(c, a, dil, sizeof(T) == 2);
+        if (rc != MBN_EUNSUPPORTED) return rc;                 // (grid too large: the generic kernel below)
+    }
+    if (!fast || dil > 1) {
         a.seg_rows = rows; a.nseg = 1; a.total = 0; a.cw = a.nslab = a.lcols = 1;
         long total = (long)c.batch * rows * cols * channels;
-        hipLaunchKernelGGL(dw_generic_nhwc<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c.stream, a, fs, stride);
+        hipLaunchKernelGGL(dw_generic_nhwc<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c.stream, a, fs, stride, dil);
         return MBN_OK;
     }
     const bool cache_resident = (double)c.batch * ((double)a.in_rows * a.in_cols + (double)rows * cols) * channels * sizeof(T) < 64.0 * 1048576;
@@ -724,15 +695,7 @@ int launch_dw(const mbn_call &c, DwArgs &a, int rows, int cols, int fs, int stri
         const int tw8 = (var & 3) == 1 ? 1 : 2;      // 2 columns per lane measured faster on every layer (tune dw_variant=1: one)
         a.lcols = (cols + tw8 - 1) / tw8;
         const long row_lanes = (long)c.batch * a.lcols * c8;
-        const long target = (long)c.ctx->num_cus * 64 * (stride == 1 ? 12 : 6);
-        int nseg = 1;
-        if (g_mbn_tune.dw_nseg > 0) nseg = g_mbn_tune.dw_nseg;
-        else if (row_lanes < target) {
-            nseg = (int)((target + row_lanes - 1) / row_lanes);
-            int max_seg = rows / 4 > 0 ? rows / 4 : 1;
-            if (row_lanes * max_seg < (long)c.ctx->num_cus * 64 || cache_resident) max_seg = rows;   // latency-bound (see the fp32 branch)
-            if (nseg > max_seg) nseg = max_seg;
-        }
+        int nseg = dw_march_segments(c, row_lanes, rows, stride, cache_resident);
         if (nseg > rows) nseg = rows;
         a.seg_rows = (rows + nseg - 1) / nseg;
         a.nseg = (rows + a.seg_rows - 1) / a.seg_rows;
@@ -768,26 +731,8 @@ int launch_dw(const mbn_call &c, DwArgs &a, int rows, int cols, int fs, int stri
     a.cw = cw;
     a.nslab = c4 / cw;
     a.lcols = (cols + tw - 1) / tw;
-    // Row segments: every extra segment re-reads 2 (stride 1) or 1 (stride 2) halo rows from HBM — measured as
-    // 19-36 % over-fetch (FETCH_SIZE, profiles/r01) when segmenting for "two full rounds" of lanes — so segment
-    // only when a full-height march leaves the chip under-filled: ~12 waves/CU for stride 1, ~6 for stride 2
-    // (whose lanes keep 10 loads in flight per step). tools/layer_bench.py --tune dw_nseg=... is the sweep.
     const long row_lanes = (long)c.batch * a.lcols * c4;
-    const long target = (long)c.ctx->num_cus * 64 * (stride == 1 ? 12 : 6);
-    int nseg = 1;
-    if (g_mbn_tune.dw_nseg > 0) nseg = g_mbn_tune.dw_nseg;
-    else if (row_lanes < target) {
-        nseg = (int)((target + row_lanes - 1) / row_lanes);
-        int max_seg = rows / 4 > 0 ? rows / 4 : 1;     // keep >= 4 output rows per segment ...
-        // ... unless even that leaves less than one wave per CU (a few images): then the launch is bound by the length of a
-        // lane's row march (one dependent memory round trip per row: 9-10 us for a 14-row map at batch 1), not by bytes, and
-        // one output row per segment is best
-        // ... or the tensors sit in L2 / Infinity Cache anyway (input + output under 64 MB: 5 ... 64 images on the 14 x 14 and 7 x 7 maps): the
-        // halo rows an extra segment re-reads come from cache, and shorter marches are what the launch is short of — measured 1-5 us per
-        // launch, 2.5-4.5 % of a forward at 8 ... 32 images (profiles/r03/w_depthwise_segments_small_batch.txt)
-        if (row_lanes * max_seg < (long)c.ctx->num_cus * 64 || cache_resident) max_seg = rows;
-        if (nseg > max_seg) nseg = max_seg;
-    }
+    int nseg = dw_march_segments(c, row_lanes, rows, stride, cache_resident);      // the row-segment rule: mbn_f32_dw.h
     // Round 4 (profiles/r04/i_depthwise_stride2_segments.txt): stride 2 on an input of streaming size (>= 512 MB: layer 4 from batch 256 up, 822 MB) runs 5-10 % faster
     // with TWO output rows per segment although a full-height march already fills the chip — 0.1988 -> 0.1861 ms at batch 256, 0.4194 -> 0.3772 at 512,
     // 0.2148 -> 0.1923 at 320 x 320 / 128 images — and 1-20 % slower below that size (411 MB at batch 128: +1 %; cache-sized inputs: +10-20 %): a lane's
@@ -858,8 +803,9 @@ int mbn_launch_f32_depthwise(const mbn_call &c, void *out, const void *in, const
     DwArgs a;
     a.out = out; a.in = in; a.filt = filt; a.scale = c.scale; a.shift = c.shift;
     a.batch = c.batch; a.in_rows = c.in_rows; a.in_cols = c.in_cols; a.rows = rows; a.cols = cols; a.ch = channels;
-    a.pad_top = c.pad_top >= 0 ? c.pad_top : mbn_same_pad(c.in_rows, rows, fs, stride);
-    a.pad_left = c.pad_left >= 0 ? c.pad_left : mbn_same_pad(c.in_cols, cols, fs, stride);
+    const int window = (fs - 1) * (c.dilation > 1 ? c.dilation : 1) + 1;      // effective window of a dilated filter: 2 D + 1 for 3x3
+    a.pad_top = c.pad_top >= 0 ? c.pad_top : mbn_same_pad(c.in_rows, rows, window, stride);
+    a.pad_left = c.pad_left >= 0 ? c.pad_left : mbn_same_pad(c.in_cols, cols, window, stride);
     a.act = c.act;
     a.prio = (g_mbn_tune.dw_variant & 128) ? 0 : 1;       // dw_variant bit 7: A/B hook, no raised priority
     if (c.dtype == MBN_DT_BF16) return launch_dw<__bf16>(c, a, rows, cols, fs, stride, channels);

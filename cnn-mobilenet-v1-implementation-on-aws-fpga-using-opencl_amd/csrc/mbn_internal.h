@@ -106,6 +106,7 @@ struct mbn_call {
     int act;
     int pad_top, pad_left;
     int in_rows, in_cols;
+    int dilation;     // mbn_depthwise: 1 = none (set from ext->dilation by mbn_depthwise; every other call leaves 0)
     int cin;
     int g0, g1;
     uint32_t quirks;

@@ -335,7 +335,7 @@ static int stem_fusable(const mbn_net *net, int count, int last_layer)
     const mbn_layer_desc *l = net->plan.layer;
     return net->fuse_stem && !net->keep && last_layer >= 3 && net->plan.n_layers >= 3 &&
            (net->dtype == MBN_DT_F32 || (net->dtype == MBN_DT_BF16 && net->bf16_filt[2])) &&
-           l[0].kind == MBN_L_CONV && l[1].kind == MBN_L_DW && l[2].kind == MBN_L_PW && l[0].in_ch == 3 && l[1].stride == 1 &&
+           l[0].kind == MBN_L_CONV && l[1].kind == MBN_L_DW && l[2].kind == MBN_L_PW && l[0].in_ch == 3 && l[1].stride == 1 && l[1].dilation <= 1 &&
            mbn_stem_envelope_hw(count, l[0].in_rows, l[0].in_cols, l[0].out_ch, l[2].out_ch) == MBN_OK &&
            layer_aligned(net, 0) && layer_aligned(net, 1) && layer_aligned(net, 2);
 }
@@ -397,6 +397,7 @@ static int block_fusable(const mbn_net *net, int i, int count, int last_layer)
     }
     const mbn_layer_desc *d = &net->plan.layer[i], *p = &net->plan.layer[i + 1];
     if (d->kind != MBN_L_DW || p->kind != MBN_L_PW || p->in_ch != d->out_ch) return 0;
+    if (d->dilation > 1) return 0;                      /* no fused kernel has a dilation: a dilated depthwise layer is its own launch */
     if (!layer_aligned(net, i) || !layer_aligned(net, i + 1)) return 0;
     const mbn_block_shape s = block_shape(net, i, count);
     return mbn_block_envelope(&s, net->dtype) == MBN_OK;
@@ -410,7 +411,7 @@ static int resident_run(const mbn_net *net, int i, int count, int last_layer)
     if (net->dtype != MBN_DT_BF16 || !net->fuse_resident || net->keep) return 0;
     const mbn_layer_desc *d0 = &net->plan.layer[i];
     int k = 0;
-    while (block_fusable(net, i + 2 * k, count, last_layer)) {
+    while (block_fusable(net, i + 2 * k, count, last_layer)) {      /* (never a dilated block: block_fusable refuses it) */
         const mbn_layer_desc *d = &net->plan.layer[i + 2 * k];
         const mbn_block_shape s = block_shape(net, i + 2 * k, count);
         if (d->in_rows != d0->in_rows || d->in_cols != d0->in_cols || mbn_resident_envelope(&s, k + 1) != MBN_OK) break;
@@ -428,6 +429,7 @@ static int tail_run(const mbn_net *net, int i, int count, int last_layer)
     const mbn_layer_desc *d0 = &net->plan.layer[i], *p0 = &net->plan.layer[i + 1], *d1 = &net->plan.layer[i + 2], *p1 = &net->plan.layer[i + 3],
                          *po = &net->plan.layer[i + 4];
     if (d0->kind != MBN_L_DW || p0->kind != MBN_L_PW || d1->kind != MBN_L_DW || p1->kind != MBN_L_PW || po->kind != MBN_L_POOL) return 0;
+    if (d0->dilation > 1 || d1->dilation > 1) return 0;     /* an output_stride 16 / 8 plan: the kernel has no dilation */
     if (!net->bf16_filt[i + 1] || !net->bf16_filt[i + 3]) return 0;
     const unsigned mask = fuse_mask(net);
     if (!((mask >> (i + 1)) & 1u) || !((mask >> (i + 3)) & 1u)) return 0;
@@ -617,6 +619,7 @@ static int run_layer(mbn_net *net, const mbn_layer_desc *l, const void *src, voi
     case MBN_L_DW:                         /* MobileNet.c:326-381 */
         ext.in_rows = l->in_rows;
         ext.in_cols = l->in_cols;
+        ext.dilation = l->dilation;        /* 0 = none; 2 / 4 on the late layers of an output_stride 16 / 8 plan */
         return mbn_depthwise(net->ctx, dst, src, filt, l->out_rows, l->out_cols, 3, l->stride, l->out_ch, &ext);
     case MBN_L_PW:                         /* MobileNet.c:417-470, with filtersize = true Cin (B3) */
         if (bf && net->bf16_packed[l->index - 1]) ext.io_flags |= MBN_IO_FILT_PACKED;

@@ -15,9 +15,14 @@
  * Deviations from the reference's literals, on purpose: layer 13 consumes layer 12
  * (B9), layer 26 has stride 1 (B10), pointwise layers sum over all Cin (B3).
  */
+#include <stddef.h>
 #include <string.h>
 
 #include "mbn.h"
+
+/* `dilation` sits in what was the padding in front of the first int64 field: plans written before it existed read as undilated */
+_Static_assert(sizeof(mbn_layer_desc) == 80 && offsetof(mbn_layer_desc, dilation) == 44 && offsetof(mbn_layer_desc, w_offset) == 48,
+               "mbn_layer_desc: dilation fills the hole at 44, the size and every other offset stay");
 
 static int64_t align_seg(int64_t x) { return (x + 63) & ~(int64_t)63; }   /* 64 floats = 256 B */
 
@@ -36,12 +41,21 @@ int mbn_plan_build(float alpha, int res, int classes, mbn_plan *plan)
  * pad_left from the cols), and the blob layout depends on neither. */
 int mbn_plan_build_hw(float alpha, int rows, int cols, int classes, mbn_plan *plan)
 {
+    return mbn_plan_build_os(alpha, rows, cols, classes, 32, plan);
+}
+
+/* output_stride 16 / 8 (mbn.h): once the map is 1/output_stride of the input, the stride-2 depthwise layers stop subsampling and the
+ * depthwise layers behind them are dilated by the subsampling left out so far; the blob layout does not depend on it. */
+int mbn_plan_build_os(float alpha, int rows, int cols, int classes, int output_stride, mbn_plan *plan)
+{
     /* output channels of conv1 and of the 13 pointwise layers at alpha = 1 (MobileNet.c:16-25) */
     static const int width[14] = { 32, 64, 128, 128, 256, 256, 512, 512, 512, 512, 512, 512, 1024, 1024 };
     /* strides of the 13 depthwise layers (MobileNet.c: L4 :503, L8 :865, L12 :1219, L24 :2264 are 2) */
     static const int dstride[13] = { 1, 2, 1, 2, 1, 2, 1, 1, 1, 1, 1, 2, 1 };
 
     if (!plan) return MBN_EINVAL;
+    if (output_stride == 0) output_stride = 32;
+    if (output_stride != 8 && output_stride != 16 && output_stride != 32) return MBN_EINVAL;
     if (!(alpha > 0.f) || alpha > 4.f || rows < 32 || rows > 4096 || cols < 32 || cols > 4096 || classes <= 0) return MBN_EINVAL;
     /* Odd feature maps are where TF-"SAME" (out = ceil(h/2), pad_top = total/2: what this table computes) and Keras
      * MobileNet (ZeroPadding2D(((0,1),(0,1))) + 'valid': pad_top = 0, out = floor((h-2)/2)+1) disagree — 25 -> 13 vs 12.
@@ -54,6 +68,7 @@ int mbn_plan_build_hw(float alpha, int rows, int cols, int classes, mbn_plan *pl
 
     int64_t off = 0, max_act = (int64_t)rows * cols * 3;
     int n = 0, h = rows, w = cols, ch = 3;
+    int current = 2, rate = 1;                            /* subsampling so far (conv1: 2) and the rate of the next dilated layer */
 
     for (int blk = -1; blk < 13; blk++) {
         if (blk >= 0) {                                   /* depthwise half of block blk */
@@ -63,11 +78,20 @@ int mbn_plan_build_hw(float alpha, int rows, int cols, int classes, mbn_plan *pl
             d->in_rows = h;
             d->in_cols = w;
             d->in_ch = d->out_ch = ch;
-            d->stride = dstride[blk];
+            int dil = 1;
+            if (current == output_stride) {               /* no more subsampling: stride 1, dilated by what was left out */
+                d->stride = 1;
+                dil = rate;
+                rate *= dstride[blk];
+            } else {
+                d->stride = dstride[blk];
+                current *= dstride[blk];
+            }
+            d->dilation = dil > 1 ? dil : 0;              /* undilated layers carry 0: an output_stride 32 plan is the plan it always was */
             d->out_rows = (h + d->stride - 1) / d->stride;
             d->out_cols = (w + d->stride - 1) / d->stride;
-            d->pad_top = same_pad(h, d->out_rows, 3, d->stride);
-            d->pad_left = same_pad(w, d->out_cols, 3, d->stride);
+            d->pad_top = same_pad(h, d->out_rows, 2 * dil + 1, d->stride);     /* effective window of the dilated 3x3 */
+            d->pad_left = same_pad(w, d->out_cols, 2 * dil + 1, d->stride);
             d->w_offset = off; d->w_count = 9 * (int64_t)ch; off = align_seg(off + d->w_count);
             d->scale_offset = off; off = align_seg(off + ch);
             d->shift_offset = off; off = align_seg(off + ch);

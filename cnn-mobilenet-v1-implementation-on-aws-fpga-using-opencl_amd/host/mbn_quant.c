@@ -22,12 +22,12 @@ static int8_t quant_w(float w, float inv)
     return (int8_t)q;
 }
 
-/* the kernels' channel coverage (mbn.h): multiples of 8, K <= 65536 */
+/* the kernels' coverage (mbn.h): channel counts multiples of 8, K <= 65536, no dilated depthwise */
 static int layer_supported(const mbn_layer_desc *l, int i)
 {
     switch (l->kind) {
     case MBN_L_CONV: return i == 0 && l->out_ch % 8 == 0 && l->in_ch > 0 && l->stride >= 1 && l->stride <= 2;
-    case MBN_L_DW:   return l->in_ch == l->out_ch && l->out_ch % 8 == 0 && (l->stride == 1 || l->stride == 2);
+    case MBN_L_DW:   return l->in_ch == l->out_ch && l->out_ch % 8 == 0 && (l->stride == 1 || l->stride == 2) && l->dilation <= 1;
     case MBN_L_PW:   return l->in_ch % 8 == 0 && l->out_ch % 8 == 0 && l->in_ch <= 65536;
     case MBN_L_POOL: return l->in_ch % 8 == 0;
     case MBN_L_FC:   return l->in_ch % 8 == 0 && l->in_ch <= 65536 && l->out_ch > 0;

@@ -74,6 +74,12 @@ int mbn_weights_from_h5(const char *path, float alpha, int res, mbn_weights *w)
 /* the blob layout does not depend on the input size: only the plan's map sizes differ from a square load */
 int mbn_weights_from_h5_hw(const char *path, float alpha, int rows, int cols, mbn_weights *w)
 {
+    return mbn_weights_from_h5_os(path, alpha, rows, cols, 32, w);
+}
+
+/* nor on the output stride: the same bytes under a plan whose last maps are larger and whose late depthwise layers are dilated */
+int mbn_weights_from_h5_os(const char *path, float alpha, int rows, int cols, int output_stride, mbn_weights *w)
+{
     if (!path || !w) return MBN_EINVAL;
     memset(w, 0, sizeof(*w));
     mbn_h5 *h5 = NULL;
@@ -93,7 +99,7 @@ int mbn_weights_from_h5_hw(const char *path, float alpha, int rows, int cols, mb
         rc = mbn_h5_get(h5, "/conv_preds/conv_preds/bias:0", &ndim, shape, &p);
         if (rc == MBN_OK) classes = (int)shape_count(ndim, shape);
     }
-    if (rc == MBN_OK) rc = mbn_plan_build_hw(alpha, rows, cols, classes, &w->plan);
+    if (rc == MBN_OK) rc = mbn_plan_build_os(alpha, rows, cols, classes, output_stride, &w->plan);
     if (rc == MBN_OK) {
         w->blob = (float *)calloc((size_t)w->plan.blob_floats, sizeof(float));
         if (!w->blob) rc = MBN_ENOMEM;

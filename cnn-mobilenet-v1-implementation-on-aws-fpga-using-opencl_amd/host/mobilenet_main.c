@@ -4,6 +4,7 @@
  *   mobilenet --h5 weights.h5 [--ppm image.ppm] [--batch N] [--res 224] [--alpha 1.0]      fp32 path
  *   mobilenet --synthetic SEED [--alpha A] [--res R] [--batch N]                              fp32, synthetic weights
  *   --res R = R x R images; --res RxC = R rows by C columns (a P6 image C wide and R high), both multiples of 32
+ *   --output-stride 32 | 16 | 8: the late stride-2 depthwise layers stop subsampling, the ones behind them are dilated (mbn_plan_build_os)
  *   mobilenet --literal [--weights weights_c.txt] [--image Cat_Image0.ppm] [--ref-args]      the reference's own mode
  *   mobilenet --gpus G --batch N [--steps K --warmup W --streams S --pw-emul 6] (--h5 F | --synthetic SEED)  N images sharded over G GPUs
  *   mobilenet --inspect weights.h5                                                             list the datasets of a .h5
@@ -328,7 +329,7 @@ int main(int argc, char **argv)
     if (argc == 3 && !strcmp(argv[1], "--inspect")) return inspect_h5(argv[2]);
     if (argc == 4 && !strcmp(argv[1], "--convert")) return convert_h5(argv[2], argv[3]);
     const char *h5 = NULL, *ppm = NULL, *wfile = "weights_c.txt", *image = "Cat_Image0.ppm";
-    int literal = 0, ref_args = 0, batch = 1, rows = 224, cols = 224, have_seed = 0, gpus = 0, steps = 20, warmup = 3, verify = 0;
+    int literal = 0, ref_args = 0, batch = 1, rows = 224, cols = 224, have_seed = 0, gpus = 0, steps = 20, warmup = 3, verify = 0, out_stride = 32;
     unsigned long long seed = 0;
     float alpha = 0.f;
     for (int i = 1; i < argc; i++) {
@@ -344,6 +345,7 @@ int main(int argc, char **argv)
             if (end && (*end == 'x' || *end == 'X')) cols = atoi(end + 1);
         }
         else if (!strcmp(argv[i], "--alpha") && i + 1 < argc) alpha = (float)atof(argv[++i]);
+        else if (!strcmp(argv[i], "--output-stride") && i + 1 < argc) out_stride = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--synthetic") && i + 1 < argc) { seed = strtoull(argv[++i], NULL, 0); have_seed = 1; }
         else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--steps") && i + 1 < argc) steps = atoi(argv[++i]);
@@ -356,11 +358,12 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--literal")) literal = 1;
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
-            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F] [--batch N] [--res R | RxC] [--alpha A] "
+            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] "
                             "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n", argv[0]);
             return 2;
         }
     }
+    if (out_stride != 0 && out_stride != 8 && out_stride != 16 && out_stride != 32) { fprintf(stderr, "bad --output-stride (32, 16 or 8)\n"); return 2; }
     mbn_context *ctx = NULL;
     if (gpus > 0 && !literal) {
         if (batch < 1 || steps < 1 || warmup < 0 || g_streams < 1 || g_streams > 8) { fprintf(stderr, "bad --batch/--steps/--warmup/--streams\n"); return 2; }
@@ -374,7 +377,7 @@ int main(int argc, char **argv)
             h5 = tmpm;
         }
         mbn_weights wm;
-        CHECK(mbn_weights_from_h5_hw(h5, alpha, rows, cols, &wm));
+        CHECK(mbn_weights_from_h5_os(h5, alpha, rows, cols, out_stride, &wm));
         if (h5 == tmpm) remove(tmpm);
         int rc = run_multi(gpus, batch, steps, warmup, &wm, verify);
         mbn_weights_free(&wm);
@@ -400,7 +403,7 @@ int main(int argc, char **argv)
         h5 = tmp;
     }
     mbn_weights w;
-    CHECK(mbn_weights_from_h5_hw(h5, alpha, rows, cols, &w));
+    CHECK(mbn_weights_from_h5_os(h5, alpha, rows, cols, out_stride, &w));
     if (have_seed) remove(tmp);
     mbn_net *net = NULL;
     CHECK(mbn_net_create(ctx, &w, batch, &net));

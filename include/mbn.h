@@ -117,7 +117,10 @@ typedef struct mbn_layer_ext {
     const void *shift;     /* F32: device ptr, op_size floats, added after scale (folded BN / FC bias); NULL => 0 */
     void    *stream;       /* hipStream_t; NULL => the context's stream */
     int32_t  io_flags;     /* MBN_DT_BF16 only: MBN_IO_* (which side of the call is fp32 instead of bf16) */
-    int32_t  reserved;
+    int32_t  dilation;     /* depthwise, F32 / BF16: dilation (atrous rate) D of the filter: tap (ky, kx) reads input row oy*stride + ky*D - pad_top,
+                            * column likewise; 0 or 1 = none, negative = MBN_EINVAL. pad_top / pad_left = -1 computes SAME with the effective
+                            * window (filtersize - 1) * D + 1 (3x3: 2 D + 1, so stride 1 pads D). LITERAL and I8: D > 1 = MBN_EUNSUPPORTED.
+                            * Every other call ignores it */
 } mbn_layer_ext;
 
 /* bf16 mode (BASELINE config 5): activations bf16 NHWC in HBM, pointwise/FC filters bf16 [Cout][Cin], everything
@@ -219,7 +222,7 @@ int mbn_convolute(mbn_context *ctx, void *output, const void *inp_image_r, const
                   const void *inp_image_b, const void *filter_k, int rows, int cols, int filtersize,
                   int stride, int op_size, const mbn_layer_ext *ext);
 
-/* depthwise (kernel.cl:62): per-channel 3x3, stride 1 or 2.
+/* depthwise (kernel.cl:62): per-channel 3x3, stride 1 or 2; F32 / BF16: dilated by ext->dilation (output-stride 16 / 8 plans).
  *   rows, cols = OUTPUT plane size (the only use kernel.cl makes of them: output_shift, :73);
  *                input plane = ext->in_rows x in_cols, default rows*stride x cols*stride
  *   op_size    = channels
@@ -430,6 +433,8 @@ typedef struct mbn_layer_desc {
     int32_t out_rows, out_cols, out_ch;
     int32_t stride;
     int32_t pad_top, pad_left;       /* TF-SAME */
+    int32_t dilation;     /* depthwise layers of an output_stride 16 / 8 plan: dilation of the 3x3 filter (2 or 4); 0 = none (readers treat 0 as 1).
+                           * It fills what was the padding in front of w_offset: the struct's size (80) and every other offset are unchanged */
     int64_t w_offset;     /* float offset of this layer's filter in the packed blob */
     int64_t w_count;
     int64_t scale_offset; /* float offset of per-channel scale (out_ch floats); -1 = none */
@@ -455,6 +460,15 @@ int  mbn_plan_build(float alpha, int res, int classes, mbn_plan *plan);
  * MBN_EINVAL as mbn_plan_build). The blob layout and every offset do not depend on the input size. plan->res = rows when rows == cols
  * (mbn_plan_build(a, r, c) is mbn_plan_build_hw(a, r, r, c), byte for byte), 0 otherwise. */
 int  mbn_plan_build_hw(float alpha, int rows, int cols, int classes, mbn_plan *plan);
+/* The same with an output stride (the option of TF-slim's mobilenet_v1_base): output_stride = 32 (or 0) is mbn_plan_build_hw byte for byte;
+ * 16 or 8 stops subsampling once the map is 1/16 or 1/8 of the input, so layer 27 is a dense feature map for detection / segmentation heads
+ * (mbn_net_forward(..., last_layer = 27)). Walk the 13 depthwise layers with current = 2 (conv1's stride) and rate = 1; a layer whose table
+ * stride is s runs, if current == output_stride, with stride 1 and dilation `rate`, and then rate *= s; otherwise with stride s, undilated, and
+ * then current *= s. A dilated stride-1 layer pads D on each side (SAME with the window 2 D + 1) and keeps the map size. 1.0x224: 16 turns
+ * layer 24 into stride 1 and dilates layer 26 by 2 (14 x 14 out); 8 turns layers 12 and 24 into stride 1, dilates 14-24 by 2 and 26 by 4 (28 x 28).
+ * The blob layout and every offset do not depend on it (trained weights stay valid); max_act_floats follows the larger maps. Any other value:
+ * MBN_EINVAL. Dilated layers run as their own launches (no fused kernel takes one) in fp32 and bf16; the I8 mode refuses such a plan. */
+int  mbn_plan_build_os(float alpha, int rows, int cols, int classes, int output_stride, mbn_plan *plan);
 
 /* int8 inference mode (MBN_DT_I8). The arithmetic, normative (tests/test_int8_*.py reproduce it bit for bit):
  *   activations  uint8 NHWC, zero point 0, real value = q * s_l with one fp32 scale per layer. Every conv / depthwise / pointwise layer
@@ -477,7 +491,9 @@ int  mbn_plan_build_hw(float alpha, int rows, int cols, int classes, mbn_plan *p
  * mbn_pointwise with MBN_IO_OUT_F32 writes fp32 (the FC) and requires MBN_ACT_NONE; MBN_ACT_NONE is accepted only there, every uint8
  * output clamps to [0, 255].
  * conv1: 3x3, 3 input channels. Depthwise: 3x3, stride 1 or 2. Channel counts (conv1 / depthwise / pointwise outputs, pointwise / pool inputs) must be multiples
- * of 8, otherwise MBN_EUNSUPPORTED. The fused entry points (stem, blocks, resident, pool + FC) have no I8 form. */
+ * of 8, otherwise MBN_EUNSUPPORTED. The fused entry points (stem, blocks, resident, pool + FC) have no I8 form.
+ * No dilation: mbn_depthwise with ext->dilation > 1 answers MBN_EUNSUPPORTED in this mode (and in LITERAL), and mbn_quantize_i8 /
+ * mbn_net_set_dtype(net, MBN_DT_I8) answer MBN_EUNSUPPORTED for a plan with a dilated layer (mbn_plan_build_os with output stride 16 or 8). */
 typedef struct mbn_i8_layer {
     int64_t w_offset;        /* byte offset of the int8 filter in the i8 blob (element order of the fp32 blob's filter); -1: conv1 keeps fp32, pool */
     int64_t mult_offset;     /* byte offset of out_ch fp32 multipliers; -1 for pool */
@@ -490,7 +506,7 @@ typedef struct mbn_i8_params { int32_t n_layers; int64_t blob_bytes; mbn_i8_laye
  * FC entries are ignored; each used one must be finite and > 0). Fills *p; i8_blob NULL = fill *p only, else p->blob_bytes bytes are
  * written there. Layout: per layer, in order, [int8 filter][mult (out_ch fp32)][bias (out_ch fp32)], each segment 256-byte aligned;
  * conv1 has no filter segment (its fp32 filter is read from the fp32 blob at plan->layer[0].w_offset), the pool has none at all.
- * MBN_EUNSUPPORTED for a plan whose channel counts the I8 kernels do not cover (see above). Host code only: also in libmbn_host.so. */
+ * MBN_EUNSUPPORTED for a plan whose channel counts the I8 kernels do not cover or that has a dilated layer (see above). Host code only: also in libmbn_host.so. */
 int  mbn_quantize_i8(const mbn_plan *plan, const float *blob, const float *act_scales, mbn_i8_params *p, void *i8_blob);
 
 /* Host-side packed weights: one contiguous fp32 blob (this is what is broadcast over RCCL). */
@@ -505,6 +521,8 @@ typedef struct mbn_weights {
 int  mbn_weights_from_h5(const char *path, float alpha, int res, mbn_weights *w);
 /* The same with a rows x cols plan (mbn_plan_build_hw); rows <= 0 => 224, cols <= 0 => rows. The blob is that of any square load. */
 int  mbn_weights_from_h5_hw(const char *path, float alpha, int rows, int cols, mbn_weights *w);
+/* The same with the plan of mbn_plan_build_os(..., output_stride): the same blob, byte for byte, under a plan with larger final maps. */
+int  mbn_weights_from_h5_os(const char *path, float alpha, int rows, int cols, int output_stride, mbn_weights *w);
 /* Deterministic synthetic weights: N(0, 2/fan_in) kernels, BN gamma U[.5,1.5], beta N(0,.1),
  * mean N(0,.1), var U[.5,1.5]; written in Keras layout so the same reader path loads them. */
 int  mbn_weights_synthetic_h5(const char *path, float alpha, int classes, uint64_t seed);

@@ -1,6 +1,8 @@
 """Throughput of non-square inputs (rows x cols) against the square networks, in one process.
 
-  python tools/rect_bench.py [--reps 7] [--steps 20]
+  python tools/rect_bench.py [--reps 7] [--steps 20] [--output-stride 32,16,8] [--configs f32_1.0_224x224,bf16_1.0_224x224]
+      --output-stride: every chosen configuration once per listed output stride (mbn_plan_build_os; `_osN` is appended to the name
+      of the 16 / 8 plans), timed alternately with the others; --configs: only the named configurations
       images/s and Mpixel/s (input pixels) of the configurations below, alternating within every repetition; each figure is the median
       over the repetitions of `steps` back-to-back forwards between two stream marks. Then each configuration's launch list (first layer,
       layers) and its per-layer forward_timed times (one launch per layer), so a shortfall names the layer responsible. Ratios: each
@@ -46,17 +48,23 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--output-stride", default="32", help="comma list of 32, 16, 8")
+    ap.add_argument("--configs", default="", help="comma list of configuration names (default: all)")
     a = ap.parse_args()
+    strides = [int(x) for x in a.output_stride.split(",")]
+    chosen = [c for c in CONFIGS if not a.configs or c[0] in a.configs.split(",")]
+    configs = [(name if os_ == 32 else "%s_os%d" % (name, os_), dtype, alpha, rows, cols, batch, os_)
+               for name, dtype, alpha, rows, cols, batch in chosen for os_ in strides]
     pkg = import_package()
     result = {}
     with tempfile.TemporaryDirectory() as d, pkg.Context(0) as ctx:
         weights, runs = {}, {}
-        for name, dtype, alpha, rows, cols, batch in CONFIGS:
+        for name, dtype, alpha, rows, cols, batch, os_ in configs:
             if alpha not in weights:
                 path = os.path.join(d, "w_%g.h5" % alpha)
                 pkg.synthetic_h5(path, alpha=alpha, classes=CLASSES, seed=7)
                 weights[alpha] = path
-            hw = pkg.HostWeights(weights[alpha], res=(rows, cols))
+            hw = pkg.HostWeights(weights[alpha], res=(rows, cols), output_stride=os_)
             net = pkg.Net(ctx, hw.plan, hw.blob.copy(), batch)
             if dtype == "bf16":
                 net.set_dtype(pkg.DT_BF16)
@@ -67,7 +75,7 @@ def main():
         for _ in range(a.reps):
             for name, r in runs.items():
                 r["ips"].append(timed(ctx, r["net"], r["d_in"], r["d_out"], r["batch"], a.steps))
-        for name, dtype, alpha, rows, cols, batch in CONFIGS:
+        for name, dtype, alpha, rows, cols, batch, os_ in configs:
             r = runs[name]
             ips = statistics.median(r["ips"])
             ms = r["net"].forward_timed(r["d_in"].ptr, r["d_out"].ptr, batch)
@@ -77,9 +85,9 @@ def main():
             print("%-18s batch %4d %9d images/s %9.1f Mpixel/s  %s" % (name, batch, result[name]["images_per_s"], result[name]["mpixel_per_s"],
                                                                       [c for _, c in result[name]["launches"]]), flush=True)
         ratios = {}
-        for name, dtype, alpha, rows, cols, batch in CONFIGS:
-            sq = next(n for n, dt, al, rr, cc, _ in CONFIGS if dt == dtype and al == alpha and rr == cc)
-            if name != sq:
+        for name, dtype, alpha, rows, cols, batch, os_ in configs:
+            sq = next((n for n, dt, al, rr, cc, _, o in configs if dt == dtype and al == alpha and rr == cc and o == os_), None)
+            if sq is not None and name != sq:
                 ratios[name] = round(result[name]["mpixel_per_s"] / result[sq]["mpixel_per_s"], 3)
         result["mpixel_ratio_to_square"] = ratios
         print("Mpixel/s over the square shape's:", ratios)
