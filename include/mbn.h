@@ -207,6 +207,27 @@ int  mbn_profile_null(mbn_context *ctx, int with_kernel, void *stream);
 int  mbn_mark(mbn_context *ctx, void *stream);
 int  mbn_marks_read(mbn_context *ctx, float *ms_between, int capacity, int *count);
 
+/* --------------------------------------------------------------- pointer alignment (tests/test_alignment_gpu.py pins the layer calls and one refusal of every call below;
+ * mbn_classifier_tail_fused, the _ex / _u8 stem forms and the uint8 stem image are stated from the code, not tested there)
+ * The four layer calls — mbn_convolute, mbn_depthwise, mbn_pointwise, mbn_pool — in F32 and BF16 accept ANY pointer that is a multiple
+ * of its own element size (fp32 4 bytes, bf16 2, the MBN_IO_IN_U8 image 1; scale / shift 4) for every operand: an interior pointer of an
+ * mbn_alloc buffer, a sliced torch tensor. They never refuse one and never touch a byte outside the tensors. An input, filter or (outside
+ * mbn_pointwise) output, scale or shift that is not on 16 bytes (bf16 activations of mbn_depthwise: 8) makes the call take a slower kernel,
+ * down to one lane per output element, whose summation order may differ from the aligned call's in the last bits (within the mode's
+ * tolerance). mbn_pointwise keeps its GEMM for any element-aligned `out`, `scale` and `shift` (its bf16 epilogue relies on the device's
+ * unaligned-access mode for that: mbn_f32_pw.hip); only the bf16 streaming kernels want `out` on 4 and scale / shift on 8 bytes and hand
+ * the call to that GEMM otherwise. (I8: 8 bytes, see below; LITERAL is byte-granular.)
+ * The other device calls load and store 16 bytes at a time and REFUSE instead, launching nothing:
+ *   mbn_dwpw_fused, mbn_dwpw_fused_bf16, mbn_blocks_resident_bf16   any pointer off 16 bytes: MBN_EUNSUPPORTED
+ *   mbn_tail_resident_bf16        `in` or a parameter off 16 bytes: MBN_EUNSUPPORTED (`out` is stored per bf16 element: any multiple of 2)
+ *   mbn_stem_fused_hw (_ex, _u8)  a filter / scale / shift off 16 bytes: MBN_EUNSUPPORTED; `out` off 16 bytes, an fp32 image off 8 or a
+ *                                 uint8 image off 2: MBN_EINVAL
+ *   mbn_pool_fc, mbn_classifier_tail_fused   `fc_w` or `workspace` off 16 bytes: MBN_EUNSUPPORTED (`in`, `logits`, `fc_bias`: any multiple of 4)
+ *   mbn_convert_f32_to_bf16       `src_f32` off 16 bytes or `dst_bf16` off 8: MBN_EINVAL (mbn_convert_bf16_to_f32: any element-aligned pointer)
+ *   mbn_normalize_u8_to_f32       `out_f32` off 16 bytes or `in_u8` off 4: MBN_EINVAL
+ * MBN_EUNSUPPORTED is the code a caller answers by issuing the separate layer calls (mbn_net_forward does); MBN_EINVAL has no such fall-back.
+ */
+
 /* --------------------------------------------------------------- layer calls
  * Positional parameters are kernel.cl's, in kernel.cl's order and meaning:
  *
