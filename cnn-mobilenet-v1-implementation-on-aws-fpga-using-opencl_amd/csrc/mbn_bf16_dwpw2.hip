@@ -17,6 +17,7 @@
 // within the bf16 tolerance of the parity tests, not bit-identical.
 #include "mbn_internal.h"
 #include "mbn_epilogue.h"
+#include "mbn_block_window.h"
 
 namespace {
 
@@ -40,7 +41,7 @@ struct DwPw2Args {
     int dbg;                // experiments (tune misc): 1 = no x loads after the first, 2 = no depthwise math, 4 = no output stores, 8 = no filter DMA, 16 = no MFMA
     unsigned wo_m, wo_s, ho_m, ho_s;   // floor(v / wo) = umulhi(v, wo_m) >> wo_s for v < 2^31 (m == 0: the divisor is 1)
     int use4;               // launcher: the 4-wave / two-workgroups-per-CU form is allowed (tune exp2 == 44 in the lab build until measured)
-    int fast_off;           // launcher: 1 = the FO instantiation (tile offsets in their full-rate form, as in mbn_f32_dwpw2.hip: input < 0x70000000 bytes)
+    int fast_off;           // launcher: 1 = the FO instantiation (tile offsets in their full-rate form: mbn_block_fast_offsets)
     float inv_wo, inv_ho;   // 1 / wo, 1 / ho
 };
 
@@ -61,7 +62,7 @@ __device__ __forceinline__ void dma_filter(__amdgpu_buffer_rsrc_t rsrc, float *l
 // bf16 1.0x224 batch 512, alternating runs): blocks 4-11 0.746-0.754 ms against 0.739-0.749 with 32x32x16 — equal within the run-to-run spread, 0.8 % worse
 // on the means: a block's matrix work is a sixteenth of the fp32 kernel's, too thin to pull the clock down, and the 16 x 16 form holds 24-32 more
 // fragment registers. Parity-tested (oracle + exact integers, tests/test_parity_gpu.py::test_bf16_dwpw_fused under MBN_LAB=1), not shipped.
-// FO (round 5): set_offsets from full-rate instructions — see mbn_f32_dwpw2.hip (set_offsets_fast). In bf16 a block with Cin <= 64 is ONE chunk per tile, so the
+// FO (round 5): set_offsets from full-rate instructions — see mbn_block_window.h. In bf16 a block with Cin <= 64 is ONE chunk per tile, so the
 // offsets are computed in every step: the general form's two v_mul_hi_u32, six v_mul_lo_u32 and 12-15 compare/select pairs under exec-mask branches were ~20 % of it.
 // NW (round 5): 8 = one workgroup of 8 waves per CU on 128-row tiles (rounds 2-4); 4 = 4 waves on 64-row tiles, two independent workgroups per CU (61 KB of LDS each:
 // Cin, Cout <= 256): they fall out of phase by themselves, so one's waits, barrier and epilogue run under the other's depthwise arithmetic. Pays only below the power limit
@@ -99,13 +100,7 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_bf16(DwPw2Args a)
     const int nk = (a.cin + 63) / 64, nwg = a.mt * a.nt;
     const unsigned mtot = (unsigned)a.m;
 
-    for (int i = tid * 4; i < 9 * a.cin; i += NT * 4) *reinterpret_cast<f4 *>(wd_s + i) = *reinterpret_cast<const f4 *>(a.wd + i);
-    for (int i = tid * 4; i < a.cin; i += NT * 4) {
-        *reinterpret_cast<f4 *>(sb_s + i) = *reinterpret_cast<const f4 *>(a.s2 + i);
-        *reinterpret_cast<f4 *>(sb_s + a.cin + i) = *reinterpret_cast<const f4 *>(a.b2 + i);
-    }
-    for (int i = tid; i < a.cout; i += NT) { sc3_s[i] = a.s3[i]; sh3_s[i] = a.b3[i]; }
-    __syncthreads();
+    mbn_block_constants_to_lds<NT, CMAX, NOUT>(a, tid, wd_s);
     if ((int)blockIdx.x >= nwg) return;
 
     // ---- roles of this lane
@@ -136,56 +131,10 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_bf16(DwPw2Args a)
     const float *sk = sb_s + c4 * 8;
 
     unsigned off[3][XC];
-    auto set_offsets_general = [&](unsigned m0) __attribute__((always_inline)) {
-        const unsigned m = m0 + 2 * pair;
-        const bool mok = m < mtot && cok;
-        const unsigned q = a.wo_m ? __umulhi(m, a.wo_m) >> a.wo_s : m;
-        const unsigned x = m - q * (unsigned)a.wo;
-        const unsigned n = a.ho_m ? __umulhi(q, a.ho_m) >> a.ho_s : q;
-        const unsigned y = q - n * (unsigned)a.ho;
-        const int iy0 = (int)y * S - a.pad_top, ix0 = (int)x * S - a.pad_left;
-        const unsigned cs = (unsigned)a.cin * 2u, rs = (unsigned)a.w * cs;                    // column / row stride in bytes
-        const unsigned base = ((n * a.h + iy0) * a.w + ix0) * cs + (unsigned)(c4 * 8) * 2u;         // wraps for taps that are masked out below
-#pragma unroll
-        for (int dy = 0; dy < 3; dy++) {
-            const bool rok = mok && (unsigned)(iy0 + dy) < (unsigned)a.h;
-#pragma unroll
-            for (int j = 0; j < XC; j++) {
-                const bool ok = rok && (unsigned)(ix0 + j) < (unsigned)a.w;
-                off[dy][j] = ok ? base + dy * rs + j * cs : MBN_OOB;
-            }
-        }
-    };
-    auto set_offsets_fast = [&](unsigned m0) __attribute__((always_inline)) {
-        const unsigned q0 = a.wo_m ? __umulhi(m0, a.wo_m) >> a.wo_s : m0;                    // wave-uniform: scalar unit
-        const unsigned x0 = m0 - q0 * (unsigned)a.wo;
-        const unsigned n0 = a.ho_m ? __umulhi(q0, a.ho_m) >> a.ho_s : q0;
-        const unsigned y0 = q0 - n0 * (unsigned)a.ho;
-        const unsigned r = x0 + 2u * (unsigned)pair;
-        const unsigned q1 = (unsigned)__builtin_fmaf((float)r, a.inv_wo, 0.5f * a.inv_wo);     // exact: r < wo + 128, see the fp32 kernel
-        const unsigned x = r - q1 * (unsigned)a.wo;
-        const unsigned yy = y0 + q1;
-        const unsigned q2 = (unsigned)__builtin_fmaf((float)yy, a.inv_ho, 0.5f * a.inv_ho);
-        const unsigned y = yy - q2 * (unsigned)a.ho;
-        const unsigned n = n0 + q2;
-        const bool mok = m0 + 2u * (unsigned)pair < mtot && cok;
-        const int iy0 = (int)y * S - a.pad_top, ix0 = (int)x * S - a.pad_left;
-        const unsigned cs = (unsigned)a.cin * 2u, rs = (unsigned)a.w * cs;
-        const int pix = __mul24((int)(n * (unsigned)a.h) + iy0, a.w) + ix0;
-        const unsigned base = (unsigned)pix * cs + (unsigned)(c4 * 8) * 2u;
-        unsigned rowv[3], colv[XC];
-#pragma unroll
-        for (int dy = 0; dy < 3; dy++) rowv[dy] = (mok && (unsigned)(iy0 + dy) < (unsigned)a.h) ? base + dy * rs : 0x80000000u;
-#pragma unroll
-        for (int j = 0; j < XC; j++) colv[j] = ((unsigned)(ix0 + j) < (unsigned)a.w) ? j * cs : 0x70000000u;
-#pragma unroll
-        for (int dy = 0; dy < 3; dy++)
-#pragma unroll
-            for (int j = 0; j < XC; j++) off[dy][j] = rowv[dy] + colv[j];
-    };
-    auto set_offsets = [&](unsigned m0) __attribute__((always_inline)) {
-        if constexpr (FO) set_offsets_fast(m0);
-        else set_offsets_general(m0);
+    const unsigned cs = (unsigned)a.cin * 2u, cb = (unsigned)(c4 * 8) * 2u;             // pixel stride, this lane's channels: bytes
+    auto set_offsets = [&](unsigned m0) __attribute__((always_inline)) {                 // mbn_block_window.h
+        if constexpr (FO) mbn_window_offsets_fast<S>(off, a, cs, cb, m0, 2u * (unsigned)pair, mtot, cok);
+        else mbn_window_offsets<S>(off, a, cs, cb, m0 + 2 * pair, mtot, cok);
     };
     u4 xr[3][XC];                                                             // the window stays packed (4 VGPRs per vector)
     auto ldx = [&](int kc) __attribute__((always_inline)) {
@@ -464,15 +413,8 @@ int mbn_launch_bf16_dwpw2(mbn_context *ctx, hipStream_t stream, const mbn_block_
     const int variant = g_mbn_tune.dwpw_variant;
     a.wp_bytes = (unsigned)(2.0 * s.cin * s.cout);
     a.dbg = variant >= 100 ? variant - 100 : 0;
-    a.inv_wo = 1.0f / (float)s.out_cols;
-    a.inv_ho = 1.0f / (float)s.out_rows;
     a.use4 = 0;
-    // the full-rate offsets' range: every input byte offset PLUS a left-pad column stays below the invalid-column constant 0x70000000
-    // (a left-pad tap of image 0 / row 0 has base = -pad_left * cs: its sum with the constant must not wrap into the descriptor's range), the
-    // row / image quotients stay in exact float range, (n h + iy0) in mul24 range
-    const double cs_b = 2.0 * s.cin;
-    a.fast_off = (2.0 * s.batch * s.in_rows * s.in_cols * s.cin + (s.pad_left + 1) * cs_b <= (double)0x70000000u && (double)s.batch * s.in_rows < 8388000.0 &&
-                  s.in_cols < 32768 && s.out_cols < 32768 && s.out_rows < 32768 && s.pad_left <= 1) ? 1 : 0;
+    a.fast_off = mbn_block_fast_offsets(&s, MBN_DT_BF16) == MBN_OK ? 1 : 0;
 #ifdef MBN_LAB
     a.use4 = g_mbn_tune.exp2 == 44 ? 1 : 0;
     if (g_mbn_tune.exp0 == 51) a.fast_off = 0;                                     // lab A/B: the general offsets

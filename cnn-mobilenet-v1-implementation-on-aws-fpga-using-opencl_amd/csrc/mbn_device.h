@@ -1,6 +1,8 @@
 // mbn_device.h — the device helpers every kernel file shares: vector types, buffer descriptors, the persistent grids' tile
 // order, the LDS swizzles, bf16 widening, the ReLU6 epilogue, counted waits and the 16-byte store hazard. Several of these are
 // formats the kernels must agree on byte for byte (the fused blocks' LDS image is that of pw_gemm), so each has one definition.
+// What only a family of kernels shares sits on top of this header: mbn_epilogue.h (buffer-store epilogues), mbn_block_window.h (the fused
+// blocks' window offsets and prologue), mbn_x6.h (the pw_emul kernels' operand split and product list).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -25,6 +25,7 @@
 // When Cout > BN the depthwise work is recomputed per column tile (n-tile index fastest, so the re-reads hit L2).
 #include "mbn_internal.h"
 #include "mbn_epilogue.h"
+#include "mbn_block_window.h"
 
 namespace {
 
@@ -85,26 +86,7 @@ __global__ __launch_bounds__(NT) void dwpw_f32(DwPwArgs a)
             const int lid = mbn_xcd_remap(v, nwg);
             const int n0 = (lid % a.nt) * BN;
             const unsigned m = (unsigned)(lid / a.nt) * BM + 2 * pair;
-            const bool mok = m < mtot;
-            // (n, y, x) of the pixel by multiply-high division (host-computed magic numbers), then every tap offset as
-            // base + dy * row stride + j * column stride: this runs once per tile per lane and used to cost ~400 VALU
-            // instructions (two 32-bit divisions + 12-15 independent offset computations)
-            const unsigned q = a.wo_m ? __umulhi(m, a.wo_m) >> a.wo_s : m;
-            const unsigned x = m - q * (unsigned)a.wo;
-            const unsigned n = a.ho_m ? __umulhi(q, a.ho_m) >> a.ho_s : q;
-            const unsigned y = q - n * (unsigned)a.ho;
-            const int iy0 = (int)y * S - a.pad_top, ix0 = (int)x * S - a.pad_left;
-            const unsigned cs = (unsigned)a.cin * 4u, rs = (unsigned)a.w * cs;                    // column / row stride in bytes
-            const unsigned base = ((n * a.h + iy0) * a.w + ix0) * cs + (unsigned)(c4 * 4) * 4u;         // wraps for taps that are masked out below
-#pragma unroll
-            for (int dy = 0; dy < 3; dy++) {
-                const bool rok = mok && (unsigned)(iy0 + dy) < (unsigned)a.h;
-#pragma unroll
-                for (int j = 0; j < XC; j++) {
-                    const bool ok = rok && (unsigned)(ix0 + j) < (unsigned)a.w;
-                    off[dy][j] = ok ? base + dy * rs + j * cs : MBN_OOB;
-                }
-            }
+            mbn_window_offsets<S>(off, a, (unsigned)a.cin * 4u, (unsigned)(c4 * 4) * 4u, m, mtot, true);      // mbn_block_window.h
 #pragma unroll
             for (int p = 0; p < B_LD; p++) {
                 const int row = (p * NP + t) >> 3;

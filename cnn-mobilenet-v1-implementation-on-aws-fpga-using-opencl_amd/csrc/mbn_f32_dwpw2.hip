@@ -35,6 +35,7 @@
 // LDS-DMA of buffer p^1 apart from the fragment reads of buffer p instead of draining vmcnt before each ds_read).
 #include "mbn_internal.h"
 #include "mbn_epilogue.h"
+#include "mbn_block_window.h"
 
 namespace {
 
@@ -62,7 +63,7 @@ struct DwPw2Args {
                             // 8 = no filter DMA, 16 = no MFMA, 32 = unpaired column blocks (4-byte stores); round 5 (timing only): 1024 = no tap reads after the first chunk,
                             // 2048 = only the first fragment read of a step (the MFMAs reuse registers), 4096 = no barrier (waits only), 8192 = no epilogue arithmetic/zeroing either (with 4)
     unsigned wo_m, wo_s, ho_m, ho_s;   // floor(v / wo) = umulhi(v, wo_m) >> wo_s for v < 2^31 (m == 0: the divisor is 1)
-    int fast_off;           // launcher: 1 = the FO instantiation (set_offsets in its full-rate form: input < 0x70000000 bytes); 0 = the general form (rounds 2-4; lab A/B: exp0 = 51)
+    int fast_off;           // launcher: 1 = the FO instantiation (set_offsets in its full-rate form: mbn_block_fast_offsets); 0 = the general form (rounds 2-4; lab A/B: exp0 = 51)
     float inv_wo, inv_ho;   // 1 / wo, 1 / ho
 };
 
@@ -94,7 +95,7 @@ __device__ __forceinline__ void dma_filter(__amdgpu_buffer_rsrc_t rsrc, float *l
 // the step. The two waves fall one group apart by themselves (one's MFMA group runs while the other does its loads, LDS reads, scalar work and waits) and the
 // matrix pipe has work at every point of the step. Same fma order: bit-identical. The last step of a workgroup issues its DMA / loads on stale cursors
 // (valid addresses, results unused) instead of branching around them: the counted waits are the same in every step.
-// FO: set_offsets in its full-rate form (see there); the launcher takes the FO = false instantiation for inputs outside that form's range.
+// FO: set_offsets in its full-rate form (mbn_block_window.h); the launcher takes the FO = false instantiation for inputs outside that form's range.
 template <int S, int BN, bool PRE, bool DBG, int NW = 8, bool XA2 = false, bool IL = false, bool FO = false>
 __global__ __launch_bounds__(64 * NW) void dwpw2_f32(DwPw2Args a)
 {
@@ -124,13 +125,7 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_f32(DwPw2Args a)
     const int nk = a.cin / 32, nwg = a.mt * a.nt;
     const unsigned mtot = (unsigned)a.m;
 
-    for (int i = tid * 4; i < 9 * a.cin; i += NT * 4) *reinterpret_cast<f4 *>(wd_s + i) = *reinterpret_cast<const f4 *>(a.wd + i);
-    for (int i = tid * 4; i < a.cin; i += NT * 4) {
-        *reinterpret_cast<f4 *>(sb_s + i) = *reinterpret_cast<const f4 *>(a.s2 + i);
-        *reinterpret_cast<f4 *>(sb_s + a.cin + i) = *reinterpret_cast<const f4 *>(a.b2 + i);
-    }
-    for (int i = tid; i < a.cout; i += NT) { sc3_s[i] = a.s3[i]; sh3_s[i] = a.b3[i]; }
-    __syncthreads();
+    mbn_block_constants_to_lds<NT, CMAXK, NOUTK>(a, tid, wd_s);
     if ((int)blockIdx.x >= nwg) return;
     // De-phasing. All workgroups run the same steps on the same amount of work, so they reach their epilogues together: a
     // chip-wide store burst during which — vmcnt retires in order — no wave sees a younger load complete (round 3: loads and stores of
@@ -170,63 +165,10 @@ __global__ __launch_bounds__(64 * NW) void dwpw2_f32(DwPw2Args a)
     const float *sk = sb_s + c4 * 4;
 
     unsigned off[3][XC];
-    auto set_offsets_general = [&](unsigned m0) __attribute__((always_inline)) {
-        const unsigned m = m0 + 2 * pair;
-        const bool mok = m < mtot;
-        const unsigned q = a.wo_m ? __umulhi(m, a.wo_m) >> a.wo_s : m;
-        const unsigned x = m - q * (unsigned)a.wo;
-        const unsigned n = a.ho_m ? __umulhi(q, a.ho_m) >> a.ho_s : q;
-        const unsigned y = q - n * (unsigned)a.ho;
-        const int iy0 = (int)y * S - a.pad_top, ix0 = (int)x * S - a.pad_left;
-        const unsigned cs = (unsigned)a.cin * 4u, rs = (unsigned)a.w * cs;                    // column / row stride in bytes
-        const unsigned base = ((n * a.h + iy0) * a.w + ix0) * cs + (unsigned)(c4 * 4) * 4u;         // wraps for taps that are masked out below
-#pragma unroll
-        for (int dy = 0; dy < 3; dy++) {
-            const bool rok = mok && (unsigned)(iy0 + dy) < (unsigned)a.h;
-#pragma unroll
-            for (int j = 0; j < XC; j++) {
-                const bool ok = rok && (unsigned)(ix0 + j) < (unsigned)a.w;
-                off[dy][j] = ok ? base + dy * rs + j * cs : MBN_OOB;
-            }
-        }
-    };
-    // Round 5: the same offsets from full-rate instructions. The stamps of the general form (profiles/r05/d_*) read ~1100-1250 cycles per tile for it on a
-    // SIMD's two waves: two v_mul_hi_u32 and six v_mul_lo_u32 (quarter rate), a 64-bit mad, and 12-15 compare / select pairs under exec-mask branches.
-    // Here: (n, y, x) of the tile's first pixel on the scalar unit (magic division); the lane's own pixel from it by two float reciprocal divisions of
-    // small numbers (r < wo + 128, exact: (r + 0.5) / wo is >= 0.5 / wo away from an integer, the float error is < 2e-5); ONE 32-bit multiply for the
-    // byte offset; validity separable by row and column: off[dy][j] = rowv[dy] + colv[j] where an invalid row is 0x80000000 and an invalid column
-    // 0x70000000, so that any sum with an invalid term lies in [0x70000000, 0xF0005000) — beyond the descriptor's num_records (launch2 takes this form
-    // only for inputs < 0x70000000 bytes) and without wrapping. Same offsets for every valid tap, zeros for every other: bit-identical results.
-    auto set_offsets_fast = [&](unsigned m0) __attribute__((always_inline)) {
-        const unsigned q0 = a.wo_m ? __umulhi(m0, a.wo_m) >> a.wo_s : m0;                    // wave-uniform: scalar unit
-        const unsigned x0 = m0 - q0 * (unsigned)a.wo;
-        const unsigned n0 = a.ho_m ? __umulhi(q0, a.ho_m) >> a.ho_s : q0;
-        const unsigned y0 = q0 - n0 * (unsigned)a.ho;
-        const unsigned r = x0 + 2u * (unsigned)pair;
-        const unsigned q1 = (unsigned)__builtin_fmaf((float)r, a.inv_wo, 0.5f * a.inv_wo);
-        const unsigned x = r - q1 * (unsigned)a.wo;                                       // q1 < 2^8, wo < 2^16: mul24 range
-        const unsigned yy = y0 + q1;
-        const unsigned q2 = (unsigned)__builtin_fmaf((float)yy, a.inv_ho, 0.5f * a.inv_ho);
-        const unsigned y = yy - q2 * (unsigned)a.ho;
-        const unsigned n = n0 + q2;
-        const bool mok = m0 + 2u * (unsigned)pair < mtot;
-        const int iy0 = (int)y * S - a.pad_top, ix0 = (int)x * S - a.pad_left;
-        const unsigned cs = (unsigned)a.cin * 4u, rs = (unsigned)a.w * cs;
-        const int pix = __mul24((int)(n * (unsigned)a.h) + iy0, a.w) + ix0;               // (n h + iy0) < 2^23 (launch2 checks), w < 2^16
-        const unsigned base = (unsigned)pix * cs + (unsigned)(c4 * 4) * 4u;
-        unsigned rowv[3], colv[XC];
-#pragma unroll
-        for (int dy = 0; dy < 3; dy++) rowv[dy] = (mok && (unsigned)(iy0 + dy) < (unsigned)a.h) ? base + dy * rs : 0x80000000u;
-#pragma unroll
-        for (int j = 0; j < XC; j++) colv[j] = ((unsigned)(ix0 + j) < (unsigned)a.w) ? j * cs : 0x70000000u;
-#pragma unroll
-        for (int dy = 0; dy < 3; dy++)
-#pragma unroll
-            for (int j = 0; j < XC; j++) off[dy][j] = rowv[dy] + colv[j];
-    };
-    auto set_offsets = [&](unsigned m0) __attribute__((always_inline)) {
-        if constexpr (FO) set_offsets_fast(m0);
-        else set_offsets_general(m0);
+    const unsigned cs = (unsigned)a.cin * 4u, cb = (unsigned)(c4 * 4) * 4u;             // pixel stride, this lane's channels: bytes
+    auto set_offsets = [&](unsigned m0) __attribute__((always_inline)) {                 // mbn_block_window.h
+        if constexpr (FO) mbn_window_offsets_fast<S>(off, a, cs, cb, m0, 2u * (unsigned)pair, mtot, true);
+        else mbn_window_offsets<S>(off, a, cs, cb, m0 + 2 * pair, mtot, true);
     };
     f4 xr[XA2 ? 2 : 1][3][XC];
     auto ldx_set = [&](int kc, const int set) __attribute__((always_inline)) {
@@ -689,14 +631,7 @@ int mbn_launch_f32_dwpw2(mbn_context *ctx, hipStream_t stream, const mbn_block_s
     const int variant = g_mbn_tune.dwpw_variant;
     a.wp_bytes = (unsigned)(4.0 * s.cin * s.cout);
     a.dbg = variant >= 100 ? variant - 100 : 0;
-    a.inv_wo = 1.0f / (float)s.out_cols;
-    a.inv_ho = 1.0f / (float)s.out_rows;
-    // the full-rate offsets need every input byte offset below the invalid-column constant, and (n h + iy0) in mul24 range
-    //  ... PLUS a left-pad column: a left-pad tap of image 0 / row 0 has base = -pad_left * cs, and its sum with the invalid-column
-    // constant must stay beyond num_records without wrapping; out_rows bounded so the row quotient stays in exact float range
-    const double cs_b = 4.0 * s.cin;
-    a.fast_off = (4.0 * s.batch * s.in_rows * s.in_cols * s.cin + (s.pad_left + 1) * cs_b <= (double)0x70000000u && (double)s.batch * s.in_rows < 8388000.0 &&
-                  s.in_cols < 32768 && s.out_cols < 32768 && s.out_rows < 32768 && s.pad_left <= 1) ? 1 : 0;
+    a.fast_off = mbn_block_fast_offsets(&s, MBN_DT_F32) == MBN_OK ? 1 : 0;
 #ifdef MBN_LAB
     if (g_mbn_tune.exp0 == 51) a.fast_off = 0;                                     // lab A/B: the general offsets
 #endif

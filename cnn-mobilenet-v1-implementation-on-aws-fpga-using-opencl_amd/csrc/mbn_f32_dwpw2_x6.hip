@@ -19,6 +19,8 @@
 // 128-column tile (Cin <= 512) or fall back to the fp32-MFMA kernels.
 #include "mbn_internal.h"
 #include "mbn_epilogue.h"
+#include "mbn_block_window.h"
+#include "mbn_x6.h"
 
 namespace {
 
@@ -39,23 +41,6 @@ struct XbArgs {
     unsigned wo_m, wo_s, ho_m, ho_s;
 };
 
-// 4 consecutive channels of one pixel -> the three bf16 planes (exact: h + m + l == v)
-__device__ __forceinline__ void split4(const f4 &v, u2 &H, u2 &M, u2 &L)
-{
-    const f2 p[2] = { f2{ v.x, v.y }, f2{ v.z, v.w } };
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        const bf2 h = __builtin_convertvector(p[j], bf2);
-        const f2 r = p[j] - __builtin_convertvector(h, f2);
-        const bf2 m = __builtin_convertvector(r, bf2);
-        const f2 l = r - __builtin_convertvector(m, f2);
-        const bf2 lo = __builtin_convertvector(l, bf2);
-        H[j] = __builtin_bit_cast(unsigned, h);
-        M[j] = __builtin_bit_cast(unsigned, m);
-        L[j] = __builtin_bit_cast(unsigned, lo);
-    }
-}
-
 template <int NPC>
 __device__ __forceinline__ void dma_image(__amdgpu_buffer_rsrc_t rsrc, unsigned *lds_b, const unsigned *voff, unsigned soff, int wave_u)
 {
@@ -63,11 +48,6 @@ __device__ __forceinline__ void dma_image(__amdgpu_buffer_rsrc_t rsrc, unsigned 
     for (int p = 0; p < NPC; p++)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(lds_b + (p * NW + wave_u) * 256), 16, voff[p], soff, 0, 0);
 }
-
-// product list of mbn_f32_pw_x6.hip (plane of A, plane of B; 0 = h, 1 = m, 2 = l), smallest terms first
-template <int NP> struct Prod;
-template <> struct Prod<9> { static constexpr int pa[9] = { 2, 2, 1, 2, 0, 1, 1, 0, 0 }, pb[9] = { 2, 1, 2, 0, 2, 1, 0, 1, 0 }; };
-template <> struct Prod<6> { static constexpr int pa[6] = { 2, 0, 1, 1, 0, 0 }, pb[6] = { 0, 2, 1, 0, 1, 0 }; };
 
 // CM = largest Cin (depthwise constants in LDS), NO = largest Cout (pointwise scale/shift in LDS)
 template <int S, int BN, int NP, int CM, int NO, bool PRE>
@@ -93,13 +73,7 @@ __global__ __launch_bounds__(NT) void dwpw2_x6(XbArgs a)
     const int nk = a.cin / 32, nwg = a.mt * a.nt;
     const unsigned mtot = (unsigned)a.m;
 
-    for (int i = tid * 4; i < 9 * a.cin; i += NT * 4) *reinterpret_cast<f4 *>(wd_s + i) = *reinterpret_cast<const f4 *>(a.wd + i);
-    for (int i = tid * 4; i < a.cin; i += NT * 4) {
-        *reinterpret_cast<f4 *>(sb_s + i) = *reinterpret_cast<const f4 *>(a.s2 + i);
-        *reinterpret_cast<f4 *>(sb_s + a.cin + i) = *reinterpret_cast<const f4 *>(a.b2 + i);
-    }
-    for (int i = tid; i < a.cout; i += NT) { sc3_s[i] = a.s3[i]; sh3_s[i] = a.b3[i]; }
-    __syncthreads();
+    mbn_block_constants_to_lds<NT, CM, NO>(a, tid, wd_s);
     if ((int)blockIdx.x >= nwg) return;
 
     const int c4 = tid & 7, pair = tid >> 3;                        // depthwise: tile rows 2*pair, 2*pair+1, channels 4*c4..+3 of the chunk
@@ -123,26 +97,8 @@ __global__ __launch_bounds__(NT) void dwpw2_x6(XbArgs a)
     const float *sk = sb_s + c4 * 4;
 
     unsigned off[3][XC];
-    auto set_offsets = [&](unsigned m0) __attribute__((always_inline)) {
-        const unsigned m = m0 + 2 * pair;
-        const bool mok = m < mtot;
-        const unsigned q = a.wo_m ? __umulhi(m, a.wo_m) >> a.wo_s : m;
-        const unsigned x = m - q * (unsigned)a.wo;
-        const unsigned n = a.ho_m ? __umulhi(q, a.ho_m) >> a.ho_s : q;
-        const unsigned y = q - n * (unsigned)a.ho;
-        const int iy0 = (int)y * S - a.pad_top, ix0 = (int)x * S - a.pad_left;
-        const unsigned cs = (unsigned)a.cin * 4u, rs = (unsigned)a.w * cs;
-        const unsigned base = ((n * a.h + iy0) * a.w + ix0) * cs + (unsigned)(c4 * 4) * 4u;
-#pragma unroll
-        for (int dy = 0; dy < 3; dy++) {
-            const bool rok = mok && (unsigned)(iy0 + dy) < (unsigned)a.h;
-#pragma unroll
-            for (int j = 0; j < XC; j++) {
-                const bool ok = rok && (unsigned)(ix0 + j) < (unsigned)a.w;
-                off[dy][j] = ok ? base + dy * rs + j * cs : MBN_OOB;
-            }
-        }
-    };
+    const unsigned cs = (unsigned)a.cin * 4u, cb = (unsigned)(c4 * 4) * 4u;             // pixel stride, this lane's channels: bytes
+    auto set_offsets = [&](unsigned m0) __attribute__((always_inline)) { mbn_window_offsets<S>(off, a, cs, cb, m0 + 2 * pair, mtot, true); };
     f4 xr[3][XC];
     auto ldx = [&](int kc) __attribute__((always_inline)) {
 #pragma unroll
@@ -176,11 +132,11 @@ __global__ __launch_bounds__(NT) void dwpw2_x6(XbArgs a)
             }
         u2 H, M, L;
         unsigned *const ab = a_s0 + buf * ABUF;
-        split4(mbn_bn_relu6(acc0, wreg[9], wreg[10]), H, M, L);
+        mbn_x6_split4(mbn_bn_relu6(acc0, wreg[9], wreg[10]), H, M, L);
         *reinterpret_cast<u2 *>(ab + aw0) = H;
         *reinterpret_cast<u2 *>(ab + PLANE_A + aw0) = M;
         *reinterpret_cast<u2 *>(ab + 2 * PLANE_A + aw0) = L;
-        split4(mbn_bn_relu6(acc1, wreg[9], wreg[10]), H, M, L);
+        mbn_x6_split4(mbn_bn_relu6(acc1, wreg[9], wreg[10]), H, M, L);
         *reinterpret_cast<u2 *>(ab + aw1) = H;
         *reinterpret_cast<u2 *>(ab + PLANE_A + aw1) = M;
         *reinterpret_cast<u2 *>(ab + 2 * PLANE_A + aw1) = L;

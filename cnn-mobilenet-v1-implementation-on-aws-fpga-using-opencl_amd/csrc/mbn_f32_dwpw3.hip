@@ -38,12 +38,13 @@
 // stores (mbn_device.h) was found here (profiles/r06/a_*).
 #include "mbn_internal.h"
 #include "mbn_epilogue.h"
+#include "mbn_block_window.h"
 
 namespace {
 
 constexpr int BN3 = 128;                       // output channels per workgroup slice
 constexpr int WT = 32;                         // output pixels per wave tile (16 pixel pairs)
-constexpr unsigned PO_INVALID = 0x80000000u;   // output offset of a pixel pair past the end: beyond any descriptor, the store is dropped
+constexpr unsigned PO_INVALID = MBN_OFF_BAD_ROW;   // output offset of a pixel pair past the end: beyond any descriptor, the store is dropped
 
 struct DwPw3Args {
     float *out;
@@ -181,9 +182,7 @@ __global__ __launch_bounds__(512) void dwpw3_f32(DwPw3Args a)
     unsigned rowv_k[SEP ? AH : 1][3], colv_k[SEP ? AH : 1][XC];
     // Window offsets of half-round hh of the tile whose first pair is p0 (wave-uniform), and the pair's output offset into po_w[slot].
     // Tile-uniform part on the scalar unit (magic division); the lane's pair by float-reciprocal divisions of small numbers (exact: the
-    // quotients' numerators stay below 2^21, see the launcher's range checks); validity separable by row and column: an invalid row is
-    // 0x80000000, an invalid column 0x70000000, so any sum with an invalid term lies beyond the descriptor's num_records without wrapping and
-    // the buffer unit returns zeros (= the zero padding).
+    // quotients' numerators stay below 2^21, see the launcher's range checks); then the separable row / column terms of mbn_block_window.h.
     auto set_offsets = [&](unsigned p0, const int hh, int pslot) __attribute__((always_inline)) {
         const unsigned bg0 = a.pb_m ? __umulhi(p0, a.pb_m) >> a.pb_s : p0;          // band (over the whole batch) of the tile's first pair
         const unsigned i0 = p0 - bg0 * a.pb;
@@ -199,15 +198,8 @@ __global__ __launch_bounds__(512) void dwpw3_f32(DwPw3Args a)
         const unsigned n = im0 + dn;
         const unsigned y = (band << a.rsh) + (i & ((1u << a.rsh) - 1u)), x = (i >> a.rsh) << 1;
         const bool mok = p0 + qq < ptot;
-        const int iy0 = (int)y * S - a.pad_top, ix0 = (int)x * S - a.pad_left;
-        const unsigned cs = (unsigned)CIN * 4u, rs = (unsigned)a.w * cs;
-        const int pix = __mul24((int)(n * (unsigned)a.h) + iy0, a.w) + ix0;
-        const unsigned base = (unsigned)pix * cs + (unsigned)(cl * 16);
         unsigned rowv[3], colv[XC];
-#pragma unroll
-        for (int dy = 0; dy < 3; dy++) rowv[dy] = (mok && (unsigned)(iy0 + dy) < (unsigned)a.h) ? base + dy * rs : 0x80000000u;
-#pragma unroll
-        for (int jj = 0; jj < XC; jj++) colv[jj] = ((unsigned)(ix0 + jj) < (unsigned)a.w) ? jj * cs : 0x70000000u;
+        mbn_window_rowcol<S>(rowv, colv, a, (unsigned)CIN * 4u, (unsigned)(cl * 16), n, y, x, mok);
         if constexpr (SEP) {
 #pragma unroll
             for (int dy = 0; dy < 3; dy++) rowv_k[hh][dy] = rowv[dy];
@@ -509,8 +501,8 @@ void launch3(const DwPw3Args &a, hipStream_t s, int grid)
 }   // namespace
 
 // 1 when the wave-private form takes this block (inside mbn_block_envelope): Cin 64 / 128 / 256 (filter slice resident in LDS,
-// substeps unrolled), the full-rate window offsets' range (every input byte offset + a left-pad column below the invalid-column constant; n h + iy0
-// in mul24 range; the band / image quotients' numerators below 2^21: exact float-reciprocal division), at least one workgroup per XCD and slice.
+// substeps unrolled), the full-rate window offsets' range (mbn_block_fast_offsets) and this form's own, narrower one (the band / image
+// quotients' numerators below 2^21: exact float-reciprocal division), at least one workgroup per XCD and slice.
 int mbn_f32_dwpw3_eligible(const mbn_context *ctx, const mbn_block_shape &s)
 {
     if (s.cin != 64 && s.cin != 128 && s.cin != 256) return 0;
@@ -518,8 +510,7 @@ int mbn_f32_dwpw3_eligible(const mbn_context *ctx, const mbn_block_shape &s)
     if (!MBN_DWPW3_DEFAULT(s.stride, s.cin)) return 0;      // the shipped library holds only the instantiations its dispatch rule reaches (stride 1, Cin 128 / 256)
 #endif
     if ((s.cout % BN3) != 0) return 0;
-    if (4.0 * s.batch * s.in_rows * s.in_cols * s.cin + 4.0 * (s.pad_left + 1) * s.cin > (double)0x70000000u) return 0;
-    if ((double)s.batch * s.in_rows >= 8388000.0 || s.in_cols >= 32768 || s.out_cols >= 16384 || s.out_rows >= 32768 || s.pad_left > 1 || s.pad_top > 1) return 0;
+    if (mbn_block_fast_offsets(&s, MBN_DT_F32) != MBN_OK || s.out_cols >= 16384 || s.pad_top > 1) return 0;
     if ((double)s.batch * s.out_rows >= 2000000.0 || (double)s.batch * s.out_rows * s.out_cols >= 2147483000.0) return 0;
     // a pixel pair past the end of a ragged last tile stores at PO_INVALID + its channel offset: dropped only while the whole output (+ one
     // wave tile) stays below PO_INVALID; beyond it those stores would land inside the output (outputs of 2 .. 4 GiB run on dwpw2 / dwpw)

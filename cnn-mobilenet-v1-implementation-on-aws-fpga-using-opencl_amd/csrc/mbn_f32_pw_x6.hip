@@ -39,6 +39,7 @@
 // matrix cores flush the bf16 denormals of the low planes below 2^-110): (19).
 #include "mbn_internal.h"
 #include "mbn_epilogue.h"
+#include "mbn_x6.h"
 
 namespace {
 
@@ -56,32 +57,6 @@ struct XArgs {
 
 constexpr int KT = 32;            // k per k-tile
 constexpr int PW = 16;            // 4-byte words per plane row (32 bf16)
-
-// 8 consecutive k of one row -> the three bf16 planes (exact: h + m + l == x)
-__device__ __forceinline__ void split8(const f4 &x0, const f4 &x1, u4 &H, u4 &M, u4 &L)
-{
-    const f2 v[4] = { f2{ x0.x, x0.y }, f2{ x0.z, x0.w }, f2{ x1.x, x1.y }, f2{ x1.z, x1.w } };
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const bf2 h = __builtin_convertvector(v[j], bf2);
-        const f2 r = v[j] - __builtin_convertvector(h, f2);
-        const bf2 m = __builtin_convertvector(r, bf2);
-        const f2 l = r - __builtin_convertvector(m, f2);
-        const bf2 lo = __builtin_convertvector(l, bf2);
-        H[j] = __builtin_bit_cast(unsigned, h);
-        M[j] = __builtin_bit_cast(unsigned, m);
-        L[j] = __builtin_bit_cast(unsigned, lo);
-    }
-}
-
-// product list: plane of A, plane of B (0 = h, 1 = m, 2 = l); smallest terms first
-template <int NP> struct Prod;
-template <> struct Prod<9> { static constexpr int pa[9] = { 2, 2, 1, 2, 0, 1, 1, 0, 0 }, pb[9] = { 2, 1, 2, 0, 2, 1, 0, 1, 0 }; };
-template <> struct Prod<6> { static constexpr int pa[6] = { 2, 0, 1, 1, 0, 0 }, pb[6] = { 0, 2, 1, 0, 1, 0 }; };
-#ifdef MBN_LAB
-template <> struct Prod<3> { static constexpr int pa[3] = { 1, 0, 0 }, pb[3] = { 0, 1, 0 }; };      // measurement only: 2^-16
-template <> struct Prod<1> { static constexpr int pa[1] = { 0 }, pb[1] = { 0 }; };                  // measurement only: bf16 operands
-#endif
 
 template <int BM, int BN, int WM, int WN, int NP, int NBUF, int OCC>
 __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void pw_gemm_x(XArgs a)
@@ -148,7 +123,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) __attribute__((amdgpu_w
 #pragma unroll
         for (int p = 0; p < A_LD; p++) {
             u4 H, M, L;
-            split8(a_reg[p][0], a_reg[p][1], H, M, L);
+            mbn_x6_split8(a_reg[p][0], a_reg[p][1], H, M, L);
             *reinterpret_cast<u4 *>(base + st_off[p]) = H;
             if (NPL > 1) *reinterpret_cast<u4 *>(base + PLANE_A + st_off[p]) = M;
             if (NPL > 2) *reinterpret_cast<u4 *>(base + 2 * PLANE_A + st_off[p]) = L;
@@ -156,7 +131,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) __attribute__((amdgpu_w
 #pragma unroll
         for (int p = 0; p < B_LD; p++) {
             u4 H, M, L;
-            split8(b_reg[p][0], b_reg[p][1], H, M, L);
+            mbn_x6_split8(b_reg[p][0], b_reg[p][1], H, M, L);
             *reinterpret_cast<u4 *>(base + 3 * PLANE_A + st_off[p]) = H;
             if (NPL > 1) *reinterpret_cast<u4 *>(base + 3 * PLANE_A + PLANE_B + st_off[p]) = M;
             if (NPL > 2) *reinterpret_cast<u4 *>(base + 3 * PLANE_A + 2 * PLANE_B + st_off[p]) = L;
@@ -276,7 +251,7 @@ __global__ __launch_bounds__(4 * BN) void split_filter(unsigned *ws, const float
     const int gn = min(ntile * BN + (paired ? mbn_pair_channel(row) : row), n - 1);
     const float *src = filt + (long)gn * k + kt * KT + c * 8;
     u4 H, M, L;
-    split8(*reinterpret_cast<const f4 *>(src), *reinterpret_cast<const f4 *>(src + 4), H, M, L);
+    mbn_x6_split8(*reinterpret_cast<const f4 *>(src), *reinterpret_cast<const f4 *>(src + 4), H, M, L);
     unsigned *dst = ws + (size_t)(ntile * nk + kt) * 3 * BN * PW + mbn_pswz(row, c);
     *reinterpret_cast<u4 *>(dst) = H;
     *reinterpret_cast<u4 *>(dst + BN * PW) = M;
@@ -354,7 +329,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) __attribute__((amdgpu_w
 #pragma unroll
         for (int p = 0; p < A_LD; p++) {
             u4 H, M, L;
-            split8(r[p][0], r[p][1], H, M, L);
+            mbn_x6_split8(r[p][0], r[p][1], H, M, L);
             *reinterpret_cast<u4 *>(lds + st_off[p]) = H;
             *reinterpret_cast<u4 *>(lds + PLANE_A + st_off[p]) = M;
             *reinterpret_cast<u4 *>(lds + 2 * PLANE_A + st_off[p]) = L;

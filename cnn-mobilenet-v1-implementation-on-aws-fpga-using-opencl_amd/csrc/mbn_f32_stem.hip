@@ -23,6 +23,7 @@
 // depthwise) to keep all 256 lanes busy; A/B tile rows are 64 instead of 128 bytes (four 16-byte slots, their own swizzle).
 #include "mbn_internal.h"
 #include "mbn_epilogue.h"
+#include "mbn_x6.h"
 
 namespace {
 
@@ -117,31 +118,6 @@ __device__ __forceinline__ void patch_store(float *in_s, int tid, const f2 (&pf)
 // separate launches would store them — the pointwise filter is the bf16 copy, and the result is stored as bf16.
 __device__ __forceinline__ float rbf(float v) { return (float)(__bf16)v; }
 __device__ __forceinline__ f4 rbf4(f4 v) { return f4{ rbf(v.x), rbf(v.y), rbf(v.z), rbf(v.w) }; }
-// exact three-way bf16 split of fp32 values (mbn_f32_pw_x6.hip: h = bf16(x), m = bf16(x - h), l = x - h - m), packed two per word
-__device__ __forceinline__ void x6_split2(float x0, float x1, unsigned &h, unsigned &m, unsigned &l)
-{
-    const f2 v = f2{ x0, x1 };
-    const bf2 hh = __builtin_convertvector(v, bf2);
-    const f2 r = v - __builtin_convertvector(hh, f2);
-    const bf2 mm = __builtin_convertvector(r, bf2);
-    const f2 lo = r - __builtin_convertvector(mm, f2);
-    h = __builtin_bit_cast(unsigned, hh);
-    m = __builtin_bit_cast(unsigned, mm);
-    l = __builtin_bit_cast(unsigned, __builtin_convertvector(lo, bf2));
-}
-__device__ __forceinline__ void x6_split4(f4 v, unsigned (&h)[2], unsigned (&m)[2], unsigned (&l)[2])
-{
-    x6_split2(v.x, v.y, h[0], m[0], l[0]);
-    x6_split2(v.z, v.w, h[1], m[1], l[1]);
-}
-__device__ __forceinline__ void x6_split8(f4 v0, f4 v1, unsigned (&h)[4], unsigned (&m)[4], unsigned (&l)[4])
-{
-    x6_split2(v0.x, v0.y, h[0], m[0], l[0]);
-    x6_split2(v0.z, v0.w, h[1], m[1], l[1]);
-    x6_split2(v1.x, v1.y, h[2], m[2], l[2]);
-    x6_split2(v1.z, v1.w, h[3], m[3], l[3]);
-}
-
 // WPE = workgroups per CU (= waves per SIMD). The alpha = 1 forms need 59.6 KB (fp32) / 48.7 KB (bf16: A/B tiles in bf16) of LDS
 // and 246 / 232 VGPRs: two. With the nine depthwise tap vectors re-read from LDS per tile instead of living in 36 VGPRs for the
 // whole kernel (WDL, WPE >= 3) the bf16 form fits three (150 VGPRs) and the alpha = 0.5 forms four (118 / 126 VGPRs, 28.6 /
@@ -203,11 +179,11 @@ __global__ __launch_bounds__(256, WPE) void stem_fused_f32(StemArgs a)
         if (tid < C3 * SL) {                                              // 8 consecutive k of one filter row -> the three planes
             const int row = tid / SL, slot = tid % SL;
             const float *src = a.wp + row * C1 + slot * 8;
-            unsigned hw[4], mw[4], lw[4];
-            x6_split8(*reinterpret_cast<const f4 *>(src), *reinterpret_cast<const f4 *>(src + 4), hw, mw, lw);
-            *reinterpret_cast<u4 *>(b_s + swzb<C1>(row, slot)) = u4{ hw[0], hw[1], hw[2], hw[3] };
-            *reinterpret_cast<u4 *>(b_s + BPL + swzb<C1>(row, slot)) = u4{ mw[0], mw[1], mw[2], mw[3] };
-            *reinterpret_cast<u4 *>(b_s + 2 * BPL + swzb<C1>(row, slot)) = u4{ lw[0], lw[1], lw[2], lw[3] };
+            u4 hw, mw, lw;
+            mbn_x6_split8(*reinterpret_cast<const f4 *>(src), *reinterpret_cast<const f4 *>(src + 4), hw, mw, lw);
+            *reinterpret_cast<u4 *>(b_s + swzb<C1>(row, slot)) = hw;
+            *reinterpret_cast<u4 *>(b_s + BPL + swzb<C1>(row, slot)) = mw;
+            *reinterpret_cast<u4 *>(b_s + 2 * BPL + swzb<C1>(row, slot)) = lw;
         }
     } else if constexpr (!BREG)
     for (int i = tid; i < C3 * Q1; i += 256) {                            // pointwise filter [C3][C1] -> swizzled B tile
@@ -463,11 +439,11 @@ __global__ __launch_bounds__(256, WPE) void stem_fused_f32(StemArgs a)
                     *reinterpret_cast<bf4 *>(a_s + swzb<C1>(row, c4 >> 1) + 2 * (c4 & 1)) = bf4{ (__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w };
                 } else if constexpr (X6 != 0) {                           // exact split of the fp32 value: 8 bytes per lane and plane
                     const int o = swzb<C1>(cy * TW + cx + p, c4 >> 1) + 2 * (c4 & 1);
-                    unsigned hw[2], mw[2], lw[2];
-                    x6_split4(v, hw, mw, lw);
-                    *reinterpret_cast<u2 *>(a_s + o) = u2{ hw[0], hw[1] };
-                    *reinterpret_cast<u2 *>(a_s + APL + o) = u2{ mw[0], mw[1] };
-                    *reinterpret_cast<u2 *>(a_s + 2 * APL + o) = u2{ lw[0], lw[1] };
+                    u2 hw, mw, lw;
+                    mbn_x6_split4(v, hw, mw, lw);
+                    *reinterpret_cast<u2 *>(a_s + o) = hw;
+                    *reinterpret_cast<u2 *>(a_s + APL + o) = mw;
+                    *reinterpret_cast<u2 *>(a_s + 2 * APL + o) = lw;
                 } else *reinterpret_cast<f4 *>(a_s + swz<C1>(cy * TW + cx + p, c4)) = v;
             }
         }

@@ -176,6 +176,15 @@ int mbn_launch_bf16_dwpw(mbn_context *ctx, hipStream_t stream, const mbn_block_s
 int mbn_launch_bf16_dwpw2(mbn_context *ctx, hipStream_t stream, const mbn_block_shape &s, void *out, const void *in, const mbn_block_params &p);
 // The kernel-argument fields every block form shares (the structs differ, the names agree): the shape, the activations, the depthwise
 // parameters and the pointwise scale / shift. esize = bytes per activation element. The pointwise filter is the caller's (wp, or dwpw2_x6's image).
+// (the reciprocals of the full-rate window offsets, in the forms that carry them)
+template <typename Args>
+static inline auto mbn_block_args_inv(Args &a, const mbn_block_shape &s, int) -> decltype((void)a.inv_wo)
+{
+    a.inv_wo = 1.0f / (float)s.out_cols;
+    a.inv_ho = 1.0f / (float)s.out_rows;
+}
+template <typename Args>
+static inline void mbn_block_args_inv(Args &, const mbn_block_shape &, long) {}
 template <typename Args>
 static inline void mbn_block_args(Args &a, const mbn_block_shape &s, void *out, const void *in, const mbn_block_params &p, double esize)
 {
@@ -187,6 +196,7 @@ static inline void mbn_block_args(Args &a, const mbn_block_shape &s, void *out, 
     mbn_udiv_magic((unsigned)s.out_cols, &a.wo_m, &a.wo_s);
     mbn_udiv_magic((unsigned)s.out_rows, &a.ho_m, &a.ho_s);
     a.in_bytes = (unsigned)(esize * s.batch * s.in_rows * s.in_cols * s.cin);
+    mbn_block_args_inv(a, s, 0);
 }
 // short-K pointwise GEMM with the filter slice resident in LDS (mbn_f32_pw3.hip, round 6). Taken where it measured faster than pw_gemm (profiles/r06/l_*:
 // layers 5 / 7 / 9 / 11 at batch 256: -22 / -12 / -12 / -7 %, batch 64: -17 / -8 / -9 / -2 %, batch 16: equal; layer 13 (N = 512, four slices): +2 ... +40 %):

@@ -23,6 +23,21 @@ int mbn_block_envelope(const mbn_block_shape *s, int dtype)
     return MBN_OK;
 }
 
+/* The range in which csrc/mbn_block_window.h's full-rate offsets equal the general ones:
+ *  - every input byte offset PLUS a left-pad column below MBN_OFF_BAD_COL: a left-pad tap of image 0 / row 0 has base = -pad_left * (pixel
+ *    stride), and its sum with MBN_OFF_BAD_COL must stay beyond num_records without wrapping into the descriptor's range;
+ *  - (image * in_rows + row) in __mul24 range, in_cols in its 16-bit factor;
+ *  - the float-reciprocal row / image quotients exact: out_cols, out_rows < 2^15;
+ *  - at most one pad column on the left (the term above counts one). */
+int mbn_block_fast_offsets(const mbn_block_shape *s, int dtype)
+{
+    const double es = dtype == MBN_DT_BF16 ? 2.0 : 4.0;
+    if (es * s->batch * s->in_rows * s->in_cols * s->cin + (s->pad_left + 1) * es * s->cin > (double)MBN_OFF_BAD_COL) return MBN_EUNSUPPORTED;
+    if ((double)s->batch * s->in_rows >= 8388000.0 || s->in_cols >= 32768 || s->out_cols >= 32768 || s->out_rows >= 32768 || s->pad_left > 1)
+        return MBN_EUNSUPPORTED;
+    return MBN_OK;
+}
+
 int mbn_resident_envelope(const mbn_block_shape *s, int nblocks)
 {
     if (s->cin != 256 || s->cout != 256 || s->stride != 1 || s->pad_top != 1 || s->pad_left != 1 || s->in_rows < 1 || s->in_cols < 1 ||

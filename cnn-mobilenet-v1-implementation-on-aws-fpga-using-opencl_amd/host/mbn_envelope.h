@@ -14,6 +14,11 @@ extern "C" {
 #define MBN_CMAX 1024                /* largest Cin: the depthwise constants stay resident in LDS (44 KB) */
 #define MBN_COUT_MAX 1024            /* largest Cout: its scale / shift stay resident in LDS */
 #define MBN_OOB 0xF0000000u          /* byte offset beyond any supported tensor: a buffer load there returns zeros, so inputs stay below it */
+/* full-rate window offsets (csrc/mbn_block_window.h): a tap's offset is (row term) + (column term), and a tap outside the image carries one of
+ * these instead. Any sum with one of them lies in [MBN_OFF_BAD_COL, MBN_OOB + a little): beyond the descriptor's num_records and without
+ * wrapping, as long as every input byte offset plus one left-pad column stays below MBN_OFF_BAD_COL: mbn_block_fast_offsets */
+#define MBN_OFF_BAD_ROW 0x80000000u
+#define MBN_OFF_BAD_COL 0x70000000u
 /* bf16 resident run (mbn_bf16_res.hip): pixel rows of its two LDS images, the map with its border and the map, and blocks per launch */
 #define MBN_RES_XPIX 144
 #define MBN_RES_YROWS 104
@@ -29,6 +34,9 @@ typedef struct mbn_block_shape {
 
 /* mbn_dwpw_fused (dtype MBN_DT_F32) and mbn_dwpw_fused_bf16 (MBN_DT_BF16) */
 int mbn_block_envelope(const mbn_block_shape *s, int dtype);
+/* a block inside mbn_block_envelope whose window offsets may take the full-rate form (the unified-wave kernels' FO instantiations; one of the
+ * terms of mbn_f32_dwpw3_eligible); the others run on the general form */
+int mbn_block_fast_offsets(const mbn_block_shape *s, int dtype);
 /* one block of a run of `nblocks` (mbn_blocks_resident_bf16): stride 1, pad 1, the map and the channels unchanged */
 int mbn_resident_envelope(const mbn_block_shape *s, int nblocks);
 /* the two blocks of mbn_tail_resident_bf16: b0 stride 2 without top / left padding on an even map, b1 stride 1 with pad 1 on b0's output */

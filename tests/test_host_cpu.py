@@ -606,6 +606,45 @@ def test_fused_kernel_envelopes(pkg):
     assert host.mbn_stem_envelope(21913099, 224, 32, 64) == no           # 2 147 483 702 >= 2^31 - 1: no 32-bit tile index
 
 
+def test_block_fast_offsets_range(pkg):
+    """mbn_block_fast_offsets (host/mbn_envelope.c): the range in which the fused blocks' full-rate window offsets (csrc/mbn_block_window.h)
+    are legal, one term at a time. Every shape is inside mbn_block_envelope; every expectation is worked out by hand in its comment.
+    0x70000000 = 1 879 048 192."""
+    host = pkg.host_lib()
+    ok, no = pkg.OK, pkg.EUNSUPPORTED
+    f32, bf16 = pkg.DT_F32, pkg.DT_BF16
+
+    def fast(dtype, *shape):            # batch, in_rows, in_cols, out_rows, out_cols, cin, cout, stride, pad_top, pad_left
+        s = _BlockShape(*shape)
+        assert host.mbn_block_envelope(C.byref(s), dtype) == ok, shape
+        return host.mbn_block_fast_offsets(C.byref(s), dtype)
+
+    # the cases test_large_tensors_gpu.py runs: 108 x 108 x 64 = 746 496 elements per image
+    assert fast(f32, 629, 108, 108, 54, 54, 64, 128, 2, 0, 0) == ok          # 1 878 183 936 + 256
+    assert fast(f32, 630, 108, 108, 54, 54, 64, 128, 2, 0, 0) == no          # 1 881 169 920
+    assert fast(bf16, 1258, 108, 108, 54, 54, 64, 128, 2, 0, 0) == ok        # 1 878 183 936 + 128
+    assert fast(bf16, 1259, 108, 108, 54, 54, 64, 128, 2, 0, 0) == no        # 1 879 676 928
+    # the left-pad column on its own: 7 * 2^20 pixels of 64 fp32 channels are exactly 0x70000000 bytes, one pixel more than fits with the column
+    assert fast(f32, 7, 1024, 1024, 1024, 1024, 64, 128, 1, 1, 1) == no      # 1 879 048 192 + 512
+    assert fast(f32, 7, 1024, 1024, 1024, 1024, 64, 128, 1, 1, 0) == no      # 1 879 048 192 + 256
+    assert fast(f32, 7, 1024, 1023, 1024, 1022, 64, 128, 1, 1, 1) == ok      # one column fewer: 1 877 213 184 + 512
+    # ... and to the byte: 271 853 x 3 x 9 = 7 * 2^20 - 1 pixels, 1 879 047 936 bytes
+    assert fast(f32, 271853, 3, 9, 3, 8, 64, 128, 1, 1, 0) == ok             # + 256 = 0x70000000 exactly
+    assert fast(f32, 271853, 3, 9, 3, 8, 64, 128, 1, 1, 1) == no             # + 512
+    # every other term, flipped alone
+    assert fast(f32, 4, 16, 16, 16, 16, 64, 128, 1, 1, 1) == ok
+    assert fast(f32, 4, 16, 16, 16, 16, 64, 128, 1, 1, 2) == no              # two pad columns on the left
+    assert fast(f32, 4, 16, 16, 16, 16, 64, 128, 1, 2, 1) == ok              # (pad rows are not this rule's: dwpw3 has its own)
+    assert fast(f32, 1, 2, 32767, 1, 16384, 32, 128, 2, 0, 0) == ok
+    assert fast(f32, 1, 2, 32768, 1, 16384, 32, 128, 2, 0, 0) == no          # in_cols = 2^15
+    assert fast(f32, 1, 2, 32767, 2, 32766, 32, 128, 1, 1, 1) == ok
+    assert fast(f32, 1, 2, 32767, 2, 32768, 32, 128, 1, 1, 1) == no          # out_cols = 2^15
+    assert fast(f32, 1, 32767, 2, 32767, 2, 32, 128, 1, 1, 1) == ok
+    assert fast(f32, 1, 32768, 2, 32768, 2, 32, 128, 1, 1, 1) == no          # out_rows = 2^15
+    assert fast(bf16, 8387, 1000, 2, 1000, 2, 32, 64, 1, 1, 1) == ok         # batch * in_rows = 8 387 000 (1 073 536 000 bytes)
+    assert fast(bf16, 8388, 1000, 2, 1000, 2, 32, 64, 1, 1, 1) == no         # 8 388 000
+
+
 def test_pw_gemm_counted_waits_match_the_isa():
     """`s_waitcnt vmcnt(NSTF); s_barrier` at the top of a pw_gemm tile is right only if the previous tile's fast epilogue is
     EXACTLY NSTF buffer stores, all behind the next tile's first LDS-DMA, in the instruction stream the compiler produced. The source

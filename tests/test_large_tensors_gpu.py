@@ -7,11 +7,11 @@ A new descriptor-based kernel adds its row here.
 
 | limit                                            | guard (file:line)                                  | below (case)                      | above (case)                                    |
 |--------------------------------------------------|----------------------------------------------------|-----------------------------------|-------------------------------------------------|
-| dwpw3 output + 32 px <= 2 GiB (ragged pairs      | mbn_f32_dwpw3.hip:534 (mbn_f32_dwpw3_eligible)     | 719 x 54^2, 128->256 (dwpw3_f32)  | 721 x 54^2, 128->256; 343 x 54^2, 128->1024     |
+| dwpw3 output + 32 px <= 2 GiB (ragged pairs      | mbn_f32_dwpw3.hip:517 (mbn_f32_dwpw3_eligible)     | 719 x 54^2, 128->256 (dwpw3_f32)  | 721 x 54^2, 128->256; 343 x 54^2, 128->1024     |
 |   store at PO_INVALID = 0x80000000)              |                                                    |                                   |   (round-1 dwpw_f32)                            |
-| input <= 0x70000000 (fp32 dwpw2 fast_off)        | mbn_f32_dwpw2.hip:726                              | 629 x 108^2 x 64, s2              | 630 x 108^2 x 64, s2 (general offsets)          |
-| input <= 0x70000000 (bf16 dwpw2 fast_off)        | mbn_bf16_dwpw2.hip:515                             | 1258 x 108^2 x 64, s2             | 1259 (general offsets)                          |
-| input <= 0x70000000 (dwpw3 input)                | mbn_f32_dwpw3.hip:529                              | 1258 x 54^2, 128->128 (dwpw3)     | 1259: 128->128 (dwpw2), 128->256 (dwpw_f32)     |
+| input <= 0x70000000 (fp32 dwpw2 fast_off)        | host/mbn_envelope.c:35 (mbn_block_fast_offsets)    | 629 x 108^2 x 64, s2              | 630 x 108^2 x 64, s2 (general offsets)          |
+| input <= 0x70000000 (bf16 dwpw2 fast_off)        | host/mbn_envelope.c:35 (mbn_block_fast_offsets)    | 1258 x 108^2 x 64, s2             | 1259 (general offsets)                          |
+| input <= 0x70000000 (dwpw3 input)                | host/mbn_envelope.c:35, via mbn_f32_dwpw3.hip:513  | 1258 x 54^2, 128->128 (dwpw3)     | 1259: 128->128 (dwpw2), 128->256 (dwpw_f32)     |
 | input < 0xF0000000 (fused block envelope)        | host/mbn_envelope.c:19 (mbn_block_envelope)        | 1348 x 108^2 x 64, s2             | 1349: MBN_EUNSUPPORTED; net batch 1399 unfused  |
 | (output + 256 rows) < 4 GiB (fused envelope)     | host/mbn_envelope.c:22 (mbn_block_envelope)        | 359 x 54^2, 128->1024             | 360: MBN_EUNSUPPORTED                           |
 | output < 4 GiB (pw_gemm fast_epi)                | mbn_f32_pw.hip:597                                 | m = 2^24 - 37, 32->64             | m = 2^24 + 37 (general epilogue)                |
@@ -23,7 +23,7 @@ A new descriptor-based kernel adds its row here.
 | stride-2 input >= 512 MiB, >= 40 rows (2 rows    | mbn_f32_dw.hip:833                                 | 167 x 112^2 x 64                  | 168 x 112^2 x 64                                |
 |   per segment)                                   |                                                    |                                   |                                                 |
 | none (64-bit pointers): depthwise > 4 GiB        | mbn_f32_dw.hip (fp32, bf16x8)                      | the P-image twins                 | fp32 / bf16 at stride 1 and 2, 4.3 GB           |
-| input < 4 GiB (bf16 resident tail)               | host/mbn_envelope.c:44 (mbn_tail_envelope)         | 83 885 x 10^2 x 256               | 83 887: MBN_EUNSUPPORTED                        |
+| input < 4 GiB (bf16 resident tail)               | host/mbn_envelope.c:59 (mbn_tail_envelope)         | 83 885 x 10^2 x 256               | 83 887: MBN_EUNSUPPORTED                        |
 | stem / conv1 (64-bit pointers)                   | mbn_f32_stem.hip                                   | forward(7)                        | net batch 1399 (fp32 fused and unfused stem),   |
 |                                                  |                                                    |                                   |   bf16 batch 2700                               |
 

@@ -1563,6 +1563,105 @@ def test_f32_dwpw_fused_top_left_padding(pkg, orc, ctx):
     assert_close(d_f.download(want.shape, np.float32), want, TOL_PW, "dwpw top/left padding")
 
 
+# Asymmetric pads on tiles that span many images: 9 images of 6 x 10 pixels, (stride, pad_top, pad_left, out_rows, out_cols). The output sizes are
+# given explicitly: 48 / 40 / 16 / 18 pixels per image, so a 128-row tile covers 2.7 - 8 images (in the full-rate window offsets the second
+# reciprocal division, the image quotient q2, is then > 0 for most lanes) and the last tile is ragged (432, 360, 144, 162 pixels).
+DWPW_ASYM_N, DWPW_ASYM_H, DWPW_ASYM_W = 9, 6, 10
+DWPW_ASYM_GEOM = [(1, 1, 0, 6, 8), (1, 0, 1, 4, 10), (2, 1, 0, 4, 4), (2, 0, 1, 3, 6)]
+
+
+def _dwpw_asym_taps(geom):
+    """inside[oy][ox] = taps of output pixel (oy, ox) that lie inside the 6 x 10 image (of 9)."""
+    stride, pt, pl, oh, ow = geom
+    iy = np.arange(oh)[:, None] * stride - pt + np.arange(3)[None, :]                 # [oh][dy]
+    ix = np.arange(ow)[:, None] * stride - pl + np.arange(3)[None, :]                 # [ow][dx]
+    rin = ((iy >= 0) & (iy < DWPW_ASYM_H)).sum(1)
+    cin = ((ix >= 0) & (ix < DWPW_ASYM_W)).sum(1)
+    return rin[:, None] * cin[None, :]
+
+
+def _dwpw_asym_check(geom):
+    """What makes the case a test of the padding: no output pixel is all padding (the data decides every value), every pixel of the padded edge
+    has taps outside the image (zeros that are not there change it), the far edge overruns the image too, and the tiles are as the table
+    above says. (A pixel in the middle of the map has its nine taps inside: not every pixel can have one outside; those pixels are there too.)"""
+    stride, pt, pl, oh, ow = geom
+    inside = _dwpw_asym_taps(geom)
+    assert inside.min() >= 1, geom
+    outside = inside < 9
+    assert (outside[0, :].all() if pt else outside[:, 0].all()), geom                # the padded edge: every pixel of it
+    assert (outside[:, -1].all() if pl else outside[-1, :].all()), geom              # the far edge of the same axis: past the image
+    assert (~outside).any(), geom
+    m = DWPW_ASYM_N * oh * ow
+    assert ow % 2 == 0 and oh * ow <= 64 and m > 128 and m % 128 != 0, geom          # >= 2 images per tile, >= 2 tiles, ragged
+
+
+@pytest.mark.parametrize("chan", [(64, 128), (128, 128)])
+@pytest.mark.parametrize("geom", DWPW_ASYM_GEOM)
+def test_f32_dwpw_fused_asymmetric_pads_many_images(pkg, orc, ctx, geom, chan):
+    """mbn_dwpw_fused with pad_top != pad_left on tiles that span several images (see DWPW_ASYM_GEOM): vs the oracle at TOL_PW and bit-identical
+    with mbn_depthwise + mbn_pointwise (pw_gemm). 64 -> 128: the unified-wave kernel; 128 -> 128 at stride 1: the wave-private form."""
+    _dwpw_asym_check(geom)
+    stride, pt, pl, oh, ow = geom
+    cin, cout = chan
+    n, h, w = DWPW_ASYM_N, DWPW_ASYM_H, DWPW_ASYM_W
+    rng = np.random.default_rng(1000 * stride + 100 * pt + 10 * pl + cin)
+    x = rng.uniform(-1, 1, (n, h, w, cin)).astype(np.float32)
+    wd = rng.normal(0, 0.5, (3, 3, cin)).astype(np.float32)
+    wp = rng.normal(0, (2.0 / cin) ** 0.5, (cout, cin)).astype(np.float32)
+    s2, s3 = rng.uniform(0.5, 1.5, cin).astype(np.float32), rng.uniform(0.5, 1.5, cout).astype(np.float32)
+    b2, b3 = rng.normal(0, 0.1, cin).astype(np.float32), rng.normal(0, 0.1, cout).astype(np.float32)
+    mid = orc.f32_depthwise(x, wd, s2, b2, stride, 2, out_rows=oh, out_cols=ow, pad_top=pt, pad_left=pl)
+    want = orc.f32_pointwise(mid.reshape(-1, cin), wp, s3, b3, 2).reshape(n, oh, ow, cout)
+    d = [ctx.to_device(a) for a in (x, wd, s2, b2, wp, s3, b3)]
+    d_f, d_m, d_u = ctx.alloc(want.nbytes), ctx.alloc(mid.nbytes), ctx.alloc(want.nbytes)
+    rc = ctx.lib.mbn_dwpw_fused(ctx.h, d_f.ptr, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, d[4].ptr, d[5].ptr, d[6].ptr,
+                                n, h, w, oh, ow, cin, cout, stride, pt, pl, None)
+    assert rc == 0, rc
+    ctx.depthwise(d_m.ptr, d[0].ptr, d[1].ptr, oh, ow, 3, stride, cin,
+                  pkg.make_ext(batch=n, act=2, pad_top=pt, pad_left=pl, in_rows=h, in_cols=w, scale=d[2].ptr, shift=d[3].ptr))
+    try:
+        assert ctx.lib.mbn_tune_set(b"pw_splitk", 1) == 0
+        ctx.pointwise(d_u.ptr, d_m.ptr, d[4].ptr, n * oh * ow, 1, cin, cout, pkg.make_ext(batch=1, act=2, scale=d[5].ptr, shift=d[6].ptr))
+    finally:
+        ctx.lib.mbn_tune_set(b"pw_splitk", 0)
+    ctx.sync()
+    fused, unfused = d_f.download(want.shape, np.float32), d_u.download(want.shape, np.float32)
+    for b in d + [d_f, d_m, d_u]:
+        b.free()
+    assert_close(fused, want, TOL_PW, "dwpw %s %s vs oracle" % (geom, chan))
+    assert np.array_equal(fused, unfused), "fused block %s %s differs from depthwise+pointwise by %g" % (geom, chan, np.abs(fused - unfused).max())
+
+
+@pytest.mark.parametrize("chan", [(64, 128), (128, 128), (32, 64)])
+@pytest.mark.parametrize("geom", DWPW_ASYM_GEOM)
+def test_bf16_dwpw_fused_asymmetric_pads_many_images(pkg, orc, ctx, geom, chan):
+    """mbn_dwpw_fused_bf16 on the same geometry; 32 -> 64 is the form in which four lanes cover a pixel pair (256-row tiles) and, on the general
+    offsets, the one with lanes masked out. Against the oracle's bf16 emulation at the bf16 tests' tolerance."""
+    _dwpw_asym_check(geom)
+    stride, pt, pl, oh, ow = geom
+    cin, cout = chan
+    n, h, w = DWPW_ASYM_N, DWPW_ASYM_H, DWPW_ASYM_W
+    rng = np.random.default_rng(2000 * stride + 100 * pt + 10 * pl + cin)
+    x = orc.bf16_round(rng.uniform(0, 4, (n, h, w, cin)).astype(np.float32))
+    wd = rng.normal(0, 0.5, (3, 3, cin)).astype(np.float32)
+    wp = orc.bf16_round(rng.normal(0, (2.0 / cin) ** 0.5, (cout, cin)).astype(np.float32))
+    s2, s3 = rng.uniform(0.5, 1.5, cin).astype(np.float32), rng.uniform(0.5, 1.5, cout).astype(np.float32)
+    b2, b3 = rng.normal(0, 0.1, cin).astype(np.float32), rng.normal(0, 0.1, cout).astype(np.float32)
+    mid = orc.bf16_round(orc.f32_depthwise(x, wd, s2, b2, stride, 2, out_rows=oh, out_cols=ow, pad_top=pt, pad_left=pl))
+    want = orc.bf16_round(orc.f32_pointwise(mid.reshape(-1, cin), wp, s3, b3, 2).reshape(n, oh, ow, cout))
+    d_x, d_wp = _bf16_dev(pkg, ctx, x), _bf16_dev(pkg, ctx, wp)
+    d = [ctx.to_device(a) for a in (wd, s2, b2, s3, b3)]
+    d_f = ctx.alloc(want.size * 2)
+    rc = ctx.lib.mbn_dwpw_fused_bf16(ctx.h, d_f.ptr, d_x.ptr, d[0].ptr, d[1].ptr, d[2].ptr, d_wp.ptr, d[3].ptr, d[4].ptr,
+                                     n, h, w, oh, ow, cin, cout, stride, pt, pl, None)
+    assert rc == 0, rc
+    ctx.sync()
+    fused = _bf16_get(pkg, d_f, want.shape)
+    for b in d + [d_x, d_wp, d_f]:
+        b.free()
+    assert_close(fused, want, TOL_BF16, "bf16 fused block %s %s vs oracle" % (geom, chan))
+
+
 @pytest.mark.parametrize("alpha", [1.0, 0.5])
 def test_bf16_fused_stem_vs_oracle_and_separate_layers(pkg, orc, ctx, tmp_path, alpha):
     """bf16 mode of the fused stem (MBN_STEM_BF16): layer-3 activation vs the oracle's bf16 emulation of layers 1-3 (every
