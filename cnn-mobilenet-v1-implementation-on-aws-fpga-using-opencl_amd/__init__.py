@@ -127,6 +127,7 @@ def _declare_host(lib):
     lib.mbn_rank_barrier.argtypes = [C.c_void_p]
     lib.mbn_rank_fail.argtypes = [C.c_void_p]
     lib.mbn_quantize_i8.argtypes = [C.POINTER(Plan), C.c_void_p, C.c_void_p, C.POINTER(I8Params), C.c_void_p]
+    lib.mbn_upsample_argmax_envelope.argtypes = [C.c_int] * 5      # mbn_envelope.h: exported, not in mbn.h
     return lib
 
 
@@ -228,6 +229,9 @@ def load():
         lib.mbn_tail_resident_bf16.argtypes = [vp, vp, vp, C.POINTER(BlockParams), ci, ci, ci, ci, ci, vp]
         lib.mbn_softmax_topk_f32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, vp]
         lib.mbn_classifier_tail.argtypes = [vp] * 9 + [ci] * 6 + [vp]
+        lib.mbn_upsample_argmax_f32.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
+        lib.mbn_net_forward_dense.argtypes = [vp, vp, vp, ci]
+        lib.mbn_net_segment.argtypes = [vp, vp, ci, vp, vp]
         lib.mbn_graph_begin.argtypes = [vp, vp]
         lib.mbn_graph_end.argtypes = [vp, vp, C.POINTER(vp)]
         lib.mbn_graph_launch.argtypes = [vp, vp, vp]
@@ -438,6 +442,11 @@ class Context:
         _chk(self.lib.mbn_pool(self.h, out, inp, rows, cols, filtersize, op_size,
                                None if ext is None else C.byref(ext)), self.last_error())
 
+    def upsample_argmax(self, labels, score, logits, batch, rows, cols, classes, factor):
+        """mbn_upsample_argmax_f32: fp32 logits [batch][rows][cols][classes] -> int32 labels (and, unless `score` is None, the winning fp32
+        logit) [batch][rows*factor][cols*factor]: bilinear upsample + argmax in one kernel."""
+        _chk(self.lib.mbn_upsample_argmax_f32(self.h, labels, score, logits, batch, rows, cols, classes, factor, None), self.last_error())
+
     def __enter__(self):
         return self
 
@@ -542,6 +551,14 @@ class Net:
 
     def classify(self, images_dev, batch, k, topk_idx_dev, topk_prob_dev):
         _chk(self.ctx.lib.mbn_net_classify(self.h, images_dev, batch, k, topk_idx_dev, topk_prob_dev), self.ctx.last_error())
+
+    def forward_dense(self, images_ptr, out_ptr, batch):
+        """The FC at every pixel of the map in front of the pool: out [batch][h][w][classes] fp32 (mbn_net_forward_dense)."""
+        _chk(self.ctx.lib.mbn_net_forward_dense(self.h, images_ptr, out_ptr, batch), self.ctx.last_error())
+
+    def segment(self, images_ptr, batch, labels_ptr, score_ptr=None):
+        """forward_dense + bilinear upsample to the input size + argmax: int32 labels (and fp32 scores) [batch][rows][cols] (mbn_net_segment)."""
+        _chk(self.ctx.lib.mbn_net_segment(self.h, images_ptr, batch, labels_ptr, score_ptr), self.ctx.last_error())
 
     def set_input_u8(self, enabled=True):
         _chk(self.ctx.lib.mbn_net_set_input_u8(self.h, int(enabled)))

@@ -806,6 +806,21 @@ int mbn_softmax_topk_f32(mbn_context *ctx, void *probs, void *topk_idx_i32, void
                                                  (const float *)logits, batch, classes, k));
 }
 
+int mbn_upsample_argmax_f32(mbn_context *ctx, void *labels_i32, void *score_f32, const void *logits, int batch, int rows, int cols, int classes,
+                            int factor, void *stream)
+{
+    if (!ctx || !labels_i32 || !logits || batch <= 0 || rows <= 0 || cols <= 0 || classes <= 0) return MBN_EINVAL;
+    if (((uintptr_t)labels_i32 | (uintptr_t)score_f32 | (uintptr_t)logits) % 4) return MBN_EINVAL;
+    if (mbn_upsample_argmax_envelope(batch, rows, cols, classes, factor) != MBN_OK) return MBN_EUNSUPPORTED;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    const double out = 4.0 * batch * rows * factor * cols * factor;
+    MBN_SPANS(ctx, { logits, 4.0 * batch * rows * cols * classes, "upsample_argmax logits" }, { labels_i32, out, "upsample_argmax labels" },
+              { score_f32, out, "upsample_argmax score" });
+    Scope sc(ctx, s);
+    return sc.finish(mbn_launch_f32_upsample_argmax(ctx, s, (int32_t *)labels_i32, (float *)score_f32, (const float *)logits, batch, rows, cols,
+                                                    classes, factor));
+}
+
 int mbn_classifier_tail(mbn_context *ctx, void *topk_idx_i32, void *topk_prob_f32, void *probs, void *logits_scratch,
                         void *pooled_scratch, const void *in, const void *fc_w, const void *fc_bias, int batch, int rows,
                         int cols, int channels, int classes, int k, void *stream)

@@ -222,6 +222,9 @@ int mbn_launch_f32_softmax(mbn_context *ctx, hipStream_t s, float *probs, int32_
                            int batch, int classes);
 int mbn_launch_f32_softmax_topk(mbn_context *ctx, hipStream_t s, float *probs, int32_t *topk_idx, float *topk_prob,
                                 const float *logits, int batch, int classes, int k);
+// dense head read-out (mbn_f32_dense.hip): bilinear upsample by `factor` + argmax over the classes; the shape is inside mbn_upsample_argmax_envelope
+int mbn_launch_f32_upsample_argmax(mbn_context *ctx, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows,
+                                   int cols, int classes, int factor);
 int mbn_launch_normalize(mbn_context *ctx, hipStream_t s, float *out, const uint8_t *in, size_t count, float scale,
                          float bias);
 

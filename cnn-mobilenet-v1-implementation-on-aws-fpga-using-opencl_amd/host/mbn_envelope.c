@@ -74,3 +74,14 @@ int mbn_stem_envelope_hw(int batch, int rows, int cols, int c1, int c3)
     if (4.0 * rows * cols * 3 >= (double)MBN_OOB || 4.0 * (rows / 2) * (cols / 2) * c3 >= 4294967296.0) return MBN_EUNSUPPORTED;
     return MBN_OK;
 }
+
+int mbn_upsample_argmax_envelope(int batch, int rows, int cols, int classes, int factor)
+{
+    if ((factor != 8 && factor != 16 && factor != 32) || batch <= 0 || batch > MBN_DENSE_MAX_BATCH || rows <= 0 || cols <= 0 || classes <= 0)
+        return MBN_EUNSUPPORTED;
+    if (4.0 * rows * cols * classes >= 2147483648.0) return MBN_EUNSUPPORTED;                                   /* an image's logits */
+    if (4.0 * rows * factor * cols * factor >= 2147483648.0) return MBN_EUNSUPPORTED;                           /* an image's labels / scores */
+    /* (both sides of the output map are now below 2^29, so the tile counts are ints) */
+    if ((long)MBN_DENSE_TILES(rows, factor) * MBN_DENSE_TILES(cols, factor) > MBN_DENSE_MAX_TILES) return MBN_EUNSUPPORTED;
+    return MBN_OK;
+}

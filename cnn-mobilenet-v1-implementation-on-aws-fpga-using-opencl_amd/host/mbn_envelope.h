@@ -26,6 +26,12 @@ extern "C" {
 #define MBN_TAIL_MAXSIDE 10          /* bf16 resident tail (mbn_bf16_tail.hip): largest side of its input map */
 #define MBN_STEM_TH 8                /* fused stem (mbn_f32_stem.hip): output tile of a workgroup */
 #define MBN_STEM_TW 16
+/* dense head read-out (mbn_f32_dense.hip): a workgroup owns a 32 x 32 output tile of a grid that starts factor / 2 before the image; tiles along
+ * an axis of n coarse samples, and the most tiles a launch can have (HIP: grid.x * 256 lanes below 2^32; the batch is grid.y, below 2^16) */
+#define MBN_DENSE_TILE 32
+#define MBN_DENSE_TILES(n, factor) (((n) * (factor) + (factor) / 2 + MBN_DENSE_TILE - 1) / MBN_DENSE_TILE)
+#define MBN_DENSE_MAX_TILES 0xFFFFFFL
+#define MBN_DENSE_MAX_BATCH 65535
 
 /* one 3x3 depthwise (stride, zero padding pad_top / pad_left) -> 1x1 pointwise block on `batch` NHWC images */
 typedef struct mbn_block_shape {
@@ -44,6 +50,9 @@ int mbn_tail_envelope(const mbn_block_shape *b0, const mbn_block_shape *b1);
 /* mbn_stem_fused_hw: c1 -> c1 -> c3 channels on rows x cols images; mbn_stem_envelope is the square form (mbn_stem_fused, _u8, _ex) */
 int mbn_stem_envelope_hw(int batch, int rows, int cols, int c1, int c3);
 int mbn_stem_envelope(int batch, int res, int c1, int c3);
+/* mbn_upsample_argmax_f32: fp32 logits [batch][rows][cols][classes] -> labels (and scores) [batch][rows * factor][cols * factor]. factor 8, 16 or 32;
+ * an image's logits and an image's output map each below 2^31 bytes (32-bit offsets inside an image; the batch goes through a 64-bit base) */
+int mbn_upsample_argmax_envelope(int batch, int rows, int cols, int classes, int factor);
 
 #ifdef __cplusplus
 }

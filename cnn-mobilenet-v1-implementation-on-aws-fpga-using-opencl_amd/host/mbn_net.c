@@ -47,6 +47,8 @@ struct mbn_net {
     unsigned char bf16_packed[MBN_MAX_LAYERS];   /* the copy is followed by its packed image (mbn_pack_filter_bf16) */
     void *keep_buf[MBN_MAX_LAYERS];
     void *logits_buf;          /* mbn_net_classify: [max_batch][classes] fp32 */
+    void *dense_feat;          /* mbn_net_forward_dense: the activation in front of the pool, [max_batch][h][w][channels] at fp32 size */
+    void *dense_logits;        /* mbn_net_segment: [max_batch][h][w][classes] fp32 */
     void *poolfc_ws;           /* workspace of mbn_pool_fc (1...4 images: pool + FC in one launch), allocated and zeroed at creation */
     size_t poolfc_ws_bytes;
     int fuse_tail;             /* mbn_net_set_fuse_tail (default 0) */
@@ -135,6 +137,8 @@ int mbn_net_destroy(mbn_net *net)
     mbn_sync(net->ctx);
     if (net->graph) mbn_graph_destroy(net->ctx, net->graph);
     if (net->logits_buf) mbn_free(net->ctx, net->logits_buf);
+    if (net->dense_feat) mbn_free(net->ctx, net->dense_feat);
+    if (net->dense_logits) mbn_free(net->ctx, net->dense_logits);
     if (net->poolfc_ws) mbn_free(net->ctx, net->poolfc_ws);
     for (int j = 0; j < 8; j++)
         if (net->streams[j]) mbn_stream_destroy(net->ctx, net->streams[j]);
@@ -586,8 +590,9 @@ int mbn_net_layer_output(mbn_net *net, int index, void **dptr, size_t *floats_pe
     return *dptr ? MBN_OK : MBN_ENOTFOUND;
 }
 
-/* One layer through the C-ABI: the positional arguments are kernel.cl's (see mbn.h). */
-static int run_layer(mbn_net *net, const mbn_layer_desc *l, const void *src, void *dst, int batch, void *stream)
+/* One layer through the C-ABI: the positional arguments are kernel.cl's (see mbn.h). The FC runs on an fc_rows x fc_cols map: 1 x 1 in the
+ * network's own sequence, the map in front of the pool for the dense head (mbn_net_forward_dense). */
+static int run_layer_on(mbn_net *net, const mbn_layer_desc *l, const void *src, void *dst, int batch, void *stream, int fc_rows, int fc_cols)
 {
     const int bf = net->dtype == MBN_DT_BF16, i8 = net->dtype == MBN_DT_I8;
     mbn_layer_ext ext;
@@ -630,10 +635,15 @@ static int run_layer(mbn_net *net, const mbn_layer_desc *l, const void *src, voi
     case MBN_L_FC:                         /* MobileNet.c:2682-2739: pointwise with rows = cols = 1; bias, no ReLU (B15) */
         ext.act = MBN_ACT_NONE;
         if (bf || i8) ext.io_flags = MBN_IO_OUT_F32;   /* logits stay fp32 */
-        return mbn_pointwise(net->ctx, dst, src, filt, 1, 1, l->in_ch, l->out_ch, &ext);
+        return mbn_pointwise(net->ctx, dst, src, filt, fc_rows, fc_cols, l->in_ch, l->out_ch, &ext);
     default:
         return MBN_EINVAL;
     }
+}
+
+static int run_layer(mbn_net *net, const mbn_layer_desc *l, const void *src, void *dst, int batch, void *stream)
+{
+    return run_layer_on(net, l, src, dst, batch, stream, 1, 1);
 }
 
 /* bytes per element of layer i's output in the current mode (FC logits are fp32 in every mode) */
@@ -830,6 +840,51 @@ int mbn_net_classify(mbn_net *net, const void *images, int batch, int k, void *t
     int rc = forward_impl(net, images, net->logits_buf, batch, 0, NULL, 0);
     if (rc != MBN_OK) return rc;
     return mbn_softmax_topk_f32(net->ctx, NULL, topk_idx_i32, topk_prob_f32, net->logits_buf, batch, fc->out_ch, k, NULL);
+}
+
+/* the dense head's layers: *feat = the layer in front of the pool, *fc = the FC; MBN_EUNSUPPORTED for a plan that does not end in pool, FC */
+static int dense_layers(const mbn_net *net, const mbn_layer_desc **feat, const mbn_layer_desc **fc)
+{
+    const int n = net->plan.n_layers;
+    if (n < 3 || net->plan.layer[n - 2].kind != MBN_L_POOL || net->plan.layer[n - 1].kind != MBN_L_FC) return MBN_EUNSUPPORTED;
+    *feat = &net->plan.layer[n - 3];
+    *fc = &net->plan.layer[n - 1];
+    if ((*fc)->in_ch != (*feat)->out_ch || (*feat)->out_rows <= 0 || (*feat)->out_cols <= 0) return MBN_EUNSUPPORTED;
+    return MBN_OK;
+}
+
+int mbn_net_forward_dense(mbn_net *net, const void *images, void *dense_logits, int batch)
+{
+    if (!net || !images || !dense_logits || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
+    const mbn_layer_desc *feat, *fc;
+    int rc = dense_layers(net, &feat, &fc);
+    if (rc != MBN_OK) return rc;
+    if (!net->dense_feat) {
+        rc = mbn_alloc(net->ctx, (size_t)net->max_batch * feat->out_rows * feat->out_cols * feat->out_ch * sizeof(float), &net->dense_feat);
+        if (rc != MBN_OK) { net->dense_feat = NULL; return rc; }
+    }
+    rc = forward_impl(net, images, net->dense_feat, batch, net->plan.n_layers - 2, NULL, 0);
+    if (rc != MBN_OK) return rc;
+    /* the sub-batch streams have joined the context's stream: the FC over every pixel follows on it */
+    return run_layer_on(net, fc, net->dense_feat, dense_logits, batch, NULL, feat->out_rows, feat->out_cols);
+}
+
+int mbn_net_segment(mbn_net *net, const void *images, int batch, void *labels_i32, void *score_f32)
+{
+    if (!net || !images || !labels_i32 || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
+    const mbn_layer_desc *feat, *fc;
+    int rc = dense_layers(net, &feat, &fc);
+    if (rc != MBN_OK) return rc;
+    const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols, h = feat->out_rows, w = feat->out_cols;
+    const int factor = rows / h;
+    if (factor * h != rows || factor * w != cols || (factor != 8 && factor != 16 && factor != 32)) return MBN_EUNSUPPORTED;
+    if (!net->dense_logits) {
+        rc = mbn_alloc(net->ctx, (size_t)net->max_batch * h * w * fc->out_ch * sizeof(float), &net->dense_logits);
+        if (rc != MBN_OK) { net->dense_logits = NULL; return rc; }
+    }
+    rc = mbn_net_forward_dense(net, images, net->dense_logits, batch);
+    if (rc != MBN_OK) return rc;
+    return mbn_upsample_argmax_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, factor, NULL);
 }
 
 int mbn_net_forward_timed(mbn_net *net, const void *images, void *logits, int batch, float *layer_ms, int n_layer_ms)

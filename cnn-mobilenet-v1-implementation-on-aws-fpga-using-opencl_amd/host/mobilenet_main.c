@@ -5,6 +5,7 @@
  *   mobilenet --synthetic SEED [--alpha A] [--res R] [--batch N]                              fp32, synthetic weights
  *   --res R = R x R images; --res RxC = R rows by C columns (a P6 image C wide and R high), both multiples of 32
  *   --output-stride 32 | 16 | 8: the late stride-2 depthwise layers stop subsampling, the ones behind them are dilated (mbn_plan_build_os)
+ *   --segment FILE: after the classification, the dense head (mbn_net_segment): the label map of image 0 as a binary PGM and its five most frequent labels
  *   mobilenet --literal [--weights weights_c.txt] [--image Cat_Image0.ppm] [--ref-args]      the reference's own mode
  *   mobilenet --gpus G --batch N [--steps K --warmup W --streams S --pw-emul 6] (--h5 F | --synthetic SEED)  N images sharded over G GPUs
  *   mobilenet --inspect weights.h5                                                             list the datasets of a .h5
@@ -324,11 +325,41 @@ done:
     return bad;
 }
 
+/* --segment: image 0's label map [rows][cols] as a binary PGM (P5), maxval = max(classes - 1, 1), two big-endian bytes per pixel beyond 255;
+ * then one line with the (at most) five most frequent labels, 0-based, and their pixel counts, most frequent first (ties: lowest label) */
+static int write_label_map(const char *path, const int *labels, int rows, int cols, int classes)
+{
+    const int maxval = classes - 1 > 1 ? classes - 1 : 1, wide = maxval > 255;
+    FILE *fp = fopen(path, "wb");
+    long *count = calloc((size_t)classes, sizeof(long));
+    if (!fp || !count) { if (fp) fclose(fp); free(count); fprintf(stderr, "Error: cannot write %s\n", path); return 1; }
+    fprintf(fp, "P5\n%d %d\n%d\n", cols, rows, maxval);
+    for (long i = 0; i < (long)rows * cols; i++) {
+        const int v = labels[i] < 0 ? 0 : labels[i] >= classes ? classes - 1 : labels[i];
+        count[v]++;
+        if (wide) fputc(v >> 8, fp);
+        fputc(v & 255, fp);
+    }
+    const int bad = fclose(fp) != 0;
+    printf("segment: %dx%d label map -> %s; most frequent labels:", cols, rows, path);
+    for (int j = 0; j < 5; j++) {
+        int best = -1;
+        for (int c = 0; c < classes; c++)
+            if (count[c] > 0 && (best < 0 || count[c] > count[best])) best = c;
+        if (best < 0) break;
+        printf(" %d (%ld)", best, count[best]);
+        count[best] = 0;
+    }
+    printf("\n");
+    free(count);
+    return bad;
+}
+
 int main(int argc, char **argv)
 {
     if (argc == 3 && !strcmp(argv[1], "--inspect")) return inspect_h5(argv[2]);
     if (argc == 4 && !strcmp(argv[1], "--convert")) return convert_h5(argv[2], argv[3]);
-    const char *h5 = NULL, *ppm = NULL, *wfile = "weights_c.txt", *image = "Cat_Image0.ppm";
+    const char *h5 = NULL, *ppm = NULL, *segment = NULL, *wfile = "weights_c.txt", *image = "Cat_Image0.ppm";
     int literal = 0, ref_args = 0, batch = 1, rows = 224, cols = 224, have_seed = 0, gpus = 0, steps = 20, warmup = 3, verify = 0, out_stride = 32;
     unsigned long long seed = 0;
     float alpha = 0.f;
@@ -346,6 +377,7 @@ int main(int argc, char **argv)
         }
         else if (!strcmp(argv[i], "--alpha") && i + 1 < argc) alpha = (float)atof(argv[++i]);
         else if (!strcmp(argv[i], "--output-stride") && i + 1 < argc) out_stride = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--segment") && i + 1 < argc) segment = argv[++i];
         else if (!strcmp(argv[i], "--synthetic") && i + 1 < argc) { seed = strtoull(argv[++i], NULL, 0); have_seed = 1; }
         else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--steps") && i + 1 < argc) steps = atoi(argv[++i]);
@@ -358,7 +390,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--literal")) literal = 1;
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
-            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] "
+            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] "
                             "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n", argv[0]);
             return 2;
         }
@@ -446,6 +478,17 @@ int main(int argc, char **argv)
     printf("top-%d:", topk);
     for (int j = 0; j < topk; j++) printf(" %d (%f)", arg[j] + 1, probs[j]);
     printf("\n");
+    if (segment) {
+        void *d_labels;
+        int *labels = malloc(sizeof(int) * (size_t)rows * cols);
+        if (!labels) return 1;
+        CHECK(mbn_alloc(ctx, sizeof(int) * (size_t)batch * rows * cols, &d_labels));
+        CHECK(mbn_net_segment(net, d_u8, batch, d_labels, NULL));
+        CHECK(mbn_download(ctx, labels, d_labels, sizeof(int) * (size_t)rows * cols));
+        const int bad = write_label_map(segment, labels, rows, cols, classes);
+        free(labels);
+        if (bad) return 1;
+    }
     mbn_net_destroy(net);
     mbn_weights_free(&w);
     mbn_shutdown(ctx);

@@ -360,6 +360,26 @@ int mbn_dwpw_fused_bf16(mbn_context *ctx, void *out, const void *in, const void 
  * cross PCIe instead of the 1000 logits of MobileNet.c:2744 + the host exp loop :2771-2792. */
 int mbn_softmax_topk_f32(mbn_context *ctx, void *probs, void *topk_idx_i32, void *topk_prob_f32, const void *logits,
                          int batch, int classes, int k, void *stream);
+/* Dense head read-out (segmentation; the reference has none: its only read-out is MobileNet.c:2771-2792 over 1000 pooled logits): bilinear upsample of
+ * per-pixel logits by `factor` and the argmax over the classes, in one kernel that never writes the upsampled tensor (mbn_f32_dense.hip).
+ * logits: fp32 NHWC [batch][rows][cols][classes]; labels_i32: [batch][rows*factor][cols*factor] int32; score_f32 (may be NULL): the same shape in
+ * fp32, the winning interpolated logit. factor 8, 16 or 32, an image's logits and an image's output map each below 2^31 bytes, batch <= 65535:
+ * otherwise MBN_EUNSUPPORTED. NULL labels / logits, a non-positive size or a pointer off 4 bytes: MBN_EINVAL. Any 4-byte-aligned pointer is taken
+ * (`logits` on 16 bytes with classes % 4 == 0 loads 16 bytes at a time; same results).
+ * The arithmetic, normative (tests/dense_ref.py reproduces it bit for bit in numpy float32). Half-pixel centres, as
+ * torch.nn.functional.interpolate(mode="bilinear", align_corners=False). For output row oy, with S = factor:
+ *     num = max(2*oy + 1 - S, 0);  y0 = num / (2S) (integer division);  y1 = min(y0 + 1, rows - 1);
+ *     fy = (float)(num % (2S)) / (float)(2S);  wy1 = fy;  wy0 = 1.0f - fy
+ * and x0, x1, wx0, wx1 from the output column ox and `cols` likewise. Every weight is an exact dyadic fraction, so only the three sums below round.
+ * Per class c, without FMA contraction (fmul / fadd each round to nearest even):
+ *     t0 = fadd(fmul(x[y0][x0][c], wx0), fmul(x[y0][x1][c], wx1))        horizontal first
+ *     t1 = fadd(fmul(x[y1][x0][c], wx0), fmul(x[y1][x1][c], wx1))
+ *     v  = fadd(fmul(t0, wy0), fmul(t1, wy1))                            then vertical
+ * (a weight of zero still multiplies: 0 * inf is a NaN here as it is in IEEE arithmetic).
+ * Argmax: best = -inf, label = 0; classes in ascending order, class c is taken iff v > best (strict). So the lowest index wins a tie, a NaN
+ * never wins, and a pixel whose every v is NaN or -inf has label 0 and score -inf. */
+int mbn_upsample_argmax_f32(mbn_context *ctx, void *labels_i32, void *score_f32, const void *logits, int batch, int rows, int cols, int classes,
+                            int factor, void *stream);
 /* The classifier tail of the sequence as one call (MobileNet.c:2601-2792): global average pool (kernel.cl:116) ->
  * FC = pointwise with rows = cols = 1 (kernel.cl:94; bias, no ReLU: B15) -> softmax + top-k. fp32 NHWC,
  * in [batch][rows][cols][channels], fc_w [classes][channels], fc_bias [classes] or NULL; pooled_scratch
@@ -643,6 +663,23 @@ int  mbn_net_forward(mbn_net *net, const void *images, void *logits, int batch, 
  * net's own logits buffer): topk_idx [batch][k] int32, topk_prob [batch][k] fp32, device pointers. What MobileNet.c:2744-2792
  * does with a 1000-byte D2H and a host loop, with 2k values per image to download. */
 int  mbn_net_classify(mbn_net *net, const void *images, int batch, int k, void *topk_idx_i32, void *topk_prob_f32);
+/* Dense head (fully-convolutional MobileNet-V1; with a trained 1x1 conv_preds a DeepLab-style head): the classifier applied at EVERY pixel of the
+ * last feature map instead of its average. For a plan whose last two layers are the pool and the FC (every plan of mbn_plan_build*), F = the layer
+ * in front of the pool (27), h x w its output map:
+ *   mbn_net_forward_dense  runs layers 1..F exactly as mbn_net_forward(net, images, ., batch, F) does (same launches, streams, dtype rules), skips
+ *                          the pool and runs the FC as mbn_pointwise with rows = h, cols = w (MBN_ACT_NONE, the FC's bias, the filter of the
+ *                          current mode, MBN_IO_OUT_F32 in bf16 and I8): dense_logits [batch][h][w][classes] fp32 in every mode, on the
+ *                          context's stream. On a 1 x 1 map (input 32 x 32 at output stride 32) these are mbn_net_forward's logits bit for bit
+ *                          (the pool of one pixel divides by 1) wherever layers 1..F run as the same launches in both calls; in bf16 the
+ *                          resident tail, which only the full forward can take, groups its pointwise sums differently: mbn_net_set_fuse_resident).
+ *   mbn_net_segment        mbn_net_forward_dense into a scratch buffer of the net, then mbn_upsample_argmax_f32 by factor = input rows / h:
+ *                          labels_i32 [batch][rows][cols] int32 and score_f32 (may be NULL) [batch][rows][cols] fp32 at input resolution. The
+ *                          factor must be the same for the columns and 8, 16 or 32 (any plan of mbn_plan_build_os), else MBN_EUNSUPPORTED.
+ * They keep their buffers in the net (the layer-F activation and, for segment, the dense logits: max_batch x h x w x classes floats), allocated on
+ * the first call and freed by mbn_net_destroy; MBN_ENOMEM leaves the net usable. F32, BF16 and I8 (which refuses dilated plans: output stride 32
+ * only). The FC and the read-out are not part of a graph captured under mbn_net_set_graph. */
+int  mbn_net_forward_dense(mbn_net *net, const void *images, void *dense_logits, int batch);
+int  mbn_net_segment(mbn_net *net, const void *images, int batch, void *labels_i32, void *score_f32);
 /* Per-layer milliseconds of the most recent mbn_net_forward_timed call (hipEvents between layers). */
 int  mbn_net_forward_timed(mbn_net *net, const void *images, void *logits, int batch, float *layer_ms,
                            int n_layer_ms);

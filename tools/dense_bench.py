@@ -1,0 +1,144 @@
+"""The dense head's read-out against the two-pass route it exists to avoid, in one process.
+
+  python tools/dense_bench.py [--reps 7] [--steps 20] [--batch 32] [--configs f32_os8,bf16_os16] [--no-torch]
+      1.0x224, 1000 classes, fp32 and bf16, output stride 8 and 16. Per configuration, alternating within every repetition:
+        kernel   mbn_upsample_argmax_f32 alone on the net's own dense logits (labels + scores), ms per call
+        segment  all of mbn_net_segment (layers 1-27, the FC at every pixel, the read-out), ms per call
+        torch    the yardstick, not the code under test: torch-ROCm on the SAME device buffer,
+                 interpolate(mode="bilinear", align_corners=False).argmax(1): the upsampled [batch][1000][224][224] tensor is written
+                 and read back (the route the fused kernel avoids), ms per call
+      Each figure is the median over the repetitions of `steps` back-to-back calls between two stream marks (torch: two torch events
+      on its own stream, synchronised). Then what the kernel's time means: the bytes it has to move (coarse logits in once, 4 bytes of
+      label + 4 of score per pixel out) over 8 TB/s, and its VALU work (per pixel and class: 3 interpolants of 2 multiplies + 1 add
+      shared as the kernel shares them, + compare and two selects) over the vector rate. The labels of the two routes are compared
+      once (agreement, not timing). One JSON object at the end. No GPU: the Context raises; nothing falls back.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from mbn_amd import import_package  # noqa: E402
+
+CLASSES, RES, ALPHA = 1000, 224, 1.0
+CONFIGS = [("f32_os8", "f32", 8), ("f32_os16", "f32", 16), ("bf16_os8", "bf16", 8), ("bf16_os16", "bf16", 16)]
+HBM_BYTES_PER_S = 8.0e12                    # spec
+VALU_LANE_OPS_PER_S = 256 * 4 * 32 * 2.4e9  # CUs x SIMDs x lanes per clock x max clock: fp32 vector instructions (an FMA counts once here)
+
+
+def kernel_work(batch, h, w, classes, S):
+    """(bytes the read-out must move, vector lane-operations it issues) from the shapes"""
+    pix = batch * h * S * w * S
+    bytes_ = 4.0 * batch * h * w * classes + 8.0 * pix
+    # per class: a lane forms t0, t1 (3 ops each) once for its 4 rows, then per row 3 ops of interpolation, 1 compare, 2 selects
+    ops = pix * classes * (6.0 / 4 + 6.0)
+    return bytes_, ops
+
+
+def marks_ms(ctx, fn, steps):
+    ctx.mark()
+    for _ in range(steps):
+        fn()
+    ctx.mark()
+    return sum(ctx.marks_read(4)) / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--configs", default="", help="comma list of configuration names (default: all)")
+    ap.add_argument("--no-torch", action="store_true", help="skip the torch yardstick")
+    a = ap.parse_args()
+    chosen = [c for c in CONFIGS if not a.configs or c[0] in a.configs.split(",")]
+    pkg = import_package()
+    torch = None
+    if not a.no_torch:
+        import torch
+        assert torch.cuda.is_available(), "the yardstick needs torch on the same GPU"
+    n = a.batch
+    result = {}
+    with tempfile.TemporaryDirectory() as d, pkg.Context(0) as ctx:
+        path = os.path.join(d, "w.h5")
+        pkg.synthetic_h5(path, alpha=ALPHA, classes=CLASSES, seed=7)
+        imgs = np.random.default_rng(0).uniform(-1, 1, (n, RES, RES, 3)).astype(np.float32)
+        d_in = ctx.to_device(imgs)
+        d_lab, d_sc = ctx.alloc(n * RES * RES * 4), ctx.alloc(n * RES * RES * 4)
+        runs = {}
+        for name, dtype, os_ in chosen:
+            hw = pkg.HostWeights(path, res=RES, output_stride=os_)
+            net = pkg.Net(ctx, hw.plan, hw.blob.copy(), n)
+            if dtype == "bf16":
+                net.set_dtype(pkg.DT_BF16)
+            h = w = RES // os_
+            if torch is not None:
+                # the yardstick reads the SAME device memory the kernel reads: a torch tensor owns it, the library writes into it
+                t_logits = torch.empty((n, h, w, CLASSES), dtype=torch.float32, device="cuda")
+                dense_ptr, d_dense = t_logits.data_ptr(), None
+            else:
+                t_logits, d_dense = None, ctx.alloc(n * h * w * CLASSES * 4)
+                dense_ptr = d_dense.ptr
+            net.forward_dense(d_in.ptr, dense_ptr, n)
+            ctx.sync()
+            r = dict(net=net, hw=hw, os=os_, h=h, w=w, dense_ptr=dense_ptr, d_dense=d_dense, t_logits=t_logits, kernel=[], segment=[], torch=[])
+            r["run_kernel"] = lambda r=r: ctx.upsample_argmax(d_lab.ptr, d_sc.ptr, r["dense_ptr"], n, r["h"], r["w"], CLASSES, r["os"])
+            r["run_segment"] = lambda r=r: r["net"].segment(d_in.ptr, n, d_lab.ptr, d_sc.ptr)
+            if torch is not None:
+                nchw = t_logits.permute(0, 3, 1, 2)         # a view: the same bytes, channels-last strides
+                r["run_torch"] = lambda nchw=nchw: torch.nn.functional.interpolate(nchw, size=(RES, RES), mode="bilinear",
+                                                                                   align_corners=False).argmax(1)
+            runs[name] = r
+            marks_ms(ctx, r["run_kernel"], 3)               # warm-up of every timed shape
+            marks_ms(ctx, r["run_segment"], 3)
+            if torch is not None:
+                for _ in range(3):
+                    t_lab = r["run_torch"]()
+                torch.cuda.synchronize()
+                r["run_kernel"]()
+                ctx.sync()
+                ours = d_lab.download((n, RES, RES), np.int32)
+                r["agree"] = float((ours == t_lab.cpu().numpy()).mean())
+                del t_lab
+        for _ in range(a.reps):
+            for name, r in runs.items():
+                r["kernel"].append(marks_ms(ctx, r["run_kernel"], a.steps))
+                r["segment"].append(marks_ms(ctx, r["run_segment"], a.steps))
+                if torch is not None:
+                    ctx.sync()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(a.steps):
+                        r["run_torch"]()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    r["torch"].append(e0.elapsed_time(e1) / a.steps)
+        for name, r in runs.items():
+            k, s = statistics.median(r["kernel"]), statistics.median(r["segment"])
+            bytes_, ops = kernel_work(n, r["h"], r["w"], CLASSES, r["os"])
+            out = {"batch": n, "kernel_ms": round(k, 4), "segment_ms": round(s, 4), "kernel_runs_ms": [round(x, 4) for x in r["kernel"]],
+                   "kernel_bytes": int(bytes_), "kernel_frac_of_8TBps": round(bytes_ / HBM_BYTES_PER_S / (k / 1e3), 4),
+                   "kernel_valu_lane_ops": int(ops), "kernel_frac_of_valu_rate": round(ops / VALU_LANE_OPS_PER_S / (k / 1e3), 4),
+                   "two_pass_bytes": int(2 * 4.0 * n * CLASSES * RES * RES)}
+            if r["torch"]:
+                t = statistics.median(r["torch"])
+                out.update({"torch_ms": round(t, 4), "torch_runs_ms": [round(x, 4) for x in r["torch"]], "torch_over_kernel": round(t / k, 2),
+                            "label_agreement_with_torch": round(r["agree"], 6)})
+            result[name] = out
+            print("%-10s batch %d  kernel %.4f ms  segment %.4f ms  torch %s ms  (kernel: %.1f %% of 8 TB/s, %.1f %% of the VALU rate)" % (
+                name, n, k, s, ("%.4f" % out["torch_ms"]) if r["torch"] else "-", 100 * out["kernel_frac_of_8TBps"],
+                100 * out["kernel_frac_of_valu_rate"]), flush=True)
+        for r in runs.values():
+            r["net"].destroy()
+            r["hw"].free()
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
