@@ -81,6 +81,18 @@ class I8Params(C.Structure):
     _fields_ = [("n_layers", C.c_int32), ("blob_bytes", C.c_int64), ("layer", I8Layer * MAX_LAYERS)]
 
 
+class I8PwPlan(C.Structure):
+    """mbn_i8_pw_plan_t (host/mbn_envelope.h): the launch mbn_launch_i8_pointwise issues for a shape"""
+    _fields_ = [(n, C.c_int) for n in ("form", "ks", "g", "out_f32", "pt", "threads", "gy", "lds_bytes")] + \
+               [("ntiles", C.c_long), ("gx", C.c_long)] + \
+               [(n, C.c_int) for n in ("kp", "cpw", "rep", "resident", "maxg")] + \
+               [("per_round", C.c_long), ("rounds", C.c_long)] + \
+               [(n, C.c_int) for n in ("nkb", "nchunks", "cpg", "ngroups")]
+
+
+I8_PW_PERSISTENT, I8_PW_KREG = 1, 2
+
+
 def build(force: bool = False) -> None:
     """Compile the HIP kernels for gfx950 + the C host (make; hipcc cross-compiles without a GPU): the shipped library and
     the lab build beside it (`all lab`)."""
@@ -128,6 +140,7 @@ def _declare_host(lib):
     lib.mbn_rank_fail.argtypes = [C.c_void_p]
     lib.mbn_quantize_i8.argtypes = [C.POINTER(Plan), C.c_void_p, C.c_void_p, C.POINTER(I8Params), C.c_void_p]
     lib.mbn_upsample_argmax_envelope.argtypes = [C.c_int] * 5      # mbn_envelope.h: exported, not in mbn.h
+    lib.mbn_i8_pw_plan.argtypes = [C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(I8PwPlan)]
     return lib
 
 
@@ -261,6 +274,14 @@ def _strerror(code):
 def _chk(rc, what=""):
     if rc != OK:
         raise MbnError(rc, what)
+
+
+def i8_pw_plan(m, cin, op_size, num_cus, operands_on_16=True, out_f32=False, lib=None) -> I8PwPlan:
+    """mbn_i8_pw_plan: the launch of an int8 pointwise call of m pixels, K = cin, N = op_size on a device of num_cus CUs."""
+    p = I8PwPlan()
+    _chk((lib or host_lib()).mbn_i8_pw_plan(m, cin, op_size, num_cus, int(operands_on_16), int(out_f32), C.byref(p)),
+         "i8_pw_plan(%d, %d, %d)" % (m, cin, op_size))
+    return p
 
 
 def declared_symbols():

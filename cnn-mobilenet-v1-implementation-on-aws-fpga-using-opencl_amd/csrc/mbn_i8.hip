@@ -11,7 +11,8 @@
 //              activations enter the signed MFMA as x ^ 0x80 = x - 128 and 128 * sum(w) is added back in int32: exact for any order and
 //              tiling. Two forms. i8_pw2_k (K <= 1024: every layer of the network): persistent, a wave keeps one 32-column chunk's filter
 //              rows in registers and the workgroup streams pixel tiles through two LDS buffers. i8_pw_k (K > 1024, or operands on 8 but
-//              not 16 bytes): a wave keeps 32 pixels' K in registers (K blocks streamed beyond 32 * KS) and reads the filter rows from L2.
+//              not 16 bytes, or where the staging bound of the first form fails): a wave keeps 32 pixels' K in registers (K blocks streamed
+//              beyond 32 * KS) and reads the filter rows from L2. Which form, tile and grid: mbn_i8_pw_plan (host/mbn_envelope.c).
 //   pool       global average: exact int32 sums of four channels per lane, one fp32 multiply by 1 / (rows * cols).
 // Every index is 64-bit (plain global loads and stores, no buffer descriptors): no 32-bit offset limit.
 #include "mbn_internal.h"
@@ -428,6 +429,8 @@ __global__ __launch_bounds__(MAXT) void i8_pw2_k(Pw2Args a)
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[r] = 0;
             const uint8_t *brow = xb + (sub + li) * str + 16 * lh;
+            // With K % 32 != 0 the last k step reads row bytes [K, kp) that put() never writes (whatever the LDS held). They meet filter
+            // bytes that pw_load zeroed past K, so they add nothing to acc or ws: exactness rests on that zero fill, not on the LDS.
 #pragma unroll
             for (int s = 0; s < KS; s++)
                 if (s < ksteps) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[s], *reinterpret_cast<const i4v *>(brow + 32 * s), acc, 0, 0, 0);
@@ -560,68 +563,42 @@ static void pw2_launch(const mbn_call &c, const Pw2Args &a, dim3 grid, int threa
 
 int mbn_launch_i8_pointwise(const mbn_call &c, void *out, const uint8_t *in, const int8_t *filt, long m, int cin, int op_size)
 {
+    // every number of the launch comes from mbn_i8_pw_plan (host/mbn_envelope.c): the form, the tile, the grid, the instantiation
     const bool f32 = (c.io_flags & MBN_IO_OUT_F32) != 0;
-    const bool g16 = (cin % 16) == 0 && (uintptr_t)in % 16 == 0 && (uintptr_t)filt % 16 == 0;
-    if (cin <= 1024 && (g16 || (cin % 16) != 0)) {
-        // persistent form: per workgroup up to 8 waves = 32-column chunks x groups of pixel sub-tiles
+    mbn_i8_pw_plan_t pl;
+    const int rc = mbn_i8_pw_plan(m, cin, op_size, c.ctx->num_cus, (uintptr_t)in % 16 == 0 && (uintptr_t)filt % 16 == 0, f32, &pl);
+    if (rc != MBN_OK) return rc;
+    if (pl.form == MBN_I8_PW_PERSISTENT) {
         Pw2Args a;
         a.out = out; a.in = in; a.w = filt; a.mult = c.scale; a.bias = c.shift;
-        a.m = m; a.k = cin; a.kp = (cin + 31) / 32 * 32; a.n = op_size;
-        const int nchunks = (op_size + 31) / 32, maxw = 8, gb = cin % 16 == 0 ? 16 : 8;
-        const int ngy = (nchunks + maxw - 1) / maxw, cpw = (nchunks + ngy - 1) / ngy;
-        const int maxg = a.kp / 32 <= 4 ? 8 : 4;                              // the kernel's MAXG (granules per thread and tile)
-        const long str = a.kp + 16;
-        // waves: cpw chunks x rep groups of 32-pixel sub-tiles, four waves where the chunks allow
-        int rep = cpw >= 4 ? 1 : 4 / cpw;
-        // workgroups a CU holds at once: about 12 waves of these register counts; the tile's two LDS buffers are sized to fit them
-        const int resident = cpw * rep >= 8 ? 1 : 12 / (cpw * rep);
-        int pt = (int)std::min<long>(32768 / a.kp, (160L * 1024 / resident) / (2 * str)) / 32 * 32;   // ~32 KB tiles
-        if (pt > 1024) pt = 1024;
-        if (pt < 32) pt = 32;
-        // the fewest rounds of the resident slots the largest tile allows, then the smallest tile that keeps to them (short layers,
-        // the 14 x 14 and smaller maps: one round, every slot busy, no straggling second round)
-        const long per_round = std::max<long>(1, (long)c.ctx->num_cus * resident / ngy);
-        const long rounds = ((m + pt - 1) / pt + per_round - 1) / per_round;
-        pt = (int)std::min<long>(pt, ((m + rounds * per_round - 1) / (rounds * per_round) + 31) / 32 * 32);
-        if (rep > pt / 32) rep = pt / 32;
-        // more waves where staging a tile needs them
-        while (cpw * rep < maxw && (long)pt * (cin / gb) > (long)maxg * 64 * cpw * rep) rep++;
-        while (pt > 32 && (long)pt * (cin / gb) > (long)maxg * 64 * cpw * rep) pt -= 32;
-        const int waves = cpw * rep, threads = 64 * waves;
-        if (waves <= maxw && (long)pt * (cin / gb) <= (long)maxg * threads) {
-        a.cpw = cpw;
-        a.pt = pt;
-        a.ntiles = (m + pt - 1) / pt;
-        const size_t lds = 2 * (size_t)pt * str;
-        const long gx = std::min<long>(a.ntiles, per_round);               // persistent: the resident slots
-        const dim3 grid((unsigned)gx, (unsigned)ngy);
-        const int ks = a.kp / 32;
-        if (ks <= 1) pw2_launch<1, 512>(c, a, grid, threads, lds, f32);
-        else if (ks <= 2) pw2_launch<2, 512>(c, a, grid, threads, lds, f32);
-        else if (ks <= 4) pw2_launch<4, 512>(c, a, grid, threads, lds, f32);
-        else if (ks <= 8) pw2_launch<8, 512>(c, a, grid, threads, lds, f32);
-        else if (ks <= 16) pw2_launch<16, 512>(c, a, grid, threads, lds, f32);
-        else pw2_launch<32, 512>(c, a, grid, threads, lds, f32);
-        return MBN_OK;
+        a.m = m; a.k = cin; a.kp = pl.kp; a.n = op_size;
+        a.cpw = pl.cpw;
+        a.pt = pl.pt;
+        a.ntiles = pl.ntiles;
+        const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
+        const size_t lds = (size_t)pl.lds_bytes;
+        switch (pl.ks) {
+        case 1: pw2_launch<1, 512>(c, a, grid, pl.threads, lds, f32); break;
+        case 2: pw2_launch<2, 512>(c, a, grid, pl.threads, lds, f32); break;
+        case 4: pw2_launch<4, 512>(c, a, grid, pl.threads, lds, f32); break;
+        case 8: pw2_launch<8, 512>(c, a, grid, pl.threads, lds, f32); break;
+        case 16: pw2_launch<16, 512>(c, a, grid, pl.threads, lds, f32); break;
+        default: pw2_launch<32, 512>(c, a, grid, pl.threads, lds, f32); break;
         }
+        return MBN_OK;
     }
     PwArgs a;
     a.out = out; a.in = in; a.w = filt; a.mult = c.scale; a.bias = c.shift;
     a.m = m; a.k = cin; a.n = op_size;
-    a.nchunks = (op_size + 31) / 32;
-    const long tiles = (m + PW_PIX - 1) / PW_PIX;
-    // column groups: split the chunks over workgroups until the grid holds two workgroups per CU (the pixels are then read once per group,
-    // the later reads from the L2 / MALL)
-    long ng = (2L * c.ctx->num_cus + tiles - 1) / tiles;
-    if (ng > a.nchunks) ng = a.nchunks;
-    if (ng < 1) ng = 1;
-    a.cpg = (int)((a.nchunks + ng - 1) / ng);
-    a.ngroups = (a.nchunks + a.cpg - 1) / a.cpg;
-    const long blocks = tiles * a.ngroups;
-    if (blocks > 0x7fffffffL) return MBN_EUNSUPPORTED;
-    if (cin <= 128) { if (g16) pw_launch<4, 16>(c, a, (unsigned)blocks, f32); else pw_launch<4, 8>(c, a, (unsigned)blocks, f32); }
-    else if (cin <= 512) { if (g16) pw_launch<16, 16>(c, a, (unsigned)blocks, f32); else pw_launch<16, 8>(c, a, (unsigned)blocks, f32); }
-    else { if (g16) pw_launch<32, 16>(c, a, (unsigned)blocks, f32); else pw_launch<32, 8>(c, a, (unsigned)blocks, f32); }
+    a.nchunks = pl.nchunks;
+    a.cpg = pl.cpg;
+    a.ngroups = pl.ngroups;
+    if (pl.pt != PW_PIX || pl.threads != 64 * PW_WAVES) return MBN_EINVAL;   // the kernel's own tile: 4 waves x 32 pixels
+    const unsigned blocks = (unsigned)pl.gx;
+    const bool g16 = pl.g == 16;
+    if (pl.ks == 4) { if (g16) pw_launch<4, 16>(c, a, blocks, f32); else pw_launch<4, 8>(c, a, blocks, f32); }
+    else if (pl.ks == 16) { if (g16) pw_launch<16, 16>(c, a, blocks, f32); else pw_launch<16, 8>(c, a, blocks, f32); }
+    else { if (g16) pw_launch<32, 16>(c, a, blocks, f32); else pw_launch<32, 8>(c, a, blocks, f32); }
     return MBN_OK;
 }
 

@@ -85,3 +85,75 @@ int mbn_upsample_argmax_envelope(int batch, int rows, int cols, int classes, int
     if ((long)MBN_DENSE_TILES(rows, factor) * MBN_DENSE_TILES(cols, factor) > MBN_DENSE_MAX_TILES) return MBN_EUNSUPPORTED;
     return MBN_OK;
 }
+
+static long lmin(long a, long b) { return a < b ? a : b; }
+
+int mbn_i8_pw_plan(long m, int cin, int op_size, int num_cus, int operands_on_16, int out_f32, mbn_i8_pw_plan_t *p)
+{
+    if (!p || m <= 0 || cin <= 0 || (cin % 8) != 0 || cin > 65536 || op_size <= 0 || num_cus <= 0) return MBN_EINVAL;
+    const mbn_i8_pw_plan_t zero = { 0 };
+    *p = zero;
+    p->out_f32 = out_f32 != 0;
+    const int g16 = (cin % 16) == 0 && operands_on_16;
+    const int nchunks = (op_size + 31) / 32;
+    if (cin <= 1024 && (g16 || (cin % 16) != 0)) {
+        /* persistent form: per workgroup up to 8 waves = 32-column chunks x groups of pixel sub-tiles */
+        const int kp = (cin + 31) / 32 * 32, maxw = MBN_I8_PW_MAXWAVES, gb = cin % 16 == 0 ? 16 : 8;
+        const int ngy = (nchunks + maxw - 1) / maxw, cpw = (nchunks + ngy - 1) / ngy;
+        const int maxg = kp / 32 <= 4 ? 8 : 4;                               /* the kernel's MAXG (granules per thread and tile) */
+        const long str = kp + 16;
+        /* waves: cpw chunks x rep groups of 32-pixel sub-tiles, four waves where the chunks allow */
+        int rep = cpw >= 4 ? 1 : 4 / cpw;
+        /* workgroups a CU holds at once: about 12 waves of these register counts; the tile's two LDS buffers are sized to fit them */
+        const int resident = cpw * rep >= 8 ? 1 : 12 / (cpw * rep);
+        int pt = (int)lmin(32768 / kp, ((long)MBN_I8_PW_LDS_MAX / resident) / (2 * str)) / 32 * 32;   /* ~32 KB tiles */
+        if (pt > 1024) pt = 1024;
+        if (pt < 32) pt = 32;
+        /* the fewest rounds of the resident slots the largest tile allows, then the smallest tile that keeps to them (short layers,
+         * the 14 x 14 and smaller maps: one round, every slot busy, no straggling second round) */
+        long per_round = (long)num_cus * resident / ngy;
+        if (per_round < 1) per_round = 1;
+        const long rounds = ((m + pt - 1) / pt + per_round - 1) / per_round;
+        pt = (int)lmin(pt, ((m + rounds * per_round - 1) / (rounds * per_round) + 31) / 32 * 32);
+        if (rep > pt / 32) rep = pt / 32;
+        /* more waves where staging a tile needs them */
+        while (cpw * rep < maxw && (long)pt * (cin / gb) > (long)maxg * 64 * cpw * rep) rep++;
+        while (pt > 32 && (long)pt * (cin / gb) > (long)maxg * 64 * cpw * rep) pt -= 32;
+        const int waves = cpw * rep, threads = 64 * waves;
+        if (waves <= maxw && (long)pt * (cin / gb) <= (long)maxg * threads) {
+            const int ks = kp / 32;
+            p->form = MBN_I8_PW_PERSISTENT;
+            p->ks = ks <= 1 ? 1 : ks <= 2 ? 2 : ks <= 4 ? 4 : ks <= 8 ? 8 : ks <= 16 ? 16 : 32;
+            p->g = gb;
+            p->pt = pt;
+            p->threads = threads;
+            p->gy = ngy;
+            p->lds_bytes = (int)(2 * (long)pt * str);
+            p->ntiles = (m + pt - 1) / pt;
+            p->gx = lmin(p->ntiles, per_round);                              /* persistent: the resident slots */
+            p->kp = kp; p->cpw = cpw; p->rep = rep; p->resident = resident; p->maxg = maxg;
+            p->per_round = per_round; p->rounds = rounds;
+            return MBN_OK;
+        }
+        /* K % 16 == 8 above 512: a 32-pixel tile's 8-byte granules outnumber what 512 threads stage */
+    }
+    p->form = MBN_I8_PW_KREG;
+    p->ks = cin <= 128 ? 4 : cin <= 512 ? 16 : 32;
+    p->g = g16 ? 16 : 8;
+    p->pt = 128;
+    p->threads = 256;
+    p->gy = 1;
+    p->nkb = (cin + 32 * p->ks - 1) / (32 * p->ks);
+    p->nchunks = nchunks;
+    p->ntiles = (m + p->pt - 1) / p->pt;
+    /* column groups: split the chunks over workgroups until the grid holds two workgroups per CU (the pixels are then read once per
+     * group, the later reads from the L2 / MALL) */
+    long ng = (2L * num_cus + p->ntiles - 1) / p->ntiles;
+    if (ng > nchunks) ng = nchunks;
+    if (ng < 1) ng = 1;
+    p->cpg = (int)((nchunks + ng - 1) / ng);
+    p->ngroups = (nchunks + p->cpg - 1) / p->cpg;
+    p->gx = p->ntiles * p->ngroups;
+    if (p->gx > 0x7fffffffL) return MBN_EUNSUPPORTED;
+    return MBN_OK;
+}

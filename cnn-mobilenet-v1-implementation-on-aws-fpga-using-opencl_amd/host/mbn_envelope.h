@@ -54,6 +54,39 @@ int mbn_stem_envelope(int batch, int res, int c1, int c3);
  * an image's logits and an image's output map each below 2^31 bytes (32-bit offsets inside an image; the batch goes through a 64-bit base) */
 int mbn_upsample_argmax_envelope(int batch, int rows, int cols, int classes, int factor);
 
+/* int8 pointwise / FC (mbn_i8.hip): the whole launch arithmetic of mbn_launch_i8_pointwise, which launches what this says and
+ * computes nothing of its own. Two forms: the persistent one (i8_pw2_k<ks, 512, out_f32>: a wave keeps a 32-column chunk's filter
+ * rows, the workgroup's gx * gy copies walk `ntiles` tiles of `pt` pixels grid-strided through two LDS buffers) and the
+ * K-in-registers one (i8_pw_k<ks, g, out_f32>: a workgroup = 128 pixels x cpg chunks, K streamed in blocks of 32 * ks bytes). */
+#define MBN_I8_PW_PERSISTENT 1
+#define MBN_I8_PW_KREG 2
+#define MBN_I8_PW_MAXWAVES 8         /* waves of a persistent workgroup at most */
+#define MBN_I8_PW_LDS_MAX (160 * 1024)
+typedef struct mbn_i8_pw_plan_t {
+    int form;                        /* MBN_I8_PW_PERSISTENT or MBN_I8_PW_KREG */
+    int ks;                          /* the kernel's KS: 32-byte k steps held in registers (1, 2, 4, 8, 16, 32; KREG: 4, 16, 32) */
+    int g;                           /* bytes per global load of a row: 16 (K % 16 == 0) or 8; KREG: 16 only with the operands on 16 bytes */
+    int out_f32;                     /* the OUTF32 instantiation */
+    int pt;                          /* pixels per tile (PERSISTENT: a multiple of 32; KREG: 128) */
+    int threads;                     /* per workgroup */
+    int gy;                          /* grid.y: column groups of the PERSISTENT form (KREG: 1, its groups are folded into grid.x) */
+    int lds_bytes;                   /* dynamic LDS (KREG: 0) */
+    long ntiles;                     /* ceil(m / pt) */
+    long gx;                         /* grid.x. PERSISTENT: workgroup x takes tiles x, x + gx, ...; KREG: ntiles * ngroups */
+    /* PERSISTENT only (0 in a KREG plan) */
+    int kp;                          /* K rounded up to 32: a row of a tile in LDS is kp + 16 bytes */
+    int cpw, rep;                    /* waves = cpw chunks x rep groups of 32-pixel sub-tiles */
+    int resident;                    /* workgroups a CU is counted to hold */
+    int maxg;                        /* the kernel's MAXG: granules a thread stages per tile; pt * (K / g) <= maxg * threads */
+    long per_round, rounds;          /* resident slots per column group; passes over them the largest tile needs */
+    /* KREG only (0 in a PERSISTENT plan) */
+    int nkb;                         /* K blocks of 32 * ks bytes */
+    int nchunks, cpg, ngroups;       /* 32-column chunks, chunks per workgroup, workgroups per pixel tile */
+} mbn_i8_pw_plan_t;
+/* m pixels, K = cin (a multiple of 8), N = op_size on a device of num_cus CUs; operands_on_16: activations and filter on 16 bytes (they
+ * are on 8 at least). MBN_EINVAL for a shape the C-ABI refuses before it, MBN_EUNSUPPORTED for a grid beyond 2^31 - 1 workgroups. */
+int mbn_i8_pw_plan(long m, int cin, int op_size, int num_cus, int operands_on_16, int out_f32, mbn_i8_pw_plan_t *plan);
+
 #ifdef __cplusplus
 }
 #endif

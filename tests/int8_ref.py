@@ -104,6 +104,14 @@ def pw(x, w8, mult, bias, out_f32=False):
     return y if out_f32 else to_u8(y)
 
 
+def pw_blocks(x, w8, mult, bias, out_f32=False, block=8192):
+    """pw() over row blocks of a tall x: yields (first row, rows' outputs); the float64 product of a block only is in memory"""
+    w = np.asarray(w8, np.float64).T.copy()
+    for i in range(0, len(x), block):
+        y = requant_f32((np.asarray(x[i:i + block], np.float64) @ w).astype(np.int64), mult, bias)
+        yield i, (y if out_f32 else to_u8(y))
+
+
 def pool(x):
     """x uint8 [N][H][W][C] -> uint8 [N][C]"""
     n, h, w, c = x.shape
@@ -112,12 +120,18 @@ def pool(x):
     return to_u8((s.astype(np.float32) * inv).astype(np.float32))
 
 
-def conv1_y(img, w, mult, bias, stride=2):
+def conv1_y(img, w, mult, bias, stride=2, pad_top=None, pad_left=None):
     """img float [N][H][W][cin] (already normalised), w fp32 [3][3][cin][C] -> float64 y = acc * mult + bias [N][ho][wo][C]"""
+    return conv1_acc(img, w, stride, pad_top, pad_left) * np.asarray(mult, np.float64) + np.asarray(bias, np.float64)
+
+
+def conv1_acc(img, w, stride=2, pad_top=None, pad_left=None):
+    """float64 sums of the 3x3 convolution; the output map is ceil(H / stride) x ceil(W / stride) whatever the pads (None: TF-SAME)"""
     n, h, wd, cin = img.shape
     C = w.shape[-1]
     ho, wo = (h + stride - 1) // stride, (wd + stride - 1) // stride
-    pt, pl = same_pad(h, ho, stride), same_pad(wd, wo, stride)
+    pt = same_pad(h, ho, stride) if pad_top is None else pad_top
+    pl = same_pad(wd, wo, stride) if pad_left is None else pad_left
     xp = np.zeros((n, h + 4, wd + 4, cin), np.float64)
     xp[:, pt:pt + h, pl:pl + wd] = img
     acc = np.zeros((n, ho, wo, C), np.float64)
@@ -126,7 +140,57 @@ def conv1_y(img, w, mult, bias, stride=2):
         for kx in range(3):
             patch = xp[:, ky:ky + (ho - 1) * stride + 1:stride, kx:kx + (wo - 1) * stride + 1:stride]
             acc += patch @ wk[ky, kx]
-    return acc * np.asarray(mult, np.float64) + np.asarray(bias, np.float64)
+    return acc
+
+
+# conv1 on a grid on which its fp32 sum is exact in any order: image values k / 2^7 in [-1, 1], taps k / 2^6 with |w| <= 2. A term is a multiple
+# of 2^-13 of at most 2^14 units and the 27 of a sum stay below 27 * 2^14 < 2^24 units: every partial sum, fused or not, is an integer number of
+# units that fp32 holds exactly (tests/test_int8_cpu.py proves it on the inputs built here).
+CONV1_IMG_BITS, CONV1_TAP_BITS = 7, 6
+
+
+CONV1_CHANNELS = (8, 16, 24, 32, 48)                            # every NG of i8_conv_k, and blockIdx.y > 0
+CONV1_MAPS = ((64, 64), (63, 37), (5, 3))                       # a square map, an odd non-square one, one smaller than a workgroup
+CONV1_PADS = ((None, None), (0, 1), (1, 0))                     # TF-SAME, and explicit pads with pad_top != pad_left
+
+
+def conv1_exact_inputs(rng, n, h, w, c):
+    """(image fp32 [n][h][w][3], taps fp32 [3][3][3][c], mult, bias) on that grid; mult / bias spread y over both clamps and the interior:
+    the sums have a standard deviation near 3.5 (27 terms of variance 1/3 * 4/3), y = 36 acc + 128 leaves [0, 255] for |acc| > 3.5"""
+    img = (rng.integers(-(1 << CONV1_IMG_BITS), (1 << CONV1_IMG_BITS) + 1, (n, h, w, 3)) / float(1 << CONV1_IMG_BITS)).astype(np.float32)
+    taps = (rng.integers(-(2 << CONV1_TAP_BITS), (2 << CONV1_TAP_BITS) + 1, (3, 3, 3, c)) / float(1 << CONV1_TAP_BITS)).astype(np.float32)
+    mult = rng.uniform(24, 48, c).astype(np.float32)
+    bias = rng.uniform(100, 156, c).astype(np.float32)
+    return img, taps, mult, bias
+
+
+def conv1_grid_units(img, taps, stride=1, pad_top=None, pad_left=None):
+    """max over the outputs of sum |term| in units of 2^-(CONV1_IMG_BITS + CONV1_TAP_BITS): below 2^24, every order of the sum is exact"""
+    unit = float(1 << (CONV1_IMG_BITS + CONV1_TAP_BITS))
+    for a, bits in ((img, CONV1_IMG_BITS), (taps, CONV1_TAP_BITS)):
+        k = np.asarray(a, np.float64) * (1 << bits)
+        assert np.array_equal(k, np.rint(k)), "off the grid"
+    return float(conv1_acc(np.abs(img), np.abs(taps), stride, pad_top, pad_left).max() * unit)
+
+
+def conv1_exact(img, taps, mult, bias, stride=2, pad_top=None, pad_left=None):
+    """uint8 conv1 of grid inputs: the exact sum (fp32 holds it), then the header's two float32 roundings, rint, clamp"""
+    acc = conv1_acc(img, taps, stride, pad_top, pad_left)
+    a32 = acc.astype(np.float32)
+    assert np.array_equal(a32.astype(np.float64), acc)
+    return to_u8((a32 * np.asarray(mult, np.float32)).astype(np.float32) + np.asarray(bias, np.float32))
+
+
+def assert_conv1_one_step(got, y, what=""):
+    """The rule for a conv1 whose fp32 sum is not exact: within one step of rint(clip(y)) of the float64 y, and different only where y is
+    within 2^-10 of a half-integer"""
+    got = np.asarray(got).astype(np.int64)
+    want = np.clip(np.rint(y), 0, 255).astype(np.int64)
+    diff = got != want
+    assert np.abs(got - want).max() <= 1, what
+    yc = np.clip(y, 0, 255)
+    assert np.all(np.abs(yc[diff] - (np.floor(yc[diff]) + 0.5)) < 2.0 ** -10), "%s: mismatch away from a half-integer" % what
+    assert diff.mean() < 1e-3, what
 
 
 def layer_from_prev(l, q, prev):

@@ -178,3 +178,186 @@ int main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %d\n", sizeof(mbn_i8_
     L, P = pkg.I8Layer, pkg.I8Params
     assert vals == [C.sizeof(L), L.mult_offset.offset, L.bias_offset.offset, L.in_scale.offset, L.out_scale.offset, C.sizeof(P),
                     P.blob_bytes.offset, P.layer.offset, C.sizeof(pkg.LayerExt), pkg.DT_I8]
+
+
+# ------------------------------------------------------------------------------------------- the pointwise launch plan (mbn_i8_pw_plan)
+
+def _plan(pkg, m, k, n, cus=256, on16=True, f32=False):
+    return pkg.i8_pw_plan(m, k, n, cus, on16, f32)
+
+
+def test_pw_plan_first_second_tile_n1024(pkg):
+    """N = 1024 on 256 CUs: 32 chunks = 4 column groups (gy) of cpw = 8 chunks, so 8 waves with rep = 1, one resident workgroup per CU
+    and per_round = 256 * 1 / 4 = 64 slots per group. The largest tile is min(32768 / K, 160 KB / (2 (K + 16))) rounded down to 32 and
+    capped at 1024: 1024, 512, 256, 128, 64, 32 pixels for K = 32 ... 1024 (the first term decides each). 64 such tiles hold 2^16,
+    2^15, ... 2^11 pixels, so one pixel more is the first M that needs a second round: rounds = 2, and the tile shrinks to
+    ceil(M / 128) rounded up to 32. The rows of the issue's table (a hand mirror; a few pixels above these) are multi-pass as well."""
+    for k, ptmax, pt2, issue_m in ((32, 1024, 544, 65559), (64, 512, 288, 32777), (128, 256, 160, 16386), (256, 128, 96, 8209),
+                                   (512, 64, 64, 4102), (1024, 32, 32, 2067)):
+        last1 = 64 * ptmax
+        p = _plan(pkg, last1, k, 1024)
+        assert (p.form, p.pt, p.ntiles, p.gx, p.gy, p.rounds) == (pkg.I8_PW_PERSISTENT, ptmax, 64, 64, 4, 1), k
+        p = _plan(pkg, last1 + 1, k, 1024)
+        # 2 rounds x 64 slots: ceil((last1 + 1) / 128) = ptmax / 2 + 1 -> up to 32: ptmax / 2 + 32 (K = 512, 1024: the cap ptmax)
+        assert p.pt == pt2 == min(ptmax, ptmax // 2 + 32) and p.rounds == 2, k
+        assert (p.ntiles, p.gx) == (-(-(last1 + 1) // pt2), 64) and p.ntiles > p.gx, k
+        assert (p.ks, p.kp, p.cpw, p.rep, p.resident, p.threads, p.per_round) == (k // 32, k, 8, 1, 1, 512, 64), k
+        assert p.lds_bytes == 2 * pt2 * (k + 16) and p.g == 16 and p.maxg == (8 if k <= 128 else 4)
+        q = _plan(pkg, issue_m, k, 1024)
+        assert q.form == pkg.I8_PW_PERSISTENT and q.ntiles > q.gx == 64, k
+
+
+def test_pw_plan_first_second_tile_n64(pkg):
+    """N = 64: two chunks, one column group, cpw = 2, rep = 4 / 2 = 2 (four waves), resident = 12 / 4 = 3, per_round = 768. Largest tile:
+    K = 32: min(1024, 54613 / 96 = 568) -> 544; K = 256: min(128, 54613 / 544 = 100) -> 96; K = 1024: 32. 768 of them hold 417 792,
+    73 728 and 24 576 pixels: M must exceed those for a second tile."""
+    for k, last1 in ((32, 417792), (256, 73728), (1024, 24576)):
+        p = _plan(pkg, last1, k, 64)
+        assert (p.form, p.rounds, p.per_round, p.resident, p.cpw) == (pkg.I8_PW_PERSISTENT, 1, 768, 3, 2) and p.ntiles <= p.gx
+        p = _plan(pkg, last1 + 1, k, 64)
+        assert p.rounds == 2 and p.ntiles > p.gx == 768, k
+
+
+def test_pw_plan_three_subtile_groups_384_threads(pkg):
+    """K = 256 -> N = 64, M = 150 000: cpw = 2, rep = 2, resident = 3, the largest tile 96 (above). ceil(150000 / 96) = 1563 tiles over 768
+    slots: 3 rounds, and ceil(150000 / 2304) = 66 -> 96 keeps the tile. Staging 96 x (256 / 16) = 1536 granules > MAXG 4 x 256 threads:
+    rep -> 3, 4 x 384 = 1536 fits. So 6 waves, nrep = 3."""
+    p = _plan(pkg, 150000, 256, 64)
+    assert (p.form, p.pt, p.rep, p.cpw, p.threads, p.ntiles, p.gx, p.rounds) == (pkg.I8_PW_PERSISTENT, 96, 3, 2, 384, 1563, 768, 3)
+    assert p.lds_bytes == 2 * 96 * 272 and p.maxg == 4 and p.ks == 8
+
+
+def test_pw_plan_tile_shrinks_for_short_maps(pkg):
+    """14 x 14 x 512 -> 512 (M = 196): gy = 2, per_round = 128, largest tile 64: 4 tiles, one round; ceil(196 / 128) = 2 -> 32: 7 tiles of
+    32 pixels on 7 slots instead of 4 of 64. 28 x 28 x 256 -> 256 (M = 784): largest tile 128, per_round 256, ceil(784 / 256) = 4 -> 32:
+    25 tiles. 7 x 7 x 1024 -> 1024: the 32-pixel minimum, 2 tiles. An FC on 5 images: one tile."""
+    p = _plan(pkg, 196, 512, 512)
+    assert (p.pt, p.ntiles, p.gx, p.gy, p.rounds, p.lds_bytes) == (32, 7, 7, 2, 1, 2 * 32 * 528)
+    p = _plan(pkg, 784, 256, 256)
+    assert (p.pt, p.ntiles, p.gx, p.gy, p.rounds) == (32, 25, 25, 1, 1)
+    p = _plan(pkg, 49, 1024, 1024)
+    assert (p.pt, p.ntiles, p.gx, p.gy) == (32, 2, 2, 4)
+    p = _plan(pkg, 5, 1024, 1000, f32=True)
+    assert (p.form, p.ks, p.pt, p.ntiles, p.gx, p.gy, p.out_f32) == (pkg.I8_PW_PERSISTENT, 32, 32, 1, 1, 4, 1)
+
+
+def test_pw_plan_k_in_registers_forms(pkg):
+    """The K-in-registers form i8_pw_k<ks, g>: ks = 4 / 16 / 32 for K <= 128 / <= 512 / above, K blocks of 32 ks bytes.
+    - K % 16 == 8 stages 8-byte granules, K / 8 per pixel. K = 504: 63 x 32 pixels = 2016 <= MAXG 4 x 512 threads = 2048: persistent, on
+      8 waves (N = 40: cpw = 2, rep 4). K = 520: 65 x 32 = 2080 > 2048 even at 8 waves and the smallest tile: falls through; so does
+      K = 1016 (127 x 32 = 4064). One K block of 1024 bytes each.
+    - K > 1024: K = 2048 two whole blocks, K = 1040 a 16-byte second block (g = 16), K = 1032 an 8-byte one (g = 8).
+    - operands on 8 but not 16 bytes with K % 16 == 0: K = 64 -> <4, 8>, 256 -> <16, 8>, 1024 -> <32, 8>, one block each.
+    M = 997 is 8 tiles of 128; N = 40 two chunks; 2 x 256 CUs / 8 tiles asks for more groups than chunks: cpg = 1, 2 groups, 16 workgroups."""
+    p = _plan(pkg, 997, 504, 40)
+    assert (p.form, p.g, p.pt, p.threads, p.rep, p.ks) == (pkg.I8_PW_PERSISTENT, 8, 32, 512, 4, 16)
+    for k, on16, ks, g, nkb in ((520, True, 32, 8, 1), (1016, True, 32, 8, 1), (2048, True, 32, 16, 2), (1040, True, 32, 16, 2),
+                                (1032, True, 32, 8, 2), (64, False, 4, 8, 1), (256, False, 16, 8, 1), (1024, False, 32, 8, 1),
+                                (2048, False, 32, 8, 2)):
+        for f32 in (False, True):
+            p = _plan(pkg, 997, k, 40, on16=on16, f32=f32)
+            assert (p.form, p.ks, p.g, p.nkb, p.out_f32) == (pkg.I8_PW_KREG, ks, g, nkb, int(f32)), k
+            assert (p.pt, p.threads, p.ntiles, p.nchunks, p.cpg, p.ngroups, p.gx, p.gy, p.lds_bytes) == (128, 256, 8, 2, 1, 2, 16, 1, 0)
+    # many tiles: 2 * 256 / 4000 -> one group of all chunks
+    p = _plan(pkg, 512000, 2048, 1000)
+    assert (p.ntiles, p.nchunks, p.cpg, p.ngroups, p.gx) == (4000, 32, 32, 1, 4000)
+    # the grid's 2^31 - 1 workgroups; shapes the C-ABI refuses
+    host = pkg.host_lib()
+    q = pkg.I8PwPlan()
+    assert host.mbn_i8_pw_plan(1 << 40, 2048, 8, 256, 1, 0, C.byref(q)) == pkg.EUNSUPPORTED
+    for bad in ((0, 64, 64, 256), (5, 12, 64, 256), (5, 0, 64, 256), (5, 65544, 64, 256), (5, 64, 0, 256), (5, 64, 64, 0)):
+        assert host.mbn_i8_pw_plan(*bad, 1, 0, C.byref(q)) == pkg.EINVAL, bad
+    assert host.mbn_i8_pw_plan(5, 64, 64, 256, 1, 0, None) == pkg.EINVAL
+
+
+def test_pw_plan_aligned_small_k_forms(pkg):
+    """Which K-in-registers forms operands on 16 bytes with K <= 1024, K % 16 == 0 can reach. <4, 16> (K <= 128): none in the sweep.
+    <16, 16> and <32, 16> with one K block: reached when the chunks per workgroup are 3, 5, 6 or 7 (N in 65..96 or 129..224, and wherever
+    else ceil(chunks / gy) is one of them) and a tile needs more staging threads than the waves have: `rep` is raised while cpw * rep < 8,
+    lands on 9, 10, 12 or 14 waves, and the plan falls through instead of shrinking the tile. K = 256 -> N = 160 on 256 CUs: cpw = 5, resident 2, largest tile 128, per_round
+    512: up to M = 32 768 the tile is <= 64 (64 x 16 = 1024 granules <= 4 x 320 threads), at M = 32 769 it is 96 (1536 > 1280)."""
+    assert _plan(pkg, 32768, 256, 160).form == pkg.I8_PW_PERSISTENT
+    p = _plan(pkg, 32769, 256, 160)
+    assert (p.form, p.ks, p.g, p.nkb) == (pkg.I8_PW_KREG, 16, 16, 1)
+    p = _plan(pkg, 1, 1024, 160)                  # K = 1024: 32 x 64 = 2048 granules > 4 x 320 at any M
+    assert (p.form, p.ks, p.g, p.nkb) == (pkg.I8_PW_KREG, 32, 16, 1)
+    seen = set()
+    for cus in (1, 8, 104, 256, 304):
+        for k in range(16, 1025, 16):
+            for n in (8, 40, 64, 96, 136, 160, 192, 224, 264, 520, 1000, 1024, 1320):
+                for m in (1, 33, 997, 4097, 32769, 150000, 1 << 22):
+                    p = _plan(pkg, m, k, n, cus)
+                    if p.form == pkg.I8_PW_KREG:
+                        seen.add((p.ks, p.g))
+                        chunks = (n + 31) // 32
+                        gy = (chunks + 7) // 8
+                        assert (chunks + gy - 1) // gy in (3, 5, 6, 7), (m, k, n, cus)
+    assert seen == {(16, 16), (32, 16)}
+
+
+def test_pw_plan_invariants_over_a_sweep(pkg):
+    """Every persistent plan: whole 32-pixel sub-tiles, at most 8 waves made of cpw x rep, the staging bound the kernel's MAXG registers
+    rely on, both LDS buffers within 160 KB, no workgroup without a first tile, the tiles cover M, and the KS instantiation holds K.
+    Every K-in-registers plan: groups cover the chunks, grid = tiles x groups."""
+    n_p = n_k = 0
+    for cus in (1, 8, 104, 256, 304):
+        for k in list(range(8, 257, 8)) + [384, 504, 512, 520, 768, 1000, 1016, 1024, 1032, 1040, 2048, 4104, 65536]:
+            for n in (1, 3, 8, 24, 40, 64, 100, 128, 160, 256, 264, 1000, 1001, 1024, 2048):
+                for m in (1, 31, 32, 33, 196, 997, 3136, 8209, 32777, 65559, 150000, 417793, (1 << 22) + 37):
+                    for on16 in (True, False):
+                        p = _plan(pkg, m, k, n, cus, on16)
+                        chunks = (n + 31) // 32
+                        if p.form == pkg.I8_PW_PERSISTENT:
+                            n_p += 1
+                            waves = p.cpw * p.rep
+                            assert k <= 1024 and (on16 or k % 16) and p.g == (16 if k % 16 == 0 else 8)
+                            assert p.pt % 32 == 0 and 32 <= p.pt <= 1024
+                            assert 1 <= waves <= 8 and p.threads == 64 * waves      # (rep may exceed pt / 32: those waves only stage)
+                            assert p.pt * (k // p.g) <= p.maxg * p.threads and p.maxg == (8 if p.ks <= 4 else 4)
+                            assert p.kp % 32 == 0 and k <= p.kp < k + 32 and p.kp // 32 <= p.ks < 2 * max(1, p.kp // 32)
+                            assert p.lds_bytes == 2 * p.pt * (p.kp + 16) <= 160 * 1024
+                            assert p.ntiles == -(-m // p.pt) and 1 <= p.gx <= p.ntiles and p.gx <= p.per_round
+                            assert p.gy * p.cpw >= chunks > (p.gy - 1) * p.cpw
+                        else:
+                            n_k += 1
+                            assert p.form == pkg.I8_PW_KREG and p.pt == 128 and p.threads == 256 and p.lds_bytes == 0
+                            assert p.ks == (4 if k <= 128 else 16 if k <= 512 else 32) and p.nkb == -(-k // (32 * p.ks))
+                            assert p.g == (16 if (k % 16 == 0 and on16) else 8)
+                            assert p.nchunks == chunks and p.ngroups * p.cpg >= chunks > (p.ngroups - 1) * p.cpg
+                            assert p.ntiles == -(-m // 128) and p.gx == p.ntiles * p.ngroups
+    assert n_p > 20000 and n_k > 10000
+
+
+# ------------------------------------------------------------------------------------------------------------ conv1 on grid inputs
+
+def test_conv1_grid_inputs_are_exact_in_fp32():
+    """The gate of tests/test_int8_gpu.py::test_conv1_bit_exact_on_grid_inputs, on the very inputs it builds: max sum |term| in grid units
+    (2^-13) stays below 2^24, so the fp32 sum is exact in any order and with any fusing; shown as well by summing the 27 terms in fp32 forwards
+    and backwards against float64. The worst case the builder can produce is 27 x 2^7 x 2^7 = 442 368 units. Each case reaches both clamps and
+    leaves at least half of its outputs between them."""
+    assert 27 * (1 << ref.CONV1_IMG_BITS) * (2 << ref.CONV1_TAP_BITS) < 2 ** 24
+    for c in ref.CONV1_CHANNELS:
+        for stride in (1, 2):
+            for h, w in ref.CONV1_MAPS:
+                for pads in ref.CONV1_PADS:
+                    rng = np.random.default_rng(c * 100 + stride * 10 + h)
+                    img, wk, mult, bias = ref.conv1_exact_inputs(rng, 2, h, w, c)
+                    assert np.abs(img).max() <= 1 and np.abs(wk).max() <= 2
+                    assert ref.conv1_grid_units(img, wk, stride, *pads) < 2 ** 24
+                    got = ref.conv1_exact(img, wk, mult, bias, stride, *pads)
+                    lo, hi = (got == 0).mean(), (got == 255).mean()
+                    assert lo > 0 and hi > 0 and lo + hi <= 0.5, (c, stride, h, w, pads, lo, hi)
+    # one case term by term: fp32 sums in both orders equal the float64 sum
+    rng = np.random.default_rng(1)
+    img, wk, _, _ = ref.conv1_exact_inputs(rng, 1, 9, 7, 8)
+    xp = np.zeros((11, 9, 3), np.float32)
+    xp[1:10, 1:8] = img[0]
+    for oy, ox in ((0, 0), (4, 3), (8, 6)):
+        terms = (xp[oy:oy + 3, ox:ox + 3].reshape(27, 1) * wk.reshape(27, 8)).astype(np.float32)      # each product exact
+        fwd = np.zeros(8, np.float32)
+        bwd = np.zeros(8, np.float32)
+        for t in range(27):
+            fwd = (fwd + terms[t]).astype(np.float32)
+            bwd = (bwd + terms[26 - t]).astype(np.float32)
+        want = ref.conv1_acc(img, wk, 1)[0, oy, ox]
+        assert np.array_equal(fwd.astype(np.float64), want) and np.array_equal(bwd.astype(np.float64), want)

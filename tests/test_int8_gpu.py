@@ -2,7 +2,8 @@
 
 Layer kernels (csrc/mbn_i8.hip) against the numpy integer reference bit for bit: every depthwise geometry of the network at three
 widths plus odd maps, every pointwise (K, N) pair with a ragged pixel count, the FC with fp32 output, an exact GEMM with an asymmetric
-filter, the pool; conv1 against float64 within one step. The net runner: every layer of a kept forward recomputed from the device's
+filter, the pool; conv1 bit for bit on grid inputs whose fp32 sum is exact, and against float64 within one step otherwise; the pointwise forms and loop passes
+chosen from the launch plan (mbn_i8_pw_plan) for the device's CU count. The net runner: every layer of a kept forward recomputed from the device's
 previous layer, equivalences of streams / graph / last_layer, raw uint8 input, classify, the launch list, the C-ABI's error paths, and
 the accuracy against the fp32 oracle. The new kernels index in 64 bits (no buffer descriptors), so they have no 32-bit offset guard."""
 import ctypes as C
@@ -144,6 +145,195 @@ def test_exact_gemm_with_asymmetric_filter(pkg, ctx):
     assert np.array_equal(got, want.astype(np.float32))
 
 
+# ---- the pointwise launch plan (mbn_i8_pw_plan, host/mbn_envelope.c: what mbn_launch_i8_pointwise launches) decides each case's M, so the
+# ---- cases below hold their intent on a device of any CU count
+
+SENTINEL, GUARD = 0xA5, 4096
+
+
+def _cus(ctx):
+    n = C.c_int()
+    assert ctx.lib.mbn_device_cus(ctx.h, C.byref(n)) == 0 and n.value > 0
+    return n.value
+
+
+def _plan_str(p, pkg):
+    if p.form == pkg.I8_PW_PERSISTENT:
+        return "persistent KS=%d G=%d pt=%d threads=%d ntiles=%d grid=%dx%d tiles/wg=%d..%d" % (
+            p.ks, p.g, p.pt, p.threads, p.ntiles, p.gx, p.gy, p.ntiles // p.gx, -(-p.ntiles // p.gx))
+    return "k-in-registers KS=%d G=%d nkb=%d pt=128 ntiles=%d cpg=%d ngroups=%d grid=%d" % (p.ks, p.g, p.nkb, p.ntiles, p.cpg, p.ngroups, p.gx)
+
+
+def _run_pw_checked(pkg, ctx, x, wk, mult, bias, f32, off_in=0, off_w=0, off_out=0, off_par=0):
+    """One mbn_pointwise call (operands at the given byte offsets inside their allocations) against int8_ref.pw in row blocks, bit for
+    bit; the output is filled with a sentinel first and the bytes after it must keep it."""
+    m, k = x.shape
+    nout = wk.shape[0]
+    es = 4 if f32 else 1
+    out_bytes = m * nout * es
+    dx, dw_, dout = ctx.alloc(x.nbytes + 16), ctx.alloc(wk.nbytes + 16), ctx.alloc(out_bytes + 16 + GUARD)
+    dm, db = ctx.alloc(mult.nbytes + 16), ctx.alloc(bias.nbytes + 16)
+    try:
+        for d, off, a in ((dx, off_in, x), (dw_, off_w, wk), (dm, off_par, mult), (db, off_par, bias)):
+            pkg._chk(ctx.lib.mbn_upload(ctx.h, d.ptr + off, a.ctypes.data, a.nbytes))
+        pkg._chk(ctx.lib.mbn_memset(ctx.h, dout.ptr, SENTINEL, dout.nbytes))
+        e = _ext(pkg, 1, dm.ptr + off_par, db.ptr + off_par, act=pkg.ACT_NONE if f32 else None, io=pkg.IO_OUT_F32 if f32 else 0)
+        ctx.pointwise(dout.ptr + off_out, dx.ptr + off_in, dw_.ptr + off_w, 1, m, k, nout, e)
+        ctx.sync()
+        step = max(1, (64 << 20) // (nout * 8))
+        got = np.empty((step, nout), np.float32 if f32 else np.uint8)
+        mean = 0.0
+        for i, want in ref.pw_blocks(x, wk, mult, bias, out_f32=f32, block=step):
+            g = got[:len(want)]
+            pkg._chk(ctx.lib.mbn_download(ctx.h, g.ctypes.data, dout.ptr + off_out + i * nout * es, g.nbytes))
+            same = g.view(np.uint32) == want.view(np.uint32) if f32 else g == want
+            assert same.all(), "rows %d..%d: %d elements differ, first at row %d" % (
+                i, i + len(want) - 1, (~same).sum(), i + int(np.argmax(~same.all(axis=1))))
+            mean += float(g.sum(dtype=np.float64))
+        edge = np.empty(off_out + 0, np.uint8), np.empty(16 - off_out + GUARD, np.uint8)
+        if off_out:
+            pkg._chk(ctx.lib.mbn_download(ctx.h, edge[0].ctypes.data, dout.ptr, off_out))
+        pkg._chk(ctx.lib.mbn_download(ctx.h, edge[1].ctypes.data, dout.ptr + off_out + out_bytes, len(edge[1])))
+        assert np.all(edge[0] == SENTINEL) and np.all(edge[1] == SENTINEL), "stores outside the output"
+        return mean / (m * nout)
+    finally:
+        for b in (dx, dw_, dout, dm, db):
+            b.free()
+
+
+def _pw_inputs(seed, m, k, nout, f32):
+    rng = np.random.default_rng(seed)
+    x = rng.integers(0, 256, (m, k), dtype=np.uint8)
+    wk = rng.integers(-127, 128, (nout, k), dtype=np.int8)
+    mult = rng.uniform(1e-5, 1e-4, nout).astype(np.float32) if f32 else rng.uniform(0.2 / k, 0.9 / k, nout).astype(np.float32)
+    bias = rng.uniform(-40, 60, nout).astype(np.float32)
+    return x, wk, mult, bias
+
+
+def _multipass_m(pkg, cus, k, nout, f32, threads=None):
+    """The smallest ragged M (searched from the plan) at which some workgroups of the persistent form walk three tiles and some two, and the
+    last tile is part-filled with a part-filled 32-pixel sub-tile."""
+    def ok(m, ragged):
+        p = pkg.i8_pw_plan(m, k, nout, cus, True, f32)
+        good = p.form == pkg.I8_PW_PERSISTENT and p.ntiles > 2 * p.gx and (threads is None or p.threads == threads)
+        return good and (not ragged or (p.ntiles % p.gx != 0 and m % p.pt % 32 != 0))
+    lo, hi = 1, 64
+    while not ok(hi, False):
+        lo, hi = hi, hi * 2
+        assert hi < 1 << 26, "no multi-pass M for %d -> %d" % (k, nout)
+    while hi - lo > 1:                                # first M past two tiles per workgroup (the rule is monotone there)
+        mid = (lo + hi) // 2
+        lo, hi = (lo, mid) if ok(mid, False) else (mid, hi)
+    m = hi
+    while not ok(m, True):
+        m += 1
+        assert m < hi + 100000
+    return m
+
+
+def _assert_multipass(pkg, p, m):
+    assert p.form == pkg.I8_PW_PERSISTENT
+    assert p.ntiles > 2 * p.gx, "no workgroup walks three tiles"
+    assert p.ntiles % p.gx != 0, "every workgroup walks the same number of tiles"
+    assert m % p.pt != 0 and (m % p.pt) % 32 != 0, "the last tile is whole, or made of whole sub-tiles"
+
+
+def _assert_distinct_tiles(x, pt):
+    """No two tiles of the input are equal (their first rows already differ), so a tile read from the wrong buffer or pass cannot pass."""
+    first = x[::pt]
+    assert len(np.unique(first, axis=0)) == len(first)
+
+
+# (K, N, fp32 output): every KS instantiation of i8_pw2_k on the fewest slots per column group (N = 1024; the FC's N = 1000, whose last chunk
+# holds 8 channels, rows on the aligned float4 path), one N with N & 3 != 0 (scalar fp32 stores), and K = 24: 8-byte staging granules, a k step
+# whose LDS bytes 24..31 are never written (they meet zeroed filter bytes)
+_MULTIPASS = [(k, 1024, False) for k in (32, 64, 128, 256, 512, 1024)] + [(k, 1000, True) for k in (32, 64, 128, 256, 512, 1024)] + \
+             [(1024, 1001, True), (24, 1024, False), (24, 1000, True)]
+
+
+@pytest.mark.parametrize("k,nout,f32", _MULTIPASS)
+def test_pointwise_persistent_two_and_three_tiles_per_workgroup(pkg, ctx, k, nout, f32):
+    """i8_pw2_k past its first tile: the fetch(next) / put(cur ^ 1) / rotation half of the loop, a ragged last pass (some workgroups stop a
+    tile earlier, so the run ends on either buffer) and a last tile with rows p >= m."""
+    cus = _cus(ctx)
+    m = _multipass_m(pkg, cus, k, nout, f32)
+    p = pkg.i8_pw_plan(m, k, nout, cus, True, f32)
+    _assert_multipass(pkg, p, m)
+    assert p.ks == max(1, k // 32) and p.g == (16 if k % 16 == 0 else 8) and p.out_f32 == int(f32)
+    print("pw %d -> %d %s m=%d: %s" % (k, nout, "f32" if f32 else "u8", m, _plan_str(p, pkg)))
+    x, wk, mult, bias = _pw_inputs(k + nout, m, k, nout, f32)
+    _assert_distinct_tiles(x, p.pt)
+    mean = _run_pw_checked(pkg, ctx, x, wk, mult, bias, f32)
+    assert f32 or 0 < mean < 255
+
+
+@pytest.mark.parametrize("f32", [False, True])
+def test_pointwise_persistent_three_subtile_groups_multipass(pkg, ctx, f32):
+    """K = 256 -> N = 64 at large M: 384 threads, nrep = 3 (a wave's sub-tiles are sub0, sub0 + 96: one per 96-pixel tile), multi-pass."""
+    cus = _cus(ctx)
+    k, nout = 256, 64
+    m = _multipass_m(pkg, cus, k, nout, f32, threads=384)
+    p = pkg.i8_pw_plan(m, k, nout, cus, True, f32)
+    _assert_multipass(pkg, p, m)
+    assert (p.threads, p.cpw, p.rep, p.pt) == (384, 2, 3, 96)
+    print("pw 256 -> 64 %s m=%d: %s" % ("f32" if f32 else "u8", m, _plan_str(p, pkg)))
+    x, wk, mult, bias = _pw_inputs(384 + f32, m, k, nout, f32)
+    _assert_distinct_tiles(x, p.pt)
+    _run_pw_checked(pkg, ctx, x, wk, mult, bias, f32)
+
+
+def test_pointwise_output_on_8_bytes_with_n_multiple_of_16(pkg, ctx):
+    """Output at 8 mod 16 with N % 16 == 0 (inputs aligned): full16 is false, so whole chunks take the 4-byte store path."""
+    m, k, nout = 301, 64, 48
+    p = pkg.i8_pw_plan(m, k, nout, _cus(ctx), True, False)
+    assert p.form == pkg.I8_PW_PERSISTENT and p.ntiles <= p.gx
+    x, wk, mult, bias = _pw_inputs(48, m, k, nout, False)
+    assert 0 < _run_pw_checked(pkg, ctx, x, wk, mult, bias, False, off_out=8) < 255
+
+
+# (name, K, operand offset, N, M (None: from the plan), form expected: (KS, G, K blocks)). N = 72: three chunks, the last with 8 channels;
+# M = 301: three 128-pixel tiles, the last ragged, and with so few tiles every chunk is a column group of its own (cpg = 1)
+_KREG = [
+    ("16x8", 256, 8, 72, 301, (16, 8, 1)),                      # K % 16 == 0 on 8-byte operands
+    ("16x8_two_chunks_per_group", 256, 8, 72, None, (16, 8, 1)),   # enough tiles that a workgroup loops over two chunks (cpg = 2)
+    ("32x8_one_block", 1024, 8, 72, 301, (32, 8, 1)),
+    ("32x8_k520", 520, 0, 72, 301, (32, 8, 1)),                 # K % 16 == 8 above the persistent form's staging bound
+    ("32x8_k1016", 1016, 0, 72, 301, (32, 8, 1)),
+    ("32x16_two_blocks", 2048, 0, 72, 301, (32, 16, 2)),
+    ("32x16_k1040", 1040, 0, 72, 301, (32, 16, 2)),             # a 16-byte second block
+    ("32x8_k1032", 1032, 0, 72, 301, (32, 8, 2)),               # an 8-byte second block
+    ("32x8_k1032_n70", 1032, 0, 70, 301, (32, 8, 2)),           # N & 3 != 0 (fp32 output only: scalar stores)
+    ("16x16_cpw5", 256, 0, 136, None, (16, 16, 1)),             # aligned K <= 1024 that the persistent form gives up: 5 chunks per workgroup
+    ("32x16_cpw5", 1024, 0, 136, 301, (32, 16, 1)),
+]
+
+
+@pytest.mark.parametrize("case,f32", [(c, f) for c in _KREG for f in (False, True) if f or c[3] % 8 == 0],
+                         ids=lambda v: v[0] if isinstance(v, tuple) else ("f32" if v else "u8"))
+def test_pointwise_k_in_registers_forms(pkg, ctx, case, f32):
+    """Every reachable instantiation of i8_pw_k, uint8 and fp32 output, each asserted from the plan to be the one that runs."""
+    name, k, off, nout, m, form = case
+    cus = _cus(ctx)
+    on16 = off % 16 == 0
+    if m is None and name.startswith("16x16"):        # the first M the persistent form gives up, made ragged
+        m = 1
+        while pkg.i8_pw_plan(m, k, nout, cus, on16, f32).form != pkg.I8_PW_KREG:
+            m += 128
+            assert m < 1 << 22
+        m += 45
+    elif m is None:                                   # tiles > 2 CUs / 2: two column groups over three chunks
+        m = 128 * (cus + 2) + 45
+    p = pkg.i8_pw_plan(m, k, nout, cus, on16, f32)
+    assert (p.form, p.ks, p.g, p.nkb) == (pkg.I8_PW_KREG,) + form, _plan_str(p, pkg)
+    assert p.ngroups > 1 and m % 128 % 32 != 0 and nout % 32 != 0
+    if "two_chunks" in name:
+        assert p.cpg == 2 and p.ngroups == 2
+    print("pw %s %s m=%d: %s" % (name, "f32" if f32 else "u8", m, _plan_str(p, pkg)))
+    x, wk, mult, bias = _pw_inputs(k + nout + off, m, k, nout, f32)
+    mean = _run_pw_checked(pkg, ctx, x, wk, mult, bias, f32, off_in=off, off_w=off)
+    assert f32 or 0 < mean < 255
+
+
 @pytest.mark.parametrize("shape", [(2, 7, 7, 1024), (3, 4, 4, 256), (1, 5, 3, 8), (4, 1, 1, 64)])
 def test_pool_bit_exact(pkg, ctx, shape):
     n, h, w, c = shape
@@ -178,6 +368,121 @@ def test_conv1_within_one_step(pkg, ctx, u8in):
     yc = np.clip(y, 0, 255)
     assert np.all(np.abs(yc[diff] - (np.floor(yc[diff]) + 0.5)) < 2.0 ** -10), "mismatch away from a half-integer"
     assert diff.mean() < 1e-3 and 10 < got.mean() < 245
+
+
+_CONV1_MAPS, _CONV1_PADS = ref.CONV1_MAPS, ref.CONV1_PADS
+
+
+def _run_conv1(pkg, ctx, src, wk, mult, bias, stride, pads, u8in):
+    n, h, w = src.shape[:3]
+    c = wk.shape[-1]
+    ho, wo = (h + stride - 1) // stride, (w + stride - 1) // stride
+    nbytes = n * ho * wo * c
+    dx, dw_, dm, db, dout = ctx.to_device(src), ctx.to_device(wk), ctx.to_device(mult), ctx.to_device(bias), ctx.alloc(nbytes + GUARD)
+    try:
+        pkg._chk(ctx.lib.mbn_memset(ctx.h, dout.ptr, SENTINEL, nbytes + GUARD))
+        e = _ext(pkg, n, dm.ptr, db.ptr, io=pkg.IO_IN_U8 if u8in else 0, cin=3)
+        if pads[0] is not None:
+            e.pad_top, e.pad_left = pads
+        ctx.convolute(dout.ptr, dx.ptr, None, None, dw_.ptr, h, w, 3, stride, c, e)
+        ctx.sync()
+        assert np.all(dout.download((nbytes + GUARD,), np.uint8)[nbytes:] == SENTINEL), "stores past the output"
+        return dout.download((n, ho, wo, c), np.uint8)
+    finally:
+        for b in (dx, dw_, dm, db, dout):
+            b.free()
+
+
+@pytest.mark.parametrize("stride", [1, 2])
+@pytest.mark.parametrize("c", ref.CONV1_CHANNELS)
+def test_conv1_bit_exact_on_grid_inputs(pkg, ctx, c, stride):
+    """fp32-input conv1 bit for bit on inputs whose 27-term sum is exact in fp32 (int8_ref.conv1_exact_inputs): every NG (C = 8, 24: 1 with
+    blockIdx.y up to 2; 16, 48: 2; 32: 4), both strides, three maps, SAME and explicit pads; each case reaches both clamps and the interior."""
+    for h, w in _CONV1_MAPS:
+        for pads in _CONV1_PADS:
+            rng = np.random.default_rng(c * 100 + stride * 10 + h)
+            img, wk, mult, bias = ref.conv1_exact_inputs(rng, 2, h, w, c)
+            assert ref.conv1_grid_units(img, wk, stride, *pads) < 2 ** 24
+            got = _run_conv1(pkg, ctx, img, wk, mult, bias, stride, pads, False)
+            want = ref.conv1_exact(img, wk, mult, bias, stride, *pads)
+            what = "conv1 C=%d s%d %dx%d pads %s" % (c, stride, h, w, pads)
+            assert np.array_equal(got, want), "%s: %d of %d differ" % (what, (got != want).sum(), got.size)
+            lo, hi = (got == 0).mean(), (got == 255).mean()
+            assert lo > 0 and hi > 0 and lo + hi <= 0.5, "%s: shares at 0 / 255: %.3f / %.3f" % (what, lo, hi)
+
+
+@pytest.mark.parametrize("stride", [1, 2])
+@pytest.mark.parametrize("c", ref.CONV1_CHANNELS)
+def test_conv1_u8_input_within_one_step_every_form(pkg, ctx, c, stride):
+    """Raw uint8 input (normalised in the kernel, so the sum is not exact) across the same channel counts, strides, maps and pads: within one
+    step of the float64 value, different only at its half-integers."""
+    for h, w in _CONV1_MAPS:
+        for pads in _CONV1_PADS:
+            rng = np.random.default_rng(c * 100 + stride * 10 + h + 1)
+            raw = rng.integers(0, 256, (2, h, w, 3), dtype=np.uint8)
+            wk = (rng.standard_normal((3, 3, 3, c)) * 0.4).astype(np.float32)
+            mult = rng.uniform(20, 60, c).astype(np.float32)
+            bias = rng.uniform(-30, 90, c).astype(np.float32)
+            got = _run_conv1(pkg, ctx, raw, wk, mult, bias, stride, pads, True)
+            y = ref.conv1_y(raw.astype(np.float64) / 127.5 - 1.0, wk, mult, bias, stride, *pads)
+            if got.size >= 10000:
+                ref.assert_conv1_one_step(got, y, "conv1 u8 C=%d s%d %dx%d pads %s" % (c, stride, h, w, pads))
+            else:                                       # a 5 x 3 map: too few outputs for the mismatch share to mean anything
+                d = got.astype(np.int64) != np.clip(np.rint(y), 0, 255)
+                yc = np.clip(y, 0, 255)
+                assert np.abs(got - np.clip(np.rint(y), 0, 255)).max() <= 1
+                assert np.all(np.abs(yc[d] - (np.floor(yc[d]) + 0.5)) < 2.0 ** -10)
+            assert 10 < got.mean() < 245
+
+
+# ------------------------------------------------------------------------------------------------- depthwise: pads, map sizes, pointers
+
+@pytest.mark.parametrize("stride", [1, 2])
+@pytest.mark.parametrize("pads", [(0, 1), (1, 0)])
+def test_depthwise_explicit_pads_and_input_map(pkg, ctx, stride, pads):
+    """Explicit pads with pad_top != pad_left, on an input map that is not rows * stride (one row and three columns more, one column less)."""
+    c = 24
+    for ho, wo, h, w in ((17, 13, 17 * stride + 1, 13 * stride + 3), (9, 13, 9 * stride, 13 * stride - 1)):
+        rng = np.random.default_rng(ho + stride + pads[0])
+        x = rng.integers(0, 256, (2, h, w, c), dtype=np.uint8)
+        wk = rng.integers(-127, 128, (3, 3, c), dtype=np.int8)
+        mult, bias, dm, db = _params(ctx, rng, c)
+        dx, dw_, dout = ctx.to_device(x), ctx.to_device(wk), ctx.alloc(2 * ho * wo * c + GUARD)
+        pkg._chk(ctx.lib.mbn_memset(ctx.h, dout.ptr, SENTINEL, dout.nbytes))
+        e = _ext(pkg, 2, dm.ptr, db.ptr, in_rows=h, in_cols=w)
+        e.pad_top, e.pad_left = pads
+        ctx.depthwise(dout.ptr, dx.ptr, dw_.ptr, ho, wo, 3, stride, c, e)
+        ctx.sync()
+        want = ref.dw(x, wk, mult, bias, stride, pads[0], pads[1], ho, wo)
+        assert np.array_equal(dout.download((2, ho, wo, c), np.uint8), want), (ho, wo, h, w)
+        assert np.all(dout.download((dout.nbytes,), np.uint8)[want.size:] == SENTINEL)
+        assert 0 < want.mean() < 255
+        for b in (dx, dw_, dout, dm, db):
+            b.free()
+
+
+@pytest.mark.parametrize("stride", [1, 2])
+def test_depthwise_interior_pointers(pkg, ctx, stride):
+    """Input, filter and output 8 bytes into their allocations, mult / bias 4 bytes into theirs."""
+    n, h, w, c = 2, 17, 13, 24
+    ho, wo = (h + stride - 1) // stride, (w + stride - 1) // stride
+    rng = np.random.default_rng(170 + stride)
+    x = rng.integers(0, 256, (n, h, w, c), dtype=np.uint8)
+    wk = rng.integers(-127, 128, (3, 3, c), dtype=np.int8)
+    mult = rng.uniform(2e-3, 8e-3, c).astype(np.float32)
+    bias = rng.uniform(-40, 60, c).astype(np.float32)
+    nbytes = n * ho * wo * c
+    dx, dw_, dm, db, dout = ctx.alloc(x.nbytes + 16), ctx.alloc(wk.nbytes + 16), ctx.alloc(4 * c + 16), ctx.alloc(4 * c + 16), ctx.alloc(nbytes + 16 + GUARD)
+    for d, off, a in ((dx, 8, x), (dw_, 8, wk), (dm, 4, mult), (db, 4, bias)):
+        pkg._chk(ctx.lib.mbn_upload(ctx.h, d.ptr + off, a.ctypes.data, a.nbytes))
+    pkg._chk(ctx.lib.mbn_memset(ctx.h, dout.ptr, SENTINEL, dout.nbytes))
+    ctx.depthwise(dout.ptr + 8, dx.ptr + 8, dw_.ptr + 8, ho, wo, 3, stride, c, _ext(pkg, n, dm.ptr + 4, db.ptr + 4, in_rows=h, in_cols=w))
+    ctx.sync()
+    raw = dout.download((dout.nbytes,), np.uint8)
+    assert np.array_equal(raw[8:8 + nbytes].reshape(n, ho, wo, c), ref.dw(x, wk, mult, bias, stride))
+    assert np.all(raw[:8] == SENTINEL) and np.all(raw[8 + nbytes:] == SENTINEL)
+    for b in (dx, dw_, dout, dm, db):
+        b.free()
 
 
 # ------------------------------------------------------------------------------------------------------------------- net runner
@@ -224,6 +529,10 @@ def test_net_every_layer_bit_exact(pkg, ctx, tmp_path, alpha, res, calibrate):
     p, _ = pkg.quantize_i8(plan, hw.blob, scales)
     prev = net.layer_output(1, n)
     assert prev.dtype == np.uint8 and 0 < prev.mean() < 255
+    l0 = plan.layer[0]
+    y = ref.conv1_y(_images(res, n, 3).astype(np.float64), hw.blob[l0.w_offset:l0.w_offset + l0.w_count].reshape(3, 3, 3, -1),
+                    q[0]["mult"], q[0]["bias"], l0.stride, l0.pad_top, l0.pad_left)
+    ref.assert_conv1_one_step(prev, y, "layer 1")
     for i in range(2, plan.n_layers + 1):
         l = plan.layer[i - 1]
         want = ref.layer_from_prev(l, q[i - 1], prev)

@@ -23,6 +23,8 @@ A new descriptor-based kernel adds its row here.
 | stride-2 input >= 512 MiB, >= 40 rows (2 rows    | mbn_f32_dw.hip:833                                 | 167 x 112^2 x 64                  | 168 x 112^2 x 64                                |
 |   per segment)                                   |                                                    |                                   |                                                 |
 | none (64-bit pointers): depthwise > 4 GiB        | mbn_f32_dw.hip (fp32, bf16x8)                      | the P-image twins                 | fp32 / bf16 at stride 1 and 2, 4.3 GB           |
+| none (64-bit pointers): int8 pointwise > 4 GiB   | mbn_i8.hip (i8_pw2_k: input; uint8 and fp32 output)| the P-row twins (int8_ref.pw)     | K 1024 -> 8, K 8 -> 1024, K 8 -> 1000 fp32      |
+| none (64-bit pointers): int8 depthwise > 4 GiB   | mbn_i8.hip (i8_dw_k<1>, <2>)                       | the P-image twins (int8_ref.dw)   | 5351 x 112^2 x 64 at stride 1 and 2, 4.3 GB     |
 | input < 4 GiB (bf16 resident tail)               | host/mbn_envelope.c:59 (mbn_tail_envelope)         | 83 885 x 10^2 x 256               | 83 887: MBN_EUNSUPPORTED                        |
 | stem / conv1 (64-bit pointers)                   | mbn_f32_stem.hip                                   | forward(7)                        | net batch 1399 (fp32 fused and unfused stem),   |
 |                                                  |                                                    |                                   |   bf16 batch 2700                               |
@@ -41,6 +43,7 @@ Host transfers go in chunks of at most 256 MiB; device buffers are freed in `fin
 import numpy as np
 import pytest
 
+import int8_ref
 from test_parity_gpu import TOL_BF16, TOL_DW, TOL_PW, assert_close, _make_net
 
 pytestmark = pytest.mark.gpu
@@ -419,6 +422,88 @@ def test_f32_depthwise_one_image_around_2e9(pkg, orc, ctx, h):
             t[y == h - 1] = ht - 1
             return t
         _check_items(ctx, d_o.ptr, h, twin, index, what)
+    finally:
+        bufs.free()
+
+
+# =========================================================================== int8 mode: no descriptors, every index 64-bit
+
+def _i8_ext(pkg, batch, dm, db, f32=False, **kw):
+    return pkg.make_ext(batch=batch, dtype=pkg.DT_I8, act=pkg.ACT_NONE if f32 else pkg.ACT_RELU6, scale=dm.ptr, shift=db.ptr,
+                        io_flags=pkg.IO_OUT_F32 if f32 else 0, **kw)
+
+
+I8_PW_CASES = [  # (name, m, K, N, fp32 output): each crosses the 2^31 and the 2^32 byte offset of the named tensor
+    ("input_over_4g", (1 << 22) + 37, 1024, 8, False),       # input 4 295 005 184 bytes
+    ("u8_output_over_4g", (1 << 22) + 37, 8, 1024, False),   # output 4 295 005 184 bytes
+    ("f32_output_over_4g", 1073780, 8, 1000, True),          # output 4 295 120 000 bytes
+]
+
+
+@pytest.mark.parametrize("case", I8_PW_CASES, ids=lambda c: c[0])
+def test_i8_pointwise_large(pkg, ctx, case):
+    """int8 pointwise on m rows with row i = base[i % P]: the P-row twin against int8_ref.pw bit for bit, every output row against the twin."""
+    _, m, cin, cout, f32 = case
+    assert m % 32 != 0 and m % P != 0 and max(m * cin, m * cout * (4 if f32 else 1)) > GIB4
+    es = 4 if f32 else 1
+    rng = np.random.default_rng(m + cin + cout)
+    x = rng.integers(0, 256, (P, cin), dtype=np.uint8)
+    f = rng.integers(-127, 128, (cout, cin), dtype=np.int8)
+    mult = (rng.uniform(1e-5, 1e-4, cout) if f32 else rng.uniform(0.2 / cin, 0.9 / cin, cout)).astype(np.float32)
+    bias = rng.uniform(-40, 60, cout).astype(np.float32)
+    bufs = _Bufs(ctx)
+    try:
+        d_f, d_m, d_b = bufs.dev(f), bufs.dev(mult), bufs.dev(bias)
+        ext = _i8_ext(pkg, 1, d_m, d_b, f32)
+        d_tx, d_to = bufs.dev(x), bufs.alloc(P * cout * es)
+        ctx.pointwise(d_to.ptr, d_tx.ptr, d_f.ptr, P, 1, cin, cout, ext)
+        ctx.sync()
+        twin = d_to.download((P, cout), np.float32 if f32 else np.uint8)
+        want = int8_ref.pw(x, f, mult, bias, out_f32=f32)
+        assert np.array_equal(_bits(twin), _bits(want)), "i8 pw twin"
+        out_bytes = m * cout * es
+        d_x, d_o = bufs.alloc(m * cin), bufs.alloc(out_bytes + GUARD)
+        _upload_periodic(ctx, d_x.ptr, x, m)
+        _fill(ctx, d_o, out_bytes + GUARD)
+        ctx.pointwise(d_o.ptr, d_x.ptr, d_f.ptr, m, 1, cin, cout, ext)
+        ctx.sync()
+        what = "i8 pw m=%d %d->%d%s" % (m, cin, cout, " fp32" if f32 else "")
+        _check_guard(ctx, d_o, out_bytes, what)
+        _check_periodic(ctx, d_o.ptr, m, twin, what)
+    finally:
+        bufs.free()
+
+
+@pytest.mark.parametrize("stride", [1, 2], ids=["s1_over_4g", "s2_over_4g"])
+def test_i8_depthwise_large(pkg, ctx, stride):
+    """int8 depthwise on 5351 images of 112 x 112 x 64 (input 4 295 868 416 bytes; the stride-1 output as large) with image i = base[i % P]:
+    the P-image twin against int8_ref.dw bit for bit, every output image against the twin."""
+    n, h, ch = 5351, 112, 64
+    assert n * h * h * ch > GIB4 and n % P != 0
+    oh = (h + stride - 1) // stride
+    rng = np.random.default_rng(n + stride)
+    x = rng.integers(0, 256, (P, h, h, ch), dtype=np.uint8)
+    f = rng.integers(-127, 128, (3, 3, ch), dtype=np.int8)
+    mult = rng.uniform(2e-3, 8e-3, ch).astype(np.float32)
+    bias = rng.uniform(-40, 60, ch).astype(np.float32)
+    bufs = _Bufs(ctx)
+    try:
+        d_f, d_m, d_b = bufs.dev(f), bufs.dev(mult), bufs.dev(bias)
+        ext = lambda nb: _i8_ext(pkg, nb, d_m, d_b, in_rows=h, in_cols=h)
+        d_tx, d_to = bufs.dev(x), bufs.alloc(P * oh * oh * ch)
+        ctx.depthwise(d_to.ptr, d_tx.ptr, d_f.ptr, oh, oh, 3, stride, ch, ext(P))
+        ctx.sync()
+        twin = d_to.download((P, oh, oh, ch), np.uint8)
+        assert np.array_equal(twin, int8_ref.dw(x, f, mult, bias, stride)), "i8 dw twin"
+        out_bytes = n * oh * oh * ch
+        d_x, d_o = bufs.alloc(n * h * h * ch), bufs.alloc(out_bytes + GUARD)
+        _upload_periodic(ctx, d_x.ptr, x, n)
+        _fill(ctx, d_o, out_bytes + GUARD)
+        ctx.depthwise(d_o.ptr, d_x.ptr, d_f.ptr, oh, oh, 3, stride, ch, ext(n))
+        ctx.sync()
+        what = "i8 dw n=%d %dx%dx%d s%d" % (n, h, h, ch, stride)
+        _check_guard(ctx, d_o, out_bytes, what)
+        _check_periodic(ctx, d_o.ptr, n, twin, what)
     finally:
         bufs.free()
 

@@ -387,6 +387,7 @@ def test_int8_every_layer_bit_exact(pkg, ctx, tmp_path, alpha, rows, cols):
     y = ref.conv1_y(imgs.astype(np.float64), hw.blob[l0.w_offset:l0.w_offset + l0.w_count].reshape(3, 3, 3, -1), q[0]["mult"], q[0]["bias"])
     want = np.clip(np.rint(y), 0, 255).astype(np.int64)
     assert np.abs(conv - want).max() <= 1 and (conv != want).mean() < 1e-3
+    ref.assert_conv1_one_step(conv, y, "layer 1")          # and the mismatches only at half-integers of y
     prev = net.layer_output(1, n)
     for i in range(2, plan.n_layers + 1):
         l = plan.layer[i - 1]
