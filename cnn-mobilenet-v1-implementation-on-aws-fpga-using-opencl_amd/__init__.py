@@ -35,6 +35,7 @@ Q_CARRY_SUM, Q_DW_PLANE0, Q_LITERAL_INDEX, Q_POOL_DIV49 = 1, 2, 4, 8
 QUIRKS_NONE, QUIRKS_KERNEL_CL = 0, 0xF
 L_CONV, L_DW, L_PW, L_POOL, L_FC = 1, 2, 3, 4, 5
 MAX_LAYERS = 32
+FIT_STRETCH, FIT_CROP = 0, 1
 
 
 class MbnError(RuntimeError):
@@ -140,6 +141,11 @@ def _declare_host(lib):
     lib.mbn_rank_fail.argtypes = [C.c_void_p]
     lib.mbn_quantize_i8.argtypes = [C.POINTER(Plan), C.c_void_p, C.c_void_p, C.POINTER(I8Params), C.c_void_p]
     lib.mbn_upsample_argmax_envelope.argtypes = [C.c_int] * 5      # mbn_envelope.h: exported, not in mbn.h
+    i32p = C.POINTER(C.c_int32)
+    lib.mbn_resize_ksize.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int]
+    lib.mbn_resize_taps.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int, i32p, i32p, i32p]
+    lib.mbn_fit_box.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float)]
+    lib.mbn_resize_envelope.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int]      # mbn_envelope.h: exported, not in mbn.h
     lib.mbn_i8_pw_plan.argtypes = [C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(I8PwPlan)]
     return lib
 
@@ -245,6 +251,10 @@ def load():
         lib.mbn_upsample_argmax_f32.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
         lib.mbn_net_forward_dense.argtypes = [vp, vp, vp, ci]
         lib.mbn_net_segment.argtypes = [vp, vp, ci, vp, vp]
+        lib.mbn_resizer_create.argtypes = [vp, ci, ci, C.POINTER(C.c_float), ci, ci, C.POINTER(vp)]
+        lib.mbn_resize_u8.argtypes = [vp, vp, vp, ci, vp]
+        lib.mbn_resizer_destroy.argtypes = [vp]
+        lib.mbn_net_resize_input.argtypes = [vp, vp, ci, ci, ci, ci, C.c_float, C.POINTER(vp)]
         lib.mbn_graph_begin.argtypes = [vp, vp]
         lib.mbn_graph_end.argtypes = [vp, vp, C.POINTER(vp)]
         lib.mbn_graph_launch.argtypes = [vp, vp, vp]
@@ -282,6 +292,41 @@ def i8_pw_plan(m, cin, op_size, num_cus, operands_on_16=True, out_f32=False, lib
     _chk((lib or host_lib()).mbn_i8_pw_plan(m, cin, op_size, num_cus, int(operands_on_16), int(out_f32), C.byref(p)),
          "i8_pw_plan(%d, %d, %d)" % (m, cin, op_size))
     return p
+
+
+def _box4(box):
+    """A box (left, upper, right, lower) as a C float[4], or None for the whole image."""
+    if box is None:
+        return None
+    return (C.c_float * 4)(*[float(np.float32(v)) for v in box])
+
+
+def resize_ksize(in_size, b0, b1, out_size, lib=None) -> int:
+    """mbn_resize_ksize: taps per output of one axis of the resize front-end (raises MbnError on a refused box)."""
+    k = (lib or host_lib()).mbn_resize_ksize(in_size, b0, b1, out_size)
+    if k < 0:
+        raise MbnError(k, "resize_ksize(%d, %r, %r, %d)" % (in_size, b0, b1, out_size))
+    return k
+
+
+def resize_taps(in_size, b0, b1, out_size, lib=None):
+    """mbn_resize_taps: (first [out_size], count [out_size], weights [out_size][ksize]) of one axis, int32."""
+    lib = lib or host_lib()
+    ks = resize_ksize(in_size, b0, b1, out_size, lib)
+    first, count, weights = np.zeros(out_size, np.int32), np.zeros(out_size, np.int32), np.zeros((out_size, ks), np.int32)
+    i32p = C.POINTER(C.c_int32)
+    rc = lib.mbn_resize_taps(in_size, b0, b1, out_size, first.ctypes.data_as(i32p), count.ctypes.data_as(i32p), weights.ctypes.data_as(i32p))
+    if rc < 0:
+        raise MbnError(rc, "resize_taps")
+    return first, count, weights
+
+
+def fit_box(in_rows, in_cols, out_rows, out_cols, fit=FIT_CROP, crop_fraction=1.0, lib=None) -> np.ndarray:
+    """mbn_fit_box: (left, upper, right, lower) as float32 for FIT_STRETCH (the whole image) or FIT_CROP (the centred box with the output's
+    aspect ratio, shrunk by crop_fraction)."""
+    box = (C.c_float * 4)()
+    _chk((lib or host_lib()).mbn_fit_box(in_rows, in_cols, out_rows, out_cols, fit, crop_fraction, box), "fit_box")
+    return np.array(box[:], np.float32)
 
 
 def declared_symbols():
@@ -443,8 +488,10 @@ class Context:
 
     def close(self):
         if self.h:
-            self.lib.mbn_shutdown(self.h)
+            self.lib.mbn_shutdown(self.h)          # frees the resizers still alive as well: their handles are dead from here on
             self.h = None
+            for r in getattr(self, "_resizers", []):
+                r.h = None
 
     # ---- layer calls: positional arguments are kernel.cl's ----
     def convolute(self, out, inp_r, inp_g, inp_b, filt, rows, cols, filtersize, stride, op_size, ext=None):
@@ -473,6 +520,29 @@ class Context:
 
     def __exit__(self, *a):
         self.close()
+
+
+class Resizer:
+    """mbn_resizer_create / mbn_resize_u8: uint8 HWC images [batch][in_rows][in_cols][3] -> [batch][out_rows][out_cols][3], Pillow's 8-bit bilinear
+    resize of `box` = (left, upper, right, lower) (None = the whole image), byte for byte. One geometry per handle."""
+
+    def __init__(self, ctx: Context, in_rows, in_cols, out_rows, out_cols, box=None):
+        self.ctx = ctx
+        self.shape_in, self.shape_out = (in_rows, in_cols, 3), (out_rows, out_cols, 3)
+        h = C.c_void_p()
+        _chk(ctx.lib.mbn_resizer_create(ctx.h, in_rows, in_cols, _box4(box), out_rows, out_cols, C.byref(h)), ctx.last_error())
+        self.h = h
+        if not hasattr(ctx, "_resizers"):
+            ctx._resizers = []
+        ctx._resizers.append(self)
+
+    def run(self, out_ptr, in_ptr, batch, stream=None):
+        _chk(self.ctx.lib.mbn_resize_u8(self.h, out_ptr, in_ptr, batch, stream), self.ctx.last_error())
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.mbn_resizer_destroy(self.h)
+            self.h = None
 
 
 def input_hw(res):
@@ -580,6 +650,13 @@ class Net:
     def segment(self, images_ptr, batch, labels_ptr, score_ptr=None):
         """forward_dense + bilinear upsample to the input size + argmax: int32 labels (and fp32 scores) [batch][rows][cols] (mbn_net_segment)."""
         _chk(self.ctx.lib.mbn_net_segment(self.h, images_ptr, batch, labels_ptr, score_ptr), self.ctx.last_error())
+
+    def resize_input(self, src_ptr, batch, in_rows, in_cols, fit=FIT_CROP, crop_fraction=1.0) -> int:
+        """mbn_net_resize_input: uint8 images [batch][in_rows][in_cols][3] of any size -> the net's staging buffer [batch][rows][cols][3] (its
+        device pointer is returned): the `images` of forward / classify / forward_dense / segment under set_input_u8()."""
+        p = C.c_void_p()
+        _chk(self.ctx.lib.mbn_net_resize_input(self.h, src_ptr, batch, in_rows, in_cols, fit, crop_fraction, C.byref(p)), self.ctx.last_error())
+        return p.value
 
     def set_input_u8(self, enabled=True):
         _chk(self.ctx.lib.mbn_net_set_input_u8(self.h, int(enabled)))

@@ -184,6 +184,7 @@ int mbn_shutdown(mbn_context *ctx)
     for (auto &kv : ctx->allocs) (void)hipFree((void *)kv.first);
     if (ctx->lit_ws) (void)hipFree(ctx->lit_ws);
     for (auto &kv : ctx->emul_ws) (void)hipFree(kv.second.p);
+    for (mbn_resizer *r : ctx->resizers) mbn_resizer_release(r);
     ctx->allocs.clear();
     for (hipEvent_t e : ctx->pool) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->marks) (void)hipEventDestroy(e);
@@ -819,6 +820,45 @@ int mbn_upsample_argmax_f32(mbn_context *ctx, void *labels_i32, void *score_f32,
     Scope sc(ctx, s);
     return sc.finish(mbn_launch_f32_upsample_argmax(ctx, s, (int32_t *)labels_i32, (float *)score_f32, (const float *)logits, batch, rows, cols,
                                                     classes, factor));
+}
+
+int mbn_resizer_create(mbn_context *ctx, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r)
+{
+    if (!ctx || !r) return MBN_EINVAL;
+    *r = nullptr;
+    int rc = mbn_resize_envelope(in_rows, in_cols, box, out_rows, out_cols);
+    if (rc != MBN_OK) return rc;
+    rc = mbn_resizer_build(ctx, in_rows, in_cols, box, out_rows, out_cols, r);
+    if (rc != MBN_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->resizers.push_back(*r);
+    return MBN_OK;
+}
+
+int mbn_resizer_destroy(mbn_resizer *r)
+{
+    if (!r) return MBN_OK;
+    mbn_context *ctx = r->ctx;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        for (auto it = ctx->resizers.begin(); it != ctx->resizers.end(); ++it)
+            if (*it == r) { ctx->resizers.erase(it); break; }
+    }
+    (void)hipSetDevice(ctx->device);
+    MBN_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    mbn_resizer_release(r);
+    return MBN_OK;
+}
+
+int mbn_resize_u8(mbn_resizer *r, void *out_u8, const void *in_u8, int batch, void *stream)
+{
+    if (!r || !out_u8 || !in_u8 || batch <= 0) return MBN_EINVAL;
+    if (batch > MBN_RESIZE_MAX_BATCH) return MBN_EUNSUPPORTED;
+    mbn_context *ctx = r->ctx;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    MBN_SPANS(ctx, { in_u8, 3.0 * batch * r->in_rows * r->in_cols, "resize_u8 in" }, { out_u8, 3.0 * batch * r->out_rows * r->out_cols, "resize_u8 out" });
+    Scope sc(ctx, s);
+    return sc.finish(mbn_launch_u8_resize(r, s, (uint8_t *)out_u8, (const uint8_t *)in_u8, batch));
 }
 
 int mbn_classifier_tail(mbn_context *ctx, void *topk_idx_i32, void *topk_prob_f32, void *probs, void *logits_scratch,

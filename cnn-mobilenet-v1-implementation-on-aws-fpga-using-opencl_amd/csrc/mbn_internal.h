@@ -21,6 +21,16 @@ struct mbn_emul_img {
     bool built = false;          // pw_emul_static: the image holds the split of the current filter contents
 };
 
+// mbn_resizer_create's handle (mbn_u8_resize.hip): one geometry, its tap tables on the device and the tile the host chose for it
+struct mbn_resizer {
+    mbn_context *ctx = nullptr;
+    int in_rows = 0, in_cols = 0, out_rows = 0, out_cols = 0;
+    int kx = 0, ky = 0;                          // taps per output column / row (the tables' row length)
+    int tow = 0, toh = 0, tiles_x = 0, tiles_y = 0;
+    int seg_stride = 0, stage_off = 0, tmp_off = 0, lds_bytes = 0;
+    void *tables = nullptr;                      // device: fx, cx [out_cols], fy, cy [out_rows], wx [out_cols][kx], wy [out_rows][ky], int32
+};
+
 struct mbn_context {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -41,6 +51,7 @@ struct mbn_context {
     void *lit_ws = nullptr;                      // LITERAL pointwise on v_dot4: packed int8 filter + per-channel weight sums + flag
     size_t lit_ws_bytes = 0;
     std::map<std::pair<uintptr_t, int>, mbn_emul_img> emul_ws;   // pw_emul: pre-split filter images, by (filter pointer, layout) (mbn_f32_pw_x6.hip)
+    std::vector<mbn_resizer *> resizers;         // live mbn_resizer_create handles (mbn_shutdown frees the stragglers)
     std::mutex mu;
     std::map<uintptr_t, size_t> allocs;          // buffers handed out by mbn_alloc: base address -> bytes (ordered: mbn_span_check
                                                  // finds the allocation that CONTAINS an interior pointer)
@@ -225,6 +236,10 @@ int mbn_launch_f32_softmax_topk(mbn_context *ctx, hipStream_t s, float *probs, i
 // dense head read-out (mbn_f32_dense.hip): bilinear upsample by `factor` + argmax over the classes; the shape is inside mbn_upsample_argmax_envelope
 int mbn_launch_f32_upsample_argmax(mbn_context *ctx, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows,
                                    int cols, int classes, int factor);
+// resize front-end (mbn_u8_resize.hip): the geometry is inside mbn_resize_envelope; build uploads the tables (blocking), release frees them
+int mbn_resizer_build(mbn_context *ctx, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r);
+void mbn_resizer_release(mbn_resizer *r);
+int mbn_launch_u8_resize(const mbn_resizer *r, hipStream_t s, uint8_t *out, const uint8_t *in, int batch);
 int mbn_launch_normalize(mbn_context *ctx, hipStream_t s, float *out, const uint8_t *in, size_t count, float scale,
                          float bias);
 

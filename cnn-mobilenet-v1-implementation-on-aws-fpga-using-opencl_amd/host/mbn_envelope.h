@@ -53,6 +53,14 @@ int mbn_stem_envelope(int batch, int res, int c1, int c3);
 /* mbn_upsample_argmax_f32: fp32 logits [batch][rows][cols][classes] -> labels (and scores) [batch][rows * factor][cols * factor]. factor 8, 16 or 32;
  * an image's logits and an image's output map each below 2^31 bytes (32-bit offsets inside an image; the batch goes through a 64-bit base) */
 int mbn_upsample_argmax_envelope(int batch, int rows, int cols, int classes, int factor);
+/* resize front-end (mbn_u8_resize.hip): one geometry of mbn_resizer_create. Source sides 1..8192, output sides 1..4096, at most MBN_RESIZE_MAX_KSIZE
+ * taps per axis (a 32x downscale; any upscale has 3). box = (left, upper, right, lower), NULL = the whole image. MBN_EINVAL for a non-positive
+ * size or a box mbn_resize_ksize refuses, else MBN_EUNSUPPORTED outside the limits. The batch (1..MBN_RESIZE_MAX_BATCH: grid.y) belongs to the call. */
+#define MBN_RESIZE_MAX_IN 8192
+#define MBN_RESIZE_MAX_OUT 4096
+#define MBN_RESIZE_MAX_KSIZE 67
+#define MBN_RESIZE_MAX_BATCH 65535
+int mbn_resize_envelope(int in_rows, int in_cols, const float *box, int out_rows, int out_cols);
 
 /* int8 pointwise / FC (mbn_i8.hip): the whole launch arithmetic of mbn_launch_i8_pointwise, which launches what this says and
  * computes nothing of its own. Two forms: the persistent one (i8_pw2_k<ks, 512, out_f32>: a wave keeps a 32-column chunk's filter

@@ -49,6 +49,10 @@ struct mbn_net {
     void *logits_buf;          /* mbn_net_classify: [max_batch][classes] fp32 */
     void *dense_feat;          /* mbn_net_forward_dense: the activation in front of the pool, [max_batch][h][w][channels] at fp32 size */
     void *dense_logits;        /* mbn_net_segment: [max_batch][h][w][classes] fp32 */
+    mbn_resizer *resizer;      /* mbn_net_resize_input: the resizer of the geometry below, rebuilt when it changes */
+    int rs_rows, rs_cols, rs_fit;
+    float rs_fraction;
+    void *resize_buf;          /* mbn_net_resize_input: [max_batch][rows][cols][3] uint8, the resized images */
     void *poolfc_ws;           /* workspace of mbn_pool_fc (1...4 images: pool + FC in one launch), allocated and zeroed at creation */
     size_t poolfc_ws_bytes;
     int fuse_tail;             /* mbn_net_set_fuse_tail (default 0) */
@@ -140,6 +144,8 @@ int mbn_net_destroy(mbn_net *net)
     if (net->dense_feat) mbn_free(net->ctx, net->dense_feat);
     if (net->dense_logits) mbn_free(net->ctx, net->dense_logits);
     if (net->poolfc_ws) mbn_free(net->ctx, net->poolfc_ws);
+    if (net->resizer) mbn_resizer_destroy(net->resizer);
+    if (net->resize_buf) mbn_free(net->ctx, net->resize_buf);
     for (int j = 0; j < 8; j++)
         if (net->streams[j]) mbn_stream_destroy(net->ctx, net->streams[j]);
     for (int i = 0; i < MBN_MAX_LAYERS; i++) {
@@ -885,6 +891,31 @@ int mbn_net_segment(mbn_net *net, const void *images, int batch, void *labels_i3
     rc = mbn_net_forward_dense(net, images, net->dense_logits, batch);
     if (rc != MBN_OK) return rc;
     return mbn_upsample_argmax_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, factor, NULL);
+}
+
+int mbn_net_resize_input(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, float crop_fraction, void **images_u8)
+{
+    if (!net || !src_u8 || !images_u8 || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
+    *images_u8 = NULL;
+    const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols;
+    if (fit == MBN_FIT_STRETCH) crop_fraction = 1.0f;
+    if (!net->resizer || net->rs_rows != in_rows || net->rs_cols != in_cols || net->rs_fit != fit || net->rs_fraction != crop_fraction) {
+        float box[4];
+        mbn_resizer *r = NULL;
+        int rc = mbn_fit_box(in_rows, in_cols, rows, cols, fit, crop_fraction, box);
+        if (rc == MBN_OK) rc = mbn_resizer_create(net->ctx, in_rows, in_cols, box, rows, cols, &r);
+        if (rc != MBN_OK) return rc;                          /* the resizer of the previous geometry stays */
+        if (net->resizer) mbn_resizer_destroy(net->resizer);  /* waits for the stream: a resize still running reads its tables */
+        net->resizer = r;
+        net->rs_rows = in_rows; net->rs_cols = in_cols; net->rs_fit = fit; net->rs_fraction = crop_fraction;
+    }
+    if (!net->resize_buf) {
+        int rc = mbn_alloc(net->ctx, (size_t)net->max_batch * rows * cols * 3, &net->resize_buf);
+        if (rc != MBN_OK) { net->resize_buf = NULL; return rc; }
+    }
+    int rc = mbn_resize_u8(net->resizer, net->resize_buf, src_u8, batch, NULL);
+    if (rc == MBN_OK) *images_u8 = net->resize_buf;
+    return rc;
 }
 
 int mbn_net_forward_timed(mbn_net *net, const void *images, void *logits, int batch, float *layer_ms, int n_layer_ms)

@@ -5,6 +5,9 @@
  *   mobilenet --synthetic SEED [--alpha A] [--res R] [--batch N]                              fp32, synthetic weights
  *   --res R = R x R images; --res RxC = R rows by C columns (a P6 image C wide and R high), both multiples of 32
  *   --output-stride 32 | 16 | 8: the late stride-2 depthwise layers stop subsampling, the ones behind them are dilated (mbn_plan_build_os)
+ *   --ppm F: a P6 image of ANY size up to 8192 x 8192; one that is not cols wide and rows high is resized on the device (mbn_net_resize_input: Pillow's 8-bit
+ *   bilinear). --fit crop (default: the centred box with the plan's aspect ratio) | stretch (the whole image); --crop-fraction F in (0, 1] shrinks the crop box
+ *   (0.875 = "resize to 256, crop 224"). An image of the plan's size is taken as it is
  *   --segment FILE: after the classification, the dense head (mbn_net_segment): the label map of image 0 as a binary PGM and its five most frequent labels
  *   mobilenet --literal [--weights weights_c.txt] [--image Cat_Image0.ppm] [--ref-args]      the reference's own mode
  *   mobilenet --gpus G --batch N [--steps K --warmup W --streams S --pw-emul 6] (--h5 F | --synthetic SEED)  N images sharded over G GPUs
@@ -355,11 +358,39 @@ static int write_label_map(const char *path, const int *labels, int rows, int co
     return bad;
 }
 
+/* width and height of a P6 file from its header (whitespace and # comments between the fields), so that the image buffer can be sized before
+ * mbn_read_ppm fills it. MBN_OK, MBN_EIO or MBN_EFORMAT */
+static int ppm_size(const char *path, int *width, int *height)
+{
+    FILE *fp = fopen(path, "rb");
+    if (!fp) return MBN_EIO;
+    int ok = fgetc(fp) == 'P' && fgetc(fp) == '6', v[2] = { 0, 0 };
+    for (int f = 0; ok && f < 2; f++) {
+        int c = fgetc(fp);
+        while (c == '#' || c == ' ' || c == '\t' || c == '\n' || c == '\r') {
+            if (c == '#') while (c != '\n' && c != EOF) c = fgetc(fp);
+            c = fgetc(fp);
+        }
+        int digits = 0;
+        for (; c >= '0' && c <= '9' && digits < 6; c = fgetc(fp), digits++) v[f] = v[f] * 10 + (c - '0');
+        ok = digits > 0 && digits < 6 && v[f] > 0;
+    }
+    fclose(fp);
+    if (!ok) return MBN_EFORMAT;
+    *width = v[0];
+    *height = v[1];
+    return MBN_OK;
+}
+
+#define PPM_MAX_SIDE 8192     /* the resize front-end's largest source side */
+
 int main(int argc, char **argv)
 {
     if (argc == 3 && !strcmp(argv[1], "--inspect")) return inspect_h5(argv[2]);
     if (argc == 4 && !strcmp(argv[1], "--convert")) return convert_h5(argv[2], argv[3]);
     const char *h5 = NULL, *ppm = NULL, *segment = NULL, *wfile = "weights_c.txt", *image = "Cat_Image0.ppm";
+    int fit = MBN_FIT_CROP;
+    float crop_fraction = 1.0f;
     int literal = 0, ref_args = 0, batch = 1, rows = 224, cols = 224, have_seed = 0, gpus = 0, steps = 20, warmup = 3, verify = 0, out_stride = 32;
     unsigned long long seed = 0;
     float alpha = 0.f;
@@ -378,6 +409,9 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--alpha") && i + 1 < argc) alpha = (float)atof(argv[++i]);
         else if (!strcmp(argv[i], "--output-stride") && i + 1 < argc) out_stride = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--segment") && i + 1 < argc) segment = argv[++i];
+        else if (!strcmp(argv[i], "--fit") && i + 1 < argc && (!strcmp(argv[i + 1], "crop") || !strcmp(argv[i + 1], "stretch")))
+            fit = !strcmp(argv[++i], "crop") ? MBN_FIT_CROP : MBN_FIT_STRETCH;
+        else if (!strcmp(argv[i], "--crop-fraction") && i + 1 < argc) crop_fraction = (float)atof(argv[++i]);
         else if (!strcmp(argv[i], "--synthetic") && i + 1 < argc) { seed = strtoull(argv[++i], NULL, 0); have_seed = 1; }
         else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--steps") && i + 1 < argc) steps = atoi(argv[++i]);
@@ -390,11 +424,12 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--literal")) literal = 1;
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
-            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] "
+            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F [--fit crop|stretch] [--crop-fraction F]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] "
                             "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n", argv[0]);
             return 2;
         }
     }
+    if (!(crop_fraction > 0.f) || !(crop_fraction <= 1.f)) { fprintf(stderr, "bad --crop-fraction (0 < F <= 1)\n"); return 2; }
     if (out_stride != 0 && out_stride != 8 && out_stride != 16 && out_stride != 32) { fprintf(stderr, "bad --output-stride (32, 16 or 8)\n"); return 2; }
     mbn_context *ctx = NULL;
     if (gpus > 0 && !literal) {
@@ -444,14 +479,28 @@ int main(int argc, char **argv)
     size_t img_count = (size_t)batch * img;
     unsigned char *u8 = malloc(img_count);
     if (!u8) return 1;
-    int pw = 0, ph = 0;
-    if (ppm && mbn_read_ppm(ppm, u8, &pw, &ph, rows * cols) == MBN_OK && pw == cols && ph == rows) {
+    int pw = 0, ph = 0, have = 0;
+    unsigned char *src = NULL;          /* the image at its own size */
+    if (ppm && ppm_size(ppm, &pw, &ph) == MBN_OK && pw <= PPM_MAX_SIDE && ph <= PPM_MAX_SIDE && (src = malloc((size_t)pw * ph * 3)) != NULL)
+        have = mbn_read_ppm(ppm, src, &pw, &ph, pw * ph) == MBN_OK;
+    if (have && pw == cols && ph == rows) {
+        for (int n = 0; n < batch; n++) memcpy(u8 + (size_t)n * img, src, img);
+    } else if (have) {
+        /* any other size: resized on the device into the net's staging buffer; the batch is `batch` copies of that image, as above */
+        void *d_src, *d_img;
+        CHECK(mbn_alloc(ctx, (size_t)pw * ph * 3, &d_src));
+        CHECK(mbn_upload(ctx, d_src, src, (size_t)pw * ph * 3));
+        CHECK(mbn_net_resize_input(net, d_src, 1, ph, pw, fit, crop_fraction, &d_img));
+        CHECK(mbn_download(ctx, u8, d_img, img));
+        CHECK(mbn_free(ctx, d_src));
         for (int n = 1; n < batch; n++) memcpy(u8 + (size_t)n * img, u8, img);
+        printf("image: %s, %d wide, %d high, resized to %d x %d (%s)\n", ppm, pw, ph, cols, rows, fit == MBN_FIT_CROP ? "crop" : "stretch");
     } else {
-        if (ppm) fprintf(stderr, "warning: %s is not a %d wide, %d high P6 image; using a synthetic one\n", ppm, cols, rows);
+        if (ppm) fprintf(stderr, "warning: %s is not a readable P6 image of at most %d x %d pixels; using a synthetic one\n", ppm, PPM_MAX_SIDE, PPM_MAX_SIDE);
         unsigned long long s = 0xC0FFEEULL;
         for (size_t i = 0; i < img_count; i++) { s = s * 6364136223846793005ULL + 1442695040888963407ULL; u8[i] = (unsigned char)(s >> 56); }
     }
+    free(src);
     void *d_u8, *d_logits, *d_probs, *d_arg;
     CHECK(mbn_alloc(ctx, img_count, &d_u8));
     CHECK(mbn_alloc(ctx, (size_t)batch * classes * sizeof(float), &d_logits));

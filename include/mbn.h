@@ -414,6 +414,51 @@ int mbn_classifier_tail_fused(mbn_context *ctx, void *topk_idx_i32, void *topk_p
 int mbn_normalize_u8_to_f32(mbn_context *ctx, void *out_f32, const void *in_u8, size_t count, float scale,
                             float bias, void *stream);
 
+/* Resize front-end: images of any size -> the plan's rows x cols, on device, in front of the uint8 stem (MBN_IO_IN_U8). What Keras's
+ * load_img(target_size=...) does with Pillow: an 8-bit bilinear resize of a box of the source, BYTE FOR BYTE what
+ * PIL.Image.resize((out_cols, out_rows), Image.BILINEAR, box=box) returns (tests/golden/resize_pillow.npz records Pillow's own bytes;
+ * tests/resize_ref.py restates the arithmetic in numpy). The reference has no counterpart: decode_image (MobileNet.c:49-57) takes 224*224*3 raw bytes.
+ * The arithmetic, normative. Source: uint8 HWC [H][W][3]. Box: (left, upper, right, lower), four float32. Output: uint8 [oh][ow][3].
+ * Per axis, with in_size, the box edges b0 < b1 (float32) and out_size:
+ *     scale = (double)(b1 - b0) / out_size          the subtraction in float32, the division in double
+ *     fs = max(scale, 1.0);  support = fs;  ksize = (int)ceil(support) * 2 + 1
+ *   and for output index i:
+ *     center = (double)b0 + (i + 0.5) * scale
+ *     lo = max((int)(center - support + 0.5), 0);  hi = min((int)(center + support + 0.5), in_size)      (the casts truncate toward zero)
+ *     n = hi - lo;  tap t < n:  w_t = max(0, 1 - |(t + lo - center + 0.5) / fs|)                           in double
+ *     sum = w_0 + w_1 + ... in order;  w_t /= sum when sum != 0;  k_t = (int)(w_t * 4194304.0 + 0.5)       22 fractional bits
+ * Two passes, each over all three channels: horizontal first, tmp = clamp((2097152 + sum_t src[lo + t] * k_t) >> 22, 0, 255) ROUNDED TO uint8
+ * (int32 sums: the weights are >= 0 and sum to about 2^22), then the vertical pass the same way over tmp. An axis that is neither scaled
+ * nor cropped has the weights (2^22, 0): the identity.
+ *   mbn_resize_ksize   ksize of an axis, or a negative status
+ *   mbn_resize_taps    the tables of an axis: first[i] = lo, count[i] = n, weights [out_size][ksize] zero padded; returns ksize (>= 3) or a
+ *                      negative status. Host code; also in libmbn_host.so
+ *   mbn_fit_box        the box of a fit mode. MBN_FIT_STRETCH: (0, 0, W, H). MBN_FIT_CROP: the centred box with the output's aspect ratio,
+ *                      shrunk by crop_fraction f in (0, 1] (f = 0.875 is the usual "resize to 256, crop 224"); in double
+ *                      bw = min(W, H * ow / oh) * f, bh = bw * oh / ow, left = (W - bw) / 2, upper = (H - bh) / 2, each edge then rounded to
+ *                      float32 and clamped into the image. 480 x 640 -> 224 x 224, f = 1: (80, 0, 560, 480)
+ * A box edge below 0 or beyond the image, b1 <= b0, a NaN or a non-positive size: MBN_EINVAL.
+ * Device (mbn_u8_resize.hip): ONE launch runs both passes; the uint8 intermediate lives in LDS and never reaches memory.
+ *   mbn_resizer_create  builds both tap tables on the host and uploads them (blocking: here, not in the hot call). box NULL = the whole
+ *                       image. Envelope: source sides 1..8192, output sides 1..4096, ksize <= 67 per axis (a downscale up to 32x, any
+ *                       upscale); outside: MBN_EUNSUPPORTED, nothing launched
+ *   mbn_resize_u8       in [batch][H][W][3] -> out [batch][oh][ow][3], one geometry for the whole batch (1..65535 images, else MBN_EINVAL /
+ *                       MBN_EUNSUPPORTED above). Asynchronous on `stream` (NULL = the context's); no host allocation and no blocking call, so
+ *                       it may be captured between mbn_graph_begin / _end. ANY byte pointer is taken for `in` and `out` (a source row is
+ *                       read 4 bytes at a time from its first 4-byte boundary on, bytewise around it: the same bytes out); no byte outside
+ *                       the two tensors is read or written. The mbn_alloc bounds rule above applies: an undersized tracked `in` or `out` is
+ *                       MBN_EINVAL and nothing is launched. NULL pointers, batch <= 0: MBN_EINVAL
+ *   mbn_resizer_destroy frees the handle (waits for the context's stream); mbn_shutdown frees the handles still alive */
+#define MBN_FIT_STRETCH 0
+#define MBN_FIT_CROP    1
+int  mbn_resize_ksize(int in_size, float b0, float b1, int out_size);
+int  mbn_resize_taps(int in_size, float b0, float b1, int out_size, int32_t *first, int32_t *count, int32_t *weights);
+int  mbn_fit_box(int in_rows, int in_cols, int out_rows, int out_cols, int fit, float crop_fraction, float box[4]);
+typedef struct mbn_resizer mbn_resizer;
+int  mbn_resizer_create(mbn_context *ctx, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r);
+int  mbn_resize_u8(mbn_resizer *r, void *out_u8, const void *in_u8, int batch, void *stream);
+int  mbn_resizer_destroy(mbn_resizer *r);
+
 /* fp32 <-> bf16 (round to nearest even) on device; used to build the bf16 copy of the pointwise/FC filters. */
 int mbn_convert_f32_to_bf16(mbn_context *ctx, void *dst_bf16, const void *src_f32, size_t count, void *stream);
 int mbn_convert_bf16_to_f32(mbn_context *ctx, void *dst_f32, const void *src_bf16, size_t count, void *stream);
@@ -617,6 +662,14 @@ int  mbn_net_set_fuse_stem(mbn_net *net, int enabled);
 /* 1 = the `images` handed to mbn_net_forward / _timed / _classify are raw uint8 HWC [batch][rows][cols][3] (device);
  * layer 1 (or the fused stem) normalises them at load (MBN_IO_IN_U8). 0 (default) = fp32 NHWC, already normalised. */
 int  mbn_net_set_input_u8(mbn_net *net, int enabled);
+/* Images of any size for a net: src_u8 is [batch][in_rows][in_cols][3] uint8 on the device; the box of `fit` (mbn_fit_box with the plan's
+ * input rows x cols; crop_fraction is ignored by MBN_FIT_STRETCH) is resized (resize front-end above) into a staging buffer of the net, on the
+ * context's stream, and *images_u8 receives that buffer: [batch][rows][cols][3] uint8, the `images` of mbn_net_forward / _classify /
+ * _forward_dense / _segment under mbn_net_set_input_u8(net, 1), valid until the next call. Any dtype, any plan. The net keeps ONE resizer,
+ * rebuilt only when (in_rows, in_cols, fit, crop_fraction) changes, and the staging buffer (max_batch x rows x cols x 3 bytes, allocated on the
+ * first call, freed by mbn_net_destroy; MBN_ENOMEM leaves the net usable). Changes nothing in any forward path. */
+int  mbn_net_resize_input(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, float crop_fraction,
+                          void **images_u8);
 int  mbn_net_fused_layers(const mbn_net *net, int last_layer, int *count);
 /* Fused depthwise->pointwise blocks (mbn_dwpw_fused): bit L of `mask` (L = 1-based number of a depthwise layer) lets
  * layers L and L+1 run as one launch when the plan is fp32, activations are not kept and the shapes are inside the

@@ -1,0 +1,146 @@
+"""The resize front-end (mbn_resize_u8) against torch-ROCm's antialiased bilinear interpolate and against the forward it precedes, in one process.
+
+  python tools/resize_bench.py [--reps 7] [--steps 20] [--configs photo_b256,identity_b256] [--no-torch] [--no-forward]
+      Geometries (uint8 HWC sources, random bytes):
+        photo_b256 / photo_b512   375 x 500 -> 224 x 224, fit CROP with crop fraction 0.875, batch 256 / 512
+        hd_b64                    1080 x 1920 -> 224 x 224, fit CROP (the centred 1080 x 1080 box), batch 64
+        identity_b256             224 x 224 -> 224 x 224, the whole image, batch 256
+      Per geometry, alternating within every repetition:
+        kernel   mbn_resize_u8 on a torch-owned device buffer, ms per call
+        torch    the yardstick, not the code under test: on the SAME device buffer, the box's integer hull cut out as a view, then
+                 F.interpolate(x.float(), size, mode="bilinear", antialias=True). Its arithmetic differs (float, integer crop): a time
+                 comparison only, ms per call
+      Each figure is the median over the repetitions of `steps` back-to-back calls between two stream marks (torch: two torch events on its own
+      stream, synchronised). What the kernel's time means: the bytes it has to move — every source byte inside the rows and columns the tap
+      tables reach, once, plus the output — over 8 TB/s. Then the forward the resize precedes (1.0x224, uint8 input): fp32 at batch 256 and bf16
+      at batch 512, and the resize's share of it. The kernel's output is compared once with tests/resize_ref.py on image 0 (agreement, not timing).
+      One JSON object at the end. No GPU: the Context raises; nothing falls back.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from mbn_amd import import_package  # noqa: E402
+
+RES = 224
+HBM_BYTES_PER_S = 8.0e12                    # spec
+# (name, H, W, fit, crop fraction, batch, the forward it is compared with)
+CONFIGS = [("photo_b256", 375, 500, "crop", 0.875, 256, "f32_b256"), ("photo_b512", 375, 500, "crop", 0.875, 512, "bf16_b512"),
+           ("hd_b64", 1080, 1920, "crop", 1.0, 64, None), ("identity_b256", 224, 224, "stretch", 1.0, 256, "f32_b256")]
+FORWARDS = {"f32_b256": ("f32", 256), "bf16_b512": ("bf16", 512)}
+
+
+def window(pkg, in_size, b0, b1, out_size):
+    """[lo, hi): the source positions the tap tables of an axis reach"""
+    first, count, _ = pkg.resize_taps(in_size, float(b0), float(b1), out_size)
+    return int(first[0]), int(first[-1] + count[-1])
+
+
+def marks_ms(ctx, fn, steps):
+    ctx.mark()
+    for _ in range(steps):
+        fn()
+    ctx.mark()
+    return sum(ctx.marks_read(4)) / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--configs", default="", help="comma list of geometry names (default: all)")
+    ap.add_argument("--no-torch", action="store_true", help="skip the torch yardstick")
+    ap.add_argument("--no-forward", action="store_true", help="skip the forwards the resize is compared with")
+    a = ap.parse_args()
+    chosen = [c for c in CONFIGS if not a.configs or c[0] in a.configs.split(",")]
+    pkg = import_package()
+    import resize_ref
+    import torch
+    assert torch.cuda.is_available(), "the buffers are torch tensors on the same GPU"
+    F = torch.nn.functional
+    result = {}
+    with tempfile.TemporaryDirectory() as d, pkg.Context(0) as ctx:
+        runs = {}
+        for name, H, W, fit, frac, n, fwd in chosen:
+            box = pkg.fit_box(H, W, RES, RES, pkg.FIT_CROP if fit == "crop" else pkg.FIT_STRETCH, frac)
+            x0, x1 = window(pkg, W, box[0], box[2], RES)
+            y0, y1 = window(pkg, H, box[1], box[3], RES)
+            t_src = torch.randint(0, 256, (n, H, W, 3), dtype=torch.uint8, device="cuda")       # the library reads what torch owns
+            t_out = torch.zeros((n, RES, RES, 3), dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            rz = pkg.Resizer(ctx, H, W, RES, RES, box)
+            r = dict(rz=rz, n=n, fwd=fwd, t_src=t_src, t_out=t_out, kernel=[], torch=[],
+                     bytes=3.0 * n * ((y1 - y0) * (x1 - x0) + RES * RES), box=[float(v) for v in box])
+            r["run_kernel"] = lambda r=r: r["rz"].run(r["t_out"].data_ptr(), r["t_src"].data_ptr(), r["n"])
+            hull = t_src[:, int(np.floor(box[1])):int(np.ceil(box[3])), int(np.floor(box[0])):int(np.ceil(box[2])), :].permute(0, 3, 1, 2)
+            r["run_torch"] = lambda hull=hull: F.interpolate(hull.float(), size=(RES, RES), mode="bilinear", antialias=True)
+            marks_ms(ctx, r["run_kernel"], 3)               # warm-up of every timed shape
+            ctx.sync()
+            want = resize_ref.resize(t_src[0].cpu().numpy(), RES, RES, box)
+            r["bytes_differ_from_ref"] = int((t_out[0].cpu().numpy() != want).sum())
+            if not a.no_torch:
+                for _ in range(3):
+                    r["run_torch"]()
+                torch.cuda.synchronize()
+            runs[name] = r
+        for _ in range(a.reps):
+            for name, r in runs.items():
+                r["kernel"].append(marks_ms(ctx, r["run_kernel"], a.steps))
+                if not a.no_torch:
+                    ctx.sync()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(a.steps):
+                        r["run_torch"]()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    r["torch"].append(e0.elapsed_time(e1) / a.steps)
+        forward_ms = {}
+        if not a.no_forward:
+            path = os.path.join(d, "w.h5")
+            pkg.synthetic_h5(path, alpha=1.0, classes=1000, seed=7)
+            for key in sorted(set(r["fwd"] for r in runs.values() if r["fwd"])):
+                dtype, n = FORWARDS[key]
+                hw = pkg.HostWeights(path, res=RES)
+                net = pkg.Net(ctx, hw.plan, hw.blob.copy(), n)
+                if dtype == "bf16":
+                    net.set_dtype(pkg.DT_BF16)
+                net.set_input_u8(True)
+                t_img = torch.randint(0, 256, (n, RES, RES, 3), dtype=torch.uint8, device="cuda")
+                torch.cuda.synchronize()
+                d_logits = ctx.alloc(n * 1000 * 4)
+                run = lambda: net.forward(t_img.data_ptr(), d_logits.ptr, n)
+                marks_ms(ctx, run, 3)
+                forward_ms[key] = statistics.median(marks_ms(ctx, run, a.steps) for _ in range(a.reps))
+                ctx.sync()
+                net.destroy()
+                hw.free()
+                d_logits.free()
+        for name, r in runs.items():
+            k = statistics.median(r["kernel"])
+            out = {"batch": r["n"], "box": r["box"], "kernel_ms": round(k, 4), "kernel_runs_ms": [round(x, 4) for x in r["kernel"]],
+                   "kernel_bytes": int(r["bytes"]), "kernel_frac_of_8TBps": round(r["bytes"] / HBM_BYTES_PER_S / (k / 1e3), 4),
+                   "bytes_differ_from_ref_image0": r["bytes_differ_from_ref"]}
+            if r["torch"]:
+                t = statistics.median(r["torch"])
+                out.update({"torch_ms": round(t, 4), "torch_runs_ms": [round(x, 4) for x in r["torch"]], "torch_over_kernel": round(t / k, 2)})
+            if r["fwd"] in forward_ms:
+                out.update({"forward": r["fwd"], "forward_ms": round(forward_ms[r["fwd"]], 4), "kernel_over_forward": round(k / forward_ms[r["fwd"]], 4)})
+            result[name] = out
+            print("%-14s batch %3d  kernel %.4f ms (%.1f %% of 8 TB/s)  torch %s ms  forward %s ms" % (
+                name, r["n"], k, 100 * out["kernel_frac_of_8TBps"], ("%.4f" % out["torch_ms"]) if r["torch"] else "-",
+                ("%.4f (%s)" % (out["forward_ms"], r["fwd"])) if "forward_ms" in out else "-"), flush=True)
+            r["rz"].close()
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
