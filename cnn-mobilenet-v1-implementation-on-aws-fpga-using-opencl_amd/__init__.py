@@ -82,6 +82,17 @@ class I8Params(C.Structure):
     _fields_ = [("n_layers", C.c_int32), ("blob_bytes", C.c_int64), ("layer", I8Layer * MAX_LAYERS)]
 
 
+class ResizeItem(C.Structure):
+    """mbn_resize_item (include/mbn.h): one image of a ragged resize"""
+    _fields_ = [("src_offset", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32), ("box", C.c_float * 4)]
+
+
+class ResizeDesc(C.Structure):
+    """mbn_resize_desc (host/mbn_envelope.h): an image's descriptor in device memory, the item and what the host planned for it"""
+    _fields_ = [("src_offset", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32), ("box", C.c_float * 4)] + \
+               [(n, C.c_int32) for n in ("kx", "ky", "toh", "tiles_y", "wg0", "seg_stride", "tmp_off", "lds_bytes")]
+
+
 class I8PwPlan(C.Structure):
     """mbn_i8_pw_plan_t (host/mbn_envelope.h): the launch mbn_launch_i8_pointwise issues for a shape"""
     _fields_ = [(n, C.c_int) for n in ("form", "ks", "g", "out_f32", "pt", "threads", "gy", "lds_bytes")] + \
@@ -147,6 +158,9 @@ def _declare_host(lib):
     lib.mbn_fit_box.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float)]
     lib.mbn_resize_envelope.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int]      # mbn_envelope.h: exported, not in mbn.h
     lib.mbn_i8_pw_plan.argtypes = [C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(I8PwPlan)]
+    lib.mbn_resize_window.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, i32p, i32p]      # mbn_envelope.h, like the two below
+    lib.mbn_resize_ragged_plan.argtypes = [C.POINTER(ResizeItem), C.c_int, C.c_int, C.POINTER(ResizeDesc)]
+    lib.mbn_resize_ragged_plan_batch.argtypes = [C.POINTER(ResizeItem), C.c_int, C.c_int, C.c_int, C.POINTER(ResizeDesc), i32p, i32p, C.POINTER(C.c_int64)]
     return lib
 
 
@@ -255,6 +269,12 @@ def load():
         lib.mbn_resize_u8.argtypes = [vp, vp, vp, ci, vp]
         lib.mbn_resizer_destroy.argtypes = [vp]
         lib.mbn_net_resize_input.argtypes = [vp, vp, ci, ci, ci, ci, C.c_float, C.POINTER(vp)]
+        lib.mbn_ragged_resizer_create.argtypes = [vp, ci, ci, ci, C.POINTER(vp)]
+        lib.mbn_ragged_resizer_set.argtypes = [vp, C.POINTER(ResizeItem), ci, vp]
+        lib.mbn_resize_ragged_u8.argtypes = [vp, vp, vp, vp]
+        lib.mbn_ragged_resizer_destroy.argtypes = [vp]
+        lib.mbn_resize_taps_device.argtypes = [vp, ci, C.c_float, C.c_float, ci, vp, vp, vp]
+        lib.mbn_net_resize_inputs.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, ci, C.c_float, C.POINTER(vp)]
         lib.mbn_graph_begin.argtypes = [vp, vp]
         lib.mbn_graph_end.argtypes = [vp, vp, C.POINTER(vp)]
         lib.mbn_graph_launch.argtypes = [vp, vp, vp]
@@ -327,6 +347,33 @@ def fit_box(in_rows, in_cols, out_rows, out_cols, fit=FIT_CROP, crop_fraction=1.
     box = (C.c_float * 4)()
     _chk((lib or host_lib()).mbn_fit_box(in_rows, in_cols, out_rows, out_cols, fit, crop_fraction, box), "fit_box")
     return np.array(box[:], np.float32)
+
+
+def resize_items(items):
+    """A C array of mbn_resize_item from (src_offset, rows, cols, box) tuples; box None = the whole image."""
+    arr = (ResizeItem * len(items))()
+    for it, (off, rows, cols, box) in zip(arr, items):
+        it.src_offset, it.rows, it.cols = int(off), int(rows), int(cols)
+        it.box[:] = [float(np.float32(v)) for v in (box if box is not None else (0.0, 0.0, cols, rows))]
+    return arr
+
+
+def resize_window(in_size, b0, b1, out_size, o_first, o_last, lib=None):
+    """mbn_resize_window: [lo, hi) of the source positions the outputs o_first..o_last of an axis reach (no table is built)."""
+    lo, hi = C.c_int32(), C.c_int32()
+    _chk((lib or host_lib()).mbn_resize_window(in_size, b0, b1, out_size, o_first, o_last, C.byref(lo), C.byref(hi)), "resize_window")
+    return lo.value, hi.value
+
+
+def resize_ragged_plan(items, out_rows, out_cols, lib=None):
+    """mbn_resize_ragged_plan_batch: (descriptors, workgroups, dynamic LDS bytes, bytes of src reached) of a ragged launch of `items`
+    ((src_offset, rows, cols, box) tuples, or a ResizeItem array)."""
+    arr = items if isinstance(items, C.Array) else resize_items(items)
+    desc = (ResizeDesc * len(arr))()
+    wgs, lds, span = C.c_int32(), C.c_int32(), C.c_int64()
+    _chk((lib or host_lib()).mbn_resize_ragged_plan_batch(arr, len(arr), out_rows, out_cols, desc, C.byref(wgs), C.byref(lds), C.byref(span)),
+         "resize_ragged_plan")
+    return desc, wgs.value, lds.value, span.value
 
 
 def declared_symbols():
@@ -545,6 +592,52 @@ class Resizer:
             self.h = None
 
 
+class RaggedResizer:
+    """mbn_ragged_resizer_create / _set / mbn_resize_ragged_u8: up to max_batch uint8 HWC images, each with its own rows, cols and box, to one
+    [batch][out_rows][out_cols][3] in ONE launch, Pillow's 8-bit bilinear resize byte for byte. set() takes (src_offset, rows, cols, box) tuples
+    (byte offsets from the src pointer of run(); box None = the whole image)."""
+
+    def __init__(self, ctx: Context, max_batch, out_rows, out_cols):
+        self.ctx = ctx
+        self.shape_out = (out_rows, out_cols, 3)
+        self.batch = 0
+        h = C.c_void_p()
+        _chk(ctx.lib.mbn_ragged_resizer_create(ctx.h, max_batch, out_rows, out_cols, C.byref(h)), ctx.last_error())
+        self.h = h
+        if not hasattr(ctx, "_resizers"):
+            ctx._resizers = []
+        ctx._resizers.append(self)
+
+    def set(self, items, stream=None):
+        self.batch = 0
+        arr = items if isinstance(items, C.Array) else resize_items(items)
+        _chk(self.ctx.lib.mbn_ragged_resizer_set(self.h, arr, len(arr), stream), self.ctx.last_error())
+        self.batch = len(arr)
+
+    def run(self, out_ptr, src_ptr, stream=None):
+        _chk(self.ctx.lib.mbn_resize_ragged_u8(self.h, out_ptr, src_ptr, stream), self.ctx.last_error())
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.mbn_ragged_resizer_destroy(self.h)
+            self.h = None
+
+
+def resize_taps_device(ctx, in_size, b0, b1, out_size):
+    """mbn_resize_taps_device: the kernel's own tap function for one axis, downloaded: (first, count, weights [out_size][ksize]) int32."""
+    ks = resize_ksize(in_size, b0, b1, out_size, ctx.lib)
+    d_f, d_c, d_w = ctx.alloc(4 * out_size), ctx.alloc(4 * out_size), ctx.alloc(4 * out_size * ks)
+    rc = ctx.lib.mbn_resize_taps_device(ctx.h, in_size, b0, b1, out_size, d_f.ptr, d_c.ptr, d_w.ptr)
+    if rc < 0:
+        raise MbnError(rc, "resize_taps_device")
+    assert rc == ks
+    ctx.sync()
+    out = d_f.download((out_size,), np.int32), d_c.download((out_size,), np.int32), d_w.download((out_size, ks), np.int32)
+    for b in (d_f, d_c, d_w):
+        b.free()
+    return out
+
+
 def input_hw(res):
     """(rows, cols) of a `res` argument: an int is a square side, a pair is (rows, cols)."""
     if isinstance(res, (tuple, list)):
@@ -656,6 +749,16 @@ class Net:
         device pointer is returned): the `images` of forward / classify / forward_dense / segment under set_input_u8()."""
         p = C.c_void_p()
         _chk(self.ctx.lib.mbn_net_resize_input(self.h, src_ptr, batch, in_rows, in_cols, fit, crop_fraction, C.byref(p)), self.ctx.last_error())
+        return p.value
+
+    def resize_inputs(self, src_ptr, offsets, rows, cols, fit=FIT_CROP, crop_fraction=1.0) -> int:
+        """mbn_net_resize_inputs: image i is uint8 [rows[i]][cols[i]][3] at src_ptr + offsets[i]; all of them -> the net's staging buffer in one
+        ragged launch (its device pointer is returned), each through its own fit box."""
+        n = len(offsets)
+        assert len(rows) == n and len(cols) == n
+        p = C.c_void_p()
+        _chk(self.ctx.lib.mbn_net_resize_inputs(self.h, src_ptr, (C.c_int64 * n)(*[int(v) for v in offsets]), (C.c_int32 * n)(*[int(v) for v in rows]),
+                                                (C.c_int32 * n)(*[int(v) for v in cols]), n, fit, crop_fraction, C.byref(p)), self.ctx.last_error())
         return p.value
 
     def set_input_u8(self, enabled=True):

@@ -185,6 +185,7 @@ int mbn_shutdown(mbn_context *ctx)
     if (ctx->lit_ws) (void)hipFree(ctx->lit_ws);
     for (auto &kv : ctx->emul_ws) (void)hipFree(kv.second.p);
     for (mbn_resizer *r : ctx->resizers) mbn_resizer_release(r);
+    for (mbn_ragged_resizer *r : ctx->ragged_resizers) mbn_ragged_resizer_release(r);
     ctx->allocs.clear();
     for (hipEvent_t e : ctx->pool) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->marks) (void)hipEventDestroy(e);
@@ -859,6 +860,70 @@ int mbn_resize_u8(mbn_resizer *r, void *out_u8, const void *in_u8, int batch, vo
     MBN_SPANS(ctx, { in_u8, 3.0 * batch * r->in_rows * r->in_cols, "resize_u8 in" }, { out_u8, 3.0 * batch * r->out_rows * r->out_cols, "resize_u8 out" });
     Scope sc(ctx, s);
     return sc.finish(mbn_launch_u8_resize(r, s, (uint8_t *)out_u8, (const uint8_t *)in_u8, batch));
+}
+
+int mbn_ragged_resizer_create(mbn_context *ctx, int max_batch, int out_rows, int out_cols, mbn_ragged_resizer **r)
+{
+    if (!ctx || !r) return MBN_EINVAL;
+    *r = nullptr;
+    if (max_batch <= 0 || out_rows <= 0 || out_cols <= 0) return MBN_EINVAL;
+    if (max_batch > MBN_RESIZE_MAX_BATCH || out_rows > MBN_RESIZE_MAX_OUT || out_cols > MBN_RESIZE_MAX_OUT) return MBN_EUNSUPPORTED;
+    const int rc = mbn_ragged_resizer_build(ctx, max_batch, out_rows, out_cols, r);
+    if (rc != MBN_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->ragged_resizers.push_back(*r);
+    return MBN_OK;
+}
+
+int mbn_ragged_resizer_destroy(mbn_ragged_resizer *r)
+{
+    if (!r) return MBN_OK;
+    mbn_context *ctx = r->ctx;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        for (auto it = ctx->ragged_resizers.begin(); it != ctx->ragged_resizers.end(); ++it)
+            if (*it == r) { ctx->ragged_resizers.erase(it); break; }
+    }
+    (void)hipSetDevice(ctx->device);
+    MBN_HIP_TRY(ctx, hipEventSynchronize(r->done));              // its last upload or launch, whatever the stream
+    MBN_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    mbn_ragged_resizer_release(r);
+    return MBN_OK;
+}
+
+int mbn_ragged_resizer_set(mbn_ragged_resizer *r, const mbn_resize_item *items, int batch, void *stream)
+{
+    if (!r) return MBN_EINVAL;
+    r->batch = 0;                                                // a failed set leaves the handle without a batch
+    if (!items || batch <= 0 || batch > r->max_batch) return MBN_EINVAL;
+    mbn_context *ctx = r->ctx;
+    (void)hipSetDevice(ctx->device);
+    return mbn_ragged_resizer_plan(r, stream ? (hipStream_t)stream : ctx->stream, items, batch);
+}
+
+int mbn_resize_ragged_u8(mbn_ragged_resizer *r, void *out_u8, const void *src_u8, void *stream)
+{
+    if (!r || !out_u8 || !src_u8 || r->batch <= 0) return MBN_EINVAL;
+    mbn_context *ctx = r->ctx;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    MBN_SPANS(ctx, { src_u8, (double)r->src_span, "resize_ragged_u8 src" }, { out_u8, 3.0 * r->batch * r->out_rows * r->out_cols, "resize_ragged_u8 out" });
+    Scope sc(ctx, s);
+    return sc.finish(mbn_launch_u8_resize_ragged(r, s, (uint8_t *)out_u8, (const uint8_t *)src_u8));
+}
+
+int mbn_resize_taps_device(mbn_context *ctx, int in_size, float b0, float b1, int out_size, void *first_i32, void *count_i32, void *weights_i32)
+{
+    if (!ctx || !first_i32 || !count_i32 || !weights_i32) return MBN_EINVAL;
+    if (((uintptr_t)first_i32 | (uintptr_t)count_i32 | (uintptr_t)weights_i32) % 4) return MBN_EINVAL;
+    const int ksize = mbn_resize_ksize(in_size, b0, b1, out_size);
+    if (ksize == MBN_EINVAL) return MBN_EINVAL;
+    if (ksize < 0 || ksize > MBN_RESIZE_MAX_KSIZE || in_size > MBN_RESIZE_MAX_IN || out_size > MBN_RESIZE_MAX_OUT) return MBN_EUNSUPPORTED;
+    MBN_SPANS(ctx, { first_i32, 4.0 * out_size, "resize_taps_device first" }, { count_i32, 4.0 * out_size, "resize_taps_device count" },
+              { weights_i32, 4.0 * out_size * ksize, "resize_taps_device weights" });
+    Scope sc(ctx, ctx->stream);
+    const int rc = sc.finish(mbn_launch_resize_taps(ctx->stream, in_size, b0, b1, out_size, ksize, (int32_t *)first_i32, (int32_t *)count_i32,
+                                                    (int32_t *)weights_i32));
+    return rc == MBN_OK ? ksize : rc;
 }
 
 int mbn_classifier_tail(mbn_context *ctx, void *topk_idx_i32, void *topk_prob_f32, void *probs, void *logits_scratch,

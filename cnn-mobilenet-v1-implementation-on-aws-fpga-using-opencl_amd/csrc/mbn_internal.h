@@ -31,6 +31,18 @@ struct mbn_resizer {
     void *tables = nullptr;                      // device: fx, cx [out_cols], fy, cy [out_rows], wx [out_cols][kx], wy [out_rows][ky], int32
 };
 
+// mbn_ragged_resizer_create's handle (mbn_u8_resize_ragged.hip): the descriptors of up to max_batch images, on the device and pinned on the host
+struct mbn_ragged_resizer {
+    mbn_context *ctx = nullptr;
+    int max_batch = 0, out_rows = 0, out_cols = 0, tow = 0, tiles_x = 0;
+    int batch = 0;                               // of the last successful set; 0 = none
+    int total_wgs = 0, lds_bytes = 0;            // its launch
+    int generation = 0;                          // counts the sets: a captured launch replayed after another set does nothing
+    int64_t src_span = 0;                        // bytes of src its images reach
+    void *dev = nullptr, *host = nullptr;        // 64-byte head + mbn_resize_desc [max_batch]
+    hipEvent_t done = nullptr;                   // behind the last upload or launch: the next set waits for it
+};
+
 struct mbn_context {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -52,6 +64,7 @@ struct mbn_context {
     size_t lit_ws_bytes = 0;
     std::map<std::pair<uintptr_t, int>, mbn_emul_img> emul_ws;   // pw_emul: pre-split filter images, by (filter pointer, layout) (mbn_f32_pw_x6.hip)
     std::vector<mbn_resizer *> resizers;         // live mbn_resizer_create handles (mbn_shutdown frees the stragglers)
+    std::vector<mbn_ragged_resizer *> ragged_resizers;   // live mbn_ragged_resizer_create handles, likewise
     std::mutex mu;
     std::map<uintptr_t, size_t> allocs;          // buffers handed out by mbn_alloc: base address -> bytes (ordered: mbn_span_check
                                                  // finds the allocation that CONTAINS an interior pointer)
@@ -240,6 +253,13 @@ int mbn_launch_f32_upsample_argmax(mbn_context *ctx, hipStream_t s, int32_t *lab
 int mbn_resizer_build(mbn_context *ctx, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r);
 void mbn_resizer_release(mbn_resizer *r);
 int mbn_launch_u8_resize(const mbn_resizer *r, hipStream_t s, uint8_t *out, const uint8_t *in, int batch);
+// ragged resize (mbn_u8_resize_ragged.hip): build allocates, plan checks and plans a batch and enqueues the descriptors' upload (waits for the handle's
+// earlier work first), the launch is asynchronous; taps: the kernel's tap function for one axis into device tables
+int mbn_ragged_resizer_build(mbn_context *ctx, int max_batch, int out_rows, int out_cols, mbn_ragged_resizer **r);
+void mbn_ragged_resizer_release(mbn_ragged_resizer *r);
+int mbn_ragged_resizer_plan(mbn_ragged_resizer *r, hipStream_t s, const mbn_resize_item *items, int batch);
+int mbn_launch_u8_resize_ragged(mbn_ragged_resizer *r, hipStream_t s, uint8_t *out, const uint8_t *src);
+int mbn_launch_resize_taps(hipStream_t s, int in_size, float b0, float b1, int out_size, int ksize, int32_t *first, int32_t *count, int32_t *weights);
 int mbn_launch_normalize(mbn_context *ctx, hipStream_t s, float *out, const uint8_t *in, size_t count, float scale,
                          float bias);
 

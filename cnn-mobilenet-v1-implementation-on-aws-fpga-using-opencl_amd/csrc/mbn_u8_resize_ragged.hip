@@ -1,0 +1,312 @@
+// mbn_u8_resize_ragged.hip — the ragged resize on gfx950: ONE launch takes `batch` uint8 HWC images, each with its own rows, cols and box, to one common
+// [batch][oh][ow][3], byte for byte the arithmetic of include/mbn.h ("resize front-end"). mbn_u8_resize.hip is its single-geometry sibling and stays the
+// path of uniform batches; what is the same here is said there: a workgroup of 4 waves owns a tile of toh x tow outputs of one image, the waves stage
+// the source rows of the tile's window in LDS (head / dword body / tail split by address), form the horizontal sums into the uint8 window in LDS and
+// then run the vertical pass out of it. What differs:
+//   taps        no table exists anywhere. The workgroup forms its tile's taps itself, straight into LDS where the horizontal weights lived already:
+//               lane c of wave 0 runs output column c of the tile, lane r of wave 1 output row r, each its <= 67 taps one after the other (axis_taps:
+//               the expressions of host/mbn_resize.c in fp64, contraction off). The vertical weights, first rows and counts sit in LDS as well;
+//   geometry    per image, from a 64-byte descriptor in device memory (mbn_resize_desc, host/mbn_envelope.h): the caller's item and what the host
+//               planned without a table (host/mbn_resize.c, mbn_resize_ragged_plan): ksize per axis, the tile height, the staged row's stride, the
+//               window's LDS offset, and the image's first workgroup;
+//   mapping     the grid is 1-D, one workgroup per tile of the batch and none idle: workgroup w belongs to the last image whose first workgroup is
+//               <= w, found by a 64-ary search of the descriptors (each lane probes one, a ballot counts: one probe round up to 64 images, two up to
+//               4096). A (most tiles, batch) grid with early exit would launch batch x out_rows x tiles_x workgroups as soon as ONE image of the
+//               batch is a steep downscale with one-row tiles.
+// The tile's window comes from axis_span at its edge outputs, as the host's plan did (mbn_resize_window): the same expressions on both sides. Should
+// they ever disagree, the kernel's capacity clamps turn that into wrong bytes (which the tests compare) and never into an access outside LDS, the
+// images or the output. lo and hi grow with the output index because every floating operation in them is monotonic, so a tile's first and last
+// outputs bound the windows of all of them.
+#include "mbn_internal.h"
+
+#include <new>
+
+// The taps must equal the host's bit for bit, and the host build (baseline x86-64) has no fused multiply-add: nothing in this file may contract.
+// (The fp64 division expands to its correctly rounded sequence; that is the division itself, not a contraction.)
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int RAGGED_EPL = 64 * 3 / 64;      // horizontal sums of a row per lane at most (tow <= 64)
+constexpr int RAGGED_HALF = 1 << 21, RAGGED_SHIFT = 22;
+
+// head of the device block, in front of the descriptors; 64 bytes like them
+struct RaggedHead {
+    int32_t batch, total_wgs, lds_bytes, generation;
+    int32_t pad[12];
+};
+static_assert(sizeof(RaggedHead) == 64 && sizeof(mbn_resize_desc) == 64 && sizeof(mbn_resize_item) == 32, "device layout");
+
+struct RaggedArgs {
+    uint8_t *out;
+    const uint8_t *src;
+    const RaggedHead *head;
+    const mbn_resize_desc *desc;
+    int oh, ow, tow, tiles_x;
+    int lds_bytes;           // the launch's dynamic LDS
+    int generation;          // of the set this launch was issued (or captured) for
+};
+
+struct Axis {
+    double b0, scale, fs;    // fs = support = max(scale, 1)
+    int in_size;
+};
+
+__device__ __forceinline__ Axis axis_of(int in_size, float b0, float b1, int out_size)
+{
+    const float extent = b1 - b0;                                // the subtraction in float32, everything behind it in double
+    Axis a;
+    a.in_size = in_size;
+    a.b0 = (double)b0;
+    a.scale = (double)extent / (double)out_size;
+    a.fs = a.scale < 1.0 ? 1.0 : a.scale;
+    return a;
+}
+
+// [lo, hi) of output i and its centre: axis_span of host/mbn_resize.c
+__device__ __forceinline__ double axis_span(const Axis &a, int i, int &lo, int &hi)
+{
+    const double center = a.b0 + ((double)i + 0.5) * a.scale;
+    lo = max((int)(center - a.fs + 0.5), 0);                     // the casts truncate toward zero
+    hi = min((int)(center + a.fs + 0.5), a.in_size);
+    return center;
+}
+
+__device__ __forceinline__ double axis_weight(const Axis &a, int pos, double center)
+{
+    double x = ((double)pos - center + 0.5) / a.fs;
+    if (x < 0.0) x = -x;
+    return x < 1.0 ? 1.0 - x : 0.0;
+}
+
+// the taps of output i: k[0, ksize) = its 22-bit weights, zero padded; returns the count and its first source position. Two passes over the taps, the
+// weight formed again in the second: a lane has no room for 67 doubles, and the same expression gives the same bits
+__device__ __forceinline__ int axis_taps(const Axis &a, int i, int ksize, int32_t *k, int &first)
+{
+    int lo, hi;
+    const double center = axis_span(a, i, lo, hi);
+    const int n = min(max(hi - lo, 0), ksize);
+    double sum = 0.0;
+    for (int t = 0; t < n; t++) sum += axis_weight(a, t + lo, center);       // w_0 + w_1 + ... in order
+    for (int t = 0; t < n; t++) {
+        double w = axis_weight(a, t + lo, center);
+        if (sum != 0.0) w /= sum;
+        k[t] = (int32_t)(w * 4194304.0 + 0.5);
+    }
+    for (int t = n; t < ksize; t++) k[t] = 0;
+    first = lo;
+    return n;
+}
+
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ uint8_t resize_round(int acc)
+{
+    return (uint8_t)min(max(acc >> RAGGED_SHIFT, 0), 255);
+}
+
+__global__ __launch_bounds__(256, 8) void resize_ragged_u8(const RaggedArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t s_mem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wg = (int)blockIdx.x;
+    // a replay of a captured launch after another set: the descriptors are no longer the ones its grid, LDS and spans were checked for
+    if (a.head->generation != a.generation || wg >= a.head->total_wgs) return;
+    // ---- the image: the last one whose first workgroup is <= wg, among [base, base + n). desc[base].wg0 <= wg holds throughout (desc[0].wg0 = 0)
+    int base = 0, n = a.head->batch;
+    while (n > 1) {
+        const int stride = (n + 63) >> 6;
+        const bool le = lane * stride < n && a.desc[base + lane * stride].wg0 <= wg;
+        const int step = (max(__popcll(__ballot(le)), 1) - 1) * stride;      // wg0 grows with the index: the lanes that say yes are the first ones
+        base += step;
+        n = min(stride, n - step);
+    }
+    const mbn_resize_desc &d = a.desc[__builtin_amdgcn_readfirstlane(base)];
+    const int kx = d.kx, ky = d.ky, toh = d.toh, tow = a.tow;
+    const int tile = wg - d.wg0, ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+    if (tile < 0 || ty >= d.tiles_y) return;
+    const int ox0 = tx * tow, oxn = min(tow, a.ow - ox0), oy0 = ty * toh, oyn = min(toh, a.oh - oy0);
+    const int row_e = oxn * 3;                                   // horizontal sums of a source row
+    const Axis gx = axis_of(d.cols, d.box[0], d.box[2], a.ow), gy = axis_of(d.rows, d.box[1], d.box[3], a.oh);
+    int xs0, xs1, y0, y1, unused;
+    (void)axis_span(gx, ox0, xs0, unused);
+    (void)axis_span(gx, ox0 + oxn - 1, unused, xs1);
+    (void)axis_span(gy, oy0, y0, unused);
+    (void)axis_span(gy, oy0 + oyn - 1, unused, y1);
+    // the LDS image of a tile (host/mbn_envelope.h)
+    int32_t *s_wx = reinterpret_cast<int32_t *>(s_mem), *s_wy = s_wx + tow * kx, *s_fx = s_wy + toh * ky, *s_fy = s_fx + tow, *s_cy = s_fy + toh;
+    uint8_t *s_row = s_mem + MBN_RESIZE_STAGE_OFF(tow, kx, toh, ky) + wave * d.seg_stride;
+    uint8_t *s_tmp = s_mem + d.tmp_off;
+    const int tmp_ld = tow * 3;
+    // what the plan left room for: the host derived the same windows, so neither clamp binds
+    const int nb = max(min((xs1 - xs0) * 3, d.seg_stride - 3 - kx * 3), 0);
+    const int nrows = max(min(y1 - y0, (a.lds_bytes - d.tmp_off) / tmp_ld), 0);
+
+    // ---- the tile's taps: wave 0 a column per lane, wave 1 a row per lane (toh <= 32)
+    if (tid < oxn) {
+        int f;
+        (void)axis_taps(gx, ox0 + tid, kx, s_wx + tid * kx, f);
+        s_fx[tid] = f;
+    } else if (tid >= 64 && tid - 64 < oyn) {
+        const int r = tid - 64;
+        int f;
+        s_cy[r] = axis_taps(gy, oy0 + r, ky, s_wy + r * ky, f);
+        s_fy[r] = f;
+    }
+    __syncthreads();                                             // the taps are in place
+
+    const size_t img = (size_t)(&d - a.desc);
+    const uint8_t *__restrict__ src = a.src + d.src_offset;
+    uint8_t *__restrict__ dst = a.out + img * ((size_t)a.oh * a.ow * 3);
+    // this lane's horizontal sums: element e = lane + 64 j of a row is column e / 3, channel e % 3
+    int lo[RAGGED_EPL], wofs[RAGGED_EPL];
+#pragma unroll
+    for (int j = 0; j < RAGGED_EPL; j++) {
+        const int e = lane + 64 * j, ox = e / 3;
+        const bool on = e < row_e;
+        lo[j] = on ? min(max(s_fx[ox] - xs0, 0), max(nb / 3 - 1, 0)) * 3 + (e - 3 * ox) : 0;
+        wofs[j] = on ? ox * kx : 0;
+    }
+    // ---- horizontal: wave v takes rows y0 + v, y0 + v + 4, ... of the window, each wave at its own pace (the staged row is its own)
+    for (int r = wave; r < nrows; r += MBN_RESIZE_WAVES) {
+        const uint8_t *g = src + ((size_t)(y0 + r) * d.cols + xs0) * 3;
+        const int off = (int)((uintptr_t)g & 3);                 // byte j of the segment goes to s_row[off + j]: a dword of memory is a dword of LDS
+        const int head = min(nb, (4 - off) & 3), body = (nb - head) >> 2, tail0 = head + 4 * body;
+        if (lane < head) s_row[off + lane] = g[lane];
+        for (int i = lane; i < body; i += 64)
+            *reinterpret_cast<uint32_t *>(s_row + off + head + 4 * i) = *reinterpret_cast<const uint32_t *>(g + head + 4 * i);
+        if (tail0 + lane < nb) s_row[off + tail0 + lane] = g[tail0 + lane];
+        wave_sync();
+#pragma unroll
+        for (int j = 0; j < RAGGED_EPL; j++) {
+            const int e = lane + 64 * j;
+            if (e < row_e) {
+                int acc = RAGGED_HALF;
+                const uint8_t *p = s_row + off + lo[j];
+                const int32_t *k = s_wx + wofs[j];
+                for (int t = 0; t < kx; t++) acc += (int)p[3 * t] * k[t];      // past this column's count: a zero weight times a byte of the slack
+                s_tmp[r * tmp_ld + e] = resize_round(acc);
+            }
+        }
+        wave_sync();                                             // the next row is staged over this one
+    }
+    __syncthreads();                                             // the window is complete
+
+    // ---- vertical: wave v takes output rows v, v + 4, ... of the tile; the row's first source row, count and weights are the same for all its lanes
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    int idx[RAGGED_EPL];
+#pragma unroll
+    for (int j = 0; j < RAGGED_EPL; j++) idx[j] = lane + 64 * j < row_e ? lane + 64 * j : 0;
+    for (int oy = wv; oy < oyn; oy += MBN_RESIZE_WAVES) {
+        const int f = min(max(__builtin_amdgcn_readfirstlane(s_fy[oy]) - y0, 0), max(nrows - 1, 0));
+        const int cnt = min(__builtin_amdgcn_readfirstlane(s_cy[oy]), nrows - f);
+        const int32_t *k = s_wy + oy * ky;
+        const uint8_t *p = s_tmp + f * tmp_ld;
+        int acc[RAGGED_EPL];
+#pragma unroll
+        for (int j = 0; j < RAGGED_EPL; j++) acc[j] = RAGGED_HALF;
+        for (int t = 0; t < cnt; t++) {
+            const int kt = k[t];
+#pragma unroll
+            for (int j = 0; j < RAGGED_EPL; j++) acc[j] += (int)p[t * tmp_ld + idx[j]] * kt;
+        }
+        uint8_t *o = dst + ((size_t)(oy0 + oy) * a.ow + ox0) * 3;
+#pragma unroll
+        for (int j = 0; j < RAGGED_EPL; j++)
+            if (lane + 64 * j < row_e) o[lane + 64 * j] = resize_round(acc[j]);
+    }
+}
+
+// mbn_resize_taps_device: the tables of one axis from axis_taps, an output per lane
+__global__ __launch_bounds__(64) void resize_taps_k(int in_size, float b0, float b1, int out_size, int ksize, int32_t *first, int32_t *count, int32_t *weights)
+{
+    const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
+    if (i >= out_size) return;
+    const Axis a = axis_of(in_size, b0, b1, out_size);
+    int f;
+    count[i] = axis_taps(a, i, ksize, weights + (size_t)i * ksize, f);
+    first[i] = f;
+}
+
+}   // namespace
+
+int mbn_ragged_resizer_build(mbn_context *ctx, int max_batch, int out_rows, int out_cols, mbn_ragged_resizer **out)
+{
+    mbn_ragged_resizer *r = new (std::nothrow) mbn_ragged_resizer();
+    if (!r) return MBN_ENOMEM;
+    r->ctx = ctx;
+    r->max_batch = max_batch; r->out_rows = out_rows; r->out_cols = out_cols;
+    r->tow = MBN_RESIZE_TOW(out_cols);
+    r->tiles_x = (out_cols + r->tow - 1) / r->tow;
+    const size_t bytes = 64 * ((size_t)max_batch + 1);
+    (void)hipSetDevice(ctx->device);
+    hipError_t e = hipMalloc(&r->dev, bytes);
+    if (e == hipSuccess) e = hipHostMalloc(&r->host, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&r->done, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        mbn_ragged_resizer_release(r);
+        return e == hipErrorOutOfMemory ? MBN_ENOMEM : mbn_record_hip_error(ctx, e, "ragged resizer buffers");
+    }
+    *out = r;
+    return MBN_OK;
+}
+
+void mbn_ragged_resizer_release(mbn_ragged_resizer *r)
+{
+    if (r->done) (void)hipEventDestroy(r->done);
+    if (r->host) (void)hipHostFree(r->host);
+    if (r->dev) (void)hipFree(r->dev);
+    delete r;
+}
+
+// Plans into the pinned copy and enqueues its upload. Waits first for what still reads either copy: the previous upload and every launch since
+int mbn_ragged_resizer_plan(mbn_ragged_resizer *r, hipStream_t s, const mbn_resize_item *items, int batch)
+{
+    mbn_context *ctx = r->ctx;
+    r->batch = 0;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return MBN_EINVAL;      // a set is not part of a graph
+    MBN_HIP_TRY(ctx, hipEventSynchronize(r->done));
+    RaggedHead *h = (RaggedHead *)r->host;
+    mbn_resize_desc *desc = (mbn_resize_desc *)(h + 1);
+    int32_t total = 0, lds = 0;
+    int64_t span = 0;
+    const int rc = mbn_resize_ragged_plan_batch(items, batch, r->out_rows, r->out_cols, desc, &total, &lds, &span);
+    if (rc != MBN_OK) return rc;
+    memset(h, 0, sizeof *h);
+    h->batch = batch; h->total_wgs = total; h->lds_bytes = lds; h->generation = r->generation + 1;
+    MBN_HIP_TRY(ctx, hipMemcpyAsync(r->dev, r->host, 64 * ((size_t)batch + 1), hipMemcpyHostToDevice, s));
+    MBN_HIP_TRY(ctx, hipEventRecord(r->done, s));
+    r->generation = h->generation;
+    r->total_wgs = total; r->lds_bytes = lds; r->src_span = span;
+    r->batch = batch;
+    return MBN_OK;
+}
+
+// the handle has a batch, the pointers are non-null and the spans fit (the caller has checked)
+int mbn_launch_u8_resize_ragged(mbn_ragged_resizer *r, hipStream_t s, uint8_t *out, const uint8_t *src)
+{
+    RaggedArgs a;
+    a.out = out; a.src = src;
+    a.head = (const RaggedHead *)r->dev;
+    a.desc = (const mbn_resize_desc *)(a.head + 1);
+    a.oh = r->out_rows; a.ow = r->out_cols; a.tow = r->tow; a.tiles_x = r->tiles_x;
+    a.lds_bytes = r->lds_bytes; a.generation = r->generation;
+    hipLaunchKernelGGL(resize_ragged_u8, dim3((unsigned)r->total_wgs), dim3(256), (size_t)r->lds_bytes, s, a);
+    // the next set waits for this launch; inside a capture there is nothing to wait for (the replays are the caller's to order)
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) (void)hipEventRecord(r->done, s);
+    return MBN_OK;
+}
+
+// the geometry is inside the device's envelope and ksize is the axis's (the caller has checked)
+int mbn_launch_resize_taps(hipStream_t s, int in_size, float b0, float b1, int out_size, int ksize, int32_t *first, int32_t *count, int32_t *weights)
+{
+    hipLaunchKernelGGL(resize_taps_k, dim3((unsigned)((out_size + 63) / 64)), dim3(64), 0, s, in_size, b0, b1, out_size, ksize, first, count, weights);
+    return MBN_OK;
+}

@@ -5,6 +5,9 @@
  * heuristics and the consistency between layers stay with the callers. Exported by libmbn.so and libmbn_host.so, not in mbn.h.
  */
 #pragma once
+#include <stdint.h>
+
+#include "mbn.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -61,6 +64,37 @@ int mbn_upsample_argmax_envelope(int batch, int rows, int cols, int classes, int
 #define MBN_RESIZE_MAX_KSIZE 67
 #define MBN_RESIZE_MAX_BATCH 65535
 int mbn_resize_envelope(int in_rows, int in_cols, const float *box, int out_rows, int out_cols);
+/* ragged resize (mbn_u8_resize_ragged.hip): every image of a launch has its own rows, cols and box. What the host plans, without a tap table:
+ * a workgroup of MBN_RESIZE_WAVES waves owns a tile of toh x tow outputs of one image; tow follows the output (the rule of mbn_resizer_create), toh is
+ * the tallest tile (MBN_RESIZE_TOH at most) whose LDS image fits MBN_RESIZE_LDS bytes. The LDS image of a tile, in this order:
+ *   int32  wx [tow][kx], wy [toh][ky], fx [tow], fy [toh], cy [toh]      the tile's taps, formed by the kernel
+ *   MBN_RESIZE_STAGE_OFF: MBN_RESIZE_WAVES staged source rows of seg_stride bytes each, then at tmp_off the window [source rows][tow * 3] uint8 */
+#define MBN_RESIZE_WAVES 4
+#define MBN_RESIZE_TOH 32
+#define MBN_RESIZE_LDS (60 * 1024)
+#define MBN_RESIZE_TOW(out_cols) ((out_cols) <= 32 ? 32 : 64)
+#define MBN_RESIZE_STAGE_OFF(tow, kx, toh, ky) ((4 * ((tow) * (kx) + (toh) * (ky) + (tow) + 2 * (toh)) + 15) & ~15)
+/* the descriptor of one image in device memory, 64 bytes: the caller's mbn_resize_item, then the plan */
+typedef struct mbn_resize_desc {
+    int64_t src_offset;              /* bytes from the launch's src pointer to the image's first byte */
+    int32_t rows, cols;
+    float box[4];                    /* left, upper, right, lower */
+    int32_t kx, ky;                  /* mbn_resize_ksize of the two axes */
+    int32_t toh, tiles_y;            /* rows of a tile; ceil(out_rows / toh) */
+    int32_t wg0;                     /* the image's first workgroup: the prefix sum of tiles_x * tiles_y over the images before it */
+    int32_t seg_stride;              /* bytes of a staged row: the widest tile's segment + kx pixels of slack + 3, a multiple of 4 */
+    int32_t tmp_off;                 /* LDS byte offset of the window */
+    int32_t lds_bytes;               /* tmp_off + the tallest window * tow * 3: what this image needs; a launch takes the largest of its batch */
+} mbn_resize_desc;
+/* [lo, hi): the source positions the outputs o_first..o_last of an axis reach, from the exact expressions of mbn_resize_taps at those two outputs only
+ * (first[o_first] and first[o_last] + count[o_last] of the tables). MBN_EINVAL for what mbn_resize_ksize refuses or indices outside the axis */
+int mbn_resize_window(int in_size, float b0, float b1, int out_size, int o_first, int o_last, int32_t *lo, int32_t *hi);
+/* one image: MBN_EINVAL for a negative offset and whatever mbn_resize_envelope answers; fills *d (wg0 = 0). O(tiles) evaluations of lo / hi */
+int mbn_resize_ragged_plan(const mbn_resize_item *item, int out_rows, int out_cols, mbn_resize_desc *d);
+/* a batch: desc[i] with its wg0, the launch's workgroups (below 2^31, else MBN_EUNSUPPORTED) and dynamic LDS, and the bytes of src the batch reaches,
+ * max(src_offset + rows * cols * 3). The first refused item's status is returned */
+int mbn_resize_ragged_plan_batch(const mbn_resize_item *items, int batch, int out_rows, int out_cols, mbn_resize_desc *desc, int32_t *total_wgs,
+                                 int32_t *lds_bytes, int64_t *src_span);
 
 /* int8 pointwise / FC (mbn_i8.hip): the whole launch arithmetic of mbn_launch_i8_pointwise, which launches what this says and
  * computes nothing of its own. Two forms: the persistent one (i8_pw2_k<ks, 512, out_f32>: a wave keeps a 32-column chunk's filter

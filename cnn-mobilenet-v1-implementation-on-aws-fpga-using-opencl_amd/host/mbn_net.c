@@ -52,7 +52,9 @@ struct mbn_net {
     mbn_resizer *resizer;      /* mbn_net_resize_input: the resizer of the geometry below, rebuilt when it changes */
     int rs_rows, rs_cols, rs_fit;
     float rs_fraction;
-    void *resize_buf;          /* mbn_net_resize_input: [max_batch][rows][cols][3] uint8, the resized images */
+    void *resize_buf;          /* mbn_net_resize_input / _inputs: [max_batch][rows][cols][3] uint8, the resized images */
+    mbn_ragged_resizer *ragged;     /* mbn_net_resize_inputs: one ragged resizer of max_batch images, made on the first call */
+    mbn_resize_item *ragged_items;  /* ... and the items it is set from, [max_batch] */
     void *poolfc_ws;           /* workspace of mbn_pool_fc (1...4 images: pool + FC in one launch), allocated and zeroed at creation */
     size_t poolfc_ws_bytes;
     int fuse_tail;             /* mbn_net_set_fuse_tail (default 0) */
@@ -145,6 +147,8 @@ int mbn_net_destroy(mbn_net *net)
     if (net->dense_logits) mbn_free(net->ctx, net->dense_logits);
     if (net->poolfc_ws) mbn_free(net->ctx, net->poolfc_ws);
     if (net->resizer) mbn_resizer_destroy(net->resizer);
+    if (net->ragged) mbn_ragged_resizer_destroy(net->ragged);
+    free(net->ragged_items);
     if (net->resize_buf) mbn_free(net->ctx, net->resize_buf);
     for (int j = 0; j < 8; j++)
         if (net->streams[j]) mbn_stream_destroy(net->ctx, net->streams[j]);
@@ -914,6 +918,39 @@ int mbn_net_resize_input(mbn_net *net, const void *src_u8, int batch, int in_row
         if (rc != MBN_OK) { net->resize_buf = NULL; return rc; }
     }
     int rc = mbn_resize_u8(net->resizer, net->resize_buf, src_u8, batch, NULL);
+    if (rc == MBN_OK) *images_u8 = net->resize_buf;
+    return rc;
+}
+
+int mbn_net_resize_inputs(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *in_rows, const int32_t *in_cols, int batch, int fit,
+                          float crop_fraction, void **images_u8)
+{
+    if (!net || !src_u8 || !offsets || !in_rows || !in_cols || !images_u8 || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
+    *images_u8 = NULL;
+    const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols;
+    if (fit == MBN_FIT_STRETCH) crop_fraction = 1.0f;
+    if (!net->ragged_items) {
+        net->ragged_items = malloc((size_t)net->max_batch * sizeof(mbn_resize_item));
+        if (!net->ragged_items) return MBN_ENOMEM;
+    }
+    for (int i = 0; i < batch; i++) {
+        mbn_resize_item *it = &net->ragged_items[i];
+        it->src_offset = offsets[i];
+        it->rows = in_rows[i];
+        it->cols = in_cols[i];
+        const int rc = mbn_fit_box(in_rows[i], in_cols[i], rows, cols, fit, crop_fraction, it->box);
+        if (rc != MBN_OK) return rc;
+    }
+    if (!net->ragged) {
+        const int rc = mbn_ragged_resizer_create(net->ctx, net->max_batch, rows, cols, &net->ragged);
+        if (rc != MBN_OK) { net->ragged = NULL; return rc; }
+    }
+    if (!net->resize_buf) {
+        const int rc = mbn_alloc(net->ctx, (size_t)net->max_batch * rows * cols * 3, &net->resize_buf);
+        if (rc != MBN_OK) { net->resize_buf = NULL; return rc; }
+    }
+    int rc = mbn_ragged_resizer_set(net->ragged, net->ragged_items, batch, NULL);
+    if (rc == MBN_OK) rc = mbn_resize_ragged_u8(net->ragged, net->resize_buf, src_u8, NULL);
     if (rc == MBN_OK) *images_u8 = net->resize_buf;
     return rc;
 }

@@ -5,7 +5,8 @@
  *   mobilenet --synthetic SEED [--alpha A] [--res R] [--batch N]                              fp32, synthetic weights
  *   --res R = R x R images; --res RxC = R rows by C columns (a P6 image C wide and R high), both multiples of 32
  *   --output-stride 32 | 16 | 8: the late stride-2 depthwise layers stop subsampling, the ones behind them are dilated (mbn_plan_build_os)
- *   --ppm F: a P6 image of ANY size up to 8192 x 8192; one that is not cols wide and rows high is resized on the device (mbn_net_resize_input: Pillow's 8-bit
+ *   --ppm F (several times, up to --batch, for files of different sizes: they are resized in ONE ragged launch, mbn_net_resize_inputs, and the top-1 of
+ *   each is printed; the rest of the batch repeats the first): a P6 image of ANY size up to 8192 x 8192; one that is not cols wide and rows high is resized on the device (mbn_net_resize_input: Pillow's 8-bit
  *   bilinear). --fit crop (default: the centred box with the plan's aspect ratio) | stretch (the whole image); --crop-fraction F in (0, 1] shrinks the crop box
  *   (0.875 = "resize to 256, crop 224"). An image of the plan's size is taken as it is
  *   --segment FILE: after the classification, the dense head (mbn_net_segment): the label map of image 0 as a binary PGM and its five most frequent labels
@@ -388,6 +389,9 @@ int main(int argc, char **argv)
 {
     if (argc == 3 && !strcmp(argv[1], "--inspect")) return inspect_h5(argv[2]);
     if (argc == 4 && !strcmp(argv[1], "--convert")) return convert_h5(argv[2], argv[3]);
+    const char **ppms = malloc(sizeof(char *) * (size_t)argc);          /* every --ppm, in order */
+    int n_ppm = 0;
+    if (!ppms) return 1;
     const char *h5 = NULL, *ppm = NULL, *segment = NULL, *wfile = "weights_c.txt", *image = "Cat_Image0.ppm";
     int fit = MBN_FIT_CROP;
     float crop_fraction = 1.0f;
@@ -396,7 +400,7 @@ int main(int argc, char **argv)
     float alpha = 0.f;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--h5") && i + 1 < argc) h5 = argv[++i];
-        else if (!strcmp(argv[i], "--ppm") && i + 1 < argc) ppm = argv[++i];
+        else if (!strcmp(argv[i], "--ppm") && i + 1 < argc) ppms[n_ppm++] = argv[++i];
         else if (!strcmp(argv[i], "--weights") && i + 1 < argc) wfile = argv[++i];
         else if (!strcmp(argv[i], "--image") && i + 1 < argc) image = argv[++i];
         else if (!strcmp(argv[i], "--batch") && i + 1 < argc) batch = atoi(argv[++i]);
@@ -424,12 +428,14 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--literal")) literal = 1;
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
-            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F [--fit crop|stretch] [--crop-fraction F]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] "
+            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch] [--crop-fraction F]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] "
                             "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n", argv[0]);
             return 2;
         }
     }
     if (!(crop_fraction > 0.f) || !(crop_fraction <= 1.f)) { fprintf(stderr, "bad --crop-fraction (0 < F <= 1)\n"); return 2; }
+    if (n_ppm > 1 && n_ppm > batch) { fprintf(stderr, "%d --ppm files need --batch %d at least\n", n_ppm, n_ppm); return 2; }
+    if (n_ppm == 1) ppm = ppms[0];
     if (out_stride != 0 && out_stride != 8 && out_stride != 16 && out_stride != 32) { fprintf(stderr, "bad --output-stride (32, 16 or 8)\n"); return 2; }
     mbn_context *ctx = NULL;
     if (gpus > 0 && !literal) {
@@ -483,7 +489,37 @@ int main(int argc, char **argv)
     unsigned char *src = NULL;          /* the image at its own size */
     if (ppm && ppm_size(ppm, &pw, &ph) == MBN_OK && pw <= PPM_MAX_SIDE && ph <= PPM_MAX_SIDE && (src = malloc((size_t)pw * ph * 3)) != NULL)
         have = mbn_read_ppm(ppm, src, &pw, &ph, pw * ph) == MBN_OK;
-    if (have && pw == cols && ph == rows) {
+    if (n_ppm > 1) {
+        /* files of different sizes: uploaded one behind the other into ONE buffer and resized by one ragged launch; slots n_ppm.. repeat image 0 */
+        int64_t *offs = malloc(sizeof(int64_t) * (size_t)n_ppm);
+        int32_t *hs = malloc(sizeof(int32_t) * (size_t)n_ppm), *ws = malloc(sizeof(int32_t) * (size_t)n_ppm);
+        if (!offs || !hs || !ws) return 1;
+        size_t total = 0;
+        for (int n = 0; n < n_ppm; n++) {
+            if (ppm_size(ppms[n], &pw, &ph) != MBN_OK || pw > PPM_MAX_SIDE || ph > PPM_MAX_SIDE) {
+                fprintf(stderr, "%s is not a readable P6 image of at most %d x %d pixels\n", ppms[n], PPM_MAX_SIDE, PPM_MAX_SIDE);
+                return 2;
+            }
+            offs[n] = (int64_t)total; hs[n] = ph; ws[n] = pw;
+            total += (size_t)pw * ph * 3;
+        }
+        unsigned char *all = malloc(total);
+        if (!all) return 1;
+        for (int n = 0; n < n_ppm; n++) {
+            pw = ws[n]; ph = hs[n];
+            if (mbn_read_ppm(ppms[n], all + offs[n], &pw, &ph, pw * ph) != MBN_OK) { fprintf(stderr, "cannot read %s\n", ppms[n]); return 2; }
+        }
+        void *d_src, *d_img;
+        CHECK(mbn_alloc(ctx, total, &d_src));
+        CHECK(mbn_upload(ctx, d_src, all, total));
+        CHECK(mbn_net_resize_inputs(net, d_src, offs, hs, ws, n_ppm, fit, crop_fraction, &d_img));
+        CHECK(mbn_download(ctx, u8, d_img, (size_t)n_ppm * img));
+        CHECK(mbn_free(ctx, d_src));
+        for (int n = n_ppm; n < batch; n++) memcpy(u8 + (size_t)n * img, u8, img);
+        for (int n = 0; n < n_ppm; n++)
+            printf("image %d: %s, %d wide, %d high, resized to %d x %d (%s)\n", n, ppms[n], ws[n], hs[n], cols, rows, fit == MBN_FIT_CROP ? "crop" : "stretch");
+        free(all); free(offs); free(hs); free(ws);
+    } else if (have && pw == cols && ph == rows) {
         for (int n = 0; n < batch; n++) memcpy(u8 + (size_t)n * img, src, img);
     } else if (have) {
         /* any other size: resized on the device into the net's staging buffer; the batch is `batch` copies of that image, as above */
@@ -527,6 +563,7 @@ int main(int argc, char **argv)
     printf("top-%d:", topk);
     for (int j = 0; j < topk; j++) printf(" %d (%f)", arg[j] + 1, probs[j]);
     printf("\n");
+    for (int n = 0; n_ppm > 1 && n < n_ppm; n++) printf("top-1 of image %d (%s): %d (%f)\n", n, ppms[n], arg[n * topk] + 1, probs[n * topk]);
     if (segment) {
         void *d_labels;
         int *labels = malloc(sizeof(int) * (size_t)rows * cols);
@@ -541,6 +578,6 @@ int main(int argc, char **argv)
     mbn_net_destroy(net);
     mbn_weights_free(&w);
     mbn_shutdown(ctx);
-    free(u8); free(arg); free(probs);
+    free(u8); free(arg); free(probs); free(ppms);
     return 0;
 }

@@ -458,6 +458,37 @@ typedef struct mbn_resizer mbn_resizer;
 int  mbn_resizer_create(mbn_context *ctx, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r);
 int  mbn_resize_u8(mbn_resizer *r, void *out_u8, const void *in_u8, int batch, void *stream);
 int  mbn_resizer_destroy(mbn_resizer *r);
+/* Ragged resize (mbn_u8_resize_ragged.hip): ONE launch takes `batch` images, each with its own rows, cols and box, to one common
+ * [batch][out_rows][out_cols][3]. The arithmetic is the one above, byte for byte; what differs is where the taps are formed: no table is built on the
+ * host and none crosses to the device. The kernel evaluates the expressions above itself, in fp64 with the float32 subtraction, truncating casts, the
+ * sum in order, a true division and no contraction into fused multiply-adds, per tile, straight into LDS. An image is an
+ * mbn_resize_item: src_offset = bytes from the launch's src pointer to its first byte (any value >= 0, any order, two items may share one), rows, cols,
+ * and its box (all four edges; the whole image is (0, 0, cols, rows)). Envelope per image: that of mbn_resizer_create.
+ *   mbn_ragged_resizer_create   allocates everything once: descriptors of max_batch (1..65535) images on the device and a pinned host copy. The
+ *                               handle belongs to the context: mbn_shutdown frees the ones still alive
+ *   mbn_ragged_resizer_set      checks every item (MBN_EINVAL: a bad box, a bad size, a negative offset, batch outside 1..max_batch;
+ *                               MBN_EUNSUPPORTED: any one item outside the envelope), plans the tiles (per image a few evaluations of lo / hi per
+ *                               tile: no table) and enqueues ONE asynchronous copy of the descriptors on `stream`. No allocation. It first WAITS
+ *                               for the handle's previous copy and launches, whatever their streams: they read what it overwrites. A set is not
+ *                               part of a graph (a capturing `stream`: MBN_EINVAL). A failed set leaves the handle without a batch: a launch
+ *                               then answers MBN_EINVAL
+ *   mbn_resize_ragged_u8        the launch, asynchronous on `stream`, ordered behind the set by the stream (another stream: the caller orders
+ *                               them). No host allocation, no blocking call: it may be captured between mbn_graph_begin / _end as one kernel node;
+ *                               a captured launch belongs to the batch set when it was captured, and replayed after another set it does nothing.
+ *                               ANY byte pointer for src and out. The mbn_alloc bounds rule applies: src spans max(src_offset + rows * cols * 3)
+ *                               bytes, out batch * out_rows * out_cols * 3; an undersized tracked buffer is MBN_EINVAL and nothing is launched. No
+ *                               byte outside the images and the output is read or written
+ *   mbn_resize_taps_device      the kernel's own tap function for one axis, into int32 DEVICE arrays first [out_size], count [out_size],
+ *                               weights [out_size][ksize] (zero padded), on the context's stream: what mbn_resize_taps gives on the host, so the
+ *                               device arithmetic is pinned as tables and not only through bytes. Returns ksize or a negative status
+ *                               (MBN_EUNSUPPORTED beyond in_size 8192, out_size 4096 or 67 taps) */
+typedef struct mbn_resize_item { int64_t src_offset; int32_t rows, cols; float box[4]; } mbn_resize_item;   /* 32 bytes */
+typedef struct mbn_ragged_resizer mbn_ragged_resizer;
+int  mbn_ragged_resizer_create(mbn_context *ctx, int max_batch, int out_rows, int out_cols, mbn_ragged_resizer **r);
+int  mbn_ragged_resizer_set(mbn_ragged_resizer *r, const mbn_resize_item *items, int batch, void *stream);
+int  mbn_resize_ragged_u8(mbn_ragged_resizer *r, void *out_u8, const void *src_u8, void *stream);
+int  mbn_ragged_resizer_destroy(mbn_ragged_resizer *r);
+int  mbn_resize_taps_device(mbn_context *ctx, int in_size, float b0, float b1, int out_size, void *first_i32, void *count_i32, void *weights_i32);
 
 /* fp32 <-> bf16 (round to nearest even) on device; used to build the bf16 copy of the pointwise/FC filters. */
 int mbn_convert_f32_to_bf16(mbn_context *ctx, void *dst_bf16, const void *src_f32, size_t count, void *stream);
@@ -670,6 +701,11 @@ int  mbn_net_set_input_u8(mbn_net *net, int enabled);
  * first call, freed by mbn_net_destroy; MBN_ENOMEM leaves the net usable). Changes nothing in any forward path. */
 int  mbn_net_resize_input(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, float crop_fraction,
                           void **images_u8);
+/* The same for images of DIFFERENT sizes: image i is [rows[i]][cols[i]][3] uint8 at src_u8 + offsets[i] (device; bytes, >= 0, any order). One
+ * mbn_fit_box per image against the plan's rows x cols, then ONE ragged launch (mbn_resize_ragged_u8 above) into the same staging buffer. The net keeps
+ * one ragged resizer of max_batch images, created on the first call and freed by mbn_net_destroy. Any dtype, any plan; no forward path changes. */
+int  mbn_net_resize_inputs(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *rows, const int32_t *cols, int batch, int fit,
+                           float crop_fraction, void **images_u8);
 int  mbn_net_fused_layers(const mbn_net *net, int last_layer, int *count);
 /* Fused depthwise->pointwise blocks (mbn_dwpw_fused): bit L of `mask` (L = 1-based number of a depthwise layer) lets
  * layers L and L+1 run as one launch when the plan is fp32, activations are not kept and the shapes are inside the

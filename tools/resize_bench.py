@@ -15,6 +15,17 @@
       tables reach, once, plus the output — over 8 TB/s. Then the forward the resize precedes (1.0x224, uint8 input): fp32 at batch 256 and bf16
       at batch 512, and the resize's share of it. The kernel's output is compared once with tests/resize_ref.py on image 0 (agreement, not timing).
       One JSON object at the end. No GPU: the Context raises; nothing falls back.
+
+  python tools/resize_bench.py --ragged [--seed 1] [--batch 256] [--reps 7] [--steps 20]
+      The ragged resize (mbn_resize_ragged_u8) on a seeded batch of images of DIFFERENT sizes: rows 300-600, cols 300-700, each through its crop-0.875
+      box to 224 x 224; the batch is built once and its seed printed. Two comparisons, the forms alternating within every repetition:
+        mixed    the batch one image at a time, mbn_resize_u8 at batch 1 with one resizer per image built beforehand and NOT timed (the best case of
+                 doing without the ragged launch); the same including the builds (create, launch, destroy per image: what mbn_net_resize_input pays
+                 when every image has another size); and the ragged way, set + ONE launch
+        uniform  `batch` x 375 x 500: mbn_resize_u8 (tables from the host) against the ragged launch alone and with its set: the price of forming the
+                 taps on the device and of the descriptor lookup
+      Every figure is a host clock around `steps` calls that end in a device synchronise, in ms per batch: median over the repetitions and their
+      range. The ragged output of both batches is compared once with the table kernel's bytes, image by image (agreement, not timing).
 """
 import argparse
 import json
@@ -52,6 +63,92 @@ def marks_ms(ctx, fn, steps):
     return sum(ctx.marks_read(4)) / steps
 
 
+def wall_ms(ctx, fn, steps):
+    """ms per call of fn: a host clock around `steps` calls and the synchronise behind them"""
+    import time
+    ctx.sync()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        fn()
+    ctx.sync()
+    return (time.perf_counter() - t0) * 1e3 / steps
+
+
+def figure(runs):
+    return {"median_ms": round(statistics.median(runs), 4), "min_ms": round(min(runs), 4), "max_ms": round(max(runs), 4), "runs_ms": [round(x, 4) for x in runs]}
+
+
+def ragged_main(a):
+    pkg = import_package()
+    import torch
+    assert torch.cuda.is_available(), "the buffers are torch tensors on the same GPU"
+    rng = np.random.default_rng(a.seed)
+    n = a.batch
+    print("ragged: seed %d, batch %d, rows 300-600 x cols 300-700 -> %d x %d, crop 0.875" % (a.seed, n, RES, RES), flush=True)
+    batches = {"mixed": [(int(rng.integers(300, 601)), int(rng.integers(300, 701))) for _ in range(n)], "uniform": [(375, 500)] * n}
+    result = {"seed": a.seed, "batch": n, "steps": a.steps, "reps": a.reps}
+    with pkg.Context(0) as ctx:
+        forms = {}
+        for name, sizes in batches.items():
+            offs = np.concatenate([[0], np.cumsum([h * w * 3 for h, w in sizes])]).astype(np.int64)
+            t_src = torch.randint(0, 256, (int(offs[-1]),), dtype=torch.uint8, device="cuda")
+            t_one, t_rag = (torch.zeros((n, RES, RES, 3), dtype=torch.uint8, device="cuda") for _ in range(2))
+            torch.cuda.synchronize()
+            boxes = [pkg.fit_box(h, w, RES, RES, pkg.FIT_CROP, 0.875) for h, w in sizes]
+            items = pkg.resize_items([(int(o), h, w, b) for o, (h, w), b in zip(offs, sizes, boxes)])
+            src, one, rag, img = t_src.data_ptr(), t_one.data_ptr(), t_rag.data_ptr(), RES * RES * 3
+            rr = pkg.RaggedResizer(ctx, n, RES, RES)
+
+            def ragged(rr=rr, items=items, rag=rag, src=src):
+                rr.set(items)
+                rr.run(rag, src)
+
+            def with_builds(sizes=sizes, boxes=boxes, offs=offs, one=one, src=src):
+                for i, ((h, w), b) in enumerate(zip(sizes, boxes)):
+                    rz = pkg.Resizer(ctx, h, w, RES, RES, b)
+                    rz.run(one + i * img, src + int(offs[i]), 1)
+                    rz.close()
+
+            f = {"ragged_set_and_launch": ragged}
+            if name == "mixed":
+                built = [pkg.Resizer(ctx, h, w, RES, RES, b) for (h, w), b in zip(sizes, boxes)]
+                f["one_by_one_prebuilt"] = lambda built=built, offs=offs, one=one, src=src: [rz.run(one + i * img, src + int(offs[i]), 1) for i, rz in enumerate(built)]
+                f["one_by_one_with_builds"] = with_builds
+            else:
+                built = [pkg.Resizer(ctx, 375, 500, RES, RES, boxes[0])]
+                f["table_kernel"] = lambda rz=built[0], one=one, src=src: rz.run(one, src, n)
+                f["ragged_launch_alone"] = lambda rr=rr, rag=rag, src=src: rr.run(rag, src)
+            for fn in f.values():                           # warm-up of every timed form; the last ragged set stays for the launch alone
+                fn()
+            ragged()
+            f[next(k for k in f if k != "ragged_set_and_launch")]()
+            ctx.sync()
+            differ = int((t_one != t_rag).sum().item())
+            forms[name] = dict(f=f, runs={k: [] for k in f}, differ=differ, keep=(t_src, t_one, t_rag, built, rr), src_bytes=int(offs[-1]))
+        for _ in range(a.reps):
+            for name, r in forms.items():
+                for k, fn in r["f"].items():
+                    steps = max(1, a.steps // 10) if k == "one_by_one_with_builds" else a.steps
+                    r["runs"][k].append(wall_ms(ctx, fn, steps))
+        for name, r in forms.items():
+            out = {k: figure(v) for k, v in r["runs"].items()}
+            out["bytes_differ_from_table_kernel"] = r["differ"]
+            out["src_bytes"] = r["src_bytes"]
+            med = {k: v["median_ms"] for k, v in out.items() if isinstance(v, dict)}
+            if name == "mixed":
+                out["prebuilt_over_ragged"] = round(med["one_by_one_prebuilt"] / med["ragged_set_and_launch"], 2)
+                out["with_builds_over_ragged"] = round(med["one_by_one_with_builds"] / med["ragged_set_and_launch"], 2)
+            else:
+                out["ragged_launch_over_table"] = round(med["ragged_launch_alone"] / med["table_kernel"], 3)
+            result[name] = out
+            print("%-8s %s  differing bytes %d" % (name, "  ".join("%s %.4f ms (%.4f-%.4f)" % (k, out[k]["median_ms"], out[k]["min_ms"], out[k]["max_ms"])
+                                                                    for k in r["runs"]), r["differ"]), flush=True)
+            for rz in r["keep"][3]:
+                rz.close()
+            r["keep"][4].close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
@@ -59,7 +156,12 @@ def main():
     ap.add_argument("--configs", default="", help="comma list of geometry names (default: all)")
     ap.add_argument("--no-torch", action="store_true", help="skip the torch yardstick")
     ap.add_argument("--no-forward", action="store_true", help="skip the forwards the resize is compared with")
+    ap.add_argument("--ragged", action="store_true", help="the ragged resize against one launch per image and against the table kernel")
+    ap.add_argument("--seed", type=int, default=1, help="--ragged: seed of the batch's size list")
+    ap.add_argument("--batch", type=int, default=256, help="--ragged: images per batch")
     a = ap.parse_args()
+    if a.ragged:
+        return ragged_main(a)
     chosen = [c for c in CONFIGS if not a.configs or c[0] in a.configs.split(",")]
     pkg = import_package()
     import resize_ref
