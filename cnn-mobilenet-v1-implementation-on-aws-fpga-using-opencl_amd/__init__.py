@@ -190,6 +190,7 @@ def load():
         lib.mbn_device_count.argtypes = [C.POINTER(ci)]
         lib.mbn_device_name.argtypes = [vp, C.c_char_p, C.c_size_t]
         lib.mbn_device_cus.argtypes = [vp, C.POINTER(C.c_int)]
+        lib.mbn_set_planning_cus.argtypes = [vp, ci]
         lib.mbn_device_pci_bus_id.argtypes = [vp, C.c_char_p, C.c_size_t]
         lib.mbn_pw_clock_read.argtypes = [vp, ci, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
         lib.mbn_set_literal_quirks.argtypes = [vp, C.c_uint32]
@@ -477,6 +478,16 @@ class Context:
         b = C.create_string_buffer(64)
         _chk(self.lib.mbn_device_pci_bus_id(self.h, b, 64), self.last_error())
         return b.value.decode()
+
+    def device_cus(self) -> int:
+        """mbn_device_cus: the count the launches are planned for (the device's own unless set_planning_cus changed it)."""
+        n = C.c_int()
+        _chk(self.lib.mbn_device_cus(self.h, C.byref(n)), "mbn_device_cus")
+        return n.value
+
+    def set_planning_cus(self, cus: int):
+        """mbn_set_planning_cus: plan every launch for `cus` compute units (0 = the device's own count). Not while launches are in flight."""
+        _chk(self.lib.mbn_set_planning_cus(self.h, int(cus)), "mbn_set_planning_cus(%d)" % cus)
 
     def pw_clock(self, reset=True):
         """(GHz, launches): the core clock held inside the pw_gemm launches recorded since the last reset (tune key pw_clock)."""

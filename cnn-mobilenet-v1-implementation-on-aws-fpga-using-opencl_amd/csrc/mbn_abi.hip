@@ -170,7 +170,7 @@ int mbn_init(int device_ordinal, mbn_context **out)
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device_ordinal) == hipSuccess) {
         snprintf(ctx->name, sizeof(ctx->name), "%s (%s)", prop.name, prop.gcnArchName);
-        ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        ctx->num_cus = ctx->device_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
     *out = ctx;
     return MBN_OK;
@@ -216,6 +216,13 @@ int mbn_device_cus(mbn_context *ctx, int *count)
 {
     if (!ctx || !count) return MBN_EINVAL;
     *count = ctx->num_cus;
+    return MBN_OK;
+}
+
+int mbn_set_planning_cus(mbn_context *ctx, int cus)
+{
+    if (!ctx || cus < 0 || cus > ctx->device_cus) return MBN_EINVAL;
+    ctx->num_cus = cus ? cus : ctx->device_cus;
     return MBN_OK;
 }
 

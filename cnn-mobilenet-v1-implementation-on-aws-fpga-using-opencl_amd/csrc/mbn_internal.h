@@ -52,7 +52,8 @@ struct mbn_context {
     uint32_t literal_quirks = MBN_QUIRKS_KERNEL_CL;
     char last_error[256] = {0};
     char name[128] = {0};
-    int num_cus = 256;
+    int num_cus = 256;                           // the PLANNING count every launcher reads: the device's, or fewer (mbn_set_planning_cus)
+    int device_cus = 256;                        // compute units of the device itself
     std::vector<hipEvent_t> sync_events;         // mbn_stream_wait: reusable fork/join events (round robin)
     size_t sync_next = 0;
     std::vector<hipEvent_t> pool;                // mbn_profile_begin/end: 2 events per recorded call

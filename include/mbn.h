@@ -144,7 +144,17 @@ int  mbn_shutdown(mbn_context *ctx);
 int  mbn_device_count(int *count);                       /* 0 devices => *count = 0, MBN_OK */
 int  mbn_device_name(mbn_context *ctx, char *buf, size_t buflen);
 int  mbn_device_cus(mbn_context *ctx, int *count);       /* compute units of the context's GPU (256 on MI355X): the counterpart of
-                                                          * CL_DEVICE_MAX_COMPUTE_UNITS; the net runner sizes its small-batch choices by it */
+                                                          * CL_DEVICE_MAX_COMPUTE_UNITS; the net runner sizes its small-batch choices by it.
+                                                          * After mbn_set_planning_cus it is the PLANNING count, so a net created
+                                                          * afterwards plans with that */
+/* Plan every launch of this context for `cus` compute units instead of the device's own count: persistent grids, the per-XCD tile
+ * distributions and the count-dependent kernel choices all size themselves by it. 1 <= cus <= the device's count; 0 restores the
+ * device's count; anything else, or a NULL context, is MBN_EINVAL (a grid larger than the device offers nothing). A smaller
+ * persistent grid is always legal (no kernel waits on another workgroup) and every kernel's result is the same bits at every count.
+ * For tests (the tile loops' multi-round paths are reached by small shapes at small counts) and for a caller that shares the device
+ * with other work. It costs a launch nothing. Do not change it while launches of this context are in flight or while a graph is
+ * being captured; a net (mbn_net_create) keeps the count it was created under. */
+int  mbn_set_planning_cus(mbn_context *ctx, int cus);
 int  mbn_device_pci_bus_id(mbn_context *ctx, char *buf, size_t buflen);   /* "0000:05:00.0": which physical GPU this context holds. The
                                                           * reference picks device 0 of platform 0 (MobileNet.c:155); with one context
                                                           * per rank the multi-GPU bench line proves its ranks held N cards */

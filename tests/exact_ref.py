@@ -371,13 +371,13 @@ def chain_case(n, h, w, chans, strides, seed=0, images=None, first_density=1.0, 
     return layers
 
 
-def stem_case(n, rows, cols, c1, c3, density=1.0, seed=0):
-    """conv1 3x3x3 stride 2 -> depthwise stride 1 -> pointwise, every output rounded to bf16 (the bf16 fused stem)."""
+def stem_case(n, rows, cols, c1, c3, density=1.0, seed=0, rounded=True):
+    """conv1 3x3x3 stride 2 -> depthwise stride 1 -> pointwise, every output rounded to bf16 (the bf16 fused stem), or none (rounded False: the fp32 one)."""
     rng = np.random.default_rng([6, n, rows, cols, c1, c3, seed])
     img = gen_image(rng, (n, rows, cols, 3))
-    a = make_layer(rng, "conv1", img, gen_conv1_filter(rng, c1, density))
-    d = make_layer(rng, "dw", a.out, gen_dw_filter(rng, c1, first=False), stride=1, pad_top=1, pad_left=1)
-    p = make_layer(rng, "pw", d.out, gen_pw_filter(rng, c3, c1), rounded=True)
+    a = make_layer(rng, "conv1", img, gen_conv1_filter(rng, c1, density), rounded=rounded)
+    d = make_layer(rng, "dw", a.out, gen_dw_filter(rng, c1, first=False), rounded=rounded, stride=1, pad_top=1, pad_left=1)
+    p = make_layer(rng, "pw", d.out, gen_pw_filter(rng, c3, c1), rounded=rounded)
     return [a, d, p]
 
 

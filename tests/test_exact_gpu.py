@@ -65,7 +65,8 @@ def pw_route_eligible(knobs, shape, cus=256, act=2):
     if ring == 6:
         return k in (256, 512, 1024) and n % 256 == 0 and m >= 4 * 196
     if ring == 7:
-        return k % 64 == 0 and k >= 128 and n % 256 == 0 and (m // 256) * (n // 256) // cus * cus >= cus
+        tiles = (m // 256) * (n // 256) // cus * cus if n % 256 == 0 else 0
+        return k % 64 == 0 and k >= 128 and n % 256 == 0 and tiles - tiles % (n // 256) >= cus       # (whole rounds, then whole row tiles)
     if ring == 8:
         return k == 512 and n % 256 == 0 and cus >= 8 * (n // 256)
     if knobs.get("pw_emul"):
@@ -164,7 +165,7 @@ def _tune_lab(ctx, key, value):
     assert rc == 0, rc
 
 
-LAB_KNOBS = ("pw_ring", "misc", "exp0", "dw_nseg")
+LAB_KNOBS = ("pw_ring", "misc", "exp0", "dw_nseg", "dwpw_variant", "pw_xn", "exp1", "exp2")
 MBN_STEM_BF16 = 2                                            # include/mbn.h
 
 
@@ -277,11 +278,13 @@ def block_params(dev, layers):
 
 # ----------------------------------------------------------------------------- bf16 pointwise
 
-def _run_pw(pkg, ctx, l, knobs=None, packed=False, dtype=None):
+def _run_pw(pkg, ctx, l, knobs=None, packed=False, dtype=None, in_envelope=True):
+    """One pointwise call, compared with the layer's exact bits; returns the bits. in_envelope False: the caller has shown that the forced kernel does
+    NOT take this call (a planning CU count outside its envelope) and checks whatever kernel does."""
     m, k = l.x.reshape(-1, l.x.shape[-1]).shape
     n = l.w.shape[0]
     bf = dtype != "f32"
-    assert pw_route_eligible(knobs or {}, (m, k, n), _cus(ctx), l.act), "the forced kernel would not take this call on this device: %s %s" % (knobs, (m, k, n))
+    assert pw_route_eligible(knobs or {}, (m, k, n), _cus(ctx), l.act) == in_envelope, "the forced kernel would %stake this call on this device: %s %s" % ("not " if in_envelope else "", knobs, (m, k, n))
     with Dev(pkg, ctx) as dev, Knobs(ctx, knobs or {}):
         d_x = dev.bf16(l.x) if bf else dev.f32(l.x)
         flag = 0
@@ -299,6 +302,7 @@ def _run_pw(pkg, ctx, l, knobs=None, packed=False, dtype=None):
         ctx.pointwise(d_o.ptr, d_x.ptr, d_f.ptr, m, 1, k, n, ext)
         got = dev.fetch(d_o, m * n, np.uint32 if out_f32 else np.uint16)
     same_bits(got, want_bits(pkg, l), "pointwise (%d, %d, %d) act %d %s" % (m, k, n, l.act, knobs or ""))
+    return got
 
 
 @pytest.mark.parametrize("act", [2, 0])
@@ -337,6 +341,7 @@ def _run_dw(pkg, ctx, l, knobs=None, dtype=None):
         ctx.depthwise(d_o.ptr, d_x.ptr, d_f.ptr, oh, ow, 3, g["stride"], c, ext)
         got = dev.fetch(d_o, l.y.size, np.uint16 if bf else np.uint32)
     same_bits(got, want_bits(pkg, l), "depthwise %s %s %s" % (l.x.shape, g, knobs or ""))
+    return got
 
 
 @pytest.mark.parametrize("case", DW_CASES, ids=lambda c: "%dx%dx%d-s%d%s" % (c[0], c[1], c[2], c[3], "".join("-%s%d" % kv for kv in sorted(c[4].items()))))
@@ -387,6 +392,7 @@ def _run_block(pkg, ctx, layers, knobs=None, dtype=None):
         assert rc == 0, rc
         got = dev.fetch(d_o, p.y.size, np.uint16 if bf else np.uint32)
     same_bits(got, want_bits(pkg, p), "fused block %s -> %s %s %s" % (d.x.shape, p.y.shape, d.geom, knobs or ""))
+    return got
 
 
 @pytest.mark.parametrize("shape", BLOCK_CASES)
@@ -416,8 +422,11 @@ def test_bf16_blocks_resident_exact(pkg, ctx, case):
     every layer output drops the fine bits of all but its smallest values — the gate measures max sum|terms| = 2^22.2 grid units for 2, 3, 5 and 8 blocks
     alike (test_exact_cpu.py asserts it below 2^24 for each). 600 images are four distinct ones tiled: every image of every pass of the persistent grid
     is compared."""
+    _run_res(pkg, ctx, case, res_layers(case))
+
+
+def _run_res(pkg, ctx, case, layers):
     n, h, w, nblk = case
-    layers = res_layers(case)
     x, y = layers[0].x, layers[-1]
     reps = -(-n // x.shape[0])
     with Dev(pkg, ctx) as dev:
@@ -429,14 +438,18 @@ def test_bf16_blocks_resident_exact(pkg, ctx, case):
         got = dev.fetch(d_o, n * h * w * 256, np.uint16)
     want = np.tile(want_bits(pkg, y).reshape(x.shape[0], -1), (reps, 1))[:n]
     same_bits(got, want, "resident blocks %s" % (case,))
+    return got
 
 
 @pytest.mark.parametrize("case", TAIL_CASES, ids=lambda c: "%dx%dx%d" % c)
 def test_bf16_tail_resident_exact(pkg, ctx, case):
     """mbn_tail_resident_bf16: depthwise stride 2 (256) -> pointwise 256 -> 512 -> depthwise -> pointwise 512 -> 512 -> whole-map mean, every stage
     rounded to bf16; the pooled map has a power-of-two pixel count, so the mean is exact before its rounding."""
+    _run_tail(pkg, ctx, case, tail_layers(case))
+
+
+def _run_tail(pkg, ctx, case, layers):
     n, h, w = case
-    layers = tail_layers(case)
     with Dev(pkg, ctx) as dev:
         d_x = dev.bf16(layers[0].x)
         arr = block_params(dev, layers)
@@ -445,25 +458,33 @@ def test_bf16_tail_resident_exact(pkg, ctx, case):
         assert rc == 0, rc
         got = dev.fetch(d_o, n * 512, np.uint16)
     same_bits(got, want_bits(pkg, layers[-1]), "resident tail %s" % (case,))
+    return got
 
 
 @pytest.mark.parametrize("case", STEM_CASES, ids=lambda c: "%dx%dx%d-%d-%d" % c)
 def test_bf16_fused_stem_exact(pkg, ctx, case):
     """mbn_stem_fused_hw with MBN_STEM_BF16 through the C-ABI: integer conv1 (all 27 taps live: no thinning was needed for the gate), depthwise and
     pointwise filters, the image on a 1/8 grid in [-1, 1], both on-chip intermediates rounded to bf16; alpha 1.0 and 0.5 channel counts, 32 x 32 and 32 x 64."""
+    _run_stem(pkg, ctx, case, stem_layers(case))
+
+
+def _run_stem(pkg, ctx, case, layers, dtype=None):
+    """mbn_stem_fused_hw in bf16 (MBN_STEM_BF16) or, dtype "f32", in fp32 (layers built with rounded False: fp32 filter, fp32 bits out)"""
     n, rows, cols, c1, c3 = case
-    a, d, p = stem_layers(case)
+    a, d, p = layers
+    bf = dtype != "f32"
     with Dev(pkg, ctx) as dev:
         d_img = dev.f32(a.x)
         w1, s1, b1 = dev.params(a)
         wd, s2, b2 = dev.params(d)
-        wp, s3, b3 = dev.params(p)
-        d_o = dev.out(p.y.size, 2)
+        wp, s3, b3 = dev.params(p) if bf else (dev.f32(p.w), dev.f32(p.scale), dev.f32(p.shift))
+        d_o = dev.out(p.y.size, 2 if bf else 4)
         rc = ctx.lib.mbn_stem_fused_hw(ctx.h, d_o.ptr, d_img.ptr, w1.ptr, s1.ptr, b1.ptr, wd.ptr, s2.ptr, b2.ptr, wp.ptr, s3.ptr, b3.ptr,
-                                       n, rows, cols, c1, c3, MBN_STEM_BF16, None)
+                                       n, rows, cols, c1, c3, MBN_STEM_BF16 if bf else 0, None)
         assert rc == 0, rc
-        got = dev.fetch(d_o, p.y.size, np.uint16)
-    same_bits(got, want_bits(pkg, p), "bf16 fused stem %s" % (case,))
+        got = dev.fetch(d_o, p.y.size, np.uint16 if bf else np.uint32)
+    same_bits(got, want_bits(pkg, p), "%s fused stem %s" % ("bf16" if bf else "fp32", case))
+    return got
 
 
 # ----------------------------------------------------------------------------- fp32 kernels: same generators, nothing rounded
