@@ -93,6 +93,11 @@ class ResizeDesc(C.Structure):
                [(n, C.c_int32) for n in ("kx", "ky", "toh", "tiles_y", "wg0", "seg_stride", "tmp_off", "lds_bytes")]
 
 
+class ResizePlan(C.Structure):
+    """mbn_resize_plan_t (host/mbn_envelope.h): the tile of a resize geometry and its LDS image"""
+    _fields_ = [(n, C.c_int32) for n in ("kx", "ky", "tow", "toh", "tiles_x", "tiles_y", "seg_stride", "stage_off", "tmp_off", "lds_bytes")]
+
+
 class I8PwPlan(C.Structure):
     """mbn_i8_pw_plan_t (host/mbn_envelope.h): the launch mbn_launch_i8_pointwise issues for a shape"""
     _fields_ = [(n, C.c_int) for n in ("form", "ks", "g", "out_f32", "pt", "threads", "gy", "lds_bytes")] + \
@@ -158,7 +163,8 @@ def _declare_host(lib):
     lib.mbn_fit_box.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float)]
     lib.mbn_resize_envelope.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int]      # mbn_envelope.h: exported, not in mbn.h
     lib.mbn_i8_pw_plan.argtypes = [C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(I8PwPlan)]
-    lib.mbn_resize_window.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, i32p, i32p]      # mbn_envelope.h, like the two below
+    lib.mbn_resize_window.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, i32p, i32p]      # mbn_envelope.h, like the three below
+    lib.mbn_resize_table_plan.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(ResizePlan)]
     lib.mbn_resize_ragged_plan.argtypes = [C.POINTER(ResizeItem), C.c_int, C.c_int, C.POINTER(ResizeDesc)]
     lib.mbn_resize_ragged_plan_batch.argtypes = [C.POINTER(ResizeItem), C.c_int, C.c_int, C.c_int, C.POINTER(ResizeDesc), i32p, i32p, C.POINTER(C.c_int64)]
     return lib
@@ -364,6 +370,14 @@ def resize_window(in_size, b0, b1, out_size, o_first, o_last, lib=None):
     lo, hi = C.c_int32(), C.c_int32()
     _chk((lib or host_lib()).mbn_resize_window(in_size, b0, b1, out_size, o_first, o_last, C.byref(lo), C.byref(hi)), "resize_window")
     return lo.value, hi.value
+
+
+def resize_table_plan(in_rows, in_cols, out_rows, out_cols, box=None, lib=None) -> ResizePlan:
+    """mbn_resize_table_plan: the tile mbn_resizer_create chooses for a geometry (box None = the whole image)."""
+    p = ResizePlan()
+    _chk((lib or host_lib()).mbn_resize_table_plan(in_rows, in_cols, _box4(box), out_rows, out_cols, C.byref(p)),
+         "resize_table_plan(%d, %d, %d, %d)" % (in_rows, in_cols, out_rows, out_cols))
+    return p
 
 
 def resize_ragged_plan(items, out_rows, out_cols, lib=None):

@@ -25,9 +25,7 @@ struct mbn_emul_img {
 struct mbn_resizer {
     mbn_context *ctx = nullptr;
     int in_rows = 0, in_cols = 0, out_rows = 0, out_cols = 0;
-    int kx = 0, ky = 0;                          // taps per output column / row (the tables' row length)
-    int tow = 0, toh = 0, tiles_x = 0, tiles_y = 0;
-    int seg_stride = 0, stage_off = 0, tmp_off = 0, lds_bytes = 0;
+    mbn_resize_plan_t plan = {};                 // mbn_resize_table_plan; kx, ky = taps per output column / row (the tables' row length)
     void *tables = nullptr;                      // device: fx, cx [out_cols], fy, cy [out_rows], wx [out_cols][kx], wy [out_rows][ky], int32
 };
 

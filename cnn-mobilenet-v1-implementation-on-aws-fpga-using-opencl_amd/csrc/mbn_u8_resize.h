@@ -1,0 +1,116 @@
+// mbn_u8_resize.h — the tile body of the resize front-end on gfx950, shared by the table kernel (mbn_u8_resize.hip) and the ragged kernel
+// (mbn_u8_resize_ragged.hip): Pillow's 8-bit bilinear resize of a box of a uint8 HWC image, both passes in ONE launch (include/mbn.h, "resize
+// front-end", is the normative statement of the arithmetic). Each kernel brings its own geometry and its own source of first / count / weights.
+//
+// A workgroup of 256 lanes (MBN_RESIZE_WAVES waves) owns a tile of `toh` output rows x `tow` output columns of one image. The taps say which source
+// rows [y0, y1) and columns [xs0, xs1) the tile needs, and nothing else is read:
+//   horizontal  the waves take the source rows of the window in turn (wave v the rows y0 + v, y0 + v + 4, ...), each at its own pace. A wave stages its
+//               row's segment [xs0, xs1) in LDS (resize_stage_row) and then forms the tile's `tow` x 3 horizontal sums of that row from LDS, each rounded
+//               to uint8 as Pillow rounds its intermediate image, into the window s_tmp [y1 - y0][tow * 3] in LDS (resize_row_sums). The tile's horizontal
+//               weights sit in LDS as well, and every column runs all kx taps: those past its count carry zero padding (the staged row has kx pixels of
+//               slack for them). The staged row is the wave's own and a wave's LDS accesses complete in the order it issues them, so between staging and
+//               summing only the compiler has to keep that order (wave_sync); the waves do not wait for each other;
+//   vertical    behind a barrier the waves take the tile's output rows in turn (resize_vertical): a row's first source row, count and weights are scalars of
+//               the wave, a lane sums three bytes of the row's segment over s_tmp, rounds to uint8 and stores (consecutive lanes, consecutive bytes).
+// The uint8 intermediate never reaches memory. The host sizes the tile so that tables + 4 staged rows + window fit MBN_RESIZE_LDS bytes
+// (host/mbn_resize.c; a 32x downscale has 67 taps per axis: its window alone is 67 + rows, so tiles get flatter as the factor grows; `toh` = 1 always
+// fits). Images are addressed through 64-bit offsets; offsets inside LDS and inside a tile are 32-bit.
+#pragma once
+#include "mbn_internal.h"
+
+namespace {
+
+constexpr int RESIZE_EPL = MBN_RESIZE_TOW(MBN_RESIZE_MAX_OUT) * 3 / 64;      // horizontal sums of a row per lane at most
+
+// orders a wave's LDS writes before its later LDS reads (and the reverse) for data that only this wave touches
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ uint8_t resize_round(int acc)
+{
+    return (uint8_t)min(max(acc >> MBN_RESIZE_BITS, 0), 255);
+}
+
+// This lane's horizontal sums: element e = lane + 64 j of a row of the tile (row_e of them) is column e / 3, channel e % 3. lo[j] = its first byte in
+// the staged segment, wofs[j] = its weights in s_wx [tow][kx]; first(column) = the column's first source column, counted from the segment's
+template <class First>
+__device__ __forceinline__ void resize_lane_elems(int (&lo)[RESIZE_EPL], int (&wofs)[RESIZE_EPL], int lane, int row_e, int kx, First first)
+{
+#pragma unroll
+    for (int j = 0; j < RESIZE_EPL; j++) {
+        const int e = lane + 64 * j, ox = e / 3;
+        const bool on = e < row_e;
+        lo[j] = on ? first(ox) * 3 + (e - 3 * ox) : 0;
+        wofs[j] = on ? ox * kx : 0;
+    }
+}
+
+// Stages the nb bytes at g in the wave's row and returns where byte 0 went: bytewise up to the first 4-byte boundary of the ADDRESS, 4 bytes per lane
+// from there, bytewise for the rest, so any byte pointer and any W * 3 give the same bytes. s_row is on 4 bytes and has nb + 3 bytes of room
+__device__ __forceinline__ const uint8_t *resize_stage_row(uint8_t *s_row, const uint8_t *g, int nb, int lane)
+{
+    const int off = (int)((uintptr_t)g & 3);                     // byte j of the segment goes to s_row[off + j]: a dword of memory is a dword of LDS
+    const int head = min(nb, (4 - off) & 3), body = (nb - head) >> 2, tail0 = head + 4 * body;
+    if (lane < head) s_row[off + lane] = g[lane];
+    for (int i = lane; i < body; i += 64)
+        *reinterpret_cast<uint32_t *>(s_row + off + head + 4 * i) = *reinterpret_cast<const uint32_t *>(g + head + 4 * i);
+    if (tail0 + lane < nb) s_row[off + tail0 + lane] = g[tail0 + lane];
+    wave_sync();
+    return s_row + off;
+}
+
+// the horizontal sums of the staged row s_seg into its row s_out of the window
+__device__ __forceinline__ void resize_row_sums(uint8_t *s_out, const uint8_t *s_seg, const int32_t *s_wx, const int (&lo)[RESIZE_EPL],
+                                                const int (&wofs)[RESIZE_EPL], int kx, int row_e, int lane)
+{
+#pragma unroll
+    for (int j = 0; j < RESIZE_EPL; j++) {
+        const int e = lane + 64 * j;
+        if (e < row_e) {
+            int acc = MBN_RESIZE_HALF;
+            const uint8_t *p = s_seg + lo[j];
+            const int32_t *k = s_wx + wofs[j];
+            for (int t = 0; t < kx; t++) acc += (int)p[3 * t] * k[t];            // past this column's count: a zero weight times a byte of the slack
+            s_out[e] = resize_round(acc);
+        }
+    }
+    wave_sync();                                                 // the next row is staged over this one
+}
+
+// The vertical pass out of the finished window s_tmp [rows][tmp_ld]: wave v takes output rows v, v + 4, ... of the tile's oyn, a lane the bytes lane,
+// lane + 64, lane + 128 of the row's row_e. dst = the tile's first output byte, dst_ld = bytes of an output row. row(oy, f, n) gives the row's weights
+// and sets f = its first row in the window and n = its count: the row is the wave's, so all three are the same for all its lanes. dst is __restrict__
+// (the output is no table and no LDS): only then can the compiler prove that the stores leave the table kernel's counts and weights alone and read
+// them with scalar loads (s_load_dwordx8 for eight taps); without it they are per-lane loads of one address and a v_readfirstlane
+template <class Row>
+__device__ __forceinline__ void resize_vertical(uint8_t *__restrict__ dst, size_t dst_ld, const uint8_t *s_tmp, int tmp_ld, int oyn, int row_e, int lane,
+                                                int wave, Row row)
+{
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    int idx[RESIZE_EPL];
+#pragma unroll
+    for (int j = 0; j < RESIZE_EPL; j++) idx[j] = lane + 64 * j < row_e ? lane + 64 * j : 0;
+    for (int oy = wv; oy < oyn; oy += MBN_RESIZE_WAVES) {
+        int f, n;
+        const int32_t *__restrict__ k = row(oy, f, n);
+        const uint8_t *p = s_tmp + f * tmp_ld;
+        int acc[RESIZE_EPL];
+#pragma unroll
+        for (int j = 0; j < RESIZE_EPL; j++) acc[j] = MBN_RESIZE_HALF;
+        for (int t = 0; t < n; t++) {
+            const int kt = k[t];
+#pragma unroll
+            for (int j = 0; j < RESIZE_EPL; j++) acc[j] += (int)p[t * tmp_ld + idx[j]] * kt;
+        }
+        uint8_t *d = dst + oy * dst_ld;
+#pragma unroll
+        for (int j = 0; j < RESIZE_EPL; j++)
+            if (lane + 64 * j < row_e) d[lane + 64 * j] = resize_round(acc[j]);
+    }
+}
+
+}   // namespace

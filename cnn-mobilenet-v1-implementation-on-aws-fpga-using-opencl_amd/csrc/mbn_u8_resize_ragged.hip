@@ -1,11 +1,9 @@
 // mbn_u8_resize_ragged.hip — the ragged resize on gfx950: ONE launch takes `batch` uint8 HWC images, each with its own rows, cols and box, to one common
 // [batch][oh][ow][3], byte for byte the arithmetic of include/mbn.h ("resize front-end"). mbn_u8_resize.hip is its single-geometry sibling and stays the
-// path of uniform batches; what is the same here is said there: a workgroup of 4 waves owns a tile of toh x tow outputs of one image, the waves stage
-// the source rows of the tile's window in LDS (head / dword body / tail split by address), form the horizontal sums into the uint8 window in LDS and
-// then run the vertical pass out of it. What differs:
-//   taps        no table exists anywhere. The workgroup forms its tile's taps itself, straight into LDS where the horizontal weights lived already:
-//               lane c of wave 0 runs output column c of the tile, lane r of wave 1 output row r, each its <= 67 taps one after the other (axis_taps:
-//               the expressions of host/mbn_resize.c in fp64, contraction off). The vertical weights, first rows and counts sit in LDS as well;
+// path of uniform batches; the tile body is mbn_u8_resize.h's for both. What is this file's own:
+//   taps        no table exists anywhere. The workgroup forms its tile's taps itself, straight into LDS: lane c of wave 0 runs output column c of the
+//               tile, lane r of wave 1 output row r, each its <= 67 taps one after the other (mbn_axis_taps of host/mbn_resize_axis.h: the host's own
+//               expressions, in fp64 with contraction off). The vertical weights, first rows and counts sit in LDS as well;
 //   geometry    per image, from a 64-byte descriptor in device memory (mbn_resize_desc, host/mbn_envelope.h): the caller's item and what the host
 //               planned without a table (host/mbn_resize.c, mbn_resize_ragged_plan): ksize per axis, the tile height, the staged row's stride, the
 //               window's LDS offset, and the image's first workgroup;
@@ -13,22 +11,15 @@
 //               <= w, found by a 64-ary search of the descriptors (each lane probes one, a ballot counts: one probe round up to 64 images, two up to
 //               4096). A (most tiles, batch) grid with early exit would launch batch x out_rows x tiles_x workgroups as soon as ONE image of the
 //               batch is a steep downscale with one-row tiles.
-// The tile's window comes from axis_span at its edge outputs, as the host's plan did (mbn_resize_window): the same expressions on both sides. Should
+// The tile's window comes from mbn_axis_span at its edge outputs, as the host's plan did (mbn_resize_window): the same code on both sides. Should
 // they ever disagree, the kernel's capacity clamps turn that into wrong bytes (which the tests compare) and never into an access outside LDS, the
-// images or the output. lo and hi grow with the output index because every floating operation in them is monotonic, so a tile's first and last
-// outputs bound the windows of all of them.
-#include "mbn_internal.h"
+// images or the output.
+#include "mbn_resize_axis.h"
+#include "mbn_u8_resize.h"
 
 #include <new>
 
-// The taps must equal the host's bit for bit, and the host build (baseline x86-64) has no fused multiply-add: nothing in this file may contract.
-// (The fp64 division expands to its correctly rounded sequence; that is the division itself, not a contraction.)
-#pragma clang fp contract(off)
-
 namespace {
-
-constexpr int RAGGED_EPL = 64 * 3 / 64;      // horizontal sums of a row per lane at most (tow <= 64)
-constexpr int RAGGED_HALF = 1 << 21, RAGGED_SHIFT = 22;
 
 // head of the device block, in front of the descriptors; 64 bytes like them
 struct RaggedHead {
@@ -46,69 +37,6 @@ struct RaggedArgs {
     int lds_bytes;           // the launch's dynamic LDS
     int generation;          // of the set this launch was issued (or captured) for
 };
-
-struct Axis {
-    double b0, scale, fs;    // fs = support = max(scale, 1)
-    int in_size;
-};
-
-__device__ __forceinline__ Axis axis_of(int in_size, float b0, float b1, int out_size)
-{
-    const float extent = b1 - b0;                                // the subtraction in float32, everything behind it in double
-    Axis a;
-    a.in_size = in_size;
-    a.b0 = (double)b0;
-    a.scale = (double)extent / (double)out_size;
-    a.fs = a.scale < 1.0 ? 1.0 : a.scale;
-    return a;
-}
-
-// [lo, hi) of output i and its centre: axis_span of host/mbn_resize.c
-__device__ __forceinline__ double axis_span(const Axis &a, int i, int &lo, int &hi)
-{
-    const double center = a.b0 + ((double)i + 0.5) * a.scale;
-    lo = max((int)(center - a.fs + 0.5), 0);                     // the casts truncate toward zero
-    hi = min((int)(center + a.fs + 0.5), a.in_size);
-    return center;
-}
-
-__device__ __forceinline__ double axis_weight(const Axis &a, int pos, double center)
-{
-    double x = ((double)pos - center + 0.5) / a.fs;
-    if (x < 0.0) x = -x;
-    return x < 1.0 ? 1.0 - x : 0.0;
-}
-
-// the taps of output i: k[0, ksize) = its 22-bit weights, zero padded; returns the count and its first source position. Two passes over the taps, the
-// weight formed again in the second: a lane has no room for 67 doubles, and the same expression gives the same bits
-__device__ __forceinline__ int axis_taps(const Axis &a, int i, int ksize, int32_t *k, int &first)
-{
-    int lo, hi;
-    const double center = axis_span(a, i, lo, hi);
-    const int n = min(max(hi - lo, 0), ksize);
-    double sum = 0.0;
-    for (int t = 0; t < n; t++) sum += axis_weight(a, t + lo, center);       // w_0 + w_1 + ... in order
-    for (int t = 0; t < n; t++) {
-        double w = axis_weight(a, t + lo, center);
-        if (sum != 0.0) w /= sum;
-        k[t] = (int32_t)(w * 4194304.0 + 0.5);
-    }
-    for (int t = n; t < ksize; t++) k[t] = 0;
-    first = lo;
-    return n;
-}
-
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ uint8_t resize_round(int acc)
-{
-    return (uint8_t)min(max(acc >> RAGGED_SHIFT, 0), 255);
-}
 
 __global__ __launch_bounds__(256, 8) void resize_ragged_u8(const RaggedArgs a)
 {
@@ -132,12 +60,12 @@ __global__ __launch_bounds__(256, 8) void resize_ragged_u8(const RaggedArgs a)
     if (tile < 0 || ty >= d.tiles_y) return;
     const int ox0 = tx * tow, oxn = min(tow, a.ow - ox0), oy0 = ty * toh, oyn = min(toh, a.oh - oy0);
     const int row_e = oxn * 3;                                   // horizontal sums of a source row
-    const Axis gx = axis_of(d.cols, d.box[0], d.box[2], a.ow), gy = axis_of(d.rows, d.box[1], d.box[3], a.oh);
+    const mbn_axis gx = mbn_axis_of(d.cols, d.box[0], d.box[2], a.ow), gy = mbn_axis_of(d.rows, d.box[1], d.box[3], a.oh);
     int xs0, xs1, y0, y1, unused;
-    (void)axis_span(gx, ox0, xs0, unused);
-    (void)axis_span(gx, ox0 + oxn - 1, unused, xs1);
-    (void)axis_span(gy, oy0, y0, unused);
-    (void)axis_span(gy, oy0 + oyn - 1, unused, y1);
+    (void)mbn_axis_span(&gx, ox0, &xs0, &unused);
+    (void)mbn_axis_span(&gx, ox0 + oxn - 1, &unused, &xs1);
+    (void)mbn_axis_span(&gy, oy0, &y0, &unused);
+    (void)mbn_axis_span(&gy, oy0 + oyn - 1, &unused, &y1);
     // the LDS image of a tile (host/mbn_envelope.h)
     int32_t *s_wx = reinterpret_cast<int32_t *>(s_mem), *s_wy = s_wx + tow * kx, *s_fx = s_wy + toh * ky, *s_fy = s_fx + tow, *s_cy = s_fy + toh;
     uint8_t *s_row = s_mem + MBN_RESIZE_STAGE_OFF(tow, kx, toh, ky) + wave * d.seg_stride;
@@ -149,88 +77,38 @@ __global__ __launch_bounds__(256, 8) void resize_ragged_u8(const RaggedArgs a)
 
     // ---- the tile's taps: wave 0 a column per lane, wave 1 a row per lane (toh <= 32)
     if (tid < oxn) {
-        int f;
-        (void)axis_taps(gx, ox0 + tid, kx, s_wx + tid * kx, f);
-        s_fx[tid] = f;
+        (void)mbn_axis_taps(&gx, ox0 + tid, kx, s_wx + tid * kx, &s_fx[tid]);
     } else if (tid >= 64 && tid - 64 < oyn) {
         const int r = tid - 64;
-        int f;
-        s_cy[r] = axis_taps(gy, oy0 + r, ky, s_wy + r * ky, f);
-        s_fy[r] = f;
+        s_cy[r] = mbn_axis_taps(&gy, oy0 + r, ky, s_wy + r * ky, &s_fy[r]);
     }
     __syncthreads();                                             // the taps are in place
 
     const size_t img = (size_t)(&d - a.desc);
     const uint8_t *__restrict__ src = a.src + d.src_offset;
     uint8_t *__restrict__ dst = a.out + img * ((size_t)a.oh * a.ow * 3);
-    // this lane's horizontal sums: element e = lane + 64 j of a row is column e / 3, channel e % 3
-    int lo[RAGGED_EPL], wofs[RAGGED_EPL];
-#pragma unroll
-    for (int j = 0; j < RAGGED_EPL; j++) {
-        const int e = lane + 64 * j, ox = e / 3;
-        const bool on = e < row_e;
-        lo[j] = on ? min(max(s_fx[ox] - xs0, 0), max(nb / 3 - 1, 0)) * 3 + (e - 3 * ox) : 0;
-        wofs[j] = on ? ox * kx : 0;
-    }
-    // ---- horizontal: wave v takes rows y0 + v, y0 + v + 4, ... of the window, each wave at its own pace (the staged row is its own)
+    int lo[RESIZE_EPL], wofs[RESIZE_EPL];
+    const int last = max(nb / 3 - 1, 0);                         // the last pixel the staged segment holds
+    resize_lane_elems(lo, wofs, lane, row_e, kx, [&](int ox) { return min(max(s_fx[ox] - xs0, 0), last); });
     for (int r = wave; r < nrows; r += MBN_RESIZE_WAVES) {
-        const uint8_t *g = src + ((size_t)(y0 + r) * d.cols + xs0) * 3;
-        const int off = (int)((uintptr_t)g & 3);                 // byte j of the segment goes to s_row[off + j]: a dword of memory is a dword of LDS
-        const int head = min(nb, (4 - off) & 3), body = (nb - head) >> 2, tail0 = head + 4 * body;
-        if (lane < head) s_row[off + lane] = g[lane];
-        for (int i = lane; i < body; i += 64)
-            *reinterpret_cast<uint32_t *>(s_row + off + head + 4 * i) = *reinterpret_cast<const uint32_t *>(g + head + 4 * i);
-        if (tail0 + lane < nb) s_row[off + tail0 + lane] = g[tail0 + lane];
-        wave_sync();
-#pragma unroll
-        for (int j = 0; j < RAGGED_EPL; j++) {
-            const int e = lane + 64 * j;
-            if (e < row_e) {
-                int acc = RAGGED_HALF;
-                const uint8_t *p = s_row + off + lo[j];
-                const int32_t *k = s_wx + wofs[j];
-                for (int t = 0; t < kx; t++) acc += (int)p[3 * t] * k[t];      // past this column's count: a zero weight times a byte of the slack
-                s_tmp[r * tmp_ld + e] = resize_round(acc);
-            }
-        }
-        wave_sync();                                             // the next row is staged over this one
+        const uint8_t *s_seg = resize_stage_row(s_row, src + ((size_t)(y0 + r) * d.cols + xs0) * 3, nb, lane);
+        resize_row_sums(s_tmp + r * tmp_ld, s_seg, s_wx, lo, wofs, kx, row_e, lane);
     }
     __syncthreads();                                             // the window is complete
-
-    // ---- vertical: wave v takes output rows v, v + 4, ... of the tile; the row's first source row, count and weights are the same for all its lanes
-    const int wv = __builtin_amdgcn_readfirstlane(wave);
-    int idx[RAGGED_EPL];
-#pragma unroll
-    for (int j = 0; j < RAGGED_EPL; j++) idx[j] = lane + 64 * j < row_e ? lane + 64 * j : 0;
-    for (int oy = wv; oy < oyn; oy += MBN_RESIZE_WAVES) {
-        const int f = min(max(__builtin_amdgcn_readfirstlane(s_fy[oy]) - y0, 0), max(nrows - 1, 0));
-        const int cnt = min(__builtin_amdgcn_readfirstlane(s_cy[oy]), nrows - f);
-        const int32_t *k = s_wy + oy * ky;
-        const uint8_t *p = s_tmp + f * tmp_ld;
-        int acc[RAGGED_EPL];
-#pragma unroll
-        for (int j = 0; j < RAGGED_EPL; j++) acc[j] = RAGGED_HALF;
-        for (int t = 0; t < cnt; t++) {
-            const int kt = k[t];
-#pragma unroll
-            for (int j = 0; j < RAGGED_EPL; j++) acc[j] += (int)p[t * tmp_ld + idx[j]] * kt;
-        }
-        uint8_t *o = dst + ((size_t)(oy0 + oy) * a.ow + ox0) * 3;
-#pragma unroll
-        for (int j = 0; j < RAGGED_EPL; j++)
-            if (lane + 64 * j < row_e) o[lane + 64 * j] = resize_round(acc[j]);
-    }
+    resize_vertical(dst + ((size_t)oy0 * a.ow + ox0) * 3, (size_t)a.ow * 3, s_tmp, tmp_ld, oyn, row_e, lane, wave, [&](int oy, int &f, int &n) {
+        f = min(max(__builtin_amdgcn_readfirstlane(s_fy[oy]) - y0, 0), max(nrows - 1, 0));
+        n = min(__builtin_amdgcn_readfirstlane(s_cy[oy]), nrows - f);
+        return s_wy + oy * ky;
+    });
 }
 
-// mbn_resize_taps_device: the tables of one axis from axis_taps, an output per lane
+// mbn_resize_taps_device: the tables of one axis from mbn_axis_taps, an output per lane
 __global__ __launch_bounds__(64) void resize_taps_k(int in_size, float b0, float b1, int out_size, int ksize, int32_t *first, int32_t *count, int32_t *weights)
 {
     const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
     if (i >= out_size) return;
-    const Axis a = axis_of(in_size, b0, b1, out_size);
-    int f;
-    count[i] = axis_taps(a, i, ksize, weights + (size_t)i * ksize, f);
-    first[i] = f;
+    const mbn_axis a = mbn_axis_of(in_size, b0, b1, out_size);
+    count[i] = mbn_axis_taps(&a, i, ksize, weights + (size_t)i * ksize, &first[i]);
 }
 
 }   // namespace

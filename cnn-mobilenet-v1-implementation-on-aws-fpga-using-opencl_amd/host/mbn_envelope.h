@@ -63,17 +63,33 @@ int mbn_upsample_argmax_envelope(int batch, int rows, int cols, int classes, int
 #define MBN_RESIZE_MAX_OUT 4096
 #define MBN_RESIZE_MAX_KSIZE 67
 #define MBN_RESIZE_MAX_BATCH 65535
+#define MBN_RESIZE_BITS 22           /* fractional bits of a weight: 32 - 8 - 2 */
+#define MBN_RESIZE_HALF (1 << 21)    /* what a sum of weights x bytes starts from: it rounds to nearest */
 int mbn_resize_envelope(int in_rows, int in_cols, const float *box, int out_rows, int out_cols);
-/* ragged resize (mbn_u8_resize_ragged.hip): every image of a launch has its own rows, cols and box. What the host plans, without a tap table:
- * a workgroup of MBN_RESIZE_WAVES waves owns a tile of toh x tow outputs of one image; tow follows the output (the rule of mbn_resizer_create), toh is
- * the tallest tile (MBN_RESIZE_TOH at most) whose LDS image fits MBN_RESIZE_LDS bytes. The LDS image of a tile, in this order:
- *   int32  wx [tow][kx], wy [toh][ky], fx [tow], fy [toh], cy [toh]      the tile's taps, formed by the kernel
- *   MBN_RESIZE_STAGE_OFF: MBN_RESIZE_WAVES staged source rows of seg_stride bytes each, then at tmp_off the window [source rows][tow * 3] uint8 */
+/* The tile of both resize kernels (csrc/mbn_u8_resize.h is its body): a workgroup of MBN_RESIZE_WAVES waves owns toh x tow outputs of one image. tow
+ * follows the output (MBN_RESIZE_TOW), toh is the tallest tile (MBN_RESIZE_TOH at most) whose LDS image fits MBN_RESIZE_LDS bytes: the tile's int32
+ * tables, then at stage_off MBN_RESIZE_WAVES staged source rows of seg_stride bytes each, then at tmp_off the window [source rows][tow * 3] uint8.
+ * The tables are, in this order,
+ *   table kernel (mbn_u8_resize.hip)           wx [tow][kx], copied from the handle's tables; the other tables stay in memory
+ *   ragged kernel (mbn_u8_resize_ragged.hip)   wx [tow][kx], wy [toh][ky], fx [tow], fy [toh], cy [toh], formed by the kernel: MBN_RESIZE_STAGE_OFF bytes
+ * host/mbn_resize.c plans both from the exact lo / hi of every tile's two edge outputs (host/mbn_resize_axis.h), without a tap table. */
 #define MBN_RESIZE_WAVES 4
 #define MBN_RESIZE_TOH 32
 #define MBN_RESIZE_LDS (60 * 1024)
 #define MBN_RESIZE_TOW(out_cols) ((out_cols) <= 32 ? 32 : 64)
 #define MBN_RESIZE_STAGE_OFF(tow, kx, toh, ky) ((4 * ((tow) * (kx) + (toh) * (ky) + (tow) + 2 * (toh)) + 15) & ~15)
+typedef struct mbn_resize_plan_t {
+    int32_t kx, ky;                  /* mbn_resize_ksize of the two axes */
+    int32_t tow, toh;                /* columns and rows of a tile */
+    int32_t tiles_x, tiles_y;        /* ceil(out_cols / tow), ceil(out_rows / toh) */
+    int32_t seg_stride;              /* bytes of a staged row: the widest tile's segment + kx pixels of slack + 3, a multiple of 4 */
+    int32_t stage_off, tmp_off;      /* LDS byte offsets of the staged rows and of the window */
+    int32_t lds_bytes;               /* tmp_off + the tallest window * tow * 3 */
+} mbn_resize_plan_t;
+/* the table kernel's tile for one geometry (mbn_resizer_create): whatever mbn_resize_envelope answers, and MBN_EUNSUPPORTED when a tile of one
+ * output row does not fit (no geometry inside the envelope does that) */
+int mbn_resize_table_plan(int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resize_plan_t *plan);
+/* ragged resize (mbn_u8_resize_ragged.hip): every image of a launch has its own rows, cols and box, and its own plan in its descriptor. */
 /* the descriptor of one image in device memory, 64 bytes: the caller's mbn_resize_item, then the plan */
 typedef struct mbn_resize_desc {
     int64_t src_offset;              /* bytes from the launch's src pointer to the image's first byte */

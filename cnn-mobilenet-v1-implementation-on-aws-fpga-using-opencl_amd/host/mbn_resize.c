@@ -1,8 +1,10 @@
 /*
  * mbn_resize.c — host side of the resize front-end (include/mbn.h, "resize front-end"): the tap tables of Pillow's 8-bit bilinear
  * resize for one axis, and the box a fit mode selects. Plain C, no device: also in libmbn_host.so (tests/test_resize_cpu.py compares
- * the tables with tests/resize_ref.py as int32, exactly). Behind them the planner of the ragged resize (mbn_envelope.h: mbn_resize_window,
- * mbn_resize_ragged_plan, _plan_batch): per image O(tiles) evaluations of lo / hi and no table (tests/test_resize_ragged_cpu.py).
+ * the tables with tests/resize_ref.py as int32, exactly). Behind them the tile plans of both resize kernels (mbn_envelope.h: mbn_resize_window,
+ * mbn_resize_table_plan, mbn_resize_ragged_plan, _plan_batch): O(tiles) evaluations of lo / hi and no table (tests/test_resize_cpu.py,
+ * tests/test_resize_ragged_cpu.py). The arithmetic of an axis is mbn_resize_axis.h's, shared with the device; what a box and a size must satisfy,
+ * and the status codes, are here.
  *
  * The reference has no counterpart: decode_image (MobileNet.c:49-57) reads 224*224*3 raw bytes and nothing resizes them.
  */
@@ -12,41 +14,26 @@
 
 #include "mbn.h"
 #include "mbn_envelope.h"
+#include "mbn_resize_axis.h"
 
-#define RESIZE_BITS 22        /* fractional bits of a weight: 32 - 8 - 2 */
 #define RESIZE_MAX_TAPS 4096  /* mbn_resize_taps: the longest row of weights it builds (a 2047x downscale; the device takes 67) */
 
-/* scale of an axis, or a status: the box edges are float32 and their difference is formed in float32 */
-static int axis_scale(int in_size, float b0, float b1, int out_size, double *scale)
+/* an axis, or a status: the box edges are float32 */
+static int axis_make(int in_size, float b0, float b1, int out_size, mbn_axis *a)
 {
     if (in_size <= 0 || out_size <= 0) return MBN_EINVAL;
     if (!(b0 >= 0.0f) || !(b1 <= (float)in_size) || !(b1 > b0)) return MBN_EINVAL;      /* a NaN fails every comparison */
-    const volatile float extent = b1 - b0;         /* volatile: rounded to float32 whatever the compiler's excess precision */
-    *scale = (double)extent / out_size;
+    *a = mbn_axis_of(in_size, b0, b1, out_size);
     return MBN_OK;
 }
 
 int mbn_resize_ksize(int in_size, float b0, float b1, int out_size)
 {
-    double scale;
-    const int rc = axis_scale(in_size, b0, b1, out_size, &scale);
+    mbn_axis a;
+    const int rc = axis_make(in_size, b0, b1, out_size, &a);
     if (rc != MBN_OK) return rc;
-    const double fs = scale < 1.0 ? 1.0 : scale;
-    if (fs > 1.0e6) return MBN_EUNSUPPORTED;
-    return (int)ceil(fs) * 2 + 1;
-}
-
-/* [lo, hi): the source positions output i of an axis reaches, and its centre. The ONE host statement of these expressions: the tables below and the
- * ragged planner's tile windows both come from here, and csrc/mbn_u8_resize_ragged.hip restates them for the device (axis_span) */
-static double axis_span(int in_size, float b0, double scale, double support, int i, int *lo_out, int *hi_out)
-{
-    const double center = (double)b0 + (i + 0.5) * scale;
-    int lo = (int)(center - support + 0.5), hi = (int)(center + support + 0.5);
-    if (lo < 0) lo = 0;
-    if (hi > in_size) hi = in_size;
-    *lo_out = lo;
-    *hi_out = hi;
-    return center;
+    if (a.fs > 1.0e6) return MBN_EUNSUPPORTED;
+    return (int)ceil(a.fs) * 2 + 1;
 }
 
 int mbn_resize_taps(int in_size, float b0, float b1, int out_size, int32_t *first, int32_t *count, int32_t *weights)
@@ -54,31 +41,9 @@ int mbn_resize_taps(int in_size, float b0, float b1, int out_size, int32_t *firs
     if (!first || !count || !weights) return MBN_EINVAL;
     const int ksize = mbn_resize_ksize(in_size, b0, b1, out_size);
     if (ksize < 0) return ksize;
-    double scale = 1.0;
-    (void)axis_scale(in_size, b0, b1, out_size, &scale);
-    const double fs = scale < 1.0 ? 1.0 : scale, support = fs;
     if (ksize > RESIZE_MAX_TAPS) return MBN_EUNSUPPORTED;
-    double w[RESIZE_MAX_TAPS];
-    for (int i = 0; i < out_size; i++) {
-        int lo, hi;
-        const double center = axis_span(in_size, b0, scale, support, i, &lo, &hi);
-        const int n = hi - lo;
-        double sum = 0.0;
-        for (int t = 0; t < n; t++) {
-            double x = (t + lo - center + 0.5) / fs;
-            if (x < 0.0) x = -x;
-            w[t] = x < 1.0 ? 1.0 - x : 0.0;
-            sum += w[t];
-        }
-        int32_t *k = weights + (size_t)i * ksize;
-        for (int t = 0; t < n; t++) {
-            if (sum != 0.0) w[t] /= sum;
-            k[t] = (int32_t)(w[t] * (double)(1 << RESIZE_BITS) + 0.5);
-        }
-        for (int t = n > 0 ? n : 0; t < ksize; t++) k[t] = 0;
-        first[i] = lo;
-        count[i] = n > 0 ? n : 0;
-    }
+    const mbn_axis a = mbn_axis_of(in_size, b0, b1, out_size);
+    for (int i = 0; i < out_size; i++) count[i] = mbn_axis_taps(&a, i, ksize, weights + (size_t)i * ksize, &first[i]);
     return ksize;
 }
 
@@ -114,68 +79,89 @@ int mbn_resize_envelope(int in_rows, int in_cols, const float *box, int out_rows
     return MBN_OK;
 }
 
-/* ---- the ragged resize (csrc/mbn_u8_resize_ragged.hip): what the host plans per image. No table is built: a tile's window is the exact lo of its first
- * output and the exact hi of its last one, which the kernel derives again from the same expressions */
+/* ---- the tile plans of the two kernels (csrc/mbn_u8_resize.hip, csrc/mbn_u8_resize_ragged.hip). No table is built: a tile's window is the exact lo of
+ * its first output and the exact hi of its last one, which the ragged kernel derives again from the same expressions and the table kernel reads from
+ * its tables (tests/test_resize_ragged_cpu.py pins the two equal) */
 
 int mbn_resize_window(int in_size, float b0, float b1, int out_size, int o_first, int o_last, int32_t *lo, int32_t *hi)
 {
-    double scale;
-    const int rc = axis_scale(in_size, b0, b1, out_size, &scale);
+    mbn_axis a;
+    const int rc = axis_make(in_size, b0, b1, out_size, &a);
     if (rc != MBN_OK) return rc;
     if (!lo || !hi || o_first < 0 || o_last < o_first || o_last >= out_size) return MBN_EINVAL;
-    const double support = scale < 1.0 ? 1.0 : scale;
     int l, h, unused;
-    (void)axis_span(in_size, b0, scale, support, o_first, &l, &unused);
-    (void)axis_span(in_size, b0, scale, support, o_last, &unused, &h);
+    (void)mbn_axis_span(&a, o_first, &l, &unused);
+    (void)mbn_axis_span(&a, o_last, &unused, &h);
     *lo = l;
     *hi = h;
     return MBN_OK;
 }
 
 /* most source positions a tile of `t` outputs reaches along an axis: exact at every tile's two edge outputs */
-static int axis_most(int in_size, float b0, double scale, int out_size, int t)
+static int axis_most(const mbn_axis *a, int out_size, int t)
 {
-    const double support = scale < 1.0 ? 1.0 : scale;
     int most = 0;
     for (int o = 0; o < out_size; o += t) {
         const int last = (o + t < out_size ? o + t : out_size) - 1;
         int lo, hi, unused;
-        (void)axis_span(in_size, b0, scale, support, o, &lo, &unused);
-        (void)axis_span(in_size, b0, scale, support, last, &unused, &hi);
+        (void)mbn_axis_span(a, o, &lo, &unused);
+        (void)mbn_axis_span(a, last, &unused, &hi);
         if (hi - lo > most) most = hi - lo;
     }
     return most;
 }
 
+/* The tile of a geometry inside mbn_resize_envelope. In front of the staged rows stand the tile's horizontal weights alone (the table kernel), or
+ * with all_taps every table of the tile (the ragged kernel: MBN_RESIZE_STAGE_OFF, which grows with the tile's height) */
+static int tile_fit(int in_rows, int in_cols, const float *box, int out_rows, int out_cols, int all_taps, mbn_resize_plan_t *p)
+{
+    const mbn_axis ax = mbn_axis_of(in_cols, box[0], box[2], out_cols), ay = mbn_axis_of(in_rows, box[1], box[3], out_rows);
+    p->kx = mbn_resize_ksize(in_cols, box[0], box[2], out_cols);
+    p->ky = mbn_resize_ksize(in_rows, box[1], box[3], out_rows);
+    p->tow = MBN_RESIZE_TOW(out_cols);
+    p->tiles_x = (out_cols + p->tow - 1) / p->tow;
+    /* a staged row: the widest tile's segment + kx pixels of slack (the horizontal loop runs kx taps for every column) + 3 (the address's offset in its dword) */
+    p->seg_stride = ((axis_most(&ax, out_cols, p->tow) + p->kx) * 3 + 3 + 3) & ~3;
+    /* the tallest tile whose tables + 4 staged rows + window fit; one output row reaches at most ky <= 67 source rows (13 KB of window), which always fits */
+    for (p->toh = out_rows < MBN_RESIZE_TOH ? out_rows : MBN_RESIZE_TOH;; p->toh--) {
+        p->stage_off = all_taps ? MBN_RESIZE_STAGE_OFF(p->tow, p->kx, p->toh, p->ky) : (p->tow * p->kx * 4 + 15) & ~15;
+        p->tmp_off = (p->stage_off + MBN_RESIZE_WAVES * p->seg_stride + 15) & ~15;
+        p->lds_bytes = p->tmp_off + axis_most(&ay, out_rows, p->toh) * p->tow * 3;
+        if (p->lds_bytes <= MBN_RESIZE_LDS || p->toh == 1) break;
+    }
+    p->tiles_y = (out_rows + p->toh - 1) / p->toh;
+    return p->lds_bytes <= MBN_RESIZE_LDS ? MBN_OK : MBN_EUNSUPPORTED;
+}
+
+int mbn_resize_table_plan(int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resize_plan_t *plan)
+{
+    if (!plan) return MBN_EINVAL;
+    const int rc = mbn_resize_envelope(in_rows, in_cols, box, out_rows, out_cols);
+    if (rc != MBN_OK) return rc;
+    const float whole[4] = { 0.0f, 0.0f, (float)in_cols, (float)in_rows };
+    return tile_fit(in_rows, in_cols, box ? box : whole, out_rows, out_cols, 0, plan);
+}
+
 int mbn_resize_ragged_plan(const mbn_resize_item *it, int out_rows, int out_cols, mbn_resize_desc *d)
 {
     if (!it || !d || it->src_offset < 0) return MBN_EINVAL;
-    const int rc = mbn_resize_envelope(it->rows, it->cols, it->box, out_rows, out_cols);
+    int rc = mbn_resize_envelope(it->rows, it->cols, it->box, out_rows, out_cols);
     if (rc != MBN_OK) return rc;
-    double sx = 1.0, sy = 1.0;
-    (void)axis_scale(it->cols, it->box[0], it->box[2], out_cols, &sx);
-    (void)axis_scale(it->rows, it->box[1], it->box[3], out_rows, &sy);
+    mbn_resize_plan_t p;
+    rc = tile_fit(it->rows, it->cols, it->box, out_rows, out_cols, 1, &p);
     memset(d, 0, sizeof *d);
     d->src_offset = it->src_offset;
     d->rows = it->rows;
     d->cols = it->cols;
     memcpy(d->box, it->box, sizeof d->box);
-    d->kx = mbn_resize_ksize(it->cols, it->box[0], it->box[2], out_cols);
-    d->ky = mbn_resize_ksize(it->rows, it->box[1], it->box[3], out_rows);
-    const int tow = MBN_RESIZE_TOW(out_cols);
-    /* a staged row: the widest tile's segment + kx pixels of slack (the horizontal loop runs kx taps for every column) + 3 (the address's offset in its dword) */
-    d->seg_stride = ((axis_most(it->cols, it->box[0], sx, out_cols, tow) + d->kx) * 3 + 3 + 3) & ~3;
-    /* the tallest tile whose tables + 4 staged rows + window fit; one output row reaches at most ky <= 67 source rows (13 KB of window), which always fits */
-    int toh = out_rows < MBN_RESIZE_TOH ? out_rows : MBN_RESIZE_TOH;
-    for (;; toh--) {
-        d->toh = toh;
-        d->tmp_off = (MBN_RESIZE_STAGE_OFF(tow, d->kx, toh, d->ky) + MBN_RESIZE_WAVES * d->seg_stride + 15) & ~15;
-        d->lds_bytes = d->tmp_off + axis_most(it->rows, it->box[1], sy, out_rows, toh) * tow * 3;
-        if (d->lds_bytes <= MBN_RESIZE_LDS || toh == 1) break;
-    }
-    if (d->lds_bytes > MBN_RESIZE_LDS) return MBN_EUNSUPPORTED;
-    d->tiles_y = (out_rows + toh - 1) / toh;
-    return MBN_OK;
+    d->kx = p.kx;
+    d->ky = p.ky;
+    d->toh = p.toh;
+    d->tiles_y = p.tiles_y;
+    d->seg_stride = p.seg_stride;
+    d->tmp_off = p.tmp_off;
+    d->lds_bytes = p.lds_bytes;
+    return rc;
 }
 
 int mbn_resize_ragged_plan_batch(const mbn_resize_item *items, int batch, int out_rows, int out_cols, mbn_resize_desc *desc, int32_t *total_wgs,

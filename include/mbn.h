@@ -442,13 +442,15 @@ int mbn_normalize_u8_to_f32(mbn_context *ctx, void *out_f32, const void *in_u8, 
  * nor cropped has the weights (2^22, 0): the identity.
  *   mbn_resize_ksize   ksize of an axis, or a negative status
  *   mbn_resize_taps    the tables of an axis: first[i] = lo, count[i] = n, weights [out_size][ksize] zero padded; returns ksize (>= 3) or a
- *                      negative status. Host code; also in libmbn_host.so
+ *                      negative status. Host code (host/mbn_resize.c; the expressions above are host/mbn_resize_axis.h, compiled for the host
+ *                      and for the device); also in libmbn_host.so
  *   mbn_fit_box        the box of a fit mode. MBN_FIT_STRETCH: (0, 0, W, H). MBN_FIT_CROP: the centred box with the output's aspect ratio,
  *                      shrunk by crop_fraction f in (0, 1] (f = 0.875 is the usual "resize to 256, crop 224"); in double
  *                      bw = min(W, H * ow / oh) * f, bh = bw * oh / ow, left = (W - bw) / 2, upper = (H - bh) / 2, each edge then rounded to
  *                      float32 and clamped into the image. 480 x 640 -> 224 x 224, f = 1: (80, 0, 560, 480)
  * A box edge below 0 or beyond the image, b1 <= b0, a NaN or a non-positive size: MBN_EINVAL.
- * Device (mbn_u8_resize.hip): ONE launch runs both passes; the uint8 intermediate lives in LDS and never reaches memory.
+ * Device (mbn_u8_resize.hip; the tile body, mbn_u8_resize.h, is the ragged kernel's too): ONE launch runs both passes; the uint8 intermediate
+ * lives in LDS and never reaches memory.
  *   mbn_resizer_create  builds both tap tables on the host and uploads them (blocking: here, not in the hot call). box NULL = the whole
  *                       image. Envelope: source sides 1..8192, output sides 1..4096, ksize <= 67 per axis (a downscale up to 32x, any
  *                       upscale); outside: MBN_EUNSUPPORTED, nothing launched
@@ -470,7 +472,7 @@ int  mbn_resize_u8(mbn_resizer *r, void *out_u8, const void *in_u8, int batch, v
 int  mbn_resizer_destroy(mbn_resizer *r);
 /* Ragged resize (mbn_u8_resize_ragged.hip): ONE launch takes `batch` images, each with its own rows, cols and box, to one common
  * [batch][out_rows][out_cols][3]. The arithmetic is the one above, byte for byte; what differs is where the taps are formed: no table is built on the
- * host and none crosses to the device. The kernel evaluates the expressions above itself, in fp64 with the float32 subtraction, truncating casts, the
+ * host and none crosses to the device. The kernel evaluates the expressions above itself (the host's own code, host/mbn_resize_axis.h), in fp64 with the float32 subtraction, truncating casts, the
  * sum in order, a true division and no contraction into fused multiply-adds, per tile, straight into LDS. An image is an
  * mbn_resize_item: src_offset = bytes from the launch's src pointer to its first byte (any value >= 0, any order, two items may share one), rows, cols,
  * and its box (all four edges; the whole image is (0, 0, cols, rows)). Envelope per image: that of mbn_resizer_create.

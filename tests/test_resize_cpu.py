@@ -146,10 +146,63 @@ def test_envelope_edges(pkg):
     assert lib.mbn_resize_envelope(1, 1, None, 4096, 4096) == pkg.OK                  # any upscale
 
 
+def _table_plan_rule(H, W, oh, ow, box):
+    """The tile rule of mbn_resizer_create as it stood when the plan lived beside the kernel, from resize_ref's tables: a tile's window is
+    first[last] + count[last] - first[o], and a rule's window the largest over the tiles."""
+    b = box if box is not None else (0.0, 0.0, float(W), float(H))
+    (fx, cx, wx), (fy, cy, wy) = resize_ref.taps(W, b[0], b[2], ow), resize_ref.taps(H, b[1], b[3], oh)
+    window = lambda f, c, t: max(int(f[min(o + t, len(f)) - 1] + c[min(o + t, len(f)) - 1] - f[o]) for o in range(0, len(f), t))
+    kx, ky = wx.shape[1], wy.shape[1]
+    tow = 32 if ow <= 32 else 64
+    stage_off = (tow * kx * 4 + 15) & ~15
+    seg_stride = ((window(fx, cx, tow) + kx) * 3 + 6) & ~3
+    tmp_off = (stage_off + 4 * seg_stride + 15) & ~15
+    toh = min(oh, 32)
+    while toh > 1 and tmp_off + window(fy, cy, toh) * tow * 3 > 61440:
+        toh -= 1
+    return dict(kx=kx, ky=ky, tow=tow, toh=toh, tiles_x=-(-ow // tow), tiles_y=-(-oh // toh), seg_stride=seg_stride, stage_off=stage_off,
+                tmp_off=tmp_off, lds_bytes=tmp_off + window(fy, cy, toh) * tow * 3)
+
+
+def test_table_plan_did_not_move(pkg):
+    """mbn_resize_table_plan (plain C, two exact lo / hi per tile) gives, field for field, the tile mbn_resizer_build used to size from whole tap
+    tables: on every geometry of test_resize_gpu.CASES, the 33x downscale of both axes, every image of test_resize_ragged_cpu.BATCHES (the golden
+    fixtures are among them) and four anchors written out. No geometry inside mbn_resize_envelope has an output row that does not fit: the
+    largest one-row tile is the 33x downscale of both axes below, 55984 of 61440 bytes (64 x 67 weights, four staged rows of 64 x 33 + 2 x 67
+    pixels, a window of 67 rows), and a fractional box moves a window by a pixel or two. So MBN_EUNSUPPORTED is pinned here only as the
+    envelope's answer."""
+    import test_resize_gpu
+    import test_resize_ragged_cpu
+    crop = lambda H, W, f: tuple(float(v) for v in pkg.fit_box(H, W, 224, 224, pkg.FIT_CROP, f))
+    geoms = [(H, W, oh, ow, crop(H, W, 0.875) if box == "crop" else box) for H, W, oh, ow, box, _ in test_resize_gpu.CASES]
+    geoms += [(1056, 2112, 32, 64, None), (1080, 1920, 224, 224, crop(1080, 1920, 1.0))]
+    geoms += [(rows, cols, oh, ow, box) for oh, ow, images in test_resize_ragged_cpu.BATCHES for rows, cols, box in images]
+    fields = [n for n, _ in pkg.ResizePlan._fields_]
+    plans = {}
+    for H, W, oh, ow, box in geoms:
+        p = pkg.resize_table_plan(H, W, oh, ow, box)
+        plans[(H, W, oh, ow)] = got = {n: getattr(p, n) for n in fields}
+        assert got == _table_plan_rule(H, W, oh, ow, box), (H, W, oh, ow, box)
+        assert got["lds_bytes"] <= 61440
+    assert crop(375, 500, 0.875) == (85.9375, 23.4375, 414.0625, 351.5625) and crop(1080, 1920, 1.0) == (420.0, 0.0, 1500.0, 1080.0)
+    anchors = {(375, 500, 224, 224): dict(kx=5, ky=5, toh=32, seg_stride=304, tmp_off=2496, lds_bytes=11904, tiles_x=4, tiles_y=7),
+               (1000, 17, 32, 32): dict(kx=3, ky=65, toh=19, seg_stride=64, tmp_off=640, lds_bytes=59104),
+               (1056, 2112, 32, 64): dict(kx=67, ky=67, toh=1, seg_stride=6540, tmp_off=43312, lds_bytes=55984),
+               (1080, 1920, 224, 224): dict(kx=11, ky=11, toh=32, seg_stride=980, tmp_off=6736, lds_bytes=37456)}
+    for g, want in anchors.items():
+        assert {n: plans[g][n] for n in want} == want, g
+    window_rows = lambda g: (plans[g]["lds_bytes"] - plans[g]["tmp_off"]) // (plans[g]["tow"] * 3)
+    assert window_rows((375, 500, 224, 224)) == 49 and window_rows((1000, 17, 32, 32)) == 609
+    lib, p = pkg.host_lib(), pkg.ResizePlan()
+    assert lib.mbn_resize_table_plan(1057, 40, None, 32, 32, C.byref(p)) == pkg.EUNSUPPORTED           # 69 taps: the envelope's answer
+    assert lib.mbn_resize_table_plan(37, 53, (C.c_float * 4)(0.0, 0.0, 54.0, 37.0), 32, 32, C.byref(p)) == pkg.EINVAL
+    assert lib.mbn_resize_table_plan(37, 53, None, 32, 32, None) == pkg.EINVAL
+
+
 def test_symbols_declared(pkg):
     names = pkg.declared_symbols()
     for s in ("mbn_resize_ksize", "mbn_resize_taps", "mbn_fit_box", "mbn_resizer_create", "mbn_resize_u8", "mbn_resizer_destroy", "mbn_net_resize_input"):
         assert s in names, s
     host = pkg.host_lib()
-    for s in ("mbn_resize_ksize", "mbn_resize_taps", "mbn_fit_box", "mbn_resize_envelope"):
+    for s in ("mbn_resize_ksize", "mbn_resize_taps", "mbn_fit_box", "mbn_resize_envelope", "mbn_resize_table_plan"):
         assert hasattr(host, s), s
