@@ -87,6 +87,16 @@ class ResizeItem(C.Structure):
     _fields_ = [("src_offset", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32), ("box", C.c_float * 4)]
 
 
+class LabelItem(C.Structure):
+    """mbn_label_item (include/mbn.h): one image of a ragged read-out; dst_offset in elements from labels (and score)"""
+    _fields_ = [("dst_offset", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32)]
+
+
+class ResampleLaunch(C.Structure):
+    """mbn_resample_launch_t (host/mbn_envelope.h): LDS footprint, class chunk, dynamic LDS, grid.x and output span of a read-out launch"""
+    _fields_ = [(n, C.c_int32) for n in ("fy", "fx", "ch", "lds_bytes", "tiles")] + [("span", C.c_int64)]
+
+
 class ResizeDesc(C.Structure):
     """mbn_resize_desc (host/mbn_envelope.h): an image's descriptor in device memory, the item and what the host planned for it"""
     _fields_ = [("src_offset", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32), ("box", C.c_float * 4)] + \
@@ -157,6 +167,10 @@ def _declare_host(lib):
     lib.mbn_rank_fail.argtypes = [C.c_void_p]
     lib.mbn_quantize_i8.argtypes = [C.POINTER(Plan), C.c_void_p, C.c_void_p, C.POINTER(I8Params), C.c_void_p]
     lib.mbn_upsample_argmax_envelope.argtypes = [C.c_int] * 5      # mbn_envelope.h: exported, not in mbn.h
+    lib.mbn_resample_argmax_envelope.argtypes = [C.c_int] * 6      # mbn_envelope.h, like the two below
+    lib.mbn_resample_plan.argtypes = [C.c_int] * 4 + [C.POINTER(ResampleLaunch)]
+    lib.mbn_resample_plan.restype = None
+    lib.mbn_resample_ragged_check.argtypes = [C.c_int] * 3 + [C.POINTER(LabelItem), C.c_int, C.POINTER(C.c_int64), C.POINTER(ResampleLaunch)]
     i32p = C.POINTER(C.c_int32)
     lib.mbn_resize_ksize.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int]
     lib.mbn_resize_taps.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int, i32p, i32p, i32p]
@@ -272,6 +286,13 @@ def load():
         lib.mbn_upsample_argmax_f32.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
         lib.mbn_net_forward_dense.argtypes = [vp, vp, vp, ci]
         lib.mbn_net_segment.argtypes = [vp, vp, ci, vp, vp]
+        lib.mbn_resample_argmax_f32.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
+        lib.mbn_ragged_readout_create.argtypes = [vp, ci, C.POINTER(vp)]
+        lib.mbn_ragged_readout_set.argtypes = [vp, ci, ci, ci, C.POINTER(LabelItem), ci, vp]
+        lib.mbn_resample_argmax_ragged_f32.argtypes = [vp, vp, vp, vp, vp]
+        lib.mbn_ragged_readout_destroy.argtypes = [vp]
+        lib.mbn_net_segment_to.argtypes = [vp, vp, ci, ci, ci, vp, vp]
+        lib.mbn_net_segment_images.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, vp, C.POINTER(C.c_int64), vp]
         lib.mbn_resizer_create.argtypes = [vp, ci, ci, C.POINTER(C.c_float), ci, ci, C.POINTER(vp)]
         lib.mbn_resize_u8.argtypes = [vp, vp, vp, ci, vp]
         lib.mbn_resizer_destroy.argtypes = [vp]
@@ -389,6 +410,34 @@ def resize_ragged_plan(items, out_rows, out_cols, lib=None):
     _chk((lib or host_lib()).mbn_resize_ragged_plan_batch(arr, len(arr), out_rows, out_cols, desc, C.byref(wgs), C.byref(lds), C.byref(span)),
          "resize_ragged_plan")
     return desc, wgs.value, lds.value, span.value
+
+
+def label_items(items):
+    """A C array of mbn_label_item from (dst_offset, rows, cols) tuples."""
+    arr = (LabelItem * len(items))()
+    for it, (off, rows, cols) in zip(arr, items):
+        it.dst_offset, it.rows, it.cols = int(off), int(rows), int(cols)
+    return arr
+
+
+def resample_argmax_envelope(batch, rows, cols, classes, out_rows, out_cols, lib=None) -> int:
+    """mbn_resample_argmax_envelope: the status (OK, EINVAL or EUNSUPPORTED) mbn_resample_argmax_f32 gives the shape."""
+    return (lib or host_lib()).mbn_resample_argmax_envelope(batch, rows, cols, classes, out_rows, out_cols)
+
+
+def resample_plan(rows, cols, out_rows, out_cols, lib=None) -> ResampleLaunch:
+    """mbn_resample_plan: the launch of one output size of a rows x cols map (LDS footprint, class chunk, dynamic LDS, tiles)."""
+    l = ResampleLaunch()
+    (lib or host_lib()).mbn_resample_plan(rows, cols, out_rows, out_cols, C.byref(l))
+    return l
+
+
+def resample_ragged_check(rows, cols, classes, items, lib=None):
+    """mbn_resample_ragged_check: (status, launch) of a ragged set of (dst_offset, rows, cols) tuples over a rows x cols x classes map."""
+    arr = items if isinstance(items, C.Array) else label_items(items)
+    l = ResampleLaunch()
+    rc = (lib or host_lib()).mbn_resample_ragged_check(rows, cols, classes, arr, len(arr), (C.c_int64 * (2 * max(len(arr), 1)))(), C.byref(l))
+    return rc, l
 
 
 def declared_symbols():
@@ -587,11 +636,45 @@ class Context:
         logit) [batch][rows*factor][cols*factor]: bilinear upsample + argmax in one kernel."""
         _chk(self.lib.mbn_upsample_argmax_f32(self.h, labels, score, logits, batch, rows, cols, classes, factor, None), self.last_error())
 
+    def resample_argmax(self, labels, score, logits, batch, rows, cols, classes, out_rows, out_cols):
+        """mbn_resample_argmax_f32: fp32 logits [batch][rows][cols][classes] -> int32 labels (and, unless `score` is None, the winning fp32
+        logit) [batch][out_rows][out_cols]: bilinear resample to any size (at least 4 x the map) + argmax in one kernel."""
+        _chk(self.lib.mbn_resample_argmax_f32(self.h, labels, score, logits, batch, rows, cols, classes, out_rows, out_cols, None), self.last_error())
+
     def __enter__(self):
         return self
 
     def __exit__(self, *a):
         self.close()
+
+
+class RaggedReadout:
+    """mbn_ragged_readout_create / _set / mbn_resample_argmax_ragged_f32: the read-out of up to max_batch images of one coarse shape, each to its
+    own rows x cols at its own place, in ONE launch. set() takes (dst_offset, rows, cols) tuples (element offsets from the labels / score pointers
+    of run()); a refused set raises and leaves the previous one in place."""
+
+    def __init__(self, ctx: Context, max_batch):
+        self.ctx = ctx
+        self.batch = 0
+        h = C.c_void_p()
+        _chk(ctx.lib.mbn_ragged_readout_create(ctx.h, max_batch, C.byref(h)), ctx.last_error())
+        self.h = h
+        if not hasattr(ctx, "_resizers"):
+            ctx._resizers = []
+        ctx._resizers.append(self)
+
+    def set(self, rows, cols, classes, items, stream=None):
+        arr = items if isinstance(items, C.Array) else label_items(items)
+        _chk(self.ctx.lib.mbn_ragged_readout_set(self.h, rows, cols, classes, arr, len(arr), stream), self.ctx.last_error())
+        self.batch = len(arr)
+
+    def run(self, labels_ptr, score_ptr, logits_ptr, stream=None):
+        _chk(self.ctx.lib.mbn_resample_argmax_ragged_f32(self.h, labels_ptr, score_ptr, logits_ptr, stream), self.ctx.last_error())
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.mbn_ragged_readout_destroy(self.h)
+            self.h = None
 
 
 class Resizer:
@@ -768,6 +851,20 @@ class Net:
     def segment(self, images_ptr, batch, labels_ptr, score_ptr=None):
         """forward_dense + bilinear upsample to the input size + argmax: int32 labels (and fp32 scores) [batch][rows][cols] (mbn_net_segment)."""
         _chk(self.ctx.lib.mbn_net_segment(self.h, images_ptr, batch, labels_ptr, score_ptr), self.ctx.last_error())
+
+    def segment_to(self, images_ptr, batch, out_rows, out_cols, labels_ptr, score_ptr=None):
+        """forward_dense + bilinear resample to out_rows x out_cols + argmax: int32 labels (and fp32 scores) [batch][out_rows][out_cols]
+        (mbn_net_segment_to): the label map at the source resolution of images that went through resize_input(..., FIT_STRETCH)."""
+        _chk(self.ctx.lib.mbn_net_segment_to(self.h, images_ptr, batch, out_rows, out_cols, labels_ptr, score_ptr), self.ctx.last_error())
+
+    def segment_images(self, src_ptr, offsets, rows, cols, labels_ptr, dst_offsets, score_ptr=None):
+        """mbn_net_segment_images: image i is uint8 [rows[i]][cols[i]][3] at src_ptr + offsets[i]; stretch resize, forward_dense and one ragged
+        read-out: its labels (and scores) [rows[i]][cols[i]] at element dst_offsets[i] of labels_ptr (score_ptr). Needs set_input_u8()."""
+        n = len(offsets)
+        assert len(rows) == n and len(cols) == n and len(dst_offsets) == n
+        _chk(self.ctx.lib.mbn_net_segment_images(self.h, src_ptr, (C.c_int64 * n)(*[int(v) for v in offsets]), (C.c_int32 * n)(*[int(v) for v in rows]),
+                                                 (C.c_int32 * n)(*[int(v) for v in cols]), n, labels_ptr, (C.c_int64 * n)(*[int(v) for v in dst_offsets]),
+                                                 score_ptr), self.ctx.last_error())
 
     def resize_input(self, src_ptr, batch, in_rows, in_cols, fit=FIT_CROP, crop_fraction=1.0) -> int:
         """mbn_net_resize_input: uint8 images [batch][in_rows][in_cols][3] of any size -> the net's staging buffer [batch][rows][cols][3] (its

@@ -186,6 +186,7 @@ int mbn_shutdown(mbn_context *ctx)
     for (auto &kv : ctx->emul_ws) (void)hipFree(kv.second.p);
     for (mbn_resizer *r : ctx->resizers) mbn_resizer_release(r);
     for (mbn_ragged_resizer *r : ctx->ragged_resizers) mbn_ragged_resizer_release(r);
+    for (mbn_ragged_readout *r : ctx->ragged_readouts) mbn_ragged_readout_release(r);
     ctx->allocs.clear();
     for (hipEvent_t e : ctx->pool) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->marks) (void)hipEventDestroy(e);
@@ -828,6 +829,71 @@ int mbn_upsample_argmax_f32(mbn_context *ctx, void *labels_i32, void *score_f32,
     Scope sc(ctx, s);
     return sc.finish(mbn_launch_f32_upsample_argmax(ctx, s, (int32_t *)labels_i32, (float *)score_f32, (const float *)logits, batch, rows, cols,
                                                     classes, factor));
+}
+
+int mbn_resample_argmax_f32(mbn_context *ctx, void *labels_i32, void *score_f32, const void *logits, int batch, int rows, int cols, int classes,
+                            int out_rows, int out_cols, void *stream)
+{
+    if (!ctx || !labels_i32 || !logits || batch <= 0 || rows <= 0 || cols <= 0 || classes <= 0 || out_rows <= 0 || out_cols <= 0) return MBN_EINVAL;
+    if (((uintptr_t)labels_i32 | (uintptr_t)score_f32 | (uintptr_t)logits) % 4) return MBN_EINVAL;
+    if (mbn_resample_argmax_envelope(batch, rows, cols, classes, out_rows, out_cols) != MBN_OK) return MBN_EUNSUPPORTED;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    const double out = 4.0 * batch * out_rows * out_cols;
+    MBN_SPANS(ctx, { logits, 4.0 * batch * rows * cols * classes, "resample_argmax logits" }, { labels_i32, out, "resample_argmax labels" },
+              { score_f32, out, "resample_argmax score" });
+    Scope sc(ctx, s);
+    return sc.finish(mbn_launch_f32_resample_argmax(ctx, s, (int32_t *)labels_i32, (float *)score_f32, (const float *)logits, batch, rows, cols,
+                                                    classes, out_rows, out_cols));
+}
+
+int mbn_ragged_readout_create(mbn_context *ctx, int max_batch, mbn_ragged_readout **r)
+{
+    if (!ctx || !r) return MBN_EINVAL;
+    *r = nullptr;
+    if (max_batch <= 0) return MBN_EINVAL;
+    if (max_batch > MBN_DENSE_MAX_BATCH) return MBN_EUNSUPPORTED;
+    const int rc = mbn_ragged_readout_build(ctx, max_batch, r);
+    if (rc != MBN_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->ragged_readouts.push_back(*r);
+    return MBN_OK;
+}
+
+int mbn_ragged_readout_destroy(mbn_ragged_readout *r)
+{
+    if (!r) return MBN_OK;
+    mbn_context *ctx = r->ctx;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        for (auto it = ctx->ragged_readouts.begin(); it != ctx->ragged_readouts.end(); ++it)
+            if (*it == r) { ctx->ragged_readouts.erase(it); break; }
+    }
+    (void)hipSetDevice(ctx->device);
+    MBN_HIP_TRY(ctx, hipEventSynchronize(r->done));              // its last upload or launch, whatever the stream
+    MBN_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    mbn_ragged_readout_release(r);
+    return MBN_OK;
+}
+
+int mbn_ragged_readout_set(mbn_ragged_readout *r, int rows, int cols, int classes, const mbn_label_item *items, int batch, void *stream)
+{
+    if (!r || !items || batch <= 0 || batch > r->max_batch || rows <= 0 || cols <= 0 || classes <= 0) return MBN_EINVAL;
+    mbn_context *ctx = r->ctx;
+    (void)hipSetDevice(ctx->device);
+    return mbn_ragged_readout_plan(r, stream ? (hipStream_t)stream : ctx->stream, rows, cols, classes, items, batch);
+}
+
+int mbn_resample_argmax_ragged_f32(mbn_ragged_readout *r, void *labels_i32, void *score_f32, const void *logits, void *stream)
+{
+    if (!r || !labels_i32 || !logits || r->batch <= 0) return MBN_EINVAL;
+    if (((uintptr_t)labels_i32 | (uintptr_t)score_f32 | (uintptr_t)logits) % 4) return MBN_EINVAL;
+    mbn_context *ctx = r->ctx;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    const double out = 4.0 * (double)r->launch.span;
+    MBN_SPANS(ctx, { logits, 4.0 * r->batch * r->rows * r->cols * r->classes, "resample_argmax_ragged logits" },
+              { labels_i32, out, "resample_argmax_ragged labels" }, { score_f32, out, "resample_argmax_ragged score" });
+    Scope sc(ctx, s);
+    return sc.finish(mbn_launch_f32_resample_argmax_ragged(r, s, (int32_t *)labels_i32, (float *)score_f32, (const float *)logits));
 }
 
 int mbn_resizer_create(mbn_context *ctx, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r)

@@ -1,0 +1,304 @@
+// mbn_f32_resample.hip — the dense head's read-out at ANY output size on gfx950: bilinear resample of the per-pixel logits from rows x cols to
+// out_rows x out_cols and the argmax over the classes, in one kernel (mbn_resample_argmax_f32 and its ragged form; include/mbn.h, "dense head at
+// the source resolution", is the normative statement of the arithmetic). mbn_f32_dense.hip is the integer-factor sibling and stays mbn_net_segment's:
+// its structure rests on the factor (a lane's four rows share one patch, a tile owns (P+1)^2 vectors on a grid shifted by S/2); neither holds here.
+//
+// The resampled tensor [out_rows][out_cols][classes] is never formed in memory. A workgroup of 256 lanes owns a 32 x 32 output tile (unshifted: tile
+// (ty, tx) starts at output (32 ty, 32 tx)). The envelope's ratio (out >= 4 x coarse on both axes) bounds what a tile touches: along an axis the
+// source span of 32 outputs is 31 n / N < 8, so i0 takes at most floor(31 n / N) + 2 values and i1 one more: MBN_RESAMPLE_FOOT(n, N) <= 10 coarse
+// rows / columns, fy x fx class vectors. The launch's dynamic LDS holds exactly that footprint (6 x 6 at ratio 8, 10 x 10 only at ratio 4).
+//   stage   per class chunk the fy x fx vectors go from global memory to LDS once (16-byte loads when `logits` is on 16 bytes and classes % 4 == 0,
+//           else dword loads; classes past the end are staged as NaN, which never wins). Vector (j, i) is coarse row min(ybase + j, rows - 1),
+//           column min(xbase + i, cols - 1), ybase / xbase = i0 of the tile's first output row / column;
+//   reduce  a lane owns one output column and four consecutive output rows. Four rows span 3 n / N < 1 of the source, so their i0 is ya or ya + 1
+//           and they touch at most the three coarse rows ya, ya + 1, ya + 2 (clamped). Per class the lane forms the three horizontal interpolants
+//           t0, t1, t2 of its column once; row r takes (t0, t1) or (t1, t2) by a per-row select and keeps a running (best, label) in registers.
+//           A wave neither of whose two row groups crosses a coarse row (a group crosses with probability about 3 n / N; none does at an integer
+//           factor, where i0 steps at multiples of 4) takes the loop without t2 and without the selects: the same products and sums.
+// Classes are visited in ascending order with a strict compare, which IS the definition, so there is no cross-lane reduction. Borders are no special
+// case: every lane evaluates the normative index / weight rule for its own pixel, the weight's quotient in fp64 rounded once to fp32.
+// Every product and sum rounds on its own: contraction into FMA is switched off where they are formed (the build contracts by default).
+// The class chunk is the launch's (MBN_RESAMPLE_CH): 128 while the footprint still leaves eight workgroups on a CU's 160 KB, else 64.
+// The uniform and the ragged form share the tile body; they differ in where a workgroup finds its image's (out_rows, out_cols, destination).
+#include "mbn_internal.h"
+#include "mbn_device.h"
+
+#include <new>
+
+namespace {
+
+constexpr int RS_TILE = MBN_RESAMPLE_TILE;   // output tile side of a workgroup
+constexpr int RS_ROWS = 4;                   // output rows of a lane
+
+// head of the ragged handle's device block, in front of the items; 16 bytes like them
+struct ReadoutHead {
+    int32_t batch, generation, pad[2];
+};
+static_assert(sizeof(ReadoutHead) == 16 && sizeof(mbn_label_item) == 16, "device layout");
+
+struct ResampleArgs {
+    int *labels;
+    float *score;            // may be null
+    const float *logits;
+    int rows, cols, classes; // the coarse map
+    int out_rows, out_cols;  // uniform form: every image's output
+    int tiles_x;             // of the launch's grid.x (ragged: of the widest item)
+    int fy, fx;              // the launch's LDS footprint in vectors; every tile's own is inside it
+    int ch;                  // classes per chunk, a multiple of 4; an LDS row is ch + 4 floats
+    const ReadoutHead *head; // ragged form
+    const mbn_label_item *items;
+    int generation;
+};
+
+// a * wa + b * wb with three roundings
+__device__ __forceinline__ float rs_lerp(float a, float wa, float b, float wb)
+{
+#pragma clang fp contract(off)
+    const float p = a * wa, q = b * wb;
+    return p + q;
+}
+
+// the normative index / weight rule for output coordinate o of an axis with n coarse samples and N outputs: i0 and the weight of i1
+__device__ __forceinline__ void rs_axis(int o, int n, int N, int *i0, float *w1)
+{
+    const int num = max((2 * o + 1) * n - N, 0), den = 2 * N;
+    *i0 = num / den;
+    *w1 = (float)((double)(num % den) / (double)den);       // fp64 quotient, rounded once
+}
+
+// The reduce pass of one staged chunk of cn4 classes for a lane's four rows. CROSS: some row of the wave interpolates between (ya + 1, ya + 2), so
+// the third interpolant and the per-row selects are needed; otherwise every row of the wave uses (t0, t1) and neither is formed. The same products
+// and sums in the same order either way.
+template <bool CROSS>
+__device__ __forceinline__ void rs_reduce(const float *(&p)[3][2], int cn4, int c0, float wx0, float wx1, const float (&wy0)[RS_ROWS],
+                                          const float (&wy1)[RS_ROWS], const bool (&up)[RS_ROWS], float (&best)[RS_ROWS], int (&label)[RS_ROWS])
+{
+    constexpr int NT = CROSS ? 3 : 2;
+    for (int c = 0; c < cn4; c += 4) {
+        f4 v0[NT], v1[NT];
+#pragma unroll
+        for (int j = 0; j < NT; j++) {
+            v0[j] = *reinterpret_cast<const f4 *>(p[j][0] + c);
+            v1[j] = *reinterpret_cast<const f4 *>(p[j][1] + c);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            float t[NT];
+#pragma unroll
+            for (int j = 0; j < NT; j++) t[j] = rs_lerp(v0[j][k], wx0, v1[j][k], wx1);      // horizontal first
+#pragma unroll
+            for (int r = 0; r < RS_ROWS; r++) {
+                const float ta = CROSS && up[r] ? t[1] : t[0], tb = CROSS && up[r] ? t[NT - 1] : t[1];
+                const float v = rs_lerp(ta, wy0[r], tb, wy1[r]);                            // then vertical
+                if (v > best[r]) { best[r] = v; label[r] = c0 + c + k; }
+            }
+        }
+    }
+}
+
+// One 32 x 32 tile of one image: src = the image's logits, labels / score = the image's output maps (score may be null), H x W their size.
+template <bool VEC>
+__device__ __forceinline__ void resample_tile(const ResampleArgs &a, const float *__restrict__ src, int *__restrict__ labels,
+                                              float *__restrict__ score, int H, int W, int ty, int tx, float *s_x)
+{
+    const int tid = threadIdx.x;
+    const int ld = a.ch + 4;                  // 16-byte aligned rows, consecutive vectors 4 banks apart
+    const int nv = a.fy * a.fx;
+    int ybase, xbase;
+    float unused;
+    rs_axis(RS_TILE * ty, a.rows, H, &ybase, &unused);
+    rs_axis(RS_TILE * tx, a.cols, W, &xbase, &unused);
+
+    // this lane's pixels: column ox, rows oy0 .. oy0 + 3 (a coordinate past the image is evaluated at the last one and not stored)
+    const int ox = RS_TILE * tx + (tid & 31), oy0 = RS_TILE * ty + RS_ROWS * (tid >> 5);
+    const bool active = ox < W && oy0 < H;
+    int x0, ya = 0;
+    float wx1, wy1[RS_ROWS], wy0[RS_ROWS];
+    bool up[RS_ROWS];                         // row r interpolates between (ya + 1, ya + 2) instead of (ya, ya + 1)
+    rs_axis(min(ox, W - 1), a.cols, W, &x0, &wx1);
+    const float wx0 = 1.0f - wx1;
+#pragma unroll
+    for (int r = 0; r < RS_ROWS; r++) {
+        int r0;
+        rs_axis(min(oy0 + r, H - 1), a.rows, H, &r0, &wy1[r]);
+        wy0[r] = 1.0f - wy1[r];
+        if (r == 0) ya = r0;
+        up[r] = r0 != ya;                     // r0 is ya or ya + 1: four rows span less than one coarse row
+    }
+    // the same for every lane of the wave (its two groups of rows): at ratio r about 3 / r of the groups cross a coarse row
+    const bool cross = __ballot(up[1] || up[2] || up[3]) != 0;
+    // LDS word offsets of the six vectors: rows ya, min(ya + 1, rows - 1), min(ya + 2, rows - 1) x columns x0, min(x0 + 1, cols - 1). The slots are
+    // inside the staged block by construction; the clamps cost nothing and keep every read inside the launch's LDS whatever the arguments.
+    const int last_y = a.rows - 1, last_x = a.cols - 1;
+    const int sx0 = min(max(x0 - xbase, 0), a.fx - 1), sx1 = min(max(min(x0 + 1, last_x) - xbase, 0), a.fx - 1);
+    const float *p[3][2];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const int sy = min(max(min(ya + j, last_y) - ybase, 0), a.fy - 1);
+        p[j][0] = s_x + (sy * a.fx + sx0) * ld;
+        p[j][1] = s_x + (sy * a.fx + sx1) * ld;
+    }
+
+    float best[RS_ROWS];
+    int label[RS_ROWS];
+#pragma unroll
+    for (int r = 0; r < RS_ROWS; r++) { best[r] = -__builtin_inff(); label[r] = 0; }
+    const float nan = __builtin_nanf("");
+
+    for (int c0 = 0; c0 < a.classes; c0 += a.ch) {
+        const int cn = min(a.ch, a.classes - c0), cn4 = (cn + 3) & ~3;
+        // ---- stage: nv vectors x cn4 classes
+        if (VEC) {
+            const int q = cn4 >> 2;                  // classes % 4 == 0: cn4 == cn
+            for (int e = tid; e < nv * q; e += 256) {
+                const int v = e / q, c = (e - v * q) << 2;
+                const int ry = min(ybase + v / a.fx, last_y), rx = min(xbase + v % a.fx, last_x);
+                *reinterpret_cast<f4 *>(s_x + v * ld + c) = *reinterpret_cast<const f4 *>(src + (unsigned)((ry * a.cols + rx) * a.classes + c0 + c));
+            }
+        } else {
+            for (int e = tid; e < nv * cn4; e += 256) {
+                const int v = e / cn4, c = e - v * cn4;
+                const int ry = min(ybase + v / a.fx, last_y), rx = min(xbase + v % a.fx, last_x);
+                s_x[v * ld + c] = c < cn ? src[(unsigned)((ry * a.cols + rx) * a.classes + c0 + c)] : nan;
+            }
+        }
+        __syncthreads();
+        // ---- reduce
+        if (active) {
+            if (cross) rs_reduce<true>(p, cn4, c0, wx0, wx1, wy0, wy1, up, best, label);
+            else rs_reduce<false>(p, cn4, c0, wx0, wx1, wy0, wy1, up, best, label);
+        }
+        __syncthreads();
+    }
+    if (!active) return;
+    const unsigned out = (unsigned)(oy0 * W + ox);        // 32-bit inside an image: its map is below 2^31 bytes
+#pragma unroll
+    for (int r = 0; r < RS_ROWS; r++) {
+        if (oy0 + r >= H) break;
+        labels[out + (unsigned)(r * W)] = label[r];
+        if (score) score[out + (unsigned)(r * W)] = best[r];
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void resample_argmax_f32(const ResampleArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_rs[];
+    const int ty = (int)blockIdx.x / a.tiles_x, tx = (int)blockIdx.x - ty * a.tiles_x;
+    const size_t img = (size_t)blockIdx.y;                                                      // 64-bit base, 32-bit offsets inside an image
+    const size_t map = (size_t)a.out_rows * a.out_cols;
+    resample_tile<VEC>(a, a.logits + img * ((size_t)a.rows * a.cols * a.classes), a.labels + img * map, a.score ? a.score + img * map : nullptr,
+                       a.out_rows, a.out_cols, ty, tx, s_rs);
+}
+
+// grid = (tiles of the largest item, batch): a workgroup past its own image's tiles returns before any load or barrier
+template <bool VEC>
+__global__ __launch_bounds__(256) void resample_argmax_ragged_f32(const ResampleArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_rs[];
+    // a replay of a captured launch after another set: the items are no longer the ones its grid, LDS and spans were checked for
+    if (a.head->generation != a.generation || (int)blockIdx.y >= a.head->batch) return;
+    const mbn_label_item it = a.items[blockIdx.y];
+    const int tiles_x = (it.cols + RS_TILE - 1) / RS_TILE, tiles_y = (it.rows + RS_TILE - 1) / RS_TILE;
+    const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
+    if (ty >= tiles_y) return;
+    const size_t img = (size_t)blockIdx.y;
+    resample_tile<VEC>(a, a.logits + img * ((size_t)a.rows * a.cols * a.classes), a.labels + it.dst_offset, a.score ? a.score + it.dst_offset : nullptr,
+                       it.rows, it.cols, ty, tx, s_rs);
+}
+
+bool vec_loads(const float *logits, int classes) { return ((uintptr_t)logits % 16) == 0 && (classes % 4) == 0; }   // every class vector then starts on 16 bytes
+
+}   // namespace
+
+// The shape is inside mbn_resample_argmax_envelope and the pointers are non-null multiples of 4 (the caller has checked both).
+int mbn_launch_f32_resample_argmax(mbn_context *, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows, int cols,
+                                   int classes, int out_rows, int out_cols)
+{
+    mbn_resample_launch_t l = { 0, 0, 0, 0, 0, 0 };
+    mbn_resample_plan(rows, cols, out_rows, out_cols, &l);
+    ResampleArgs a = {};
+    a.labels = labels; a.score = score; a.logits = logits;
+    a.rows = rows; a.cols = cols; a.classes = classes;
+    a.out_rows = out_rows; a.out_cols = out_cols;
+    a.tiles_x = (out_cols + RS_TILE - 1) / RS_TILE;
+    a.fy = l.fy; a.fx = l.fx; a.ch = l.ch;
+    const dim3 grid((unsigned)l.tiles, (unsigned)batch);
+    if (vec_loads(logits, classes)) hipLaunchKernelGGL((resample_argmax_f32<true>), grid, dim3(256), (size_t)l.lds_bytes, s, a);
+    else hipLaunchKernelGGL((resample_argmax_f32<false>), grid, dim3(256), (size_t)l.lds_bytes, s, a);
+    return MBN_OK;
+}
+
+int mbn_ragged_readout_build(mbn_context *ctx, int max_batch, mbn_ragged_readout **out)
+{
+    mbn_ragged_readout *r = new (std::nothrow) mbn_ragged_readout();
+    if (!r) return MBN_ENOMEM;
+    r->ctx = ctx;
+    r->max_batch = max_batch;
+    const size_t bytes = 16 * ((size_t)max_batch + 1);
+    r->sort = new (std::nothrow) int64_t[2 * (size_t)max_batch];
+    (void)hipSetDevice(ctx->device);
+    hipError_t e = r->sort ? hipMalloc(&r->dev, bytes) : hipErrorOutOfMemory;
+    if (e == hipSuccess) e = hipHostMalloc(&r->host, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&r->done, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        mbn_ragged_readout_release(r);
+        return e == hipErrorOutOfMemory ? MBN_ENOMEM : mbn_record_hip_error(ctx, e, "ragged read-out buffers");
+    }
+    *out = r;
+    return MBN_OK;
+}
+
+void mbn_ragged_readout_release(mbn_ragged_readout *r)
+{
+    if (r->done) (void)hipEventDestroy(r->done);
+    if (r->host) (void)hipHostFree(r->host);
+    if (r->dev) (void)hipFree(r->dev);
+    delete[] r->sort;
+    delete r;
+}
+
+// Checks the batch first and touches nothing when it is refused: the previous set stays. Then waits for what still reads either copy (the previous
+// upload and every launch since), writes the items into the pinned copy and enqueues its upload.
+int mbn_ragged_readout_plan(mbn_ragged_readout *r, hipStream_t s, int rows, int cols, int classes, const mbn_label_item *items, int batch)
+{
+    mbn_context *ctx = r->ctx;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return MBN_EINVAL;      // a set is not part of a graph
+    mbn_resample_launch_t l = { 0, 0, 0, 0, 0, 0 };
+    const int rc = mbn_resample_ragged_check(rows, cols, classes, items, batch, r->sort, &l);
+    if (rc != MBN_OK) return rc;
+    MBN_HIP_TRY(ctx, hipEventSynchronize(r->done));
+    ReadoutHead *h = (ReadoutHead *)r->host;
+    memset(h, 0, sizeof *h);
+    h->batch = batch; h->generation = r->generation + 1;
+    memcpy(h + 1, items, (size_t)batch * sizeof(mbn_label_item));
+    r->batch = 0;                                               // from here on a failure leaves the handle without a batch
+    MBN_HIP_TRY(ctx, hipMemcpyAsync(r->dev, r->host, 16 * ((size_t)batch + 1), hipMemcpyHostToDevice, s));
+    MBN_HIP_TRY(ctx, hipEventRecord(r->done, s));
+    r->generation = h->generation;
+    r->rows = rows; r->cols = cols; r->classes = classes;
+    r->launch = l;
+    r->batch = batch;
+    return MBN_OK;
+}
+
+// the handle has a batch, the pointers are non-null multiples of 4 and the spans fit (the caller has checked)
+int mbn_launch_f32_resample_argmax_ragged(mbn_ragged_readout *r, hipStream_t s, int32_t *labels, float *score, const float *logits)
+{
+    ResampleArgs a = {};
+    a.labels = labels; a.score = score; a.logits = logits;
+    a.rows = r->rows; a.cols = r->cols; a.classes = r->classes;
+    a.tiles_x = 1;                                              // unused: a workgroup takes its image's own
+    a.fy = r->launch.fy; a.fx = r->launch.fx; a.ch = r->launch.ch;
+    a.head = (const ReadoutHead *)r->dev;
+    a.items = (const mbn_label_item *)(a.head + 1);
+    a.generation = r->generation;
+    const dim3 grid((unsigned)r->launch.tiles, (unsigned)r->batch);
+    if (vec_loads(logits, r->classes)) hipLaunchKernelGGL((resample_argmax_ragged_f32<true>), grid, dim3(256), (size_t)r->launch.lds_bytes, s, a);
+    else hipLaunchKernelGGL((resample_argmax_ragged_f32<false>), grid, dim3(256), (size_t)r->launch.lds_bytes, s, a);
+    // the next set waits for this launch; inside a capture there is nothing to wait for (the replays are the caller's to order)
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) (void)hipEventRecord(r->done, s);
+    return MBN_OK;
+}

@@ -41,6 +41,19 @@ struct mbn_ragged_resizer {
     hipEvent_t done = nullptr;                   // behind the last upload or launch: the next set waits for it
 };
 
+// mbn_ragged_readout_create's handle (mbn_f32_resample.hip): the items of up to max_batch images, on the device and pinned on the host
+struct mbn_ragged_readout {
+    mbn_context *ctx = nullptr;
+    int max_batch = 0;
+    int batch = 0;                               // of the last successful set; 0 = none
+    int rows = 0, cols = 0, classes = 0;         // its coarse map
+    mbn_resample_launch_t launch = {};           // its launch: LDS footprint, class chunk, grid.x, the elements of labels / score it reaches
+    int generation = 0;                          // counts the sets: a captured launch replayed after another set does nothing
+    void *dev = nullptr, *host = nullptr;        // 16-byte head + mbn_label_item [max_batch]
+    int64_t *sort = nullptr;                     // [2 * max_batch]: the overlap check's scratch, so that a set allocates nothing
+    hipEvent_t done = nullptr;                   // behind the last upload or launch: the next set waits for it
+};
+
 struct mbn_context {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -64,6 +77,7 @@ struct mbn_context {
     std::map<std::pair<uintptr_t, int>, mbn_emul_img> emul_ws;   // pw_emul: pre-split filter images, by (filter pointer, layout) (mbn_f32_pw_x6.hip)
     std::vector<mbn_resizer *> resizers;         // live mbn_resizer_create handles (mbn_shutdown frees the stragglers)
     std::vector<mbn_ragged_resizer *> ragged_resizers;   // live mbn_ragged_resizer_create handles, likewise
+    std::vector<mbn_ragged_readout *> ragged_readouts;   // live mbn_ragged_readout_create handles, likewise
     std::mutex mu;
     std::map<uintptr_t, size_t> allocs;          // buffers handed out by mbn_alloc: base address -> bytes (ordered: mbn_span_check
                                                  // finds the allocation that CONTAINS an interior pointer)
@@ -248,6 +262,14 @@ int mbn_launch_f32_softmax_topk(mbn_context *ctx, hipStream_t s, float *probs, i
 // dense head read-out (mbn_f32_dense.hip): bilinear upsample by `factor` + argmax over the classes; the shape is inside mbn_upsample_argmax_envelope
 int mbn_launch_f32_upsample_argmax(mbn_context *ctx, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows,
                                    int cols, int classes, int factor);
+// dense head read-out at any output size (mbn_f32_resample.hip): bilinear resample to out_rows x out_cols + argmax; the shape is inside
+// mbn_resample_argmax_envelope. Ragged form: build allocates, plan checks a batch (a refused one changes nothing) and enqueues the items' upload
+int mbn_launch_f32_resample_argmax(mbn_context *ctx, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows, int cols,
+                                   int classes, int out_rows, int out_cols);
+int mbn_ragged_readout_build(mbn_context *ctx, int max_batch, mbn_ragged_readout **r);
+void mbn_ragged_readout_release(mbn_ragged_readout *r);
+int mbn_ragged_readout_plan(mbn_ragged_readout *r, hipStream_t s, int rows, int cols, int classes, const mbn_label_item *items, int batch);
+int mbn_launch_f32_resample_argmax_ragged(mbn_ragged_readout *r, hipStream_t s, int32_t *labels, float *score, const float *logits);
 // resize front-end (mbn_u8_resize.hip): the geometry is inside mbn_resize_envelope; build uploads the tables (blocking), release frees them
 int mbn_resizer_build(mbn_context *ctx, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r);
 void mbn_resizer_release(mbn_resizer *r);

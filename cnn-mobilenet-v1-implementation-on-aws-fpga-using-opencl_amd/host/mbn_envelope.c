@@ -3,6 +3,8 @@
 #include "mbn_envelope.h"
 #include "mbn.h"
 
+#include <stdlib.h>
+
 int mbn_block_envelope(const mbn_block_shape *s, int dtype)
 {
     const int bf = dtype == MBN_DT_BF16;
@@ -83,6 +85,59 @@ int mbn_upsample_argmax_envelope(int batch, int rows, int cols, int classes, int
     if (4.0 * rows * factor * cols * factor >= 2147483648.0) return MBN_EUNSUPPORTED;                           /* an image's labels / scores */
     /* (both sides of the output map are now below 2^29, so the tile counts are ints) */
     if ((long)MBN_DENSE_TILES(rows, factor) * MBN_DENSE_TILES(cols, factor) > MBN_DENSE_MAX_TILES) return MBN_EUNSUPPORTED;
+    return MBN_OK;
+}
+
+int mbn_resample_argmax_envelope(int batch, int rows, int cols, int classes, int out_rows, int out_cols)
+{
+    if (batch <= 0 || rows <= 0 || cols <= 0 || classes <= 0 || out_rows <= 0 || out_cols <= 0) return MBN_EINVAL;
+    if (batch > MBN_DENSE_MAX_BATCH || out_rows > MBN_RESAMPLE_MAX_OUT || out_cols > MBN_RESAMPLE_MAX_OUT) return MBN_EUNSUPPORTED;
+    if (out_rows < (int64_t)MBN_RESAMPLE_MIN_RATIO * rows || out_cols < (int64_t)MBN_RESAMPLE_MIN_RATIO * cols) return MBN_EUNSUPPORTED;
+    if (4.0 * rows * cols * classes >= 2147483648.0) return MBN_EUNSUPPORTED;                                   /* an image's logits */
+    if (4.0 * out_rows * out_cols >= 2147483648.0) return MBN_EUNSUPPORTED;                                     /* an image's labels / scores */
+    if ((long)((out_rows + MBN_RESAMPLE_TILE - 1) / MBN_RESAMPLE_TILE) * ((out_cols + MBN_RESAMPLE_TILE - 1) / MBN_RESAMPLE_TILE) > MBN_DENSE_MAX_TILES)
+        return MBN_EUNSUPPORTED;
+    return MBN_OK;
+}
+
+void mbn_resample_plan(int rows, int cols, int out_rows, int out_cols, mbn_resample_launch_t *l)
+{
+    const int fy = MBN_RESAMPLE_FOOT(rows, out_rows), fx = MBN_RESAMPLE_FOOT(cols, out_cols);
+    const int tiles = ((out_rows + MBN_RESAMPLE_TILE - 1) / MBN_RESAMPLE_TILE) * ((out_cols + MBN_RESAMPLE_TILE - 1) / MBN_RESAMPLE_TILE);
+    if (fy > l->fy) l->fy = fy;
+    if (fx > l->fx) l->fx = fx;
+    if (tiles > l->tiles) l->tiles = tiles;
+    if ((int64_t)out_rows * out_cols > l->span) l->span = (int64_t)out_rows * out_cols;
+    l->ch = MBN_RESAMPLE_CH(l->fy * l->fx);
+    l->lds_bytes = l->fy * l->fx * (l->ch + 4) * 4;
+}
+
+static int cmp_i64_pair(const void *a, const void *b)
+{
+    const int64_t x = *(const int64_t *)a, y = *(const int64_t *)b;
+    return x < y ? -1 : x > y;
+}
+
+int mbn_resample_ragged_check(int rows, int cols, int classes, const mbn_label_item *items, int batch, int64_t *sort, mbn_resample_launch_t *l)
+{
+    if (!items || !sort || !l || batch <= 0) return MBN_EINVAL;
+    const mbn_resample_launch_t zero = { 0, 0, 0, 0, 0, 0 };
+    mbn_resample_launch_t acc = zero;
+    int64_t span = 0;
+    for (int i = 0; i < batch; i++) {
+        if (items[i].dst_offset < 0) return MBN_EINVAL;
+        const int rc = mbn_resample_argmax_envelope(batch, rows, cols, classes, items[i].rows, items[i].cols);
+        if (rc != MBN_OK) return rc;
+        mbn_resample_plan(rows, cols, items[i].rows, items[i].cols, &acc);
+        sort[2 * i] = items[i].dst_offset;
+        sort[2 * i + 1] = items[i].dst_offset + (int64_t)items[i].rows * items[i].cols;
+        if (sort[2 * i + 1] > span) span = sort[2 * i + 1];
+    }
+    qsort(sort, (size_t)batch, 2 * sizeof(int64_t), cmp_i64_pair);
+    for (int i = 0; i + 1 < batch; i++)
+        if (sort[2 * i + 1] > sort[2 * i + 2]) return MBN_EINVAL;                                               /* two maps overlap */
+    acc.span = span;
+    *l = acc;
     return MBN_OK;
 }
 

@@ -35,6 +35,17 @@ extern "C" {
 #define MBN_DENSE_TILES(n, factor) (((n) * (factor) + (factor) / 2 + MBN_DENSE_TILE - 1) / MBN_DENSE_TILE)
 #define MBN_DENSE_MAX_TILES 0xFFFFFFL
 #define MBN_DENSE_MAX_BATCH 65535
+/* dense head read-out at any output size (mbn_f32_resample.hip): a workgroup owns a 32 x 32 output tile (unshifted). The output is at least
+ * MBN_RESAMPLE_MIN_RATIO times the coarse map on both axes and at most MBN_RESAMPLE_MAX_OUT a side ((2o + 1) * n then stays inside int32 and
+ * den = 2N is exact). MBN_RESAMPLE_FOOT: the coarse samples a tile touches along an axis of n samples and N outputs at most: the source span of 32
+ * outputs is 31 n / N, so i0 takes at most floor(31 n / N) + 2 values and i1 one more (10 at ratio 4, 6 at ratio 8). MBN_RESAMPLE_CH: the class
+ * chunk of a launch whose tiles stage nv vectors: 128 while eight workgroups of nv * 132 floats fit a CU's 160 KB, else 64 (100 vectors: 27 KB, five
+ * workgroups) */
+#define MBN_RESAMPLE_TILE 32
+#define MBN_RESAMPLE_MIN_RATIO 4
+#define MBN_RESAMPLE_MAX_OUT 16384
+#define MBN_RESAMPLE_FOOT(n, N) (31 * (n) / (N) + 3 < (n) ? 31 * (n) / (N) + 3 : (n))
+#define MBN_RESAMPLE_CH(nv) ((nv) * 132 * 4 <= 20 * 1024 ? 128 : 64)
 
 /* one 3x3 depthwise (stride, zero padding pad_top / pad_left) -> 1x1 pointwise block on `batch` NHWC images */
 typedef struct mbn_block_shape {
@@ -56,6 +67,21 @@ int mbn_stem_envelope(int batch, int res, int c1, int c3);
 /* mbn_upsample_argmax_f32: fp32 logits [batch][rows][cols][classes] -> labels (and scores) [batch][rows * factor][cols * factor]. factor 8, 16 or 32;
  * an image's logits and an image's output map each below 2^31 bytes (32-bit offsets inside an image; the batch goes through a 64-bit base) */
 int mbn_upsample_argmax_envelope(int batch, int rows, int cols, int classes, int factor);
+/* mbn_resample_argmax_f32: fp32 logits [batch][rows][cols][classes] -> labels (and scores) [batch][out_rows][out_cols]. MBN_EINVAL for a
+ * non-positive size; else MBN_EUNSUPPORTED unless out_rows >= 4 rows, out_cols >= 4 cols, both at most 16384, an image's logits and an image's
+ * output map each below 2^31 bytes, its tiles below 2^24 and batch at most 65535 */
+int mbn_resample_argmax_envelope(int batch, int rows, int cols, int classes, int out_rows, int out_cols);
+/* what a launch of that kernel needs. mbn_resample_plan WIDENS *l by one output size of a rows x cols map (zero it first): fy, fx = the LDS
+ * footprint in vectors, ch = the class chunk, lds_bytes = fy * fx * (ch + 4) * 4, tiles = grid.x, span = elements of labels / score reached */
+typedef struct mbn_resample_launch_t {
+    int32_t fy, fx, ch, lds_bytes, tiles;
+    int64_t span;
+} mbn_resample_launch_t;
+void mbn_resample_plan(int rows, int cols, int out_rows, int out_cols, mbn_resample_launch_t *l);
+/* the items of one ragged set (mbn_ragged_readout_set) over a rows x cols x classes map: MBN_EINVAL for a non-positive size, a negative
+ * dst_offset or two items whose maps overlap; MBN_EUNSUPPORTED for an item outside the per-image part of mbn_resample_argmax_envelope or a batch
+ * above 65535. sort: scratch of 2 * batch int64. *l: the launch of the whole batch (span = max(dst_offset + rows * cols)) */
+int mbn_resample_ragged_check(int rows, int cols, int classes, const mbn_label_item *items, int batch, int64_t *sort, mbn_resample_launch_t *l);
 /* resize front-end (mbn_u8_resize.hip): one geometry of mbn_resizer_create. Source sides 1..8192, output sides 1..4096, at most MBN_RESIZE_MAX_KSIZE
  * taps per axis (a 32x downscale; any upscale has 3). box = (left, upper, right, lower), NULL = the whole image. MBN_EINVAL for a non-positive
  * size or a box mbn_resize_ksize refuses, else MBN_EUNSUPPORTED outside the limits. The batch (1..MBN_RESIZE_MAX_BATCH: grid.y) belongs to the call. */

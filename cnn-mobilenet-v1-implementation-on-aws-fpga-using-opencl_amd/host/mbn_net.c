@@ -55,6 +55,8 @@ struct mbn_net {
     void *resize_buf;          /* mbn_net_resize_input / _inputs: [max_batch][rows][cols][3] uint8, the resized images */
     mbn_ragged_resizer *ragged;     /* mbn_net_resize_inputs: one ragged resizer of max_batch images, made on the first call */
     mbn_resize_item *ragged_items;  /* ... and the items it is set from, [max_batch] */
+    mbn_ragged_readout *readout;    /* mbn_net_segment_images: one ragged read-out of max_batch images, made on the first call */
+    mbn_label_item *label_items;    /* ... and the items it is set from, [max_batch] */
     void *poolfc_ws;           /* workspace of mbn_pool_fc (1...4 images: pool + FC in one launch), allocated and zeroed at creation */
     size_t poolfc_ws_bytes;
     int fuse_tail;             /* mbn_net_set_fuse_tail (default 0) */
@@ -149,6 +151,8 @@ int mbn_net_destroy(mbn_net *net)
     if (net->resizer) mbn_resizer_destroy(net->resizer);
     if (net->ragged) mbn_ragged_resizer_destroy(net->ragged);
     free(net->ragged_items);
+    if (net->readout) mbn_ragged_readout_destroy(net->readout);
+    free(net->label_items);
     if (net->resize_buf) mbn_free(net->ctx, net->resize_buf);
     for (int j = 0; j < 8; j++)
         if (net->streams[j]) mbn_stream_destroy(net->ctx, net->streams[j]);
@@ -895,6 +899,61 @@ int mbn_net_segment(mbn_net *net, const void *images, int batch, void *labels_i3
     rc = mbn_net_forward_dense(net, images, net->dense_logits, batch);
     if (rc != MBN_OK) return rc;
     return mbn_upsample_argmax_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, factor, NULL);
+}
+
+/* the net's dense logits, [max_batch][h][w][classes] fp32, allocated on first use */
+static int dense_logits_buf(mbn_net *net, const mbn_layer_desc *feat, const mbn_layer_desc *fc)
+{
+    if (net->dense_logits) return MBN_OK;
+    const int rc = mbn_alloc(net->ctx, (size_t)net->max_batch * feat->out_rows * feat->out_cols * fc->out_ch * sizeof(float), &net->dense_logits);
+    if (rc != MBN_OK) net->dense_logits = NULL;
+    return rc;
+}
+
+int mbn_net_segment_to(mbn_net *net, const void *images, int batch, int out_rows, int out_cols, void *labels_i32, void *score_f32)
+{
+    if (!net || !images || !labels_i32 || batch <= 0 || batch > net->max_batch || out_rows <= 0 || out_cols <= 0) return MBN_EINVAL;
+    const mbn_layer_desc *feat, *fc;
+    int rc = dense_layers(net, &feat, &fc);
+    if (rc != MBN_OK) return rc;
+    const int h = feat->out_rows, w = feat->out_cols;
+    if (mbn_resample_argmax_envelope(batch, h, w, fc->out_ch, out_rows, out_cols) != MBN_OK) return MBN_EUNSUPPORTED;   /* before the forward runs */
+    rc = dense_logits_buf(net, feat, fc);
+    if (rc == MBN_OK) rc = mbn_net_forward_dense(net, images, net->dense_logits, batch);
+    if (rc != MBN_OK) return rc;
+    return mbn_resample_argmax_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, out_rows, out_cols, NULL);
+}
+
+int mbn_net_segment_images(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *in_rows, const int32_t *in_cols, int batch,
+                           void *labels_i32, const int64_t *dst_offsets, void *score_f32)
+{
+    if (!net || !src_u8 || !offsets || !in_rows || !in_cols || !labels_i32 || !dst_offsets || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
+    if (!net->input_u8) return MBN_EINVAL;                    /* the resized images are uint8: the net must take them as such */
+    const mbn_layer_desc *feat, *fc;
+    int rc = dense_layers(net, &feat, &fc);
+    if (rc != MBN_OK) return rc;
+    if (!net->label_items) {
+        net->label_items = malloc((size_t)net->max_batch * sizeof(mbn_label_item));
+        if (!net->label_items) return MBN_ENOMEM;
+    }
+    for (int i = 0; i < batch; i++) {
+        net->label_items[i].dst_offset = dst_offsets[i];
+        net->label_items[i].rows = in_rows[i];
+        net->label_items[i].cols = in_cols[i];
+    }
+    if (!net->readout) {
+        rc = mbn_ragged_readout_create(net->ctx, net->max_batch, &net->readout);
+        if (rc != MBN_OK) { net->readout = NULL; return rc; }
+    }
+    /* the set first: it checks every item, so a refusal comes before the resize and the forward run; its upload is ordered by the stream */
+    rc = mbn_ragged_readout_set(net->readout, feat->out_rows, feat->out_cols, fc->out_ch, net->label_items, batch, NULL);
+    if (rc != MBN_OK) return rc;
+    void *images = NULL;
+    rc = mbn_net_resize_inputs(net, src_u8, offsets, in_rows, in_cols, batch, MBN_FIT_STRETCH, 1.0f, &images);
+    if (rc == MBN_OK) rc = dense_logits_buf(net, feat, fc);
+    if (rc == MBN_OK) rc = mbn_net_forward_dense(net, images, net->dense_logits, batch);
+    if (rc != MBN_OK) return rc;
+    return mbn_resample_argmax_ragged_f32(net->readout, labels_i32, score_f32, net->dense_logits, NULL);
 }
 
 int mbn_net_resize_input(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, float crop_fraction, void **images_u8)

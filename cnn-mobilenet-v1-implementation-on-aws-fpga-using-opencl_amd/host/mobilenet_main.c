@@ -10,6 +10,8 @@
  *   bilinear). --fit crop (default: the centred box with the plan's aspect ratio) | stretch (the whole image); --crop-fraction F in (0, 1] shrinks the crop box
  *   (0.875 = "resize to 256, crop 224"). An image of the plan's size is taken as it is
  *   --segment FILE: after the classification, the dense head (mbn_net_segment): the label map of image 0 as a binary PGM and its five most frequent labels
+ *   --segment-source FILE: the label map of image 0 at that --ppm file's OWN width x height (needs --ppm and --fit stretch, else usage status 2): one --ppm
+ *   goes through mbn_net_resize_input + mbn_net_segment_to, several through mbn_net_segment_images (one ragged resize, one ragged read-out)
  *   mobilenet --literal [--weights weights_c.txt] [--image Cat_Image0.ppm] [--ref-args]      the reference's own mode
  *   mobilenet --gpus G --batch N [--steps K --warmup W --streams S --pw-emul 6] (--h5 F | --synthetic SEED)  N images sharded over G GPUs
  *   mobilenet --inspect weights.h5                                                             list the datasets of a .h5
@@ -385,6 +387,49 @@ static int ppm_size(const char *path, int *width, int *height)
 
 #define PPM_MAX_SIDE 8192     /* the resize front-end's largest source side */
 
+/* --segment-source: the --ppm files again, at their own sizes, one behind the other in ONE device buffer; image 0's label map at its own size.
+ * One file: mbn_net_resize_input (stretch) + mbn_net_segment_to; several: mbn_net_segment_images. The net takes uint8 images (the caller has set that) */
+static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int n_ppm, const char *path, int classes)
+{
+    int64_t *offs = malloc(sizeof(int64_t) * (size_t)n_ppm), *dst = malloc(sizeof(int64_t) * (size_t)n_ppm);
+    int32_t *hs = malloc(sizeof(int32_t) * (size_t)n_ppm), *ws = malloc(sizeof(int32_t) * (size_t)n_ppm);
+    if (!offs || !dst || !hs || !ws) return 1;
+    size_t total = 0, pixels = 0;
+    for (int n = 0; n < n_ppm; n++) {
+        int pw = 0, ph = 0;
+        if (ppm_size(ppms[n], &pw, &ph) != MBN_OK || pw > PPM_MAX_SIDE || ph > PPM_MAX_SIDE) {
+            fprintf(stderr, "%s is not a readable P6 image of at most %d x %d pixels\n", ppms[n], PPM_MAX_SIDE, PPM_MAX_SIDE);
+            return 2;
+        }
+        offs[n] = (int64_t)total; dst[n] = (int64_t)pixels; hs[n] = ph; ws[n] = pw;
+        total += (size_t)pw * ph * 3;
+        pixels += (size_t)pw * ph;
+    }
+    unsigned char *all = malloc(total);
+    int *labels = malloc(sizeof(int) * (size_t)hs[0] * ws[0]);
+    if (!all || !labels) return 1;
+    for (int n = 0; n < n_ppm; n++) {
+        int pw = ws[n], ph = hs[n];
+        if (mbn_read_ppm(ppms[n], all + offs[n], &pw, &ph, pw * ph) != MBN_OK) { fprintf(stderr, "cannot read %s\n", ppms[n]); return 2; }
+    }
+    void *d_src, *d_img, *d_labels;
+    CHECK(mbn_alloc(ctx, total, &d_src));
+    CHECK(mbn_alloc(ctx, sizeof(int) * pixels, &d_labels));
+    CHECK(mbn_upload(ctx, d_src, all, total));
+    if (n_ppm == 1) {
+        CHECK(mbn_net_resize_input(net, d_src, 1, hs[0], ws[0], MBN_FIT_STRETCH, 1.0f, &d_img));
+        CHECK(mbn_net_segment_to(net, d_img, 1, hs[0], ws[0], d_labels, NULL));
+    } else {
+        CHECK(mbn_net_segment_images(net, d_src, offs, hs, ws, n_ppm, d_labels, dst, NULL));
+    }
+    CHECK(mbn_download(ctx, labels, d_labels, sizeof(int) * (size_t)hs[0] * ws[0]));      /* image 0 is first in the buffer */
+    CHECK(mbn_free(ctx, d_src));
+    CHECK(mbn_free(ctx, d_labels));
+    const int bad = write_label_map(path, labels, hs[0], ws[0], classes);
+    free(all); free(labels); free(offs); free(dst); free(hs); free(ws);
+    return bad;
+}
+
 int main(int argc, char **argv)
 {
     if (argc == 3 && !strcmp(argv[1], "--inspect")) return inspect_h5(argv[2]);
@@ -392,7 +437,7 @@ int main(int argc, char **argv)
     const char **ppms = malloc(sizeof(char *) * (size_t)argc);          /* every --ppm, in order */
     int n_ppm = 0;
     if (!ppms) return 1;
-    const char *h5 = NULL, *ppm = NULL, *segment = NULL, *wfile = "weights_c.txt", *image = "Cat_Image0.ppm";
+    const char *h5 = NULL, *ppm = NULL, *segment = NULL, *segment_src = NULL, *wfile = "weights_c.txt", *image = "Cat_Image0.ppm";
     int fit = MBN_FIT_CROP;
     float crop_fraction = 1.0f;
     int literal = 0, ref_args = 0, batch = 1, rows = 224, cols = 224, have_seed = 0, gpus = 0, steps = 20, warmup = 3, verify = 0, out_stride = 32;
@@ -413,6 +458,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--alpha") && i + 1 < argc) alpha = (float)atof(argv[++i]);
         else if (!strcmp(argv[i], "--output-stride") && i + 1 < argc) out_stride = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--segment") && i + 1 < argc) segment = argv[++i];
+        else if (!strcmp(argv[i], "--segment-source") && i + 1 < argc) segment_src = argv[++i];
         else if (!strcmp(argv[i], "--fit") && i + 1 < argc && (!strcmp(argv[i + 1], "crop") || !strcmp(argv[i + 1], "stretch")))
             fit = !strcmp(argv[++i], "crop") ? MBN_FIT_CROP : MBN_FIT_STRETCH;
         else if (!strcmp(argv[i], "--crop-fraction") && i + 1 < argc) crop_fraction = (float)atof(argv[++i]);
@@ -428,7 +474,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--literal")) literal = 1;
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
-            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch] [--crop-fraction F]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] "
+            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch] [--crop-fraction F]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm] "
                             "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n", argv[0]);
             return 2;
         }
@@ -436,6 +482,7 @@ int main(int argc, char **argv)
     if (!(crop_fraction > 0.f) || !(crop_fraction <= 1.f)) { fprintf(stderr, "bad --crop-fraction (0 < F <= 1)\n"); return 2; }
     if (n_ppm > 1 && n_ppm > batch) { fprintf(stderr, "%d --ppm files need --batch %d at least\n", n_ppm, n_ppm); return 2; }
     if (n_ppm == 1) ppm = ppms[0];
+    if (segment_src && (n_ppm < 1 || fit != MBN_FIT_STRETCH)) { fprintf(stderr, "--segment-source needs --ppm and --fit stretch\n"); return 2; }
     if (out_stride != 0 && out_stride != 8 && out_stride != 16 && out_stride != 32) { fprintf(stderr, "bad --output-stride (32, 16 or 8)\n"); return 2; }
     mbn_context *ctx = NULL;
     if (gpus > 0 && !literal) {
@@ -574,6 +621,10 @@ int main(int argc, char **argv)
         const int bad = write_label_map(segment, labels, rows, cols, classes);
         free(labels);
         if (bad) return 1;
+    }
+    if (segment_src) {
+        const int bad = segment_source(ctx, net, ppms, n_ppm, segment_src, classes);
+        if (bad) return bad;
     }
     mbn_net_destroy(net);
     mbn_weights_free(&w);

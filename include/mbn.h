@@ -390,6 +390,46 @@ int mbn_softmax_topk_f32(mbn_context *ctx, void *probs, void *topk_idx_i32, void
  * never wins, and a pixel whose every v is NaN or -inf has label 0 and score -inf. */
 int mbn_upsample_argmax_f32(mbn_context *ctx, void *labels_i32, void *score_f32, const void *logits, int batch, int rows, int cols, int classes,
                             int factor, void *stream);
+/* Dense head at the source resolution: the same read-out to ANY output size, out_rows x out_cols instead of rows*factor x cols*factor, in one
+ * kernel that never writes the resampled tensor (mbn_f32_resample.hip). What a segmentation user does after a stretch resize:
+ * resample the coarse logits to the photograph's own size, then take the argmax. logits: fp32 NHWC [batch][rows][cols][classes]; labels_i32 and
+ * score_f32 (may be NULL): [batch][out_rows][out_cols].
+ * The arithmetic, normative (tests/dense_any_ref.py reproduces it bit for bit in numpy). For an axis with n coarse samples and N output samples,
+ * at output coordinate o, with half-pixel centres as torch.nn.functional.interpolate(mode="bilinear", align_corners=False):
+ *     num = max((2*o + 1) * n - N, 0);   den = 2 * N;                                  (integers)
+ *     i0  = num / den;   i1 = min(i0 + 1, n - 1);
+ *     w1  = (float)((double)(num % den) / (double)den);   w0 = 1.0f - w1;
+ * The quotient is formed in fp64 and rounded once to fp32 (numpy reproduces that bit for bit, and it does not depend on how a build compiles a
+ * float division). The interpolation and the argmax are exactly those of mbn_upsample_argmax_f32 above: horizontal first (t0, t1 from x0, x1 and
+ * wx0, wx1), then vertical (v from t0, t1 and wy0, wy1), fmul / fadd each rounded with no contraction, a zero weight still multiplies; classes in
+ * ascending order, class c taken iff v > best (strict), label 0 and score -inf when nothing wins. For N = n * S, S = 8, 16 or 32, the rule
+ * gives the weights and therefore the results of mbn_upsample_argmax_f32 bit for bit.
+ * Envelope: out_rows >= 4 * rows and out_cols >= 4 * cols (a 32 x 32 output tile then touches at most 10 x 10 coarse vectors and a lane's four
+ * rows at most three coarse rows), out_rows and out_cols at most 16384 ((2o + 1) * n stays inside int32), an image's logits and an image's output
+ * map each below 2^31 bytes, batch <= 65535: otherwise MBN_EUNSUPPORTED and nothing is launched. NULL labels / logits, a non-positive size or a
+ * pointer off 4 bytes: MBN_EINVAL. `logits` on 16 bytes with classes % 4 == 0 loads 16 bytes at a time; same results.
+ * Ragged form: ONE launch reads out `batch` images of one coarse shape, each to its own size and place. An image is an mbn_label_item: its
+ * output is rows x cols, at labels + dst_offset (and score + dst_offset), dst_offset in ELEMENTS. Items may come in any order; their maps must
+ * not overlap.
+ *   mbn_ragged_readout_create       allocates everything once: the items of max_batch (1..65535) images on the device and a pinned host copy.
+ *                                   The handle belongs to the context: mbn_shutdown frees the ones still alive
+ *   mbn_ragged_readout_set          checks every item against the coarse shape rows x cols x classes (MBN_EINVAL: a non-positive size, a negative
+ *                                   offset, overlapping maps, batch outside 1..max_batch; MBN_EUNSUPPORTED: an item outside the per-image
+ *                                   envelope above) and enqueues ONE asynchronous copy of the items on `stream`. No allocation. A REFUSED set
+ *                                   changes nothing: the previous set stays valid. It first waits for the handle's previous copy and launches,
+ *                                   whatever their streams. A set is not part of a graph (a capturing `stream`: MBN_EINVAL)
+ *   mbn_resample_argmax_ragged_f32  the launch, asynchronous on `stream`, ordered behind the set by the stream. logits [batch][rows][cols][classes]
+ *                                   of the set. No host allocation and no blocking call: it may be captured as one kernel node; a captured launch
+ *                                   belongs to the set it was captured under and replayed after another set it does nothing. The mbn_alloc bounds
+ *                                   rule applies: labels / score span max(dst_offset + rows * cols) elements. Nothing between the maps is written */
+int mbn_resample_argmax_f32(mbn_context *ctx, void *labels_i32, void *score_f32, const void *logits, int batch, int rows, int cols, int classes,
+                            int out_rows, int out_cols, void *stream);
+typedef struct mbn_label_item { int64_t dst_offset; int32_t rows, cols; } mbn_label_item;   /* 16 bytes; dst_offset in ELEMENTS from labels (and score) */
+typedef struct mbn_ragged_readout mbn_ragged_readout;
+int mbn_ragged_readout_create(mbn_context *ctx, int max_batch, mbn_ragged_readout **r);
+int mbn_ragged_readout_set(mbn_ragged_readout *r, int rows, int cols, int classes, const mbn_label_item *items, int batch, void *stream);
+int mbn_resample_argmax_ragged_f32(mbn_ragged_readout *r, void *labels_i32, void *score_f32, const void *logits, void *stream);
+int mbn_ragged_readout_destroy(mbn_ragged_readout *r);
 /* The classifier tail of the sequence as one call (MobileNet.c:2601-2792): global average pool (kernel.cl:116) ->
  * FC = pointwise with rows = cols = 1 (kernel.cl:94; bias, no ReLU: B15) -> softmax + top-k. fp32 NHWC,
  * in [batch][rows][cols][channels], fc_w [classes][channels], fc_bias [classes] or NULL; pooled_scratch
@@ -781,6 +821,20 @@ int  mbn_net_classify(mbn_net *net, const void *images, int batch, int k, void *
  * only). The FC and the read-out are not part of a graph captured under mbn_net_set_graph. */
 int  mbn_net_forward_dense(mbn_net *net, const void *images, void *dense_logits, int batch);
 int  mbn_net_segment(mbn_net *net, const void *images, int batch, void *labels_i32, void *score_f32);
+/* Labels at the SOURCE resolution (mbn_resample_argmax_f32 above; the stretch fit only: with a crop the network saw a box of the image and labels
+ * for the rest would be invented):
+ *   mbn_net_segment_to      mbn_net_forward_dense into the net's dense logits, then mbn_resample_argmax_f32 to out_rows x out_cols: labels_i32 (and
+ *                           score_f32, may be NULL) [batch][out_rows][out_cols]. The caller pairs it with mbn_net_resize_input(..., MBN_FIT_STRETCH, ...)
+ *                           and the source size. An output below 4 x the map: MBN_EUNSUPPORTED before anything runs
+ *   mbn_net_segment_images  the whole path for images of DIFFERENT sizes, as mbn_net_resize_inputs takes them: needs mbn_net_set_input_u8(net, 1)
+ *                           (else MBN_EINVAL); mbn_net_resize_inputs with MBN_FIT_STRETCH, mbn_net_forward_dense, then ONE ragged read-out of
+ *                           image i to its own rows[i] x cols[i] at labels_i32 + dst_offsets[i] (and score_f32 + dst_offsets[i]; elements). The net
+ *                           keeps one ragged read-out handle of max_batch images, created on the first call and freed by mbn_net_destroy. The
+ *                           items are checked before anything runs
+ * F32, BF16 and I8 (output stride 32 only), any plan of mbn_plan_build_os. A refusal leaves the net usable. */
+int  mbn_net_segment_to(mbn_net *net, const void *images, int batch, int out_rows, int out_cols, void *labels_i32, void *score_f32);
+int  mbn_net_segment_images(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *rows, const int32_t *cols, int batch,
+                            void *labels_i32, const int64_t *dst_offsets, void *score_f32);
 /* Per-layer milliseconds of the most recent mbn_net_forward_timed call (hipEvents between layers). */
 int  mbn_net_forward_timed(mbn_net *net, const void *images, void *logits, int batch, float *layer_ms,
                            int n_layer_ms);

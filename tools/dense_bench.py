@@ -12,6 +12,10 @@
       label + 4 of score per pixel out) over 8 TB/s, and its VALU work (per pixel and class: 3 interpolants of 2 multiplies + 1 add
       shared as the kernel shares them, + compare and two selects) over the vector rate. The labels of the two routes are compared
       once (agreement, not timing). One JSON object at the end. No GPU: the Context raises; nothing falls back.
+
+  python tools/dense_bench.py --any [--reps 7] [--steps 20] [--batch 32] [--torch-steps 2] [--no-torch]
+      mbn_resample_argmax_f32, the read-out at any output size (main_any): against mbn_upsample_argmax_f32 at equal shapes, to 375 x 500
+      against torch, and ragged.
 """
 import argparse
 import json
@@ -49,6 +53,98 @@ def marks_ms(ctx, fn, steps):
     return sum(ctx.marks_read(4)) / steps
 
 
+def resample_work(batch, h, w, classes, pix, three=True):
+    """(bytes, vector lane-operations) of mbn_resample_argmax_f32 for `pix` output pixels in all. three: counted as if every wave took the loop
+    with three horizontal interpolants per class and lane and two more selects per row (an upper count: a wave whose rows cross no coarse row
+    takes kernel_work's loop, and at an integer factor every wave does: three=False)"""
+    return 4.0 * batch * h * w * classes + 8.0 * pix, pix * classes * ((9.0 / 4 + 8.0) if three else (6.0 / 4 + 6.0))
+
+
+def main_any(a):
+    """--any: mbn_resample_argmax_f32, the read-out at any output size, on the maps of a 1.0x224 net (1000 classes, --batch images of random
+    logits; the kernels' time does not depend on the values):
+      factor   at out = S x coarse (28 x 28 x 8, 14 x 14 x 16, 7 x 7 x 32) against mbn_upsample_argmax_f32 on the same buffer, alternating
+      source   to 375 x 500 from the 28 x 28 and the 14 x 14 map; the yardstick is torch-ROCm's interpolate(size=(375, 500)).argmax(1) on the
+               same buffer (it writes and reads back batch x 1000 x 375 x 500 floats, in slices of 8 images because its kernel refuses
+               outputs of 2^31 elements: --torch-steps passes per repetition)
+      ragged   --batch images of 300-600 x 300-700 in one launch from the 14 x 14 map (no torch counterpart: torch is timed uniform only)"""
+    pkg = import_package()
+    torch = None
+    if not a.no_torch:
+        import torch
+        assert torch.cuda.is_available(), "the yardstick needs torch on the same GPU"
+    n, rng = a.batch, np.random.default_rng(0)
+    sizes = [(int(rng.integers(300, 601)), int(rng.integers(300, 701))) for _ in range(n)]
+    offs = np.concatenate([[0], np.cumsum([r * c for r, c in sizes])]).astype(np.int64)
+    cap = max(int(offs[-1]), n * 375 * 500, n * RES * RES)
+    result = {}
+    with pkg.Context(0) as ctx:
+        d_lab, d_sc = ctx.alloc(cap * 4), ctx.alloc(cap * 4)
+        maps, runs = {}, []
+        for hw_ in (28, 14, 7):
+            x = (3.0 * rng.standard_normal((n, hw_, hw_, CLASSES))).astype(np.float32)
+            if torch is not None:
+                t = torch.from_numpy(x).cuda()
+                maps[hw_] = (t.data_ptr(), t)
+            else:
+                b = ctx.to_device(x)
+                maps[hw_] = (b.ptr, b)
+        for hw_ in (28, 14, 7):
+            S, p = RES // hw_, maps[hw_][0]
+            runs.append(("factor_%dx%d_any" % (hw_, S), lambda p=p, hw_=hw_: ctx.resample_argmax(d_lab.ptr, d_sc.ptr, p, n, hw_, hw_, CLASSES, RES, RES),
+                         resample_work(n, hw_, hw_, CLASSES, n * RES * RES, three=False)))
+            runs.append(("factor_%dx%d_factor_kernel" % (hw_, S), lambda p=p, hw_=hw_, S=S: ctx.upsample_argmax(d_lab.ptr, d_sc.ptr, p, n, hw_, hw_, CLASSES, S),
+                         kernel_work(n, hw_, hw_, CLASSES, S)))
+        for hw_ in (28, 14):
+            p = maps[hw_][0]
+            runs.append(("source_375x500_from_%d" % hw_, lambda p=p, hw_=hw_: ctx.resample_argmax(d_lab.ptr, d_sc.ptr, p, n, hw_, hw_, CLASSES, 375, 500),
+                         resample_work(n, hw_, hw_, CLASSES, n * 375 * 500)))
+        rd = pkg.RaggedReadout(ctx, n)
+        rd.set(14, 14, CLASSES, [(int(o), r, c) for o, (r, c) in zip(offs, sizes)])
+        runs.append(("ragged_%d_images_from_14" % n, lambda: rd.run(d_lab.ptr, d_sc.ptr, maps[14][0]), resample_work(n, 14, 14, CLASSES, int(offs[-1]))))
+        times = {name: [] for name, _, _ in runs}
+        for _, fn, _ in runs:
+            marks_ms(ctx, fn, 3)
+        t_times = {28: [], 14: []}
+        for _ in range(a.reps):
+            for name, fn, _ in runs:
+                times[name].append(marks_ms(ctx, fn, a.steps))
+            for hw_ in (28, 14) if torch is not None else ():
+                ctx.sync()
+                nchw = maps[hw_][1].permute(0, 3, 1, 2)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+                def two_pass():     # torch's kernel takes outputs below 2^31 elements: 8 images of 1000 x 375 x 500 a call
+                    for i in range(0, n, 8):
+                        torch.nn.functional.interpolate(nchw[i:i + 8], size=(375, 500), mode="bilinear", align_corners=False).argmax(1)
+                two_pass()
+                e0.record()
+                for _ in range(a.torch_steps):
+                    two_pass()
+                e1.record()
+                torch.cuda.synchronize()
+                t_times[hw_].append(e0.elapsed_time(e1) / a.torch_steps)
+        for name, _, (bytes_, ops) in runs:
+            k = statistics.median(times[name])
+            result[name] = {"batch": n, "kernel_ms": round(k, 4), "kernel_runs_ms": [round(v, 4) for v in times[name]], "kernel_bytes": int(bytes_),
+                            "kernel_frac_of_8TBps": round(bytes_ / HBM_BYTES_PER_S / (k / 1e3), 4),
+                            "kernel_frac_of_valu_rate": round(ops / VALU_LANE_OPS_PER_S / (k / 1e3), 4)}
+            print("%-32s %.4f ms  (%.1f %% of 8 TB/s, %.1f %% of the VALU rate)" % (name, k, 100 * result[name]["kernel_frac_of_8TBps"],
+                                                                                     100 * result[name]["kernel_frac_of_valu_rate"]), flush=True)
+        for hw_ in (28, 14, 7):
+            S = RES // hw_
+            result["factor_%dx%d_any_over_factor_kernel" % (hw_, S)] = round(
+                result["factor_%dx%d_any" % (hw_, S)]["kernel_ms"] / result["factor_%dx%d_factor_kernel" % (hw_, S)]["kernel_ms"], 3)
+        for hw_, ts in t_times.items():
+            if ts:
+                t = statistics.median(ts)
+                result["source_375x500_from_%d" % hw_].update({"torch_ms": round(t, 4), "torch_runs_ms": [round(v, 4) for v in ts],
+                                                               "torch_over_kernel": round(t / result["source_375x500_from_%d" % hw_]["kernel_ms"], 2)})
+        result["ragged_pixels"] = int(offs[-1])
+        rd.close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
@@ -56,7 +152,11 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--configs", default="", help="comma list of configuration names (default: all)")
     ap.add_argument("--no-torch", action="store_true", help="skip the torch yardstick")
+    ap.add_argument("--any", action="store_true", help="time mbn_resample_argmax_f32 (the read-out at any output size) instead: see main_any")
+    ap.add_argument("--torch-steps", type=int, default=2, help="--any: torch calls per repetition (each writes batch x 1000 x 375 x 500 floats)")
     a = ap.parse_args()
+    if a.any:
+        return main_any(a)
     chosen = [c for c in CONFIGS if not a.configs or c[0] in a.configs.split(",")]
     pkg = import_package()
     torch = None
