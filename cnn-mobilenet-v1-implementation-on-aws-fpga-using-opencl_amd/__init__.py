@@ -36,6 +36,9 @@ QUIRKS_NONE, QUIRKS_KERNEL_CL = 0, 0xF
 L_CONV, L_DW, L_PW, L_POOL, L_FC = 1, 2, 3, 4, 5
 MAX_LAYERS = 32
 FIT_STRETCH, FIT_CROP = 0, 1
+# MBN_FILTER_*: the filter of the resize front-end, PIL.Image.Resampling's own numbers
+FILTER_NEAREST, FILTER_LANCZOS, FILTER_BILINEAR, FILTER_BICUBIC, FILTER_BOX, FILTER_HAMMING = 0, 1, 2, 3, 4, 5
+FILTER_NAMES = {"nearest": 0, "lanczos": 1, "bilinear": 2, "bicubic": 3, "box": 4, "hamming": 5}
 
 
 class MbnError(RuntimeError):
@@ -181,6 +184,15 @@ def _declare_host(lib):
     lib.mbn_resize_table_plan.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(ResizePlan)]
     lib.mbn_resize_ragged_plan.argtypes = [C.POINTER(ResizeItem), C.c_int, C.c_int, C.POINTER(ResizeDesc)]
     lib.mbn_resize_ragged_plan_batch.argtypes = [C.POINTER(ResizeItem), C.c_int, C.c_int, C.c_int, C.POINTER(ResizeDesc), i32p, i32p, C.POINTER(C.c_int64)]
+    # the same under a filter (MBN_FILTER_*): the filter is the first argument
+    lib.mbn_resize_ksize_filter.argtypes = [C.c_int] + lib.mbn_resize_ksize.argtypes
+    lib.mbn_resize_taps_filter.argtypes = [C.c_int] + lib.mbn_resize_taps.argtypes
+    lib.mbn_resize_nearest_index.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int, i32p]
+    lib.mbn_resize_envelope_filter.argtypes = [C.c_int] + lib.mbn_resize_envelope.argtypes
+    lib.mbn_resize_window_filter.argtypes = [C.c_int] + lib.mbn_resize_window.argtypes
+    lib.mbn_resize_table_plan_filter.argtypes = [C.c_int] + lib.mbn_resize_table_plan.argtypes
+    lib.mbn_resize_ragged_plan_filter.argtypes = [C.c_int] + lib.mbn_resize_ragged_plan.argtypes
+    lib.mbn_resize_ragged_plan_batch_filter.argtypes = [C.c_int] + lib.mbn_resize_ragged_plan_batch.argtypes
     return lib
 
 
@@ -303,6 +315,11 @@ def load():
         lib.mbn_ragged_resizer_destroy.argtypes = [vp]
         lib.mbn_resize_taps_device.argtypes = [vp, ci, C.c_float, C.c_float, ci, vp, vp, vp]
         lib.mbn_net_resize_inputs.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, ci, C.c_float, C.POINTER(vp)]
+        lib.mbn_resizer_create_filter.argtypes = [vp, ci, ci, ci, C.POINTER(C.c_float), ci, ci, C.POINTER(vp)]
+        lib.mbn_ragged_resizer_create_filter.argtypes = [vp, ci, ci, ci, ci, C.POINTER(vp)]
+        lib.mbn_resize_taps_device_filter.argtypes = [vp, ci, ci, C.c_float, C.c_float, ci, vp, vp, vp]
+        lib.mbn_net_set_resize_filter.argtypes = [vp, ci]
+        lib.mbn_net_get_resize_filter.argtypes = [vp, C.POINTER(ci)]
         lib.mbn_graph_begin.argtypes = [vp, vp]
         lib.mbn_graph_end.argtypes = [vp, vp, C.POINTER(vp)]
         lib.mbn_graph_launch.argtypes = [vp, vp, vp]
@@ -349,24 +366,32 @@ def _box4(box):
     return (C.c_float * 4)(*[float(np.float32(v)) for v in box])
 
 
-def resize_ksize(in_size, b0, b1, out_size, lib=None) -> int:
-    """mbn_resize_ksize: taps per output of one axis of the resize front-end (raises MbnError on a refused box)."""
-    k = (lib or host_lib()).mbn_resize_ksize(in_size, b0, b1, out_size)
+def resize_ksize(in_size, b0, b1, out_size, lib=None, filter=FILTER_BILINEAR) -> int:
+    """mbn_resize_ksize_filter: taps per output of one axis of the resize front-end (raises MbnError on a refused box or filter)."""
+    k = (lib or host_lib()).mbn_resize_ksize_filter(filter, in_size, b0, b1, out_size)
     if k < 0:
         raise MbnError(k, "resize_ksize(%d, %r, %r, %d)" % (in_size, b0, b1, out_size))
     return k
 
 
-def resize_taps(in_size, b0, b1, out_size, lib=None):
-    """mbn_resize_taps: (first [out_size], count [out_size], weights [out_size][ksize]) of one axis, int32."""
+def resize_taps(in_size, b0, b1, out_size, lib=None, filter=FILTER_BILINEAR):
+    """mbn_resize_taps_filter: (first [out_size], count [out_size], weights [out_size][ksize]) of one axis, int32."""
     lib = lib or host_lib()
-    ks = resize_ksize(in_size, b0, b1, out_size, lib)
+    ks = resize_ksize(in_size, b0, b1, out_size, lib, filter)
     first, count, weights = np.zeros(out_size, np.int32), np.zeros(out_size, np.int32), np.zeros((out_size, ks), np.int32)
     i32p = C.POINTER(C.c_int32)
-    rc = lib.mbn_resize_taps(in_size, b0, b1, out_size, first.ctypes.data_as(i32p), count.ctypes.data_as(i32p), weights.ctypes.data_as(i32p))
+    rc = lib.mbn_resize_taps_filter(filter, in_size, b0, b1, out_size, first.ctypes.data_as(i32p), count.ctypes.data_as(i32p),
+                                    weights.ctypes.data_as(i32p))
     if rc < 0:
         raise MbnError(rc, "resize_taps")
     return first, count, weights
+
+
+def resize_nearest_index(in_size, b0, b1, out_size, lib=None) -> np.ndarray:
+    """mbn_resize_nearest_index: the source position of every output of one axis under FILTER_NEAREST, int32 [out_size]."""
+    index = np.zeros(out_size, np.int32)
+    _chk((lib or host_lib()).mbn_resize_nearest_index(in_size, b0, b1, out_size, index.ctypes.data_as(C.POINTER(C.c_int32))), "resize_nearest_index")
+    return index
 
 
 def fit_box(in_rows, in_cols, out_rows, out_cols, fit=FIT_CROP, crop_fraction=1.0, lib=None) -> np.ndarray:
@@ -386,29 +411,29 @@ def resize_items(items):
     return arr
 
 
-def resize_window(in_size, b0, b1, out_size, o_first, o_last, lib=None):
-    """mbn_resize_window: [lo, hi) of the source positions the outputs o_first..o_last of an axis reach (no table is built)."""
+def resize_window(in_size, b0, b1, out_size, o_first, o_last, lib=None, filter=FILTER_BILINEAR):
+    """mbn_resize_window_filter: [lo, hi) of the source positions the outputs o_first..o_last of an axis reach (no table is built)."""
     lo, hi = C.c_int32(), C.c_int32()
-    _chk((lib or host_lib()).mbn_resize_window(in_size, b0, b1, out_size, o_first, o_last, C.byref(lo), C.byref(hi)), "resize_window")
+    _chk((lib or host_lib()).mbn_resize_window_filter(filter, in_size, b0, b1, out_size, o_first, o_last, C.byref(lo), C.byref(hi)), "resize_window")
     return lo.value, hi.value
 
 
-def resize_table_plan(in_rows, in_cols, out_rows, out_cols, box=None, lib=None) -> ResizePlan:
-    """mbn_resize_table_plan: the tile mbn_resizer_create chooses for a geometry (box None = the whole image)."""
+def resize_table_plan(in_rows, in_cols, out_rows, out_cols, box=None, lib=None, filter=FILTER_BILINEAR) -> ResizePlan:
+    """mbn_resize_table_plan_filter: the tile mbn_resizer_create_filter chooses for a geometry (box None = the whole image)."""
     p = ResizePlan()
-    _chk((lib or host_lib()).mbn_resize_table_plan(in_rows, in_cols, _box4(box), out_rows, out_cols, C.byref(p)),
+    _chk((lib or host_lib()).mbn_resize_table_plan_filter(filter, in_rows, in_cols, _box4(box), out_rows, out_cols, C.byref(p)),
          "resize_table_plan(%d, %d, %d, %d)" % (in_rows, in_cols, out_rows, out_cols))
     return p
 
 
-def resize_ragged_plan(items, out_rows, out_cols, lib=None):
-    """mbn_resize_ragged_plan_batch: (descriptors, workgroups, dynamic LDS bytes, bytes of src reached) of a ragged launch of `items`
+def resize_ragged_plan(items, out_rows, out_cols, lib=None, filter=FILTER_BILINEAR):
+    """mbn_resize_ragged_plan_batch_filter: (descriptors, workgroups, dynamic LDS bytes, bytes of src reached) of a ragged launch of `items`
     ((src_offset, rows, cols, box) tuples, or a ResizeItem array)."""
     arr = items if isinstance(items, C.Array) else resize_items(items)
     desc = (ResizeDesc * len(arr))()
     wgs, lds, span = C.c_int32(), C.c_int32(), C.c_int64()
-    _chk((lib or host_lib()).mbn_resize_ragged_plan_batch(arr, len(arr), out_rows, out_cols, desc, C.byref(wgs), C.byref(lds), C.byref(span)),
-         "resize_ragged_plan")
+    _chk((lib or host_lib()).mbn_resize_ragged_plan_batch_filter(filter, arr, len(arr), out_rows, out_cols, desc, C.byref(wgs), C.byref(lds),
+                                                                  C.byref(span)), "resize_ragged_plan")
     return desc, wgs.value, lds.value, span.value
 
 
@@ -678,14 +703,16 @@ class RaggedReadout:
 
 
 class Resizer:
-    """mbn_resizer_create / mbn_resize_u8: uint8 HWC images [batch][in_rows][in_cols][3] -> [batch][out_rows][out_cols][3], Pillow's 8-bit bilinear
-    resize of `box` = (left, upper, right, lower) (None = the whole image), byte for byte. One geometry per handle."""
+    """mbn_resizer_create_filter / mbn_resize_u8: uint8 HWC images [batch][in_rows][in_cols][3] -> [batch][out_rows][out_cols][3], Pillow's 8-bit
+    resize of `box` = (left, upper, right, lower) (None = the whole image) under `filter` (FILTER_*, bilinear by default), byte for byte. One
+    geometry and one filter per handle."""
 
-    def __init__(self, ctx: Context, in_rows, in_cols, out_rows, out_cols, box=None):
+    def __init__(self, ctx: Context, in_rows, in_cols, out_rows, out_cols, box=None, filter=FILTER_BILINEAR):
         self.ctx = ctx
+        self.filter = filter
         self.shape_in, self.shape_out = (in_rows, in_cols, 3), (out_rows, out_cols, 3)
         h = C.c_void_p()
-        _chk(ctx.lib.mbn_resizer_create(ctx.h, in_rows, in_cols, _box4(box), out_rows, out_cols, C.byref(h)), ctx.last_error())
+        _chk(ctx.lib.mbn_resizer_create_filter(ctx.h, filter, in_rows, in_cols, _box4(box), out_rows, out_cols, C.byref(h)), ctx.last_error())
         self.h = h
         if not hasattr(ctx, "_resizers"):
             ctx._resizers = []
@@ -702,15 +729,17 @@ class Resizer:
 
 class RaggedResizer:
     """mbn_ragged_resizer_create / _set / mbn_resize_ragged_u8: up to max_batch uint8 HWC images, each with its own rows, cols and box, to one
-    [batch][out_rows][out_cols][3] in ONE launch, Pillow's 8-bit bilinear resize byte for byte. set() takes (src_offset, rows, cols, box) tuples
-    (byte offsets from the src pointer of run(); box None = the whole image)."""
+    [batch][out_rows][out_cols][3] in ONE launch, Pillow's 8-bit resize under `filter` byte for byte (FILTER_NEAREST, _BOX, _BILINEAR, the default,
+    or _BICUBIC; hamming and lanczos raise MbnError: EUNSUPPORTED). set() takes (src_offset, rows, cols, box) tuples (byte offsets from the src
+    pointer of run(); box None = the whole image)."""
 
-    def __init__(self, ctx: Context, max_batch, out_rows, out_cols):
+    def __init__(self, ctx: Context, max_batch, out_rows, out_cols, filter=FILTER_BILINEAR):
         self.ctx = ctx
+        self.filter = filter
         self.shape_out = (out_rows, out_cols, 3)
         self.batch = 0
         h = C.c_void_p()
-        _chk(ctx.lib.mbn_ragged_resizer_create(ctx.h, max_batch, out_rows, out_cols, C.byref(h)), ctx.last_error())
+        _chk(ctx.lib.mbn_ragged_resizer_create_filter(ctx.h, filter, max_batch, out_rows, out_cols, C.byref(h)), ctx.last_error())
         self.h = h
         if not hasattr(ctx, "_resizers"):
             ctx._resizers = []
@@ -731,12 +760,14 @@ class RaggedResizer:
             self.h = None
 
 
-def resize_taps_device(ctx, in_size, b0, b1, out_size):
-    """mbn_resize_taps_device: the kernel's own tap function for one axis, downloaded: (first, count, weights [out_size][ksize]) int32."""
-    ks = resize_ksize(in_size, b0, b1, out_size, ctx.lib)
+def resize_taps_device(ctx, in_size, b0, b1, out_size, filter=FILTER_BILINEAR):
+    """mbn_resize_taps_device_filter: the kernel's own tap function for one axis, downloaded: (first, count, weights [out_size][ksize]) int32."""
+    ks = resize_ksize(in_size, b0, b1, out_size, ctx.lib, filter)
     d_f, d_c, d_w = ctx.alloc(4 * out_size), ctx.alloc(4 * out_size), ctx.alloc(4 * out_size * ks)
-    rc = ctx.lib.mbn_resize_taps_device(ctx.h, in_size, b0, b1, out_size, d_f.ptr, d_c.ptr, d_w.ptr)
+    rc = ctx.lib.mbn_resize_taps_device_filter(ctx.h, filter, in_size, b0, b1, out_size, d_f.ptr, d_c.ptr, d_w.ptr)
     if rc < 0:
+        for b in (d_f, d_c, d_w):
+            b.free()
         raise MbnError(rc, "resize_taps_device")
     assert rc == ks
     ctx.sync()
@@ -882,6 +913,15 @@ class Net:
         _chk(self.ctx.lib.mbn_net_resize_inputs(self.h, src_ptr, (C.c_int64 * n)(*[int(v) for v in offsets]), (C.c_int32 * n)(*[int(v) for v in rows]),
                                                 (C.c_int32 * n)(*[int(v) for v in cols]), n, fit, crop_fraction, C.byref(p)), self.ctx.last_error())
         return p.value
+
+    def set_resize_filter(self, filter):
+        """mbn_net_set_resize_filter: FILTER_* of resize_input / resize_inputs / segment_images (bilinear until it is called)."""
+        _chk(self.ctx.lib.mbn_net_set_resize_filter(self.h, int(filter)), "set_resize_filter(%r)" % (filter,))
+
+    def resize_filter(self) -> int:
+        f = C.c_int()
+        _chk(self.ctx.lib.mbn_net_get_resize_filter(self.h, C.byref(f)))
+        return f.value
 
     def set_input_u8(self, enabled=True):
         _chk(self.ctx.lib.mbn_net_set_input_u8(self.h, int(enabled)))

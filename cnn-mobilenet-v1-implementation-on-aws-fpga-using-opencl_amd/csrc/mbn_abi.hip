@@ -896,17 +896,22 @@ int mbn_resample_argmax_ragged_f32(mbn_ragged_readout *r, void *labels_i32, void
     return sc.finish(mbn_launch_f32_resample_argmax_ragged(r, s, (int32_t *)labels_i32, (float *)score_f32, (const float *)logits));
 }
 
-int mbn_resizer_create(mbn_context *ctx, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r)
+int mbn_resizer_create_filter(mbn_context *ctx, int filter, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r)
 {
     if (!ctx || !r) return MBN_EINVAL;
     *r = nullptr;
-    int rc = mbn_resize_envelope(in_rows, in_cols, box, out_rows, out_cols);
+    int rc = mbn_resize_envelope_filter(filter, in_rows, in_cols, box, out_rows, out_cols);
     if (rc != MBN_OK) return rc;
-    rc = mbn_resizer_build(ctx, in_rows, in_cols, box, out_rows, out_cols, r);
+    rc = mbn_resizer_build(ctx, filter, in_rows, in_cols, box, out_rows, out_cols, r);
     if (rc != MBN_OK) return rc;
     std::lock_guard<std::mutex> lk(ctx->mu);
     ctx->resizers.push_back(*r);
     return MBN_OK;
+}
+
+int mbn_resizer_create(mbn_context *ctx, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r)
+{
+    return mbn_resizer_create_filter(ctx, MBN_FILTER_BILINEAR, in_rows, in_cols, box, out_rows, out_cols, r);
 }
 
 int mbn_resizer_destroy(mbn_resizer *r)
@@ -935,17 +940,23 @@ int mbn_resize_u8(mbn_resizer *r, void *out_u8, const void *in_u8, int batch, vo
     return sc.finish(mbn_launch_u8_resize(r, s, (uint8_t *)out_u8, (const uint8_t *)in_u8, batch));
 }
 
-int mbn_ragged_resizer_create(mbn_context *ctx, int max_batch, int out_rows, int out_cols, mbn_ragged_resizer **r)
+int mbn_ragged_resizer_create_filter(mbn_context *ctx, int filter, int max_batch, int out_rows, int out_cols, mbn_ragged_resizer **r)
 {
     if (!ctx || !r) return MBN_EINVAL;
     *r = nullptr;
-    if (max_batch <= 0 || out_rows <= 0 || out_cols <= 0) return MBN_EINVAL;
+    if (filter < MBN_FILTER_NEAREST || filter > MBN_FILTER_HAMMING || max_batch <= 0 || out_rows <= 0 || out_cols <= 0) return MBN_EINVAL;
+    if (filter == MBN_FILTER_HAMMING || filter == MBN_FILTER_LANCZOS) return MBN_EUNSUPPORTED;       // no device form of their weights (mbn.h)
     if (max_batch > MBN_RESIZE_MAX_BATCH || out_rows > MBN_RESIZE_MAX_OUT || out_cols > MBN_RESIZE_MAX_OUT) return MBN_EUNSUPPORTED;
-    const int rc = mbn_ragged_resizer_build(ctx, max_batch, out_rows, out_cols, r);
+    const int rc = mbn_ragged_resizer_build(ctx, filter, max_batch, out_rows, out_cols, r);
     if (rc != MBN_OK) return rc;
     std::lock_guard<std::mutex> lk(ctx->mu);
     ctx->ragged_resizers.push_back(*r);
     return MBN_OK;
+}
+
+int mbn_ragged_resizer_create(mbn_context *ctx, int max_batch, int out_rows, int out_cols, mbn_ragged_resizer **r)
+{
+    return mbn_ragged_resizer_create_filter(ctx, MBN_FILTER_BILINEAR, max_batch, out_rows, out_cols, r);
 }
 
 int mbn_ragged_resizer_destroy(mbn_ragged_resizer *r)
@@ -986,15 +997,22 @@ int mbn_resize_ragged_u8(mbn_ragged_resizer *r, void *out_u8, const void *src_u8
 
 int mbn_resize_taps_device(mbn_context *ctx, int in_size, float b0, float b1, int out_size, void *first_i32, void *count_i32, void *weights_i32)
 {
+    return mbn_resize_taps_device_filter(ctx, MBN_FILTER_BILINEAR, in_size, b0, b1, out_size, first_i32, count_i32, weights_i32);
+}
+
+int mbn_resize_taps_device_filter(mbn_context *ctx, int filter, int in_size, float b0, float b1, int out_size, void *first_i32, void *count_i32,
+                                  void *weights_i32)
+{
     if (!ctx || !first_i32 || !count_i32 || !weights_i32) return MBN_EINVAL;
     if (((uintptr_t)first_i32 | (uintptr_t)count_i32 | (uintptr_t)weights_i32) % 4) return MBN_EINVAL;
-    const int ksize = mbn_resize_ksize(in_size, b0, b1, out_size);
+    const int ksize = mbn_resize_ksize_filter(filter, in_size, b0, b1, out_size);
     if (ksize == MBN_EINVAL) return MBN_EINVAL;
+    if (filter == MBN_FILTER_HAMMING || filter == MBN_FILTER_LANCZOS) return MBN_EUNSUPPORTED;       // no device form of their weights (mbn.h)
     if (ksize < 0 || ksize > MBN_RESIZE_MAX_KSIZE || in_size > MBN_RESIZE_MAX_IN || out_size > MBN_RESIZE_MAX_OUT) return MBN_EUNSUPPORTED;
     MBN_SPANS(ctx, { first_i32, 4.0 * out_size, "resize_taps_device first" }, { count_i32, 4.0 * out_size, "resize_taps_device count" },
               { weights_i32, 4.0 * out_size * ksize, "resize_taps_device weights" });
     Scope sc(ctx, ctx->stream);
-    const int rc = sc.finish(mbn_launch_resize_taps(ctx->stream, in_size, b0, b1, out_size, ksize, (int32_t *)first_i32, (int32_t *)count_i32,
+    const int rc = sc.finish(mbn_launch_resize_taps(ctx->stream, filter, in_size, b0, b1, out_size, ksize, (int32_t *)first_i32, (int32_t *)count_i32,
                                                     (int32_t *)weights_i32));
     return rc == MBN_OK ? ksize : rc;
 }

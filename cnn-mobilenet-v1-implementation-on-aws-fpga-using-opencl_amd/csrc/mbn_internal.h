@@ -25,6 +25,7 @@ struct mbn_emul_img {
 struct mbn_resizer {
     mbn_context *ctx = nullptr;
     int in_rows = 0, in_cols = 0, out_rows = 0, out_cols = 0;
+    int filter = MBN_FILTER_BILINEAR;            // MBN_FILTER_*: NEAREST runs the gather kernel on ix [out_cols], iy [out_rows] in `tables`
     mbn_resize_plan_t plan = {};                 // mbn_resize_table_plan; kx, ky = taps per output column / row (the tables' row length)
     void *tables = nullptr;                      // device: fx, cx [out_cols], fy, cy [out_rows], wx [out_cols][kx], wy [out_rows][ky], int32
 };
@@ -33,6 +34,7 @@ struct mbn_resizer {
 struct mbn_ragged_resizer {
     mbn_context *ctx = nullptr;
     int max_batch = 0, out_rows = 0, out_cols = 0, tow = 0, tiles_x = 0;
+    int filter = MBN_FILTER_BILINEAR;            // MBN_FILTER_NEAREST, _BOX, _BILINEAR or _BICUBIC: which kernel instantiation a launch takes
     int batch = 0;                               // of the last successful set; 0 = none
     int total_wgs = 0, lds_bytes = 0;            // its launch
     int generation = 0;                          // counts the sets: a captured launch replayed after another set does nothing
@@ -271,16 +273,16 @@ void mbn_ragged_readout_release(mbn_ragged_readout *r);
 int mbn_ragged_readout_plan(mbn_ragged_readout *r, hipStream_t s, int rows, int cols, int classes, const mbn_label_item *items, int batch);
 int mbn_launch_f32_resample_argmax_ragged(mbn_ragged_readout *r, hipStream_t s, int32_t *labels, float *score, const float *logits);
 // resize front-end (mbn_u8_resize.hip): the geometry is inside mbn_resize_envelope; build uploads the tables (blocking), release frees them
-int mbn_resizer_build(mbn_context *ctx, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r);
+int mbn_resizer_build(mbn_context *ctx, int filter, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r);
 void mbn_resizer_release(mbn_resizer *r);
 int mbn_launch_u8_resize(const mbn_resizer *r, hipStream_t s, uint8_t *out, const uint8_t *in, int batch);
 // ragged resize (mbn_u8_resize_ragged.hip): build allocates, plan checks and plans a batch and enqueues the descriptors' upload (waits for the handle's
 // earlier work first), the launch is asynchronous; taps: the kernel's tap function for one axis into device tables
-int mbn_ragged_resizer_build(mbn_context *ctx, int max_batch, int out_rows, int out_cols, mbn_ragged_resizer **r);
+int mbn_ragged_resizer_build(mbn_context *ctx, int filter, int max_batch, int out_rows, int out_cols, mbn_ragged_resizer **r);
 void mbn_ragged_resizer_release(mbn_ragged_resizer *r);
 int mbn_ragged_resizer_plan(mbn_ragged_resizer *r, hipStream_t s, const mbn_resize_item *items, int batch);
 int mbn_launch_u8_resize_ragged(mbn_ragged_resizer *r, hipStream_t s, uint8_t *out, const uint8_t *src);
-int mbn_launch_resize_taps(hipStream_t s, int in_size, float b0, float b1, int out_size, int ksize, int32_t *first, int32_t *count, int32_t *weights);
+int mbn_launch_resize_taps(hipStream_t s, int filter, int in_size, float b0, float b1, int out_size, int ksize, int32_t *first, int32_t *count, int32_t *weights);
 int mbn_launch_normalize(mbn_context *ctx, hipStream_t s, float *out, const uint8_t *in, size_t count, float scale,
                          float bias);
 

@@ -1,6 +1,8 @@
 // mbn_u8_resize.h — the tile body of the resize front-end on gfx950, shared by the table kernel (mbn_u8_resize.hip) and the ragged kernel
-// (mbn_u8_resize_ragged.hip): Pillow's 8-bit bilinear resize of a box of a uint8 HWC image, both passes in ONE launch (include/mbn.h, "resize
+// (mbn_u8_resize_ragged.hip): Pillow's 8-bit resize of a box of a uint8 HWC image, both passes in ONE launch (include/mbn.h, "resize
 // front-end", is the normative statement of the arithmetic). Each kernel brings its own geometry and its own source of first / count / weights.
+// The filter is in the weights alone (bilinear, box, hamming, bicubic, lanczos): nothing here assumes a weight >= 0 or a row of them summing to
+// 2^22, and both passes clamp. MBN_FILTER_NEAREST has no weights and its own body at the end of this file (resize_nearest_rows).
 //
 // A workgroup of 256 lanes (MBN_RESIZE_WAVES waves) owns a tile of `toh` output rows x `tow` output columns of one image. The taps say which source
 // rows [y0, y1) and columns [xs0, xs1) the tile needs, and nothing else is read:
@@ -110,6 +112,30 @@ __device__ __forceinline__ void resize_vertical(uint8_t *__restrict__ dst, size_
 #pragma unroll
         for (int j = 0; j < RESIZE_EPL; j++)
             if (lane + 64 * j < row_e) d[lane + 64 * j] = resize_round(acc[j]);
+    }
+}
+
+// MBN_FILTER_NEAREST, the rows of a tile: a gather of 3-byte pixels and nothing else. Wave v takes output rows v, v + 4, ... of the tile's oyn; a row's
+// segment is row_e consecutive bytes at dst + oy * dst_ld, byte e of it channel e % 3 of the source pixel (iy(oy), ix(e / 3)) of src [..][w][3]
+// (ix, iy: the tile's indices, already inside the source). Stored as resize_stage_row loads: bytewise up to the first 4-byte boundary of the
+// ADDRESS, a dword per lane from there (consecutive lanes, consecutive dwords), bytewise for the rest, so any byte pointer and any ow * 3 write
+// the same bytes and none beside them
+template <class Ix, class Iy>
+__device__ __forceinline__ void resize_nearest_rows(uint8_t *__restrict__ dst, size_t dst_ld, const uint8_t *__restrict__ src, int w, int oyn, int row_e,
+                                                    int lane, int wave, Ix ix, Iy iy)
+{
+    for (int oy = wave; oy < oyn; oy += MBN_RESIZE_WAVES) {
+        uint8_t *d = dst + oy * dst_ld;
+        const uint8_t *row = src + (size_t)iy(oy) * w * 3;
+        auto byte = [&](int e) -> uint32_t { const int p = e / 3; return row[ix(p) * 3 + (e - 3 * p)]; };
+        const int off = (int)((uintptr_t)d & 3);
+        const int head = min(row_e, (4 - off) & 3), body = (row_e - head) >> 2, tail0 = head + 4 * body;
+        if (lane < head) d[lane] = (uint8_t)byte(lane);
+        for (int i = lane; i < body; i += 64) {
+            const int e = head + 4 * i;
+            *reinterpret_cast<uint32_t *>(d + e) = byte(e) | byte(e + 1) << 8 | byte(e + 2) << 16 | byte(e + 3) << 24;
+        }
+        if (tail0 + lane < row_e) d[tail0 + lane] = (uint8_t)byte(tail0 + lane);
     }
 }
 

@@ -1,5 +1,6 @@
-// mbn_u8_resize.hip — the table kernel of the resize front-end: `batch` uint8 HWC images of ONE geometry, whose tap tables the host built
-// (host/mbn_resize.c, mbn_resize_taps) and the handle keeps in device memory. The tile body is mbn_u8_resize.h's and the tile plan
+// mbn_u8_resize.hip — the table kernels of the resize front-end: `batch` uint8 HWC images of ONE geometry, whose tap tables the host built
+// (host/mbn_resize.c, mbn_resize_taps_filter: one kernel for the five convolution filters, which differ in their tables alone) and the handle keeps
+// in device memory; MBN_FILTER_NEAREST has no taps and a gather kernel of its own (resize_nearest_u8, below). The tile body is mbn_u8_resize.h's and the tile plan
 // mbn_resize_table_plan's (host/mbn_resize.c); what is this file's own: the tables' addressing, their validation, and the handle.
 // The reference has no counterpart: decode_image (MobileNet.c:49-57) reads 224*224*3 raw bytes and nothing resizes them.
 //
@@ -55,6 +56,33 @@ __global__ __launch_bounds__(256, 8) void resize_u8(const ResizeArgs a)
     });
 }
 
+// MBN_FILTER_NEAREST: no taps, the uploaded indices ix [ow], iy [oh]. A workgroup takes MBN_RESIZE_WAVES whole output rows of one image, a wave a row
+// (resize_nearest_rows: tow = ow). index_ok has checked the indices at create time; they are clamped here anyway, for memory safety only
+struct NearestArgs {
+    uint8_t *out;
+    const uint8_t *in;
+    const int32_t *ix, *iy;
+    int h, w, oh, ow;
+};
+
+__global__ __launch_bounds__(256) void resize_nearest_u8(const NearestArgs a)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int oy0 = (int)blockIdx.x * MBN_RESIZE_WAVES, oyn = min(MBN_RESIZE_WAVES, a.oh - oy0);
+    const size_t img = (size_t)blockIdx.y;
+    const uint8_t *__restrict__ src = a.in + img * ((size_t)a.h * a.w * 3);
+    uint8_t *__restrict__ dst = a.out + img * ((size_t)a.oh * a.ow * 3);
+    resize_nearest_rows(dst + (size_t)oy0 * a.ow * 3, (size_t)a.ow * 3, src, a.w, oyn, a.ow * 3, lane, wave,
+                        [&](int ox) { return min(max(a.ix[ox], 0), a.w - 1); }, [&](int oy) { return min(max(a.iy[oy0 + oy], 0), a.h - 1); });
+}
+
+bool index_ok(const int32_t *index, int out_size, int in_size)
+{
+    for (int i = 0; i < out_size; i++)
+        if (index[i] < 0 || index[i] >= in_size || (i && index[i] < index[i - 1])) return false;
+    return true;
+}
+
 // an axis's tables are what the kernel's bounds rest on: every tap inside the source, first and first + count growing with the index
 bool axis_ok(const int32_t *first, const int32_t *count, int out_size, int in_size, int ksize)
 {
@@ -68,26 +96,37 @@ bool axis_ok(const int32_t *first, const int32_t *count, int out_size, int in_si
 }   // namespace
 
 // The geometry is inside mbn_resize_envelope (the caller has checked it). Plans the tile, builds the tables and uploads them: blocking.
-int mbn_resizer_build(mbn_context *ctx, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **out)
+int mbn_resizer_build(mbn_context *ctx, int filter, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **out)
 {
     const float whole[4] = { 0.0f, 0.0f, (float)in_cols, (float)in_rows };
     const float *b = box ? box : whole;
     mbn_resize_plan_t p;
-    int rc = mbn_resize_table_plan(in_rows, in_cols, b, out_rows, out_cols, &p);
+    int rc = mbn_resize_table_plan_filter(filter, in_rows, in_cols, b, out_rows, out_cols, &p);
     if (rc != MBN_OK) return rc;
-    // one host block, the layout of the device block: fx, cx, fy, cy, wx, wy
-    const size_t n32 = 2 * (size_t)out_cols + 2 * (size_t)out_rows + (size_t)out_cols * p.kx + (size_t)out_rows * p.ky;
+    // one host block, the layout of the device block: fx, cx, fy, cy, wx, wy; NEAREST: ix, iy
+    const bool nearest = filter == MBN_FILTER_NEAREST;
+    const size_t n32 = nearest ? (size_t)out_cols + (size_t)out_rows
+                               : 2 * (size_t)out_cols + 2 * (size_t)out_rows + (size_t)out_cols * p.kx + (size_t)out_rows * p.ky;
     std::vector<int32_t> tab;
     try { tab.resize(n32); } catch (const std::bad_alloc &) { return MBN_ENOMEM; }
-    int32_t *fx = tab.data(), *cx = fx + out_cols, *fy = cx + out_cols, *cy = fy + out_rows, *wx = cy + out_rows, *wy = wx + (size_t)out_cols * p.kx;
-    rc = mbn_resize_taps(in_cols, b[0], b[2], out_cols, fx, cx, wx);
-    if (rc >= 0) rc = mbn_resize_taps(in_rows, b[1], b[3], out_rows, fy, cy, wy);
-    if (rc < 0) return rc;
-    if (!axis_ok(fx, cx, out_cols, in_cols, p.kx) || !axis_ok(fy, cy, out_rows, in_rows, p.ky)) return MBN_EINVAL;
+    if (nearest) {
+        int32_t *ix = tab.data(), *iy = ix + out_cols;
+        rc = mbn_resize_nearest_index(in_cols, b[0], b[2], out_cols, ix);
+        if (rc == MBN_OK) rc = mbn_resize_nearest_index(in_rows, b[1], b[3], out_rows, iy);
+        if (rc != MBN_OK) return rc;
+        if (!index_ok(ix, out_cols, in_cols) || !index_ok(iy, out_rows, in_rows)) return MBN_EINVAL;
+    } else {
+        int32_t *fx = tab.data(), *cx = fx + out_cols, *fy = cx + out_cols, *cy = fy + out_rows, *wx = cy + out_rows, *wy = wx + (size_t)out_cols * p.kx;
+        rc = mbn_resize_taps_filter(filter, in_cols, b[0], b[2], out_cols, fx, cx, wx);
+        if (rc >= 0) rc = mbn_resize_taps_filter(filter, in_rows, b[1], b[3], out_rows, fy, cy, wy);
+        if (rc < 0) return rc;
+        if (!axis_ok(fx, cx, out_cols, in_cols, p.kx) || !axis_ok(fy, cy, out_rows, in_rows, p.ky)) return MBN_EINVAL;
+    }
 
     mbn_resizer *r = new (std::nothrow) mbn_resizer();
     if (!r) return MBN_ENOMEM;
     r->ctx = ctx;
+    r->filter = filter;
     r->in_rows = in_rows; r->in_cols = in_cols; r->out_rows = out_rows; r->out_cols = out_cols;
     r->plan = p;
     (void)hipSetDevice(ctx->device);
@@ -112,9 +151,17 @@ void mbn_resizer_release(mbn_resizer *r)
 int mbn_launch_u8_resize(const mbn_resizer *r, hipStream_t s, uint8_t *out, const uint8_t *in, int batch)
 {
     const mbn_resize_plan_t &p = r->plan;
+    const int32_t *t = (const int32_t *)r->tables;
+    if (r->filter == MBN_FILTER_NEAREST) {
+        NearestArgs n;
+        n.out = out; n.in = in;
+        n.ix = t; n.iy = t + r->out_cols;
+        n.h = r->in_rows; n.w = r->in_cols; n.oh = r->out_rows; n.ow = r->out_cols;
+        hipLaunchKernelGGL(resize_nearest_u8, dim3((unsigned)((r->out_rows + MBN_RESIZE_WAVES - 1) / MBN_RESIZE_WAVES), (unsigned)batch), dim3(256), 0, s, n);
+        return MBN_OK;
+    }
     ResizeArgs a;
     a.out = out; a.in = in;
-    const int32_t *t = (const int32_t *)r->tables;
     a.fx = t; a.cx = a.fx + r->out_cols; a.fy = a.cx + r->out_cols; a.cy = a.fy + r->out_rows;
     a.wx = a.cy + r->out_rows; a.wy = a.wx + (size_t)r->out_cols * p.kx;
     a.h = r->in_rows; a.w = r->in_cols; a.oh = r->out_rows; a.ow = r->out_cols; a.kx = p.kx; a.ky = p.ky;

@@ -4,6 +4,9 @@
 //   taps        no table exists anywhere. The workgroup forms its tile's taps itself, straight into LDS: lane c of wave 0 runs output column c of the
 //               tile, lane r of wave 1 output row r, each its <= 67 taps one after the other (mbn_axis_taps of host/mbn_resize_axis.h: the host's own
 //               expressions, in fp64 with contraction off). The vertical weights, first rows and counts sit in LDS as well;
+//   filters     the handle's: MBN_FILTER_BOX, _BILINEAR and _BICUBIC are instantiations of one kernel (plain fp64 arithmetic, the reciprocal 1.0 / fs
+//               a true division: the host's bits), MBN_FILTER_NEAREST is a gather kernel of its own. HAMMING and LANCZOS have no device form: their
+//               weights need sin / cos bit-equal to the host's libm, which device math does not promise (the plan answers MBN_EUNSUPPORTED);
 //   geometry    per image, from a 64-byte descriptor in device memory (mbn_resize_desc, host/mbn_envelope.h): the caller's item and what the host
 //               planned without a table (host/mbn_resize.c, mbn_resize_ragged_plan): ksize per axis, the tile height, the staged row's stride, the
 //               window's LDS offset, and the image's first workgroup;
@@ -38,14 +41,9 @@ struct RaggedArgs {
     int generation;          // of the set this launch was issued (or captured) for
 };
 
-__global__ __launch_bounds__(256, 8) void resize_ragged_u8(const RaggedArgs a)
+// the image of workgroup wg: the last one whose first workgroup is <= wg, among [base, base + n). desc[base].wg0 <= wg holds throughout (desc[0].wg0 = 0)
+__device__ __forceinline__ const mbn_resize_desc &ragged_image(const RaggedArgs &a, int wg, int lane)
 {
-    extern __shared__ __attribute__((aligned(16))) uint8_t s_mem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wg = (int)blockIdx.x;
-    // a replay of a captured launch after another set: the descriptors are no longer the ones its grid, LDS and spans were checked for
-    if (a.head->generation != a.generation || wg >= a.head->total_wgs) return;
-    // ---- the image: the last one whose first workgroup is <= wg, among [base, base + n). desc[base].wg0 <= wg holds throughout (desc[0].wg0 = 0)
     int base = 0, n = a.head->batch;
     while (n > 1) {
         const int stride = (n + 63) >> 6;
@@ -54,13 +52,26 @@ __global__ __launch_bounds__(256, 8) void resize_ragged_u8(const RaggedArgs a)
         base += step;
         n = min(stride, n - step);
     }
-    const mbn_resize_desc &d = a.desc[__builtin_amdgcn_readfirstlane(base)];
+    return a.desc[__builtin_amdgcn_readfirstlane(base)];
+}
+
+// FILTER = MBN_FILTER_BOX, _BILINEAR or _BICUBIC: a template argument, so the weight function's dispatch (mbn_axis_weight) is decided when the kernel is
+// compiled and the tap loops carry no branch on it
+template <int FILTER>
+__global__ __launch_bounds__(256, 8) void resize_ragged_u8(const RaggedArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t s_mem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wg = (int)blockIdx.x;
+    // a replay of a captured launch after another set: the descriptors are no longer the ones its grid, LDS and spans were checked for
+    if (a.head->generation != a.generation || wg >= a.head->total_wgs) return;
+    const mbn_resize_desc &d = ragged_image(a, wg, lane);
     const int kx = d.kx, ky = d.ky, toh = d.toh, tow = a.tow;
     const int tile = wg - d.wg0, ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
     if (tile < 0 || ty >= d.tiles_y) return;
     const int ox0 = tx * tow, oxn = min(tow, a.ow - ox0), oy0 = ty * toh, oyn = min(toh, a.oh - oy0);
     const int row_e = oxn * 3;                                   // horizontal sums of a source row
-    const mbn_axis gx = mbn_axis_of(d.cols, d.box[0], d.box[2], a.ow), gy = mbn_axis_of(d.rows, d.box[1], d.box[3], a.oh);
+    const mbn_axis gx = mbn_axis_of_filter(FILTER, d.cols, d.box[0], d.box[2], a.ow), gy = mbn_axis_of_filter(FILTER, d.rows, d.box[1], d.box[3], a.oh);
     int xs0, xs1, y0, y1, unused;
     (void)mbn_axis_span(&gx, ox0, &xs0, &unused);
     (void)mbn_axis_span(&gx, ox0 + oxn - 1, &unused, &xs1);
@@ -102,22 +113,63 @@ __global__ __launch_bounds__(256, 8) void resize_ragged_u8(const RaggedArgs a)
     });
 }
 
-// mbn_resize_taps_device: the tables of one axis from mbn_axis_taps, an output per lane
+// MBN_FILTER_NEAREST: the same grid, descriptors and mapping; a tile is a gather (resize_nearest_rows of mbn_u8_resize.h). Its LDS image is the tile's
+// indices alone, ix [tow] then iy [toh]: lane c of wave 0 forms column ox0 + c, lane r of wave 1 row oy0 + r, each with its OWN chain of ox0 + c
+// (oy0 + r) dependent fp64 additions from xo_0 (mbn_axis_nearest_index: at most 4095, 223 for this network's outputs). The index is defined by that
+// accumulated sum, additions do not associate, and the closed form b0 + a * (i + 0.5) gives other indices: no cheaper form gives the same bits
+__global__ __launch_bounds__(256) void resize_ragged_nearest_u8(const RaggedArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t s_mem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wg = (int)blockIdx.x;
+    if (a.head->generation != a.generation || wg >= a.head->total_wgs) return;
+    const mbn_resize_desc &d = ragged_image(a, wg, lane);
+    const int tow = a.tow, toh = min(d.toh, a.lds_bytes / 4 - tow);      // what the launch's LDS has room for: the plan's toh, so the clamp does not bind
+    const int tile = wg - d.wg0, ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+    if (tile < 0 || ty >= d.tiles_y || toh < 1) return;
+    const int ox0 = tx * tow, oxn = min(tow, a.ow - ox0), oy0 = ty * toh, oyn = min(toh, a.oh - oy0);
+    int32_t *s_ix = reinterpret_cast<int32_t *>(s_mem), *s_iy = s_ix + tow;
+    if (tid < oxn) {
+        const mbn_axis gx = mbn_axis_of_filter(MBN_FILTER_NEAREST, d.cols, d.box[0], d.box[2], a.ow);
+        s_ix[tid] = mbn_axis_nearest_index(&gx, ox0 + tid);
+    } else if (tid >= 64 && tid - 64 < oyn) {
+        const mbn_axis gy = mbn_axis_of_filter(MBN_FILTER_NEAREST, d.rows, d.box[1], d.box[3], a.oh);
+        s_iy[tid - 64] = mbn_axis_nearest_index(&gy, oy0 + tid - 64);
+    }
+    __syncthreads();                                             // the indices are in place
+    const size_t img = (size_t)(&d - a.desc);
+    const uint8_t *__restrict__ src = a.src + d.src_offset;
+    uint8_t *__restrict__ dst = a.out + img * ((size_t)a.oh * a.ow * 3);
+    resize_nearest_rows(dst + ((size_t)oy0 * a.ow + ox0) * 3, (size_t)a.ow * 3, src, d.cols, oyn, oxn * 3, lane, wave,
+                        [&](int ox) { return s_ix[ox]; }, [&](int oy) { return s_iy[oy]; });
+}
+
+// mbn_resize_taps_device_filter: the tables of one axis from mbn_axis_taps, an output per lane. NEAREST: first = the index (the lane's own chain of
+// additions, as in the kernel above), one tap, the whole weight
+template <int FILTER>
 __global__ __launch_bounds__(64) void resize_taps_k(int in_size, float b0, float b1, int out_size, int ksize, int32_t *first, int32_t *count, int32_t *weights)
 {
     const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
     if (i >= out_size) return;
-    const mbn_axis a = mbn_axis_of(in_size, b0, b1, out_size);
-    count[i] = mbn_axis_taps(&a, i, ksize, weights + (size_t)i * ksize, &first[i]);
+    const mbn_axis a = mbn_axis_of_filter(FILTER, in_size, b0, b1, out_size);
+    if (FILTER == MBN_FILTER_NEAREST) {
+        first[i] = mbn_axis_nearest_index(&a, i);
+        count[i] = 1;
+        weights[i] = 1 << MBN_RESIZE_BITS;
+    } else {
+        count[i] = mbn_axis_taps(&a, i, ksize, weights + (size_t)i * ksize, &first[i]);
+    }
 }
 
 }   // namespace
 
-int mbn_ragged_resizer_build(mbn_context *ctx, int max_batch, int out_rows, int out_cols, mbn_ragged_resizer **out)
+// filter: MBN_FILTER_NEAREST, _BOX, _BILINEAR or _BICUBIC (the caller has checked)
+int mbn_ragged_resizer_build(mbn_context *ctx, int filter, int max_batch, int out_rows, int out_cols, mbn_ragged_resizer **out)
 {
     mbn_ragged_resizer *r = new (std::nothrow) mbn_ragged_resizer();
     if (!r) return MBN_ENOMEM;
     r->ctx = ctx;
+    r->filter = filter;
     r->max_batch = max_batch; r->out_rows = out_rows; r->out_cols = out_cols;
     r->tow = MBN_RESIZE_TOW(out_cols);
     r->tiles_x = (out_cols + r->tow - 1) / r->tow;
@@ -154,7 +206,7 @@ int mbn_ragged_resizer_plan(mbn_ragged_resizer *r, hipStream_t s, const mbn_resi
     mbn_resize_desc *desc = (mbn_resize_desc *)(h + 1);
     int32_t total = 0, lds = 0;
     int64_t span = 0;
-    const int rc = mbn_resize_ragged_plan_batch(items, batch, r->out_rows, r->out_cols, desc, &total, &lds, &span);
+    const int rc = mbn_resize_ragged_plan_batch_filter(r->filter, items, batch, r->out_rows, r->out_cols, desc, &total, &lds, &span);
     if (rc != MBN_OK) return rc;
     memset(h, 0, sizeof *h);
     h->batch = batch; h->total_wgs = total; h->lds_bytes = lds; h->generation = r->generation + 1;
@@ -175,7 +227,15 @@ int mbn_launch_u8_resize_ragged(mbn_ragged_resizer *r, hipStream_t s, uint8_t *o
     a.desc = (const mbn_resize_desc *)(a.head + 1);
     a.oh = r->out_rows; a.ow = r->out_cols; a.tow = r->tow; a.tiles_x = r->tiles_x;
     a.lds_bytes = r->lds_bytes; a.generation = r->generation;
-    hipLaunchKernelGGL(resize_ragged_u8, dim3((unsigned)r->total_wgs), dim3(256), (size_t)r->lds_bytes, s, a);
+    const dim3 grid((unsigned)r->total_wgs), block(256);
+    const size_t lds = (size_t)r->lds_bytes;
+    switch (r->filter) {
+    case MBN_FILTER_NEAREST: hipLaunchKernelGGL(resize_ragged_nearest_u8, grid, block, lds, s, a); break;
+    case MBN_FILTER_BOX: hipLaunchKernelGGL(resize_ragged_u8<MBN_FILTER_BOX>, grid, block, lds, s, a); break;
+    case MBN_FILTER_BILINEAR: hipLaunchKernelGGL(resize_ragged_u8<MBN_FILTER_BILINEAR>, grid, block, lds, s, a); break;
+    case MBN_FILTER_BICUBIC: hipLaunchKernelGGL(resize_ragged_u8<MBN_FILTER_BICUBIC>, grid, block, lds, s, a); break;
+    default: return MBN_EUNSUPPORTED;                            // no handle has another filter
+    }
     // the next set waits for this launch; inside a capture there is nothing to wait for (the replays are the caller's to order)
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) (void)hipEventRecord(r->done, s);
@@ -183,8 +243,15 @@ int mbn_launch_u8_resize_ragged(mbn_ragged_resizer *r, hipStream_t s, uint8_t *o
 }
 
 // the geometry is inside the device's envelope and ksize is the axis's (the caller has checked)
-int mbn_launch_resize_taps(hipStream_t s, int in_size, float b0, float b1, int out_size, int ksize, int32_t *first, int32_t *count, int32_t *weights)
+int mbn_launch_resize_taps(hipStream_t s, int filter, int in_size, float b0, float b1, int out_size, int ksize, int32_t *first, int32_t *count, int32_t *weights)
 {
-    hipLaunchKernelGGL(resize_taps_k, dim3((unsigned)((out_size + 63) / 64)), dim3(64), 0, s, in_size, b0, b1, out_size, ksize, first, count, weights);
+    const dim3 grid((unsigned)((out_size + 63) / 64)), block(64);
+    switch (filter) {
+    case MBN_FILTER_NEAREST: hipLaunchKernelGGL(resize_taps_k<MBN_FILTER_NEAREST>, grid, block, 0, s, in_size, b0, b1, out_size, ksize, first, count, weights); break;
+    case MBN_FILTER_BOX: hipLaunchKernelGGL(resize_taps_k<MBN_FILTER_BOX>, grid, block, 0, s, in_size, b0, b1, out_size, ksize, first, count, weights); break;
+    case MBN_FILTER_BILINEAR: hipLaunchKernelGGL(resize_taps_k<MBN_FILTER_BILINEAR>, grid, block, 0, s, in_size, b0, b1, out_size, ksize, first, count, weights); break;
+    case MBN_FILTER_BICUBIC: hipLaunchKernelGGL(resize_taps_k<MBN_FILTER_BICUBIC>, grid, block, 0, s, in_size, b0, b1, out_size, ksize, first, count, weights); break;
+    default: return MBN_EUNSUPPORTED;
+    }
     return MBN_OK;
 }

@@ -137,6 +137,19 @@ int mbn_resize_ragged_plan(const mbn_resize_item *item, int out_rows, int out_co
  * max(src_offset + rows * cols * 3). The first refused item's status is returned */
 int mbn_resize_ragged_plan_batch(const mbn_resize_item *items, int batch, int out_rows, int out_cols, mbn_resize_desc *desc, int32_t *total_wgs,
                                  int32_t *lds_bytes, int64_t *src_span);
+/* The same under a filter (MBN_FILTER_*, include/mbn.h; any other value: MBN_EINVAL): every function above is the MBN_FILTER_BILINEAR call of its
+ * sibling here. The limits do not change with the filter; what changes is how soon they bind: support = S * fs widens the windows (S = 0.5 box,
+ * 2 bicubic, 3 lanczos), so ksize <= 67 ends lanczos at 11x and bicubic at 16.5x, and box, whose 67 taps span 66 source positions, is ended by the
+ * one-row tile that must fit MBN_RESIZE_LDS (the plan's MBN_EUNSUPPORTED). MBN_FILTER_NEAREST is a gather: ksize 1, a window is [index[o_first],
+ * index[o_last] + 1), a table plan needs no LDS (kx = ky = 1, toh = min(out_rows, MBN_RESIZE_TOH), the offsets 0) and a ragged plan the tile's
+ * tow + toh int32 indices. The ragged plans answer MBN_EUNSUPPORTED for MBN_FILTER_HAMMING and MBN_FILTER_LANCZOS (no device form of sin / cos
+ * gives the host's bits) */
+int mbn_resize_envelope_filter(int filter, int in_rows, int in_cols, const float *box, int out_rows, int out_cols);
+int mbn_resize_table_plan_filter(int filter, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resize_plan_t *plan);
+int mbn_resize_window_filter(int filter, int in_size, float b0, float b1, int out_size, int o_first, int o_last, int32_t *lo, int32_t *hi);
+int mbn_resize_ragged_plan_filter(int filter, const mbn_resize_item *item, int out_rows, int out_cols, mbn_resize_desc *d);
+int mbn_resize_ragged_plan_batch_filter(int filter, const mbn_resize_item *items, int batch, int out_rows, int out_cols, mbn_resize_desc *desc,
+                                        int32_t *total_wgs, int32_t *lds_bytes, int64_t *src_span);
 
 /* int8 pointwise / FC (mbn_i8.hip): the whole launch arithmetic of mbn_launch_i8_pointwise, which launches what this says and
  * computes nothing of its own. Two forms: the persistent one (i8_pw2_k<ks, 512, out_f32>: a wave keeps a 32-column chunk's filter

@@ -50,8 +50,10 @@ struct mbn_net {
     void *dense_feat;          /* mbn_net_forward_dense: the activation in front of the pool, [max_batch][h][w][channels] at fp32 size */
     void *dense_logits;        /* mbn_net_segment: [max_batch][h][w][classes] fp32 */
     mbn_resizer *resizer;      /* mbn_net_resize_input: the resizer of the geometry below, rebuilt when it changes */
-    int rs_rows, rs_cols, rs_fit;
+    int rs_rows, rs_cols, rs_fit, rs_filter;
     float rs_fraction;
+    int resize_filter;         /* mbn_net_set_resize_filter: MBN_FILTER_* of both resizers (MBN_FILTER_BILINEAR until it is called) */
+    int ragged_filter;         /* the filter `ragged` was made for */
     void *resize_buf;          /* mbn_net_resize_input / _inputs: [max_batch][rows][cols][3] uint8, the resized images */
     mbn_ragged_resizer *ragged;     /* mbn_net_resize_inputs: one ragged resizer of max_batch images, made on the first call */
     mbn_resize_item *ragged_items;  /* ... and the items it is set from, [max_batch] */
@@ -86,6 +88,7 @@ static int net_alloc_common(mbn_context *ctx, const mbn_plan *plan, int max_batc
     net->nstreams = 1;
     net->fuse_stem = 1;
     net->fuse_blocks = MBN_FUSE_BLOCKS_DEFAULT;
+    net->resize_filter = MBN_FILTER_BILINEAR;
     net->plan = *plan;
     net->max_batch = max_batch;
     net->num_cus = 256;
@@ -956,21 +959,36 @@ int mbn_net_segment_images(mbn_net *net, const void *src_u8, const int64_t *offs
     return mbn_resample_argmax_ragged_f32(net->readout, labels_i32, score_f32, net->dense_logits, NULL);
 }
 
+int mbn_net_set_resize_filter(mbn_net *net, int filter)
+{
+    if (!net || filter < MBN_FILTER_NEAREST || filter > MBN_FILTER_HAMMING) return MBN_EINVAL;
+    net->resize_filter = filter;                              /* the kept resizers are rebuilt by the next call that finds another filter in them */
+    return MBN_OK;
+}
+
+int mbn_net_get_resize_filter(const mbn_net *net, int *filter)
+{
+    if (!net || !filter) return MBN_EINVAL;
+    *filter = net->resize_filter;
+    return MBN_OK;
+}
+
 int mbn_net_resize_input(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, float crop_fraction, void **images_u8)
 {
     if (!net || !src_u8 || !images_u8 || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
     *images_u8 = NULL;
     const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols;
     if (fit == MBN_FIT_STRETCH) crop_fraction = 1.0f;
-    if (!net->resizer || net->rs_rows != in_rows || net->rs_cols != in_cols || net->rs_fit != fit || net->rs_fraction != crop_fraction) {
+    if (!net->resizer || net->rs_rows != in_rows || net->rs_cols != in_cols || net->rs_fit != fit || net->rs_fraction != crop_fraction ||
+        net->rs_filter != net->resize_filter) {
         float box[4];
         mbn_resizer *r = NULL;
         int rc = mbn_fit_box(in_rows, in_cols, rows, cols, fit, crop_fraction, box);
-        if (rc == MBN_OK) rc = mbn_resizer_create(net->ctx, in_rows, in_cols, box, rows, cols, &r);
+        if (rc == MBN_OK) rc = mbn_resizer_create_filter(net->ctx, net->resize_filter, in_rows, in_cols, box, rows, cols, &r);
         if (rc != MBN_OK) return rc;                          /* the resizer of the previous geometry stays */
         if (net->resizer) mbn_resizer_destroy(net->resizer);  /* waits for the stream: a resize still running reads its tables */
         net->resizer = r;
-        net->rs_rows = in_rows; net->rs_cols = in_cols; net->rs_fit = fit; net->rs_fraction = crop_fraction;
+        net->rs_rows = in_rows; net->rs_cols = in_cols; net->rs_fit = fit; net->rs_fraction = crop_fraction; net->rs_filter = net->resize_filter;
     }
     if (!net->resize_buf) {
         int rc = mbn_alloc(net->ctx, (size_t)net->max_batch * rows * cols * 3, &net->resize_buf);
@@ -1000,9 +1018,13 @@ int mbn_net_resize_inputs(mbn_net *net, const void *src_u8, const int64_t *offse
         const int rc = mbn_fit_box(in_rows[i], in_cols[i], rows, cols, fit, crop_fraction, it->box);
         if (rc != MBN_OK) return rc;
     }
-    if (!net->ragged) {
-        const int rc = mbn_ragged_resizer_create(net->ctx, net->max_batch, rows, cols, &net->ragged);
-        if (rc != MBN_OK) { net->ragged = NULL; return rc; }
+    if (!net->ragged || net->ragged_filter != net->resize_filter) {
+        mbn_ragged_resizer *r = NULL;                         /* HAMMING / LANCZOS: MBN_EUNSUPPORTED, and the resizer of the previous filter stays */
+        const int rc = mbn_ragged_resizer_create_filter(net->ctx, net->resize_filter, net->max_batch, rows, cols, &r);
+        if (rc != MBN_OK) return rc;
+        if (net->ragged) mbn_ragged_resizer_destroy(net->ragged);       /* waits for its last launch */
+        net->ragged = r;
+        net->ragged_filter = net->resize_filter;
     }
     if (!net->resize_buf) {
         const int rc = mbn_alloc(net->ctx, (size_t)net->max_batch * rows * cols * 3, &net->resize_buf);

@@ -9,6 +9,8 @@
  *   each is printed; the rest of the batch repeats the first): a P6 image of ANY size up to 8192 x 8192; one that is not cols wide and rows high is resized on the device (mbn_net_resize_input: Pillow's 8-bit
  *   bilinear). --fit crop (default: the centred box with the plan's aspect ratio) | stretch (the whole image); --crop-fraction F in (0, 1] shrinks the crop box
  *   (0.875 = "resize to 256, crop 224"). An image of the plan's size is taken as it is
+ *   --filter nearest | box | bilinear (default) | hamming | bicubic | lanczos: Pillow's filter of that resize (mbn_net_set_resize_filter). Several --ppm
+ *   take the ragged launch, which has no hamming and no lanczos (their weights need the host's sin / cos): usage status 2
  *   --segment FILE: after the classification, the dense head (mbn_net_segment): the label map of image 0 as a binary PGM and its five most frequent labels
  *   --segment-source FILE: the label map of image 0 at that --ppm file's OWN width x height (needs --ppm and --fit stretch, else usage status 2): one --ppm
  *   goes through mbn_net_resize_input + mbn_net_segment_to, several through mbn_net_segment_images (one ragged resize, one ragged read-out)
@@ -430,6 +432,15 @@ static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int
     return bad;
 }
 
+/* --filter NAME: MBN_FILTER_*, or -1 for an unknown name */
+static int filter_of(const char *name)
+{
+    static const char *const names[] = { "nearest", "lanczos", "bilinear", "bicubic", "box", "hamming" };      /* MBN_FILTER_* order */
+    for (int f = 0; f < 6; f++)
+        if (!strcmp(name, names[f])) return f;
+    return -1;
+}
+
 int main(int argc, char **argv)
 {
     if (argc == 3 && !strcmp(argv[1], "--inspect")) return inspect_h5(argv[2]);
@@ -438,7 +449,7 @@ int main(int argc, char **argv)
     int n_ppm = 0;
     if (!ppms) return 1;
     const char *h5 = NULL, *ppm = NULL, *segment = NULL, *segment_src = NULL, *wfile = "weights_c.txt", *image = "Cat_Image0.ppm";
-    int fit = MBN_FIT_CROP;
+    int fit = MBN_FIT_CROP, filter = MBN_FILTER_BILINEAR;
     float crop_fraction = 1.0f;
     int literal = 0, ref_args = 0, batch = 1, rows = 224, cols = 224, have_seed = 0, gpus = 0, steps = 20, warmup = 3, verify = 0, out_stride = 32;
     unsigned long long seed = 0;
@@ -462,6 +473,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--fit") && i + 1 < argc && (!strcmp(argv[i + 1], "crop") || !strcmp(argv[i + 1], "stretch")))
             fit = !strcmp(argv[++i], "crop") ? MBN_FIT_CROP : MBN_FIT_STRETCH;
         else if (!strcmp(argv[i], "--crop-fraction") && i + 1 < argc) crop_fraction = (float)atof(argv[++i]);
+        else if (!strcmp(argv[i], "--filter") && i + 1 < argc && filter_of(argv[i + 1]) >= 0) filter = filter_of(argv[++i]);
         else if (!strcmp(argv[i], "--synthetic") && i + 1 < argc) { seed = strtoull(argv[++i], NULL, 0); have_seed = 1; }
         else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--steps") && i + 1 < argc) steps = atoi(argv[++i]);
@@ -474,13 +486,18 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--literal")) literal = 1;
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
-            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch] [--crop-fraction F]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm] "
+            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch] [--crop-fraction F] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm] "
                             "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n", argv[0]);
             return 2;
         }
     }
     if (!(crop_fraction > 0.f) || !(crop_fraction <= 1.f)) { fprintf(stderr, "bad --crop-fraction (0 < F <= 1)\n"); return 2; }
     if (n_ppm > 1 && n_ppm > batch) { fprintf(stderr, "%d --ppm files need --batch %d at least\n", n_ppm, n_ppm); return 2; }
+    if (n_ppm > 1 && (filter == MBN_FILTER_HAMMING || filter == MBN_FILTER_LANCZOS)) {
+        fprintf(stderr, "--filter %s with several --ppm: the ragged resize forms its weights on the device, which has no sin / cos bit-equal to the host's; "
+                        "use nearest, box, bilinear or bicubic, or one --ppm\n", filter == MBN_FILTER_HAMMING ? "hamming" : "lanczos");
+        return 2;
+    }
     if (n_ppm == 1) ppm = ppms[0];
     if (segment_src && (n_ppm < 1 || fit != MBN_FIT_STRETCH)) { fprintf(stderr, "--segment-source needs --ppm and --fit stretch\n"); return 2; }
     if (out_stride != 0 && out_stride != 8 && out_stride != 16 && out_stride != 32) { fprintf(stderr, "bad --output-stride (32, 16 or 8)\n"); return 2; }
@@ -527,6 +544,7 @@ int main(int argc, char **argv)
     if (have_seed) remove(tmp);
     mbn_net *net = NULL;
     CHECK(mbn_net_create(ctx, &w, batch, &net));
+    CHECK(mbn_net_set_resize_filter(net, filter));
     const int classes = w.plan.classes;
     const size_t img = (size_t)rows * cols * 3;          /* [rows][cols][3]: a P6 image cols wide and rows high */
     size_t img_count = (size_t)batch * img;

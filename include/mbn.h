@@ -480,10 +480,38 @@ int mbn_normalize_u8_to_f32(mbn_context *ctx, void *out_f32, const void *in_u8, 
  * Two passes, each over all three channels: horizontal first, tmp = clamp((2097152 + sum_t src[lo + t] * k_t) >> 22, 0, 255) ROUNDED TO uint8
  * (int32 sums: the weights are >= 0 and sum to about 2^22), then the vertical pass the same way over tmp. An axis that is neither scaled
  * nor cropped has the weights (2^22, 0): the identity.
- *   mbn_resize_ksize   ksize of an axis, or a negative status
+ * The filter. What stands above is MBN_FILTER_BILINEAR, the default everywhere and the only filter of every function without `_filter` in its
+ * name. The `_filter` functions take one of MBN_FILTER_* (Pillow's own Image.Resampling numbers; any other value: MBN_EINVAL), and give BYTE FOR BYTE
+ * what PIL.Image.resize((out_cols, out_rows), filter, box=box) returns (tests/golden/resize_pillow_filters.npz records Pillow 12.2.0's bytes;
+ * tests/resize_filters_ref.py restates the arithmetic in numpy).
+ * Convolution filters (all but NEAREST) run as above with two changes. The support:
+ *     support = S * fs, S = 0.5 (BOX), 1 (BILINEAR, HAMMING), 2 (BICUBIC), 3 (LANCZOS);  ksize = (int)ceil(support) * 2 + 1;  lo, hi with this support
+ * and the weight, w_t = f((t + lo - center + 0.5) * (1.0 / fs)): a multiply by the reciprocal, Pillow's own form (BILINEAR keeps the division it
+ * has above: its tables are pinned as integers). f in double:
+ *     BOX       1 if x > -0.5 && x <= 0.5, else 0
+ *     HAMMING   with x = |x|: 1 at 0, 0 for x >= 1, else with x *= M_PI: sin(x) / x * (0.54 + 0.46 * cos(x))
+ *     BICUBIC   a = -0.5, with x = |x|: ((a + 2) * x - (a + 3)) * x * x + 1 below 1, (((x - 5) * x + 8) * x - 4) * a below 2, else 0
+ *     LANCZOS   sinc(x) * sinc(x / 3) for -3 <= x < 3, else 0; sinc(0) = 1, otherwise sin(x * M_PI) / (x * M_PI)
+ * The sum is taken in order and divides when it is nonzero; k_t = (int)(w_t * 4194304.0 + 0.5) for w_t >= 0 and (int)(w_t * 4194304.0 - 0.5) for
+ * w_t < 0. The two passes are unchanged (an int32 sum from 2^21, >> 22 arithmetic, the clamp to [0, 255], the uint8 intermediate): weights
+ * may be negative and a row of them need not sum to 2^22. An axis that is neither scaled nor cropped has identity weights under every filter.
+ * NEAREST is Pillow's scaled-affine path, no convolution. Per axis
+ *     a = (double)(b1 - b0) / out_size  (the subtraction in float32);  xo = (double)b0 + a * 0.5;  for i = 0 .. out_size - 1: index[i] = (int)xo; xo += a
+ * with the sum ACCUMULATED: the closed form b0 + a * (i + 0.5) gives other indices (4 of 188 columns for 504 -> 188, 6 of 65 for 1222 -> 65).
+ * out[y][x] = src[iy[y]][ix[x]]. For a box inside the image an index never leaves it; it is clamped into the source anyway, for memory safety only.
+ * As an axis table NEAREST is ksize 1: first = index, count = 1, weight 2^22.
+ * The envelope is the same for every filter: source sides <= 8192, output sides <= 4096, ksize <= 67, and a tile of one output row must fit the
+ * kernel's 60 KB of LDS (MBN_EUNSUPPORTED otherwise, from the plan). The largest downscale that leaves per filter (tests/test_resize_filters_cpu.py
+ * pins each one step inside and one step outside):
+ *     LANCZOS  11x (ksize 67)      BICUBIC  16.5x (ksize 67)      BILINEAR, HAMMING  33x (ksize 67)      NEAREST  any (8192 -> 1)
+ *     BOX      66x by its taps (ksize 67) when only the rows shrink; the four staged source rows of a one-row tile bind first when the columns
+ *              shrink: 58x with more than 32 output columns (3712 -> 64, not 3776) and 49x on both axes at once (3136 x 3136 -> 64 x 64, not
+ *              3200 x 3200), in both kernels; 66x on both axes with at most 32 output columns (a tile of 32 columns stages half as much)
+ *   mbn_resize_ksize   ksize of an axis, or a negative status; mbn_resize_ksize_filter likewise (NEAREST: 1)
  *   mbn_resize_taps    the tables of an axis: first[i] = lo, count[i] = n, weights [out_size][ksize] zero padded; returns ksize (>= 3) or a
  *                      negative status. Host code (host/mbn_resize.c; the expressions above are host/mbn_resize_axis.h, compiled for the host
- *                      and for the device); also in libmbn_host.so
+ *                      and for the device); also in libmbn_host.so. mbn_resize_taps_filter likewise (ksize >= 1)
+ *   mbn_resize_nearest_index   NEAREST's index [out_size] of an axis; MBN_OK or MBN_EINVAL
  *   mbn_fit_box        the box of a fit mode. MBN_FIT_STRETCH: (0, 0, W, H). MBN_FIT_CROP: the centred box with the output's aspect ratio,
  *                      shrunk by crop_fraction f in (0, 1] (f = 0.875 is the usual "resize to 256, crop 224"); in double
  *                      bw = min(W, H * ow / oh) * f, bh = bw * oh / ow, left = (W - bw) / 2, upper = (H - bh) / 2, each edge then rounded to
@@ -500,14 +528,28 @@ int mbn_normalize_u8_to_f32(mbn_context *ctx, void *out_f32, const void *in_u8, 
  *                       read 4 bytes at a time from its first 4-byte boundary on, bytewise around it: the same bytes out); no byte outside
  *                       the two tensors is read or written. The mbn_alloc bounds rule above applies: an undersized tracked `in` or `out` is
  *                       MBN_EINVAL and nothing is launched. NULL pointers, batch <= 0: MBN_EINVAL
- *   mbn_resizer_destroy frees the handle (waits for the context's stream); mbn_shutdown frees the handles still alive */
+ *   mbn_resizer_destroy frees the handle (waits for the context's stream); mbn_shutdown frees the handles still alive
+ *   mbn_resizer_create_filter   the same under any filter; mbn_resizer_create is its MBN_FILTER_BILINEAR call. The filter belongs to the handle:
+ *                       mbn_resize_u8 is the one hot call. The five convolution filters run the same kernel on their own tables; NEAREST has a
+ *                       kernel of its own, a gather of 3-byte pixels through the uploaded ix [out_cols], iy [out_rows], under the same contract
+ *                       (any byte pointers: dword stores from the first 4-byte boundary of an output row's address on, bytewise around them) */
 #define MBN_FIT_STRETCH 0
 #define MBN_FIT_CROP    1
+#define MBN_FILTER_NEAREST  0        /* PIL.Image.Resampling's numbers */
+#define MBN_FILTER_LANCZOS  1
+#define MBN_FILTER_BILINEAR 2
+#define MBN_FILTER_BICUBIC  3
+#define MBN_FILTER_BOX      4
+#define MBN_FILTER_HAMMING  5
 int  mbn_resize_ksize(int in_size, float b0, float b1, int out_size);
 int  mbn_resize_taps(int in_size, float b0, float b1, int out_size, int32_t *first, int32_t *count, int32_t *weights);
+int  mbn_resize_ksize_filter(int filter, int in_size, float b0, float b1, int out_size);
+int  mbn_resize_taps_filter(int filter, int in_size, float b0, float b1, int out_size, int32_t *first, int32_t *count, int32_t *weights);
+int  mbn_resize_nearest_index(int in_size, float b0, float b1, int out_size, int32_t *index);
 int  mbn_fit_box(int in_rows, int in_cols, int out_rows, int out_cols, int fit, float crop_fraction, float box[4]);
 typedef struct mbn_resizer mbn_resizer;
 int  mbn_resizer_create(mbn_context *ctx, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r);
+int  mbn_resizer_create_filter(mbn_context *ctx, int filter, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r);
 int  mbn_resize_u8(mbn_resizer *r, void *out_u8, const void *in_u8, int batch, void *stream);
 int  mbn_resizer_destroy(mbn_resizer *r);
 /* Ragged resize (mbn_u8_resize_ragged.hip): ONE launch takes `batch` images, each with its own rows, cols and box, to one common
@@ -533,10 +575,22 @@ int  mbn_resizer_destroy(mbn_resizer *r);
  *   mbn_resize_taps_device      the kernel's own tap function for one axis, into int32 DEVICE arrays first [out_size], count [out_size],
  *                               weights [out_size][ksize] (zero padded), on the context's stream: what mbn_resize_taps gives on the host, so the
  *                               device arithmetic is pinned as tables and not only through bytes. Returns ksize or a negative status
- *                               (MBN_EUNSUPPORTED beyond in_size 8192, out_size 4096 or 67 taps) */
+ *                               (MBN_EUNSUPPORTED beyond in_size 8192, out_size 4096 or 67 taps)
+ *   mbn_ragged_resizer_create_filter   the same handle under a filter (mbn_ragged_resizer_create is its MBN_FILTER_BILINEAR call); _set and the
+ *                               launch are unchanged. NEAREST, BOX, BILINEAR and BICUBIC only: their taps are plain fp64 arithmetic, which the
+ *                               kernel forms with the host's bits (the reciprocal 1.0 / fs a true division, no contraction). NEAREST is a kernel
+ *                               of its own: lane c of a tile forms its column's index with its own chain of dependent fp64 additions from xo_0
+ *                               (at most 4095; no cheaper form gives the same bits), likewise the rows. MBN_FILTER_HAMMING and
+ *                               MBN_FILTER_LANCZOS answer MBN_EUNSUPPORTED here: their weights need sin / cos bit-equal to the host's libm,
+ *                               which device math does not promise, and a nearly-always-equal form is not shipped. Use mbn_resizer_create_filter
+ *   mbn_resize_taps_device_filter      mbn_resize_taps_device under one of those four filters (HAMMING, LANCZOS: MBN_EUNSUPPORTED): what
+ *                               mbn_resize_taps_filter gives on the host (NEAREST: first = the index, count 1, weight 2^22) */
 typedef struct mbn_resize_item { int64_t src_offset; int32_t rows, cols; float box[4]; } mbn_resize_item;   /* 32 bytes */
 typedef struct mbn_ragged_resizer mbn_ragged_resizer;
 int  mbn_ragged_resizer_create(mbn_context *ctx, int max_batch, int out_rows, int out_cols, mbn_ragged_resizer **r);
+int  mbn_ragged_resizer_create_filter(mbn_context *ctx, int filter, int max_batch, int out_rows, int out_cols, mbn_ragged_resizer **r);
+int  mbn_resize_taps_device_filter(mbn_context *ctx, int filter, int in_size, float b0, float b1, int out_size, void *first_i32, void *count_i32,
+                                   void *weights_i32);
 int  mbn_ragged_resizer_set(mbn_ragged_resizer *r, const mbn_resize_item *items, int batch, void *stream);
 int  mbn_resize_ragged_u8(mbn_ragged_resizer *r, void *out_u8, const void *src_u8, void *stream);
 int  mbn_ragged_resizer_destroy(mbn_ragged_resizer *r);
@@ -758,6 +812,11 @@ int  mbn_net_resize_input(mbn_net *net, const void *src_u8, int batch, int in_ro
  * one ragged resizer of max_batch images, created on the first call and freed by mbn_net_destroy. Any dtype, any plan; no forward path changes. */
 int  mbn_net_resize_inputs(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *rows, const int32_t *cols, int batch, int fit,
                            float crop_fraction, void **images_u8);
+/* The filter of mbn_net_resize_input / _inputs and, through them, mbn_net_segment_images: one of MBN_FILTER_* (else MBN_EINVAL; nothing changes).
+ * MBN_FILTER_BILINEAR until this is called. The kept resizers are rebuilt on the next call after a change. Under MBN_FILTER_HAMMING / _LANCZOS
+ * mbn_net_resize_inputs passes the ragged path's MBN_EUNSUPPORTED on and the net stays usable (mbn_net_resize_input takes every filter). */
+int  mbn_net_set_resize_filter(mbn_net *net, int filter);
+int  mbn_net_get_resize_filter(const mbn_net *net, int *filter);
 int  mbn_net_fused_layers(const mbn_net *net, int last_layer, int *count);
 /* Fused depthwise->pointwise blocks (mbn_dwpw_fused): bit L of `mask` (L = 1-based number of a depthwise layer) lets
  * layers L and L+1 run as one launch when the plan is fp32, activations are not kept and the shapes are inside the

@@ -1,4 +1,4 @@
-"""The resize front-end (mbn_resize_u8) against torch-ROCm's antialiased bilinear interpolate and against the forward it precedes, in one process.
+"""The resize front-end (mbn_resize_u8, under any of Pillow's filters) against torch-ROCm's antialiased interpolate and against the forward it precedes, in one process.
 
   python tools/resize_bench.py [--reps 7] [--steps 20] [--configs photo_b256,identity_b256] [--no-torch] [--no-forward]
       Geometries (uint8 HWC sources, random bytes):
@@ -15,6 +15,10 @@
       tables reach, once, plus the output — over 8 TB/s. Then the forward the resize precedes (1.0x224, uint8 input): fp32 at batch 256 and bf16
       at batch 512, and the resize's share of it. The kernel's output is compared once with tests/resize_ref.py on image 0 (agreement, not timing).
       One JSON object at the end. No GPU: the Context raises; nothing falls back.
+      --filter LIST: comma list of nearest, box, bilinear (the default), hamming, bicubic, lanczos, or `all`. Every geometry runs once per filter, all
+      of them alternating within every repetition; the entries are named <geometry>:<filter> (the bilinear ones keep the bare name) and carry the
+      taps per axis. The kernel's bytes are compared with tests/resize_filters_ref.py; the torch yardstick is mode="bicubic" under bicubic and
+      lanczos, "nearest" under nearest, "bilinear" with antialias otherwise.
 
   python tools/resize_bench.py --ragged [--seed 1] [--batch 256] [--reps 7] [--steps 20]
       The ragged resize (mbn_resize_ragged_u8) on a seeded batch of images of DIFFERENT sizes: rows 300-600, cols 300-700, each through its crop-0.875
@@ -26,6 +30,7 @@
                  taps on the device and of the descriptor lookup
       Every figure is a host clock around `steps` calls that end in a device synchronise, in ms per batch: median over the repetitions and their
       range. The ragged output of both batches is compared once with the table kernel's bytes, image by image (agreement, not timing).
+      --filter NAME: one of nearest, box, bilinear (the default), bicubic, for the ragged and the table resizers alike.
 """
 import argparse
 import json
@@ -49,10 +54,10 @@ CONFIGS = [("photo_b256", 375, 500, "crop", 0.875, 256, "f32_b256"), ("photo_b51
 FORWARDS = {"f32_b256": ("f32", 256), "bf16_b512": ("bf16", 512)}
 
 
-def window(pkg, in_size, b0, b1, out_size):
-    """[lo, hi): the source positions the tap tables of an axis reach"""
-    first, count, _ = pkg.resize_taps(in_size, float(b0), float(b1), out_size)
-    return int(first[0]), int(first[-1] + count[-1])
+def window(pkg, in_size, b0, b1, out_size, filt):
+    """[lo, hi): the source positions the tap tables of an axis reach, and its taps per output"""
+    first, count, w = pkg.resize_taps(in_size, float(b0), float(b1), out_size, filter=filt)
+    return int(first[0]), int(first[-1] + count[-1]), int(w.shape[1])
 
 
 def marks_ms(ctx, fn, steps):
@@ -84,9 +89,10 @@ def ragged_main(a):
     assert torch.cuda.is_available(), "the buffers are torch tensors on the same GPU"
     rng = np.random.default_rng(a.seed)
     n = a.batch
-    print("ragged: seed %d, batch %d, rows 300-600 x cols 300-700 -> %d x %d, crop 0.875" % (a.seed, n, RES, RES), flush=True)
+    filt = pkg.FILTER_NAMES[a.filter or "bilinear"]
+    print("ragged: seed %d, batch %d, rows 300-600 x cols 300-700 -> %d x %d, crop 0.875, filter %s" % (a.seed, n, RES, RES, a.filter or "bilinear"), flush=True)
     batches = {"mixed": [(int(rng.integers(300, 601)), int(rng.integers(300, 701))) for _ in range(n)], "uniform": [(375, 500)] * n}
-    result = {"seed": a.seed, "batch": n, "steps": a.steps, "reps": a.reps}
+    result = {"seed": a.seed, "batch": n, "steps": a.steps, "reps": a.reps, "filter": a.filter or "bilinear"}
     with pkg.Context(0) as ctx:
         forms = {}
         for name, sizes in batches.items():
@@ -97,7 +103,7 @@ def ragged_main(a):
             boxes = [pkg.fit_box(h, w, RES, RES, pkg.FIT_CROP, 0.875) for h, w in sizes]
             items = pkg.resize_items([(int(o), h, w, b) for o, (h, w), b in zip(offs, sizes, boxes)])
             src, one, rag, img = t_src.data_ptr(), t_one.data_ptr(), t_rag.data_ptr(), RES * RES * 3
-            rr = pkg.RaggedResizer(ctx, n, RES, RES)
+            rr = pkg.RaggedResizer(ctx, n, RES, RES, filter=filt)
 
             def ragged(rr=rr, items=items, rag=rag, src=src):
                 rr.set(items)
@@ -105,17 +111,17 @@ def ragged_main(a):
 
             def with_builds(sizes=sizes, boxes=boxes, offs=offs, one=one, src=src):
                 for i, ((h, w), b) in enumerate(zip(sizes, boxes)):
-                    rz = pkg.Resizer(ctx, h, w, RES, RES, b)
+                    rz = pkg.Resizer(ctx, h, w, RES, RES, b, filter=filt)
                     rz.run(one + i * img, src + int(offs[i]), 1)
                     rz.close()
 
             f = {"ragged_set_and_launch": ragged}
             if name == "mixed":
-                built = [pkg.Resizer(ctx, h, w, RES, RES, b) for (h, w), b in zip(sizes, boxes)]
+                built = [pkg.Resizer(ctx, h, w, RES, RES, b, filter=filt) for (h, w), b in zip(sizes, boxes)]
                 f["one_by_one_prebuilt"] = lambda built=built, offs=offs, one=one, src=src: [rz.run(one + i * img, src + int(offs[i]), 1) for i, rz in enumerate(built)]
                 f["one_by_one_with_builds"] = with_builds
             else:
-                built = [pkg.Resizer(ctx, 375, 500, RES, RES, boxes[0])]
+                built = [pkg.Resizer(ctx, 375, 500, RES, RES, boxes[0], filter=filt)]
                 f["table_kernel"] = lambda rz=built[0], one=one, src=src: rz.run(one, src, n)
                 f["ragged_launch_alone"] = lambda rr=rr, rag=rag, src=src: rr.run(rag, src)
             for fn in f.values():                           # warm-up of every timed form; the last ragged set stays for the launch alone
@@ -159,34 +165,42 @@ def main():
     ap.add_argument("--ragged", action="store_true", help="the ragged resize against one launch per image and against the table kernel")
     ap.add_argument("--seed", type=int, default=1, help="--ragged: seed of the batch's size list")
     ap.add_argument("--batch", type=int, default=256, help="--ragged: images per batch")
+    ap.add_argument("--filter", default="", help="comma list of Pillow filter names, or all (--ragged: one name); default bilinear")
     a = ap.parse_args()
     if a.ragged:
         return ragged_main(a)
     chosen = [c for c in CONFIGS if not a.configs or c[0] in a.configs.split(",")]
     pkg = import_package()
-    import resize_ref
+    import resize_filters_ref
     import torch
     assert torch.cuda.is_available(), "the buffers are torch tensors on the same GPU"
     F = torch.nn.functional
     result = {}
     with tempfile.TemporaryDirectory() as d, pkg.Context(0) as ctx:
         runs = {}
-        for name, H, W, fit, frac, n, fwd in chosen:
+        names = [f for f in ("nearest", "box", "bilinear", "hamming", "bicubic", "lanczos") if a.filter == "all" or f in (a.filter or "bilinear").split(",")]
+        assert names and (a.filter in ("", "all") or len(names) == len(a.filter.split(","))), "--filter: unknown name in %r" % a.filter
+        for name, H, W, fit, frac, n, fwd, fname in [c + (f,) for c in chosen for f in names]:
+            filt = pkg.FILTER_NAMES[fname]
+            name = name if fname == "bilinear" else "%s:%s" % (name, fname)
             box = pkg.fit_box(H, W, RES, RES, pkg.FIT_CROP if fit == "crop" else pkg.FIT_STRETCH, frac)
-            x0, x1 = window(pkg, W, box[0], box[2], RES)
-            y0, y1 = window(pkg, H, box[1], box[3], RES)
+            x0, x1, kx = window(pkg, W, box[0], box[2], RES, filt)
+            y0, y1, ky = window(pkg, H, box[1], box[3], RES, filt)
             t_src = torch.randint(0, 256, (n, H, W, 3), dtype=torch.uint8, device="cuda")       # the library reads what torch owns
             t_out = torch.zeros((n, RES, RES, 3), dtype=torch.uint8, device="cuda")
             torch.cuda.synchronize()
-            rz = pkg.Resizer(ctx, H, W, RES, RES, box)
-            r = dict(rz=rz, n=n, fwd=fwd, t_src=t_src, t_out=t_out, kernel=[], torch=[],
+            rz = pkg.Resizer(ctx, H, W, RES, RES, box, filter=filt)
+            r = dict(rz=rz, n=n, fwd=fwd, filter=fname, kx=kx, ky=ky, t_src=t_src, t_out=t_out, kernel=[], torch=[],
                      bytes=3.0 * n * ((y1 - y0) * (x1 - x0) + RES * RES), box=[float(v) for v in box])
             r["run_kernel"] = lambda r=r: r["rz"].run(r["t_out"].data_ptr(), r["t_src"].data_ptr(), r["n"])
             hull = t_src[:, int(np.floor(box[1])):int(np.ceil(box[3])), int(np.floor(box[0])):int(np.ceil(box[2])), :].permute(0, 3, 1, 2)
-            r["run_torch"] = lambda hull=hull: F.interpolate(hull.float(), size=(RES, RES), mode="bilinear", antialias=True)
+            mode = {"bicubic": "bicubic", "lanczos": "bicubic", "nearest": "nearest"}.get(fname, "bilinear")
+            r["run_torch"] = ((lambda hull=hull: F.interpolate(hull.float(), size=(RES, RES), mode="nearest")) if mode == "nearest" else
+                              (lambda hull=hull, mode=mode: F.interpolate(hull.float(), size=(RES, RES), mode=mode, antialias=True)))
+            r["torch_mode"] = mode
             marks_ms(ctx, r["run_kernel"], 3)               # warm-up of every timed shape
             ctx.sync()
-            want = resize_ref.resize(t_src[0].cpu().numpy(), RES, RES, box)
+            want = resize_filters_ref.resize(filt, t_src[0].cpu().numpy(), RES, RES, box)
             r["bytes_differ_from_ref"] = int((t_out[0].cpu().numpy() != want).sum())
             if not a.no_torch:
                 for _ in range(3):
@@ -228,16 +242,16 @@ def main():
                 d_logits.free()
         for name, r in runs.items():
             k = statistics.median(r["kernel"])
-            out = {"batch": r["n"], "box": r["box"], "kernel_ms": round(k, 4), "kernel_runs_ms": [round(x, 4) for x in r["kernel"]],
+            out = {"batch": r["n"], "box": r["box"], "filter": r["filter"], "kx": r["kx"], "ky": r["ky"], "kernel_ms": round(k, 4), "kernel_runs_ms": [round(x, 4) for x in r["kernel"]],
                    "kernel_bytes": int(r["bytes"]), "kernel_frac_of_8TBps": round(r["bytes"] / HBM_BYTES_PER_S / (k / 1e3), 4),
                    "bytes_differ_from_ref_image0": r["bytes_differ_from_ref"]}
             if r["torch"]:
                 t = statistics.median(r["torch"])
-                out.update({"torch_ms": round(t, 4), "torch_runs_ms": [round(x, 4) for x in r["torch"]], "torch_over_kernel": round(t / k, 2)})
+                out.update({"torch_mode": r["torch_mode"], "torch_ms": round(t, 4), "torch_runs_ms": [round(x, 4) for x in r["torch"]], "torch_over_kernel": round(t / k, 2)})
             if r["fwd"] in forward_ms:
                 out.update({"forward": r["fwd"], "forward_ms": round(forward_ms[r["fwd"]], 4), "kernel_over_forward": round(k / forward_ms[r["fwd"]], 4)})
             result[name] = out
-            print("%-14s batch %3d  kernel %.4f ms (%.1f %% of 8 TB/s)  torch %s ms  forward %s ms" % (
+            print("%-22s batch %3d  kernel %.4f ms (%.1f %% of 8 TB/s)  torch %s ms  forward %s ms" % (
                 name, r["n"], k, 100 * out["kernel_frac_of_8TBps"], ("%.4f" % out["torch_ms"]) if r["torch"] else "-",
                 ("%.4f (%s)" % (out["forward_ms"], r["fwd"])) if "forward_ms" in out else "-"), flush=True)
             r["rz"].close()
