@@ -6,8 +6,8 @@ a power of two per channel and the shift a multiple of 2^-7, so fma(acc, scale, 
 output is then bf16_rne(clip(exact, 0, 6)) bit for bit, whatever its summation order, and a test compares with array_equal.
 
 Contract (the oracle's): activations NHWC, depthwise filter [3][3][C] fp32, pointwise filter [Cout][Cin] (bf16 values),
-conv1 filter [3][3][3][Cout] fp32, scale / shift fp32 per output channel, act 0 (none) or 2 (ReLU6), every layer output
-rounded to bf16 (round to nearest even) in bf16 mode. All arithmetic here is float64 numpy.
+conv1 filter [3][3][3][Cout] fp32, scale / shift fp32 per output channel (either may be NULL: 1 / 0), act 0 (none), 1 (ReLU) or
+2 (ReLU6), every layer output rounded to bf16 (round to nearest even) in bf16 mode. All arithmetic here is float64 numpy.
 
 Test infrastructure only (like int8_ref.py); not a conftest.
 """
@@ -15,7 +15,11 @@ from __future__ import annotations
 
 import numpy as np
 
-ACT_NONE, ACT_RELU6 = 0, 2
+ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
+ACTS = (ACT_NONE, ACT_RELU, ACT_RELU6)
+PARAMS = ("both", "scale", "shift", "none")          # which of scale / shift a call gives; the other is NULL
+COMBOS = [(a, p) for p in PARAMS for a in ACTS]      # the 12 epilogue combinations, the forms with a scale first
+Z_SHARES = dict(neg=0.10, mid=0.20, high=0.02)       # the least shares of z < 0, 0 < z < 6, z > 6 an epilogue case must have
 LIMIT = 2.0 ** 24              # fp32 holds every integer below it
 
 
@@ -58,13 +62,17 @@ def relu6(y):
     return np.clip(y, 0.0, 6.0)
 
 
-def coverage(y, act=ACT_RELU6):
-    """Shares of a tensor that is about to be rounded to bf16 (y: exact values after the activation)."""
+def coverage(y, act=ACT_RELU6, z=None):
+    """Shares of a tensor that is about to be rounded to bf16 (y: exact values after the activation). z: the values before the activation;
+    with them the shares below 0, strictly inside (0, 6) and above 6 — the regions in which no activation, ReLU and ReLU6 differ."""
     u = f32_bits(y)
     low, odd = u & 0xFFFF, (u >> 16) & 1
     tie = low == 0x8000
-    return dict(n=int(y.size), act=act, inside=float(np.mean((y > 0) & (y < 6))), at0=float(np.mean(y == 0)), at6=float(np.mean(y == 6)),
-                changed=float(np.mean(low != 0)), ties_up=int(np.sum(tie & (odd == 1))), ties_down=int(np.sum(tie & (odd == 0))))
+    cov = dict(n=int(y.size), act=act, inside=float(np.mean((y > 0) & (y < 6))), at0=float(np.mean(y == 0)), at6=float(np.mean(y == 6)),
+               changed=float(np.mean(low != 0)), ties_up=int(np.sum(tie & (odd == 1))), ties_down=int(np.sum(tie & (odd == 0))))
+    if z is not None:
+        cov.update(neg=float(np.mean(z < 0)), mid=float(np.mean((z > 0) & (z < 6))), high=float(np.mean(z > 6)))
+    return cov
 
 
 def lsb_grid(a):
@@ -89,9 +97,9 @@ def gen_act(rng, shape, step=1.0 / 8, fine=False):
     return np.clip(rng.integers(-hi // 5, hi + hi // 6 + 1, shape), 0, hi) * step
 
 
-def gen_image(rng, shape):
-    """Network input on a 1/8 grid in [-1, 1]."""
-    return rng.integers(-8, 9, shape) / 8.0
+def gen_image(rng, shape, steps=8):
+    """Network input on a 1/8 grid in [-1, 1] (the image is fp32 in every mode, so a finer grid, 1/steps, stays exact as well)."""
+    return rng.integers(-steps, steps + 1, shape) / float(steps)
 
 
 def gen_dw_filter(rng, c, first=True, live=7):
@@ -122,17 +130,24 @@ def gen_conv1_filter(rng, cout, density=1.0):
     return w
 
 
-def gen_scale_shift(rng, acc, lo, hi, target=2.0, spread=1):
+def spread_exponent(acc, target=2.0):
+    """e0 with std(acc) * 2^-e0 nearest `target`: the accumulator's spread, pooled over the channels"""
+    c = acc.shape[-1]
+    sd = max(float(np.sqrt(np.mean(np.var(acc.reshape(-1, c), axis=0)))), 2.0 ** -20)
+    return int(np.round(np.log2(sd / target)))
+
+
+def gen_scale_shift(rng, acc, lo, hi, target=2.0, spread=1, unit_scale=False):
     """Per-channel scale 2^-e[c], e[c] = e0 + {-spread..spread}, e0 from the accumulator's per-channel standard deviation so that acc * scale
     has one near `target`; shift: an odd multiple of 2^-7 that puts the channel's mean at a value drawn from [lo, hi] (a channel whose filter sums
-    far from zero would otherwise sit wholly at one clamp). Adjacent channels differ in both."""
+    far from zero would otherwise sit wholly at one clamp). Adjacent channels differ in both. unit_scale: the same draws, but the scale is 1
+    for every channel (a call with scale NULL) and the shift is the one that goes with that."""
     c = acc.shape[-1]
     a2 = acc.reshape(-1, c)
-    sd = max(float(np.sqrt(np.mean(np.var(a2, axis=0)))), 2.0 ** -20)
-    e0 = int(np.round(np.log2(sd / target)))
+    e0 = spread_exponent(acc, target)
     e = e0 + rng.integers(-spread, spread + 1, c)
     e[1::2] = np.where(e[1::2] == e[0::2][:e[1::2].size], e[1::2] - 1, e[1::2])          # a channel pair never shares its scale
-    scale = 2.0 ** -e.astype(np.float64)
+    scale = np.ones(c) if unit_scale else 2.0 ** -e.astype(np.float64)
     mu = lo + (hi - lo) * (rng.permutation(c) + rng.random(c)) / c            # stratified: a handful of channels still spans [lo, hi]
     shift = 2.0 * np.round((mu - a2.mean(axis=0) * scale) * 64.0) + 1.0      # odd: the 2^-7 bit reaches every element
     shift[1::2] = np.where(shift[1::2] == shift[0::2][:shift[1::2].size], shift[1::2] + 2, shift[1::2])
@@ -207,7 +222,9 @@ def pw_acc_f32(x2d, wp, order=1):
 
 def bn_act(acc, scale, shift, act):
     y = acc * (1.0 if scale is None else scale) + (0.0 if shift is None else shift)
-    return relu6(y) if act == ACT_RELU6 else y
+    if act not in ACTS:
+        raise ValueError(act)
+    return relu6(y) if act == ACT_RELU6 else np.maximum(y, 0.0) if act == ACT_RELU else y
 
 
 def pool_mean(x):
@@ -220,9 +237,11 @@ def pool_mean(x):
 class Layer:
     """One evaluated layer: inputs, parameters, the exact result y (after the activation) and `out` = what the next layer reads."""
 
-    def __init__(self, kind, x, w, scale, shift, act, acc, mag, rounded, geom=None):
+    def __init__(self, kind, x, w, scale, shift, act, acc, mag, rounded, geom=None, epilogue_case=False):
         self.kind, self.x, self.w, self.scale, self.shift, self.act, self.acc, self.mag, self.rounded = kind, x, w, scale, shift, act, acc, mag, rounded
         self.geom = geom or {}
+        self.epilogue_case = epilogue_case        # a case of the epilogue matrix: check_gate asks for Z_SHARES of z
+        self.z = bn_act(acc, scale, shift, ACT_NONE)
         self.y = bn_act(acc, scale, shift, act)
         self.out = bf16_rne(self.y) if rounded else self.y
 
@@ -235,10 +254,19 @@ class Layer:
         unit = np.minimum(grid * sc, lsb_grid(sh) if np.any(sh) else np.inf)
         epi = np.max((self.mag.reshape(-1, self.acc.shape[-1]).max(axis=0) * sc + np.abs(sh)) / unit)
         return dict(kind=self.kind, grid=grid, terms=float(self.mag.max() / grid), epilogue=float(epi),
-                    rounded=self.rounded, coverage=coverage(self.y, self.act))
+                    rounded=self.rounded, coverage=coverage(self.y, self.act, self.z))
 
 
-def make_layer(rng, kind, x, w, act=ACT_RELU6, rounded=True, shift_range=None, scale=True, target=2.0, spread=1, **geom):
+def make_layer(rng, kind, x, w, act=ACT_RELU6, rounded=True, shift_range=None, scale=True, target=2.0, spread=1, params=None, **geom):
+    """params None: scale and shift given (scale False: the FC form), as every case before the epilogue matrix. params in PARAMS: a case of that
+    matrix. "both" makes the same draws as None. With scale NULL ("shift", "none") the raw accumulator would lie far outside [0, 6]: the input is
+    shrunk by the power of two that brings the accumulator's standard deviation s into [1.5, 3) x `target` (the operands stay bf16 values,
+    sum|terms| in grid units does not change), and the shift centres the channels as it does behind a scale. That interval, [3, 6) at the default
+    target: no per-channel scale spreads the channels here, and a channel centred on 0 (conv1: a zero-mean image) has P(z > 6) = 1 - Phi(6 / s),
+    2.3 % at s = 3, and P(0 < z < 6) = Phi(6 / s) - 1 / 2, 34 % at s = 6. With shift NULL ("scale", "none") nothing centres a channel: z is what
+    the filter gives. x and w do not depend on act or params beyond that power of two, so one upload serves a whole matrix."""
+    if params is not None and (params not in PARAMS or not scale):
+        raise ValueError(params)
     if kind == "dw":
         acc, mag = dw_acc(x, w, **geom)
         rng_sh = shift_range or (-1, 4)
@@ -250,10 +278,17 @@ def make_layer(rng, kind, x, w, act=ACT_RELU6, rounded=True, shift_range=None, s
         rng_sh = shift_range or (-1, 4)
     else:
         raise ValueError(kind)
-    sc, sh = gen_scale_shift(rng, acc, *rng_sh, target=target, spread=spread)
+    if params in ("shift", "none"):
+        down = 2.0 ** -spread_exponent(acc, 1.5 * target * 2.0 ** 0.5)              # nearest to 1.5 sqrt(2) t in log2: s * down in [1.5 t, 3 t)
+        x, acc, mag = x * down, acc * down, mag * down
+    sc, sh = gen_scale_shift(rng, acc, *rng_sh, target=target, spread=spread, unit_scale=params in ("shift", "none"))
     if not scale:                                        # the FC form: integer bias, nothing to centre
         sh = rng.integers(rng_sh[0], rng_sh[1] + 1, acc.shape[-1]).astype(np.float64)
-    return Layer(kind, x, w, sc if scale else None, sh, act, acc, mag, rounded, geom)
+    if not scale or params in ("shift", "none"):
+        sc = None
+    if params in ("scale", "none"):
+        sh = None
+    return Layer(kind, x, w, sc, sh, act, acc, mag, rounded, geom, epilogue_case=params is not None)
 
 
 def pool_layer(x, rounded=True):
@@ -279,8 +314,13 @@ def check_gate(layers, what=""):
             ties = 16 if cov["n"] >= 4096 else 2
             assert cov["changed"] >= 0.20, "%s: %s" % (tag, cov)
             assert cov["ties_up"] >= ties and cov["ties_down"] >= ties, "%s: %s" % (tag, cov)
-        if l.act == ACT_RELU6:       # rounded or not (the fp32 epilogues clamp too); the clamp shares mean nothing without a clamp
+        if l.act == ACT_RELU6 and not (l.epilogue_case and (l.scale is None or l.shift is None)):
+            # rounded or not (the fp32 epilogues clamp too); the clamp shares mean nothing without a clamp, and they are what a per-channel scale
+            # and a centring shift give: an epilogue case with one of them NULL has Z_SHARES alone
             assert cov["inside"] >= 0.40 and cov["at0"] >= 0.10 and cov["at6"] >= 0.02, "%s: %s" % (tag, cov)
+        if l.epilogue_case:          # every act: elements below 0, inside (0, 6) and above 6 tell none / ReLU / ReLU6 apart
+            assert l.act in ACTS
+            assert all(cov[k] >= v for k, v in Z_SHARES.items()), "%s: %s" % (tag, cov)
     return figs
 
 
@@ -324,20 +364,21 @@ def fp32_orders_agree(l, work=4.0e8, rows=2048):
 
 # ----------------------------------------------------------------------------- cases (what the GPU tests run; the CPU tests gate them)
 
-def pw_case(m, k, n, act=ACT_RELU6, rounded=True, fc=False, seed=0):
-    """One pointwise layer. fc: the FC form (scale NULL, shift given, act 0, fp32 out: nothing is rounded)."""
+def pw_case(m, k, n, act=ACT_RELU6, rounded=True, fc=False, seed=0, params=None):
+    """One pointwise layer. fc: the FC form (scale NULL, shift given, act 0, fp32 out: nothing is rounded). params: see make_layer."""
     rng = np.random.default_rng([1, m, k, n, seed])
     x = gen_act(rng, (m, k), fine=True)
     w = gen_pw_filter(rng, n, k)
     if fc:
         return [make_layer(rng, "pw", x, w, act=ACT_NONE, rounded=False, scale=False, shift_range=(-50, 50))]
-    return [make_layer(rng, "pw", x, w, act=act, rounded=rounded)]
+    return [make_layer(rng, "pw", x, w, act=act, rounded=rounded, params=params)]
 
 
-def dw_case(n, h, c, stride, w=None, rounded=True, seed=0, **geom):
+def dw_case(n, h, c, stride, w=None, rounded=True, seed=0, act=ACT_RELU6, params=None, target=2.0, **geom):
+    """(the seed of a case is the last thing to change when it misses a share of the gate: the conditions stay)"""
     rng = np.random.default_rng([2, n, h, c, stride, seed] + sorted(geom.values()))
     x = gen_act(rng, (n, h, w or h, c), fine=True)
-    return [make_layer(rng, "dw", x, gen_dw_filter(rng, c), rounded=rounded, stride=stride, **geom)]
+    return [make_layer(rng, "dw", x, gen_dw_filter(rng, c), act=act, rounded=rounded, params=params, target=target, stride=stride, **geom)]
 
 
 def pool_case(n, h, c, seed=0):
@@ -381,9 +422,12 @@ def stem_case(n, rows, cols, c1, c3, density=1.0, seed=0, rounded=True):
     return [a, d, p]
 
 
-def conv1_case(n, rows, cols, cout, seed=0):
+def conv1_case(n, rows, cols, cout, seed=0, act=ACT_RELU6, params=None, rounded=False):
+    """params given (the epilogue matrix): the image on a 1/256 grid. With shift NULL no 2^-7 bit reaches the output, and sums of a 1/8-grid image
+    times an integer filter have too few significant bits for a bf16 rounding to change any."""
     rng = np.random.default_rng([7, n, rows, cols, cout, seed])
-    return [make_layer(rng, "conv1", gen_image(rng, (n, rows, cols, 3)), gen_conv1_filter(rng, cout), rounded=False)]
+    img = gen_image(rng, (n, rows, cols, 3), 8 if params is None else 256)
+    return [make_layer(rng, "conv1", img, gen_conv1_filter(rng, cout), act=act, rounded=rounded, params=params)]
 
 
 def inflate(wd, d):

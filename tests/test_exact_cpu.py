@@ -6,15 +6,19 @@ exact comparison catches what the tolerance comparison lets through.
     >= 20 % of the elements changed by the rounding and >= 16 exact ties in each direction (>= 2 under 4096 elements); behind a ReLU6 >= 40 %
     strictly inside (0, 6), >= 10 % at 0 and >= 2 % at 6. (A tensor with no clamp in front of it — act 0, the pooled mean — has no clamp shares
     to ask for.) These are conditions on the inputs, not measurements of any kernel.
-(2) exact_ref == oracle.f32_* + bf16_round bit for bit on these inputs (both are exact, so equality).
+    The cases of tests/test_epilogue_gpu.py (every act with scale / shift given or NULL, 12 per route) pass the same gate, and in each at least
+    10 % of z = acc * scale + shift lie below 0, 20 % inside (0, 6) and 2 % above 6: the three regions in which none / ReLU / ReLU6 differ.
+(2) exact_ref == oracle.f32_* + bf16_round bit for bit on these inputs (both are exact, so equality), ReLU and the NULL forms included.
 (3) Six mutants of the reference — what a subtly wrong kernel would compute — all differ from it under array_equal; on the random-data recipe
-    of test_parity_gpu.py most of them pass that file's assert_close(..., TOL_BF16).
+    of test_parity_gpu.py most of them pass that file's assert_close(..., TOL_BF16). Four more, (g) - (j), are wrong epilogues: the wrong
+    activation, a parameter dropped, the activation before the affine; each differs in every combination it applies to.
 """
 import numpy as np
 import pytest
 
 import exact_ref as E
 import test_exact_gpu as G
+import test_epilogue_gpu as P
 
 TOL_BF16 = 1e-2
 
@@ -129,6 +133,68 @@ def test_forced_routes_are_inside_their_kernels_envelopes():
     assert [tiles(s) > 512 for s in G.PW_DEFAULT] == [False] * 5 + [True] * 2      # more than one tile per workgroup of the persistent streaming grid
 
 
+# ----------------------------------------------------------------------------- (1b) the gate on every case of the epilogue matrix
+
+def _gate_matrix(layers, what):
+    """All 12 cases of one route: the gate (with exact_ref.Z_SHARES of z = acc * scale + shift below 0, inside (0, 6) and above 6), and that one upload
+    of the filter, two of the activations and one of each parameter vector serve them all. Prints the three shares of every case."""
+    down = P.shared_operands(layers)
+    assert down is not None and down <= 1.0, what           # (1: conv1's accumulator of a [-1, 1] image has the wanted spread as it is)
+    assert sorted(layers) == sorted(E.COMBOS)
+    for (act, params), l in layers.items():
+        assert l.epilogue_case and l.act == act
+        (f,) = _gate([l], "%s act %d %-5s" % (what, act, params))
+        c = f["coverage"]
+        print("    z < 0 %.3f   0 < z < 6 %.3f   z > 6 %.3f" % (c["neg"], c["mid"], c["high"]))
+        assert c["neg"] >= 0.10 and c["mid"] >= 0.20 and c["high"] >= 0.02, (what, act, params, c)
+    for p in E.PARAMS:                                 # z does not depend on act, and the three acts differ on it
+        ys = [layers[(a, p)].y for a in E.ACTS]
+        assert np.array_equal(layers[(0, p)].z, layers[(2, p)].z)
+        assert not np.array_equal(ys[0], ys[1]) and not np.array_equal(ys[1], ys[2])
+
+
+@pytest.mark.parametrize("shape", sorted(set(s for _, s in P.F32_PW_ROUTES)))
+def test_gate_epilogue_f32_pointwise(shape):
+    layers = P.pw_matrix(shape, rounded=False)
+    _gate_matrix(layers, "epilogue f32 pw %s" % (shape,))
+    for a in (layers[(2, "both")].x, layers[(2, "none")].x, layers[(2, "both")].w):      # pw_emul's split is exact for <= 8 significant bits
+        assert np.array_equal(E.bf16_rne(a), a)
+
+
+@pytest.mark.parametrize("route", P.BF16_PW_ROUTES, ids=str)
+def test_gate_epilogue_bf16_pointwise(route):
+    shape, out_f32 = route
+    _gate_matrix(P.pw_matrix(shape, rounded=not out_f32), "epilogue bf16 pw %s%s" % (shape, " fp32 out" if out_f32 else ""))
+
+
+@pytest.mark.parametrize("rounded", [False, True], ids=["f32", "bf16"])
+@pytest.mark.parametrize("case", P.DW_ROUTES + [P.DW_LDS_LAB], ids=str)
+def test_gate_epilogue_depthwise(case, rounded):
+    if case == P.DW_LDS_LAB and rounded:
+        return                                         # the LDS-staged form is fp32 only
+    _gate_matrix(P.dw_matrix(case, rounded), "epilogue %s dw %s" % ("bf16" if rounded else "f32", case))
+
+
+@pytest.mark.parametrize("rounded", [False, True], ids=["f32", "bf16"])
+@pytest.mark.parametrize("case", P.CONV_ROUTES, ids=str)
+def test_gate_epilogue_conv1(case, rounded):
+    _gate_matrix(P.conv_matrix(case, rounded), "epilogue %s conv1 %s" % ("bf16" if rounded else "f32", case))
+
+
+def test_epilogue_routes_are_inside_their_kernels_envelopes():
+    """The forced fp32 pointwise routes lie inside the envelope of the kernel their knob forces; the two bf16 shapes meant for the streaming kernels'
+    launcher are inside its envelope with the default combination and outside it with every other act."""
+    for knobs, shape in P.F32_PW_ROUTES:
+        assert G.pw_route_eligible({"pw_splitk": 2} if knobs.get("pw_splitk", 0) > 1 else knobs, shape), (knobs, shape)
+    assert G.pw_route_eligible({"pw_tile": 9}, P.PW_SHAPE, act=2) and not G.pw_route_eligible({"pw_tile": 9}, P.PW_SHAPE, act=1)
+    m, k, n = P.PW_SHAPE                               # split-K's default regime: a 4-image form of the call covers less than half of 256 CUs
+    assert -(-4 * m // 64) * -(-n // 64) * 2 <= 256 and k >= 128 and k % 64 == 0
+    for shape in [(397, 256, 256), (549, 64, 128)]:
+        assert (shape, False) in P.BF16_PW_ROUTES
+        assert G.pw_route_eligible({"pw_ring": 4}, (max(shape[0], 512),) + shape[1:], act=2) and not G.pw_route_eligible({"pw_ring": 4}, shape, act=0)
+    assert (549, 64, 128)[0] >= 512 and (397, 256, 256)[1] >= 256       # the 32x32x16 form needs M >= 512, the 16x16x32 form (K >= 256) takes every M
+
+
 # ----------------------------------------------------------------------------- (2) the reference is the oracle
 
 def _oracle_layer(orc, l):
@@ -153,6 +219,9 @@ def test_reference_equals_oracle(orc, pkg):
     layers += G.block_layers(G.BLOCK_CASES[2]) + G.block_asym_layers(G.BLOCK_ASYM[1]) + G.res_layers(G.RES_CASES[7]) + G.tail_layers(G.TAIL_CASES[1])
     layers += G.stem_layers(G.STEM_CASES[2]) + E.conv1_case(1, 33, 33, 8)
     layers += [E.pool_layer(E.pool_case(*s)) for s in G.POOL_CASES]
+    # the epilogue matrix: per kind, ReLU with both parameters and every NULL form (under ReLU, no activation and ReLU6 in turn)
+    for matrix in (P.pw_matrix((130, 8, 24), True), P.dw_matrix(P.DW_ROUTES[0], True), P.dw_matrix(P.DW_ROUTES[4], False), P.conv_matrix(P.CONV_ROUTES[1], False)):
+        layers += [matrix[(1, "both")], matrix[(1, "scale")], matrix[(0, "shift")], matrix[(2, "none")], matrix[(1, "none")]]
     for l in layers:
         if l.kind == "pool" and l.x.shape[1] != l.x.shape[2]:
             continue                                   # the oracle's pool window is square
@@ -249,3 +318,44 @@ def test_mutants_exact_comparison_catches_all_old_yardstick_few():
     want = rnd(E.relu6((rnd(d_y).reshape(-1, 64) @ wp.T) * s3 + b3))
     verdict = {name[0]: old_yardstick_accepts(got, want) for name, got in _block_mutants(d_y, wp, s3, b3, rnd, _f32).items()}
     assert verdict["a"] and verdict["b"] and verdict["e"], verdict
+
+
+def _epilogue_mutants(l):
+    """name -> what a kernel with one wrong epilogue would give for layer l (before the bf16 rounding), or None where the mutation does not apply
+    to l's combination: (g) ReLU6 where ReLU was asked, (h) ReLU where no activation was asked, (i) `ss = scale && shift` applied to the arithmetic:
+    both parameters dropped when only one is NULL, (j) the activation applied before the affine."""
+    sc = 1.0 if l.scale is None else l.scale
+    sh = 0.0 if l.shift is None else l.shift
+    act = lambda v, a=l.act: E.bn_act(v, None, None, a)
+    return {
+        "g ReLU6 for ReLU": E.relu6(l.z) if l.act == E.ACT_RELU else None,
+        "h ReLU for none": np.maximum(l.z, 0.0) if l.act == E.ACT_NONE else None,
+        "i both dropped when one is NULL": act(l.acc) if (l.scale is None) != (l.shift is None) else None,
+        # (with a shift; or a scale alone under ReLU6, whose upper clamp does not commute with it. ReLU commutes with a positive scale.)
+        "j activation before the affine": act(l.acc) * sc + sh if l.act != E.ACT_NONE and (l.shift is not None or (l.scale is not None and l.act == E.ACT_RELU6)) else None,
+    }
+
+
+def test_epilogue_mutants_are_caught_and_the_old_relu_test_was_blind():
+    """(g) - (j) on one pointwise and one depthwise case of the epilogue matrix (the bf16 forms: the mutant's value is rounded as the reference's is):
+    every mutant differs from the reference under array_equal in EVERY combination it applies to — (g) under ReLU with each of the four parameter
+    forms, (h) under no activation with each of the four, (i) under each act with scale alone and with shift alone, (j) under ReLU and ReLU6 with
+    both and with shift alone, and under ReLU6 with scale alone (under ReLU a positive scale alone commutes with the activation). On test_parity_gpu.py's ReLU recipe (test_f32_depthwise_explicit_padding_and_generic_path: x ~ U(-1, 1),
+    filter ~ N(0, 0.5), stride 2, neither parameter) mutant (g) IS the reference: |acc| stays far below 6, so a kernel that clamps at 6 under ReLU
+    passed that test whatever its tolerance."""
+    for matrix, what in ((P.pw_matrix((130, 8, 24), True), "pointwise"), (P.dw_matrix(P.DW_ROUTES[0], True), "depthwise")):
+        hit = {}
+        for (a, p), l in matrix.items():
+            for name, got in _epilogue_mutants(l).items():
+                if got is not None:
+                    assert not np.array_equal(E.bf16_rne(got), l.out), "%s act %d %s: mutant (%s) not caught" % (what, a, p, name)
+                    assert not np.array_equal(got, l.y)
+                    hit[name[0]] = hit.get(name[0], 0) + 1
+        assert hit == {"g": 4, "h": 4, "i": 6, "j": 5}, hit
+    rng = np.random.default_rng(3)
+    for ch in (8, 6):
+        x = _f32(rng.uniform(-1, 1, (2, 12, 12, ch)))
+        f = _f32(rng.normal(0, 0.5, (3, 3, ch)))
+        z = E.dw_acc(x, f, stride=2, pad_top=1, pad_left=1, out_rows=6, out_cols=6)[0]
+        assert z.max() < 6.0 and z.min() < 0.0 < z.max()
+        assert np.array_equal(E.relu6(z), np.maximum(z, 0.0))

@@ -242,9 +242,17 @@ class Dev:
         return raw[:-64].view(dtype)
 
     def params(self, l):
-        """(wd or bf16 wp, scale, shift) of a layer on the device"""
+        """(wd or bf16 wp, scale, shift) of a layer on the device; None for a scale or shift the layer does not have (the call then passes NULL)"""
         w = self.bf16(l.w) if l.kind == "pw" else self.f32(l.w)
-        return w, self.f32(l.scale), self.f32(l.shift)
+        return w, self.opt_f32(l.scale), self.opt_f32(l.shift)
+
+    def opt_f32(self, a):
+        return None if a is None else self.f32(a)
+
+
+def ptr(buf):
+    """the device pointer of a buffer, NULL for None"""
+    return None if buf is None else buf.ptr
 
 
 def same_bits(got, want, what):
@@ -293,11 +301,10 @@ def _run_pw(pkg, ctx, l, knobs=None, packed=False, dtype=None, in_envelope=True)
             assert flag == pkg.IO_FILT_PACKED
         else:
             d_f = dev.bf16(l.w) if bf else dev.f32(l.w)
-        d_sc = dev.f32(l.scale) if l.scale is not None else None
-        d_sh = dev.f32(l.shift)
+        d_sc, d_sh = dev.opt_f32(l.scale), dev.opt_f32(l.shift)
         out_f32 = not l.rounded
         d_o = dev.out(m * n, 4 if out_f32 else 2)
-        ext = pkg.make_ext(dtype=pkg.DT_BF16 if bf else pkg.DT_F32, act=l.act, scale=d_sc.ptr if d_sc else None, shift=d_sh.ptr,
+        ext = pkg.make_ext(dtype=pkg.DT_BF16 if bf else pkg.DT_F32, act=l.act, scale=ptr(d_sc), shift=ptr(d_sh),
                            io_flags=flag | (pkg.IO_OUT_F32 if (bf and out_f32) else 0))
         ctx.pointwise(d_o.ptr, d_x.ptr, d_f.ptr, m, 1, k, n, ext)
         got = dev.fetch(d_o, m * n, np.uint32 if out_f32 else np.uint16)
@@ -336,7 +343,7 @@ def _run_dw(pkg, ctx, l, knobs=None, dtype=None):
         d_x = dev.bf16(l.x) if bf else dev.f32(l.x)
         d_f, d_sc, d_sh = dev.params(l)
         d_o = dev.out(l.y.size, 2 if bf else 4)
-        ext = pkg.make_ext(batch=n, dtype=pkg.DT_BF16 if bf else pkg.DT_F32, act=l.act, in_rows=h, in_cols=w, scale=d_sc.ptr, shift=d_sh.ptr,
+        ext = pkg.make_ext(batch=n, dtype=pkg.DT_BF16 if bf else pkg.DT_F32, act=l.act, in_rows=h, in_cols=w, scale=ptr(d_sc), shift=ptr(d_sh),
                            pad_top=g.get("pad_top", -1), pad_left=g.get("pad_left", -1), dilation=g.get("dilation", 0))
         ctx.depthwise(d_o.ptr, d_x.ptr, d_f.ptr, oh, ow, 3, g["stride"], c, ext)
         got = dev.fetch(d_o, l.y.size, np.uint16 if bf else np.uint32)
