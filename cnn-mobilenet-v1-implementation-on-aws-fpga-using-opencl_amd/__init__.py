@@ -35,7 +35,7 @@ Q_CARRY_SUM, Q_DW_PLANE0, Q_LITERAL_INDEX, Q_POOL_DIV49 = 1, 2, 4, 8
 QUIRKS_NONE, QUIRKS_KERNEL_CL = 0, 0xF
 L_CONV, L_DW, L_PW, L_POOL, L_FC = 1, 2, 3, 4, 5
 MAX_LAYERS = 32
-FIT_STRETCH, FIT_CROP = 0, 1
+FIT_STRETCH, FIT_CROP, FIT_PAD = 0, 1, 2
 # MBN_FILTER_*: the filter of the resize front-end, PIL.Image.Resampling's own numbers
 FILTER_NEAREST, FILTER_LANCZOS, FILTER_BILINEAR, FILTER_BICUBIC, FILTER_BOX, FILTER_HAMMING = 0, 1, 2, 3, 4, 5
 FILTER_NAMES = {"nearest": 0, "lanczos": 1, "bilinear": 2, "bicubic": 3, "box": 4, "hamming": 5}
@@ -109,6 +109,16 @@ class ResizeDesc(C.Structure):
 class ResizePlan(C.Structure):
     """mbn_resize_plan_t (host/mbn_envelope.h): the tile of a resize geometry and its LDS image"""
     _fields_ = [(n, C.c_int32) for n in ("kx", "ky", "tow", "toh", "tiles_x", "tiles_y", "seg_stride", "stage_off", "tmp_off", "lds_bytes")]
+
+
+class ResizePadPlan(C.Structure):
+    """mbn_resize_pad_plan_t (host/mbn_envelope.h): the table plan of a letterbox's inner image, its rectangle and its border workgroups"""
+    _fields_ = [("plan", ResizePlan)] + [(n, C.c_int32) for n in ("x", "y", "iw", "ih", "fill_rows", "fill_wgs")]
+
+
+class ResizePadDesc(C.Structure):
+    """mbn_resize_pad_desc (host/mbn_envelope.h): an image's descriptor of a letterbox launch, 96 bytes"""
+    _fields_ = [("img", ResizeDesc)] + [(n, C.c_int32) for n in ("x", "y", "iw", "ih", "tow", "tiles_x", "fill_rows", "fill_wgs")]
 
 
 class I8PwPlan(C.Structure):
@@ -193,6 +203,12 @@ def _declare_host(lib):
     lib.mbn_resize_table_plan_filter.argtypes = [C.c_int] + lib.mbn_resize_table_plan.argtypes
     lib.mbn_resize_ragged_plan_filter.argtypes = [C.c_int] + lib.mbn_resize_ragged_plan.argtypes
     lib.mbn_resize_ragged_plan_batch_filter.argtypes = [C.c_int] + lib.mbn_resize_ragged_plan_batch.argtypes
+    # the letterbox (MBN_FIT_PAD): the rectangle, and the plans of its two launches
+    lib.mbn_fit_pad.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, i32p]
+    lib.mbn_resize_pad_table_plan_filter.argtypes = [C.c_int] * 5 + [C.POINTER(ResizePadPlan)]
+    lib.mbn_resize_pad_ragged_plan_filter.argtypes = [C.c_int, C.POINTER(ResizeItem), C.c_int, C.c_int, C.POINTER(ResizePadDesc)]
+    lib.mbn_resize_pad_ragged_plan_batch_filter.argtypes = [C.c_int, C.POINTER(ResizeItem), C.c_int, C.c_int, C.c_int, C.POINTER(ResizePadDesc), i32p, i32p,
+                                                            C.POINTER(C.c_int64)]
     return lib
 
 
@@ -320,6 +336,11 @@ def load():
         lib.mbn_resize_taps_device_filter.argtypes = [vp, ci, ci, C.c_float, C.c_float, ci, vp, vp, vp]
         lib.mbn_net_set_resize_filter.argtypes = [vp, ci]
         lib.mbn_net_get_resize_filter.argtypes = [vp, C.POINTER(ci)]
+        u8p = C.POINTER(C.c_uint8)
+        lib.mbn_resizer_create_pad.argtypes = [vp, ci, ci, ci, ci, ci, u8p, C.POINTER(vp)]
+        lib.mbn_ragged_resizer_create_pad.argtypes = [vp, ci, ci, ci, ci, u8p, C.POINTER(vp)]
+        lib.mbn_net_set_pad_color.argtypes = [vp, ci, ci, ci]
+        lib.mbn_net_get_pad_color.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
         lib.mbn_graph_begin.argtypes = [vp, vp]
         lib.mbn_graph_end.argtypes = [vp, vp, C.POINTER(vp)]
         lib.mbn_graph_launch.argtypes = [vp, vp, vp]
@@ -402,6 +423,19 @@ def fit_box(in_rows, in_cols, out_rows, out_cols, fit=FIT_CROP, crop_fraction=1.
     return np.array(box[:], np.float32)
 
 
+def fit_pad(in_rows, in_cols, out_rows, out_cols, lib=None):
+    """mbn_fit_pad: (x, y, iw, ih) of the letterbox of an in_rows x in_cols image in an out_rows x out_cols canvas (PIL.ImageOps.pad, centred)."""
+    rect = (C.c_int32 * 4)()
+    _chk((lib or host_lib()).mbn_fit_pad(in_rows, in_cols, out_rows, out_cols, rect), "fit_pad(%d, %d, %d, %d)" % (in_rows, in_cols, out_rows, out_cols))
+    return tuple(rect[:])
+
+
+def _fill3(pad):
+    """A letterbox's border colour (R, G, B) as a C uint8[3]."""
+    r, g, b = (int(v) for v in pad)
+    return (C.c_uint8 * 3)(r, g, b)
+
+
 def resize_items(items):
     """A C array of mbn_resize_item from (src_offset, rows, cols, box) tuples; box None = the whole image."""
     arr = (ResizeItem * len(items))()
@@ -424,6 +458,24 @@ def resize_table_plan(in_rows, in_cols, out_rows, out_cols, box=None, lib=None, 
     _chk((lib or host_lib()).mbn_resize_table_plan_filter(filter, in_rows, in_cols, _box4(box), out_rows, out_cols, C.byref(p)),
          "resize_table_plan(%d, %d, %d, %d)" % (in_rows, in_cols, out_rows, out_cols))
     return p
+
+
+def resize_pad_table_plan(in_rows, in_cols, out_rows, out_cols, lib=None, filter=FILTER_BILINEAR) -> ResizePadPlan:
+    """mbn_resize_pad_table_plan_filter: what mbn_resizer_create_pad plans: the tile of (in_rows, in_cols) -> (ih, iw), the rectangle, the border."""
+    p = ResizePadPlan()
+    _chk((lib or host_lib()).mbn_resize_pad_table_plan_filter(filter, in_rows, in_cols, out_rows, out_cols, C.byref(p)),
+         "resize_pad_table_plan(%d, %d, %d, %d)" % (in_rows, in_cols, out_rows, out_cols))
+    return p
+
+
+def resize_pad_ragged_plan(items, out_rows, out_cols, lib=None, filter=FILTER_BILINEAR):
+    """mbn_resize_pad_ragged_plan_batch_filter: (descriptors, workgroups, dynamic LDS bytes, bytes of src reached) of a letterbox launch of `items`."""
+    arr = items if isinstance(items, C.Array) else resize_items(items)
+    desc = (ResizePadDesc * len(arr))()
+    wgs, lds, span = C.c_int32(), C.c_int32(), C.c_int64()
+    _chk((lib or host_lib()).mbn_resize_pad_ragged_plan_batch_filter(filter, arr, len(arr), out_rows, out_cols, desc, C.byref(wgs), C.byref(lds),
+                                                                      C.byref(span)), "resize_pad_ragged_plan")
+    return desc, wgs.value, lds.value, span.value
 
 
 def resize_ragged_plan(items, out_rows, out_cols, lib=None, filter=FILTER_BILINEAR):
@@ -705,14 +757,20 @@ class RaggedReadout:
 class Resizer:
     """mbn_resizer_create_filter / mbn_resize_u8: uint8 HWC images [batch][in_rows][in_cols][3] -> [batch][out_rows][out_cols][3], Pillow's 8-bit
     resize of `box` = (left, upper, right, lower) (None = the whole image) under `filter` (FILTER_*, bilinear by default), byte for byte. One
-    geometry and one filter per handle."""
+    geometry and one filter per handle. pad = (R, G, B): the letterbox form (mbn_resizer_create_pad): the whole image with its aspect ratio kept,
+    centred on an out_rows x out_cols canvas of that colour (PIL.ImageOps.pad); no box then."""
 
-    def __init__(self, ctx: Context, in_rows, in_cols, out_rows, out_cols, box=None, filter=FILTER_BILINEAR):
+    def __init__(self, ctx: Context, in_rows, in_cols, out_rows, out_cols, box=None, filter=FILTER_BILINEAR, pad=None):
         self.ctx = ctx
         self.filter = filter
         self.shape_in, self.shape_out = (in_rows, in_cols, 3), (out_rows, out_cols, 3)
         h = C.c_void_p()
-        _chk(ctx.lib.mbn_resizer_create_filter(ctx.h, filter, in_rows, in_cols, _box4(box), out_rows, out_cols, C.byref(h)), ctx.last_error())
+        if pad is not None:
+            if box is not None:
+                raise ValueError("a letterbox takes the whole image: no box")
+            _chk(ctx.lib.mbn_resizer_create_pad(ctx.h, filter, in_rows, in_cols, out_rows, out_cols, _fill3(pad), C.byref(h)), ctx.last_error())
+        else:
+            _chk(ctx.lib.mbn_resizer_create_filter(ctx.h, filter, in_rows, in_cols, _box4(box), out_rows, out_cols, C.byref(h)), ctx.last_error())
         self.h = h
         if not hasattr(ctx, "_resizers"):
             ctx._resizers = []
@@ -731,15 +789,19 @@ class RaggedResizer:
     """mbn_ragged_resizer_create / _set / mbn_resize_ragged_u8: up to max_batch uint8 HWC images, each with its own rows, cols and box, to one
     [batch][out_rows][out_cols][3] in ONE launch, Pillow's 8-bit resize under `filter` byte for byte (FILTER_NEAREST, _BOX, _BILINEAR, the default,
     or _BICUBIC; hamming and lanczos raise MbnError: EUNSUPPORTED). set() takes (src_offset, rows, cols, box) tuples (byte offsets from the src
-    pointer of run(); box None = the whole image)."""
+    pointer of run(); box None = the whole image). pad = (R, G, B): the letterbox form (mbn_ragged_resizer_create_pad): every image whole, its
+    aspect ratio kept, centred on its own out_rows x out_cols canvas of that colour; an item's box must then be None (or the whole image)."""
 
-    def __init__(self, ctx: Context, max_batch, out_rows, out_cols, filter=FILTER_BILINEAR):
+    def __init__(self, ctx: Context, max_batch, out_rows, out_cols, filter=FILTER_BILINEAR, pad=None):
         self.ctx = ctx
         self.filter = filter
         self.shape_out = (out_rows, out_cols, 3)
         self.batch = 0
         h = C.c_void_p()
-        _chk(ctx.lib.mbn_ragged_resizer_create_filter(ctx.h, filter, max_batch, out_rows, out_cols, C.byref(h)), ctx.last_error())
+        if pad is not None:
+            _chk(ctx.lib.mbn_ragged_resizer_create_pad(ctx.h, filter, max_batch, out_rows, out_cols, _fill3(pad), C.byref(h)), ctx.last_error())
+        else:
+            _chk(ctx.lib.mbn_ragged_resizer_create_filter(ctx.h, filter, max_batch, out_rows, out_cols, C.byref(h)), ctx.last_error())
         self.h = h
         if not hasattr(ctx, "_resizers"):
             ctx._resizers = []
@@ -899,7 +961,8 @@ class Net:
 
     def resize_input(self, src_ptr, batch, in_rows, in_cols, fit=FIT_CROP, crop_fraction=1.0) -> int:
         """mbn_net_resize_input: uint8 images [batch][in_rows][in_cols][3] of any size -> the net's staging buffer [batch][rows][cols][3] (its
-        device pointer is returned): the `images` of forward / classify / forward_dense / segment under set_input_u8()."""
+        device pointer is returned): the `images` of forward / classify / forward_dense / segment under set_input_u8(). fit: FIT_CROP, FIT_STRETCH
+        or FIT_PAD (the letterbox in the net's pad colour; crop_fraction is ignored)."""
         p = C.c_void_p()
         _chk(self.ctx.lib.mbn_net_resize_input(self.h, src_ptr, batch, in_rows, in_cols, fit, crop_fraction, C.byref(p)), self.ctx.last_error())
         return p.value
@@ -917,6 +980,15 @@ class Net:
     def set_resize_filter(self, filter):
         """mbn_net_set_resize_filter: FILTER_* of resize_input / resize_inputs / segment_images (bilinear until it is called)."""
         _chk(self.ctx.lib.mbn_net_set_resize_filter(self.h, int(filter)), "set_resize_filter(%r)" % (filter,))
+
+    def set_pad_color(self, r, g, b):
+        """mbn_net_set_pad_color: the border of resize_input / resize_inputs under FIT_PAD (black until it is called)."""
+        _chk(self.ctx.lib.mbn_net_set_pad_color(self.h, int(r), int(g), int(b)), "set_pad_color(%r, %r, %r)" % (r, g, b))
+
+    def pad_color(self):
+        r, g, b = C.c_int(), C.c_int(), C.c_int()
+        _chk(self.ctx.lib.mbn_net_get_pad_color(self.h, C.byref(r), C.byref(g), C.byref(b)))
+        return r.value, g.value, b.value
 
     def resize_filter(self) -> int:
         f = C.c_int()

@@ -914,6 +914,18 @@ int mbn_resizer_create(mbn_context *ctx, int in_rows, int in_cols, const float *
     return mbn_resizer_create_filter(ctx, MBN_FILTER_BILINEAR, in_rows, in_cols, box, out_rows, out_cols, r);
 }
 
+int mbn_resizer_create_pad(mbn_context *ctx, int filter, int in_rows, int in_cols, int out_rows, int out_cols, const uint8_t fill[3], mbn_resizer **r)
+{
+    if (!ctx || !r) return MBN_EINVAL;
+    *r = nullptr;
+    if (!fill) return MBN_EINVAL;
+    const int rc = mbn_resizer_build_pad(ctx, filter, in_rows, in_cols, out_rows, out_cols, fill, r);      // the plan answers for the geometry
+    if (rc != MBN_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->resizers.push_back(*r);
+    return MBN_OK;
+}
+
 int mbn_resizer_destroy(mbn_resizer *r)
 {
     if (!r) return MBN_OK;
@@ -935,23 +947,37 @@ int mbn_resize_u8(mbn_resizer *r, void *out_u8, const void *in_u8, int batch, vo
     if (batch > MBN_RESIZE_MAX_BATCH) return MBN_EUNSUPPORTED;
     mbn_context *ctx = r->ctx;
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    MBN_SPANS(ctx, { in_u8, 3.0 * batch * r->in_rows * r->in_cols, "resize_u8 in" }, { out_u8, 3.0 * batch * r->out_rows * r->out_cols, "resize_u8 out" });
+    MBN_SPANS(ctx, { in_u8, 3.0 * batch * r->in_rows * r->in_cols, "resize_u8 in" }, { out_u8, 3.0 * batch * r->canvas_rows * r->canvas_cols, "resize_u8 out" });
     Scope sc(ctx, s);
     return sc.finish(mbn_launch_u8_resize(r, s, (uint8_t *)out_u8, (const uint8_t *)in_u8, batch));
+}
+
+// fill: NULL for the plain handle, the border's colour for a letterbox
+static int ragged_resizer_create(mbn_context *ctx, int filter, int max_batch, int out_rows, int out_cols, const uint8_t *fill, mbn_ragged_resizer **r)
+{
+    if (filter < MBN_FILTER_NEAREST || filter > MBN_FILTER_HAMMING || max_batch <= 0 || out_rows <= 0 || out_cols <= 0) return MBN_EINVAL;
+    if (filter == MBN_FILTER_HAMMING || filter == MBN_FILTER_LANCZOS) return MBN_EUNSUPPORTED;       // no device form of their weights (mbn.h)
+    if (max_batch > MBN_RESIZE_MAX_BATCH || out_rows > MBN_RESIZE_MAX_OUT || out_cols > MBN_RESIZE_MAX_OUT) return MBN_EUNSUPPORTED;
+    const int rc = mbn_ragged_resizer_build(ctx, filter, max_batch, out_rows, out_cols, fill, r);
+    if (rc != MBN_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->ragged_resizers.push_back(*r);
+    return MBN_OK;
 }
 
 int mbn_ragged_resizer_create_filter(mbn_context *ctx, int filter, int max_batch, int out_rows, int out_cols, mbn_ragged_resizer **r)
 {
     if (!ctx || !r) return MBN_EINVAL;
     *r = nullptr;
-    if (filter < MBN_FILTER_NEAREST || filter > MBN_FILTER_HAMMING || max_batch <= 0 || out_rows <= 0 || out_cols <= 0) return MBN_EINVAL;
-    if (filter == MBN_FILTER_HAMMING || filter == MBN_FILTER_LANCZOS) return MBN_EUNSUPPORTED;       // no device form of their weights (mbn.h)
-    if (max_batch > MBN_RESIZE_MAX_BATCH || out_rows > MBN_RESIZE_MAX_OUT || out_cols > MBN_RESIZE_MAX_OUT) return MBN_EUNSUPPORTED;
-    const int rc = mbn_ragged_resizer_build(ctx, filter, max_batch, out_rows, out_cols, r);
-    if (rc != MBN_OK) return rc;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->ragged_resizers.push_back(*r);
-    return MBN_OK;
+    return ragged_resizer_create(ctx, filter, max_batch, out_rows, out_cols, nullptr, r);
+}
+
+int mbn_ragged_resizer_create_pad(mbn_context *ctx, int filter, int max_batch, int out_rows, int out_cols, const uint8_t fill[3], mbn_ragged_resizer **r)
+{
+    if (!ctx || !r) return MBN_EINVAL;
+    *r = nullptr;
+    if (!fill) return MBN_EINVAL;
+    return ragged_resizer_create(ctx, filter, max_batch, out_rows, out_cols, fill, r);
 }
 
 int mbn_ragged_resizer_create(mbn_context *ctx, int max_batch, int out_rows, int out_cols, mbn_ragged_resizer **r)

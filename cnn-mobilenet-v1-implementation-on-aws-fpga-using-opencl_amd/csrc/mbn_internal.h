@@ -28,6 +28,12 @@ struct mbn_resizer {
     int filter = MBN_FILTER_BILINEAR;            // MBN_FILTER_*: NEAREST runs the gather kernel on ix [out_cols], iy [out_rows] in `tables`
     mbn_resize_plan_t plan = {};                 // mbn_resize_table_plan; kx, ky = taps per output column / row (the tables' row length)
     void *tables = nullptr;                      // device: fx, cx [out_cols], fy, cy [out_rows], wx [out_cols][kx], wy [out_rows][ky], int32
+    // what `out` holds per image: out_rows x out_cols, except under mbn_resizer_create_pad, where out_rows x out_cols is the inner image (ih x iw)
+    // at (pad_x, pad_y) of this canvas and `fill` is everywhere else (fill_rows, fill_wgs: mbn_resize_pad_plan_t)
+    int canvas_rows = 0, canvas_cols = 0;
+    bool pad = false;
+    int pad_x = 0, pad_y = 0, fill_rows = 0, fill_wgs = 0;
+    uint8_t fill[3] = { 0, 0, 0 };
 };
 
 // mbn_ragged_resizer_create's handle (mbn_u8_resize_ragged.hip): the descriptors of up to max_batch images, on the device and pinned on the host
@@ -39,7 +45,9 @@ struct mbn_ragged_resizer {
     int total_wgs = 0, lds_bytes = 0;            // its launch
     int generation = 0;                          // counts the sets: a captured launch replayed after another set does nothing
     int64_t src_span = 0;                        // bytes of src its images reach
-    void *dev = nullptr, *host = nullptr;        // 64-byte head + mbn_resize_desc [max_batch]
+    bool pad = false;                            // mbn_ragged_resizer_create_pad: a letterbox into out_rows x out_cols canvases of `fill`
+    uint8_t fill[3] = { 0, 0, 0 };
+    void *dev = nullptr, *host = nullptr;        // 64-byte head + mbn_resize_desc [max_batch] (pad: mbn_resize_pad_desc [max_batch])
     hipEvent_t done = nullptr;                   // behind the last upload or launch: the next set waits for it
 };
 
@@ -274,11 +282,12 @@ int mbn_ragged_readout_plan(mbn_ragged_readout *r, hipStream_t s, int rows, int 
 int mbn_launch_f32_resample_argmax_ragged(mbn_ragged_readout *r, hipStream_t s, int32_t *labels, float *score, const float *logits);
 // resize front-end (mbn_u8_resize.hip): the geometry is inside mbn_resize_envelope; build uploads the tables (blocking), release frees them
 int mbn_resizer_build(mbn_context *ctx, int filter, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r);
+int mbn_resizer_build_pad(mbn_context *ctx, int filter, int in_rows, int in_cols, int out_rows, int out_cols, const uint8_t fill[3], mbn_resizer **r);
 void mbn_resizer_release(mbn_resizer *r);
 int mbn_launch_u8_resize(const mbn_resizer *r, hipStream_t s, uint8_t *out, const uint8_t *in, int batch);
 // ragged resize (mbn_u8_resize_ragged.hip): build allocates, plan checks and plans a batch and enqueues the descriptors' upload (waits for the handle's
 // earlier work first), the launch is asynchronous; taps: the kernel's tap function for one axis into device tables
-int mbn_ragged_resizer_build(mbn_context *ctx, int filter, int max_batch, int out_rows, int out_cols, mbn_ragged_resizer **r);
+int mbn_ragged_resizer_build(mbn_context *ctx, int filter, int max_batch, int out_rows, int out_cols, const uint8_t *fill, mbn_ragged_resizer **r);
 void mbn_ragged_resizer_release(mbn_ragged_resizer *r);
 int mbn_ragged_resizer_plan(mbn_ragged_resizer *r, hipStream_t s, const mbn_resize_item *items, int batch);
 int mbn_launch_u8_resize_ragged(mbn_ragged_resizer *r, hipStream_t s, uint8_t *out, const uint8_t *src);

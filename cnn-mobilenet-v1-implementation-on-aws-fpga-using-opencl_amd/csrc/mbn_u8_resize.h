@@ -139,4 +139,50 @@ __device__ __forceinline__ void resize_nearest_rows(uint8_t *__restrict__ dst, s
     }
 }
 
+// The letterbox's border (mbn_fit_pad, include/mbn.h): the fill colour as the three dwords an RGB run can start with. w[c] holds channels c, c + 1, c + 2, c
+// (mod 3) from its low byte up: what the four bytes at a position of channel c are, and its low byte is channel c itself
+struct ResizeFill {
+    uint32_t w[3];
+};
+
+inline ResizeFill resize_fill_of(const uint8_t rgb[3])
+{
+    ResizeFill f;
+    for (int c = 0; c < 3; c++)
+        f.w[c] = (uint32_t)rgb[c] | (uint32_t)rgb[(c + 1) % 3] << 8 | (uint32_t)rgb[(c + 2) % 3] << 16 | (uint32_t)rgb[c] << 24;
+    return f;
+}
+
+// nb bytes of fill at d, byte 0 a pixel's first channel (every border run starts with a pixel). The store shape of resize_nearest_rows: bytewise up to
+// the first 4-byte boundary of the ADDRESS, a dword per lane from there, bytewise for the rest, so any byte pointer works and no byte beside the run is
+// touched. One wave; nothing is read
+__device__ __forceinline__ void resize_fill_run(uint8_t *__restrict__ d, int nb, const ResizeFill &f, int lane)
+{
+    auto word = [&](int e) -> uint32_t { const int c = e % 3; return c == 0 ? f.w[0] : c == 1 ? f.w[1] : f.w[2]; };
+    const int off = (int)((uintptr_t)d & 3);
+    const int head = min(nb, (4 - off) & 3), body = (nb - head) >> 2, tail0 = head + 4 * body;
+    if (lane < head) d[lane] = (uint8_t)word(lane);
+    for (int i = lane; i < body; i += 64) *reinterpret_cast<uint32_t *>(d + head + 4 * i) = word(head + 4 * i);
+    if (tail0 + lane < nb) d[tail0 + lane] = (uint8_t)word(tail0 + lane);
+}
+
+// Border rows k0 .. k0 + MBN_RESIZE_FILL_ROWS - 1 (below fill_rows) of one oh x ow canvas around the rectangle (x, y, iw, ih), which lies inside it
+// (mbn_fit_pad): wave v takes the rows k0 + v, k0 + v + 4, ... A row outside the rectangle is one run of ow pixels, a row through it the runs left
+// and right of it. What is inside the rectangle is the tiles' to write
+__device__ __forceinline__ void resize_fill_rows(uint8_t *__restrict__ canvas, int ow, int x, int y, int iw, int ih, int k0, int fill_rows,
+                                                 const ResizeFill &f, int lane, int wave)
+{
+    const int kn = min(k0 + MBN_RESIZE_FILL_ROWS, fill_rows);
+    for (int k = k0 + wave; k < kn; k += MBN_RESIZE_WAVES) {
+        const int r = MBN_RESIZE_FILL_ROW(k, y, iw, ih, ow);
+        uint8_t *d = canvas + (size_t)r * ow * 3;
+        if (r < y || r >= y + ih) {
+            resize_fill_run(d, ow * 3, f, lane);
+        } else {
+            resize_fill_run(d, x * 3, f, lane);
+            resize_fill_run(d + (x + iw) * 3, (ow - x - iw) * 3, f, lane);
+        }
+    }
+}
+
 }   // namespace

@@ -12,6 +12,28 @@
 
 namespace {
 
+// Where the oh x ow outputs of an image go: out_img bytes from one image's first output to the next one's, out_ld from a row to the next, the first
+// one out_org bytes into the image's part of `out` (PAD only). oh * ow * 3, ow * 3 and 0, what the kernels used to compute, except under a letterbox
+// (mbn_resizer_create_pad): there an image's part of `out` is a canvas_rows x canvas_cols canvas, the outputs are its rectangle at (x, y), and the PAD
+// instantiations of the kernels run fill_wgs more workgroups per image behind the `tiles` that resize, which write the canvas outside the rectangle
+// (resize_fill_rows: no taps, no LDS, no barrier; they touch no byte the tiles write)
+struct ResizeDest {
+    size_t out_img, out_org;
+    int out_ld;
+    int tiles;                               // grid.x of the plain launch
+    int canvas_cols, x, y, fill_rows;        // letterbox only
+    ResizeFill fill;
+};
+
+// letterbox: true when this workgroup was one of the border's (and is done); the whole workgroup takes the same way
+__device__ __forceinline__ bool resize_border(const ResizeDest &d, uint8_t *out, int iw, int ih, int lane, int wave)
+{
+    const int b = (int)blockIdx.x - d.tiles;
+    if (b < 0) return false;
+    resize_fill_rows(out + (size_t)blockIdx.y * d.out_img, d.canvas_cols, d.x, d.y, iw, ih, b * MBN_RESIZE_FILL_ROWS, d.fill_rows, d.fill, lane, wave);
+    return true;
+}
+
 struct ResizeArgs {
     uint8_t *out;
     const uint8_t *in;
@@ -19,13 +41,17 @@ struct ResizeArgs {
     int h, w, oh, ow, kx, ky;
     int tow, toh, tiles_x;
     int seg_stride, stage_off, tmp_off;      // mbn_resize_plan_t
+    ResizeDest d;
 };
 
+template <bool PAD>
 __global__ __launch_bounds__(256, 8) void resize_u8(const ResizeArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_mem[];
     int32_t *s_wx = reinterpret_cast<int32_t *>(s_mem);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if constexpr (PAD)
+        if (resize_border(a.d, a.out, a.ow, a.oh, lane, wave)) return;       // before anything indexes the tables with a tile that is none
     const int ty = (int)blockIdx.x / a.tiles_x, tx = (int)blockIdx.x - ty * a.tiles_x;
     const int ox0 = tx * a.tow, oxn = min(a.tow, a.ow - ox0), oy0 = ty * a.toh, oyn = min(a.toh, a.oh - oy0);
     const int row_e = oxn * 3;                                   // horizontal sums of a source row
@@ -35,7 +61,7 @@ __global__ __launch_bounds__(256, 8) void resize_u8(const ResizeArgs a)
     const int nrows = y1 - y0, nb = (xs1 - xs0) * 3;
     const size_t img = (size_t)blockIdx.y;
     const uint8_t *__restrict__ src = a.in + img * ((size_t)a.h * a.w * 3);
-    uint8_t *__restrict__ dst = a.out + img * ((size_t)a.oh * a.ow * 3);
+    uint8_t *__restrict__ dst = a.out + img * a.d.out_img + (PAD ? a.d.out_org : 0);
     uint8_t *s_row = s_mem + a.stage_off + wave * a.seg_stride;
     uint8_t *s_tmp = s_mem + a.tmp_off;
     const int tmp_ld = a.tow * 3;
@@ -49,7 +75,7 @@ __global__ __launch_bounds__(256, 8) void resize_u8(const ResizeArgs a)
         resize_row_sums(s_tmp + r * tmp_ld, s_seg, s_wx, lo, wofs, a.kx, row_e, lane);
     }
     __syncthreads();                                             // the window is complete
-    resize_vertical(dst + ((size_t)oy0 * a.ow + ox0) * 3, (size_t)a.ow * 3, s_tmp, tmp_ld, oyn, row_e, lane, wave, [&](int oy, int &f, int &n) {
+    resize_vertical(dst + (size_t)oy0 * a.d.out_ld + ox0 * 3, (size_t)a.d.out_ld, s_tmp, tmp_ld, oyn, row_e, lane, wave, [&](int oy, int &f, int &n) {
         f = a.fy[oy0 + oy] - y0;
         n = a.cy[oy0 + oy];
         return a.wy + (size_t)(oy0 + oy) * a.ky;
@@ -63,16 +89,20 @@ struct NearestArgs {
     const uint8_t *in;
     const int32_t *ix, *iy;
     int h, w, oh, ow;
+    ResizeDest d;
 };
 
+template <bool PAD>
 __global__ __launch_bounds__(256) void resize_nearest_u8(const NearestArgs a)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if constexpr (PAD)
+        if (resize_border(a.d, a.out, a.ow, a.oh, lane, wave)) return;
     const int oy0 = (int)blockIdx.x * MBN_RESIZE_WAVES, oyn = min(MBN_RESIZE_WAVES, a.oh - oy0);
     const size_t img = (size_t)blockIdx.y;
     const uint8_t *__restrict__ src = a.in + img * ((size_t)a.h * a.w * 3);
-    uint8_t *__restrict__ dst = a.out + img * ((size_t)a.oh * a.ow * 3);
-    resize_nearest_rows(dst + (size_t)oy0 * a.ow * 3, (size_t)a.ow * 3, src, a.w, oyn, a.ow * 3, lane, wave,
+    uint8_t *__restrict__ dst = a.out + img * a.d.out_img + (PAD ? a.d.out_org : 0);
+    resize_nearest_rows(dst + (size_t)oy0 * a.d.out_ld, (size_t)a.d.out_ld, src, a.w, oyn, a.ow * 3, lane, wave,
                         [&](int ox) { return min(max(a.ix[ox], 0), a.w - 1); }, [&](int oy) { return min(max(a.iy[oy0 + oy], 0), a.h - 1); });
 }
 
@@ -128,6 +158,7 @@ int mbn_resizer_build(mbn_context *ctx, int filter, int in_rows, int in_cols, co
     r->ctx = ctx;
     r->filter = filter;
     r->in_rows = in_rows; r->in_cols = in_cols; r->out_rows = out_rows; r->out_cols = out_cols;
+    r->canvas_rows = out_rows; r->canvas_cols = out_cols;
     r->plan = p;
     (void)hipSetDevice(ctx->device);
     hipError_t e = hipMalloc(&r->tables, n32 * sizeof(int32_t));
@@ -141,23 +172,51 @@ int mbn_resizer_build(mbn_context *ctx, int filter, int in_rows, int in_cols, co
     return MBN_OK;
 }
 
+// The letterbox: the handle of the whole image -> ih x iw, and where that lies in the out_rows x out_cols canvas. fill is non-null (the caller has checked)
+int mbn_resizer_build_pad(mbn_context *ctx, int filter, int in_rows, int in_cols, int out_rows, int out_cols, const uint8_t fill[3], mbn_resizer **out)
+{
+    mbn_resize_pad_plan_t pp;
+    int rc = mbn_resize_pad_table_plan_filter(filter, in_rows, in_cols, out_rows, out_cols, &pp);
+    if (rc != MBN_OK) return rc;
+    rc = mbn_resizer_build(ctx, filter, in_rows, in_cols, nullptr, pp.ih, pp.iw, out);
+    if (rc != MBN_OK) return rc;
+    mbn_resizer *r = *out;
+    r->canvas_rows = out_rows; r->canvas_cols = out_cols;
+    r->pad = true;
+    r->pad_x = pp.x; r->pad_y = pp.y; r->fill_rows = pp.fill_rows; r->fill_wgs = pp.fill_wgs;
+    memcpy(r->fill, fill, 3);
+    return MBN_OK;
+}
+
 void mbn_resizer_release(mbn_resizer *r)
 {
     if (r->tables) (void)hipFree(r->tables);
     delete r;
 }
 
-// in [batch][in_rows][in_cols][3] -> out [batch][out_rows][out_cols][3]; batch in 1..MBN_RESIZE_MAX_BATCH, pointers non-null (the caller has checked)
+// in [batch][in_rows][in_cols][3] -> out [batch][canvas_rows][canvas_cols][3]; batch in 1..MBN_RESIZE_MAX_BATCH, pointers non-null (the caller has
+// checked). A letterbox handle: the PAD instantiation of the same kernel, with the canvas's strides and fill_wgs more workgroups per image
 int mbn_launch_u8_resize(const mbn_resizer *r, hipStream_t s, uint8_t *out, const uint8_t *in, int batch)
 {
     const mbn_resize_plan_t &p = r->plan;
     const int32_t *t = (const int32_t *)r->tables;
-    if (r->filter == MBN_FILTER_NEAREST) {
+    const bool nearest = r->filter == MBN_FILTER_NEAREST;
+    ResizeDest d;
+    d.out_img = (size_t)r->canvas_rows * r->canvas_cols * 3;
+    d.out_org = ((size_t)r->pad_y * r->canvas_cols + r->pad_x) * 3;
+    d.out_ld = r->canvas_cols * 3;
+    d.tiles = nearest ? (r->out_rows + MBN_RESIZE_WAVES - 1) / MBN_RESIZE_WAVES : p.tiles_x * p.tiles_y;
+    d.canvas_cols = r->canvas_cols; d.x = r->pad_x; d.y = r->pad_y; d.fill_rows = r->fill_rows;
+    d.fill = resize_fill_of(r->fill);
+    const dim3 grid((unsigned)(d.tiles + r->fill_wgs), (unsigned)batch), block(256);
+    if (nearest) {
         NearestArgs n;
         n.out = out; n.in = in;
         n.ix = t; n.iy = t + r->out_cols;
         n.h = r->in_rows; n.w = r->in_cols; n.oh = r->out_rows; n.ow = r->out_cols;
-        hipLaunchKernelGGL(resize_nearest_u8, dim3((unsigned)((r->out_rows + MBN_RESIZE_WAVES - 1) / MBN_RESIZE_WAVES), (unsigned)batch), dim3(256), 0, s, n);
+        n.d = d;
+        if (r->pad) hipLaunchKernelGGL(resize_nearest_u8<true>, grid, block, 0, s, n);
+        else hipLaunchKernelGGL(resize_nearest_u8<false>, grid, block, 0, s, n);
         return MBN_OK;
     }
     ResizeArgs a;
@@ -167,6 +226,8 @@ int mbn_launch_u8_resize(const mbn_resizer *r, hipStream_t s, uint8_t *out, cons
     a.h = r->in_rows; a.w = r->in_cols; a.oh = r->out_rows; a.ow = r->out_cols; a.kx = p.kx; a.ky = p.ky;
     a.tow = p.tow; a.toh = p.toh; a.tiles_x = p.tiles_x;
     a.seg_stride = p.seg_stride; a.stage_off = p.stage_off; a.tmp_off = p.tmp_off;
-    hipLaunchKernelGGL(resize_u8, dim3((unsigned)(p.tiles_x * p.tiles_y), (unsigned)batch), dim3(256), (size_t)p.lds_bytes, s, a);
+    a.d = d;
+    if (r->pad) hipLaunchKernelGGL(resize_u8<true>, grid, block, (size_t)p.lds_bytes, s, a);
+    else hipLaunchKernelGGL(resize_u8<false>, grid, block, (size_t)p.lds_bytes, s, a);
     return MBN_OK;
 }

@@ -150,6 +150,37 @@ int mbn_resize_window_filter(int filter, int in_size, float b0, float b1, int ou
 int mbn_resize_ragged_plan_filter(int filter, const mbn_resize_item *item, int out_rows, int out_cols, mbn_resize_desc *d);
 int mbn_resize_ragged_plan_batch_filter(int filter, const mbn_resize_item *items, int batch, int out_rows, int out_cols, mbn_resize_desc *desc,
                                         int32_t *total_wgs, int32_t *lds_bytes, int64_t *src_span);
+/* The letterbox (mbn_fit_pad, include/mbn.h): the whole image resized to ih x iw into the rectangle (x, y, iw, ih) of an out_rows x out_cols canvas,
+ * `fill` elsewhere. The tiles are those of the plain resize (H, W) -> (ih, iw), laid over the rectangle; the border is written by workgroups of its own,
+ * each MBN_RESIZE_FILL_ROWS border rows of one canvas, a wave a row at a time. Border row k (of fill_rows) is canvas row k where the rectangle is
+ * narrower than the canvas (every row has a border then) and otherwise the k-th row outside it: k above the rectangle, k + ih below it
+ * (MBN_RESIZE_FILL_ROW). fill_wgs = ceil(fill_rows / MBN_RESIZE_FILL_ROWS): none where the aspect ratios agree. */
+#define MBN_RESIZE_FILL_ROWS 32
+#define MBN_RESIZE_FILL_ROW(k, y, iw, ih, ow) ((iw) < (ow) || (k) < (y) ? (k) : (k) + (ih))
+/* the table form (mbn_resizer_create_pad): mbn_resize_table_plan_filter of (H, W) -> (ih, iw), the whole image, and the rectangle. Whatever
+ * mbn_fit_pad and that plan answer */
+typedef struct mbn_resize_pad_plan_t {
+    mbn_resize_plan_t plan;          /* of the inner image: tow = MBN_RESIZE_TOW(iw), tiles_x * tiles_y tiles per image */
+    int32_t x, y, iw, ih;            /* mbn_fit_pad */
+    int32_t fill_rows, fill_wgs;     /* border rows of a canvas and the workgroups that write them: grid.x is tiles_x * tiles_y + fill_wgs */
+} mbn_resize_pad_plan_t;
+int mbn_resize_pad_table_plan_filter(int filter, int in_rows, int in_cols, int out_rows, int out_cols, mbn_resize_pad_plan_t *plan);
+/* the ragged form (mbn_ragged_resizer_create_pad): the descriptor of one image in device memory, 96 bytes. img is mbn_resize_ragged_plan_filter of the
+ * item against ih x iw, field for field (kx .. lds_bytes as for a plain ragged launch whose output is ih x iw); its wg0 is the image's first workgroup
+ * of the pad launch, which gives the image tiles_x * tiles_y tile workgroups and then fill_wgs border workgroups. The inner size is the image's own, so
+ * tow and tiles_x, which a plain launch has once per handle, are here too */
+typedef struct mbn_resize_pad_desc {
+    mbn_resize_desc img;
+    int32_t x, y, iw, ih;            /* mbn_fit_pad of (rows, cols) into the handle's canvas */
+    int32_t tow, tiles_x;            /* MBN_RESIZE_TOW(iw), ceil(iw / tow) */
+    int32_t fill_rows, fill_wgs;     /* as in mbn_resize_pad_plan_t */
+} mbn_resize_pad_desc;
+/* one image (wg0 = 0): MBN_EINVAL for a negative offset, a box that is not the whole image or what mbn_fit_pad refuses, else what
+ * mbn_resize_ragged_plan_filter answers for (rows, cols) -> (ih, iw) */
+int mbn_resize_pad_ragged_plan_filter(int filter, const mbn_resize_item *item, int out_rows, int out_cols, mbn_resize_pad_desc *d);
+/* a batch, as mbn_resize_ragged_plan_batch_filter: the launch's workgroups count every image's tiles and border workgroups */
+int mbn_resize_pad_ragged_plan_batch_filter(int filter, const mbn_resize_item *items, int batch, int out_rows, int out_cols, mbn_resize_pad_desc *desc,
+                                            int32_t *total_wgs, int32_t *lds_bytes, int64_t *src_span);
 
 /* int8 pointwise / FC (mbn_i8.hip): the whole launch arithmetic of mbn_launch_i8_pointwise, which launches what this says and
  * computes nothing of its own. Two forms: the persistent one (i8_pw2_k<ks, 512, out_f32>: a wave keeps a 32-column chunk's filter

@@ -54,6 +54,9 @@ struct mbn_net {
     float rs_fraction;
     int resize_filter;         /* mbn_net_set_resize_filter: MBN_FILTER_* of both resizers (MBN_FILTER_BILINEAR until it is called) */
     int ragged_filter;         /* the filter `ragged` was made for */
+    uint8_t pad_color[3];      /* mbn_net_set_pad_color: the border of MBN_FIT_PAD, R, G, B (black until it is called) */
+    uint8_t rs_color[3], ragged_color[3];       /* the colour `resizer` / `ragged` was made for, when it is a letterbox */
+    int ragged_pad;            /* `ragged` is a letterbox handle (mbn_ragged_resizer_create_pad) */
     void *resize_buf;          /* mbn_net_resize_input / _inputs: [max_batch][rows][cols][3] uint8, the resized images */
     mbn_ragged_resizer *ragged;     /* mbn_net_resize_inputs: one ragged resizer of max_batch images, made on the first call */
     mbn_resize_item *ragged_items;  /* ... and the items it is set from, [max_batch] */
@@ -973,22 +976,39 @@ int mbn_net_get_resize_filter(const mbn_net *net, int *filter)
     return MBN_OK;
 }
 
+int mbn_net_set_pad_color(mbn_net *net, int r, int g, int b)
+{
+    if (!net || r < 0 || r > 255 || g < 0 || g > 255 || b < 0 || b > 255) return MBN_EINVAL;
+    net->pad_color[0] = (uint8_t)r; net->pad_color[1] = (uint8_t)g; net->pad_color[2] = (uint8_t)b;     /* a kept letterbox of another colour is rebuilt */
+    return MBN_OK;
+}
+
+int mbn_net_get_pad_color(const mbn_net *net, int *r, int *g, int *b)
+{
+    if (!net || !r || !g || !b) return MBN_EINVAL;
+    *r = net->pad_color[0]; *g = net->pad_color[1]; *b = net->pad_color[2];
+    return MBN_OK;
+}
+
 int mbn_net_resize_input(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, float crop_fraction, void **images_u8)
 {
     if (!net || !src_u8 || !images_u8 || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
     *images_u8 = NULL;
     const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols;
-    if (fit == MBN_FIT_STRETCH) crop_fraction = 1.0f;
+    if (fit == MBN_FIT_STRETCH || fit == MBN_FIT_PAD) crop_fraction = 1.0f;
     if (!net->resizer || net->rs_rows != in_rows || net->rs_cols != in_cols || net->rs_fit != fit || net->rs_fraction != crop_fraction ||
-        net->rs_filter != net->resize_filter) {
+        net->rs_filter != net->resize_filter || (fit == MBN_FIT_PAD && memcmp(net->rs_color, net->pad_color, 3) != 0)) {
         float box[4];
         mbn_resizer *r = NULL;
         int rc = mbn_fit_box(in_rows, in_cols, rows, cols, fit, crop_fraction, box);
-        if (rc == MBN_OK) rc = mbn_resizer_create_filter(net->ctx, net->resize_filter, in_rows, in_cols, box, rows, cols, &r);
+        if (rc == MBN_OK)
+            rc = fit == MBN_FIT_PAD ? mbn_resizer_create_pad(net->ctx, net->resize_filter, in_rows, in_cols, rows, cols, net->pad_color, &r)
+                                    : mbn_resizer_create_filter(net->ctx, net->resize_filter, in_rows, in_cols, box, rows, cols, &r);
         if (rc != MBN_OK) return rc;                          /* the resizer of the previous geometry stays */
         if (net->resizer) mbn_resizer_destroy(net->resizer);  /* waits for the stream: a resize still running reads its tables */
         net->resizer = r;
         net->rs_rows = in_rows; net->rs_cols = in_cols; net->rs_fit = fit; net->rs_fraction = crop_fraction; net->rs_filter = net->resize_filter;
+        memcpy(net->rs_color, net->pad_color, 3);
     }
     if (!net->resize_buf) {
         int rc = mbn_alloc(net->ctx, (size_t)net->max_batch * rows * cols * 3, &net->resize_buf);
@@ -1005,7 +1025,8 @@ int mbn_net_resize_inputs(mbn_net *net, const void *src_u8, const int64_t *offse
     if (!net || !src_u8 || !offsets || !in_rows || !in_cols || !images_u8 || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
     *images_u8 = NULL;
     const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols;
-    if (fit == MBN_FIT_STRETCH) crop_fraction = 1.0f;
+    const int pad = fit == MBN_FIT_PAD;
+    if (fit == MBN_FIT_STRETCH || pad) crop_fraction = 1.0f;
     if (!net->ragged_items) {
         net->ragged_items = malloc((size_t)net->max_batch * sizeof(mbn_resize_item));
         if (!net->ragged_items) return MBN_ENOMEM;
@@ -1018,13 +1039,16 @@ int mbn_net_resize_inputs(mbn_net *net, const void *src_u8, const int64_t *offse
         const int rc = mbn_fit_box(in_rows[i], in_cols[i], rows, cols, fit, crop_fraction, it->box);
         if (rc != MBN_OK) return rc;
     }
-    if (!net->ragged || net->ragged_filter != net->resize_filter) {
+    if (!net->ragged || net->ragged_filter != net->resize_filter || net->ragged_pad != pad || (pad && memcmp(net->ragged_color, net->pad_color, 3) != 0)) {
         mbn_ragged_resizer *r = NULL;                         /* HAMMING / LANCZOS: MBN_EUNSUPPORTED, and the resizer of the previous filter stays */
-        const int rc = mbn_ragged_resizer_create_filter(net->ctx, net->resize_filter, net->max_batch, rows, cols, &r);
+        const int rc = pad ? mbn_ragged_resizer_create_pad(net->ctx, net->resize_filter, net->max_batch, rows, cols, net->pad_color, &r)
+                           : mbn_ragged_resizer_create_filter(net->ctx, net->resize_filter, net->max_batch, rows, cols, &r);
         if (rc != MBN_OK) return rc;
         if (net->ragged) mbn_ragged_resizer_destroy(net->ragged);       /* waits for its last launch */
         net->ragged = r;
         net->ragged_filter = net->resize_filter;
+        net->ragged_pad = pad;
+        memcpy(net->ragged_color, net->pad_color, 3);
     }
     if (!net->resize_buf) {
         const int rc = mbn_alloc(net->ctx, (size_t)net->max_batch * rows * cols * 3, &net->resize_buf);

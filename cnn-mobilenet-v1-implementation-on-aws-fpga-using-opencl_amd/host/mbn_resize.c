@@ -88,7 +88,7 @@ int mbn_fit_box(int in_rows, int in_cols, int out_rows, int out_cols, int fit, f
 {
     if (!box || in_rows <= 0 || in_cols <= 0 || out_rows <= 0 || out_cols <= 0) return MBN_EINVAL;
     const double W = in_cols, H = in_rows;
-    if (fit == MBN_FIT_STRETCH) {
+    if (fit == MBN_FIT_STRETCH || fit == MBN_FIT_PAD) {        /* a letterbox resizes the whole image as well (mbn_fit_pad says where to) */
         box[0] = 0.0f; box[1] = 0.0f; box[2] = (float)in_cols; box[3] = (float)in_rows;
         return MBN_OK;
     }
@@ -101,6 +101,25 @@ int mbn_fit_box(int in_rows, int in_cols, int out_rows, int out_cols, int fit, f
     if (box[1] < 0.0f) box[1] = 0.0f;
     if (box[2] > (float)in_cols) box[2] = (float)in_cols;
     if (box[3] > (float)in_rows) box[3] = (float)in_rows;
+    return MBN_OK;
+}
+
+/* PIL.ImageOps.contain + pad, centering (0.5, 0.5) (include/mbn.h): doubles throughout, the quotient formed before the product, rint in the default
+ * rounding mode = Python's round (half to even) */
+int mbn_fit_pad(int in_rows, int in_cols, int out_rows, int out_cols, int32_t rect[4])
+{
+    if (!rect || in_rows <= 0 || in_cols <= 0 || out_rows <= 0 || out_cols <= 0) return MBN_EINVAL;
+    const double W = in_cols, H = in_rows, ow = out_cols, oh = out_rows;
+    const double im_ratio = W / H, dest_ratio = ow / oh;
+    double iw = ow, ih = oh, x = 0.0, y = 0.0;
+    if (im_ratio != dest_ratio) {
+        if (im_ratio > dest_ratio) ih = rint(H / W * ow);
+        else iw = rint(W / H * oh);
+    }
+    if (iw < 1.0 || ih < 1.0 || iw > ow || ih > oh) return MBN_EINVAL;       /* above the canvas: no ratio gives it; the kernels' bounds rest on it */
+    if (iw != ow) x = rint((ow - iw) * 0.5);
+    else if (ih != oh) y = rint((oh - ih) * 0.5);
+    rect[0] = (int32_t)x; rect[1] = (int32_t)y; rect[2] = (int32_t)iw; rect[3] = (int32_t)ih;
     return MBN_OK;
 }
 
@@ -265,4 +284,68 @@ int mbn_resize_ragged_plan_batch(const mbn_resize_item *items, int batch, int ou
                                  int32_t *lds_bytes, int64_t *src_span)
 {
     return mbn_resize_ragged_plan_batch_filter(MBN_FILTER_BILINEAR, items, batch, out_rows, out_cols, desc, total_wgs, lds_bytes, src_span);
+}
+
+/* ---- the letterbox: the plans above for (H, W) -> (ih, iw), and the border's workgroups (mbn_envelope.h) */
+
+static void pad_border(const int32_t rect[4], int out_rows, int out_cols, int32_t *fill_rows, int32_t *fill_wgs)
+{
+    *fill_rows = rect[2] < out_cols ? out_rows : out_rows - rect[3];
+    *fill_wgs = (*fill_rows + MBN_RESIZE_FILL_ROWS - 1) / MBN_RESIZE_FILL_ROWS;
+}
+
+int mbn_resize_pad_table_plan_filter(int filter, int in_rows, int in_cols, int out_rows, int out_cols, mbn_resize_pad_plan_t *plan)
+{
+    if (!plan || !filter_ok(filter)) return MBN_EINVAL;
+    int32_t rect[4];
+    int rc = mbn_fit_pad(in_rows, in_cols, out_rows, out_cols, rect);
+    if (rc != MBN_OK) return rc;
+    if (out_rows > MBN_RESIZE_MAX_OUT || out_cols > MBN_RESIZE_MAX_OUT) return MBN_EUNSUPPORTED;        /* the canvas: a batch of them is grid.y x fill_wgs */
+    rc = mbn_resize_table_plan_filter(filter, in_rows, in_cols, NULL, rect[3], rect[2], &plan->plan);
+    if (rc != MBN_OK) return rc;
+    plan->x = rect[0]; plan->y = rect[1]; plan->iw = rect[2]; plan->ih = rect[3];
+    pad_border(rect, out_rows, out_cols, &plan->fill_rows, &plan->fill_wgs);
+    return MBN_OK;
+}
+
+int mbn_resize_pad_ragged_plan_filter(int filter, const mbn_resize_item *it, int out_rows, int out_cols, mbn_resize_pad_desc *d)
+{
+    if (!it || !d || !filter_ok(filter)) return MBN_EINVAL;
+    if (filter == MBN_FILTER_HAMMING || filter == MBN_FILTER_LANCZOS) return MBN_EUNSUPPORTED;
+    /* a pad of a box is not built: the item says the whole image, as mbn_fit_box(MBN_FIT_PAD) gives it */
+    if (!(it->box[0] == 0.0f) || !(it->box[1] == 0.0f) || !(it->box[2] == (float)it->cols) || !(it->box[3] == (float)it->rows)) return MBN_EINVAL;
+    int32_t rect[4];
+    int rc = mbn_fit_pad(it->rows, it->cols, out_rows, out_cols, rect);
+    if (rc != MBN_OK) return rc;
+    if (out_rows > MBN_RESIZE_MAX_OUT || out_cols > MBN_RESIZE_MAX_OUT) return MBN_EUNSUPPORTED;
+    rc = mbn_resize_ragged_plan_filter(filter, it, rect[3], rect[2], &d->img);
+    if (rc != MBN_OK) return rc;
+    d->x = rect[0]; d->y = rect[1]; d->iw = rect[2]; d->ih = rect[3];
+    d->tow = MBN_RESIZE_TOW(d->iw);
+    d->tiles_x = (d->iw + d->tow - 1) / d->tow;
+    pad_border(rect, out_rows, out_cols, &d->fill_rows, &d->fill_wgs);
+    return MBN_OK;
+}
+
+int mbn_resize_pad_ragged_plan_batch_filter(int filter, const mbn_resize_item *items, int batch, int out_rows, int out_cols, mbn_resize_pad_desc *desc,
+                                            int32_t *total_wgs, int32_t *lds_bytes, int64_t *src_span)
+{
+    if (!items || !desc || !total_wgs || !lds_bytes || !src_span || batch <= 0) return MBN_EINVAL;
+    int64_t wgs = 0, span = 0;
+    int lds = 0;
+    for (int i = 0; i < batch; i++) {
+        const int rc = mbn_resize_pad_ragged_plan_filter(filter, &items[i], out_rows, out_cols, &desc[i]);
+        if (rc != MBN_OK) return rc;
+        desc[i].img.wg0 = (int32_t)wgs;
+        wgs += (int64_t)desc[i].img.tiles_y * desc[i].tiles_x + desc[i].fill_wgs;
+        if (wgs > INT32_MAX) return MBN_EUNSUPPORTED;
+        const int64_t end = items[i].src_offset + (int64_t)items[i].rows * items[i].cols * 3;
+        if (end < items[i].src_offset) return MBN_EINVAL;
+        if (end > span) span = end;
+        if (desc[i].img.lds_bytes > lds) lds = desc[i].img.lds_bytes;
+    }
+    *total_wgs = (int32_t)wgs;
+    *lds_bytes = lds;
+    *src_span = span;
+    return MBN_OK;
 }

@@ -8,7 +8,9 @@
  *   --ppm F (several times, up to --batch, for files of different sizes: they are resized in ONE ragged launch, mbn_net_resize_inputs, and the top-1 of
  *   each is printed; the rest of the batch repeats the first): a P6 image of ANY size up to 8192 x 8192; one that is not cols wide and rows high is resized on the device (mbn_net_resize_input: Pillow's 8-bit
  *   bilinear). --fit crop (default: the centred box with the plan's aspect ratio) | stretch (the whole image); --crop-fraction F in (0, 1] shrinks the crop box
- *   (0.875 = "resize to 256, crop 224"). An image of the plan's size is taken as it is
+ *   (0.875 = "resize to 256, crop 224") | pad (the whole image with its aspect ratio kept, centred on a canvas of --pad-color R,G,B, default 0,0,0:
+ *   PIL.ImageOps.pad, mbn_fit_pad; --segment then also prints the rectangle of image 0, which is where its labels are). An image of the plan's size
+ *   is taken as it is
  *   --filter nearest | box | bilinear (default) | hamming | bicubic | lanczos: Pillow's filter of that resize (mbn_net_set_resize_filter). Several --ppm
  *   take the ragged launch, which has no hamming and no lanczos (their weights need the host's sin / cos): usage status 2
  *   --segment FILE: after the classification, the dense head (mbn_net_segment): the label map of image 0 as a binary PGM and its five most frequent labels
@@ -432,6 +434,25 @@ static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int
     return bad;
 }
 
+/* --fit NAME: MBN_FIT_*, or -1 for an unknown name */
+static int fit_of(const char *name)
+{
+    return !strcmp(name, "crop") ? MBN_FIT_CROP : !strcmp(name, "stretch") ? MBN_FIT_STRETCH : !strcmp(name, "pad") ? MBN_FIT_PAD : -1;
+}
+
+static const char *fit_name(int fit)
+{
+    return fit == MBN_FIT_CROP ? "crop" : fit == MBN_FIT_PAD ? "pad" : "stretch";
+}
+
+/* --pad-color R,G,B: three integers 0..255 and nothing behind them */
+static int pad_color_of(const char *s, int rgb[3])
+{
+    char extra;
+    if (sscanf(s, "%d,%d,%d%c", &rgb[0], &rgb[1], &rgb[2], &extra) != 3) return 0;
+    return rgb[0] >= 0 && rgb[0] <= 255 && rgb[1] >= 0 && rgb[1] <= 255 && rgb[2] >= 0 && rgb[2] <= 255;
+}
+
 /* --filter NAME: MBN_FILTER_*, or -1 for an unknown name */
 static int filter_of(const char *name)
 {
@@ -450,6 +471,7 @@ int main(int argc, char **argv)
     if (!ppms) return 1;
     const char *h5 = NULL, *ppm = NULL, *segment = NULL, *segment_src = NULL, *wfile = "weights_c.txt", *image = "Cat_Image0.ppm";
     int fit = MBN_FIT_CROP, filter = MBN_FILTER_BILINEAR;
+    int pad_rgb[3] = { 0, 0, 0 }, src_h0 = 0, src_w0 = 0;              /* src_h0 x src_w0: image 0 as it was resized (0: it was not) */
     float crop_fraction = 1.0f;
     int literal = 0, ref_args = 0, batch = 1, rows = 224, cols = 224, have_seed = 0, gpus = 0, steps = 20, warmup = 3, verify = 0, out_stride = 32;
     unsigned long long seed = 0;
@@ -470,8 +492,8 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--output-stride") && i + 1 < argc) out_stride = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--segment") && i + 1 < argc) segment = argv[++i];
         else if (!strcmp(argv[i], "--segment-source") && i + 1 < argc) segment_src = argv[++i];
-        else if (!strcmp(argv[i], "--fit") && i + 1 < argc && (!strcmp(argv[i + 1], "crop") || !strcmp(argv[i + 1], "stretch")))
-            fit = !strcmp(argv[++i], "crop") ? MBN_FIT_CROP : MBN_FIT_STRETCH;
+        else if (!strcmp(argv[i], "--fit") && i + 1 < argc && fit_of(argv[i + 1]) >= 0) fit = fit_of(argv[++i]);
+        else if (!strcmp(argv[i], "--pad-color") && i + 1 < argc && pad_color_of(argv[i + 1], pad_rgb)) i++;
         else if (!strcmp(argv[i], "--crop-fraction") && i + 1 < argc) crop_fraction = (float)atof(argv[++i]);
         else if (!strcmp(argv[i], "--filter") && i + 1 < argc && filter_of(argv[i + 1]) >= 0) filter = filter_of(argv[++i]);
         else if (!strcmp(argv[i], "--synthetic") && i + 1 < argc) { seed = strtoull(argv[++i], NULL, 0); have_seed = 1; }
@@ -486,7 +508,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--literal")) literal = 1;
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
-            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch] [--crop-fraction F] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm] "
+            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm] "
                             "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n", argv[0]);
             return 2;
         }
@@ -545,6 +567,7 @@ int main(int argc, char **argv)
     mbn_net *net = NULL;
     CHECK(mbn_net_create(ctx, &w, batch, &net));
     CHECK(mbn_net_set_resize_filter(net, filter));
+    CHECK(mbn_net_set_pad_color(net, pad_rgb[0], pad_rgb[1], pad_rgb[2]));
     const int classes = w.plan.classes;
     const size_t img = (size_t)rows * cols * 3;          /* [rows][cols][3]: a P6 image cols wide and rows high */
     size_t img_count = (size_t)batch * img;
@@ -582,7 +605,8 @@ int main(int argc, char **argv)
         CHECK(mbn_free(ctx, d_src));
         for (int n = n_ppm; n < batch; n++) memcpy(u8 + (size_t)n * img, u8, img);
         for (int n = 0; n < n_ppm; n++)
-            printf("image %d: %s, %d wide, %d high, resized to %d x %d (%s)\n", n, ppms[n], ws[n], hs[n], cols, rows, fit == MBN_FIT_CROP ? "crop" : "stretch");
+            printf("image %d: %s, %d wide, %d high, resized to %d x %d (%s)\n", n, ppms[n], ws[n], hs[n], cols, rows, fit_name(fit));
+        src_h0 = hs[0]; src_w0 = ws[0];
         free(all); free(offs); free(hs); free(ws);
     } else if (have && pw == cols && ph == rows) {
         for (int n = 0; n < batch; n++) memcpy(u8 + (size_t)n * img, src, img);
@@ -595,7 +619,8 @@ int main(int argc, char **argv)
         CHECK(mbn_download(ctx, u8, d_img, img));
         CHECK(mbn_free(ctx, d_src));
         for (int n = 1; n < batch; n++) memcpy(u8 + (size_t)n * img, u8, img);
-        printf("image: %s, %d wide, %d high, resized to %d x %d (%s)\n", ppm, pw, ph, cols, rows, fit == MBN_FIT_CROP ? "crop" : "stretch");
+        printf("image: %s, %d wide, %d high, resized to %d x %d (%s)\n", ppm, pw, ph, cols, rows, fit_name(fit));
+        src_h0 = ph; src_w0 = pw;
     } else {
         if (ppm) fprintf(stderr, "warning: %s is not a readable P6 image of at most %d x %d pixels; using a synthetic one\n", ppm, PPM_MAX_SIDE, PPM_MAX_SIDE);
         unsigned long long s = 0xC0FFEEULL;
@@ -639,6 +664,10 @@ int main(int argc, char **argv)
         const int bad = write_label_map(segment, labels, rows, cols, classes);
         free(labels);
         if (bad) return 1;
+        int32_t rect[4];
+        if (fit == MBN_FIT_PAD && src_h0 > 0 && mbn_fit_pad(src_h0, src_w0, rows, cols, rect) == MBN_OK)
+            printf("segment: image 0 is the %d x %d rectangle at (%d, %d) of the label map (wide x high, left, upper); the rest labels the border\n", rect[2],
+                   rect[3], rect[0], rect[1]);
     }
     if (segment_src) {
         const int bad = segment_source(ctx, net, ppms, n_ppm, segment_src, classes);

@@ -516,6 +516,21 @@ int mbn_normalize_u8_to_f32(mbn_context *ctx, void *out_f32, const void *in_u8, 
  *                      shrunk by crop_fraction f in (0, 1] (f = 0.875 is the usual "resize to 256, crop 224"); in double
  *                      bw = min(W, H * ow / oh) * f, bh = bw * oh / ow, left = (W - bw) / 2, upper = (H - bh) / 2, each edge then rounded to
  *                      float32 and clamped into the image. 480 x 640 -> 224 x 224, f = 1: (80, 0, 560, 480)
+ *                      MBN_FIT_PAD: (0, 0, W, H) again, the whole image being what a letterbox resizes; any other fit: MBN_EINVAL
+ *   mbn_fit_pad        the letterbox, normative: PIL.ImageOps.pad(image, (ow, oh), filter, color=fill) of Pillow 12.2.0 (ImageOps.contain, then the
+ *                      paste with centering (0.5, 0.5)), byte for byte (tests/golden/resize_pillow_pad.npz records Pillow's bytes). Source H x W,
+ *                      canvas oh x ow, everything in double; rint rounds half to EVEN (Python's round):
+ *                          im_ratio = W / H;  dest_ratio = ow / oh;  iw = ow;  ih = oh
+ *                          if im_ratio != dest_ratio:
+ *                              if im_ratio > dest_ratio:  ih = rint(H / W * ow)        the division first, then the product
+ *                              else:                      iw = rint(W / H * oh)
+ *                          if (iw, ih) == (ow, oh):  x = y = 0
+ *                          else if iw != ow:         x = rint((ow - iw) * 0.5);  y = 0
+ *                          else:                     x = 0;  y = rint((oh - ih) * 0.5)
+ *                      rect = (x, y, iw, ih). The inner image canvas[y .. y + ih)[x .. x + iw) is the resize above of the WHOLE image, box
+ *                      (0, 0, W, H), to ih x iw under the handle's filter; every other pixel of the canvas is fill[3] = (R, G, B). 33 x 100 ->
+ *                      32 x 32: ih = 11, y = rint(10.5) = 10. iw < 1 or ih < 1 (8192 x 1 -> 32 x 32, where Pillow raises), a non-positive size
+ *                      or NULL: MBN_EINVAL. The envelope of a letterbox is the one below applied to (H, W) -> (ih, iw)
  * A box edge below 0 or beyond the image, b1 <= b0, a NaN or a non-positive size: MBN_EINVAL.
  * Device (mbn_u8_resize.hip; the tile body, mbn_u8_resize.h, is the ragged kernel's too): ONE launch runs both passes; the uint8 intermediate
  * lives in LDS and never reaches memory.
@@ -532,9 +547,16 @@ int mbn_normalize_u8_to_f32(mbn_context *ctx, void *out_f32, const void *in_u8, 
  *   mbn_resizer_create_filter   the same under any filter; mbn_resizer_create is its MBN_FILTER_BILINEAR call. The filter belongs to the handle:
  *                       mbn_resize_u8 is the one hot call. The five convolution filters run the same kernel on their own tables; NEAREST has a
  *                       kernel of its own, a gather of 3-byte pixels through the uploaded ix [out_cols], iy [out_rows], under the same contract
- *                       (any byte pointers: dword stores from the first 4-byte boundary of an output row's address on, bytewise around them) */
+ *                       (any byte pointers: dword stores from the first 4-byte boundary of an output row's address on, bytewise around them)
+ *   mbn_resizer_create_pad      the letterbox of mbn_fit_pad as a handle: mbn_resize_u8 then takes in [batch][H][W][3] to the CANVAS
+ *                       out [batch][out_rows][out_cols][3]. Any filter. Still ONE kernel node and nothing else: the launch that resizes the
+ *                       whole image into the rectangle of every canvas carries, per image, the workgroups that fill what lies outside it, so
+ *                       the call stays legal inside a capture. The same contract for pointers and bounds; every byte of the canvas is written, the
+ *                       border as NEAREST stores (bytewise to the first 4-byte boundary of the address, dwords, a bytewise tail). fill NULL:
+ *                       MBN_EINVAL; an empty inner side: MBN_EINVAL; the envelope: mbn_resizer_create's on (H, W) -> (ih, iw) */
 #define MBN_FIT_STRETCH 0
 #define MBN_FIT_CROP    1
+#define MBN_FIT_PAD     2
 #define MBN_FILTER_NEAREST  0        /* PIL.Image.Resampling's numbers */
 #define MBN_FILTER_LANCZOS  1
 #define MBN_FILTER_BILINEAR 2
@@ -547,9 +569,11 @@ int  mbn_resize_ksize_filter(int filter, int in_size, float b0, float b1, int ou
 int  mbn_resize_taps_filter(int filter, int in_size, float b0, float b1, int out_size, int32_t *first, int32_t *count, int32_t *weights);
 int  mbn_resize_nearest_index(int in_size, float b0, float b1, int out_size, int32_t *index);
 int  mbn_fit_box(int in_rows, int in_cols, int out_rows, int out_cols, int fit, float crop_fraction, float box[4]);
+int  mbn_fit_pad(int in_rows, int in_cols, int out_rows, int out_cols, int32_t rect[4]);
 typedef struct mbn_resizer mbn_resizer;
 int  mbn_resizer_create(mbn_context *ctx, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r);
 int  mbn_resizer_create_filter(mbn_context *ctx, int filter, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r);
+int  mbn_resizer_create_pad(mbn_context *ctx, int filter, int in_rows, int in_cols, int out_rows, int out_cols, const uint8_t fill[3], mbn_resizer **r);
 int  mbn_resize_u8(mbn_resizer *r, void *out_u8, const void *in_u8, int batch, void *stream);
 int  mbn_resizer_destroy(mbn_resizer *r);
 /* Ragged resize (mbn_u8_resize_ragged.hip): ONE launch takes `batch` images, each with its own rows, cols and box, to one common
@@ -584,11 +608,20 @@ int  mbn_resizer_destroy(mbn_resizer *r);
  *                               MBN_FILTER_LANCZOS answer MBN_EUNSUPPORTED here: their weights need sin / cos bit-equal to the host's libm,
  *                               which device math does not promise, and a nearly-always-equal form is not shipped. Use mbn_resizer_create_filter
  *   mbn_resize_taps_device_filter      mbn_resize_taps_device under one of those four filters (HAMMING, LANCZOS: MBN_EUNSUPPORTED): what
- *                               mbn_resize_taps_filter gives on the host (NEAREST: first = the index, count 1, weight 2^22) */
+ *                               mbn_resize_taps_filter gives on the host (NEAREST: first = the index, count 1, weight 2^22)
+ *   mbn_ragged_resizer_create_pad      the letterbox of mbn_fit_pad for images of different sizes: in ONE launch image i goes to its own rectangle
+ *                               of canvas i of out [batch][out_rows][out_cols][3] and the rest of every canvas is `fill`. _set and the launch
+ *                               are driven as above, with the same generation, first-set-waits and failed-set rules; an item's box must be the
+ *                               whole image (0, 0, cols, rows), else MBN_EINVAL, as is an empty inner side. The same four filters. The inner
+ *                               size is the image's own, so its axis geometry, tile counts and the workgroup -> (image, tile) search run on
+ *                               96-byte descriptors (mbn_resize_pad_desc, host/mbn_envelope.h); the border is written by extra workgroups of the
+ *                               same launch, counted into each image's share of the grid ("Letterbox") */
 typedef struct mbn_resize_item { int64_t src_offset; int32_t rows, cols; float box[4]; } mbn_resize_item;   /* 32 bytes */
 typedef struct mbn_ragged_resizer mbn_ragged_resizer;
 int  mbn_ragged_resizer_create(mbn_context *ctx, int max_batch, int out_rows, int out_cols, mbn_ragged_resizer **r);
 int  mbn_ragged_resizer_create_filter(mbn_context *ctx, int filter, int max_batch, int out_rows, int out_cols, mbn_ragged_resizer **r);
+int  mbn_ragged_resizer_create_pad(mbn_context *ctx, int filter, int max_batch, int out_rows, int out_cols, const uint8_t fill[3],
+                                   mbn_ragged_resizer **r);
 int  mbn_resize_taps_device_filter(mbn_context *ctx, int filter, int in_size, float b0, float b1, int out_size, void *first_i32, void *count_i32,
                                    void *weights_i32);
 int  mbn_ragged_resizer_set(mbn_ragged_resizer *r, const mbn_resize_item *items, int batch, void *stream);
@@ -817,6 +850,13 @@ int  mbn_net_resize_inputs(mbn_net *net, const void *src_u8, const int64_t *offs
  * mbn_net_resize_inputs passes the ragged path's MBN_EUNSUPPORTED on and the net stays usable (mbn_net_resize_input takes every filter). */
 int  mbn_net_set_resize_filter(mbn_net *net, int filter);
 int  mbn_net_get_resize_filter(const mbn_net *net, int *filter);
+/* MBN_FIT_PAD as the `fit` of mbn_net_resize_input / _inputs: the letterbox of mbn_fit_pad into the plan's rows x cols (mbn_resizer_create_pad /
+ * mbn_ragged_resizer_create_pad above); crop_fraction is ignored. The border is the net's pad colour, (0, 0, 0) = Pillow's default until
+ * mbn_net_set_pad_color is called (a channel outside 0..255: MBN_EINVAL, nothing changes); the kept resizers are rebuilt on the next call after the
+ * fit or the colour changed. No forward path changes. mbn_net_segment_to and mbn_net_segment_images stay stretch-only: after a letterbox the labels
+ * of the image are the rectangle mbn_fit_pad gives, in the label map of mbn_net_segment. */
+int  mbn_net_set_pad_color(mbn_net *net, int r, int g, int b);
+int  mbn_net_get_pad_color(const mbn_net *net, int *r, int *g, int *b);
 int  mbn_net_fused_layers(const mbn_net *net, int last_layer, int *count);
 /* Fused depthwise->pointwise blocks (mbn_dwpw_fused): bit L of `mask` (L = 1-based number of a depthwise layer) lets
  * layers L and L+1 run as one launch when the plan is fp32, activations are not kept and the shapes are inside the

@@ -19,6 +19,9 @@
       of them alternating within every repetition; the entries are named <geometry>:<filter> (the bilinear ones keep the bare name) and carry the
       taps per axis. The kernel's bytes are compared with tests/resize_filters_ref.py; the torch yardstick is mode="bicubic" under bicubic and
       lanczos, "nearest" under nearest, "bilinear" with antialias otherwise.
+      --fit LIST: comma list of crop, stretch, pad: every geometry runs once per fit (crop with the geometry's own fraction) instead of its own fit, all
+      alternating within every repetition; the entries are named <geometry>/<fit>. pad is the letterbox (mbn_resizer_create_pad, black border),
+      compared with the rule + tests/resize_filters_ref.py; it has no torch yardstick.
 
   python tools/resize_bench.py --ragged [--seed 1] [--batch 256] [--reps 7] [--steps 20]
       The ragged resize (mbn_resize_ragged_u8) on a seeded batch of images of DIFFERENT sizes: rows 300-600, cols 300-700, each through its crop-0.875
@@ -31,6 +34,10 @@
       Every figure is a host clock around `steps` calls that end in a device synchronise, in ms per batch: median over the repetitions and their
       range. The ragged output of both batches is compared once with the table kernel's bytes, image by image (agreement, not timing).
       --filter NAME: one of nearest, box, bilinear (the default), bicubic, for the ragged and the table resizers alike.
+
+  python tools/resize_bench.py --ragged --fit pad,stretch [--seed 1] [--batch 256] [--reps 7] [--steps 20] [--filter NAME]
+      The same mixed batch under each fit of the list (crop: fraction 0.875; pad: mbn_ragged_resizer_create_pad, black border), one ragged handle per
+      fit, the fits alternating within every repetition: set + launch, and the launch alone. Image 0 of every fit is compared with the reference.
 """
 import argparse
 import json
@@ -83,7 +90,71 @@ def figure(runs):
     return {"median_ms": round(statistics.median(runs), 4), "min_ms": round(min(runs), 4), "max_ms": round(max(runs), 4), "runs_ms": [round(x, 4) for x in runs]}
 
 
+def canvas_ref(pkg, filt, img, fit, frac):
+    """image 0's reference bytes under a fit: tests/resize_filters_ref.py on the fit's box, or into the letterbox's rectangle of a black canvas"""
+    import resize_filters_ref
+    H, W = img.shape[:2]
+    if fit != "pad":
+        return resize_filters_ref.resize(filt, img, RES, RES, pkg.fit_box(H, W, RES, RES, pkg.FIT_CROP if fit == "crop" else pkg.FIT_STRETCH, frac))
+    x, y, iw, ih = pkg.fit_pad(H, W, RES, RES)
+    out = np.zeros((RES, RES, 3), np.uint8)
+    out[y:y + ih, x:x + iw] = resize_filters_ref.resize(filt, img, ih, iw)
+    return out
+
+
+def ragged_fit_main(a):
+    """--ragged --fit LIST: the mixed batch under each fit, alternating"""
+    pkg = import_package()
+    import torch
+    assert torch.cuda.is_available(), "the buffers are torch tensors on the same GPU"
+    fits = a.fit.split(",")
+    assert all(f in ("crop", "stretch", "pad") for f in fits), "--fit: unknown name in %r" % a.fit
+    rng = np.random.default_rng(a.seed)
+    n = a.batch
+    filt = pkg.FILTER_NAMES[a.filter or "bilinear"]
+    sizes = [(int(rng.integers(300, 601)), int(rng.integers(300, 701))) for _ in range(n)]
+    print("ragged: seed %d, batch %d, rows 300-600 x cols 300-700 -> %d x %d, fits %s, filter %s" % (a.seed, n, RES, RES, a.fit, a.filter or "bilinear"), flush=True)
+    result = {"seed": a.seed, "batch": n, "steps": a.steps, "reps": a.reps, "filter": a.filter or "bilinear"}
+    with pkg.Context(0) as ctx:
+        offs = np.concatenate([[0], np.cumsum([h * w * 3 for h, w in sizes])]).astype(np.int64)
+        t_src = torch.randint(0, 256, (int(offs[-1]),), dtype=torch.uint8, device="cuda")
+        t_out = torch.zeros((n, RES, RES, 3), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        img0 = t_src[:sizes[0][0] * sizes[0][1] * 3].cpu().numpy().reshape(sizes[0] + (3,))
+        forms, keep = {}, []
+        for fit in fits:
+            code = {"crop": pkg.FIT_CROP, "stretch": pkg.FIT_STRETCH, "pad": pkg.FIT_PAD}[fit]
+            items = pkg.resize_items([(int(o), h, w, pkg.fit_box(h, w, RES, RES, code, 0.875)) for o, (h, w) in zip(offs, sizes)])
+            rr = pkg.RaggedResizer(ctx, n, RES, RES, filter=filt, pad=(0, 0, 0) if fit == "pad" else None)
+            keep.append(rr)
+
+            def set_and_launch(rr=rr, items=items):
+                rr.set(items)
+                rr.run(t_out.data_ptr(), t_src.data_ptr())
+
+            set_and_launch()
+            ctx.sync()
+            differ = int((t_out[0].cpu().numpy() != canvas_ref(pkg, filt, img0, fit, 0.875)).sum())
+            forms[fit] = dict(f={"set_and_launch": set_and_launch, "launch_alone": lambda rr=rr: rr.run(t_out.data_ptr(), t_src.data_ptr())},
+                              runs={"set_and_launch": [], "launch_alone": []}, differ=differ)
+        for _ in range(a.reps):
+            for fit, r in forms.items():
+                for k, fn in r["f"].items():               # the set of set_and_launch stays for the launch alone
+                    r["runs"][k].append(wall_ms(ctx, fn, a.steps))
+        for fit, r in forms.items():
+            out = {k: figure(v) for k, v in r["runs"].items()}
+            out["bytes_differ_from_ref_image0"] = r["differ"]
+            result[fit] = out
+            print("%-8s %s  differing bytes %d" % (fit, "  ".join("%s %.4f ms (%.4f-%.4f)" % (k, out[k]["median_ms"], out[k]["min_ms"], out[k]["max_ms"])
+                                                                    for k in r["runs"]), r["differ"]), flush=True)
+        for rr in keep:
+            rr.close()
+    print(json.dumps(result))
+
+
 def ragged_main(a):
+    if a.fit:
+        return ragged_fit_main(a)
     pkg = import_package()
     import torch
     assert torch.cuda.is_available(), "the buffers are torch tensors on the same GPU"
@@ -166,6 +237,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1, help="--ragged: seed of the batch's size list")
     ap.add_argument("--batch", type=int, default=256, help="--ragged: images per batch")
     ap.add_argument("--filter", default="", help="comma list of Pillow filter names, or all (--ragged: one name); default bilinear")
+    ap.add_argument("--fit", default="", help="comma list of crop, stretch, pad: every geometry (--ragged: the mixed batch) under each of them")
     a = ap.parse_args()
     if a.ragged:
         return ragged_main(a)
@@ -180,16 +252,19 @@ def main():
         runs = {}
         names = [f for f in ("nearest", "box", "bilinear", "hamming", "bicubic", "lanczos") if a.filter == "all" or f in (a.filter or "bilinear").split(",")]
         assert names and (a.filter in ("", "all") or len(names) == len(a.filter.split(","))), "--filter: unknown name in %r" % a.filter
+        assert all(f in ("crop", "stretch", "pad") for f in a.fit.split(",") if f), "--fit: unknown name in %r" % a.fit
+        if a.fit:
+            chosen = [(c[0] + "/" + f, c[1], c[2], f) + c[4:] for c in chosen for f in a.fit.split(",")]
         for name, H, W, fit, frac, n, fwd, fname in [c + (f,) for c in chosen for f in names]:
             filt = pkg.FILTER_NAMES[fname]
             name = name if fname == "bilinear" else "%s:%s" % (name, fname)
-            box = pkg.fit_box(H, W, RES, RES, pkg.FIT_CROP if fit == "crop" else pkg.FIT_STRETCH, frac)
+            box = pkg.fit_box(H, W, RES, RES, {"crop": pkg.FIT_CROP, "stretch": pkg.FIT_STRETCH, "pad": pkg.FIT_PAD}[fit], frac)
             x0, x1, kx = window(pkg, W, box[0], box[2], RES, filt)
             y0, y1, ky = window(pkg, H, box[1], box[3], RES, filt)
             t_src = torch.randint(0, 256, (n, H, W, 3), dtype=torch.uint8, device="cuda")       # the library reads what torch owns
             t_out = torch.zeros((n, RES, RES, 3), dtype=torch.uint8, device="cuda")
             torch.cuda.synchronize()
-            rz = pkg.Resizer(ctx, H, W, RES, RES, box, filter=filt)
+            rz = pkg.Resizer(ctx, H, W, RES, RES, filter=filt, pad=(0, 0, 0)) if fit == "pad" else pkg.Resizer(ctx, H, W, RES, RES, box, filter=filt)
             r = dict(rz=rz, n=n, fwd=fwd, filter=fname, kx=kx, ky=ky, t_src=t_src, t_out=t_out, kernel=[], torch=[],
                      bytes=3.0 * n * ((y1 - y0) * (x1 - x0) + RES * RES), box=[float(v) for v in box])
             r["run_kernel"] = lambda r=r: r["rz"].run(r["t_out"].data_ptr(), r["t_src"].data_ptr(), r["n"])
@@ -200,9 +275,10 @@ def main():
             r["torch_mode"] = mode
             marks_ms(ctx, r["run_kernel"], 3)               # warm-up of every timed shape
             ctx.sync()
-            want = resize_filters_ref.resize(filt, t_src[0].cpu().numpy(), RES, RES, box)
+            want = canvas_ref(pkg, filt, t_src[0].cpu().numpy(), fit, frac)
             r["bytes_differ_from_ref"] = int((t_out[0].cpu().numpy() != want).sum())
-            if not a.no_torch:
+            r["has_torch"] = not a.no_torch and fit != "pad"
+            if r["has_torch"]:
                 for _ in range(3):
                     r["run_torch"]()
                 torch.cuda.synchronize()
@@ -210,7 +286,7 @@ def main():
         for _ in range(a.reps):
             for name, r in runs.items():
                 r["kernel"].append(marks_ms(ctx, r["run_kernel"], a.steps))
-                if not a.no_torch:
+                if r["has_torch"]:
                     ctx.sync()
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record()
