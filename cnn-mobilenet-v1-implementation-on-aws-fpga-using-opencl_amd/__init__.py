@@ -95,6 +95,11 @@ class LabelItem(C.Structure):
     _fields_ = [("dst_offset", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32)]
 
 
+class LabelWindowItem(C.Structure):
+    """mbn_label_window_item (include/mbn.h): one image of a ragged window read-out: LabelItem and its rectangle (x, y, iw, ih) of the network input"""
+    _fields_ = [("dst_offset", C.c_int64)] + [(n, C.c_int32) for n in ("rows", "cols", "x", "y", "iw", "ih")]
+
+
 class ResampleLaunch(C.Structure):
     """mbn_resample_launch_t (host/mbn_envelope.h): LDS footprint, class chunk, dynamic LDS, grid.x and output span of a read-out launch"""
     _fields_ = [(n, C.c_int32) for n in ("fy", "fx", "ch", "lds_bytes", "tiles")] + [("span", C.c_int64)]
@@ -184,6 +189,11 @@ def _declare_host(lib):
     lib.mbn_resample_plan.argtypes = [C.c_int] * 4 + [C.POINTER(ResampleLaunch)]
     lib.mbn_resample_plan.restype = None
     lib.mbn_resample_ragged_check.argtypes = [C.c_int] * 3 + [C.POINTER(LabelItem), C.c_int, C.POINTER(C.c_int64), C.POINTER(ResampleLaunch)]
+    lib.mbn_resample_window_envelope.argtypes = [C.c_int] * 6 + [C.POINTER(C.c_int32), C.c_int, C.c_int]
+    lib.mbn_resample_window_plan.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(ResampleLaunch)]
+    lib.mbn_resample_window_plan.restype = None
+    lib.mbn_resample_ragged_window_check.argtypes = [C.c_int] * 5 + [C.POINTER(LabelWindowItem), C.c_int, C.POINTER(C.c_int64),
+                                                                     C.POINTER(ResampleLaunch)]
     i32p = C.POINTER(C.c_int32)
     lib.mbn_resize_ksize.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int]
     lib.mbn_resize_taps.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int, i32p, i32p, i32p]
@@ -319,6 +329,11 @@ def load():
         lib.mbn_ragged_readout_set.argtypes = [vp, ci, ci, ci, C.POINTER(LabelItem), ci, vp]
         lib.mbn_resample_argmax_ragged_f32.argtypes = [vp, vp, vp, vp, vp]
         lib.mbn_ragged_readout_destroy.argtypes = [vp]
+        lib.mbn_resample_argmax_window_f32.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(C.c_int32), ci, ci, vp]
+        lib.mbn_ragged_readout_set_window.argtypes = [vp, ci, ci, ci, ci, ci, C.POINTER(LabelWindowItem), ci, vp]
+        lib.mbn_net_segment_fit.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
+        lib.mbn_net_segment_images_fit.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, ci, vp,
+                                                   C.POINTER(C.c_int64), vp]
         lib.mbn_net_segment_to.argtypes = [vp, vp, ci, ci, ci, vp, vp]
         lib.mbn_net_segment_images.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, vp, C.POINTER(C.c_int64), vp]
         lib.mbn_resizer_create.argtypes = [vp, ci, ci, C.POINTER(C.c_float), ci, ci, C.POINTER(vp)]
@@ -495,6 +510,42 @@ def label_items(items):
     for it, (off, rows, cols) in zip(arr, items):
         it.dst_offset, it.rows, it.cols = int(off), int(rows), int(cols)
     return arr
+
+
+def label_window_items(items):
+    """A C array of mbn_label_window_item from (dst_offset, rows, cols, (x, y, iw, ih)) tuples."""
+    arr = (LabelWindowItem * len(items))()
+    for it, (off, rows, cols, rect) in zip(arr, items):
+        it.dst_offset, it.rows, it.cols = int(off), int(rows), int(cols)
+        it.x, it.y, it.iw, it.ih = (int(v) for v in rect)
+    return arr
+
+
+def _rect(rect):
+    return (C.c_int32 * 4)(*[int(v) for v in rect])
+
+
+def resample_window_envelope(batch, rows, cols, classes, in_rows, in_cols, rect, out_rows, out_cols, lib=None) -> int:
+    """mbn_resample_window_envelope: the status mbn_resample_argmax_window_f32 gives the shape and the window rect = (x, y, iw, ih)."""
+    return (lib or host_lib()).mbn_resample_window_envelope(batch, rows, cols, classes, in_rows, in_cols, None if rect is None else _rect(rect),
+                                                            out_rows, out_cols)
+
+
+def resample_window_plan(rows, cols, in_rows, in_cols, rect, out_rows, out_cols, lib=None) -> ResampleLaunch:
+    """mbn_resample_window_plan: the launch of one output size of one window of a rows x cols map."""
+    l = ResampleLaunch()
+    (lib or host_lib()).mbn_resample_window_plan(rows, cols, in_rows, in_cols, _rect(rect), out_rows, out_cols, C.byref(l))
+    return l
+
+
+def resample_ragged_window_check(rows, cols, classes, in_rows, in_cols, items, launch=None, lib=None):
+    """mbn_resample_ragged_window_check: (status, launch) of a ragged window set of (dst_offset, rows, cols, rect) tuples. `launch`: the record
+    to write into (a refused batch leaves it as it was)."""
+    arr = items if isinstance(items, C.Array) else label_window_items(items)
+    l = launch if launch is not None else ResampleLaunch()
+    rc = (lib or host_lib()).mbn_resample_ragged_window_check(rows, cols, classes, in_rows, in_cols, arr, len(arr),
+                                                              (C.c_int64 * (2 * max(len(arr), 1)))(), C.byref(l))
+    return rc, l
 
 
 def resample_argmax_envelope(batch, rows, cols, classes, out_rows, out_cols, lib=None) -> int:
@@ -718,6 +769,12 @@ class Context:
         logit) [batch][out_rows][out_cols]: bilinear resample to any size (at least 4 x the map) + argmax in one kernel."""
         _chk(self.lib.mbn_resample_argmax_f32(self.h, labels, score, logits, batch, rows, cols, classes, out_rows, out_cols, None), self.last_error())
 
+    def resample_argmax_window(self, labels, score, logits, batch, rows, cols, classes, in_rows, in_cols, rect, out_rows, out_cols):
+        """mbn_resample_argmax_window_f32: the same read-out of the window rect = (x, y, iw, ih) of the in_rows x in_cols network input that the
+        rows x cols map covers (fit_pad's rectangle: the labels of a letterboxed image at its own size)."""
+        _chk(self.lib.mbn_resample_argmax_window_f32(self.h, labels, score, logits, batch, rows, cols, classes, in_rows, in_cols, _rect(rect),
+                                                     out_rows, out_cols, None), self.last_error())
+
     def __enter__(self):
         return self
 
@@ -743,6 +800,12 @@ class RaggedReadout:
     def set(self, rows, cols, classes, items, stream=None):
         arr = items if isinstance(items, C.Array) else label_items(items)
         _chk(self.ctx.lib.mbn_ragged_readout_set(self.h, rows, cols, classes, arr, len(arr), stream), self.ctx.last_error())
+        self.batch = len(arr)
+
+    def set_window(self, rows, cols, classes, in_rows, in_cols, items, stream=None):
+        """mbn_ragged_readout_set_window: (dst_offset, rows, cols, (x, y, iw, ih)) tuples, each image with its own rectangle of the network input."""
+        arr = items if isinstance(items, C.Array) else label_window_items(items)
+        _chk(self.ctx.lib.mbn_ragged_readout_set_window(self.h, rows, cols, classes, in_rows, in_cols, arr, len(arr), stream), self.ctx.last_error())
         self.batch = len(arr)
 
     def run(self, labels_ptr, score_ptr, logits_ptr, stream=None):
@@ -958,6 +1021,19 @@ class Net:
         _chk(self.ctx.lib.mbn_net_segment_images(self.h, src_ptr, (C.c_int64 * n)(*[int(v) for v in offsets]), (C.c_int32 * n)(*[int(v) for v in rows]),
                                                  (C.c_int32 * n)(*[int(v) for v in cols]), n, labels_ptr, (C.c_int64 * n)(*[int(v) for v in dst_offsets]),
                                                  score_ptr), self.ctx.last_error())
+
+    def segment_fit(self, src_ptr, batch, in_rows, in_cols, fit, labels_ptr, score_ptr=None):
+        """mbn_net_segment_fit: uint8 sources [batch][in_rows][in_cols][3] -> resize_input(fit), forward_dense and the read-out to the source size:
+        labels (and scores) [batch][in_rows][in_cols]. FIT_STRETCH or FIT_PAD (the window read-out of fit_pad's rectangle). Needs set_input_u8()."""
+        _chk(self.ctx.lib.mbn_net_segment_fit(self.h, src_ptr, batch, in_rows, in_cols, fit, labels_ptr, score_ptr), self.ctx.last_error())
+
+    def segment_images_fit(self, src_ptr, offsets, rows, cols, fit, labels_ptr, dst_offsets, score_ptr=None):
+        """mbn_net_segment_images_fit: segment_images under FIT_STRETCH or FIT_PAD (one ragged window read-out, each image's own rectangle)."""
+        n = len(offsets)
+        assert len(rows) == n and len(cols) == n and len(dst_offsets) == n
+        _chk(self.ctx.lib.mbn_net_segment_images_fit(self.h, src_ptr, (C.c_int64 * n)(*[int(v) for v in offsets]),
+                                                     (C.c_int32 * n)(*[int(v) for v in rows]), (C.c_int32 * n)(*[int(v) for v in cols]), n, fit,
+                                                     labels_ptr, (C.c_int64 * n)(*[int(v) for v in dst_offsets]), score_ptr), self.ctx.last_error())
 
     def resize_input(self, src_ptr, batch, in_rows, in_cols, fit=FIT_CROP, crop_fraction=1.0) -> int:
         """mbn_net_resize_input: uint8 images [batch][in_rows][in_cols][3] of any size -> the net's staging buffer [batch][rows][cols][3] (its

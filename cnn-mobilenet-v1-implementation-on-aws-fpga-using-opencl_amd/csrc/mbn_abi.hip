@@ -846,6 +846,22 @@ int mbn_resample_argmax_f32(mbn_context *ctx, void *labels_i32, void *score_f32,
                                                     classes, out_rows, out_cols));
 }
 
+int mbn_resample_argmax_window_f32(mbn_context *ctx, void *labels_i32, void *score_f32, const void *logits, int batch, int rows, int cols, int classes,
+                                   int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols, void *stream)
+{
+    if (!ctx || !labels_i32 || !logits || !rect) return MBN_EINVAL;
+    if (((uintptr_t)labels_i32 | (uintptr_t)score_f32 | (uintptr_t)logits) % 4) return MBN_EINVAL;
+    const int rc = mbn_resample_window_envelope(batch, rows, cols, classes, in_rows, in_cols, rect, out_rows, out_cols);
+    if (rc != MBN_OK) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    const double out = 4.0 * batch * out_rows * out_cols;
+    MBN_SPANS(ctx, { logits, 4.0 * batch * rows * cols * classes, "resample_argmax_window logits" },
+              { labels_i32, out, "resample_argmax_window labels" }, { score_f32, out, "resample_argmax_window score" });
+    Scope sc(ctx, s);
+    return sc.finish(mbn_launch_f32_resample_argmax_window(ctx, s, (int32_t *)labels_i32, (float *)score_f32, (const float *)logits, batch, rows,
+                                                           cols, classes, in_rows, in_cols, rect, out_rows, out_cols));
+}
+
 int mbn_ragged_readout_create(mbn_context *ctx, int max_batch, mbn_ragged_readout **r)
 {
     if (!ctx || !r) return MBN_EINVAL;
@@ -881,6 +897,15 @@ int mbn_ragged_readout_set(mbn_ragged_readout *r, int rows, int cols, int classe
     mbn_context *ctx = r->ctx;
     (void)hipSetDevice(ctx->device);
     return mbn_ragged_readout_plan(r, stream ? (hipStream_t)stream : ctx->stream, rows, cols, classes, items, batch);
+}
+
+int mbn_ragged_readout_set_window(mbn_ragged_readout *r, int rows, int cols, int classes, int in_rows, int in_cols,
+                                  const mbn_label_window_item *items, int batch, void *stream)
+{
+    if (!r || !items || batch <= 0 || batch > r->max_batch || rows <= 0 || cols <= 0 || classes <= 0 || in_rows <= 0 || in_cols <= 0) return MBN_EINVAL;
+    mbn_context *ctx = r->ctx;
+    (void)hipSetDevice(ctx->device);
+    return mbn_ragged_readout_plan_window(r, stream ? (hipStream_t)stream : ctx->stream, rows, cols, classes, in_rows, in_cols, items, batch);
 }
 
 int mbn_resample_argmax_ragged_f32(mbn_ragged_readout *r, void *labels_i32, void *score_f32, const void *logits, void *stream)

@@ -20,6 +20,10 @@
 // Every product and sum rounds on its own: contraction into FMA is switched off where they are formed (the build contracts by default).
 // The class chunk is the launch's (MBN_RESAMPLE_CH): 128 while the footprint still leaves eight workgroups on a CU's 160 KB, else 64.
 // The uniform and the ragged form share the tile body; they differ in where a workgroup finds its image's (out_rows, out_cols, destination).
+// WIN (mbn_resample_argmax_window_f32, mbn_ragged_readout_set_window): the outputs resample a rectangle of the network's input, the letterbox's
+// inner image, instead of the whole map. Only the index / weight rule differs (rs_axis_win: 64-bit integers, still one fp64 division per axis
+// coordinate, once per lane in front of the class loop); the footprint bound holds with n / N replaced by l n / (N R) (host/mbn_envelope.h), so
+// stage, reduce, the cross ballot, the store and the LDS layout are the same code. The other instantiations compile to what they were without it.
 #include "mbn_internal.h"
 #include "mbn_device.h"
 
@@ -34,7 +38,7 @@ constexpr int RS_ROWS = 4;                   // output rows of a lane
 struct ReadoutHead {
     int32_t batch, generation, pad[2];
 };
-static_assert(sizeof(ReadoutHead) == 16 && sizeof(mbn_label_item) == 16, "device layout");
+static_assert(sizeof(ReadoutHead) == 16 && sizeof(mbn_label_item) == 16 && sizeof(mbn_label_window_item) == 32, "device layout");
 
 struct ResampleArgs {
     int *labels;
@@ -48,6 +52,15 @@ struct ResampleArgs {
     const ReadoutHead *head; // ragged form
     const mbn_label_item *items;
     int generation;
+    // WIN instantiations only (behind everything the others read, whose kernel arguments stay where they were)
+    int in_rows, in_cols;    // R, C: the network-input pixels the coarse map covers
+    int wx, wy, wiw, wih;    // uniform form: the window, ordered as mbn_fit_pad writes it
+    const mbn_label_window_item *witems;   // ragged form
+};
+
+// a window of the network's input along one axis: [b, b + l) of the R pixels the n coarse samples cover
+struct RsWindow {
+    int R, b, l;
 };
 
 // a * wa + b * wb with three roundings
@@ -64,6 +77,23 @@ __device__ __forceinline__ void rs_axis(int o, int n, int N, int *i0, float *w1)
     const int num = max((2 * o + 1) * n - N, 0), den = 2 * N;
     *i0 = num / den;
     *w1 = (float)((double)(num % den) / (double)den);       // fp64 quotient, rounded once
+}
+
+// The same for a window (include/mbn.h, "segment through the letterbox"): output o of N sits at input coordinate b + (o + 1/2) l / N. 64-bit integers
+// (num < 2^46, den <= 2^29 inside the envelope: both exact in fp64); evaluated once per lane and axis coordinate, outside the class loop.
+__device__ __forceinline__ void rs_axis_win(int o, int n, int N, const RsWindow &w, int *i0, float *w1)
+{
+    const int64_t num = max((int64_t)(2 * o + 1) * w.l * n + 2 * (int64_t)w.b * n * N - (int64_t)N * w.R, (int64_t)0), den = 2 * (int64_t)N * w.R;
+    const int64_t q = num / den;
+    *i0 = (int)q;
+    *w1 = (float)((double)(num - q * den) / (double)den);   // fp64 quotient, rounded once
+}
+
+template <bool WIN>
+__device__ __forceinline__ void rs_coord(int o, int n, int N, const RsWindow &w, int *i0, float *w1)
+{
+    if (WIN) rs_axis_win(o, n, N, w, i0, w1);
+    else rs_axis(o, n, N, i0, w1);
 }
 
 // The reduce pass of one staged chunk of cn4 classes for a lane's four rows. CROSS: some row of the wave interpolates between (ya + 1, ya + 2), so
@@ -97,17 +127,19 @@ __device__ __forceinline__ void rs_reduce(const float *(&p)[3][2], int cn4, int 
 }
 
 // One 32 x 32 tile of one image: src = the image's logits, labels / score = the image's output maps (score may be null), H x W their size.
-template <bool VEC>
+// WIN: the outputs resample the window (wy, wx) of the network's input instead of the whole map; only the index / weight rule differs.
+template <bool VEC, bool WIN>
 __device__ __forceinline__ void resample_tile(const ResampleArgs &a, const float *__restrict__ src, int *__restrict__ labels,
-                                              float *__restrict__ score, int H, int W, int ty, int tx, float *s_x)
+                                              float *__restrict__ score, int H, int W, int ty, int tx, float *s_x, const RsWindow &wy,
+                                              const RsWindow &wx)
 {
     const int tid = threadIdx.x;
     const int ld = a.ch + 4;                  // 16-byte aligned rows, consecutive vectors 4 banks apart
     const int nv = a.fy * a.fx;
     int ybase, xbase;
     float unused;
-    rs_axis(RS_TILE * ty, a.rows, H, &ybase, &unused);
-    rs_axis(RS_TILE * tx, a.cols, W, &xbase, &unused);
+    rs_coord<WIN>(RS_TILE * ty, a.rows, H, wy, &ybase, &unused);
+    rs_coord<WIN>(RS_TILE * tx, a.cols, W, wx, &xbase, &unused);
 
     // this lane's pixels: column ox, rows oy0 .. oy0 + 3 (a coordinate past the image is evaluated at the last one and not stored)
     const int ox = RS_TILE * tx + (tid & 31), oy0 = RS_TILE * ty + RS_ROWS * (tid >> 5);
@@ -115,12 +147,12 @@ __device__ __forceinline__ void resample_tile(const ResampleArgs &a, const float
     int x0, ya = 0;
     float wx1, wy1[RS_ROWS], wy0[RS_ROWS];
     bool up[RS_ROWS];                         // row r interpolates between (ya + 1, ya + 2) instead of (ya, ya + 1)
-    rs_axis(min(ox, W - 1), a.cols, W, &x0, &wx1);
+    rs_coord<WIN>(min(ox, W - 1), a.cols, W, wx, &x0, &wx1);
     const float wx0 = 1.0f - wx1;
 #pragma unroll
     for (int r = 0; r < RS_ROWS; r++) {
         int r0;
-        rs_axis(min(oy0 + r, H - 1), a.rows, H, &r0, &wy1[r]);
+        rs_coord<WIN>(min(oy0 + r, H - 1), a.rows, H, wy, &r0, &wy1[r]);
         wy0[r] = 1.0f - wy1[r];
         if (r == 0) ya = r0;
         up[r] = r0 != ya;                     // r0 is ya or ya + 1: four rows span less than one coarse row
@@ -180,31 +212,44 @@ __device__ __forceinline__ void resample_tile(const ResampleArgs &a, const float
     }
 }
 
-template <bool VEC>
+template <bool VEC, bool WIN>
 __global__ __launch_bounds__(256) void resample_argmax_f32(const ResampleArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float s_rs[];
     const int ty = (int)blockIdx.x / a.tiles_x, tx = (int)blockIdx.x - ty * a.tiles_x;
     const size_t img = (size_t)blockIdx.y;                                                      // 64-bit base, 32-bit offsets inside an image
     const size_t map = (size_t)a.out_rows * a.out_cols;
-    resample_tile<VEC>(a, a.logits + img * ((size_t)a.rows * a.cols * a.classes), a.labels + img * map, a.score ? a.score + img * map : nullptr,
-                       a.out_rows, a.out_cols, ty, tx, s_rs);
+    const RsWindow wy = { a.in_rows, a.wy, a.wih }, wx = { a.in_cols, a.wx, a.wiw };          // read by the WIN instantiations only
+    resample_tile<VEC, WIN>(a, a.logits + img * ((size_t)a.rows * a.cols * a.classes), a.labels + img * map, a.score ? a.score + img * map : nullptr,
+                            a.out_rows, a.out_cols, ty, tx, s_rs, wy, wx);
 }
 
 // grid = (tiles of the largest item, batch): a workgroup past its own image's tiles returns before any load or barrier
-template <bool VEC>
+template <bool VEC, bool WIN>
 __global__ __launch_bounds__(256) void resample_argmax_ragged_f32(const ResampleArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float s_rs[];
     // a replay of a captured launch after another set: the items are no longer the ones its grid, LDS and spans were checked for
     if (a.head->generation != a.generation || (int)blockIdx.y >= a.head->batch) return;
+    if (WIN) {
+        const mbn_label_window_item it = a.witems[blockIdx.y];
+        const int tiles_x = (it.cols + RS_TILE - 1) / RS_TILE, tiles_y = (it.rows + RS_TILE - 1) / RS_TILE;
+        const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
+        if (ty >= tiles_y) return;
+        const size_t img = (size_t)blockIdx.y;
+        const RsWindow wy = { a.in_rows, it.y, it.ih }, wx = { a.in_cols, it.x, it.iw };
+        resample_tile<VEC, true>(a, a.logits + img * ((size_t)a.rows * a.cols * a.classes), a.labels + it.dst_offset,
+                                 a.score ? a.score + it.dst_offset : nullptr, it.rows, it.cols, ty, tx, s_rs, wy, wx);
+        return;
+    }
     const mbn_label_item it = a.items[blockIdx.y];
     const int tiles_x = (it.cols + RS_TILE - 1) / RS_TILE, tiles_y = (it.rows + RS_TILE - 1) / RS_TILE;
     const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
     if (ty >= tiles_y) return;
     const size_t img = (size_t)blockIdx.y;
-    resample_tile<VEC>(a, a.logits + img * ((size_t)a.rows * a.cols * a.classes), a.labels + it.dst_offset, a.score ? a.score + it.dst_offset : nullptr,
-                       it.rows, it.cols, ty, tx, s_rs);
+    const RsWindow none = { 0, 0, 0 };
+    resample_tile<VEC, false>(a, a.logits + img * ((size_t)a.rows * a.cols * a.classes), a.labels + it.dst_offset,
+                              a.score ? a.score + it.dst_offset : nullptr, it.rows, it.cols, ty, tx, s_rs, none, none);
 }
 
 bool vec_loads(const float *logits, int classes) { return ((uintptr_t)logits % 16) == 0 && (classes % 4) == 0; }   // every class vector then starts on 16 bytes
@@ -224,8 +269,28 @@ int mbn_launch_f32_resample_argmax(mbn_context *, hipStream_t s, int32_t *labels
     a.tiles_x = (out_cols + RS_TILE - 1) / RS_TILE;
     a.fy = l.fy; a.fx = l.fx; a.ch = l.ch;
     const dim3 grid((unsigned)l.tiles, (unsigned)batch);
-    if (vec_loads(logits, classes)) hipLaunchKernelGGL((resample_argmax_f32<true>), grid, dim3(256), (size_t)l.lds_bytes, s, a);
-    else hipLaunchKernelGGL((resample_argmax_f32<false>), grid, dim3(256), (size_t)l.lds_bytes, s, a);
+    if (vec_loads(logits, classes)) hipLaunchKernelGGL((resample_argmax_f32<true, false>), grid, dim3(256), (size_t)l.lds_bytes, s, a);
+    else hipLaunchKernelGGL((resample_argmax_f32<false, false>), grid, dim3(256), (size_t)l.lds_bytes, s, a);
+    return MBN_OK;
+}
+
+// The shape and the window are inside mbn_resample_window_envelope and the pointers are non-null multiples of 4 (the caller has checked both).
+int mbn_launch_f32_resample_argmax_window(mbn_context *, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows,
+                                          int cols, int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols)
+{
+    mbn_resample_launch_t l = { 0, 0, 0, 0, 0, 0 };
+    mbn_resample_window_plan(rows, cols, in_rows, in_cols, rect, out_rows, out_cols, &l);
+    ResampleArgs a = {};
+    a.labels = labels; a.score = score; a.logits = logits;
+    a.rows = rows; a.cols = cols; a.classes = classes;
+    a.out_rows = out_rows; a.out_cols = out_cols;
+    a.tiles_x = (out_cols + RS_TILE - 1) / RS_TILE;
+    a.fy = l.fy; a.fx = l.fx; a.ch = l.ch;
+    a.in_rows = in_rows; a.in_cols = in_cols;
+    a.wx = rect[0]; a.wy = rect[1]; a.wiw = rect[2]; a.wih = rect[3];
+    const dim3 grid((unsigned)l.tiles, (unsigned)batch);
+    if (vec_loads(logits, classes)) hipLaunchKernelGGL((resample_argmax_f32<true, true>), grid, dim3(256), (size_t)l.lds_bytes, s, a);
+    else hipLaunchKernelGGL((resample_argmax_f32<false, true>), grid, dim3(256), (size_t)l.lds_bytes, s, a);
     return MBN_OK;
 }
 
@@ -235,7 +300,7 @@ int mbn_ragged_readout_build(mbn_context *ctx, int max_batch, mbn_ragged_readout
     if (!r) return MBN_ENOMEM;
     r->ctx = ctx;
     r->max_batch = max_batch;
-    const size_t bytes = 16 * ((size_t)max_batch + 1);
+    const size_t bytes = sizeof(ReadoutHead) + sizeof(mbn_label_window_item) * (size_t)max_batch;     // the larger kind of item
     r->sort = new (std::nothrow) int64_t[2 * (size_t)max_batch];
     (void)hipSetDevice(ctx->device);
     hipError_t e = r->sort ? hipMalloc(&r->dev, bytes) : hipErrorOutOfMemory;
@@ -258,29 +323,49 @@ void mbn_ragged_readout_release(mbn_ragged_readout *r)
     delete r;
 }
 
-// Checks the batch first and touches nothing when it is refused: the previous set stays. Then waits for what still reads either copy (the previous
-// upload and every launch since), writes the items into the pinned copy and enqueues its upload.
-int mbn_ragged_readout_plan(mbn_ragged_readout *r, hipStream_t s, int rows, int cols, int classes, const mbn_label_item *items, int batch)
+// A checked batch becomes the handle's set: waits for what still reads either copy (the previous upload and every launch since), writes the items
+// (item_bytes each: mbn_label_item, or mbn_label_window_item when `window`) into the pinned copy and enqueues its upload.
+static int readout_upload(mbn_ragged_readout *r, hipStream_t s, int rows, int cols, int classes, int window, int in_rows, int in_cols,
+                          const void *items, size_t item_bytes, int batch, const mbn_resample_launch_t &l)
 {
     mbn_context *ctx = r->ctx;
+    MBN_HIP_TRY(ctx, hipEventSynchronize(r->done));
+    ReadoutHead *h = (ReadoutHead *)r->host;
+    memset(h, 0, sizeof *h);
+    h->batch = batch; h->generation = r->generation + 1;
+    memcpy(h + 1, items, (size_t)batch * item_bytes);
+    r->batch = 0;                                               // from here on a failure leaves the handle without a batch
+    MBN_HIP_TRY(ctx, hipMemcpyAsync(r->dev, r->host, sizeof(ReadoutHead) + (size_t)batch * item_bytes, hipMemcpyHostToDevice, s));
+    MBN_HIP_TRY(ctx, hipEventRecord(r->done, s));
+    r->generation = h->generation;
+    r->rows = rows; r->cols = cols; r->classes = classes;
+    r->window = window; r->in_rows = in_rows; r->in_cols = in_cols;
+    r->launch = l;
+    r->batch = batch;
+    return MBN_OK;
+}
+
+// Checks the batch first and touches nothing when it is refused: the previous set stays.
+int mbn_ragged_readout_plan(mbn_ragged_readout *r, hipStream_t s, int rows, int cols, int classes, const mbn_label_item *items, int batch)
+{
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return MBN_EINVAL;      // a set is not part of a graph
     mbn_resample_launch_t l = { 0, 0, 0, 0, 0, 0 };
     const int rc = mbn_resample_ragged_check(rows, cols, classes, items, batch, r->sort, &l);
     if (rc != MBN_OK) return rc;
-    MBN_HIP_TRY(ctx, hipEventSynchronize(r->done));
-    ReadoutHead *h = (ReadoutHead *)r->host;
-    memset(h, 0, sizeof *h);
-    h->batch = batch; h->generation = r->generation + 1;
-    memcpy(h + 1, items, (size_t)batch * sizeof(mbn_label_item));
-    r->batch = 0;                                               // from here on a failure leaves the handle without a batch
-    MBN_HIP_TRY(ctx, hipMemcpyAsync(r->dev, r->host, 16 * ((size_t)batch + 1), hipMemcpyHostToDevice, s));
-    MBN_HIP_TRY(ctx, hipEventRecord(r->done, s));
-    r->generation = h->generation;
-    r->rows = rows; r->cols = cols; r->classes = classes;
-    r->launch = l;
-    r->batch = batch;
-    return MBN_OK;
+    return readout_upload(r, s, rows, cols, classes, 0, 0, 0, items, sizeof(mbn_label_item), batch, l);
+}
+
+// The window set: the same, with every item's own rectangle of the in_rows x in_cols network input.
+int mbn_ragged_readout_plan_window(mbn_ragged_readout *r, hipStream_t s, int rows, int cols, int classes, int in_rows, int in_cols,
+                                   const mbn_label_window_item *items, int batch)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return MBN_EINVAL;
+    mbn_resample_launch_t l = { 0, 0, 0, 0, 0, 0 };
+    const int rc = mbn_resample_ragged_window_check(rows, cols, classes, in_rows, in_cols, items, batch, r->sort, &l);
+    if (rc != MBN_OK) return rc;
+    return readout_upload(r, s, rows, cols, classes, 1, in_rows, in_cols, items, sizeof(mbn_label_window_item), batch, l);
 }
 
 // the handle has a batch, the pointers are non-null multiples of 4 and the spans fit (the caller has checked)
@@ -293,10 +378,16 @@ int mbn_launch_f32_resample_argmax_ragged(mbn_ragged_readout *r, hipStream_t s, 
     a.fy = r->launch.fy; a.fx = r->launch.fx; a.ch = r->launch.ch;
     a.head = (const ReadoutHead *)r->dev;
     a.items = (const mbn_label_item *)(a.head + 1);
+    a.witems = (const mbn_label_window_item *)(a.head + 1);     // the last set decides which of the two the block holds
+    a.in_rows = r->in_rows; a.in_cols = r->in_cols;
     a.generation = r->generation;
     const dim3 grid((unsigned)r->launch.tiles, (unsigned)r->batch);
-    if (vec_loads(logits, r->classes)) hipLaunchKernelGGL((resample_argmax_ragged_f32<true>), grid, dim3(256), (size_t)r->launch.lds_bytes, s, a);
-    else hipLaunchKernelGGL((resample_argmax_ragged_f32<false>), grid, dim3(256), (size_t)r->launch.lds_bytes, s, a);
+    const bool vec = vec_loads(logits, r->classes);
+    if (r->window) {
+        if (vec) hipLaunchKernelGGL((resample_argmax_ragged_f32<true, true>), grid, dim3(256), (size_t)r->launch.lds_bytes, s, a);
+        else hipLaunchKernelGGL((resample_argmax_ragged_f32<false, true>), grid, dim3(256), (size_t)r->launch.lds_bytes, s, a);
+    } else if (vec) hipLaunchKernelGGL((resample_argmax_ragged_f32<true, false>), grid, dim3(256), (size_t)r->launch.lds_bytes, s, a);
+    else hipLaunchKernelGGL((resample_argmax_ragged_f32<false, false>), grid, dim3(256), (size_t)r->launch.lds_bytes, s, a);
     // the next set waits for this launch; inside a capture there is nothing to wait for (the replays are the caller's to order)
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) (void)hipEventRecord(r->done, s);

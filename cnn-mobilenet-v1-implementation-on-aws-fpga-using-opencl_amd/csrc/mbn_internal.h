@@ -57,9 +57,10 @@ struct mbn_ragged_readout {
     int max_batch = 0;
     int batch = 0;                               // of the last successful set; 0 = none
     int rows = 0, cols = 0, classes = 0;         // its coarse map
+    int window = 0, in_rows = 0, in_cols = 0;    // a window set (mbn_ragged_readout_set_window): the network input its rectangles lie in
     mbn_resample_launch_t launch = {};           // its launch: LDS footprint, class chunk, grid.x, the elements of labels / score it reaches
     int generation = 0;                          // counts the sets: a captured launch replayed after another set does nothing
-    void *dev = nullptr, *host = nullptr;        // 16-byte head + mbn_label_item [max_batch]
+    void *dev = nullptr, *host = nullptr;        // 16-byte head + mbn_label_item or mbn_label_window_item [max_batch] (sized for the latter)
     int64_t *sort = nullptr;                     // [2 * max_batch]: the overlap check's scratch, so that a set allocates nothing
     hipEvent_t done = nullptr;                   // behind the last upload or launch: the next set waits for it
 };
@@ -276,9 +277,13 @@ int mbn_launch_f32_upsample_argmax(mbn_context *ctx, hipStream_t s, int32_t *lab
 // mbn_resample_argmax_envelope. Ragged form: build allocates, plan checks a batch (a refused one changes nothing) and enqueues the items' upload
 int mbn_launch_f32_resample_argmax(mbn_context *ctx, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows, int cols,
                                    int classes, int out_rows, int out_cols);
+int mbn_launch_f32_resample_argmax_window(mbn_context *ctx, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows,
+                                          int cols, int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols);
 int mbn_ragged_readout_build(mbn_context *ctx, int max_batch, mbn_ragged_readout **r);
 void mbn_ragged_readout_release(mbn_ragged_readout *r);
 int mbn_ragged_readout_plan(mbn_ragged_readout *r, hipStream_t s, int rows, int cols, int classes, const mbn_label_item *items, int batch);
+int mbn_ragged_readout_plan_window(mbn_ragged_readout *r, hipStream_t s, int rows, int cols, int classes, int in_rows, int in_cols,
+                                   const mbn_label_window_item *items, int batch);
 int mbn_launch_f32_resample_argmax_ragged(mbn_ragged_readout *r, hipStream_t s, int32_t *labels, float *score, const float *logits);
 // resize front-end (mbn_u8_resize.hip): the geometry is inside mbn_resize_envelope; build uploads the tables (blocking), release frees them
 int mbn_resizer_build(mbn_context *ctx, int filter, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r);

@@ -141,6 +141,64 @@ int mbn_resample_ragged_check(int rows, int cols, int classes, const mbn_label_i
     return MBN_OK;
 }
 
+int mbn_resample_window_envelope(int batch, int rows, int cols, int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows,
+                                 int out_cols)
+{
+    if (batch <= 0 || rows <= 0 || cols <= 0 || classes <= 0 || in_rows <= 0 || in_cols <= 0 || out_rows <= 0 || out_cols <= 0 || !rect)
+        return MBN_EINVAL;
+    const int64_t x = rect[0], y = rect[1], iw = rect[2], ih = rect[3];
+    if (x < 0 || y < 0 || iw < 1 || ih < 1 || x + iw > in_cols || y + ih > in_rows || in_rows < rows || in_cols < cols) return MBN_EINVAL;
+    if (batch > MBN_DENSE_MAX_BATCH || out_rows > MBN_RESAMPLE_MAX_OUT || out_cols > MBN_RESAMPLE_MAX_OUT || in_rows > MBN_RESAMPLE_MAX_OUT ||
+        in_cols > MBN_RESAMPLE_MAX_OUT)
+        return MBN_EUNSUPPORTED;
+    /* the ratio of the output to the coarse samples under the window: N R >= 4 l n */
+    if ((int64_t)out_rows * in_rows < MBN_RESAMPLE_MIN_RATIO * ih * rows || (int64_t)out_cols * in_cols < MBN_RESAMPLE_MIN_RATIO * iw * cols)
+        return MBN_EUNSUPPORTED;
+    if (4.0 * rows * cols * classes >= 2147483648.0) return MBN_EUNSUPPORTED;                                   /* an image's logits */
+    if (4.0 * out_rows * out_cols >= 2147483648.0) return MBN_EUNSUPPORTED;                                     /* an image's labels / scores */
+    if ((long)((out_rows + MBN_RESAMPLE_TILE - 1) / MBN_RESAMPLE_TILE) * ((out_cols + MBN_RESAMPLE_TILE - 1) / MBN_RESAMPLE_TILE) > MBN_DENSE_MAX_TILES)
+        return MBN_EUNSUPPORTED;
+    return MBN_OK;
+}
+
+void mbn_resample_window_plan(int rows, int cols, int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols,
+                              mbn_resample_launch_t *l)
+{
+    const int fy = MBN_RESAMPLE_WINDOW_FOOT(rows, out_rows, in_rows, rect[3]), fx = MBN_RESAMPLE_WINDOW_FOOT(cols, out_cols, in_cols, rect[2]);
+    const int tiles = ((out_rows + MBN_RESAMPLE_TILE - 1) / MBN_RESAMPLE_TILE) * ((out_cols + MBN_RESAMPLE_TILE - 1) / MBN_RESAMPLE_TILE);
+    if (fy > l->fy) l->fy = fy;
+    if (fx > l->fx) l->fx = fx;
+    if (tiles > l->tiles) l->tiles = tiles;
+    if ((int64_t)out_rows * out_cols > l->span) l->span = (int64_t)out_rows * out_cols;
+    l->ch = MBN_RESAMPLE_CH(l->fy * l->fx);
+    l->lds_bytes = l->fy * l->fx * (l->ch + 4) * 4;
+}
+
+int mbn_resample_ragged_window_check(int rows, int cols, int classes, int in_rows, int in_cols, const mbn_label_window_item *items, int batch,
+                                     int64_t *sort, mbn_resample_launch_t *l)
+{
+    if (!items || !sort || !l || batch <= 0) return MBN_EINVAL;
+    const mbn_resample_launch_t zero = { 0, 0, 0, 0, 0, 0 };
+    mbn_resample_launch_t acc = zero;
+    int64_t span = 0;
+    for (int i = 0; i < batch; i++) {
+        if (items[i].dst_offset < 0) return MBN_EINVAL;
+        const int32_t rect[4] = { items[i].x, items[i].y, items[i].iw, items[i].ih };
+        const int rc = mbn_resample_window_envelope(batch, rows, cols, classes, in_rows, in_cols, rect, items[i].rows, items[i].cols);
+        if (rc != MBN_OK) return rc;
+        mbn_resample_window_plan(rows, cols, in_rows, in_cols, rect, items[i].rows, items[i].cols, &acc);
+        sort[2 * i] = items[i].dst_offset;
+        sort[2 * i + 1] = items[i].dst_offset + (int64_t)items[i].rows * items[i].cols;
+        if (sort[2 * i + 1] > span) span = sort[2 * i + 1];
+    }
+    qsort(sort, (size_t)batch, 2 * sizeof(int64_t), cmp_i64_pair);
+    for (int i = 0; i + 1 < batch; i++)
+        if (sort[2 * i + 1] > sort[2 * i + 2]) return MBN_EINVAL;                                               /* two maps overlap */
+    acc.span = span;
+    *l = acc;
+    return MBN_OK;
+}
+
 static long lmin(long a, long b) { return a < b ? a : b; }
 
 int mbn_i8_pw_plan(long m, int cin, int op_size, int num_cus, int operands_on_16, int out_f32, mbn_i8_pw_plan_t *p)

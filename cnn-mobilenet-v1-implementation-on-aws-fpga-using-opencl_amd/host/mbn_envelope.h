@@ -82,6 +82,23 @@ void mbn_resample_plan(int rows, int cols, int out_rows, int out_cols, mbn_resam
  * dst_offset or two items whose maps overlap; MBN_EUNSUPPORTED for an item outside the per-image part of mbn_resample_argmax_envelope or a batch
  * above 65535. sort: scratch of 2 * batch int64. *l: the launch of the whole batch (span = max(dst_offset + rows * cols)) */
 int mbn_resample_ragged_check(int rows, int cols, int classes, const mbn_label_item *items, int batch, int64_t *sort, mbn_resample_launch_t *l);
+/* mbn_resample_argmax_window_f32: the same read-out of the window rect = (x, y, iw, ih) of the in_rows x in_cols network input that the rows x cols
+ * map covers. MBN_EINVAL: a non-positive size, a NULL rect, x < 0, y < 0, iw < 1, ih < 1, x + iw > in_cols, y + ih > in_rows, in_rows < rows or
+ * in_cols < cols. Else MBN_EUNSUPPORTED unless out_rows * in_rows >= 4 * ih * rows and out_cols * in_cols >= 4 * iw * cols, the output sides,
+ * in_rows and in_cols are at most MBN_RESAMPLE_MAX_OUT (num < 2^46 and den <= 2^29 of the window rule are then exact in fp64) and the byte, tile
+ * and batch limits of mbn_resample_argmax_envelope hold. MBN_RESAMPLE_WINDOW_FOOT: MBN_RESAMPLE_FOOT with n / N replaced by l n / (N R), in
+ * 64-bit: the coarse samples 32 aligned outputs touch along an axis; for the full window (l = R) it is MBN_RESAMPLE_FOOT(n, N). */
+#define MBN_RESAMPLE_WINDOW_FOOT(n, N, R, l) \
+    (31 * (int64_t)(l) * (n) / ((int64_t)(N) * (R)) + 3 < (n) ? (int)(31 * (int64_t)(l) * (n) / ((int64_t)(N) * (R))) + 3 : (n))
+int mbn_resample_window_envelope(int batch, int rows, int cols, int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows,
+                                 int out_cols);
+/* mbn_resample_plan for a window: widens *l likewise, with the window's footprint. The full window gives exactly mbn_resample_plan's answer */
+void mbn_resample_window_plan(int rows, int cols, int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols,
+                              mbn_resample_launch_t *l);
+/* mbn_resample_ragged_check for the items of mbn_ragged_readout_set_window: the same statuses, overlap sort and scratch, every item under
+ * mbn_resample_window_envelope with its own rectangle; *l is written only when the batch is accepted */
+int mbn_resample_ragged_window_check(int rows, int cols, int classes, int in_rows, int in_cols, const mbn_label_window_item *items, int batch,
+                                     int64_t *sort, mbn_resample_launch_t *l);
 /* resize front-end (mbn_u8_resize.hip): one geometry of mbn_resizer_create. Source sides 1..8192, output sides 1..4096, at most MBN_RESIZE_MAX_KSIZE
  * taps per axis (a 32x downscale; any upscale has 3). box = (left, upper, right, lower), NULL = the whole image. MBN_EINVAL for a non-positive
  * size or a box mbn_resize_ksize refuses, else MBN_EUNSUPPORTED outside the limits. The batch (1..MBN_RESIZE_MAX_BATCH: grid.y) belongs to the call. */

@@ -61,7 +61,7 @@ struct mbn_net {
     mbn_ragged_resizer *ragged;     /* mbn_net_resize_inputs: one ragged resizer of max_batch images, made on the first call */
     mbn_resize_item *ragged_items;  /* ... and the items it is set from, [max_batch] */
     mbn_ragged_readout *readout;    /* mbn_net_segment_images: one ragged read-out of max_batch images, made on the first call */
-    mbn_label_item *label_items;    /* ... and the items it is set from, [max_batch] */
+    void *label_items;              /* ... and the items it is set from, [max_batch] mbn_label_window_item (or as many mbn_label_item) */
     void *poolfc_ws;           /* workspace of mbn_pool_fc (1...4 images: pool + FC in one launch), allocated and zeroed at creation */
     size_t poolfc_ws_bytes;
     int fuse_tail;             /* mbn_net_set_fuse_tail (default 0) */
@@ -930,32 +930,91 @@ int mbn_net_segment_to(mbn_net *net, const void *images, int batch, int out_rows
     return mbn_resample_argmax_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, out_rows, out_cols, NULL);
 }
 
+/* MBN_OK for the fits a source-size read-out exists for; a crop's box is fractional and the network never saw the rest of the image */
+static int segment_fit_status(int fit)
+{
+    if (fit == MBN_FIT_STRETCH || fit == MBN_FIT_PAD) return MBN_OK;
+    return fit == MBN_FIT_CROP ? MBN_EUNSUPPORTED : MBN_EINVAL;
+}
+
+int mbn_net_segment_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, void *labels_i32, void *score_f32)
+{
+    if (!net || !src_u8 || !labels_i32 || batch <= 0 || batch > net->max_batch || in_rows <= 0 || in_cols <= 0) return MBN_EINVAL;
+    if (!net->input_u8) return MBN_EINVAL;                    /* the resized images are uint8: the net must take them as such */
+    int rc = segment_fit_status(fit);
+    if (rc != MBN_OK) return rc;
+    const mbn_layer_desc *feat, *fc;
+    rc = dense_layers(net, &feat, &fc);
+    if (rc != MBN_OK) return rc;
+    const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols, h = feat->out_rows, w = feat->out_cols;
+    int32_t rect[4] = { 0, 0, cols, rows };
+    /* the envelope before the resize and the forward run */
+    if (fit == MBN_FIT_PAD) {
+        rc = mbn_fit_pad(in_rows, in_cols, rows, cols, rect);
+        if (rc == MBN_OK) rc = mbn_resample_window_envelope(batch, h, w, fc->out_ch, rows, cols, rect, in_rows, in_cols);
+        if (rc != MBN_OK) return rc;
+    } else if (mbn_resample_argmax_envelope(batch, h, w, fc->out_ch, in_rows, in_cols) != MBN_OK) return MBN_EUNSUPPORTED;
+    void *images = NULL;
+    rc = mbn_net_resize_input(net, src_u8, batch, in_rows, in_cols, fit, 1.0f, &images);
+    if (rc == MBN_OK) rc = dense_logits_buf(net, feat, fc);
+    if (rc == MBN_OK) rc = mbn_net_forward_dense(net, images, net->dense_logits, batch);
+    if (rc != MBN_OK) return rc;
+    if (fit == MBN_FIT_PAD)
+        return mbn_resample_argmax_window_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, rows, cols, rect, in_rows,
+                                              in_cols, NULL);
+    return mbn_resample_argmax_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, in_rows, in_cols, NULL);
+}
+
 int mbn_net_segment_images(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *in_rows, const int32_t *in_cols, int batch,
                            void *labels_i32, const int64_t *dst_offsets, void *score_f32)
 {
+    return mbn_net_segment_images_fit(net, src_u8, offsets, in_rows, in_cols, batch, MBN_FIT_STRETCH, labels_i32, dst_offsets, score_f32);
+}
+
+int mbn_net_segment_images_fit(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *in_rows, const int32_t *in_cols, int batch,
+                               int fit, void *labels_i32, const int64_t *dst_offsets, void *score_f32)
+{
     if (!net || !src_u8 || !offsets || !in_rows || !in_cols || !labels_i32 || !dst_offsets || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
     if (!net->input_u8) return MBN_EINVAL;                    /* the resized images are uint8: the net must take them as such */
-    const mbn_layer_desc *feat, *fc;
-    int rc = dense_layers(net, &feat, &fc);
+    int rc = segment_fit_status(fit);
     if (rc != MBN_OK) return rc;
+    const mbn_layer_desc *feat, *fc;
+    rc = dense_layers(net, &feat, &fc);
+    if (rc != MBN_OK) return rc;
+    const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols;
     if (!net->label_items) {
-        net->label_items = malloc((size_t)net->max_batch * sizeof(mbn_label_item));
+        net->label_items = malloc((size_t)net->max_batch * sizeof(mbn_label_window_item));       /* either kind of item */
         if (!net->label_items) return MBN_ENOMEM;
     }
-    for (int i = 0; i < batch; i++) {
-        net->label_items[i].dst_offset = dst_offsets[i];
-        net->label_items[i].rows = in_rows[i];
-        net->label_items[i].cols = in_cols[i];
+    if (fit == MBN_FIT_PAD) {
+        mbn_label_window_item *items = net->label_items;
+        for (int i = 0; i < batch; i++) {
+            int32_t rect[4];
+            rc = mbn_fit_pad(in_rows[i], in_cols[i], rows, cols, rect);
+            if (rc != MBN_OK) return rc;
+            items[i].dst_offset = dst_offsets[i];
+            items[i].rows = in_rows[i];
+            items[i].cols = in_cols[i];
+            items[i].x = rect[0]; items[i].y = rect[1]; items[i].iw = rect[2]; items[i].ih = rect[3];
+        }
+    } else {
+        mbn_label_item *items = net->label_items;
+        for (int i = 0; i < batch; i++) {
+            items[i].dst_offset = dst_offsets[i];
+            items[i].rows = in_rows[i];
+            items[i].cols = in_cols[i];
+        }
     }
     if (!net->readout) {
         rc = mbn_ragged_readout_create(net->ctx, net->max_batch, &net->readout);
         if (rc != MBN_OK) { net->readout = NULL; return rc; }
     }
     /* the set first: it checks every item, so a refusal comes before the resize and the forward run; its upload is ordered by the stream */
-    rc = mbn_ragged_readout_set(net->readout, feat->out_rows, feat->out_cols, fc->out_ch, net->label_items, batch, NULL);
+    rc = fit == MBN_FIT_PAD ? mbn_ragged_readout_set_window(net->readout, feat->out_rows, feat->out_cols, fc->out_ch, rows, cols, net->label_items, batch, NULL)
+                            : mbn_ragged_readout_set(net->readout, feat->out_rows, feat->out_cols, fc->out_ch, net->label_items, batch, NULL);
     if (rc != MBN_OK) return rc;
     void *images = NULL;
-    rc = mbn_net_resize_inputs(net, src_u8, offsets, in_rows, in_cols, batch, MBN_FIT_STRETCH, 1.0f, &images);
+    rc = mbn_net_resize_inputs(net, src_u8, offsets, in_rows, in_cols, batch, fit, 1.0f, &images);
     if (rc == MBN_OK) rc = dense_logits_buf(net, feat, fc);
     if (rc == MBN_OK) rc = mbn_net_forward_dense(net, images, net->dense_logits, batch);
     if (rc != MBN_OK) return rc;

@@ -14,8 +14,10 @@
  *   --filter nearest | box | bilinear (default) | hamming | bicubic | lanczos: Pillow's filter of that resize (mbn_net_set_resize_filter). Several --ppm
  *   take the ragged launch, which has no hamming and no lanczos (their weights need the host's sin / cos): usage status 2
  *   --segment FILE: after the classification, the dense head (mbn_net_segment): the label map of image 0 as a binary PGM and its five most frequent labels
- *   --segment-source FILE: the label map of image 0 at that --ppm file's OWN width x height (needs --ppm and --fit stretch, else usage status 2): one --ppm
- *   goes through mbn_net_resize_input + mbn_net_segment_to, several through mbn_net_segment_images (one ragged resize, one ragged read-out)
+ *   --segment-source FILE: the label map of image 0 at that --ppm file's OWN width x height (needs --ppm and --fit stretch or --fit pad, else usage
+ *   status 2: a crop has no labels for the rest of the image). stretch: one --ppm goes through mbn_net_resize_input + mbn_net_segment_to, several
+ *   through mbn_net_segment_images (one ragged resize, one ragged read-out); pad: mbn_net_segment_fit / mbn_net_segment_images_fit, the read-out of
+ *   the letterbox's rectangle, so the image is labelled undistorted
  *   mobilenet --literal [--weights weights_c.txt] [--image Cat_Image0.ppm] [--ref-args]      the reference's own mode
  *   mobilenet --gpus G --batch N [--steps K --warmup W --streams S --pw-emul 6] (--h5 F | --synthetic SEED)  N images sharded over G GPUs
  *   mobilenet --inspect weights.h5                                                             list the datasets of a .h5
@@ -392,8 +394,9 @@ static int ppm_size(const char *path, int *width, int *height)
 #define PPM_MAX_SIDE 8192     /* the resize front-end's largest source side */
 
 /* --segment-source: the --ppm files again, at their own sizes, one behind the other in ONE device buffer; image 0's label map at its own size.
- * One file: mbn_net_resize_input (stretch) + mbn_net_segment_to; several: mbn_net_segment_images. The net takes uint8 images (the caller has set that) */
-static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int n_ppm, const char *path, int classes)
+ * One file: mbn_net_resize_input (stretch) + mbn_net_segment_to; several: mbn_net_segment_images. Under --fit pad mbn_net_segment_fit /
+ * mbn_net_segment_images_fit, the read-out through the letterbox. The net takes uint8 images (the caller has set that) */
+static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int n_ppm, const char *path, int classes, int fit)
 {
     int64_t *offs = malloc(sizeof(int64_t) * (size_t)n_ppm), *dst = malloc(sizeof(int64_t) * (size_t)n_ppm);
     int32_t *hs = malloc(sizeof(int32_t) * (size_t)n_ppm), *ws = malloc(sizeof(int32_t) * (size_t)n_ppm);
@@ -420,7 +423,10 @@ static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int
     CHECK(mbn_alloc(ctx, total, &d_src));
     CHECK(mbn_alloc(ctx, sizeof(int) * pixels, &d_labels));
     CHECK(mbn_upload(ctx, d_src, all, total));
-    if (n_ppm == 1) {
+    if (fit == MBN_FIT_PAD) {
+        if (n_ppm == 1) CHECK(mbn_net_segment_fit(net, d_src, 1, hs[0], ws[0], MBN_FIT_PAD, d_labels, NULL));
+        else CHECK(mbn_net_segment_images_fit(net, d_src, offs, hs, ws, n_ppm, MBN_FIT_PAD, d_labels, dst, NULL));
+    } else if (n_ppm == 1) {
         CHECK(mbn_net_resize_input(net, d_src, 1, hs[0], ws[0], MBN_FIT_STRETCH, 1.0f, &d_img));
         CHECK(mbn_net_segment_to(net, d_img, 1, hs[0], ws[0], d_labels, NULL));
     } else {
@@ -521,7 +527,10 @@ int main(int argc, char **argv)
         return 2;
     }
     if (n_ppm == 1) ppm = ppms[0];
-    if (segment_src && (n_ppm < 1 || fit != MBN_FIT_STRETCH)) { fprintf(stderr, "--segment-source needs --ppm and --fit stretch\n"); return 2; }
+    if (segment_src && (n_ppm < 1 || (fit != MBN_FIT_STRETCH && fit != MBN_FIT_PAD))) {
+        fprintf(stderr, "--segment-source needs --ppm and --fit stretch or --fit pad\n");
+        return 2;
+    }
     if (out_stride != 0 && out_stride != 8 && out_stride != 16 && out_stride != 32) { fprintf(stderr, "bad --output-stride (32, 16 or 8)\n"); return 2; }
     mbn_context *ctx = NULL;
     if (gpus > 0 && !literal) {
@@ -670,7 +679,7 @@ int main(int argc, char **argv)
                    rect[3], rect[0], rect[1]);
     }
     if (segment_src) {
-        const int bad = segment_source(ctx, net, ppms, n_ppm, segment_src, classes);
+        const int bad = segment_source(ctx, net, ppms, n_ppm, segment_src, classes, fit);
         if (bad) return bad;
     }
     mbn_net_destroy(net);

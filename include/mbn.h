@@ -430,6 +430,37 @@ int mbn_ragged_readout_create(mbn_context *ctx, int max_batch, mbn_ragged_readou
 int mbn_ragged_readout_set(mbn_ragged_readout *r, int rows, int cols, int classes, const mbn_label_item *items, int batch, void *stream);
 int mbn_resample_argmax_ragged_f32(mbn_ragged_readout *r, void *labels_i32, void *score_f32, const void *logits, void *stream);
 int mbn_ragged_readout_destroy(mbn_ragged_readout *r);
+/* Segment through the letterbox: the same read-out of a WINDOW of the network's input instead of the whole coarse map, so that the labels of an
+ * image that went through MBN_FIT_PAD come out at the source size, one per source pixel, without the distortion of a stretch.
+ * The coarse map has n samples along an axis and covers R network-input pixels (R = in_rows or in_cols; R / n need not be an integer). A window
+ * [b, b + l) of those R pixels (integers, b >= 0, l >= 1, b + l <= R) is resampled to N outputs: output o sits at input coordinate
+ * b + (o + 1/2) * l / N, that is at map coordinate u = (b + (o + 1/2) * l / N) * n / R - 1/2. Normative (tests/dense_window_ref.py reproduces it bit
+ * for bit in numpy), all integers 64-bit:
+ *     num = max((2*o + 1) * l * n + 2 * b * n * N - N * R, 0);   den = 2 * N * R;
+ *     i0  = num / den;   i1 = min(i0 + 1, n - 1);
+ *     w1  = (float)((double)(num % den) / (double)den);   w0 = 1.0f - w1;
+ * i0 <= n - 1 follows from b + l <= R. There is NO clamp at the window's edge: an output next to the letterbox border interpolates with the coarse
+ * samples outside the rectangle, which is the true bilinear value of the logits there (a zero weight still multiplies). The interpolation order, the
+ * per-operation rounding and the argmax rule are those of mbn_resample_argmax_f32 unchanged. With b = 0, l = R the rule is mbn_resample_argmax_f32's
+ * bit for bit (num and den are R times its own: the same rational, both fp64 operands exact); a window with R * N / l and b * N / l integers gives
+ * rows b * N / l ... of mbn_resample_argmax_f32's resample to R * N / l bit for bit.
+ * rect = (x, y, iw, ih), ordered as mbn_fit_pad writes it: columns [x, x + iw), rows [y, y + ih) of the in_rows x in_cols input.
+ *   mbn_resample_argmax_window_f32  logits [batch][rows][cols][classes] -> labels_i32 (and score_f32, may be NULL) [batch][out_rows][out_cols], one
+ *                                   rectangle for the whole batch. MBN_EINVAL: NULL labels / logits / rect, a pointer off 4 bytes, a non-positive
+ *                                   size, x < 0, y < 0, iw < 1, ih < 1, a rectangle reaching past in_cols / in_rows, in_rows < rows or
+ *                                   in_cols < cols. MBN_EUNSUPPORTED unless out_rows * in_rows >= 4 * ih * rows and out_cols * in_cols >=
+ *                                   4 * iw * cols (the tile then touches at most 10 x 10 coarse vectors, as above), the output sides, in_rows and
+ *                                   in_cols are at most 16384 (num < 2^46 and den <= 2^29 are then exact in fp64) and the byte and batch limits of
+ *                                   mbn_resample_argmax_f32 hold. Nothing is launched on a refusal. The mbn_alloc bounds rule applies
+ *   mbn_ragged_readout_set_window   a set whose image i has its own rectangle: mbn_label_window_item, 32 bytes (mbn_label_item keeps its 16). The
+ *                                   checks of mbn_ragged_readout_set plus the ones above per item; a REFUSED set changes nothing. After it
+ *                                   mbn_resample_argmax_ragged_f32 launches the window kernel, after a plain set the kernel it always launched. A
+ *                                   captured launch replayed after ANY later set, of either kind, does nothing */
+typedef struct mbn_label_window_item { int64_t dst_offset; int32_t rows, cols; int32_t x, y, iw, ih; } mbn_label_window_item;
+int mbn_resample_argmax_window_f32(mbn_context *ctx, void *labels_i32, void *score_f32, const void *logits, int batch, int rows, int cols, int classes,
+                                   int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols, void *stream);
+int mbn_ragged_readout_set_window(mbn_ragged_readout *r, int rows, int cols, int classes, int in_rows, int in_cols,
+                                  const mbn_label_window_item *items, int batch, void *stream);
 /* The classifier tail of the sequence as one call (MobileNet.c:2601-2792): global average pool (kernel.cl:116) ->
  * FC = pointwise with rows = cols = 1 (kernel.cl:94; bias, no ReLU: B15) -> softmax + top-k. fp32 NHWC,
  * in [batch][rows][cols][channels], fc_w [classes][channels], fc_bias [classes] or NULL; pooled_scratch
@@ -853,8 +884,9 @@ int  mbn_net_get_resize_filter(const mbn_net *net, int *filter);
 /* MBN_FIT_PAD as the `fit` of mbn_net_resize_input / _inputs: the letterbox of mbn_fit_pad into the plan's rows x cols (mbn_resizer_create_pad /
  * mbn_ragged_resizer_create_pad above); crop_fraction is ignored. The border is the net's pad colour, (0, 0, 0) = Pillow's default until
  * mbn_net_set_pad_color is called (a channel outside 0..255: MBN_EINVAL, nothing changes); the kept resizers are rebuilt on the next call after the
- * fit or the colour changed. No forward path changes. mbn_net_segment_to and mbn_net_segment_images stay stretch-only: after a letterbox the labels
- * of the image are the rectangle mbn_fit_pad gives, in the label map of mbn_net_segment. */
+ * fit or the colour changed. No forward path changes. mbn_net_segment_to and mbn_net_segment_images stay stretch-only; mbn_net_segment_fit and
+ * mbn_net_segment_images_fit below take MBN_FIT_PAD and give the labels of a letterboxed image at its own size (the read-out of the rectangle
+ * mbn_fit_pad gives; cutting that rectangle out of mbn_net_segment's label map gives them at the network's resolution only). */
 int  mbn_net_set_pad_color(mbn_net *net, int r, int g, int b);
 int  mbn_net_get_pad_color(const mbn_net *net, int *r, int *g, int *b);
 int  mbn_net_fused_layers(const mbn_net *net, int last_layer, int *count);
@@ -934,6 +966,20 @@ int  mbn_net_segment(mbn_net *net, const void *images, int batch, void *labels_i
 int  mbn_net_segment_to(mbn_net *net, const void *images, int batch, int out_rows, int out_cols, void *labels_i32, void *score_f32);
 int  mbn_net_segment_images(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *rows, const int32_t *cols, int batch,
                             void *labels_i32, const int64_t *dst_offsets, void *score_f32);
+/* The same under a fit: labels at the source resolution of images that the network saw stretched OR letterboxed.
+ *   mbn_net_segment_fit         uniform sources: src_u8 [batch][in_rows][in_cols][3] uint8 (device). mbn_net_resize_input with `fit`,
+ *                               mbn_net_forward_dense, then the read-out to in_rows x in_cols: labels_i32 (and score_f32, may be NULL)
+ *                               [batch][in_rows][in_cols]. MBN_FIT_STRETCH: mbn_resample_argmax_f32, the labels of mbn_net_segment_to bit for bit.
+ *                               MBN_FIT_PAD: mbn_resample_argmax_window_f32 with mbn_fit_pad's rectangle of the plan's rows x cols, so the border
+ *                               gets no label and the image is not distorted. Needs mbn_net_set_input_u8(net, 1), else MBN_EINVAL
+ *   mbn_net_segment_images_fit  mbn_net_segment_images with a fit: MBN_FIT_STRETCH issues the plain set and the plain kernel, MBN_FIT_PAD ONE
+ *                               window set with every image's own rectangle, then mbn_net_resize_inputs with the fit
+ * MBN_FIT_CROP: MBN_EUNSUPPORTED from both, nothing written. Its box has fractional edges (mbn_fit_box), which the integer window above does not
+ * express, and the network never saw the rest of the image: labels there would be invented. Any other fit: MBN_EINVAL. The envelope (and, ragged,
+ * every item) is checked before the resize and the forward run. */
+int  mbn_net_segment_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, void *labels_i32, void *score_f32);
+int  mbn_net_segment_images_fit(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *rows, const int32_t *cols, int batch,
+                                int fit, void *labels_i32, const int64_t *dst_offsets, void *score_f32);
 /* Per-layer milliseconds of the most recent mbn_net_forward_timed call (hipEvents between layers). */
 int  mbn_net_forward_timed(mbn_net *net, const void *images, void *logits, int batch, float *layer_ms,
                            int n_layer_ms);

@@ -16,6 +16,10 @@
   python tools/dense_bench.py --any [--reps 7] [--steps 20] [--batch 32] [--torch-steps 2] [--no-torch]
       mbn_resample_argmax_f32, the read-out at any output size (main_any): against mbn_upsample_argmax_f32 at equal shapes, to 375 x 500
       against torch, and ragged.
+
+  python tools/dense_bench.py --any --fit pad [--reps 7] [--steps 20] [--batch 32]
+      mbn_resample_argmax_window_f32, the read-out through the letterbox (main_any_pad): against mbn_resample_argmax_f32 to the same 375 x 500,
+      alternating in one process.
 """
 import argparse
 import json
@@ -145,6 +149,58 @@ def main_any(a):
     print(json.dumps(result))
 
 
+def main_any_pad(a):
+    """--any --fit pad: the window kernel against the plain one at equal output size, 375 x 500 from the 28 x 28 and the 14 x 14 map of a
+    224 x 224 input (1000 classes, --batch images of random logits). Per map, alternating within every repetition:
+      plain        mbn_resample_argmax_f32 (what a stretch fit reads out)
+      window_full  mbn_resample_argmax_window_f32 with the whole input as the window: the plain kernel's results, footprint and LDS, so the
+                   difference is the window rule's per-lane set-up alone
+      window_pad   the same with mbn_fit_pad's rectangle of a 375 x 500 source: what segment_fit(FIT_PAD) launches; the larger ratio of the
+                   letterbox shrinks the footprint (printed)
+    Each figure is the median over the repetitions of `steps` back-to-back calls between two stream marks; the runs are kept, and the spread
+    is (max - min) / median of a name's own repetitions."""
+    pkg = import_package()
+    n, rng = a.batch, np.random.default_rng(0)
+    H, W = 375, 500
+    rect = tuple(pkg.fit_pad(H, W, RES, RES))
+    full = (0, 0, RES, RES)
+    result = {"rect": list(rect), "batch": n}
+    with pkg.Context(0) as ctx:
+        d_lab, d_sc = ctx.alloc(n * H * W * 4), ctx.alloc(n * H * W * 4)
+        runs, keep = [], []
+        for hw_ in (28, 14):
+            b = ctx.to_device((3.0 * rng.standard_normal((n, hw_, hw_, CLASSES))).astype(np.float32))
+            keep.append(b)
+            p = b.ptr
+            work = resample_work(n, hw_, hw_, CLASSES, n * H * W)
+            runs.append(("plain_from_%d" % hw_, lambda p=p, hw_=hw_: ctx.resample_argmax(d_lab.ptr, d_sc.ptr, p, n, hw_, hw_, CLASSES, H, W), work,
+                         pkg.resample_plan(hw_, hw_, H, W)))
+            for name, r in (("window_full", full), ("window_pad", rect)):
+                runs.append(("%s_from_%d" % (name, hw_),
+                             lambda p=p, hw_=hw_, r=r: ctx.resample_argmax_window(d_lab.ptr, d_sc.ptr, p, n, hw_, hw_, CLASSES, RES, RES, r, H, W), work,
+                             pkg.resample_window_plan(hw_, hw_, RES, RES, r, H, W)))
+        times = {name: [] for name, _, _, _ in runs}
+        for _, fn, _, _ in runs:
+            marks_ms(ctx, fn, 3)
+        for _ in range(a.reps):
+            for name, fn, _, _ in runs:
+                times[name].append(marks_ms(ctx, fn, a.steps))
+        for name, _, (bytes_, ops), l in runs:
+            k = statistics.median(times[name])
+            result[name] = {"kernel_ms": round(k, 4), "kernel_runs_ms": [round(v, 4) for v in times[name]],
+                            "spread": round((max(times[name]) - min(times[name])) / k, 4), "footprint": [l.fy, l.fx], "lds_bytes": l.lds_bytes,
+                            "kernel_frac_of_valu_rate": round(ops / VALU_LANE_OPS_PER_S / (k / 1e3), 4)}
+            print("%-24s %.4f ms  spread %.1f %%  footprint %d x %d  (%.1f %% of the VALU rate)"
+                  % (name, k, 100 * result[name]["spread"], l.fy, l.fx, 100 * result[name]["kernel_frac_of_valu_rate"]), flush=True)
+        for hw_ in (28, 14):
+            for name in ("window_full", "window_pad"):
+                result["%s_over_plain_from_%d" % (name, hw_)] = round(result["%s_from_%d" % (name, hw_)]["kernel_ms"] /
+                                                                      result["plain_from_%d" % hw_]["kernel_ms"], 4)
+        for b in keep + [d_lab, d_sc]:
+            b.free()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
@@ -154,9 +210,10 @@ def main():
     ap.add_argument("--no-torch", action="store_true", help="skip the torch yardstick")
     ap.add_argument("--any", action="store_true", help="time mbn_resample_argmax_f32 (the read-out at any output size) instead: see main_any")
     ap.add_argument("--torch-steps", type=int, default=2, help="--any: torch calls per repetition (each writes batch x 1000 x 375 x 500 floats)")
+    ap.add_argument("--fit", default="stretch", choices=("stretch", "pad"), help="--any: pad times the window kernel instead: see main_any_pad")
     a = ap.parse_args()
     if a.any:
-        return main_any(a)
+        return main_any_pad(a) if a.fit == "pad" else main_any(a)
     chosen = [c for c in CONFIGS if not a.configs or c[0] in a.configs.split(",")]
     pkg = import_package()
     torch = None
