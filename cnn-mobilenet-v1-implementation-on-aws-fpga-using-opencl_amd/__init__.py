@@ -186,6 +186,7 @@ def _declare_host(lib):
     lib.mbn_quantize_i8.argtypes = [C.POINTER(Plan), C.c_void_p, C.c_void_p, C.POINTER(I8Params), C.c_void_p]
     lib.mbn_upsample_argmax_envelope.argtypes = [C.c_int] * 5      # mbn_envelope.h: exported, not in mbn.h
     lib.mbn_resample_argmax_envelope.argtypes = [C.c_int] * 6      # mbn_envelope.h, like the two below
+    lib.mbn_softmax_readout_check.argtypes = [C.c_int, C.c_float]
     lib.mbn_resample_plan.argtypes = [C.c_int] * 4 + [C.POINTER(ResampleLaunch)]
     lib.mbn_resample_plan.restype = None
     lib.mbn_resample_ragged_check.argtypes = [C.c_int] * 3 + [C.POINTER(LabelItem), C.c_int, C.POINTER(C.c_int64), C.POINTER(ResampleLaunch)]
@@ -335,6 +336,13 @@ def load():
         lib.mbn_net_segment_images_fit.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, ci, vp,
                                                    C.POINTER(C.c_int64), vp]
         lib.mbn_net_segment_to.argtypes = [vp, vp, ci, ci, ci, vp, vp]
+        lib.mbn_resample_softmax_f32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, C.c_float, ci, vp]
+        lib.mbn_resample_softmax_window_f32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(C.c_int32), ci, ci, C.c_float, ci, vp]
+        lib.mbn_resample_softmax_ragged_f32.argtypes = [vp, vp, vp, vp, vp, C.c_float, ci, vp]
+        lib.mbn_net_segment_prob_to.argtypes = [vp, vp, ci, ci, ci, vp, vp, C.c_float, ci]
+        lib.mbn_net_segment_prob_fit.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, C.c_float, ci]
+        lib.mbn_net_segment_prob_images_fit.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, ci, vp,
+                                                        C.POINTER(C.c_int64), vp, C.c_float, ci]
         lib.mbn_net_segment_images.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, vp, C.POINTER(C.c_int64), vp]
         lib.mbn_resizer_create.argtypes = [vp, ci, ci, C.POINTER(C.c_float), ci, ci, C.POINTER(vp)]
         lib.mbn_resize_u8.argtypes = [vp, vp, vp, ci, vp]
@@ -546,6 +554,11 @@ def resample_ragged_window_check(rows, cols, classes, in_rows, in_cols, items, l
     rc = (lib or host_lib()).mbn_resample_ragged_window_check(rows, cols, classes, in_rows, in_cols, arr, len(arr),
                                                               (C.c_int64 * (2 * max(len(arr), 1)))(), C.byref(l))
     return rc, l
+
+
+def softmax_readout_check(have_prob, min_prob, lib=None) -> int:
+    """mbn_softmax_readout_check: the status (OK or EINVAL) the softmax read-outs give min_prob, with or without a prob map."""
+    return (lib or host_lib()).mbn_softmax_readout_check(1 if have_prob else 0, min_prob)
 
 
 def resample_argmax_envelope(batch, rows, cols, classes, out_rows, out_cols, lib=None) -> int:
@@ -775,6 +788,18 @@ class Context:
         _chk(self.lib.mbn_resample_argmax_window_f32(self.h, labels, score, logits, batch, rows, cols, classes, in_rows, in_cols, _rect(rect),
                                                      out_rows, out_cols, None), self.last_error())
 
+    def resample_softmax(self, labels, prob, score, logits, batch, rows, cols, classes, out_rows, out_cols, min_prob=0.0, ignore_label=0):
+        """mbn_resample_softmax_f32: resample_argmax which also writes the softmax probability of the winning class (fp32 `prob`, the shape of the
+        labels; None only with min_prob > 0) and stores ignore_label where that probability is below min_prob. `score` may be None."""
+        _chk(self.lib.mbn_resample_softmax_f32(self.h, labels, prob, score, logits, batch, rows, cols, classes, out_rows, out_cols, min_prob,
+                                               ignore_label, None), self.last_error())
+
+    def resample_softmax_window(self, labels, prob, score, logits, batch, rows, cols, classes, in_rows, in_cols, rect, out_rows, out_cols,
+                                min_prob=0.0, ignore_label=0):
+        """mbn_resample_softmax_window_f32: resample_argmax_window with the probability map and the threshold of resample_softmax."""
+        _chk(self.lib.mbn_resample_softmax_window_f32(self.h, labels, prob, score, logits, batch, rows, cols, classes, in_rows, in_cols, _rect(rect),
+                                                      out_rows, out_cols, min_prob, ignore_label, None), self.last_error())
+
     def __enter__(self):
         return self
 
@@ -810,6 +835,12 @@ class RaggedReadout:
 
     def run(self, labels_ptr, score_ptr, logits_ptr, stream=None):
         _chk(self.ctx.lib.mbn_resample_argmax_ragged_f32(self.h, labels_ptr, score_ptr, logits_ptr, stream), self.ctx.last_error())
+
+    def run_softmax(self, labels_ptr, prob_ptr, score_ptr, logits_ptr, min_prob=0.0, ignore_label=0, stream=None):
+        """mbn_resample_softmax_ragged_f32: run() with the probability map (at the items' offsets, like the score) and the threshold; after
+        either kind of set."""
+        _chk(self.ctx.lib.mbn_resample_softmax_ragged_f32(self.h, labels_ptr, prob_ptr, score_ptr, logits_ptr, min_prob, ignore_label, stream),
+             self.ctx.last_error())
 
     def close(self):
         if self.h:
@@ -1034,6 +1065,26 @@ class Net:
         _chk(self.ctx.lib.mbn_net_segment_images_fit(self.h, src_ptr, (C.c_int64 * n)(*[int(v) for v in offsets]),
                                                      (C.c_int32 * n)(*[int(v) for v in rows]), (C.c_int32 * n)(*[int(v) for v in cols]), n, fit,
                                                      labels_ptr, (C.c_int64 * n)(*[int(v) for v in dst_offsets]), score_ptr), self.ctx.last_error())
+
+    def segment_prob_to(self, images_ptr, batch, out_rows, out_cols, labels_ptr, prob_ptr, min_prob=0.0, ignore_label=0):
+        """mbn_net_segment_prob_to: segment_to with the softmax read-out: int32 labels and the fp32 probability of the winning class
+        [batch][out_rows][out_cols]; a pixel below min_prob holds ignore_label. prob_ptr may be None only with min_prob > 0."""
+        _chk(self.ctx.lib.mbn_net_segment_prob_to(self.h, images_ptr, batch, out_rows, out_cols, labels_ptr, prob_ptr, min_prob, ignore_label),
+             self.ctx.last_error())
+
+    def segment_prob_fit(self, src_ptr, batch, in_rows, in_cols, fit, labels_ptr, prob_ptr, min_prob=0.0, ignore_label=0):
+        """mbn_net_segment_prob_fit: segment_fit (FIT_STRETCH or FIT_PAD) with the softmax read-out of segment_prob_to."""
+        _chk(self.ctx.lib.mbn_net_segment_prob_fit(self.h, src_ptr, batch, in_rows, in_cols, fit, labels_ptr, prob_ptr, min_prob, ignore_label),
+             self.ctx.last_error())
+
+    def segment_prob_images_fit(self, src_ptr, offsets, rows, cols, fit, labels_ptr, dst_offsets, prob_ptr, min_prob=0.0, ignore_label=0):
+        """mbn_net_segment_prob_images_fit: segment_images_fit with the softmax read-out; image i's probabilities at prob_ptr + dst_offsets[i]."""
+        n = len(offsets)
+        assert len(rows) == n and len(cols) == n and len(dst_offsets) == n
+        _chk(self.ctx.lib.mbn_net_segment_prob_images_fit(self.h, src_ptr, (C.c_int64 * n)(*[int(v) for v in offsets]),
+                                                          (C.c_int32 * n)(*[int(v) for v in rows]), (C.c_int32 * n)(*[int(v) for v in cols]), n, fit,
+                                                          labels_ptr, (C.c_int64 * n)(*[int(v) for v in dst_offsets]), prob_ptr, min_prob,
+                                                          ignore_label), self.ctx.last_error())
 
     def resize_input(self, src_ptr, batch, in_rows, in_cols, fit=FIT_CROP, crop_fraction=1.0) -> int:
         """mbn_net_resize_input: uint8 images [batch][in_rows][in_cols][3] of any size -> the net's staging buffer [batch][rows][cols][3] (its

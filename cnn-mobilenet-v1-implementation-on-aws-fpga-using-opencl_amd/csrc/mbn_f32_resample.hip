@@ -24,6 +24,18 @@
 // inner image, instead of the whole map. Only the index / weight rule differs (rs_axis_win: 64-bit integers, still one fp64 division per axis
 // coordinate, once per lane in front of the class loop); the footprint bound holds with n / N replaced by l n / (N R) (host/mbn_envelope.h), so
 // stage, reduce, the cross ballot, the store and the LDS layout are the same code. The other instantiations compile to what they were without it.
+// PROB (mbn_resample_softmax_f32, _window_f32, _ragged_f32; include/mbn.h, "segment with confidence"): the same tile body also keeps the softmax
+// denominator of each of the lane's four pixels and writes prob = 1 / sum_c exp(v_c - best) beside the label; labels and scores are the argmax
+// instantiations' bit for bit (the same v, the same compare). The sum is ONE pass with a LAZY reference: per row a reference `ref` and
+// sum = sum_c exp(v_c - ref). Per four classes the row's maximum m of the four is compared with ref: more than RS_MARGIN = 16 above it, m becomes
+// the reference and the old sum is rescaled by exp(ref - m) < e^-16; then the four add exp(v - ref). So every v seen is at most 16 above ref,
+// best - ref stays in [0, 16], ref is itself a v seen (its term is exp(0) = 1: sum >= 1), and a part of the sum that went through k rescales
+// weighs below classes * e^(-16 (k - 1)) of it: only the first rescale of a part counts, and an ascending ramp costs one rescale per 16 units of
+// logit instead of one per class. That is what keeps the error bound of include/mbn.h for every input. The alternative, a second pass with the
+// final best, stages every chunk and forms every interpolant twice: about 10 plain VALU per pixel and class on top of the same exp, against
+// about 7 issue slots here (subtract, max, multiply, add, v_exp_f32 at two slots, and a quarter of the group's three maxima, subtract and
+// compare). prob = exp(best - ref) / sum at the end, 0 when best is not finite. A NaN v (the padding classes of the dword path among them) is
+// dropped by the maxima, and its difference is replaced by -200 by a max that drops the NaN: it adds exp(-200) = 0, exactly.
 #include "mbn_internal.h"
 #include "mbn_device.h"
 
@@ -56,7 +68,13 @@ struct ResampleArgs {
     int in_rows, in_cols;    // R, C: the network-input pixels the coarse map covers
     int wx, wy, wiw, wih;    // uniform form: the window, ordered as mbn_fit_pad writes it
     const mbn_label_window_item *witems;   // ragged form
+    // PROB instantiations only (likewise behind everything else)
+    float *prob;             // may be null when min_prob > 0
+    float min_prob;          // a pixel whose stored prob is below it gets ignore_label
+    int ignore_label;
 };
+
+constexpr float RS_MARGIN = 16.0f;           // the lazy reference moves when a logit exceeds it by more than this
 
 // a window of the network's input along one axis: [b, b + l) of the R pixels the n coarse samples cover
 struct RsWindow {
@@ -96,16 +114,22 @@ __device__ __forceinline__ void rs_coord(int o, int n, int N, const RsWindow &w,
     else rs_axis(o, n, N, i0, w1);
 }
 
+// exp(d) for the softmax sum: d <= RS_MARGIN, -inf gives 0. One multiply and v_exp_f32 (1 ulp; a result below 2^-126 may flush to 0, far below
+// the bound against a sum of at least 1).
+__device__ __forceinline__ float rs_exp(float d) { return __builtin_amdgcn_exp2f(d * 1.44269504088896341f); }
+
 // The reduce pass of one staged chunk of cn4 classes for a lane's four rows. CROSS: some row of the wave interpolates between (ya + 1, ya + 2), so
 // the third interpolant and the per-row selects are needed; otherwise every row of the wave uses (t0, t1) and neither is formed. The same products
-// and sums in the same order either way.
-template <bool CROSS>
+// and sums in the same order either way. PROB: each row's lazy reference and softmax sum follow v (the file's head); untouched otherwise.
+template <bool CROSS, bool PROB>
 __device__ __forceinline__ void rs_reduce(const float *(&p)[3][2], int cn4, int c0, float wx0, float wx1, const float (&wy0)[RS_ROWS],
-                                          const float (&wy1)[RS_ROWS], const bool (&up)[RS_ROWS], float (&best)[RS_ROWS], int (&label)[RS_ROWS])
+                                          const float (&wy1)[RS_ROWS], const bool (&up)[RS_ROWS], float (&best)[RS_ROWS], int (&label)[RS_ROWS],
+                                          float (&ref)[RS_ROWS], float (&sum)[RS_ROWS])
 {
     constexpr int NT = CROSS ? 3 : 2;
     for (int c = 0; c < cn4; c += 4) {
         f4 v0[NT], v1[NT];
+        float vv[RS_ROWS][4];                                                               // PROB: the four classes' v of each row
 #pragma unroll
         for (int j = 0; j < NT; j++) {
             v0[j] = *reinterpret_cast<const f4 *>(p[j][0] + c);
@@ -121,6 +145,19 @@ __device__ __forceinline__ void rs_reduce(const float *(&p)[3][2], int cn4, int 
                 const float ta = CROSS && up[r] ? t[1] : t[0], tb = CROSS && up[r] ? t[NT - 1] : t[1];
                 const float v = rs_lerp(ta, wy0[r], tb, wy1[r]);                            // then vertical
                 if (v > best[r]) { best[r] = v; label[r] = c0 + c + k; }
+                if (PROB) vv[r][k] = v;
+            }
+        }
+        if (PROB) {
+#pragma clang fp contract(off)                      // the same operations in every instantiation: a pixel's prob does not depend on the kernel
+#pragma unroll
+            for (int r = 0; r < RS_ROWS; r++) {
+                // the reference moves at most once per four classes, to their maximum m (the maxima drop NaNs; an all-NaN m fails the compare, and
+                // so does -inf - -inf): everything seen so far is then at most RS_MARGIN above ref, the four included
+                const float m = __builtin_fmaxf(__builtin_fmaxf(vv[r][0], vv[r][1]), __builtin_fmaxf(vv[r][2], vv[r][3]));
+                if (m - ref[r] > RS_MARGIN) { sum[r] *= rs_exp(ref[r] - m); ref[r] = m; }
+#pragma unroll
+                for (int k = 0; k < 4; k++) sum[r] += rs_exp(__builtin_fmaxf(vv[r][k] - ref[r], -200.0f));     // a NaN difference adds exp(-200) = 0
             }
         }
     }
@@ -128,10 +165,11 @@ __device__ __forceinline__ void rs_reduce(const float *(&p)[3][2], int cn4, int 
 
 // One 32 x 32 tile of one image: src = the image's logits, labels / score = the image's output maps (score may be null), H x W their size.
 // WIN: the outputs resample the window (wy, wx) of the network's input instead of the whole map; only the index / weight rule differs.
-template <bool VEC, bool WIN>
+// PROB: prob = the image's probability map (may be null), written beside the score; a pixel below a.min_prob stores a.ignore_label.
+template <bool VEC, bool WIN, bool PROB>
 __device__ __forceinline__ void resample_tile(const ResampleArgs &a, const float *__restrict__ src, int *__restrict__ labels,
-                                              float *__restrict__ score, int H, int W, int ty, int tx, float *s_x, const RsWindow &wy,
-                                              const RsWindow &wx)
+                                              float *__restrict__ score, float *__restrict__ prob, int H, int W, int ty, int tx, float *s_x,
+                                              const RsWindow &wy, const RsWindow &wx)
 {
     const int tid = threadIdx.x;
     const int ld = a.ch + 4;                  // 16-byte aligned rows, consecutive vectors 4 banks apart
@@ -171,10 +209,10 @@ __device__ __forceinline__ void resample_tile(const ResampleArgs &a, const float
         p[j][1] = s_x + (sy * a.fx + sx1) * ld;
     }
 
-    float best[RS_ROWS];
+    float best[RS_ROWS], ref[RS_ROWS], sum[RS_ROWS];      // ref, sum: the PROB instantiations' lazy reference and softmax sum
     int label[RS_ROWS];
 #pragma unroll
-    for (int r = 0; r < RS_ROWS; r++) { best[r] = -__builtin_inff(); label[r] = 0; }
+    for (int r = 0; r < RS_ROWS; r++) { best[r] = ref[r] = -__builtin_inff(); sum[r] = 0.0f; label[r] = 0; }
     const float nan = __builtin_nanf("");
 
     for (int c0 = 0; c0 < a.classes; c0 += a.ch) {
@@ -197,8 +235,8 @@ __device__ __forceinline__ void resample_tile(const ResampleArgs &a, const float
         __syncthreads();
         // ---- reduce
         if (active) {
-            if (cross) rs_reduce<true>(p, cn4, c0, wx0, wx1, wy0, wy1, up, best, label);
-            else rs_reduce<false>(p, cn4, c0, wx0, wx1, wy0, wy1, up, best, label);
+            if (cross) rs_reduce<true, PROB>(p, cn4, c0, wx0, wx1, wy0, wy1, up, best, label, ref, sum);
+            else rs_reduce<false, PROB>(p, cn4, c0, wx0, wx1, wy0, wy1, up, best, label, ref, sum);
         }
         __syncthreads();
     }
@@ -207,28 +245,47 @@ __device__ __forceinline__ void resample_tile(const ResampleArgs &a, const float
 #pragma unroll
     for (int r = 0; r < RS_ROWS; r++) {
         if (oy0 + r >= H) break;
+        if (PROB) {
+            // a finite best has a finite ref <= best <= ref + RS_MARGIN and a sum >= 1 that holds best's own term: 0 < pr <= 1
+            const float pr = __builtin_fabsf(best[r]) < __builtin_inff() ? rs_exp(best[r] - ref[r]) / sum[r] : 0.0f;
+            if (pr < a.min_prob) label[r] = a.ignore_label;                                 // strict, on the value stored below
+            if (prob) prob[out + (unsigned)(r * W)] = pr;
+        }
         labels[out + (unsigned)(r * W)] = label[r];
         if (score) score[out + (unsigned)(r * W)] = best[r];
     }
+}
+
+template <bool VEC, bool WIN, bool PROB>
+__device__ __forceinline__ void resample_uniform(const ResampleArgs &a, float *s_rs)
+{
+    const int ty = (int)blockIdx.x / a.tiles_x, tx = (int)blockIdx.x - ty * a.tiles_x;
+    const size_t img = (size_t)blockIdx.y;                                                      // 64-bit base, 32-bit offsets inside an image
+    const size_t map = (size_t)a.out_rows * a.out_cols;
+    const RsWindow wy = { a.in_rows, a.wy, a.wih }, wx = { a.in_cols, a.wx, a.wiw };          // read by the WIN instantiations only
+    resample_tile<VEC, WIN, PROB>(a, a.logits + img * ((size_t)a.rows * a.cols * a.classes), a.labels + img * map,
+                                  a.score ? a.score + img * map : nullptr, PROB && a.prob ? a.prob + img * map : nullptr, a.out_rows, a.out_cols, ty, tx,
+                                  s_rs, wy, wx);
 }
 
 template <bool VEC, bool WIN>
 __global__ __launch_bounds__(256) void resample_argmax_f32(const ResampleArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float s_rs[];
-    const int ty = (int)blockIdx.x / a.tiles_x, tx = (int)blockIdx.x - ty * a.tiles_x;
-    const size_t img = (size_t)blockIdx.y;                                                      // 64-bit base, 32-bit offsets inside an image
-    const size_t map = (size_t)a.out_rows * a.out_cols;
-    const RsWindow wy = { a.in_rows, a.wy, a.wih }, wx = { a.in_cols, a.wx, a.wiw };          // read by the WIN instantiations only
-    resample_tile<VEC, WIN>(a, a.logits + img * ((size_t)a.rows * a.cols * a.classes), a.labels + img * map, a.score ? a.score + img * map : nullptr,
-                            a.out_rows, a.out_cols, ty, tx, s_rs, wy, wx);
+    resample_uniform<VEC, WIN, false>(a, s_rs);
+}
+
+template <bool VEC, bool WIN>
+__global__ __launch_bounds__(256) void resample_softmax_f32(const ResampleArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_rs[];
+    resample_uniform<VEC, WIN, true>(a, s_rs);
 }
 
 // grid = (tiles of the largest item, batch): a workgroup past its own image's tiles returns before any load or barrier
-template <bool VEC, bool WIN>
-__global__ __launch_bounds__(256) void resample_argmax_ragged_f32(const ResampleArgs a)
+template <bool VEC, bool WIN, bool PROB>
+__device__ __forceinline__ void resample_ragged(const ResampleArgs &a, float *s_rs)
 {
-    extern __shared__ __attribute__((aligned(16))) float s_rs[];
     // a replay of a captured launch after another set: the items are no longer the ones its grid, LDS and spans were checked for
     if (a.head->generation != a.generation || (int)blockIdx.y >= a.head->batch) return;
     if (WIN) {
@@ -238,8 +295,9 @@ __global__ __launch_bounds__(256) void resample_argmax_ragged_f32(const Resample
         if (ty >= tiles_y) return;
         const size_t img = (size_t)blockIdx.y;
         const RsWindow wy = { a.in_rows, it.y, it.ih }, wx = { a.in_cols, it.x, it.iw };
-        resample_tile<VEC, true>(a, a.logits + img * ((size_t)a.rows * a.cols * a.classes), a.labels + it.dst_offset,
-                                 a.score ? a.score + it.dst_offset : nullptr, it.rows, it.cols, ty, tx, s_rs, wy, wx);
+        resample_tile<VEC, true, PROB>(a, a.logits + img * ((size_t)a.rows * a.cols * a.classes), a.labels + it.dst_offset,
+                                       a.score ? a.score + it.dst_offset : nullptr, PROB && a.prob ? a.prob + it.dst_offset : nullptr, it.rows,
+                                       it.cols, ty, tx, s_rs, wy, wx);
         return;
     }
     const mbn_label_item it = a.items[blockIdx.y];
@@ -248,17 +306,53 @@ __global__ __launch_bounds__(256) void resample_argmax_ragged_f32(const Resample
     if (ty >= tiles_y) return;
     const size_t img = (size_t)blockIdx.y;
     const RsWindow none = { 0, 0, 0 };
-    resample_tile<VEC, false>(a, a.logits + img * ((size_t)a.rows * a.cols * a.classes), a.labels + it.dst_offset,
-                              a.score ? a.score + it.dst_offset : nullptr, it.rows, it.cols, ty, tx, s_rs, none, none);
+    resample_tile<VEC, false, PROB>(a, a.logits + img * ((size_t)a.rows * a.cols * a.classes), a.labels + it.dst_offset,
+                                    a.score ? a.score + it.dst_offset : nullptr, PROB && a.prob ? a.prob + it.dst_offset : nullptr, it.rows, it.cols,
+                                    ty, tx, s_rs, none, none);
+}
+
+template <bool VEC, bool WIN>
+__global__ __launch_bounds__(256) void resample_argmax_ragged_f32(const ResampleArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_rs[];
+    resample_ragged<VEC, WIN, false>(a, s_rs);
+}
+
+template <bool VEC, bool WIN>
+__global__ __launch_bounds__(256) void resample_softmax_ragged_f32(const ResampleArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_rs[];
+    resample_ragged<VEC, WIN, true>(a, s_rs);
 }
 
 bool vec_loads(const float *logits, int classes) { return ((uintptr_t)logits % 16) == 0 && (classes % 4) == 0; }   // every class vector then starts on 16 bytes
+
+// q: the softmax read-out's extras, null for the argmax read-out
+void set_prob(ResampleArgs &a, const mbn_readout_prob *q)
+{
+    if (!q) return;
+    a.prob = q->prob; a.min_prob = q->min_prob; a.ignore_label = q->ignore_label;
+}
+
+// one of the eight kernels of a form: K = the argmax kernel template, KP = the softmax one
+#define RS_LAUNCH(K, KP, vec, win, prob, grid, lds, s, a)                                                          \
+    do {                                                                                                           \
+        if (prob) {                                                                                                \
+            if (win) { if (vec) hipLaunchKernelGGL((KP<true, true>), grid, dim3(256), lds, s, a);                  \
+                       else hipLaunchKernelGGL((KP<false, true>), grid, dim3(256), lds, s, a); }                   \
+            else if (vec) hipLaunchKernelGGL((KP<true, false>), grid, dim3(256), lds, s, a);                       \
+            else hipLaunchKernelGGL((KP<false, false>), grid, dim3(256), lds, s, a);                               \
+        } else if (win) { if (vec) hipLaunchKernelGGL((K<true, true>), grid, dim3(256), lds, s, a);                \
+                          else hipLaunchKernelGGL((K<false, true>), grid, dim3(256), lds, s, a); }                 \
+        else if (vec) hipLaunchKernelGGL((K<true, false>), grid, dim3(256), lds, s, a);                            \
+        else hipLaunchKernelGGL((K<false, false>), grid, dim3(256), lds, s, a);                                    \
+    } while (0)
 
 }   // namespace
 
 // The shape is inside mbn_resample_argmax_envelope and the pointers are non-null multiples of 4 (the caller has checked both).
 int mbn_launch_f32_resample_argmax(mbn_context *, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows, int cols,
-                                   int classes, int out_rows, int out_cols)
+                                   int classes, int out_rows, int out_cols, const mbn_readout_prob *q)
 {
     mbn_resample_launch_t l = { 0, 0, 0, 0, 0, 0 };
     mbn_resample_plan(rows, cols, out_rows, out_cols, &l);
@@ -268,15 +362,16 @@ int mbn_launch_f32_resample_argmax(mbn_context *, hipStream_t s, int32_t *labels
     a.out_rows = out_rows; a.out_cols = out_cols;
     a.tiles_x = (out_cols + RS_TILE - 1) / RS_TILE;
     a.fy = l.fy; a.fx = l.fx; a.ch = l.ch;
+    set_prob(a, q);
     const dim3 grid((unsigned)l.tiles, (unsigned)batch);
-    if (vec_loads(logits, classes)) hipLaunchKernelGGL((resample_argmax_f32<true, false>), grid, dim3(256), (size_t)l.lds_bytes, s, a);
-    else hipLaunchKernelGGL((resample_argmax_f32<false, false>), grid, dim3(256), (size_t)l.lds_bytes, s, a);
+    RS_LAUNCH(resample_argmax_f32, resample_softmax_f32, vec_loads(logits, classes), false, q != nullptr, grid, (size_t)l.lds_bytes, s, a);
     return MBN_OK;
 }
 
 // The shape and the window are inside mbn_resample_window_envelope and the pointers are non-null multiples of 4 (the caller has checked both).
 int mbn_launch_f32_resample_argmax_window(mbn_context *, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows,
-                                          int cols, int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols)
+                                          int cols, int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols,
+                                          const mbn_readout_prob *q)
 {
     mbn_resample_launch_t l = { 0, 0, 0, 0, 0, 0 };
     mbn_resample_window_plan(rows, cols, in_rows, in_cols, rect, out_rows, out_cols, &l);
@@ -288,9 +383,9 @@ int mbn_launch_f32_resample_argmax_window(mbn_context *, hipStream_t s, int32_t 
     a.fy = l.fy; a.fx = l.fx; a.ch = l.ch;
     a.in_rows = in_rows; a.in_cols = in_cols;
     a.wx = rect[0]; a.wy = rect[1]; a.wiw = rect[2]; a.wih = rect[3];
+    set_prob(a, q);
     const dim3 grid((unsigned)l.tiles, (unsigned)batch);
-    if (vec_loads(logits, classes)) hipLaunchKernelGGL((resample_argmax_f32<true, true>), grid, dim3(256), (size_t)l.lds_bytes, s, a);
-    else hipLaunchKernelGGL((resample_argmax_f32<false, true>), grid, dim3(256), (size_t)l.lds_bytes, s, a);
+    RS_LAUNCH(resample_argmax_f32, resample_softmax_f32, vec_loads(logits, classes), true, q != nullptr, grid, (size_t)l.lds_bytes, s, a);
     return MBN_OK;
 }
 
@@ -369,7 +464,8 @@ int mbn_ragged_readout_plan_window(mbn_ragged_readout *r, hipStream_t s, int row
 }
 
 // the handle has a batch, the pointers are non-null multiples of 4 and the spans fit (the caller has checked)
-int mbn_launch_f32_resample_argmax_ragged(mbn_ragged_readout *r, hipStream_t s, int32_t *labels, float *score, const float *logits)
+int mbn_launch_f32_resample_argmax_ragged(mbn_ragged_readout *r, hipStream_t s, int32_t *labels, float *score, const float *logits,
+                                          const mbn_readout_prob *q)
 {
     ResampleArgs a = {};
     a.labels = labels; a.score = score; a.logits = logits;
@@ -381,13 +477,10 @@ int mbn_launch_f32_resample_argmax_ragged(mbn_ragged_readout *r, hipStream_t s, 
     a.witems = (const mbn_label_window_item *)(a.head + 1);     // the last set decides which of the two the block holds
     a.in_rows = r->in_rows; a.in_cols = r->in_cols;
     a.generation = r->generation;
+    set_prob(a, q);
     const dim3 grid((unsigned)r->launch.tiles, (unsigned)r->batch);
-    const bool vec = vec_loads(logits, r->classes);
-    if (r->window) {
-        if (vec) hipLaunchKernelGGL((resample_argmax_ragged_f32<true, true>), grid, dim3(256), (size_t)r->launch.lds_bytes, s, a);
-        else hipLaunchKernelGGL((resample_argmax_ragged_f32<false, true>), grid, dim3(256), (size_t)r->launch.lds_bytes, s, a);
-    } else if (vec) hipLaunchKernelGGL((resample_argmax_ragged_f32<true, false>), grid, dim3(256), (size_t)r->launch.lds_bytes, s, a);
-    else hipLaunchKernelGGL((resample_argmax_ragged_f32<false, false>), grid, dim3(256), (size_t)r->launch.lds_bytes, s, a);
+    RS_LAUNCH(resample_argmax_ragged_f32, resample_softmax_ragged_f32, vec_loads(logits, r->classes), r->window != 0, q != nullptr, grid,
+              (size_t)r->launch.lds_bytes, s, a);
     // the next set waits for this launch; inside a capture there is nothing to wait for (the replays are the caller's to order)
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) (void)hipEventRecord(r->done, s);

@@ -141,6 +141,13 @@ int mbn_resample_ragged_check(int rows, int cols, int classes, const mbn_label_i
     return MBN_OK;
 }
 
+int mbn_softmax_readout_check(int have_prob, float min_prob)
+{
+    if (!(min_prob >= 0.0f && min_prob <= 1.0f)) return MBN_EINVAL;      /* a NaN fails both compares */
+    if (!have_prob && min_prob == 0.0f) return MBN_EINVAL;
+    return MBN_OK;
+}
+
 int mbn_resample_window_envelope(int batch, int rows, int cols, int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows,
                                  int out_cols)
 {

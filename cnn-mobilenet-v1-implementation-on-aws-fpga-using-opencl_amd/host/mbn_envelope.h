@@ -71,6 +71,9 @@ int mbn_upsample_argmax_envelope(int batch, int rows, int cols, int classes, int
  * non-positive size; else MBN_EUNSUPPORTED unless out_rows >= 4 rows, out_cols >= 4 cols, both at most 16384, an image's logits and an image's
  * output map each below 2^31 bytes, its tiles below 2^24 and batch at most 65535 */
 int mbn_resample_argmax_envelope(int batch, int rows, int cols, int classes, int out_rows, int out_cols);
+/* mbn_resample_softmax_f32 / _window_f32 / _ragged_f32: their shape checks are the argmax calls' above and below; this is the rest. MBN_EINVAL
+ * unless min_prob is in [0, 1] (a NaN is not) and, without a prob map (have_prob == 0), min_prob > 0: without either the call is the argmax one */
+int mbn_softmax_readout_check(int have_prob, float min_prob);
 /* what a launch of that kernel needs. mbn_resample_plan WIDENS *l by one output size of a rows x cols map (zero it first): fy, fx = the LDS
  * footprint in vectors, ch = the class chunk, lds_bytes = fy * fx * (ch + 4) * 4, tiles = grid.x, span = elements of labels / score reached */
 typedef struct mbn_resample_launch_t {

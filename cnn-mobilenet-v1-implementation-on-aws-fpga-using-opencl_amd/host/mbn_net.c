@@ -916,9 +916,26 @@ static int dense_logits_buf(mbn_net *net, const mbn_layer_desc *feat, const mbn_
     return rc;
 }
 
-int mbn_net_segment_to(mbn_net *net, const void *images, int batch, int out_rows, int out_cols, void *labels_i32, void *score_f32)
+/* The read-out of the three source-size paths below: q = NULL is the argmax read-out (labels and score), q given the softmax read-out
+ * (mbn_net_segment_prob_*: labels and prob, no score). One body per path, so both families run the same checks, resize and forward. */
+typedef struct readout_prob {
+    void *prob;
+    float min_prob;
+    int ignore_label;
+} readout_prob;
+
+/* the softmax read-out's own argument check, in front of everything else */
+static int prob_status(const readout_prob *q)
+{
+    if (!q) return MBN_OK;
+    if ((uintptr_t)q->prob % 4) return MBN_EINVAL;
+    return mbn_softmax_readout_check(q->prob != NULL, q->min_prob);
+}
+
+static int segment_to(mbn_net *net, const void *images, int batch, int out_rows, int out_cols, void *labels_i32, void *score_f32, const readout_prob *q)
 {
     if (!net || !images || !labels_i32 || batch <= 0 || batch > net->max_batch || out_rows <= 0 || out_cols <= 0) return MBN_EINVAL;
+    if (prob_status(q) != MBN_OK) return MBN_EINVAL;
     const mbn_layer_desc *feat, *fc;
     int rc = dense_layers(net, &feat, &fc);
     if (rc != MBN_OK) return rc;
@@ -927,7 +944,22 @@ int mbn_net_segment_to(mbn_net *net, const void *images, int batch, int out_rows
     rc = dense_logits_buf(net, feat, fc);
     if (rc == MBN_OK) rc = mbn_net_forward_dense(net, images, net->dense_logits, batch);
     if (rc != MBN_OK) return rc;
+    if (q)
+        return mbn_resample_softmax_f32(net->ctx, labels_i32, q->prob, NULL, net->dense_logits, batch, h, w, fc->out_ch, out_rows, out_cols, q->min_prob,
+                                        q->ignore_label, NULL);
     return mbn_resample_argmax_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, out_rows, out_cols, NULL);
+}
+
+int mbn_net_segment_to(mbn_net *net, const void *images, int batch, int out_rows, int out_cols, void *labels_i32, void *score_f32)
+{
+    return segment_to(net, images, batch, out_rows, out_cols, labels_i32, score_f32, NULL);
+}
+
+int mbn_net_segment_prob_to(mbn_net *net, const void *images, int batch, int out_rows, int out_cols, void *labels_i32, void *prob_f32, float min_prob,
+                            int ignore_label)
+{
+    const readout_prob q = { prob_f32, min_prob, ignore_label };
+    return segment_to(net, images, batch, out_rows, out_cols, labels_i32, NULL, &q);
 }
 
 /* MBN_OK for the fits a source-size read-out exists for; a crop's box is fractional and the network never saw the rest of the image */
@@ -937,10 +969,12 @@ static int segment_fit_status(int fit)
     return fit == MBN_FIT_CROP ? MBN_EUNSUPPORTED : MBN_EINVAL;
 }
 
-int mbn_net_segment_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, void *labels_i32, void *score_f32)
+static int segment_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, void *labels_i32, void *score_f32,
+                       const readout_prob *q)
 {
     if (!net || !src_u8 || !labels_i32 || batch <= 0 || batch > net->max_batch || in_rows <= 0 || in_cols <= 0) return MBN_EINVAL;
     if (!net->input_u8) return MBN_EINVAL;                    /* the resized images are uint8: the net must take them as such */
+    if (prob_status(q) != MBN_OK) return MBN_EINVAL;
     int rc = segment_fit_status(fit);
     if (rc != MBN_OK) return rc;
     const mbn_layer_desc *feat, *fc;
@@ -959,10 +993,28 @@ int mbn_net_segment_fit(mbn_net *net, const void *src_u8, int batch, int in_rows
     if (rc == MBN_OK) rc = dense_logits_buf(net, feat, fc);
     if (rc == MBN_OK) rc = mbn_net_forward_dense(net, images, net->dense_logits, batch);
     if (rc != MBN_OK) return rc;
+    if (q && fit == MBN_FIT_PAD)
+        return mbn_resample_softmax_window_f32(net->ctx, labels_i32, q->prob, NULL, net->dense_logits, batch, h, w, fc->out_ch, rows, cols, rect,
+                                               in_rows, in_cols, q->min_prob, q->ignore_label, NULL);
+    if (q)
+        return mbn_resample_softmax_f32(net->ctx, labels_i32, q->prob, NULL, net->dense_logits, batch, h, w, fc->out_ch, in_rows, in_cols, q->min_prob,
+                                        q->ignore_label, NULL);
     if (fit == MBN_FIT_PAD)
         return mbn_resample_argmax_window_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, rows, cols, rect, in_rows,
                                               in_cols, NULL);
     return mbn_resample_argmax_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, in_rows, in_cols, NULL);
+}
+
+int mbn_net_segment_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, void *labels_i32, void *score_f32)
+{
+    return segment_fit(net, src_u8, batch, in_rows, in_cols, fit, labels_i32, score_f32, NULL);
+}
+
+int mbn_net_segment_prob_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, void *labels_i32, void *prob_f32,
+                             float min_prob, int ignore_label)
+{
+    const readout_prob q = { prob_f32, min_prob, ignore_label };
+    return segment_fit(net, src_u8, batch, in_rows, in_cols, fit, labels_i32, NULL, &q);
 }
 
 int mbn_net_segment_images(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *in_rows, const int32_t *in_cols, int batch,
@@ -971,11 +1023,12 @@ int mbn_net_segment_images(mbn_net *net, const void *src_u8, const int64_t *offs
     return mbn_net_segment_images_fit(net, src_u8, offsets, in_rows, in_cols, batch, MBN_FIT_STRETCH, labels_i32, dst_offsets, score_f32);
 }
 
-int mbn_net_segment_images_fit(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *in_rows, const int32_t *in_cols, int batch,
-                               int fit, void *labels_i32, const int64_t *dst_offsets, void *score_f32)
+static int segment_images_fit(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *in_rows, const int32_t *in_cols, int batch,
+                              int fit, void *labels_i32, const int64_t *dst_offsets, void *score_f32, const readout_prob *q)
 {
     if (!net || !src_u8 || !offsets || !in_rows || !in_cols || !labels_i32 || !dst_offsets || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
     if (!net->input_u8) return MBN_EINVAL;                    /* the resized images are uint8: the net must take them as such */
+    if (prob_status(q) != MBN_OK) return MBN_EINVAL;
     int rc = segment_fit_status(fit);
     if (rc != MBN_OK) return rc;
     const mbn_layer_desc *feat, *fc;
@@ -1018,7 +1071,22 @@ int mbn_net_segment_images_fit(mbn_net *net, const void *src_u8, const int64_t *
     if (rc == MBN_OK) rc = dense_logits_buf(net, feat, fc);
     if (rc == MBN_OK) rc = mbn_net_forward_dense(net, images, net->dense_logits, batch);
     if (rc != MBN_OK) return rc;
+    if (q) return mbn_resample_softmax_ragged_f32(net->readout, labels_i32, q->prob, NULL, net->dense_logits, q->min_prob, q->ignore_label, NULL);
     return mbn_resample_argmax_ragged_f32(net->readout, labels_i32, score_f32, net->dense_logits, NULL);
+}
+
+int mbn_net_segment_images_fit(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *in_rows, const int32_t *in_cols, int batch,
+                               int fit, void *labels_i32, const int64_t *dst_offsets, void *score_f32)
+{
+    return segment_images_fit(net, src_u8, offsets, in_rows, in_cols, batch, fit, labels_i32, dst_offsets, score_f32, NULL);
+}
+
+int mbn_net_segment_prob_images_fit(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *in_rows, const int32_t *in_cols,
+                                    int batch, int fit, void *labels_i32, const int64_t *dst_offsets, void *prob_f32, float min_prob,
+                                    int ignore_label)
+{
+    const readout_prob q = { prob_f32, min_prob, ignore_label };
+    return segment_images_fit(net, src_u8, offsets, in_rows, in_cols, batch, fit, labels_i32, dst_offsets, NULL, &q);
 }
 
 int mbn_net_set_resize_filter(mbn_net *net, int filter)

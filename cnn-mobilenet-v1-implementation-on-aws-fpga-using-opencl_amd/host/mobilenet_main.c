@@ -18,6 +18,10 @@
  *   status 2: a crop has no labels for the rest of the image). stretch: one --ppm goes through mbn_net_resize_input + mbn_net_segment_to, several
  *   through mbn_net_segment_images (one ragged resize, one ragged read-out); pad: mbn_net_segment_fit / mbn_net_segment_images_fit, the read-out of
  *   the letterbox's rectangle, so the image is labelled undistorted
+ *   --segment-confidence FILE: the softmax probability of the winning class at every pixel of image 0, at its own size, as an 8-bit PGM, byte =
+ *   floor(prob * 255 + 0.5) (mbn_net_segment_prob_fit / _images_fit); valid wherever --segment-source is, with or without it
+ *   --min-confidence P --ignore-label L (together, with --segment-source; P in [0, 1], L in 0..65535): the pixels of that label map whose probability
+ *   is below P hold L instead of their label
  *   mobilenet --literal [--weights weights_c.txt] [--image Cat_Image0.ppm] [--ref-args]      the reference's own mode
  *   mobilenet --gpus G --batch N [--steps K --warmup W --streams S --pw-emul 6] (--h5 F | --synthetic SEED)  N images sharded over G GPUs
  *   mobilenet --inspect weights.h5                                                             list the datasets of a .h5
@@ -30,6 +34,7 @@
  * Prints the same two kinds of line as the reference: per-layer kernel time (MobileNet.c:315) and the argmax
  * line (MobileNet.c:2792).
  */
+#include <math.h>
 #include <pthread.h>
 #include <stdio.h>
 #include <unistd.h>
@@ -338,17 +343,21 @@ done:
 }
 
 /* --segment: image 0's label map [rows][cols] as a binary PGM (P5), maxval = max(classes - 1, 1), two big-endian bytes per pixel beyond 255;
- * then one line with the (at most) five most frequent labels, 0-based, and their pixel counts, most frequent first (ties: lowest label) */
-static int write_label_map(const char *path, const int *labels, int rows, int cols, int classes)
+ * then one line with the (at most) five most frequent labels, 0-based, and their pixel counts, most frequent first (ties: lowest label).
+ * ignore >= 0 (--ignore-label): a pixel that holds it is written as it is and counted apart; maxval then covers it too */
+static int write_label_map(const char *path, const int *labels, int rows, int cols, int classes, int ignore)
 {
-    const int maxval = classes - 1 > 1 ? classes - 1 : 1, wide = maxval > 255;
+    const int top = classes - 1 > ignore ? classes - 1 : ignore, maxval = top > 1 ? top : 1, wide = maxval > 255;
+    long ignored = 0;
     FILE *fp = fopen(path, "wb");
     long *count = calloc((size_t)classes, sizeof(long));
     if (!fp || !count) { if (fp) fclose(fp); free(count); fprintf(stderr, "Error: cannot write %s\n", path); return 1; }
     fprintf(fp, "P5\n%d %d\n%d\n", cols, rows, maxval);
     for (long i = 0; i < (long)rows * cols; i++) {
-        const int v = labels[i] < 0 ? 0 : labels[i] >= classes ? classes - 1 : labels[i];
-        count[v]++;
+        const int skip = ignore >= 0 && labels[i] == ignore;
+        const int v = skip ? ignore : labels[i] < 0 ? 0 : labels[i] >= classes ? classes - 1 : labels[i];
+        if (skip) ignored++;
+        else count[v]++;
         if (wide) fputc(v >> 8, fp);
         fputc(v & 255, fp);
     }
@@ -362,6 +371,7 @@ static int write_label_map(const char *path, const int *labels, int rows, int co
         printf(" %d (%ld)", best, count[best]);
         count[best] = 0;
     }
+    if (ignore >= 0) printf("; below --min-confidence: %ld pixels, label %d", ignored, ignore);
     printf("\n");
     free(count);
     return bad;
@@ -393,10 +403,29 @@ static int ppm_size(const char *path, int *width, int *height)
 
 #define PPM_MAX_SIDE 8192     /* the resize front-end's largest source side */
 
+/* --segment-confidence: image 0's probability map [rows][cols] as an 8-bit P5, byte = floor(prob * 255 + 0.5) */
+static int write_confidence_map(const char *path, const float *prob, int rows, int cols)
+{
+    FILE *fp = fopen(path, "wb");
+    if (!fp) { fprintf(stderr, "Error: cannot write %s\n", path); return 1; }
+    fprintf(fp, "P5\n%d %d\n255\n", cols, rows);
+    double sum = 0.0;
+    for (long i = 0; i < (long)rows * cols; i++) {
+        fputc((int)floor((double)prob[i] * 255.0 + 0.5), fp);      /* exact in double: no build rounds it another way */
+        sum += prob[i];
+    }
+    printf("segment: %dx%d confidence map -> %s; mean probability %.4f\n", cols, rows, path, sum / ((double)rows * cols));
+    return fclose(fp) != 0;
+}
+
 /* --segment-source: the --ppm files again, at their own sizes, one behind the other in ONE device buffer; image 0's label map at its own size.
  * One file: mbn_net_resize_input (stretch) + mbn_net_segment_to; several: mbn_net_segment_images. Under --fit pad mbn_net_segment_fit /
- * mbn_net_segment_images_fit, the read-out through the letterbox. The net takes uint8 images (the caller has set that) */
-static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int n_ppm, const char *path, int classes, int fit)
+ * mbn_net_segment_images_fit, the read-out through the letterbox. The net takes uint8 images (the caller has set that).
+ * conf_path (--segment-confidence) or ignore >= 0 (--min-confidence with --ignore-label): the softmax read-out instead, mbn_net_segment_prob_fit /
+ * mbn_net_segment_prob_images_fit: image 0's probability map as an 8-bit P5, byte = floor(prob * 255 + 0.5), and the label map with the pixels
+ * below min_conf replaced by `ignore`. path may then be NULL (no label map asked for) */
+static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int n_ppm, const char *path, int classes, int fit, const char *conf_path,
+                          float min_conf, int ignore)
 {
     int64_t *offs = malloc(sizeof(int64_t) * (size_t)n_ppm), *dst = malloc(sizeof(int64_t) * (size_t)n_ppm);
     int32_t *hs = malloc(sizeof(int32_t) * (size_t)n_ppm), *ws = malloc(sizeof(int32_t) * (size_t)n_ppm);
@@ -419,11 +448,17 @@ static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int
         int pw = ws[n], ph = hs[n];
         if (mbn_read_ppm(ppms[n], all + offs[n], &pw, &ph, pw * ph) != MBN_OK) { fprintf(stderr, "cannot read %s\n", ppms[n]); return 2; }
     }
-    void *d_src, *d_img, *d_labels;
+    void *d_src, *d_img, *d_labels, *d_prob = NULL;
     CHECK(mbn_alloc(ctx, total, &d_src));
     CHECK(mbn_alloc(ctx, sizeof(int) * pixels, &d_labels));
     CHECK(mbn_upload(ctx, d_src, all, total));
-    if (fit == MBN_FIT_PAD) {
+    if (!(min_conf > 0.0f)) ignore = -1;                        /* --min-confidence 0 replaces nothing: the argmax read-out, unless a map is asked for */
+    if (conf_path || ignore >= 0) {
+        const float min_prob = ignore >= 0 ? min_conf : 0.0f;
+        if (conf_path) CHECK(mbn_alloc(ctx, sizeof(float) * pixels, &d_prob));
+        if (n_ppm == 1) CHECK(mbn_net_segment_prob_fit(net, d_src, 1, hs[0], ws[0], fit, d_labels, d_prob, min_prob, ignore));
+        else CHECK(mbn_net_segment_prob_images_fit(net, d_src, offs, hs, ws, n_ppm, fit, d_labels, dst, d_prob, min_prob, ignore));
+    } else if (fit == MBN_FIT_PAD) {
         if (n_ppm == 1) CHECK(mbn_net_segment_fit(net, d_src, 1, hs[0], ws[0], MBN_FIT_PAD, d_labels, NULL));
         else CHECK(mbn_net_segment_images_fit(net, d_src, offs, hs, ws, n_ppm, MBN_FIT_PAD, d_labels, dst, NULL));
     } else if (n_ppm == 1) {
@@ -433,9 +468,18 @@ static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int
         CHECK(mbn_net_segment_images(net, d_src, offs, hs, ws, n_ppm, d_labels, dst, NULL));
     }
     CHECK(mbn_download(ctx, labels, d_labels, sizeof(int) * (size_t)hs[0] * ws[0]));      /* image 0 is first in the buffer */
+    int bad = 0;
+    if (conf_path) {
+        float *prob = malloc(sizeof(float) * (size_t)hs[0] * ws[0]);
+        if (!prob) return 1;
+        CHECK(mbn_download(ctx, prob, d_prob, sizeof(float) * (size_t)hs[0] * ws[0]));
+        CHECK(mbn_free(ctx, d_prob));
+        bad = write_confidence_map(conf_path, prob, hs[0], ws[0]);
+        free(prob);
+    }
     CHECK(mbn_free(ctx, d_src));
     CHECK(mbn_free(ctx, d_labels));
-    const int bad = write_label_map(path, labels, hs[0], ws[0], classes);
+    if (path) bad |= write_label_map(path, labels, hs[0], ws[0], classes, ignore);
     free(all); free(labels); free(offs); free(dst); free(hs); free(ws);
     return bad;
 }
@@ -475,10 +519,11 @@ int main(int argc, char **argv)
     const char **ppms = malloc(sizeof(char *) * (size_t)argc);          /* every --ppm, in order */
     int n_ppm = 0;
     if (!ppms) return 1;
-    const char *h5 = NULL, *ppm = NULL, *segment = NULL, *segment_src = NULL, *wfile = "weights_c.txt", *image = "Cat_Image0.ppm";
+    const char *h5 = NULL, *ppm = NULL, *segment = NULL, *segment_src = NULL, *segment_conf = NULL, *wfile = "weights_c.txt", *image = "Cat_Image0.ppm";
     int fit = MBN_FIT_CROP, filter = MBN_FILTER_BILINEAR;
     int pad_rgb[3] = { 0, 0, 0 }, src_h0 = 0, src_w0 = 0;              /* src_h0 x src_w0: image 0 as it was resized (0: it was not) */
-    float crop_fraction = 1.0f;
+    float crop_fraction = 1.0f, min_conf = 0.0f;
+    int have_min_conf = 0, have_ignore = 0, ignore_label = -1;
     int literal = 0, ref_args = 0, batch = 1, rows = 224, cols = 224, have_seed = 0, gpus = 0, steps = 20, warmup = 3, verify = 0, out_stride = 32;
     unsigned long long seed = 0;
     float alpha = 0.f;
@@ -498,6 +543,9 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--output-stride") && i + 1 < argc) out_stride = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--segment") && i + 1 < argc) segment = argv[++i];
         else if (!strcmp(argv[i], "--segment-source") && i + 1 < argc) segment_src = argv[++i];
+        else if (!strcmp(argv[i], "--segment-confidence") && i + 1 < argc) segment_conf = argv[++i];
+        else if (!strcmp(argv[i], "--min-confidence") && i + 1 < argc) { min_conf = (float)atof(argv[++i]); have_min_conf = 1; }
+        else if (!strcmp(argv[i], "--ignore-label") && i + 1 < argc) { ignore_label = atoi(argv[++i]); have_ignore = 1; }
         else if (!strcmp(argv[i], "--fit") && i + 1 < argc && fit_of(argv[i + 1]) >= 0) fit = fit_of(argv[++i]);
         else if (!strcmp(argv[i], "--pad-color") && i + 1 < argc && pad_color_of(argv[i + 1], pad_rgb)) i++;
         else if (!strcmp(argv[i], "--crop-fraction") && i + 1 < argc) crop_fraction = (float)atof(argv[++i]);
@@ -514,7 +562,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--literal")) literal = 1;
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
-            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm] "
+            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--min-confidence P --ignore-label L]] [--segment-confidence OUT.pgm] "
                             "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n", argv[0]);
             return 2;
         }
@@ -529,6 +577,18 @@ int main(int argc, char **argv)
     if (n_ppm == 1) ppm = ppms[0];
     if (segment_src && (n_ppm < 1 || (fit != MBN_FIT_STRETCH && fit != MBN_FIT_PAD))) {
         fprintf(stderr, "--segment-source needs --ppm and --fit stretch or --fit pad\n");
+        return 2;
+    }
+    if (segment_conf && (n_ppm < 1 || (fit != MBN_FIT_STRETCH && fit != MBN_FIT_PAD))) {
+        fprintf(stderr, "--segment-confidence needs --ppm and --fit stretch or --fit pad\n");
+        return 2;
+    }
+    if (have_min_conf != have_ignore || (have_min_conf && !segment_src)) {
+        fprintf(stderr, "--min-confidence P and --ignore-label L come together and with --segment-source\n");
+        return 2;
+    }
+    if (have_min_conf && (!(min_conf >= 0.f) || !(min_conf <= 1.f) || ignore_label < 0 || ignore_label > 65535)) {
+        fprintf(stderr, "bad --min-confidence (0 <= P <= 1) or --ignore-label (0..65535: it is written into the PGM)\n");
         return 2;
     }
     if (out_stride != 0 && out_stride != 8 && out_stride != 16 && out_stride != 32) { fprintf(stderr, "bad --output-stride (32, 16 or 8)\n"); return 2; }
@@ -670,7 +730,7 @@ int main(int argc, char **argv)
         CHECK(mbn_alloc(ctx, sizeof(int) * (size_t)batch * rows * cols, &d_labels));
         CHECK(mbn_net_segment(net, d_u8, batch, d_labels, NULL));
         CHECK(mbn_download(ctx, labels, d_labels, sizeof(int) * (size_t)rows * cols));
-        const int bad = write_label_map(segment, labels, rows, cols, classes);
+        const int bad = write_label_map(segment, labels, rows, cols, classes, -1);
         free(labels);
         if (bad) return 1;
         int32_t rect[4];
@@ -678,8 +738,8 @@ int main(int argc, char **argv)
             printf("segment: image 0 is the %d x %d rectangle at (%d, %d) of the label map (wide x high, left, upper); the rest labels the border\n", rect[2],
                    rect[3], rect[0], rect[1]);
     }
-    if (segment_src) {
-        const int bad = segment_source(ctx, net, ppms, n_ppm, segment_src, classes, fit);
+    if (segment_src || segment_conf) {
+        const int bad = segment_source(ctx, net, ppms, n_ppm, segment_src, classes, fit, segment_conf, min_conf, have_ignore ? ignore_label : -1);
         if (bad) return bad;
     }
     mbn_net_destroy(net);

@@ -461,6 +461,38 @@ int mbn_resample_argmax_window_f32(mbn_context *ctx, void *labels_i32, void *sco
                                    int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols, void *stream);
 int mbn_ragged_readout_set_window(mbn_ragged_readout *r, int rows, int cols, int classes, int in_rows, int in_cols,
                                   const mbn_label_window_item *items, int batch, void *stream);
+/* Segment with confidence: the same read-outs, which also give the softmax probability of the winning class at every output pixel and can replace
+ * the label of a pixel below a threshold. The full [out_rows][out_cols][classes] probabilities are never formed in memory.
+ * Normative:
+ *   Interpolants. For an output pixel the v_c, c = 0 .. classes - 1, are exactly the interpolated logits of mbn_resample_argmax_f32 (of
+ *     mbn_resample_argmax_window_f32 for the window and a window set); best and label are exactly theirs. The labels (at min_prob = 0) and the
+ *     score bits of these calls equal those of the argmax calls on the same arguments, bit for bit.
+ *   Probability. prob = 1 / sum_c e(v_c), e(v) = exp(v - best) when v is not NaN, e(v) = 0 when v is NaN (a NaN never wins and adds nothing).
+ *     If best is not finite, prob = 0: a pixel where nothing won (-inf) and a +inf winner; it falls under any positive threshold.
+ *   Tolerance. prob is fp32 and NOT bit-pinned: exp and the order of the summation are the implementation's. Wherever the reference prob is
+ *     nonzero the relative error is at most (classes + 200) * 2^-24; where it is 0 (a non-finite best) prob is exactly 0. The reference is the
+ *     float64 evaluation of the formula on the fp32 v_c (tests/dense_prob_ref.py). Where the bound comes from: classes - 1 roundings of a
+ *     sequential fp32 sum of non-negative terms; the rounding of v - best (or v - a reference near best) and of a log2(e) pre-multiply, each an
+ *     absolute error of at most |d| * 2^-24 in the exponent of a term that weighs e^d (|d| e^d < 1 for d <= 0, |d| < 88 before underflow; for a
+ *     reference at most 16 below best, d <= 16: at most 2.5 * 16 + 1 = 41 units for a term, once more for ONE rescale of the sum that counts and
+ *     once more for exp(best - reference), 123 in all); exp within 2 ulp; the final division. The bound holds for EVERY input: the kernel does
+ *     not rescale its sum at every new maximum (on an ascending ramp that would add one exp error per class) but only when a logit exceeds the
+ *     sum's reference by more than 16, which leaves the rescaled part below classes * e^-16 of the sum from the second rescale on.
+ *   Threshold. min_prob in [0, 1]; a NaN or a value outside is MBN_EINVAL. The stored label is ignore_label (any int32) iff the stored prob <
+ *     min_prob: strict, on the fp32 value the kernel writes. min_prob = 0 never replaces a label. prob and score are written unchanged either way.
+ * score_f32 may be NULL. prob_f32 may be NULL only when min_prob > 0 (thresholded labels alone); NULL with min_prob = 0 is MBN_EINVAL: that is
+ * the argmax call. prob_f32 has the shape and the dst_offset rule of score_f32 and must be on 4 bytes. The envelope, pointer, alignment and
+ * byte limits and their statuses are exactly those of the argmax call of the same form; nothing is launched on a refusal; the mbn_alloc bounds
+ * rule applies to prob_f32 as to score_f32. mbn_resample_softmax_ragged_f32 works after either kind of set (mbn_ragged_readout_set: the plain
+ * kernel, _set_window: the window kernel) and keeps the generation rule: a captured launch replayed after a later set does nothing. The handle
+ * and its items are unchanged. Each of the three is ONE kernel and may be captured as one kernel node. */
+int mbn_resample_softmax_f32(mbn_context *ctx, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, int batch, int rows, int cols,
+                             int classes, int out_rows, int out_cols, float min_prob, int ignore_label, void *stream);
+int mbn_resample_softmax_window_f32(mbn_context *ctx, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, int batch, int rows,
+                                    int cols, int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols,
+                                    float min_prob, int ignore_label, void *stream);
+int mbn_resample_softmax_ragged_f32(mbn_ragged_readout *r, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, float min_prob,
+                                    int ignore_label, void *stream);
 /* The classifier tail of the sequence as one call (MobileNet.c:2601-2792): global average pool (kernel.cl:116) ->
  * FC = pointwise with rows = cols = 1 (kernel.cl:94; bias, no ReLU: B15) -> softmax + top-k. fp32 NHWC,
  * in [batch][rows][cols][channels], fc_w [classes][channels], fc_bias [classes] or NULL; pooled_scratch
@@ -980,6 +1012,18 @@ int  mbn_net_segment_images(mbn_net *net, const void *src_u8, const int64_t *off
 int  mbn_net_segment_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, void *labels_i32, void *score_f32);
 int  mbn_net_segment_images_fit(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *rows, const int32_t *cols, int batch,
                                 int fit, void *labels_i32, const int64_t *dst_offsets, void *score_f32);
+/* The same three paths with the softmax read-out (mbn_resample_softmax_f32 / _window_f32 / _ragged_f32 above): labels_i32 and prob_f32 (fp32, the
+ * shape and offsets of the labels; may be NULL when min_prob > 0) instead of labels and score. Step for step mbn_net_segment_to / _fit /
+ * _images_fit: the same checks before anything runs, the same resize, mbn_net_forward_dense, net-owned buffers and ragged handle; min_prob outside
+ * [0, 1] or NaN, or NULL prob_f32 with min_prob = 0: MBN_EINVAL; MBN_FIT_CROP: MBN_EUNSUPPORTED, any other fit MBN_EINVAL. Every dtype at output
+ * stride 32 (the dense logits are fp32 in every mode), fp32 and bf16 at 16 and 8. At min_prob = 0 the labels are those of the argmax path bit for
+ * bit; mbn_net_segment_prob_to at the plan's own input size gives mbn_net_segment's labels (the equivalence stated at mbn_resample_argmax_f32). */
+int  mbn_net_segment_prob_to(mbn_net *net, const void *images, int batch, int out_rows, int out_cols, void *labels_i32, void *prob_f32, float min_prob,
+                             int ignore_label);
+int  mbn_net_segment_prob_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, void *labels_i32, void *prob_f32,
+                              float min_prob, int ignore_label);
+int  mbn_net_segment_prob_images_fit(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *rows, const int32_t *cols, int batch,
+                                     int fit, void *labels_i32, const int64_t *dst_offsets, void *prob_f32, float min_prob, int ignore_label);
 /* Per-layer milliseconds of the most recent mbn_net_forward_timed call (hipEvents between layers). */
 int  mbn_net_forward_timed(mbn_net *net, const void *images, void *logits, int batch, float *layer_ms,
                            int n_layer_ms);

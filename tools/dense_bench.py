@@ -20,6 +20,10 @@
   python tools/dense_bench.py --any --fit pad [--reps 7] [--steps 20] [--batch 32]
       mbn_resample_argmax_window_f32, the read-out through the letterbox (main_any_pad): against mbn_resample_argmax_f32 to the same 375 x 500,
       alternating in one process.
+
+  python tools/dense_bench.py --any --prob [--reps 7] [--steps 20] [--batch 32] [--torch-steps 2] [--no-torch]
+      mbn_resample_softmax_f32 / _window_f32 / _ragged_f32, the read-out with confidence (main_prob): each beside the argmax kernel of the same
+      form on the same buffers, alternating in one process, and torch's three-pass interpolate(size=...).softmax(1).max(1).
 """
 import argparse
 import json
@@ -201,6 +205,105 @@ def main_any_pad(a):
     print(json.dumps(result))
 
 
+def prob_work(batch, h, w, classes, pix):
+    """(bytes, vector issue slots) of the softmax read-out: resample_work's upper count, 4 more bytes per pixel for prob and, per pixel and
+    class, subtract, max, multiply, add, one v_exp_f32 at two slots, and a quarter of the group's three maxima, subtract and compare"""
+    bytes_, ops = resample_work(batch, h, w, classes, pix)
+    return bytes_ + 4.0 * pix, ops + pix * classes * (6.0 + 5.0 / 4)
+
+
+def main_prob(a):
+    """--any --prob: the softmax read-out beside the argmax read-out, 1000 classes, --batch images of random logits (sigma 3), to 375 x 500 from
+    the 28 x 28 and the 14 x 14 map of a 224 x 224 input. Per shape, alternating within every repetition, on the same buffers:
+      plain        mbn_resample_argmax_f32 / mbn_resample_softmax_f32 (labels + score / labels + score + prob)
+      window_pad   the _window_f32 pair with mbn_fit_pad's rectangle of a 375 x 500 source: what segment_fit / segment_prob_fit(FIT_PAD) launch
+      ragged       the ragged pair, --batch images of 300-600 x 300-700 in one launch from the 14 x 14 map (main_any's sizes)
+      torch        the yardstick: interpolate(size=(375, 500)).softmax(1).max(1) on the same buffer, three passes over batch x 1000 x 375 x 500
+                   floats, in slices of 8 images (its interpolate refuses outputs of 2^31 elements; a slice's two tensors are 12 GB)
+    Each figure is the median over the repetitions of `steps` back-to-back calls between two stream marks; the runs are kept, the spread is
+    (max - min) / median of a name's own repetitions. The argmax kernel is unchanged code: its times here belong beside main_any's."""
+    pkg = import_package()
+    torch = None
+    if not a.no_torch:
+        import torch
+        assert torch.cuda.is_available(), "the yardstick needs torch on the same GPU"
+    n, rng = a.batch, np.random.default_rng(0)
+    H, W = 375, 500
+    sizes = [(int(rng.integers(300, 601)), int(rng.integers(300, 701))) for _ in range(n)]
+    offs = np.concatenate([[0], np.cumsum([r * c for r, c in sizes])]).astype(np.int64)
+    cap = max(int(offs[-1]), n * H * W)
+    rect = tuple(pkg.fit_pad(H, W, RES, RES))
+    result = {"batch": n, "rect": list(rect), "ragged_pixels": int(offs[-1])}
+    with pkg.Context(0) as ctx:
+        d_lab, d_sc, d_pr = ctx.alloc(cap * 4), ctx.alloc(cap * 4), ctx.alloc(cap * 4)
+        maps, runs = {}, []
+        for hw_ in (28, 14):
+            x = (3.0 * rng.standard_normal((n, hw_, hw_, CLASSES))).astype(np.float32)
+            if torch is not None:
+                t = torch.from_numpy(x).cuda()
+                maps[hw_] = (t.data_ptr(), t)
+            else:
+                b = ctx.to_device(x)
+                maps[hw_] = (b.ptr, b)
+        for hw_ in (28, 14):
+            p = maps[hw_][0]
+            runs.append(("plain_from_%d" % hw_, lambda p=p, hw_=hw_: ctx.resample_argmax(d_lab.ptr, d_sc.ptr, p, n, hw_, hw_, CLASSES, H, W),
+                         lambda p=p, hw_=hw_: ctx.resample_softmax(d_lab.ptr, d_pr.ptr, d_sc.ptr, p, n, hw_, hw_, CLASSES, H, W), (n, hw_, n * H * W)))
+            runs.append(("window_pad_from_%d" % hw_,
+                         lambda p=p, hw_=hw_: ctx.resample_argmax_window(d_lab.ptr, d_sc.ptr, p, n, hw_, hw_, CLASSES, RES, RES, rect, H, W),
+                         lambda p=p, hw_=hw_: ctx.resample_softmax_window(d_lab.ptr, d_pr.ptr, d_sc.ptr, p, n, hw_, hw_, CLASSES, RES, RES, rect, H, W),
+                         (n, hw_, n * H * W)))
+        rd = pkg.RaggedReadout(ctx, n)
+        rd.set(14, 14, CLASSES, [(int(o), r, c) for o, (r, c) in zip(offs, sizes)])
+        runs.append(("ragged_from_14", lambda: rd.run(d_lab.ptr, d_sc.ptr, maps[14][0]),
+                     lambda: rd.run_softmax(d_lab.ptr, d_pr.ptr, d_sc.ptr, maps[14][0]), (n, 14, int(offs[-1]))))
+        times = {(name, k): [] for name, _, _, _ in runs for k in ("argmax", "softmax")}
+        for _, f_arg, f_soft, _ in runs:
+            marks_ms(ctx, f_arg, 3)
+            marks_ms(ctx, f_soft, 3)
+        t_times = {28: [], 14: []}
+        for _ in range(a.reps):
+            for name, f_arg, f_soft, _ in runs:
+                times[(name, "argmax")].append(marks_ms(ctx, f_arg, a.steps))
+                times[(name, "softmax")].append(marks_ms(ctx, f_soft, a.steps))
+            for hw_ in (28, 14) if torch is not None else ():
+                ctx.sync()
+                nchw = maps[hw_][1].permute(0, 3, 1, 2)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+                def three_pass():
+                    for i in range(0, n, 8):
+                        torch.nn.functional.interpolate(nchw[i:i + 8], size=(H, W), mode="bilinear", align_corners=False).softmax(1).max(1)
+                three_pass()
+                e0.record()
+                for _ in range(a.torch_steps):
+                    three_pass()
+                e1.record()
+                torch.cuda.synchronize()
+                t_times[hw_].append(e0.elapsed_time(e1) / a.torch_steps)
+        for name, _, _, (nb, hw_, pix) in runs:
+            out = {}
+            for k, work in (("argmax", resample_work(nb, hw_, hw_, CLASSES, pix)), ("softmax", prob_work(nb, hw_, hw_, CLASSES, pix))):
+                ts = times[(name, k)]
+                m = statistics.median(ts)
+                out[k] = {"kernel_ms": round(m, 4), "kernel_runs_ms": [round(v, 4) for v in ts], "spread": round((max(ts) - min(ts)) / m, 4),
+                          "kernel_frac_of_8TBps": round(work[0] / HBM_BYTES_PER_S / (m / 1e3), 4),
+                          "kernel_frac_of_valu_rate": round(work[1] / VALU_LANE_OPS_PER_S / (m / 1e3), 4)}
+            out["softmax_over_argmax"] = round(out["softmax"]["kernel_ms"] / out["argmax"]["kernel_ms"], 3)
+            result[name] = out
+            print("%-20s argmax %.4f ms (spread %.1f %%)  softmax %.4f ms (spread %.1f %%, %.1f %% of the VALU rate)  ratio %.3f"
+                  % (name, out["argmax"]["kernel_ms"], 100 * out["argmax"]["spread"], out["softmax"]["kernel_ms"], 100 * out["softmax"]["spread"],
+                     100 * out["softmax"]["kernel_frac_of_valu_rate"], out["softmax_over_argmax"]), flush=True)
+        for hw_, ts in t_times.items():
+            if ts:
+                t = statistics.median(ts)
+                result["plain_from_%d" % hw_].update({"torch_ms": round(t, 4), "torch_runs_ms": [round(v, 4) for v in ts],
+                                                      "torch_over_softmax": round(t / result["plain_from_%d" % hw_]["softmax"]["kernel_ms"], 2)})
+                print("torch three-pass from %d: %.2f ms" % (hw_, t), flush=True)
+        rd.close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
@@ -211,7 +314,10 @@ def main():
     ap.add_argument("--any", action="store_true", help="time mbn_resample_argmax_f32 (the read-out at any output size) instead: see main_any")
     ap.add_argument("--torch-steps", type=int, default=2, help="--any: torch calls per repetition (each writes batch x 1000 x 375 x 500 floats)")
     ap.add_argument("--fit", default="stretch", choices=("stretch", "pad"), help="--any: pad times the window kernel instead: see main_any_pad")
+    ap.add_argument("--prob", action="store_true", help="--any: time the softmax read-out beside the argmax read-out instead: see main_prob")
     a = ap.parse_args()
+    if a.any and a.prob:
+        return main_prob(a)
     if a.any:
         return main_any_pad(a) if a.fit == "pad" else main_any(a)
     chosen = [c for c in CONFIGS if not a.configs or c[0] in a.configs.split(",")]
