@@ -831,59 +831,58 @@ int mbn_upsample_argmax_f32(mbn_context *ctx, void *labels_i32, void *score_f32,
                                                     classes, factor));
 }
 
-// The three uniform / window / ragged read-outs below serve both families: q = null is mbn_resample_argmax_*, q given mbn_resample_softmax_*
-// (whose own argument checks, mbn_softmax_readout_check and prob's alignment, come first). Every other check is the same line for both.
-static int resample_uniform(mbn_context *ctx, void *labels_i32, void *score_f32, const void *logits, int batch, int rows, int cols, int classes,
-                            int out_rows, int out_cols, void *stream, const mbn_readout_prob *q)
+// What the six read-outs at any output size share. q = null is mbn_resample_argmax_*, q given mbn_resample_softmax_* (whose own argument checks,
+// prob's alignment and mbn_softmax_readout_check, come with the pointers', in front of the shape). shape: what the call's own envelope answered;
+// out_bytes: what the launch reaches of labels, score and prob each; launch(s) enqueues it on the stream chosen here.
+extern "C++" {
+template <typename Launch>
+static int readout_call(mbn_context *ctx, void *labels_i32, void *score_f32, const void *logits, const mbn_readout_prob *q, int shape,
+                        double logits_bytes, double out_bytes, void *stream, Launch launch)
 {
-    if (!ctx || !labels_i32 || !logits || batch <= 0 || rows <= 0 || cols <= 0 || classes <= 0 || out_rows <= 0 || out_cols <= 0) return MBN_EINVAL;
+    if (!ctx || !labels_i32 || !logits) return MBN_EINVAL;
     if (((uintptr_t)labels_i32 | (uintptr_t)score_f32 | (uintptr_t)logits | (uintptr_t)(q ? q->prob : nullptr)) % 4) return MBN_EINVAL;
     if (q && mbn_softmax_readout_check(q->prob != nullptr, q->min_prob) != MBN_OK) return MBN_EINVAL;
-    if (mbn_resample_argmax_envelope(batch, rows, cols, classes, out_rows, out_cols) != MBN_OK) return MBN_EUNSUPPORTED;
+    if (shape != MBN_OK) return shape;
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    const double out = 4.0 * batch * out_rows * out_cols;
-    MBN_SPANS(ctx, { logits, 4.0 * batch * rows * cols * classes, "resample_argmax logits" }, { labels_i32, out, "resample_argmax labels" },
-              { score_f32, out, "resample_argmax score" }, { q ? q->prob : nullptr, out, "resample_softmax prob" });
+    MBN_SPANS(ctx, { logits, logits_bytes, "resample read-out logits" }, { labels_i32, out_bytes, "resample read-out labels" },
+              { score_f32, out_bytes, "resample read-out score" }, { q ? q->prob : nullptr, out_bytes, "resample read-out prob" });
     Scope sc(ctx, s);
-    return sc.finish(mbn_launch_f32_resample_argmax(ctx, s, (int32_t *)labels_i32, (float *)score_f32, (const float *)logits, batch, rows, cols,
-                                                    classes, out_rows, out_cols, q));
+    return sc.finish(launch(s));
+}
+}   // extern "C++"
+
+// rect = null: the whole map, mbn_resample_argmax_f32 / _softmax_f32 (window = false: a null rect of the window calls is their envelope's to refuse)
+static int resample_uniform(mbn_context *ctx, void *labels_i32, void *score_f32, const void *logits, int batch, int rows, int cols, int classes,
+                            bool window, int in_rows, int in_cols, const int32_t *rect, int out_rows, int out_cols, void *stream,
+                            const mbn_readout_prob *q)
+{
+    const int shape = window ? mbn_resample_window_envelope(batch, rows, cols, classes, in_rows, in_cols, rect, out_rows, out_cols)
+                             : mbn_resample_argmax_envelope(batch, rows, cols, classes, out_rows, out_cols);
+    return readout_call(ctx, labels_i32, score_f32, logits, q, shape, 4.0 * batch * rows * cols * classes, 4.0 * batch * out_rows * out_cols, stream,
+                        [&](hipStream_t s) {
+                            return mbn_launch_f32_resample_argmax(ctx, s, (int32_t *)labels_i32, (float *)score_f32, (const float *)logits, batch, rows,
+                                                                  cols, classes, in_rows, in_cols, rect, out_rows, out_cols, q);
+                        });
 }
 
 int mbn_resample_argmax_f32(mbn_context *ctx, void *labels_i32, void *score_f32, const void *logits, int batch, int rows, int cols, int classes,
                             int out_rows, int out_cols, void *stream)
 {
-    return resample_uniform(ctx, labels_i32, score_f32, logits, batch, rows, cols, classes, out_rows, out_cols, stream, nullptr);
+    return resample_uniform(ctx, labels_i32, score_f32, logits, batch, rows, cols, classes, false, 0, 0, nullptr, out_rows, out_cols, stream, nullptr);
 }
 
 int mbn_resample_softmax_f32(mbn_context *ctx, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, int batch, int rows, int cols,
                              int classes, int out_rows, int out_cols, float min_prob, int ignore_label, void *stream)
 {
     const mbn_readout_prob q = { (float *)prob_f32, min_prob, ignore_label };
-    return resample_uniform(ctx, labels_i32, score_f32, logits, batch, rows, cols, classes, out_rows, out_cols, stream, &q);
-}
-
-static int resample_window(mbn_context *ctx, void *labels_i32, void *score_f32, const void *logits, int batch, int rows, int cols, int classes,
-                           int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols, void *stream, const mbn_readout_prob *q)
-{
-    if (!ctx || !labels_i32 || !logits || !rect) return MBN_EINVAL;
-    if (((uintptr_t)labels_i32 | (uintptr_t)score_f32 | (uintptr_t)logits | (uintptr_t)(q ? q->prob : nullptr)) % 4) return MBN_EINVAL;
-    if (q && mbn_softmax_readout_check(q->prob != nullptr, q->min_prob) != MBN_OK) return MBN_EINVAL;
-    const int rc = mbn_resample_window_envelope(batch, rows, cols, classes, in_rows, in_cols, rect, out_rows, out_cols);
-    if (rc != MBN_OK) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    const double out = 4.0 * batch * out_rows * out_cols;
-    MBN_SPANS(ctx, { logits, 4.0 * batch * rows * cols * classes, "resample_argmax_window logits" },
-              { labels_i32, out, "resample_argmax_window labels" }, { score_f32, out, "resample_argmax_window score" },
-              { q ? q->prob : nullptr, out, "resample_softmax_window prob" });
-    Scope sc(ctx, s);
-    return sc.finish(mbn_launch_f32_resample_argmax_window(ctx, s, (int32_t *)labels_i32, (float *)score_f32, (const float *)logits, batch, rows,
-                                                           cols, classes, in_rows, in_cols, rect, out_rows, out_cols, q));
+    return resample_uniform(ctx, labels_i32, score_f32, logits, batch, rows, cols, classes, false, 0, 0, nullptr, out_rows, out_cols, stream, &q);
 }
 
 int mbn_resample_argmax_window_f32(mbn_context *ctx, void *labels_i32, void *score_f32, const void *logits, int batch, int rows, int cols, int classes,
                                    int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols, void *stream)
 {
-    return resample_window(ctx, labels_i32, score_f32, logits, batch, rows, cols, classes, in_rows, in_cols, rect, out_rows, out_cols, stream, nullptr);
+    return resample_uniform(ctx, labels_i32, score_f32, logits, batch, rows, cols, classes, true, in_rows, in_cols, rect, out_rows, out_cols, stream,
+                            nullptr);
 }
 
 int mbn_resample_softmax_window_f32(mbn_context *ctx, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, int batch, int rows,
@@ -891,7 +890,7 @@ int mbn_resample_softmax_window_f32(mbn_context *ctx, void *labels_i32, void *pr
                                     float min_prob, int ignore_label, void *stream)
 {
     const mbn_readout_prob q = { (float *)prob_f32, min_prob, ignore_label };
-    return resample_window(ctx, labels_i32, score_f32, logits, batch, rows, cols, classes, in_rows, in_cols, rect, out_rows, out_cols, stream, &q);
+    return resample_uniform(ctx, labels_i32, score_f32, logits, batch, rows, cols, classes, true, in_rows, in_cols, rect, out_rows, out_cols, stream, &q);
 }
 
 int mbn_ragged_readout_create(mbn_context *ctx, int max_batch, mbn_ragged_readout **r)
@@ -928,7 +927,7 @@ int mbn_ragged_readout_set(mbn_ragged_readout *r, int rows, int cols, int classe
     if (!r || !items || batch <= 0 || batch > r->max_batch || rows <= 0 || cols <= 0 || classes <= 0) return MBN_EINVAL;
     mbn_context *ctx = r->ctx;
     (void)hipSetDevice(ctx->device);
-    return mbn_ragged_readout_plan(r, stream ? (hipStream_t)stream : ctx->stream, rows, cols, classes, items, batch);
+    return mbn_ragged_readout_plan(r, stream ? (hipStream_t)stream : ctx->stream, rows, cols, classes, 0, 0, 0, items, batch);
 }
 
 int mbn_ragged_readout_set_window(mbn_ragged_readout *r, int rows, int cols, int classes, int in_rows, int in_cols,
@@ -937,22 +936,16 @@ int mbn_ragged_readout_set_window(mbn_ragged_readout *r, int rows, int cols, int
     if (!r || !items || batch <= 0 || batch > r->max_batch || rows <= 0 || cols <= 0 || classes <= 0 || in_rows <= 0 || in_cols <= 0) return MBN_EINVAL;
     mbn_context *ctx = r->ctx;
     (void)hipSetDevice(ctx->device);
-    return mbn_ragged_readout_plan_window(r, stream ? (hipStream_t)stream : ctx->stream, rows, cols, classes, in_rows, in_cols, items, batch);
+    return mbn_ragged_readout_plan(r, stream ? (hipStream_t)stream : ctx->stream, rows, cols, classes, 1, in_rows, in_cols, items, batch);
 }
 
 static int resample_ragged(mbn_ragged_readout *r, void *labels_i32, void *score_f32, const void *logits, void *stream, const mbn_readout_prob *q)
 {
-    if (!r || !labels_i32 || !logits || r->batch <= 0) return MBN_EINVAL;
-    if (((uintptr_t)labels_i32 | (uintptr_t)score_f32 | (uintptr_t)logits | (uintptr_t)(q ? q->prob : nullptr)) % 4) return MBN_EINVAL;
-    if (q && mbn_softmax_readout_check(q->prob != nullptr, q->min_prob) != MBN_OK) return MBN_EINVAL;
-    mbn_context *ctx = r->ctx;
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    const double out = 4.0 * (double)r->launch.span;
-    MBN_SPANS(ctx, { logits, 4.0 * r->batch * r->rows * r->cols * r->classes, "resample_argmax_ragged logits" },
-              { labels_i32, out, "resample_argmax_ragged labels" }, { score_f32, out, "resample_argmax_ragged score" },
-              { q ? q->prob : nullptr, out, "resample_softmax_ragged prob" });
-    Scope sc(ctx, s);
-    return sc.finish(mbn_launch_f32_resample_argmax_ragged(r, s, (int32_t *)labels_i32, (float *)score_f32, (const float *)logits, q));
+    if (!r || r->batch <= 0) return MBN_EINVAL;                  // no set: nothing to launch
+    return readout_call(r->ctx, labels_i32, score_f32, logits, q, MBN_OK, 4.0 * r->batch * r->rows * r->cols * r->classes, 4.0 * (double)r->launch.span,
+                        stream, [&](hipStream_t s) {
+                            return mbn_launch_f32_resample_argmax_ragged(r, s, (int32_t *)labels_i32, (float *)score_f32, (const float *)logits, q);
+                        });
 }
 
 int mbn_resample_argmax_ragged_f32(mbn_ragged_readout *r, void *labels_i32, void *score_f32, const void *logits, void *stream)

@@ -24,6 +24,9 @@
 // inner image, instead of the whole map. Only the index / weight rule differs (rs_axis_win: 64-bit integers, still one fp64 division per axis
 // coordinate, once per lane in front of the class loop); the footprint bound holds with n / N replaced by l n / (N R) (host/mbn_envelope.h), so
 // stage, reduce, the cross ballot, the store and the LDS layout are the same code. The other instantiations compile to what they were without it.
+// On the host the whole map is the window that covers the whole input (host/mbn_envelope.c: one envelope, one plan), and here one launch entry
+// takes an optional rectangle. The device keeps both rules: the window rule's 64-bit divisions cost 0.6-0.7 % at equal footprint (profiles/LOG.md,
+// "Through the letterbox"), so WIN stays a compile-time parameter and a null rectangle launches the plain kernels.
 // PROB (mbn_resample_softmax_f32, _window_f32, _ragged_f32; include/mbn.h, "segment with confidence"): the same tile body also keeps the softmax
 // denominator of each of the lane's four pixels and writes prob = 1 / sum_c exp(v_c - best) beside the label; labels and scores are the argmax
 // instantiations' bit for bit (the same v, the same compare). The sum is ONE pass with a LAZY reference: per row a reference `ref` and
@@ -40,6 +43,7 @@
 #include "mbn_device.h"
 
 #include <new>
+#include <type_traits>
 
 namespace {
 
@@ -282,33 +286,32 @@ __global__ __launch_bounds__(256) void resample_softmax_f32(const ResampleArgs a
     resample_uniform<VEC, WIN, true>(a, s_rs);
 }
 
+// A ragged set holds one kind of item, which WIN selects; rs_windows gives an item's windows along y and x (read by the WIN instantiations only).
+template <bool WIN>
+using RsItem = typename std::conditional<WIN, mbn_label_window_item, mbn_label_item>::type;
+__device__ __forceinline__ void rs_windows(const ResampleArgs &, const mbn_label_item &, RsWindow *wy, RsWindow *wx) { *wy = *wx = RsWindow{ 0, 0, 0 }; }
+__device__ __forceinline__ void rs_windows(const ResampleArgs &a, const mbn_label_window_item &it, RsWindow *wy, RsWindow *wx)
+{
+    *wy = RsWindow{ a.in_rows, it.y, it.ih };
+    *wx = RsWindow{ a.in_cols, it.x, it.iw };
+}
+
 // grid = (tiles of the largest item, batch): a workgroup past its own image's tiles returns before any load or barrier
 template <bool VEC, bool WIN, bool PROB>
 __device__ __forceinline__ void resample_ragged(const ResampleArgs &a, float *s_rs)
 {
     // a replay of a captured launch after another set: the items are no longer the ones its grid, LDS and spans were checked for
     if (a.head->generation != a.generation || (int)blockIdx.y >= a.head->batch) return;
-    if (WIN) {
-        const mbn_label_window_item it = a.witems[blockIdx.y];
-        const int tiles_x = (it.cols + RS_TILE - 1) / RS_TILE, tiles_y = (it.rows + RS_TILE - 1) / RS_TILE;
-        const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
-        if (ty >= tiles_y) return;
-        const size_t img = (size_t)blockIdx.y;
-        const RsWindow wy = { a.in_rows, it.y, it.ih }, wx = { a.in_cols, it.x, it.iw };
-        resample_tile<VEC, true, PROB>(a, a.logits + img * ((size_t)a.rows * a.cols * a.classes), a.labels + it.dst_offset,
-                                       a.score ? a.score + it.dst_offset : nullptr, PROB && a.prob ? a.prob + it.dst_offset : nullptr, it.rows,
-                                       it.cols, ty, tx, s_rs, wy, wx);
-        return;
-    }
-    const mbn_label_item it = a.items[blockIdx.y];
+    const RsItem<WIN> it = (WIN ? (const RsItem<WIN> *)a.witems : (const RsItem<WIN> *)a.items)[blockIdx.y];
     const int tiles_x = (it.cols + RS_TILE - 1) / RS_TILE, tiles_y = (it.rows + RS_TILE - 1) / RS_TILE;
     const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
     if (ty >= tiles_y) return;
     const size_t img = (size_t)blockIdx.y;
-    const RsWindow none = { 0, 0, 0 };
-    resample_tile<VEC, false, PROB>(a, a.logits + img * ((size_t)a.rows * a.cols * a.classes), a.labels + it.dst_offset,
-                                    a.score ? a.score + it.dst_offset : nullptr, PROB && a.prob ? a.prob + it.dst_offset : nullptr, it.rows, it.cols,
-                                    ty, tx, s_rs, none, none);
+    RsWindow wy, wx;
+    rs_windows(a, it, &wy, &wx);
+    resample_tile<VEC, WIN, PROB>(a, a.logits + img * ((size_t)a.rows * a.cols * a.classes), a.labels + it.dst_offset,
+                                  a.score ? a.score + it.dst_offset : nullptr, PROB && a.prob ? a.prob + it.dst_offset : nullptr, it.rows, it.cols,
+                                  ty, tx, s_rs, wy, wx);
 }
 
 template <bool VEC, bool WIN>
@@ -325,67 +328,53 @@ __global__ __launch_bounds__(256) void resample_softmax_ragged_f32(const Resampl
     resample_ragged<VEC, WIN, true>(a, s_rs);
 }
 
-bool vec_loads(const float *logits, int classes) { return ((uintptr_t)logits % 16) == 0 && (classes % 4) == 0; }   // every class vector then starts on 16 bytes
+// The sixteen kernels by [ragged][prob][win][vec]; vec: `logits` on 16 bytes and classes % 4 == 0, so that every class vector starts on 16 bytes
+typedef void (*RsKernel)(const ResampleArgs);
+const RsKernel rs_kernels[2][2][2][2] = {
+    { { { resample_argmax_f32<false, false>, resample_argmax_f32<true, false> }, { resample_argmax_f32<false, true>, resample_argmax_f32<true, true> } },
+      { { resample_softmax_f32<false, false>, resample_softmax_f32<true, false> }, { resample_softmax_f32<false, true>, resample_softmax_f32<true, true> } } },
+    { { { resample_argmax_ragged_f32<false, false>, resample_argmax_ragged_f32<true, false> },
+        { resample_argmax_ragged_f32<false, true>, resample_argmax_ragged_f32<true, true> } },
+      { { resample_softmax_ragged_f32<false, false>, resample_softmax_ragged_f32<true, false> },
+        { resample_softmax_ragged_f32<false, true>, resample_softmax_ragged_f32<true, true> } } },
+};
 
-// q: the softmax read-out's extras, null for the argmax read-out
-void set_prob(ResampleArgs &a, const mbn_readout_prob *q)
+// What every form's launch carries: the buffers, the coarse map, the launch's plan, the network input a window lies in (WIN) and q, the softmax
+// read-out's extras (null for the argmax read-out). The form adds its own: the output size and rectangle, or the handle's items.
+ResampleArgs rs_args(int32_t *labels, float *score, const float *logits, int rows, int cols, int classes, const mbn_resample_launch_t &l, int in_rows,
+                     int in_cols, const mbn_readout_prob *q)
 {
-    if (!q) return;
-    a.prob = q->prob; a.min_prob = q->min_prob; a.ignore_label = q->ignore_label;
+    ResampleArgs a = {};
+    a.labels = labels; a.score = score; a.logits = logits;
+    a.rows = rows; a.cols = cols; a.classes = classes;
+    a.fy = l.fy; a.fx = l.fx; a.ch = l.ch;
+    a.in_rows = in_rows; a.in_cols = in_cols;
+    if (q) { a.prob = q->prob; a.min_prob = q->min_prob; a.ignore_label = q->ignore_label; }
+    return a;
 }
 
-// one of the eight kernels of a form: K = the argmax kernel template, KP = the softmax one
-#define RS_LAUNCH(K, KP, vec, win, prob, grid, lds, s, a)                                                          \
-    do {                                                                                                           \
-        if (prob) {                                                                                                \
-            if (win) { if (vec) hipLaunchKernelGGL((KP<true, true>), grid, dim3(256), lds, s, a);                  \
-                       else hipLaunchKernelGGL((KP<false, true>), grid, dim3(256), lds, s, a); }                   \
-            else if (vec) hipLaunchKernelGGL((KP<true, false>), grid, dim3(256), lds, s, a);                       \
-            else hipLaunchKernelGGL((KP<false, false>), grid, dim3(256), lds, s, a);                               \
-        } else if (win) { if (vec) hipLaunchKernelGGL((K<true, true>), grid, dim3(256), lds, s, a);                \
-                          else hipLaunchKernelGGL((K<false, true>), grid, dim3(256), lds, s, a); }                 \
-        else if (vec) hipLaunchKernelGGL((K<true, false>), grid, dim3(256), lds, s, a);                            \
-        else hipLaunchKernelGGL((K<false, false>), grid, dim3(256), lds, s, a);                                    \
-    } while (0)
+void rs_launch(bool ragged, bool prob, bool win, int batch, const mbn_resample_launch_t &l, hipStream_t s, const ResampleArgs &a)
+{
+    const bool vec = ((uintptr_t)a.logits % 16) == 0 && (a.classes % 4) == 0;
+    hipLaunchKernelGGL(rs_kernels[ragged][prob][win][vec], dim3((unsigned)l.tiles, (unsigned)batch), dim3(256), (size_t)l.lds_bytes, s, a);
+}
 
 }   // namespace
 
-// The shape is inside mbn_resample_argmax_envelope and the pointers are non-null multiples of 4 (the caller has checked both).
+// rect = (x, y, iw, ih) of the in_rows x in_cols network input: the window kernels; null: the whole map, the plain kernels (in_rows, in_cols are not
+// read). The shape is inside mbn_resample_window_envelope, without a rect mbn_resample_argmax_envelope, and the pointers are non-null multiples of 4
+// (the caller has checked both).
 int mbn_launch_f32_resample_argmax(mbn_context *, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows, int cols,
-                                   int classes, int out_rows, int out_cols, const mbn_readout_prob *q)
+                                   int classes, int in_rows, int in_cols, const int32_t *rect, int out_rows, int out_cols, const mbn_readout_prob *q)
 {
     mbn_resample_launch_t l = { 0, 0, 0, 0, 0, 0 };
-    mbn_resample_plan(rows, cols, out_rows, out_cols, &l);
-    ResampleArgs a = {};
-    a.labels = labels; a.score = score; a.logits = logits;
-    a.rows = rows; a.cols = cols; a.classes = classes;
+    if (rect) mbn_resample_window_plan(rows, cols, in_rows, in_cols, rect, out_rows, out_cols, &l);
+    else mbn_resample_plan(rows, cols, out_rows, out_cols, &l);
+    ResampleArgs a = rs_args(labels, score, logits, rows, cols, classes, l, in_rows, in_cols, q);
     a.out_rows = out_rows; a.out_cols = out_cols;
     a.tiles_x = (out_cols + RS_TILE - 1) / RS_TILE;
-    a.fy = l.fy; a.fx = l.fx; a.ch = l.ch;
-    set_prob(a, q);
-    const dim3 grid((unsigned)l.tiles, (unsigned)batch);
-    RS_LAUNCH(resample_argmax_f32, resample_softmax_f32, vec_loads(logits, classes), false, q != nullptr, grid, (size_t)l.lds_bytes, s, a);
-    return MBN_OK;
-}
-
-// The shape and the window are inside mbn_resample_window_envelope and the pointers are non-null multiples of 4 (the caller has checked both).
-int mbn_launch_f32_resample_argmax_window(mbn_context *, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows,
-                                          int cols, int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols,
-                                          const mbn_readout_prob *q)
-{
-    mbn_resample_launch_t l = { 0, 0, 0, 0, 0, 0 };
-    mbn_resample_window_plan(rows, cols, in_rows, in_cols, rect, out_rows, out_cols, &l);
-    ResampleArgs a = {};
-    a.labels = labels; a.score = score; a.logits = logits;
-    a.rows = rows; a.cols = cols; a.classes = classes;
-    a.out_rows = out_rows; a.out_cols = out_cols;
-    a.tiles_x = (out_cols + RS_TILE - 1) / RS_TILE;
-    a.fy = l.fy; a.fx = l.fx; a.ch = l.ch;
-    a.in_rows = in_rows; a.in_cols = in_cols;
-    a.wx = rect[0]; a.wy = rect[1]; a.wiw = rect[2]; a.wih = rect[3];
-    set_prob(a, q);
-    const dim3 grid((unsigned)l.tiles, (unsigned)batch);
-    RS_LAUNCH(resample_argmax_f32, resample_softmax_f32, vec_loads(logits, classes), true, q != nullptr, grid, (size_t)l.lds_bytes, s, a);
+    if (rect) { a.wx = rect[0]; a.wy = rect[1]; a.wiw = rect[2]; a.wih = rect[3]; }
+    rs_launch(false, q != nullptr, rect != nullptr, batch, l, s, a);
     return MBN_OK;
 }
 
@@ -418,12 +407,20 @@ void mbn_ragged_readout_release(mbn_ragged_readout *r)
     delete r;
 }
 
-// A checked batch becomes the handle's set: waits for what still reads either copy (the previous upload and every launch since), writes the items
-// (item_bytes each: mbn_label_item, or mbn_label_window_item when `window`) into the pinned copy and enqueues its upload.
-static int readout_upload(mbn_ragged_readout *r, hipStream_t s, int rows, int cols, int classes, int window, int in_rows, int in_cols,
-                          const void *items, size_t item_bytes, int batch, const mbn_resample_launch_t &l)
+// Checks the batch first and touches nothing when it is refused: the previous set stays. Then the batch becomes the handle's set: waits for what
+// still reads either copy (the previous upload and every launch since), writes the items into the pinned copy and enqueues its upload.
+// window: the items are mbn_label_window_item, each with its own rectangle of the in_rows x in_cols network input; else mbn_label_item.
+int mbn_ragged_readout_plan(mbn_ragged_readout *r, hipStream_t s, int rows, int cols, int classes, int window, int in_rows, int in_cols,
+                            const void *items, int batch)
 {
     mbn_context *ctx = r->ctx;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return MBN_EINVAL;      // a set is not part of a graph
+    mbn_resample_launch_t l = { 0, 0, 0, 0, 0, 0 };
+    const int rc = window ? mbn_resample_ragged_window_check(rows, cols, classes, in_rows, in_cols, (const mbn_label_window_item *)items, batch, r->sort, &l)
+                          : mbn_resample_ragged_check(rows, cols, classes, (const mbn_label_item *)items, batch, r->sort, &l);
+    if (rc != MBN_OK) return rc;
+    const size_t item_bytes = window ? sizeof(mbn_label_window_item) : sizeof(mbn_label_item);
     MBN_HIP_TRY(ctx, hipEventSynchronize(r->done));
     ReadoutHead *h = (ReadoutHead *)r->host;
     memset(h, 0, sizeof *h);
@@ -440,47 +437,17 @@ static int readout_upload(mbn_ragged_readout *r, hipStream_t s, int rows, int co
     return MBN_OK;
 }
 
-// Checks the batch first and touches nothing when it is refused: the previous set stays.
-int mbn_ragged_readout_plan(mbn_ragged_readout *r, hipStream_t s, int rows, int cols, int classes, const mbn_label_item *items, int batch)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return MBN_EINVAL;      // a set is not part of a graph
-    mbn_resample_launch_t l = { 0, 0, 0, 0, 0, 0 };
-    const int rc = mbn_resample_ragged_check(rows, cols, classes, items, batch, r->sort, &l);
-    if (rc != MBN_OK) return rc;
-    return readout_upload(r, s, rows, cols, classes, 0, 0, 0, items, sizeof(mbn_label_item), batch, l);
-}
-
-// The window set: the same, with every item's own rectangle of the in_rows x in_cols network input.
-int mbn_ragged_readout_plan_window(mbn_ragged_readout *r, hipStream_t s, int rows, int cols, int classes, int in_rows, int in_cols,
-                                   const mbn_label_window_item *items, int batch)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return MBN_EINVAL;
-    mbn_resample_launch_t l = { 0, 0, 0, 0, 0, 0 };
-    const int rc = mbn_resample_ragged_window_check(rows, cols, classes, in_rows, in_cols, items, batch, r->sort, &l);
-    if (rc != MBN_OK) return rc;
-    return readout_upload(r, s, rows, cols, classes, 1, in_rows, in_cols, items, sizeof(mbn_label_window_item), batch, l);
-}
-
 // the handle has a batch, the pointers are non-null multiples of 4 and the spans fit (the caller has checked)
 int mbn_launch_f32_resample_argmax_ragged(mbn_ragged_readout *r, hipStream_t s, int32_t *labels, float *score, const float *logits,
                                           const mbn_readout_prob *q)
 {
-    ResampleArgs a = {};
-    a.labels = labels; a.score = score; a.logits = logits;
-    a.rows = r->rows; a.cols = r->cols; a.classes = r->classes;
+    ResampleArgs a = rs_args(labels, score, logits, r->rows, r->cols, r->classes, r->launch, r->in_rows, r->in_cols, q);
     a.tiles_x = 1;                                              // unused: a workgroup takes its image's own
-    a.fy = r->launch.fy; a.fx = r->launch.fx; a.ch = r->launch.ch;
     a.head = (const ReadoutHead *)r->dev;
     a.items = (const mbn_label_item *)(a.head + 1);
     a.witems = (const mbn_label_window_item *)(a.head + 1);     // the last set decides which of the two the block holds
-    a.in_rows = r->in_rows; a.in_cols = r->in_cols;
     a.generation = r->generation;
-    set_prob(a, q);
-    const dim3 grid((unsigned)r->launch.tiles, (unsigned)r->batch);
-    RS_LAUNCH(resample_argmax_ragged_f32, resample_softmax_ragged_f32, vec_loads(logits, r->classes), r->window != 0, q != nullptr, grid,
-              (size_t)r->launch.lds_bytes, s, a);
+    rs_launch(true, q != nullptr, r->window != 0, r->batch, r->launch, s, a);
     // the next set waits for this launch; inside a capture there is nothing to wait for (the replays are the caller's to order)
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) (void)hipEventRecord(r->done, s);

@@ -274,20 +274,18 @@ int mbn_launch_f32_softmax_topk(mbn_context *ctx, hipStream_t s, float *probs, i
 int mbn_launch_f32_upsample_argmax(mbn_context *ctx, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows,
                                    int cols, int classes, int factor);
 // dense head read-out at any output size (mbn_f32_resample.hip): bilinear resample to out_rows x out_cols + argmax; the shape is inside
-// mbn_resample_argmax_envelope. Ragged form: build allocates, plan checks a batch (a refused one changes nothing) and enqueues the items' upload.
+// mbn_resample_argmax_envelope, or with rect = (x, y, iw, ih) of the in_rows x in_cols network input (null: the whole map) inside
+// mbn_resample_window_envelope. Ragged form: build allocates, plan checks a batch of mbn_label_item, or with `window` of mbn_label_window_item (a
+// refused one changes nothing), and enqueues the items' upload.
 // q = null: the argmax kernels. q given: the softmax kernels (mbn_resample_softmax_*), which also write prob (may be null when min_prob > 0) and
 // store ignore_label where prob < min_prob.
 struct mbn_readout_prob { float *prob; float min_prob; int ignore_label; };
 int mbn_launch_f32_resample_argmax(mbn_context *ctx, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows, int cols,
-                                   int classes, int out_rows, int out_cols, const mbn_readout_prob *q);
-int mbn_launch_f32_resample_argmax_window(mbn_context *ctx, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows,
-                                          int cols, int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols,
-                                          const mbn_readout_prob *q);
+                                   int classes, int in_rows, int in_cols, const int32_t *rect, int out_rows, int out_cols, const mbn_readout_prob *q);
 int mbn_ragged_readout_build(mbn_context *ctx, int max_batch, mbn_ragged_readout **r);
 void mbn_ragged_readout_release(mbn_ragged_readout *r);
-int mbn_ragged_readout_plan(mbn_ragged_readout *r, hipStream_t s, int rows, int cols, int classes, const mbn_label_item *items, int batch);
-int mbn_ragged_readout_plan_window(mbn_ragged_readout *r, hipStream_t s, int rows, int cols, int classes, int in_rows, int in_cols,
-                                   const mbn_label_window_item *items, int batch);
+int mbn_ragged_readout_plan(mbn_ragged_readout *r, hipStream_t s, int rows, int cols, int classes, int window, int in_rows, int in_cols,
+                            const void *items, int batch);
 int mbn_launch_f32_resample_argmax_ragged(mbn_ragged_readout *r, hipStream_t s, int32_t *labels, float *score, const float *logits,
                                           const mbn_readout_prob *q);
 // resize front-end (mbn_u8_resize.hip): the geometry is inside mbn_resize_envelope; build uploads the tables (blocking), release frees them

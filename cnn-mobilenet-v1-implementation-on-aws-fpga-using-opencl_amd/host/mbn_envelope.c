@@ -3,7 +3,9 @@
 #include "mbn_envelope.h"
 #include "mbn.h"
 
+#include <stddef.h>
 #include <stdlib.h>
+#include <string.h>
 
 int mbn_block_envelope(const mbn_block_shape *s, int dtype)
 {
@@ -88,59 +90,6 @@ int mbn_upsample_argmax_envelope(int batch, int rows, int cols, int classes, int
     return MBN_OK;
 }
 
-int mbn_resample_argmax_envelope(int batch, int rows, int cols, int classes, int out_rows, int out_cols)
-{
-    if (batch <= 0 || rows <= 0 || cols <= 0 || classes <= 0 || out_rows <= 0 || out_cols <= 0) return MBN_EINVAL;
-    if (batch > MBN_DENSE_MAX_BATCH || out_rows > MBN_RESAMPLE_MAX_OUT || out_cols > MBN_RESAMPLE_MAX_OUT) return MBN_EUNSUPPORTED;
-    if (out_rows < (int64_t)MBN_RESAMPLE_MIN_RATIO * rows || out_cols < (int64_t)MBN_RESAMPLE_MIN_RATIO * cols) return MBN_EUNSUPPORTED;
-    if (4.0 * rows * cols * classes >= 2147483648.0) return MBN_EUNSUPPORTED;                                   /* an image's logits */
-    if (4.0 * out_rows * out_cols >= 2147483648.0) return MBN_EUNSUPPORTED;                                     /* an image's labels / scores */
-    if ((long)((out_rows + MBN_RESAMPLE_TILE - 1) / MBN_RESAMPLE_TILE) * ((out_cols + MBN_RESAMPLE_TILE - 1) / MBN_RESAMPLE_TILE) > MBN_DENSE_MAX_TILES)
-        return MBN_EUNSUPPORTED;
-    return MBN_OK;
-}
-
-void mbn_resample_plan(int rows, int cols, int out_rows, int out_cols, mbn_resample_launch_t *l)
-{
-    const int fy = MBN_RESAMPLE_FOOT(rows, out_rows), fx = MBN_RESAMPLE_FOOT(cols, out_cols);
-    const int tiles = ((out_rows + MBN_RESAMPLE_TILE - 1) / MBN_RESAMPLE_TILE) * ((out_cols + MBN_RESAMPLE_TILE - 1) / MBN_RESAMPLE_TILE);
-    if (fy > l->fy) l->fy = fy;
-    if (fx > l->fx) l->fx = fx;
-    if (tiles > l->tiles) l->tiles = tiles;
-    if ((int64_t)out_rows * out_cols > l->span) l->span = (int64_t)out_rows * out_cols;
-    l->ch = MBN_RESAMPLE_CH(l->fy * l->fx);
-    l->lds_bytes = l->fy * l->fx * (l->ch + 4) * 4;
-}
-
-static int cmp_i64_pair(const void *a, const void *b)
-{
-    const int64_t x = *(const int64_t *)a, y = *(const int64_t *)b;
-    return x < y ? -1 : x > y;
-}
-
-int mbn_resample_ragged_check(int rows, int cols, int classes, const mbn_label_item *items, int batch, int64_t *sort, mbn_resample_launch_t *l)
-{
-    if (!items || !sort || !l || batch <= 0) return MBN_EINVAL;
-    const mbn_resample_launch_t zero = { 0, 0, 0, 0, 0, 0 };
-    mbn_resample_launch_t acc = zero;
-    int64_t span = 0;
-    for (int i = 0; i < batch; i++) {
-        if (items[i].dst_offset < 0) return MBN_EINVAL;
-        const int rc = mbn_resample_argmax_envelope(batch, rows, cols, classes, items[i].rows, items[i].cols);
-        if (rc != MBN_OK) return rc;
-        mbn_resample_plan(rows, cols, items[i].rows, items[i].cols, &acc);
-        sort[2 * i] = items[i].dst_offset;
-        sort[2 * i + 1] = items[i].dst_offset + (int64_t)items[i].rows * items[i].cols;
-        if (sort[2 * i + 1] > span) span = sort[2 * i + 1];
-    }
-    qsort(sort, (size_t)batch, 2 * sizeof(int64_t), cmp_i64_pair);
-    for (int i = 0; i + 1 < batch; i++)
-        if (sort[2 * i + 1] > sort[2 * i + 2]) return MBN_EINVAL;                                               /* two maps overlap */
-    acc.span = span;
-    *l = acc;
-    return MBN_OK;
-}
-
 int mbn_softmax_readout_check(int have_prob, float min_prob)
 {
     if (!(min_prob >= 0.0f && min_prob <= 1.0f)) return MBN_EINVAL;      /* a NaN fails both compares */
@@ -148,6 +97,9 @@ int mbn_softmax_readout_check(int have_prob, float min_prob)
     return MBN_OK;
 }
 
+/* The read-out at any output size has ONE geometry, the window's: the whole map is the window that covers the whole input, rect = (0, 0, cols, rows)
+ * of in = (rows, cols). There the ratio test is out >= 4 x coarse and MBN_RESAMPLE_WINDOW_FOOT is MBN_RESAMPLE_FOOT, so the plain functions are the
+ * window functions of that rectangle: same status for every argument, same launch (tests/test_dense_window_cpu.py sweeps both). */
 int mbn_resample_window_envelope(int batch, int rows, int cols, int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows,
                                  int out_cols)
 {
@@ -168,6 +120,12 @@ int mbn_resample_window_envelope(int batch, int rows, int cols, int classes, int
     return MBN_OK;
 }
 
+int mbn_resample_argmax_envelope(int batch, int rows, int cols, int classes, int out_rows, int out_cols)
+{
+    const int32_t full[4] = { 0, 0, cols, rows };
+    return mbn_resample_window_envelope(batch, rows, cols, classes, rows, cols, full, out_rows, out_cols);
+}
+
 void mbn_resample_window_plan(int rows, int cols, int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols,
                               mbn_resample_launch_t *l)
 {
@@ -181,21 +139,40 @@ void mbn_resample_window_plan(int rows, int cols, int in_rows, int in_cols, cons
     l->lds_bytes = l->fy * l->fx * (l->ch + 4) * 4;
 }
 
-int mbn_resample_ragged_window_check(int rows, int cols, int classes, int in_rows, int in_cols, const mbn_label_window_item *items, int batch,
-                                     int64_t *sort, mbn_resample_launch_t *l)
+void mbn_resample_plan(int rows, int cols, int out_rows, int out_cols, mbn_resample_launch_t *l)
+{
+    const int32_t full[4] = { 0, 0, cols, rows };
+    mbn_resample_window_plan(rows, cols, rows, cols, full, out_rows, out_cols, l);
+}
+
+static int cmp_i64_pair(const void *a, const void *b)
+{
+    const int64_t x = *(const int64_t *)a, y = *(const int64_t *)b;
+    return x < y ? -1 : x > y;
+}
+
+/* Both kinds of ragged set: `items` holds `batch` items of item_bytes each, mbn_label_item or mbn_label_window_item, which begins with the former's
+ * fields. A plain item's rectangle is the whole in_rows x in_cols input (the caller passes rows x cols) */
+_Static_assert(offsetof(mbn_label_window_item, x) == sizeof(mbn_label_item), "a window item is a label item and its rectangle");
+static int ragged_check(int rows, int cols, int classes, int in_rows, int in_cols, const void *items, size_t item_bytes, int batch, int64_t *sort,
+                        mbn_resample_launch_t *l)
 {
     if (!items || !sort || !l || batch <= 0) return MBN_EINVAL;
     const mbn_resample_launch_t zero = { 0, 0, 0, 0, 0, 0 };
     mbn_resample_launch_t acc = zero;
     int64_t span = 0;
     for (int i = 0; i < batch; i++) {
-        if (items[i].dst_offset < 0) return MBN_EINVAL;
-        const int32_t rect[4] = { items[i].x, items[i].y, items[i].iw, items[i].ih };
-        const int rc = mbn_resample_window_envelope(batch, rows, cols, classes, in_rows, in_cols, rect, items[i].rows, items[i].cols);
+        const char *at = (const char *)items + (size_t)i * item_bytes;
+        mbn_label_item it;
+        int32_t rect[4] = { 0, 0, in_cols, in_rows };
+        memcpy(&it, at, sizeof it);
+        if (item_bytes == sizeof(mbn_label_window_item)) memcpy(rect, at + sizeof it, sizeof rect);
+        if (it.dst_offset < 0) return MBN_EINVAL;
+        const int rc = mbn_resample_window_envelope(batch, rows, cols, classes, in_rows, in_cols, rect, it.rows, it.cols);
         if (rc != MBN_OK) return rc;
-        mbn_resample_window_plan(rows, cols, in_rows, in_cols, rect, items[i].rows, items[i].cols, &acc);
-        sort[2 * i] = items[i].dst_offset;
-        sort[2 * i + 1] = items[i].dst_offset + (int64_t)items[i].rows * items[i].cols;
+        mbn_resample_window_plan(rows, cols, in_rows, in_cols, rect, it.rows, it.cols, &acc);
+        sort[2 * i] = it.dst_offset;
+        sort[2 * i + 1] = it.dst_offset + (int64_t)it.rows * it.cols;
         if (sort[2 * i + 1] > span) span = sort[2 * i + 1];
     }
     qsort(sort, (size_t)batch, 2 * sizeof(int64_t), cmp_i64_pair);
@@ -204,6 +181,17 @@ int mbn_resample_ragged_window_check(int rows, int cols, int classes, int in_row
     acc.span = span;
     *l = acc;
     return MBN_OK;
+}
+
+int mbn_resample_ragged_check(int rows, int cols, int classes, const mbn_label_item *items, int batch, int64_t *sort, mbn_resample_launch_t *l)
+{
+    return ragged_check(rows, cols, classes, rows, cols, items, sizeof *items, batch, sort, l);
+}
+
+int mbn_resample_ragged_window_check(int rows, int cols, int classes, int in_rows, int in_cols, const mbn_label_window_item *items, int batch,
+                                     int64_t *sort, mbn_resample_launch_t *l)
+{
+    return ragged_check(rows, cols, classes, in_rows, in_cols, items, sizeof *items, batch, sort, l);
 }
 
 static long lmin(long a, long b) { return a < b ? a : b; }

@@ -889,6 +889,16 @@ int mbn_net_forward_dense(mbn_net *net, const void *images, void *dense_logits, 
     return run_layer_on(net, fc, net->dense_feat, dense_logits, batch, NULL, feat->out_rows, feat->out_cols);
 }
 
+/* the dense logits of `batch` images into net->dense_logits, [max_batch][h][w][classes] fp32, allocated on first use */
+static int dense_forward(mbn_net *net, const mbn_layer_desc *feat, const mbn_layer_desc *fc, const void *images, int batch)
+{
+    if (!net->dense_logits) {
+        const int rc = mbn_alloc(net->ctx, (size_t)net->max_batch * feat->out_rows * feat->out_cols * fc->out_ch * sizeof(float), &net->dense_logits);
+        if (rc != MBN_OK) { net->dense_logits = NULL; return rc; }
+    }
+    return mbn_net_forward_dense(net, images, net->dense_logits, batch);
+}
+
 int mbn_net_segment(mbn_net *net, const void *images, int batch, void *labels_i32, void *score_f32)
 {
     if (!net || !images || !labels_i32 || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
@@ -898,22 +908,9 @@ int mbn_net_segment(mbn_net *net, const void *images, int batch, void *labels_i3
     const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols, h = feat->out_rows, w = feat->out_cols;
     const int factor = rows / h;
     if (factor * h != rows || factor * w != cols || (factor != 8 && factor != 16 && factor != 32)) return MBN_EUNSUPPORTED;
-    if (!net->dense_logits) {
-        rc = mbn_alloc(net->ctx, (size_t)net->max_batch * h * w * fc->out_ch * sizeof(float), &net->dense_logits);
-        if (rc != MBN_OK) { net->dense_logits = NULL; return rc; }
-    }
-    rc = mbn_net_forward_dense(net, images, net->dense_logits, batch);
+    rc = dense_forward(net, feat, fc, images, batch);
     if (rc != MBN_OK) return rc;
     return mbn_upsample_argmax_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, factor, NULL);
-}
-
-/* the net's dense logits, [max_batch][h][w][classes] fp32, allocated on first use */
-static int dense_logits_buf(mbn_net *net, const mbn_layer_desc *feat, const mbn_layer_desc *fc)
-{
-    if (net->dense_logits) return MBN_OK;
-    const int rc = mbn_alloc(net->ctx, (size_t)net->max_batch * feat->out_rows * feat->out_cols * fc->out_ch * sizeof(float), &net->dense_logits);
-    if (rc != MBN_OK) net->dense_logits = NULL;
-    return rc;
 }
 
 /* The read-out of the three source-size paths below: q = NULL is the argmax read-out (labels and score), q given the softmax read-out
@@ -932,22 +929,44 @@ static int prob_status(const readout_prob *q)
     return mbn_softmax_readout_check(q->prob != NULL, q->min_prob);
 }
 
+/* The uniform read-out of the net's dense logits at out_rows x out_cols: of the window `rect` of the network's input, or (rect = NULL) of the whole
+ * map. uniform_envelope is asked before the resize and the forward run; uniform_readout is the one place that chooses among the four public calls. */
+static int uniform_envelope(const mbn_net *net, const mbn_layer_desc *feat, const mbn_layer_desc *fc, int batch, const int32_t *rect, int out_rows,
+                            int out_cols)
+{
+    if (rect)
+        return mbn_resample_window_envelope(batch, feat->out_rows, feat->out_cols, fc->out_ch, net->plan.layer[0].in_rows, net->plan.layer[0].in_cols,
+                                            rect, out_rows, out_cols);
+    /* every size is positive here (the callers' checks, dense_layers): what the plain shape can miss is a limit */
+    return mbn_resample_argmax_envelope(batch, feat->out_rows, feat->out_cols, fc->out_ch, out_rows, out_cols) != MBN_OK ? MBN_EUNSUPPORTED : MBN_OK;
+}
+
+static int uniform_readout(mbn_net *net, const mbn_layer_desc *feat, const mbn_layer_desc *fc, int batch, const int32_t *rect, int out_rows,
+                           int out_cols, void *labels_i32, void *score_f32, const readout_prob *q)
+{
+    const int h = feat->out_rows, w = feat->out_cols, rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols;
+    if (q && rect)
+        return mbn_resample_softmax_window_f32(net->ctx, labels_i32, q->prob, NULL, net->dense_logits, batch, h, w, fc->out_ch, rows, cols, rect,
+                                               out_rows, out_cols, q->min_prob, q->ignore_label, NULL);
+    if (q)
+        return mbn_resample_softmax_f32(net->ctx, labels_i32, q->prob, NULL, net->dense_logits, batch, h, w, fc->out_ch, out_rows, out_cols, q->min_prob,
+                                        q->ignore_label, NULL);
+    if (rect)
+        return mbn_resample_argmax_window_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, rows, cols, rect, out_rows,
+                                              out_cols, NULL);
+    return mbn_resample_argmax_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, out_rows, out_cols, NULL);
+}
+
 static int segment_to(mbn_net *net, const void *images, int batch, int out_rows, int out_cols, void *labels_i32, void *score_f32, const readout_prob *q)
 {
     if (!net || !images || !labels_i32 || batch <= 0 || batch > net->max_batch || out_rows <= 0 || out_cols <= 0) return MBN_EINVAL;
     if (prob_status(q) != MBN_OK) return MBN_EINVAL;
     const mbn_layer_desc *feat, *fc;
     int rc = dense_layers(net, &feat, &fc);
+    if (rc == MBN_OK) rc = uniform_envelope(net, feat, fc, batch, NULL, out_rows, out_cols);
+    if (rc == MBN_OK) rc = dense_forward(net, feat, fc, images, batch);
     if (rc != MBN_OK) return rc;
-    const int h = feat->out_rows, w = feat->out_cols;
-    if (mbn_resample_argmax_envelope(batch, h, w, fc->out_ch, out_rows, out_cols) != MBN_OK) return MBN_EUNSUPPORTED;   /* before the forward runs */
-    rc = dense_logits_buf(net, feat, fc);
-    if (rc == MBN_OK) rc = mbn_net_forward_dense(net, images, net->dense_logits, batch);
-    if (rc != MBN_OK) return rc;
-    if (q)
-        return mbn_resample_softmax_f32(net->ctx, labels_i32, q->prob, NULL, net->dense_logits, batch, h, w, fc->out_ch, out_rows, out_cols, q->min_prob,
-                                        q->ignore_label, NULL);
-    return mbn_resample_argmax_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, out_rows, out_cols, NULL);
+    return uniform_readout(net, feat, fc, batch, NULL, out_rows, out_cols, labels_i32, score_f32, q);
 }
 
 int mbn_net_segment_to(mbn_net *net, const void *images, int batch, int out_rows, int out_cols, void *labels_i32, void *score_f32)
@@ -980,29 +999,20 @@ static int segment_fit(mbn_net *net, const void *src_u8, int batch, int in_rows,
     const mbn_layer_desc *feat, *fc;
     rc = dense_layers(net, &feat, &fc);
     if (rc != MBN_OK) return rc;
-    const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols, h = feat->out_rows, w = feat->out_cols;
-    int32_t rect[4] = { 0, 0, cols, rows };
-    /* the envelope before the resize and the forward run */
+    int32_t pad[4];
+    const int32_t *rect = NULL;                               /* a stretch reads out the whole map */
     if (fit == MBN_FIT_PAD) {
-        rc = mbn_fit_pad(in_rows, in_cols, rows, cols, rect);
-        if (rc == MBN_OK) rc = mbn_resample_window_envelope(batch, h, w, fc->out_ch, rows, cols, rect, in_rows, in_cols);
+        rc = mbn_fit_pad(in_rows, in_cols, net->plan.layer[0].in_rows, net->plan.layer[0].in_cols, pad);
         if (rc != MBN_OK) return rc;
-    } else if (mbn_resample_argmax_envelope(batch, h, w, fc->out_ch, in_rows, in_cols) != MBN_OK) return MBN_EUNSUPPORTED;
+        rect = pad;
+    }
+    rc = uniform_envelope(net, feat, fc, batch, rect, in_rows, in_cols);
+    if (rc != MBN_OK) return rc;
     void *images = NULL;
     rc = mbn_net_resize_input(net, src_u8, batch, in_rows, in_cols, fit, 1.0f, &images);
-    if (rc == MBN_OK) rc = dense_logits_buf(net, feat, fc);
-    if (rc == MBN_OK) rc = mbn_net_forward_dense(net, images, net->dense_logits, batch);
+    if (rc == MBN_OK) rc = dense_forward(net, feat, fc, images, batch);
     if (rc != MBN_OK) return rc;
-    if (q && fit == MBN_FIT_PAD)
-        return mbn_resample_softmax_window_f32(net->ctx, labels_i32, q->prob, NULL, net->dense_logits, batch, h, w, fc->out_ch, rows, cols, rect,
-                                               in_rows, in_cols, q->min_prob, q->ignore_label, NULL);
-    if (q)
-        return mbn_resample_softmax_f32(net->ctx, labels_i32, q->prob, NULL, net->dense_logits, batch, h, w, fc->out_ch, in_rows, in_cols, q->min_prob,
-                                        q->ignore_label, NULL);
-    if (fit == MBN_FIT_PAD)
-        return mbn_resample_argmax_window_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, rows, cols, rect, in_rows,
-                                              in_cols, NULL);
-    return mbn_resample_argmax_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, in_rows, in_cols, NULL);
+    return uniform_readout(net, feat, fc, batch, rect, in_rows, in_cols, labels_i32, score_f32, q);
 }
 
 int mbn_net_segment_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, void *labels_i32, void *score_f32)
@@ -1039,24 +1049,16 @@ static int segment_images_fit(mbn_net *net, const void *src_u8, const int64_t *o
         net->label_items = malloc((size_t)net->max_batch * sizeof(mbn_label_window_item));       /* either kind of item */
         if (!net->label_items) return MBN_ENOMEM;
     }
-    if (fit == MBN_FIT_PAD) {
-        mbn_label_window_item *items = net->label_items;
-        for (int i = 0; i < batch; i++) {
-            int32_t rect[4];
+    /* a window item is a label item and then its rectangle: the first item_bytes of `it` are the item of either kind */
+    const size_t item_bytes = fit == MBN_FIT_PAD ? sizeof(mbn_label_window_item) : sizeof(mbn_label_item);
+    for (int i = 0; i < batch; i++) {
+        int32_t rect[4] = { 0, 0, 0, 0 };
+        if (fit == MBN_FIT_PAD) {
             rc = mbn_fit_pad(in_rows[i], in_cols[i], rows, cols, rect);
             if (rc != MBN_OK) return rc;
-            items[i].dst_offset = dst_offsets[i];
-            items[i].rows = in_rows[i];
-            items[i].cols = in_cols[i];
-            items[i].x = rect[0]; items[i].y = rect[1]; items[i].iw = rect[2]; items[i].ih = rect[3];
         }
-    } else {
-        mbn_label_item *items = net->label_items;
-        for (int i = 0; i < batch; i++) {
-            items[i].dst_offset = dst_offsets[i];
-            items[i].rows = in_rows[i];
-            items[i].cols = in_cols[i];
-        }
+        const mbn_label_window_item it = { dst_offsets[i], in_rows[i], in_cols[i], rect[0], rect[1], rect[2], rect[3] };
+        memcpy((char *)net->label_items + (size_t)i * item_bytes, &it, item_bytes);
     }
     if (!net->readout) {
         rc = mbn_ragged_readout_create(net->ctx, net->max_batch, &net->readout);
@@ -1068,8 +1070,7 @@ static int segment_images_fit(mbn_net *net, const void *src_u8, const int64_t *o
     if (rc != MBN_OK) return rc;
     void *images = NULL;
     rc = mbn_net_resize_inputs(net, src_u8, offsets, in_rows, in_cols, batch, fit, 1.0f, &images);
-    if (rc == MBN_OK) rc = dense_logits_buf(net, feat, fc);
-    if (rc == MBN_OK) rc = mbn_net_forward_dense(net, images, net->dense_logits, batch);
+    if (rc == MBN_OK) rc = dense_forward(net, feat, fc, images, batch);
     if (rc != MBN_OK) return rc;
     if (q) return mbn_resample_softmax_ragged_f32(net->readout, labels_i32, q->prob, NULL, net->dense_logits, q->min_prob, q->ignore_label, NULL);
     return mbn_resample_argmax_ragged_f32(net->readout, labels_i32, score_f32, net->dense_logits, NULL);

@@ -292,6 +292,92 @@ def test_ragged_window_check(pkg):
     assert rc == pkg.OK and _fields(rec) == _fields(l)
 
 
+# ------------------------------------------------------------------------------------------- the whole map is the full window
+
+def _edge_geometry(rng):
+    """(batch, rows, cols, classes, H, W): inside the envelope of mbn_resample_argmax_f32 unless `edge` pushes one argument onto or over a limit"""
+    rows, cols = int(rng.integers(1, 48)), int(rng.integers(1, 48))
+    H, W = int(rng.integers(4 * rows, 12 * rows + 1)), int(rng.integers(4 * cols, 12 * cols + 1))
+    batch, classes = int(rng.integers(1, 65)), int(rng.integers(1, 1001))
+    edge = int(rng.integers(0, 40))                          # 20 and above: none
+    zero = int(rng.integers(-1, 1))                          # 0 or -1
+    if edge == 0: rows = zero
+    elif edge == 1: cols = zero
+    elif edge == 2: H = zero
+    elif edge == 3: W = zero
+    elif edge == 4: classes = zero
+    elif edge == 5: batch = zero
+    elif edge == 6: H = 16385
+    elif edge == 7: W = 16385
+    elif edge == 8: H = W = 16384
+    elif edge == 9: H = 4 * rows - 1                         # the ratio just under 4
+    elif edge == 10: W = 4 * cols - 1
+    elif edge == 11: H, W = 4 * rows, 4 * cols               # and exactly 4
+    elif edge == 12: batch = 65536
+    elif edge == 13: batch = 65535
+    elif edge == 14: classes = -(-2 ** 29 // (rows * cols))  # the first class count at which an image's logits reach 2^31 bytes
+    elif edge == 15: classes = -(-2 ** 29 // (rows * cols)) - 1
+    elif edge == 16: rows, H = 16385, 16384                  # a map no output can be four times of
+    elif edge == 17: rows, H = 4096, 16384
+    elif edge == 18: rows, H = 4097, 16384
+    elif edge == 19: cols, W, rows, H = 4096, 16384, 4096, 16384
+    return batch, rows, cols, classes, H, W
+
+
+def _multiple(rng, rows, cols):
+    """1, or m >= 2 with m * rows and m * cols at most 16384 where there is one"""
+    top = 16384 // max(rows, cols, 1)
+    return int(rng.integers(2, top + 1)) if top >= 2 and rng.integers(0, 4) else 1
+
+
+def test_whole_map_is_the_full_window(pkg):
+    """What lets host/mbn_envelope.c keep ONE geometry: the plain envelope, plan and ragged check are the window ones given the rectangle
+    (0, 0, in_cols, in_rows), for in = (rows, cols) and for a multiple of it: the same status for every argument, refusals included, and where both
+    accept the same mbn_resample_launch_t field for field. A fixed-seed sweep that sits on the limits (sides 0, -1, 16384 and 16385, ratio 4 and
+    just under it, batch 65535 and 65536, class counts on both sides of the byte limit) and must see all three statuses."""
+    host = pkg.host_lib()
+    rng = np.random.default_rng(11)
+    rect4, seen = C.c_int32 * 4, set()
+    for _ in range(3000):
+        batch, rows, cols, classes, H, W = _edge_geometry(rng)
+        want = host.mbn_resample_argmax_envelope(batch, rows, cols, classes, H, W)
+        seen.add(want)
+        for m in {1, _multiple(rng, rows, cols)}:
+            full = rect4(0, 0, m * cols, m * rows)
+            got = host.mbn_resample_window_envelope(batch, rows, cols, classes, m * rows, m * cols, full, H, W)
+            assert got == want, (batch, rows, cols, classes, H, W, m, got, want)
+            if want == pkg.OK:
+                a, b = pkg.ResampleLaunch(), pkg.ResampleLaunch()
+                host.mbn_resample_plan(rows, cols, H, W, C.byref(a))
+                host.mbn_resample_window_plan(rows, cols, m * rows, m * cols, full, H, W, C.byref(b))
+                assert _fields(a) == _fields(b), (rows, cols, H, W, m)
+    assert seen == {pkg.OK, pkg.EINVAL, pkg.EUNSUPPORTED}, seen
+    # ragged: item lists that differ only in carrying the full rectangle
+    seen = set()
+    for _ in range(1500):
+        _, rows, cols, classes, _, _ = _edge_geometry(rng)
+        m = _multiple(rng, rows, cols)
+        plain, window, at = [], [], 0
+        for _ in range(int(rng.integers(1, 6))):
+            _, _, _, _, H, W = _edge_geometry(rng)
+            if rng.integers(0, 3):                           # mostly an output of THIS map
+                H, W = int(rng.integers(4 * max(rows, 1), 12 * max(rows, 1) + 1)), int(rng.integers(4 * max(cols, 1), 12 * max(cols, 1) + 1))
+            at += int(rng.integers(-1, 50)) if rng.integers(0, 8) else -int(rng.integers(0, 3))     # touching, a gap, or now and then an overlap
+            plain.append((at, H, W))
+            window.append((at, H, W, (0, 0, m * cols, m * rows)))
+            at += max(H, 0) * max(W, 0)
+        a, b = pkg.ResampleLaunch(), pkg.ResampleLaunch()
+        a.tiles = b.tiles = -5                               # a refused batch leaves the record alone
+        pa, wa = pkg.label_items(plain), pkg.label_window_items(window)
+        sort = (C.c_int64 * (2 * len(plain)))()
+        want = host.mbn_resample_ragged_check(rows, cols, classes, pa, len(plain), sort, C.byref(a))
+        got = host.mbn_resample_ragged_window_check(rows, cols, classes, m * rows, m * cols, wa, len(window), sort, C.byref(b))
+        seen.add(want)
+        assert got == want and _fields(a) == _fields(b), (rows, cols, classes, m, plain, got, want)
+        assert (a.tiles == -5) == (want != pkg.OK)
+    assert seen == {pkg.OK, pkg.EINVAL, pkg.EUNSUPPORTED}, seen
+
+
 # ------------------------------------------------------------------------------------------------------------------------ symbols
 
 DEVICE = ("mbn_resample_argmax_window_f32", "mbn_ragged_readout_set_window", "mbn_net_segment_fit", "mbn_net_segment_images_fit")
