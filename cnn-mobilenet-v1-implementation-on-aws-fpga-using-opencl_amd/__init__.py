@@ -100,6 +100,19 @@ class LabelWindowItem(C.Structure):
     _fields_ = [("dst_offset", C.c_int64)] + [(n, C.c_int32) for n in ("rows", "cols", "x", "y", "iw", "ih")]
 
 
+ENSEMBLE_MAX_VIEWS = 8
+
+
+class View(C.Structure):
+    """mbn_view (include/mbn.h): one presentation of an image to the network: the rectangle (x, y, iw, ih) of the network input that holds the whole
+    image, mirrored left-to-right when mirror = 1; 32 bytes, the reserved words 0"""
+    _fields_ = [(n, C.c_int32) for n in ("x", "y", "iw", "ih", "mirror")] + [("reserved", C.c_int32 * 3)]
+
+    @property
+    def rect(self):
+        return (self.x, self.y, self.iw, self.ih)
+
+
 class ResampleLaunch(C.Structure):
     """mbn_resample_launch_t (host/mbn_envelope.h): LDS footprint, class chunk, dynamic LDS, grid.x and output span of a read-out launch"""
     _fields_ = [(n, C.c_int32) for n in ("fy", "fx", "ch", "lds_bytes", "tiles")] + [("span", C.c_int64)]
@@ -193,6 +206,10 @@ def _declare_host(lib):
     lib.mbn_resample_window_envelope.argtypes = [C.c_int] * 6 + [C.POINTER(C.c_int32), C.c_int, C.c_int]
     lib.mbn_resample_window_plan.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(ResampleLaunch)]
     lib.mbn_resample_window_plan.restype = None
+    lib.mbn_fit_view.argtypes = [C.c_int] * 4 + [C.c_float, C.c_int, C.POINTER(View)]
+    lib.mbn_resample_ensemble_envelope.argtypes = [C.c_int] * 6 + [C.POINTER(View), C.c_int, C.c_int, C.c_int]      # mbn_envelope.h, like the next two
+    lib.mbn_resample_ensemble_plan.argtypes = [C.c_int] * 4 + [C.POINTER(View), C.c_int, C.c_int, C.c_int, C.POINTER(ResampleLaunch)]
+    lib.mbn_resize_view_table_plan_filter.argtypes = [C.c_int] * 5 + [C.POINTER(View), C.POINTER(ResizePadPlan)]
     lib.mbn_resample_ragged_window_check.argtypes = [C.c_int] * 5 + [C.POINTER(LabelWindowItem), C.c_int, C.POINTER(C.c_int64),
                                                                      C.POINTER(ResampleLaunch)]
     i32p = C.POINTER(C.c_int32)
@@ -344,6 +361,10 @@ def load():
         lib.mbn_net_segment_prob_images_fit.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, ci, vp,
                                                         C.POINTER(C.c_int64), vp, C.c_float, ci]
         lib.mbn_net_segment_images.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, vp, C.POINTER(C.c_int64), vp]
+        lib.mbn_resample_ensemble_f32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(View), ci, ci, ci, C.c_float, ci, vp]
+        lib.mbn_resizer_create_view.argtypes = [vp, ci, ci, ci, ci, ci, C.POINTER(View), C.POINTER(C.c_uint8), C.POINTER(vp)]
+        lib.mbn_net_resize_views.argtypes = [vp, vp, ci, ci, ci, C.POINTER(C.c_float), C.POINTER(C.c_int32), ci, C.POINTER(vp)]
+        lib.mbn_net_segment_views_fit.argtypes = [vp, vp, ci, ci, ci, C.POINTER(C.c_float), C.POINTER(C.c_int32), ci, vp, vp, vp, C.c_float, ci]
         lib.mbn_resizer_create.argtypes = [vp, ci, ci, C.POINTER(C.c_float), ci, ci, C.POINTER(vp)]
         lib.mbn_resize_u8.argtypes = [vp, vp, vp, ci, vp]
         lib.mbn_resizer_destroy.argtypes = [vp]
@@ -451,6 +472,43 @@ def fit_pad(in_rows, in_cols, out_rows, out_cols, lib=None):
     rect = (C.c_int32 * 4)()
     _chk((lib or host_lib()).mbn_fit_pad(in_rows, in_cols, out_rows, out_cols, rect), "fit_pad(%d, %d, %d, %d)" % (in_rows, in_cols, out_rows, out_cols))
     return tuple(rect[:])
+
+
+def fit_view(in_rows, in_cols, out_rows, out_cols, scale=1.0, mirror=0, lib=None) -> View:
+    """mbn_fit_view: the view of an in_rows x in_cols image at `scale` (0 < scale <= 1) in an out_rows x out_cols network input: fit_pad into the
+    canvas scaled about its centre; mirror 0 / 1 applies to the inner image alone."""
+    v = View()
+    _chk((lib or host_lib()).mbn_fit_view(in_rows, in_cols, out_rows, out_cols, scale, mirror, C.byref(v)),
+         "fit_view(%d, %d, %d, %d, %r, %r)" % (in_rows, in_cols, out_rows, out_cols, scale, mirror))
+    return v
+
+
+def views(items):
+    """A C array of mbn_view from View objects or (x, y, iw, ih, mirror) tuples."""
+    arr = (View * len(items))()
+    for dst, it in zip(arr, items):
+        if isinstance(it, View):
+            C.memmove(C.byref(dst), C.byref(it), C.sizeof(View))
+        else:
+            dst.x, dst.y, dst.iw, dst.ih, dst.mirror = (int(v) for v in it)
+    return arr
+
+
+def resample_ensemble_envelope(batch, rows, cols, classes, in_rows, in_cols, view_list, out_rows, out_cols, lib=None, n_views=None) -> int:
+    """mbn_resample_ensemble_envelope: the status mbn_resample_ensemble_f32 gives the shape and the views (n_views: the count handed over, for the
+    refusals; the list's length by default)."""
+    arr = view_list if isinstance(view_list, C.Array) else views(view_list)
+    return (lib or host_lib()).mbn_resample_ensemble_envelope(batch, rows, cols, classes, in_rows, in_cols, arr, len(arr) if n_views is None else n_views,
+                                                              out_rows, out_cols)
+
+
+def resample_ensemble_plan(rows, cols, in_rows, in_cols, view_list, out_rows, out_cols, lib=None) -> ResampleLaunch:
+    """mbn_resample_ensemble_plan: the launch of a set of views: the largest footprint over them, the class chunk that keeps all of them in 64 KB."""
+    arr = view_list if isinstance(view_list, C.Array) else views(view_list)
+    l = ResampleLaunch()
+    _chk((lib or host_lib()).mbn_resample_ensemble_plan(rows, cols, in_rows, in_cols, arr, len(arr), out_rows, out_cols, C.byref(l)),
+         "resample_ensemble_plan")
+    return l
 
 
 def _fill3(pad):
@@ -800,6 +858,16 @@ class Context:
         _chk(self.lib.mbn_resample_softmax_window_f32(self.h, labels, prob, score, logits, batch, rows, cols, classes, in_rows, in_cols, _rect(rect),
                                                       out_rows, out_cols, min_prob, ignore_label, None), self.last_error())
 
+    def resample_ensemble(self, labels, prob, score, logits, batch, rows, cols, classes, in_rows, in_cols, view_list, out_rows, out_cols,
+                          min_prob=0.0, ignore_label=0, n_views=None):
+        """mbn_resample_ensemble_f32: ONE read-out of the views in view_list (View objects or (x, y, iw, ih, mirror)) over view-major logits
+        [n_views][batch][rows][cols][classes]: the interpolated logits are averaged over the views in front of the argmax (and the softmax).
+        prob None with min_prob 0: the argmax form. `score` may be None."""
+        arr = view_list if isinstance(view_list, C.Array) else views(view_list)
+        _chk(self.lib.mbn_resample_ensemble_f32(self.h, labels, prob, score, logits, batch, rows, cols, classes, in_rows, in_cols, arr,
+                                                len(arr) if n_views is None else n_views, out_rows, out_cols, min_prob, ignore_label, None),
+             self.last_error())
+
     def __enter__(self):
         return self
 
@@ -852,14 +920,20 @@ class Resizer:
     """mbn_resizer_create_filter / mbn_resize_u8: uint8 HWC images [batch][in_rows][in_cols][3] -> [batch][out_rows][out_cols][3], Pillow's 8-bit
     resize of `box` = (left, upper, right, lower) (None = the whole image) under `filter` (FILTER_*, bilinear by default), byte for byte. One
     geometry and one filter per handle. pad = (R, G, B): the letterbox form (mbn_resizer_create_pad): the whole image with its aspect ratio kept,
-    centred on an out_rows x out_cols canvas of that colour (PIL.ImageOps.pad); no box then."""
+    centred on an out_rows x out_cols canvas of that colour (PIL.ImageOps.pad); no box then. view = a View (or (x, y, iw, ih, mirror)) with pad:
+    the rectangle given instead of derived, the inner image mirrored when the view says so (mbn_resizer_create_view)."""
 
-    def __init__(self, ctx: Context, in_rows, in_cols, out_rows, out_cols, box=None, filter=FILTER_BILINEAR, pad=None):
+    def __init__(self, ctx: Context, in_rows, in_cols, out_rows, out_cols, box=None, filter=FILTER_BILINEAR, pad=None, view=None):
         self.ctx = ctx
         self.filter = filter
         self.shape_in, self.shape_out = (in_rows, in_cols, 3), (out_rows, out_cols, 3)
         h = C.c_void_p()
-        if pad is not None:
+        if view is not None:
+            if box is not None:
+                raise ValueError("a view takes the whole image: no box")
+            _chk(ctx.lib.mbn_resizer_create_view(ctx.h, filter, in_rows, in_cols, out_rows, out_cols, views([view]),
+                                                 _fill3(pad if pad is not None else (0, 0, 0)), C.byref(h)), ctx.last_error())
+        elif pad is not None:
             if box is not None:
                 raise ValueError("a letterbox takes the whole image: no box")
             _chk(ctx.lib.mbn_resizer_create_pad(ctx.h, filter, in_rows, in_cols, out_rows, out_cols, _fill3(pad), C.byref(h)), ctx.last_error())
@@ -1085,6 +1159,26 @@ class Net:
                                                           (C.c_int32 * n)(*[int(v) for v in rows]), (C.c_int32 * n)(*[int(v) for v in cols]), n, fit,
                                                           labels_ptr, (C.c_int64 * n)(*[int(v) for v in dst_offsets]), prob_ptr, min_prob,
                                                           ignore_label), self.ctx.last_error())
+
+    def resize_views(self, src_ptr, batch, in_rows, in_cols, scales, mirrors) -> int:
+        """mbn_net_resize_views: uint8 sources [batch][in_rows][in_cols][3] -> the net's staging buffer, view-major: view k = fit_view(scales[k],
+        mirrors[k]) of every image at images k * batch .. (its device pointer is returned). batch * views <= max_batch."""
+        n = len(scales)
+        assert len(mirrors) == n
+        p = C.c_void_p()
+        _chk(self.ctx.lib.mbn_net_resize_views(self.h, src_ptr, batch, in_rows, in_cols, (C.c_float * n)(*[float(v) for v in scales]),
+                                               (C.c_int32 * n)(*[int(v) for v in mirrors]), n, C.byref(p)), self.ctx.last_error())
+        return p.value
+
+    def segment_views_fit(self, src_ptr, batch, in_rows, in_cols, scales, mirrors, labels_ptr, prob_ptr=None, score_ptr=None, min_prob=0.0,
+                          ignore_label=0):
+        """mbn_net_segment_views_fit: test-time augmentation through the letterbox: resize_views, ONE forward_dense of batch * views images and ONE
+        ensemble read-out (Context.resample_ensemble) to the source size: labels, prob and score [batch][in_rows][in_cols]. Needs set_input_u8()."""
+        n = len(scales)
+        assert len(mirrors) == n
+        _chk(self.ctx.lib.mbn_net_segment_views_fit(self.h, src_ptr, batch, in_rows, in_cols, (C.c_float * n)(*[float(v) for v in scales]),
+                                                    (C.c_int32 * n)(*[int(v) for v in mirrors]), n, labels_ptr, prob_ptr, score_ptr, min_prob,
+                                                    ignore_label), self.ctx.last_error())
 
     def resize_input(self, src_ptr, batch, in_rows, in_cols, fit=FIT_CROP, crop_fraction=1.0) -> int:
         """mbn_net_resize_input: uint8 images [batch][in_rows][in_cols][3] of any size -> the net's staging buffer [batch][rows][cols][3] (its

@@ -893,6 +893,22 @@ int mbn_resample_softmax_window_f32(mbn_context *ctx, void *labels_i32, void *pr
     return resample_uniform(ctx, labels_i32, score_f32, logits, batch, rows, cols, classes, true, in_rows, in_cols, rect, out_rows, out_cols, stream, &q);
 }
 
+int mbn_resample_ensemble_f32(mbn_context *ctx, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, int batch, int rows, int cols,
+                              int classes, int in_rows, int in_cols, const mbn_view *views, int n_views, int out_rows, int out_cols, float min_prob,
+                              int ignore_label, void *stream)
+{
+    if (!views || n_views < 1 || n_views > MBN_ENSEMBLE_MAX_VIEWS) return MBN_EINVAL;
+    // no prob map and no threshold: the argmax form (a NaN threshold is not 0: the softmax check refuses it)
+    const mbn_readout_prob prob = { (float *)prob_f32, min_prob, ignore_label };
+    const mbn_readout_prob *q = prob_f32 || !(min_prob == 0.0f) ? &prob : nullptr;
+    const int shape = mbn_resample_ensemble_envelope(batch, rows, cols, classes, in_rows, in_cols, views, n_views, out_rows, out_cols);
+    return readout_call(ctx, labels_i32, score_f32, logits, q, shape, 4.0 * n_views * batch * rows * cols * classes, 4.0 * batch * out_rows * out_cols,
+                        stream, [&](hipStream_t s) {
+                            return mbn_launch_f32_resample_ensemble(ctx, s, (int32_t *)labels_i32, (float *)score_f32, (const float *)logits, batch,
+                                                                    rows, cols, classes, in_rows, in_cols, views, n_views, out_rows, out_cols, q);
+                        });
+}
+
 int mbn_ragged_readout_create(mbn_context *ctx, int max_batch, mbn_ragged_readout **r)
 {
     if (!ctx || !r) return MBN_EINVAL;
@@ -966,7 +982,7 @@ int mbn_resizer_create_filter(mbn_context *ctx, int filter, int in_rows, int in_
     *r = nullptr;
     int rc = mbn_resize_envelope_filter(filter, in_rows, in_cols, box, out_rows, out_cols);
     if (rc != MBN_OK) return rc;
-    rc = mbn_resizer_build(ctx, filter, in_rows, in_cols, box, out_rows, out_cols, r);
+    rc = mbn_resizer_build(ctx, filter, in_rows, in_cols, box, out_rows, out_cols, false, r);
     if (rc != MBN_OK) return rc;
     std::lock_guard<std::mutex> lk(ctx->mu);
     ctx->resizers.push_back(*r);
@@ -984,6 +1000,19 @@ int mbn_resizer_create_pad(mbn_context *ctx, int filter, int in_rows, int in_col
     *r = nullptr;
     if (!fill) return MBN_EINVAL;
     const int rc = mbn_resizer_build_pad(ctx, filter, in_rows, in_cols, out_rows, out_cols, fill, r);      // the plan answers for the geometry
+    if (rc != MBN_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->resizers.push_back(*r);
+    return MBN_OK;
+}
+
+int mbn_resizer_create_view(mbn_context *ctx, int filter, int in_rows, int in_cols, int out_rows, int out_cols, const mbn_view *view,
+                            const uint8_t fill[3], mbn_resizer **r)
+{
+    if (!ctx || !r) return MBN_EINVAL;
+    *r = nullptr;
+    if (!view || !fill) return MBN_EINVAL;
+    const int rc = mbn_resizer_build_view(ctx, filter, in_rows, in_cols, out_rows, out_cols, view, fill, r);       // the plan answers for the geometry
     if (rc != MBN_OK) return rc;
     std::lock_guard<std::mutex> lk(ctx->mu);
     ctx->resizers.push_back(*r);

@@ -39,6 +39,8 @@
 // about 7 issue slots here (subtract, max, multiply, add, v_exp_f32 at two slots, and a quarter of the group's three maxima, subtract and
 // compare). prob = exp(best - ref) / sum at the end, 0 when best is not finite. A NaN v (the padding classes of the dword path among them) is
 // dropped by the maxima, and its difference is replaced by -200 by a max that drops the NaN: it adds exp(-200) = 0, exactly.
+// ENSEMBLE (mbn_resample_ensemble_f32; include/mbn.h, "segment with test-time augmentation"): K views read out as one map, kernels of their own on
+// the same tile, stage pass, lerps, softmax sum and store; described where they stand, behind rs_launch.
 #include "mbn_internal.h"
 #include "mbn_device.h"
 
@@ -122,6 +124,23 @@ __device__ __forceinline__ void rs_coord(int o, int n, int N, const RsWindow &w,
 // the bound against a sum of at least 1).
 __device__ __forceinline__ float rs_exp(float d) { return __builtin_amdgcn_exp2f(d * 1.44269504088896341f); }
 
+// The lazy-reference softmax sum (the file's head) of a lane's four rows over one group of four classes, vv[r][k] = row r's v of the group's class k:
+// the ensemble kernels' copy of what rs_reduce does in place. rs_reduce keeps its own text because the sixteen kernels built from it are pinned to
+// the registers they had before the ensemble existed, and calling this from there moved the softmax ones from 102 to 98 VGPRs
+__device__ __forceinline__ void rs_softmax_group(const float (&vv)[RS_ROWS][4], float (&ref)[RS_ROWS], float (&sum)[RS_ROWS])
+{
+#pragma clang fp contract(off)                      // the same operations in every instantiation: a pixel's prob does not depend on the kernel
+#pragma unroll
+    for (int r = 0; r < RS_ROWS; r++) {
+        // the reference moves at most once per four classes, to their maximum m (the maxima drop NaNs; an all-NaN m fails the compare, and
+        // so does -inf - -inf): everything seen so far is then at most RS_MARGIN above ref, the four included
+        const float m = __builtin_fmaxf(__builtin_fmaxf(vv[r][0], vv[r][1]), __builtin_fmaxf(vv[r][2], vv[r][3]));
+        if (m - ref[r] > RS_MARGIN) { sum[r] *= rs_exp(ref[r] - m); ref[r] = m; }
+#pragma unroll
+        for (int k = 0; k < 4; k++) sum[r] += rs_exp(__builtin_fmaxf(vv[r][k] - ref[r], -200.0f));     // a NaN difference adds exp(-200) = 0
+    }
+}
+
 // The reduce pass of one staged chunk of cn4 classes for a lane's four rows. CROSS: some row of the wave interpolates between (ya + 1, ya + 2), so
 // the third interpolant and the per-row selects are needed; otherwise every row of the wave uses (t0, t1) and neither is formed. The same products
 // and sums in the same order either way. PROB: each row's lazy reference and softmax sum follow v (the file's head); untouched otherwise.
@@ -164,6 +183,51 @@ __device__ __forceinline__ void rs_reduce(const float *(&p)[3][2], int cn4, int 
                 for (int k = 0; k < 4; k++) sum[r] += rs_exp(__builtin_fmaxf(vv[r][k] - ref[r], -200.0f));     // a NaN difference adds exp(-200) = 0
             }
         }
+    }
+}
+
+// The stage pass of one class chunk (classes c0 .. c0 + cn - 1, cn4 = cn rounded up to 4): the nv = fy x fx vectors of one image's map, from
+// (ybase, xbase) on and clamped to the map, go to s_x, ld floats apart. VEC: 16-byte loads; else dword loads, the classes past cn staged as NaN
+template <bool VEC>
+__device__ __forceinline__ void rs_stage(float *s_x, const float *__restrict__ src, int ybase, int xbase, int fx, int nv, int ld, int cols, int classes,
+                                         int last_y, int last_x, int c0, int cn, int cn4, int tid)
+{
+    if (VEC) {
+        const int q = cn4 >> 2;                  // classes % 4 == 0: cn4 == cn
+        for (int e = tid; e < nv * q; e += 256) {
+            const int v = e / q, c = (e - v * q) << 2;
+            const int ry = min(ybase + v / fx, last_y), rx = min(xbase + v % fx, last_x);
+            *reinterpret_cast<f4 *>(s_x + v * ld + c) = *reinterpret_cast<const f4 *>(src + (unsigned)((ry * cols + rx) * classes + c0 + c));
+        }
+    } else {
+        const float nan = __builtin_nanf("");
+        for (int e = tid; e < nv * cn4; e += 256) {
+            const int v = e / cn4, c = e - v * cn4;
+            const int ry = min(ybase + v / fx, last_y), rx = min(xbase + v % fx, last_x);
+            s_x[v * ld + c] = c < cn ? src[(unsigned)((ry * cols + rx) * classes + c0 + c)] : nan;
+        }
+    }
+}
+
+// What an active lane stores for its column ox and rows oy0 .. oy0 + 3 (those inside the H x W map): the label, the score (may be null) and, PROB,
+// the probability (may be null) with the threshold on the value stored
+template <bool PROB>
+__device__ __forceinline__ void rs_store(int *__restrict__ labels, float *__restrict__ score, float *__restrict__ prob, int H, int W, int oy0, int ox,
+                                         const float (&best)[RS_ROWS], int (&label)[RS_ROWS], const float (&ref)[RS_ROWS],
+                                         const float (&sum)[RS_ROWS], float min_prob, int ignore_label)
+{
+    const unsigned out = (unsigned)(oy0 * W + ox);        // 32-bit inside an image: its map is below 2^31 bytes
+#pragma unroll
+    for (int r = 0; r < RS_ROWS; r++) {
+        if (oy0 + r >= H) break;
+        if (PROB) {
+            // a finite best has a finite ref <= best <= ref + RS_MARGIN and a sum >= 1 that holds best's own term: 0 < pr <= 1
+            const float pr = __builtin_fabsf(best[r]) < __builtin_inff() ? rs_exp(best[r] - ref[r]) / sum[r] : 0.0f;
+            if (pr < min_prob) label[r] = ignore_label;                                     // strict, on the value stored below
+            if (prob) prob[out + (unsigned)(r * W)] = pr;
+        }
+        labels[out + (unsigned)(r * W)] = label[r];
+        if (score) score[out + (unsigned)(r * W)] = best[r];
     }
 }
 
@@ -217,25 +281,11 @@ __device__ __forceinline__ void resample_tile(const ResampleArgs &a, const float
     int label[RS_ROWS];
 #pragma unroll
     for (int r = 0; r < RS_ROWS; r++) { best[r] = ref[r] = -__builtin_inff(); sum[r] = 0.0f; label[r] = 0; }
-    const float nan = __builtin_nanf("");
 
     for (int c0 = 0; c0 < a.classes; c0 += a.ch) {
         const int cn = min(a.ch, a.classes - c0), cn4 = (cn + 3) & ~3;
         // ---- stage: nv vectors x cn4 classes
-        if (VEC) {
-            const int q = cn4 >> 2;                  // classes % 4 == 0: cn4 == cn
-            for (int e = tid; e < nv * q; e += 256) {
-                const int v = e / q, c = (e - v * q) << 2;
-                const int ry = min(ybase + v / a.fx, last_y), rx = min(xbase + v % a.fx, last_x);
-                *reinterpret_cast<f4 *>(s_x + v * ld + c) = *reinterpret_cast<const f4 *>(src + (unsigned)((ry * a.cols + rx) * a.classes + c0 + c));
-            }
-        } else {
-            for (int e = tid; e < nv * cn4; e += 256) {
-                const int v = e / cn4, c = e - v * cn4;
-                const int ry = min(ybase + v / a.fx, last_y), rx = min(xbase + v % a.fx, last_x);
-                s_x[v * ld + c] = c < cn ? src[(unsigned)((ry * a.cols + rx) * a.classes + c0 + c)] : nan;
-            }
-        }
+        rs_stage<VEC>(s_x, src, ybase, xbase, a.fx, nv, ld, a.cols, a.classes, last_y, last_x, c0, cn, cn4, tid);
         __syncthreads();
         // ---- reduce
         if (active) {
@@ -245,19 +295,7 @@ __device__ __forceinline__ void resample_tile(const ResampleArgs &a, const float
         __syncthreads();
     }
     if (!active) return;
-    const unsigned out = (unsigned)(oy0 * W + ox);        // 32-bit inside an image: its map is below 2^31 bytes
-#pragma unroll
-    for (int r = 0; r < RS_ROWS; r++) {
-        if (oy0 + r >= H) break;
-        if (PROB) {
-            // a finite best has a finite ref <= best <= ref + RS_MARGIN and a sum >= 1 that holds best's own term: 0 < pr <= 1
-            const float pr = __builtin_fabsf(best[r]) < __builtin_inff() ? rs_exp(best[r] - ref[r]) / sum[r] : 0.0f;
-            if (pr < a.min_prob) label[r] = a.ignore_label;                                 // strict, on the value stored below
-            if (prob) prob[out + (unsigned)(r * W)] = pr;
-        }
-        labels[out + (unsigned)(r * W)] = label[r];
-        if (score) score[out + (unsigned)(r * W)] = best[r];
-    }
+    rs_store<PROB>(labels, score, prob, H, W, oy0, ox, best, label, ref, sum, a.min_prob, a.ignore_label);
 }
 
 template <bool VEC, bool WIN, bool PROB>
@@ -359,7 +397,185 @@ void rs_launch(bool ragged, bool prob, bool win, int batch, const mbn_resample_l
     hipLaunchKernelGGL(rs_kernels[ragged][prob][win][vec], dim3((unsigned)l.tiles, (unsigned)batch), dim3(256), (size_t)l.lds_bytes, s, a);
 }
 
+// ---- ENSEMBLE (mbn_resample_ensemble_f32; include/mbn.h, "segment with test-time augmentation"): K views of the same images, each a window of the
+// network's input and possibly mirrored, are read out as ONE map: per class and pixel the K interpolants are summed in view order, the sum is scaled
+// by 1 / K, and the compare (and the softmax sum) sees that mean. The tile is resample_tile's: 32 x 32 outputs per workgroup, a lane one column and
+// four rows, the same index / weight rule (rs_coord<true>), the same lerps, the same lazy-reference sum, the same store. What differs:
+//   stage   per class chunk ALL K footprints go to LDS, view k's fy x fx vectors at k * fy * fx, each from its own (ybase, xbase): the rectangles
+//           differ, so the views' footprints lie elsewhere in the map. The chunk is smaller for it (host/mbn_envelope.h, MBN_RESAMPLE_ENSEMBLE_CH)
+//   reduce  per group of four classes the views are visited in order and the four rows' sums stay in registers; the compare runs once per class
+//           on the mean. A view takes the two-interpolant form when none of the wave's rows crosses a coarse row IN THAT VIEW (a ballot per view)
+//   mirror  a mirrored view evaluates its columns at W - 1 - ox: the lane's column of that view, and the tile's xbase from its LAST column
+// A lane's per-view state (LDS offsets, weights, up bits) is indexed at compile time only: K is a template parameter and every loop over the views
+// is unrolled, so the state stays in registers (a runtime index would send it to scratch). The views travel by value in the kernel's arguments.
+struct EnsembleArgs {
+    int *labels;
+    float *score, *prob;     // either may be null (prob: PROB instantiations only)
+    const float *logits;     // [K][batch][rows][cols][classes]
+    int rows, cols, classes, batch;
+    int out_rows, out_cols, tiles_x;
+    int fy, fx, ch;          // the launch's footprint PER VIEW and the class chunk: mbn_resample_ensemble_plan
+    int in_rows, in_cols;
+    float inv_k, min_prob;   // 1.0f / (float)K
+    int ignore_label;
+    mbn_view views[MBN_ENSEMBLE_MAX_VIEWS];
+};
+static_assert(sizeof(mbn_view) == 32, "a view is 32 bytes: eight of them travel in the kernel's arguments");
+
+// a lane's state for one view
+struct EnsView {
+    int off[3][2];           // LDS word offsets of the six vectors, as resample_tile's p
+    float wx1, wy1[RS_ROWS]; // the weights of i1; those of i0 are formed where they are used (1.0f - w1: the same value every time)
+    unsigned up;             // bit r: row r interpolates between (ya + 1, ya + 2); one register per view instead of four lane masks
+    bool cross;              // some row of the wave has a bit set in this view
+};
+
+// adds one view's interpolants of the four classes at c to the lane's sums (first: they ARE the sums); rs_reduce's products and sums
+template <bool CROSS>
+__device__ __forceinline__ void ens_add(const float *s_x, const EnsView &e, int c, bool first, float (&s)[RS_ROWS][4])
+{
+#pragma clang fp contract(off)
+    constexpr int NT = CROSS ? 3 : 2;
+    const float wx0 = 1.0f - e.wx1;
+    f4 v0[NT], v1[NT];
+#pragma unroll
+    for (int j = 0; j < NT; j++) {
+        v0[j] = *reinterpret_cast<const f4 *>(s_x + e.off[j][0] + c);
+        v1[j] = *reinterpret_cast<const f4 *>(s_x + e.off[j][1] + c);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        float t[NT];
+#pragma unroll
+        for (int j = 0; j < NT; j++) t[j] = rs_lerp(v0[j][k], wx0, v1[j][k], e.wx1);            // horizontal first
+#pragma unroll
+        for (int r = 0; r < RS_ROWS; r++) {
+            const bool up = CROSS && (e.up >> r & 1u);
+            const float ta = up ? t[1] : t[0], tb = up ? t[NT - 1] : t[1];
+            const float v = rs_lerp(ta, 1.0f - e.wy1[r], tb, e.wy1[r]);                         // then vertical
+            s[r][k] = first ? v : s[r][k] + v;                                                  // view order, one rounding per view
+        }
+    }
+}
+
+template <int K, bool VEC, bool PROB>
+__global__ __launch_bounds__(256) void resample_ensemble_f32(const EnsembleArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_rs[];
+    const int tid = threadIdx.x;
+    const int ty = (int)blockIdx.x / a.tiles_x, tx = (int)blockIdx.x - ty * a.tiles_x;
+    const size_t img = (size_t)blockIdx.y;                                                      // 64-bit bases, 32-bit offsets inside a map
+    const size_t map = (size_t)a.out_rows * a.out_cols, lmap = (size_t)a.rows * a.cols * a.classes;
+    const int H = a.out_rows, W = a.out_cols;
+    const int ld = a.ch + 4, nv = a.fy * a.fx;
+    const int last_y = a.rows - 1, last_x = a.cols - 1;
+    const int ox = RS_TILE * tx + (tid & 31), oy0 = RS_TILE * ty + RS_ROWS * (tid >> 5);
+    const bool active = ox < W && oy0 < H;
+    const int oxc = min(ox, W - 1), xe = min(RS_TILE * tx + RS_TILE - 1, W - 1);                // this lane's column, the tile's last one
+
+    EnsView e[K];
+    int ybase[K], xbase[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const mbn_view &vw = a.views[k];
+        const RsWindow wy = { a.in_rows, vw.y, vw.ih }, wx = { a.in_cols, vw.x, vw.iw };
+        const bool mirror = vw.mirror != 0;
+        float unused;
+        rs_coord<true>(RS_TILE * ty, a.rows, H, wy, &ybase[k], &unused);
+        // i0 grows with the coordinate: the tile's leftmost source column belongs to its first output, mirrored to its last one
+        rs_coord<true>(mirror ? W - 1 - xe : RS_TILE * tx, a.cols, W, wx, &xbase[k], &unused);
+        int x0, ya = 0;
+        rs_coord<true>(mirror ? W - 1 - oxc : oxc, a.cols, W, wx, &x0, &e[k].wx1);
+        e[k].up = 0;
+#pragma unroll
+        for (int r = 0; r < RS_ROWS; r++) {
+            int r0;
+            rs_coord<true>(min(oy0 + r, H - 1), a.rows, H, wy, &r0, &e[k].wy1[r]);
+            if (r == 0) ya = r0;
+            e[k].up |= (unsigned)(r0 != ya) << r; // r0 is ya or ya + 1: four rows span less than one coarse row
+        }
+        e[k].cross = __ballot(e[k].up != 0) != 0;
+        // inside view k's staged block by construction; the clamps keep every read inside the launch's LDS whatever the arguments
+        const int sx0 = min(max(x0 - xbase[k], 0), a.fx - 1), sx1 = min(max(min(x0 + 1, last_x) - xbase[k], 0), a.fx - 1);
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const int sy = min(max(min(ya + j, last_y) - ybase[k], 0), a.fy - 1);
+            e[k].off[j][0] = (k * nv + sy * a.fx + sx0) * ld;
+            e[k].off[j][1] = (k * nv + sy * a.fx + sx1) * ld;
+        }
+    }
+
+    float best[RS_ROWS], ref[RS_ROWS], sum[RS_ROWS];
+    int label[RS_ROWS];
+#pragma unroll
+    for (int r = 0; r < RS_ROWS; r++) { best[r] = ref[r] = -__builtin_inff(); sum[r] = 0.0f; label[r] = 0; }
+
+    for (int c0 = 0; c0 < a.classes; c0 += a.ch) {
+        const int cn = min(a.ch, a.classes - c0), cn4 = (cn + 3) & ~3;
+#pragma unroll
+        for (int k = 0; k < K; k++)
+            rs_stage<VEC>(s_rs + k * nv * ld, a.logits + ((size_t)k * a.batch + img) * lmap, ybase[k], xbase[k], a.fx, nv, ld, a.cols, a.classes, last_y,
+                          last_x, c0, cn, cn4, tid);
+        __syncthreads();
+        if (active) {
+            for (int c = 0; c < cn4; c += 4) {
+                float s[RS_ROWS][4] = {}, vv[RS_ROWS][4];
+#pragma unroll
+                for (int k = 0; k < K; k++) {
+                    if (e[k].cross) ens_add<true>(s_rs, e[k], c, k == 0, s);
+                    else ens_add<false>(s_rs, e[k], c, k == 0, s);
+                }
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+#pragma unroll
+                    for (int r = 0; r < RS_ROWS; r++) {
+#pragma clang fp contract(off)
+                        const float t = s[r][k] * a.inv_k;                                      // the mean: one rounding
+                        if (t > best[r]) { best[r] = t; label[r] = c0 + c + k; }
+                        vv[r][k] = t;
+                    }
+                }
+                if (PROB) rs_softmax_group(vv, ref, sum);
+            }
+        }
+        __syncthreads();
+    }
+    if (!active) return;
+    rs_store<PROB>(a.labels + img * map, a.score ? a.score + img * map : nullptr, PROB && a.prob ? a.prob + img * map : nullptr, H, W, oy0, ox, best,
+                   label, ref, sum, a.min_prob, a.ignore_label);
+}
+
+// the thirty-two ensemble kernels by [K - 1][prob][vec]
+typedef void (*EnsKernel)(const EnsembleArgs);
+#define ENS_K(K) { { resample_ensemble_f32<K, false, false>, resample_ensemble_f32<K, true, false> },   \
+                   { resample_ensemble_f32<K, false, true>, resample_ensemble_f32<K, true, true> } }
+const EnsKernel ens_kernels[MBN_ENSEMBLE_MAX_VIEWS][2][2] = { ENS_K(1), ENS_K(2), ENS_K(3), ENS_K(4), ENS_K(5), ENS_K(6), ENS_K(7), ENS_K(8) };
+#undef ENS_K
+
 }   // namespace
+
+// The views are inside mbn_resample_ensemble_envelope and the pointers are non-null multiples of 4 (the caller has checked both)
+int mbn_launch_f32_resample_ensemble(mbn_context *, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows, int cols,
+                                     int classes, int in_rows, int in_cols, const mbn_view *views, int n_views, int out_rows, int out_cols,
+                                     const mbn_readout_prob *q)
+{
+    mbn_resample_launch_t l;
+    const int rc = mbn_resample_ensemble_plan(rows, cols, in_rows, in_cols, views, n_views, out_rows, out_cols, &l);
+    if (rc != MBN_OK) return rc;
+    EnsembleArgs a = {};
+    a.labels = labels; a.score = score; a.logits = logits;
+    a.rows = rows; a.cols = cols; a.classes = classes; a.batch = batch;
+    a.out_rows = out_rows; a.out_cols = out_cols;
+    a.tiles_x = (out_cols + RS_TILE - 1) / RS_TILE;
+    a.fy = l.fy; a.fx = l.fx; a.ch = l.ch;
+    a.in_rows = in_rows; a.in_cols = in_cols;
+    a.inv_k = 1.0f / (float)n_views;
+    if (q) { a.prob = q->prob; a.min_prob = q->min_prob; a.ignore_label = q->ignore_label; }
+    for (int k = 0; k < n_views; k++) a.views[k] = views[k];
+    const bool vec = ((uintptr_t)logits % 16) == 0 && (classes % 4) == 0;
+    hipLaunchKernelGGL(ens_kernels[n_views - 1][q != nullptr][vec], dim3((unsigned)l.tiles, (unsigned)batch), dim3(256), (size_t)l.lds_bytes, s, a);
+    return MBN_OK;
+}
 
 // rect = (x, y, iw, ih) of the in_rows x in_cols network input: the window kernels; null: the whole map, the plain kernels (in_rows, in_cols are not
 // read). The shape is inside mbn_resample_window_envelope, without a rect mbn_resample_argmax_envelope, and the pointers are non-null multiples of 4

@@ -32,6 +32,7 @@ struct mbn_resizer {
     // at (pad_x, pad_y) of this canvas and `fill` is everywhere else (fill_rows, fill_wgs: mbn_resize_pad_plan_t)
     int canvas_rows = 0, canvas_cols = 0;
     bool pad = false;
+    bool mirror = false;                         // mbn_resizer_create_view, mirror = 1: inner column o holds the resize's column out_cols - 1 - o
     int pad_x = 0, pad_y = 0, fill_rows = 0, fill_wgs = 0;
     uint8_t fill[3] = { 0, 0, 0 };
 };
@@ -288,9 +289,16 @@ int mbn_ragged_readout_plan(mbn_ragged_readout *r, hipStream_t s, int rows, int 
                             const void *items, int batch);
 int mbn_launch_f32_resample_argmax_ragged(mbn_ragged_readout *r, hipStream_t s, int32_t *labels, float *score, const float *logits,
                                           const mbn_readout_prob *q);
-// resize front-end (mbn_u8_resize.hip): the geometry is inside mbn_resize_envelope; build uploads the tables (blocking), release frees them
-int mbn_resizer_build(mbn_context *ctx, int filter, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r);
+// the ensemble read-out of n_views views (logits [n_views][batch][rows][cols][classes]) inside mbn_resample_ensemble_envelope; q as above
+int mbn_launch_f32_resample_ensemble(mbn_context *ctx, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows, int cols,
+                                     int classes, int in_rows, int in_cols, const mbn_view *views, int n_views, int out_rows, int out_cols,
+                                     const mbn_readout_prob *q);
+// resize front-end (mbn_u8_resize.hip): the geometry is inside mbn_resize_envelope; build uploads the tables (blocking), release frees them.
+// mirror: the outputs' columns in reverse order (a view's inner image). build_view: the rectangle given (view and fill are non-null)
+int mbn_resizer_build(mbn_context *ctx, int filter, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, bool mirror, mbn_resizer **r);
 int mbn_resizer_build_pad(mbn_context *ctx, int filter, int in_rows, int in_cols, int out_rows, int out_cols, const uint8_t fill[3], mbn_resizer **r);
+int mbn_resizer_build_view(mbn_context *ctx, int filter, int in_rows, int in_cols, int out_rows, int out_cols, const mbn_view *view, const uint8_t fill[3],
+                           mbn_resizer **r);
 void mbn_resizer_release(mbn_resizer *r);
 int mbn_launch_u8_resize(const mbn_resizer *r, hipStream_t s, uint8_t *out, const uint8_t *in, int batch);
 // ragged resize (mbn_u8_resize_ragged.hip): build allocates, plan checks and plans a batch and enqueues the descriptors' upload (waits for the handle's

@@ -8,6 +8,7 @@
 // weights stay in memory, where a wave reads its output row's as scalars. Nothing here clamps: axis_ok has checked at create time what the bounds rest on.
 #include "mbn_u8_resize.h"
 
+#include <algorithm>
 #include <new>
 
 namespace {
@@ -44,7 +45,10 @@ struct ResizeArgs {
     ResizeDest d;
 };
 
-template <bool PAD>
+// MIRROR (mbn_resizer_create_view with mirror = 1; PAD only): the inner image is the resize's, its columns in reverse order. A tile still resizes
+// the columns [ox0, ox0 + oxn) of the tables, with the same window and the same plan; it forms them from right to left (its weights are copied to LDS
+// in reverse column order and a lane's element takes the mirrored column's first tap) and lands at the mirrored place, column ow - ox0 - oxn
+template <bool PAD, bool MIRROR = false>
 __global__ __launch_bounds__(256, 8) void resize_u8(const ResizeArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_mem[];
@@ -66,16 +70,23 @@ __global__ __launch_bounds__(256, 8) void resize_u8(const ResizeArgs a)
     uint8_t *s_tmp = s_mem + a.tmp_off;
     const int tmp_ld = a.tow * 3;
 
-    for (int e = tid; e < oxn * a.kx; e += 256) s_wx[e] = a.wx[ox0 * a.kx + e];
+    if constexpr (MIRROR) {
+        for (int e = tid; e < oxn * a.kx; e += 256) {
+            const int ox = e / a.kx;
+            s_wx[e] = a.wx[(ox0 + oxn - 1 - ox) * a.kx + (e - ox * a.kx)];
+        }
+    } else {
+        for (int e = tid; e < oxn * a.kx; e += 256) s_wx[e] = a.wx[ox0 * a.kx + e];
+    }
     int lo[RESIZE_EPL], wofs[RESIZE_EPL];
-    resize_lane_elems(lo, wofs, lane, row_e, a.kx, [&](int ox) { return a.fx[ox0 + ox] - xs0; });
+    resize_lane_elems(lo, wofs, lane, row_e, a.kx, [&](int ox) { return a.fx[ox0 + (MIRROR ? oxn - 1 - ox : ox)] - xs0; });
     __syncthreads();                                             // the weights are in place
     for (int r = wave; r < nrows; r += MBN_RESIZE_WAVES) {
         const uint8_t *s_seg = resize_stage_row(s_row, src + ((size_t)(y0 + r) * a.w + xs0) * 3, nb, lane);
         resize_row_sums(s_tmp + r * tmp_ld, s_seg, s_wx, lo, wofs, a.kx, row_e, lane);
     }
     __syncthreads();                                             // the window is complete
-    resize_vertical(dst + (size_t)oy0 * a.d.out_ld + ox0 * 3, (size_t)a.d.out_ld, s_tmp, tmp_ld, oyn, row_e, lane, wave, [&](int oy, int &f, int &n) {
+    resize_vertical(dst + (size_t)oy0 * a.d.out_ld + (MIRROR ? a.ow - ox0 - oxn : ox0) * 3, (size_t)a.d.out_ld, s_tmp, tmp_ld, oyn, row_e, lane, wave, [&](int oy, int &f, int &n) {
         f = a.fy[oy0 + oy] - y0;
         n = a.cy[oy0 + oy];
         return a.wy + (size_t)(oy0 + oy) * a.ky;
@@ -126,7 +137,8 @@ bool axis_ok(const int32_t *first, const int32_t *count, int out_size, int in_si
 }   // namespace
 
 // The geometry is inside mbn_resize_envelope (the caller has checked it). Plans the tile, builds the tables and uploads them: blocking.
-int mbn_resizer_build(mbn_context *ctx, int filter, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **out)
+int mbn_resizer_build(mbn_context *ctx, int filter, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, bool mirror,
+                      mbn_resizer **out)
 {
     const float whole[4] = { 0.0f, 0.0f, (float)in_cols, (float)in_rows };
     const float *b = box ? box : whole;
@@ -145,6 +157,7 @@ int mbn_resizer_build(mbn_context *ctx, int filter, int in_rows, int in_cols, co
         if (rc == MBN_OK) rc = mbn_resize_nearest_index(in_rows, b[1], b[3], out_rows, iy);
         if (rc != MBN_OK) return rc;
         if (!index_ok(ix, out_cols, in_cols) || !index_ok(iy, out_rows, in_rows)) return MBN_EINVAL;
+        if (mirror) std::reverse(ix, ix + out_cols);         // a gather: the mirror is the column indices in reverse order (the kernel asks them no order)
     } else {
         int32_t *fx = tab.data(), *cx = fx + out_cols, *fy = cx + out_cols, *cy = fy + out_rows, *wx = cy + out_rows, *wy = wx + (size_t)out_cols * p.kx;
         rc = mbn_resize_taps_filter(filter, in_cols, b[0], b[2], out_cols, fx, cx, wx);
@@ -157,6 +170,7 @@ int mbn_resizer_build(mbn_context *ctx, int filter, int in_rows, int in_cols, co
     if (!r) return MBN_ENOMEM;
     r->ctx = ctx;
     r->filter = filter;
+    r->mirror = mirror;
     r->in_rows = in_rows; r->in_cols = in_cols; r->out_rows = out_rows; r->out_cols = out_cols;
     r->canvas_rows = out_rows; r->canvas_cols = out_cols;
     r->plan = p;
@@ -172,13 +186,11 @@ int mbn_resizer_build(mbn_context *ctx, int filter, int in_rows, int in_cols, co
     return MBN_OK;
 }
 
-// The letterbox: the handle of the whole image -> ih x iw, and where that lies in the out_rows x out_cols canvas. fill is non-null (the caller has checked)
-int mbn_resizer_build_pad(mbn_context *ctx, int filter, int in_rows, int in_cols, int out_rows, int out_cols, const uint8_t fill[3], mbn_resizer **out)
+// The handle of the whole image -> pp.ih x pp.iw (mirrored or not), and where that lies in the out_rows x out_cols canvas
+static int build_in_canvas(mbn_context *ctx, int filter, int in_rows, int in_cols, int out_rows, int out_cols, const mbn_resize_pad_plan_t &pp, bool mirror,
+                           const uint8_t fill[3], mbn_resizer **out)
 {
-    mbn_resize_pad_plan_t pp;
-    int rc = mbn_resize_pad_table_plan_filter(filter, in_rows, in_cols, out_rows, out_cols, &pp);
-    if (rc != MBN_OK) return rc;
-    rc = mbn_resizer_build(ctx, filter, in_rows, in_cols, nullptr, pp.ih, pp.iw, out);
+    const int rc = mbn_resizer_build(ctx, filter, in_rows, in_cols, nullptr, pp.ih, pp.iw, mirror, out);
     if (rc != MBN_OK) return rc;
     mbn_resizer *r = *out;
     r->canvas_rows = out_rows; r->canvas_cols = out_cols;
@@ -186,6 +198,25 @@ int mbn_resizer_build_pad(mbn_context *ctx, int filter, int in_rows, int in_cols
     r->pad_x = pp.x; r->pad_y = pp.y; r->fill_rows = pp.fill_rows; r->fill_wgs = pp.fill_wgs;
     memcpy(r->fill, fill, 3);
     return MBN_OK;
+}
+
+// The letterbox: the rectangle is mbn_fit_pad's. fill is non-null (the caller has checked)
+int mbn_resizer_build_pad(mbn_context *ctx, int filter, int in_rows, int in_cols, int out_rows, int out_cols, const uint8_t fill[3], mbn_resizer **out)
+{
+    mbn_resize_pad_plan_t pp;
+    const int rc = mbn_resize_pad_table_plan_filter(filter, in_rows, in_cols, out_rows, out_cols, &pp);
+    if (rc != MBN_OK) return rc;
+    return build_in_canvas(ctx, filter, in_rows, in_cols, out_rows, out_cols, pp, false, fill, out);
+}
+
+// A view: the rectangle is the caller's, the inner image mirrored when the view says so. view and fill are non-null (the caller has checked)
+int mbn_resizer_build_view(mbn_context *ctx, int filter, int in_rows, int in_cols, int out_rows, int out_cols, const mbn_view *view, const uint8_t fill[3],
+                           mbn_resizer **out)
+{
+    mbn_resize_pad_plan_t pp;
+    const int rc = mbn_resize_view_table_plan_filter(filter, in_rows, in_cols, out_rows, out_cols, view, &pp);
+    if (rc != MBN_OK) return rc;
+    return build_in_canvas(ctx, filter, in_rows, in_cols, out_rows, out_cols, pp, view->mirror != 0, fill, out);
 }
 
 void mbn_resizer_release(mbn_resizer *r)
@@ -227,7 +258,8 @@ int mbn_launch_u8_resize(const mbn_resizer *r, hipStream_t s, uint8_t *out, cons
     a.tow = p.tow; a.toh = p.toh; a.tiles_x = p.tiles_x;
     a.seg_stride = p.seg_stride; a.stage_off = p.stage_off; a.tmp_off = p.tmp_off;
     a.d = d;
-    if (r->pad) hipLaunchKernelGGL(resize_u8<true>, grid, block, (size_t)p.lds_bytes, s, a);
+    if (r->pad && r->mirror) hipLaunchKernelGGL((resize_u8<true, true>), grid, block, (size_t)p.lds_bytes, s, a);
+    else if (r->pad) hipLaunchKernelGGL(resize_u8<true>, grid, block, (size_t)p.lds_bytes, s, a);
     else hipLaunchKernelGGL(resize_u8<false>, grid, block, (size_t)p.lds_bytes, s, a);
     return MBN_OK;
 }

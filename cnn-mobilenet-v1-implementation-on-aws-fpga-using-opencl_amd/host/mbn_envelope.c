@@ -145,6 +145,41 @@ void mbn_resample_plan(int rows, int cols, int out_rows, int out_cols, mbn_resam
     mbn_resample_window_plan(rows, cols, rows, cols, full, out_rows, out_cols, l);
 }
 
+int mbn_resample_ensemble_envelope(int batch, int rows, int cols, int classes, int in_rows, int in_cols, const mbn_view *views, int n_views,
+                                   int out_rows, int out_cols)
+{
+    if (!views || n_views < 1 || n_views > MBN_ENSEMBLE_MAX_VIEWS || batch <= 0) return MBN_EINVAL;
+    int status = MBN_OK;
+    for (int k = 0; k < n_views; k++) {
+        const mbn_view *v = &views[k];
+        if ((v->mirror != 0 && v->mirror != 1) || v->reserved[0] || v->reserved[1] || v->reserved[2]) return MBN_EINVAL;
+        const int32_t rect[4] = { v->x, v->y, v->iw, v->ih };
+        /* the logits hold batch * n_views maps (64-bit: the product may pass int) */
+        const int64_t maps = (int64_t)batch * n_views;
+        const int rc = mbn_resample_window_envelope(maps > MBN_DENSE_MAX_BATCH ? MBN_DENSE_MAX_BATCH + 1 : (int)maps, rows, cols, classes, in_rows, in_cols,
+                                                    rect, out_rows, out_cols);
+        if (rc == MBN_EINVAL) return rc;
+        if (rc != MBN_OK) status = rc;
+    }
+    return status;
+}
+
+int mbn_resample_ensemble_plan(int rows, int cols, int in_rows, int in_cols, const mbn_view *views, int n_views, int out_rows, int out_cols,
+                               mbn_resample_launch_t *l)
+{
+    if (!views || !l || n_views < 1 || n_views > MBN_ENSEMBLE_MAX_VIEWS) return MBN_EINVAL;
+    const mbn_resample_launch_t zero = { 0, 0, 0, 0, 0, 0 };
+    *l = zero;
+    for (int k = 0; k < n_views; k++) {
+        const int32_t rect[4] = { views[k].x, views[k].y, views[k].iw, views[k].ih };
+        mbn_resample_window_plan(rows, cols, in_rows, in_cols, rect, out_rows, out_cols, l);            /* the largest footprint over the views */
+    }
+    const int nv = n_views * l->fy * l->fx;
+    l->ch = MBN_RESAMPLE_ENSEMBLE_CH(nv);
+    l->lds_bytes = nv * (l->ch + 4) * 4;
+    return MBN_OK;
+}
+
 static int cmp_i64_pair(const void *a, const void *b)
 {
     const int64_t x = *(const int64_t *)a, y = *(const int64_t *)b;

@@ -102,6 +102,22 @@ void mbn_resample_window_plan(int rows, int cols, int in_rows, int in_cols, cons
  * mbn_resample_window_envelope with its own rectangle; *l is written only when the batch is accepted */
 int mbn_resample_ragged_window_check(int rows, int cols, int classes, int in_rows, int in_cols, const mbn_label_window_item *items, int batch,
                                      int64_t *sort, mbn_resample_launch_t *l);
+/* mbn_resample_ensemble_f32: the read-out of n_views views of `batch` images (logits [n_views][batch][rows][cols][classes]). MBN_EINVAL: a
+ * non-positive size, NULL views, n_views outside 1..MBN_ENSEMBLE_MAX_VIEWS, a view whose mirror is not 0 / 1, whose reserved words are not 0 or
+ * whose rectangle mbn_resample_window_envelope calls MBN_EINVAL. Else MBN_EUNSUPPORTED when any view is outside mbn_resample_window_envelope taken
+ * with batch * n_views images: one bad view refuses the set (an MBN_EINVAL of any view goes before an MBN_EUNSUPPORTED of another).
+ * The plan WIDENS nothing: it writes *l for the whole set. fy, fx = the largest footprint over the views; the kernel stages all n_views footprints
+ * per class chunk, view k at k * fy * fx vectors, so ch = MBN_RESAMPLE_ENSEMBLE_CH(n_views * fy * fx): the largest of 128 / 64 / 32 / 16 whose
+ * staged block nv * (ch + 4) * 4 bytes stays at or under 64 KB, what a launch gets without asking for more and what leaves two workgroups on a CU.
+ * Every set inside the envelope fits: 8 views x 10 x 10 vectors x 20 floats = 64 000 bytes. lds_bytes = n_views * fy * fx * (ch + 4) * 4; tiles
+ * and span are those of one out_rows x out_cols map. MBN_EINVAL for NULL views / l or n_views outside 1..8 */
+#define MBN_RESAMPLE_ENSEMBLE_LDS 65536
+#define MBN_RESAMPLE_ENSEMBLE_CH(nv) \
+    ((nv) * 132 * 4 <= MBN_RESAMPLE_ENSEMBLE_LDS ? 128 : (nv) * 68 * 4 <= MBN_RESAMPLE_ENSEMBLE_LDS ? 64 : (nv) * 36 * 4 <= MBN_RESAMPLE_ENSEMBLE_LDS ? 32 : 16)
+int mbn_resample_ensemble_envelope(int batch, int rows, int cols, int classes, int in_rows, int in_cols, const mbn_view *views, int n_views,
+                                   int out_rows, int out_cols);
+int mbn_resample_ensemble_plan(int rows, int cols, int in_rows, int in_cols, const mbn_view *views, int n_views, int out_rows, int out_cols,
+                               mbn_resample_launch_t *l);
 /* resize front-end (mbn_u8_resize.hip): one geometry of mbn_resizer_create. Source sides 1..8192, output sides 1..4096, at most MBN_RESIZE_MAX_KSIZE
  * taps per axis (a 32x downscale; any upscale has 3). box = (left, upper, right, lower), NULL = the whole image. MBN_EINVAL for a non-positive
  * size or a box mbn_resize_ksize refuses, else MBN_EUNSUPPORTED outside the limits. The batch (1..MBN_RESIZE_MAX_BATCH: grid.y) belongs to the call. */
@@ -185,6 +201,10 @@ typedef struct mbn_resize_pad_plan_t {
     int32_t fill_rows, fill_wgs;     /* border rows of a canvas and the workgroups that write them: grid.x is tiles_x * tiles_y + fill_wgs */
 } mbn_resize_pad_plan_t;
 int mbn_resize_pad_table_plan_filter(int filter, int in_rows, int in_cols, int out_rows, int out_cols, mbn_resize_pad_plan_t *plan);
+/* the same with the rectangle given (mbn_resizer_create_view): MBN_EINVAL for a NULL view, a rectangle outside the canvas, an empty side, a non-zero
+ * reserved word or mirror outside 0 / 1, else that plan's answer for (H, W) -> (ih, iw). The mirror changes no tile and no border */
+int mbn_resize_view_table_plan_filter(int filter, int in_rows, int in_cols, int out_rows, int out_cols, const mbn_view *view,
+                                      mbn_resize_pad_plan_t *plan);
 /* the ragged form (mbn_ragged_resizer_create_pad): the descriptor of one image in device memory, 96 bytes. img is mbn_resize_ragged_plan_filter of the
  * item against ih x iw, field for field (kx .. lds_bytes as for a plain ragged launch whose output is ih x iw); its wg0 is the image's first workgroup
  * of the pad launch, which gives the image tiles_x * tiles_y tile workgroups and then fill_wgs border workgroups. The inner size is the image's own, so

@@ -62,6 +62,15 @@ struct mbn_net {
     mbn_resize_item *ragged_items;  /* ... and the items it is set from, [max_batch] */
     mbn_ragged_readout *readout;    /* mbn_net_segment_images: one ragged read-out of max_batch images, made on the first call */
     void *label_items;              /* ... and the items it is set from, [max_batch] mbn_label_window_item (or as many mbn_label_item) */
+    /* mbn_net_resize_views: the view resizers kept, each made for one (source size, scale, mirror, filter, pad colour); used = the clock of its last use */
+    struct view_slot {
+        mbn_resizer *r;
+        int rows, cols, mirror, filter;
+        float scale;
+        uint8_t color[3];
+        unsigned used;
+    } view_cache[MBN_ENSEMBLE_MAX_VIEWS];
+    unsigned view_clock;
     void *poolfc_ws;           /* workspace of mbn_pool_fc (1...4 images: pool + FC in one launch), allocated and zeroed at creation */
     size_t poolfc_ws_bytes;
     int fuse_tail;             /* mbn_net_set_fuse_tail (default 0) */
@@ -156,6 +165,8 @@ int mbn_net_destroy(mbn_net *net)
     if (net->poolfc_ws) mbn_free(net->ctx, net->poolfc_ws);
     if (net->resizer) mbn_resizer_destroy(net->resizer);
     if (net->ragged) mbn_ragged_resizer_destroy(net->ragged);
+    for (int i = 0; i < MBN_ENSEMBLE_MAX_VIEWS; i++)
+        if (net->view_cache[i].r) mbn_resizer_destroy(net->view_cache[i].r);
     free(net->ragged_items);
     if (net->readout) mbn_ragged_readout_destroy(net->readout);
     free(net->label_items);
@@ -1186,6 +1197,102 @@ int mbn_net_resize_inputs(mbn_net *net, const void *src_u8, const int64_t *offse
     if (rc == MBN_OK) rc = mbn_resize_ragged_u8(net->ragged, net->resize_buf, src_u8, NULL);
     if (rc == MBN_OK) *images_u8 = net->resize_buf;
     return rc;
+}
+
+/* the views of (scales[k], mirrors[k]) for a source of in_rows x in_cols: what both calls below check first */
+static int views_of(const mbn_net *net, int batch, int in_rows, int in_cols, const float *scales, const int32_t *mirrors, int n_views, mbn_view *views)
+{
+    if (!scales || !mirrors || n_views < 1 || n_views > MBN_ENSEMBLE_MAX_VIEWS || batch <= 0 || in_rows <= 0 || in_cols <= 0) return MBN_EINVAL;
+    if ((int64_t)batch * n_views > net->max_batch) return MBN_EINVAL;
+    for (int k = 0; k < n_views; k++) {
+        const int rc = mbn_fit_view(in_rows, in_cols, net->plan.layer[0].in_rows, net->plan.layer[0].in_cols, scales[k], mirrors[k], &views[k]);
+        if (rc != MBN_OK) return rc;
+    }
+    return MBN_OK;
+}
+
+/* the kept resizer of one view, made on first use; the least recently used slot makes room (a call has at most as many views as there are slots and
+ * stamps each with the call's own clock, so it never takes a slot from itself) */
+static int view_resizer(mbn_net *net, int in_rows, int in_cols, float scale, const mbn_view *view, mbn_resizer **out)
+{
+    struct view_slot *oldest = NULL;                              /* where a new one goes: an empty slot, else the least recently used */
+    for (int i = 0; i < MBN_ENSEMBLE_MAX_VIEWS; i++) {
+        struct view_slot *v = &net->view_cache[i];
+        if (v->r && v->rows == in_rows && v->cols == in_cols && v->scale == scale && v->mirror == view->mirror && v->filter == net->resize_filter &&
+            memcmp(v->color, net->pad_color, 3) == 0) {
+            v->used = net->view_clock;
+            *out = v->r;
+            return MBN_OK;
+        }
+        if (!oldest || (oldest->r && (!v->r || (int)(v->used - oldest->used) < 0))) oldest = v;
+    }
+    mbn_resizer *r = NULL;
+    const int rc = mbn_resizer_create_view(net->ctx, net->resize_filter, in_rows, in_cols, net->plan.layer[0].in_rows, net->plan.layer[0].in_cols, view,
+                                           net->pad_color, &r);
+    if (rc != MBN_OK) return rc;
+    if (oldest->r) mbn_resizer_destroy(oldest->r);                /* waits for the stream: a resize still running reads its tables */
+    oldest->r = r;
+    oldest->rows = in_rows; oldest->cols = in_cols; oldest->scale = scale; oldest->mirror = view->mirror; oldest->filter = net->resize_filter;
+    memcpy(oldest->color, net->pad_color, 3);
+    oldest->used = net->view_clock;
+    *out = r;
+    return MBN_OK;
+}
+
+static int resize_views(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, const float *scales, const mbn_view *views, int n_views,
+                        void **staged)
+{
+    const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols;
+    if (!net->resize_buf) {
+        const int rc = mbn_alloc(net->ctx, (size_t)net->max_batch * rows * cols * 3, &net->resize_buf);
+        if (rc != MBN_OK) { net->resize_buf = NULL; return rc; }
+    }
+    net->view_clock++;
+    for (int k = 0; k < n_views; k++) {
+        mbn_resizer *r = NULL;
+        int rc = view_resizer(net, in_rows, in_cols, scales[k], &views[k], &r);
+        /* view-major: view k's canvases are images k * batch .. of the staging buffer */
+        if (rc == MBN_OK) rc = mbn_resize_u8(r, (uint8_t *)net->resize_buf + (size_t)k * batch * rows * cols * 3, src_u8, batch, NULL);
+        if (rc != MBN_OK) return rc;
+    }
+    *staged = net->resize_buf;
+    return MBN_OK;
+}
+
+int mbn_net_resize_views(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, const float *scales, const int32_t *mirrors,
+                         int n_views, void **staged)
+{
+    if (!net || !src_u8 || !staged) return MBN_EINVAL;
+    *staged = NULL;
+    mbn_view views[MBN_ENSEMBLE_MAX_VIEWS];
+    const int rc = views_of(net, batch, in_rows, in_cols, scales, mirrors, n_views, views);
+    if (rc != MBN_OK) return rc;
+    return resize_views(net, src_u8, batch, in_rows, in_cols, scales, views, n_views, staged);
+}
+
+int mbn_net_segment_views_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, const float *scales, const int32_t *mirrors,
+                              int n_views, void *labels_i32, void *prob_f32, void *score_f32, float min_prob, int ignore_label)
+{
+    if (!net || !src_u8 || !labels_i32) return MBN_EINVAL;
+    if (!net->input_u8) return MBN_EINVAL;                    /* the staged canvases are uint8: the net must take them as such */
+    if (((uintptr_t)labels_i32 | (uintptr_t)prob_f32 | (uintptr_t)score_f32) % 4) return MBN_EINVAL;
+    /* the ensemble call's own rule: no prob map and no threshold is the argmax form */
+    if ((prob_f32 || !(min_prob == 0.0f)) && mbn_softmax_readout_check(prob_f32 != NULL, min_prob) != MBN_OK) return MBN_EINVAL;
+    mbn_view views[MBN_ENSEMBLE_MAX_VIEWS];
+    int rc = views_of(net, batch, in_rows, in_cols, scales, mirrors, n_views, views);
+    if (rc != MBN_OK) return rc;
+    const mbn_layer_desc *feat, *fc;
+    rc = dense_layers(net, &feat, &fc);
+    if (rc != MBN_OK) return rc;
+    const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols;
+    rc = mbn_resample_ensemble_envelope(batch, feat->out_rows, feat->out_cols, fc->out_ch, rows, cols, views, n_views, in_rows, in_cols);
+    if (rc != MBN_OK) return rc;
+    void *images = NULL;
+    rc = resize_views(net, src_u8, batch, in_rows, in_cols, scales, views, n_views, &images);
+    if (rc == MBN_OK) rc = dense_forward(net, feat, fc, images, batch * n_views);
+    if (rc != MBN_OK) return rc;
+    return mbn_resample_ensemble_f32(net->ctx, labels_i32, prob_f32, score_f32, net->dense_logits, batch, feat->out_rows, feat->out_cols, fc->out_ch, rows,
+                                     cols, views, n_views, in_rows, in_cols, min_prob, ignore_label, NULL);
 }
 
 int mbn_net_forward_timed(mbn_net *net, const void *images, void *logits, int batch, float *layer_ms, int n_layer_ms)

@@ -123,6 +123,25 @@ int mbn_fit_pad(int in_rows, int in_cols, int out_rows, int out_cols, int32_t re
     return MBN_OK;
 }
 
+/* one view of test-time augmentation (include/mbn.h): mbn_fit_pad into the canvas scaled by `scale`, centred in the canvas itself */
+int mbn_fit_view(int in_rows, int in_cols, int out_rows, int out_cols, float scale, int mirror, mbn_view *v)
+{
+    if (!v || in_rows <= 0 || in_cols <= 0 || out_rows <= 0 || out_cols <= 0) return MBN_EINVAL;
+    if (!(scale > 0.0f && scale <= 1.0f) || (mirror != 0 && mirror != 1)) return MBN_EINVAL;                 /* a NaN fails both compares */
+    const int sc = (int)rint((double)out_cols * (double)scale), sr = (int)rint((double)out_rows * (double)scale);
+    if (sr < 1 || sc < 1) return MBN_EINVAL;
+    int32_t rect[4];
+    const int rc = mbn_fit_pad(in_rows, in_cols, sr, sc, rect);
+    if (rc != MBN_OK) return rc;
+    memset(v, 0, sizeof *v);
+    v->x = rect[0] + (out_cols - sc) / 2;
+    v->y = rect[1] + (out_rows - sr) / 2;
+    v->iw = rect[2];
+    v->ih = rect[3];
+    v->mirror = mirror;
+    return MBN_OK;
+}
+
 int mbn_resize_envelope_filter(int filter, int in_rows, int in_cols, const float *box, int out_rows, int out_cols)
 {
     if (!filter_ok(filter) || in_rows <= 0 || in_cols <= 0 || out_rows <= 0 || out_cols <= 0) return MBN_EINVAL;
@@ -294,18 +313,35 @@ static void pad_border(const int32_t rect[4], int out_rows, int out_cols, int32_
     *fill_wgs = (*fill_rows + MBN_RESIZE_FILL_ROWS - 1) / MBN_RESIZE_FILL_ROWS;
 }
 
-int mbn_resize_pad_table_plan_filter(int filter, int in_rows, int in_cols, int out_rows, int out_cols, mbn_resize_pad_plan_t *plan)
+/* the whole image into the rectangle rect of the canvas, which holds it (the callers have checked) */
+static int rect_table_plan(int filter, int in_rows, int in_cols, int out_rows, int out_cols, const int32_t rect[4], mbn_resize_pad_plan_t *plan)
 {
-    if (!plan || !filter_ok(filter)) return MBN_EINVAL;
-    int32_t rect[4];
-    int rc = mbn_fit_pad(in_rows, in_cols, out_rows, out_cols, rect);
-    if (rc != MBN_OK) return rc;
     if (out_rows > MBN_RESIZE_MAX_OUT || out_cols > MBN_RESIZE_MAX_OUT) return MBN_EUNSUPPORTED;        /* the canvas: a batch of them is grid.y x fill_wgs */
-    rc = mbn_resize_table_plan_filter(filter, in_rows, in_cols, NULL, rect[3], rect[2], &plan->plan);
+    const int rc = mbn_resize_table_plan_filter(filter, in_rows, in_cols, NULL, rect[3], rect[2], &plan->plan);
     if (rc != MBN_OK) return rc;
     plan->x = rect[0]; plan->y = rect[1]; plan->iw = rect[2]; plan->ih = rect[3];
     pad_border(rect, out_rows, out_cols, &plan->fill_rows, &plan->fill_wgs);
     return MBN_OK;
+}
+
+int mbn_resize_pad_table_plan_filter(int filter, int in_rows, int in_cols, int out_rows, int out_cols, mbn_resize_pad_plan_t *plan)
+{
+    if (!plan || !filter_ok(filter)) return MBN_EINVAL;
+    int32_t rect[4];
+    const int rc = mbn_fit_pad(in_rows, in_cols, out_rows, out_cols, rect);
+    if (rc != MBN_OK) return rc;
+    return rect_table_plan(filter, in_rows, in_cols, out_rows, out_cols, rect, plan);
+}
+
+int mbn_resize_view_table_plan_filter(int filter, int in_rows, int in_cols, int out_rows, int out_cols, const mbn_view *view,
+                                      mbn_resize_pad_plan_t *plan)
+{
+    if (!plan || !view || !filter_ok(filter) || in_rows <= 0 || in_cols <= 0 || out_rows <= 0 || out_cols <= 0) return MBN_EINVAL;
+    if ((view->mirror != 0 && view->mirror != 1) || view->reserved[0] || view->reserved[1] || view->reserved[2]) return MBN_EINVAL;
+    if (view->x < 0 || view->y < 0 || view->iw < 1 || view->ih < 1 || (int64_t)view->x + view->iw > out_cols || (int64_t)view->y + view->ih > out_rows)
+        return MBN_EINVAL;
+    const int32_t rect[4] = { view->x, view->y, view->iw, view->ih };
+    return rect_table_plan(filter, in_rows, in_cols, out_rows, out_cols, rect, plan);
 }
 
 int mbn_resize_pad_ragged_plan_filter(int filter, const mbn_resize_item *it, int out_rows, int out_cols, mbn_resize_pad_desc *d)

@@ -22,6 +22,10 @@
  *   floor(prob * 255 + 0.5) (mbn_net_segment_prob_fit / _images_fit); valid wherever --segment-source is, with or without it
  *   --min-confidence P --ignore-label L (together, with --segment-source; P in [0, 1], L in 0..65535): the pixels of that label map whose probability
  *   is below P hold L instead of their label
+ *   --tta-scales S1,S2,... [--tta-flip] (with ONE --ppm, --fit pad and --segment-source): test-time augmentation, mbn_net_segment_views_fit: the image
+ *   is shown to the network at every scale (0 < S <= 1: the letterbox shrunk about the centre of the input), with --tta-flip also mirrored, and ONE
+ *   read-out averages the views' logits. The views are (S1, plain), (S1, mirrored), (S2, plain), ... in that order, 8 at most (else usage status 2);
+ *   --segment-confidence, --min-confidence and --ignore-label work as without it
  *   mobilenet --literal [--weights weights_c.txt] [--image Cat_Image0.ppm] [--ref-args]      the reference's own mode
  *   mobilenet --gpus G --batch N [--steps K --warmup W --streams S --pw-emul 6] (--h5 F | --synthetic SEED)  N images sharded over G GPUs
  *   mobilenet --inspect weights.h5                                                             list the datasets of a .h5
@@ -423,9 +427,10 @@ static int write_confidence_map(const char *path, const float *prob, int rows, i
  * mbn_net_segment_images_fit, the read-out through the letterbox. The net takes uint8 images (the caller has set that).
  * conf_path (--segment-confidence) or ignore >= 0 (--min-confidence with --ignore-label): the softmax read-out instead, mbn_net_segment_prob_fit /
  * mbn_net_segment_prob_images_fit: image 0's probability map as an 8-bit P5, byte = floor(prob * 255 + 0.5), and the label map with the pixels
- * below min_conf replaced by `ignore`. path may then be NULL (no label map asked for) */
+ * below min_conf replaced by `ignore`. path may then be NULL (no label map asked for).
+ * n_views > 0 (--tta-scales; one file, --fit pad): mbn_net_segment_views_fit over the views (scales[k], mirrors[k]) instead, either read-out */
 static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int n_ppm, const char *path, int classes, int fit, const char *conf_path,
-                          float min_conf, int ignore)
+                          float min_conf, int ignore, const float *scales, const int32_t *mirrors, int n_views)
 {
     int64_t *offs = malloc(sizeof(int64_t) * (size_t)n_ppm), *dst = malloc(sizeof(int64_t) * (size_t)n_ppm);
     int32_t *hs = malloc(sizeof(int32_t) * (size_t)n_ppm), *ws = malloc(sizeof(int32_t) * (size_t)n_ppm);
@@ -453,7 +458,12 @@ static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int
     CHECK(mbn_alloc(ctx, sizeof(int) * pixels, &d_labels));
     CHECK(mbn_upload(ctx, d_src, all, total));
     if (!(min_conf > 0.0f)) ignore = -1;                        /* --min-confidence 0 replaces nothing: the argmax read-out, unless a map is asked for */
-    if (conf_path || ignore >= 0) {
+    if (n_views > 0) {
+        if (conf_path) CHECK(mbn_alloc(ctx, sizeof(float) * pixels, &d_prob));
+        CHECK(mbn_net_segment_views_fit(net, d_src, 1, hs[0], ws[0], scales, mirrors, n_views, d_labels, d_prob, NULL, ignore >= 0 ? min_conf : 0.0f,
+                                        ignore >= 0 ? ignore : 0));
+        printf("segment: %d views averaged in one read-out\n", n_views);
+    } else if (conf_path || ignore >= 0) {
         const float min_prob = ignore >= 0 ? min_conf : 0.0f;
         if (conf_path) CHECK(mbn_alloc(ctx, sizeof(float) * pixels, &d_prob));
         if (n_ppm == 1) CHECK(mbn_net_segment_prob_fit(net, d_src, 1, hs[0], ws[0], fit, d_labels, d_prob, min_prob, ignore));
@@ -503,6 +513,22 @@ static int pad_color_of(const char *s, int rgb[3])
     return rgb[0] >= 0 && rgb[0] <= 255 && rgb[1] >= 0 && rgb[1] <= 255 && rgb[2] >= 0 && rgb[2] <= 255;
 }
 
+/* --tta-scales S1,S2,...: up to MBN_ENSEMBLE_MAX_VIEWS numbers in (0, 1] and nothing else; their count, or 0 for anything else */
+static int tta_scales_of(const char *s, float scales[MBN_ENSEMBLE_MAX_VIEWS])
+{
+    int n = 0;
+    while (*s) {
+        char *end;
+        const float v = strtof(s, &end);
+        if (end == s || n == MBN_ENSEMBLE_MAX_VIEWS || !(v > 0.0f) || !(v <= 1.0f)) return 0;
+        scales[n++] = v;
+        if (*end == ',' && end[1]) s = end + 1;
+        else if (!*end) break;
+        else return 0;
+    }
+    return n;
+}
+
 /* --filter NAME: MBN_FILTER_*, or -1 for an unknown name */
 static int filter_of(const char *name)
 {
@@ -524,6 +550,10 @@ int main(int argc, char **argv)
     int pad_rgb[3] = { 0, 0, 0 }, src_h0 = 0, src_w0 = 0;              /* src_h0 x src_w0: image 0 as it was resized (0: it was not) */
     float crop_fraction = 1.0f, min_conf = 0.0f;
     int have_min_conf = 0, have_ignore = 0, ignore_label = -1;
+    const char *tta = NULL;
+    int tta_flip = 0, n_views = 0;
+    float tta_scales[MBN_ENSEMBLE_MAX_VIEWS], view_scales[MBN_ENSEMBLE_MAX_VIEWS];
+    int32_t view_mirrors[MBN_ENSEMBLE_MAX_VIEWS];
     int literal = 0, ref_args = 0, batch = 1, rows = 224, cols = 224, have_seed = 0, gpus = 0, steps = 20, warmup = 3, verify = 0, out_stride = 32;
     unsigned long long seed = 0;
     float alpha = 0.f;
@@ -546,6 +576,8 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--segment-confidence") && i + 1 < argc) segment_conf = argv[++i];
         else if (!strcmp(argv[i], "--min-confidence") && i + 1 < argc) { min_conf = (float)atof(argv[++i]); have_min_conf = 1; }
         else if (!strcmp(argv[i], "--ignore-label") && i + 1 < argc) { ignore_label = atoi(argv[++i]); have_ignore = 1; }
+        else if (!strcmp(argv[i], "--tta-scales") && i + 1 < argc) tta = argv[++i];
+        else if (!strcmp(argv[i], "--tta-flip")) tta_flip = 1;
         else if (!strcmp(argv[i], "--fit") && i + 1 < argc && fit_of(argv[i + 1]) >= 0) fit = fit_of(argv[++i]);
         else if (!strcmp(argv[i], "--pad-color") && i + 1 < argc && pad_color_of(argv[i + 1], pad_rgb)) i++;
         else if (!strcmp(argv[i], "--crop-fraction") && i + 1 < argc) crop_fraction = (float)atof(argv[++i]);
@@ -562,7 +594,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--literal")) literal = 1;
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
-            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--min-confidence P --ignore-label L]] [--segment-confidence OUT.pgm] "
+            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]]] [--segment-confidence OUT.pgm] "
                             "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n", argv[0]);
             return 2;
         }
@@ -582,6 +614,16 @@ int main(int argc, char **argv)
     if (segment_conf && (n_ppm < 1 || (fit != MBN_FIT_STRETCH && fit != MBN_FIT_PAD))) {
         fprintf(stderr, "--segment-confidence needs --ppm and --fit stretch or --fit pad\n");
         return 2;
+    }
+    if (tta || tta_flip) {
+        const int n_scales = tta ? tta_scales_of(tta, tta_scales) : 0;
+        if (!segment_src || fit != MBN_FIT_PAD || n_ppm != 1 || n_scales < 1 || n_scales * (1 + tta_flip) > MBN_ENSEMBLE_MAX_VIEWS) {
+            fprintf(stderr, "--tta-scales S1,S2,... (each in (0, 1]; with --tta-flip twice as many views, %d at most) needs one --ppm, --fit pad and "
+                            "--segment-source\n", MBN_ENSEMBLE_MAX_VIEWS);
+            return 2;
+        }
+        for (int k = 0; k < n_scales; k++)
+            for (int m = 0; m <= tta_flip; m++) { view_scales[n_views] = tta_scales[k]; view_mirrors[n_views++] = m; }
     }
     if (have_min_conf != have_ignore || (have_min_conf && !segment_src)) {
         fprintf(stderr, "--min-confidence P and --ignore-label L come together and with --segment-source\n");
@@ -634,7 +676,7 @@ int main(int argc, char **argv)
     CHECK(mbn_weights_from_h5_os(h5, alpha, rows, cols, out_stride, &w));
     if (have_seed) remove(tmp);
     mbn_net *net = NULL;
-    CHECK(mbn_net_create(ctx, &w, batch, &net));
+    CHECK(mbn_net_create(ctx, &w, batch > n_views ? batch : n_views, &net));      /* the views of one image are one batch of the net */
     CHECK(mbn_net_set_resize_filter(net, filter));
     CHECK(mbn_net_set_pad_color(net, pad_rgb[0], pad_rgb[1], pad_rgb[2]));
     const int classes = w.plan.classes;
@@ -739,7 +781,8 @@ int main(int argc, char **argv)
                    rect[3], rect[0], rect[1]);
     }
     if (segment_src || segment_conf) {
-        const int bad = segment_source(ctx, net, ppms, n_ppm, segment_src, classes, fit, segment_conf, min_conf, have_ignore ? ignore_label : -1);
+        const int bad = segment_source(ctx, net, ppms, n_ppm, segment_src, classes, fit, segment_conf, min_conf, have_ignore ? ignore_label : -1,
+                                       view_scales, view_mirrors, n_views);
         if (bad) return bad;
     }
     mbn_net_destroy(net);

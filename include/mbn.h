@@ -493,6 +493,36 @@ int mbn_resample_softmax_window_f32(mbn_context *ctx, void *labels_i32, void *pr
                                     float min_prob, int ignore_label, void *stream);
 int mbn_resample_softmax_ragged_f32(mbn_ragged_readout *r, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, float min_prob,
                                     int ignore_label, void *stream);
+/* Segment with test-time augmentation: ONE read-out of K views of the same images, their interpolated logits averaged per class and pixel in front
+ * of the compare (multi-scale + flip evaluation). A VIEW is one presentation of the source image to the network: the whole image
+ * resized, its aspect kept, into the rectangle (x, y, iw, ih) of the in_rows x in_cols network input, mirrored left-to-right when mirror = 1, the
+ * pad colour elsewhere (mbn_fit_view and mbn_resizer_create_view below make one). One net of fixed input size serves every view; scales above 1
+ * would crop and are refused for the reason mbn_net_segment_fit refuses MBN_FIT_CROP. The K tensors [out_rows][out_cols][classes] are never formed.
+ * logits is VIEW-MAJOR: [n_views][batch][rows][cols][classes] fp32, what one mbn_net_forward_dense of the batch * n_views staged canvases gives;
+ * labels_i32, prob_f32 and score_f32 are [batch][out_rows][out_cols]. Normative (tests/dense_ensemble_ref.py reproduces it bit for bit in numpy):
+ *   Interpolants. For view k the v_c^(k) at output (oy, ox) are exactly those of mbn_resample_argmax_window_f32 for the rectangle of view k, the
+ *     rows evaluated at oy, the columns at ox when mirror = 0 and at out_cols - 1 - ox when mirror = 1: the same index and weight rule, horizontal
+ *     first, every product and sum rounded on its own.
+ *   Sum. s_c = v_c^(0), then s_c = s_c + v_c^(k) for k = 1 .. K - 1 in view order, each addition one fp32 rounding.
+ *   Mean. t_c = s_c * invK, invK = 1.0f / (float)K, one rounding.
+ *   Label. The argmax of t_c over the classes in ascending order, strict compare: a NaN never wins; label 0 and score -inf when nothing wins. The
+ *     score is the winning t.
+ *   Probability. prob, min_prob and ignore_label follow "segment with confidence" above applied to t_c: prob = 1 / sum_c e(t_c) within
+ *     (classes + 200) * 2^-24 relative of the float64 evaluation on the fp32 t_c, exactly 0 when best is not finite; the stored label is
+ *     ignore_label iff the stored prob < min_prob.
+ * prob_f32 = NULL with min_prob = 0 is the argmax form: no exponential is evaluated. score_f32 may be NULL. K = 1 gives
+ * mbn_resample_argmax_window_f32's labels and score bit for bit (a mirror aside), and so do 2 or 4 copies of one view over the same logits: the sum
+ * and the product by 1/2 or 1/4 are exact.
+ * MBN_EINVAL: a NULL labels / logits / views, a pointer off 4 bytes, n_views outside 1..MBN_ENSEMBLE_MAX_VIEWS, a view whose rectangle
+ * mbn_resample_argmax_window_f32 calls MBN_EINVAL, whose mirror is not 0 / 1 or whose reserved words are not 0, a non-positive size, min_prob outside
+ * [0, 1] or NaN, or an undersized tracked buffer (mbn_alloc's bounds rule; the logits span n_views * batch maps). MBN_EUNSUPPORTED: any view outside
+ * mbn_resample_argmax_window_f32's envelope taken with batch * n_views images. Nothing is launched on a refusal. ONE kernel, the views by value in
+ * its arguments: it may be captured as one kernel node. */
+#define MBN_ENSEMBLE_MAX_VIEWS 8
+typedef struct mbn_view { int32_t x, y, iw, ih; int32_t mirror; int32_t reserved[3]; } mbn_view;   /* 32 bytes; mirror 0 / 1; reserved 0 */
+int mbn_resample_ensemble_f32(mbn_context *ctx, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, int batch, int rows, int cols,
+                              int classes, int in_rows, int in_cols, const mbn_view *views, int n_views, int out_rows, int out_cols, float min_prob,
+                              int ignore_label, void *stream);
 /* The classifier tail of the sequence as one call (MobileNet.c:2601-2792): global average pool (kernel.cl:116) ->
  * FC = pointwise with rows = cols = 1 (kernel.cl:94; bias, no ReLU: B15) -> softmax + top-k. fp32 NHWC,
  * in [batch][rows][cols][channels], fc_w [classes][channels], fc_bias [classes] or NULL; pooled_scratch
@@ -616,7 +646,21 @@ int mbn_normalize_u8_to_f32(mbn_context *ctx, void *out_f32, const void *in_u8, 
  *                       whole image into the rectangle of every canvas carries, per image, the workgroups that fill what lies outside it, so
  *                       the call stays legal inside a capture. The same contract for pointers and bounds; every byte of the canvas is written, the
  *                       border as NEAREST stores (bytewise to the first 4-byte boundary of the address, dwords, a bytewise tail). fill NULL:
- *                       MBN_EINVAL; an empty inner side: MBN_EINVAL; the envelope: mbn_resizer_create's on (H, W) -> (ih, iw) */
+ *                       MBN_EINVAL; an empty inner side: MBN_EINVAL; the envelope: mbn_resizer_create's on (H, W) -> (ih, iw)
+ *   mbn_fit_view        the rectangle of one VIEW of test-time augmentation (mbn_view, at mbn_resample_ensemble_f32 above): the whole H x W image,
+ *                       its aspect kept, inside a canvas scaled by `scale` about the centre of the out_rows x out_cols canvas:
+ *                           sc = (int)rint((double)out_cols * (double)scale);   sr = (int)rint((double)out_rows * (double)scale);
+ *                           (x, y, iw, ih) = mbn_fit_pad(H, W, sr, sc), moved by ((out_cols - sc) / 2, (out_rows - sr) / 2)      (integer division)
+ *                       MBN_EINVAL unless 0 < scale <= 1, sr >= 1, sc >= 1 and mirror is 0 or 1, and whatever mbn_fit_pad answers. scale = 1 is
+ *                       mbn_fit_pad's rectangle exactly. The mirror applies to the inner image only: the rectangle is the same with and without it
+ *   mbn_resizer_create_view     mbn_resizer_create_pad with the rectangle given instead of derived: the whole image resized to view->ih x view->iw
+ *                       under any filter, mirrored left-to-right when view->mirror = 1, at (view->x, view->y) of the canvas, fill elsewhere. Byte
+ *                       for byte canvas = Image.new("RGB", (ow, oh), fill); inner = im.resize((iw, ih), filter); inner =
+ *                       inner.transpose(FLIP_LEFT_RIGHT) if mirror; canvas.paste(inner, (x, y)). mbn_resize_u8 and mbn_resizer_destroy are
+ *                       unchanged; still ONE kernel node. MBN_EINVAL: a NULL view / fill, a rectangle outside the canvas, an empty side, a
+ *                       non-zero reserved word, mirror outside 0 / 1; the envelope: mbn_resizer_create's on (H, W) -> (ih, iw). The mirror costs
+ *                       no table of its own: a tile forms its columns in reverse order and lands at the mirrored place (NEAREST: the index table
+ *                       is uploaded in reverse) */
 #define MBN_FIT_STRETCH 0
 #define MBN_FIT_CROP    1
 #define MBN_FIT_PAD     2
@@ -637,6 +681,9 @@ typedef struct mbn_resizer mbn_resizer;
 int  mbn_resizer_create(mbn_context *ctx, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r);
 int  mbn_resizer_create_filter(mbn_context *ctx, int filter, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r);
 int  mbn_resizer_create_pad(mbn_context *ctx, int filter, int in_rows, int in_cols, int out_rows, int out_cols, const uint8_t fill[3], mbn_resizer **r);
+int  mbn_fit_view(int in_rows, int in_cols, int out_rows, int out_cols, float scale, int mirror, mbn_view *v);
+int  mbn_resizer_create_view(mbn_context *ctx, int filter, int in_rows, int in_cols, int out_rows, int out_cols, const mbn_view *view,
+                             const uint8_t fill[3], mbn_resizer **r);
 int  mbn_resize_u8(mbn_resizer *r, void *out_u8, const void *in_u8, int batch, void *stream);
 int  mbn_resizer_destroy(mbn_resizer *r);
 /* Ragged resize (mbn_u8_resize_ragged.hip): ONE launch takes `batch` images, each with its own rows, cols and box, to one common
@@ -1024,6 +1071,23 @@ int  mbn_net_segment_prob_fit(mbn_net *net, const void *src_u8, int batch, int i
                               float min_prob, int ignore_label);
 int  mbn_net_segment_prob_images_fit(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *rows, const int32_t *cols, int batch,
                                      int fit, void *labels_i32, const int64_t *dst_offsets, void *prob_f32, float min_prob, int ignore_label);
+/* Test-time augmentation through the letterbox (mbn_resample_ensemble_f32 above): view k is (scales[k], mirrors[k]) of mbn_fit_view into the plan's
+ * rows x cols, n_views in 1..MBN_ENSEMBLE_MAX_VIEWS, batch * n_views <= max_batch.
+ *   mbn_net_resize_views       src_u8 [batch][in_rows][in_cols][3] uint8 (device) -> the net's staging buffer, view-major: view k's `batch` canvases
+ *                              are images k * batch .. of it; *staged receives the buffer, as mbn_net_resize_input reports it. One view resizer
+ *                              (mbn_resizer_create_view, the net's filter and pad colour) per (scale, mirror), built or reused from a cache of up
+ *                              to MBN_ENSEMBLE_MAX_VIEWS handles keyed on the source size, scale, mirror, filter and colour (a change of filter or
+ *                              colour builds new ones; the least recently used one makes room); freed by mbn_net_destroy
+ *   mbn_net_segment_views_fit  checks everything first (mbn_net_set_input_u8(net, 1), batch * n_views <= max_batch, every scale and mirror, the
+ *                              ensemble's envelope at the source size, the softmax arguments): a refusal writes nothing and leaves the net usable.
+ *                              Then mbn_net_resize_views, ONE mbn_net_forward_dense of batch * n_views images and ONE mbn_resample_ensemble_f32 to
+ *                              in_rows x in_cols: labels_i32, prob_f32 (may be NULL) and score_f32 (may be NULL) [batch][in_rows][in_cols].
+ *                              prob_f32 = NULL with min_prob = 0: the argmax form
+ * F32, BF16 and I8 (output stride 32 only), any plan of mbn_plan_build_os: the dense logits are fp32 in all of them. */
+int  mbn_net_resize_views(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, const float *scales, const int32_t *mirrors,
+                          int n_views, void **staged);
+int  mbn_net_segment_views_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, const float *scales, const int32_t *mirrors,
+                               int n_views, void *labels_i32, void *prob_f32, void *score_f32, float min_prob, int ignore_label);
 /* Per-layer milliseconds of the most recent mbn_net_forward_timed call (hipEvents between layers). */
 int  mbn_net_forward_timed(mbn_net *net, const void *images, void *logits, int batch, float *layer_ms,
                            int n_layer_ms);

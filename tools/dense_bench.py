@@ -24,6 +24,10 @@
   python tools/dense_bench.py --any --prob [--reps 7] [--steps 20] [--batch 32] [--torch-steps 2] [--no-torch]
       mbn_resample_softmax_f32 / _window_f32 / _ragged_f32, the read-out with confidence (main_prob): each beside the argmax kernel of the same
       form on the same buffers, alternating in one process, and torch's three-pass interpolate(size=...).softmax(1).max(1).
+
+  python tools/dense_bench.py --ensemble 1,2,3,6 [--reps 7] [--steps 20] [--batch 32] [--torch-steps 1] [--no-torch]
+      mbn_resample_ensemble_f32, the fused multi-view read-out (main_ensemble): per view count K against the unchanged window kernel on one view,
+      against K launches of it, and against torch's sum of K interpolate(...) then argmax / softmax(1).max(1), argmax and --prob forms alike.
 """
 import argparse
 import json
@@ -304,6 +308,117 @@ def main_prob(a):
     print(json.dumps(result))
 
 
+TTA_VIEWS = [(1.0, 0), (1.0, 1), (0.75, 0), (0.75, 1), (0.5, 0), (0.5, 1), (0.875, 0), (0.875, 1)]      # (scale, mirror): the first K are timed
+
+
+def main_ensemble(a):
+    """--ensemble K[,K...]: the README's read-out shapes (1000 classes, to 375 x 500 from the 28 x 28 and the 14 x 14 map of a 224 x 224 input,
+    through the letterbox, --batch output images of random logits, sigma 3), K views = the first K of TTA_VIEWS through mbn_fit_view, the logits
+    view-major. Per map and K, alternating within every repetition, argmax form and prob form (labels + score / labels + score + prob):
+      window     (a) the unchanged window kernel on view 0 alone: mbn_resample_argmax_window_f32 / _softmax_window_f32
+      k_windows  (b) K launches of it, view k's rectangle over view k's logits (the yardstick: the ensemble forms K times its interpolants)
+      ensemble   mbn_resample_ensemble_f32 over the K views, ONE launch
+      torch      (c) on the same buffers: sum_k interpolate(view k, size=(375, 500)) then argmax(1) / softmax(1).max(1), in slices of 8 images
+                 (its interpolate refuses outputs of 2^31 elements), in the first three repetitions only: a pass at K = 6 takes about a second
+    Each figure is the median over the repetitions of `steps` back-to-back calls between two stream marks; the runs are kept, the spread is
+    (max - min) / median of a name's own repetitions. ensemble_over_k_windows is the figure the issue asks for: at or under 1 plus the spread."""
+    pkg = import_package()
+    torch = None
+    if not a.no_torch:
+        import torch
+        assert torch.cuda.is_available(), "the yardstick needs torch on the same GPU"
+    ks = sorted({int(k) for k in a.ensemble.split(",")})
+    assert ks and 1 <= ks[0] and ks[-1] <= len(TTA_VIEWS)
+    n, rng, H, W = a.batch, np.random.default_rng(0), 375, 500
+    views = [pkg.fit_view(H, W, RES, RES, s, m) for s, m in TTA_VIEWS[:ks[-1]]]
+    result = {"batch": n, "views": [list(v.rect) + [v.mirror] for v in views]}
+    with pkg.Context(0) as ctx:
+        d_lab, d_sc, d_pr = ctx.alloc(n * H * W * 4), ctx.alloc(n * H * W * 4), ctx.alloc(n * H * W * 4)
+        for hw_ in (28, 14):
+            x = (3.0 * rng.standard_normal((ks[-1], n, hw_, hw_, CLASSES))).astype(np.float32)
+            if torch is not None:
+                t = torch.from_numpy(x).cuda()
+                p = t.data_ptr()
+            else:
+                t = ctx.to_device(x)
+                p = t.ptr
+            stride = n * hw_ * hw_ * CLASSES * 4
+            runs = []
+
+            def window(k, prob, p=p, hw_=hw_, stride=stride):
+                if prob:
+                    ctx.resample_softmax_window(d_lab.ptr, d_pr.ptr, d_sc.ptr, p + k * stride, n, hw_, hw_, CLASSES, RES, RES, views[k].rect, H, W)
+                else:
+                    ctx.resample_argmax_window(d_lab.ptr, d_sc.ptr, p + k * stride, n, hw_, hw_, CLASSES, RES, RES, views[k].rect, H, W)
+
+            for prob in (False, True):
+                form = "prob" if prob else "argmax"
+                runs.append(("window_%s" % form, lambda prob=prob: window(0, prob)))
+                for K in ks:
+                    runs.append(("k_windows_%s_K%d" % (form, K), lambda prob=prob, K=K: [window(k, prob) for k in range(K)]))
+                    runs.append(("ensemble_%s_K%d" % (form, K),
+                                 lambda prob=prob, K=K, p=p, hw_=hw_: ctx.resample_ensemble(d_lab.ptr, d_pr.ptr if prob else None, d_sc.ptr, p, n, hw_, hw_,
+                                                                                            CLASSES, RES, RES, views[:K], H, W)))
+            times = {name: [] for name, _ in runs}
+            t_times = {(form, K): [] for form in ("argmax", "prob") for K in ks}
+            for _, fn in runs:
+                marks_ms(ctx, fn, 2)
+            for rep in range(a.reps):
+                for name, fn in runs:
+                    times[name].append(marks_ms(ctx, fn, a.steps))
+                if torch is None or rep >= 3:
+                    continue
+                ctx.sync()
+                nchw = t.permute(0, 1, 4, 2, 3)
+                for form in ("argmax", "prob"):
+                    for K in ks:
+                        def passes():
+                            for i in range(0, n, 8):
+                                acc = torch.nn.functional.interpolate(nchw[0, i:i + 8], size=(H, W), mode="bilinear", align_corners=False)
+                                for k in range(1, K):
+                                    acc += torch.nn.functional.interpolate(nchw[k, i:i + 8], size=(H, W), mode="bilinear", align_corners=False)
+                                if form == "prob":
+                                    acc.softmax(1).max(1)
+                                else:
+                                    acc.argmax(1)
+                        if rep == 0:
+                            passes()
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        for _ in range(a.torch_steps):
+                            passes()
+                        e1.record()
+                        torch.cuda.synchronize()
+                        t_times[(form, K)].append(e0.elapsed_time(e1) / a.torch_steps)
+            out = {}
+            for name, _ in runs:
+                m = statistics.median(times[name])
+                out[name] = {"kernel_ms": round(m, 4), "kernel_runs_ms": [round(v, 4) for v in times[name]],
+                             "spread": round((max(times[name]) - min(times[name])) / m, 4)}
+            for form in ("argmax", "prob"):
+                one = out["window_%s" % form]["kernel_ms"]
+                for K in ks:
+                    l = pkg.resample_ensemble_plan(hw_, hw_, RES, RES, views[:K], H, W)
+                    e, kw = out["ensemble_%s_K%d" % (form, K)], out["k_windows_%s_K%d" % (form, K)]
+                    e.update({"footprint": [l.fy, l.fx], "chunk": l.ch, "lds_bytes": l.lds_bytes, "over_k_windows": round(e["kernel_ms"] / kw["kernel_ms"], 3),
+                              "over_k_times_window": round(e["kernel_ms"] / (K * one), 3)})
+                    ts = t_times[(form, K)]
+                    if ts:
+                        tm = statistics.median(ts)
+                        e.update({"torch_ms": round(tm, 3), "torch_runs_ms": [round(v, 3) for v in ts], "torch_over_ensemble": round(tm / e["kernel_ms"], 1)})
+                    print("from %d %-6s K %d: window %.4f  K windows %.4f (spread %.1f %%)  ensemble %.4f ms (spread %.1f %%, chunk %d, %d B LDS)  "
+                          "ensemble / K windows %.3f  torch %s ms" % (hw_, form, K, one, kw["kernel_ms"], 100 * kw["spread"], e["kernel_ms"],
+                                                                      100 * e["spread"], l.ch, l.lds_bytes, e["over_k_windows"],
+                                                                      ("%.1f" % e["torch_ms"]) if ts else "-"), flush=True)
+            result["from_%d" % hw_] = out
+            if torch is not None:
+                del t
+                torch.cuda.empty_cache()
+            else:
+                t.free()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
@@ -315,7 +430,10 @@ def main():
     ap.add_argument("--torch-steps", type=int, default=2, help="--any: torch calls per repetition (each writes batch x 1000 x 375 x 500 floats)")
     ap.add_argument("--fit", default="stretch", choices=("stretch", "pad"), help="--any: pad times the window kernel instead: see main_any_pad")
     ap.add_argument("--prob", action="store_true", help="--any: time the softmax read-out beside the argmax read-out instead: see main_prob")
+    ap.add_argument("--ensemble", default="", help="comma list of view counts: time mbn_resample_ensemble_f32 instead: see main_ensemble")
     a = ap.parse_args()
+    if a.ensemble:
+        return main_ensemble(a)
     if a.any and a.prob:
         return main_prob(a)
     if a.any:
