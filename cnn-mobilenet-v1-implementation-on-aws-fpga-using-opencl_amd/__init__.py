@@ -113,6 +113,13 @@ class View(C.Structure):
         return (self.x, self.y, self.iw, self.ih)
 
 
+class SegMetrics(C.Structure):
+    """mbn_seg_metrics (include/mbn.h, "score a segmentation")"""
+    _fields_ = [("pixels", C.c_double), ("valid", C.c_double), ("void_pixels", C.c_double), ("abstained", C.c_double),
+                ("pixel_accuracy", C.c_double), ("mean_accuracy", C.c_double), ("miou", C.c_double), ("fw_iou", C.c_double),
+                ("classes_present", C.c_int32), ("reserved", C.c_int32)]
+
+
 class ResampleLaunch(C.Structure):
     """mbn_resample_launch_t (host/mbn_envelope.h): LDS footprint, class chunk, dynamic LDS, grid.x and output span of a read-out launch"""
     _fields_ = [(n, C.c_int32) for n in ("fy", "fx", "ch", "lds_bytes", "tiles")] + [("span", C.c_int64)]
@@ -212,6 +219,9 @@ def _declare_host(lib):
     lib.mbn_resize_view_table_plan_filter.argtypes = [C.c_int] * 5 + [C.POINTER(View), C.POINTER(ResizePadPlan)]
     lib.mbn_resample_ragged_window_check.argtypes = [C.c_int] * 5 + [C.POINTER(LabelWindowItem), C.c_int, C.POINTER(C.c_int64),
                                                                      C.POINTER(ResampleLaunch)]
+    lib.mbn_confusion_envelope.argtypes = [C.c_int, C.c_int, C.c_int64]
+    lib.mbn_confusion_form.argtypes = [C.c_int]
+    lib.mbn_confusion_metrics.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.POINTER(SegMetrics), C.POINTER(C.c_double)]
     i32p = C.POINTER(C.c_int32)
     lib.mbn_resize_ksize.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int]
     lib.mbn_resize_taps.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int, i32p, i32p, i32p]
@@ -365,6 +375,9 @@ def load():
         lib.mbn_resizer_create_view.argtypes = [vp, ci, ci, ci, ci, ci, C.POINTER(View), C.POINTER(C.c_uint8), C.POINTER(vp)]
         lib.mbn_net_resize_views.argtypes = [vp, vp, ci, ci, ci, C.POINTER(C.c_float), C.POINTER(C.c_int32), ci, C.POINTER(vp)]
         lib.mbn_net_segment_views_fit.argtypes = [vp, vp, ci, ci, ci, C.POINTER(C.c_float), C.POINTER(C.c_int32), ci, vp, vp, vp, C.c_float, ci]
+        lib.mbn_confusion_i32.argtypes = [vp, vp, vp, vp, ci, ci, C.c_int64, vp]
+        lib.mbn_confusion_ragged_i32.argtypes = [vp, vp, vp, vp, ci, ci, vp]
+        lib.mbn_net_segment_score.argtypes = [vp, vp, vp, ci, vp]
         lib.mbn_resizer_create.argtypes = [vp, ci, ci, C.POINTER(C.c_float), ci, ci, C.POINTER(vp)]
         lib.mbn_resize_u8.argtypes = [vp, vp, vp, ci, vp]
         lib.mbn_resizer_destroy.argtypes = [vp]
@@ -639,6 +652,31 @@ def resample_ragged_check(rows, cols, classes, items, lib=None):
     return rc, l
 
 
+CONFUSION_MAX_CLASSES = 4096
+CONFUSION_FORM_LDS, CONFUSION_FORM_GLOBAL = 0, 1
+
+
+def confusion_envelope(classes, truth_bytes, count, lib=None) -> int:
+    """mbn_confusion_envelope: the status (OK, EINVAL or EUNSUPPORTED) mbn_confusion_i32 gives the shape."""
+    return (lib or host_lib()).mbn_confusion_envelope(classes, truth_bytes, count)
+
+
+def confusion_form(classes, lib=None) -> int:
+    """mbn_confusion_form: CONFUSION_FORM_LDS (a workgroup counts in LDS) or CONFUSION_FORM_GLOBAL (global atomics only) for a class count."""
+    return (lib or host_lib()).mbn_confusion_form(classes)
+
+
+def confusion_metrics(counts, classes, lib=None):
+    """mbn_confusion_metrics: (SegMetrics, iou float64 [classes], NaN for an absent class) of counts, uint64 [classes + 1][classes + 1]."""
+    n = np.ascontiguousarray(counts, dtype=np.uint64)
+    if n.size != (classes + 1) ** 2:
+        raise ValueError("counts has %d cells, classes = %d needs %d" % (n.size, classes, (classes + 1) ** 2))
+    m, iou = SegMetrics(), np.empty(classes, np.float64)
+    _chk((lib or host_lib()).mbn_confusion_metrics(n.ctypes.data_as(C.POINTER(C.c_uint64)), classes, C.byref(m),
+                                                   iou.ctypes.data_as(C.POINTER(C.c_double))), "confusion_metrics")
+    return m, iou
+
+
 def declared_symbols():
     """Every function name declared in include/mbn.h (for the export test)."""
     import re
@@ -867,6 +905,15 @@ class Context:
         _chk(self.lib.mbn_resample_ensemble_f32(self.h, labels, prob, score, logits, batch, rows, cols, classes, in_rows, in_cols, arr,
                                                 len(arr) if n_views is None else n_views, out_rows, out_cols, min_prob, ignore_label, None),
              self.last_error())
+
+    def confusion(self, counts, labels, truth, truth_bytes, classes, count, stream=None):
+        """mbn_confusion_i32: counts (uint64 [classes + 1][classes + 1], device) += the confusion matrix of `count` int32 labels against truth
+        (uint8: truth_bytes 1, int32: 4); row = truth (row `classes`: void), column = label (column `classes`: abstained)."""
+        _chk(self.lib.mbn_confusion_i32(self.h, counts, labels, truth, truth_bytes, classes, count, stream), self.last_error())
+
+    def confusion_ragged(self, readout, counts, labels, truth, truth_bytes, classes, stream=None):
+        """mbn_confusion_ragged_i32: the same over the maps of a RaggedReadout's set; truth at the labels' element offsets."""
+        _chk(self.lib.mbn_confusion_ragged_i32(readout.h, counts, labels, truth, truth_bytes, classes, stream), self.last_error())
 
     def __enter__(self):
         return self
@@ -1179,6 +1226,11 @@ class Net:
         _chk(self.ctx.lib.mbn_net_segment_views_fit(self.h, src_ptr, batch, in_rows, in_cols, (C.c_float * n)(*[float(v) for v in scales]),
                                                     (C.c_int32 * n)(*[int(v) for v in mirrors]), n, labels_ptr, prob_ptr, score_ptr, min_prob,
                                                     ignore_label), self.ctx.last_error())
+
+    def segment_score(self, labels_ptr, truth_ptr, truth_bytes, counts_ptr):
+        """mbn_net_segment_score: counts (uint64 [classes + 1][classes + 1]) += the confusion matrix of the maps the most recent successful
+        source-size segment call wrote against truth (uint8 or int32, at the labels' element offsets)."""
+        _chk(self.ctx.lib.mbn_net_segment_score(self.h, labels_ptr, truth_ptr, truth_bytes, counts_ptr), self.ctx.last_error())
 
     def resize_input(self, src_ptr, batch, in_rows, in_cols, fit=FIT_CROP, crop_fraction=1.0) -> int:
         """mbn_net_resize_input: uint8 images [batch][in_rows][in_cols][3] of any size -> the net's staging buffer [batch][rows][cols][3] (its

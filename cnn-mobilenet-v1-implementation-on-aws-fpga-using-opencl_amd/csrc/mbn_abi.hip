@@ -976,6 +976,42 @@ int mbn_resample_softmax_ragged_f32(mbn_ragged_readout *r, void *labels_i32, voi
     return resample_ragged(r, labels_i32, score_f32, logits, stream, &q);
 }
 
+// What the two confusion calls share: the pointer and alignment checks, the envelope, the spans (`elements` of labels and truth), the launch
+extern "C++" {
+template <typename Launch>
+static int confusion_call(mbn_context *ctx, void *counts_u64, const void *labels_i32, const void *truth, int truth_bytes, int classes, int64_t elements,
+                          void *stream, Launch launch)
+{
+    if (!ctx || !counts_u64 || !labels_i32 || !truth) return MBN_EINVAL;
+    const int shape = mbn_confusion_envelope(classes, truth_bytes, elements);
+    if (shape == MBN_EINVAL) return shape;
+    if ((uintptr_t)counts_u64 % 8 || (uintptr_t)labels_i32 % 4 || (truth_bytes == 4 && (uintptr_t)truth % 4)) return MBN_EINVAL;
+    if (shape != MBN_OK) return shape;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    MBN_SPANS(ctx, { counts_u64, 8.0 * (classes + 1) * (classes + 1), "confusion counts" }, { labels_i32, 4.0 * (double)elements, "confusion labels" },
+              { truth, (double)truth_bytes * (double)elements, "confusion truth" });
+    Scope sc(ctx, s);
+    return sc.finish(launch(s));
+}
+}   // extern "C++"
+
+int mbn_confusion_i32(mbn_context *ctx, void *counts_u64, const void *labels_i32, const void *truth, int truth_bytes, int classes, int64_t count,
+                      void *stream)
+{
+    return confusion_call(ctx, counts_u64, labels_i32, truth, truth_bytes, classes, count, stream, [&](hipStream_t s) {
+        return mbn_launch_i32_confusion(ctx, s, counts_u64, labels_i32, truth, truth_bytes, classes, count);
+    });
+}
+
+int mbn_confusion_ragged_i32(mbn_ragged_readout *r, void *counts_u64, const void *labels_i32, const void *truth, int truth_bytes, int classes,
+                             void *stream)
+{
+    if (!r || r->batch <= 0) return MBN_EINVAL;                  // no set: nothing to score
+    return confusion_call(r->ctx, counts_u64, labels_i32, truth, truth_bytes, classes, r->launch.span, stream, [&](hipStream_t s) {
+        return mbn_launch_i32_confusion_ragged(r, s, counts_u64, labels_i32, truth, truth_bytes, classes);
+    });
+}
+
 int mbn_resizer_create_filter(mbn_context *ctx, int filter, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, mbn_resizer **r)
 {
     if (!ctx || !r) return MBN_EINVAL;

@@ -293,6 +293,12 @@ int mbn_launch_f32_resample_argmax_ragged(mbn_ragged_readout *r, hipStream_t s, 
 int mbn_launch_f32_resample_ensemble(mbn_context *ctx, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows, int cols,
                                      int classes, int in_rows, int in_cols, const mbn_view *views, int n_views, int out_rows, int out_cols,
                                      const mbn_readout_prob *q);
+// score a segmentation (mbn_i32_confusion.hip): counts [classes + 1][classes + 1] uint64 += the confusion matrix of `count` labels against truth
+// (uint8 or int32). The arguments are inside mbn_confusion_envelope and the pointers checked; the ragged form scores the items of the handle's set
+int mbn_launch_i32_confusion(mbn_context *ctx, hipStream_t s, void *counts, const void *labels, const void *truth, int truth_bytes, int classes,
+                             int64_t count);
+int mbn_launch_i32_confusion_ragged(mbn_ragged_readout *r, hipStream_t s, void *counts, const void *labels, const void *truth, int truth_bytes,
+                                    int classes);
 // resize front-end (mbn_u8_resize.hip): the geometry is inside mbn_resize_envelope; build uploads the tables (blocking), release frees them.
 // mirror: the outputs' columns in reverse order (a view's inner image). build_view: the rectangle given (view and fill are non-null)
 int mbn_resizer_build(mbn_context *ctx, int filter, int in_rows, int in_cols, const float *box, int out_rows, int out_cols, bool mirror, mbn_resizer **r);

@@ -118,6 +118,21 @@ int mbn_resample_ensemble_envelope(int batch, int rows, int cols, int classes, i
                                    int out_rows, int out_cols);
 int mbn_resample_ensemble_plan(int rows, int cols, int in_rows, int in_cols, const mbn_view *views, int n_views, int out_rows, int out_cols,
                                mbn_resample_launch_t *l);
+/* score a segmentation (mbn_i32_confusion.hip, host/mbn_score.c; declared in mbn.h too). mbn_confusion_envelope: MBN_EINVAL for classes < 1,
+ * count < 1 or truth_bytes other than 1 / 4, else MBN_EUNSUPPORTED for classes > MBN_CONFUSION_MAX_CLASSES or count > MBN_CONFUSION_MAX_COUNT.
+ * mbn_confusion_form: MBN_CONFUSION_FORM_LDS while the workgroup's table of (classes + 1)^2 32-bit bins fits MBN_CONFUSION_LDS bytes of LDS,
+ * that is up to MBN_CONFUSION_LDS_CLASSES (151^2 * 4 = 91 204 bytes: one workgroup of 16 waves on a CU; a table of at most half a CU's 160 KB, up to
+ * 142 classes, leaves room for two), MBN_CONFUSION_FORM_GLOBAL above. MBN_CONFUSION_EPOCH: the chunks of 4096 pixels a workgroup counts between two flushes of
+ * that table, so that a 32-bit bin stays below 2^32 */
+#define MBN_CONFUSION_MAX_COUNT ((int64_t)1 << 34)
+#define MBN_CONFUSION_LDS (92 * 1024)
+#define MBN_CONFUSION_CU_LDS (160 * 1024)
+#define MBN_CONFUSION_LDS_CLASSES 150
+#define MBN_CONFUSION_EPOCH 512
+#define MBN_CONFUSION_FORM_LDS 0
+#define MBN_CONFUSION_FORM_GLOBAL 1
+int mbn_confusion_envelope(int classes, int truth_bytes, int64_t count);
+int mbn_confusion_form(int classes);
 /* resize front-end (mbn_u8_resize.hip): one geometry of mbn_resizer_create. Source sides 1..8192, output sides 1..4096, at most MBN_RESIZE_MAX_KSIZE
  * taps per axis (a 32x downscale; any upscale has 3). box = (left, upper, right, lower), NULL = the whole image. MBN_EINVAL for a non-positive
  * size or a box mbn_resize_ksize refuses, else MBN_EUNSUPPORTED outside the limits. The batch (1..MBN_RESIZE_MAX_BATCH: grid.y) belongs to the call. */

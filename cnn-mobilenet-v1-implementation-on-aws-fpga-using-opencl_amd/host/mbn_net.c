@@ -62,6 +62,8 @@ struct mbn_net {
     mbn_resize_item *ragged_items;  /* ... and the items it is set from, [max_batch] */
     mbn_ragged_readout *readout;    /* mbn_net_segment_images: one ragged read-out of max_batch images, made on the first call */
     void *label_items;              /* ... and the items it is set from, [max_batch] mbn_label_window_item (or as many mbn_label_item) */
+    int score_kind;                 /* mbn_net_segment_score: what the last successful source-size segment call wrote: SCORE_NONE, _UNIFORM, _RAGGED */
+    int64_t score_count;            /* SCORE_UNIFORM: its batch * out_rows * out_cols pixels */
     /* mbn_net_resize_views: the view resizers kept, each made for one (source size, scale, mirror, filter, pad colour); used = the clock of its last use */
     struct view_slot {
         mbn_resizer *r;
@@ -910,6 +912,21 @@ static int dense_forward(mbn_net *net, const mbn_layer_desc *feat, const mbn_lay
     return mbn_net_forward_dense(net, images, net->dense_logits, batch);
 }
 
+/* mbn_net_segment_score's record: every source-size segment call ends in one of these two, so only a successful read-out changes it */
+enum { SCORE_NONE = 0, SCORE_UNIFORM = 1, SCORE_RAGGED = 2 };
+
+static int scored_uniform(mbn_net *net, int rc, int batch, int out_rows, int out_cols)
+{
+    if (rc == MBN_OK) { net->score_kind = SCORE_UNIFORM; net->score_count = (int64_t)batch * out_rows * out_cols; }
+    return rc;
+}
+
+static int scored_ragged(mbn_net *net, int rc)
+{
+    if (rc == MBN_OK) net->score_kind = SCORE_RAGGED;
+    return rc;
+}
+
 int mbn_net_segment(mbn_net *net, const void *images, int batch, void *labels_i32, void *score_f32)
 {
     if (!net || !images || !labels_i32 || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
@@ -921,7 +938,8 @@ int mbn_net_segment(mbn_net *net, const void *images, int batch, void *labels_i3
     if (factor * h != rows || factor * w != cols || (factor != 8 && factor != 16 && factor != 32)) return MBN_EUNSUPPORTED;
     rc = dense_forward(net, feat, fc, images, batch);
     if (rc != MBN_OK) return rc;
-    return mbn_upsample_argmax_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, factor, NULL);
+    return scored_uniform(net, mbn_upsample_argmax_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, factor, NULL), batch,
+                          rows, cols);
 }
 
 /* The read-out of the three source-size paths below: q = NULL is the argmax read-out (labels and score), q given the softmax read-out
@@ -977,7 +995,7 @@ static int segment_to(mbn_net *net, const void *images, int batch, int out_rows,
     if (rc == MBN_OK) rc = uniform_envelope(net, feat, fc, batch, NULL, out_rows, out_cols);
     if (rc == MBN_OK) rc = dense_forward(net, feat, fc, images, batch);
     if (rc != MBN_OK) return rc;
-    return uniform_readout(net, feat, fc, batch, NULL, out_rows, out_cols, labels_i32, score_f32, q);
+    return scored_uniform(net, uniform_readout(net, feat, fc, batch, NULL, out_rows, out_cols, labels_i32, score_f32, q), batch, out_rows, out_cols);
 }
 
 int mbn_net_segment_to(mbn_net *net, const void *images, int batch, int out_rows, int out_cols, void *labels_i32, void *score_f32)
@@ -1023,7 +1041,7 @@ static int segment_fit(mbn_net *net, const void *src_u8, int batch, int in_rows,
     rc = mbn_net_resize_input(net, src_u8, batch, in_rows, in_cols, fit, 1.0f, &images);
     if (rc == MBN_OK) rc = dense_forward(net, feat, fc, images, batch);
     if (rc != MBN_OK) return rc;
-    return uniform_readout(net, feat, fc, batch, rect, in_rows, in_cols, labels_i32, score_f32, q);
+    return scored_uniform(net, uniform_readout(net, feat, fc, batch, rect, in_rows, in_cols, labels_i32, score_f32, q), batch, in_rows, in_cols);
 }
 
 int mbn_net_segment_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, void *labels_i32, void *score_f32)
@@ -1083,8 +1101,10 @@ static int segment_images_fit(mbn_net *net, const void *src_u8, const int64_t *o
     rc = mbn_net_resize_inputs(net, src_u8, offsets, in_rows, in_cols, batch, fit, 1.0f, &images);
     if (rc == MBN_OK) rc = dense_forward(net, feat, fc, images, batch);
     if (rc != MBN_OK) return rc;
-    if (q) return mbn_resample_softmax_ragged_f32(net->readout, labels_i32, q->prob, NULL, net->dense_logits, q->min_prob, q->ignore_label, NULL);
-    return mbn_resample_argmax_ragged_f32(net->readout, labels_i32, score_f32, net->dense_logits, NULL);
+    if (q)
+        return scored_ragged(net, mbn_resample_softmax_ragged_f32(net->readout, labels_i32, q->prob, NULL, net->dense_logits, q->min_prob,
+                                                                  q->ignore_label, NULL));
+    return scored_ragged(net, mbn_resample_argmax_ragged_f32(net->readout, labels_i32, score_f32, net->dense_logits, NULL));
 }
 
 int mbn_net_segment_images_fit(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *in_rows, const int32_t *in_cols, int batch,
@@ -1291,8 +1311,19 @@ int mbn_net_segment_views_fit(mbn_net *net, const void *src_u8, int batch, int i
     rc = resize_views(net, src_u8, batch, in_rows, in_cols, scales, views, n_views, &images);
     if (rc == MBN_OK) rc = dense_forward(net, feat, fc, images, batch * n_views);
     if (rc != MBN_OK) return rc;
-    return mbn_resample_ensemble_f32(net->ctx, labels_i32, prob_f32, score_f32, net->dense_logits, batch, feat->out_rows, feat->out_cols, fc->out_ch, rows,
-                                     cols, views, n_views, in_rows, in_cols, min_prob, ignore_label, NULL);
+    return scored_uniform(net, mbn_resample_ensemble_f32(net->ctx, labels_i32, prob_f32, score_f32, net->dense_logits, batch, feat->out_rows,
+                                                         feat->out_cols, fc->out_ch, rows, cols, views, n_views, in_rows, in_cols, min_prob,
+                                                         ignore_label, NULL), batch, in_rows, in_cols);
+}
+
+int mbn_net_segment_score(mbn_net *net, const void *labels_i32, const void *truth, int truth_bytes, void *counts_u64)
+{
+    if (!net || net->score_kind == SCORE_NONE) return MBN_EINVAL;
+    const mbn_layer_desc *feat, *fc;
+    const int rc = dense_layers(net, &feat, &fc);
+    if (rc != MBN_OK) return rc;
+    if (net->score_kind == SCORE_RAGGED) return mbn_confusion_ragged_i32(net->readout, counts_u64, labels_i32, truth, truth_bytes, fc->out_ch, NULL);
+    return mbn_confusion_i32(net->ctx, counts_u64, labels_i32, truth, truth_bytes, fc->out_ch, net->score_count, NULL);
 }
 
 int mbn_net_forward_timed(mbn_net *net, const void *images, void *logits, int batch, float *layer_ms, int n_layer_ms)

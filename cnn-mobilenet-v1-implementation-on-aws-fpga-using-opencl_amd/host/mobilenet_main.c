@@ -26,6 +26,11 @@
  *   is shown to the network at every scale (0 < S <= 1: the letterbox shrunk about the centre of the input), with --tta-flip also mirrored, and ONE
  *   read-out averages the views' logits. The views are (S1, plain), (S1, mirrored), (S2, plain), ... in that order, 8 at most (else usage status 2);
  *   --segment-confidence, --min-confidence and --ignore-label work as without it
+ *   --truth F.pgm (several times: the n-th pairs with the n-th --ppm, as many as there are; needs --segment-source): the ground truth of that image, a P5
+ *   of its size (another size: error exit). maxval <= 255: one byte per pixel, uint8 truth; larger: two big-endian bytes, the format --segment-source
+ *   itself writes, int32 truth, so a label map this tool wrote can be fed back. The label maps are scored on the device (mbn_net_segment_score: a value
+ *   outside the classes is void in the truth and abstained in the labels, --ignore-label among them) and ONE line is printed:
+ *   score: pixels=... valid=... void=... abstained=... classes_present=... pixel_acc=... mean_acc=... miou=... fw_iou=... (mbn_confusion_metrics, %.17g)
  *   mobilenet --literal [--weights weights_c.txt] [--image Cat_Image0.ppm] [--ref-args]      the reference's own mode
  *   mobilenet --gpus G --batch N [--steps K --warmup W --streams S --pw-emul 6] (--h5 F | --synthetic SEED)  N images sharded over G GPUs
  *   mobilenet --inspect weights.h5                                                             list the datasets of a .h5
@@ -407,6 +412,81 @@ static int ppm_size(const char *path, int *width, int *height)
 
 #define PPM_MAX_SIDE 8192     /* the resize front-end's largest source side */
 
+/* --truth: a P5 of exactly width x height into out [height * width]; maxval <= 255: a byte per pixel, else two big-endian bytes. *wide: maxval > 255.
+ * 0, or 2 with a message for a file that is not such a P5 or has another size */
+static int read_truth_pgm(const char *path, int width, int height, int32_t *out, int *wide)
+{
+    FILE *fp = fopen(path, "rb");
+    int v[3] = { 0, 0, 0 };
+    int ok = fp && fgetc(fp) == 'P' && fgetc(fp) == '5';
+    for (int f = 0; ok && f < 3; f++) {
+        int c = fgetc(fp);
+        while (c == '#' || c == ' ' || c == '\t' || c == '\n' || c == '\r') {
+            if (c == '#') while (c != '\n' && c != EOF) c = fgetc(fp);
+            c = fgetc(fp);
+        }
+        int digits = 0;
+        for (; c >= '0' && c <= '9' && digits < 6; c = fgetc(fp), digits++) v[f] = v[f] * 10 + (c - '0');
+        ok = digits > 0 && digits < 6 && v[f] > 0 && (f < 2 || (v[f] <= 65535 && (c == ' ' || c == '\t' || c == '\n' || c == '\r')));
+    }
+    if (!ok) { if (fp) fclose(fp); fprintf(stderr, "--truth %s is not a readable P5 image\n", path); return 2; }
+    if (v[0] != width || v[1] != height) {
+        fclose(fp);
+        fprintf(stderr, "--truth %s is %d x %d, its image %d x %d\n", path, v[0], v[1], width, height);
+        return 2;
+    }
+    *wide = v[2] > 255;
+    for (long i = 0; ok && i < (long)width * height; i++) {
+        const int hi = *wide ? fgetc(fp) : 0, lo = fgetc(fp);
+        ok = hi != EOF && lo != EOF;
+        out[i] = (hi << 8) | lo;
+    }
+    fclose(fp);
+    if (!ok) { fprintf(stderr, "--truth %s ends before its last pixel\n", path); return 2; }
+    return 0;
+}
+
+/* --truth: scores the label maps the segment call just wrote at d_labels (image n at element dst[n]) against the files, and prints the line */
+static int score_truth(mbn_context *ctx, mbn_net *net, const char **truths, int n, const int64_t *dst, const int32_t *hs, const int32_t *ws, size_t pixels,
+                       void *d_labels, int classes)
+{
+    int32_t *tv = calloc(pixels, sizeof(int32_t));
+    if (!tv) return 1;
+    int any_wide = 0;
+    for (int i = 0; i < n; i++) {
+        int wide = 0;
+        const int bad = read_truth_pgm(truths[i], ws[i], hs[i], tv + dst[i], &wide);
+        if (bad) return bad;
+        any_wide |= wide;
+    }
+    unsigned char *t8 = NULL;
+    if (!any_wide) {                                            /* every file has a byte per pixel: uint8 truth */
+        t8 = malloc(pixels);
+        if (!t8) return 1;
+        for (size_t i = 0; i < pixels; i++) t8[i] = (unsigned char)tv[i];
+    }
+    const int tb = any_wide ? 4 : 1;
+    const size_t cells = ((size_t)classes + 1) * ((size_t)classes + 1);
+    uint64_t *counts = malloc(cells * sizeof(uint64_t));
+    double *iou = malloc((size_t)classes * sizeof(double));
+    if (!counts || !iou) return 1;
+    void *d_truth, *d_counts;
+    CHECK(mbn_alloc(ctx, pixels * (size_t)tb, &d_truth));
+    CHECK(mbn_alloc(ctx, cells * sizeof(uint64_t), &d_counts));
+    CHECK(mbn_upload(ctx, d_truth, any_wide ? (const void *)tv : (const void *)t8, pixels * (size_t)tb));
+    CHECK(mbn_memset(ctx, d_counts, 0, cells * sizeof(uint64_t)));
+    CHECK(mbn_net_segment_score(net, d_labels, d_truth, tb, d_counts));
+    CHECK(mbn_download(ctx, counts, d_counts, cells * sizeof(uint64_t)));
+    CHECK(mbn_free(ctx, d_truth));
+    CHECK(mbn_free(ctx, d_counts));
+    mbn_seg_metrics m;
+    CHECK(mbn_confusion_metrics(counts, classes, &m, iou));
+    printf("score: pixels=%.0f valid=%.0f void=%.0f abstained=%.0f classes_present=%d pixel_acc=%.17g mean_acc=%.17g miou=%.17g fw_iou=%.17g\n", m.pixels,
+           m.valid, m.void_pixels, m.abstained, m.classes_present, m.pixel_accuracy, m.mean_accuracy, m.miou, m.fw_iou);
+    free(tv); free(t8); free(counts); free(iou);
+    return 0;
+}
+
 /* --segment-confidence: image 0's probability map [rows][cols] as an 8-bit P5, byte = floor(prob * 255 + 0.5) */
 static int write_confidence_map(const char *path, const float *prob, int rows, int cols)
 {
@@ -428,9 +508,10 @@ static int write_confidence_map(const char *path, const float *prob, int rows, i
  * conf_path (--segment-confidence) or ignore >= 0 (--min-confidence with --ignore-label): the softmax read-out instead, mbn_net_segment_prob_fit /
  * mbn_net_segment_prob_images_fit: image 0's probability map as an 8-bit P5, byte = floor(prob * 255 + 0.5), and the label map with the pixels
  * below min_conf replaced by `ignore`. path may then be NULL (no label map asked for).
- * n_views > 0 (--tta-scales; one file, --fit pad): mbn_net_segment_views_fit over the views (scales[k], mirrors[k]) instead, either read-out */
+ * n_views > 0 (--tta-scales; one file, --fit pad): mbn_net_segment_views_fit over the views (scales[k], mirrors[k]) instead, either read-out.
+ * n_truth > 0 (--truth, one per image): the maps are scored against them on the device before anything is written */
 static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int n_ppm, const char *path, int classes, int fit, const char *conf_path,
-                          float min_conf, int ignore, const float *scales, const int32_t *mirrors, int n_views)
+                          float min_conf, int ignore, const float *scales, const int32_t *mirrors, int n_views, const char **truths, int n_truth)
 {
     int64_t *offs = malloc(sizeof(int64_t) * (size_t)n_ppm), *dst = malloc(sizeof(int64_t) * (size_t)n_ppm);
     int32_t *hs = malloc(sizeof(int32_t) * (size_t)n_ppm), *ws = malloc(sizeof(int32_t) * (size_t)n_ppm);
@@ -479,6 +560,10 @@ static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int
     }
     CHECK(mbn_download(ctx, labels, d_labels, sizeof(int) * (size_t)hs[0] * ws[0]));      /* image 0 is first in the buffer */
     int bad = 0;
+    if (n_truth > 0) {                                          /* the maps are where every path above wrote them: image n at element dst[n] */
+        bad = score_truth(ctx, net, truths, n_truth, dst, hs, ws, pixels, d_labels, classes);
+        if (bad) return bad;
+    }
     if (conf_path) {
         float *prob = malloc(sizeof(float) * (size_t)hs[0] * ws[0]);
         if (!prob) return 1;
@@ -543,8 +628,9 @@ int main(int argc, char **argv)
     if (argc == 3 && !strcmp(argv[1], "--inspect")) return inspect_h5(argv[2]);
     if (argc == 4 && !strcmp(argv[1], "--convert")) return convert_h5(argv[2], argv[3]);
     const char **ppms = malloc(sizeof(char *) * (size_t)argc);          /* every --ppm, in order */
-    int n_ppm = 0;
-    if (!ppms) return 1;
+    const char **truths = malloc(sizeof(char *) * (size_t)argc);        /* every --truth, in order */
+    int n_ppm = 0, n_truth = 0;
+    if (!ppms || !truths) return 1;
     const char *h5 = NULL, *ppm = NULL, *segment = NULL, *segment_src = NULL, *segment_conf = NULL, *wfile = "weights_c.txt", *image = "Cat_Image0.ppm";
     int fit = MBN_FIT_CROP, filter = MBN_FILTER_BILINEAR;
     int pad_rgb[3] = { 0, 0, 0 }, src_h0 = 0, src_w0 = 0;              /* src_h0 x src_w0: image 0 as it was resized (0: it was not) */
@@ -578,6 +664,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--ignore-label") && i + 1 < argc) { ignore_label = atoi(argv[++i]); have_ignore = 1; }
         else if (!strcmp(argv[i], "--tta-scales") && i + 1 < argc) tta = argv[++i];
         else if (!strcmp(argv[i], "--tta-flip")) tta_flip = 1;
+        else if (!strcmp(argv[i], "--truth") && i + 1 < argc) truths[n_truth++] = argv[++i];
         else if (!strcmp(argv[i], "--fit") && i + 1 < argc && fit_of(argv[i + 1]) >= 0) fit = fit_of(argv[++i]);
         else if (!strcmp(argv[i], "--pad-color") && i + 1 < argc && pad_color_of(argv[i + 1], pad_rgb)) i++;
         else if (!strcmp(argv[i], "--crop-fraction") && i + 1 < argc) crop_fraction = (float)atof(argv[++i]);
@@ -594,7 +681,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--literal")) literal = 1;
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
-            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]]] [--segment-confidence OUT.pgm] "
+            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]] [--truth F.pgm ...]] [--segment-confidence OUT.pgm] "
                             "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n", argv[0]);
             return 2;
         }
@@ -624,6 +711,10 @@ int main(int argc, char **argv)
         }
         for (int k = 0; k < n_scales; k++)
             for (int m = 0; m <= tta_flip; m++) { view_scales[n_views] = tta_scales[k]; view_mirrors[n_views++] = m; }
+    }
+    if (n_truth > 0 && (!segment_src || n_truth != n_ppm)) {
+        fprintf(stderr, "--truth F.pgm needs --segment-source and comes once per --ppm, in the same order\n");
+        return 2;
     }
     if (have_min_conf != have_ignore || (have_min_conf && !segment_src)) {
         fprintf(stderr, "--min-confidence P and --ignore-label L come together and with --segment-source\n");
@@ -782,12 +873,12 @@ int main(int argc, char **argv)
     }
     if (segment_src || segment_conf) {
         const int bad = segment_source(ctx, net, ppms, n_ppm, segment_src, classes, fit, segment_conf, min_conf, have_ignore ? ignore_label : -1,
-                                       view_scales, view_mirrors, n_views);
+                                       view_scales, view_mirrors, n_views, truths, n_truth);
         if (bad) return bad;
     }
     mbn_net_destroy(net);
     mbn_weights_free(&w);
     mbn_shutdown(ctx);
-    free(u8); free(arg); free(probs); free(ppms);
+    free(u8); free(arg); free(probs); free(ppms); free(truths);
     return 0;
 }

@@ -523,6 +523,52 @@ typedef struct mbn_view { int32_t x, y, iw, ih; int32_t mirror; int32_t reserved
 int mbn_resample_ensemble_f32(mbn_context *ctx, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, int batch, int rows, int cols,
                               int classes, int in_rows, int in_cols, const mbn_view *views, int n_views, int out_rows, int out_cols, float min_prob,
                               int ignore_label, void *stream);
+/* Score a segmentation: the confusion matrix of the label maps the read-outs above write against a ground truth, accumulated on the device, and
+ * the standard metrics of such a matrix on the host. The dense counterpart of mbn_softmax_topk_f32.
+ * Normative (tests/confusion_ref.py reproduces it in numpy; the arithmetic is integer, so every result is exact and does not depend on the order
+ * in which the device's atomics arrive):
+ *   counts is uint64_t [classes + 1][classes + 1], row-major, on 8 bytes. The ROW is the truth; row `classes` is VOID: a truth value outside
+ *     [0, classes), for example the usual 255. The COLUMN is the prediction; column `classes` is ABSTAINED: a label outside [0, classes): the
+ *     ignore_label the thresholded read-outs store, and any other int32, negative values included.
+ *   Every pixel adds exactly 1 to exactly one cell. The call ADDS to counts: the caller clears it (mbn_memset) and a dataset accumulates over many
+ *     calls. After any sequence of calls the sum of all cells equals the number of pixels scored.
+ *   Truth is uint8 (truth_bytes = 1) or int32 (truth_bytes = 4). A uint8 value v goes to row v < classes ? v : classes; an int32 value likewise,
+ *     negative values to the void row.
+ *   mbn_confusion_i32         `count` pixels: labels_i32 [count], truth [count]. labels_i32 may be any pointer on 4 bytes, a uint8 truth any byte
+ *                             pointer, an int32 truth any pointer on 4 bytes, independently of each other. ONE kernel, asynchronous on `stream`
+ *                             (NULL: the context's); it may be captured as one kernel node. The grid is persistent, sized from the planning CU
+ *                             count (mbn_set_planning_cus); the counts are the same at every planning count
+ *   mbn_confusion_ragged_i32  the maps of a ragged set: the pixels of item i are labels_i32 [dst_offset_i .. + rows_i * cols_i) and truth uses the
+ *                             SAME element offsets; nothing between the maps is read. After either kind of set (the 16-byte and the 32-byte items
+ *                             share their first 16 bytes). ONE kernel; it keeps the handle's generation rule (a captured launch replayed after a
+ *                             later set does nothing) and the next set waits for it. `classes` is the call's and need not be the set's
+ * MBN_EINVAL: a NULL pointer, counts_u64 off 8 bytes, labels_i32 off 4, an int32 truth off 4, classes < 1, count < 1, truth_bytes not 1 or 4, a
+ * handle without a set, or an undersized tracked buffer (mbn_alloc's bounds rule: counts_u64 spans (classes + 1)^2 * 8 bytes; labels_i32 and
+ * truth span `count` elements, in the ragged form max(dst_offset + rows * cols)). MBN_EUNSUPPORTED: classes > MBN_CONFUSION_MAX_CLASSES or
+ * count > 2^34. Nothing is launched on a refusal. mbn_confusion_envelope answers the shape part; mbn_confusion_form says which form of the kernel
+ * a class count takes (0: a workgroup counts in LDS; 1: global atomics only; monotone, one switch point). Both are pure host functions.
+ *   mbn_confusion_metrics     pure C in doubles, exact for counts below 2^53. n = counts, C = classes:
+ *     valid = the sum of rows t < C over all columns; void_pixels = the sum of row C; abstained = sum over t < C of n[t][C]; pixels = valid + void.
+ *     For class c: tp = n[c][c]; fn = (sum of row c) - tp (the abstained column counts as a miss); fp = sum over t < C, t != c of n[t][c] (the
+ *     void row is excluded). iou_c = tp / (tp + fp + fn); a class is PRESENT iff that denominator is > 0, otherwise iou_c = NaN.
+ *     pixel_accuracy = sum of tp / valid (0 when valid = 0); miou = the mean of iou_c over the present classes (0 when there are none);
+ *     mean_accuracy = the mean of tp / (tp + fn) over the classes with tp + fn > 0 (0 when there are none);
+ *     fw_iou = sum over the present classes of ((tp + fn) / valid) * iou_c; classes_present = the number of present classes.
+ *     Every ratio is one division of exact integers; the means are summed in ascending class order. iou: [classes] or NULL.
+ *     MBN_EINVAL: NULL counts or m, classes < 1; MBN_EUNSUPPORTED: classes > MBN_CONFUSION_MAX_CLASSES. */
+#define MBN_CONFUSION_MAX_CLASSES 4096
+typedef struct mbn_seg_metrics {
+    double pixels, valid, void_pixels, abstained;
+    double pixel_accuracy, mean_accuracy, miou, fw_iou;
+    int32_t classes_present, reserved;
+} mbn_seg_metrics;
+int mbn_confusion_i32(mbn_context *ctx, void *counts_u64, const void *labels_i32, const void *truth, int truth_bytes, int classes, int64_t count,
+                      void *stream);
+int mbn_confusion_ragged_i32(mbn_ragged_readout *r, void *counts_u64, const void *labels_i32, const void *truth, int truth_bytes, int classes,
+                             void *stream);
+int mbn_confusion_envelope(int classes, int truth_bytes, int64_t count);
+int mbn_confusion_form(int classes);
+int mbn_confusion_metrics(const uint64_t *counts, int classes, mbn_seg_metrics *m, double *iou);
 /* The classifier tail of the sequence as one call (MobileNet.c:2601-2792): global average pool (kernel.cl:116) ->
  * FC = pointwise with rows = cols = 1 (kernel.cl:94; bias, no ReLU: B15) -> softmax + top-k. fp32 NHWC,
  * in [batch][rows][cols][channels], fc_w [classes][channels], fc_bias [classes] or NULL; pooled_scratch
@@ -1088,6 +1134,13 @@ int  mbn_net_resize_views(mbn_net *net, const void *src_u8, int batch, int in_ro
                           int n_views, void **staged);
 int  mbn_net_segment_views_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, const float *scales, const int32_t *mirrors,
                                int n_views, void *labels_i32, void *prob_f32, void *score_f32, float min_prob, int ignore_label);
+/* Score the label maps of the net's most recent SUCCESSFUL source-size segment call (mbn_net_segment, _segment_to, _segment_fit, _segment_images,
+ * _segment_images_fit, the three _segment_prob_ calls, _segment_views_fit) against `truth` (uint8 or int32, truth_bytes 1 or 4; "score a
+ * segmentation" above): a uniform call is one span of batch * out_rows * out_cols pixels (mbn_confusion_i32), an image call the net's own ragged
+ * set (mbn_confusion_ragged_i32: truth at the labels' dst_offsets). classes is the plan's; counts_u64 [classes + 1][classes + 1] is added to.
+ * labels_i32 is the buffer that call wrote (or a copy of it). MBN_EINVAL before any such call; a refused segment call leaves the record of the
+ * one before in place. Otherwise whatever the confusion call answers. */
+int  mbn_net_segment_score(mbn_net *net, const void *labels_i32, const void *truth, int truth_bytes, void *counts_u64);
 /* Per-layer milliseconds of the most recent mbn_net_forward_timed call (hipEvents between layers). */
 int  mbn_net_forward_timed(mbn_net *net, const void *images, void *logits, int batch, float *layer_ms,
                            int n_layer_ms);

@@ -28,6 +28,10 @@
   python tools/dense_bench.py --ensemble 1,2,3,6 [--reps 7] [--steps 20] [--batch 32] [--torch-steps 1] [--no-torch]
       mbn_resample_ensemble_f32, the fused multi-view read-out (main_ensemble): per view count K against the unchanged window kernel on one view,
       against K launches of it, and against torch's sum of K interpolate(...) then argmax / softmax(1).max(1), argmax and --prob forms alike.
+
+  python tools/dense_bench.py --score [--reps 7] [--steps 20] [--batch 32] [--no-torch]
+      mbn_confusion_i32, the confusion matrix of --batch label maps of 375 x 500 against a uint8 truth (main_score): 21 / 150 / 1000 classes,
+      random and piecewise-constant inputs, beside torch.bincount on the same buffers.
 """
 import argparse
 import json
@@ -419,6 +423,91 @@ def main_ensemble(a):
     print(json.dumps(result))
 
 
+def main_score(a):
+    """--score: mbn_confusion_i32 on --batch maps of 375 x 500 (6 M pixels at 32), int32 labels against uint8 truth, at 21 / 150 / 1000 classes
+    (the LDS form with two workgroups a CU, the LDS form at its largest table, the global form). Three inputs per class count:
+      random     labels and truth uniform over the classes (the truth over min(classes, 256)): no two neighbours agree, every add is its own
+      blocks     piecewise constant: blocks of 25 x 25 pixels of one class, the prediction = the truth shifted by one pixel along the row: what a
+                 label map looks like, and what the wave aggregation is for
+      constant   one (truth, label) pair everywhere: every wave is uniform, one add per wave and chunk; what is left is the loads and the launch
+    Per cell, alternating within every repetition: the kernel (counts cleared once in front; it accumulates) and torch's route on the SAME device
+    buffers, conversions included: torch.bincount(t.long() * (C + 1) + p.long(), minlength=(C + 1) ** 2). The counts of the two routes are compared
+    once. Each figure is the median over the repetitions of `steps` back-to-back calls between two stream marks (torch: two torch events); the runs
+    are kept, the spread is (max - min) / median. share_of_hbm: 5 bytes a pixel over the kernel's time against 8 TB/s."""
+    pkg = import_package()
+    torch = None
+    if not a.no_torch:
+        import torch
+        assert torch.cuda.is_available(), "the yardstick needs torch on the same GPU"
+    n, H, W = a.batch, 375, 500
+    pix = n * H * W
+    rng = np.random.default_rng(0)
+    result = {"batch": n, "pixels": pix, "bytes_per_pixel": 5}
+    with pkg.Context(0) as ctx:
+        for classes in (21, 150, 1000):
+            tc = min(classes, 256)
+            yy, xx = np.mgrid[0:H, 0:W]
+            blocks = rng.integers(0, tc, (n, H // 25 + 1, W // 25 + 2))
+            tr_b = blocks[:, yy // 25, xx // 25]
+            lab_b = blocks[:, yy // 25, (xx + 1) // 25]
+            inputs = {"random": (rng.integers(0, classes, pix).astype(np.int32), rng.integers(0, tc, pix).astype(np.uint8)),
+                      "blocks": (lab_b.astype(np.int32).ravel(), tr_b.astype(np.uint8).ravel()),
+                      "constant": (np.full(pix, classes - 1, np.int32), np.full(pix, tc - 1, np.uint8))}
+            cells = (classes + 1) ** 2
+            d_n = ctx.alloc(cells * 8)
+            for name, (lab, tr) in inputs.items():
+                if torch is not None:
+                    t_lab, t_tr = torch.from_numpy(lab).cuda(), torch.from_numpy(tr).cuda()
+                    p_lab, p_tr = t_lab.data_ptr(), t_tr.data_ptr()
+                else:
+                    t_lab, t_tr = ctx.to_device(lab), ctx.to_device(tr)
+                    p_lab, p_tr = t_lab.ptr, t_tr.ptr
+                ctx.lib.mbn_memset(ctx.h, d_n.ptr, 0, cells * 8)
+                fn = lambda: ctx.confusion(d_n.ptr, p_lab, p_tr, 1, classes, pix)
+                fn()
+                ctx.sync()
+                once = d_n.download((cells,), np.uint64)
+                assert int(once.sum()) == pix
+                agree = None
+                if torch is not None:
+                    route = lambda: torch.bincount(t_tr.long() * (classes + 1) + t_lab.long(), minlength=cells)
+                    agree = bool(np.array_equal(route().cpu().numpy().astype(np.uint64), once))
+                marks_ms(ctx, fn, 2)
+                ks, ts = [], []
+                for _ in range(a.reps):
+                    ks.append(marks_ms(ctx, fn, a.steps))
+                    if torch is None:
+                        continue
+                    ctx.sync()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(a.steps):
+                        route()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    ts.append(e0.elapsed_time(e1) / a.steps)
+                k = statistics.median(ks)
+                out = {"form": "lds" if pkg.confusion_form(classes) == pkg.CONFUSION_FORM_LDS else "global", "kernel_ms": round(k, 4),
+                       "kernel_runs_ms": [round(v, 4) for v in ks], "spread": round((max(ks) - min(ks)) / k, 4),
+                       "share_of_hbm": round(5.0 * pix / (k * 1e-3) / HBM_BYTES_PER_S, 4), "nonzero_cells": int((once != 0).sum())}
+                if ts:
+                    tm = statistics.median(ts)
+                    out.update({"torch_ms": round(tm, 4), "torch_runs_ms": [round(v, 4) for v in ts], "torch_over_kernel": round(tm / k, 2),
+                                "counts_equal_torch": agree})
+                print("classes %4d %-6s (%s): kernel %.4f ms (spread %.1f %%, %.1f %% of 8 TB/s at 5 B/pixel)  torch %s ms" %
+                      (classes, name, out["form"], k, 100 * out["spread"], 100 * out["share_of_hbm"], ("%.4f" % out["torch_ms"]) if ts else "-"),
+                      flush=True)
+                result["classes_%d_%s" % (classes, name)] = out
+                if torch is not None:
+                    del t_lab, t_tr
+                    torch.cuda.empty_cache()
+                else:
+                    t_lab.free()
+                    t_tr.free()
+            d_n.free()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
@@ -431,7 +520,10 @@ def main():
     ap.add_argument("--fit", default="stretch", choices=("stretch", "pad"), help="--any: pad times the window kernel instead: see main_any_pad")
     ap.add_argument("--prob", action="store_true", help="--any: time the softmax read-out beside the argmax read-out instead: see main_prob")
     ap.add_argument("--ensemble", default="", help="comma list of view counts: time mbn_resample_ensemble_f32 instead: see main_ensemble")
+    ap.add_argument("--score", action="store_true", help="time mbn_confusion_i32 beside torch.bincount instead: see main_score")
     a = ap.parse_args()
+    if a.score:
+        return main_score(a)
     if a.ensemble:
         return main_ensemble(a)
     if a.any and a.prob:
