@@ -120,6 +120,14 @@ class SegMetrics(C.Structure):
                 ("classes_present", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Region(C.Structure):
+    """mbn_region (include/mbn.h, "regions of a label map"): eight int32"""
+    _fields_ = [(n, C.c_int32) for n in ("label", "area", "first_row", "first_col", "min_row", "min_col", "max_row", "max_col")]
+
+
+REGION_DTYPE = np.dtype([(n, np.int32) for n in ("label", "area", "first_row", "first_col", "min_row", "min_col", "max_row", "max_col")])
+
+
 class ResampleLaunch(C.Structure):
     """mbn_resample_launch_t (host/mbn_envelope.h): LDS footprint, class chunk, dynamic LDS, grid.x and output span of a read-out launch"""
     _fields_ = [(n, C.c_int32) for n in ("fy", "fx", "ch", "lds_bytes", "tiles")] + [("span", C.c_int64)]
@@ -222,6 +230,10 @@ def _declare_host(lib):
     lib.mbn_confusion_envelope.argtypes = [C.c_int, C.c_int, C.c_int64]
     lib.mbn_confusion_form.argtypes = [C.c_int]
     lib.mbn_confusion_metrics.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.POINTER(SegMetrics), C.POINTER(C.c_double)]
+    lib.mbn_components_envelope.argtypes = [C.c_int] * 7
+    lib.mbn_components_tile.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.mbn_components_scratch_bytes.argtypes = [C.c_int, C.c_int64]
+    lib.mbn_components_scratch_bytes.restype = C.c_int64
     i32p = C.POINTER(C.c_int32)
     lib.mbn_resize_ksize.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int]
     lib.mbn_resize_taps.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int, i32p, i32p, i32p]
@@ -378,6 +390,11 @@ def load():
         lib.mbn_confusion_i32.argtypes = [vp, vp, vp, vp, ci, ci, C.c_int64, vp]
         lib.mbn_confusion_ragged_i32.argtypes = [vp, vp, vp, vp, ci, ci, vp]
         lib.mbn_net_segment_score.argtypes = [vp, vp, vp, ci, vp]
+        lib.mbn_components_create.argtypes = [vp, ci, C.c_int64, C.POINTER(vp)]
+        lib.mbn_components_destroy.argtypes = [vp]
+        lib.mbn_components_i32.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]
+        lib.mbn_components_ragged_i32.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
+        lib.mbn_net_segment_regions.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci]
         lib.mbn_resizer_create.argtypes = [vp, ci, ci, C.POINTER(C.c_float), ci, ci, C.POINTER(vp)]
         lib.mbn_resize_u8.argtypes = [vp, vp, vp, ci, vp]
         lib.mbn_resizer_destroy.argtypes = [vp]
@@ -677,6 +694,26 @@ def confusion_metrics(counts, classes, lib=None):
     return m, iou
 
 
+COMPONENTS_MAX_REGIONS = 1 << 24
+
+
+def components_envelope(batch, rows, cols, classes, connectivity=4, min_area=1, max_regions=0, lib=None) -> int:
+    """mbn_components_envelope: the status (OK, EINVAL or EUNSUPPORTED) mbn_components_i32 gives the shape."""
+    return (lib or host_lib()).mbn_components_envelope(batch, rows, cols, classes, connectivity, min_area, max_regions)
+
+
+def components_tile(lib=None):
+    """mbn_components_tile: (tile_rows, tile_cols) of the first kernel: a seam of the union-find lies at every multiple of them."""
+    tr, tc = C.c_int(), C.c_int()
+    _chk((lib or host_lib()).mbn_components_tile(C.byref(tr), C.byref(tc)), "components_tile")
+    return tr.value, tc.value
+
+
+def components_scratch_bytes(max_batch, max_pixels, lib=None) -> int:
+    """mbn_components_scratch_bytes: the device memory a Components handle of that size holds (0: a size mbn_components_create refuses)."""
+    return (lib or host_lib()).mbn_components_scratch_bytes(max_batch, max_pixels)
+
+
 def declared_symbols():
     """Every function name declared in include/mbn.h (for the export test)."""
     import re
@@ -915,11 +952,43 @@ class Context:
         """mbn_confusion_ragged_i32: the same over the maps of a RaggedReadout's set; truth at the labels' element offsets."""
         _chk(self.lib.mbn_confusion_ragged_i32(readout.h, counts, labels, truth, truth_bytes, classes, stream), self.last_error())
 
+    def components(self, handle, labels, batch, rows, cols, classes, n_regions, comp=None, regions=None, labels_out=None, connectivity=4,
+                   min_area=1, ignore_label=0, max_regions=0, stream=None):
+        """mbn_components_i32: the regions of int32 maps [batch][rows][cols] (device pointers): comp (region number per pixel, -1: none),
+        regions (Region [batch][max_regions]), n_regions (int32 [batch], the true counts), labels_out (the maps without the dropped regions)."""
+        _chk(self.lib.mbn_components_i32(handle.h, comp, regions, n_regions, labels_out, labels, batch, rows, cols, classes, connectivity, min_area,
+                                         ignore_label, max_regions, stream), self.last_error())
+
+    def components_ragged(self, handle, readout, labels, classes, n_regions, comp=None, regions=None, labels_out=None, connectivity=4, min_area=1,
+                          ignore_label=0, max_regions=0, stream=None):
+        """mbn_components_ragged_i32: the same over the maps of a RaggedReadout's set; comp and labels_out at the labels' element offsets."""
+        _chk(self.lib.mbn_components_ragged_i32(handle.h, readout.h, comp, regions, n_regions, labels_out, labels, classes, connectivity, min_area,
+                                                ignore_label, max_regions, stream), self.last_error())
+
     def __enter__(self):
         return self
 
     def __exit__(self, *a):
         self.close()
+
+
+class Components:
+    """mbn_components_create: the scratch of the connected-component kernels for up to max_batch maps of max_pixels pixels in all, allocated once;
+    the `handle` of Context.components / components_ragged."""
+
+    def __init__(self, ctx: Context, max_batch, max_pixels):
+        self.ctx = ctx
+        h = C.c_void_p()
+        _chk(ctx.lib.mbn_components_create(ctx.h, max_batch, max_pixels, C.byref(h)), ctx.last_error())
+        self.h = h
+        if not hasattr(ctx, "_resizers"):
+            ctx._resizers = []
+        ctx._resizers.append(self)
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.mbn_components_destroy(self.h)
+            self.h = None
 
 
 class RaggedReadout:
@@ -1231,6 +1300,13 @@ class Net:
         """mbn_net_segment_score: counts (uint64 [classes + 1][classes + 1]) += the confusion matrix of the maps the most recent successful
         source-size segment call wrote against truth (uint8 or int32, at the labels' element offsets)."""
         _chk(self.ctx.lib.mbn_net_segment_score(self.h, labels_ptr, truth_ptr, truth_bytes, counts_ptr), self.ctx.last_error())
+
+    def segment_regions(self, labels_ptr, n_regions_ptr, comp_ptr=None, regions_ptr=None, labels_out_ptr=None, connectivity=4, min_area=1,
+                        ignore_label=0, max_regions=0):
+        """mbn_net_segment_regions: the regions of the maps the most recent successful source-size segment call wrote (Context.components, or
+        components_ragged on the net's own set after an image call); classes is the plan's."""
+        _chk(self.ctx.lib.mbn_net_segment_regions(self.h, labels_ptr, comp_ptr, regions_ptr, n_regions_ptr, labels_out_ptr, connectivity, min_area,
+                                                  ignore_label, max_regions), self.ctx.last_error())
 
     def resize_input(self, src_ptr, batch, in_rows, in_cols, fit=FIT_CROP, crop_fraction=1.0) -> int:
         """mbn_net_resize_input: uint8 images [batch][in_rows][in_cols][3] of any size -> the net's staging buffer [batch][rows][cols][3] (its

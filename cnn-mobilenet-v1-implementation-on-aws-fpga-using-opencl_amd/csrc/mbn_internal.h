@@ -66,6 +66,21 @@ struct mbn_ragged_readout {
     hipEvent_t done = nullptr;                   // behind the last upload or launch: the next set waits for it
 };
 
+// mbn_components_create's handle (mbn_i32_components.hip): the scratch of the seven kernels, allocated once
+struct mbn_components {
+    mbn_context *ctx = nullptr;
+    int max_batch = 0;
+    int64_t max_pixels = 0;
+    void *scratch = nullptr;                     // parent [max_pixels], area / rank [max_pixels], chunk counts [max_pixels / CHUNK + max_batch], int32
+};
+
+// the live mbn_components_create handles of a context. Its destructor (mbn_i32_components.hip) frees the stragglers when mbn_shutdown deletes
+// the context
+struct mbn_components_list {
+    std::vector<mbn_components *> live;
+    ~mbn_components_list();
+};
+
 struct mbn_context {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -90,6 +105,7 @@ struct mbn_context {
     std::vector<mbn_resizer *> resizers;         // live mbn_resizer_create handles (mbn_shutdown frees the stragglers)
     std::vector<mbn_ragged_resizer *> ragged_resizers;   // live mbn_ragged_resizer_create handles, likewise
     std::vector<mbn_ragged_readout *> ragged_readouts;   // live mbn_ragged_readout_create handles, likewise
+    mbn_components_list components;              // live mbn_components_create handles (freed with the context)
     std::mutex mu;
     std::map<uintptr_t, size_t> allocs;          // buffers handed out by mbn_alloc: base address -> bytes (ordered: mbn_span_check
                                                  // finds the allocation that CONTAINS an interior pointer)

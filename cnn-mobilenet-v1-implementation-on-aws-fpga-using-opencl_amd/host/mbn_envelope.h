@@ -133,6 +133,15 @@ int mbn_resample_ensemble_plan(int rows, int cols, int in_rows, int in_cols, con
 #define MBN_CONFUSION_FORM_GLOBAL 1
 int mbn_confusion_envelope(int classes, int truth_bytes, int64_t count);
 int mbn_confusion_form(int classes);
+/* regions of a label map (mbn_i32_components.hip, host/mbn_regions.c; the functions are declared in mbn.h). MBN_COMPONENTS_TILE_ROWS x _COLS: the
+ * tile a workgroup of the first kernel labels in LDS; MBN_COMPONENTS_CHUNK: the pixels of one unit of the flatten, numbering and write kernels, and
+ * of one count of the two-level scan; MBN_COMPONENTS_MAX_PIXELS: what one handle may hold; an image stays below MBN_COMPONENTS_MAX_MAP pixels
+ * (2^31 bytes of int32) */
+#define MBN_COMPONENTS_TILE_ROWS 32
+#define MBN_COMPONENTS_TILE_COLS 64
+#define MBN_COMPONENTS_CHUNK 1024
+#define MBN_COMPONENTS_MAX_PIXELS ((int64_t)1 << 34)
+#define MBN_COMPONENTS_MAX_MAP ((int64_t)1 << 29)
 /* resize front-end (mbn_u8_resize.hip): one geometry of mbn_resizer_create. Source sides 1..8192, output sides 1..4096, at most MBN_RESIZE_MAX_KSIZE
  * taps per axis (a 32x downscale; any upscale has 3). box = (left, upper, right, lower), NULL = the whole image. MBN_EINVAL for a non-positive
  * size or a box mbn_resize_ksize refuses, else MBN_EUNSUPPORTED outside the limits. The batch (1..MBN_RESIZE_MAX_BATCH: grid.y) belongs to the call. */

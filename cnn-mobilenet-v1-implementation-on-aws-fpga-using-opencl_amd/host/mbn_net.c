@@ -63,7 +63,11 @@ struct mbn_net {
     mbn_ragged_readout *readout;    /* mbn_net_segment_images: one ragged read-out of max_batch images, made on the first call */
     void *label_items;              /* ... and the items it is set from, [max_batch] mbn_label_window_item (or as many mbn_label_item) */
     int score_kind;                 /* mbn_net_segment_score: what the last successful source-size segment call wrote: SCORE_NONE, _UNIFORM, _RAGGED */
-    int64_t score_count;            /* SCORE_UNIFORM: its batch * out_rows * out_cols pixels */
+    int64_t score_count;            /* SCORE_UNIFORM: its batch * out_rows * out_cols pixels; SCORE_RAGGED: the pixels of its maps */
+    int score_batch, score_rows, score_cols;   /* its batch, and SCORE_UNIFORM: the size of one map */
+    mbn_components *components;     /* mbn_net_segment_regions: one handle, made on first use and again when a call needs more */
+    int components_batch;           /* ... and what it holds */
+    int64_t components_pixels;
     /* mbn_net_resize_views: the view resizers kept, each made for one (source size, scale, mirror, filter, pad colour); used = the clock of its last use */
     struct view_slot {
         mbn_resizer *r;
@@ -171,6 +175,7 @@ int mbn_net_destroy(mbn_net *net)
         if (net->view_cache[i].r) mbn_resizer_destroy(net->view_cache[i].r);
     free(net->ragged_items);
     if (net->readout) mbn_ragged_readout_destroy(net->readout);
+    if (net->components) mbn_components_destroy(net->components);
     free(net->label_items);
     if (net->resize_buf) mbn_free(net->ctx, net->resize_buf);
     for (int j = 0; j < 8; j++)
@@ -917,13 +922,21 @@ enum { SCORE_NONE = 0, SCORE_UNIFORM = 1, SCORE_RAGGED = 2 };
 
 static int scored_uniform(mbn_net *net, int rc, int batch, int out_rows, int out_cols)
 {
-    if (rc == MBN_OK) { net->score_kind = SCORE_UNIFORM; net->score_count = (int64_t)batch * out_rows * out_cols; }
+    if (rc == MBN_OK) {
+        net->score_kind = SCORE_UNIFORM;
+        net->score_count = (int64_t)batch * out_rows * out_cols;
+        net->score_batch = batch; net->score_rows = out_rows; net->score_cols = out_cols;
+    }
     return rc;
 }
 
-static int scored_ragged(mbn_net *net, int rc)
+static int scored_ragged(mbn_net *net, int rc, int batch, int64_t pixels)
 {
-    if (rc == MBN_OK) net->score_kind = SCORE_RAGGED;
+    if (rc == MBN_OK) {
+        net->score_kind = SCORE_RAGGED;
+        net->score_count = pixels;
+        net->score_batch = batch; net->score_rows = net->score_cols = 0;
+    }
     return rc;
 }
 
@@ -1080,7 +1093,9 @@ static int segment_images_fit(mbn_net *net, const void *src_u8, const int64_t *o
     }
     /* a window item is a label item and then its rectangle: the first item_bytes of `it` are the item of either kind */
     const size_t item_bytes = fit == MBN_FIT_PAD ? sizeof(mbn_label_window_item) : sizeof(mbn_label_item);
+    int64_t pixels = 0;
     for (int i = 0; i < batch; i++) {
+        pixels += (int64_t)in_rows[i] * in_cols[i];
         int32_t rect[4] = { 0, 0, 0, 0 };
         if (fit == MBN_FIT_PAD) {
             rc = mbn_fit_pad(in_rows[i], in_cols[i], rows, cols, rect);
@@ -1103,8 +1118,8 @@ static int segment_images_fit(mbn_net *net, const void *src_u8, const int64_t *o
     if (rc != MBN_OK) return rc;
     if (q)
         return scored_ragged(net, mbn_resample_softmax_ragged_f32(net->readout, labels_i32, q->prob, NULL, net->dense_logits, q->min_prob,
-                                                                  q->ignore_label, NULL));
-    return scored_ragged(net, mbn_resample_argmax_ragged_f32(net->readout, labels_i32, score_f32, net->dense_logits, NULL));
+                                                                  q->ignore_label, NULL), batch, pixels);
+    return scored_ragged(net, mbn_resample_argmax_ragged_f32(net->readout, labels_i32, score_f32, net->dense_logits, NULL), batch, pixels);
 }
 
 int mbn_net_segment_images_fit(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *in_rows, const int32_t *in_cols, int batch,
@@ -1324,6 +1339,32 @@ int mbn_net_segment_score(mbn_net *net, const void *labels_i32, const void *trut
     if (rc != MBN_OK) return rc;
     if (net->score_kind == SCORE_RAGGED) return mbn_confusion_ragged_i32(net->readout, counts_u64, labels_i32, truth, truth_bytes, fc->out_ch, NULL);
     return mbn_confusion_i32(net->ctx, counts_u64, labels_i32, truth, truth_bytes, fc->out_ch, net->score_count, NULL);
+}
+
+int mbn_net_segment_regions(mbn_net *net, const void *labels_i32, void *comp_i32, mbn_region *regions, void *n_regions_i32, void *labels_out_i32,
+                            int connectivity, int min_area, int ignore_label, int max_regions)
+{
+    if (!net || net->score_kind == SCORE_NONE) return MBN_EINVAL;
+    const mbn_layer_desc *feat, *fc;
+    int rc = dense_layers(net, &feat, &fc);
+    if (rc != MBN_OK) return rc;
+    if (!net->components || net->score_batch > net->components_batch || net->score_count > net->components_pixels) {
+        /* the new handle first: when it cannot be had, the old one stays */
+        const int batch = net->score_batch > net->components_batch ? net->score_batch : net->components_batch;
+        const int64_t pixels = net->score_count > net->components_pixels ? net->score_count : net->components_pixels;
+        mbn_components *h = NULL;
+        rc = mbn_components_create(net->ctx, batch, pixels, &h);
+        if (rc != MBN_OK) return rc;
+        if (net->components) mbn_components_destroy(net->components);
+        net->components = h;
+        net->components_batch = batch;
+        net->components_pixels = pixels;
+    }
+    if (net->score_kind == SCORE_RAGGED)
+        return mbn_components_ragged_i32(net->components, net->readout, comp_i32, regions, n_regions_i32, labels_out_i32, labels_i32, fc->out_ch,
+                                         connectivity, min_area, ignore_label, max_regions, NULL);
+    return mbn_components_i32(net->components, comp_i32, regions, n_regions_i32, labels_out_i32, labels_i32, net->score_batch, net->score_rows,
+                              net->score_cols, fc->out_ch, connectivity, min_area, ignore_label, max_regions, NULL);
 }
 
 int mbn_net_forward_timed(mbn_net *net, const void *images, void *logits, int batch, float *layer_ms, int n_layer_ms)

@@ -31,6 +31,12 @@
  *   itself writes, int32 truth, so a label map this tool wrote can be fed back. The label maps are scored on the device (mbn_net_segment_score: a value
  *   outside the classes is void in the truth and abstained in the labels, --ignore-label among them) and ONE line is printed:
  *   score: pixels=... valid=... void=... abstained=... classes_present=... pixel_acc=... mean_acc=... miou=... fw_iou=... (mbn_confusion_metrics, %.17g)
+ *   --regions [--connectivity 4|8] [--min-area N] [--max-regions M] (with --segment-source; defaults 4, 1, 256): the connected regions of every label
+ *   map, found on the device (mbn_net_segment_regions). Per image one line `regions: image <n> count <k>` (k is the true count, even above M), then
+ *   for each of its first min(k, M) regions `region <i> class <c> area <a> box <r0> <c0> <r1> <c1>` (rows first, both corners inside the box), in
+ *   the order of the regions' first pixels. With --min-area N > 1 the regions of fewer than N pixels are dropped: the map written to --segment-source
+ *   and the map scored by --truth are the cleaned ones, whose dropped pixels hold --ignore-label (where --min-confidence brought one), else the class
+ *   count
  *   mobilenet --literal [--weights weights_c.txt] [--image Cat_Image0.ppm] [--ref-args]      the reference's own mode
  *   mobilenet --gpus G --batch N [--steps K --warmup W --streams S --pw-emul 6] (--h5 F | --synthetic SEED)  N images sharded over G GPUs
  *   mobilenet --inspect weights.h5                                                             list the datasets of a .h5
@@ -353,8 +359,9 @@ done:
 
 /* --segment: image 0's label map [rows][cols] as a binary PGM (P5), maxval = max(classes - 1, 1), two big-endian bytes per pixel beyond 255;
  * then one line with the (at most) five most frequent labels, 0-based, and their pixel counts, most frequent first (ties: lowest label).
- * ignore >= 0 (--ignore-label): a pixel that holds it is written as it is and counted apart; maxval then covers it too */
-static int write_label_map(const char *path, const int *labels, int rows, int cols, int classes, int ignore)
+ * ignore >= 0 (--ignore-label, or the label of the pixels --min-area dropped): a pixel that holds it is written as it is and counted apart (`why`
+ * says for what); maxval then covers it too */
+static int write_label_map(const char *path, const int *labels, int rows, int cols, int classes, int ignore, const char *why)
 {
     const int top = classes - 1 > ignore ? classes - 1 : ignore, maxval = top > 1 ? top : 1, wide = maxval > 255;
     long ignored = 0;
@@ -380,7 +387,7 @@ static int write_label_map(const char *path, const int *labels, int rows, int co
         printf(" %d (%ld)", best, count[best]);
         count[best] = 0;
     }
-    if (ignore >= 0) printf("; below --min-confidence: %ld pixels, label %d", ignored, ignore);
+    if (ignore >= 0) printf("; %s: %ld pixels, label %d", why, ignored, ignore);
     printf("\n");
     free(count);
     return bad;
@@ -487,6 +494,38 @@ static int score_truth(mbn_context *ctx, mbn_net *net, const char **truths, int 
     return 0;
 }
 
+/* --regions: what the command line asked for; on = 0: nothing */
+typedef struct region_opts { int on, connectivity, min_area, max_regions; } region_opts;
+
+/* --regions: the regions of the label maps the segment call just wrote at d_labels (n images), printed; *d_clean: with --min-area > 1 a new buffer
+ * with the cleaned maps at the same offsets (dropped pixels hold `ignore`), else NULL */
+static int print_regions(mbn_context *ctx, mbn_net *net, const region_opts *ro, int n, size_t pixels, void *d_labels, int ignore, void **d_clean)
+{
+    const size_t cap = (size_t)ro->max_regions;
+    mbn_region *table = malloc((cap ? cap : 1) * (size_t)n * sizeof(mbn_region));
+    int32_t *count = malloc((size_t)n * sizeof(int32_t));
+    if (!table || !count) return 1;
+    void *d_table = NULL, *d_count;
+    *d_clean = NULL;
+    if (cap) CHECK(mbn_alloc(ctx, cap * (size_t)n * sizeof(mbn_region), &d_table));
+    CHECK(mbn_alloc(ctx, (size_t)n * sizeof(int32_t), &d_count));
+    if (ro->min_area > 1) CHECK(mbn_alloc(ctx, pixels * sizeof(int32_t), d_clean));
+    CHECK(mbn_net_segment_regions(net, d_labels, NULL, (mbn_region *)d_table, d_count, *d_clean, ro->connectivity, ro->min_area, ignore, ro->max_regions));
+    CHECK(mbn_download(ctx, count, d_count, (size_t)n * sizeof(int32_t)));
+    if (cap) CHECK(mbn_download(ctx, table, d_table, cap * (size_t)n * sizeof(mbn_region)));
+    for (int i = 0; i < n; i++) {
+        printf("regions: image %d count %d\n", i, count[i]);
+        for (size_t k = 0; k < cap && k < (size_t)count[i]; k++) {
+            const mbn_region *g = &table[(size_t)i * cap + k];
+            printf("region %zu class %d area %d box %d %d %d %d\n", k, g->label, g->area, g->min_row, g->min_col, g->max_row, g->max_col);
+        }
+    }
+    if (d_table) CHECK(mbn_free(ctx, d_table));
+    CHECK(mbn_free(ctx, d_count));
+    free(table); free(count);
+    return 0;
+}
+
 /* --segment-confidence: image 0's probability map [rows][cols] as an 8-bit P5, byte = floor(prob * 255 + 0.5) */
 static int write_confidence_map(const char *path, const float *prob, int rows, int cols)
 {
@@ -509,9 +548,11 @@ static int write_confidence_map(const char *path, const float *prob, int rows, i
  * mbn_net_segment_prob_images_fit: image 0's probability map as an 8-bit P5, byte = floor(prob * 255 + 0.5), and the label map with the pixels
  * below min_conf replaced by `ignore`. path may then be NULL (no label map asked for).
  * n_views > 0 (--tta-scales; one file, --fit pad): mbn_net_segment_views_fit over the views (scales[k], mirrors[k]) instead, either read-out.
+ * ro->on (--regions): the regions of every map are printed first; with --min-area > 1 the cleaned maps take the place of the maps from there on.
  * n_truth > 0 (--truth, one per image): the maps are scored against them on the device before anything is written */
 static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int n_ppm, const char *path, int classes, int fit, const char *conf_path,
-                          float min_conf, int ignore, const float *scales, const int32_t *mirrors, int n_views, const char **truths, int n_truth)
+                          float min_conf, int ignore, const float *scales, const int32_t *mirrors, int n_views, const char **truths, int n_truth,
+                          const region_opts *ro)
 {
     int64_t *offs = malloc(sizeof(int64_t) * (size_t)n_ppm), *dst = malloc(sizeof(int64_t) * (size_t)n_ppm);
     int32_t *hs = malloc(sizeof(int32_t) * (size_t)n_ppm), *ws = malloc(sizeof(int32_t) * (size_t)n_ppm);
@@ -558,12 +599,24 @@ static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int
     } else {
         CHECK(mbn_net_segment_images(net, d_src, offs, hs, ws, n_ppm, d_labels, dst, NULL));
     }
-    CHECK(mbn_download(ctx, labels, d_labels, sizeof(int) * (size_t)hs[0] * ws[0]));      /* image 0 is first in the buffer */
     int bad = 0;
+    const char *why = "below --min-confidence";
+    void *d_maps = d_labels, *d_clean = NULL;                   /* the maps that are scored and written */
+    if (ro->on) {
+        bad = print_regions(ctx, net, ro, n_ppm, pixels, d_labels, ignore >= 0 ? ignore : classes, &d_clean);
+        if (bad) return bad;
+        if (d_clean) {
+            d_maps = d_clean;
+            why = ignore >= 0 ? "below --min-confidence or --min-area" : "below --min-area";
+            if (ignore < 0) ignore = classes;
+        }
+    }
+    CHECK(mbn_download(ctx, labels, d_maps, sizeof(int) * (size_t)hs[0] * ws[0]));        /* image 0 is first in the buffer */
     if (n_truth > 0) {                                          /* the maps are where every path above wrote them: image n at element dst[n] */
-        bad = score_truth(ctx, net, truths, n_truth, dst, hs, ws, pixels, d_labels, classes);
+        bad = score_truth(ctx, net, truths, n_truth, dst, hs, ws, pixels, d_maps, classes);
         if (bad) return bad;
     }
+    if (d_clean) CHECK(mbn_free(ctx, d_clean));
     if (conf_path) {
         float *prob = malloc(sizeof(float) * (size_t)hs[0] * ws[0]);
         if (!prob) return 1;
@@ -574,7 +627,7 @@ static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int
     }
     CHECK(mbn_free(ctx, d_src));
     CHECK(mbn_free(ctx, d_labels));
-    if (path) bad |= write_label_map(path, labels, hs[0], ws[0], classes, ignore);
+    if (path) bad |= write_label_map(path, labels, hs[0], ws[0], classes, ignore, why);
     free(all); free(labels); free(offs); free(dst); free(hs); free(ws);
     return bad;
 }
@@ -637,6 +690,8 @@ int main(int argc, char **argv)
     float crop_fraction = 1.0f, min_conf = 0.0f;
     int have_min_conf = 0, have_ignore = 0, ignore_label = -1;
     const char *tta = NULL;
+    region_opts regions = { 0, 4, 1, 256 };
+    int region_flags = 0;                                       /* --connectivity, --min-area or --max-regions seen */
     int tta_flip = 0, n_views = 0;
     float tta_scales[MBN_ENSEMBLE_MAX_VIEWS], view_scales[MBN_ENSEMBLE_MAX_VIEWS];
     int32_t view_mirrors[MBN_ENSEMBLE_MAX_VIEWS];
@@ -665,6 +720,10 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--tta-scales") && i + 1 < argc) tta = argv[++i];
         else if (!strcmp(argv[i], "--tta-flip")) tta_flip = 1;
         else if (!strcmp(argv[i], "--truth") && i + 1 < argc) truths[n_truth++] = argv[++i];
+        else if (!strcmp(argv[i], "--regions")) regions.on = 1;
+        else if (!strcmp(argv[i], "--connectivity") && i + 1 < argc) { regions.connectivity = atoi(argv[++i]); region_flags = 1; }
+        else if (!strcmp(argv[i], "--min-area") && i + 1 < argc) { regions.min_area = atoi(argv[++i]); region_flags = 1; }
+        else if (!strcmp(argv[i], "--max-regions") && i + 1 < argc) { regions.max_regions = atoi(argv[++i]); region_flags = 1; }
         else if (!strcmp(argv[i], "--fit") && i + 1 < argc && fit_of(argv[i + 1]) >= 0) fit = fit_of(argv[++i]);
         else if (!strcmp(argv[i], "--pad-color") && i + 1 < argc && pad_color_of(argv[i + 1], pad_rgb)) i++;
         else if (!strcmp(argv[i], "--crop-fraction") && i + 1 < argc) crop_fraction = (float)atof(argv[++i]);
@@ -681,7 +740,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--literal")) literal = 1;
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
-            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]] [--truth F.pgm ...]] [--segment-confidence OUT.pgm] "
+            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]] [--truth F.pgm ...] [--regions [--connectivity 4|8] [--min-area N] [--max-regions M]]] [--segment-confidence OUT.pgm] "
                             "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n", argv[0]);
             return 2;
         }
@@ -714,6 +773,15 @@ int main(int argc, char **argv)
     }
     if (n_truth > 0 && (!segment_src || n_truth != n_ppm)) {
         fprintf(stderr, "--truth F.pgm needs --segment-source and comes once per --ppm, in the same order\n");
+        return 2;
+    }
+    if ((regions.on || region_flags) && (!regions.on || !segment_src)) {
+        fprintf(stderr, "--regions needs --segment-source; --connectivity, --min-area and --max-regions need --regions\n");
+        return 2;
+    }
+    if (regions.on && ((regions.connectivity != 4 && regions.connectivity != 8) || regions.min_area < 1 || regions.max_regions < 0 ||
+                       regions.max_regions > MBN_COMPONENTS_MAX_REGIONS)) {
+        fprintf(stderr, "bad --connectivity (4 or 8), --min-area (N >= 1) or --max-regions (0 <= M <= %d)\n", MBN_COMPONENTS_MAX_REGIONS);
         return 2;
     }
     if (have_min_conf != have_ignore || (have_min_conf && !segment_src)) {
@@ -863,7 +931,7 @@ int main(int argc, char **argv)
         CHECK(mbn_alloc(ctx, sizeof(int) * (size_t)batch * rows * cols, &d_labels));
         CHECK(mbn_net_segment(net, d_u8, batch, d_labels, NULL));
         CHECK(mbn_download(ctx, labels, d_labels, sizeof(int) * (size_t)rows * cols));
-        const int bad = write_label_map(segment, labels, rows, cols, classes, -1);
+        const int bad = write_label_map(segment, labels, rows, cols, classes, -1, "");
         free(labels);
         if (bad) return 1;
         int32_t rect[4];
@@ -873,7 +941,7 @@ int main(int argc, char **argv)
     }
     if (segment_src || segment_conf) {
         const int bad = segment_source(ctx, net, ppms, n_ppm, segment_src, classes, fit, segment_conf, min_conf, have_ignore ? ignore_label : -1,
-                                       view_scales, view_mirrors, n_views, truths, n_truth);
+                                       view_scales, view_mirrors, n_views, truths, n_truth, &regions);
         if (bad) return bad;
     }
     mbn_net_destroy(net);

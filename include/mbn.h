@@ -569,6 +569,56 @@ int mbn_confusion_ragged_i32(mbn_ragged_readout *r, void *counts_u64, const void
 int mbn_confusion_envelope(int classes, int truth_bytes, int64_t count);
 int mbn_confusion_form(int classes);
 int mbn_confusion_metrics(const uint64_t *counts, int classes, mbn_seg_metrics *m, double *iou);
+/* Regions of a label map: connected-component labelling of the int32 maps the read-outs above write, on the device.
+ * Normative (tests/components_ref.py is the numpy form; everything is integer, so the result is a function of the input alone: the same bytes at
+ * every planning CU count, in both forms, on every run and on graph replay). For one image L [rows][cols] and classes >= 1:
+ *   A pixel whose label lies outside [0, classes) is ABSTAINED (the ignore_label of the thresholded read-outs, negatives, INT32_MAX): it belongs
+ *     to no region and neither connects nor separates anything else.
+ *   Two valid pixels are adjacent if they have the same label and are neighbours under `connectivity`: 4 = the edge neighbours, 8 = the edge and
+ *     corner neighbours. A REGION is a connected component of that relation.
+ *   A region's FIRST PIXEL is its smallest linear index r * cols + c. Regions are numbered 0 .. n - 1 per image in ascending order of their first pixel.
+ *   min_area >= 1: a region of fewer than min_area pixels is DROPPED. Connectivity is decided before the drop; dropping does not merge the
+ *     neighbours of a dropped region afterwards; the survivors are numbered as above among themselves. min_area = 1 keeps everything.
+ * Outputs per image:
+ *   comp_i32 [rows][cols]        the pixel's region number; -1 for abstained pixels and for pixels of dropped regions. May be NULL.
+ *   n_regions_i32                the number of surviving regions: the true count, even above max_regions. Required.
+ *   regions [max_regions]        mbn_region (32 bytes): record i describes region i; records >= min(n, max_regions) are NOT written. NULL iff
+ *                                max_regions = 0.
+ *   labels_out_i32 [rows][cols]  L with the pixels of dropped regions replaced by ignore_label; every other pixel copied, abstained ones included.
+ *                                May be NULL. It (and comp_i32) must not overlap labels_i32.
+ *   mbn_components_i32         maps [batch][rows][cols], the table [batch][max_regions], n_regions_i32 [batch]
+ *   mbn_components_ragged_i32  the maps of a ragged set, of either item kind (only the items' first 16 bytes are used): comp_i32 and labels_out_i32
+ *                              use the labels' dst_offset, nothing between the maps is read or written; the table is [set batch][max_regions].
+ *                              It keeps the handle's generation rule (a captured launch replayed after a later set does nothing) and the next
+ *                              set waits for it
+ * Both are a FIXED sequence of seven kernels on `stream` (NULL: the context's) with no host decision between them, no host allocation, no copy to
+ * the host and no blocking call: a call may be captured as a linear chain of kernel nodes. The grids are sized from the planning CU count. Calls on
+ * one handle share its scratch: they must be ordered on one stream (or by the caller's events).
+ * labels_i32, comp_i32, labels_out_i32, regions and n_regions_i32 may be any pointers on 4 bytes.
+ * The handle holds all scratch (mbn_components_scratch_bytes (max_batch, max_pixels): 8 bytes per pixel + 4 bytes per 1024 pixels and per image),
+ * allocated once by mbn_components_create; mbn_shutdown frees the handles still alive.
+ * MBN_EINVAL: a NULL handle, labels_i32 or n_regions_i32; regions NULL with max_regions > 0; a pointer off 4 bytes; batch, rows, cols or
+ * classes < 1; connectivity other than 4 or 8; min_area < 1; max_regions < 0; labels_out_i32 or comp_i32 overlapping labels_i32; batch above the
+ * handle's max_batch or more pixels in all than its max_pixels; a ragged handle without a set; an undersized tracked buffer (mbn_alloc's bounds
+ * rule: the maps span batch * rows * cols elements, in the ragged form max(dst_offset + rows * cols); regions batch * max_regions records;
+ * n_regions_i32 batch elements). MBN_EUNSUPPORTED: a map of 2^31 bytes or more (rows * cols >= 2^29: indices and areas are int32), batch > 65535,
+ * max_regions > MBN_COMPONENTS_MAX_REGIONS. A refusal launches nothing. mbn_components_envelope answers the shape part, mbn_components_tile the
+ * tile of the first kernel (a seam of the union-find lies at every multiple of it); both and _scratch_bytes (0 for arguments _create refuses) are
+ * pure host functions. mbn_components_create: MBN_EINVAL for max_batch < 1 or max_pixels < 1, MBN_EUNSUPPORTED for max_batch > 65535 or
+ * max_pixels > 2^34, MBN_ENOMEM when the device has no room. */
+#define MBN_COMPONENTS_MAX_REGIONS (1 << 24)
+typedef struct mbn_region { int32_t label, area, first_row, first_col, min_row, min_col, max_row, max_col; } mbn_region;
+typedef struct mbn_components mbn_components;
+int mbn_components_create(mbn_context *ctx, int max_batch, int64_t max_pixels, mbn_components **h);
+int mbn_components_destroy(mbn_components *h);
+int64_t mbn_components_scratch_bytes(int max_batch, int64_t max_pixels);
+int mbn_components_envelope(int batch, int rows, int cols, int classes, int connectivity, int min_area, int max_regions);
+int mbn_components_tile(int *tile_rows, int *tile_cols);
+int mbn_components_i32(mbn_components *h, void *comp_i32, mbn_region *regions, void *n_regions_i32, void *labels_out_i32, const void *labels_i32,
+                       int batch, int rows, int cols, int classes, int connectivity, int min_area, int ignore_label, int max_regions, void *stream);
+int mbn_components_ragged_i32(mbn_components *h, mbn_ragged_readout *readout, void *comp_i32, mbn_region *regions, void *n_regions_i32,
+                              void *labels_out_i32, const void *labels_i32, int classes, int connectivity, int min_area, int ignore_label,
+                              int max_regions, void *stream);
 /* The classifier tail of the sequence as one call (MobileNet.c:2601-2792): global average pool (kernel.cl:116) ->
  * FC = pointwise with rows = cols = 1 (kernel.cl:94; bias, no ReLU: B15) -> softmax + top-k. fp32 NHWC,
  * in [batch][rows][cols][channels], fc_w [classes][channels], fc_bias [classes] or NULL; pooled_scratch
@@ -1141,6 +1191,12 @@ int  mbn_net_segment_views_fit(mbn_net *net, const void *src_u8, int batch, int 
  * labels_i32 is the buffer that call wrote (or a copy of it). MBN_EINVAL before any such call; a refused segment call leaves the record of the
  * one before in place. Otherwise whatever the confusion call answers. */
 int  mbn_net_segment_score(mbn_net *net, const void *labels_i32, const void *truth, int truth_bytes, void *counts_u64);
+/* The regions of the label maps of that same call ("regions of a label map" above; found exactly as mbn_net_segment_score finds it): a uniform
+ * call is one mbn_components_i32 over [batch][out_rows][out_cols], an image call mbn_components_ragged_i32 on the net's own ragged set. classes is
+ * the plan's. The net owns one mbn_components handle, sized for the call on first use, made again when a later call needs more, freed by
+ * mbn_net_destroy; MBN_ENOMEM leaves the net usable. MBN_EINVAL before any segment call. Otherwise whatever the components call answers. */
+int  mbn_net_segment_regions(mbn_net *net, const void *labels_i32, void *comp_i32, mbn_region *regions, void *n_regions_i32, void *labels_out_i32,
+                             int connectivity, int min_area, int ignore_label, int max_regions);
 /* Per-layer milliseconds of the most recent mbn_net_forward_timed call (hipEvents between layers). */
 int  mbn_net_forward_timed(mbn_net *net, const void *images, void *logits, int batch, float *layer_ms,
                            int n_layer_ms);

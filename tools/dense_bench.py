@@ -32,6 +32,11 @@
   python tools/dense_bench.py --score [--reps 7] [--steps 20] [--batch 32] [--no-torch]
       mbn_confusion_i32, the confusion matrix of --batch label maps of 375 x 500 against a uint8 truth (main_score): 21 / 150 / 1000 classes,
       random and piecewise-constant inputs, beside torch.bincount on the same buffers.
+
+  python tools/dense_bench.py --regions [--reps 7] [--steps 20] [--batch 32] [--host-maps 2] [--no-host] [--configs random,blocks,constant]
+      mbn_components_i32, the connected regions of --batch label maps of 375 x 500 (main_regions): 21 / 150 / 1000 classes, random, 25 x 25-block
+      and constant inputs, connectivity 4 and 8, min_area 1 (comp alone) and 50 (comp and labels_out), beside scipy.ndimage.label per class on
+      the host, download included.
 """
 import argparse
 import json
@@ -508,6 +513,79 @@ def main_score(a):
     print(json.dumps(result))
 
 
+def main_regions(a):
+    """--regions: mbn_components_i32 on --batch maps of 375 x 500 (6 M pixels at 32) at 21 / 150 / 1000 classes. Three inputs per class count:
+      random     labels uniform over the classes: nearly every pixel its own region at 1000 classes, large tangled ones at 21 under connectivity 8
+      blocks     blocks of 25 x 25 pixels of one class: what a label map looks like
+      constant   one class everywhere: one region through every seam; every union and every area add of an image meets on one word
+    x connectivity 4 / 8 x (min_area 1 writing comp alone: 8 bytes a pixel; min_area 50 writing comp and labels_out: 12 bytes a pixel). The table
+    holds 4096 regions a map. Each figure is the median over the repetitions of `steps` back-to-back calls between two stream marks; the runs are
+    kept, the spread is (max - min) / median. share_of_hbm: the bytes above over the call's time against 8 TB/s. The results are checked once per
+    cell against the host's (n_regions of the first --host-maps maps).
+    host_ms: what a user has without the call: the download of the maps, then scipy.ndimage.label once per class present, on the first --host-maps
+    maps, scaled to the batch (host_maps says how many were really labelled)."""
+    pkg = import_package()
+    n, H, W = a.batch, 375, 500
+    pix, max_regions = n * H * W, 4096
+    rng = np.random.default_rng(0)
+    result = {"batch": n, "pixels": pix, "max_regions": max_regions}
+    eight, four = np.ones((3, 3), int), np.array([[0, 1, 0], [1, 1, 1], [0, 1, 0]])
+    with pkg.Context(0) as ctx:
+        handle = pkg.Components(ctx, n, pix)
+        d_comp, d_out, d_reg, d_n = ctx.alloc(4 * pix), ctx.alloc(4 * pix), ctx.alloc(32 * n * max_regions), ctx.alloc(4 * n)
+        for classes in (21, 150, 1000):
+            yy, xx = np.mgrid[0:H, 0:W]
+            coarse = rng.integers(0, classes, (n, H // 25 + 1, W // 25 + 1))
+            inputs = {"random": rng.integers(0, classes, (n, H, W)).astype(np.int32), "blocks": coarse[:, yy // 25, xx // 25].astype(np.int32),
+                      "constant": np.full((n, H, W), classes - 1, np.int32)}
+            for name, maps in inputs.items():
+                if a.configs and name not in a.configs.split(","):     # --configs random,blocks,constant: one input kind (a profiler run of its own)
+                    continue
+                d_lab = ctx.to_device(maps)
+                for conn in (4, 8):
+                    host_ms, host_n = None, None
+                    if not a.no_host:
+                        from scipy import ndimage
+                        import time
+                        k = min(a.host_maps, n)
+                        t0 = time.perf_counter()
+                        got = d_lab.download((n, H, W), np.int32)
+                        host_n = []
+                        for i in range(k):
+                            host_n.append(sum(ndimage.label(got[i] == c, structure=eight if conn == 8 else four)[1] for c in np.unique(got[i])))
+                        t1 = time.perf_counter()
+                        t_dl = time.perf_counter()
+                        d_lab.download((n, H, W), np.int32)
+                        t_dl = time.perf_counter() - t_dl
+                        host_ms = 1e3 * (t_dl + (t1 - t0 - t_dl) * n / k)
+                    for min_area in (1, 50):
+                        out_ptr = d_out.ptr if min_area > 1 else None
+                        fn = lambda: ctx.components(handle, d_lab.ptr, n, H, W, classes, d_n.ptr, comp=d_comp.ptr, regions=d_reg.ptr,
+                                                    labels_out=out_ptr, connectivity=conn, min_area=min_area, ignore_label=classes,
+                                                    max_regions=max_regions)
+                        fn()
+                        ctx.sync()
+                        counts = d_n.download((n,), np.int32)
+                        if host_n is not None and min_area == 1:
+                            assert counts[:len(host_n)].tolist() == host_n, (classes, name, conn, counts[:len(host_n)].tolist(), host_n)
+                        marks_ms(ctx, fn, 2)
+                        ks = [marks_ms(ctx, fn, a.steps) for _ in range(a.reps)]
+                        k_ms = statistics.median(ks)
+                        bpp = 12 if min_area > 1 else 8
+                        out = {"call_ms": round(k_ms, 4), "runs_ms": [round(v, 4) for v in ks], "spread": round((max(ks) - min(ks)) / k_ms, 4),
+                               "bytes_per_pixel": bpp, "floor_ms": round(1e3 * bpp * pix / HBM_BYTES_PER_S, 4),
+                               "share_of_hbm": round(bpp * pix / (k_ms * 1e-3) / HBM_BYTES_PER_S, 4), "regions_per_map": round(float(counts.mean()), 1)}
+                        if host_ms is not None:
+                            out.update({"host_ms": round(host_ms, 1), "host_maps": len(host_n), "host_over_call": round(host_ms / k_ms, 1)})
+                        print("classes %4d %-8s conn %d min_area %2d: call %.4f ms (spread %.1f %%, floor %.4f ms, %.1f %% of 8 TB/s)  regions/map %.1f  "
+                              "host %s ms" % (classes, name, conn, min_area, k_ms, 100 * out["spread"], out["floor_ms"], 100 * out["share_of_hbm"],
+                                              out["regions_per_map"], ("%.1f" % host_ms) if host_ms is not None else "-"), flush=True)
+                        result["classes_%d_%s_c%d_a%d" % (classes, name, conn, min_area)] = out
+                d_lab.free()
+        handle.close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
@@ -521,7 +599,12 @@ def main():
     ap.add_argument("--prob", action="store_true", help="--any: time the softmax read-out beside the argmax read-out instead: see main_prob")
     ap.add_argument("--ensemble", default="", help="comma list of view counts: time mbn_resample_ensemble_f32 instead: see main_ensemble")
     ap.add_argument("--score", action="store_true", help="time mbn_confusion_i32 beside torch.bincount instead: see main_score")
+    ap.add_argument("--regions", action="store_true", help="time mbn_components_i32 beside scipy.ndimage.label on the host instead: see main_regions")
+    ap.add_argument("--host-maps", type=int, default=2, help="--regions: the maps the host yardstick really labels (its time is scaled to the batch)")
+    ap.add_argument("--no-host", action="store_true", help="--regions: skip the host yardstick")
     a = ap.parse_args()
+    if a.regions:
+        return main_regions(a)
     if a.score:
         return main_score(a)
     if a.ensemble:
