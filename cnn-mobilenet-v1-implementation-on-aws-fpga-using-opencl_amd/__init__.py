@@ -113,6 +113,12 @@ class View(C.Structure):
         return (self.x, self.y, self.iw, self.ih)
 
 
+class BoundaryMetrics(C.Structure):
+    """mbn_boundary_metrics_t (include/mbn.h, "score a segmentation at its boundaries")"""
+    _fields_ = [("boundary_miou", C.c_double), ("truth_band_pixels", C.c_double), ("pred_band_pixels", C.c_double),
+                ("classes_present", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SegMetrics(C.Structure):
     """mbn_seg_metrics (include/mbn.h, "score a segmentation")"""
     _fields_ = [("pixels", C.c_double), ("valid", C.c_double), ("void_pixels", C.c_double), ("abstained", C.c_double),
@@ -234,6 +240,10 @@ def _declare_host(lib):
     lib.mbn_components_tile.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.mbn_components_scratch_bytes.argtypes = [C.c_int, C.c_int64]
     lib.mbn_components_scratch_bytes.restype = C.c_int64
+    lib.mbn_boundary_d.argtypes = [C.c_int, C.c_int, C.c_double]
+    lib.mbn_boundary_envelope.argtypes = [C.c_int] * 7
+    lib.mbn_boundary_tile.argtypes = [C.c_int] + [C.POINTER(C.c_int)] * 3
+    lib.mbn_boundary_metrics.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.POINTER(BoundaryMetrics), C.POINTER(C.c_double)]
     i32p = C.POINTER(C.c_int32)
     lib.mbn_resize_ksize.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int]
     lib.mbn_resize_taps.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int, i32p, i32p, i32p]
@@ -395,6 +405,13 @@ def load():
         lib.mbn_components_i32.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]
         lib.mbn_components_ragged_i32.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
         lib.mbn_net_segment_regions.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci]
+        lib.mbn_boundary_d_items.argtypes = [vp, C.c_double, C.POINTER(C.c_int32)]
+        lib.mbn_boundary_depth.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
+        lib.mbn_boundary_depth_ragged.argtypes = [vp, vp, vp, ci, ci, vp, ci, vp]
+        lib.mbn_boundary_score_i32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
+        lib.mbn_boundary_score_ragged_i32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, vp, ci, vp]
+        lib.mbn_net_segment_boundary_score.argtypes = [vp, vp, vp, ci, vp, vp, C.c_double, ci, ci]
+        lib.mbn_net_segment_boundary_depth.argtypes = [vp, vp, vp, C.c_double, ci, ci]
         lib.mbn_resizer_create.argtypes = [vp, ci, ci, C.POINTER(C.c_float), ci, ci, C.POINTER(vp)]
         lib.mbn_resize_u8.argtypes = [vp, vp, vp, ci, vp]
         lib.mbn_resizer_destroy.argtypes = [vp]
@@ -709,6 +726,37 @@ def components_tile(lib=None):
     return tr.value, tc.value
 
 
+BOUNDARY_MAX_D = 64
+
+
+def boundary_d(rows, cols, ratio, lib=None) -> int:
+    """mbn_boundary_d: the half-width round (ratio * diagonal), ties to even, at least 1; or the negative status (EINVAL, EUNSUPPORTED)."""
+    return (lib or host_lib()).mbn_boundary_d(rows, cols, ratio)
+
+
+def boundary_envelope(elem_bytes, classes, batch, rows, cols, d, edge, lib=None) -> int:
+    """mbn_boundary_envelope: the status (OK, EINVAL or EUNSUPPORTED) the boundary calls give the shape (classes = 1 for the depth calls)."""
+    return (lib or host_lib()).mbn_boundary_envelope(elem_bytes, classes, batch, rows, cols, d, edge)
+
+
+def boundary_tile(d, lib=None):
+    """mbn_boundary_tile: (tile_rows, tile_cols, lds_bytes) of the kernel at half-width d: a seam lies at every multiple of the tile."""
+    tr, tc, lds = C.c_int(0), C.c_int(0), C.c_int(0)
+    _chk((lib or host_lib()).mbn_boundary_tile(d, C.byref(tr), C.byref(tc), C.byref(lds)), "boundary_tile")
+    return tr.value, tc.value, lds.value
+
+
+def boundary_metrics(biou, classes, lib=None):
+    """mbn_boundary_metrics: (BoundaryMetrics, iou float64 [classes], NaN for an absent class) of biou, uint64 [classes][3]."""
+    n = np.ascontiguousarray(biou, dtype=np.uint64)
+    if n.size != classes * 3:
+        raise ValueError("biou has %d cells, classes = %d needs %d" % (n.size, classes, classes * 3))
+    m, iou = BoundaryMetrics(), np.empty(classes, np.float64)
+    _chk((lib or host_lib()).mbn_boundary_metrics(n.ctypes.data_as(C.POINTER(C.c_uint64)), classes, C.byref(m),
+                                                  iou.ctypes.data_as(C.POINTER(C.c_double))), "boundary_metrics")
+    return m, iou
+
+
 def components_scratch_bytes(max_batch, max_pixels, lib=None) -> int:
     """mbn_components_scratch_bytes: the device memory a Components handle of that size holds (0: a size mbn_components_create refuses)."""
     return (lib or host_lib()).mbn_components_scratch_bytes(max_batch, max_pixels)
@@ -958,6 +1006,31 @@ class Context:
         regions (Region [batch][max_regions]), n_regions (int32 [batch], the true counts), labels_out (the maps without the dropped regions)."""
         _chk(self.lib.mbn_components_i32(handle.h, comp, regions, n_regions, labels_out, labels, batch, rows, cols, classes, connectivity, min_area,
                                          ignore_label, max_regions, stream), self.last_error())
+
+    def boundary_depth(self, depth, map_ptr, elem_bytes, batch, rows, cols, d, edge=1, stream=None):
+        """mbn_boundary_depth: depth (uint8 [batch][rows][cols], device) = min (D, d + 1) of the maps (uint8: elem_bytes 1, int32: 4)."""
+        _chk(self.lib.mbn_boundary_depth(self.h, depth, map_ptr, elem_bytes, batch, rows, cols, d, edge, stream), self.last_error())
+
+    def boundary_depth_ragged(self, readout, depth, map_ptr, elem_bytes, d, d_items=None, edge=1, stream=None):
+        """mbn_boundary_depth_ragged: the same over the maps of a RaggedReadout's set; d_items: device int32 [set batch] or None (d for all)."""
+        _chk(self.lib.mbn_boundary_depth_ragged(readout.h, depth, map_ptr, elem_bytes, d, d_items, edge, stream), self.last_error())
+
+    def boundary_score(self, trimap, biou, labels, truth, truth_bytes, classes, batch, rows, cols, d, edge=1, stream=None):
+        """mbn_boundary_score_i32: trimap (uint64 [classes + 1][classes + 1]) and biou (uint64 [classes][3]) += the boundary score of int32 labels
+        against truth [batch][rows][cols]; either table may be None."""
+        _chk(self.lib.mbn_boundary_score_i32(self.h, trimap, biou, labels, truth, truth_bytes, classes, batch, rows, cols, d, edge, stream),
+             self.last_error())
+
+    def boundary_score_ragged(self, readout, trimap, biou, labels, truth, truth_bytes, classes, d, d_items=None, edge=1, stream=None):
+        """mbn_boundary_score_ragged_i32: the same over the maps of a RaggedReadout's set; truth at the labels' element offsets."""
+        _chk(self.lib.mbn_boundary_score_ragged_i32(readout.h, trimap, biou, labels, truth, truth_bytes, classes, d, d_items, edge, stream),
+             self.last_error())
+
+    def boundary_d_items(self, readout, ratio):
+        """mbn_boundary_d_items: int32 [set batch] (numpy), each item's own half-width at `ratio`."""
+        out = np.zeros(max(readout.batch, 1), np.int32)
+        _chk(self.lib.mbn_boundary_d_items(readout.h, ratio, out.ctypes.data_as(C.POINTER(C.c_int32))), self.last_error())
+        return out
 
     def components_ragged(self, handle, readout, labels, classes, n_regions, comp=None, regions=None, labels_out=None, connectivity=4, min_area=1,
                           ignore_label=0, max_regions=0, stream=None):
@@ -1300,6 +1373,16 @@ class Net:
         """mbn_net_segment_score: counts (uint64 [classes + 1][classes + 1]) += the confusion matrix of the maps the most recent successful
         source-size segment call wrote against truth (uint8 or int32, at the labels' element offsets)."""
         _chk(self.ctx.lib.mbn_net_segment_score(self.h, labels_ptr, truth_ptr, truth_bytes, counts_ptr), self.ctx.last_error())
+
+    def segment_boundary_score(self, labels_ptr, truth_ptr, truth_bytes, trimap_ptr, biou_ptr, ratio=0.02, d=0, edge=1):
+        """mbn_net_segment_boundary_score: the boundary score of the maps the most recent successful source-size segment call wrote; d > 0 is a
+        fixed half-width, d = 0 takes ratio (per image after an image call)."""
+        _chk(self.ctx.lib.mbn_net_segment_boundary_score(self.h, labels_ptr, truth_ptr, truth_bytes, trimap_ptr, biou_ptr, ratio, d, edge),
+             self.ctx.last_error())
+
+    def segment_boundary_depth(self, labels_ptr, depth_ptr, ratio=0.02, d=0, edge=1):
+        """mbn_net_segment_boundary_depth: the band (depth uint8) of those maps, at the labels' element offsets."""
+        _chk(self.ctx.lib.mbn_net_segment_boundary_depth(self.h, labels_ptr, depth_ptr, ratio, d, edge), self.ctx.last_error())
 
     def segment_regions(self, labels_ptr, n_regions_ptr, comp_ptr=None, regions_ptr=None, labels_out_ptr=None, connectivity=4, min_area=1,
                         ignore_label=0, max_regions=0):

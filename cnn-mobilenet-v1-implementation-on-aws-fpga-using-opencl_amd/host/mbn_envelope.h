@@ -142,6 +142,22 @@ int mbn_confusion_form(int classes);
 #define MBN_COMPONENTS_CHUNK 1024
 #define MBN_COMPONENTS_MAX_PIXELS ((int64_t)1 << 34)
 #define MBN_COMPONENTS_MAX_MAP ((int64_t)1 << 29)
+/* boundary score (mbn_i32_boundary.hip, host/mbn_boundary.c; the functions are declared in mbn.h). Two half-width classes: d up to
+ * MBN_BOUNDARY_SMALL_D takes tiles of MBN_BOUNDARY_SMALL_ROWS x MBN_BOUNDARY_TILE_COLS, a larger d tiles of MBN_BOUNDARY_LARGE_ROWS rows. A tile
+ * keeps, per map, the value (4 bytes) and the horizontal distance (1 byte) of its own columns over its rows and d rows above and below:
+ * (tile_rows + 2 d) * tile_cols * MBN_BOUNDARY_PIXEL_BYTES bytes of LDS, twice for the score kernel (truth and labels), which also holds
+ * MBN_BOUNDARY_TABLE_BYTES of 32-bit bins: up to MBN_BOUNDARY_LDS_CLASSES classes a workgroup counts a tile there, (classes + 1)^2 trimap bins and
+ * 3 * classes biou bins. MBN_BOUNDARY_MAX_MAP: a map stays below 2^29 pixels (indices are int32); MBN_BOUNDARY_MAX_BATCH: the maps of a uniform call */
+#define MBN_BOUNDARY_SMALL_D 16
+#define MBN_BOUNDARY_SMALL_ROWS 32
+#define MBN_BOUNDARY_LARGE_ROWS 64
+#define MBN_BOUNDARY_TILE_COLS 64
+#define MBN_BOUNDARY_PIXEL_BYTES 5
+#define MBN_BOUNDARY_LDS_CLASSES 31
+#define MBN_BOUNDARY_TABLE_BYTES 4480
+#define MBN_BOUNDARY_CU_LDS (160 * 1024)
+#define MBN_BOUNDARY_MAX_MAP ((int64_t)1 << 29)
+#define MBN_BOUNDARY_MAX_BATCH 65535
 /* resize front-end (mbn_u8_resize.hip): one geometry of mbn_resizer_create. Source sides 1..8192, output sides 1..4096, at most MBN_RESIZE_MAX_KSIZE
  * taps per axis (a 32x downscale; any upscale has 3). box = (left, upper, right, lower), NULL = the whole image. MBN_EINVAL for a non-positive
  * size or a box mbn_resize_ksize refuses, else MBN_EUNSUPPORTED outside the limits. The batch (1..MBN_RESIZE_MAX_BATCH: grid.y) belongs to the call. */

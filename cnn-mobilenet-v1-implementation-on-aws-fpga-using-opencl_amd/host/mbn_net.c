@@ -68,6 +68,7 @@ struct mbn_net {
     mbn_components *components;     /* mbn_net_segment_regions: one handle, made on first use and again when a call needs more */
     int components_batch;           /* ... and what it holds */
     int64_t components_pixels;
+    void *boundary_d;               /* mbn_net_segment_boundary_*: [max_batch] int32 on the device, the per-image half-widths of an image call */
     /* mbn_net_resize_views: the view resizers kept, each made for one (source size, scale, mirror, filter, pad colour); used = the clock of its last use */
     struct view_slot {
         mbn_resizer *r;
@@ -176,6 +177,7 @@ int mbn_net_destroy(mbn_net *net)
     free(net->ragged_items);
     if (net->readout) mbn_ragged_readout_destroy(net->readout);
     if (net->components) mbn_components_destroy(net->components);
+    if (net->boundary_d) mbn_free(net->ctx, net->boundary_d);
     free(net->label_items);
     if (net->resize_buf) mbn_free(net->ctx, net->resize_buf);
     for (int j = 0; j < 8; j++)
@@ -1365,6 +1367,57 @@ int mbn_net_segment_regions(mbn_net *net, const void *labels_i32, void *comp_i32
                                          connectivity, min_area, ignore_label, max_regions, NULL);
     return mbn_components_i32(net->components, comp_i32, regions, n_regions_i32, labels_out_i32, labels_i32, net->score_batch, net->score_rows,
                               net->score_cols, fc->out_ch, connectivity, min_area, ignore_label, max_regions, NULL);
+}
+
+/* The half-width of the two boundary calls: d > 0 as given; d == 0 from ratio, for a uniform call mbn_boundary_d of the map size (*d_out), for
+ * an image call every image's own, uploaded to net->boundary_d (*d_items; *d_out is not read by the ragged forms then) */
+static int boundary_half_width(mbn_net *net, double ratio, int d, int *d_out, const void **d_items)
+{
+    *d_out = d;
+    *d_items = NULL;
+    if (d < 0) return MBN_EINVAL;
+    if (d > 0) return MBN_OK;
+    if (net->score_kind == SCORE_UNIFORM) {
+        const int w = mbn_boundary_d(net->score_rows, net->score_cols, ratio);
+        if (w < 0) return w;
+        *d_out = w;
+        return MBN_OK;
+    }
+    int32_t *host = (int32_t *)malloc((size_t)net->max_batch * sizeof(int32_t));
+    if (!host) return MBN_ENOMEM;
+    int rc = mbn_boundary_d_items(net->readout, ratio, host);
+    if (rc == MBN_OK && !net->boundary_d) rc = mbn_alloc(net->ctx, (size_t)net->max_batch * sizeof(int32_t), &net->boundary_d);
+    if (rc == MBN_OK) rc = mbn_upload(net->ctx, net->boundary_d, host, (size_t)net->score_batch * sizeof(int32_t));
+    free(host);
+    *d_out = 1;
+    *d_items = net->boundary_d;
+    return rc;
+}
+
+int mbn_net_segment_boundary_score(mbn_net *net, const void *labels_i32, const void *truth, int truth_bytes, void *trimap_u64, void *biou_u64,
+                                   double ratio, int d, int edge)
+{
+    if (!net || net->score_kind == SCORE_NONE) return MBN_EINVAL;
+    const mbn_layer_desc *feat, *fc;
+    int rc = dense_layers(net, &feat, &fc);
+    if (rc != MBN_OK) return rc;
+    const void *d_items;
+    rc = boundary_half_width(net, ratio, d, &d, &d_items);
+    if (rc != MBN_OK) return rc;
+    if (net->score_kind == SCORE_RAGGED)
+        return mbn_boundary_score_ragged_i32(net->readout, trimap_u64, biou_u64, labels_i32, truth, truth_bytes, fc->out_ch, d, d_items, edge, NULL);
+    return mbn_boundary_score_i32(net->ctx, trimap_u64, biou_u64, labels_i32, truth, truth_bytes, fc->out_ch, net->score_batch, net->score_rows,
+                                  net->score_cols, d, edge, NULL);
+}
+
+int mbn_net_segment_boundary_depth(mbn_net *net, const void *labels_i32, void *depth_u8, double ratio, int d, int edge)
+{
+    if (!net || net->score_kind == SCORE_NONE) return MBN_EINVAL;
+    const void *d_items;
+    const int rc = boundary_half_width(net, ratio, d, &d, &d_items);
+    if (rc != MBN_OK) return rc;
+    if (net->score_kind == SCORE_RAGGED) return mbn_boundary_depth_ragged(net->readout, depth_u8, labels_i32, 4, d, d_items, edge, NULL);
+    return mbn_boundary_depth(net->ctx, depth_u8, labels_i32, 4, net->score_batch, net->score_rows, net->score_cols, d, edge, NULL);
 }
 
 int mbn_net_forward_timed(mbn_net *net, const void *images, void *logits, int batch, float *layer_ms, int n_layer_ms)

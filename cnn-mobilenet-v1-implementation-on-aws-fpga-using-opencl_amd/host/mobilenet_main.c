@@ -37,6 +37,13 @@
  *   the order of the regions' first pixels. With --min-area N > 1 the regions of fewer than N pixels are dropped: the map written to --segment-source
  *   and the map scored by --truth are the cleaned ones, whose dropped pixels hold --ignore-label (where --min-confidence brought one), else the class
  *   count
+ *   --boundary-ratio R | --boundary-d N [--boundary-edge 0|1] [--boundary-map out.pgm] (with --segment-source; edge defaults to 1): contour quality,
+ *   "score a segmentation at its boundaries" in mbn.h. The half-width is N pixels, or R of every image's own diagonal (0.02 is the usual value).
+ *   With --truth three kinds of line follow the score line (mbn_net_segment_boundary_score):
+ *   boundary: d=... edge=... classes_present=... truth_band=... pred_band=... boundary_miou=...      (d: image 0's half-width)
+ *   boundary_iou: class <c> <iou>                                                                   (one per present class)
+ *   trimap: ... the fields of the score line, over the pixels within d of a contour of the truth
+ *   --boundary-map writes image 0's band as an 8-bit P5: byte = min (depth, d + 1) of its label map (mbn_net_segment_boundary_depth)
  *   mobilenet --literal [--weights weights_c.txt] [--image Cat_Image0.ppm] [--ref-args]      the reference's own mode
  *   mobilenet --gpus G --batch N [--steps K --warmup W --streams S --pw-emul 6] (--h5 F | --synthetic SEED)  N images sharded over G GPUs
  *   mobilenet --inspect weights.h5                                                             list the datasets of a .h5
@@ -453,9 +460,67 @@ static int read_truth_pgm(const char *path, int width, int height, int32_t *out,
     return 0;
 }
 
-/* --truth: scores the label maps the segment call just wrote at d_labels (image n at element dst[n]) against the files, and prints the line */
+/* --boundary-ratio / --boundary-d / --boundary-edge / --boundary-map: what the command line asked for; on = 0: nothing. d > 0: a fixed half-width,
+ * else `ratio` of every image's diagonal */
+typedef struct boundary_opts { int on, d, edge; double ratio; const char *map; } boundary_opts;
+
+/* --truth with --boundary-ratio or --boundary-d: the boundary IoU and the trimap scores of the same maps (mbn_net_segment_boundary_score) */
+static int score_boundary(mbn_context *ctx, mbn_net *net, const boundary_opts *bo, void *d_labels, void *d_truth, int tb, int classes, int rows0, int cols0)
+{
+    const size_t cells = ((size_t)classes + 1) * ((size_t)classes + 1), bcells = (size_t)classes * 3;
+    uint64_t *trimap = malloc(cells * sizeof(uint64_t)), *biou = malloc(bcells * sizeof(uint64_t));
+    double *iou = malloc((size_t)classes * sizeof(double));
+    if (!trimap || !biou || !iou) return 1;
+    void *d_trimap, *d_biou;
+    CHECK(mbn_alloc(ctx, cells * sizeof(uint64_t), &d_trimap));
+    CHECK(mbn_alloc(ctx, bcells * sizeof(uint64_t), &d_biou));
+    CHECK(mbn_memset(ctx, d_trimap, 0, cells * sizeof(uint64_t)));
+    CHECK(mbn_memset(ctx, d_biou, 0, bcells * sizeof(uint64_t)));
+    CHECK(mbn_net_segment_boundary_score(net, d_labels, d_truth, tb, d_trimap, d_biou, bo->ratio, bo->d, bo->edge));
+    CHECK(mbn_download(ctx, trimap, d_trimap, cells * sizeof(uint64_t)));
+    CHECK(mbn_download(ctx, biou, d_biou, bcells * sizeof(uint64_t)));
+    CHECK(mbn_free(ctx, d_trimap));
+    CHECK(mbn_free(ctx, d_biou));
+    mbn_boundary_metrics_t b;
+    mbn_seg_metrics m;
+    CHECK(mbn_boundary_metrics(biou, classes, &b, iou));
+    printf("boundary: d=%d edge=%d classes_present=%d truth_band=%.0f pred_band=%.0f boundary_miou=%.17g\n",
+           bo->d > 0 ? bo->d : mbn_boundary_d(rows0, cols0, bo->ratio), bo->edge, b.classes_present, b.truth_band_pixels, b.pred_band_pixels, b.boundary_miou);
+    for (int c = 0; c < classes; c++)
+        if (!isnan(iou[c])) printf("boundary_iou: class %d %.17g\n", c, iou[c]);
+    CHECK(mbn_confusion_metrics(trimap, classes, &m, NULL));
+    printf("trimap: pixels=%.0f valid=%.0f void=%.0f abstained=%.0f classes_present=%d pixel_acc=%.17g mean_acc=%.17g miou=%.17g fw_iou=%.17g\n", m.pixels,
+           m.valid, m.void_pixels, m.abstained, m.classes_present, m.pixel_accuracy, m.mean_accuracy, m.miou, m.fw_iou);
+    free(trimap); free(biou); free(iou);
+    return 0;
+}
+
+/* --boundary-map: image 0's band, the depth min (D, d + 1) of its label map as an 8-bit P5 (mbn_net_segment_boundary_depth) */
+static int write_boundary_map(mbn_context *ctx, mbn_net *net, const boundary_opts *bo, void *d_labels, size_t pixels, int rows, int cols)
+{
+    unsigned char *depth = malloc((size_t)rows * cols);
+    if (!depth) return 1;
+    void *d_depth;
+    CHECK(mbn_alloc(ctx, pixels, &d_depth));
+    CHECK(mbn_net_segment_boundary_depth(net, d_labels, d_depth, bo->ratio, bo->d, bo->edge));
+    CHECK(mbn_download(ctx, depth, d_depth, (size_t)rows * cols));       /* image 0 is first in the buffer */
+    CHECK(mbn_free(ctx, d_depth));
+    FILE *fp = fopen(bo->map, "wb");
+    if (!fp) { fprintf(stderr, "Error: cannot write %s\n", bo->map); return 1; }
+    fprintf(fp, "P5\n%d %d\n255\n", cols, rows);
+    const int d = bo->d > 0 ? bo->d : mbn_boundary_d(rows, cols, bo->ratio);
+    long band = 0;
+    for (long i = 0; i < (long)rows * cols; i++) band += depth[i] <= d;
+    const int ok = fwrite(depth, 1, (size_t)rows * cols, fp) == (size_t)rows * cols;
+    printf("boundary-map: %dx%d -> %s; d=%d, %ld pixels in the band\n", cols, rows, bo->map, d, band);
+    free(depth);
+    return (fclose(fp) != 0) | !ok;
+}
+
+/* --truth: scores the label maps the segment call just wrote at d_labels (image n at element dst[n]) against the files, and prints the line;
+ * bo->on: the boundary lines behind it */
 static int score_truth(mbn_context *ctx, mbn_net *net, const char **truths, int n, const int64_t *dst, const int32_t *hs, const int32_t *ws, size_t pixels,
-                       void *d_labels, int classes)
+                       void *d_labels, int classes, const boundary_opts *bo)
 {
     int32_t *tv = calloc(pixels, sizeof(int32_t));
     if (!tv) return 1;
@@ -484,12 +549,16 @@ static int score_truth(mbn_context *ctx, mbn_net *net, const char **truths, int 
     CHECK(mbn_memset(ctx, d_counts, 0, cells * sizeof(uint64_t)));
     CHECK(mbn_net_segment_score(net, d_labels, d_truth, tb, d_counts));
     CHECK(mbn_download(ctx, counts, d_counts, cells * sizeof(uint64_t)));
-    CHECK(mbn_free(ctx, d_truth));
     CHECK(mbn_free(ctx, d_counts));
     mbn_seg_metrics m;
     CHECK(mbn_confusion_metrics(counts, classes, &m, iou));
     printf("score: pixels=%.0f valid=%.0f void=%.0f abstained=%.0f classes_present=%d pixel_acc=%.17g mean_acc=%.17g miou=%.17g fw_iou=%.17g\n", m.pixels,
            m.valid, m.void_pixels, m.abstained, m.classes_present, m.pixel_accuracy, m.mean_accuracy, m.miou, m.fw_iou);
+    if (bo->on) {
+        const int bad = score_boundary(ctx, net, bo, d_labels, d_truth, tb, classes, hs[0], ws[0]);
+        if (bad) return bad;
+    }
+    CHECK(mbn_free(ctx, d_truth));
     free(tv); free(t8); free(counts); free(iou);
     return 0;
 }
@@ -552,7 +621,7 @@ static int write_confidence_map(const char *path, const float *prob, int rows, i
  * n_truth > 0 (--truth, one per image): the maps are scored against them on the device before anything is written */
 static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int n_ppm, const char *path, int classes, int fit, const char *conf_path,
                           float min_conf, int ignore, const float *scales, const int32_t *mirrors, int n_views, const char **truths, int n_truth,
-                          const region_opts *ro)
+                          const region_opts *ro, const boundary_opts *bo)
 {
     int64_t *offs = malloc(sizeof(int64_t) * (size_t)n_ppm), *dst = malloc(sizeof(int64_t) * (size_t)n_ppm);
     int32_t *hs = malloc(sizeof(int32_t) * (size_t)n_ppm), *ws = malloc(sizeof(int32_t) * (size_t)n_ppm);
@@ -613,7 +682,11 @@ static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int
     }
     CHECK(mbn_download(ctx, labels, d_maps, sizeof(int) * (size_t)hs[0] * ws[0]));        /* image 0 is first in the buffer */
     if (n_truth > 0) {                                          /* the maps are where every path above wrote them: image n at element dst[n] */
-        bad = score_truth(ctx, net, truths, n_truth, dst, hs, ws, pixels, d_maps, classes);
+        bad = score_truth(ctx, net, truths, n_truth, dst, hs, ws, pixels, d_maps, classes, bo);
+        if (bad) return bad;
+    }
+    if (bo->map) {
+        bad = write_boundary_map(ctx, net, bo, d_maps, pixels, hs[0], ws[0]);
         if (bad) return bad;
     }
     if (d_clean) CHECK(mbn_free(ctx, d_clean));
@@ -692,6 +765,8 @@ int main(int argc, char **argv)
     const char *tta = NULL;
     region_opts regions = { 0, 4, 1, 256 };
     int region_flags = 0;                                       /* --connectivity, --min-area or --max-regions seen */
+    boundary_opts boundary = { 0, 0, 1, 0.0, NULL };
+    int boundary_flags = 0;                                     /* --boundary-edge seen */
     int tta_flip = 0, n_views = 0;
     float tta_scales[MBN_ENSEMBLE_MAX_VIEWS], view_scales[MBN_ENSEMBLE_MAX_VIEWS];
     int32_t view_mirrors[MBN_ENSEMBLE_MAX_VIEWS];
@@ -721,6 +796,10 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--tta-flip")) tta_flip = 1;
         else if (!strcmp(argv[i], "--truth") && i + 1 < argc) truths[n_truth++] = argv[++i];
         else if (!strcmp(argv[i], "--regions")) regions.on = 1;
+        else if (!strcmp(argv[i], "--boundary-ratio") && i + 1 < argc) { boundary.ratio = atof(argv[++i]); boundary.on |= 1; }
+        else if (!strcmp(argv[i], "--boundary-d") && i + 1 < argc) { boundary.d = atoi(argv[++i]); boundary.on |= 2; }
+        else if (!strcmp(argv[i], "--boundary-edge") && i + 1 < argc) { boundary.edge = atoi(argv[++i]); boundary_flags = 1; }
+        else if (!strcmp(argv[i], "--boundary-map") && i + 1 < argc) boundary.map = argv[++i];
         else if (!strcmp(argv[i], "--connectivity") && i + 1 < argc) { regions.connectivity = atoi(argv[++i]); region_flags = 1; }
         else if (!strcmp(argv[i], "--min-area") && i + 1 < argc) { regions.min_area = atoi(argv[++i]); region_flags = 1; }
         else if (!strcmp(argv[i], "--max-regions") && i + 1 < argc) { regions.max_regions = atoi(argv[++i]); region_flags = 1; }
@@ -740,7 +819,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--literal")) literal = 1;
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
-            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]] [--truth F.pgm ...] [--regions [--connectivity 4|8] [--min-area N] [--max-regions M]]] [--segment-confidence OUT.pgm] "
+            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]] [--truth F.pgm ...] [--regions [--connectivity 4|8] [--min-area N] [--max-regions M]] [--boundary-ratio R | --boundary-d N [--boundary-edge 0|1] [--boundary-map OUT.pgm]]] [--segment-confidence OUT.pgm] "
                             "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n", argv[0]);
             return 2;
         }
@@ -774,6 +853,21 @@ int main(int argc, char **argv)
     if (n_truth > 0 && (!segment_src || n_truth != n_ppm)) {
         fprintf(stderr, "--truth F.pgm needs --segment-source and comes once per --ppm, in the same order\n");
         return 2;
+    }
+    if (boundary.on || boundary_flags || boundary.map) {
+        const int both = boundary.on == 3, none = boundary.on == 0;
+        if (both || none || !segment_src || (n_truth == 0 && !boundary.map)) {
+            fprintf(stderr, "--boundary-ratio R or --boundary-d N (one of them) needs --segment-source and --truth or --boundary-map; "
+                            "--boundary-edge and --boundary-map need one of them\n");
+            return 2;
+        }
+        if ((boundary.on == 1 && !(boundary.ratio > 0.0 && boundary.ratio <= 1.0)) || (boundary.on == 2 && (boundary.d < 1 || boundary.d > MBN_BOUNDARY_MAX_D)) ||
+            (boundary.edge != 0 && boundary.edge != 1)) {
+            fprintf(stderr, "bad --boundary-ratio (0 < R <= 1), --boundary-d (1 <= N <= %d) or --boundary-edge (0 or 1)\n", MBN_BOUNDARY_MAX_D);
+            return 2;
+        }
+        if (boundary.on == 1) boundary.d = 0;
+        boundary.on = n_truth > 0;
     }
     if ((regions.on || region_flags) && (!regions.on || !segment_src)) {
         fprintf(stderr, "--regions needs --segment-source; --connectivity, --min-area and --max-regions need --regions\n");
@@ -941,7 +1035,7 @@ int main(int argc, char **argv)
     }
     if (segment_src || segment_conf) {
         const int bad = segment_source(ctx, net, ppms, n_ppm, segment_src, classes, fit, segment_conf, min_conf, have_ignore ? ignore_label : -1,
-                                       view_scales, view_mirrors, n_views, truths, n_truth, &regions);
+                                       view_scales, view_mirrors, n_views, truths, n_truth, &regions, &boundary);
         if (bad) return bad;
     }
     mbn_net_destroy(net);

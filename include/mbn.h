@@ -619,6 +619,69 @@ int mbn_components_i32(mbn_components *h, void *comp_i32, mbn_region *regions, v
 int mbn_components_ragged_i32(mbn_components *h, mbn_ragged_readout *readout, void *comp_i32, mbn_region *regions, void *n_regions_i32,
                               void *labels_out_i32, const void *labels_i32, int classes, int connectivity, int min_area, int ignore_label,
                               int max_regions, void *stream);
+/* Score a segmentation at its boundaries: boundary IoU (Cheng et al., CVPR 2021) and the trimap scores of the DeepLab papers, on the device
+ * (DESIGN.md 7d.6). Both rest on the DEPTH of a pixel: its Chebyshev distance to the nearest pixel that carries another value. The arithmetic is
+ * integer: every result is pinned bit for bit at every planning CU count and on graph replay. Normative (tests/boundary_ref.py is the numpy form):
+ *   DEPTH. For one map L [rows][cols], a half-width d >= 1 and edge in {0, 1}, D (r, c) is the smallest max (|dr|, |dc|) >= 1 for which pixel
+ *     (r + dr, c + dc) lies inside the map and its value differs from L (r, c), or edge = 1 and that pixel lies outside the map; capped at d + 1.
+ *     Values are compared as stored: an int32 as an int32, a uint8 zero-extended. 255, negative values and an ignore_label are values like any
+ *     other: a void or abstained pixel is a contour for its neighbours and has a depth itself. A pixel is IN THE BAND iff D <= d. This is d
+ *     erosions with a 3 x 3 element, per value. edge = 1 is the official boundary IoU (the image frame is a contour); edge = 0 is what trimap
+ *     users want for classes that touch the frame.
+ *   HALF-WIDTH. mbn_boundary_d (rows, cols, ratio) = ratio * sqrt ((double) rows * rows + (double) cols * cols) rounded to nearest, ties to even
+ *     (nearbyint under the default rounding mode; the int (round (...)) of the official Python), at least 1: the RETURN VALUE (a status is negative).
+ *     375 x 500 at 0.02 gives 12, 224 x 224 gives 6. MBN_EINVAL: rows or cols < 1, a ratio not in (0, 1] (NaN included); MBN_EUNSUPPORTED: the
+ *     result exceeds MBN_BOUNDARY_MAX_D.
+ *   SCORE. For truth t, prediction p, their depths Dt and Dp (same d, same edge) and classes = C:
+ *     trimap_u64 [C + 1][C + 1] has the layout and the row and column rules of mbn_confusion_i32 (void row, abstained column). Every pixel with
+ *       Dt <= d adds 1 to its cell, no other pixel adds anything: mbn_confusion_metrics of it yields the trimap pixel accuracy, mIoU and the rest.
+ *     biou_u64 [C][3]: [c][0] counts the pixels with t == c and Dt <= d; [c][1] those with p == c, Dp <= d and t valid (inside [0, C): a
+ *       prediction over void truth is not scored); [c][2] those with t == c, p == c, Dt <= d and Dp <= d.
+ *     Both tables are ADDED TO: the caller clears them and a dataset accumulates over many calls. Either may be NULL, not both.
+ *   mbn_boundary_depth          depth_u8 [batch][rows][cols] = min (D, d + 1) of map [batch][rows][cols], elem_bytes 1 (uint8) or 4 (int32)
+ *   mbn_boundary_depth_ragged   the same over the maps of a ragged set of either item kind (the items' first 16 bytes): depth_u8 and map use the
+ *                               labels' dst_offset in ELEMENTS; nothing between the maps is read or written
+ *   mbn_boundary_score_i32      labels_i32 and truth (truth_bytes 1 or 4) [batch][rows][cols]. FUSED: both depths are formed in LDS and never
+ *                               reach memory
+ *   mbn_boundary_score_ragged_i32  the same over a ragged set; truth at the labels' element offsets
+ *   Half-width of the ragged forms: d_items_i32 == NULL: d holds for every item. Otherwise d_items_i32 is a DEVICE array [set batch] of int32, one
+ *     half-width per item, and d is ignored. The kernel CLAMPS an entry into [1, MBN_BOUNDARY_MAX_D]: the host cannot see a device array without
+ *     a copy, and these calls make none. mbn_boundary_d_items (readout, ratio, d_host) is the way to produce that array: pure host, it fills
+ *     d_host [set batch] from the handle's pinned items with mbn_boundary_d and answers its refusals (MBN_EINVAL also for a handle without a set).
+ * Each of the four device calls is ONE kernel, asynchronous on `stream` (NULL: the context's), capturable as one kernel node; no handle of its
+ * own, no scratch, no host copy; a persistent grid sized from the planning CU count; the ragged forms keep the handle's generation rule (a
+ * captured launch replayed after a later set does nothing) and the next set waits for them. int32 maps may be any pointers on 4 bytes, uint8 maps
+ * and depth_u8 any byte pointers; nothing outside the maps is read.
+ * MBN_EINVAL: a NULL pointer (both tables NULL); a table off 8 bytes, an int32 map off 4; batch, rows, cols or classes < 1; d < 1 (without
+ * d_items_i32); edge not 0 or 1; elem_bytes or truth_bytes not 1 or 4; d_items_i32 off 4 bytes; depth_u8 overlapping map; a handle without a
+ * set; an undersized tracked buffer (mbn_alloc's bounds rule: the maps span batch * rows * cols elements, in the ragged form
+ * max (dst_offset + rows * cols); trimap (C + 1)^2 * 8 bytes, biou C * 24 bytes, d_items_i32 4 bytes per item). MBN_EUNSUPPORTED:
+ * d > MBN_BOUNDARY_MAX_D, classes > MBN_CONFUSION_MAX_CLASSES, rows * cols >= 2^29, batch > 65535. A refusal launches nothing.
+ * mbn_boundary_envelope answers the shape part (classes = 1 for the depth calls). mbn_boundary_tile gives the tile and the LDS bytes a workgroup of
+ * the score kernel takes at this d (the depth kernel takes less than half): a seam lies at every multiple of the tile; lds_bytes is monotone in d and at
+ * most 160 KiB. The ragged forms with d_items_i32 take what d = MBN_BOUNDARY_MAX_D takes. Pure host functions.
+ *   mbn_boundary_metrics   pure C in doubles. n = biou, C = classes. For class c: den = n[c][0] + n[c][1] - n[c][2]; a class is PRESENT iff den > 0;
+ *     iou[c] = n[c][2] / den, NaN for an absent class; boundary_miou = the mean over the present classes in ascending class order (0 when there
+ *     are none); truth_band_pixels = sum of n[c][0], pred_band_pixels = sum of n[c][1]. Every ratio is one division of exact integers. iou:
+ *     [classes] or NULL. MBN_EINVAL: NULL biou or m, classes < 1; MBN_EUNSUPPORTED: classes > MBN_CONFUSION_MAX_CLASSES. */
+#define MBN_BOUNDARY_MAX_D 64
+typedef struct mbn_boundary_metrics_t {
+    double boundary_miou, truth_band_pixels, pred_band_pixels;
+    int32_t classes_present, reserved;
+} mbn_boundary_metrics_t;
+int mbn_boundary_d(int rows, int cols, double ratio);
+int mbn_boundary_d_items(mbn_ragged_readout *readout, double ratio, int32_t *d_host);
+int mbn_boundary_envelope(int elem_bytes, int classes, int batch, int rows, int cols, int d, int edge);
+int mbn_boundary_tile(int d, int *tile_rows, int *tile_cols, int *lds_bytes);
+int mbn_boundary_metrics(const uint64_t *biou, int classes, mbn_boundary_metrics_t *m, double *iou);
+int mbn_boundary_depth(mbn_context *ctx, void *depth_u8, const void *map, int elem_bytes, int batch, int rows, int cols, int d, int edge,
+                       void *stream);
+int mbn_boundary_depth_ragged(mbn_ragged_readout *readout, void *depth_u8, const void *map, int elem_bytes, int d, const void *d_items_i32, int edge,
+                              void *stream);
+int mbn_boundary_score_i32(mbn_context *ctx, void *trimap_u64, void *biou_u64, const void *labels_i32, const void *truth, int truth_bytes,
+                           int classes, int batch, int rows, int cols, int d, int edge, void *stream);
+int mbn_boundary_score_ragged_i32(mbn_ragged_readout *readout, void *trimap_u64, void *biou_u64, const void *labels_i32, const void *truth,
+                                  int truth_bytes, int classes, int d, const void *d_items_i32, int edge, void *stream);
 /* The classifier tail of the sequence as one call (MobileNet.c:2601-2792): global average pool (kernel.cl:116) ->
  * FC = pointwise with rows = cols = 1 (kernel.cl:94; bias, no ReLU: B15) -> softmax + top-k. fp32 NHWC,
  * in [batch][rows][cols][channels], fc_w [classes][channels], fc_bias [classes] or NULL; pooled_scratch
@@ -1197,6 +1260,16 @@ int  mbn_net_segment_score(mbn_net *net, const void *labels_i32, const void *tru
  * mbn_net_destroy; MBN_ENOMEM leaves the net usable. MBN_EINVAL before any segment call. Otherwise whatever the components call answers. */
 int  mbn_net_segment_regions(mbn_net *net, const void *labels_i32, void *comp_i32, mbn_region *regions, void *n_regions_i32, void *labels_out_i32,
                              int connectivity, int min_area, int ignore_label, int max_regions);
+/* The boundary score of the label maps of that same call ("score a segmentation at its boundaries" above; found exactly as mbn_net_segment_score
+ * finds it): a uniform call is one mbn_boundary_score_i32 over [batch][out_rows][out_cols], an image call mbn_boundary_score_ragged_i32 on the
+ * net's own ragged set. classes is the plan's; trimap_u64 [classes + 1][classes + 1] and biou_u64 [classes][3] are added to, either may be NULL.
+ * d > 0 is a fixed half-width and ratio is not read. d == 0 takes ratio: mbn_boundary_d of the output size for a uniform call; for an image call
+ * each image's own half-width (mbn_boundary_d_items), uploaded into a net-owned device buffer of max_batch int32 on the context's stream (made on
+ * first use, freed by mbn_net_destroy). MBN_EINVAL before any segment call or for d < 0; otherwise whatever mbn_boundary_d and the score call answer.
+ * mbn_net_segment_boundary_depth does the same for the band of the labels: depth_u8 at the labels' element offsets (mbn_boundary_depth / _ragged). */
+int  mbn_net_segment_boundary_score(mbn_net *net, const void *labels_i32, const void *truth, int truth_bytes, void *trimap_u64, void *biou_u64,
+                                    double ratio, int d, int edge);
+int  mbn_net_segment_boundary_depth(mbn_net *net, const void *labels_i32, void *depth_u8, double ratio, int d, int edge);
 /* Per-layer milliseconds of the most recent mbn_net_forward_timed call (hipEvents between layers). */
 int  mbn_net_forward_timed(mbn_net *net, const void *images, void *logits, int batch, float *layer_ms,
                            int n_layer_ms);

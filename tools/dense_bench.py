@@ -37,6 +37,12 @@
       mbn_components_i32, the connected regions of --batch label maps of 375 x 500 (main_regions): 21 / 150 / 1000 classes, random, 25 x 25-block
       and constant inputs, connectivity 4 and 8, min_area 1 (comp alone) and 50 (comp and labels_out), beside scipy.ndimage.label per class on
       the host, download included.
+
+  python tools/dense_bench.py --boundary [--reps 7] [--steps 20] [--batch 32] [--torch-steps 2] [--host-maps 2] [--no-torch] [--no-host]
+                              [--configs random,blocks,constant]
+      mbn_boundary_score_i32, the trimap and boundary-IoU tables of --batch label maps of 375 x 500 against a uint8 truth (main_boundary):
+      21 / 150 / 1000 classes, random, 25 x 25-block and constant inputs, d = 12 (ratio 0.02) and d = 3, edge 0 and 1, beside mbn_confusion_i32
+      on the same buffers, torch's one-hot / max_pool2d / bincount route and scipy.ndimage.binary_erosion per class on the host.
 """
 import argparse
 import json
@@ -586,6 +592,160 @@ def main_regions(a):
     print(json.dumps(result))
 
 
+def main_boundary(a):
+    """--boundary: mbn_boundary_score_i32 (both tables) on --batch maps of 375 x 500 (6 M pixels at 32), int32 labels against uint8 truth, at
+    21 / 150 / 1000 classes, main_score's three inputs (random: every pixel is in every band; blocks of 25 x 25 with the prediction shifted by one
+    pixel: what a label map looks like; constant: no band but the frame's), d = 12 (375 x 500 at ratio 0.02) and d = 3, edge 0 and 1.
+    Per cell, alternating within every repetition, on the SAME device buffers:
+      kernel     the fused call, tables cleared once in front (it accumulates)
+      confusion  mbn_confusion_i32: the price of contour scoring as a multiple of plain scoring
+      torch      conversions included: one_hot -> the complement -> max_pool2d with one (2 d + 1) window (edge 1: the complement padded with ones
+                 first; edge 0: the pool's own padding, which never wins) -> the own channel picks the band -> bincount of the masked cells, for
+                 truth and prediction; in image chunks of at most 4096 planes. Its tables are compared with the kernel's once per cell.
+    Each figure is the median over the repetitions of `steps` (torch: --torch-steps) back-to-back calls between two stream marks (torch: two torch
+    events); the runs are kept, the spread is (max - min) / median. floor_ms: 5 bytes a pixel over 8 TB/s.
+    host_ms, once per (classes, input, d) at edge 1: what a user has without the call: the download of both maps, then per class present
+    mask & ~scipy.ndimage.binary_erosion(mask, ones((3, 3)), iterations=d, border_value=0) for truth and prediction and the three sums, on the
+    first --host-maps maps, scaled to the batch; its biou table is compared with the kernel's on those maps."""
+    pkg = import_package()
+    torch = None
+    if not a.no_torch:
+        import torch
+        import torch.nn.functional as F
+        assert torch.cuda.is_available(), "the yardstick needs torch on the same GPU"
+    n, H, W = a.batch, 375, 500
+    pix = n * H * W
+    rng = np.random.default_rng(0)
+    result = {"batch": n, "pixels": pix, "bytes_per_pixel": 5, "floor_ms": round(1e3 * 5.0 * pix / HBM_BYTES_PER_S, 4)}
+
+    def spread(v):
+        return round((max(v) - min(v)) / statistics.median(v), 4)
+
+    with pkg.Context(0) as ctx:
+        for classes in (21, 150, 1000):
+            tc = min(classes, 256)
+            yy, xx = np.mgrid[0:H, 0:W]
+            blocks = rng.integers(0, tc, (n, H // 25 + 1, W // 25 + 2))
+            inputs = {"random": (rng.integers(0, classes, (n, H, W)).astype(np.int32), rng.integers(0, tc, (n, H, W)).astype(np.uint8)),
+                      "blocks": (blocks[:, yy // 25, (xx + 1) // 25].astype(np.int32), blocks[:, yy // 25, xx // 25].astype(np.uint8)),
+                      "constant": (np.full((n, H, W), classes - 1, np.int32), np.full((n, H, W), tc - 1, np.uint8))}
+            inputs = {k: (np.ascontiguousarray(v[0]), np.ascontiguousarray(v[1])) for k, v in inputs.items()}     # [n][H][W] in memory
+            cells, bcells = (classes + 1) ** 2, classes * 3
+            d_tri, d_bio, d_n = ctx.alloc(cells * 8), ctx.alloc(bcells * 8), ctx.alloc(cells * 8)
+            for name, (lab, tr) in inputs.items():
+                if a.configs and name not in a.configs.split(","):
+                    continue
+                if torch is not None:
+                    t_lab, t_tr = torch.from_numpy(lab).cuda(), torch.from_numpy(tr).cuda()
+                    p_lab, p_tr = t_lab.data_ptr(), t_tr.data_ptr()
+                else:
+                    t_lab, t_tr = ctx.to_device(lab), ctx.to_device(tr)
+                    p_lab, p_tr = t_lab.ptr, t_tr.ptr
+                conf = lambda: ctx.confusion(d_n.ptr, p_lab, p_tr, 1, classes, pix)
+                for d in (12, 3):
+                    host_ms, host_bio, k_host = None, None, min(a.host_maps, n)
+                    if not a.no_host:
+                        from scipy import ndimage
+                        import time
+                        t0 = time.perf_counter()
+                        h_lab = np.empty((n, H, W), np.int32)
+                        h_tr = np.empty((n, H, W), np.uint8)
+                        ctx.lib.mbn_download(ctx.h, h_lab.ctypes.data, p_lab, h_lab.nbytes)
+                        ctx.lib.mbn_download(ctx.h, h_tr.ctypes.data, p_tr, h_tr.nbytes)
+                        t_dl = time.perf_counter() - t0
+                        host_bio = np.zeros((classes, 3), np.uint64)
+                        t0 = time.perf_counter()
+                        for i in range(k_host):
+                            for c in np.union1d(np.unique(h_lab[i]), np.unique(h_tr[i])):
+                                bands = []
+                                for m in (h_tr[i] == c, h_lab[i] == c):
+                                    bands.append(m & ~ndimage.binary_erosion(m, structure=np.ones((3, 3)), iterations=d, border_value=0))
+                                host_bio[c] += np.array([bands[0].sum(), bands[1].sum(), (bands[0] & bands[1]).sum()], np.uint64)
+                        host_ms = 1e3 * (t_dl + (time.perf_counter() - t0) * n / k_host)
+                    for edge in (1, 0):
+                        fn = lambda: ctx.boundary_score(d_tri.ptr, d_bio.ptr, p_lab, p_tr, 1, classes, n, H, W, d, edge)
+                        ctx.lib.mbn_memset(ctx.h, d_tri.ptr, 0, cells * 8)
+                        ctx.lib.mbn_memset(ctx.h, d_bio.ptr, 0, bcells * 8)
+                        fn()
+                        ctx.sync()
+                        tri, bio = d_tri.download((cells,), np.uint64), d_bio.download((classes, 3), np.uint64)
+                        agree_host = None
+                        if host_bio is not None and edge == 1:
+                            ctx.lib.mbn_memset(ctx.h, d_bio.ptr, 0, bcells * 8)
+                            ctx.boundary_score(None, d_bio.ptr, p_lab, p_tr, 1, classes, k_host, H, W, d, 1)
+                            ctx.sync()
+                            agree_host = bool(np.array_equal(d_bio.download((classes, 3), np.uint64), host_bio))
+                        agree = None
+                        if torch is not None:
+                            chunk = max(1, 4096 // classes)
+
+                            def route():
+                                tri_t = torch.zeros(cells, dtype=torch.int64, device="cuda")
+                                bio_t = torch.zeros((3, classes), dtype=torch.int64, device="cuda")
+                                for i0 in range(0, n, chunk):
+                                    t, p = t_tr[i0:i0 + chunk].long(), t_lab[i0:i0 + chunk].long()
+                                    band = []
+                                    for x in (t, p):
+                                        oh = F.one_hot(x, classes).permute(0, 3, 1, 2).to(torch.float16)
+                                        comp = 1 - oh
+                                        if edge:
+                                            pooled = F.max_pool2d(F.pad(comp, (d, d, d, d), value=1.0), 2 * d + 1, stride=1)
+                                        else:
+                                            pooled = F.max_pool2d(comp, 2 * d + 1, stride=1, padding=d)
+                                        band.append((pooled * oh).sum(1) > 0)
+                                    tri_t += torch.bincount((t * (classes + 1) + p)[band[0]], minlength=cells)
+                                    bio_t[0] += torch.bincount(t[band[0]], minlength=classes)
+                                    bio_t[1] += torch.bincount(p[band[1]], minlength=classes)
+                                    bio_t[2] += torch.bincount(t[band[0] & band[1] & (t == p)], minlength=classes)
+                                return tri_t, bio_t
+
+                            tri_t, bio_t = route()
+                            agree = bool(np.array_equal(tri_t.cpu().numpy().astype(np.uint64), tri) and
+                                         np.array_equal(bio_t.t().cpu().numpy().astype(np.uint64), bio))
+                        marks_ms(ctx, fn, 2)
+                        marks_ms(ctx, conf, 2)
+                        ks, cs, ts = [], [], []
+                        for _ in range(a.reps):
+                            ks.append(marks_ms(ctx, fn, a.steps))
+                            cs.append(marks_ms(ctx, conf, a.steps))
+                            if torch is None:
+                                continue
+                            ctx.sync()
+                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            e0.record()
+                            for _ in range(a.torch_steps):
+                                route()
+                            e1.record()
+                            torch.cuda.synchronize()
+                            ts.append(e0.elapsed_time(e1) / a.torch_steps)
+                        k, c_ms = statistics.median(ks), statistics.median(cs)
+                        out = {"kernel_ms": round(k, 4), "kernel_runs_ms": [round(v, 4) for v in ks], "spread": spread(ks),
+                               "confusion_ms": round(c_ms, 4), "confusion_runs_ms": [round(v, 4) for v in cs], "kernel_over_confusion": round(k / c_ms, 2),
+                               "share_of_hbm": round(5.0 * pix / (k * 1e-3) / HBM_BYTES_PER_S, 4), "truth_band_share": round(int(tri.sum()) / pix, 4)}
+                        if ts:
+                            tm = statistics.median(ts)
+                            out.update({"torch_ms": round(tm, 3), "torch_runs_ms": [round(v, 3) for v in ts], "torch_over_kernel": round(tm / k, 1),
+                                        "tables_equal_torch": agree})
+                        if host_ms is not None:
+                            out.update({"host_ms": round(host_ms, 1), "host_maps": k_host, "host_over_kernel": round(host_ms / k, 1)})
+                            if agree_host is not None:
+                                out["biou_equal_host"] = agree_host
+                        print("classes %4d %-8s d %2d edge %d: kernel %.4f ms (%.4f - %.4f, %.1f %% of 8 TB/s at 5 B/pixel, band %.1f %%)  confusion %.4f ms  "
+                              "torch %s ms  host %s ms" % (classes, name, d, edge, k, min(ks), max(ks), 100 * out["share_of_hbm"], 100 * out["truth_band_share"],
+                                                           c_ms, ("%.3f" % out["torch_ms"]) if ts else "-",
+                                                           ("%.1f" % host_ms) if host_ms is not None else "-"), flush=True)
+                        result["classes_%d_%s_d%d_e%d" % (classes, name, d, edge)] = out
+                if torch is not None:
+                    del t_lab, t_tr
+                    torch.cuda.empty_cache()
+                else:
+                    t_lab.free()
+                    t_tr.free()
+            for b in (d_tri, d_bio, d_n):
+                b.free()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
@@ -600,9 +760,12 @@ def main():
     ap.add_argument("--ensemble", default="", help="comma list of view counts: time mbn_resample_ensemble_f32 instead: see main_ensemble")
     ap.add_argument("--score", action="store_true", help="time mbn_confusion_i32 beside torch.bincount instead: see main_score")
     ap.add_argument("--regions", action="store_true", help="time mbn_components_i32 beside scipy.ndimage.label on the host instead: see main_regions")
-    ap.add_argument("--host-maps", type=int, default=2, help="--regions: the maps the host yardstick really labels (its time is scaled to the batch)")
-    ap.add_argument("--no-host", action="store_true", help="--regions: skip the host yardstick")
+    ap.add_argument("--boundary", action="store_true", help="time mbn_boundary_score_i32 beside mbn_confusion_i32, torch and scipy instead: see main_boundary")
+    ap.add_argument("--host-maps", type=int, default=2, help="--regions, --boundary: the maps the host yardstick really works on (its time is scaled to the batch)")
+    ap.add_argument("--no-host", action="store_true", help="--regions, --boundary: skip the host yardstick")
     a = ap.parse_args()
+    if a.boundary:
+        return main_boundary(a)
     if a.regions:
         return main_regions(a)
     if a.score:
