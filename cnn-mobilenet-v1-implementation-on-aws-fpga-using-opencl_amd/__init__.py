@@ -126,6 +126,11 @@ class SegMetrics(C.Structure):
                 ("classes_present", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PanopticMetrics(C.Structure):
+    """mbn_panoptic_metrics_t (include/mbn.h, "score a segmentation by its regions")"""
+    _fields_ = [(n, C.c_double) for n in ("pq", "sq", "rq", "tp", "fp", "fn")] + [("classes_present", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Region(C.Structure):
     """mbn_region (include/mbn.h, "regions of a label map"): eight int32"""
     _fields_ = [(n, C.c_int32) for n in ("label", "area", "first_row", "first_col", "min_row", "min_col", "max_row", "max_col")]
@@ -240,6 +245,10 @@ def _declare_host(lib):
     lib.mbn_components_tile.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.mbn_components_scratch_bytes.argtypes = [C.c_int, C.c_int64]
     lib.mbn_components_scratch_bytes.restype = C.c_int64
+    lib.mbn_panoptic_envelope.argtypes = [C.c_int] * 6
+    lib.mbn_panoptic_scratch_bytes.argtypes = [C.c_int, C.c_int64]
+    lib.mbn_panoptic_scratch_bytes.restype = C.c_int64
+    lib.mbn_panoptic_metrics.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.POINTER(PanopticMetrics)] + [C.POINTER(C.c_double)] * 3
     lib.mbn_boundary_d.argtypes = [C.c_int, C.c_int, C.c_double]
     lib.mbn_boundary_envelope.argtypes = [C.c_int] * 7
     lib.mbn_boundary_tile.argtypes = [C.c_int] + [C.POINTER(C.c_int)] * 3
@@ -405,6 +414,15 @@ def load():
         lib.mbn_components_i32.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]
         lib.mbn_components_ragged_i32.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
         lib.mbn_net_segment_regions.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci]
+        lib.mbn_panoptic_create.argtypes = [vp, ci, C.c_int64, C.POINTER(vp)]
+        lib.mbn_panoptic_destroy.argtypes = [vp]
+        lib.mbn_panoptic_i32.argtypes = [vp] * 10 + [ci] + [vp] * 3 + [ci] * 5 + [vp]
+        lib.mbn_panoptic_ragged_i32.argtypes = [vp] * 11 + [ci] + [vp] * 3 + [ci] * 2 + [vp]
+        lib.mbn_widen_u8_i32.argtypes = [vp, vp, vp, C.c_int64, vp]
+        lib.mbn_ragged_readout_span.argtypes = [vp]
+        lib.mbn_ragged_readout_span.restype = C.c_int64
+        lib.mbn_net_set_panoptic_regions.argtypes = [vp, ci]
+        lib.mbn_net_segment_panoptic.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp]
         lib.mbn_boundary_d_items.argtypes = [vp, C.c_double, C.POINTER(C.c_int32)]
         lib.mbn_boundary_depth.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
         lib.mbn_boundary_depth_ragged.argtypes = [vp, vp, vp, ci, ci, vp, ci, vp]
@@ -757,6 +775,33 @@ def boundary_metrics(biou, classes, lib=None):
     return m, iou
 
 
+PANOPTIC_CHUNK = 1024            # MBN_PANOPTIC_CHUNK: the pixels of one unit of work of the two pixel kernels of mbn_panoptic_i32
+PANOPTIC_LDS_CLASSES = 1024      # MBN_PANOPTIC_LDS_CLASSES: up to here its two deciding kernels count a workgroup's classes in LDS
+NET_PANOPTIC_REGIONS = 4096      # MBN_NET_PANOPTIC_REGIONS
+
+
+def panoptic_envelope(batch, rows, cols, classes, max_pred, max_truth, lib=None) -> int:
+    """mbn_panoptic_envelope: the status (OK, EINVAL or EUNSUPPORTED) mbn_panoptic_i32 gives the shape."""
+    return (lib or host_lib()).mbn_panoptic_envelope(batch, rows, cols, classes, max_pred, max_truth)
+
+
+def panoptic_scratch_bytes(max_batch, max_slots, lib=None) -> int:
+    """mbn_panoptic_scratch_bytes: the device memory a Panoptic handle of that size holds (0: a size mbn_panoptic_create refuses)."""
+    return (lib or host_lib()).mbn_panoptic_scratch_bytes(max_batch, max_slots)
+
+
+def panoptic_metrics(pq, classes, lib=None):
+    """mbn_panoptic_metrics: (PanopticMetrics, pq_c, sq_c, rq_c: float64 [classes], NaN for an absent class) of pq, uint64 [classes][4] =
+    tp, fp, fn, S."""
+    n = np.ascontiguousarray(pq, dtype=np.uint64)
+    if n.size != classes * 4:
+        raise ValueError("pq has %d cells, classes = %d needs %d" % (n.size, classes, classes * 4))
+    m, out = PanopticMetrics(), [np.empty(classes, np.float64) for _ in range(3)]
+    _chk((lib or host_lib()).mbn_panoptic_metrics(n.ctypes.data_as(C.POINTER(C.c_uint64)), classes, C.byref(m),
+                                                  *[o.ctypes.data_as(C.POINTER(C.c_double)) for o in out]), "panoptic_metrics")
+    return (m,) + tuple(out)
+
+
 def components_scratch_bytes(max_batch, max_pixels, lib=None) -> int:
     """mbn_components_scratch_bytes: the device memory a Components handle of that size holds (0: a size mbn_components_create refuses)."""
     return (lib or host_lib()).mbn_components_scratch_bytes(max_batch, max_pixels)
@@ -1038,11 +1083,48 @@ class Context:
         _chk(self.lib.mbn_components_ragged_i32(handle.h, readout.h, comp, regions, n_regions, labels_out, labels, classes, connectivity, min_area,
                                                 ignore_label, max_regions, stream), self.last_error())
 
+    def panoptic(self, handle, pq, scored, comp_pred, pred, n_pred, max_pred, comp_truth, truth, n_truth, max_truth, batch, rows, cols, classes,
+                 match_pred=None, match_truth=None, inter=None, void=None, stream=None):
+        """mbn_panoptic_i32: pq (uint64 [classes][4] = tp, fp, fn, S; device) += the panoptic score of the predicted segment maps comp_pred
+        [batch][rows][cols] with their records pred (Region [batch][max_pred]) and counts n_pred (int32 [batch]) against the truth's; scored
+        (int32 [batch]): 0 for an image whose tables were too small, which adds nothing."""
+        _chk(self.lib.mbn_panoptic_i32(handle.h, pq, scored, match_pred, match_truth, inter, void, comp_pred, pred, n_pred, max_pred, comp_truth,
+                                       truth, n_truth, max_truth, batch, rows, cols, classes, stream), self.last_error())
+
+    def panoptic_ragged(self, handle, readout, pq, scored, comp_pred, pred, n_pred, max_pred, comp_truth, truth, n_truth, max_truth, classes,
+                        match_pred=None, match_truth=None, inter=None, void=None, stream=None):
+        """mbn_panoptic_ragged_i32: the same over the maps of a RaggedReadout's set; both maps at the labels' element offsets."""
+        _chk(self.lib.mbn_panoptic_ragged_i32(handle.h, readout.h, pq, scored, match_pred, match_truth, inter, void, comp_pred, pred, n_pred,
+                                              max_pred, comp_truth, truth, n_truth, max_truth, classes, stream), self.last_error())
+
+    def widen_u8(self, dst, src, count, stream=None):
+        """mbn_widen_u8_i32: dst (int32 [count]) = src (uint8 [count]), value for value."""
+        _chk(self.lib.mbn_widen_u8_i32(self.h, dst, src, count, stream), self.last_error())
+
     def __enter__(self):
         return self
 
     def __exit__(self, *a):
         self.close()
+
+
+class Panoptic:
+    """mbn_panoptic_create: the scratch of the panoptic kernels for up to max_batch images and max_slots = batch * max (max_pred, max_truth) table
+    entries in all, allocated once; the `handle` of Context.panoptic / panoptic_ragged."""
+
+    def __init__(self, ctx: "Context", max_batch, max_slots):
+        self.ctx = ctx
+        h = C.c_void_p()
+        _chk(ctx.lib.mbn_panoptic_create(ctx.h, max_batch, max_slots, C.byref(h)), ctx.last_error())
+        self.h = h
+        if not hasattr(ctx, "_resizers"):
+            ctx._resizers = []
+        ctx._resizers.append(self)
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.mbn_panoptic_destroy(self.h)
+            self.h = None
 
 
 class Components:
@@ -1383,6 +1465,16 @@ class Net:
     def segment_boundary_depth(self, labels_ptr, depth_ptr, ratio=0.02, d=0, edge=1):
         """mbn_net_segment_boundary_depth: the band (depth uint8) of those maps, at the labels' element offsets."""
         _chk(self.ctx.lib.mbn_net_segment_boundary_depth(self.h, labels_ptr, depth_ptr, ratio, d, edge), self.ctx.last_error())
+
+    def segment_panoptic(self, labels_ptr, truth_ptr, truth_bytes, pq_ptr, scored_ptr, connectivity=4, min_area=1):
+        """mbn_net_segment_panoptic: pq (uint64 [classes][4]) += the panoptic score of the maps the most recent successful source-size segment call
+        wrote against truth (components on both, then Context.panoptic); scored (int32 [batch]) says which images were scored."""
+        _chk(self.ctx.lib.mbn_net_segment_panoptic(self.h, labels_ptr, truth_ptr, truth_bytes, connectivity, min_area, pq_ptr, scored_ptr),
+             self.ctx.last_error())
+
+    def set_panoptic_regions(self, max_regions):
+        """mbn_net_set_panoptic_regions: the table size of both sides of segment_panoptic (NET_PANOPTIC_REGIONS until it is called)."""
+        _chk(self.ctx.lib.mbn_net_set_panoptic_regions(self.h, max_regions), self.ctx.last_error())
 
     def segment_regions(self, labels_ptr, n_regions_ptr, comp_ptr=None, regions_ptr=None, labels_out_ptr=None, connectivity=4, min_area=1,
                         ignore_label=0, max_regions=0):

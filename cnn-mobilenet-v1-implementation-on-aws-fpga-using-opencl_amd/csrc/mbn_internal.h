@@ -81,6 +81,20 @@ struct mbn_components_list {
     ~mbn_components_list();
 };
 
+// mbn_panoptic_create's handle (mbn_i32_panoptic.hip): the slots of the six kernels, allocated once
+struct mbn_panoptic {
+    mbn_context *ctx = nullptr;
+    int max_batch = 0;
+    int64_t max_slots = 0;
+    void *scratch = nullptr;                     // predicted slots [max_slots][MBN_PANOPTIC_SLOT_WORDS], truth slots [max_slots], candidates [max_slots], int32
+};
+
+// the live mbn_panoptic_create handles of a context, freed like the components handles (the destructor is in mbn_i32_panoptic.hip)
+struct mbn_panoptic_list {
+    std::vector<mbn_panoptic *> live;
+    ~mbn_panoptic_list();
+};
+
 struct mbn_context {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -106,6 +120,7 @@ struct mbn_context {
     std::vector<mbn_ragged_resizer *> ragged_resizers;   // live mbn_ragged_resizer_create handles, likewise
     std::vector<mbn_ragged_readout *> ragged_readouts;   // live mbn_ragged_readout_create handles, likewise
     mbn_components_list components;              // live mbn_components_create handles (freed with the context)
+    mbn_panoptic_list panoptic;                  // live mbn_panoptic_create handles, likewise
     std::mutex mu;
     std::map<uintptr_t, size_t> allocs;          // buffers handed out by mbn_alloc: base address -> bytes (ordered: mbn_span_check
                                                  // finds the allocation that CONTAINS an interior pointer)

@@ -142,6 +142,17 @@ int mbn_confusion_form(int classes);
 #define MBN_COMPONENTS_CHUNK 1024
 #define MBN_COMPONENTS_MAX_PIXELS ((int64_t)1 << 34)
 #define MBN_COMPONENTS_MAX_MAP ((int64_t)1 << 29)
+/* panoptic quality (mbn_i32_panoptic.hip, host/mbn_panoptic.c; the functions are declared in mbn.h). MBN_PANOPTIC_CHUNK: the pixels of one unit of
+ * the two pixel kernels (a wave holds 64 consecutive ones); MBN_PANOPTIC_BITS: the bits of a truth segment number (below
+ * MBN_COMPONENTS_MAX_REGIONS = 2^24); MBN_PANOPTIC_SLOT_WORDS: the int32 words a predicted slot holds in the handle's scratch (non-void pixels, void
+ * pixels, inter, one counter per bit), beside them one word for its candidate and one per truth slot; MBN_PANOPTIC_MAX_SLOTS: what one handle may
+ * hold; MBN_PANOPTIC_LDS_CLASSES: up to that many classes a workgroup of the two deciding kernels counts its cells of pq_u64 in LDS (32 bytes a
+ * class) and adds each to memory once, above it every segment adds to memory itself */
+#define MBN_PANOPTIC_CHUNK 1024
+#define MBN_PANOPTIC_BITS 24
+#define MBN_PANOPTIC_SLOT_WORDS (3 + MBN_PANOPTIC_BITS)
+#define MBN_PANOPTIC_LDS_CLASSES 1024
+#define MBN_PANOPTIC_MAX_SLOTS ((int64_t)1 << 32)
 /* boundary score (mbn_i32_boundary.hip, host/mbn_boundary.c; the functions are declared in mbn.h). Two half-width classes: d up to
  * MBN_BOUNDARY_SMALL_D takes tiles of MBN_BOUNDARY_SMALL_ROWS x MBN_BOUNDARY_TILE_COLS, a larger d tiles of MBN_BOUNDARY_LARGE_ROWS rows. A tile
  * keeps, per map, the value (4 bytes) and the horizontal distance (1 byte) of its own columns over its rows and d rows above and below:

@@ -68,6 +68,12 @@ struct mbn_net {
     mbn_components *components;     /* mbn_net_segment_regions: one handle, made on first use and again when a call needs more */
     int components_batch;           /* ... and what it holds */
     int64_t components_pixels;
+    /* mbn_net_segment_panoptic: its handle and what it holds, the table size of both sides (mbn_net_set_panoptic_regions), and the buffers: both
+     * segment maps and a widened uint8 truth ([panoptic_span] int32 each), both tables and both counts ([panoptic_batch] images) */
+    mbn_panoptic *panoptic;
+    int panoptic_batch, panoptic_regions, panoptic_max_regions;
+    int64_t panoptic_span;
+    void *panoptic_comp[2], *panoptic_wide, *panoptic_table[2], *panoptic_n[2];
     void *boundary_d;               /* mbn_net_segment_boundary_*: [max_batch] int32 on the device, the per-image half-widths of an image call */
     /* mbn_net_resize_views: the view resizers kept, each made for one (source size, scale, mirror, filter, pad colour); used = the clock of its last use */
     struct view_slot {
@@ -91,6 +97,20 @@ struct mbn_net {
     float *host_blob;
 };
 
+static void panoptic_release(mbn_net *net)
+{
+    if (net->panoptic) mbn_panoptic_destroy(net->panoptic);
+    net->panoptic = NULL;
+    void **bufs[] = { &net->panoptic_comp[0], &net->panoptic_comp[1], &net->panoptic_wide, &net->panoptic_table[0], &net->panoptic_table[1],
+                      &net->panoptic_n[0], &net->panoptic_n[1] };
+    for (size_t i = 0; i < sizeof bufs / sizeof bufs[0]; i++) {
+        if (*bufs[i]) mbn_free(net->ctx, *bufs[i]);
+        *bufs[i] = NULL;
+    }
+    net->panoptic_batch = net->panoptic_regions = 0;
+    net->panoptic_span = 0;
+}
+
 static const float *blob_at(const mbn_net *net, int64_t off)
 {
     return off < 0 ? NULL : (const float *)net->dev_blob + off;
@@ -108,6 +128,7 @@ static int net_alloc_common(mbn_context *ctx, const mbn_plan *plan, int max_batc
     net->fuse_stem = 1;
     net->fuse_blocks = MBN_FUSE_BLOCKS_DEFAULT;
     net->resize_filter = MBN_FILTER_BILINEAR;
+    net->panoptic_max_regions = MBN_NET_PANOPTIC_REGIONS;
     net->plan = *plan;
     net->max_batch = max_batch;
     net->num_cus = 256;
@@ -178,6 +199,7 @@ int mbn_net_destroy(mbn_net *net)
     if (net->readout) mbn_ragged_readout_destroy(net->readout);
     if (net->components) mbn_components_destroy(net->components);
     if (net->boundary_d) mbn_free(net->ctx, net->boundary_d);
+    panoptic_release(net);
     free(net->label_items);
     if (net->resize_buf) mbn_free(net->ctx, net->resize_buf);
     for (int j = 0; j < 8; j++)
@@ -1343,6 +1365,23 @@ int mbn_net_segment_score(mbn_net *net, const void *labels_i32, const void *trut
     return mbn_confusion_i32(net->ctx, counts_u64, labels_i32, truth, truth_bytes, fc->out_ch, net->score_count, NULL);
 }
 
+/* the net's one mbn_components handle holds at least the maps of the last segment call */
+static int components_ready(mbn_net *net)
+{
+    if (net->components && net->score_batch <= net->components_batch && net->score_count <= net->components_pixels) return MBN_OK;
+    /* the new handle first: when it cannot be had, the old one stays */
+    const int batch = net->score_batch > net->components_batch ? net->score_batch : net->components_batch;
+    const int64_t pixels = net->score_count > net->components_pixels ? net->score_count : net->components_pixels;
+    mbn_components *h = NULL;
+    const int rc = mbn_components_create(net->ctx, batch, pixels, &h);
+    if (rc != MBN_OK) return rc;
+    if (net->components) mbn_components_destroy(net->components);
+    net->components = h;
+    net->components_batch = batch;
+    net->components_pixels = pixels;
+    return MBN_OK;
+}
+
 int mbn_net_segment_regions(mbn_net *net, const void *labels_i32, void *comp_i32, mbn_region *regions, void *n_regions_i32, void *labels_out_i32,
                             int connectivity, int min_area, int ignore_label, int max_regions)
 {
@@ -1350,23 +1389,84 @@ int mbn_net_segment_regions(mbn_net *net, const void *labels_i32, void *comp_i32
     const mbn_layer_desc *feat, *fc;
     int rc = dense_layers(net, &feat, &fc);
     if (rc != MBN_OK) return rc;
-    if (!net->components || net->score_batch > net->components_batch || net->score_count > net->components_pixels) {
-        /* the new handle first: when it cannot be had, the old one stays */
-        const int batch = net->score_batch > net->components_batch ? net->score_batch : net->components_batch;
-        const int64_t pixels = net->score_count > net->components_pixels ? net->score_count : net->components_pixels;
-        mbn_components *h = NULL;
-        rc = mbn_components_create(net->ctx, batch, pixels, &h);
-        if (rc != MBN_OK) return rc;
-        if (net->components) mbn_components_destroy(net->components);
-        net->components = h;
-        net->components_batch = batch;
-        net->components_pixels = pixels;
-    }
+    rc = components_ready(net);
+    if (rc != MBN_OK) return rc;
     if (net->score_kind == SCORE_RAGGED)
         return mbn_components_ragged_i32(net->components, net->readout, comp_i32, regions, n_regions_i32, labels_out_i32, labels_i32, fc->out_ch,
                                          connectivity, min_area, ignore_label, max_regions, NULL);
     return mbn_components_i32(net->components, comp_i32, regions, n_regions_i32, labels_out_i32, labels_i32, net->score_batch, net->score_rows,
                               net->score_cols, fc->out_ch, connectivity, min_area, ignore_label, max_regions, NULL);
+}
+
+int mbn_net_set_panoptic_regions(mbn_net *net, int max_regions)
+{
+    if (!net || max_regions < 1) return MBN_EINVAL;
+    if (max_regions > MBN_COMPONENTS_MAX_REGIONS) return MBN_EUNSUPPORTED;
+    net->panoptic_max_regions = max_regions;
+    return MBN_OK;
+}
+
+/* the handle and the buffers of mbn_net_segment_panoptic hold `batch` images whose maps span `span` elements, with tables of the net's setting.
+ * Everything is made again when a call needs more of any of them; a failure leaves nothing behind and the net usable */
+static int panoptic_ready(mbn_net *net, int batch, int64_t span)
+{
+    const int regions = net->panoptic_max_regions;
+    if (net->panoptic && batch <= net->panoptic_batch && span <= net->panoptic_span && regions == net->panoptic_regions) return MBN_OK;
+    if (batch < net->panoptic_batch) batch = net->panoptic_batch;
+    if (span < net->panoptic_span) span = net->panoptic_span;
+    panoptic_release(net);                                         /* waits for the device: an earlier call may still read them */
+    int rc = mbn_panoptic_create(net->ctx, batch, (int64_t)batch * regions, &net->panoptic);
+    if (rc != MBN_OK) net->panoptic = NULL;
+    for (int k = 0; k < 2 && rc == MBN_OK; k++) {
+        rc = mbn_alloc(net->ctx, (size_t)span * 4, &net->panoptic_comp[k]);
+        if (rc == MBN_OK) rc = mbn_alloc(net->ctx, (size_t)batch * regions * sizeof(mbn_region), &net->panoptic_table[k]);
+        if (rc == MBN_OK) rc = mbn_alloc(net->ctx, (size_t)batch * 4, &net->panoptic_n[k]);
+    }
+    if (rc == MBN_OK) rc = mbn_alloc(net->ctx, (size_t)span * 4, &net->panoptic_wide);
+    if (rc != MBN_OK) { panoptic_release(net); return rc; }
+    net->panoptic_batch = batch;
+    net->panoptic_span = span;
+    net->panoptic_regions = regions;
+    return MBN_OK;
+}
+
+int mbn_net_segment_panoptic(mbn_net *net, const void *labels_i32, const void *truth, int truth_bytes, int connectivity, int min_area, void *pq_u64,
+                             void *scored_i32)
+{
+    if (!net || net->score_kind == SCORE_NONE || !labels_i32 || !truth || !pq_u64 || !scored_i32) return MBN_EINVAL;
+    if ((truth_bytes != 1 && truth_bytes != 4) || (truth_bytes == 4 && (uintptr_t)truth % 4)) return MBN_EINVAL;
+    const mbn_layer_desc *feat, *fc;
+    int rc = dense_layers(net, &feat, &fc);
+    if (rc != MBN_OK) return rc;
+    const int ragged = net->score_kind == SCORE_RAGGED, batch = net->score_batch, classes = fc->out_ch;
+    const int64_t span = ragged ? mbn_ragged_readout_span(net->readout) : net->score_count;
+    if (span < 1) return MBN_EINVAL;
+    rc = components_ready(net);
+    if (rc == MBN_OK) rc = panoptic_ready(net, batch, span);
+    if (rc != MBN_OK) return rc;
+    const int regions = net->panoptic_regions;
+    const void *maps[2] = { labels_i32, truth };
+    if (truth_bytes == 1) {
+        /* the flat span: the gaps of a ragged set are widened too, into this private buffer only, and nothing reads them there */
+        rc = mbn_widen_u8_i32(net->ctx, net->panoptic_wide, truth, span, NULL);
+        if (rc != MBN_OK) return rc;
+        maps[1] = net->panoptic_wide;
+    }
+    /* the two calls share the components handle's scratch: they are ordered by the context's stream */
+    for (int k = 0; k < 2; k++) {
+        rc = ragged ? mbn_components_ragged_i32(net->components, net->readout, net->panoptic_comp[k], (mbn_region *)net->panoptic_table[k],
+                                                net->panoptic_n[k], NULL, maps[k], classes, connectivity, min_area, 0, regions, NULL)
+                    : mbn_components_i32(net->components, net->panoptic_comp[k], (mbn_region *)net->panoptic_table[k], net->panoptic_n[k], NULL, maps[k],
+                                         batch, net->score_rows, net->score_cols, classes, connectivity, min_area, 0, regions, NULL);
+        if (rc != MBN_OK) return rc;
+    }
+    if (ragged)
+        return mbn_panoptic_ragged_i32(net->panoptic, net->readout, pq_u64, scored_i32, NULL, NULL, NULL, NULL, net->panoptic_comp[0],
+                                       (const mbn_region *)net->panoptic_table[0], net->panoptic_n[0], regions, net->panoptic_comp[1],
+                                       (const mbn_region *)net->panoptic_table[1], net->panoptic_n[1], regions, classes, NULL);
+    return mbn_panoptic_i32(net->panoptic, pq_u64, scored_i32, NULL, NULL, NULL, NULL, net->panoptic_comp[0], (const mbn_region *)net->panoptic_table[0],
+                            net->panoptic_n[0], regions, net->panoptic_comp[1], (const mbn_region *)net->panoptic_table[1], net->panoptic_n[1], regions,
+                            batch, net->score_rows, net->score_cols, classes, NULL);
 }
 
 /* The half-width of the two boundary calls: d > 0 as given; d == 0 from ratio, for a uniform call mbn_boundary_d of the map size (*d_out), for

@@ -37,6 +37,11 @@
  *   the order of the regions' first pixels. With --min-area N > 1 the regions of fewer than N pixels are dropped: the map written to --segment-source
  *   and the map scored by --truth are the cleaned ones, whose dropped pixels hold --ignore-label (where --min-confidence brought one), else the class
  *   count
+ *   --panoptic [--connectivity 4|8] [--min-area N] (with --segment-source and --truth; defaults 4, 1): panoptic quality. The regions of every label
+ *   map against the regions of its truth, both found on the device (mbn_net_segment_panoptic), at most 4096 a side. Behind the score line:
+ *   panoptic: connectivity=... min_area=... scored=<images scored>/<images> classes_present=... tp=... fp=... fn=... pq=... sq=... rq=...
+ *   panoptic_class: class <c> tp <n> fp <n> fn <n> pq <v> sq <v> rq <v>                               (one per present class)
+ *   and, in front of them, `panoptic: image <n> not scored: ...` for an image with more regions than that on either side.
  *   --boundary-ratio R | --boundary-d N [--boundary-edge 0|1] [--boundary-map out.pgm] (with --segment-source; edge defaults to 1): contour quality,
  *   "score a segmentation at its boundaries" in mbn.h. The half-width is N pixels, or R of every image's own diagonal (0.02 is the usual value).
  *   With --truth three kinds of line follow the score line (mbn_net_segment_boundary_score):
@@ -517,10 +522,63 @@ static int write_boundary_map(mbn_context *ctx, mbn_net *net, const boundary_opt
     return (fclose(fp) != 0) | !ok;
 }
 
+/* --panoptic [--connectivity 4|8] [--min-area N]: what the command line asked for; on = 0: nothing */
+typedef struct panoptic_opts { int on, connectivity, min_area; } panoptic_opts;
+
+/* --truth with --panoptic: the regions of the same maps against the regions of the truth (mbn_net_segment_panoptic) */
+static int panoptic_table(mbn_context *ctx, mbn_net *net, const panoptic_opts *po, int n, void *d_labels, void *d_truth, int tb, size_t cells,
+                          void *d_pq, void *d_scored, uint64_t *pq, int32_t *scored)
+{
+    CHECK(mbn_memset(ctx, d_pq, 0, cells * sizeof(uint64_t)));
+    CHECK(mbn_net_segment_panoptic(net, d_labels, d_truth, tb, po->connectivity, po->min_area, d_pq, d_scored));
+    CHECK(mbn_download(ctx, pq, d_pq, cells * sizeof(uint64_t)));
+    CHECK(mbn_download(ctx, scored, d_scored, (size_t)n * sizeof(int32_t)));
+    return 0;
+}
+
+static int score_panoptic(mbn_context *ctx, mbn_net *net, const panoptic_opts *po, int n, void *d_labels, void *d_truth, int tb, int classes)
+{
+    const size_t cells = (size_t)classes * 4;
+    uint64_t *pq = malloc(cells * sizeof(uint64_t));
+    int32_t *scored = malloc((size_t)n * sizeof(int32_t));
+    double *per = malloc(3 * (size_t)classes * sizeof(double));
+    void *d_pq = NULL, *d_scored = NULL;
+    int bad = !pq || !scored || !per;
+    if (!bad && (mbn_alloc(ctx, cells * sizeof(uint64_t), &d_pq) != MBN_OK || mbn_alloc(ctx, (size_t)n * sizeof(int32_t), &d_scored) != MBN_OK)) {
+        fprintf(stderr, "Error: --panoptic: no device memory for its table (%s)\n", mbn_last_device_error(ctx));
+        bad = 1;
+    }
+    if (!bad) bad = panoptic_table(ctx, net, po, n, d_labels, d_truth, tb, cells, d_pq, d_scored, pq, scored);
+    if (d_pq) mbn_free(ctx, d_pq);
+    if (d_scored) mbn_free(ctx, d_scored);
+    if (bad) {
+        free(pq); free(scored); free(per);
+        return 1;
+    }
+    int images = 0;
+    for (int i = 0; i < n; i++) {
+        images += scored[i] != 0;
+        if (!scored[i]) printf("panoptic: image %d not scored: more than %d regions on one side\n", i, MBN_NET_PANOPTIC_REGIONS);
+    }
+    mbn_panoptic_metrics_t m;
+    if (mbn_panoptic_metrics(pq, classes, &m, per, per + classes, per + 2 * classes) != MBN_OK) {
+        free(pq); free(scored); free(per);
+        return 1;
+    }
+    printf("panoptic: connectivity=%d min_area=%d scored=%d/%d classes_present=%d tp=%.0f fp=%.0f fn=%.0f pq=%.17g sq=%.17g rq=%.17g\n", po->connectivity,
+           po->min_area, images, n, m.classes_present, m.tp, m.fp, m.fn, m.pq, m.sq, m.rq);
+    for (int c = 0; c < classes; c++)
+        if (!isnan(per[c]))
+            printf("panoptic_class: class %d tp %llu fp %llu fn %llu pq %.17g sq %.17g rq %.17g\n", c, (unsigned long long)pq[4 * c],
+                   (unsigned long long)pq[4 * c + 1], (unsigned long long)pq[4 * c + 2], per[c], per[classes + c], per[2 * classes + c]);
+    free(pq); free(scored); free(per);
+    return 0;
+}
+
 /* --truth: scores the label maps the segment call just wrote at d_labels (image n at element dst[n]) against the files, and prints the line;
- * bo->on: the boundary lines behind it */
+ * bo->on: the boundary lines behind it; po->on: the panoptic lines behind those */
 static int score_truth(mbn_context *ctx, mbn_net *net, const char **truths, int n, const int64_t *dst, const int32_t *hs, const int32_t *ws, size_t pixels,
-                       void *d_labels, int classes, const boundary_opts *bo)
+                       void *d_labels, int classes, const boundary_opts *bo, const panoptic_opts *po)
 {
     int32_t *tv = calloc(pixels, sizeof(int32_t));
     if (!tv) return 1;
@@ -556,6 +614,10 @@ static int score_truth(mbn_context *ctx, mbn_net *net, const char **truths, int 
            m.valid, m.void_pixels, m.abstained, m.classes_present, m.pixel_accuracy, m.mean_accuracy, m.miou, m.fw_iou);
     if (bo->on) {
         const int bad = score_boundary(ctx, net, bo, d_labels, d_truth, tb, classes, hs[0], ws[0]);
+        if (bad) return bad;
+    }
+    if (po->on) {
+        const int bad = score_panoptic(ctx, net, po, n, d_labels, d_truth, tb, classes);
         if (bad) return bad;
     }
     CHECK(mbn_free(ctx, d_truth));
@@ -621,7 +683,7 @@ static int write_confidence_map(const char *path, const float *prob, int rows, i
  * n_truth > 0 (--truth, one per image): the maps are scored against them on the device before anything is written */
 static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int n_ppm, const char *path, int classes, int fit, const char *conf_path,
                           float min_conf, int ignore, const float *scales, const int32_t *mirrors, int n_views, const char **truths, int n_truth,
-                          const region_opts *ro, const boundary_opts *bo)
+                          const region_opts *ro, const boundary_opts *bo, const panoptic_opts *po)
 {
     int64_t *offs = malloc(sizeof(int64_t) * (size_t)n_ppm), *dst = malloc(sizeof(int64_t) * (size_t)n_ppm);
     int32_t *hs = malloc(sizeof(int32_t) * (size_t)n_ppm), *ws = malloc(sizeof(int32_t) * (size_t)n_ppm);
@@ -682,7 +744,7 @@ static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int
     }
     CHECK(mbn_download(ctx, labels, d_maps, sizeof(int) * (size_t)hs[0] * ws[0]));        /* image 0 is first in the buffer */
     if (n_truth > 0) {                                          /* the maps are where every path above wrote them: image n at element dst[n] */
-        bad = score_truth(ctx, net, truths, n_truth, dst, hs, ws, pixels, d_maps, classes, bo);
+        bad = score_truth(ctx, net, truths, n_truth, dst, hs, ws, pixels, d_maps, classes, bo, po);
         if (bad) return bad;
     }
     if (bo->map) {
@@ -765,6 +827,8 @@ int main(int argc, char **argv)
     const char *tta = NULL;
     region_opts regions = { 0, 4, 1, 256 };
     int region_flags = 0;                                       /* --connectivity, --min-area or --max-regions seen */
+    int max_regions_flag = 0;                                   /* --max-regions seen: it belongs to --regions alone */
+    panoptic_opts panoptic = { 0, 4, 1 };
     boundary_opts boundary = { 0, 0, 1, 0.0, NULL };
     int boundary_flags = 0;                                     /* --boundary-edge seen */
     int tta_flip = 0, n_views = 0;
@@ -796,13 +860,14 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--tta-flip")) tta_flip = 1;
         else if (!strcmp(argv[i], "--truth") && i + 1 < argc) truths[n_truth++] = argv[++i];
         else if (!strcmp(argv[i], "--regions")) regions.on = 1;
+        else if (!strcmp(argv[i], "--panoptic")) panoptic.on = 1;
         else if (!strcmp(argv[i], "--boundary-ratio") && i + 1 < argc) { boundary.ratio = atof(argv[++i]); boundary.on |= 1; }
         else if (!strcmp(argv[i], "--boundary-d") && i + 1 < argc) { boundary.d = atoi(argv[++i]); boundary.on |= 2; }
         else if (!strcmp(argv[i], "--boundary-edge") && i + 1 < argc) { boundary.edge = atoi(argv[++i]); boundary_flags = 1; }
         else if (!strcmp(argv[i], "--boundary-map") && i + 1 < argc) boundary.map = argv[++i];
         else if (!strcmp(argv[i], "--connectivity") && i + 1 < argc) { regions.connectivity = atoi(argv[++i]); region_flags = 1; }
         else if (!strcmp(argv[i], "--min-area") && i + 1 < argc) { regions.min_area = atoi(argv[++i]); region_flags = 1; }
-        else if (!strcmp(argv[i], "--max-regions") && i + 1 < argc) { regions.max_regions = atoi(argv[++i]); region_flags = 1; }
+        else if (!strcmp(argv[i], "--max-regions") && i + 1 < argc) { regions.max_regions = atoi(argv[++i]); region_flags = max_regions_flag = 1; }
         else if (!strcmp(argv[i], "--fit") && i + 1 < argc && fit_of(argv[i + 1]) >= 0) fit = fit_of(argv[++i]);
         else if (!strcmp(argv[i], "--pad-color") && i + 1 < argc && pad_color_of(argv[i + 1], pad_rgb)) i++;
         else if (!strcmp(argv[i], "--crop-fraction") && i + 1 < argc) crop_fraction = (float)atof(argv[++i]);
@@ -819,7 +884,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--literal")) literal = 1;
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
-            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]] [--truth F.pgm ...] [--regions [--connectivity 4|8] [--min-area N] [--max-regions M]] [--boundary-ratio R | --boundary-d N [--boundary-edge 0|1] [--boundary-map OUT.pgm]]] [--segment-confidence OUT.pgm] "
+            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]] [--truth F.pgm ...] [--regions [--connectivity 4|8] [--min-area N] [--max-regions M]] [--boundary-ratio R | --boundary-d N [--boundary-edge 0|1] [--boundary-map OUT.pgm]] [--panoptic [--connectivity 4|8] [--min-area N]]] [--segment-confidence OUT.pgm] "
                             "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n", argv[0]);
             return 2;
         }
@@ -869,8 +934,18 @@ int main(int argc, char **argv)
         if (boundary.on == 1) boundary.d = 0;
         boundary.on = n_truth > 0;
     }
-    if ((regions.on || region_flags) && (!regions.on || !segment_src)) {
-        fprintf(stderr, "--regions needs --segment-source; --connectivity, --min-area and --max-regions need --regions\n");
+    if (panoptic.on && (!segment_src || n_truth == 0)) {
+        fprintf(stderr, "--panoptic needs --segment-source and --truth\n");
+        return 2;
+    }
+    if ((regions.on && !segment_src) || (region_flags && !regions.on && !panoptic.on) || (max_regions_flag && !regions.on)) {
+        fprintf(stderr, "--regions needs --segment-source; --connectivity and --min-area need --regions or --panoptic, --max-regions needs --regions\n");
+        return 2;
+    }
+    panoptic.connectivity = regions.connectivity;
+    panoptic.min_area = regions.min_area;
+    if (panoptic.on && ((panoptic.connectivity != 4 && panoptic.connectivity != 8) || panoptic.min_area < 1)) {
+        fprintf(stderr, "bad --connectivity (4 or 8) or --min-area (N >= 1)\n");
         return 2;
     }
     if (regions.on && ((regions.connectivity != 4 && regions.connectivity != 8) || regions.min_area < 1 || regions.max_regions < 0 ||
@@ -1035,7 +1110,7 @@ int main(int argc, char **argv)
     }
     if (segment_src || segment_conf) {
         const int bad = segment_source(ctx, net, ppms, n_ppm, segment_src, classes, fit, segment_conf, min_conf, have_ignore ? ignore_label : -1,
-                                       view_scales, view_mirrors, n_views, truths, n_truth, &regions, &boundary);
+                                       view_scales, view_mirrors, n_views, truths, n_truth, &regions, &boundary, &panoptic);
         if (bad) return bad;
     }
     mbn_net_destroy(net);

@@ -619,6 +619,79 @@ int mbn_components_i32(mbn_components *h, void *comp_i32, mbn_region *regions, v
 int mbn_components_ragged_i32(mbn_components *h, mbn_ragged_readout *readout, void *comp_i32, mbn_region *regions, void *n_regions_i32,
                               void *labels_out_i32, const void *labels_i32, int classes, int connectivity, int min_area, int ignore_label,
                               int max_regions, void *stream);
+/* Score a segmentation by its regions: panoptic quality (PQ = SQ x RQ, Kirillov et al., CVPR 2019), on the device.
+ * Normative (tests/panoptic_ref.py is the numpy form, written as the pair histogram; everything the device writes is an integer, so the result is
+ * a function of the input alone: the same bytes at every planning CU count, in both forms, on every run and on graph replay). For one image:
+ *   comp_pred [rows][cols] int32: a predicted segment number in [0, n_pred), anything else (-1) is "no segment"; records pred [max_pred].
+ *   comp_truth [rows][cols], n_truth, truth [max_truth]: the same for the truth; a truth pixel with comp_truth < 0 is VOID. The records are
+ *     mbn_region; only .label and .area are read, and .area must be the number of pixels that carry the segment's number. The calls do not care
+ *     who made the maps: two mbn_components_i32 calls are the usual source, whole-class "stuff" segments are as good. A predicted pixel of no
+ *     segment still counts in its truth segment's area. With areas that are not the maps' the matches are unspecified (a pair whose union
+ *     would fall below its inter never matches, two p may claim one g and either is recorded); nothing faults and nothing outside the tables
+ *     is touched.
+ *   For a predicted segment p and a truth segment g: inter (p, g) = the pixels in both; void (p) = the pixels of p over void truth;
+ *     union (p, g) = area (p) - void (p) + area (g) - inter (p, g).
+ *   p and g MATCH iff label (p) == label (g) and 2 * inter > union, in int64 and exact: IoU = 1/2 exactly is no match. A segment has at most
+ *     one match on either side (a match needs inter > (area (p) - void (p)) / 2 and inter > area (g) / 2).
+ *   A matched p is a TRUE POSITIVE of its class; an unmatched g a FALSE NEGATIVE of its class; an unmatched p a FALSE POSITIVE of its class,
+ *     unless 2 * void (p) > area (p): then it is EXCUSED and counts nowhere (a tie is a false positive).
+ *   This is pq_compute_single_core of the COCO panoptic API with the crowd rule left out.
+ *   pq_u64 [classes][4] = tp, fp, fn, S, row-major on 8 bytes. The calls ADD to it: the caller clears it (mbn_memset) and a dataset accumulates
+ *     over many calls. S is the sum over the matches of floor (inter * 2^32 / union) (inter < 2^29: the product fits a uint64). A segment whose
+ *     label lies outside [0, classes) adds nothing to pq_u64; it is matched and written to the per-segment outputs like any other.
+ * Outputs per image:
+ *   scored_i32 [batch]                  1: the image was scored. 0: n_pred > max_pred or n_truth > max_truth: the image adds NOTHING to pq_u64 and
+ *                                       none of its other outputs is written. Decided on the device from n_*_i32; a negative n counts as 0. Required.
+ *   match_pred_i32 [batch][max_pred]    the matched g; -1 for a false positive; -2 for an excused segment. May be NULL.
+ *   match_truth_i32 [batch][max_truth]  the matched p, or -1. May be NULL.
+ *   inter_i32 [batch][max_pred]         inter of the match, else 0. May be NULL.
+ *   void_i32 [batch][max_pred]          void (p). May be NULL.
+ *   Entries are written for i < n only; the rest are untouched.
+ *   mbn_panoptic_i32         maps [batch][rows][cols], tables [batch][max_*], n_*_i32 [batch] (device, as mbn_components_i32 wrote them)
+ *   mbn_panoptic_ragged_i32  the maps of a ragged set of either item kind: both maps at the labels' dst_offset, nothing between the maps is read;
+ *                            the tables are [set batch][max_*]. It keeps the handle's generation rule (a captured launch replayed after a later
+ *                            set does nothing) and the next set waits for it
+ * Both are a FIXED sequence of six kernels on `stream` (NULL: the context's): clear, vote, candidate, intersect, decide, truth. No host decision,
+ * allocation, copy or blocking call: a call may be captured as a linear chain of kernel nodes. The grids are sized from the planning CU count; a
+ * unit of the two pixel kernels is MBN_PANOPTIC_CHUNK = 1024 pixels. Calls on one handle share its scratch: they must be ordered on one stream.
+ * The handle holds all scratch: mbn_panoptic_scratch_bytes (max_batch, max_slots) = 116 bytes per slot, rounded up to 256, a function of those
+ * two numbers only, never of the pixel count. A call needs batch <= max_batch and batch * max (max_pred, max_truth) <= max_slots.
+ * mbn_shutdown frees the handles still alive.
+ * MBN_EINVAL: a NULL handle, pq_u64, scored_i32, map, table or n_*_i32; a pointer off 4 bytes (pq_u64 off 8); batch, rows, cols, classes,
+ * max_pred or max_truth < 1; a request over the handle's limits; a ragged handle without a set or of another context; an undersized tracked
+ * buffer (mbn_alloc's bounds rule: the maps span batch * rows * cols elements, in the ragged form max (dst_offset + rows * cols); the tables
+ * batch * max_* records or elements; pq_u64 classes * 32 bytes; scored_i32 and n_*_i32 batch elements). MBN_EUNSUPPORTED: rows * cols >= 2^29,
+ * batch > 65535, max_pred or max_truth > MBN_COMPONENTS_MAX_REGIONS, classes > MBN_CONFUSION_MAX_CLASSES. A refusal launches nothing.
+ * mbn_panoptic_envelope answers the shape part; it and _scratch_bytes (0 for arguments _create refuses) are pure host functions.
+ * mbn_panoptic_create: MBN_EINVAL for max_batch < 1 or max_slots < 1, MBN_EUNSUPPORTED for max_batch > 65535 or max_slots > 2^32, MBN_ENOMEM
+ * when the device has no room.
+ *   mbn_panoptic_metrics   pure C in doubles. For class c with iou = ldexp ((double) S, -32) and den = 2 * tp + fp + fn: a class is PRESENT iff
+ *     tp + fp + fn > 0; pq_c = 2 * iou / den, rq_c = 2 * tp / den, sq_c = tp ? iou / tp : 0, each one division; NaN for an absent class.
+ *     m: pq, sq, rq = the means over the present classes, summed in ascending class order (0 when there are none); tp, fp, fn = the totals;
+ *     classes_present. pq_c, sq_c, rq_c: [classes] or NULL. MBN_EINVAL: NULL pq or m, classes < 1; MBN_EUNSUPPORTED: classes >
+ *     MBN_CONFUSION_MAX_CLASSES. */
+typedef struct mbn_panoptic_metrics_t {
+    double pq, sq, rq, tp, fp, fn;
+    int32_t classes_present, reserved;
+} mbn_panoptic_metrics_t;
+typedef struct mbn_panoptic mbn_panoptic;
+int mbn_panoptic_create(mbn_context *ctx, int max_batch, int64_t max_slots, mbn_panoptic **h);
+int mbn_panoptic_destroy(mbn_panoptic *h);
+int64_t mbn_panoptic_scratch_bytes(int max_batch, int64_t max_slots);
+int mbn_panoptic_envelope(int batch, int rows, int cols, int classes, int max_pred, int max_truth);
+int mbn_panoptic_metrics(const uint64_t *pq, int classes, mbn_panoptic_metrics_t *m, double *pq_c, double *sq_c, double *rq_c);
+int mbn_panoptic_i32(mbn_panoptic *h, void *pq_u64, void *scored_i32, void *match_pred_i32, void *match_truth_i32, void *inter_i32, void *void_i32,
+                     const void *comp_pred_i32, const mbn_region *pred, const void *n_pred_i32, int max_pred, const void *comp_truth_i32,
+                     const mbn_region *truth, const void *n_truth_i32, int max_truth, int batch, int rows, int cols, int classes, void *stream);
+int mbn_panoptic_ragged_i32(mbn_panoptic *h, mbn_ragged_readout *readout, void *pq_u64, void *scored_i32, void *match_pred_i32,
+                            void *match_truth_i32, void *inter_i32, void *void_i32, const void *comp_pred_i32, const mbn_region *pred,
+                            const void *n_pred_i32, int max_pred, const void *comp_truth_i32, const mbn_region *truth, const void *n_truth_i32,
+                            int max_truth, int classes, void *stream);
+/* Helpers of the layers above: a uint8 map widened to int32 value for value (255 stays 255, void for classes <= 255), one kernel on `stream`;
+ * and the elements the maps of a ragged read-out's last set span, max (dst_offset + rows * cols) (0 without a set). mbn_widen_u8_i32: MBN_EINVAL
+ * for a NULL pointer, dst_i32 off 4 bytes, count < 1 or an undersized tracked buffer. */
+int mbn_widen_u8_i32(mbn_context *ctx, void *dst_i32, const void *src_u8, int64_t count, void *stream);
+int64_t mbn_ragged_readout_span(const mbn_ragged_readout *readout);
 /* Score a segmentation at its boundaries: boundary IoU (Cheng et al., CVPR 2021) and the trimap scores of the DeepLab papers, on the device
  * (DESIGN.md 7d.6). Both rest on the DEPTH of a pixel: its Chebyshev distance to the nearest pixel that carries another value. The arithmetic is
  * integer: every result is pinned bit for bit at every planning CU count and on graph replay. Normative (tests/boundary_ref.py is the numpy form):
@@ -1270,6 +1343,20 @@ int  mbn_net_segment_regions(mbn_net *net, const void *labels_i32, void *comp_i3
 int  mbn_net_segment_boundary_score(mbn_net *net, const void *labels_i32, const void *truth, int truth_bytes, void *trimap_u64, void *biou_u64,
                                     double ratio, int d, int edge);
 int  mbn_net_segment_boundary_depth(mbn_net *net, const void *labels_i32, void *depth_u8, double ratio, int d, int edge);
+/* The panoptic quality of the label maps of that same call ("score a segmentation by its regions" above; found exactly as mbn_net_segment_score
+ * finds it) against `truth` (uint8 or int32, truth_bytes 1 or 4; in an image call at the labels' dst_offsets): mbn_components on the labels, the same
+ * on the truth (classes the plan's, `connectivity` and `min_area` for both, a label or truth value outside [0, classes) belongs to no segment:
+ * the usual 255 is void), then mbn_panoptic: pq_u64 [classes][4] is added to, scored_i32 [batch] says which images were scored: an image with more
+ * than the setting's regions on either side is NOT scored, and that is reported here, not hidden. A uint8 truth is first widened to int32 over the
+ * flat span of the maps into a net-owned buffer. The net owns the panoptic handle, both segment maps, both tables and counts: made on first use,
+ * made again when a later call needs more, freed by mbn_net_destroy; MBN_ENOMEM leaves the net usable. Everything runs on the context's stream with
+ * no copy to the host. mbn_net_set_panoptic_regions: the table size of both sides, MBN_NET_PANOPTIC_REGIONS until it is called (MBN_EINVAL below 1,
+ * MBN_EUNSUPPORTED above MBN_COMPONENTS_MAX_REGIONS). MBN_EINVAL before any segment call, for a NULL pointer, truth_bytes not 1 or 4 or an int32
+ * truth off 4 bytes; otherwise whatever the components and panoptic calls answer. */
+#define MBN_NET_PANOPTIC_REGIONS 4096
+int  mbn_net_set_panoptic_regions(mbn_net *net, int max_regions);
+int  mbn_net_segment_panoptic(mbn_net *net, const void *labels_i32, const void *truth, int truth_bytes, int connectivity, int min_area, void *pq_u64,
+                              void *scored_i32);
 /* Per-layer milliseconds of the most recent mbn_net_forward_timed call (hipEvents between layers). */
 int  mbn_net_forward_timed(mbn_net *net, const void *images, void *logits, int batch, float *layer_ms,
                            int n_layer_ms);

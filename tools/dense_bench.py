@@ -43,6 +43,12 @@
       mbn_boundary_score_i32, the trimap and boundary-IoU tables of --batch label maps of 375 x 500 against a uint8 truth (main_boundary):
       21 / 150 / 1000 classes, random, 25 x 25-block and constant inputs, d = 12 (ratio 0.02) and d = 3, edge 0 and 1, beside mbn_confusion_i32
       on the same buffers, torch's one-hot / max_pool2d / bincount route and scipy.ndimage.binary_erosion per class on the host.
+
+  python tools/dense_bench.py --panoptic [--reps 7] [--steps 20] [--batch 32] [--torch-steps 2] [--no-torch] [--no-host]
+                              [--configs blocks,random,constant]
+      mbn_panoptic_i32, the panoptic quality of --batch label maps of 375 x 500 against a truth (main_panoptic): 21 / 1000 classes, 25 x 25-block
+      (the prediction shifted and with noise), random and constant inputs; the scoring call alone and the whole chain of two mbn_components_i32
+      and the score, beside torch.unique of the (predicted, truth) pairs on the same buffers and numpy's after a download.
 """
 import argparse
 import json
@@ -746,6 +752,175 @@ def main_boundary(a):
     print(json.dumps(result))
 
 
+def pq_from_pairs(img, p, g, cnt, rec_p, n_p, rec_t, n_t, classes):
+    """pq uint64 [classes][4] from the pair histogram of a batch: (img, p, g) unique with p >= 0, g = -1 over void truth, cnt pixels each. The match
+    rule of include/mbn.h, "score a segmentation by its regions", vectorised; rec_*: int64 [batch][cap][8], n_*: [batch]"""
+    batch, cap_p, cap_t = rec_p.shape[0], rec_p.shape[1], rec_t.shape[1]
+    void = np.zeros(batch * cap_p, np.int64)
+    void[(img * cap_p + p)[g < 0]] = cnt[g < 0]
+    k = g >= 0
+    img, p, g, cnt = img[k], p[k], g[k], cnt[k]
+    lab_p, lab_g = rec_p[img, p, 0], rec_t[img, g, 0]
+    union = rec_p[img, p, 1] - void[img * cap_p + p] + rec_t[img, g, 1] - cnt
+    match = (lab_p == lab_g) & (2 * cnt > union)
+    pq = np.zeros((classes, 4), np.uint64)
+    inside = match & (lab_p >= 0) & (lab_p < classes)
+    pq[:, 0] = np.bincount(lab_p[inside], minlength=classes).astype(np.uint64)
+    np.add.at(pq[:, 3], lab_p[inside], (cnt[inside].astype(np.uint64) << np.uint64(32)) // union[inside].astype(np.uint64))
+    hit_p, hit_g = np.zeros(batch * cap_p, bool), np.zeros(batch * cap_t, bool)
+    hit_p[(img * cap_p + p)[match]] = True
+    hit_g[(img * cap_t + g)[match]] = True
+    listed_p, listed_g = np.arange(cap_p)[None, :] < n_p[:, None], np.arange(cap_t)[None, :] < n_t[:, None]
+    labs_p, labs_g = rec_p[:, :, 0], rec_t[:, :, 0]
+    fp = listed_p & ~hit_p.reshape(batch, cap_p) & ~(2 * void.reshape(batch, cap_p) > rec_p[:, :, 1]) & (labs_p >= 0) & (labs_p < classes)
+    fn = listed_g & ~hit_g.reshape(batch, cap_t) & (labs_g >= 0) & (labs_g < classes)
+    pq[:, 1] = np.bincount(labs_p[fp], minlength=classes).astype(np.uint64)
+    pq[:, 2] = np.bincount(labs_g[fn], minlength=classes).astype(np.uint64)
+    return pq
+
+
+def main_panoptic(a):
+    """--panoptic: mbn_panoptic_i32 on --batch maps of 375 x 500 (6 M pixels at 32) at 21 / 1000 classes. Three inputs per class count:
+      blocks     the truth is blocks of 25 x 25 pixels of one class; the prediction is the same blocks shifted by two columns with 3 % of the
+                 pixels at random classes: what a label map looks like
+      random     labels uniform over the classes on both sides: at 1000 classes nearly every pixel is a segment of its own, no majorities
+      constant   one class everywhere on both sides: one segment a map, every wave inside it
+    The segment maps, tables and counts come from mbn_components_i32 (connectivity 4, min_area 1) with tables of 375 x 500 records a side, so
+    every image is scored. Per cell, alternating within every repetition, on the SAME device buffers:
+      score      mbn_panoptic_i32 alone
+      chain      mbn_components_i32 on the labels, on the truth, then the score: what mbn_net_segment_panoptic issues
+      torch      torch.unique ((image * P + pred) * (T + 1) + truth + 1, return_counts=True) over the pixels of the predicted segments, the key's
+                 construction included: the pair histogram alone, without the match rule (--torch-steps calls per repetition)
+    Each figure is the median over the repetitions of `steps` back-to-back calls between two stream marks (torch: two torch events); the runs are
+    kept, the spread is (max - min) / median. floor_ms: the two pixel passes read 16 bytes a pixel, over 8 TB/s.
+    numpy_ms, once per cell: the download of both segment maps, np.unique of the same keys and the match rule in numpy (pq_from_pairs).
+    pq_u64 of the call, of torch's pairs and of numpy's pairs are asserted equal, and every image scored."""
+    import time
+    pkg = import_package()
+    torch = None
+    if not a.no_torch:
+        import torch
+        assert torch.cuda.is_available(), "the yardstick needs torch on the same GPU"
+    n, H, W = a.batch, 375, 500
+    pix, cap = n * H * W, H * W
+    rng = np.random.default_rng(0)
+    result = {"batch": n, "pixels": pix, "max_regions": cap, "bytes_per_pixel": 16, "floor_ms": round(1e3 * 16.0 * pix / HBM_BYTES_PER_S, 4)}
+
+    def spread(v):
+        return round((max(v) - min(v)) / statistics.median(v), 4)
+
+    with pkg.Context(0) as ctx:
+        comps, handle = pkg.Components(ctx, n, pix), pkg.Panoptic(ctx, n, n * cap)
+        result["scratch_bytes"] = pkg.panoptic_scratch_bytes(n, n * cap)
+        if torch is not None:
+            t_comp = [torch.empty((n, H, W), dtype=torch.int32, device="cuda") for _ in range(2)]
+            comp_ptr, d_comp = [t.data_ptr() for t in t_comp], None
+        else:
+            d_comp = [ctx.alloc(4 * pix) for _ in range(2)]
+            comp_ptr = [b.ptr for b in d_comp]
+        d_reg, d_n = [ctx.alloc(32 * n * cap) for _ in range(2)], [ctx.alloc(4 * n) for _ in range(2)]
+        d_scored = ctx.alloc(4 * n)
+        for classes in (21, 1000):
+            yy, xx = np.mgrid[0:H, 0:W]
+            coarse = rng.integers(0, classes, (n, H // 25 + 1, W // 25 + 2))
+            shifted = coarse[:, yy // 25, (xx + 23) // 25].astype(np.int32)              # the blocks of the truth, two columns to the right
+            noise = rng.random((n, H, W)) < 0.03
+            shifted[noise] = rng.integers(0, classes, int(noise.sum()))
+            inputs = {"blocks": (shifted, coarse[:, yy // 25, xx // 25 + 1].astype(np.int32)),
+                      "random": (rng.integers(0, classes, (n, H, W)).astype(np.int32), rng.integers(0, classes, (n, H, W)).astype(np.int32)),
+                      "constant": (np.full((n, H, W), classes - 1, np.int32), np.full((n, H, W), classes - 1, np.int32))}
+            d_pq = ctx.alloc(32 * classes)
+            for name, maps in inputs.items():
+                if a.configs and name not in a.configs.split(","):
+                    continue
+                d_lab = [ctx.to_device(m) for m in maps]
+
+                def regions(k):
+                    ctx.components(comps, d_lab[k].ptr, n, H, W, classes, d_n[k].ptr, comp=comp_ptr[k], regions=d_reg[k].ptr, connectivity=4,
+                                   min_area=1, max_regions=cap)
+
+                def score():
+                    ctx.panoptic(handle, d_pq.ptr, d_scored.ptr, comp_ptr[0], d_reg[0].ptr, d_n[0].ptr, cap, comp_ptr[1], d_reg[1].ptr, d_n[1].ptr,
+                                 cap, n, H, W, classes)
+
+                def chain():
+                    regions(0)
+                    regions(1)
+                    score()
+
+                ctx.lib.mbn_memset(ctx.h, d_pq.ptr, 0, 32 * classes)
+                chain()
+                ctx.sync()
+                ours = d_pq.download((classes, 4), np.uint64)
+                assert d_scored.download((n,), np.int32).all(), "every image is scored"
+                counts = [b.download((n,), np.int32).astype(np.int64) for b in d_n]
+                recs = [b.download((n, cap, 8), np.int32).astype(np.int64) for b in d_reg]
+
+                def keys_to_pq(keys, cnt):
+                    g = keys % (cap + 1) - 1
+                    ip = keys // (cap + 1)
+                    return pq_from_pairs(ip // cap, ip % cap, g, cnt, recs[0], counts[0], recs[1], counts[1], classes)
+
+                out = {"segments_per_map": [round(float(c.mean()), 1) for c in counts], "tp_fp_fn": [int(v) for v in ours[:, :3].sum(0)]}
+                if not a.no_host:
+                    t0 = time.perf_counter()
+                    cp = np.empty((n, H, W), np.int32)
+                    ct = np.empty((n, H, W), np.int32)
+                    ctx.lib.mbn_download(ctx.h, cp.ctypes.data, comp_ptr[0], cp.nbytes)
+                    ctx.lib.mbn_download(ctx.h, ct.ctypes.data, comp_ptr[1], ct.nbytes)
+                    image = np.arange(n, dtype=np.int64)[:, None, None]
+                    key = ((image * cap + cp) * (cap + 1) + ct + 1)[cp >= 0]
+                    keys, cnt = np.unique(key, return_counts=True)
+                    host = keys_to_pq(keys, cnt)
+                    out["numpy_ms"] = round(1e3 * (time.perf_counter() - t0), 1)
+                    assert np.array_equal(host, ours), (classes, name, "numpy")
+                ts = []
+                if torch is not None:
+                    t_image = torch.arange(n, dtype=torch.int64, device="cuda")[:, None, None]
+
+                    def pairs():
+                        key = ((t_image * cap + t_comp[0]) * (cap + 1) + t_comp[1] + 1)[t_comp[0] >= 0]
+                        return torch.unique(key, return_counts=True)
+
+                    keys, cnt = pairs()
+                    torch.cuda.synchronize()
+                    assert np.array_equal(keys_to_pq(keys.cpu().numpy(), cnt.cpu().numpy()), ours), (classes, name, "torch")
+                    del keys, cnt
+                marks_ms(ctx, score, 2)
+                marks_ms(ctx, chain, 2)
+                ss, cs = [], []
+                for _ in range(a.reps):
+                    ss.append(marks_ms(ctx, score, a.steps))
+                    cs.append(marks_ms(ctx, chain, a.steps))
+                    if torch is not None:
+                        ctx.sync()
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        for _ in range(a.torch_steps):
+                            pairs()
+                        e1.record()
+                        torch.cuda.synchronize()
+                        ts.append(e0.elapsed_time(e1) / a.torch_steps)
+                s_ms, c_ms = statistics.median(ss), statistics.median(cs)
+                out.update({"score_ms": round(s_ms, 4), "score_runs_ms": [round(v, 4) for v in ss], "score_spread": spread(ss),
+                            "share_of_hbm": round(16.0 * pix / (s_ms * 1e-3) / HBM_BYTES_PER_S, 4),
+                            "chain_ms": round(c_ms, 4), "chain_runs_ms": [round(v, 4) for v in cs], "chain_spread": spread(cs)})
+                if ts:
+                    t_ms = statistics.median(ts)
+                    out.update({"torch_ms": round(t_ms, 4), "torch_runs_ms": [round(v, 4) for v in ts], "torch_over_score": round(t_ms / s_ms, 1)})
+                print("classes %4d %-8s: score %.4f ms (spread %.1f %%, floor %.4f ms, %.1f %% of 8 TB/s)  chain %.4f ms (spread %.1f %%)  torch %s ms  "
+                      "numpy %s ms  segments/map %s  tp, fp, fn %s" %
+                      (classes, name, s_ms, 100 * out["score_spread"], result["floor_ms"], 100 * out["share_of_hbm"], c_ms, 100 * out["chain_spread"],
+                       ("%.4f" % out["torch_ms"]) if ts else "-", out.get("numpy_ms", "-"), out["segments_per_map"], out["tp_fp_fn"]), flush=True)
+                result["classes_%d_%s" % (classes, name)] = out
+                for b in d_lab:
+                    b.free()
+            d_pq.free()
+        handle.close()
+        comps.close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
@@ -761,9 +936,12 @@ def main():
     ap.add_argument("--score", action="store_true", help="time mbn_confusion_i32 beside torch.bincount instead: see main_score")
     ap.add_argument("--regions", action="store_true", help="time mbn_components_i32 beside scipy.ndimage.label on the host instead: see main_regions")
     ap.add_argument("--boundary", action="store_true", help="time mbn_boundary_score_i32 beside mbn_confusion_i32, torch and scipy instead: see main_boundary")
+    ap.add_argument("--panoptic", action="store_true", help="time mbn_panoptic_i32 beside torch.unique and numpy's pair histogram instead: see main_panoptic")
     ap.add_argument("--host-maps", type=int, default=2, help="--regions, --boundary: the maps the host yardstick really works on (its time is scaled to the batch)")
     ap.add_argument("--no-host", action="store_true", help="--regions, --boundary: skip the host yardstick")
     a = ap.parse_args()
+    if a.panoptic:
+        return main_panoptic(a)
     if a.boundary:
         return main_boundary(a)
     if a.regions:
