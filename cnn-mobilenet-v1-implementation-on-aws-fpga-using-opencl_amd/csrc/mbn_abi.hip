@@ -10,16 +10,12 @@
 
 mbn_tunables g_mbn_tune;
 
-namespace {
-
-// Buffer-size guard. Every buffer handed out by mbn_alloc is recorded with its size; when a pointer given to a layer call
+// Buffer-size guard. Every buffer handed out by mbn_alloc is recorded with its size; when a pointer given to a call
 // lies inside one of them, the bytes the call is about to touch must fit in what is left of that allocation, otherwise
 // the call is a caller error (MBN_EINVAL) instead of a GPU memory fault. Caller-owned memory (hipMalloc, a torch tensor)
 // is not in the map and is not checked. Cause on record (round 1, gpurun_out/fault.log): the C host uploaded a uint8
 // image (3*96*96*3 bytes) and issued the fp32 first-layer kernel on it, which read 4x the buffer.
-struct Span { const void *p; double bytes; const char *what; };
-
-int span_check(mbn_context *ctx, const Span *sp, int n)
+int mbn_span_check(mbn_context *ctx, const mbn_span *sp, int n)
 {
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (ctx->allocs.empty()) return MBN_OK;
@@ -39,11 +35,48 @@ int span_check(mbn_context *ctx, const Span *sp, int n)
     }
     return MBN_OK;
 }
-#define MBN_SPANS(ctx, ...)                                                            \
-    do {                                                                               \
-        const Span _sp[] = { __VA_ARGS__ };                                            \
-        const int _rc = span_check((ctx), _sp, (int)(sizeof(_sp) / sizeof(_sp[0])));   \
-        if (_rc != MBN_OK) return _rc;                                                 \
+
+bool mbn_spans_overlap(const void *p, double p_bytes, const void *q, double q_bytes)
+{
+    if (!p || !q) return false;
+    const double x = (double)(uintptr_t)p, y = (double)(uintptr_t)q;
+    return x < y + q_bytes && y < x + p_bytes;
+}
+
+void mbn_scratch_release(mbn_scratch *h)
+{
+    if (h->scratch) (void)hipFree(h->scratch);
+    delete h;
+}
+
+mbn_scratch_list::~mbn_scratch_list()
+{
+    for (mbn_scratch *h : live) mbn_scratch_release(h);
+}
+
+int mbn_scratch_destroy(mbn_scratch *h)
+{
+    if (!h) return MBN_OK;
+    mbn_context *ctx = h->ctx;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        auto &live = ctx->scratches.live;
+        for (auto it = live.begin(); it != live.end(); ++it)
+            if (*it == h) { live.erase(it); break; }
+    }
+    (void)hipSetDevice(ctx->device);
+    MBN_HIP_TRY(ctx, hipDeviceSynchronize());                    // its last launch, whatever the stream
+    mbn_scratch_release(h);
+    return MBN_OK;
+}
+
+namespace {
+
+#define MBN_SPANS(ctx, ...)                                                               \
+    do {                                                                                  \
+        const mbn_span _sp[] = { __VA_ARGS__ };                                           \
+        const int _rc = mbn_span_check((ctx), _sp, (int)(sizeof(_sp) / sizeof(_sp[0])));  \
+        if (_rc != MBN_OK) return _rc;                                                    \
     } while (0)
 
 // Pointers of a fused launch: MBN_EINVAL when one is null, else MBN_EUNSUPPORTED when one is not on 16 bytes (the fused kernels

@@ -43,6 +43,7 @@
 // the same tile, stage pass, lerps, softmax sum and store; described where they stand, behind rs_launch.
 #include "mbn_internal.h"
 #include "mbn_device.h"
+#include "mbn_label_set.h"
 
 #include <new>
 #include <type_traits>
@@ -51,12 +52,6 @@ namespace {
 
 constexpr int RS_TILE = MBN_RESAMPLE_TILE;   // output tile side of a workgroup
 constexpr int RS_ROWS = 4;                   // output rows of a lane
-
-// head of the ragged handle's device block, in front of the items; 16 bytes like them
-struct ReadoutHead {
-    int32_t batch, generation, pad[2];
-};
-static_assert(sizeof(ReadoutHead) == 16 && sizeof(mbn_label_item) == 16 && sizeof(mbn_label_window_item) == 32, "device layout");
 
 struct ResampleArgs {
     int *labels;
@@ -67,7 +62,7 @@ struct ResampleArgs {
     int tiles_x;             // of the launch's grid.x (ragged: of the widest item)
     int fy, fx;              // the launch's LDS footprint in vectors; every tile's own is inside it
     int ch;                  // classes per chunk, a multiple of 4; an LDS row is ch + 4 floats
-    const ReadoutHead *head; // ragged form
+    const mbn_label_set_head *head;   // ragged form (mbn_label_set.h)
     const mbn_label_item *items;
     int generation;
     // WIN instantiations only (behind everything the others read, whose kernel arguments stay where they were)
@@ -600,7 +595,7 @@ int mbn_ragged_readout_build(mbn_context *ctx, int max_batch, mbn_ragged_readout
     if (!r) return MBN_ENOMEM;
     r->ctx = ctx;
     r->max_batch = max_batch;
-    const size_t bytes = sizeof(ReadoutHead) + sizeof(mbn_label_window_item) * (size_t)max_batch;     // the larger kind of item
+    const size_t bytes = sizeof(mbn_label_set_head) + sizeof(mbn_label_window_item) * (size_t)max_batch;     // the larger kind of item
     r->sort = new (std::nothrow) int64_t[2 * (size_t)max_batch];
     (void)hipSetDevice(ctx->device);
     hipError_t e = r->sort ? hipMalloc(&r->dev, bytes) : hipErrorOutOfMemory;
@@ -638,12 +633,12 @@ int mbn_ragged_readout_plan(mbn_ragged_readout *r, hipStream_t s, int rows, int 
     if (rc != MBN_OK) return rc;
     const size_t item_bytes = window ? sizeof(mbn_label_window_item) : sizeof(mbn_label_item);
     MBN_HIP_TRY(ctx, hipEventSynchronize(r->done));
-    ReadoutHead *h = (ReadoutHead *)r->host;
+    mbn_label_set_head *h = (mbn_label_set_head *)r->host;
     memset(h, 0, sizeof *h);
     h->batch = batch; h->generation = r->generation + 1;
     memcpy(h + 1, items, (size_t)batch * item_bytes);
     r->batch = 0;                                               // from here on a failure leaves the handle without a batch
-    MBN_HIP_TRY(ctx, hipMemcpyAsync(r->dev, r->host, sizeof(ReadoutHead) + (size_t)batch * item_bytes, hipMemcpyHostToDevice, s));
+    MBN_HIP_TRY(ctx, hipMemcpyAsync(r->dev, r->host, sizeof(mbn_label_set_head) + (size_t)batch * item_bytes, hipMemcpyHostToDevice, s));
     MBN_HIP_TRY(ctx, hipEventRecord(r->done, s));
     r->generation = h->generation;
     r->rows = rows; r->cols = cols; r->classes = classes;
@@ -659,13 +654,11 @@ int mbn_launch_f32_resample_argmax_ragged(mbn_ragged_readout *r, hipStream_t s, 
 {
     ResampleArgs a = rs_args(labels, score, logits, r->rows, r->cols, r->classes, r->launch, r->in_rows, r->in_cols, q);
     a.tiles_x = 1;                                              // unused: a workgroup takes its image's own
-    a.head = (const ReadoutHead *)r->dev;
+    a.head = (const mbn_label_set_head *)r->dev;
     a.items = (const mbn_label_item *)(a.head + 1);
     a.witems = (const mbn_label_window_item *)(a.head + 1);     // the last set decides which of the two the block holds
     a.generation = r->generation;
     rs_launch(true, q != nullptr, r->window != 0, r->batch, r->launch, s, a);
-    // the next set waits for this launch; inside a capture there is nothing to wait for (the replays are the caller's to order)
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) (void)hipEventRecord(r->done, s);
+    mbn_ragged_readout_mark_done(r, s);
     return MBN_OK;
 }

@@ -25,6 +25,7 @@
 // The grid is persistent: num_cus * (workgroups per CU by LDS) workgroups; workgroup b takes the tiles k with (k + rot) % grid == b, rot = the tiles
 // of the maps before. No workgroup waits for another. Indices inside a map are below 2^29 (the envelope); a map's element offset is 64-bit.
 #include "mbn_internal.h"
+#include "mbn_label_set.h"
 
 #include <mutex>
 
@@ -35,12 +36,6 @@ constexpr int BD_THREADS = 64 * BD_WAVES;
 constexpr int BD_TC = MBN_BOUNDARY_TILE_COLS;          // one lane per column
 constexpr int BD_LEADERS = 16;                         // distinct cells a wave aggregates per add; the lanes left over add on their own
 static_assert(BD_TC == 64, "a lane per tile column");
-
-// head of a ragged read-out handle's device block, in front of its items (mbn_f32_resample.hip writes it): 16 bytes like an mbn_label_item
-struct SetHead {
-    int32_t batch, generation, pad[2];
-};
-static_assert(sizeof(SetHead) == 16 && sizeof(mbn_label_item) == 16 && sizeof(mbn_label_window_item) == 32, "device layout");
 
 template <int HW>
 struct Geo {
@@ -57,8 +52,7 @@ struct BoundaryArgs {
     int d, edge;
     int lds_form;                          // score: a workgroup counts a tile in LDS bins (classes <= MBN_BOUNDARY_LDS_CLASSES)
     const int32_t *d_items;                // ragged form: per-item half-widths or null
-    const SetHead *head;                   // ragged form: the handle's block, its generation and the bytes of one item
-    int generation, item_bytes;
+    mbn_label_set set;                     // ragged form: the view of the handle's set
 };
 
 template <int EB>
@@ -182,7 +176,7 @@ __device__ __forceinline__ Item item_of(const BoundaryArgs &a, int i)
 {
     Item m;
     if (RAGGED) {
-        const mbn_label_item *it = (const mbn_label_item *)((const char *)(a.head + 1) + (size_t)i * a.item_bytes);
+        const mbn_label_item *it = mbn_label_set_item(a.set, i);
         m.off = it->dst_offset;
         m.rows = it->rows;
         m.cols = it->cols;
@@ -209,8 +203,8 @@ __global__ __launch_bounds__(BD_THREADS) void boundary_i32(const BoundaryArgs a)
     const int tri_cells = (a.classes + 1) * (a.classes + 1), bins = tri_cells + 3 * a.classes;
     int batch = a.batch;
     if (RAGGED) {
-        if (a.head->generation != a.generation) return;    // captured under an earlier set: nothing to do
-        batch = a.head->batch;
+        if (mbn_label_set_stale(a.set)) return;            // captured under an earlier set: nothing to do
+        batch = a.set.head->batch;
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned G = gridDim.x, b = blockIdx.x;
@@ -285,36 +279,6 @@ static_assert(MBN_BOUNDARY_SMALL_D == 16 && MBN_BOUNDARY_MAX_D == 64, "the two h
 static_assert(((MBN_BOUNDARY_LDS_CLASSES + 1) * (MBN_BOUNDARY_LDS_CLASSES + 1) + 3 * MBN_BOUNDARY_LDS_CLASSES) * 4 <= MBN_BOUNDARY_TABLE_BYTES &&
               MBN_BOUNDARY_TABLE_BYTES % 16 == 0, "the bins of the largest LDS class count fit their part of the LDS");
 
-// The bounds rule of mbn_alloc (mbn_abi.hip keeps its own copy for the layer calls): a pointer inside a tracked buffer must leave room for the
-// bytes the call touches
-struct Span { const void *p; double bytes; const char *what; };
-
-int bd_spans(mbn_context *ctx, const Span *sp, int count)
-{
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    for (int i = 0; i < count; i++) {
-        if (!sp[i].p || sp[i].bytes <= 0 || ctx->allocs.empty()) continue;
-        const uintptr_t at = (uintptr_t)sp[i].p;
-        auto it = ctx->allocs.upper_bound(at);
-        if (it == ctx->allocs.begin()) continue;
-        --it;
-        if (at >= it->first + it->second) continue;                                        // not inside any of our buffers
-        const double room = (double)(it->first + it->second - at);
-        if (sp[i].bytes > room) {
-            snprintf(ctx->last_error, sizeof(ctx->last_error), "%s: call touches %.0f bytes, %.0f left in its %zu-byte mbn_alloc buffer", sp[i].what,
-                     sp[i].bytes, room, it->second);
-            return MBN_EINVAL;
-        }
-    }
-    return MBN_OK;
-}
-
-bool bd_overlap(const void *p, double p_bytes, const void *q, double q_bytes)
-{
-    const double x = (double)(uintptr_t)p, y = (double)(uintptr_t)q;
-    return x < y + q_bytes && y < x + p_bytes;
-}
-
 // The launch of all four calls. d_alloc = the largest half-width of the call (MBN_BOUNDARY_MAX_D with per-item half-widths); tiles = an upper
 // bound of its tiles, which only caps the grid
 int bd_launch(mbn_context *ctx, mbn_ragged_readout *r, hipStream_t s, const BoundaryArgs &a, bool score, int elem_bytes, int d_alloc, double tiles)
@@ -325,8 +289,10 @@ int bd_launch(mbn_context *ctx, mbn_ragged_readout *r, hipStream_t s, const Boun
     const bool large = d_alloc > MBN_BOUNDARY_SMALL_D;
     int per_cu = MBN_BOUNDARY_CU_LDS / lds;
     if (per_cu > 2048 / BD_THREADS) per_cu = 2048 / BD_THREADS;
-    double grid = (double)(ctx->num_cus > 0 ? ctx->num_cus : 1) * per_cu;
-    if (grid > tiles) grid = tiles;
+    // tiles is a sum of whole numbers: a map inside the envelope has fewer than 2^29 tiles (one per pixel at most, rows * cols < 2^29), a uniform call
+    // at most 65535 maps and a set fewer than 2^31 items, so the sum is below 2^60 and its conversion cannot overflow; wherever it is too large for
+    // a double to hold exactly (above 2^53) it is far above num_cus * per_cu, which is then the grid either way
+    const unsigned grid = mbn_persistent_grid(ctx->num_cus, per_cu, (long long)tiles);
     // the large class reaches 122 880 bytes: above the 64 KB a launch gets without asking (once per process; not a stream operation)
     static std::once_flag asked;
     std::call_once(asked, [] {
@@ -338,13 +304,8 @@ int bd_launch(mbn_context *ctx, mbn_ragged_readout *r, hipStream_t s, const Boun
                     (void)hipFuncSetAttribute((const void *)bd_kernels[sc][rg][1][eb], hipFuncAttributeMaxDynamicSharedMemorySize, most);
     });
     (void)hipSetDevice(ctx->device);
-    hipLaunchKernelGGL(bd_kernels[score][r != nullptr][large][elem_bytes == 4], dim3((unsigned)(grid < 1.0 ? 1.0 : grid)), dim3(BD_THREADS), (size_t)lds,
-                       s, a);
-    if (r) {
-        // the next set waits for this launch; inside a capture there is nothing to wait for (the replays are the caller's to order)
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) (void)hipEventRecord(r->done, s);
-    }
+    hipLaunchKernelGGL(bd_kernels[score][r != nullptr][large][elem_bytes == 4], dim3(grid), dim3(BD_THREADS), (size_t)lds, s, a);
+    if (r) mbn_ragged_readout_mark_done(r, s);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? MBN_OK : mbn_record_hip_error(ctx, e, "boundary launch");
 }
@@ -355,25 +316,16 @@ double bd_tiles(int rows, int cols, int d)
     return (double)((rows + tr - 1) / tr) * (double)((cols + BD_TC - 1) / BD_TC);
 }
 
-const mbn_label_item *bd_host_item(const mbn_ragged_readout *r, int i)
-{
-    const size_t item_bytes = r->window ? sizeof(mbn_label_window_item) : sizeof(mbn_label_item);
-    return (const mbn_label_item *)((const char *)r->host + sizeof(SetHead) + (size_t)i * item_bytes);
-}
-
 // The shape of a ragged call from the handle's pinned items: the envelope's answer over every map (MBN_EINVAL first), its tiles
 int bd_ragged_shape(const mbn_ragged_readout *r, int elem_bytes, int classes, int d, const void *d_items, int edge, double *tiles)
 {
-    int shape = MBN_OK;
     const int d_each = d_items ? MBN_BOUNDARY_MAX_D : d;
     *tiles = 0.0;
-    for (int i = 0; i < r->batch; i++) {
-        const mbn_label_item *it = bd_host_item(r, i);
-        const int rc = mbn_boundary_envelope(elem_bytes, classes, 1, it->rows, it->cols, d_each, edge);
-        if (rc == MBN_EINVAL || (rc != MBN_OK && shape == MBN_OK)) shape = rc;
-        if (rc == MBN_OK) *tiles += bd_tiles(it->rows, it->cols, d_each);
-    }
-    return shape;
+    return mbn_ragged_readout_envelope(r, [&](const mbn_label_item &it) {
+        const int rc = mbn_boundary_envelope(elem_bytes, classes, 1, it.rows, it.cols, d_each, edge);
+        if (rc == MBN_OK) *tiles += bd_tiles(it.rows, it.cols, d_each);
+        return rc;
+    });
 }
 
 // What the two depth calls share once the shape is known; span = the elements of the maps
@@ -382,10 +334,10 @@ int depth_call(mbn_context *ctx, mbn_ragged_readout *r, BoundaryArgs &a, int sha
     if (shape == MBN_EINVAL) return shape;
     if ((elem_bytes == 4 && (uintptr_t)a.map % 4) || (uintptr_t)a.d_items % 4) return MBN_EINVAL;
     if (shape != MBN_OK) return shape;
-    if (bd_overlap(a.depth, span, a.map, span * elem_bytes)) return MBN_EINVAL;
-    const Span sp[] = { { a.depth, span, "boundary depth" }, { a.map, span * elem_bytes, "boundary map" },
+    if (mbn_spans_overlap(a.depth, span, a.map, span * elem_bytes)) return MBN_EINVAL;
+    const mbn_span sp[] = { { a.depth, span, "boundary depth" }, { a.map, span * elem_bytes, "boundary map" },
                         { a.d_items, 4.0 * (r ? r->batch : 0), "boundary d_items" } };
-    const int rc = bd_spans(ctx, sp, (int)(sizeof sp / sizeof sp[0]));
+    const int rc = mbn_span_check(ctx, sp, (int)(sizeof sp / sizeof sp[0]));
     if (rc != MBN_OK) return rc;
     return bd_launch(ctx, r, stream ? (hipStream_t)stream : ctx->stream, a, false, elem_bytes, d_alloc, tiles);
 }
@@ -397,10 +349,10 @@ int score_call(mbn_context *ctx, mbn_ragged_readout *r, BoundaryArgs &a, int sha
         (uintptr_t)a.d_items % 4)
         return MBN_EINVAL;
     if (shape != MBN_OK) return shape;
-    const Span sp[] = { { a.trimap, 8.0 * (a.classes + 1) * (a.classes + 1), "boundary trimap" }, { a.biou, 24.0 * a.classes, "boundary biou" },
+    const mbn_span sp[] = { { a.trimap, 8.0 * (a.classes + 1) * (a.classes + 1), "boundary trimap" }, { a.biou, 24.0 * a.classes, "boundary biou" },
                         { a.labels, 4.0 * span, "boundary labels" }, { a.map, span * truth_bytes, "boundary truth" },
                         { a.d_items, 4.0 * (r ? r->batch : 0), "boundary d_items" } };
-    const int rc = bd_spans(ctx, sp, (int)(sizeof sp / sizeof sp[0]));
+    const int rc = mbn_span_check(ctx, sp, (int)(sizeof sp / sizeof sp[0]));
     if (rc != MBN_OK) return rc;
     return bd_launch(ctx, r, stream ? (hipStream_t)stream : ctx->stream, a, true, truth_bytes, d_alloc, tiles);
 }
@@ -408,9 +360,7 @@ int score_call(mbn_context *ctx, mbn_ragged_readout *r, BoundaryArgs &a, int sha
 void ragged_args(BoundaryArgs &a, const mbn_ragged_readout *r, const void *d_items)
 {
     a.d_items = (const int32_t *)d_items;
-    a.head = (const SetHead *)r->dev;
-    a.generation = r->generation;
-    a.item_bytes = r->window ? (int)sizeof(mbn_label_window_item) : (int)sizeof(mbn_label_item);
+    a.set = mbn_ragged_readout_view(r);
 }
 
 }   // namespace
@@ -422,13 +372,13 @@ int mbn_boundary_d_items(mbn_ragged_readout *r, double ratio, int32_t *d_host)
     if (!r || !d_host || r->batch <= 0) return MBN_EINVAL;
     int status = MBN_OK;
     for (int i = 0; i < r->batch; i++) {
-        const mbn_label_item *it = bd_host_item(r, i);
+        const mbn_label_item *it = mbn_ragged_readout_item(r, i);
         const int d = mbn_boundary_d(it->rows, it->cols, ratio);
         if (d == MBN_EINVAL || (d < 0 && status == MBN_OK)) status = d;
     }
     if (status != MBN_OK) return status;
     for (int i = 0; i < r->batch; i++) {
-        const mbn_label_item *it = bd_host_item(r, i);
+        const mbn_label_item *it = mbn_ragged_readout_item(r, i);
         d_host[i] = mbn_boundary_d(it->rows, it->cols, ratio);
     }
     return MBN_OK;

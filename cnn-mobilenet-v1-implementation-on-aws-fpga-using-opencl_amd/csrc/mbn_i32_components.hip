@@ -26,8 +26,7 @@
 //              (min_row is the first pixel's row)
 // The units of a kernel (tiles, chunks or images) are dealt round robin to a grid sized from the planning CU count.
 #include "mbn_internal.h"
-
-#include <new>
+#include "mbn_label_set.h"
 
 namespace {
 
@@ -39,73 +38,26 @@ constexpr int CC_WGS_PER_CU = 8;          // 32 waves and 8 x 16 KB of LDS on a 
 static_assert(TC == 64, "a wave holds one row of a tile");
 static_assert(CHUNK == 4 * CC_THREADS, "four pixels per lane and chunk");
 
-// head of a ragged read-out handle's device block, in front of its items (mbn_f32_resample.hip writes it): 16 bytes like an mbn_label_item
-struct SetHead {
-    int32_t batch, generation, pad[2];
-};
-static_assert(sizeof(SetHead) == 16 && sizeof(mbn_label_item) == 16 && sizeof(mbn_label_window_item) == 32 && sizeof(mbn_region) == 32, "device layout");
-
 struct CcArgs {
     const int32_t *labels;
     int32_t *comp, *labels_out, *regions, *n_regions;
     int32_t *parent, *area, *chunk;           // the handle's scratch
     int batch, rows, cols;                    // uniform form
-    const SetHead *head;                      // ragged form: the read-out handle's block, its generation and the bytes of one item
-    int generation, item_bytes;
+    mbn_label_set set;                        // ragged form: the view of the read-out handle's set
     long long tiles, chunks;                  // units of the whole call
     int classes, conn8, min_area, ignore_label, max_regions;
 };
 
-// one unit of work: the image it lies in and its number inside that image
-struct Unit {
-    long long off;        // the image's first element in labels / comp / labels_out
-    long long scr;        // ... in parent / area: the pixels of the images before it
-    long long chunk0;     // ... in chunk: the chunks of the images before it
-    int rows, cols, image;
-    int unit;
-};
-
-enum { BY_TILE = 0, BY_CHUNK = 1, BY_IMAGE = 2 };
-
 __host__ __device__ inline long long cc_tiles(int rows, int cols) { return (long long)((rows + TR - 1) / TR) * ((cols + TC - 1) / TC); }
 __host__ __device__ inline long long cc_chunks(int rows, int cols) { return ((long long)rows * cols + CHUNK - 1) / CHUNK; }
 
-// unit u of a kernel whose units are tiles, chunks or images. Uniform across the workgroup (u is). The ragged form walks the items: plain loads,
-// they were uploaded before the launch
-template <bool RAGGED, int BY>
-__device__ __forceinline__ bool locate(const CcArgs &a, long long u, Unit &w)
+// unit u of a kernel whose units are tiles, chunks (PER = cc_tiles, cc_chunks) or images. Uniform across the workgroup (u is). In Unit, off is
+// the image's first element in labels / comp / labels_out, pixels that in parent / area, and sum that in chunk: the chunks of the images before it
+using Unit = mbn_label_unit;
+template <bool RAGGED, mbn_label_units_fn PER>
+__device__ __forceinline__ bool cc_unit(const CcArgs &a, long long u, Unit &w)
 {
-    if (!RAGGED) {
-        const long long per = BY == BY_TILE ? cc_tiles(a.rows, a.cols) : BY == BY_CHUNK ? cc_chunks(a.rows, a.cols) : 1;
-        const long long i = u / per;
-        if (i >= a.batch) return false;
-        w.image = (int)i;
-        w.unit = (int)(u - i * per);
-        w.rows = a.rows; w.cols = a.cols;
-        w.off = w.scr = i * ((long long)a.rows * a.cols);
-        w.chunk0 = i * cc_chunks(a.rows, a.cols);
-        return true;
-    }
-    const int batch = a.head->batch;
-    long long scr = 0, chunk0 = 0;
-    for (int i = 0; i < batch; i++) {
-        const mbn_label_item *it = (const mbn_label_item *)((const char *)(a.head + 1) + (size_t)i * a.item_bytes);
-        const int rows = it->rows, cols = it->cols;
-        const long long per = BY == BY_TILE ? cc_tiles(rows, cols) : BY == BY_CHUNK ? cc_chunks(rows, cols) : 1;
-        if (u < per) {
-            w.image = i;
-            w.unit = (int)u;
-            w.rows = rows; w.cols = cols;
-            w.off = it->dst_offset;
-            w.scr = scr;
-            w.chunk0 = chunk0;
-            return true;
-        }
-        u -= per;
-        scr += (long long)rows * cols;
-        chunk0 += cc_chunks(rows, cols);
-    }
-    return false;
+    return mbn_label_set_unit<RAGGED, PER, cc_chunks>(a.set, a.batch, a.rows, a.cols, u, w);
 }
 
 // a label as the union-find sees it: itself inside [0, classes), else -1 (abstained: equal to no valid label)
@@ -194,11 +146,11 @@ template <bool RAGGED>
 __global__ __launch_bounds__(CC_THREADS) void cc_tile(const CcArgs a)
 {
     __shared__ int s_lab[TR * TC], s_par[TR * TC];
-    if (RAGGED && a.head->generation != a.generation) return;                  // captured under an earlier set: nothing to do
+    if (RAGGED && mbn_label_set_stale(a.set)) return;                  // captured under an earlier set: nothing to do
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (long long u = blockIdx.x; u < a.tiles; u += gridDim.x) {
         Unit w;
-        if (!locate<RAGGED, BY_TILE>(a, u, w)) break;
+        if (!cc_unit<RAGGED, cc_tiles>(a, u, w)) break;
         const int tiles_x = (w.cols + TC - 1) / TC;
         const int r0 = w.unit / tiles_x * TR, c0 = w.unit % tiles_x * TC;
         const int32_t *lab = a.labels + w.off;
@@ -237,8 +189,8 @@ __global__ __launch_bounds__(CC_THREADS) void cc_tile(const CcArgs a)
                 const int t = lds_find(s_par, i);
                 root = (r0 + t / TC) * w.cols + c0 + t % TC;
             }
-            a.parent[w.scr + r * w.cols + c] = root;
-            a.area[w.scr + r * w.cols + c] = 0;
+            a.parent[w.pixels + r * w.cols + c] = root;
+            a.area[w.pixels + r * w.cols + c] = 0;
         }
         __syncthreads();                                                                   // the next tile overwrites the LDS
     }
@@ -248,7 +200,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_tile(const CcArgs a)
 template <bool RAGGED>
 __global__ __launch_bounds__(CC_THREADS) void cc_seams(const CcArgs a)
 {
-    if (RAGGED && a.head->generation != a.generation) return;
+    if (RAGGED && mbn_label_set_stale(a.set)) return;
     const int t = threadIdx.x;
     // the pixel of this lane: first row (64), first column below it (31), last column below the first row (31, connectivity 8 only)
     int rr = 0, cc = 0;
@@ -260,12 +212,12 @@ __global__ __launch_bounds__(CC_THREADS) void cc_seams(const CcArgs a)
     if (!mine) return;                                                                     // no barrier and no wave operation below
     for (long long u = blockIdx.x; u < a.tiles; u += gridDim.x) {
         Unit w;
-        if (!locate<RAGGED, BY_TILE>(a, u, w)) break;
+        if (!cc_unit<RAGGED, cc_tiles>(a, u, w)) break;
         const int tiles_x = (w.cols + TC - 1) / TC;
         const int r = w.unit / tiles_x * TR + rr, c = w.unit % tiles_x * TC + cc, cols = w.cols;
         if (r >= w.rows || c >= cols) continue;
         const int32_t *lab = a.labels + w.off;
-        int32_t *par = a.parent + w.scr;
+        int32_t *par = a.parent + w.pixels;
         const int p = r * cols + c;
         const int l = cc_valid(lab[p], a.classes);
         if (l < 0) continue;
@@ -290,13 +242,13 @@ __global__ __launch_bounds__(CC_THREADS) void cc_seams(const CcArgs a)
 template <bool RAGGED>
 __global__ __launch_bounds__(CC_THREADS) void cc_flatten(const CcArgs a)
 {
-    if (RAGGED && a.head->generation != a.generation) return;
+    if (RAGGED && mbn_label_set_stale(a.set)) return;
     const int lane = threadIdx.x & 63;
     for (long long u = blockIdx.x; u < a.chunks; u += gridDim.x) {
         Unit w;
-        if (!locate<RAGGED, BY_CHUNK>(a, u, w)) break;
+        if (!cc_unit<RAGGED, cc_chunks>(a, u, w)) break;
         const int n = w.rows * w.cols;
-        int32_t *par = a.parent + w.scr, *area = a.area + w.scr;
+        int32_t *par = a.parent + w.pixels, *area = a.area + w.pixels;
         for (int j = 0; j < CHUNK / CC_THREADS; j++) {                                     // a wave holds 64 consecutive pixels
             const int p = w.unit * CHUNK + j * CC_THREADS + (int)threadIdx.x;
             int root = -1;
@@ -333,17 +285,17 @@ template <bool RAGGED>
 __global__ __launch_bounds__(CC_THREADS) void cc_count(const CcArgs a)
 {
     __shared__ int s_w[CC_WAVES];
-    if (RAGGED && a.head->generation != a.generation) return;
+    if (RAGGED && mbn_label_set_stale(a.set)) return;
     for (long long u = blockIdx.x; u < a.chunks; u += gridDim.x) {
         Unit w;
-        if (!locate<RAGGED, BY_CHUNK>(a, u, w)) break;
+        if (!cc_unit<RAGGED, cc_chunks>(a, u, w)) break;
         const int n = w.rows * w.cols;
-        const int32_t *par = a.parent + w.scr, *area = a.area + w.scr;
+        const int32_t *par = a.parent + w.pixels, *area = a.area + w.pixels;
         int v = 0;
         for (int j = 0; j < 4; j++) v += cc_survivor(par, area, w.unit * CHUNK + 4 * (int)threadIdx.x + j, n, a.min_area);
         int total;
         (void)block_scan(v, s_w, total);
-        if (threadIdx.x == 0) a.chunk[w.chunk0 + w.unit] = total;
+        if (threadIdx.x == 0) a.chunk[w.sum + w.unit] = total;
     }
 }
 
@@ -354,14 +306,14 @@ __global__ __launch_bounds__(CC_THREADS) void cc_scan(const CcArgs a)
     __shared__ int s_w[CC_WAVES];
     int batch = a.batch;
     if (RAGGED) {
-        if (a.head->generation != a.generation) return;
-        batch = a.head->batch;
+        if (mbn_label_set_stale(a.set)) return;
+        batch = a.set.head->batch;
     }
     for (long long u = blockIdx.x; u < batch; u += gridDim.x) {
         Unit w;
-        if (!locate<RAGGED, BY_IMAGE>(a, u, w)) break;
+        if (!cc_unit<RAGGED, mbn_label_units_image>(a, u, w)) break;
         const int chunks = (int)cc_chunks(w.rows, w.cols);
-        int32_t *cnt = a.chunk + w.chunk0;
+        int32_t *cnt = a.chunk + w.sum;
         int running = 0;                                                                   // the same in every lane
         for (int base = 0; base < chunks; base += CC_THREADS) {
             const int i = base + (int)threadIdx.x;
@@ -380,13 +332,13 @@ template <bool RAGGED>
 __global__ __launch_bounds__(CC_THREADS) void cc_number(const CcArgs a)
 {
     __shared__ int s_w[CC_WAVES];
-    if (RAGGED && a.head->generation != a.generation) return;
+    if (RAGGED && mbn_label_set_stale(a.set)) return;
     for (long long u = blockIdx.x; u < a.chunks; u += gridDim.x) {
         Unit w;
-        if (!locate<RAGGED, BY_CHUNK>(a, u, w)) break;
+        if (!cc_unit<RAGGED, cc_chunks>(a, u, w)) break;
         const int n = w.rows * w.cols;
-        const int32_t *par = a.parent + w.scr;
-        int32_t *area = a.area + w.scr;
+        const int32_t *par = a.parent + w.pixels;
+        int32_t *area = a.area + w.pixels;
         const int p0 = w.unit * CHUNK + 4 * (int)threadIdx.x;
         bool keep[4];
         int v = 0;
@@ -395,7 +347,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_number(const CcArgs a)
             v += keep[j];
         }
         int total;
-        int rank = a.chunk[w.chunk0 + w.unit] + block_scan(v, s_w, total);
+        int rank = a.chunk[w.sum + w.unit] + block_scan(v, s_w, total);
         for (int j = 0; j < 4; j++) {
             const int p = p0 + j;
             if (keep[j]) {
@@ -432,13 +384,13 @@ __device__ __forceinline__ void box_grow(int32_t *rec, int cmin, int rmax, int c
 template <bool RAGGED>
 __global__ __launch_bounds__(CC_THREADS) void cc_write(const CcArgs a)
 {
-    if (RAGGED && a.head->generation != a.generation) return;
+    if (RAGGED && mbn_label_set_stale(a.set)) return;
     const int lane = threadIdx.x & 63;
     for (long long u = blockIdx.x; u < a.chunks; u += gridDim.x) {
         Unit w;
-        if (!locate<RAGGED, BY_CHUNK>(a, u, w)) break;
+        if (!cc_unit<RAGGED, cc_chunks>(a, u, w)) break;
         const int n = w.rows * w.cols;
-        const int32_t *par = a.parent + w.scr, *rank_of = a.area + w.scr;
+        const int32_t *par = a.parent + w.pixels, *rank_of = a.area + w.pixels;
         for (int j = 0; j < CHUNK / CC_THREADS; j++) {                                     // a wave holds 64 consecutive pixels
             const int p = w.unit * CHUNK + j * CC_THREADS + (int)threadIdx.x;
             int rank = -1, r = 0, c = 0;
@@ -470,54 +422,18 @@ __global__ __launch_bounds__(CC_THREADS) void cc_write(const CcArgs a)
     }
 }
 
-// the bounds rule of mbn_alloc (mbn_abi.hip keeps its own copy for the layer calls): a pointer inside a tracked buffer must leave room for the
-// bytes the call touches
-struct Span { const void *p; double bytes; const char *what; };
-
-int cc_spans(mbn_context *ctx, const Span *sp, int count)
-{
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    for (int i = 0; i < count; i++) {
-        if (!sp[i].p || sp[i].bytes <= 0 || ctx->allocs.empty()) continue;
-        const uintptr_t at = (uintptr_t)sp[i].p;
-        auto it = ctx->allocs.upper_bound(at);
-        if (it == ctx->allocs.begin()) continue;
-        --it;
-        if (at >= it->first + it->second) continue;                                        // not inside any of our buffers
-        const double room = (double)(it->first + it->second - at);
-        if (sp[i].bytes > room) {
-            snprintf(ctx->last_error, sizeof(ctx->last_error), "%s: call touches %.0f bytes, %.0f left in its %zu-byte mbn_alloc buffer", sp[i].what,
-                     sp[i].bytes, room, it->second);
-            return MBN_EINVAL;
-        }
-    }
-    return MBN_OK;
-}
-
-bool cc_overlap(const void *p, const void *q, double bytes)
-{
-    if (!p || !q) return false;
-    const double x = (double)(uintptr_t)p, y = (double)(uintptr_t)q;
-    return x < y + bytes && y < x + bytes;
-}
-
-unsigned cc_grid(const mbn_context *ctx, long long units)
-{
-    const long long most = (long long)(ctx->num_cus > 0 ? ctx->num_cus : 1) * CC_WGS_PER_CU;
-    return (unsigned)(units < most ? (units > 0 ? units : 1) : most);
-}
-
 template <bool RAGGED>
 void cc_launch(mbn_context *ctx, hipStream_t s, const CcArgs &a, int batch)
 {
     const dim3 block(CC_THREADS);
-    hipLaunchKernelGGL(cc_tile<RAGGED>, dim3(cc_grid(ctx, a.tiles)), block, 0, s, a);
-    hipLaunchKernelGGL(cc_seams<RAGGED>, dim3(cc_grid(ctx, a.tiles)), block, 0, s, a);
-    hipLaunchKernelGGL(cc_flatten<RAGGED>, dim3(cc_grid(ctx, a.chunks)), block, 0, s, a);
-    hipLaunchKernelGGL(cc_count<RAGGED>, dim3(cc_grid(ctx, a.chunks)), block, 0, s, a);
-    hipLaunchKernelGGL(cc_scan<RAGGED>, dim3(cc_grid(ctx, batch)), block, 0, s, a);
-    hipLaunchKernelGGL(cc_number<RAGGED>, dim3(cc_grid(ctx, a.chunks)), block, 0, s, a);
-    hipLaunchKernelGGL(cc_write<RAGGED>, dim3(cc_grid(ctx, a.chunks)), block, 0, s, a);
+    const auto grid = [ctx](long long units) { return mbn_persistent_grid(ctx->num_cus, CC_WGS_PER_CU, units); };
+    hipLaunchKernelGGL(cc_tile<RAGGED>, dim3(grid(a.tiles)), block, 0, s, a);
+    hipLaunchKernelGGL(cc_seams<RAGGED>, dim3(grid(a.tiles)), block, 0, s, a);
+    hipLaunchKernelGGL(cc_flatten<RAGGED>, dim3(grid(a.chunks)), block, 0, s, a);
+    hipLaunchKernelGGL(cc_count<RAGGED>, dim3(grid(a.chunks)), block, 0, s, a);
+    hipLaunchKernelGGL(cc_scan<RAGGED>, dim3(grid(batch)), block, 0, s, a);
+    hipLaunchKernelGGL(cc_number<RAGGED>, dim3(grid(a.chunks)), block, 0, s, a);
+    hipLaunchKernelGGL(cc_write<RAGGED>, dim3(grid(a.chunks)), block, 0, s, a);
 }
 
 // What the two calls share once the shape is known: `shape` = the envelope's answer, `span` = the elements of the maps, `pixels` = those inside maps
@@ -529,23 +445,22 @@ int cc_call(mbn_components *h, mbn_ragged_readout *r, CcArgs &a, int shape, int 
     if ((uintptr_t)a.labels % 4 || (uintptr_t)a.comp % 4 || (uintptr_t)a.labels_out % 4 || (uintptr_t)a.regions % 4 || (uintptr_t)a.n_regions % 4)
         return MBN_EINVAL;
     if (shape != MBN_OK) return shape;
-    if (batch > h->max_batch || pixels > (double)h->max_pixels) return MBN_EINVAL;
-    if (cc_overlap(a.labels, a.labels_out, 4.0 * span) || cc_overlap(a.labels, a.comp, 4.0 * span)) return MBN_EINVAL;
-    const Span sp[] = { { a.labels, 4.0 * span, "components labels" }, { a.comp, 4.0 * span, "components comp" },
+    if (batch > h->max_batch || pixels > (double)h->capacity) return MBN_EINVAL;
+    const double map_bytes = 4.0 * span;
+    if (mbn_spans_overlap(a.labels, map_bytes, a.labels_out, map_bytes) || mbn_spans_overlap(a.labels, map_bytes, a.comp, map_bytes)) return MBN_EINVAL;
+    const mbn_span sp[] = { { a.labels, 4.0 * span, "components labels" }, { a.comp, 4.0 * span, "components comp" },
                         { a.labels_out, 4.0 * span, "components labels_out" },
                         { a.regions, 32.0 * batch * a.max_regions, "components regions" }, { a.n_regions, 4.0 * batch, "components n_regions" } };
-    const int rc = cc_spans(ctx, sp, (int)(sizeof sp / sizeof sp[0]));
+    const int rc = mbn_span_check(ctx, sp, (int)(sizeof sp / sizeof sp[0]));
     if (rc != MBN_OK) return rc;
     a.parent = (int32_t *)h->scratch;
-    a.area = a.parent + h->max_pixels;
-    a.chunk = a.area + h->max_pixels;
+    a.area = a.parent + h->capacity;
+    a.chunk = a.area + h->capacity;
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     (void)hipSetDevice(ctx->device);
     if (r) {
         cc_launch<true>(ctx, s, a, batch);
-        // the next set waits for this launch; inside a capture there is nothing to wait for (the replays are the caller's to order)
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) (void)hipEventRecord(r->done, s);
+        mbn_ragged_readout_mark_done(r, s);
     } else {
         cc_launch<false>(ctx, s, a, batch);
     }
@@ -553,61 +468,16 @@ int cc_call(mbn_components *h, mbn_ragged_readout *r, CcArgs &a, int shape, int 
     return e == hipSuccess ? MBN_OK : mbn_record_hip_error(ctx, e, "components launch");
 }
 
-void cc_release(mbn_components *h)
-{
-    if (h->scratch) (void)hipFree(h->scratch);
-    delete h;
-}
-
 }   // namespace
-
-mbn_components_list::~mbn_components_list()
-{
-    for (mbn_components *h : live) cc_release(h);
-}
 
 extern "C" {
 
 int mbn_components_create(mbn_context *ctx, int max_batch, int64_t max_pixels, mbn_components **h)
 {
-    if (!ctx || !h) return MBN_EINVAL;
-    *h = nullptr;
-    if (max_batch < 1 || max_pixels < 1) return MBN_EINVAL;
-    const int64_t bytes = mbn_components_scratch_bytes(max_batch, max_pixels);
-    if (bytes <= 0) return MBN_EUNSUPPORTED;
-    mbn_components *c = new (std::nothrow) mbn_components();
-    if (!c) return MBN_ENOMEM;
-    c->ctx = ctx;
-    c->max_batch = max_batch;
-    c->max_pixels = max_pixels;
-    (void)hipSetDevice(ctx->device);
-    if (hipMalloc(&c->scratch, (size_t)bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        c->scratch = nullptr;
-        cc_release(c);
-        return MBN_ENOMEM;
-    }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->components.live.push_back(c);
-    *h = c;
-    return MBN_OK;
+    return mbn_scratch_create(ctx, max_batch, max_pixels, mbn_components_scratch_bytes(max_batch, max_pixels), h);
 }
 
-int mbn_components_destroy(mbn_components *h)
-{
-    if (!h) return MBN_OK;
-    mbn_context *ctx = h->ctx;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        auto &live = ctx->components.live;
-        for (auto it = live.begin(); it != live.end(); ++it)
-            if (*it == h) { live.erase(it); break; }
-    }
-    (void)hipSetDevice(ctx->device);
-    MBN_HIP_TRY(ctx, hipDeviceSynchronize());                    // its last launch, whatever the stream
-    cc_release(h);
-    return MBN_OK;
-}
+int mbn_components_destroy(mbn_components *h) { return mbn_scratch_destroy(h); }
 
 int mbn_components_i32(mbn_components *h, void *comp_i32, mbn_region *regions, void *n_regions_i32, void *labels_out_i32, const void *labels_i32,
                        int batch, int rows, int cols, int classes, int connectivity, int min_area, int ignore_label, int max_regions, void *stream)
@@ -637,21 +507,18 @@ int mbn_components_ragged_i32(mbn_components *h, mbn_ragged_readout *r, void *co
     a.labels = (const int32_t *)labels_i32;
     a.comp = (int32_t *)comp_i32; a.labels_out = (int32_t *)labels_out_i32; a.regions = (int32_t *)regions; a.n_regions = (int32_t *)n_regions_i32;
     a.classes = classes; a.conn8 = connectivity == 8; a.min_area = min_area; a.ignore_label = ignore_label; a.max_regions = max_regions;
-    a.head = (const SetHead *)r->dev;
-    a.generation = r->generation;
-    a.item_bytes = r->window ? (int)sizeof(mbn_label_window_item) : (int)sizeof(mbn_label_item);
+    a.set = mbn_ragged_readout_view(r);
     // the items of the last set, as the handle's pinned block still holds them: every map inside the envelope, and the units of the call
-    int shape = MBN_OK;
     double pixels = 0.0;
-    for (int i = 0; i < r->batch; i++) {
-        const mbn_label_item *it = (const mbn_label_item *)((const char *)r->host + sizeof(SetHead) + (size_t)i * a.item_bytes);
-        const int rc = mbn_components_envelope(r->batch, it->rows, it->cols, classes, connectivity, min_area, max_regions);
-        if (rc == MBN_EINVAL || (rc != MBN_OK && shape == MBN_OK)) shape = rc;
-        if (rc != MBN_OK) continue;
-        a.tiles += cc_tiles(it->rows, it->cols);
-        a.chunks += cc_chunks(it->rows, it->cols);
-        pixels += (double)it->rows * it->cols;
-    }
+    const int shape = mbn_ragged_readout_envelope(r, [&](const mbn_label_item &it) {
+        const int rc = mbn_components_envelope(r->batch, it.rows, it.cols, classes, connectivity, min_area, max_regions);
+        if (rc == MBN_OK) {
+            a.tiles += cc_tiles(it.rows, it.cols);
+            a.chunks += cc_chunks(it.rows, it.cols);
+            pixels += (double)it.rows * it.cols;
+        }
+        return rc;
+    });
     return cc_call(h, r, a, shape, r->batch, (double)r->launch.span, pixels, stream);
 }
 

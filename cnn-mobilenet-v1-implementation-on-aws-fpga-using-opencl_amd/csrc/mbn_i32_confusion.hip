@@ -21,18 +21,13 @@
 // ones. The lanes whose four cells agree elect a leader per distinct cell (readfirstlane + ballot) and the leader adds 4 * popcount once: a constant
 // map costs one atomic per wave and chunk (256 pixels), not 256. Lanes whose four cells differ add them one by one.
 #include "mbn_internal.h"
+#include "mbn_label_set.h"
 
 namespace {
 
 constexpr int CF_THREADS = 1024;          // lanes of a workgroup = groups of a chunk
 constexpr int CF_EPOCH = 512;             // chunks between two flushes of the LDS table: 512 * 4096 pixels < 2^32
 constexpr int CF_LEADERS = 16;            // distinct cells a wave aggregates per chunk; the lanes left over add on their own
-
-// head of a ragged read-out handle's device block, in front of its items (mbn_f32_resample.hip writes it): 16 bytes like an mbn_label_item
-struct SetHead {
-    int32_t batch, generation, pad[2];
-};
-static_assert(sizeof(SetHead) == 16 && sizeof(mbn_label_item) == 16 && sizeof(mbn_label_window_item) == 32, "device layout");
 
 struct __attribute__((packed, aligned(4))) I32x4 { int32_t x, y, z, w; };      // four int32 on 4 bytes: one global_load_dwordx4
 
@@ -42,9 +37,7 @@ struct ConfusionArgs {
     const uint8_t *truth;      // element 0 of the truth, uint8 or int32
     int classes;
     long long count;           // uniform form: the span
-    const SetHead *head;       // ragged form: the handle's block, its generation and the bytes of one item
-    int generation;
-    int item_bytes;
+    mbn_label_set set;         // ragged form: the view of the handle's set
 };
 
 template <bool LDS>
@@ -158,8 +151,8 @@ __global__ __launch_bounds__(CF_THREADS) void confusion_i32(const ConfusionArgs 
     const int bins = (a.classes + 1) * (a.classes + 1);
     int batch = 1;
     if (RAGGED) {
-        if (a.head->generation != a.generation) return;                        // captured under an earlier set: nothing to score
-        batch = a.head->batch;
+        if (mbn_label_set_stale(a.set)) return;                                // captured under an earlier set: nothing to score
+        batch = a.set.head->batch;
     }
     if (LDS) {
         for (int i = threadIdx.x; i < bins; i += CF_THREADS) s_bins[i] = 0;
@@ -171,7 +164,7 @@ __global__ __launch_bounds__(CF_THREADS) void confusion_i32(const ConfusionArgs 
     for (int i = 0; i < batch; i++) {
         long long off = 0, n = a.count;
         if (RAGGED) {
-            const mbn_label_item *it = (const mbn_label_item *)((const char *)(a.head + 1) + (size_t)i * a.item_bytes);
+            const mbn_label_item *it = mbn_label_set_item(a.set, i);
             off = it->dst_offset;
             n = (long long)it->rows * it->cols;
         }
@@ -205,9 +198,7 @@ void cf_launch(mbn_context *ctx, hipStream_t s, bool ragged, const ConfusionArgs
     const int form = mbn_confusion_form(a.classes);
     const int lds_bytes = form == MBN_CONFUSION_FORM_LDS ? (a.classes + 1) * (a.classes + 1) * 4 : 0;
     const int per_cu = 2 * lds_bytes > MBN_CONFUSION_CU_LDS ? 1 : 2;
-    long long grid = (long long)(ctx->num_cus > 0 ? ctx->num_cus : 1) * per_cu;
-    const long long chunks = pixels / (4 * CF_THREADS) + items;
-    if (grid > chunks) grid = chunks;
+    const unsigned grid = mbn_persistent_grid(ctx->num_cus, per_cu, pixels / (4 * CF_THREADS) + items);
     // the LDS form's table reaches 91 204 bytes: above the 64 KB a launch gets without asking (once per process; not a stream operation)
     static std::once_flag asked;
     std::call_once(asked, [] {
@@ -216,7 +207,7 @@ void cf_launch(mbn_context *ctx, hipStream_t s, bool ragged, const ConfusionArgs
                 (void)hipFuncSetAttribute((const void *)cf_kernels[rg][MBN_CONFUSION_FORM_LDS][tb], hipFuncAttributeMaxDynamicSharedMemorySize,
                                           MBN_CONFUSION_LDS);
     });
-    hipLaunchKernelGGL(cf_kernels[ragged][form][truth_bytes == 4], dim3((unsigned)grid), dim3(CF_THREADS), (size_t)lds_bytes, s, a);
+    hipLaunchKernelGGL(cf_kernels[ragged][form][truth_bytes == 4], dim3(grid), dim3(CF_THREADS), (size_t)lds_bytes, s, a);
 }
 
 }   // namespace
@@ -246,12 +237,8 @@ int mbn_launch_i32_confusion_ragged(mbn_ragged_readout *r, hipStream_t s, void *
     a.labels = (const int32_t *)labels;
     a.truth = (const uint8_t *)truth;
     a.classes = classes;
-    a.head = (const SetHead *)r->dev;
-    a.generation = r->generation;
-    a.item_bytes = r->window ? (int)sizeof(mbn_label_window_item) : (int)sizeof(mbn_label_item);
+    a.set = mbn_ragged_readout_view(r);
     cf_launch(r->ctx, s, true, a, truth_bytes, r->launch.span, r->batch);
-    // the next set waits for this launch; inside a capture there is nothing to wait for (the replays are the caller's to order)
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) (void)hipEventRecord(r->done, s);
+    mbn_ragged_readout_mark_done(r, s);
     return MBN_OK;
 }

@@ -22,8 +22,7 @@
 // that from n_*_i32 itself. The units of a pixel kernel (chunks of 1024 pixels) are dealt round robin to a grid sized from the planning CU count;
 // the grid of a slot kernel is batch x the workgroups of one image, each striding over the slots of its one image.
 #include "mbn_internal.h"
-
-#include <new>
+#include "mbn_label_set.h"
 
 namespace {
 
@@ -38,12 +37,6 @@ static_assert(CHUNK == 4 * PQ_THREADS, "four pixels per lane and chunk");
 static_assert(WORDS <= 64 && W_BIT0 + MBN_PANOPTIC_BITS == WORDS, "lane w of a wave carries word w of a slot");
 static_assert((1 << MBN_PANOPTIC_BITS) >= MBN_COMPONENTS_MAX_REGIONS, "a truth number fits the counted bits");
 
-// head of a ragged read-out handle's device block, in front of its items (mbn_f32_resample.hip writes it): 16 bytes like an mbn_label_item
-struct SetHead {
-    int32_t batch, generation, pad[2];
-};
-static_assert(sizeof(SetHead) == 16 && sizeof(mbn_label_item) == 16 && sizeof(mbn_label_window_item) == 32 && sizeof(mbn_region) == 32, "device layout");
-
 struct PqArgs {
     const int32_t *comp_pred, *comp_truth;
     const int32_t *pred, *truth;              // the records, eight int32 each: [0] label, [1] area
@@ -52,49 +45,20 @@ struct PqArgs {
     int32_t *scored, *match_pred, *match_truth, *inter, *voided;
     int32_t *slots, *tslots, *cands;          // the handle's scratch: [batch][max_pred][WORDS], [batch][max_truth] and [batch][max_pred]
     int batch, rows, cols;                    // batch: both forms (the ragged set's); rows, cols: uniform form
-    const SetHead *head;                      // ragged form: the read-out handle's block, its generation and the bytes of one item
-    int generation, item_bytes;
+    mbn_label_set set;                        // ragged form: the view of the read-out handle's set
     long long chunks;                         // units of a pixel kernel over the whole call
     int max_pred, max_truth, classes;
 };
 
-// one chunk of pixels: the image it lies in and its number inside that image
-struct Unit {
-    long long off;        // the image's first element in comp_pred / comp_truth
-    int rows, cols, image;
-    int unit;
-};
-
 __host__ __device__ inline long long pq_chunks(int rows, int cols) { return ((long long)rows * cols + CHUNK - 1) / CHUNK; }
 
-// chunk u of the call. Uniform across the workgroup (u is). The ragged form walks the items: plain loads, they were uploaded before the launch
+// chunk u of the call: the image it lies in (off: its first element in comp_pred / comp_truth) and its number inside that image. Uniform across
+// the workgroup (u is)
+using Unit = mbn_label_unit;
 template <bool RAGGED>
-__device__ __forceinline__ bool locate(const PqArgs &a, long long u, Unit &w)
+__device__ __forceinline__ bool pq_unit(const PqArgs &a, long long u, Unit &w)
 {
-    if (!RAGGED) {
-        const long long per = pq_chunks(a.rows, a.cols);
-        const long long i = u / per;
-        if (i >= a.batch) return false;
-        w.image = (int)i;
-        w.unit = (int)(u - i * per);
-        w.rows = a.rows; w.cols = a.cols;
-        w.off = i * ((long long)a.rows * a.cols);
-        return true;
-    }
-    const int batch = a.head->batch;
-    for (int i = 0; i < batch; i++) {
-        const mbn_label_item *it = (const mbn_label_item *)((const char *)(a.head + 1) + (size_t)i * a.item_bytes);
-        const long long per = pq_chunks(it->rows, it->cols);
-        if (u < per) {
-            w.image = i;
-            w.unit = (int)u;
-            w.rows = it->rows; w.cols = it->cols;
-            w.off = it->dst_offset;
-            return true;
-        }
-        u -= per;
-    }
-    return false;
+    return mbn_label_set_unit<RAGGED, pq_chunks>(a.set, a.batch, a.rows, a.cols, u, w);
 }
 
 // what every kernel reads of an image: its two counts (a negative one counts as 0) and whether its tables hold them
@@ -139,7 +103,7 @@ __device__ __forceinline__ void add_u64(unsigned long long *p, unsigned long lon
 template <bool RAGGED>
 __global__ __launch_bounds__(PQ_THREADS) void pq_clear(const PqArgs a)
 {
-    if (RAGGED && a.head->generation != a.generation) return;                  // captured under an earlier set: nothing to do
+    if (RAGGED && mbn_label_set_stale(a.set)) return;                  // captured under an earlier set: nothing to do
     const Share sh = pq_share(a);
     const Image im = pq_image(a, sh.image);
     if (sh.first == 0 && threadIdx.x == 0) a.scored[sh.image] = im.scored;
@@ -153,7 +117,7 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_clear(const PqArgs a)
 template <bool RAGGED>
 __global__ __launch_bounds__(PQ_THREADS) void pq_vote(const PqArgs a)
 {
-    if (RAGGED && a.head->generation != a.generation) return;
+    if (RAGGED && mbn_label_set_stale(a.set)) return;
     const int lane = threadIdx.x & 63;
     // what the wave still owes the slot it met last: lane w holds word w's count. It is added when the wave meets another slot, and at the end:
     // a wave that stays inside one segment, over all its chunks, issues one atomic instruction
@@ -161,7 +125,7 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_vote(const PqArgs a)
     int owed = 0;
     for (long long u = blockIdx.x; u < a.chunks; u += gridDim.x) {
         Unit w;
-        if (!locate<RAGGED>(a, u, w)) break;
+        if (!pq_unit<RAGGED>(a, u, w)) break;
         const Image im = pq_image(a, w.image);
         if (!im.scored) continue;
         const int n = w.rows * w.cols;
@@ -213,7 +177,7 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_vote(const PqArgs a)
 template <bool RAGGED>
 __global__ __launch_bounds__(PQ_THREADS) void pq_candidate(const PqArgs a)
 {
-    if (RAGGED && a.head->generation != a.generation) return;
+    if (RAGGED && mbn_label_set_stale(a.set)) return;
     const Share sh = pq_share(a);
     const Image im = pq_image(a, sh.image);
     if (!im.scored) return;
@@ -233,13 +197,13 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_candidate(const PqArgs a)
 template <bool RAGGED>
 __global__ __launch_bounds__(PQ_THREADS) void pq_intersect(const PqArgs a)
 {
-    if (RAGGED && a.head->generation != a.generation) return;
+    if (RAGGED && mbn_label_set_stale(a.set)) return;
     const int lane = threadIdx.x & 63;
     long long owed_slot = -1;                                                              // as in `vote`; lane 0 holds the count
     int owed = 0;
     for (long long u = blockIdx.x; u < a.chunks; u += gridDim.x) {
         Unit w;
-        if (!locate<RAGGED>(a, u, w)) break;
+        if (!pq_unit<RAGGED>(a, u, w)) break;
         const Image im = pq_image(a, w.image);
         if (!im.scored) continue;
         const int n = w.rows * w.cols;
@@ -311,7 +275,7 @@ template <bool RAGGED>
 __global__ __launch_bounds__(PQ_THREADS) void pq_decide(const PqArgs a)
 {
     extern __shared__ unsigned long long s_pq[];
-    if (RAGGED && a.head->generation != a.generation) return;
+    if (RAGGED && mbn_label_set_stale(a.set)) return;
     const Share sh = pq_share(a);
     const Image im = pq_image(a, sh.image);
     if (!im.scored) return;                                                                // the whole workgroup
@@ -354,7 +318,7 @@ template <bool RAGGED>
 __global__ __launch_bounds__(PQ_THREADS) void pq_truth(const PqArgs a)
 {
     extern __shared__ unsigned long long s_pq[];
-    if (RAGGED && a.head->generation != a.generation) return;
+    if (RAGGED && mbn_label_set_stale(a.set)) return;
     const Share sh = pq_share(a);
     const Image im = pq_image(a, sh.image);
     if (!im.scored) return;
@@ -376,35 +340,6 @@ __global__ __launch_bounds__(PQ_THREADS) void widen_u8(int32_t *dst, const uint8
     for (long long k = (long long)blockIdx.x * PQ_THREADS + threadIdx.x; k < count; k += (long long)gridDim.x * PQ_THREADS) dst[k] = src[k];
 }
 
-// the bounds rule of mbn_alloc (the neighbours keep their own copies): a pointer inside a tracked buffer must leave room for the bytes the call touches
-struct Span { const void *p; double bytes; const char *what; };
-
-int pq_spans(mbn_context *ctx, const Span *sp, int count)
-{
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    for (int i = 0; i < count; i++) {
-        if (!sp[i].p || sp[i].bytes <= 0 || ctx->allocs.empty()) continue;
-        const uintptr_t at = (uintptr_t)sp[i].p;
-        auto it = ctx->allocs.upper_bound(at);
-        if (it == ctx->allocs.begin()) continue;
-        --it;
-        if (at >= it->first + it->second) continue;                                        // not inside any of our buffers
-        const double room = (double)(it->first + it->second - at);
-        if (sp[i].bytes > room) {
-            snprintf(ctx->last_error, sizeof(ctx->last_error), "%s: call touches %.0f bytes, %.0f left in its %zu-byte mbn_alloc buffer", sp[i].what,
-                     sp[i].bytes, room, it->second);
-            return MBN_EINVAL;
-        }
-    }
-    return MBN_OK;
-}
-
-unsigned pq_grid(const mbn_context *ctx, long long units)
-{
-    const long long most = (long long)(ctx->num_cus > 0 ? ctx->num_cus : 1) * PQ_WGS_PER_CU;
-    return (unsigned)(units < most ? (units > 0 ? units : 1) : most);
-}
-
 // a slot kernel: `batch` times the workgroups of one image, as many as its units want and the planning CU count gives (one at least)
 unsigned pq_slot_grid(const mbn_context *ctx, int batch, long long units)
 {
@@ -422,9 +357,9 @@ void pq_launch(mbn_context *ctx, hipStream_t s, const PqArgs &a, int batch)
     const unsigned word_grid = pq_slot_grid(ctx, batch, (most * WORDS + PQ_THREADS - 1) / PQ_THREADS);
     const unsigned lds = a.classes <= PQ_LDS_CLASSES ? 32u * a.classes : 0u;
     hipLaunchKernelGGL(pq_clear<RAGGED>, dim3(word_grid), block, 0, s, a);
-    hipLaunchKernelGGL(pq_vote<RAGGED>, dim3(pq_grid(ctx, a.chunks)), block, 0, s, a);
+    hipLaunchKernelGGL(pq_vote<RAGGED>, dim3(mbn_persistent_grid(ctx->num_cus, PQ_WGS_PER_CU, a.chunks)), block, 0, s, a);
     hipLaunchKernelGGL(pq_candidate<RAGGED>, dim3(slot_grid), block, 0, s, a);
-    hipLaunchKernelGGL(pq_intersect<RAGGED>, dim3(pq_grid(ctx, a.chunks)), block, 0, s, a);
+    hipLaunchKernelGGL(pq_intersect<RAGGED>, dim3(mbn_persistent_grid(ctx->num_cus, PQ_WGS_PER_CU, a.chunks)), block, 0, s, a);
     hipLaunchKernelGGL(pq_decide<RAGGED>, dim3(slot_grid), block, lds, s, a);
     hipLaunchKernelGGL(pq_truth<RAGGED>, dim3(slot_grid), block, lds, s, a);
 }
@@ -440,38 +375,30 @@ int pq_call(mbn_panoptic *h, mbn_ragged_readout *r, PqArgs &a, int shape, int ba
         if ((uintptr_t)p % 4) return MBN_EINVAL;
     if (shape != MBN_OK) return shape;
     const int most = a.max_pred > a.max_truth ? a.max_pred : a.max_truth;
-    if (batch > h->max_batch || (int64_t)batch * most > h->max_slots) return MBN_EINVAL;
+    if (batch > h->max_batch || (int64_t)batch * most > h->capacity) return MBN_EINVAL;
     const double np = (double)batch * a.max_pred, nt = (double)batch * a.max_truth;
-    const Span sp[] = { { a.pq, 32.0 * a.classes, "panoptic pq" }, { a.scored, 4.0 * batch, "panoptic scored" },
+    const mbn_span sp[] = { { a.pq, 32.0 * a.classes, "panoptic pq" }, { a.scored, 4.0 * batch, "panoptic scored" },
                         { a.match_pred, 4.0 * np, "panoptic match_pred" }, { a.match_truth, 4.0 * nt, "panoptic match_truth" },
                         { a.inter, 4.0 * np, "panoptic inter" }, { a.voided, 4.0 * np, "panoptic void" },
                         { a.comp_pred, 4.0 * span, "panoptic comp_pred" }, { a.pred, 32.0 * np, "panoptic pred" },
                         { a.n_pred, 4.0 * batch, "panoptic n_pred" }, { a.comp_truth, 4.0 * span, "panoptic comp_truth" },
                         { a.truth, 32.0 * nt, "panoptic truth" }, { a.n_truth, 4.0 * batch, "panoptic n_truth" } };
-    const int rc = pq_spans(ctx, sp, (int)(sizeof sp / sizeof sp[0]));
+    const int rc = mbn_span_check(ctx, sp, (int)(sizeof sp / sizeof sp[0]));
     if (rc != MBN_OK) return rc;
     a.slots = (int32_t *)h->scratch;
-    a.tslots = a.slots + h->max_slots * WORDS;
-    a.cands = a.tslots + h->max_slots;
+    a.tslots = a.slots + h->capacity * WORDS;
+    a.cands = a.tslots + h->capacity;
     a.batch = batch;
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     (void)hipSetDevice(ctx->device);
     if (r) {
         pq_launch<true>(ctx, s, a, batch);
-        // the next set waits for this launch; inside a capture there is nothing to wait for (the replays are the caller's to order)
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) (void)hipEventRecord(r->done, s);
+        mbn_ragged_readout_mark_done(r, s);
     } else {
         pq_launch<false>(ctx, s, a, batch);
     }
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? MBN_OK : mbn_record_hip_error(ctx, e, "panoptic launch");
-}
-
-void pq_release(mbn_panoptic *h)
-{
-    if (h->scratch) (void)hipFree(h->scratch);
-    delete h;
 }
 
 PqArgs pq_args(void *pq_u64, void *scored_i32, void *match_pred_i32, void *match_truth_i32, void *inter_i32, void *void_i32, const void *comp_pred_i32,
@@ -495,53 +422,14 @@ bool pq_required(const PqArgs &a)
 
 }   // namespace
 
-mbn_panoptic_list::~mbn_panoptic_list()
-{
-    for (mbn_panoptic *h : live) pq_release(h);
-}
-
 extern "C" {
 
 int mbn_panoptic_create(mbn_context *ctx, int max_batch, int64_t max_slots, mbn_panoptic **h)
 {
-    if (!ctx || !h) return MBN_EINVAL;
-    *h = nullptr;
-    if (max_batch < 1 || max_slots < 1) return MBN_EINVAL;
-    const int64_t bytes = mbn_panoptic_scratch_bytes(max_batch, max_slots);
-    if (bytes <= 0) return MBN_EUNSUPPORTED;
-    mbn_panoptic *c = new (std::nothrow) mbn_panoptic();
-    if (!c) return MBN_ENOMEM;
-    c->ctx = ctx;
-    c->max_batch = max_batch;
-    c->max_slots = max_slots;
-    (void)hipSetDevice(ctx->device);
-    if (hipMalloc(&c->scratch, (size_t)bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        c->scratch = nullptr;
-        pq_release(c);
-        return MBN_ENOMEM;
-    }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->panoptic.live.push_back(c);
-    *h = c;
-    return MBN_OK;
+    return mbn_scratch_create(ctx, max_batch, max_slots, mbn_panoptic_scratch_bytes(max_batch, max_slots), h);
 }
 
-int mbn_panoptic_destroy(mbn_panoptic *h)
-{
-    if (!h) return MBN_OK;
-    mbn_context *ctx = h->ctx;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        auto &live = ctx->panoptic.live;
-        for (auto it = live.begin(); it != live.end(); ++it)
-            if (*it == h) { live.erase(it); break; }
-    }
-    (void)hipSetDevice(ctx->device);
-    MBN_HIP_TRY(ctx, hipDeviceSynchronize());                    // its last launch, whatever the stream
-    pq_release(h);
-    return MBN_OK;
-}
+int mbn_panoptic_destroy(mbn_panoptic *h) { return mbn_scratch_destroy(h); }
 
 int mbn_panoptic_i32(mbn_panoptic *h, void *pq_u64, void *scored_i32, void *match_pred_i32, void *match_truth_i32, void *inter_i32, void *void_i32,
                      const void *comp_pred_i32, const mbn_region *pred, const void *n_pred_i32, int max_pred, const void *comp_truth_i32,
@@ -567,18 +455,13 @@ int mbn_panoptic_ragged_i32(mbn_panoptic *h, mbn_ragged_readout *r, void *pq_u64
     PqArgs a = pq_args(pq_u64, scored_i32, match_pred_i32, match_truth_i32, inter_i32, void_i32, comp_pred_i32, pred, n_pred_i32, max_pred,
                        comp_truth_i32, truth, n_truth_i32, max_truth, classes);
     if (!h || !r || r->ctx != h->ctx || r->batch <= 0 || !pq_required(a)) return MBN_EINVAL;                   // no set: nothing to score
-    a.head = (const SetHead *)r->dev;
-    a.generation = r->generation;
-    a.item_bytes = r->window ? (int)sizeof(mbn_label_window_item) : (int)sizeof(mbn_label_item);
+    a.set = mbn_ragged_readout_view(r);
     // the items of the last set, as the handle's pinned block still holds them: every map inside the envelope, and the units of the call
-    int shape = MBN_OK;
-    for (int i = 0; i < r->batch; i++) {
-        const mbn_label_item *it = (const mbn_label_item *)((const char *)r->host + sizeof(SetHead) + (size_t)i * a.item_bytes);
-        const int rc = mbn_panoptic_envelope(r->batch, it->rows, it->cols, classes, max_pred, max_truth);
-        if (rc == MBN_EINVAL || (rc != MBN_OK && shape == MBN_OK)) shape = rc;
-        if (rc != MBN_OK) continue;
-        a.chunks += pq_chunks(it->rows, it->cols);
-    }
+    const int shape = mbn_ragged_readout_envelope(r, [&](const mbn_label_item &it) {
+        const int rc = mbn_panoptic_envelope(r->batch, it.rows, it.cols, classes, max_pred, max_truth);
+        if (rc == MBN_OK) a.chunks += pq_chunks(it.rows, it.cols);
+        return rc;
+    });
     return pq_call(h, r, a, shape, r->batch, (double)r->launch.span, stream);
 }
 
@@ -590,12 +473,13 @@ int64_t mbn_ragged_readout_span(const mbn_ragged_readout *r)
 int mbn_widen_u8_i32(mbn_context *ctx, void *dst_i32, const void *src_u8, int64_t count, void *stream)
 {
     if (!ctx || !dst_i32 || !src_u8 || count < 1 || (uintptr_t)dst_i32 % 4) return MBN_EINVAL;
-    const Span sp[] = { { dst_i32, 4.0 * (double)count, "widen dst" }, { src_u8, (double)count, "widen src" } };
-    const int rc = pq_spans(ctx, sp, 2);
+    const mbn_span sp[] = { { dst_i32, 4.0 * (double)count, "widen dst" }, { src_u8, (double)count, "widen src" } };
+    const int rc = mbn_span_check(ctx, sp, 2);
     if (rc != MBN_OK) return rc;
     (void)hipSetDevice(ctx->device);
-    hipLaunchKernelGGL(widen_u8, dim3(pq_grid(ctx, (count + CHUNK - 1) / CHUNK)), dim3(PQ_THREADS), 0, stream ? (hipStream_t)stream : ctx->stream,
-                       (int32_t *)dst_i32, (const uint8_t *)src_u8, (long long)count);
+    const unsigned grid = mbn_persistent_grid(ctx->num_cus, PQ_WGS_PER_CU, (count + CHUNK - 1) / CHUNK);
+    hipLaunchKernelGGL(widen_u8, dim3(grid), dim3(PQ_THREADS), 0, stream ? (hipStream_t)stream : ctx->stream, (int32_t *)dst_i32,
+                       (const uint8_t *)src_u8, (long long)count);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? MBN_OK : mbn_record_hip_error(ctx, e, "widen launch");
 }

@@ -9,6 +9,7 @@
 #include <atomic>
 #include <map>
 #include <mutex>
+#include <new>
 #include <vector>
 
 #include "mbn.h"
@@ -66,33 +67,26 @@ struct mbn_ragged_readout {
     hipEvent_t done = nullptr;                   // behind the last upload or launch: the next set waits for it
 };
 
-// mbn_components_create's handle (mbn_i32_components.hip): the scratch of the seven kernels, allocated once
-struct mbn_components {
+// A scratch handle: device memory for the kernels of one family of calls, allocated once for up to max_batch images and `capacity` of the
+// family's unit. mbn_scratch_create / _destroy (mbn_abi.hip) serve every family; the public types stay distinct
+struct mbn_scratch {
     mbn_context *ctx = nullptr;
     int max_batch = 0;
-    int64_t max_pixels = 0;
-    void *scratch = nullptr;                     // parent [max_pixels], area / rank [max_pixels], chunk counts [max_pixels / CHUNK + max_batch], int32
+    int64_t capacity = 0;
+    void *scratch = nullptr;
+    virtual ~mbn_scratch() = default;            // the context's list deletes a family's handle through this type
 };
+// mbn_components_create's handle (mbn_i32_components.hip): capacity = max_pixels; scratch = parent [max_pixels], area / rank [max_pixels],
+// chunk counts [max_pixels / CHUNK + max_batch], int32
+struct mbn_components : mbn_scratch {};
+// mbn_panoptic_create's handle (mbn_i32_panoptic.hip): capacity = max_slots; scratch = predicted slots [max_slots][MBN_PANOPTIC_SLOT_WORDS],
+// truth slots [max_slots], candidates [max_slots], int32
+struct mbn_panoptic : mbn_scratch {};
 
-// the live mbn_components_create handles of a context. Its destructor (mbn_i32_components.hip) frees the stragglers when mbn_shutdown deletes
-// the context
-struct mbn_components_list {
-    std::vector<mbn_components *> live;
-    ~mbn_components_list();
-};
-
-// mbn_panoptic_create's handle (mbn_i32_panoptic.hip): the slots of the six kernels, allocated once
-struct mbn_panoptic {
-    mbn_context *ctx = nullptr;
-    int max_batch = 0;
-    int64_t max_slots = 0;
-    void *scratch = nullptr;                     // predicted slots [max_slots][MBN_PANOPTIC_SLOT_WORDS], truth slots [max_slots], candidates [max_slots], int32
-};
-
-// the live mbn_panoptic_create handles of a context, freed like the components handles (the destructor is in mbn_i32_panoptic.hip)
-struct mbn_panoptic_list {
-    std::vector<mbn_panoptic *> live;
-    ~mbn_panoptic_list();
+// the live scratch handles of a context. Its destructor (mbn_abi.hip) frees the stragglers when mbn_shutdown deletes the context
+struct mbn_scratch_list {
+    std::vector<mbn_scratch *> live;
+    ~mbn_scratch_list();
 };
 
 struct mbn_context {
@@ -119,8 +113,7 @@ struct mbn_context {
     std::vector<mbn_resizer *> resizers;         // live mbn_resizer_create handles (mbn_shutdown frees the stragglers)
     std::vector<mbn_ragged_resizer *> ragged_resizers;   // live mbn_ragged_resizer_create handles, likewise
     std::vector<mbn_ragged_readout *> ragged_readouts;   // live mbn_ragged_readout_create handles, likewise
-    mbn_components_list components;              // live mbn_components_create handles (freed with the context)
-    mbn_panoptic_list panoptic;                  // live mbn_panoptic_create handles, likewise
+    mbn_scratch_list scratches;                  // live mbn_components_create / mbn_panoptic_create handles (freed with the context)
     std::mutex mu;
     std::map<uintptr_t, size_t> allocs;          // buffers handed out by mbn_alloc: base address -> bytes (ordered: mbn_span_check
                                                  // finds the allocation that CONTAINS an interior pointer)
@@ -137,6 +130,49 @@ static inline int mbn_record_hip_error(mbn_context *ctx, hipError_t e, const cha
         hipError_t _e = (expr);                                                   \
         if (_e != hipSuccess) return mbn_record_hip_error((ctx), _e, #expr);      \
     } while (0)
+
+// The bounds rule of mbn_alloc (mbn_abi.hip): a pointer inside a tracked buffer must leave room for the bytes the call touches, else MBN_EINVAL
+// and last_error names `what`. A null pointer, a span of no bytes and caller-owned memory are not checked.
+struct mbn_span { const void *p; double bytes; const char *what; };
+int mbn_span_check(mbn_context *ctx, const mbn_span *spans, int n);
+// [p, p + p_bytes) and [q, q + q_bytes) share a byte; a null pointer never overlaps
+bool mbn_spans_overlap(const void *p, double p_bytes, const void *q, double q_bytes);
+
+// The grid of a persistent kernel: per_cu workgroups on each CU of the planning count, no more than there are units, one at least
+static inline unsigned mbn_persistent_grid(int num_cus, int per_cu, long long units)
+{
+    const long long most = (long long)(num_cus > 0 ? num_cus : 1) * per_cu;
+    return (unsigned)(units < most ? (units > 0 ? units : 1) : most);
+}
+
+// The scratch handles' life. create: the checks and return codes of mbn_components_create / mbn_panoptic_create (include/mbn.h), `bytes` = the
+// family's mbn_*_scratch_bytes answer. destroy: null is MBN_OK; waits for the device (the handle's last launch, whatever the stream).
+void mbn_scratch_release(mbn_scratch *h);
+int mbn_scratch_destroy(mbn_scratch *h);
+template <typename H>
+int mbn_scratch_create(mbn_context *ctx, int max_batch, int64_t capacity, int64_t bytes, H **h)
+{
+    if (!ctx || !h) return MBN_EINVAL;
+    *h = nullptr;
+    if (max_batch < 1 || capacity < 1) return MBN_EINVAL;
+    if (bytes <= 0) return MBN_EUNSUPPORTED;
+    H *c = new (std::nothrow) H();
+    if (!c) return MBN_ENOMEM;
+    c->ctx = ctx;
+    c->max_batch = max_batch;
+    c->capacity = capacity;
+    (void)hipSetDevice(ctx->device);
+    if (hipMalloc(&c->scratch, (size_t)bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        c->scratch = nullptr;
+        mbn_scratch_release(c);
+        return MBN_ENOMEM;
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->scratches.live.push_back(c);
+    *h = c;
+    return MBN_OK;
+}
 
 // Process-wide switches (mbn_tune_set). 0 = shipped default everywhere.
 // Two kinds. PRODUCT switches select between code paths that every build contains (the opt-in pw_emul arithmetic, the
