@@ -113,6 +113,23 @@ class View(C.Structure):
         return (self.x, self.y, self.iw, self.ih)
 
 
+SLIDE_MAX_AXIS = 16
+
+
+class Slide(C.Structure):
+    """mbn_slide (include/mbn.h, "segment by sliding window"): a grid of ny x nx tiles of tile_rows x tile_cols at rows y[] and columns x[];
+    144 bytes, the unused positions 0"""
+    _fields_ = [(n, C.c_int32) for n in ("tile_rows", "tile_cols", "ny", "nx")] + [("y", C.c_int32 * SLIDE_MAX_AXIS), ("x", C.c_int32 * SLIDE_MAX_AXIS)]
+
+    @property
+    def ys(self):
+        return list(self.y[:self.ny])
+
+    @property
+    def xs(self):
+        return list(self.x[:self.nx])
+
+
 class BoundaryMetrics(C.Structure):
     """mbn_boundary_metrics_t (include/mbn.h, "score a segmentation at its boundaries")"""
     _fields_ = [("boundary_miou", C.c_double), ("truth_band_pixels", C.c_double), ("pred_band_pixels", C.c_double),
@@ -235,6 +252,11 @@ def _declare_host(lib):
     lib.mbn_fit_view.argtypes = [C.c_int] * 4 + [C.c_float, C.c_int, C.POINTER(View)]
     lib.mbn_resample_ensemble_envelope.argtypes = [C.c_int] * 6 + [C.POINTER(View), C.c_int, C.c_int, C.c_int]      # mbn_envelope.h, like the next two
     lib.mbn_resample_ensemble_plan.argtypes = [C.c_int] * 4 + [C.POINTER(View), C.c_int, C.c_int, C.c_int, C.POINTER(ResampleLaunch)]
+    lib.mbn_slide_axis.argtypes = [C.c_int] * 3 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.mbn_slide_plan.argtypes = [C.c_int] * 6 + [C.POINTER(Slide)]
+    lib.mbn_slide_check.argtypes = [C.POINTER(Slide), C.c_int, C.c_int]                                            # mbn_envelope.h, like the next two
+    lib.mbn_resample_slide_envelope.argtypes = [C.c_int] * 4 + [C.POINTER(Slide), C.c_int, C.c_int]
+    lib.mbn_resample_slide_plan.argtypes = [C.c_int, C.c_int, C.POINTER(Slide), C.c_int, C.c_int, C.POINTER(ResampleLaunch)]
     lib.mbn_resize_view_table_plan_filter.argtypes = [C.c_int] * 5 + [C.POINTER(View), C.POINTER(ResizePadPlan)]
     lib.mbn_resample_ragged_window_check.argtypes = [C.c_int] * 5 + [C.POINTER(LabelWindowItem), C.c_int, C.POINTER(C.c_int64),
                                                                      C.POINTER(ResampleLaunch)]
@@ -403,6 +425,9 @@ def load():
                                                         C.POINTER(C.c_int64), vp, C.c_float, ci]
         lib.mbn_net_segment_images.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, vp, C.POINTER(C.c_int64), vp]
         lib.mbn_resample_ensemble_f32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(View), ci, ci, ci, C.c_float, ci, vp]
+        lib.mbn_resample_slide_f32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, C.POINTER(Slide), ci, ci, C.c_float, ci, vp]
+        lib.mbn_net_resize_tiles.argtypes = [vp, vp, ci, ci, ci, C.POINTER(Slide), C.POINTER(vp)]
+        lib.mbn_net_segment_slide.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, C.c_float, ci]
         lib.mbn_resizer_create_view.argtypes = [vp, ci, ci, ci, ci, ci, C.POINTER(View), C.POINTER(C.c_uint8), C.POINTER(vp)]
         lib.mbn_net_resize_views.argtypes = [vp, vp, ci, ci, ci, C.POINTER(C.c_float), C.POINTER(C.c_int32), ci, C.POINTER(vp)]
         lib.mbn_net_segment_views_fit.argtypes = [vp, vp, ci, ci, ci, C.POINTER(C.c_float), C.POINTER(C.c_int32), ci, vp, vp, vp, C.c_float, ci]
@@ -573,6 +598,48 @@ def resample_ensemble_plan(rows, cols, in_rows, in_cols, view_list, out_rows, ou
     l = ResampleLaunch()
     _chk((lib or host_lib()).mbn_resample_ensemble_plan(rows, cols, in_rows, in_cols, arr, len(arr), out_rows, out_cols, C.byref(l)),
          "resample_ensemble_plan")
+    return l
+
+
+def slide_axis(size, tile, stride, lib=None) -> list:
+    """mbn_slide_axis: the positions of the tiles along an axis of `size`: regular steps, the last tile flush with the far edge."""
+    pos, n = (C.c_int32 * SLIDE_MAX_AXIS)(), C.c_int32()
+    _chk((lib or host_lib()).mbn_slide_axis(size, tile, stride, pos, C.byref(n)), "slide_axis(%d, %d, %d)" % (size, tile, stride))
+    return list(pos[:n.value])
+
+
+def slide_plan(in_rows, in_cols, tile_rows, tile_cols, stride_rows, stride_cols, lib=None) -> Slide:
+    """mbn_slide_plan: the grid of tiles over an in_rows x in_cols image."""
+    s = Slide()
+    _chk((lib or host_lib()).mbn_slide_plan(in_rows, in_cols, tile_rows, tile_cols, stride_rows, stride_cols, C.byref(s)),
+         "slide_plan(%d, %d, %d, %d, %d, %d)" % (in_rows, in_cols, tile_rows, tile_cols, stride_rows, stride_cols))
+    return s
+
+
+def slide(plan) -> Slide:
+    """A Slide from a Slide or a hand-made (tile_rows, tile_cols, ys, xs)."""
+    if isinstance(plan, Slide):
+        return plan
+    s = Slide()
+    s.tile_rows, s.tile_cols, ys, xs = plan
+    s.ny, s.nx = len(ys), len(xs)
+    for i, v in enumerate(ys[:SLIDE_MAX_AXIS]):
+        s.y[i] = int(v)
+    for i, v in enumerate(xs[:SLIDE_MAX_AXIS]):
+        s.x[i] = int(v)
+    return s
+
+
+def resample_slide_envelope(batch, rows, cols, classes, plan, out_rows, out_cols, lib=None) -> int:
+    """mbn_resample_slide_envelope: the status mbn_resample_slide_f32 gives the shape and the plan (None: a NULL plan)."""
+    return (lib or host_lib()).mbn_resample_slide_envelope(batch, rows, cols, classes, None if plan is None else C.byref(slide(plan)), out_rows, out_cols)
+
+
+def resample_slide_plan(rows, cols, plan, out_rows, out_cols, lib=None) -> ResampleLaunch:
+    """mbn_resample_slide_plan: the launch of a grid of tiles: a tile's footprint, the class chunk that keeps the most tiles over a piece in 64 KB,
+    one workgroup per piece of constant coverage."""
+    l = ResampleLaunch()
+    _chk((lib or host_lib()).mbn_resample_slide_plan(rows, cols, C.byref(slide(plan)), out_rows, out_cols, C.byref(l)), "resample_slide_plan")
     return l
 
 
@@ -1036,6 +1103,14 @@ class Context:
                                                 len(arr) if n_views is None else n_views, out_rows, out_cols, min_prob, ignore_label, None),
              self.last_error())
 
+    def resample_slide(self, labels, prob, score, logits, batch, rows, cols, classes, plan, out_rows, out_cols, min_prob=0.0, ignore_label=0,
+                       stream=None):
+        """mbn_resample_slide_f32: ONE read-out of the grid of tiles in `plan` (a Slide or (tile_rows, tile_cols, ys, xs)) over image-major logits
+        [batch][ny * nx][rows][cols][classes]: the interpolated logits are averaged over the tiles that cover a pixel in front of the argmax (and
+        the softmax). prob None with min_prob 0: the argmax form. `score` may be None."""
+        _chk(self.lib.mbn_resample_slide_f32(self.h, labels, prob, score, logits, batch, rows, cols, classes, C.byref(slide(plan)), out_rows, out_cols,
+                                             min_prob, ignore_label, stream), self.last_error())
+
     def confusion(self, counts, labels, truth, truth_bytes, classes, count, stream=None):
         """mbn_confusion_i32: counts (uint64 [classes + 1][classes + 1], device) += the confusion matrix of `count` int32 labels against truth
         (uint8: truth_bytes 1, int32: 4); row = truth (row `classes`: void), column = label (column `classes`: abstained)."""
@@ -1450,6 +1525,20 @@ class Net:
         _chk(self.ctx.lib.mbn_net_segment_views_fit(self.h, src_ptr, batch, in_rows, in_cols, (C.c_float * n)(*[float(v) for v in scales]),
                                                     (C.c_int32 * n)(*[int(v) for v in mirrors]), n, labels_ptr, prob_ptr, score_ptr, min_prob,
                                                     ignore_label), self.ctx.last_error())
+
+    def resize_tiles(self, src_ptr, batch, in_rows, in_cols, plan) -> int:
+        """mbn_net_resize_tiles: uint8 sources [batch][in_rows][in_cols][3] -> the net's staging buffer, image-major: image b's tile (iy, ix) of
+        `plan` at image b * ny * nx + iy * nx + ix (its device pointer is returned). batch * tiles <= max_batch."""
+        p = C.c_void_p()
+        _chk(self.ctx.lib.mbn_net_resize_tiles(self.h, src_ptr, batch, in_rows, in_cols, C.byref(slide(plan)), C.byref(p)), self.ctx.last_error())
+        return p.value
+
+    def segment_slide(self, src_ptr, batch, in_rows, in_cols, tile, stride, labels_ptr, prob_ptr=None, score_ptr=None, min_prob=0.0, ignore_label=0):
+        """mbn_net_segment_slide: sliding-window segmentation: tile = (rows, cols) crops at stride = (rows, cols), resize_tiles, ONE forward_dense
+        of batch * tiles images and ONE slide read-out (Context.resample_slide) to the source size: labels, prob and score
+        [batch][in_rows][in_cols]. Needs set_input_u8()."""
+        _chk(self.ctx.lib.mbn_net_segment_slide(self.h, src_ptr, batch, in_rows, in_cols, tile[0], tile[1], stride[0], stride[1], labels_ptr, prob_ptr,
+                                                score_ptr, min_prob, ignore_label), self.ctx.last_error())
 
     def segment_score(self, labels_ptr, truth_ptr, truth_bytes, counts_ptr):
         """mbn_net_segment_score: counts (uint64 [classes + 1][classes + 1]) += the confusion matrix of the maps the most recent successful

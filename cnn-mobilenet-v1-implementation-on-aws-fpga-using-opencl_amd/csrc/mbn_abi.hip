@@ -942,6 +942,22 @@ int mbn_resample_ensemble_f32(mbn_context *ctx, void *labels_i32, void *prob_f32
                         });
 }
 
+int mbn_resample_slide_f32(mbn_context *ctx, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, int batch, int rows, int cols,
+                           int classes, const mbn_slide *plan, int out_rows, int out_cols, float min_prob, int ignore_label, void *stream)
+{
+    if (!plan) return MBN_EINVAL;
+    // no prob map and no threshold: the argmax form (a NaN threshold is not 0: the softmax check refuses it)
+    const mbn_readout_prob prob = { (float *)prob_f32, min_prob, ignore_label };
+    const mbn_readout_prob *q = prob_f32 || !(min_prob == 0.0f) ? &prob : nullptr;
+    const int shape = mbn_resample_slide_envelope(batch, rows, cols, classes, plan, out_rows, out_cols);
+    const double maps = shape == MBN_OK ? (double)batch * plan->ny * plan->nx : 0.0;
+    return readout_call(ctx, labels_i32, score_f32, logits, q, shape, 4.0 * maps * rows * cols * classes, 4.0 * batch * out_rows * out_cols, stream,
+                        [&](hipStream_t s) {
+                            return mbn_launch_f32_resample_slide(ctx, s, (int32_t *)labels_i32, (float *)score_f32, (const float *)logits, batch, rows,
+                                                                 cols, classes, plan, out_rows, out_cols, q);
+                        });
+}
+
 int mbn_ragged_readout_create(mbn_context *ctx, int max_batch, mbn_ragged_readout **r)
 {
     if (!ctx || !r) return MBN_EINVAL;

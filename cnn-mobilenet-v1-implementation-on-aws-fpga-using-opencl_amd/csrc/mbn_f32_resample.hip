@@ -41,6 +41,8 @@
 // dropped by the maxima, and its difference is replaced by -200 by a max that drops the NaN: it adds exp(-200) = 0, exactly.
 // ENSEMBLE (mbn_resample_ensemble_f32; include/mbn.h, "segment with test-time augmentation"): K views read out as one map, kernels of their own on
 // the same tile, stage pass, lerps, softmax sum and store; described where they stand, behind rs_launch.
+// SLIDE (mbn_resample_slide_f32; include/mbn.h, "segment by sliding window"): a grid of overlapping tiles read out as one map, the ensemble's sibling
+// on pieces of constant coverage; described where it stands, behind the ensemble.
 #include "mbn_internal.h"
 #include "mbn_device.h"
 #include "mbn_label_set.h"
@@ -547,7 +549,208 @@ typedef void (*EnsKernel)(const EnsembleArgs);
 const EnsKernel ens_kernels[MBN_ENSEMBLE_MAX_VIEWS][2][2] = { ENS_K(1), ENS_K(2), ENS_K(3), ENS_K(4), ENS_K(5), ENS_K(6), ENS_K(7), ENS_K(8) };
 #undef ENS_K
 
+// ---- SLIDE (mbn_resample_slide_f32; include/mbn.h, "segment by sliding window"): a grid of overlapping tiles of the same images, each read out by
+// the plain rule to its own tile_rows x tile_cols rectangle of the output, is read out as ONE map: per class and pixel the interpolants of the tiles
+// over the pixel are summed in tile order, the sum is scaled by 1 / count, and the compare (and the softmax sum) sees that mean. A sibling of the
+// ensemble: the same lane layout, stage pass, lerps (ens_add), softmax sum and store. What differs:
+//   pieces  a view covers the whole output, a tile only its rectangle, and the number of tiles over a pixel varies. The tile edges cut each axis into
+//           cells of constant coverage (at most 31); a workgroup takes a PIECE, at most 32 x 32 outputs that start at a cell's corner and end at its
+//           far borders, so all its pixels have the same Ky x Kx <= 3 x 3 tiles over them. grid.x = pieces along y x pieces along x; a workgroup
+//           finds its cell in the per-axis prefix tables of its arguments (host/mbn_envelope.c, mbn_slide_cells). A piece need not start at a
+//           multiple of 32 of its tile: MBN_RESAMPLE_FOOT bounds what ANY 32 consecutive outputs touch
+//   rule    each tile is an image of its own: the plain rule (rs_axis, 32-bit) at the coordinate inside the tile
+//   state   a lane's state is separable: per tile ROW over the piece the four rows' weights, up bits and LDS row offsets, per tile COLUMN the
+//           column's weight and LDS offsets: 3 x 8 + 3 x 3 words instead of nine views' 9 x 12. The loops over the tile rows and columns are unrolled
+//           to three with a uniform guard, so the state is indexed at compile time only and stays in registers
+//   stage   per class chunk the Ky x Kx footprints go to LDS, tile (ky, kx) of the piece at (ky * Kx + kx) * fy * fx vectors
+struct SlideArgs {
+    int *labels;
+    float *score, *prob;     // either may be null (prob: PROB instantiations only)
+    const float *logits;     // [batch][ny * nx][rows][cols][classes]
+    int rows, cols, classes;
+    int out_rows, out_cols;
+    int fy, fx, ch;          // the launch's footprint PER TILE and the class chunk: mbn_resample_slide_plan
+    int cells_y, cells_x;
+    float min_prob;
+    int ignore_label;
+    float inv[10];           // inv[count] = 1.0f / (float)count
+    mbn_slide s;
+    int edge_y[MBN_SLIDE_MAX_CELLS + 1], pieces_y[MBN_SLIDE_MAX_CELLS + 1];      // mbn_slide_cells of the two axes
+    int edge_x[MBN_SLIDE_MAX_CELLS + 1], pieces_x[MBN_SLIDE_MAX_CELLS + 1];
+};
+static_assert(sizeof(mbn_slide) == 144, "a plan is 144 bytes: it travels in the kernel's arguments");
+
+constexpr int SL_K = 3;      // tiles over a coordinate at most
+
+// a workgroup's piece along one axis: its first output, its outputs (1..32), the first tile over it and how many are
+struct SlidePiece {
+    int o0, lim, k0, K;
+};
+
+// piece b of an axis: the cell is found in the prefix table (uniform, at most 31 steps); the tiles over it are those that hold its first output
+__device__ __forceinline__ SlidePiece slide_piece(const int *edge, const int *pieces, int cells, const int *pos, int n, int tile, int b)
+{
+    int c = 0;
+    while (c + 1 < cells && pieces[c + 1] <= b) c++;
+    SlidePiece p;
+    p.o0 = edge[c] + RS_TILE * (b - pieces[c]);
+    p.lim = min(RS_TILE, edge[c + 1] - p.o0);
+    p.k0 = p.K = 0;
+    for (int i = 0; i < n; i++) {
+        if (pos[i] + tile <= p.o0) p.k0 = i + 1;      // the positions ascend: the tiles that end in front of the piece are the first ones
+        else if (pos[i] <= p.o0) p.K++;
+    }
+    p.K = min(max(p.K, 1), SL_K);                     // 1..3 inside the envelope; the clamp keeps the staged slots inside the launch's LDS anyway
+    p.k0 = min(p.k0, n - p.K);
+    return p;
+}
+
+template <bool VEC, bool PROB>
+__global__ __launch_bounds__(256) void resample_slide_f32(const SlideArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_rs[];
+    const int tid = threadIdx.x;
+    const int pieces_x = a.pieces_x[a.cells_x];
+    const int by = (int)blockIdx.x / pieces_x, bx = (int)blockIdx.x - by * pieces_x;
+    const SlidePiece py = slide_piece(a.edge_y, a.pieces_y, a.cells_y, a.s.y, a.s.ny, a.s.tile_rows, by);
+    const SlidePiece px = slide_piece(a.edge_x, a.pieces_x, a.cells_x, a.s.x, a.s.nx, a.s.tile_cols, bx);
+    const size_t img = (size_t)blockIdx.y;                                                      // 64-bit bases, 32-bit offsets inside a map
+    const size_t map = (size_t)a.out_rows * a.out_cols, lmap = (size_t)a.rows * a.cols * a.classes;
+    const int ld = a.ch + 4, nv = a.fy * a.fx;
+    const int last_y = a.rows - 1, last_x = a.cols - 1;
+    const int lx = tid & 31, ly0 = RS_ROWS * (tid >> 5);
+    const bool active = lx < px.lim && ly0 < py.lim;
+    const int ox = px.o0 + lx, oy0 = py.o0 + ly0;
+    const int oxc = px.o0 + min(lx, px.lim - 1), y_end = py.o0 + py.lim;                       // a coordinate past the piece is evaluated at its last one
+
+    // per tile column over the piece: the footprint's first coarse column, the lane's weight and its two LDS offsets inside a tile's block
+    int xbase[SL_K], col[SL_K][2];
+    float wx1[SL_K];
+#pragma unroll
+    for (int kx = 0; kx < SL_K; kx++) {
+        const int t0 = a.s.x[px.k0 + (kx < px.K ? kx : 0)];                                     // past the last tile: the first one's, never used
+        int x0;
+        float unused;
+        rs_axis(px.o0 - t0, a.cols, a.s.tile_cols, &xbase[kx], &unused);
+        rs_axis(oxc - t0, a.cols, a.s.tile_cols, &x0, &wx1[kx]);
+        // inside the tile's staged block by construction; the clamps keep every read inside the launch's LDS whatever the arguments
+        col[kx][0] = (kx * nv + min(max(x0 - xbase[kx], 0), a.fx - 1)) * ld;
+        col[kx][1] = (kx * nv + min(max(min(x0 + 1, last_x) - xbase[kx], 0), a.fx - 1)) * ld;
+    }
+    // per tile row: the footprint's first coarse row, the four rows' weights and up bits, the LDS offsets of the three coarse rows
+    int ybase[SL_K], row[SL_K][3];
+    float wy1[SL_K][RS_ROWS];
+    unsigned up[SL_K];
+    bool cross[SL_K];
+#pragma unroll
+    for (int ky = 0; ky < SL_K; ky++) {
+        const int t0 = a.s.y[py.k0 + (ky < py.K ? ky : 0)];
+        int ya = 0;
+        float unused;
+        rs_axis(py.o0 - t0, a.rows, a.s.tile_rows, &ybase[ky], &unused);
+        up[ky] = 0;
+#pragma unroll
+        for (int r = 0; r < RS_ROWS; r++) {
+            int r0;
+            rs_axis(min(oy0 + r, y_end - 1) - t0, a.rows, a.s.tile_rows, &r0, &wy1[ky][r]);
+            if (r == 0) ya = r0;
+            up[ky] |= (unsigned)(r0 != ya) << r;      // r0 is ya or ya + 1: four rows span less than one coarse row
+        }
+        cross[ky] = __ballot(up[ky] != 0) != 0;
+#pragma unroll
+        for (int j = 0; j < 3; j++) row[ky][j] = (ky * px.K * nv + min(max(min(ya + j, last_y) - ybase[ky], 0), a.fy - 1) * a.fx) * ld;
+    }
+    const float inv = a.inv[py.K * px.K];
+    const float *tiles = a.logits + (img * (size_t)(a.s.ny * a.s.nx) + (size_t)(py.k0 * a.s.nx + px.k0)) * lmap;      // the piece's first tile
+
+    float best[RS_ROWS], ref[RS_ROWS], sum[RS_ROWS];
+    int label[RS_ROWS];
+#pragma unroll
+    for (int r = 0; r < RS_ROWS; r++) { best[r] = ref[r] = -__builtin_inff(); sum[r] = 0.0f; label[r] = 0; }
+
+    for (int c0 = 0; c0 < a.classes; c0 += a.ch) {
+        const int cn = min(a.ch, a.classes - c0), cn4 = (cn + 3) & ~3;
+#pragma unroll
+        for (int ky = 0; ky < SL_K; ky++) {
+            if (ky >= py.K) break;
+#pragma unroll
+            for (int kx = 0; kx < SL_K; kx++) {
+                if (kx >= px.K) break;
+                rs_stage<VEC>(s_rs + (ky * px.K + kx) * nv * ld, tiles + (size_t)(ky * a.s.nx + kx) * lmap, ybase[ky], xbase[kx], a.fx, nv, ld, a.cols,
+                              a.classes, last_y, last_x, c0, cn, cn4, tid);
+            }
+        }
+        __syncthreads();
+        if (active) {
+            for (int c = 0; c < cn4; c += 4) {
+                float s[RS_ROWS][4] = {}, vv[RS_ROWS][4];
+#pragma unroll
+                for (int ky = 0; ky < SL_K; ky++) {
+                    if (ky >= py.K) break;
+#pragma unroll
+                    for (int kx = 0; kx < SL_K; kx++) {
+                        if (kx >= px.K) break;
+                        EnsView e;
+#pragma unroll
+                        for (int j = 0; j < 3; j++) { e.off[j][0] = row[ky][j] + col[kx][0]; e.off[j][1] = row[ky][j] + col[kx][1]; }
+                        e.wx1 = wx1[kx];
+#pragma unroll
+                        for (int r = 0; r < RS_ROWS; r++) e.wy1[r] = wy1[ky][r];
+                        e.up = up[ky];
+                        if (cross[ky]) ens_add<true>(s_rs, e, c, ky == 0 && kx == 0, s);        // tile order: ascending iy, then ix
+                        else ens_add<false>(s_rs, e, c, ky == 0 && kx == 0, s);
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+#pragma unroll
+                    for (int r = 0; r < RS_ROWS; r++) {
+#pragma clang fp contract(off)
+                        const float t = s[r][k] * inv;                                          // the mean: one rounding
+                        if (t > best[r]) { best[r] = t; label[r] = c0 + c + k; }
+                        vv[r][k] = t;
+                    }
+                }
+                if (PROB) rs_softmax_group(vv, ref, sum);
+            }
+        }
+        __syncthreads();
+    }
+    if (!active) return;
+    // the rows of the piece end at y_end: rs_store's H
+    rs_store<PROB>(a.labels + img * map, a.score ? a.score + img * map : nullptr, PROB && a.prob ? a.prob + img * map : nullptr, y_end, a.out_cols, oy0, ox,
+                   best, label, ref, sum, a.min_prob, a.ignore_label);
+}
+
+// the four slide kernels by [prob][vec]
+typedef void (*SlideKernel)(const SlideArgs);
+const SlideKernel slide_kernels[2][2] = { { resample_slide_f32<false, false>, resample_slide_f32<true, false> },
+                                          { resample_slide_f32<false, true>, resample_slide_f32<true, true> } };
+
 }   // namespace
+
+// The plan is inside mbn_resample_slide_envelope and the pointers are non-null multiples of 4 (the caller has checked both)
+int mbn_launch_f32_resample_slide(mbn_context *, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows, int cols,
+                                  int classes, const mbn_slide *plan, int out_rows, int out_cols, const mbn_readout_prob *q)
+{
+    mbn_resample_launch_t l;
+    const int rc = mbn_resample_slide_plan(rows, cols, plan, out_rows, out_cols, &l);
+    if (rc != MBN_OK) return rc;
+    SlideArgs a = {};
+    a.labels = labels; a.score = score; a.logits = logits;
+    a.rows = rows; a.cols = cols; a.classes = classes;
+    a.out_rows = out_rows; a.out_cols = out_cols;
+    a.fy = l.fy; a.fx = l.fx; a.ch = l.ch;
+    if (q) { a.prob = q->prob; a.min_prob = q->min_prob; a.ignore_label = q->ignore_label; }
+    for (int k = 1; k < 10; k++) a.inv[k] = 1.0f / (float)k;
+    a.s = *plan;
+    int32_t kmax;
+    a.cells_y = mbn_slide_cells(plan->y, plan->ny, plan->tile_rows, a.edge_y, a.pieces_y, &kmax);
+    a.cells_x = mbn_slide_cells(plan->x, plan->nx, plan->tile_cols, a.edge_x, a.pieces_x, &kmax);
+    const bool vec = ((uintptr_t)logits % 16) == 0 && (classes % 4) == 0;
+    hipLaunchKernelGGL(slide_kernels[q != nullptr][vec], dim3((unsigned)l.tiles, (unsigned)batch), dim3(256), (size_t)l.lds_bytes, s, a);
+    return MBN_OK;
+}
 
 // The views are inside mbn_resample_ensemble_envelope and the pointers are non-null multiples of 4 (the caller has checked both)
 int mbn_launch_f32_resample_ensemble(mbn_context *, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows, int cols,

@@ -360,6 +360,9 @@ int mbn_launch_f32_resample_argmax_ragged(mbn_ragged_readout *r, hipStream_t s, 
 int mbn_launch_f32_resample_ensemble(mbn_context *ctx, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows, int cols,
                                      int classes, int in_rows, int in_cols, const mbn_view *views, int n_views, int out_rows, int out_cols,
                                      const mbn_readout_prob *q);
+// the sliding-window read-out of a grid of tiles (logits [batch][ny * nx][rows][cols][classes]) inside mbn_resample_slide_envelope; q as above
+int mbn_launch_f32_resample_slide(mbn_context *ctx, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows, int cols,
+                                  int classes, const mbn_slide *plan, int out_rows, int out_cols, const mbn_readout_prob *q);
 // score a segmentation (mbn_i32_confusion.hip): counts [classes + 1][classes + 1] uint64 += the confusion matrix of `count` labels against truth
 // (uint8 or int32). The arguments are inside mbn_confusion_envelope and the pointers checked; the ragged form scores the items of the handle's set
 int mbn_launch_i32_confusion(mbn_context *ctx, hipStream_t s, void *counts, const void *labels, const void *truth, int truth_bytes, int classes,

@@ -180,6 +180,106 @@ int mbn_resample_ensemble_plan(int rows, int cols, int in_rows, int in_cols, con
     return MBN_OK;
 }
 
+int mbn_slide_axis(int size, int tile, int stride, int32_t *pos, int32_t *n)
+{
+    if (size <= 0 || tile <= 0 || stride <= 0 || !pos || !n || stride > tile) return MBN_EINVAL;
+    if (tile > size || stride < tile - tile / 2) return MBN_EUNSUPPORTED;                           /* ceil(tile / 2) without overflow */
+    const int64_t count = (size > tile ? ((int64_t)size - tile + stride - 1) / stride : 0) + 1;
+    if (count > MBN_SLIDE_MAX_AXIS) return MBN_EUNSUPPORTED;
+    for (int i = 0; i < (int)count; i++) {
+        const int64_t p = (int64_t)i * stride;
+        pos[i] = (int32_t)(p < size - tile ? p : size - tile);
+    }
+    *n = (int32_t)count;
+    return MBN_OK;
+}
+
+int mbn_slide_plan(int in_rows, int in_cols, int tile_rows, int tile_cols, int stride_rows, int stride_cols, mbn_slide *s)
+{
+    if (!s) return MBN_EINVAL;
+    mbn_slide t;
+    memset(&t, 0, sizeof t);
+    /* an MBN_EINVAL of either axis goes before an MBN_EUNSUPPORTED of the other, as in the read-out's envelope */
+    const int ry = mbn_slide_axis(in_rows, tile_rows, stride_rows, t.y, &t.ny), rx = mbn_slide_axis(in_cols, tile_cols, stride_cols, t.x, &t.nx);
+    if (ry == MBN_EINVAL || rx == MBN_EINVAL) return MBN_EINVAL;
+    if (ry != MBN_OK) return ry;
+    if (rx != MBN_OK) return rx;
+    t.tile_rows = tile_rows; t.tile_cols = tile_cols;
+    *s = t;
+    return MBN_OK;
+}
+
+/* one axis of a plan against the rules of include/mbn.h, "segment by sliding window" (pos has MBN_SLIDE_MAX_AXIS entries) */
+static int slide_axis_check(const int32_t *pos, int n, int tile, int size)
+{
+    if (n < 1 || n > MBN_SLIDE_MAX_AXIS || tile <= 0 || size <= 0) return MBN_EINVAL;
+    if (pos[0] != 0 || (int64_t)pos[n - 1] + tile != size) return MBN_EINVAL;
+    for (int i = 0; i + 1 < n; i++)
+        if (pos[i + 1] <= pos[i] || (int64_t)pos[i + 1] > (int64_t)pos[i] + tile) return MBN_EINVAL;
+    for (int i = n; i < MBN_SLIDE_MAX_AXIS; i++)
+        if (pos[i] != 0) return MBN_EINVAL;
+    for (int i = 0; i + 3 < n; i++)
+        if ((int64_t)pos[i + 3] < (int64_t)pos[i] + tile) return MBN_EUNSUPPORTED;
+    return MBN_OK;
+}
+
+int mbn_slide_check(const mbn_slide *s, int out_rows, int out_cols)
+{
+    if (!s || out_rows <= 0 || out_cols <= 0) return MBN_EINVAL;
+    const int ry = slide_axis_check(s->y, s->ny, s->tile_rows, out_rows), rx = slide_axis_check(s->x, s->nx, s->tile_cols, out_cols);
+    if (ry == MBN_EINVAL || rx == MBN_EINVAL) return MBN_EINVAL;                                  /* of either axis, before an MBN_EUNSUPPORTED of the other */
+    return ry != MBN_OK ? ry : rx;
+}
+
+int mbn_resample_slide_envelope(int batch, int rows, int cols, int classes, const mbn_slide *s, int out_rows, int out_cols)
+{
+    if (batch <= 0 || rows <= 0 || cols <= 0 || classes <= 0) return MBN_EINVAL;
+    const int rc = mbn_slide_check(s, out_rows, out_cols);
+    if (rc != MBN_OK) return rc;
+    if (out_rows > MBN_RESAMPLE_MAX_OUT || out_cols > MBN_RESAMPLE_MAX_OUT) return MBN_EUNSUPPORTED;
+    if (4.0 * out_rows * out_cols >= 2147483648.0) return MBN_EUNSUPPORTED;                                     /* an image's labels / scores */
+    /* every tile is one read-out to tile_rows x tile_cols: its ratio and bytes; the logits hold batch * ny * nx maps (64-bit: the product may pass int) */
+    const int64_t maps = (int64_t)batch * s->ny * s->nx;
+    return mbn_resample_argmax_envelope(maps > MBN_DENSE_MAX_BATCH ? MBN_DENSE_MAX_BATCH + 1 : (int)maps, rows, cols, classes, s->tile_rows, s->tile_cols);
+}
+
+int mbn_slide_cells(const int32_t *pos, int n, int tile, int32_t edge[MBN_SLIDE_MAX_CELLS + 1], int32_t pieces[MBN_SLIDE_MAX_CELLS + 1], int32_t *kmax)
+{
+    /* the starts and the ends are each ascending: merge them, equal values once */
+    int cells = -1, a = 0, b = 0;
+    while (a < n || b < n) {
+        const int32_t v = a < n && pos[a] <= pos[b] + tile ? pos[a++] : pos[b++] + tile;              /* b <= a: pos[b] is read only while b < n */
+        if (cells < 0 || edge[cells] != v) edge[++cells] = v;
+    }
+    *kmax = 0;
+    pieces[0] = 0;
+    for (int c = 0; c < cells; c++) {
+        int k = 0;
+        for (int i = 0; i < n; i++) k += pos[i] <= edge[c] && edge[c] < pos[i] + tile;
+        if (k > *kmax) *kmax = k;
+        pieces[c + 1] = pieces[c] + (edge[c + 1] - edge[c] + MBN_RESAMPLE_TILE - 1) / MBN_RESAMPLE_TILE;
+    }
+    for (int c = cells + 1; c <= MBN_SLIDE_MAX_CELLS; c++) edge[c] = pieces[c] = 0;
+    return cells;
+}
+
+int mbn_resample_slide_plan(int rows, int cols, const mbn_slide *s, int out_rows, int out_cols, mbn_resample_launch_t *l)
+{
+    if (!s || !l) return MBN_EINVAL;
+    int32_t edge[MBN_SLIDE_MAX_CELLS + 1], py[MBN_SLIDE_MAX_CELLS + 1], px[MBN_SLIDE_MAX_CELLS + 1], ky, kx;
+    const int cy = mbn_slide_cells(s->y, s->ny, s->tile_rows, edge, py, &ky), cx = mbn_slide_cells(s->x, s->nx, s->tile_cols, edge, px, &kx);
+    const mbn_resample_launch_t zero = { 0, 0, 0, 0, 0, 0 };
+    *l = zero;
+    l->fy = MBN_RESAMPLE_FOOT(rows, s->tile_rows);
+    l->fx = MBN_RESAMPLE_FOOT(cols, s->tile_cols);
+    const int nv = ky * kx * l->fy * l->fx;
+    l->ch = MBN_RESAMPLE_SLIDE_CH(nv);
+    l->lds_bytes = nv * (l->ch + 4) * 4;
+    l->tiles = py[cy] * px[cx];
+    l->span = (int64_t)out_rows * out_cols;
+    return MBN_OK;
+}
+
 static int cmp_i64_pair(const void *a, const void *b)
 {
     const int64_t x = *(const int64_t *)a, y = *(const int64_t *)b;

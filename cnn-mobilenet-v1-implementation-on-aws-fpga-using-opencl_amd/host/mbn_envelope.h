@@ -118,6 +118,28 @@ int mbn_resample_ensemble_envelope(int batch, int rows, int cols, int classes, i
                                    int out_rows, int out_cols);
 int mbn_resample_ensemble_plan(int rows, int cols, int in_rows, int in_cols, const mbn_view *views, int n_views, int out_rows, int out_cols,
                                mbn_resample_launch_t *l);
+/* mbn_resample_slide_f32: the read-out of a grid of tiles (include/mbn.h, "segment by sliding window"; logits [batch][ny * nx][rows][cols][classes]).
+ * The envelope: MBN_EINVAL for a non-positive size, a NULL plan or a plan breaking the MBN_EINVAL rules of include/mbn.h for out_rows x out_cols
+ * (either axis); else MBN_EUNSUPPORTED for more than three tiles over a coordinate, an output side above MBN_RESAMPLE_MAX_OUT, an output map of
+ * 2^31 bytes or more, or a tile outside mbn_resample_argmax_envelope taken with batch * ny * nx maps resampled to tile_rows x tile_cols (the
+ * ratio, the logits' bytes, the batch).
+ * mbn_slide_cells: the tile edges cut an axis into cells of constant coverage, at most MBN_SLIDE_MAX_CELLS. edge[0 .. cells] are the cells'
+ * borders (edge[0] = 0, edge[cells] = the axis' size), pieces[c] the 32-output pieces in front of cell c (pieces[cells]: of the axis), *kmax the
+ * most tiles over a coordinate; the entries past `cells` are 0. Returns the number of cells; the axis is one the envelope accepts.
+ * The plan writes *l for the whole grid: fy, fx = MBN_RESAMPLE_FOOT of a tile, which holds for ANY 32 consecutive outputs, so also for a piece
+ * that starts at a cell border; the kernel stages the footprints of all tiles over a piece per class chunk, tile (ky, kx) of the piece at
+ * (ky * Kx + kx) * fy * fx vectors, so ch = MBN_RESAMPLE_SLIDE_CH(K * fy * fx) with K = kmax_y * kmax_x of the plan: the largest of
+ * 128 / 64 / 32 / 16 / 8 whose staged block stays at or under 64 KB (every plan inside the envelope fits: 9 x 10 x 10 vectors x 12 floats =
+ * 43 200 bytes). lds_bytes = K * fy * fx * (ch + 4) * 4; tiles = pieces along y x pieces along x = grid.x; span = out_rows * out_cols.
+ * MBN_EINVAL for a NULL plan / l; the plan is one the envelope accepts */
+#define MBN_SLIDE_MAX_CELLS (2 * MBN_SLIDE_MAX_AXIS - 1)
+#define MBN_RESAMPLE_SLIDE_CH(nv)                                                                                                  \
+    ((nv) * 132 * 4 <= MBN_RESAMPLE_ENSEMBLE_LDS ? 128 : (nv) * 68 * 4 <= MBN_RESAMPLE_ENSEMBLE_LDS ? 64 : (nv) * 36 * 4 <= MBN_RESAMPLE_ENSEMBLE_LDS ? 32 \
+     : (nv) * 20 * 4 <= MBN_RESAMPLE_ENSEMBLE_LDS ? 16 : 8)
+int mbn_slide_check(const mbn_slide *s, int out_rows, int out_cols);      /* the plan's rules alone, for out_rows x out_cols */
+int mbn_resample_slide_envelope(int batch, int rows, int cols, int classes, const mbn_slide *s, int out_rows, int out_cols);
+int mbn_slide_cells(const int32_t *pos, int n, int tile, int32_t edge[MBN_SLIDE_MAX_CELLS + 1], int32_t pieces[MBN_SLIDE_MAX_CELLS + 1], int32_t *kmax);
+int mbn_resample_slide_plan(int rows, int cols, const mbn_slide *s, int out_rows, int out_cols, mbn_resample_launch_t *l);
 /* score a segmentation (mbn_i32_confusion.hip, host/mbn_score.c; declared in mbn.h too). mbn_confusion_envelope: MBN_EINVAL for classes < 1,
  * count < 1 or truth_bytes other than 1 / 4, else MBN_EUNSUPPORTED for classes > MBN_CONFUSION_MAX_CLASSES or count > MBN_CONFUSION_MAX_COUNT.
  * mbn_confusion_form: MBN_CONFUSION_FORM_LDS while the workgroup's table of (classes + 1)^2 32-bit bins fits MBN_CONFUSION_LDS bytes of LDS,

@@ -1355,6 +1355,89 @@ int mbn_net_segment_views_fit(mbn_net *net, const void *src_u8, int batch, int i
                                                          ignore_label, NULL), batch, in_rows, in_cols);
 }
 
+/* the tiles of a plan the caller has checked: batch * ny * nx <= max_batch items on the net's stretch handle, one launch */
+static int resize_tiles(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, const mbn_slide *s, void **staged)
+{
+    const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols;
+    if (!net->ragged_items) {
+        net->ragged_items = malloc((size_t)net->max_batch * sizeof(mbn_resize_item));
+        if (!net->ragged_items) return MBN_ENOMEM;
+    }
+    int n = 0;
+    for (int b = 0; b < batch; b++)
+        for (int iy = 0; iy < s->ny; iy++)
+            for (int ix = 0; ix < s->nx; ix++) {
+                mbn_resize_item *it = &net->ragged_items[n++];          /* image b * ny * nx + iy * nx + ix of the staging buffer */
+                it->src_offset = (int64_t)b * in_rows * in_cols * 3;
+                it->rows = in_rows;
+                it->cols = in_cols;
+                it->box[0] = (float)s->x[ix]; it->box[1] = (float)s->y[iy];
+                it->box[2] = (float)(s->x[ix] + s->tile_cols); it->box[3] = (float)(s->y[iy] + s->tile_rows);
+            }
+    if (!net->ragged || net->ragged_filter != net->resize_filter || net->ragged_pad) {
+        mbn_ragged_resizer *r = NULL;                         /* HAMMING / LANCZOS: MBN_EUNSUPPORTED, and the resizer of the previous filter stays */
+        const int rc = mbn_ragged_resizer_create_filter(net->ctx, net->resize_filter, net->max_batch, rows, cols, &r);
+        if (rc != MBN_OK) return rc;
+        if (net->ragged) mbn_ragged_resizer_destroy(net->ragged);       /* waits for its last launch */
+        net->ragged = r;
+        net->ragged_filter = net->resize_filter;
+        net->ragged_pad = 0;
+    }
+    if (!net->resize_buf) {
+        const int rc = mbn_alloc(net->ctx, (size_t)net->max_batch * rows * cols * 3, &net->resize_buf);
+        if (rc != MBN_OK) { net->resize_buf = NULL; return rc; }
+    }
+    int rc = mbn_ragged_resizer_set(net->ragged, net->ragged_items, n, NULL);
+    if (rc == MBN_OK) rc = mbn_resize_ragged_u8(net->ragged, net->resize_buf, src_u8, NULL);
+    if (rc == MBN_OK) *staged = net->resize_buf;
+    return rc;
+}
+
+/* what both slide calls check first: the plan against the source size, its tiles against max_batch */
+static int slide_status(const mbn_net *net, int batch, int in_rows, int in_cols, const mbn_slide *s)
+{
+    if (batch <= 0 || in_rows <= 0 || in_cols <= 0) return MBN_EINVAL;
+    const int rc = mbn_slide_check(s, in_rows, in_cols);
+    if (rc != MBN_OK) return rc;
+    return (int64_t)batch * s->ny * s->nx > net->max_batch ? MBN_EINVAL : MBN_OK;
+}
+
+int mbn_net_resize_tiles(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, const mbn_slide *s, void **staged)
+{
+    if (!net || !src_u8 || !s || !staged) return MBN_EINVAL;
+    *staged = NULL;
+    const int rc = slide_status(net, batch, in_rows, in_cols, s);
+    if (rc != MBN_OK) return rc;
+    return resize_tiles(net, src_u8, batch, in_rows, in_cols, s, staged);
+}
+
+int mbn_net_segment_slide(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int tile_rows, int tile_cols, int stride_rows,
+                          int stride_cols, void *labels_i32, void *prob_f32, void *score_f32, float min_prob, int ignore_label)
+{
+    if (!net || !src_u8 || !labels_i32) return MBN_EINVAL;
+    if (!net->input_u8) return MBN_EINVAL;                    /* the staged tiles are uint8: the net must take them as such */
+    if (((uintptr_t)labels_i32 | (uintptr_t)prob_f32 | (uintptr_t)score_f32) % 4) return MBN_EINVAL;
+    /* the read-out's own rule: no prob map and no threshold is the argmax form */
+    if ((prob_f32 || !(min_prob == 0.0f)) && mbn_softmax_readout_check(prob_f32 != NULL, min_prob) != MBN_OK) return MBN_EINVAL;
+    if (batch <= 0) return MBN_EINVAL;
+    mbn_slide s;
+    int rc = mbn_slide_plan(in_rows, in_cols, tile_rows, tile_cols, stride_rows, stride_cols, &s);
+    if (rc == MBN_OK) rc = slide_status(net, batch, in_rows, in_cols, &s);
+    if (rc != MBN_OK) return rc;
+    const mbn_layer_desc *feat, *fc;
+    rc = dense_layers(net, &feat, &fc);
+    if (rc != MBN_OK) return rc;
+    rc = mbn_resample_slide_envelope(batch, feat->out_rows, feat->out_cols, fc->out_ch, &s, in_rows, in_cols);
+    if (rc != MBN_OK) return rc;
+    void *images = NULL;
+    rc = resize_tiles(net, src_u8, batch, in_rows, in_cols, &s, &images);
+    if (rc == MBN_OK) rc = dense_forward(net, feat, fc, images, batch * s.ny * s.nx);
+    if (rc != MBN_OK) return rc;
+    return scored_uniform(net, mbn_resample_slide_f32(net->ctx, labels_i32, prob_f32, score_f32, net->dense_logits, batch, feat->out_rows,
+                                                      feat->out_cols, fc->out_ch, &s, in_rows, in_cols, min_prob, ignore_label, NULL), batch, in_rows,
+                          in_cols);
+}
+
 int mbn_net_segment_score(mbn_net *net, const void *labels_i32, const void *truth, int truth_bytes, void *counts_u64)
 {
     if (!net || net->score_kind == SCORE_NONE) return MBN_EINVAL;

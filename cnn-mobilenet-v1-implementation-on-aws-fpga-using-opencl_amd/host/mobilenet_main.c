@@ -26,6 +26,11 @@
  *   is shown to the network at every scale (0 < S <= 1: the letterbox shrunk about the centre of the input), with --tta-flip also mirrored, and ONE
  *   read-out averages the views' logits. The views are (S1, plain), (S1, mirrored), (S2, plain), ... in that order, 8 at most (else usage status 2);
  *   --segment-confidence, --min-confidence and --ignore-label work as without it
+ *   --slide TH[xTW] [--slide-stride SH[xSW]] (with ONE --ppm and --segment-source; rows x columns): sliding-window segmentation,
+ *   mbn_net_segment_slide: overlapping TH x TW crops of the image, each stretched to the network's input, and ONE read-out that averages the crops'
+ *   logits where they overlap. The default stride is (2 * tile + 2) / 3 per axis. The fit is the stretch: with --fit pad or --fit crop, or with
+ *   --tta-scales / --tta-flip, usage status 2, as for a plan mbn_slide_plan refuses. --segment-confidence, --min-confidence, --ignore-label,
+ *   --truth, --regions, --panoptic and --boundary-* work as without it
  *   --truth F.pgm (several times: the n-th pairs with the n-th --ppm, as many as there are; needs --segment-source): the ground truth of that image, a P5
  *   of its size (another size: error exit). maxval <= 255: one byte per pixel, uint8 truth; larger: two big-endian bytes, the format --segment-source
  *   itself writes, int32 truth, so a label map this tool wrote can be fed back. The label maps are scored on the device (mbn_net_segment_score: a value
@@ -679,11 +684,12 @@ static int write_confidence_map(const char *path, const float *prob, int rows, i
  * mbn_net_segment_prob_images_fit: image 0's probability map as an 8-bit P5, byte = floor(prob * 255 + 0.5), and the label map with the pixels
  * below min_conf replaced by `ignore`. path may then be NULL (no label map asked for).
  * n_views > 0 (--tta-scales; one file, --fit pad): mbn_net_segment_views_fit over the views (scales[k], mirrors[k]) instead, either read-out.
+ * slide (--slide; one file): mbn_net_segment_slide with the tile slide[0] x slide[1] at the stride slide[2] x slide[3] instead, either read-out.
  * ro->on (--regions): the regions of every map are printed first; with --min-area > 1 the cleaned maps take the place of the maps from there on.
  * n_truth > 0 (--truth, one per image): the maps are scored against them on the device before anything is written */
 static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int n_ppm, const char *path, int classes, int fit, const char *conf_path,
-                          float min_conf, int ignore, const float *scales, const int32_t *mirrors, int n_views, const char **truths, int n_truth,
-                          const region_opts *ro, const boundary_opts *bo, const panoptic_opts *po)
+                          float min_conf, int ignore, const float *scales, const int32_t *mirrors, int n_views, const int *slide, const char **truths,
+                          int n_truth, const region_opts *ro, const boundary_opts *bo, const panoptic_opts *po)
 {
     int64_t *offs = malloc(sizeof(int64_t) * (size_t)n_ppm), *dst = malloc(sizeof(int64_t) * (size_t)n_ppm);
     int32_t *hs = malloc(sizeof(int32_t) * (size_t)n_ppm), *ws = malloc(sizeof(int32_t) * (size_t)n_ppm);
@@ -711,7 +717,12 @@ static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int
     CHECK(mbn_alloc(ctx, sizeof(int) * pixels, &d_labels));
     CHECK(mbn_upload(ctx, d_src, all, total));
     if (!(min_conf > 0.0f)) ignore = -1;                        /* --min-confidence 0 replaces nothing: the argmax read-out, unless a map is asked for */
-    if (n_views > 0) {
+    if (slide) {
+        if (conf_path) CHECK(mbn_alloc(ctx, sizeof(float) * pixels, &d_prob));
+        CHECK(mbn_net_segment_slide(net, d_src, 1, hs[0], ws[0], slide[0], slide[1], slide[2], slide[3], d_labels, d_prob, NULL,
+                                    ignore >= 0 ? min_conf : 0.0f, ignore >= 0 ? ignore : 0));
+        printf("segment: tiles of %d x %d at a stride of %d x %d (rows x columns) averaged in one read-out\n", slide[0], slide[1], slide[2], slide[3]);
+    } else if (n_views > 0) {
         if (conf_path) CHECK(mbn_alloc(ctx, sizeof(float) * pixels, &d_prob));
         CHECK(mbn_net_segment_views_fit(net, d_src, 1, hs[0], ws[0], scales, mirrors, n_views, d_labels, d_prob, NULL, ignore >= 0 ? min_conf : 0.0f,
                                         ignore >= 0 ? ignore : 0));
@@ -786,6 +797,23 @@ static int pad_color_of(const char *s, int rgb[3])
     return rgb[0] >= 0 && rgb[0] <= 255 && rgb[1] >= 0 && rgb[1] <= 255 && rgb[2] >= 0 && rgb[2] <= 255;
 }
 
+/* --slide TH[xTW] / --slide-stride SH[xSW]: rows, then columns (one number: both); positive integers and nothing else */
+static int rows_cols_of(const char *s, int *r, int *c)
+{
+    char *end = NULL;
+    const long a = strtol(s, &end, 10);
+    long b = a;
+    if (end == s) return 0;
+    if (*end == 'x' || *end == 'X') {
+        const char *t = end + 1;
+        b = strtol(t, &end, 10);
+        if (end == t) return 0;
+    }
+    if (*end || a < 1 || b < 1 || a > PPM_MAX_SIDE || b > PPM_MAX_SIDE) return 0;
+    *r = (int)a; *c = (int)b;
+    return 1;
+}
+
 /* --tta-scales S1,S2,...: up to MBN_ENSEMBLE_MAX_VIEWS numbers in (0, 1] and nothing else; their count, or 0 for anything else */
 static int tta_scales_of(const char *s, float scales[MBN_ENSEMBLE_MAX_VIEWS])
 {
@@ -824,7 +852,8 @@ int main(int argc, char **argv)
     int pad_rgb[3] = { 0, 0, 0 }, src_h0 = 0, src_w0 = 0;              /* src_h0 x src_w0: image 0 as it was resized (0: it was not) */
     float crop_fraction = 1.0f, min_conf = 0.0f;
     int have_min_conf = 0, have_ignore = 0, ignore_label = -1;
-    const char *tta = NULL;
+    const char *tta = NULL, *slide_arg = NULL, *slide_stride_arg = NULL;
+    int fit_given = 0, slide[4] = { 0, 0, 0, 0 }, slide_tiles = 0;      /* slide: tile rows, tile columns, stride rows, stride columns */
     region_opts regions = { 0, 4, 1, 256 };
     int region_flags = 0;                                       /* --connectivity, --min-area or --max-regions seen */
     int max_regions_flag = 0;                                   /* --max-regions seen: it belongs to --regions alone */
@@ -858,6 +887,8 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--ignore-label") && i + 1 < argc) { ignore_label = atoi(argv[++i]); have_ignore = 1; }
         else if (!strcmp(argv[i], "--tta-scales") && i + 1 < argc) tta = argv[++i];
         else if (!strcmp(argv[i], "--tta-flip")) tta_flip = 1;
+        else if (!strcmp(argv[i], "--slide") && i + 1 < argc) slide_arg = argv[++i];
+        else if (!strcmp(argv[i], "--slide-stride") && i + 1 < argc) slide_stride_arg = argv[++i];
         else if (!strcmp(argv[i], "--truth") && i + 1 < argc) truths[n_truth++] = argv[++i];
         else if (!strcmp(argv[i], "--regions")) regions.on = 1;
         else if (!strcmp(argv[i], "--panoptic")) panoptic.on = 1;
@@ -868,7 +899,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--connectivity") && i + 1 < argc) { regions.connectivity = atoi(argv[++i]); region_flags = 1; }
         else if (!strcmp(argv[i], "--min-area") && i + 1 < argc) { regions.min_area = atoi(argv[++i]); region_flags = 1; }
         else if (!strcmp(argv[i], "--max-regions") && i + 1 < argc) { regions.max_regions = atoi(argv[++i]); region_flags = max_regions_flag = 1; }
-        else if (!strcmp(argv[i], "--fit") && i + 1 < argc && fit_of(argv[i + 1]) >= 0) fit = fit_of(argv[++i]);
+        else if (!strcmp(argv[i], "--fit") && i + 1 < argc && fit_of(argv[i + 1]) >= 0) { fit = fit_of(argv[++i]); fit_given = 1; }
         else if (!strcmp(argv[i], "--pad-color") && i + 1 < argc && pad_color_of(argv[i + 1], pad_rgb)) i++;
         else if (!strcmp(argv[i], "--crop-fraction") && i + 1 < argc) crop_fraction = (float)atof(argv[++i]);
         else if (!strcmp(argv[i], "--filter") && i + 1 < argc && filter_of(argv[i + 1]) >= 0) filter = filter_of(argv[++i]);
@@ -884,7 +915,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--literal")) literal = 1;
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
-            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]] [--truth F.pgm ...] [--regions [--connectivity 4|8] [--min-area N] [--max-regions M]] [--boundary-ratio R | --boundary-d N [--boundary-edge 0|1] [--boundary-map OUT.pgm]] [--panoptic [--connectivity 4|8] [--min-area N]]] [--segment-confidence OUT.pgm] "
+            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]] [--slide TH[xTW] [--slide-stride SH[xSW]]] [--truth F.pgm ...] [--regions [--connectivity 4|8] [--min-area N] [--max-regions M]] [--boundary-ratio R | --boundary-d N [--boundary-edge 0|1] [--boundary-map OUT.pgm]] [--panoptic [--connectivity 4|8] [--min-area N]]] [--segment-confidence OUT.pgm] "
                             "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n", argv[0]);
             return 2;
         }
@@ -897,6 +928,32 @@ int main(int argc, char **argv)
         return 2;
     }
     if (n_ppm == 1) ppm = ppms[0];
+    if (slide_arg || slide_stride_arg) {
+        /* sliding window: a tile is a crop of the source stretched to the input, so the fit is the stretch; the letterbox, the crop and the views
+         * have no part in it */
+        if (!slide_arg || !segment_src || n_ppm != 1 || (fit_given && fit != MBN_FIT_STRETCH) || tta || tta_flip ||
+            !rows_cols_of(slide_arg, &slide[0], &slide[1]) || (slide_stride_arg && !rows_cols_of(slide_stride_arg, &slide[2], &slide[3]))) {
+            fprintf(stderr, "--slide TH[xTW] [--slide-stride SH[xSW]] (rows x columns; the default stride is (2 * tile + 2) / 3) needs one --ppm and "
+                            "--segment-source and goes with --fit stretch alone, not with --tta-scales / --tta-flip\n");
+            return 2;
+        }
+        if (!slide_stride_arg) { slide[2] = (2 * slide[0] + 2) / 3; slide[3] = (2 * slide[1] + 2) / 3; }
+        fit = MBN_FIT_STRETCH;
+        int sw = 0, sh = 0;
+        mbn_slide plan;
+        if (ppm_size(ppm, &sw, &sh) != MBN_OK || sw > PPM_MAX_SIDE || sh > PPM_MAX_SIDE) {
+            fprintf(stderr, "%s is not a readable P6 image of at most %d x %d pixels\n", ppm, PPM_MAX_SIDE, PPM_MAX_SIDE);
+            return 2;
+        }
+        const int rc = mbn_slide_plan(sh, sw, slide[0], slide[1], slide[2], slide[3], &plan);
+        if (rc != MBN_OK) {
+            fprintf(stderr, "--slide %dx%d --slide-stride %dx%d on a %d x %d image (rows x columns): %s; a tile is at most the image, a stride between "
+                            "half a tile and a tile, and an axis takes at most %d tiles\n", slide[0], slide[1], slide[2], slide[3], sh, sw,
+                    mbn_strerror(rc), MBN_SLIDE_MAX_AXIS);
+            return 2;
+        }
+        slide_tiles = plan.ny * plan.nx;                        /* the tiles of the image are one batch of the net */
+    }
     if (segment_src && (n_ppm < 1 || (fit != MBN_FIT_STRETCH && fit != MBN_FIT_PAD))) {
         fprintf(stderr, "--segment-source needs --ppm and --fit stretch or --fit pad\n");
         return 2;
@@ -1004,7 +1061,8 @@ int main(int argc, char **argv)
     CHECK(mbn_weights_from_h5_os(h5, alpha, rows, cols, out_stride, &w));
     if (have_seed) remove(tmp);
     mbn_net *net = NULL;
-    CHECK(mbn_net_create(ctx, &w, batch > n_views ? batch : n_views, &net));      /* the views of one image are one batch of the net */
+    const int net_batch = batch > n_views ? batch : n_views;                      /* the views of one image are one batch of the net, and so are its tiles */
+    CHECK(mbn_net_create(ctx, &w, net_batch > slide_tiles ? net_batch : slide_tiles, &net));
     CHECK(mbn_net_set_resize_filter(net, filter));
     CHECK(mbn_net_set_pad_color(net, pad_rgb[0], pad_rgb[1], pad_rgb[2]));
     const int classes = w.plan.classes;
@@ -1110,7 +1168,7 @@ int main(int argc, char **argv)
     }
     if (segment_src || segment_conf) {
         const int bad = segment_source(ctx, net, ppms, n_ppm, segment_src, classes, fit, segment_conf, min_conf, have_ignore ? ignore_label : -1,
-                                       view_scales, view_mirrors, n_views, truths, n_truth, &regions, &boundary, &panoptic);
+                                       view_scales, view_mirrors, n_views, slide_tiles ? slide : NULL, truths, n_truth, &regions, &boundary, &panoptic);
         if (bad) return bad;
     }
     mbn_net_destroy(net);

@@ -523,6 +523,48 @@ typedef struct mbn_view { int32_t x, y, iw, ih; int32_t mirror; int32_t reserved
 int mbn_resample_ensemble_f32(mbn_context *ctx, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, int batch, int rows, int cols,
                               int classes, int in_rows, int in_cols, const mbn_view *views, int n_views, int out_rows, int out_cols, float min_prob,
                               int ignore_label, void *stream);
+/* Segment by sliding window: ONE read-out of a grid of overlapping TILES of the same images, their interpolated logits averaged per class and pixel
+ * where tiles overlap, in front of the compare. A tile is a tile_rows x tile_cols crop of the source image that the network saw
+ * as one input of its own; the grid covers the image, so every source pixel has the logits of a crop at the crop's own scale instead of one
+ * coarse vector of the whole image squeezed into the network's input. The tensors [out_rows][out_cols][classes] are never formed.
+ * The plan. mbn_slide_axis places the tiles of one axis: regular steps, the last tile moved back flush with the far edge. Normative:
+ *     n = (size > tile ? ceil((size - tile) / stride) : 0) + 1;      pos[i] = min(i * stride, size - tile)
+ * MBN_EINVAL: a non-positive argument, a NULL pointer or stride > tile (gaps). MBN_EUNSUPPORTED: tile > size (that image belongs to the letterbox),
+ * stride < ceil(tile / 2) (more than three tiles over a coordinate) or n > MBN_SLIDE_MAX_AXIS. Nothing is written on a refusal. The positions are
+ * strictly ascending from 0 to size - tile without a gap, the tiles over a coordinate are a contiguous index range of at most three, and the tile
+ * edges cut the axis into at most 2n - 1 cells of constant coverage. mbn_slide_plan runs both axes and fills an mbn_slide (unused y[] / x[] are 0);
+ * it writes nothing on a refusal.
+ * A hand-made mbn_slide is legal. For an output of out_rows x out_cols the read-out checks, for y against tile_rows / out_rows and for x against
+ * tile_cols / out_cols: MBN_EINVAL unless ny (nx) is in 1..MBN_SLIDE_MAX_AXIS, the tile side is positive, y[0] = 0 and y[ny - 1] = out_rows -
+ * tile_rows, the positions are strictly ascending, y[i + 1] <= y[i] + tile_rows (no gap) and the unused entries are 0; then MBN_EUNSUPPORTED unless
+ * y[i + 3] >= y[i] + tile_rows (at most three tiles over a coordinate).
+ * The read-out. logits is IMAGE-MAJOR: fp32 [batch][ny * nx][rows][cols][classes], tile t = iy * nx + ix, what one mbn_net_forward_dense of the
+ * staged tiles gives; labels_i32, prob_f32 and score_f32 are [batch][out_rows][out_cols]. Normative (tests/dense_slide_ref.py reproduces it bit
+ * for bit in numpy):
+ *   Interpolants. Tile (iy, ix) covers output rows [y[iy], y[iy] + tile_rows) and columns [x[ix], x[ix] + tile_cols). At a pixel (oy, ox) it covers,
+ *     its v_c are exactly the interpolants of mbn_resample_argmax_f32 for that tile's map resampled to tile_rows x tile_cols, at
+ *     (oy - y[iy], ox - x[ix]): the same index and weight rule, horizontal first, every product and sum rounded on its own, a zero weight still
+ *     multiplies. Each tile is an image of its own: the rule's clamps act at the tile's edge.
+ *   Sum. Over the covering tiles in ascending iy, then ascending ix: s_c = v_c of the first, then s_c = s_c + v_c for each further tile, one fp32
+ *     rounding each.
+ *   Mean. t_c = s_c * inv, inv = 1.0f / (float)count, count the number of covering tiles (1, 2, 3, 4, 6 or 9). One rounding.
+ *   Label, score, prob, min_prob, ignore_label. Those of mbn_resample_ensemble_f32 applied to t_c: the argmax in ascending class order with a strict
+ *     compare, the score the winning t; prob = 1 / sum_c e(t_c) within (classes + 200) * 2^-24 relative of the float64 evaluation on the fp32 t_c,
+ *     exactly 0 when best is not finite; the stored label is ignore_label iff the stored prob < min_prob.
+ * prob_f32 = NULL with min_prob = 0 is the argmax form: no exponential is evaluated. score_f32 may be NULL. Where count = 1 the labels and score
+ * bits are those of mbn_resample_argmax_f32 of that tile to tile_rows x tile_cols, so a plan of one tile is that call bit for bit; where count
+ * is 2 or 4 the product by inv is exact.
+ * MBN_EINVAL: NULL labels / logits / s, a pointer off 4 bytes, a non-positive size, a plan breaking the MBN_EINVAL rules above, min_prob outside
+ * [0, 1] or NaN, or an undersized tracked buffer (mbn_alloc's bounds rule; the logits span batch * ny * nx maps). MBN_EUNSUPPORTED: more than three
+ * tiles over a coordinate, tile_rows < 4 * rows or tile_cols < 4 * cols, a side above 16384, or the byte and batch limits of
+ * mbn_resample_argmax_f32 (taken with batch * ny * nx maps). Nothing is launched on a refusal. ONE kernel, the plan by value in its arguments, no
+ * device allocation and no blocking call: it may be captured as one kernel node. */
+#define MBN_SLIDE_MAX_AXIS 16
+typedef struct mbn_slide { int32_t tile_rows, tile_cols, ny, nx; int32_t y[MBN_SLIDE_MAX_AXIS], x[MBN_SLIDE_MAX_AXIS]; } mbn_slide;  /* 144 bytes; unused y[] / x[] are 0 */
+int mbn_slide_axis(int size, int tile, int stride, int32_t *pos, int32_t *n);
+int mbn_slide_plan(int in_rows, int in_cols, int tile_rows, int tile_cols, int stride_rows, int stride_cols, mbn_slide *s);
+int mbn_resample_slide_f32(mbn_context *ctx, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, int batch, int rows, int cols,
+                           int classes, const mbn_slide *s, int out_rows, int out_cols, float min_prob, int ignore_label, void *stream);
 /* Score a segmentation: the confusion matrix of the label maps the read-outs above write against a ground truth, accumulated on the device, and
  * the standard metrics of such a matrix on the host. The dense counterpart of mbn_softmax_topk_f32.
  * Normative (tests/confusion_ref.py reproduces it in numpy; the arithmetic is integer, so every result is exact and does not depend on the order
@@ -1320,8 +1362,26 @@ int  mbn_net_resize_views(mbn_net *net, const void *src_u8, int batch, int in_ro
                           int n_views, void **staged);
 int  mbn_net_segment_views_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, const float *scales, const int32_t *mirrors,
                                int n_views, void *labels_i32, void *prob_f32, void *score_f32, float min_prob, int ignore_label);
+/* Segment by sliding window (mbn_resample_slide_f32 above): the source image is cut into overlapping tile_rows x tile_cols crops, each resized to the
+ * plan's rows x cols and run as an image of its own; batch * ny * nx <= max_batch.
+ *   mbn_net_resize_tiles   src_u8 [batch][in_rows][in_cols][3] uint8 (device) -> the net's staging buffer, image-major: image b's tile (iy, ix) is
+ *                          image b * ny * nx + iy * nx + ix of it; *staged receives the buffer. ONE set on the net's own ragged resizer (the
+ *                          stretch handle: a tile is a crop, not a letterbox) and ONE mbn_resize_ragged_u8 launch: the item of that tile is
+ *                          { b * in_rows * in_cols * 3, in_rows, in_cols, box = (x, y, x + tile_cols, y + tile_rows) }. The net's filter; the ragged
+ *                          path's MBN_EUNSUPPORTED for HAMMING / LANCZOS is passed on. A tile of the plan's own rows x cols comes out as a byte
+ *                          copy of the source pixels. MBN_EINVAL / MBN_EUNSUPPORTED: the plan's rules for in_rows x in_cols; MBN_EINVAL: more
+ *                          tiles than max_batch
+ *   mbn_net_segment_slide  checks everything first (mbn_net_set_input_u8(net, 1), mbn_slide_plan of the arguments, batch * ny * nx <= max_batch,
+ *                          the read-out's envelope at the source size, the softmax arguments): a refusal writes nothing and leaves the net
+ *                          usable. Then mbn_net_resize_tiles, ONE mbn_net_forward_dense of batch * ny * nx tiles and ONE mbn_resample_slide_f32
+ *                          to in_rows x in_cols: labels_i32, prob_f32 (may be NULL) and score_f32 (may be NULL) [batch][in_rows][in_cols].
+ *                          prob_f32 = NULL with min_prob = 0: the argmax form
+ * F32, BF16 and I8 (output stride 32 only), any plan of mbn_plan_build_os. */
+int  mbn_net_resize_tiles(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, const mbn_slide *s, void **staged);
+int  mbn_net_segment_slide(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int tile_rows, int tile_cols, int stride_rows,
+                           int stride_cols, void *labels_i32, void *prob_f32, void *score_f32, float min_prob, int ignore_label);
 /* Score the label maps of the net's most recent SUCCESSFUL source-size segment call (mbn_net_segment, _segment_to, _segment_fit, _segment_images,
- * _segment_images_fit, the three _segment_prob_ calls, _segment_views_fit) against `truth` (uint8 or int32, truth_bytes 1 or 4; "score a
+ * _segment_images_fit, the three _segment_prob_ calls, _segment_views_fit, _segment_slide) against `truth` (uint8 or int32, truth_bytes 1 or 4; "score a
  * segmentation" above): a uniform call is one span of batch * out_rows * out_cols pixels (mbn_confusion_i32), an image call the net's own ragged
  * set (mbn_confusion_ragged_i32: truth at the labels' dst_offsets). classes is the plan's; counts_u64 [classes + 1][classes + 1] is added to.
  * labels_i32 is the buffer that call wrote (or a copy of it). MBN_EINVAL before any such call; a refused segment call leaves the record of the

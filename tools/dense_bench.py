@@ -33,6 +33,11 @@
       mbn_confusion_i32, the confusion matrix of --batch label maps of 375 x 500 against a uint8 truth (main_score): 21 / 150 / 1000 classes,
       random and piecewise-constant inputs, beside torch.bincount on the same buffers.
 
+  python tools/dense_bench.py --slide [--reps 7] [--steps 20] [--batch 8] [--torch-images 2] [--no-torch]
+      mbn_resample_slide_f32, the sliding-window read-out (main_slide): a 512 x 1024 source at tile 224 / stride 150 (3 x 7 tiles) against one
+      launch of the plain kernel per tile and against torch's per-tile interpolate accumulated into [classes][H][W]; all of Net.segment_slide too.
+      --batch counts source images: the net and the logits hold 21 tiles of each.
+
   python tools/dense_bench.py --regions [--reps 7] [--steps 20] [--batch 32] [--host-maps 2] [--no-host] [--configs random,blocks,constant]
       mbn_components_i32, the connected regions of --batch label maps of 375 x 500 (main_regions): 21 / 150 / 1000 classes, random, 25 x 25-block
       and constant inputs, connectivity 4 and 8, min_area 1 (comp alone) and 50 (comp and labels_out), beside scipy.ndimage.label per class on
@@ -432,6 +437,142 @@ def main_ensemble(a):
                                                                       100 * e["spread"], l.ch, l.lds_bytes, e["over_k_windows"],
                                                                       ("%.1f" % e["torch_ms"]) if ts else "-"), flush=True)
             result["from_%d" % hw_] = out
+            if torch is not None:
+                del t
+                torch.cuda.empty_cache()
+            else:
+                t.free()
+    print(json.dumps(result))
+
+
+def main_slide(a):
+    """--slide: mbn_resample_slide_f32, the sliding-window read-out (1000 classes, the 28 x 28 and the 14 x 14 map of a 224 x 224 input, a 512 x 1024
+    source at tile 224 / stride 150: 3 x 7 tiles, --batch source images of random logits, sigma 3, image-major). Per map, alternating within every
+    repetition, argmax form and prob form (labels + score / labels + score + prob):
+      tile       the unchanged plain kernel on one tile: mbn_resample_argmax_f32 / _softmax_f32 of --batch maps to 224 x 224
+      per_tile   ny * nx launches of it, one per tile (the yardstick: they form the same interpolants but cannot combine them)
+      slide      mbn_resample_slide_f32 over the grid, ONE launch
+      torch      on the same buffer, per source image: per tile interpolate(size=(224, 224)) added into [1][classes][512][1024], divided by the
+                 count map, then argmax(1) / softmax(1).max(1); --torch-images images only (2 GB an image), in the first three repetitions,
+                 scaled to the batch
+    and segment_slide: all of Net.segment_slide (resize_tiles, forward_dense of batch * 21 tiles, the read-out) on an f32 net of that output stride.
+    Each figure is the median over the repetitions of `steps` back-to-back calls between two stream marks; the runs are kept, the spread is
+    (max - min) / median of a name's own repetitions. occupancy: active lanes / launched lanes of the slide launch, overall and of its worst cell."""
+    pkg = import_package()
+    torch = None
+    if not a.no_torch:
+        import torch
+        assert torch.cuda.is_available(), "the yardstick needs torch on the same GPU"
+    n, rng, H, W, TILE, STRIDE = a.batch, np.random.default_rng(0), 512, 1024, RES, 150
+    plan = pkg.slide_plan(H, W, TILE, TILE, STRIDE, STRIDE)
+    ys, xs, T = plan.ys, plan.xs, plan.ny * plan.nx
+
+    def cells(pos):
+        e = sorted(set(pos) | {v + TILE for v in pos})
+        return [b - c for c, b in zip(e, e[1:])]
+
+    def lanes(sizes):                           # (active, launched) outputs of an axis' pieces
+        return sum(sizes), sum(32 * -(-s // 32) for s in sizes)
+
+    (ay, ly), (ax, lx) = lanes(cells(ys)), lanes(cells(xs))
+    worst = min((hc * wc) / (32 * -(-hc // 32) * 32 * -(-wc // 32)) for hc in cells(ys) for wc in cells(xs))
+    result = {"batch": n, "source": [H, W], "tile": TILE, "stride": STRIDE, "ys": ys, "xs": xs, "cells": [cells(ys), cells(xs)],
+              "occupancy": round(ay * ax / (ly * lx), 4), "occupancy_worst_cell": round(worst, 4)}
+    with tempfile.TemporaryDirectory() as d, pkg.Context(0) as ctx:
+        path = os.path.join(d, "w.h5")
+        pkg.synthetic_h5(path, alpha=ALPHA, classes=CLASSES, seed=7)
+        src = rng.integers(0, 256, (n, H, W, 3), dtype=np.uint8)
+        d_src = ctx.to_device(src)
+        d_lab, d_sc, d_pr = ctx.alloc(n * H * W * 4), ctx.alloc(n * H * W * 4), ctx.alloc(n * H * W * 4)
+        for hw_ in (28, 14):
+            x = (3.0 * rng.standard_normal((n, T, hw_, hw_, CLASSES))).astype(np.float32)
+            if torch is not None:
+                t = torch.from_numpy(x).cuda()
+                p = t.data_ptr()
+            else:
+                t = ctx.to_device(x)
+                p = t.ptr
+            del x
+            stride = n * hw_ * hw_ * CLASSES * 4           # a per-tile launch reads --batch consecutive maps: the same bytes, whichever tile's
+
+            def tile(k, prob, p=p, hw_=hw_, stride=stride):
+                if prob:
+                    ctx.resample_softmax(d_lab.ptr, d_pr.ptr, d_sc.ptr, p + k * stride, n, hw_, hw_, CLASSES, TILE, TILE)
+                else:
+                    ctx.resample_argmax(d_lab.ptr, d_sc.ptr, p + k * stride, n, hw_, hw_, CLASSES, TILE, TILE)
+
+            hw = pkg.HostWeights(path, res=RES, output_stride=RES // hw_)
+            net = pkg.Net(ctx, hw.plan, hw.blob.copy(), n * T)
+            net.set_input_u8(True)
+            runs = []
+            for prob in (False, True):
+                form = "prob" if prob else "argmax"
+                runs.append(("tile_%s" % form, lambda prob=prob: tile(0, prob)))
+                runs.append(("per_tile_%s" % form, lambda prob=prob: [tile(k, prob) for k in range(T)]))
+                runs.append(("slide_%s" % form, lambda prob=prob, p=p, hw_=hw_: ctx.resample_slide(d_lab.ptr, d_pr.ptr if prob else None, d_sc.ptr, p, n, hw_,
+                                                                                                  hw_, CLASSES, plan, H, W)))
+                runs.append(("segment_slide_%s" % form, lambda prob=prob: net.segment_slide(d_src.ptr, n, H, W, (TILE, TILE), (STRIDE, STRIDE), d_lab.ptr,
+                                                                                            d_pr.ptr if prob else None, d_sc.ptr)))
+            times = {name: [] for name, _ in runs}
+            t_times = {"argmax": [], "prob": []}
+            for _, fn in runs:
+                marks_ms(ctx, fn, 2)
+            for rep in range(a.reps):
+                for name, fn in runs:
+                    times[name].append(marks_ms(ctx, fn, a.steps if not name.startswith("segment") else max(1, a.steps // 4)))
+                if torch is None or rep >= 3:
+                    continue
+                ctx.sync()
+                nchw = t.permute(0, 1, 4, 2, 3)
+                count = torch.zeros((H, W), device="cuda")
+                for y in ys:
+                    for x0 in xs:
+                        count[y:y + TILE, x0:x0 + TILE] += 1
+                images = min(n, a.torch_images)
+                for form in ("argmax", "prob"):
+                    def passes():
+                        for b in range(images):
+                            acc = torch.zeros((1, CLASSES, H, W), device="cuda")
+                            for iy, y in enumerate(ys):
+                                for ix, x0 in enumerate(xs):
+                                    acc[:, :, y:y + TILE, x0:x0 + TILE] += torch.nn.functional.interpolate(
+                                        nchw[b, iy * len(xs) + ix][None], size=(TILE, TILE), mode="bilinear", align_corners=False)
+                            acc /= count
+                            if form == "prob":
+                                acc.softmax(1).max(1)
+                            else:
+                                acc.argmax(1)
+                            del acc
+                    if rep == 0:
+                        passes()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    passes()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    t_times[form].append(e0.elapsed_time(e1) * n / images)
+            out = {}
+            for name, _ in runs:
+                m = statistics.median(times[name])
+                out[name] = {"kernel_ms": round(m, 4), "kernel_runs_ms": [round(v, 4) for v in times[name]],
+                             "spread": round((max(times[name]) - min(times[name])) / m, 4)}
+            l = pkg.resample_slide_plan(hw_, hw_, plan, H, W)
+            for form in ("argmax", "prob"):
+                s, pt = out["slide_%s" % form], out["per_tile_%s" % form]
+                s.update({"footprint": [l.fy, l.fx], "chunk": l.ch, "lds_bytes": l.lds_bytes, "workgroups": l.tiles,
+                          "over_per_tile": round(s["kernel_ms"] / pt["kernel_ms"], 3)})
+                ts = t_times[form]
+                if ts:
+                    tm = statistics.median(ts)
+                    s.update({"torch_ms": round(tm, 2), "torch_runs_ms": [round(v, 2) for v in ts], "torch_over_slide": round(tm / s["kernel_ms"], 1)})
+                print("from %d %-6s: tile %.4f  %d tiles %.4f (spread %.1f %%)  slide %.4f ms (spread %.1f %%, chunk %d, %d B LDS, %d workgroups)  "
+                      "slide / per tile %.3f  segment_slide %.3f ms  torch %s ms" % (
+                          hw_, form, out["tile_%s" % form]["kernel_ms"], T, pt["kernel_ms"], 100 * pt["spread"], s["kernel_ms"], 100 * s["spread"], l.ch,
+                          l.lds_bytes, l.tiles, s["over_per_tile"], out["segment_slide_%s" % form]["kernel_ms"], ("%.1f" % s["torch_ms"]) if ts else "-"),
+                      flush=True)
+            result["from_%d" % hw_] = out
+            net.destroy()
+            hw.free()
             if torch is not None:
                 del t
                 torch.cuda.empty_cache()
@@ -933,6 +1074,8 @@ def main():
     ap.add_argument("--fit", default="stretch", choices=("stretch", "pad"), help="--any: pad times the window kernel instead: see main_any_pad")
     ap.add_argument("--prob", action="store_true", help="--any: time the softmax read-out beside the argmax read-out instead: see main_prob")
     ap.add_argument("--ensemble", default="", help="comma list of view counts: time mbn_resample_ensemble_f32 instead: see main_ensemble")
+    ap.add_argument("--slide", action="store_true", help="time mbn_resample_slide_f32 (the sliding-window read-out) instead: see main_slide")
+    ap.add_argument("--torch-images", type=int, default=2, help="--slide: the source images the torch yardstick really works on (scaled to the batch)")
     ap.add_argument("--score", action="store_true", help="time mbn_confusion_i32 beside torch.bincount instead: see main_score")
     ap.add_argument("--regions", action="store_true", help="time mbn_components_i32 beside scipy.ndimage.label on the host instead: see main_regions")
     ap.add_argument("--boundary", action="store_true", help="time mbn_boundary_score_i32 beside mbn_confusion_i32, torch and scipy instead: see main_boundary")
@@ -950,6 +1093,8 @@ def main():
         return main_score(a)
     if a.ensemble:
         return main_ensemble(a)
+    if a.slide:
+        return main_slide(a)
     if a.any and a.prob:
         return main_prob(a)
     if a.any:
