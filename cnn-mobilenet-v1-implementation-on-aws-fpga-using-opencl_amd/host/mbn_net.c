@@ -14,102 +14,8 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "mbn.h"
+#include "mbn_net_internal.h"
 #include "mbn_envelope.h"
-
-struct mbn_net {
-    mbn_context *ctx;
-    mbn_plan plan;
-    int max_batch;
-    int num_cus;               /* compute units of the context's GPU (small-batch fusion rule) */
-    void *dev_blob;
-    int own_blob;
-    void *act[2];
-    int keep;
-    int dtype;                 /* MBN_DT_F32, MBN_DT_BF16 or MBN_DT_I8 */
-    int fuse_stem;             /* mbn_net_set_fuse_stem (default 1) */
-    int input_u8;              /* mbn_net_set_input_u8: images are raw uint8 HWC */
-    unsigned fuse_blocks;      /* mbn_net_set_fuse_blocks: bit L = run the depthwise layer L and the pointwise layer L+1 as one launch */
-    int fuse_blocks_set;       /* the caller chose a mask; otherwise the default of the current dtype applies */
-    int use_graph;             /* mbn_net_set_graph */
-    void *graph;               /* instantiated hipGraph of one forward, valid for the key below */
-    int g_emul;                /* pw_emul value the graph was captured under */
-    const void *g_images;
-    void *g_logits;
-    int g_batch, g_last, g_dtype, g_keep;
-    int free_running;          /* no fork dependency on the context's stream (mbn_net_set_free_running) */
-    const void *fr_images;     /* free-running: the (images, logits, batch, last_layer) of the previous forward; a call that */
-    void *fr_logits;           /* differs re-inserts the fork wait, because sub-batch slices of act[] move with the batch */
-    int fr_batch, fr_last, fr_ns, fr_stagger;
-    int nstreams;              /* sub-batch pipelining (mbn_net_set_streams); 1 = everything on the context's stream */
-    void *streams[8];
-    void *bf16_filt[MBN_MAX_LAYERS];   /* bf16 copies of the pointwise / FC filters (bf16 mode) */
-    unsigned char bf16_packed[MBN_MAX_LAYERS];   /* the copy is followed by its packed image (mbn_pack_filter_bf16) */
-    void *keep_buf[MBN_MAX_LAYERS];
-    void *logits_buf;          /* mbn_net_classify: [max_batch][classes] fp32 */
-    void *dense_feat;          /* mbn_net_forward_dense: the activation in front of the pool, [max_batch][h][w][channels] at fp32 size */
-    void *dense_logits;        /* mbn_net_segment: [max_batch][h][w][classes] fp32 */
-    mbn_resizer *resizer;      /* mbn_net_resize_input: the resizer of the geometry below, rebuilt when it changes */
-    int rs_rows, rs_cols, rs_fit, rs_filter;
-    float rs_fraction;
-    int resize_filter;         /* mbn_net_set_resize_filter: MBN_FILTER_* of both resizers (MBN_FILTER_BILINEAR until it is called) */
-    int ragged_filter;         /* the filter `ragged` was made for */
-    uint8_t pad_color[3];      /* mbn_net_set_pad_color: the border of MBN_FIT_PAD, R, G, B (black until it is called) */
-    uint8_t rs_color[3], ragged_color[3];       /* the colour `resizer` / `ragged` was made for, when it is a letterbox */
-    int ragged_pad;            /* `ragged` is a letterbox handle (mbn_ragged_resizer_create_pad) */
-    void *resize_buf;          /* mbn_net_resize_input / _inputs: [max_batch][rows][cols][3] uint8, the resized images */
-    mbn_ragged_resizer *ragged;     /* mbn_net_resize_inputs: one ragged resizer of max_batch images, made on the first call */
-    mbn_resize_item *ragged_items;  /* ... and the items it is set from, [max_batch] */
-    mbn_ragged_readout *readout;    /* mbn_net_segment_images: one ragged read-out of max_batch images, made on the first call */
-    void *label_items;              /* ... and the items it is set from, [max_batch] mbn_label_window_item (or as many mbn_label_item) */
-    int score_kind;                 /* mbn_net_segment_score: what the last successful source-size segment call wrote: SCORE_NONE, _UNIFORM, _RAGGED */
-    int64_t score_count;            /* SCORE_UNIFORM: its batch * out_rows * out_cols pixels; SCORE_RAGGED: the pixels of its maps */
-    int score_batch, score_rows, score_cols;   /* its batch, and SCORE_UNIFORM: the size of one map */
-    mbn_components *components;     /* mbn_net_segment_regions: one handle, made on first use and again when a call needs more */
-    int components_batch;           /* ... and what it holds */
-    int64_t components_pixels;
-    /* mbn_net_segment_panoptic: its handle and what it holds, the table size of both sides (mbn_net_set_panoptic_regions), and the buffers: both
-     * segment maps and a widened uint8 truth ([panoptic_span] int32 each), both tables and both counts ([panoptic_batch] images) */
-    mbn_panoptic *panoptic;
-    int panoptic_batch, panoptic_regions, panoptic_max_regions;
-    int64_t panoptic_span;
-    void *panoptic_comp[2], *panoptic_wide, *panoptic_table[2], *panoptic_n[2];
-    void *boundary_d;               /* mbn_net_segment_boundary_*: [max_batch] int32 on the device, the per-image half-widths of an image call */
-    /* mbn_net_resize_views: the view resizers kept, each made for one (source size, scale, mirror, filter, pad colour); used = the clock of its last use */
-    struct view_slot {
-        mbn_resizer *r;
-        int rows, cols, mirror, filter;
-        float scale;
-        uint8_t color[3];
-        unsigned used;
-    } view_cache[MBN_ENSEMBLE_MAX_VIEWS];
-    unsigned view_clock;
-    void *poolfc_ws;           /* workspace of mbn_pool_fc (1...4 images: pool + FC in one launch), allocated and zeroed at creation */
-    size_t poolfc_ws_bytes;
-    int fuse_tail;             /* mbn_net_set_fuse_tail (default 0) */
-    int fuse_resident;         /* mbn_net_set_fuse_resident (default 1): runs of equal bf16 blocks on a small map as one launch, the map resident in LDS */
-    void *last_out[MBN_MAX_LAYERS];
-    /* I8 mode (mbn_quantize_i8): the quantized blob on the device, its layout, the activation scales it was made with, and the
-     * host copy of the fp32 blob it is quantized from (downloaded once) */
-    void *i8_blob;
-    mbn_i8_params i8;
-    float act_scale[MBN_MAX_LAYERS];
-    float *host_blob;
-};
-
-static void panoptic_release(mbn_net *net)
-{
-    if (net->panoptic) mbn_panoptic_destroy(net->panoptic);
-    net->panoptic = NULL;
-    void **bufs[] = { &net->panoptic_comp[0], &net->panoptic_comp[1], &net->panoptic_wide, &net->panoptic_table[0], &net->panoptic_table[1],
-                      &net->panoptic_n[0], &net->panoptic_n[1] };
-    for (size_t i = 0; i < sizeof bufs / sizeof bufs[0]; i++) {
-        if (*bufs[i]) mbn_free(net->ctx, *bufs[i]);
-        *bufs[i] = NULL;
-    }
-    net->panoptic_batch = net->panoptic_regions = 0;
-    net->panoptic_span = 0;
-}
 
 static const float *blob_at(const mbn_net *net, int64_t off)
 {
@@ -127,8 +33,8 @@ static int net_alloc_common(mbn_context *ctx, const mbn_plan *plan, int max_batc
     net->nstreams = 1;
     net->fuse_stem = 1;
     net->fuse_blocks = MBN_FUSE_BLOCKS_DEFAULT;
-    net->resize_filter = MBN_FILTER_BILINEAR;
-    net->panoptic_max_regions = MBN_NET_PANOPTIC_REGIONS;
+    net->seg.resize_filter = MBN_FILTER_BILINEAR;
+    net->seg.panoptic_max_regions = MBN_NET_PANOPTIC_REGIONS;
     net->plan = *plan;
     net->max_batch = max_batch;
     net->num_cus = 256;
@@ -189,19 +95,8 @@ int mbn_net_destroy(mbn_net *net)
     if (net->graph) mbn_graph_destroy(net->ctx, net->graph);
     if (net->logits_buf) mbn_free(net->ctx, net->logits_buf);
     if (net->dense_feat) mbn_free(net->ctx, net->dense_feat);
-    if (net->dense_logits) mbn_free(net->ctx, net->dense_logits);
     if (net->poolfc_ws) mbn_free(net->ctx, net->poolfc_ws);
-    if (net->resizer) mbn_resizer_destroy(net->resizer);
-    if (net->ragged) mbn_ragged_resizer_destroy(net->ragged);
-    for (int i = 0; i < MBN_ENSEMBLE_MAX_VIEWS; i++)
-        if (net->view_cache[i].r) mbn_resizer_destroy(net->view_cache[i].r);
-    free(net->ragged_items);
-    if (net->readout) mbn_ragged_readout_destroy(net->readout);
-    if (net->components) mbn_components_destroy(net->components);
-    if (net->boundary_d) mbn_free(net->ctx, net->boundary_d);
-    panoptic_release(net);
-    free(net->label_items);
-    if (net->resize_buf) mbn_free(net->ctx, net->resize_buf);
+    mbn_net_seg_release(net);
     for (int j = 0; j < 8; j++)
         if (net->streams[j]) mbn_stream_destroy(net->ctx, net->streams[j]);
     for (int i = 0; i < MBN_MAX_LAYERS; i++) {
@@ -905,7 +800,7 @@ int mbn_net_classify(mbn_net *net, const void *images, int batch, int k, void *t
 }
 
 /* the dense head's layers: *feat = the layer in front of the pool, *fc = the FC; MBN_EUNSUPPORTED for a plan that does not end in pool, FC */
-static int dense_layers(const mbn_net *net, const mbn_layer_desc **feat, const mbn_layer_desc **fc)
+int mbn_net_dense_layers(const mbn_net *net, const mbn_layer_desc **feat, const mbn_layer_desc **fc)
 {
     const int n = net->plan.n_layers;
     if (n < 3 || net->plan.layer[n - 2].kind != MBN_L_POOL || net->plan.layer[n - 1].kind != MBN_L_FC) return MBN_EUNSUPPORTED;
@@ -919,7 +814,7 @@ int mbn_net_forward_dense(mbn_net *net, const void *images, void *dense_logits, 
 {
     if (!net || !images || !dense_logits || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
     const mbn_layer_desc *feat, *fc;
-    int rc = dense_layers(net, &feat, &fc);
+    int rc = mbn_net_dense_layers(net, &feat, &fc);
     if (rc != MBN_OK) return rc;
     if (!net->dense_feat) {
         rc = mbn_alloc(net->ctx, (size_t)net->max_batch * feat->out_rows * feat->out_cols * feat->out_ch * sizeof(float), &net->dense_feat);
@@ -929,678 +824,6 @@ int mbn_net_forward_dense(mbn_net *net, const void *images, void *dense_logits, 
     if (rc != MBN_OK) return rc;
     /* the sub-batch streams have joined the context's stream: the FC over every pixel follows on it */
     return run_layer_on(net, fc, net->dense_feat, dense_logits, batch, NULL, feat->out_rows, feat->out_cols);
-}
-
-/* the dense logits of `batch` images into net->dense_logits, [max_batch][h][w][classes] fp32, allocated on first use */
-static int dense_forward(mbn_net *net, const mbn_layer_desc *feat, const mbn_layer_desc *fc, const void *images, int batch)
-{
-    if (!net->dense_logits) {
-        const int rc = mbn_alloc(net->ctx, (size_t)net->max_batch * feat->out_rows * feat->out_cols * fc->out_ch * sizeof(float), &net->dense_logits);
-        if (rc != MBN_OK) { net->dense_logits = NULL; return rc; }
-    }
-    return mbn_net_forward_dense(net, images, net->dense_logits, batch);
-}
-
-/* mbn_net_segment_score's record: every source-size segment call ends in one of these two, so only a successful read-out changes it */
-enum { SCORE_NONE = 0, SCORE_UNIFORM = 1, SCORE_RAGGED = 2 };
-
-static int scored_uniform(mbn_net *net, int rc, int batch, int out_rows, int out_cols)
-{
-    if (rc == MBN_OK) {
-        net->score_kind = SCORE_UNIFORM;
-        net->score_count = (int64_t)batch * out_rows * out_cols;
-        net->score_batch = batch; net->score_rows = out_rows; net->score_cols = out_cols;
-    }
-    return rc;
-}
-
-static int scored_ragged(mbn_net *net, int rc, int batch, int64_t pixels)
-{
-    if (rc == MBN_OK) {
-        net->score_kind = SCORE_RAGGED;
-        net->score_count = pixels;
-        net->score_batch = batch; net->score_rows = net->score_cols = 0;
-    }
-    return rc;
-}
-
-int mbn_net_segment(mbn_net *net, const void *images, int batch, void *labels_i32, void *score_f32)
-{
-    if (!net || !images || !labels_i32 || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
-    const mbn_layer_desc *feat, *fc;
-    int rc = dense_layers(net, &feat, &fc);
-    if (rc != MBN_OK) return rc;
-    const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols, h = feat->out_rows, w = feat->out_cols;
-    const int factor = rows / h;
-    if (factor * h != rows || factor * w != cols || (factor != 8 && factor != 16 && factor != 32)) return MBN_EUNSUPPORTED;
-    rc = dense_forward(net, feat, fc, images, batch);
-    if (rc != MBN_OK) return rc;
-    return scored_uniform(net, mbn_upsample_argmax_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, factor, NULL), batch,
-                          rows, cols);
-}
-
-/* The read-out of the three source-size paths below: q = NULL is the argmax read-out (labels and score), q given the softmax read-out
- * (mbn_net_segment_prob_*: labels and prob, no score). One body per path, so both families run the same checks, resize and forward. */
-typedef struct readout_prob {
-    void *prob;
-    float min_prob;
-    int ignore_label;
-} readout_prob;
-
-/* the softmax read-out's own argument check, in front of everything else */
-static int prob_status(const readout_prob *q)
-{
-    if (!q) return MBN_OK;
-    if ((uintptr_t)q->prob % 4) return MBN_EINVAL;
-    return mbn_softmax_readout_check(q->prob != NULL, q->min_prob);
-}
-
-/* The uniform read-out of the net's dense logits at out_rows x out_cols: of the window `rect` of the network's input, or (rect = NULL) of the whole
- * map. uniform_envelope is asked before the resize and the forward run; uniform_readout is the one place that chooses among the four public calls. */
-static int uniform_envelope(const mbn_net *net, const mbn_layer_desc *feat, const mbn_layer_desc *fc, int batch, const int32_t *rect, int out_rows,
-                            int out_cols)
-{
-    if (rect)
-        return mbn_resample_window_envelope(batch, feat->out_rows, feat->out_cols, fc->out_ch, net->plan.layer[0].in_rows, net->plan.layer[0].in_cols,
-                                            rect, out_rows, out_cols);
-    /* every size is positive here (the callers' checks, dense_layers): what the plain shape can miss is a limit */
-    return mbn_resample_argmax_envelope(batch, feat->out_rows, feat->out_cols, fc->out_ch, out_rows, out_cols) != MBN_OK ? MBN_EUNSUPPORTED : MBN_OK;
-}
-
-static int uniform_readout(mbn_net *net, const mbn_layer_desc *feat, const mbn_layer_desc *fc, int batch, const int32_t *rect, int out_rows,
-                           int out_cols, void *labels_i32, void *score_f32, const readout_prob *q)
-{
-    const int h = feat->out_rows, w = feat->out_cols, rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols;
-    if (q && rect)
-        return mbn_resample_softmax_window_f32(net->ctx, labels_i32, q->prob, NULL, net->dense_logits, batch, h, w, fc->out_ch, rows, cols, rect,
-                                               out_rows, out_cols, q->min_prob, q->ignore_label, NULL);
-    if (q)
-        return mbn_resample_softmax_f32(net->ctx, labels_i32, q->prob, NULL, net->dense_logits, batch, h, w, fc->out_ch, out_rows, out_cols, q->min_prob,
-                                        q->ignore_label, NULL);
-    if (rect)
-        return mbn_resample_argmax_window_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, rows, cols, rect, out_rows,
-                                              out_cols, NULL);
-    return mbn_resample_argmax_f32(net->ctx, labels_i32, score_f32, net->dense_logits, batch, h, w, fc->out_ch, out_rows, out_cols, NULL);
-}
-
-static int segment_to(mbn_net *net, const void *images, int batch, int out_rows, int out_cols, void *labels_i32, void *score_f32, const readout_prob *q)
-{
-    if (!net || !images || !labels_i32 || batch <= 0 || batch > net->max_batch || out_rows <= 0 || out_cols <= 0) return MBN_EINVAL;
-    if (prob_status(q) != MBN_OK) return MBN_EINVAL;
-    const mbn_layer_desc *feat, *fc;
-    int rc = dense_layers(net, &feat, &fc);
-    if (rc == MBN_OK) rc = uniform_envelope(net, feat, fc, batch, NULL, out_rows, out_cols);
-    if (rc == MBN_OK) rc = dense_forward(net, feat, fc, images, batch);
-    if (rc != MBN_OK) return rc;
-    return scored_uniform(net, uniform_readout(net, feat, fc, batch, NULL, out_rows, out_cols, labels_i32, score_f32, q), batch, out_rows, out_cols);
-}
-
-int mbn_net_segment_to(mbn_net *net, const void *images, int batch, int out_rows, int out_cols, void *labels_i32, void *score_f32)
-{
-    return segment_to(net, images, batch, out_rows, out_cols, labels_i32, score_f32, NULL);
-}
-
-int mbn_net_segment_prob_to(mbn_net *net, const void *images, int batch, int out_rows, int out_cols, void *labels_i32, void *prob_f32, float min_prob,
-                            int ignore_label)
-{
-    const readout_prob q = { prob_f32, min_prob, ignore_label };
-    return segment_to(net, images, batch, out_rows, out_cols, labels_i32, NULL, &q);
-}
-
-/* MBN_OK for the fits a source-size read-out exists for; a crop's box is fractional and the network never saw the rest of the image */
-static int segment_fit_status(int fit)
-{
-    if (fit == MBN_FIT_STRETCH || fit == MBN_FIT_PAD) return MBN_OK;
-    return fit == MBN_FIT_CROP ? MBN_EUNSUPPORTED : MBN_EINVAL;
-}
-
-static int segment_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, void *labels_i32, void *score_f32,
-                       const readout_prob *q)
-{
-    if (!net || !src_u8 || !labels_i32 || batch <= 0 || batch > net->max_batch || in_rows <= 0 || in_cols <= 0) return MBN_EINVAL;
-    if (!net->input_u8) return MBN_EINVAL;                    /* the resized images are uint8: the net must take them as such */
-    if (prob_status(q) != MBN_OK) return MBN_EINVAL;
-    int rc = segment_fit_status(fit);
-    if (rc != MBN_OK) return rc;
-    const mbn_layer_desc *feat, *fc;
-    rc = dense_layers(net, &feat, &fc);
-    if (rc != MBN_OK) return rc;
-    int32_t pad[4];
-    const int32_t *rect = NULL;                               /* a stretch reads out the whole map */
-    if (fit == MBN_FIT_PAD) {
-        rc = mbn_fit_pad(in_rows, in_cols, net->plan.layer[0].in_rows, net->plan.layer[0].in_cols, pad);
-        if (rc != MBN_OK) return rc;
-        rect = pad;
-    }
-    rc = uniform_envelope(net, feat, fc, batch, rect, in_rows, in_cols);
-    if (rc != MBN_OK) return rc;
-    void *images = NULL;
-    rc = mbn_net_resize_input(net, src_u8, batch, in_rows, in_cols, fit, 1.0f, &images);
-    if (rc == MBN_OK) rc = dense_forward(net, feat, fc, images, batch);
-    if (rc != MBN_OK) return rc;
-    return scored_uniform(net, uniform_readout(net, feat, fc, batch, rect, in_rows, in_cols, labels_i32, score_f32, q), batch, in_rows, in_cols);
-}
-
-int mbn_net_segment_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, void *labels_i32, void *score_f32)
-{
-    return segment_fit(net, src_u8, batch, in_rows, in_cols, fit, labels_i32, score_f32, NULL);
-}
-
-int mbn_net_segment_prob_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, void *labels_i32, void *prob_f32,
-                             float min_prob, int ignore_label)
-{
-    const readout_prob q = { prob_f32, min_prob, ignore_label };
-    return segment_fit(net, src_u8, batch, in_rows, in_cols, fit, labels_i32, NULL, &q);
-}
-
-int mbn_net_segment_images(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *in_rows, const int32_t *in_cols, int batch,
-                           void *labels_i32, const int64_t *dst_offsets, void *score_f32)
-{
-    return mbn_net_segment_images_fit(net, src_u8, offsets, in_rows, in_cols, batch, MBN_FIT_STRETCH, labels_i32, dst_offsets, score_f32);
-}
-
-static int segment_images_fit(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *in_rows, const int32_t *in_cols, int batch,
-                              int fit, void *labels_i32, const int64_t *dst_offsets, void *score_f32, const readout_prob *q)
-{
-    if (!net || !src_u8 || !offsets || !in_rows || !in_cols || !labels_i32 || !dst_offsets || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
-    if (!net->input_u8) return MBN_EINVAL;                    /* the resized images are uint8: the net must take them as such */
-    if (prob_status(q) != MBN_OK) return MBN_EINVAL;
-    int rc = segment_fit_status(fit);
-    if (rc != MBN_OK) return rc;
-    const mbn_layer_desc *feat, *fc;
-    rc = dense_layers(net, &feat, &fc);
-    if (rc != MBN_OK) return rc;
-    const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols;
-    if (!net->label_items) {
-        net->label_items = malloc((size_t)net->max_batch * sizeof(mbn_label_window_item));       /* either kind of item */
-        if (!net->label_items) return MBN_ENOMEM;
-    }
-    /* a window item is a label item and then its rectangle: the first item_bytes of `it` are the item of either kind */
-    const size_t item_bytes = fit == MBN_FIT_PAD ? sizeof(mbn_label_window_item) : sizeof(mbn_label_item);
-    int64_t pixels = 0;
-    for (int i = 0; i < batch; i++) {
-        pixels += (int64_t)in_rows[i] * in_cols[i];
-        int32_t rect[4] = { 0, 0, 0, 0 };
-        if (fit == MBN_FIT_PAD) {
-            rc = mbn_fit_pad(in_rows[i], in_cols[i], rows, cols, rect);
-            if (rc != MBN_OK) return rc;
-        }
-        const mbn_label_window_item it = { dst_offsets[i], in_rows[i], in_cols[i], rect[0], rect[1], rect[2], rect[3] };
-        memcpy((char *)net->label_items + (size_t)i * item_bytes, &it, item_bytes);
-    }
-    if (!net->readout) {
-        rc = mbn_ragged_readout_create(net->ctx, net->max_batch, &net->readout);
-        if (rc != MBN_OK) { net->readout = NULL; return rc; }
-    }
-    /* the set first: it checks every item, so a refusal comes before the resize and the forward run; its upload is ordered by the stream */
-    rc = fit == MBN_FIT_PAD ? mbn_ragged_readout_set_window(net->readout, feat->out_rows, feat->out_cols, fc->out_ch, rows, cols, net->label_items, batch, NULL)
-                            : mbn_ragged_readout_set(net->readout, feat->out_rows, feat->out_cols, fc->out_ch, net->label_items, batch, NULL);
-    if (rc != MBN_OK) return rc;
-    void *images = NULL;
-    rc = mbn_net_resize_inputs(net, src_u8, offsets, in_rows, in_cols, batch, fit, 1.0f, &images);
-    if (rc == MBN_OK) rc = dense_forward(net, feat, fc, images, batch);
-    if (rc != MBN_OK) return rc;
-    if (q)
-        return scored_ragged(net, mbn_resample_softmax_ragged_f32(net->readout, labels_i32, q->prob, NULL, net->dense_logits, q->min_prob,
-                                                                  q->ignore_label, NULL), batch, pixels);
-    return scored_ragged(net, mbn_resample_argmax_ragged_f32(net->readout, labels_i32, score_f32, net->dense_logits, NULL), batch, pixels);
-}
-
-int mbn_net_segment_images_fit(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *in_rows, const int32_t *in_cols, int batch,
-                               int fit, void *labels_i32, const int64_t *dst_offsets, void *score_f32)
-{
-    return segment_images_fit(net, src_u8, offsets, in_rows, in_cols, batch, fit, labels_i32, dst_offsets, score_f32, NULL);
-}
-
-int mbn_net_segment_prob_images_fit(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *in_rows, const int32_t *in_cols,
-                                    int batch, int fit, void *labels_i32, const int64_t *dst_offsets, void *prob_f32, float min_prob,
-                                    int ignore_label)
-{
-    const readout_prob q = { prob_f32, min_prob, ignore_label };
-    return segment_images_fit(net, src_u8, offsets, in_rows, in_cols, batch, fit, labels_i32, dst_offsets, NULL, &q);
-}
-
-int mbn_net_set_resize_filter(mbn_net *net, int filter)
-{
-    if (!net || filter < MBN_FILTER_NEAREST || filter > MBN_FILTER_HAMMING) return MBN_EINVAL;
-    net->resize_filter = filter;                              /* the kept resizers are rebuilt by the next call that finds another filter in them */
-    return MBN_OK;
-}
-
-int mbn_net_get_resize_filter(const mbn_net *net, int *filter)
-{
-    if (!net || !filter) return MBN_EINVAL;
-    *filter = net->resize_filter;
-    return MBN_OK;
-}
-
-int mbn_net_set_pad_color(mbn_net *net, int r, int g, int b)
-{
-    if (!net || r < 0 || r > 255 || g < 0 || g > 255 || b < 0 || b > 255) return MBN_EINVAL;
-    net->pad_color[0] = (uint8_t)r; net->pad_color[1] = (uint8_t)g; net->pad_color[2] = (uint8_t)b;     /* a kept letterbox of another colour is rebuilt */
-    return MBN_OK;
-}
-
-int mbn_net_get_pad_color(const mbn_net *net, int *r, int *g, int *b)
-{
-    if (!net || !r || !g || !b) return MBN_EINVAL;
-    *r = net->pad_color[0]; *g = net->pad_color[1]; *b = net->pad_color[2];
-    return MBN_OK;
-}
-
-int mbn_net_resize_input(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, float crop_fraction, void **images_u8)
-{
-    if (!net || !src_u8 || !images_u8 || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
-    *images_u8 = NULL;
-    const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols;
-    if (fit == MBN_FIT_STRETCH || fit == MBN_FIT_PAD) crop_fraction = 1.0f;
-    if (!net->resizer || net->rs_rows != in_rows || net->rs_cols != in_cols || net->rs_fit != fit || net->rs_fraction != crop_fraction ||
-        net->rs_filter != net->resize_filter || (fit == MBN_FIT_PAD && memcmp(net->rs_color, net->pad_color, 3) != 0)) {
-        float box[4];
-        mbn_resizer *r = NULL;
-        int rc = mbn_fit_box(in_rows, in_cols, rows, cols, fit, crop_fraction, box);
-        if (rc == MBN_OK)
-            rc = fit == MBN_FIT_PAD ? mbn_resizer_create_pad(net->ctx, net->resize_filter, in_rows, in_cols, rows, cols, net->pad_color, &r)
-                                    : mbn_resizer_create_filter(net->ctx, net->resize_filter, in_rows, in_cols, box, rows, cols, &r);
-        if (rc != MBN_OK) return rc;                          /* the resizer of the previous geometry stays */
-        if (net->resizer) mbn_resizer_destroy(net->resizer);  /* waits for the stream: a resize still running reads its tables */
-        net->resizer = r;
-        net->rs_rows = in_rows; net->rs_cols = in_cols; net->rs_fit = fit; net->rs_fraction = crop_fraction; net->rs_filter = net->resize_filter;
-        memcpy(net->rs_color, net->pad_color, 3);
-    }
-    if (!net->resize_buf) {
-        int rc = mbn_alloc(net->ctx, (size_t)net->max_batch * rows * cols * 3, &net->resize_buf);
-        if (rc != MBN_OK) { net->resize_buf = NULL; return rc; }
-    }
-    int rc = mbn_resize_u8(net->resizer, net->resize_buf, src_u8, batch, NULL);
-    if (rc == MBN_OK) *images_u8 = net->resize_buf;
-    return rc;
-}
-
-int mbn_net_resize_inputs(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *in_rows, const int32_t *in_cols, int batch, int fit,
-                          float crop_fraction, void **images_u8)
-{
-    if (!net || !src_u8 || !offsets || !in_rows || !in_cols || !images_u8 || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
-    *images_u8 = NULL;
-    const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols;
-    const int pad = fit == MBN_FIT_PAD;
-    if (fit == MBN_FIT_STRETCH || pad) crop_fraction = 1.0f;
-    if (!net->ragged_items) {
-        net->ragged_items = malloc((size_t)net->max_batch * sizeof(mbn_resize_item));
-        if (!net->ragged_items) return MBN_ENOMEM;
-    }
-    for (int i = 0; i < batch; i++) {
-        mbn_resize_item *it = &net->ragged_items[i];
-        it->src_offset = offsets[i];
-        it->rows = in_rows[i];
-        it->cols = in_cols[i];
-        const int rc = mbn_fit_box(in_rows[i], in_cols[i], rows, cols, fit, crop_fraction, it->box);
-        if (rc != MBN_OK) return rc;
-    }
-    if (!net->ragged || net->ragged_filter != net->resize_filter || net->ragged_pad != pad || (pad && memcmp(net->ragged_color, net->pad_color, 3) != 0)) {
-        mbn_ragged_resizer *r = NULL;                         /* HAMMING / LANCZOS: MBN_EUNSUPPORTED, and the resizer of the previous filter stays */
-        const int rc = pad ? mbn_ragged_resizer_create_pad(net->ctx, net->resize_filter, net->max_batch, rows, cols, net->pad_color, &r)
-                           : mbn_ragged_resizer_create_filter(net->ctx, net->resize_filter, net->max_batch, rows, cols, &r);
-        if (rc != MBN_OK) return rc;
-        if (net->ragged) mbn_ragged_resizer_destroy(net->ragged);       /* waits for its last launch */
-        net->ragged = r;
-        net->ragged_filter = net->resize_filter;
-        net->ragged_pad = pad;
-        memcpy(net->ragged_color, net->pad_color, 3);
-    }
-    if (!net->resize_buf) {
-        const int rc = mbn_alloc(net->ctx, (size_t)net->max_batch * rows * cols * 3, &net->resize_buf);
-        if (rc != MBN_OK) { net->resize_buf = NULL; return rc; }
-    }
-    int rc = mbn_ragged_resizer_set(net->ragged, net->ragged_items, batch, NULL);
-    if (rc == MBN_OK) rc = mbn_resize_ragged_u8(net->ragged, net->resize_buf, src_u8, NULL);
-    if (rc == MBN_OK) *images_u8 = net->resize_buf;
-    return rc;
-}
-
-/* the views of (scales[k], mirrors[k]) for a source of in_rows x in_cols: what both calls below check first */
-static int views_of(const mbn_net *net, int batch, int in_rows, int in_cols, const float *scales, const int32_t *mirrors, int n_views, mbn_view *views)
-{
-    if (!scales || !mirrors || n_views < 1 || n_views > MBN_ENSEMBLE_MAX_VIEWS || batch <= 0 || in_rows <= 0 || in_cols <= 0) return MBN_EINVAL;
-    if ((int64_t)batch * n_views > net->max_batch) return MBN_EINVAL;
-    for (int k = 0; k < n_views; k++) {
-        const int rc = mbn_fit_view(in_rows, in_cols, net->plan.layer[0].in_rows, net->plan.layer[0].in_cols, scales[k], mirrors[k], &views[k]);
-        if (rc != MBN_OK) return rc;
-    }
-    return MBN_OK;
-}
-
-/* the kept resizer of one view, made on first use; the least recently used slot makes room (a call has at most as many views as there are slots and
- * stamps each with the call's own clock, so it never takes a slot from itself) */
-static int view_resizer(mbn_net *net, int in_rows, int in_cols, float scale, const mbn_view *view, mbn_resizer **out)
-{
-    struct view_slot *oldest = NULL;                              /* where a new one goes: an empty slot, else the least recently used */
-    for (int i = 0; i < MBN_ENSEMBLE_MAX_VIEWS; i++) {
-        struct view_slot *v = &net->view_cache[i];
-        if (v->r && v->rows == in_rows && v->cols == in_cols && v->scale == scale && v->mirror == view->mirror && v->filter == net->resize_filter &&
-            memcmp(v->color, net->pad_color, 3) == 0) {
-            v->used = net->view_clock;
-            *out = v->r;
-            return MBN_OK;
-        }
-        if (!oldest || (oldest->r && (!v->r || (int)(v->used - oldest->used) < 0))) oldest = v;
-    }
-    mbn_resizer *r = NULL;
-    const int rc = mbn_resizer_create_view(net->ctx, net->resize_filter, in_rows, in_cols, net->plan.layer[0].in_rows, net->plan.layer[0].in_cols, view,
-                                           net->pad_color, &r);
-    if (rc != MBN_OK) return rc;
-    if (oldest->r) mbn_resizer_destroy(oldest->r);                /* waits for the stream: a resize still running reads its tables */
-    oldest->r = r;
-    oldest->rows = in_rows; oldest->cols = in_cols; oldest->scale = scale; oldest->mirror = view->mirror; oldest->filter = net->resize_filter;
-    memcpy(oldest->color, net->pad_color, 3);
-    oldest->used = net->view_clock;
-    *out = r;
-    return MBN_OK;
-}
-
-static int resize_views(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, const float *scales, const mbn_view *views, int n_views,
-                        void **staged)
-{
-    const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols;
-    if (!net->resize_buf) {
-        const int rc = mbn_alloc(net->ctx, (size_t)net->max_batch * rows * cols * 3, &net->resize_buf);
-        if (rc != MBN_OK) { net->resize_buf = NULL; return rc; }
-    }
-    net->view_clock++;
-    for (int k = 0; k < n_views; k++) {
-        mbn_resizer *r = NULL;
-        int rc = view_resizer(net, in_rows, in_cols, scales[k], &views[k], &r);
-        /* view-major: view k's canvases are images k * batch .. of the staging buffer */
-        if (rc == MBN_OK) rc = mbn_resize_u8(r, (uint8_t *)net->resize_buf + (size_t)k * batch * rows * cols * 3, src_u8, batch, NULL);
-        if (rc != MBN_OK) return rc;
-    }
-    *staged = net->resize_buf;
-    return MBN_OK;
-}
-
-int mbn_net_resize_views(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, const float *scales, const int32_t *mirrors,
-                         int n_views, void **staged)
-{
-    if (!net || !src_u8 || !staged) return MBN_EINVAL;
-    *staged = NULL;
-    mbn_view views[MBN_ENSEMBLE_MAX_VIEWS];
-    const int rc = views_of(net, batch, in_rows, in_cols, scales, mirrors, n_views, views);
-    if (rc != MBN_OK) return rc;
-    return resize_views(net, src_u8, batch, in_rows, in_cols, scales, views, n_views, staged);
-}
-
-int mbn_net_segment_views_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, const float *scales, const int32_t *mirrors,
-                              int n_views, void *labels_i32, void *prob_f32, void *score_f32, float min_prob, int ignore_label)
-{
-    if (!net || !src_u8 || !labels_i32) return MBN_EINVAL;
-    if (!net->input_u8) return MBN_EINVAL;                    /* the staged canvases are uint8: the net must take them as such */
-    if (((uintptr_t)labels_i32 | (uintptr_t)prob_f32 | (uintptr_t)score_f32) % 4) return MBN_EINVAL;
-    /* the ensemble call's own rule: no prob map and no threshold is the argmax form */
-    if ((prob_f32 || !(min_prob == 0.0f)) && mbn_softmax_readout_check(prob_f32 != NULL, min_prob) != MBN_OK) return MBN_EINVAL;
-    mbn_view views[MBN_ENSEMBLE_MAX_VIEWS];
-    int rc = views_of(net, batch, in_rows, in_cols, scales, mirrors, n_views, views);
-    if (rc != MBN_OK) return rc;
-    const mbn_layer_desc *feat, *fc;
-    rc = dense_layers(net, &feat, &fc);
-    if (rc != MBN_OK) return rc;
-    const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols;
-    rc = mbn_resample_ensemble_envelope(batch, feat->out_rows, feat->out_cols, fc->out_ch, rows, cols, views, n_views, in_rows, in_cols);
-    if (rc != MBN_OK) return rc;
-    void *images = NULL;
-    rc = resize_views(net, src_u8, batch, in_rows, in_cols, scales, views, n_views, &images);
-    if (rc == MBN_OK) rc = dense_forward(net, feat, fc, images, batch * n_views);
-    if (rc != MBN_OK) return rc;
-    return scored_uniform(net, mbn_resample_ensemble_f32(net->ctx, labels_i32, prob_f32, score_f32, net->dense_logits, batch, feat->out_rows,
-                                                         feat->out_cols, fc->out_ch, rows, cols, views, n_views, in_rows, in_cols, min_prob,
-                                                         ignore_label, NULL), batch, in_rows, in_cols);
-}
-
-/* the tiles of a plan the caller has checked: batch * ny * nx <= max_batch items on the net's stretch handle, one launch */
-static int resize_tiles(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, const mbn_slide *s, void **staged)
-{
-    const int rows = net->plan.layer[0].in_rows, cols = net->plan.layer[0].in_cols;
-    if (!net->ragged_items) {
-        net->ragged_items = malloc((size_t)net->max_batch * sizeof(mbn_resize_item));
-        if (!net->ragged_items) return MBN_ENOMEM;
-    }
-    int n = 0;
-    for (int b = 0; b < batch; b++)
-        for (int iy = 0; iy < s->ny; iy++)
-            for (int ix = 0; ix < s->nx; ix++) {
-                mbn_resize_item *it = &net->ragged_items[n++];          /* image b * ny * nx + iy * nx + ix of the staging buffer */
-                it->src_offset = (int64_t)b * in_rows * in_cols * 3;
-                it->rows = in_rows;
-                it->cols = in_cols;
-                it->box[0] = (float)s->x[ix]; it->box[1] = (float)s->y[iy];
-                it->box[2] = (float)(s->x[ix] + s->tile_cols); it->box[3] = (float)(s->y[iy] + s->tile_rows);
-            }
-    if (!net->ragged || net->ragged_filter != net->resize_filter || net->ragged_pad) {
-        mbn_ragged_resizer *r = NULL;                         /* HAMMING / LANCZOS: MBN_EUNSUPPORTED, and the resizer of the previous filter stays */
-        const int rc = mbn_ragged_resizer_create_filter(net->ctx, net->resize_filter, net->max_batch, rows, cols, &r);
-        if (rc != MBN_OK) return rc;
-        if (net->ragged) mbn_ragged_resizer_destroy(net->ragged);       /* waits for its last launch */
-        net->ragged = r;
-        net->ragged_filter = net->resize_filter;
-        net->ragged_pad = 0;
-    }
-    if (!net->resize_buf) {
-        const int rc = mbn_alloc(net->ctx, (size_t)net->max_batch * rows * cols * 3, &net->resize_buf);
-        if (rc != MBN_OK) { net->resize_buf = NULL; return rc; }
-    }
-    int rc = mbn_ragged_resizer_set(net->ragged, net->ragged_items, n, NULL);
-    if (rc == MBN_OK) rc = mbn_resize_ragged_u8(net->ragged, net->resize_buf, src_u8, NULL);
-    if (rc == MBN_OK) *staged = net->resize_buf;
-    return rc;
-}
-
-/* what both slide calls check first: the plan against the source size, its tiles against max_batch */
-static int slide_status(const mbn_net *net, int batch, int in_rows, int in_cols, const mbn_slide *s)
-{
-    if (batch <= 0 || in_rows <= 0 || in_cols <= 0) return MBN_EINVAL;
-    const int rc = mbn_slide_check(s, in_rows, in_cols);
-    if (rc != MBN_OK) return rc;
-    return (int64_t)batch * s->ny * s->nx > net->max_batch ? MBN_EINVAL : MBN_OK;
-}
-
-int mbn_net_resize_tiles(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, const mbn_slide *s, void **staged)
-{
-    if (!net || !src_u8 || !s || !staged) return MBN_EINVAL;
-    *staged = NULL;
-    const int rc = slide_status(net, batch, in_rows, in_cols, s);
-    if (rc != MBN_OK) return rc;
-    return resize_tiles(net, src_u8, batch, in_rows, in_cols, s, staged);
-}
-
-int mbn_net_segment_slide(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int tile_rows, int tile_cols, int stride_rows,
-                          int stride_cols, void *labels_i32, void *prob_f32, void *score_f32, float min_prob, int ignore_label)
-{
-    if (!net || !src_u8 || !labels_i32) return MBN_EINVAL;
-    if (!net->input_u8) return MBN_EINVAL;                    /* the staged tiles are uint8: the net must take them as such */
-    if (((uintptr_t)labels_i32 | (uintptr_t)prob_f32 | (uintptr_t)score_f32) % 4) return MBN_EINVAL;
-    /* the read-out's own rule: no prob map and no threshold is the argmax form */
-    if ((prob_f32 || !(min_prob == 0.0f)) && mbn_softmax_readout_check(prob_f32 != NULL, min_prob) != MBN_OK) return MBN_EINVAL;
-    if (batch <= 0) return MBN_EINVAL;
-    mbn_slide s;
-    int rc = mbn_slide_plan(in_rows, in_cols, tile_rows, tile_cols, stride_rows, stride_cols, &s);
-    if (rc == MBN_OK) rc = slide_status(net, batch, in_rows, in_cols, &s);
-    if (rc != MBN_OK) return rc;
-    const mbn_layer_desc *feat, *fc;
-    rc = dense_layers(net, &feat, &fc);
-    if (rc != MBN_OK) return rc;
-    rc = mbn_resample_slide_envelope(batch, feat->out_rows, feat->out_cols, fc->out_ch, &s, in_rows, in_cols);
-    if (rc != MBN_OK) return rc;
-    void *images = NULL;
-    rc = resize_tiles(net, src_u8, batch, in_rows, in_cols, &s, &images);
-    if (rc == MBN_OK) rc = dense_forward(net, feat, fc, images, batch * s.ny * s.nx);
-    if (rc != MBN_OK) return rc;
-    return scored_uniform(net, mbn_resample_slide_f32(net->ctx, labels_i32, prob_f32, score_f32, net->dense_logits, batch, feat->out_rows,
-                                                      feat->out_cols, fc->out_ch, &s, in_rows, in_cols, min_prob, ignore_label, NULL), batch, in_rows,
-                          in_cols);
-}
-
-int mbn_net_segment_score(mbn_net *net, const void *labels_i32, const void *truth, int truth_bytes, void *counts_u64)
-{
-    if (!net || net->score_kind == SCORE_NONE) return MBN_EINVAL;
-    const mbn_layer_desc *feat, *fc;
-    const int rc = dense_layers(net, &feat, &fc);
-    if (rc != MBN_OK) return rc;
-    if (net->score_kind == SCORE_RAGGED) return mbn_confusion_ragged_i32(net->readout, counts_u64, labels_i32, truth, truth_bytes, fc->out_ch, NULL);
-    return mbn_confusion_i32(net->ctx, counts_u64, labels_i32, truth, truth_bytes, fc->out_ch, net->score_count, NULL);
-}
-
-/* the net's one mbn_components handle holds at least the maps of the last segment call */
-static int components_ready(mbn_net *net)
-{
-    if (net->components && net->score_batch <= net->components_batch && net->score_count <= net->components_pixels) return MBN_OK;
-    /* the new handle first: when it cannot be had, the old one stays */
-    const int batch = net->score_batch > net->components_batch ? net->score_batch : net->components_batch;
-    const int64_t pixels = net->score_count > net->components_pixels ? net->score_count : net->components_pixels;
-    mbn_components *h = NULL;
-    const int rc = mbn_components_create(net->ctx, batch, pixels, &h);
-    if (rc != MBN_OK) return rc;
-    if (net->components) mbn_components_destroy(net->components);
-    net->components = h;
-    net->components_batch = batch;
-    net->components_pixels = pixels;
-    return MBN_OK;
-}
-
-int mbn_net_segment_regions(mbn_net *net, const void *labels_i32, void *comp_i32, mbn_region *regions, void *n_regions_i32, void *labels_out_i32,
-                            int connectivity, int min_area, int ignore_label, int max_regions)
-{
-    if (!net || net->score_kind == SCORE_NONE) return MBN_EINVAL;
-    const mbn_layer_desc *feat, *fc;
-    int rc = dense_layers(net, &feat, &fc);
-    if (rc != MBN_OK) return rc;
-    rc = components_ready(net);
-    if (rc != MBN_OK) return rc;
-    if (net->score_kind == SCORE_RAGGED)
-        return mbn_components_ragged_i32(net->components, net->readout, comp_i32, regions, n_regions_i32, labels_out_i32, labels_i32, fc->out_ch,
-                                         connectivity, min_area, ignore_label, max_regions, NULL);
-    return mbn_components_i32(net->components, comp_i32, regions, n_regions_i32, labels_out_i32, labels_i32, net->score_batch, net->score_rows,
-                              net->score_cols, fc->out_ch, connectivity, min_area, ignore_label, max_regions, NULL);
-}
-
-int mbn_net_set_panoptic_regions(mbn_net *net, int max_regions)
-{
-    if (!net || max_regions < 1) return MBN_EINVAL;
-    if (max_regions > MBN_COMPONENTS_MAX_REGIONS) return MBN_EUNSUPPORTED;
-    net->panoptic_max_regions = max_regions;
-    return MBN_OK;
-}
-
-/* the handle and the buffers of mbn_net_segment_panoptic hold `batch` images whose maps span `span` elements, with tables of the net's setting.
- * Everything is made again when a call needs more of any of them; a failure leaves nothing behind and the net usable */
-static int panoptic_ready(mbn_net *net, int batch, int64_t span)
-{
-    const int regions = net->panoptic_max_regions;
-    if (net->panoptic && batch <= net->panoptic_batch && span <= net->panoptic_span && regions == net->panoptic_regions) return MBN_OK;
-    if (batch < net->panoptic_batch) batch = net->panoptic_batch;
-    if (span < net->panoptic_span) span = net->panoptic_span;
-    panoptic_release(net);                                         /* waits for the device: an earlier call may still read them */
-    int rc = mbn_panoptic_create(net->ctx, batch, (int64_t)batch * regions, &net->panoptic);
-    if (rc != MBN_OK) net->panoptic = NULL;
-    for (int k = 0; k < 2 && rc == MBN_OK; k++) {
-        rc = mbn_alloc(net->ctx, (size_t)span * 4, &net->panoptic_comp[k]);
-        if (rc == MBN_OK) rc = mbn_alloc(net->ctx, (size_t)batch * regions * sizeof(mbn_region), &net->panoptic_table[k]);
-        if (rc == MBN_OK) rc = mbn_alloc(net->ctx, (size_t)batch * 4, &net->panoptic_n[k]);
-    }
-    if (rc == MBN_OK) rc = mbn_alloc(net->ctx, (size_t)span * 4, &net->panoptic_wide);
-    if (rc != MBN_OK) { panoptic_release(net); return rc; }
-    net->panoptic_batch = batch;
-    net->panoptic_span = span;
-    net->panoptic_regions = regions;
-    return MBN_OK;
-}
-
-int mbn_net_segment_panoptic(mbn_net *net, const void *labels_i32, const void *truth, int truth_bytes, int connectivity, int min_area, void *pq_u64,
-                             void *scored_i32)
-{
-    if (!net || net->score_kind == SCORE_NONE || !labels_i32 || !truth || !pq_u64 || !scored_i32) return MBN_EINVAL;
-    if ((truth_bytes != 1 && truth_bytes != 4) || (truth_bytes == 4 && (uintptr_t)truth % 4)) return MBN_EINVAL;
-    const mbn_layer_desc *feat, *fc;
-    int rc = dense_layers(net, &feat, &fc);
-    if (rc != MBN_OK) return rc;
-    const int ragged = net->score_kind == SCORE_RAGGED, batch = net->score_batch, classes = fc->out_ch;
-    const int64_t span = ragged ? mbn_ragged_readout_span(net->readout) : net->score_count;
-    if (span < 1) return MBN_EINVAL;
-    rc = components_ready(net);
-    if (rc == MBN_OK) rc = panoptic_ready(net, batch, span);
-    if (rc != MBN_OK) return rc;
-    const int regions = net->panoptic_regions;
-    const void *maps[2] = { labels_i32, truth };
-    if (truth_bytes == 1) {
-        /* the flat span: the gaps of a ragged set are widened too, into this private buffer only, and nothing reads them there */
-        rc = mbn_widen_u8_i32(net->ctx, net->panoptic_wide, truth, span, NULL);
-        if (rc != MBN_OK) return rc;
-        maps[1] = net->panoptic_wide;
-    }
-    /* the two calls share the components handle's scratch: they are ordered by the context's stream */
-    for (int k = 0; k < 2; k++) {
-        rc = ragged ? mbn_components_ragged_i32(net->components, net->readout, net->panoptic_comp[k], (mbn_region *)net->panoptic_table[k],
-                                                net->panoptic_n[k], NULL, maps[k], classes, connectivity, min_area, 0, regions, NULL)
-                    : mbn_components_i32(net->components, net->panoptic_comp[k], (mbn_region *)net->panoptic_table[k], net->panoptic_n[k], NULL, maps[k],
-                                         batch, net->score_rows, net->score_cols, classes, connectivity, min_area, 0, regions, NULL);
-        if (rc != MBN_OK) return rc;
-    }
-    if (ragged)
-        return mbn_panoptic_ragged_i32(net->panoptic, net->readout, pq_u64, scored_i32, NULL, NULL, NULL, NULL, net->panoptic_comp[0],
-                                       (const mbn_region *)net->panoptic_table[0], net->panoptic_n[0], regions, net->panoptic_comp[1],
-                                       (const mbn_region *)net->panoptic_table[1], net->panoptic_n[1], regions, classes, NULL);
-    return mbn_panoptic_i32(net->panoptic, pq_u64, scored_i32, NULL, NULL, NULL, NULL, net->panoptic_comp[0], (const mbn_region *)net->panoptic_table[0],
-                            net->panoptic_n[0], regions, net->panoptic_comp[1], (const mbn_region *)net->panoptic_table[1], net->panoptic_n[1], regions,
-                            batch, net->score_rows, net->score_cols, classes, NULL);
-}
-
-/* The half-width of the two boundary calls: d > 0 as given; d == 0 from ratio, for a uniform call mbn_boundary_d of the map size (*d_out), for
- * an image call every image's own, uploaded to net->boundary_d (*d_items; *d_out is not read by the ragged forms then) */
-static int boundary_half_width(mbn_net *net, double ratio, int d, int *d_out, const void **d_items)
-{
-    *d_out = d;
-    *d_items = NULL;
-    if (d < 0) return MBN_EINVAL;
-    if (d > 0) return MBN_OK;
-    if (net->score_kind == SCORE_UNIFORM) {
-        const int w = mbn_boundary_d(net->score_rows, net->score_cols, ratio);
-        if (w < 0) return w;
-        *d_out = w;
-        return MBN_OK;
-    }
-    int32_t *host = (int32_t *)malloc((size_t)net->max_batch * sizeof(int32_t));
-    if (!host) return MBN_ENOMEM;
-    int rc = mbn_boundary_d_items(net->readout, ratio, host);
-    if (rc == MBN_OK && !net->boundary_d) rc = mbn_alloc(net->ctx, (size_t)net->max_batch * sizeof(int32_t), &net->boundary_d);
-    if (rc == MBN_OK) rc = mbn_upload(net->ctx, net->boundary_d, host, (size_t)net->score_batch * sizeof(int32_t));
-    free(host);
-    *d_out = 1;
-    *d_items = net->boundary_d;
-    return rc;
-}
-
-int mbn_net_segment_boundary_score(mbn_net *net, const void *labels_i32, const void *truth, int truth_bytes, void *trimap_u64, void *biou_u64,
-                                   double ratio, int d, int edge)
-{
-    if (!net || net->score_kind == SCORE_NONE) return MBN_EINVAL;
-    const mbn_layer_desc *feat, *fc;
-    int rc = dense_layers(net, &feat, &fc);
-    if (rc != MBN_OK) return rc;
-    const void *d_items;
-    rc = boundary_half_width(net, ratio, d, &d, &d_items);
-    if (rc != MBN_OK) return rc;
-    if (net->score_kind == SCORE_RAGGED)
-        return mbn_boundary_score_ragged_i32(net->readout, trimap_u64, biou_u64, labels_i32, truth, truth_bytes, fc->out_ch, d, d_items, edge, NULL);
-    return mbn_boundary_score_i32(net->ctx, trimap_u64, biou_u64, labels_i32, truth, truth_bytes, fc->out_ch, net->score_batch, net->score_rows,
-                                  net->score_cols, d, edge, NULL);
-}
-
-int mbn_net_segment_boundary_depth(mbn_net *net, const void *labels_i32, void *depth_u8, double ratio, int d, int edge)
-{
-    if (!net || net->score_kind == SCORE_NONE) return MBN_EINVAL;
-    const void *d_items;
-    const int rc = boundary_half_width(net, ratio, d, &d, &d_items);
-    if (rc != MBN_OK) return rc;
-    if (net->score_kind == SCORE_RAGGED) return mbn_boundary_depth_ragged(net->readout, depth_u8, labels_i32, 4, d, d_items, edge, NULL);
-    return mbn_boundary_depth(net->ctx, depth_u8, labels_i32, 4, net->score_batch, net->score_rows, net->score_cols, d, edge, NULL);
 }
 
 int mbn_net_forward_timed(mbn_net *net, const void *images, void *logits, int batch, float *layer_ms, int n_layer_ms)

@@ -326,5 +326,5 @@ def big_tiles(m, n, cus):
 
 
 def net_block_fused_f32(count, out_rows, out_cols, out_ch, cus):
-    """block_fusable's few-tiles rule, host/mbn_net.c:407-411 (fp32, default mask)"""
+    """block_fusable's few-tiles rule, host/mbn_net.c:354-358 (fp32, default mask)"""
     return cdiv(count * out_rows * out_cols, 128) * cdiv(out_ch, 128) * 2 >= cus

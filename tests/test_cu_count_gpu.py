@@ -124,7 +124,7 @@ def test_planning_count_error_paths(pkg, ctx):
 
 def _net_expected_fused(orc, net, hw, n, cus):
     """The depthwise + pointwise blocks (first layer, 2) the fp32 runner fuses by default for n images at a count: those an explicit mask fuses
-    (inside the kernels' envelope), less the ones the few-tiles rule of block_fusable (host/mbn_net.c:407-411) leaves as two launches."""
+    (inside the kernels' envelope), less the ones the few-tiles rule of block_fusable (host/mbn_net.c:354-358) leaves as two launches."""
     is_block = lambda l: l[1] == 2 and hw.plan.layer[l[0] - 1].kind == orc.L_DW          # launches are 1-based
     net.set_fuse_blocks(net.get_fuse_blocks())
     forced = [l for l in net.launches(n) if is_block(l)]
