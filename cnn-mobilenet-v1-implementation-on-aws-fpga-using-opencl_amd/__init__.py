@@ -263,6 +263,11 @@ def _declare_host(lib):
     lib.mbn_confusion_envelope.argtypes = [C.c_int, C.c_int, C.c_int64]
     lib.mbn_confusion_form.argtypes = [C.c_int]
     lib.mbn_confusion_metrics.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.POINTER(SegMetrics), C.POINTER(C.c_double)]
+    lib.mbn_resample_topk_envelope.argtypes = [C.c_int] * 6 + [C.POINTER(C.c_int32)] + [C.c_int] * 3
+    lib.mbn_resample_topk_ragged_check.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int64]                        # mbn_envelope.h, like the next two
+    lib.mbn_topk_rank_envelope.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64]
+    lib.mbn_topk_rank_form.argtypes = [C.c_int, C.c_int]
+    lib.mbn_topk_metrics.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int] + [C.POINTER(C.c_double)] * 3
     lib.mbn_components_envelope.argtypes = [C.c_int] * 7
     lib.mbn_components_tile.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.mbn_components_scratch_bytes.argtypes = [C.c_int, C.c_int64]
@@ -434,6 +439,14 @@ def load():
         lib.mbn_confusion_i32.argtypes = [vp, vp, vp, vp, ci, ci, C.c_int64, vp]
         lib.mbn_confusion_ragged_i32.argtypes = [vp, vp, vp, vp, ci, ci, vp]
         lib.mbn_net_segment_score.argtypes = [vp, vp, vp, ci, vp]
+        lib.mbn_resample_topk_f32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(C.c_int32), ci, ci, ci, C.c_float, ci, vp]
+        lib.mbn_resample_topk_ragged_f32.argtypes = [vp, vp, vp, vp, vp, ci, C.c_int64, C.c_float, ci, vp]
+        lib.mbn_topk_rank_i32.argtypes = [vp, vp, vp, ci, C.c_int64, vp, ci, ci, C.c_int64, vp]
+        lib.mbn_topk_rank_ragged_i32.argtypes = [vp, vp, vp, ci, C.c_int64, vp, ci, ci, vp]
+        lib.mbn_net_segment_topk_fit.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, C.c_float, ci]
+        lib.mbn_net_segment_topk_images_fit.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, ci, ci, C.c_int64,
+                                                        vp, C.POINTER(C.c_int64), vp, vp, C.c_float, ci]
+        lib.mbn_net_segment_topk_score.argtypes = [vp, vp, vp, ci, vp]
         lib.mbn_components_create.argtypes = [vp, ci, C.c_int64, C.POINTER(vp)]
         lib.mbn_components_destroy.argtypes = [vp]
         lib.mbn_components_i32.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]
@@ -796,6 +809,43 @@ def confusion_metrics(counts, classes, lib=None):
     return m, iou
 
 
+TOPK_MAX = 8
+TOPK_MAX_ELEMENTS = 1 << 40
+
+
+def resample_topk_envelope(batch, rows, cols, classes, in_rows, in_cols, rect, out_rows, out_cols, k, lib=None) -> int:
+    """mbn_resample_topk_envelope: the status mbn_resample_topk_f32 gives the shape, the window rect = (x, y, iw, ih) (None: the whole map) and k."""
+    return (lib or host_lib()).mbn_resample_topk_envelope(batch, rows, cols, classes, in_rows, in_cols, None if rect is None else _rect(rect),
+                                                          out_rows, out_cols, k)
+
+
+def resample_topk_ragged_check(classes, span, k, plane_stride, lib=None) -> int:
+    """mbn_resample_topk_ragged_check: the status mbn_resample_topk_ragged_f32 gives k and plane_stride for a set that reaches `span` elements."""
+    return (lib or host_lib()).mbn_resample_topk_ragged_check(classes, span, k, plane_stride)
+
+
+def topk_rank_envelope(classes, truth_bytes, count, k, plane_stride, lib=None) -> int:
+    """mbn_topk_rank_envelope: the status (OK, EINVAL or EUNSUPPORTED) mbn_topk_rank_i32 gives the shape."""
+    return (lib or host_lib()).mbn_topk_rank_envelope(classes, truth_bytes, count, k, plane_stride)
+
+
+def topk_rank_form(classes, k, lib=None) -> int:
+    """mbn_topk_rank_form: CONFUSION_FORM_LDS (a workgroup counts in LDS) or CONFUSION_FORM_GLOBAL for a table of (classes + 1) x (k + 1)."""
+    return (lib or host_lib()).mbn_topk_rank_form(classes, k)
+
+
+def topk_metrics(ranks, classes, k, lib=None):
+    """mbn_topk_metrics: (accuracy float64 [k], mean_accuracy float64 [k], valid) of ranks, uint64 [classes + 1][k + 1]: top-1 .. top-k."""
+    n = np.ascontiguousarray(ranks, dtype=np.uint64)
+    if n.size != (classes + 1) * (k + 1):
+        raise ValueError("ranks has %d cells, classes = %d and k = %d need %d" % (n.size, classes, k, (classes + 1) * (k + 1)))
+    acc, mean, valid = np.empty(max(k, 1), np.float64), np.empty(max(k, 1), np.float64), C.c_double()
+    dp = C.POINTER(C.c_double)
+    _chk((lib or host_lib()).mbn_topk_metrics(n.ctypes.data_as(C.POINTER(C.c_uint64)), classes, k, acc.ctypes.data_as(dp), mean.ctypes.data_as(dp),
+                                              C.byref(valid)), "topk_metrics")
+    return acc, mean, valid.value
+
+
 COMPONENTS_MAX_REGIONS = 1 << 24
 
 
@@ -1111,6 +1161,24 @@ class Context:
         _chk(self.lib.mbn_resample_slide_f32(self.h, labels, prob, score, logits, batch, rows, cols, classes, C.byref(slide(plan)), out_rows, out_cols,
                                              min_prob, ignore_label, stream), self.last_error())
 
+    def resample_topk(self, labels, prob, score, logits, batch, rows, cols, classes, out_rows, out_cols, k, rect=None, in_rows=0, in_cols=0,
+                      min_prob=0.0, ignore_label=0, stream=None):
+        """mbn_resample_topk_f32: the k best classes of every output pixel, rank-major: labels (int32), prob and score (fp32) are
+        [k][batch][out_rows][out_cols], plane 0 the map of resample_softmax. rect = (x, y, iw, ih) of the in_rows x in_cols input, None: the whole
+        map. prob None with min_prob 0: the logit form. `score` may be None. min_prob / ignore_label act on plane 0 only."""
+        _chk(self.lib.mbn_resample_topk_f32(self.h, labels, prob, score, logits, batch, rows, cols, classes, in_rows, in_cols,
+                                            None if rect is None else _rect(rect), out_rows, out_cols, k, min_prob, ignore_label, stream),
+             self.last_error())
+
+    def topk_rank(self, ranks, labels, k, plane_stride, truth, truth_bytes, classes, count, stream=None):
+        """mbn_topk_rank_i32: ranks (uint64 [classes + 1][k + 1], device) += per truth row the rank at which the truth is among the k label planes
+        (plane j at labels + j * plane_stride elements); column k: in none of them, and every void pixel."""
+        _chk(self.lib.mbn_topk_rank_i32(self.h, ranks, labels, k, plane_stride, truth, truth_bytes, classes, count, stream), self.last_error())
+
+    def topk_rank_ragged(self, readout, ranks, labels, k, plane_stride, truth, truth_bytes, classes, stream=None):
+        """mbn_topk_rank_ragged_i32: the same over the maps of a RaggedReadout's set; truth at the labels' element offsets."""
+        _chk(self.lib.mbn_topk_rank_ragged_i32(readout.h, ranks, labels, k, plane_stride, truth, truth_bytes, classes, stream), self.last_error())
+
     def confusion(self, counts, labels, truth, truth_bytes, classes, count, stream=None):
         """mbn_confusion_i32: counts (uint64 [classes + 1][classes + 1], device) += the confusion matrix of `count` int32 labels against truth
         (uint8: truth_bytes 1, int32: 4); row = truth (row `classes`: void), column = label (column `classes`: abstained)."""
@@ -1255,6 +1323,12 @@ class RaggedReadout:
         either kind of set."""
         _chk(self.ctx.lib.mbn_resample_softmax_ragged_f32(self.h, labels_ptr, prob_ptr, score_ptr, logits_ptr, min_prob, ignore_label, stream),
              self.ctx.last_error())
+
+    def resample_topk(self, labels_ptr, prob_ptr, score_ptr, logits_ptr, k, plane_stride, min_prob=0.0, ignore_label=0, stream=None):
+        """mbn_resample_topk_ragged_f32: the k best classes of every pixel of the set's maps; rank j of item i at j * plane_stride + dst_offset_i
+        elements of labels / prob / score. After either kind of set. prob None with min_prob 0: the logit form."""
+        _chk(self.ctx.lib.mbn_resample_topk_ragged_f32(self.h, labels_ptr, prob_ptr, score_ptr, logits_ptr, k, plane_stride, min_prob, ignore_label,
+                                                       stream), self.ctx.last_error())
 
     def close(self):
         if self.h:
@@ -1505,6 +1579,28 @@ class Net:
                                                           (C.c_int32 * n)(*[int(v) for v in rows]), (C.c_int32 * n)(*[int(v) for v in cols]), n, fit,
                                                           labels_ptr, (C.c_int64 * n)(*[int(v) for v in dst_offsets]), prob_ptr, min_prob,
                                                           ignore_label), self.ctx.last_error())
+
+    def segment_topk_fit(self, src_ptr, batch, in_rows, in_cols, fit, k, labels_ptr, prob_ptr=None, score_ptr=None, min_prob=0.0, ignore_label=0):
+        """mbn_net_segment_topk_fit: segment_prob_fit with the top-k read-out (Context.resample_topk): labels, prob and score are rank-major
+        [k][batch][in_rows][in_cols], plane 0 the map of segment_prob_fit. prob None with min_prob 0: the logit form."""
+        _chk(self.ctx.lib.mbn_net_segment_topk_fit(self.h, src_ptr, batch, in_rows, in_cols, fit, k, labels_ptr, prob_ptr, score_ptr, min_prob,
+                                                   ignore_label), self.ctx.last_error())
+
+    def segment_topk_images_fit(self, src_ptr, offsets, rows, cols, fit, k, plane_stride, labels_ptr, dst_offsets, prob_ptr=None, score_ptr=None,
+                                min_prob=0.0, ignore_label=0):
+        """mbn_net_segment_topk_images_fit: segment_prob_images_fit with the top-k read-out; rank j of image i at j * plane_stride + dst_offsets[i]
+        elements of labels / prob / score."""
+        n = len(offsets)
+        assert len(rows) == n and len(cols) == n and len(dst_offsets) == n
+        _chk(self.ctx.lib.mbn_net_segment_topk_images_fit(self.h, src_ptr, (C.c_int64 * n)(*[int(v) for v in offsets]),
+                                                          (C.c_int32 * n)(*[int(v) for v in rows]), (C.c_int32 * n)(*[int(v) for v in cols]), n, fit, k,
+                                                          plane_stride, labels_ptr, (C.c_int64 * n)(*[int(v) for v in dst_offsets]), prob_ptr,
+                                                          score_ptr, min_prob, ignore_label), self.ctx.last_error())
+
+    def segment_topk_score(self, labels_ptr, truth_ptr, truth_bytes, ranks_ptr):
+        """mbn_net_segment_topk_score: ranks (uint64 [classes + 1][k + 1]) += the rank score of the k planes the most recent successful segment call
+        wrote (Context.topk_rank); raises EINVAL when that call was not a top-k call."""
+        _chk(self.ctx.lib.mbn_net_segment_topk_score(self.h, labels_ptr, truth_ptr, truth_bytes, ranks_ptr), self.ctx.last_error())
 
     def resize_views(self, src_ptr, batch, in_rows, in_cols, scales, mirrors) -> int:
         """mbn_net_resize_views: uint8 sources [batch][in_rows][in_cols][3] -> the net's staging buffer, view-major: view k = fit_view(scales[k],

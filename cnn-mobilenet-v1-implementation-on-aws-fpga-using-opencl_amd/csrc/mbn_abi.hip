@@ -1025,6 +1025,74 @@ int mbn_resample_softmax_ragged_f32(mbn_ragged_readout *r, void *labels_i32, voi
     return resample_ragged(r, labels_i32, score_f32, logits, stream, &q);
 }
 
+// The top-k read-outs: readout_call with the k rank-major planes as the outputs' span. No prob map and no threshold: the logit form (q = null; a NaN
+// threshold is not 0: the softmax check refuses it), the ensemble's convention
+int mbn_resample_topk_f32(mbn_context *ctx, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, int batch, int rows, int cols,
+                          int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols, int k, float min_prob,
+                          int ignore_label, void *stream)
+{
+    const mbn_readout_prob prob = { (float *)prob_f32, min_prob, ignore_label };
+    const mbn_readout_prob *q = prob_f32 || !(min_prob == 0.0f) ? &prob : nullptr;
+    const int shape = mbn_resample_topk_envelope(batch, rows, cols, classes, in_rows, in_cols, rect, out_rows, out_cols, k);
+    return readout_call(ctx, labels_i32, score_f32, logits, q, shape, 4.0 * batch * rows * cols * classes, 4.0 * k * batch * out_rows * out_cols, stream,
+                        [&](hipStream_t s) {
+                            return mbn_launch_f32_resample_topk(ctx, s, (int32_t *)labels_i32, (float *)score_f32, (const float *)logits, batch, rows,
+                                                                cols, classes, in_rows, in_cols, rect, out_rows, out_cols, k, q);
+                        });
+}
+
+int mbn_resample_topk_ragged_f32(mbn_ragged_readout *r, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, int k,
+                                 int64_t plane_stride, float min_prob, int ignore_label, void *stream)
+{
+    if (!r || r->batch <= 0) return MBN_EINVAL;                  // no set: nothing to launch
+    const mbn_readout_prob prob = { (float *)prob_f32, min_prob, ignore_label };
+    const mbn_readout_prob *q = prob_f32 || !(min_prob == 0.0f) ? &prob : nullptr;
+    const int shape = mbn_resample_topk_ragged_check(r->classes, r->launch.span, k, plane_stride);
+    const double out_bytes = shape == MBN_OK ? 4.0 * ((double)(k - 1) * (double)plane_stride + (double)r->launch.span) : 0.0;
+    return readout_call(r->ctx, labels_i32, score_f32, logits, q, shape, 4.0 * r->batch * r->rows * r->cols * r->classes, out_bytes, stream,
+                        [&](hipStream_t s) {
+                            return mbn_launch_f32_resample_topk_ragged(r, s, (int32_t *)labels_i32, (float *)score_f32, (const float *)logits, k,
+                                                                       plane_stride, q);
+                        });
+}
+
+// What the two rank-score calls share: confusion_call's checks with the rank table and the k label planes
+extern "C++" {
+template <typename Launch>
+static int topk_rank_call(mbn_context *ctx, void *ranks_u64, const void *labels_i32, int k, int64_t plane_stride, const void *truth, int truth_bytes,
+                          int classes, int64_t elements, void *stream, Launch launch)
+{
+    if (!ctx || !ranks_u64 || !labels_i32 || !truth) return MBN_EINVAL;
+    const int shape = mbn_topk_rank_envelope(classes, truth_bytes, elements, k, plane_stride);
+    if (shape == MBN_EINVAL) return shape;
+    if ((uintptr_t)ranks_u64 % 8 || (uintptr_t)labels_i32 % 4 || (truth_bytes == 4 && (uintptr_t)truth % 4)) return MBN_EINVAL;
+    if (shape != MBN_OK) return shape;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    MBN_SPANS(ctx, { ranks_u64, 8.0 * (classes + 1) * (k + 1), "topk_rank ranks" },
+              { labels_i32, 4.0 * ((double)(k - 1) * (double)plane_stride + (double)elements), "topk_rank labels" },
+              { truth, (double)truth_bytes * (double)elements, "topk_rank truth" });
+    Scope sc(ctx, s);
+    return sc.finish(launch(s));
+}
+}   // extern "C++"
+
+int mbn_topk_rank_i32(mbn_context *ctx, void *ranks_u64, const void *labels_i32, int k, int64_t plane_stride, const void *truth, int truth_bytes,
+                      int classes, int64_t count, void *stream)
+{
+    return topk_rank_call(ctx, ranks_u64, labels_i32, k, plane_stride, truth, truth_bytes, classes, count, stream, [&](hipStream_t s) {
+        return mbn_launch_i32_topk_rank(ctx, s, ranks_u64, labels_i32, k, plane_stride, truth, truth_bytes, classes, count);
+    });
+}
+
+int mbn_topk_rank_ragged_i32(mbn_ragged_readout *r, void *ranks_u64, const void *labels_i32, int k, int64_t plane_stride, const void *truth,
+                             int truth_bytes, int classes, void *stream)
+{
+    if (!r || r->batch <= 0) return MBN_EINVAL;                  // no set: nothing to score
+    return topk_rank_call(r->ctx, ranks_u64, labels_i32, k, plane_stride, truth, truth_bytes, classes, r->launch.span, stream, [&](hipStream_t s) {
+        return mbn_launch_i32_topk_rank_ragged(r, s, ranks_u64, labels_i32, k, plane_stride, truth, truth_bytes, classes);
+    });
+}
+
 // What the two confusion calls share: the pointer and alignment checks, the envelope, the spans (`elements` of labels and truth), the launch
 extern "C++" {
 template <typename Launch>

@@ -43,6 +43,8 @@
 // the same tile, stage pass, lerps, softmax sum and store; described where they stand, behind rs_launch.
 // SLIDE (mbn_resample_slide_f32; include/mbn.h, "segment by sliding window"): a grid of overlapping tiles read out as one map, the ensemble's sibling
 // on pieces of constant coverage; described where it stands, behind the ensemble.
+// TOPK (mbn_resample_topk_f32, _ragged_f32; include/mbn.h, "segment with runners-up"): the k best classes of every pixel, rank-major, kernels of
+// their own on the same tile; described where they stand, behind the slide.
 #include "mbn_internal.h"
 #include "mbn_device.h"
 #include "mbn_label_set.h"
@@ -727,7 +729,242 @@ typedef void (*SlideKernel)(const SlideArgs);
 const SlideKernel slide_kernels[2][2] = { { resample_slide_f32<false, false>, resample_slide_f32<true, false> },
                                           { resample_slide_f32<false, true>, resample_slide_f32<true, true> } };
 
+// ---- TOPK (mbn_resample_topk_f32, _ragged_f32; include/mbn.h, "segment with runners-up"): the k best classes of every output pixel with their
+// scores and probabilities, rank-major. Kernels of their own on resample_tile's tile: the same stage pass, coordinates, lerps, lazy-reference
+// softmax sum and store pattern. What differs:
+//   rule    one index / weight rule, the window's (rs_coord<true>), as in the ensemble: the whole map is the window that covers the whole input
+//           (include/mbn.h: bit-equal), so a null rectangle and a plain set travel as that window and there is no plain instantiation
+//   state   per row K slots (val, lab), sorted by value descending, instead of (best, label). K is a template CAPACITY: every loop over the slots
+//           is unrolled and the slots are indexed at compile time only, so they stay in registers (4 rows x K x 2 words). By the prefix property
+//           (the first k' slots of a capacity-K state are the k'-slot state) capacity K serves every k <= K and stores the first k slots
+//   compare per class and row ONE compare, against the last slot: the cost of the argmax compare. A class that passes is inserted by a chain of
+//           K selects from the bottom up (tk_insert): the rare, divergent path on real logits, the common one on an ascending ramp
+//   form    uniform and ragged are one kernel: a.head says which, and a.item_bytes which kind of item the set holds (uniform branches at the head)
+struct TopkArgs {
+    int *labels;
+    float *score, *prob;     // either may be null (prob: PROB instantiations only)
+    const float *logits;
+    int rows, cols, classes;
+    int out_rows, out_cols, tiles_x;      // uniform form
+    int fy, fx, ch;
+    int k;                   // the slots stored, 1 .. K
+    long long plane;         // elements from rank j to rank j + 1 of the three outputs
+    float min_prob;
+    int ignore_label;
+    int in_rows, in_cols;    // the network input the windows lie in (a plain set: rows, cols)
+    int wx, wy, wiw, wih;    // uniform form: the window
+    const mbn_label_set_head *head;       // ragged form, else null
+    int generation, item_bytes;
+};
+
+// v > val[K - 1] (the caller's compare): v goes to the smallest j with v > val[j] and the slots from there move down one. From the bottom up slot j
+// takes its upper neighbour's content when v belongs above it, v itself when v belongs exactly there; the strict compares keep equal values in
+// ascending class order and keep a NaN out
+template <int K>
+__device__ __forceinline__ void tk_insert(float (&val)[K], int (&lab)[K], float v, int c)
+{
+#pragma unroll
+    for (int j = K - 1; j > 0; j--) {
+        const bool above = v > val[j - 1], here = v > val[j];
+        val[j] = above ? val[j - 1] : here ? v : val[j];
+        lab[j] = above ? lab[j - 1] : here ? c : lab[j];
+    }
+    if (v > val[0]) { val[0] = v; lab[0] = c; }
+}
+
+// rs_reduce with the K slots in the place of (best, label); the same products and sums in the same order, the softmax sum by rs_softmax_group
+template <int K, bool CROSS, bool PROB>
+__device__ __forceinline__ void tk_reduce(const float *(&p)[3][2], int cn4, int c0, float wx0, float wx1, const float (&wy0)[RS_ROWS],
+                                          const float (&wy1)[RS_ROWS], const bool (&up)[RS_ROWS], float (&val)[RS_ROWS][K], int (&lab)[RS_ROWS][K],
+                                          float (&ref)[RS_ROWS], float (&sum)[RS_ROWS])
+{
+    constexpr int NT = CROSS ? 3 : 2;
+    for (int c = 0; c < cn4; c += 4) {
+        f4 v0[NT], v1[NT];
+        float vv[RS_ROWS][4];
+#pragma unroll
+        for (int j = 0; j < NT; j++) {
+            v0[j] = *reinterpret_cast<const f4 *>(p[j][0] + c);
+            v1[j] = *reinterpret_cast<const f4 *>(p[j][1] + c);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            float t[NT];
+#pragma unroll
+            for (int j = 0; j < NT; j++) t[j] = rs_lerp(v0[j][k], wx0, v1[j][k], wx1);      // horizontal first
+#pragma unroll
+            for (int r = 0; r < RS_ROWS; r++) {
+                const float ta = CROSS && up[r] ? t[1] : t[0], tb = CROSS && up[r] ? t[NT - 1] : t[1];
+                const float v = rs_lerp(ta, wy0[r], tb, wy1[r]);                            // then vertical
+                if (v > val[r][K - 1]) tk_insert<K>(val[r], lab[r], v, c0 + c + k);
+                if (PROB) vv[r][k] = v;
+            }
+        }
+        if (PROB) rs_softmax_group(vv, ref, sum);
+    }
+}
+
+template <int K, bool VEC, bool PROB>
+__global__ __launch_bounds__(256) void resample_topk_f32(const TopkArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_rs[];
+    const int tid = threadIdx.x;
+    // ---- this workgroup's image: its output size, its place in a plane, its windows and its tile
+    int H = a.out_rows, W = a.out_cols, tiles_x = a.tiles_x;
+    size_t dst = (size_t)blockIdx.y * ((size_t)a.out_rows * a.out_cols);                          // 64-bit bases, 32-bit offsets inside a map
+    RsWindow wy = { a.in_rows, a.wy, a.wih }, wx = { a.in_cols, a.wx, a.wiw };
+    if (a.head) {
+        // a replay of a captured launch after another set: the items are no longer the ones its grid, LDS and spans were checked for
+        if (a.head->generation != a.generation || (int)blockIdx.y >= a.head->batch) return;
+        const char *at = (const char *)(a.head + 1) + (size_t)blockIdx.y * a.item_bytes;
+        const mbn_label_item it = *(const mbn_label_item *)at;
+        H = it.rows; W = it.cols;
+        dst = (size_t)it.dst_offset;
+        tiles_x = (W + RS_TILE - 1) / RS_TILE;
+        if (a.item_bytes == (int)sizeof(mbn_label_window_item)) {
+            const mbn_label_window_item wi = *(const mbn_label_window_item *)at;
+            wy.b = wi.y; wy.l = wi.ih; wx.b = wi.x; wx.l = wi.iw;
+        }
+    }
+    const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
+    if (ty >= (H + RS_TILE - 1) / RS_TILE) return;                                              // ragged: past this image's tiles
+    const float *__restrict__ src = a.logits + (size_t)blockIdx.y * ((size_t)a.rows * a.cols * a.classes);
+
+    // ---- resample_tile's lane state under the window rule
+    const int ld = a.ch + 4, nv = a.fy * a.fx;
+    int ybase, xbase;
+    float unused;
+    rs_coord<true>(RS_TILE * ty, a.rows, H, wy, &ybase, &unused);
+    rs_coord<true>(RS_TILE * tx, a.cols, W, wx, &xbase, &unused);
+    const int ox = RS_TILE * tx + (tid & 31), oy0 = RS_TILE * ty + RS_ROWS * (tid >> 5);
+    const bool active = ox < W && oy0 < H;
+    int x0, ya = 0;
+    float wx1, wy1[RS_ROWS], wy0[RS_ROWS];
+    bool up[RS_ROWS];
+    rs_coord<true>(min(ox, W - 1), a.cols, W, wx, &x0, &wx1);
+    const float wx0 = 1.0f - wx1;
+#pragma unroll
+    for (int r = 0; r < RS_ROWS; r++) {
+        int r0;
+        rs_coord<true>(min(oy0 + r, H - 1), a.rows, H, wy, &r0, &wy1[r]);
+        wy0[r] = 1.0f - wy1[r];
+        if (r == 0) ya = r0;
+        up[r] = r0 != ya;                     // r0 is ya or ya + 1: four rows span less than one coarse row
+    }
+    const bool cross = __ballot(up[1] || up[2] || up[3]) != 0;
+    // inside the staged block by construction; the clamps keep every read inside the launch's LDS whatever the arguments
+    const int last_y = a.rows - 1, last_x = a.cols - 1;
+    const int sx0 = min(max(x0 - xbase, 0), a.fx - 1), sx1 = min(max(min(x0 + 1, last_x) - xbase, 0), a.fx - 1);
+    const float *p[3][2];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const int sy = min(max(min(ya + j, last_y) - ybase, 0), a.fy - 1);
+        p[j][0] = s_rs + (sy * a.fx + sx0) * ld;
+        p[j][1] = s_rs + (sy * a.fx + sx1) * ld;
+    }
+
+    float val[RS_ROWS][K], ref[RS_ROWS], sum[RS_ROWS];
+    int lab[RS_ROWS][K];
+#pragma unroll
+    for (int r = 0; r < RS_ROWS; r++) {
+        ref[r] = -__builtin_inff(); sum[r] = 0.0f;
+#pragma unroll
+        for (int j = 0; j < K; j++) { val[r][j] = -__builtin_inff(); lab[r][j] = -1; }     // unfilled, wherever an insertion moves it (rank 0: the store)
+    }
+
+    for (int c0 = 0; c0 < a.classes; c0 += a.ch) {
+        const int cn = min(a.ch, a.classes - c0), cn4 = (cn + 3) & ~3;
+        rs_stage<VEC>(s_rs, src, ybase, xbase, a.fx, nv, ld, a.cols, a.classes, last_y, last_x, c0, cn, cn4, tid);
+        __syncthreads();
+        if (active) {
+            if (cross) tk_reduce<K, true, PROB>(p, cn4, c0, wx0, wx1, wy0, wy1, up, val, lab, ref, sum);
+            else tk_reduce<K, false, PROB>(p, cn4, c0, wx0, wx1, wy0, wy1, up, val, lab, ref, sum);
+        }
+        __syncthreads();
+    }
+    if (!active) return;
+
+    // ---- store: rs_store's pattern, once per rank. Rank 0 is rs_store's own text on (val[0], lab[0]): the same prob bits, the same threshold
+    const unsigned out = (unsigned)(oy0 * W + ox);        // 32-bit inside an image: its map is below 2^31 bytes
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        if (j >= a.k) break;
+        int *__restrict__ labels = a.labels + (size_t)j * (size_t)a.plane + dst;
+        float *__restrict__ score = a.score ? a.score + (size_t)j * (size_t)a.plane + dst : nullptr;
+        float *__restrict__ prob = PROB && a.prob ? a.prob + (size_t)j * (size_t)a.plane + dst : nullptr;
+#pragma unroll
+        for (int r = 0; r < RS_ROWS; r++) {
+            if (oy0 + r >= H) break;
+            int l = lab[r][j];
+            if (j == 0 && !(val[r][0] > -__builtin_inff())) l = 0;                              // nothing won: the argmax rule's label 0
+            if (PROB) {
+                // a finite best has a finite ref <= best <= ref + RS_MARGIN and a sum >= 1; val[j] <= best; an unfilled slot (-inf) gives exp = 0
+                const float pr = __builtin_fabsf(val[r][0]) < __builtin_inff() ? rs_exp(val[r][j] - ref[r]) / sum[r] : 0.0f;
+                if (j == 0 && pr < a.min_prob) l = a.ignore_label;                              // plane 0 only; strict, on the value stored below
+                if (prob) prob[out + (unsigned)(r * W)] = pr;
+            }
+            labels[out + (unsigned)(r * W)] = l;
+            if (score) score[out + (unsigned)(r * W)] = val[r][j];
+        }
+    }
+}
+
+// the eight top-k kernels by [capacity 8 instead of 4][prob][vec]; k <= 4 takes capacity 4
+typedef void (*TopkKernel)(const TopkArgs);
+const TopkKernel topk_kernels[2][2][2] = {
+    { { resample_topk_f32<4, false, false>, resample_topk_f32<4, true, false> }, { resample_topk_f32<4, false, true>, resample_topk_f32<4, true, true> } },
+    { { resample_topk_f32<8, false, false>, resample_topk_f32<8, true, false> }, { resample_topk_f32<8, false, true>, resample_topk_f32<8, true, true> } },
+};
+
+void topk_launch(hipStream_t s, int batch, const mbn_resample_launch_t &l, TopkArgs &a, const float *logits, int rows, int cols, int classes, int k,
+                 int64_t plane, int32_t *labels, float *score, const mbn_readout_prob *q)
+{
+    a.labels = labels; a.score = score; a.logits = logits;
+    a.rows = rows; a.cols = cols; a.classes = classes;
+    a.fy = l.fy; a.fx = l.fx; a.ch = l.ch;
+    a.k = k; a.plane = plane;
+    if (q) { a.prob = q->prob; a.min_prob = q->min_prob; a.ignore_label = q->ignore_label; }
+    const bool vec = ((uintptr_t)logits % 16) == 0 && (classes % 4) == 0;
+    hipLaunchKernelGGL(topk_kernels[k > 4][q != nullptr][vec], dim3((unsigned)l.tiles, (unsigned)batch), dim3(256), (size_t)l.lds_bytes, s, a);
+}
+
 }   // namespace
+
+// rect = null: the whole map, the window (0, 0, cols, rows) of a rows x cols input. The shape is inside mbn_resample_topk_envelope and the pointers
+// are non-null multiples of 4 (the caller has checked both). q = null: the logit form, no exponential
+int mbn_launch_f32_resample_topk(mbn_context *, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows, int cols,
+                                 int classes, int in_rows, int in_cols, const int32_t *rect, int out_rows, int out_cols, int k,
+                                 const mbn_readout_prob *q)
+{
+    const int32_t full[4] = { 0, 0, cols, rows };
+    if (!rect) { rect = full; in_rows = rows; in_cols = cols; }
+    mbn_resample_launch_t l = { 0, 0, 0, 0, 0, 0 };
+    mbn_resample_window_plan(rows, cols, in_rows, in_cols, rect, out_rows, out_cols, &l);
+    TopkArgs a = {};
+    a.out_rows = out_rows; a.out_cols = out_cols;
+    a.tiles_x = (out_cols + RS_TILE - 1) / RS_TILE;
+    a.in_rows = in_rows; a.in_cols = in_cols;
+    a.wx = rect[0]; a.wy = rect[1]; a.wiw = rect[2]; a.wih = rect[3];
+    topk_launch(s, batch, l, a, logits, rows, cols, classes, k, (int64_t)batch * out_rows * out_cols, labels, score, q);
+    return MBN_OK;
+}
+
+// the handle has a batch, the pointers are non-null multiples of 4, plane_stride covers the set's span and the spans fit (the caller has checked)
+int mbn_launch_f32_resample_topk_ragged(mbn_ragged_readout *r, hipStream_t s, int32_t *labels, float *score, const float *logits, int k,
+                                        int64_t plane_stride, const mbn_readout_prob *q)
+{
+    TopkArgs a = {};
+    a.tiles_x = 1;                                              // unused: a workgroup takes its image's own
+    // a plain set's items are the full window of a rows x cols input (what its check planned them as)
+    a.in_rows = r->window ? r->in_rows : r->rows; a.in_cols = r->window ? r->in_cols : r->cols;
+    a.wx = 0; a.wy = 0; a.wiw = a.in_cols; a.wih = a.in_rows;
+    a.head = (const mbn_label_set_head *)r->dev;
+    a.generation = r->generation;
+    a.item_bytes = mbn_ragged_readout_item_bytes(r);
+    topk_launch(s, r->batch, r->launch, a, logits, r->rows, r->cols, r->classes, k, plane_stride, labels, score, q);
+    mbn_ragged_readout_mark_done(r, s);
+    return MBN_OK;
+}
 
 // The plan is inside mbn_resample_slide_envelope and the pointers are non-null multiples of 4 (the caller has checked both)
 int mbn_launch_f32_resample_slide(mbn_context *, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows, int cols,

@@ -363,6 +363,19 @@ int mbn_launch_f32_resample_ensemble(mbn_context *ctx, hipStream_t s, int32_t *l
 // the sliding-window read-out of a grid of tiles (logits [batch][ny * nx][rows][cols][classes]) inside mbn_resample_slide_envelope; q as above
 int mbn_launch_f32_resample_slide(mbn_context *ctx, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows, int cols,
                                   int classes, const mbn_slide *plan, int out_rows, int out_cols, const mbn_readout_prob *q);
+// the top-k read-out (mbn_resample_topk_*): labels / score / q->prob are rank-major, rank j at j * plane elements (uniform: plane = batch * out_rows
+// * out_cols; ragged: plane_stride). The shape is inside mbn_resample_topk_envelope / mbn_resample_topk_ragged_check; q = null: the logit form
+int mbn_launch_f32_resample_topk(mbn_context *ctx, hipStream_t s, int32_t *labels, float *score, const float *logits, int batch, int rows, int cols,
+                                 int classes, int in_rows, int in_cols, const int32_t *rect, int out_rows, int out_cols, int k,
+                                 const mbn_readout_prob *q);
+int mbn_launch_f32_resample_topk_ragged(mbn_ragged_readout *r, hipStream_t s, int32_t *labels, float *score, const float *logits, int k,
+                                        int64_t plane_stride, const mbn_readout_prob *q);
+// rank score (mbn_i32_topk_rank.hip): ranks [classes + 1][k + 1] uint64 += per truth row the rank at which the truth is among the k label planes
+// (plane j at j * plane_stride elements). The arguments are inside mbn_topk_rank_envelope and the pointers checked
+int mbn_launch_i32_topk_rank(mbn_context *ctx, hipStream_t s, void *ranks, const void *labels, int k, int64_t plane_stride, const void *truth,
+                             int truth_bytes, int classes, int64_t count);
+int mbn_launch_i32_topk_rank_ragged(mbn_ragged_readout *r, hipStream_t s, void *ranks, const void *labels, int k, int64_t plane_stride,
+                                    const void *truth, int truth_bytes, int classes);
 // score a segmentation (mbn_i32_confusion.hip): counts [classes + 1][classes + 1] uint64 += the confusion matrix of `count` labels against truth
 // (uint8 or int32). The arguments are inside mbn_confusion_envelope and the pointers checked; the ragged form scores the items of the handle's set
 int mbn_launch_i32_confusion(mbn_context *ctx, hipStream_t s, void *counts, const void *labels, const void *truth, int truth_bytes, int classes,

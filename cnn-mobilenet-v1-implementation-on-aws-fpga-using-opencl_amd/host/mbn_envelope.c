@@ -329,6 +329,28 @@ int mbn_resample_ragged_window_check(int rows, int cols, int classes, int in_row
     return ragged_check(rows, cols, classes, in_rows, in_cols, items, sizeof *items, batch, sort, l);
 }
 
+/* what the two top-k forms share: k against the classes, and the k planes against MBN_TOPK_MAX_ELEMENTS */
+static int topk_planes(int classes, int k, int64_t plane, int shape)
+{
+    if (k < 1 || k > MBN_TOPK_MAX || shape == MBN_EINVAL || k > classes) return MBN_EINVAL;
+    if (shape != MBN_OK) return shape;
+    return plane > MBN_TOPK_MAX_ELEMENTS / k ? MBN_EUNSUPPORTED : MBN_OK;
+}
+
+int mbn_resample_topk_envelope(int batch, int rows, int cols, int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows,
+                               int out_cols, int k)
+{
+    const int shape = rect ? mbn_resample_window_envelope(batch, rows, cols, classes, in_rows, in_cols, rect, out_rows, out_cols)
+                           : mbn_resample_argmax_envelope(batch, rows, cols, classes, out_rows, out_cols);
+    return topk_planes(classes, k, shape == MBN_OK ? (int64_t)batch * out_rows * out_cols : 0, shape);
+}
+
+int mbn_resample_topk_ragged_check(int classes, int64_t span, int k, int64_t plane_stride)
+{
+    if (classes < 1 || span < 1 || plane_stride < span) return MBN_EINVAL;
+    return topk_planes(classes, k, plane_stride, MBN_OK);
+}
+
 static long lmin(long a, long b) { return a < b ? a : b; }
 
 int mbn_i8_pw_plan(long m, int cin, int op_size, int num_cus, int operands_on_16, int out_f32, mbn_i8_pw_plan_t *p)

@@ -140,6 +140,23 @@ int mbn_slide_check(const mbn_slide *s, int out_rows, int out_cols);      /* the
 int mbn_resample_slide_envelope(int batch, int rows, int cols, int classes, const mbn_slide *s, int out_rows, int out_cols);
 int mbn_slide_cells(const int32_t *pos, int n, int tile, int32_t edge[MBN_SLIDE_MAX_CELLS + 1], int32_t pieces[MBN_SLIDE_MAX_CELLS + 1], int32_t *kmax);
 int mbn_resample_slide_plan(int rows, int cols, const mbn_slide *s, int out_rows, int out_cols, mbn_resample_launch_t *l);
+/* mbn_resample_topk_f32 (declared in mbn.h too): MBN_EINVAL for k outside 1..MBN_TOPK_MAX, k > classes and whatever the envelope of the same form
+ * calls MBN_EINVAL (rect given: mbn_resample_window_envelope, NULL: mbn_resample_argmax_envelope; in_rows and in_cols are not read then); else that
+ * envelope's MBN_EUNSUPPORTED; else MBN_EUNSUPPORTED when the k planes hold more than MBN_TOPK_MAX_ELEMENTS elements. The kernel reaches rank j of
+ * image i through a 64-bit element base j * plane + i * map and 32-bit offsets inside a map, so nothing narrower than the base limits the planes;
+ * 2^40 elements (4 TB an output, beyond any device) keeps k * plane inside int64 with room and every byte count of the span checks exact in a double.
+ * mbn_resample_topk_ragged_check: the ragged form's part, for a set that reaches `span` elements: MBN_EINVAL for plane_stride < span, k as above;
+ * MBN_EUNSUPPORTED for k * plane_stride above the same limit. The launch is the set's own (mbn_resample_window_plan / the handle's) */
+#define MBN_TOPK_MAX_ELEMENTS ((int64_t)1 << 40)
+int mbn_resample_topk_ragged_check(int classes, int64_t span, int k, int64_t plane_stride);
+/* rank score (mbn_i32_topk_rank.hip, host/mbn_score.c; mbn_topk_metrics is declared in mbn.h). mbn_topk_rank_envelope: MBN_EINVAL for k outside
+ * 1..MBN_TOPK_MAX, plane_stride < count or whatever mbn_confusion_envelope calls MBN_EINVAL, else its MBN_EUNSUPPORTED, and MBN_EUNSUPPORTED for
+ * k * plane_stride above MBN_TOPK_MAX_ELEMENTS. mbn_topk_rank_form: MBN_CONFUSION_FORM_LDS while a workgroup's table of (classes + 1) * (k + 1)
+ * 32-bit bins fits MBN_TOPK_RANK_LDS bytes (every class count of the envelope at every k: 4097 * 9 * 4 = 147 492 bytes would not, so the table
+ * is capped at 48 KB, which leaves three workgroups of 1024 lanes a CU's LDS: up to 1364 classes at k = 8), MBN_CONFUSION_FORM_GLOBAL above */
+#define MBN_TOPK_RANK_LDS (48 * 1024)
+int mbn_topk_rank_envelope(int classes, int truth_bytes, int64_t count, int k, int64_t plane_stride);
+int mbn_topk_rank_form(int classes, int k);
 /* score a segmentation (mbn_i32_confusion.hip, host/mbn_score.c; declared in mbn.h too). mbn_confusion_envelope: MBN_EINVAL for classes < 1,
  * count < 1 or truth_bytes other than 1 / 4, else MBN_EUNSUPPORTED for classes > MBN_CONFUSION_MAX_CLASSES or count > MBN_CONFUSION_MAX_COUNT.
  * mbn_confusion_form: MBN_CONFUSION_FORM_LDS while the workgroup's table of (classes + 1)^2 32-bit bins fits MBN_CONFUSION_LDS bytes of LDS,

@@ -11,6 +11,8 @@ struct mbn_seg_maps {
     int kind;                       /* MBN_SEG_NONE until a call succeeds; _UNIFORM: [batch][rows][cols]; _RAGGED: the maps of the net's read-out set */
     int batch, rows, cols, classes; /* rows = cols = 0 for a ragged set */
     int64_t count;                  /* the pixels of all maps */
+    int topk;                       /* 0, or the k of a top-k call: the maps are plane 0 of k rank-major planes, */
+    int64_t plane_stride;           /* this many elements apart */
 };
 
 /* the segmentation state of a net: everything here is made on first use and freed by mbn_net_seg_release */

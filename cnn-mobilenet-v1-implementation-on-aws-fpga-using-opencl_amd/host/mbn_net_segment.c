@@ -258,6 +258,8 @@ typedef struct seg_call {
     const float *scales;                                /* P_VIEWS: per view, with mirrors */
     int n_views;
     int tile[2], stride[2];                             /* P_SLIDE: rows, cols */
+    int topk;                                           /* P_FIT, P_IMAGES: 0, or the k of the top-k read-out: labels, score and prob hold k planes, */
+    int64_t plane_stride;                               /* for P_IMAGES this many elements apart */
 } seg_call;
 
 /* The net's read-out set from the items of an image call: each image's map at its own size, through its letterbox window under MBN_FIT_PAD. The set
@@ -355,8 +357,21 @@ static int segment_run(mbn_net *net, const seg_call *c)
             if (rc == MBN_OK) rc = mbn_resample_window_envelope(batch, h, w, classes, in_rows, in_cols, rect, rows, cols);
         } else if (mbn_resample_argmax_envelope(batch, h, w, classes, rows, cols) != MBN_OK)
             rc = MBN_EUNSUPPORTED;                                     /* every size is positive here: what the plain shape can miss is a limit */
+        if (rc == MBN_OK && c->topk) rc = mbn_resample_topk_envelope(batch, h, w, classes, in_rows, in_cols, rect, rows, cols, c->topk);
         break;
-    case P_IMAGES: rc = readout_set(net, c, feat, fc, &pixels); break;
+    case P_IMAGES:
+        if (c->topk) {
+            /* k and the plane stride against the span the set will have, in front of the set: a refused call leaves the handle's set as it was */
+            int64_t span = 1;
+            for (int i = 0; i < batch; i++) {
+                const int64_t end = c->dst_offsets[i] + (int64_t)c->rows_of[i] * c->cols_of[i];
+                if (end > span) span = end;
+            }
+            rc = mbn_resample_topk_ragged_check(classes, span, c->topk, c->plane_stride);
+            if (rc != MBN_OK) break;
+        }
+        rc = readout_set(net, c, feat, fc, &pixels);
+        break;
     case P_VIEWS:  rc = mbn_resample_ensemble_envelope(batch, h, w, classes, in_rows, in_cols, views, c->n_views, rows, cols); break;
     case P_SLIDE:  rc = mbn_resample_slide_envelope(batch, h, w, classes, &slide, rows, cols); break;
     }
@@ -379,8 +394,11 @@ static int segment_run(mbn_net *net, const seg_call *c)
     switch (c->path) {
     case P_INPUT:  rc = mbn_upsample_argmax_f32(net->ctx, c->labels, c->score, logits, batch, h, w, classes, factor, NULL); break;
     case P_IMAGES:
-        rc = q ? mbn_resample_softmax_ragged_f32(net->seg.readout, c->labels, prob, NULL, logits, min_prob, ignore, NULL)
-               : mbn_resample_argmax_ragged_f32(net->seg.readout, c->labels, c->score, logits, NULL);
+        if (c->topk)
+            rc = mbn_resample_topk_ragged_f32(net->seg.readout, c->labels, prob, c->score, logits, c->topk, c->plane_stride, min_prob, ignore, NULL);
+        else
+            rc = q ? mbn_resample_softmax_ragged_f32(net->seg.readout, c->labels, prob, NULL, logits, min_prob, ignore, NULL)
+                   : mbn_resample_argmax_ragged_f32(net->seg.readout, c->labels, c->score, logits, NULL);
         break;
     case P_VIEWS:
         rc = mbn_resample_ensemble_f32(net->ctx, c->labels, prob, c->score, logits, batch, h, w, classes, in_rows, in_cols, views, c->n_views, rows, cols,
@@ -390,7 +408,10 @@ static int segment_run(mbn_net *net, const seg_call *c)
         rc = mbn_resample_slide_f32(net->ctx, c->labels, prob, c->score, logits, batch, h, w, classes, &slide, rows, cols, min_prob, ignore, NULL);
         break;
     default:
-        if (q && rect)
+        if (c->topk)
+            rc = mbn_resample_topk_f32(net->ctx, c->labels, prob, c->score, logits, batch, h, w, classes, in_rows, in_cols, rect, rows, cols, c->topk,
+                                       min_prob, ignore, NULL);
+        else if (q && rect)
             rc = mbn_resample_softmax_window_f32(net->ctx, c->labels, prob, NULL, logits, batch, h, w, classes, in_rows, in_cols, rect, rows, cols,
                                                  min_prob, ignore, NULL);
         else if (q) rc = mbn_resample_softmax_f32(net->ctx, c->labels, prob, NULL, logits, batch, h, w, classes, rows, cols, min_prob, ignore, NULL);
@@ -401,7 +422,8 @@ static int segment_run(mbn_net *net, const seg_call *c)
     if (rc != MBN_OK) return rc;
     /* (5) the record */
     if (c->path != P_IMAGES) pixels = (int64_t)batch * rows * cols;    /* (an image call has rows = cols = 0, and the pixels of its items) */
-    net->seg.last = (struct mbn_seg_maps){ c->path == P_IMAGES ? MBN_SEG_RAGGED : MBN_SEG_UNIFORM, batch, rows, cols, classes, pixels };
+    net->seg.last = (struct mbn_seg_maps){ c->path == P_IMAGES ? MBN_SEG_RAGGED : MBN_SEG_UNIFORM, batch, rows, cols, classes, pixels, c->topk,
+                                           c->path == P_IMAGES ? c->plane_stride : pixels };
     return MBN_OK;
 }
 
@@ -463,6 +485,30 @@ int mbn_net_segment_prob_images_fit(mbn_net *net, const void *src_u8, const int6
     return segment_run(net, &c);
 }
 
+/* the two top-k calls: the _prob_fit / _prob_images_fit paths with the top-k read-out; k outside 1..MBN_TOPK_MAX is refused here, so that 0 never
+ * reads as "no top-k" */
+int mbn_net_segment_topk_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, int k, void *labels_i32, void *prob_f32,
+                             void *score_f32, float min_prob, int ignore_label)
+{
+    if (k < 1 || k > MBN_TOPK_MAX) return MBN_EINVAL;
+    const readout_prob given = { prob_f32, min_prob, ignore_label };
+    const seg_call c = { .path = P_FIT, .src = src_u8, .labels = labels_i32, .score = score_f32, .q = softmax_form(prob_f32, min_prob) ? &given : NULL,
+                         .batch = batch, .rows = in_rows, .cols = in_cols, .fit = fit, .topk = k };
+    return segment_run(net, &c);
+}
+
+int mbn_net_segment_topk_images_fit(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *in_rows, const int32_t *in_cols,
+                                    int batch, int fit, int k, int64_t plane_stride, void *labels_i32, const int64_t *dst_offsets, void *prob_f32,
+                                    void *score_f32, float min_prob, int ignore_label)
+{
+    if (k < 1 || k > MBN_TOPK_MAX) return MBN_EINVAL;
+    const readout_prob given = { prob_f32, min_prob, ignore_label };
+    const seg_call c = { .path = P_IMAGES, .src = src_u8, .labels = labels_i32, .score = score_f32, .q = softmax_form(prob_f32, min_prob) ? &given : NULL,
+                         .batch = batch, .fit = fit, .offsets = offsets, .dst_offsets = dst_offsets, .rows_of = in_rows, .cols_of = in_cols, .topk = k,
+                         .plane_stride = plane_stride };
+    return segment_run(net, &c);
+}
+
 int mbn_net_segment_views_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, const float *scales, const int32_t *mirrors,
                               int n_views, void *labels_i32, void *prob_f32, void *score_f32, float min_prob, int ignore_label)
 {
@@ -495,6 +541,15 @@ int mbn_net_segment_score(mbn_net *net, const void *labels_i32, const void *trut
     if (!m) return MBN_EINVAL;
     if (m->kind == MBN_SEG_RAGGED) return mbn_confusion_ragged_i32(net->seg.readout, counts_u64, labels_i32, truth, truth_bytes, m->classes, NULL);
     return mbn_confusion_i32(net->ctx, counts_u64, labels_i32, truth, truth_bytes, m->classes, m->count, NULL);
+}
+
+int mbn_net_segment_topk_score(mbn_net *net, const void *labels_i32, const void *truth, int truth_bytes, void *ranks_u64)
+{
+    const struct mbn_seg_maps *m = last_maps(net);
+    if (!m || !m->topk) return MBN_EINVAL;                             /* the last call wrote one plane: there are no ranks to score */
+    if (m->kind == MBN_SEG_RAGGED)
+        return mbn_topk_rank_ragged_i32(net->seg.readout, ranks_u64, labels_i32, m->topk, m->plane_stride, truth, truth_bytes, m->classes, NULL);
+    return mbn_topk_rank_i32(net->ctx, ranks_u64, labels_i32, m->topk, m->plane_stride, truth, truth_bytes, m->classes, m->count, NULL);
 }
 
 /* the net's one mbn_components handle holds at least the maps m */

@@ -68,3 +68,46 @@ int mbn_confusion_metrics(const uint64_t *counts, int classes, mbn_seg_metrics *
     m->reserved = 0;
     return MBN_OK;
 }
+
+/* ---- rank score (include/mbn.h, "rank score"): what mbn_topk_rank_i32 accepts, which form of the kernel a table takes, and the top-1 .. top-k
+ * accuracies of a rank table */
+int mbn_topk_rank_envelope(int classes, int truth_bytes, int64_t count, int k, int64_t plane_stride)
+{
+    const int shape = mbn_confusion_envelope(classes, truth_bytes, count);
+    if (k < 1 || k > MBN_TOPK_MAX || shape == MBN_EINVAL || plane_stride < count) return MBN_EINVAL;
+    if (shape != MBN_OK) return shape;
+    return plane_stride > MBN_TOPK_MAX_ELEMENTS / k ? MBN_EUNSUPPORTED : MBN_OK;
+}
+
+/* one switch point per k: the table of (classes + 1) * (k + 1) 32-bit bins fits MBN_TOPK_RANK_LDS */
+int mbn_topk_rank_form(int classes, int k)
+{
+    return ((int64_t)classes + 1) * (k + 1) * 4 <= MBN_TOPK_RANK_LDS ? MBN_CONFUSION_FORM_LDS : MBN_CONFUSION_FORM_GLOBAL;
+}
+
+int mbn_topk_metrics(const uint64_t *ranks, int classes, int k, double *accuracy, double *mean_accuracy, double *valid)
+{
+    if (!ranks || classes < 1 || k < 1 || k > MBN_TOPK_MAX) return MBN_EINVAL;
+    if (classes > MBN_CONFUSION_MAX_CLASSES) return MBN_EUNSUPPORTED;
+    const size_t stride = (size_t)k + 1;
+    /* sums of integers in doubles: exact below 2^53 */
+    double hits[MBN_TOPK_MAX] = { 0.0 }, acc[MBN_TOPK_MAX] = { 0.0 }, total = 0.0;
+    int have_truth = 0;
+    for (int t = 0; t < classes; t++) {
+        double row = 0.0, cum = 0.0;
+        for (size_t col = 0; col < stride; col++) row += (double)ranks[(size_t)t * stride + col];
+        total += row;
+        if (row > 0.0) have_truth++;
+        for (int j = 0; j < k; j++) {
+            cum += (double)ranks[(size_t)t * stride + (size_t)j];
+            hits[j] += cum;
+            if (row > 0.0) acc[j] += cum / row;                  /* ascending class order */
+        }
+    }
+    for (int j = 0; j < k; j++) {
+        if (accuracy) accuracy[j] = total > 0.0 ? hits[j] / total : 0.0;
+        if (mean_accuracy) mean_accuracy[j] = have_truth ? acc[j] / (double)have_truth : 0.0;
+    }
+    if (valid) *valid = total;
+    return MBN_OK;
+}

@@ -22,6 +22,11 @@
  *   floor(prob * 255 + 0.5) (mbn_net_segment_prob_fit / _images_fit); valid wherever --segment-source is, with or without it
  *   --min-confidence P --ignore-label L (together, with --segment-source; P in [0, 1], L in 0..65535): the pixels of that label map whose probability
  *   is below P hold L instead of their label
+ *   --segment-topk K (with ONE --ppm and --segment-source; 1 <= K <= 8): the K best classes of every pixel, mbn_net_segment_topk_fit. Rank 0 goes to
+ *   the --segment-source file as without it, rank j >= 1 to out.rank<j>.pgm beside it (a slot no class filled is written as the value `classes`);
+ *   with --segment-confidence conf.pgm every rank's probability likewise, conf.rank<j>.pgm; --min-confidence / --ignore-label act on rank 0 alone;
+ *   with --truth ONE line: topk: k=K valid=... top1_acc=... top1_mean_acc=... ... topK_acc=... topK_mean_acc=... (mbn_topk_metrics). Not with
+ *   --tta-scales, --slide, --regions, --panoptic or --boundary-*: usage status 2
  *   --tta-scales S1,S2,... [--tta-flip] (with ONE --ppm, --fit pad and --segment-source): test-time augmentation, mbn_net_segment_views_fit: the image
  *   is shown to the network at every scale (0 < S <= 1: the letterbox shrunk about the centre of the input), with --tta-flip also mirrored, and ONE
  *   read-out averages the views' logits. The views are (S1, plain), (S1, mirrored), (S2, plain), ... in that order, 8 at most (else usage status 2);
@@ -778,6 +783,89 @@ static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int
     return bad;
 }
 
+/* path with ".rank<j>" in front of its extension (out.pgm -> out.rank2.pgm; no extension: behind the name) */
+static void rank_path(char *out, size_t size, const char *path, int j)
+{
+    const char *slash = strrchr(path, '/'), *dot = strrchr(path, '.');
+    if (!dot || (slash && dot < slash)) dot = path + strlen(path);
+    snprintf(out, size, "%.*s.rank%d%s", (int)(dot - path), path, j, dot);
+}
+
+/* --segment-topk K (one --ppm, --fit stretch or pad, --segment-source): mbn_net_segment_topk_fit. Rank 0 goes to `path` as without it, rank j >= 1 to
+ * out.rank<j>.pgm beside it (an unfilled slot, label -1, is written as the value `classes` and counted apart); with conf_path every rank's probability
+ * map likewise; with a truth file ONE line with the top-1 .. top-K pixel accuracy and mean accuracy (mbn_net_segment_topk_score, mbn_topk_metrics).
+ * min_conf / ignore act on rank 0 only, as in segment_source */
+static int segment_source_topk(mbn_context *ctx, mbn_net *net, const char *ppm, const char *path, int classes, int fit, int k, const char *conf_path,
+                               float min_conf, int ignore, const char *truth)
+{
+    int pw = 0, ph = 0;
+    if (ppm_size(ppm, &pw, &ph) != MBN_OK || pw > PPM_MAX_SIDE || ph > PPM_MAX_SIDE) {
+        fprintf(stderr, "%s is not a readable P6 image of at most %d x %d pixels\n", ppm, PPM_MAX_SIDE, PPM_MAX_SIDE);
+        return 2;
+    }
+    const size_t pixels = (size_t)pw * ph;
+    unsigned char *src = malloc(pixels * 3);
+    int *labels = malloc(sizeof(int) * pixels * (size_t)k);
+    if (!src || !labels) return 1;
+    if (mbn_read_ppm(ppm, src, &pw, &ph, pw * ph) != MBN_OK) { fprintf(stderr, "cannot read %s\n", ppm); return 2; }
+    if (!(min_conf > 0.0f)) ignore = -1;                        /* --min-confidence 0 replaces nothing */
+    void *d_src, *d_labels, *d_prob = NULL;
+    CHECK(mbn_alloc(ctx, pixels * 3, &d_src));
+    CHECK(mbn_alloc(ctx, sizeof(int) * pixels * (size_t)k, &d_labels));
+    if (conf_path) CHECK(mbn_alloc(ctx, sizeof(float) * pixels * (size_t)k, &d_prob));
+    CHECK(mbn_upload(ctx, d_src, src, pixels * 3));
+    CHECK(mbn_net_segment_topk_fit(net, d_src, 1, ph, pw, fit, k, d_labels, d_prob, NULL, ignore >= 0 ? min_conf : 0.0f, ignore >= 0 ? ignore : 0));
+    if (truth) {
+        int32_t *tv = calloc(pixels, sizeof(int32_t));
+        const size_t cells = ((size_t)classes + 1) * ((size_t)k + 1);
+        uint64_t *ranks = malloc(cells * sizeof(uint64_t));
+        if (!tv || !ranks) return 1;
+        int wide = 0;
+        const int bad = read_truth_pgm(truth, pw, ph, tv, &wide);
+        if (bad) return bad;
+        void *d_truth, *d_ranks;
+        CHECK(mbn_alloc(ctx, pixels * sizeof(int32_t), &d_truth));
+        CHECK(mbn_alloc(ctx, cells * sizeof(uint64_t), &d_ranks));
+        CHECK(mbn_upload(ctx, d_truth, tv, pixels * sizeof(int32_t)));                        /* int32 truth either way: a byte value is itself */
+        CHECK(mbn_memset(ctx, d_ranks, 0, cells * sizeof(uint64_t)));
+        CHECK(mbn_net_segment_topk_score(net, d_labels, d_truth, 4, d_ranks));
+        CHECK(mbn_download(ctx, ranks, d_ranks, cells * sizeof(uint64_t)));
+        CHECK(mbn_free(ctx, d_truth));
+        CHECK(mbn_free(ctx, d_ranks));
+        double acc[MBN_TOPK_MAX], mean[MBN_TOPK_MAX], valid = 0.0;
+        CHECK(mbn_topk_metrics(ranks, classes, k, acc, mean, &valid));
+        printf("topk: k=%d valid=%.0f", k, valid);
+        for (int j = 0; j < k; j++) printf(" top%d_acc=%.17g top%d_mean_acc=%.17g", j + 1, acc[j], j + 1, mean[j]);
+        printf("\n");
+        free(tv); free(ranks);
+    }
+    CHECK(mbn_download(ctx, labels, d_labels, sizeof(int) * pixels * (size_t)k));
+    int bad = write_label_map(path, labels, ph, pw, classes, ignore, "below --min-confidence");
+    char name[4096];
+    for (int j = 1; j < k && !bad; j++) {
+        int *plane = labels + (size_t)j * pixels;
+        for (size_t i = 0; i < pixels; i++)
+            if (plane[i] < 0) plane[i] = classes;
+        rank_path(name, sizeof name, path, j);
+        bad = write_label_map(name, plane, ph, pw, classes, classes, "unfilled");
+    }
+    if (conf_path && !bad) {
+        float *prob = malloc(sizeof(float) * pixels * (size_t)k);
+        if (!prob) return 1;
+        CHECK(mbn_download(ctx, prob, d_prob, sizeof(float) * pixels * (size_t)k));
+        CHECK(mbn_free(ctx, d_prob));
+        for (int j = 0; j < k && !bad; j++) {
+            if (j) rank_path(name, sizeof name, conf_path, j);
+            bad = write_confidence_map(j ? name : conf_path, prob + (size_t)j * pixels, ph, pw);
+        }
+        free(prob);
+    }
+    CHECK(mbn_free(ctx, d_src));
+    CHECK(mbn_free(ctx, d_labels));
+    free(src); free(labels);
+    return bad;
+}
+
 /* --fit NAME: MBN_FIT_*, or -1 for an unknown name */
 static int fit_of(const char *name)
 {
@@ -851,7 +939,7 @@ int main(int argc, char **argv)
     int fit = MBN_FIT_CROP, filter = MBN_FILTER_BILINEAR;
     int pad_rgb[3] = { 0, 0, 0 }, src_h0 = 0, src_w0 = 0;              /* src_h0 x src_w0: image 0 as it was resized (0: it was not) */
     float crop_fraction = 1.0f, min_conf = 0.0f;
-    int have_min_conf = 0, have_ignore = 0, ignore_label = -1;
+    int have_min_conf = 0, have_ignore = 0, ignore_label = -1, have_topk = 0, segment_topk = 0;
     const char *tta = NULL, *slide_arg = NULL, *slide_stride_arg = NULL;
     int fit_given = 0, slide[4] = { 0, 0, 0, 0 }, slide_tiles = 0;      /* slide: tile rows, tile columns, stride rows, stride columns */
     region_opts regions = { 0, 4, 1, 256 };
@@ -883,6 +971,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--segment") && i + 1 < argc) segment = argv[++i];
         else if (!strcmp(argv[i], "--segment-source") && i + 1 < argc) segment_src = argv[++i];
         else if (!strcmp(argv[i], "--segment-confidence") && i + 1 < argc) segment_conf = argv[++i];
+        else if (!strcmp(argv[i], "--segment-topk") && i + 1 < argc) { segment_topk = atoi(argv[++i]); have_topk = 1; }
         else if (!strcmp(argv[i], "--min-confidence") && i + 1 < argc) { min_conf = (float)atof(argv[++i]); have_min_conf = 1; }
         else if (!strcmp(argv[i], "--ignore-label") && i + 1 < argc) { ignore_label = atoi(argv[++i]); have_ignore = 1; }
         else if (!strcmp(argv[i], "--tta-scales") && i + 1 < argc) tta = argv[++i];
@@ -915,7 +1004,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--literal")) literal = 1;
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
-            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]] [--slide TH[xTW] [--slide-stride SH[xSW]]] [--truth F.pgm ...] [--regions [--connectivity 4|8] [--min-area N] [--max-regions M]] [--boundary-ratio R | --boundary-d N [--boundary-edge 0|1] [--boundary-map OUT.pgm]] [--panoptic [--connectivity 4|8] [--min-area N]]] [--segment-confidence OUT.pgm] "
+            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--segment-topk K] [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]] [--slide TH[xTW] [--slide-stride SH[xSW]]] [--truth F.pgm ...] [--regions [--connectivity 4|8] [--min-area N] [--max-regions M]] [--boundary-ratio R | --boundary-d N [--boundary-edge 0|1] [--boundary-map OUT.pgm]] [--panoptic [--connectivity 4|8] [--min-area N]]] [--segment-confidence OUT.pgm] "
                             "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n", argv[0]);
             return 2;
         }
@@ -960,6 +1049,13 @@ int main(int argc, char **argv)
     }
     if (segment_conf && (n_ppm < 1 || (fit != MBN_FIT_STRETCH && fit != MBN_FIT_PAD))) {
         fprintf(stderr, "--segment-confidence needs --ppm and --fit stretch or --fit pad\n");
+        return 2;
+    }
+    if (have_topk && (!segment_src || n_ppm != 1 || segment_topk < 1 || segment_topk > MBN_TOPK_MAX || tta || tta_flip || slide_arg || regions.on ||
+                      panoptic.on || boundary.on || boundary.map)) {
+        fprintf(stderr, "--segment-topk K (1 <= K <= %d) needs one --ppm and --segment-source with --fit stretch or --fit pad; it goes with "
+                        "--segment-confidence, --min-confidence / --ignore-label and --truth, not with --tta-scales, --slide, --regions, --panoptic or "
+                        "--boundary-*\n", MBN_TOPK_MAX);
         return 2;
     }
     if (tta || tta_flip) {
@@ -1166,7 +1262,11 @@ int main(int argc, char **argv)
             printf("segment: image 0 is the %d x %d rectangle at (%d, %d) of the label map (wide x high, left, upper); the rest labels the border\n", rect[2],
                    rect[3], rect[0], rect[1]);
     }
-    if (segment_src || segment_conf) {
+    if (have_topk) {
+        const int bad = segment_source_topk(ctx, net, ppm, segment_src, classes, fit, segment_topk, segment_conf, min_conf, have_ignore ? ignore_label : -1,
+                                            n_truth ? truths[0] : NULL);
+        if (bad) return bad;
+    } else if (segment_src || segment_conf) {
         const int bad = segment_source(ctx, net, ppms, n_ppm, segment_src, classes, fit, segment_conf, min_conf, have_ignore ? ignore_label : -1,
                                        view_scales, view_mirrors, n_views, slide_tiles ? slide : NULL, truths, n_truth, &regions, &boundary, &panoptic);
         if (bad) return bad;

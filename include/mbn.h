@@ -565,6 +565,54 @@ int mbn_slide_axis(int size, int tile, int stride, int32_t *pos, int32_t *n);
 int mbn_slide_plan(int in_rows, int in_cols, int tile_rows, int tile_cols, int stride_rows, int stride_cols, mbn_slide *s);
 int mbn_resample_slide_f32(mbn_context *ctx, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, int batch, int rows, int cols,
                            int classes, const mbn_slide *s, int out_rows, int out_cols, float min_prob, int ignore_label, void *stream);
+/* Segment with runners-up: the read-out at any output size that gives the k best classes of every output pixel with their scores and softmax
+ * probabilities instead of the winner alone: the margin between first and second place, relabelling from a short list, "is the
+ * truth among the five best" (rank score, below). The dense counterpart of mbn_softmax_topk_f32. The tensor [out_rows][out_cols][classes] is never
+ * formed. Layout, RANK-MAJOR: labels_i32, prob_f32 and score_f32 are [k][batch][out_rows][out_cols]; plane 0 is, in shape and place, the
+ * [batch][out_rows][out_cols] map every later stage takes (mbn_confusion_i32, mbn_components_i32, the boundary and panoptic calls).
+ * Ragged form: rank j of item i is at j * plane_stride + dst_offset_i, plane_stride in ELEMENTS and at least the set's span
+ * max(dst_offset + rows * cols); nothing between the maps is written, in any plane.
+ * Normative (tests/dense_topk_ref.py reproduces it in numpy):
+ *   Interpolants. The v_c, c = 0 .. classes - 1, of an output pixel are exactly those of mbn_resample_argmax_window_f32 for `rect` (for a window
+ *     set: of its item's rectangle); for a NULL rect or a plain set those of mbn_resample_argmax_f32. The same index and weight rule, horizontal
+ *     first, every product and sum rounded on its own. (The kernel evaluates the window rule throughout: a NULL rect is the window (0, 0, cols,
+ *     rows) of a rows x cols input, which is mbn_resample_argmax_f32's rule bit for bit, see "segment through the letterbox".)
+ *   Selection. State: slots j = 0 .. k - 1, each (val_j, lab_j), every val = -inf. The classes are visited in ascending order. Class c enters iff
+ *     v_c > val_{k-1} (strict: a NaN never enters, -inf never enters). It goes to the smallest j with v_c > val_j, and slots j .. k - 2 move down
+ *     one. So the slots are sorted by value, descending, and equal values keep ascending class order. Slot 0 is exactly the argmax read-out's
+ *     (best, label), and the first k' slots of a call with k are the slots of a call with k' (PREFIX property).
+ *   Unfilled slots. A slot whose val is still -inf at the end stores score -inf and prob 0; its label is 0 at rank 0 (the argmax rule: plane 0
+ *     stays bit-equal to the argmax read-out) and -1 at ranks >= 1.
+ *   Probability. prob_j = e(val_j) / sum_c e(v_c), with e and the sum exactly as in "segment with confidence" (e(v) = exp(v - best), 0 for a NaN):
+ *     the same lazy-reference operations in the same order, so prob_0 has the bits mbn_resample_softmax_f32 writes. prob_j = 0 exactly when best
+ *     is not finite or slot j is unfilled. Elsewhere, against the float64 evaluation on the fp32 v_c,
+ *         |prob_j - ref_j| <= (classes + 200 + 2 * |val_j - best|) * 2^-24 * ref_j + 2^-125.
+ *     Derivation. The denominator and the division are those of prob_0: (classes + 200) * 2^-24 covers them, with the 123 units "segment with
+ *     confidence" spends on exponents whose argument is at most 16 in magnitude: 41 of them for the numerator exp(best - reference). Here the
+ *     numerator is exp2((val_j - reference) * log2(e)) with d = val_j - reference, |d| <= |val_j - best| + 16. The subtraction and the pre-multiply
+ *     each round once, an absolute error of at most |d| * 2^-24 (natural units; the factor log2(e) cancels against the ln 2 of exp2's derivative)
+ *     in the exponent each, which is a RELATIVE error of the numerator: 2 * |val_j - best| units on top of 2 * 16 = 32 of the 41 already counted
+ *     (the rest is exp's 2 ulp and slack). A numerator below 2^-126 may be flushed to 0 by the exponential; over a sum >= 1 that is an absolute
+ *     error below 2^-126, and one more halving of slack gives the 2^-125.
+ *   Threshold. min_prob and ignore_label act on PLANE 0 ONLY, exactly as in mbn_resample_softmax_f32: the stored label of rank 0 is ignore_label
+ *     iff the stored prob_0 < min_prob (strict). The planes >= 1, every prob and every score are written unchanged.
+ *   Logit form. prob_f32 = NULL with min_prob = 0: no exponential is evaluated (the ensemble's convention). score_f32 may be NULL.
+ * MBN_EINVAL: k outside 1..MBN_TOPK_MAX, k > classes, whatever the softmax call of the same form calls MBN_EINVAL (a NULL rect is no error here: it
+ * is the whole map), plane_stride below the set's span, a handle without a set, or an undersized tracked buffer (mbn_alloc's bounds rule: each
+ * output spans (k - 1) * plane + span elements, plane = batch * out_rows * out_cols or plane_stride). MBN_EUNSUPPORTED: outside the window (rect
+ * given) or argmax (NULL) envelope; and k * plane above 2^40 elements: the kernel reaches rank j of image i through a 64-bit element base
+ * j * plane + i * out_rows * out_cols and 32-bit offsets inside a map, so only that base limits the planes, and 2^40 keeps every byte count exact.
+ * Nothing is launched on a refusal. ONE kernel per call, which may be captured as one kernel node; the ragged form works after either kind of set
+ * and keeps the generation rule (a captured launch replayed after a later set writes nothing). mbn_resample_topk_envelope answers the shape part
+ * of the uniform form; pure host. */
+#define MBN_TOPK_MAX 8
+int mbn_resample_topk_f32(mbn_context *ctx, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, int batch, int rows, int cols,
+                          int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols, int k, float min_prob,
+                          int ignore_label, void *stream);
+int mbn_resample_topk_ragged_f32(mbn_ragged_readout *r, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, int k,
+                                 int64_t plane_stride, float min_prob, int ignore_label, void *stream);
+int mbn_resample_topk_envelope(int batch, int rows, int cols, int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows,
+                               int out_cols, int k);
 /* Score a segmentation: the confusion matrix of the label maps the read-outs above write against a ground truth, accumulated on the device, and
  * the standard metrics of such a matrix on the host. The dense counterpart of mbn_softmax_topk_f32.
  * Normative (tests/confusion_ref.py reproduces it in numpy; the arithmetic is integer, so every result is exact and does not depend on the order
@@ -611,6 +659,34 @@ int mbn_confusion_ragged_i32(mbn_ragged_readout *r, void *counts_u64, const void
 int mbn_confusion_envelope(int classes, int truth_bytes, int64_t count);
 int mbn_confusion_form(int classes);
 int mbn_confusion_metrics(const uint64_t *counts, int classes, mbn_seg_metrics *m, double *iou);
+/* Rank score: is the truth among the k best. The k rank-major label planes of mbn_resample_topk_f32 against a ground truth, accumulated on the
+ * device: the dense counterpart of top-5 accuracy. Normative (tests/dense_topk_ref.py has the numpy form; the arithmetic is integer,
+ * so the bytes are the same at every planning CU count, in both forms of the kernel and on graph replay):
+ *   ranks is uint64_t [classes + 1][k + 1], row-major, on 8 bytes; the calls ADD to it. The ROW is the truth by mbn_confusion_i32's rule: uint8
+ *     (truth_bytes = 1) or int32 (4), a value outside [0, classes) goes to row `classes`, VOID. Column j < k counts the pixels whose truth equals
+ *     the rank-j label, for the smallest such j; column k counts the rest, every void pixel included. A label outside [0, classes) (ignore_label,
+ *     the -1 of an unfilled slot) matches nothing. Every pixel adds 1 to exactly one cell: after any sequence of calls the cells sum to the pixels
+ *     scored, and column 0 of row t is the diagonal cell [t][t] of mbn_confusion_i32 on plane 0.
+ *   mbn_topk_rank_i32         `count` pixels: plane j is labels_i32 [j * plane_stride .. + count), plane_stride in ELEMENTS and at least count;
+ *                             truth [count]. labels_i32 any pointer on 4 bytes, a uint8 truth any byte pointer, an int32 truth any pointer on 4
+ *                             bytes. ONE kernel, asynchronous on `stream` (NULL: the context's), capturable as one kernel node; a persistent grid
+ *                             sized from the planning CU count
+ *   mbn_topk_rank_ragged_i32  the maps of a ragged set: item i's pixels are at dst_offset_i in every plane and in truth; plane_stride at least the
+ *                             set's span. After either kind of set; ONE kernel; it keeps the generation rule and the next set waits for it
+ * MBN_EINVAL: a NULL pointer, ranks_u64 off 8 bytes, labels_i32 off 4, an int32 truth off 4, k outside 1..MBN_TOPK_MAX, classes < 1, count < 1,
+ * truth_bytes not 1 or 4, plane_stride below count (the span), a handle without a set, or an undersized tracked buffer (ranks_u64 spans
+ * (classes + 1) * (k + 1) * 8 bytes, labels_i32 (k - 1) * plane_stride + count elements, truth count elements). MBN_EUNSUPPORTED: classes >
+ * MBN_CONFUSION_MAX_CLASSES, count > 2^34 or k * plane_stride > 2^40. Nothing is launched on a refusal.
+ *   mbn_topk_metrics          pure C in doubles, exact for counts below 2^53. n = ranks, C = classes: valid = the sum of the rows t < C;
+ *     accuracy[j] = sum over t < C and i <= j of n[t][i], over valid (0 when valid = 0): top-(j + 1) pixel accuracy; mean_accuracy[j] = the mean over
+ *     the classes with a non-empty row of (sum over i <= j of n[t][i]) / (the row's sum), in ascending class order (0 when there are none).
+ *     accuracy and mean_accuracy are [k] or NULL, valid may be NULL. MBN_EINVAL: NULL ranks, classes < 1, k outside 1..MBN_TOPK_MAX;
+ *     MBN_EUNSUPPORTED: classes > MBN_CONFUSION_MAX_CLASSES. */
+int mbn_topk_rank_i32(mbn_context *ctx, void *ranks_u64, const void *labels_i32, int k, int64_t plane_stride, const void *truth, int truth_bytes,
+                      int classes, int64_t count, void *stream);
+int mbn_topk_rank_ragged_i32(mbn_ragged_readout *r, void *ranks_u64, const void *labels_i32, int k, int64_t plane_stride, const void *truth,
+                             int truth_bytes, int classes, void *stream);
+int mbn_topk_metrics(const uint64_t *ranks, int classes, int k, double *accuracy, double *mean_accuracy, double *valid);
 /* Regions of a label map: connected-component labelling of the int32 maps the read-outs above write, on the device.
  * Normative (tests/components_ref.py is the numpy form; everything is integer, so the result is a function of the input alone: the same bytes at
  * every planning CU count, in both forms, on every run and on graph replay). For one image L [rows][cols] and classes >= 1:
@@ -1345,6 +1421,18 @@ int  mbn_net_segment_prob_fit(mbn_net *net, const void *src_u8, int batch, int i
                               float min_prob, int ignore_label);
 int  mbn_net_segment_prob_images_fit(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *rows, const int32_t *cols, int batch,
                                      int fit, void *labels_i32, const int64_t *dst_offsets, void *prob_f32, float min_prob, int ignore_label);
+/* Segment with runners-up (mbn_resample_topk_f32 above): mbn_net_segment_prob_fit / _prob_images_fit, step for step, with the top-k read-out, in every
+ * dtype those serve. labels_i32, prob_f32 and score_f32 are rank-major: [k][batch][in_rows][in_cols] for the uniform call; for the image call rank j
+ * of image i at j * plane_stride + dst_offsets[i] (plane_stride in elements, at least max(dst_offsets + rows * cols)). prob_f32 = NULL with
+ * min_prob = 0 is the logit form; score_f32 may be NULL. MBN_EINVAL: k outside 1..MBN_TOPK_MAX or above the plan's classes, plane_stride below the
+ * span, and what the prob calls refuse; a refused call changes nothing, the read-out set and the record included. Both are recorded as the net's
+ * most recent successful segment call: mbn_net_segment_score, _regions, _boundary_* and _panoptic then work on plane 0 (the first batch * in_rows *
+ * in_cols elements, or the image call's maps) unchanged, and mbn_net_segment_topk_score on all k planes. */
+int  mbn_net_segment_topk_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, int k, void *labels_i32, void *prob_f32,
+                              void *score_f32, float min_prob, int ignore_label);
+int  mbn_net_segment_topk_images_fit(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *rows, const int32_t *cols, int batch,
+                                     int fit, int k, int64_t plane_stride, void *labels_i32, const int64_t *dst_offsets, void *prob_f32,
+                                     void *score_f32, float min_prob, int ignore_label);
 /* Test-time augmentation through the letterbox (mbn_resample_ensemble_f32 above): view k is (scales[k], mirrors[k]) of mbn_fit_view into the plan's
  * rows x cols, n_views in 1..MBN_ENSEMBLE_MAX_VIEWS, batch * n_views <= max_batch.
  *   mbn_net_resize_views       src_u8 [batch][in_rows][in_cols][3] uint8 (device) -> the net's staging buffer, view-major: view k's `batch` canvases
@@ -1387,6 +1475,10 @@ int  mbn_net_segment_slide(mbn_net *net, const void *src_u8, int batch, int in_r
  * labels_i32 is the buffer that call wrote (or a copy of it). MBN_EINVAL before any such call; a refused segment call leaves the record of the
  * one before in place. Otherwise whatever the confusion call answers. */
 int  mbn_net_segment_score(mbn_net *net, const void *labels_i32, const void *truth, int truth_bytes, void *counts_u64);
+/* The rank score of the k planes of that same call ("rank score" above; found exactly as mbn_net_segment_score finds it): mbn_topk_rank_i32 for a
+ * uniform call, mbn_topk_rank_ragged_i32 on the net's own set for an image call, with the call's k and plane stride and the plan's classes;
+ * ranks_u64 [classes + 1][k + 1] is added to. MBN_EINVAL before any segment call and when the last one was not a top-k call. */
+int  mbn_net_segment_topk_score(mbn_net *net, const void *labels_i32, const void *truth, int truth_bytes, void *ranks_u64);
 /* The regions of the label maps of that same call ("regions of a label map" above; found exactly as mbn_net_segment_score finds it): a uniform
  * call is one mbn_components_i32 over [batch][out_rows][out_cols], an image call mbn_components_ragged_i32 on the net's own ragged set. classes is
  * the plan's. The net owns one mbn_components handle, sized for the call on first use, made again when a later call needs more, freed by

@@ -25,6 +25,10 @@
       mbn_resample_softmax_f32 / _window_f32 / _ragged_f32, the read-out with confidence (main_prob): each beside the argmax kernel of the same
       form on the same buffers, alternating in one process, and torch's three-pass interpolate(size=...).softmax(1).max(1).
 
+  python tools/dense_bench.py --topk [--reps 7] [--steps 20] [--batch 32] [--torch-steps 2] [--no-torch]
+      mbn_resample_topk_f32, the read-out with runners-up (main_topk): k = 1, 5, 8, with and without prob, on random logits and on the ascending
+      ramp (the worst case), beside the softmax and argmax kernels on the same buffers and torch's interpolate(...).softmax(1).topk(k).
+
   python tools/dense_bench.py --ensemble 1,2,3,6 [--reps 7] [--steps 20] [--batch 32] [--torch-steps 1] [--no-torch]
       mbn_resample_ensemble_f32, the fused multi-view read-out (main_ensemble): per view count K against the unchanged window kernel on one view,
       against K launches of it, and against torch's sum of K interpolate(...) then argmax / softmax(1).max(1), argmax and --prob forms alike.
@@ -331,6 +335,93 @@ def main_prob(a):
                                                       "torch_over_softmax": round(t / result["plain_from_%d" % hw_]["softmax"]["kernel_ms"], 2)})
                 print("torch three-pass from %d: %.2f ms" % (hw_, t), flush=True)
         rd.close()
+    print(json.dumps(result))
+
+
+def main_topk(a):
+    """--topk: the top-k read-out beside the softmax and argmax read-outs, 1000 classes, --batch images, to 375 x 500 from the 28 x 28 and the 14 x 14
+    map of a 224 x 224 input. Two kinds of logits: random (sigma 3; an insertion is rare) and the ascending ramp c / 4 over the classes with a
+    little noise on it (nearly every class is a new maximum, so nearly every class is inserted at rank 0: the worst case). Per shape and kind,
+    alternating within every repetition, on the same buffers:
+      softmax, argmax   mbn_resample_softmax_f32 / mbn_resample_argmax_f32: at k = 1 the same arithmetic
+      topk k prob       mbn_resample_topk_f32 with labels, score and prob, k = 1, 5, 8 (capacity 4, 8, 8)
+      topk k logit      the same without prob: no exponential
+      torch             the yardstick, random logits only: interpolate(size=(375, 500)).softmax(1).topk(k) on the same buffer, in slices of 8 images
+    Each figure is the median over the repetitions of `steps` back-to-back calls between two stream marks; the spread is (max - min) / median of a
+    name's own repetitions."""
+    pkg = import_package()
+    torch = None
+    if not a.no_torch:
+        import torch
+        assert torch.cuda.is_available(), "the yardstick needs torch on the same GPU"
+    n, rng = a.batch, np.random.default_rng(0)
+    H, W, KS = 375, 500, (1, 5, 8)
+    result = {"batch": n, "ks": list(KS)}
+    with pkg.Context(0) as ctx:
+        npix = n * H * W
+        d_lab, d_sc, d_pr = ctx.alloc(8 * npix * 4), ctx.alloc(8 * npix * 4), ctx.alloc(8 * npix * 4)
+        for hw_ in (28, 14):
+            for kind in ("random", "ramp"):
+                if kind == "random":
+                    x = (3.0 * rng.standard_normal((n, hw_, hw_, CLASSES))).astype(np.float32)
+                else:
+                    x = (0.25 * np.arange(CLASSES, dtype=np.float32) + 0.01 * rng.standard_normal((n, hw_, hw_, CLASSES))).astype(np.float32)
+                if torch is not None:
+                    t = torch.from_numpy(x).cuda()
+                    p, keep = t.data_ptr(), t
+                else:
+                    keep = ctx.to_device(x)
+                    p = keep.ptr
+                runs = [("softmax", lambda: ctx.resample_softmax(d_lab.ptr, d_pr.ptr, d_sc.ptr, p, n, hw_, hw_, CLASSES, H, W)),
+                        ("argmax", lambda: ctx.resample_argmax(d_lab.ptr, d_sc.ptr, p, n, hw_, hw_, CLASSES, H, W))]
+                for k in KS:
+                    runs.append(("topk%d_prob" % k, lambda k=k: ctx.resample_topk(d_lab.ptr, d_pr.ptr, d_sc.ptr, p, n, hw_, hw_, CLASSES, H, W, k)))
+                    runs.append(("topk%d_logit" % k, lambda k=k: ctx.resample_topk(d_lab.ptr, None, d_sc.ptr, p, n, hw_, hw_, CLASSES, H, W, k)))
+                times = {name: [] for name, _ in runs}
+                t_times = {k: [] for k in KS}
+                for _, f in runs:
+                    marks_ms(ctx, f, 2)
+                for _ in range(a.reps):
+                    for name, f in runs:
+                        times[name].append(marks_ms(ctx, f, a.steps))
+                    for k in KS if torch is not None and kind == "random" else ():
+                        ctx.sync()
+                        nchw = keep.permute(0, 3, 1, 2)
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+                        def passes():
+                            for i in range(0, n, 8):
+                                torch.nn.functional.interpolate(nchw[i:i + 8], size=(H, W), mode="bilinear", align_corners=False).softmax(1).topk(k, dim=1)
+                        passes()
+                        e0.record()
+                        for _ in range(a.torch_steps):
+                            passes()
+                        e1.record()
+                        torch.cuda.synchronize()
+                        t_times[k].append(e0.elapsed_time(e1) / a.torch_steps)
+                out = {}
+                for name, _ in runs:
+                    ts = times[name]
+                    m = statistics.median(ts)
+                    out[name] = {"kernel_ms": round(m, 4), "kernel_runs_ms": [round(v, 4) for v in ts], "spread": round((max(ts) - min(ts)) / m, 4)}
+                for k in KS:
+                    out["topk%d_prob" % k]["over_softmax"] = round(out["topk%d_prob" % k]["kernel_ms"] / out["softmax"]["kernel_ms"], 3)
+                    out["topk%d_logit" % k]["over_argmax"] = round(out["topk%d_logit" % k]["kernel_ms"] / out["argmax"]["kernel_ms"], 3)
+                    if t_times[k]:
+                        t = statistics.median(t_times[k])
+                        out["torch_topk%d" % k] = {"torch_ms": round(t, 4), "torch_runs_ms": [round(v, 4) for v in t_times[k]],
+                                                   "torch_over_topk_prob": round(t / out["topk%d_prob" % k]["kernel_ms"], 2)}
+                result["%s_from_%d" % (kind, hw_)] = out
+                print("%s from %d: softmax %.4f ms (spread %.1f %%), argmax %.4f ms (spread %.1f %%)"
+                      % (kind, hw_, out["softmax"]["kernel_ms"], 100 * out["softmax"]["spread"], out["argmax"]["kernel_ms"], 100 * out["argmax"]["spread"]))
+                for k in KS:
+                    pr_, lg = out["topk%d_prob" % k], out["topk%d_logit" % k]
+                    print("    k %d: prob %.4f ms (spread %.1f %%, %.3f x softmax)  logit %.4f ms (spread %.1f %%, %.3f x argmax)%s"
+                          % (k, pr_["kernel_ms"], 100 * pr_["spread"], pr_["over_softmax"], lg["kernel_ms"], 100 * lg["spread"], lg["over_argmax"],
+                             "  torch %.2f ms" % out["torch_topk%d" % k]["torch_ms"] if "torch_topk%d" % k in out else ""), flush=True)
+                if torch is None:
+                    keep.free()
+                del keep
     print(json.dumps(result))
 
 
@@ -1073,6 +1164,7 @@ def main():
     ap.add_argument("--torch-steps", type=int, default=2, help="--any: torch calls per repetition (each writes batch x 1000 x 375 x 500 floats)")
     ap.add_argument("--fit", default="stretch", choices=("stretch", "pad"), help="--any: pad times the window kernel instead: see main_any_pad")
     ap.add_argument("--prob", action="store_true", help="--any: time the softmax read-out beside the argmax read-out instead: see main_prob")
+    ap.add_argument("--topk", action="store_true", help="time mbn_resample_topk_f32 beside the softmax and argmax read-outs instead: see main_topk")
     ap.add_argument("--ensemble", default="", help="comma list of view counts: time mbn_resample_ensemble_f32 instead: see main_ensemble")
     ap.add_argument("--slide", action="store_true", help="time mbn_resample_slide_f32 (the sliding-window read-out) instead: see main_slide")
     ap.add_argument("--torch-images", type=int, default=2, help="--slide: the source images the torch yardstick really works on (scaled to the batch)")
@@ -1095,6 +1187,8 @@ def main():
         return main_ensemble(a)
     if a.slide:
         return main_slide(a)
+    if a.topk:
+        return main_topk(a)
     if a.any and a.prob:
         return main_prob(a)
     if a.any:
