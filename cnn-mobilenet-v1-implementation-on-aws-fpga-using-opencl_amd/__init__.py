@@ -143,6 +143,11 @@ class SegMetrics(C.Structure):
                 ("classes_present", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Calibration(C.Structure):
+    """mbn_calibration (include/mbn.h, "calibration score")"""
+    _fields_ = [(n, C.c_double) for n in ("pixels", "answered", "abstained", "void_pixels", "accuracy", "mean_confidence", "ece", "mce", "aurc")]
+
+
 class PanopticMetrics(C.Structure):
     """mbn_panoptic_metrics_t (include/mbn.h, "score a segmentation by its regions")"""
     _fields_ = [(n, C.c_double) for n in ("pq", "sq", "rq", "tp", "fp", "fn")] + [("classes_present", C.c_int32), ("reserved", C.c_int32)]
@@ -268,6 +273,9 @@ def _declare_host(lib):
     lib.mbn_topk_rank_envelope.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64]
     lib.mbn_topk_rank_form.argtypes = [C.c_int, C.c_int]
     lib.mbn_topk_metrics.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int] + [C.POINTER(C.c_double)] * 3
+    lib.mbn_calibration_envelope.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64]
+    lib.mbn_calibration_metrics.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.POINTER(Calibration)] + [C.POINTER(C.c_double)] * 4
+    lib.mbn_calibration_threshold.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_double, C.POINTER(C.c_float)] + [C.POINTER(C.c_double)] * 2
     lib.mbn_components_envelope.argtypes = [C.c_int] * 7
     lib.mbn_components_tile.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.mbn_components_scratch_bytes.argtypes = [C.c_int, C.c_int64]
@@ -443,6 +451,9 @@ def load():
         lib.mbn_resample_topk_ragged_f32.argtypes = [vp, vp, vp, vp, vp, ci, C.c_int64, C.c_float, ci, vp]
         lib.mbn_topk_rank_i32.argtypes = [vp, vp, vp, ci, C.c_int64, vp, ci, ci, C.c_int64, vp]
         lib.mbn_topk_rank_ragged_i32.argtypes = [vp, vp, vp, ci, C.c_int64, vp, ci, ci, vp]
+        lib.mbn_calibration_f32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, C.c_int64, vp]
+        lib.mbn_calibration_ragged_f32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, vp]
+        lib.mbn_net_segment_calibration.argtypes = [vp, vp, vp, vp, ci, ci, vp]
         lib.mbn_net_segment_topk_fit.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, C.c_float, ci]
         lib.mbn_net_segment_topk_images_fit.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, ci, ci, C.c_int64,
                                                         vp, C.POINTER(C.c_int64), vp, vp, C.c_float, ci]
@@ -846,6 +857,46 @@ def topk_metrics(ranks, classes, k, lib=None):
     return acc, mean, valid.value
 
 
+CALIBRATION_MAX_BINS = 1024
+CALIBRATION_ONE = 1 << 24           # the fixed point of a table's confidence column
+
+
+def calibration_envelope(classes, truth_bytes, bins, count, lib=None) -> int:
+    """mbn_calibration_envelope: the status (OK, EINVAL or EUNSUPPORTED) mbn_calibration_f32 gives the shape."""
+    return (lib or host_lib()).mbn_calibration_envelope(classes, truth_bytes, bins, count)
+
+
+def _calibration_table(calib, bins):
+    n = np.ascontiguousarray(calib, dtype=np.uint64)
+    if n.size != (bins + 1) * 4:
+        raise ValueError("calib has %d cells, bins = %d needs %d" % (n.size, bins, (bins + 1) * 4))
+    return n
+
+
+def calibration_metrics(calib, bins, lib=None):
+    """mbn_calibration_metrics: (Calibration, accuracy, confidence, coverage, selective_accuracy), each array float64 [bins], of calib, uint64
+    [bins + 1][4]: the reliability diagram (NaN for an empty bin), ECE / MCE, and the risk-coverage curve of keeping the bins >= j with its AURC."""
+    n = _calibration_table(calib, bins)
+    m, out = Calibration(), [np.empty(max(bins, 1), np.float64) for _ in range(4)]
+    dp = C.POINTER(C.c_double)
+    _chk((lib or host_lib()).mbn_calibration_metrics(n.ctypes.data_as(C.POINTER(C.c_uint64)), bins, C.byref(m),
+                                                     *[a.ctypes.data_as(dp) for a in out]), "calibration_metrics")
+    return (m, *out)
+
+
+def calibration_threshold(calib, bins, target_accuracy, lib=None):
+    """mbn_calibration_threshold: (min_prob, coverage, selective_accuracy) of the smallest edge j / bins whose kept pixels reach target_accuracy;
+    None when no edge does (MBN_ENOTFOUND)."""
+    n = _calibration_table(calib, bins)
+    p, cov, sel = C.c_float(), C.c_double(), C.c_double()
+    rc = (lib or host_lib()).mbn_calibration_threshold(n.ctypes.data_as(C.POINTER(C.c_uint64)), bins, target_accuracy, C.byref(p), C.byref(cov),
+                                                       C.byref(sel))
+    if rc == ENOTFOUND:
+        return None
+    _chk(rc, "calibration_threshold")
+    return p.value, cov.value, sel.value
+
+
 COMPONENTS_MAX_REGIONS = 1 << 24
 
 
@@ -1178,6 +1229,15 @@ class Context:
     def topk_rank_ragged(self, readout, ranks, labels, k, plane_stride, truth, truth_bytes, classes, stream=None):
         """mbn_topk_rank_ragged_i32: the same over the maps of a RaggedReadout's set; truth at the labels' element offsets."""
         _chk(self.lib.mbn_topk_rank_ragged_i32(readout.h, ranks, labels, k, plane_stride, truth, truth_bytes, classes, stream), self.last_error())
+
+    def calibration(self, calib, labels, prob, truth, truth_bytes, classes, bins, count, stream=None):
+        """mbn_calibration_f32: calib (uint64 [bins + 1][4], device) += per probability bin the pixels answered, answered correctly, their
+        probabilities in 2^-24 fixed point and the pixels abstained, of `count` int32 labels and fp32 probabilities against truth (uint8 or int32)."""
+        _chk(self.lib.mbn_calibration_f32(self.h, calib, labels, prob, truth, truth_bytes, classes, bins, count, stream), self.last_error())
+
+    def calibration_ragged(self, readout, calib, labels, prob, truth, truth_bytes, classes, bins, stream=None):
+        """mbn_calibration_ragged_f32: the same over the maps of a RaggedReadout's set; prob and truth at the labels' element offsets."""
+        _chk(self.lib.mbn_calibration_ragged_f32(readout.h, calib, labels, prob, truth, truth_bytes, classes, bins, stream), self.last_error())
 
     def confusion(self, counts, labels, truth, truth_bytes, classes, count, stream=None):
         """mbn_confusion_i32: counts (uint64 [classes + 1][classes + 1], device) += the confusion matrix of `count` int32 labels against truth
@@ -1601,6 +1661,11 @@ class Net:
         """mbn_net_segment_topk_score: ranks (uint64 [classes + 1][k + 1]) += the rank score of the k planes the most recent successful segment call
         wrote (Context.topk_rank); raises EINVAL when that call was not a top-k call."""
         _chk(self.ctx.lib.mbn_net_segment_topk_score(self.h, labels_ptr, truth_ptr, truth_bytes, ranks_ptr), self.ctx.last_error())
+
+    def segment_calibration(self, labels_ptr, prob_ptr, truth_ptr, truth_bytes, bins, calib_ptr):
+        """mbn_net_segment_calibration: calib (uint64 [bins + 1][4]) += the calibration table of the maps and probabilities the most recent successful
+        segment call wrote (Context.calibration; the net's own set after an image call), with the plan's classes."""
+        _chk(self.ctx.lib.mbn_net_segment_calibration(self.h, labels_ptr, prob_ptr, truth_ptr, truth_bytes, bins, calib_ptr), self.ctx.last_error())
 
     def resize_views(self, src_ptr, batch, in_rows, in_cols, scales, mirrors) -> int:
         """mbn_net_resize_views: uint8 sources [batch][in_rows][in_cols][3] -> the net's staging buffer, view-major: view k = fit_view(scales[k],

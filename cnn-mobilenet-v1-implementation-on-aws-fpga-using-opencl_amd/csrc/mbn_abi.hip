@@ -1093,6 +1093,42 @@ int mbn_topk_rank_ragged_i32(mbn_ragged_readout *r, void *ranks_u64, const void 
     });
 }
 
+// What the two calibration calls share: confusion_call's checks with the table of bins and the probability map beside the labels
+extern "C++" {
+template <typename Launch>
+static int calibration_call(mbn_context *ctx, void *calib_u64, const void *labels_i32, const void *prob_f32, const void *truth, int truth_bytes,
+                            int classes, int bins, int64_t elements, void *stream, Launch launch)
+{
+    if (!ctx || !calib_u64 || !labels_i32 || !prob_f32 || !truth) return MBN_EINVAL;
+    const int shape = mbn_calibration_envelope(classes, truth_bytes, bins, elements);
+    if (shape == MBN_EINVAL) return shape;
+    if ((uintptr_t)calib_u64 % 8 || (uintptr_t)labels_i32 % 4 || (uintptr_t)prob_f32 % 4 || (truth_bytes == 4 && (uintptr_t)truth % 4)) return MBN_EINVAL;
+    if (shape != MBN_OK) return shape;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    MBN_SPANS(ctx, { calib_u64, 32.0 * (bins + 1), "calibration table" }, { labels_i32, 4.0 * (double)elements, "calibration labels" },
+              { prob_f32, 4.0 * (double)elements, "calibration prob" }, { truth, (double)truth_bytes * (double)elements, "calibration truth" });
+    Scope sc(ctx, s);
+    return sc.finish(launch(s));
+}
+}   // extern "C++"
+
+int mbn_calibration_f32(mbn_context *ctx, void *calib_u64, const void *labels_i32, const void *prob_f32, const void *truth, int truth_bytes,
+                        int classes, int bins, int64_t count, void *stream)
+{
+    return calibration_call(ctx, calib_u64, labels_i32, prob_f32, truth, truth_bytes, classes, bins, count, stream, [&](hipStream_t s) {
+        return mbn_launch_f32_calibration(ctx, s, calib_u64, labels_i32, prob_f32, truth, truth_bytes, classes, bins, count);
+    });
+}
+
+int mbn_calibration_ragged_f32(mbn_ragged_readout *r, void *calib_u64, const void *labels_i32, const void *prob_f32, const void *truth,
+                               int truth_bytes, int classes, int bins, void *stream)
+{
+    if (!r || r->batch <= 0) return MBN_EINVAL;                  // no set: nothing to score
+    return calibration_call(r->ctx, calib_u64, labels_i32, prob_f32, truth, truth_bytes, classes, bins, r->launch.span, stream, [&](hipStream_t s) {
+        return mbn_launch_f32_calibration_ragged(r, s, calib_u64, labels_i32, prob_f32, truth, truth_bytes, classes, bins);
+    });
+}
+
 // What the two confusion calls share: the pointer and alignment checks, the envelope, the spans (`elements` of labels and truth), the launch
 extern "C++" {
 template <typename Launch>

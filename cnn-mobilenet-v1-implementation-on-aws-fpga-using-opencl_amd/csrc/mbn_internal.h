@@ -376,6 +376,13 @@ int mbn_launch_i32_topk_rank(mbn_context *ctx, hipStream_t s, void *ranks, const
                              int truth_bytes, int classes, int64_t count);
 int mbn_launch_i32_topk_rank_ragged(mbn_ragged_readout *r, hipStream_t s, void *ranks, const void *labels, int k, int64_t plane_stride,
                                     const void *truth, int truth_bytes, int classes);
+// calibration score (mbn_f32_calibration.hip): calib [bins + 1][4] uint64 += per probability bin the pixels answered, answered correctly, their
+// probabilities in 2^-24 fixed point and the pixels abstained; row `bins` the void pixels. The arguments are inside mbn_calibration_envelope and
+// the pointers checked; the ragged form scores the items of the handle's set
+int mbn_launch_f32_calibration(mbn_context *ctx, hipStream_t s, void *calib, const void *labels, const void *prob, const void *truth, int truth_bytes,
+                               int classes, int bins, int64_t count);
+int mbn_launch_f32_calibration_ragged(mbn_ragged_readout *r, hipStream_t s, void *calib, const void *labels, const void *prob, const void *truth,
+                                      int truth_bytes, int classes, int bins);
 // score a segmentation (mbn_i32_confusion.hip): counts [classes + 1][classes + 1] uint64 += the confusion matrix of `count` labels against truth
 // (uint8 or int32). The arguments are inside mbn_confusion_envelope and the pointers checked; the ragged form scores the items of the handle's set
 int mbn_launch_i32_confusion(mbn_context *ctx, hipStream_t s, void *counts, const void *labels, const void *truth, int truth_bytes, int classes,

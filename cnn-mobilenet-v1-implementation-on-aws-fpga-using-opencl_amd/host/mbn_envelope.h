@@ -157,6 +157,10 @@ int mbn_resample_topk_ragged_check(int classes, int64_t span, int k, int64_t pla
 #define MBN_TOPK_RANK_LDS (48 * 1024)
 int mbn_topk_rank_envelope(int classes, int truth_bytes, int64_t count, int k, int64_t plane_stride);
 int mbn_topk_rank_form(int classes, int k);
+/* calibration score (mbn_f32_calibration.hip, host/mbn_score.c; declared in mbn.h too). mbn_calibration_envelope: MBN_EINVAL for bins < 1 or
+ * whatever mbn_confusion_envelope calls MBN_EINVAL, else its MBN_EUNSUPPORTED, and MBN_EUNSUPPORTED for bins > MBN_CALIBRATION_MAX_BINS. One form:
+ * a workgroup's table of (bins + 1) * 4 64-bit cells is at most 32 800 bytes of LDS */
+int mbn_calibration_envelope(int classes, int truth_bytes, int bins, int64_t count);
 /* score a segmentation (mbn_i32_confusion.hip, host/mbn_score.c; declared in mbn.h too). mbn_confusion_envelope: MBN_EINVAL for classes < 1,
  * count < 1 or truth_bytes other than 1 / 4, else MBN_EUNSUPPORTED for classes > MBN_CONFUSION_MAX_CLASSES or count > MBN_CONFUSION_MAX_COUNT.
  * mbn_confusion_form: MBN_CONFUSION_FORM_LDS while the workgroup's table of (classes + 1)^2 32-bit bins fits MBN_CONFUSION_LDS bytes of LDS,

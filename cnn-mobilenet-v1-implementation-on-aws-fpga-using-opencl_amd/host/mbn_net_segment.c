@@ -552,6 +552,16 @@ int mbn_net_segment_topk_score(mbn_net *net, const void *labels_i32, const void 
     return mbn_topk_rank_i32(net->ctx, ranks_u64, labels_i32, m->topk, m->plane_stride, truth, truth_bytes, m->classes, m->count, NULL);
 }
 
+int mbn_net_segment_calibration(mbn_net *net, const void *labels_i32, const void *prob_f32, const void *truth, int truth_bytes, int bins,
+                                void *calib_u64)
+{
+    const struct mbn_seg_maps *m = last_maps(net);
+    if (!m) return MBN_EINVAL;
+    if (m->kind == MBN_SEG_RAGGED)
+        return mbn_calibration_ragged_f32(net->seg.readout, calib_u64, labels_i32, prob_f32, truth, truth_bytes, m->classes, bins, NULL);
+    return mbn_calibration_f32(net->ctx, calib_u64, labels_i32, prob_f32, truth, truth_bytes, m->classes, bins, m->count, NULL);
+}
+
 /* the net's one mbn_components handle holds at least the maps m */
 static int components_ready(mbn_net *net, const struct mbn_seg_maps *m)
 {

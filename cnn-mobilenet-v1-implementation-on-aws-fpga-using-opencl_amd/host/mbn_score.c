@@ -1,6 +1,7 @@
 /*
  * mbn_score.c — the host side of "score a segmentation" (include/mbn.h): what mbn_confusion_i32 accepts, which form of the kernel a class count
- * takes, and the standard metrics of a confusion matrix. Pure C, no HIP: libmbn_host.so carries it.
+ * takes, and the standard metrics of a confusion matrix; the same for the rank score and the calibration score. Pure C, no HIP: libmbn_host.so
+ * carries it.
  */
 #include <math.h>
 #include <stddef.h>
@@ -110,4 +111,104 @@ int mbn_topk_metrics(const uint64_t *ranks, int classes, int k, double *accuracy
     }
     if (valid) *valid = total;
     return MBN_OK;
+}
+
+/* ---- calibration score (include/mbn.h, "calibration score"): what mbn_calibration_f32 accepts, and the reliability diagram, the expected
+ * calibration error and the risk-coverage curve of a table */
+int mbn_calibration_envelope(int classes, int truth_bytes, int bins, int64_t count)
+{
+    const int shape = mbn_confusion_envelope(classes, truth_bytes, count);
+    if (bins < 1 || shape == MBN_EINVAL) return MBN_EINVAL;
+    if (shape != MBN_OK) return shape;
+    return bins > MBN_CALIBRATION_MAX_BINS ? MBN_EUNSUPPORTED : MBN_OK;
+}
+
+static int calibration_table_check(const uint64_t *calib, int bins)
+{
+    if (!calib || bins < 1) return MBN_EINVAL;
+    return bins > MBN_CALIBRATION_MAX_BINS ? MBN_EUNSUPPORTED : MBN_OK;
+}
+
+/* cell (b, col) as a double: exact below 2^53 */
+static double calibration_cell(const uint64_t *calib, int b, int col) { return (double)calib[(size_t)b * 4 + (size_t)col]; }
+
+int mbn_calibration_metrics(const uint64_t *calib, int bins, mbn_calibration *m, double *accuracy, double *confidence, double *coverage,
+                            double *selective_accuracy)
+{
+    const int rc = calibration_table_check(calib, bins);
+    if (rc != MBN_OK || !m) return rc != MBN_OK ? rc : MBN_EINVAL;
+    const double one = 16777216.0;                                  /* 2^24: the fixed point of column 2 */
+    /* sums of integers in doubles: exact below 2^53 */
+    double answered = 0.0, right = 0.0, conf = 0.0, abstained = 0.0;
+    for (int b = 0; b < bins; b++) {
+        answered += calibration_cell(calib, b, 0);
+        right += calibration_cell(calib, b, 1);
+        conf += calibration_cell(calib, b, 2);
+        abstained += calibration_cell(calib, b, 3);
+    }
+    double ece = 0.0, mce = 0.0;
+    for (int b = 0; b < bins; b++) {                                /* ascending bin order */
+        const double n = calibration_cell(calib, b, 0);
+        const double acc = n > 0.0 ? calibration_cell(calib, b, 1) / n : (double)NAN;
+        const double cf = n > 0.0 ? calibration_cell(calib, b, 2) / (n * one) : (double)NAN;
+        if (accuracy) accuracy[b] = acc;
+        if (confidence) confidence[b] = cf;
+        if (n > 0.0) {
+            const double gap = fabs(acc - cf);
+            ece += (n / answered) * gap;
+            if (gap > mce) mce = gap;
+        }
+    }
+    /* the curve of keeping the bins >= j, from the last edge down; aurc sums its terms in ascending j, so they are kept first */
+    const double asked = answered + abstained;
+    double kept = 0.0, kept_right = 0.0, aurc = 0.0, next = 0.0;
+    double term[MBN_CALIBRATION_MAX_BINS];
+    for (int j = bins - 1; j >= 0; j--) {
+        kept += calibration_cell(calib, j, 0);
+        kept_right += calibration_cell(calib, j, 1);
+        const double cov = asked > 0.0 ? kept / asked : 0.0;
+        const double sel = kept > 0.0 ? kept_right / kept : (double)NAN;
+        if (coverage) coverage[j] = cov;
+        if (selective_accuracy) selective_accuracy[j] = sel;
+        term[j] = kept > 0.0 ? (1.0 - sel) * (cov - next) : 0.0;    /* an empty term is skipped */
+        next = cov;
+    }
+    for (int j = 0; j < bins; j++) aurc += term[j];
+    m->answered = answered;
+    m->abstained = abstained;
+    m->void_pixels = calibration_cell(calib, bins, 0);
+    m->pixels = answered + abstained + m->void_pixels;
+    m->accuracy = answered > 0.0 ? right / answered : 0.0;
+    m->mean_confidence = answered > 0.0 ? conf / (answered * one) : 0.0;
+    m->ece = ece;
+    m->mce = mce;
+    m->aurc = aurc;
+    return MBN_OK;
+}
+
+int mbn_calibration_threshold(const uint64_t *calib, int bins, double target_accuracy, float *min_prob, double *coverage,
+                              double *selective_accuracy)
+{
+    const int rc = calibration_table_check(calib, bins);
+    if (rc != MBN_OK) return rc;
+    if (!(target_accuracy >= 0.0 && target_accuracy <= 1.0)) return MBN_EINVAL;
+    double answered = 0.0, abstained = 0.0, right = 0.0;
+    for (int b = 0; b < bins; b++) {
+        answered += calibration_cell(calib, b, 0);
+        right += calibration_cell(calib, b, 1);
+        abstained += calibration_cell(calib, b, 3);
+    }
+    /* kept / kept_right at edge j are the sums over b >= j: the totals less the bins in front, exact integers */
+    double kept = answered, kept_right = right;
+    for (int j = 0; j < bins; j++) {
+        if (kept > 0.0 && kept_right / kept >= target_accuracy) {
+            if (min_prob) *min_prob = (float)j / (float)bins;
+            if (coverage) *coverage = kept / (answered + abstained);
+            if (selective_accuracy) *selective_accuracy = kept_right / kept;
+            return MBN_OK;
+        }
+        kept -= calibration_cell(calib, j, 0);
+        kept_right -= calibration_cell(calib, j, 1);
+    }
+    return MBN_ENOTFOUND;
 }

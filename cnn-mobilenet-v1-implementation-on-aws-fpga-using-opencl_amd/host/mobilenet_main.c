@@ -41,6 +41,14 @@
  *   itself writes, int32 truth, so a label map this tool wrote can be fed back. The label maps are scored on the device (mbn_net_segment_score: a value
  *   outside the classes is void in the truth and abstained in the labels, --ignore-label among them) and ONE line is printed:
  *   score: pixels=... valid=... void=... abstained=... classes_present=... pixel_acc=... mean_acc=... miou=... fw_iou=... (mbn_confusion_metrics, %.17g)
+ *   --calibration BINS [--target-accuracy A] (with --segment-source, --segment-confidence and --truth; 1 <= BINS <= 1024, 0 <= A <= 1; else usage
+ *   status 2): is the probability worth anything. The reliability table of the same maps and their probabilities, accumulated on the device
+ *   (mbn_net_segment_calibration), and ONE line behind the score line (with --segment-topk: behind the topk line, for rank 0):
+ *   calibration: bins=... answered=... abstained=... void=... accuracy=... mean_confidence=... ece=... mce=... aurc=...   (mbn_calibration_metrics)
+ *   and with --target-accuracy, on the same line, the smallest --min-confidence whose kept pixels reach that accuracy (mbn_calibration_threshold):
+ *   min_confidence=... coverage=... selective_accuracy=...  (min_confidence=none when no threshold of the table reaches it). With
+ *   --min-confidence P > 0 the thresholded labels are what is scored: the pixels below P are in the abstained count and in no bin's accuracy.
+ *   Works with --segment-topk, --tta-* and --slide like the other scores
  *   --regions [--connectivity 4|8] [--min-area N] [--max-regions M] (with --segment-source; defaults 4, 1, 256): the connected regions of every label
  *   map, found on the device (mbn_net_segment_regions). Per image one line `regions: image <n> count <k>` (k is the true count, even above M), then
  *   for each of its first min(k, M) regions `region <i> class <c> area <a> box <r0> <c0> <r1> <c1>` (rows first, both corners inside the box), in
@@ -585,10 +593,44 @@ static int score_panoptic(mbn_context *ctx, mbn_net *net, const panoptic_opts *p
     return 0;
 }
 
+/* --calibration BINS [--target-accuracy A]: what the command line asked for; bins = 0: nothing (like g_streams, set once by main) */
+static struct { int bins, have_target; double target; } g_calibration = { 0, 0, 0.0 };
+
+/* --truth with --calibration: the reliability table of the same maps and their probabilities at d_prob (mbn_net_segment_calibration), ONE line */
+static int score_calibration(mbn_context *ctx, mbn_net *net, void *d_labels, void *d_prob, void *d_truth, int tb)
+{
+    const int bins = g_calibration.bins;
+    const size_t bytes = ((size_t)bins + 1) * 4 * sizeof(uint64_t);
+    uint64_t *calib = malloc(bytes);
+    if (!calib) return 1;
+    void *d_calib;
+    CHECK(mbn_alloc(ctx, bytes, &d_calib));
+    CHECK(mbn_memset(ctx, d_calib, 0, bytes));
+    CHECK(mbn_net_segment_calibration(net, d_labels, d_prob, d_truth, tb, bins, d_calib));
+    CHECK(mbn_download(ctx, calib, d_calib, bytes));
+    CHECK(mbn_free(ctx, d_calib));
+    mbn_calibration m;
+    CHECK(mbn_calibration_metrics(calib, bins, &m, NULL, NULL, NULL, NULL));
+    printf("calibration: bins=%d answered=%.0f abstained=%.0f void=%.0f accuracy=%.17g mean_confidence=%.17g ece=%.17g mce=%.17g aurc=%.17g", bins,
+           m.answered, m.abstained, m.void_pixels, m.accuracy, m.mean_confidence, m.ece, m.mce, m.aurc);
+    if (g_calibration.have_target) {
+        float min_prob = 0.0f;
+        double coverage = 0.0, selective = 0.0;
+        const int rc = mbn_calibration_threshold(calib, bins, g_calibration.target, &min_prob, &coverage, &selective);
+        if (rc == MBN_OK) printf(" min_confidence=%.9g coverage=%.17g selective_accuracy=%.17g", (double)min_prob, coverage, selective);
+        else if (rc == MBN_ENOTFOUND) printf(" min_confidence=none coverage=0 selective_accuracy=nan");      /* no edge reaches the target */
+        else CHECK(rc);
+    }
+    printf("\n");
+    free(calib);
+    return 0;
+}
+
 /* --truth: scores the label maps the segment call just wrote at d_labels (image n at element dst[n]) against the files, and prints the line;
- * bo->on: the boundary lines behind it; po->on: the panoptic lines behind those */
+ * --calibration (d_prob: the probabilities of the same call): the calibration line behind it; bo->on: the boundary lines behind that; po->on: the
+ * panoptic lines behind those */
 static int score_truth(mbn_context *ctx, mbn_net *net, const char **truths, int n, const int64_t *dst, const int32_t *hs, const int32_t *ws, size_t pixels,
-                       void *d_labels, int classes, const boundary_opts *bo, const panoptic_opts *po)
+                       void *d_labels, void *d_prob, int classes, const boundary_opts *bo, const panoptic_opts *po)
 {
     int32_t *tv = calloc(pixels, sizeof(int32_t));
     if (!tv) return 1;
@@ -622,6 +664,10 @@ static int score_truth(mbn_context *ctx, mbn_net *net, const char **truths, int 
     CHECK(mbn_confusion_metrics(counts, classes, &m, iou));
     printf("score: pixels=%.0f valid=%.0f void=%.0f abstained=%.0f classes_present=%d pixel_acc=%.17g mean_acc=%.17g miou=%.17g fw_iou=%.17g\n", m.pixels,
            m.valid, m.void_pixels, m.abstained, m.classes_present, m.pixel_accuracy, m.mean_accuracy, m.miou, m.fw_iou);
+    if (g_calibration.bins) {
+        const int bad = score_calibration(ctx, net, d_labels, d_prob, d_truth, tb);
+        if (bad) return bad;
+    }
     if (bo->on) {
         const int bad = score_boundary(ctx, net, bo, d_labels, d_truth, tb, classes, hs[0], ws[0]);
         if (bad) return bad;
@@ -760,7 +806,7 @@ static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int
     }
     CHECK(mbn_download(ctx, labels, d_maps, sizeof(int) * (size_t)hs[0] * ws[0]));        /* image 0 is first in the buffer */
     if (n_truth > 0) {                                          /* the maps are where every path above wrote them: image n at element dst[n] */
-        bad = score_truth(ctx, net, truths, n_truth, dst, hs, ws, pixels, d_maps, classes, bo, po);
+        bad = score_truth(ctx, net, truths, n_truth, dst, hs, ws, pixels, d_maps, d_prob, classes, bo, po);
         if (bad) return bad;
     }
     if (bo->map) {
@@ -830,13 +876,17 @@ static int segment_source_topk(mbn_context *ctx, mbn_net *net, const char *ppm, 
         CHECK(mbn_memset(ctx, d_ranks, 0, cells * sizeof(uint64_t)));
         CHECK(mbn_net_segment_topk_score(net, d_labels, d_truth, 4, d_ranks));
         CHECK(mbn_download(ctx, ranks, d_ranks, cells * sizeof(uint64_t)));
-        CHECK(mbn_free(ctx, d_truth));
         CHECK(mbn_free(ctx, d_ranks));
         double acc[MBN_TOPK_MAX], mean[MBN_TOPK_MAX], valid = 0.0;
         CHECK(mbn_topk_metrics(ranks, classes, k, acc, mean, &valid));
         printf("topk: k=%d valid=%.0f", k, valid);
         for (int j = 0; j < k; j++) printf(" top%d_acc=%.17g top%d_mean_acc=%.17g", j + 1, acc[j], j + 1, mean[j]);
         printf("\n");
+        if (g_calibration.bins) {                               /* plane 0 of the rank-major labels and probabilities is the map to score */
+            const int bad_cal = score_calibration(ctx, net, d_labels, d_prob, d_truth, 4);
+            if (bad_cal) return bad_cal;
+        }
+        CHECK(mbn_free(ctx, d_truth));
         free(tv); free(ranks);
     }
     CHECK(mbn_download(ctx, labels, d_labels, sizeof(int) * pixels * (size_t)k));
@@ -939,7 +989,7 @@ int main(int argc, char **argv)
     int fit = MBN_FIT_CROP, filter = MBN_FILTER_BILINEAR;
     int pad_rgb[3] = { 0, 0, 0 }, src_h0 = 0, src_w0 = 0;              /* src_h0 x src_w0: image 0 as it was resized (0: it was not) */
     float crop_fraction = 1.0f, min_conf = 0.0f;
-    int have_min_conf = 0, have_ignore = 0, ignore_label = -1, have_topk = 0, segment_topk = 0;
+    int have_min_conf = 0, have_ignore = 0, ignore_label = -1, have_topk = 0, segment_topk = 0, have_calibration = 0, calibration_bins = 0;
     const char *tta = NULL, *slide_arg = NULL, *slide_stride_arg = NULL;
     int fit_given = 0, slide[4] = { 0, 0, 0, 0 }, slide_tiles = 0;      /* slide: tile rows, tile columns, stride rows, stride columns */
     region_opts regions = { 0, 4, 1, 256 };
@@ -979,6 +1029,8 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--slide") && i + 1 < argc) slide_arg = argv[++i];
         else if (!strcmp(argv[i], "--slide-stride") && i + 1 < argc) slide_stride_arg = argv[++i];
         else if (!strcmp(argv[i], "--truth") && i + 1 < argc) truths[n_truth++] = argv[++i];
+        else if (!strcmp(argv[i], "--calibration") && i + 1 < argc) { calibration_bins = atoi(argv[++i]); have_calibration = 1; }
+        else if (!strcmp(argv[i], "--target-accuracy") && i + 1 < argc) { g_calibration.target = atof(argv[++i]); g_calibration.have_target = 1; }
         else if (!strcmp(argv[i], "--regions")) regions.on = 1;
         else if (!strcmp(argv[i], "--panoptic")) panoptic.on = 1;
         else if (!strcmp(argv[i], "--boundary-ratio") && i + 1 < argc) { boundary.ratio = atof(argv[++i]); boundary.on |= 1; }
@@ -1004,8 +1056,11 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--literal")) literal = 1;
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
-            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--segment-topk K] [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]] [--slide TH[xTW] [--slide-stride SH[xSW]]] [--truth F.pgm ...] [--regions [--connectivity 4|8] [--min-area N] [--max-regions M]] [--boundary-ratio R | --boundary-d N [--boundary-edge 0|1] [--boundary-map OUT.pgm]] [--panoptic [--connectivity 4|8] [--min-area N]]] [--segment-confidence OUT.pgm] "
-                            "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n", argv[0]);
+            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--segment-topk K] [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]] [--slide TH[xTW] [--slide-stride SH[xSW]]] [--truth F.pgm ...] [--calibration BINS [--target-accuracy A]] [--regions [--connectivity 4|8] [--min-area N] [--max-regions M]] [--boundary-ratio R | --boundary-d N [--boundary-edge 0|1] [--boundary-map OUT.pgm]] [--panoptic [--connectivity 4|8] [--min-area N]]] [--segment-confidence OUT.pgm] "
+                            "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n"
+                            "  --calibration BINS [--target-accuracy A]: with --segment-confidence and --truth, one calibration: line (reliability table "
+                            "in BINS bins, ECE, MCE, AURC) and the smallest --min-confidence that reaches accuracy A; with --min-confidence P > 0 the "
+                            "thresholded labels are scored, the pixels below P count as abstained\n", argv[0]);
             return 2;
         }
     }
@@ -1071,6 +1126,19 @@ int main(int argc, char **argv)
     if (n_truth > 0 && (!segment_src || n_truth != n_ppm)) {
         fprintf(stderr, "--truth F.pgm needs --segment-source and comes once per --ppm, in the same order\n");
         return 2;
+    }
+    if (have_calibration || g_calibration.have_target) {
+        if (!have_calibration || !segment_src || !segment_conf || n_truth == 0) {
+            fprintf(stderr, "--calibration BINS [--target-accuracy A] needs --segment-source, --segment-confidence (the probabilities it scores) and "
+                            "--truth; --target-accuracy needs --calibration\n");
+            return 2;
+        }
+        if (calibration_bins < 1 || calibration_bins > MBN_CALIBRATION_MAX_BINS ||
+            (g_calibration.have_target && !(g_calibration.target >= 0.0 && g_calibration.target <= 1.0))) {
+            fprintf(stderr, "bad --calibration (1 <= BINS <= %d) or --target-accuracy (0 <= A <= 1)\n", MBN_CALIBRATION_MAX_BINS);
+            return 2;
+        }
+        g_calibration.bins = calibration_bins;
     }
     if (boundary.on || boundary_flags || boundary.map) {
         const int both = boundary.on == 3, none = boundary.on == 0;

@@ -687,6 +687,68 @@ int mbn_topk_rank_i32(mbn_context *ctx, void *ranks_u64, const void *labels_i32,
 int mbn_topk_rank_ragged_i32(mbn_ragged_readout *r, void *ranks_u64, const void *labels_i32, int k, int64_t plane_stride, const void *truth,
                              int truth_bytes, int classes, void *stream);
 int mbn_topk_metrics(const uint64_t *ranks, int classes, int k, double *accuracy, double *mean_accuracy, double *valid);
+/* Calibration score: is the probability worth anything, and which min_prob to pass. The label maps and the softmax probabilities the read-outs
+ * above write (mbn_resample_softmax_f32, its window and ragged forms, the ensemble, slide and top-k read-outs: plane 0 of a rank-major top-k call
+ * is a valid input as it is) against a ground truth, accumulated on the device into one small table: the reliability diagram and expected
+ * calibration error of Guo et al. 2017 and the risk-coverage curve of the min_prob threshold come from it on the host.
+ * Normative (tests/calibration_ref.py is the numpy form):
+ *   calib is uint64_t [bins + 1][4], row-major, on 8 bytes; the calls ADD to it. bins is in 1 .. MBN_CALIBRATION_MAX_BINS. For a pixel with label
+ *   l (int32), probability x (fp32) and truth t (uint8 or int32 by mbn_confusion_i32's rule):
+ *     p    x clamped: 0 when x is a NaN or x < 0, 1 when x > 1, else x. (The read-outs only write values in [0, 1]; the clamp defines the call for
+ *          any buffer.)
+ *     bin  min(bins - 1, (int32) trunc(p (*) (float) bins)): (*) is ONE fp32 multiplication, rounded to nearest, contracted with nothing.
+ *          numpy: (p * np.float32(bins)).astype(np.int64). p = 1 goes to bin bins - 1.
+ *     q    (uint64) trunc(p * 2^24): the product is exact in fp32 and q <= 2^24.
+ *     t outside [0, classes): VOID. Adds 1 to [bins][0] and nothing else; the other three cells of row `bins` stay 0. Neither l nor x is read.
+ *     else l outside [0, classes) (ignore_label, -1, any negative): ABSTAINED. Adds 1 to [bin][3].
+ *     else ANSWERED: adds 1 to [bin][0], (l == t) to [bin][1] and q to [bin][2].
+ *   Every pixel adds 1 to exactly one cell of columns 0 and 3: after any sequence of calls those two columns sum to the pixels scored. On the same
+ *   labels and truth, against mbn_confusion_i32: the sum of [b][1] is the trace of its matrix over the valid rows, the sum of [b][3] its abstained
+ *   column over the valid rows, [bins][0] the sum of its void row. Everything is integer once bin and q are formed per pixel, so the bytes do not
+ *   depend on the order of the atomics: the same at every planning CU count and on graph replay. The fixed-point column [b][2] cannot wrap
+ *   below 2^40 answered pixels in total (2^40 * 2^24 = 2^64); columns 0, 1 and 3 count pixels.
+ *   mbn_calibration_f32         `count` pixels: labels_i32 [count], prob_f32 [count], truth [count]. labels_i32 and prob_f32 any pointers on 4
+ *                               bytes, a uint8 truth any byte pointer, an int32 truth any pointer on 4 bytes, independently of each other. ONE
+ *                               kernel, asynchronous on `stream` (NULL: the context's), capturable as one kernel node; a persistent grid sized
+ *                               from the planning CU count
+ *   mbn_calibration_ragged_f32  the maps of a ragged set: item i's pixels are at dst_offset_i in labels_i32, in prob_f32 and in truth; nothing
+ *                               between the maps is read. After either kind of set; ONE kernel; it keeps the generation rule (a captured launch
+ *                               replayed after a later set adds nothing) and the next set waits for it
+ * MBN_EINVAL: a NULL pointer, calib_u64 off 8 bytes, labels_i32 or prob_f32 off 4, an int32 truth off 4, classes < 1, count < 1, truth_bytes not 1
+ * or 4, bins < 1, a handle without a set, or an undersized tracked buffer (calib_u64 spans (bins + 1) * 32 bytes; labels_i32, prob_f32 and truth
+ * span `count` elements, in the ragged form the set's span). MBN_EUNSUPPORTED: classes > MBN_CONFUSION_MAX_CLASSES, bins >
+ * MBN_CALIBRATION_MAX_BINS or count > 2^34. Nothing is launched on a refusal. mbn_calibration_envelope answers the shape part; pure host.
+ *   mbn_calibration_metrics     pure C in doubles, exact for cells below 2^53. accuracy, confidence, coverage and selective_accuracy are [bins] or
+ *     NULL. For bin b: n_b = [b][0]; accuracy[b] = [b][1] / n_b; confidence[b] = [b][2] / (n_b * 2^24); both NaN when n_b = 0. With N = the sum
+ *     of n_b: pixels = N + abstained + void_pixels; answered = N; abstained = the sum of [b][3]; void_pixels = [bins][0]; accuracy = (the sum of
+ *     [b][1]) / N and mean_confidence = (the sum of [b][2]) / (N * 2^24), both 0 when N = 0; ece = the sum over the non-empty bins, in ascending
+ *     order, of (n_b / N) * |accuracy[b] - confidence[b]|; mce = the largest such gap (both 0 when N = 0).
+ *     The curve, for edge j = 0 .. bins - 1, is that of keeping the bins >= j: coverage[j] = (the sum over b >= j of [b][0]) / (N + abstained)
+ *     (0 when that is 0: the pixels already abstained count against the coverage and are not brought back by a lower edge);
+ *     selective_accuracy[j] = (the sum over b >= j of [b][1]) / (the sum over b >= j of [b][0]), NaN when that is empty;
+ *     aurc = the sum over j of (1 - selective_accuracy[j]) * (coverage[j] - coverage[j + 1]) with coverage[bins] = 0, empty terms skipped.
+ *     Every ratio is one division of exact integers. MBN_EINVAL: NULL calib or m, bins < 1; MBN_EUNSUPPORTED: bins > MBN_CALIBRATION_MAX_BINS.
+ *   mbn_calibration_threshold   the smallest edge j whose selective_accuracy[j] >= target_accuracy: *min_prob = (float) j / (float) bins with that
+ *     edge's coverage and selective accuracy (each output may be NULL). MBN_EINVAL: as above, or a target outside [0, 1] (a NaN included).
+ *     MBN_ENOTFOUND when no edge reaches the target (every edge is empty, or the best kept set is still below it): nothing is written.
+ *   The power-of-two guarantee. For bins a power of two, p (*) bins is exact and (float) j / bins is exact, so bin >= j holds exactly when
+ *     p >= j / bins: the complement of the read-outs' strict test prob < min_prob at min_prob = j / bins. Edge j of the curve is then exactly what
+ *     a read-out with that min_prob will keep (tests/test_calibration_cpu.py proves it on every edge and its neighbours). For other bin counts the
+ *     curve is that of the bins, with no such guarantee. */
+#define MBN_CALIBRATION_MAX_BINS 1024
+typedef struct mbn_calibration {
+    double pixels, answered, abstained, void_pixels;
+    double accuracy, mean_confidence, ece, mce, aurc;
+} mbn_calibration;
+int mbn_calibration_f32(mbn_context *ctx, void *calib_u64, const void *labels_i32, const void *prob_f32, const void *truth, int truth_bytes,
+                        int classes, int bins, int64_t count, void *stream);
+int mbn_calibration_ragged_f32(mbn_ragged_readout *r, void *calib_u64, const void *labels_i32, const void *prob_f32, const void *truth,
+                               int truth_bytes, int classes, int bins, void *stream);
+int mbn_calibration_envelope(int classes, int truth_bytes, int bins, int64_t count);
+int mbn_calibration_metrics(const uint64_t *calib, int bins, mbn_calibration *m, double *accuracy, double *confidence, double *coverage,
+                            double *selective_accuracy);
+int mbn_calibration_threshold(const uint64_t *calib, int bins, double target_accuracy, float *min_prob, double *coverage,
+                              double *selective_accuracy);
 /* Regions of a label map: connected-component labelling of the int32 maps the read-outs above write, on the device.
  * Normative (tests/components_ref.py is the numpy form; everything is integer, so the result is a function of the input alone: the same bytes at
  * every planning CU count, in both forms, on every run and on graph replay). For one image L [rows][cols] and classes >= 1:
@@ -1479,6 +1541,12 @@ int  mbn_net_segment_score(mbn_net *net, const void *labels_i32, const void *tru
  * uniform call, mbn_topk_rank_ragged_i32 on the net's own set for an image call, with the call's k and plane stride and the plan's classes;
  * ranks_u64 [classes + 1][k + 1] is added to. MBN_EINVAL before any segment call and when the last one was not a top-k call. */
 int  mbn_net_segment_topk_score(mbn_net *net, const void *labels_i32, const void *truth, int truth_bytes, void *ranks_u64);
+/* The calibration table of that same call ("calibration score" above; found exactly as mbn_net_segment_score finds it): mbn_calibration_f32 for a
+ * uniform call, mbn_calibration_ragged_f32 on the net's own set for an image call, with the plan's classes; calib_u64 [bins + 1][4] is added to.
+ * prob_f32 is the probability map that call wrote (plane 0 of a top-k call), passed by the caller as the labels are: the record does not say
+ * whether the last call wrote one. MBN_EINVAL before any segment call. Otherwise whatever the calibration call answers. */
+int  mbn_net_segment_calibration(mbn_net *net, const void *labels_i32, const void *prob_f32, const void *truth, int truth_bytes, int bins,
+                                 void *calib_u64);
 /* The regions of the label maps of that same call ("regions of a label map" above; found exactly as mbn_net_segment_score finds it): a uniform
  * call is one mbn_components_i32 over [batch][out_rows][out_cols], an image call mbn_components_ragged_i32 on the net's own ragged set. classes is
  * the plan's. The net owns one mbn_components handle, sized for the call on first use, made again when a later call needs more, freed by

@@ -757,6 +757,131 @@ def main_score(a):
     print(json.dumps(result))
 
 
+CALIBRATION_LAB_PLAIN = 1010        # lab exp0 of mbn_f32_calibration.hip: every lane adds on its own (no wave aggregation)
+
+
+def main_calibration(a):
+    """--calibration: mbn_calibration_f32 on --batch maps of 375 x 500 (6 M pixels at 32), int32 labels and fp32 probabilities against a uint8
+    truth, 21 classes, 15 and 1024 bins. Three inputs:
+      random     prob uniform in [0, 1) per pixel, the truth uniform over the classes: the lanes of a wave hold many different bins
+      blocks     25 x 25 blocks of one truth class and one prob: what a confident region looks like, and what the wave aggregation is for
+      constant   one (truth, label, prob) everywhere: one leader per wave
+    In all three the label equals the truth with probability prob (else the next class), so the table is a calibrated one.
+    Per cell, alternating within every repetition: the kernel (table cleared once in front; it accumulates), with MBN_LAB=1 the kernel without the
+    wave aggregation (lab exp0 = 1010), mbn_confusion_i32 on the same labels and truth, and torch's route on the SAME device buffers: the bin as
+    the kernel forms it (one fp32 multiply, truncate, clamp: torch.bucketize over the edges j / bins gives the same buckets only for a power of
+    two), then torch.bincount with float64 weights for each of the four columns. The tables are compared once (the float64 column after rounding).
+    Each figure is the median over the repetitions of `steps` back-to-back calls between two stream marks (torch: two torch events); the runs are
+    kept, the spread is (max - min) / median. share_of_hbm: 9 bytes a pixel over the kernel's time against 8 TB/s."""
+    pkg = import_package()
+    torch = None
+    if not a.no_torch:
+        import torch
+        assert torch.cuda.is_available(), "the yardstick needs torch on the same GPU"
+    n, H, W, classes = a.batch, 375, 500, 21
+    pix = n * H * W
+    rng = np.random.default_rng(0)
+    result = {"batch": n, "pixels": pix, "bytes_per_pixel": 9, "classes": classes}
+    yy, xx = np.mgrid[0:H, 0:W]
+    tr_blocks = rng.integers(0, classes, (n, H // 25 + 1, W // 25 + 1))
+    pr_blocks = rng.random((n, H // 25 + 1, W // 25 + 1)) ** 0.25
+    truths = {"random": rng.integers(0, classes, pix), "blocks": tr_blocks[:, yy // 25, xx // 25].ravel(), "constant": np.full(pix, classes - 1)}
+    probs = {"random": rng.random(pix), "blocks": pr_blocks[:, yy // 25, xx // 25].ravel(), "constant": np.full(pix, 0.97)}
+    with pkg.Context(0) as ctx:
+        lab_knob = ctx.lib.mbn_tune_set(b"exp0", 0) == pkg.OK          # the lab library: the plain form can be timed beside the shipped one
+        result["lab"] = bool(lab_knob)
+        d_counts = ctx.alloc((classes + 1) ** 2 * 8)
+        for name in ("random", "blocks", "constant"):
+            tr, pr = truths[name].astype(np.uint8), probs[name].astype(np.float32)
+            lab = np.where(rng.random(pix) < pr, tr, (tr + 1) % classes).astype(np.int32) if name != "constant" else tr.astype(np.int32)
+            if torch is not None:
+                t_lab, t_pr, t_tr = torch.from_numpy(lab).cuda(), torch.from_numpy(pr).cuda(), torch.from_numpy(tr).cuda()
+                p_lab, p_pr, p_tr = t_lab.data_ptr(), t_pr.data_ptr(), t_tr.data_ptr()
+            else:
+                t_lab, t_pr, t_tr = ctx.to_device(lab), ctx.to_device(pr), ctx.to_device(tr)
+                p_lab, p_pr, p_tr = t_lab.ptr, t_pr.ptr, t_tr.ptr
+            conf = lambda: ctx.confusion(d_counts.ptr, p_lab, p_tr, 1, classes, pix)
+            for bins in (15, 1024):
+                cells = (bins + 1) * 4
+                d_cal = ctx.alloc(cells * 8)
+                fn = lambda: ctx.calibration(d_cal.ptr, p_lab, p_pr, p_tr, 1, classes, bins, pix)
+
+                def table_of(knob):
+                    if lab_knob:
+                        ctx.lib.mbn_tune_set(b"exp0", knob)
+                    ctx.lib.mbn_memset(ctx.h, d_cal.ptr, 0, cells * 8)
+                    fn()
+                    ctx.sync()
+                    return d_cal.download((bins + 1, 4), np.uint64)
+
+                once = table_of(0)
+                assert int(once[:, 0].sum() + once[:, 3].sum()) == pix
+                plain_equal = bool(np.array_equal(table_of(CALIBRATION_LAB_PLAIN), once)) if lab_knob else None
+                agree = None
+                if torch is not None:
+                    def route():
+                        p = torch.clamp(torch.nan_to_num(t_pr, nan=0.0), 0.0, 1.0)
+                        b = torch.clamp((p * float(bins)).to(torch.int64), max=bins - 1)
+                        valid = t_tr.long() < classes
+                        answered = valid & (t_lab >= 0) & (t_lab < classes)
+                        q = (p * 16777216.0).to(torch.int64).to(torch.float64)
+                        cols = [torch.bincount(b, weights=w, minlength=bins) for w in
+                                (answered.double(), (answered & (t_lab == t_tr.long())).double(), answered.double() * q, (valid & ~answered).double())]
+                        return torch.stack(cols, 1), (~valid).sum()
+                    got, void = route()
+                    want = np.zeros((bins + 1, 4), np.uint64)
+                    want[:bins] = np.rint(got.cpu().numpy()).astype(np.uint64)
+                    want[bins, 0] = int(void)
+                    agree = bool(np.array_equal(want, once))
+                marks_ms(ctx, fn, 2)
+                marks_ms(ctx, conf, 2)
+                ks, ps, cs, ts = [], [], [], []
+                for _ in range(a.reps):
+                    if lab_knob:
+                        ctx.lib.mbn_tune_set(b"exp0", 0)
+                    ks.append(marks_ms(ctx, fn, a.steps))
+                    if lab_knob:
+                        ctx.lib.mbn_tune_set(b"exp0", CALIBRATION_LAB_PLAIN)
+                        ps.append(marks_ms(ctx, fn, a.steps))
+                        ctx.lib.mbn_tune_set(b"exp0", 0)
+                    cs.append(marks_ms(ctx, conf, a.steps))
+                    if torch is None:
+                        continue
+                    ctx.sync()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(max(a.steps // 4, 1)):
+                        route()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    ts.append(e0.elapsed_time(e1) / max(a.steps // 4, 1))
+                k, c = statistics.median(ks), statistics.median(cs)
+                out = {"kernel_ms": round(k, 4), "kernel_runs_ms": [round(v, 4) for v in ks], "spread": round((max(ks) - min(ks)) / k, 4),
+                       "share_of_hbm": round(9.0 * pix / (k * 1e-3) / HBM_BYTES_PER_S, 4), "nonzero_cells": int((once != 0).sum()),
+                       "confusion_ms": round(c, 4), "confusion_runs_ms": [round(v, 4) for v in cs], "kernel_over_confusion": round(k / c, 2)}
+                if ps:
+                    p_ms = statistics.median(ps)
+                    out.update({"plain_ms": round(p_ms, 4), "plain_runs_ms": [round(v, 4) for v in ps], "plain_over_kernel": round(p_ms / k, 2),
+                                "plain_table_equal": plain_equal})
+                if ts:
+                    tm = statistics.median(ts)
+                    out.update({"torch_ms": round(tm, 4), "torch_runs_ms": [round(v, 4) for v in ts], "torch_over_kernel": round(tm / k, 2),
+                                "table_equal_torch": agree})
+                print("%-8s bins %4d: kernel %.4f ms (%.4f - %.4f, %.1f %% of 8 TB/s at 9 B/pixel)  plain %s ms  confusion %.4f ms  torch %s ms" %
+                      (name, bins, k, min(ks), max(ks), 100 * out["share_of_hbm"], ("%.4f" % out["plain_ms"]) if ps else "-", c,
+                       ("%.4f" % out["torch_ms"]) if ts else "-"), flush=True)
+                result["%s_bins_%d" % (name, bins)] = out
+                d_cal.free()
+            if torch is not None:
+                del t_lab, t_pr, t_tr
+                torch.cuda.empty_cache()
+            else:
+                for buf in (t_lab, t_pr, t_tr):
+                    buf.free()
+        d_counts.free()
+    print(json.dumps(result))
+
+
 def main_regions(a):
     """--regions: mbn_components_i32 on --batch maps of 375 x 500 (6 M pixels at 32) at 21 / 150 / 1000 classes. Three inputs per class count:
       random     labels uniform over the classes: nearly every pixel its own region at 1000 classes, large tangled ones at 21 under connectivity 8
@@ -1174,7 +1299,10 @@ def main():
     ap.add_argument("--panoptic", action="store_true", help="time mbn_panoptic_i32 beside torch.unique and numpy's pair histogram instead: see main_panoptic")
     ap.add_argument("--host-maps", type=int, default=2, help="--regions, --boundary: the maps the host yardstick really works on (its time is scaled to the batch)")
     ap.add_argument("--no-host", action="store_true", help="--regions, --boundary: skip the host yardstick")
+    ap.add_argument("--calibration", action="store_true", help="time mbn_calibration_f32 beside mbn_confusion_i32 and torch instead: see main_calibration")
     a = ap.parse_args()
+    if a.calibration:
+        return main_calibration(a)
     if a.panoptic:
         return main_panoptic(a)
     if a.boundary:
