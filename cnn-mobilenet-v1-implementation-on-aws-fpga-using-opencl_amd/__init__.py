@@ -136,6 +136,12 @@ class BoundaryMetrics(C.Structure):
                 ("classes_present", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SurfaceMetrics(C.Structure):
+    """mbn_surface_metrics_t (include/mbn.h, "score a segmentation by surface distance")"""
+    _fields_ = [(n, C.c_double) for n in ("hd", "hdp", "assd", "nsd", "n", "unmatched")] + \
+               [(n, C.c_int32) for n in ("classes_present", "classes_measurable", "saturated", "reserved")]
+
+
 class SegMetrics(C.Structure):
     """mbn_seg_metrics (include/mbn.h, "score a segmentation")"""
     _fields_ = [("pixels", C.c_double), ("valid", C.c_double), ("void_pixels", C.c_double), ("abstained", C.c_double),
@@ -288,6 +294,12 @@ def _declare_host(lib):
     lib.mbn_boundary_envelope.argtypes = [C.c_int] * 7
     lib.mbn_boundary_tile.argtypes = [C.c_int] + [C.POINTER(C.c_int)] * 3
     lib.mbn_boundary_metrics.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.POINTER(BoundaryMetrics), C.POINTER(C.c_double)]
+    lib.mbn_surface_envelope.argtypes = [C.c_int] * 7
+    lib.mbn_surface_tile.argtypes = [C.POINTER(C.c_int)] * 2
+    lib.mbn_surface_scratch_bytes.argtypes = [C.c_int, C.c_int64, C.c_int]
+    lib.mbn_surface_scratch_bytes.restype = C.c_int64
+    lib.mbn_surface_metrics.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(SurfaceMetrics)] + \
+                                       [C.POINTER(C.c_double)] * 4
     i32p = C.POINTER(C.c_int32)
     lib.mbn_resize_ksize.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int]
     lib.mbn_resize_taps.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int, i32p, i32p, i32p]
@@ -479,6 +491,11 @@ def load():
         lib.mbn_boundary_score_ragged_i32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, vp, ci, vp]
         lib.mbn_net_segment_boundary_score.argtypes = [vp, vp, vp, ci, vp, vp, C.c_double, ci, ci]
         lib.mbn_net_segment_boundary_depth.argtypes = [vp, vp, vp, C.c_double, ci, ci]
+        lib.mbn_surface_create.argtypes = [vp, ci, C.c_int64, ci, C.POINTER(vp)]
+        lib.mbn_surface_destroy.argtypes = [vp]
+        lib.mbn_surface_score_i32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
+        lib.mbn_surface_score_ragged_i32.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
+        lib.mbn_net_segment_surface.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp]
         lib.mbn_resizer_create.argtypes = [vp, ci, ci, C.POINTER(C.c_float), ci, ci, C.POINTER(vp)]
         lib.mbn_resize_u8.argtypes = [vp, vp, vp, ci, vp]
         lib.mbn_resizer_destroy.argtypes = [vp]
@@ -943,6 +960,41 @@ def boundary_metrics(biou, classes, lib=None):
     return m, iou
 
 
+SURFACE_HEAD = 4                 # MBN_SURFACE_HEAD: n, unmatched, max_d2, sum256 in front of the bins of a surface table's row
+SURFACE_MAX_BINS = 4096          # MBN_SURFACE_MAX_BINS
+SURFACE_UNMATCHED = 0xFFFFFFFE   # dist2 of a query whose class has no contour in the other map
+SURFACE_NOT_QUERY = 0xFFFFFFFF   # dist2 of a pixel that is no query
+
+
+def surface_envelope(truth_bytes, classes, bins, batch, rows, cols, edge, lib=None) -> int:
+    """mbn_surface_envelope: the status (OK, EINVAL or EUNSUPPORTED) the surface calls give the shape."""
+    return (lib or host_lib()).mbn_surface_envelope(truth_bytes, classes, bins, batch, rows, cols, edge)
+
+
+def surface_tile(lib=None):
+    """mbn_surface_tile: (unit_pixels, wave_pixels): a seam of the kernels lies at every multiple of them in a map's row-major pixel order."""
+    up, wp = C.c_int(0), C.c_int(0)
+    _chk((lib or host_lib()).mbn_surface_tile(C.byref(up), C.byref(wp)), "surface_tile")
+    return up.value, wp.value
+
+
+def surface_scratch_bytes(max_batch, max_pixels, max_classes, lib=None) -> int:
+    """mbn_surface_scratch_bytes: the device memory a Surface handle of that size holds (0: a size mbn_surface_create refuses)."""
+    return (lib or host_lib()).mbn_surface_scratch_bytes(max_batch, max_pixels, max_classes)
+
+
+def surface_metrics(surf, classes, bins, tolerance=2, percentile=95.0, lib=None):
+    """mbn_surface_metrics: (SurfaceMetrics, hd, hdp, assd, nsd: float64 [classes], NaN where a score is undefined) of surf, uint64
+    [classes][2][SURFACE_HEAD + bins]. A micro average: the table pools the contour pixels of every image and call."""
+    n = np.ascontiguousarray(surf, dtype=np.uint64)
+    if n.size != classes * 2 * (SURFACE_HEAD + bins):
+        raise ValueError("surf has %d cells, classes = %d and bins = %d need %d" % (n.size, classes, bins, classes * 2 * (SURFACE_HEAD + bins)))
+    m, out = SurfaceMetrics(), [np.empty(classes, np.float64) for _ in range(4)]
+    _chk((lib or host_lib()).mbn_surface_metrics(n.ctypes.data_as(C.POINTER(C.c_uint64)), classes, bins, tolerance, percentile, C.byref(m),
+                                                 *[o.ctypes.data_as(C.POINTER(C.c_double)) for o in out]), "surface_metrics")
+    return (m,) + tuple(out)
+
+
 PANOPTIC_CHUNK = 1024            # MBN_PANOPTIC_CHUNK: the pixels of one unit of work of the two pixel kernels of mbn_panoptic_i32
 PANOPTIC_LDS_CLASSES = 1024      # MBN_PANOPTIC_LDS_CLASSES: up to here its two deciding kernels count a workgroup's classes in LDS
 NET_PANOPTIC_REGIONS = 4096      # MBN_NET_PANOPTIC_REGIONS
@@ -1300,6 +1352,17 @@ class Context:
         _chk(self.lib.mbn_panoptic_ragged_i32(handle.h, readout.h, pq, scored, match_pred, match_truth, inter, void, comp_pred, pred, n_pred,
                                               max_pred, comp_truth, truth, n_truth, max_truth, classes, stream), self.last_error())
 
+    def surface_score(self, handle, surf, labels, truth, truth_bytes, classes, bins, batch, rows, cols, edge=1, dist2=None, stream=None):
+        """mbn_surface_score_i32: surf (uint64 [classes][2][SURFACE_HEAD + bins], device) += the surface-distance table of int32 labels against
+        truth (uint8 or int32), both [batch][rows][cols]; dist2 (uint32 at the labels' offsets, direction 0) or None."""
+        _chk(self.lib.mbn_surface_score_i32(handle.h, surf, dist2, labels, truth, truth_bytes, classes, bins, batch, rows, cols, edge, stream),
+             self.last_error())
+
+    def surface_score_ragged(self, handle, readout, surf, labels, truth, truth_bytes, classes, bins, edge=1, dist2=None, stream=None):
+        """mbn_surface_score_ragged_i32: the same over the maps of a RaggedReadout's set; truth and dist2 at the labels' element offsets."""
+        _chk(self.lib.mbn_surface_score_ragged_i32(handle.h, readout.h, surf, dist2, labels, truth, truth_bytes, classes, bins, edge, stream),
+             self.last_error())
+
     def widen_u8(self, dst, src, count, stream=None):
         """mbn_widen_u8_i32: dst (int32 [count]) = src (uint8 [count]), value for value."""
         _chk(self.lib.mbn_widen_u8_i32(self.h, dst, src, count, stream), self.last_error())
@@ -1327,6 +1390,25 @@ class Panoptic:
     def close(self):
         if self.h:
             self.ctx.lib.mbn_panoptic_destroy(self.h)
+            self.h = None
+
+
+class Surface:
+    """mbn_surface_create: the scratch of the surface-distance kernels for up to max_batch maps of max_pixels pixels in all and max_classes classes,
+    allocated once; the `handle` of Context.surface_score / surface_score_ragged."""
+
+    def __init__(self, ctx: "Context", max_batch, max_pixels, max_classes):
+        self.ctx = ctx
+        h = C.c_void_p()
+        _chk(ctx.lib.mbn_surface_create(ctx.h, max_batch, max_pixels, max_classes, C.byref(h)), ctx.last_error())
+        self.h = h
+        if not hasattr(ctx, "_resizers"):
+            ctx._resizers = []
+        ctx._resizers.append(self)
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.mbn_surface_destroy(self.h)
             self.h = None
 
 
@@ -1715,6 +1797,12 @@ class Net:
     def segment_boundary_depth(self, labels_ptr, depth_ptr, ratio=0.02, d=0, edge=1):
         """mbn_net_segment_boundary_depth: the band (depth uint8) of those maps, at the labels' element offsets."""
         _chk(self.ctx.lib.mbn_net_segment_boundary_depth(self.h, labels_ptr, depth_ptr, ratio, d, edge), self.ctx.last_error())
+
+    def segment_surface(self, labels_ptr, truth_ptr, truth_bytes, surf_ptr, bins=64, edge=1, dist2_ptr=None):
+        """mbn_net_segment_surface: surf (uint64 [classes][2][SURFACE_HEAD + bins]) += the surface-distance table of the maps the most recent
+        successful source-size segment call wrote against truth; dist2 (uint32 at the labels' element offsets) or None."""
+        _chk(self.ctx.lib.mbn_net_segment_surface(self.h, labels_ptr, truth_ptr, truth_bytes, bins, edge, surf_ptr, dist2_ptr),
+             self.ctx.last_error())
 
     def segment_panoptic(self, labels_ptr, truth_ptr, truth_bytes, pq_ptr, scored_ptr, connectivity=4, min_area=1):
         """mbn_net_segment_panoptic: pq (uint64 [classes][4]) += the panoptic score of the maps the most recent successful source-size segment call

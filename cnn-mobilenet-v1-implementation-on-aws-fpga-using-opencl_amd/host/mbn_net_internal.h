@@ -50,6 +50,9 @@ struct mbn_net_seg {
     int64_t panoptic_span;
     void *panoptic_comp[2], *panoptic_wide, *panoptic_table[2], *panoptic_n[2];
     void *boundary_d;               /* mbn_net_segment_boundary_*: [max_batch] int32 on the device, the per-image half-widths of an image call */
+    mbn_surface *surface;           /* mbn_net_segment_surface: one handle, made again when a call needs more than it holds: */
+    int surface_batch, surface_classes;
+    int64_t surface_pixels;
 };
 
 struct mbn_net {

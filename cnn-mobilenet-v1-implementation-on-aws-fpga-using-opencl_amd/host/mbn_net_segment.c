@@ -724,6 +724,37 @@ int mbn_net_segment_boundary_depth(mbn_net *net, const void *labels_i32, void *d
     return mbn_boundary_depth(net->ctx, depth_u8, labels_i32, 4, m->batch, m->rows, m->cols, d, edge, NULL);
 }
 
+/* the net's one mbn_surface handle holds at least the maps m at the plan's classes */
+static int surface_ready(mbn_net *net, const struct mbn_seg_maps *m)
+{
+    struct mbn_net_seg *s = &net->seg;
+    if (s->surface && m->batch <= s->surface_batch && m->count <= s->surface_pixels && m->classes <= s->surface_classes) return MBN_OK;
+    /* the new handle first: when it cannot be had, the old one stays. It is made for max_batch, so only more pixels or classes make it again */
+    const int batch = net->max_batch > m->batch ? net->max_batch : m->batch;
+    const int classes = m->classes > s->surface_classes ? m->classes : s->surface_classes;
+    const int64_t pixels = m->count > s->surface_pixels ? m->count : s->surface_pixels;
+    mbn_surface *h = NULL;
+    const int rc = mbn_surface_create(net->ctx, batch, pixels, classes, &h);
+    if (rc != MBN_OK) return rc;
+    if (s->surface) mbn_surface_destroy(s->surface);
+    s->surface = h; s->surface_batch = batch; s->surface_pixels = pixels; s->surface_classes = classes;
+    return MBN_OK;
+}
+
+int mbn_net_segment_surface(mbn_net *net, const void *labels_i32, const void *truth, int truth_bytes, int bins, int edge, void *surf_u64,
+                            void *dist2_u32)
+{
+    const struct mbn_seg_maps *m = last_maps(net);
+    if (!m) return MBN_EINVAL;
+    const int rc = surface_ready(net, m);
+    if (rc != MBN_OK) return rc;
+    if (m->kind == MBN_SEG_RAGGED)
+        return mbn_surface_score_ragged_i32(net->seg.surface, net->seg.readout, surf_u64, dist2_u32, labels_i32, truth, truth_bytes, m->classes, bins,
+                                            edge, NULL);
+    return mbn_surface_score_i32(net->seg.surface, surf_u64, dist2_u32, labels_i32, truth, truth_bytes, m->classes, bins, m->batch, m->rows, m->cols,
+                                 edge, NULL);
+}
+
 void mbn_net_seg_release(mbn_net *net)
 {
     struct mbn_net_seg *s = &net->seg;
@@ -737,5 +768,6 @@ void mbn_net_seg_release(mbn_net *net)
     free(s->ragged_items); free(s->label_items);
     if (s->components) mbn_components_destroy(s->components);
     if (s->boundary_d) mbn_free(net->ctx, s->boundary_d);
+    if (s->surface) mbn_surface_destroy(s->surface);
     panoptic_release(net);
 }

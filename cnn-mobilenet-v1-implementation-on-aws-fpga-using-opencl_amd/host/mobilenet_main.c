@@ -67,6 +67,13 @@
  *   boundary_iou: class <c> <iou>                                                                   (one per present class)
  *   trimap: ... the fields of the score line, over the pixels within d of a contour of the truth
  *   --boundary-map writes image 0's band as an 8-bit P5: byte = min (depth, d + 1) of its label map (mbn_net_segment_boundary_depth)
+ *   --surface [--surface-bins N] [--surface-tolerance T] [--surface-percentile P] [--surface-edge 0|1] [--surface-map out.pgm] (with
+ *   --segment-source and --truth; defaults 64, 2, 95, 1; else usage status 2, as for a bad value: 2 <= N <= 4096, 0 <= T <= N - 2, 0 < P <= 100):
+ *   how far the predicted contours lie from the true ones, in pixels, "score a segmentation by surface distance" in mbn.h. Two kinds of line
+ *   follow the other scores (mbn_net_segment_surface, mbn_surface_metrics):
+ *   surface: bins=... tolerance=... percentile=... classes_present=... classes_measurable=... hd=... hdp=... assd=... nsd=... unmatched=... saturated=...
+ *   surface_class: class <c> <hd> <hdp> <assd> <nsd>                                                (one per present class; nan where undefined)
+ *   --surface-map writes image 0's contour as a 16-bit P5: 0 no contour pixel of a class, 65535 unmatched, else 1 + min (ceil (sqrt (d2)), 65533)
  *   mobilenet --literal [--weights weights_c.txt] [--image Cat_Image0.ppm] [--ref-args]      the reference's own mode
  *   mobilenet --gpus G --batch N [--steps K --warmup W --streams S --pw-emul 6] (--h5 F | --synthetic SEED)  N images sharded over G GPUs
  *   mobilenet --inspect weights.h5                                                             list the datasets of a .h5
@@ -626,6 +633,68 @@ static int score_calibration(mbn_context *ctx, mbn_net *net, void *d_labels, voi
     return 0;
 }
 
+/* --surface [--surface-bins N] [--surface-tolerance T] [--surface-percentile P] [--surface-edge 0|1] [--surface-map out.pgm]: what the command line
+ * asked for; on = 0: nothing (set once by main) */
+static struct { int on, bins, tolerance, edge; double percentile; const char *map; } g_surface = { 0, 64, 2, 1, 95.0, NULL };
+
+/* the smallest t with t * t >= d2 (d2 < 2^31) */
+static unsigned ceil_root(unsigned d2)
+{
+    unsigned t = (unsigned)sqrt((double)d2);
+    while ((uint64_t)t * t > d2) t--;
+    while ((uint64_t)(t + 1) * (t + 1) <= d2) t++;
+    return t + ((uint64_t)t * t < d2);
+}
+
+/* --truth with --surface: the surface-distance table of the same maps (mbn_net_segment_surface), the surface: line and one surface_class: line per
+ * present class; --surface-map: image 0's contour (at element first, rows x cols) as a 16-bit P5 of its distances */
+static int score_surface(mbn_context *ctx, mbn_net *net, void *d_labels, void *d_truth, int tb, int classes, size_t pixels, int64_t first, int rows,
+                         int cols)
+{
+    const int bins = g_surface.bins;
+    const size_t cells = (size_t)classes * 2 * (MBN_SURFACE_HEAD + (size_t)bins);
+    uint64_t *surf = malloc(cells * sizeof(uint64_t));
+    double *per = malloc(4 * (size_t)classes * sizeof(double));
+    uint32_t *d2 = g_surface.map ? malloc((size_t)rows * cols * sizeof(uint32_t)) : NULL;
+    if (!surf || !per || (g_surface.map && !d2)) return 1;
+    void *d_surf, *d_d2 = NULL;
+    CHECK(mbn_alloc(ctx, cells * sizeof(uint64_t), &d_surf));
+    if (g_surface.map) CHECK(mbn_alloc(ctx, pixels * sizeof(uint32_t), &d_d2));
+    CHECK(mbn_memset(ctx, d_surf, 0, cells * sizeof(uint64_t)));
+    CHECK(mbn_net_segment_surface(net, d_labels, d_truth, tb, bins, g_surface.edge, d_surf, d_d2));
+    CHECK(mbn_download(ctx, surf, d_surf, cells * sizeof(uint64_t)));
+    CHECK(mbn_free(ctx, d_surf));
+    mbn_surface_metrics_t m;
+    CHECK(mbn_surface_metrics(surf, classes, bins, g_surface.tolerance, g_surface.percentile, &m, per, per + classes, per + 2 * classes, per + 3 * classes));
+    printf("surface: bins=%d tolerance=%d percentile=%.17g classes_present=%d classes_measurable=%d hd=%.17g hdp=%.17g assd=%.17g nsd=%.17g unmatched=%.0f "
+           "saturated=%d\n", bins, g_surface.tolerance, g_surface.percentile, m.classes_present, m.classes_measurable, m.hd, m.hdp, m.assd, m.nsd, m.unmatched,
+           m.saturated);
+    for (int c = 0; c < classes; c++)
+        if (!isnan(per[3 * classes + c]))
+            printf("surface_class: class %d %.17g %.17g %.17g %.17g\n", c, per[c], per[classes + c], per[2 * classes + c], per[3 * classes + c]);
+    free(surf); free(per);
+    if (!g_surface.map) return 0;
+    CHECK(mbn_download(ctx, d2, (const char *)d_d2 + (size_t)first * sizeof(uint32_t), (size_t)rows * cols * sizeof(uint32_t)));
+    CHECK(mbn_free(ctx, d_d2));
+    FILE *fp = fopen(g_surface.map, "wb");
+    if (!fp) { fprintf(stderr, "Error: cannot write %s\n", g_surface.map); return 1; }
+    fprintf(fp, "P5\n%d %d\n65535\n", cols, rows);
+    long queries = 0;
+    int ok = 1;
+    for (long i = 0; i < (long)rows * cols; i++) {
+        /* not a query: 0; unmatched: 65535; matched: 1 + min (ceil (sqrt (d2)), 65533) */
+        unsigned v = 0;
+        if (d2[i] == 0xFFFFFFFEu) v = 65535;
+        else if (d2[i] != 0xFFFFFFFFu) { const unsigned t = ceil_root(d2[i]); v = 1 + (t < 65533 ? t : 65533); }
+        queries += v != 0;
+        const unsigned char be[2] = { (unsigned char)(v >> 8), (unsigned char)(v & 255) };
+        ok &= fwrite(be, 1, 2, fp) == 2;
+    }
+    printf("surface-map: %dx%d -> %s; %ld contour pixels\n", cols, rows, g_surface.map, queries);
+    free(d2);
+    return (fclose(fp) != 0) | !ok;
+}
+
 /* --truth: scores the label maps the segment call just wrote at d_labels (image n at element dst[n]) against the files, and prints the line;
  * --calibration (d_prob: the probabilities of the same call): the calibration line behind it; bo->on: the boundary lines behind that; po->on: the
  * panoptic lines behind those */
@@ -674,6 +743,10 @@ static int score_truth(mbn_context *ctx, mbn_net *net, const char **truths, int 
     }
     if (po->on) {
         const int bad = score_panoptic(ctx, net, po, n, d_labels, d_truth, tb, classes);
+        if (bad) return bad;
+    }
+    if (g_surface.on) {
+        const int bad = score_surface(ctx, net, d_labels, d_truth, tb, classes, pixels, dst[0], hs[0], ws[0]);
         if (bad) return bad;
     }
     CHECK(mbn_free(ctx, d_truth));
@@ -998,6 +1071,7 @@ int main(int argc, char **argv)
     panoptic_opts panoptic = { 0, 4, 1 };
     boundary_opts boundary = { 0, 0, 1, 0.0, NULL };
     int boundary_flags = 0;                                     /* --boundary-edge seen */
+    int surface_on = 0, surface_flags = 0;                      /* --surface, one of its options */
     int tta_flip = 0, n_views = 0;
     float tta_scales[MBN_ENSEMBLE_MAX_VIEWS], view_scales[MBN_ENSEMBLE_MAX_VIEWS];
     int32_t view_mirrors[MBN_ENSEMBLE_MAX_VIEWS];
@@ -1037,6 +1111,12 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--boundary-d") && i + 1 < argc) { boundary.d = atoi(argv[++i]); boundary.on |= 2; }
         else if (!strcmp(argv[i], "--boundary-edge") && i + 1 < argc) { boundary.edge = atoi(argv[++i]); boundary_flags = 1; }
         else if (!strcmp(argv[i], "--boundary-map") && i + 1 < argc) boundary.map = argv[++i];
+        else if (!strcmp(argv[i], "--surface")) surface_on = 1;
+        else if (!strcmp(argv[i], "--surface-bins") && i + 1 < argc) { g_surface.bins = atoi(argv[++i]); surface_flags = 1; }
+        else if (!strcmp(argv[i], "--surface-tolerance") && i + 1 < argc) { g_surface.tolerance = atoi(argv[++i]); surface_flags = 1; }
+        else if (!strcmp(argv[i], "--surface-percentile") && i + 1 < argc) { g_surface.percentile = atof(argv[++i]); surface_flags = 1; }
+        else if (!strcmp(argv[i], "--surface-edge") && i + 1 < argc) { g_surface.edge = atoi(argv[++i]); surface_flags = 1; }
+        else if (!strcmp(argv[i], "--surface-map") && i + 1 < argc) { g_surface.map = argv[++i]; surface_flags = 1; }
         else if (!strcmp(argv[i], "--connectivity") && i + 1 < argc) { regions.connectivity = atoi(argv[++i]); region_flags = 1; }
         else if (!strcmp(argv[i], "--min-area") && i + 1 < argc) { regions.min_area = atoi(argv[++i]); region_flags = 1; }
         else if (!strcmp(argv[i], "--max-regions") && i + 1 < argc) { regions.max_regions = atoi(argv[++i]); region_flags = max_regions_flag = 1; }
@@ -1056,7 +1136,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--literal")) literal = 1;
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
-            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--segment-topk K] [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]] [--slide TH[xTW] [--slide-stride SH[xSW]]] [--truth F.pgm ...] [--calibration BINS [--target-accuracy A]] [--regions [--connectivity 4|8] [--min-area N] [--max-regions M]] [--boundary-ratio R | --boundary-d N [--boundary-edge 0|1] [--boundary-map OUT.pgm]] [--panoptic [--connectivity 4|8] [--min-area N]]] [--segment-confidence OUT.pgm] "
+            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--segment-topk K] [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]] [--slide TH[xTW] [--slide-stride SH[xSW]]] [--truth F.pgm ...] [--calibration BINS [--target-accuracy A]] [--regions [--connectivity 4|8] [--min-area N] [--max-regions M]] [--boundary-ratio R | --boundary-d N [--boundary-edge 0|1] [--boundary-map OUT.pgm]] [--panoptic [--connectivity 4|8] [--min-area N]] [--surface [--surface-bins N] [--surface-tolerance T] [--surface-percentile P] [--surface-edge 0|1] [--surface-map OUT.pgm]]] [--segment-confidence OUT.pgm] "
                             "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n"
                             "  --calibration BINS [--target-accuracy A]: with --segment-confidence and --truth, one calibration: line (reliability table "
                             "in BINS bins, ECE, MCE, AURC) and the smallest --min-confidence that reaches accuracy A; with --min-confidence P > 0 the "
@@ -1154,6 +1234,20 @@ int main(int argc, char **argv)
         }
         if (boundary.on == 1) boundary.d = 0;
         boundary.on = n_truth > 0;
+    }
+    if (surface_on || surface_flags) {
+        if (!surface_on || !segment_src || n_truth == 0 || have_topk) {
+            fprintf(stderr, "--surface needs --segment-source and --truth and does not go with --segment-topk; --surface-bins, --surface-tolerance, "
+                            "--surface-percentile, --surface-edge and --surface-map need --surface\n");
+            return 2;
+        }
+        if (g_surface.bins < 2 || g_surface.bins > MBN_SURFACE_MAX_BINS || g_surface.tolerance < 0 || g_surface.tolerance > g_surface.bins - 2 ||
+            !(g_surface.percentile > 0.0 && g_surface.percentile <= 100.0) || (g_surface.edge != 0 && g_surface.edge != 1)) {
+            fprintf(stderr, "bad --surface-bins (2 <= N <= %d), --surface-tolerance (0 <= T <= N - 2), --surface-percentile (0 < P <= 100) or "
+                            "--surface-edge (0 or 1)\n", MBN_SURFACE_MAX_BINS);
+            return 2;
+        }
+        g_surface.on = 1;
     }
     if (panoptic.on && (!segment_src || n_truth == 0)) {
         fprintf(stderr, "--panoptic needs --segment-source and --truth\n");

@@ -935,6 +935,78 @@ int mbn_boundary_score_i32(mbn_context *ctx, void *trimap_u64, void *biou_u64, c
                            int classes, int batch, int rows, int cols, int d, int edge, void *stream);
 int mbn_boundary_score_ragged_i32(mbn_ragged_readout *readout, void *trimap_u64, void *biou_u64, const void *labels_i32, const void *truth,
                                   int truth_bytes, int classes, int d, const void *d_items_i32, int edge, void *stream);
+/* Score a segmentation by surface distance: Hausdorff distance (HD), its percentile (HD95), the average symmetric surface distance (ASSD) and the
+ * normalized surface Dice (NSD) at a tolerance, on the device. How far a predicted contour lies from the true one, in pixels.
+ * Squared Euclidean distances between pixels are integers and both roots below are formed exactly, so every result is pinned bit for bit at every
+ * planning CU count and on graph replay. Normative (tests/surface_ref.py is the numpy form), per map and per class c in [0, classes):
+ *   CONTOUR. The contour of c in a map M is the set of pixels with M (p) == c whose mbn_boundary_depth is 1: the pixel has an 8-neighbour inside
+ *     the map with another value, or edge = 1 and it lies on the map's frame. Values outside [0, classes) (void truth, abstained labels) are
+ *     "another value": they make their neighbours contour and form no class of their own. Values are compared as stored (a uint8 zero-extended).
+ *   DIRECTIONS. 0 is predicted -> truth, 1 is truth -> predicted. A contour pixel p of c in the source map is a QUERY; d2 (p) is the minimum of
+ *     drow^2 + dcol^2 over the contour pixels of c in the OTHER map of the same image: exact, uncapped, an integer. When c has no contour in the
+ *     other map of that image, p is UNMATCHED.
+ *   TABLE. surf_u64 [classes][2][MBN_SURFACE_HEAD + bins], row-major on 8 bytes, ADDED TO: the caller clears it (mbn_memset) and a dataset
+ *     accumulates over many calls. Per class and direction:
+ *       [0] n: all queries;   [1] unmatched;   [2] max_d2 over the matched queries, a 64-bit atomic MAX (a larger value already there stays);
+ *       [3] sum256: the sum of isqrt (d2 << 16) = floor (256 d) over the matched queries;
+ *       [4 + t], t < bins - 1: the matched queries with ceil (sqrt (d2)) == t (the smallest integer t with t * t >= d2);
+ *       [4 + bins - 1]: those with ceil (sqrt (d2)) >= bins - 1 (the OVERFLOW bin).
+ *     With ceil, the cumulative count up to an integer tau is exactly the number of matched queries with d <= tau.
+ *   dist2_u32 (optional, NULL: not written), at the labels' element offsets, direction 0 only: d2 of a matched query, 0xFFFFFFFE for an unmatched
+ *     one, 0xFFFFFFFF for a pixel that is no query. Nothing outside the maps is written. It must not overlap labels_i32 or truth.
+ *   mbn_surface_score_i32         labels_i32 and truth (truth_bytes 1 or 4) [batch][rows][cols]
+ *   mbn_surface_score_ragged_i32  the same over the maps of a ragged set of either item kind (the items' first 16 bytes): truth and dist2_u32 at
+ *                                 the labels' dst_offset in ELEMENTS; nothing between the maps is read or written. It keeps the handle's
+ *                                 generation rule (a captured launch replayed after a later set adds nothing) and the next set waits for it
+ * Both are a FIXED sequence of three kernels on `stream` (NULL: the context's): clear, contour, search. No host decision, allocation, copy to the
+ * host or blocking call: a call may be captured as a linear chain of kernel nodes. The grids are sized from the planning CU count; a unit of the
+ * two pixel kernels is MBN_SURFACE_UNIT consecutive pixels of one map (mbn_surface_tile: a seam lies at every multiple of it in row-major pixel
+ * order, and between the 64-pixel shares of its waves). The search is not capped: a query far from its match reads every ring between them
+ * (profiles/LOG.md, "Surface distance", has the cost). Calls on one handle share its scratch: they must be ordered on one stream.
+ * The handle holds all scratch: mbn_surface_scratch_bytes (max_batch, max_pixels, max_classes) = 8 bytes per pixel (two int32 contour maps) + 8
+ * bytes per image and class (the presence table), rounded up to 256. A call needs batch <= max_batch, its pixels in all <= max_pixels and
+ * classes <= max_classes. mbn_shutdown frees the handles still alive. int32 maps and dist2_u32 may be any pointers on 4 bytes, a uint8 truth any.
+ * MBN_EINVAL: a NULL handle, table, labels or truth; a table off 8 bytes; labels, an int32 truth or dist2_u32 off 4; classes < 1; bins < 2; batch,
+ * rows or cols < 1; edge not 0 or 1; truth_bytes not 1 or 4; dist2_u32 overlapping an input; a ragged handle without a set or of another
+ * context; an undersized tracked buffer (mbn_alloc's bounds rule, interior pointers included: the maps span batch * rows * cols elements, in the
+ * ragged form max (dst_offset + rows * cols); the table classes * 2 * (4 + bins) * 8 bytes; last_error names "surface table", "surface labels",
+ * "surface truth" or "surface dist2"). MBN_EUNSUPPORTED: classes > MBN_CONFUSION_MAX_CLASSES, bins > MBN_SURFACE_MAX_BINS, rows or cols > 32767
+ * (so that d2 < 2^31), rows * cols >= 2^29, batch > 65535, anything over what the handle was created for. MBN_EINVAL goes first; a refusal launches
+ * nothing. mbn_surface_envelope answers the shape part; it, _tile and _scratch_bytes (0 for arguments _create refuses) are pure host functions.
+ * mbn_surface_create: MBN_EINVAL for max_batch, max_pixels or max_classes < 1, MBN_EUNSUPPORTED for max_batch > 65535, max_pixels > 2^34 or
+ * max_classes > MBN_CONFUSION_MAX_CLASSES, MBN_ENOMEM when the device has no room.
+ *   mbn_surface_metrics   pure C in doubles. The pixels of all images and calls POOL in the table: every score is a MICRO average over the
+ *     dataset's contour pixels, not a mean of per-image scores. Per class, with k the direction: matched_k = n_k - unmatched_k; the class is
+ *     PRESENT iff n_0 + n_1 > 0 and MEASURABLE iff matched_0 > 0 and matched_1 > 0. cum_k (t) = the sum of bins 0..t.
+ *       hd   = sqrt (max (max_d2_0, max_d2_1))
+ *       hdp  = the larger over k of the smallest t with cum_k (t) >= ceil (percentile / 100.0 * matched_k), formed in double: whole pixels,
+ *              rounded up; when that t is the overflow bin the class counts in m.saturated and hdp = bins - 1 is a lower bound
+ *       assd = (sum256_0 + sum256_1) / 256.0 / (matched_0 + matched_1): within 1/256 pixel below the true mean
+ *       nsd  = (cum_0 (tolerance) + cum_1 (tolerance)) / (n_0 + n_1): unmatched queries count in the denominator
+ *     hd, hdp and assd are NaN for a class that is not measurable, nsd for one that is not present. m: hd, hdp, assd = the means over the
+ *     measurable classes, nsd = the mean over the present ones, summed in ascending class order (0 when there are none); n and unmatched = the
+ *     totals over classes and directions; classes_present, classes_measurable, saturated. hd, hdp, assd, nsd: [classes] or NULL.
+ *     MBN_EINVAL: NULL surf or m, classes < 1, bins < 2, tolerance outside [0, bins - 2], percentile outside (0, 100] (NaN included);
+ *     MBN_EUNSUPPORTED: classes > MBN_CONFUSION_MAX_CLASSES, bins > MBN_SURFACE_MAX_BINS. */
+#define MBN_SURFACE_HEAD 4
+#define MBN_SURFACE_MAX_BINS 4096
+#define MBN_SURFACE_UNIT 256
+typedef struct mbn_surface_metrics_t {
+    double hd, hdp, assd, nsd, n, unmatched;
+    int32_t classes_present, classes_measurable, saturated, reserved;
+} mbn_surface_metrics_t;
+typedef struct mbn_surface mbn_surface;
+int mbn_surface_create(mbn_context *ctx, int max_batch, int64_t max_pixels, int max_classes, mbn_surface **h);
+int mbn_surface_destroy(mbn_surface *h);
+int64_t mbn_surface_scratch_bytes(int max_batch, int64_t max_pixels, int max_classes);
+int mbn_surface_envelope(int truth_bytes, int classes, int bins, int batch, int rows, int cols, int edge);
+int mbn_surface_tile(int *unit_pixels, int *wave_pixels);
+int mbn_surface_metrics(const uint64_t *surf, int classes, int bins, int tolerance, double percentile, mbn_surface_metrics_t *m, double *hd,
+                        double *hdp, double *assd, double *nsd);
+int mbn_surface_score_i32(mbn_surface *h, void *surf_u64, void *dist2_u32, const void *labels_i32, const void *truth, int truth_bytes, int classes,
+                          int bins, int batch, int rows, int cols, int edge, void *stream);
+int mbn_surface_score_ragged_i32(mbn_surface *h, mbn_ragged_readout *readout, void *surf_u64, void *dist2_u32, const void *labels_i32,
+                                 const void *truth, int truth_bytes, int classes, int bins, int edge, void *stream);
 /* The classifier tail of the sequence as one call (MobileNet.c:2601-2792): global average pool (kernel.cl:116) ->
  * FC = pointwise with rows = cols = 1 (kernel.cl:94; bias, no ReLU: B15) -> softmax + top-k. fp32 NHWC,
  * in [batch][rows][cols][channels], fc_w [classes][channels], fc_bias [classes] or NULL; pooled_scratch
@@ -1563,6 +1635,14 @@ int  mbn_net_segment_regions(mbn_net *net, const void *labels_i32, void *comp_i3
 int  mbn_net_segment_boundary_score(mbn_net *net, const void *labels_i32, const void *truth, int truth_bytes, void *trimap_u64, void *biou_u64,
                                     double ratio, int d, int edge);
 int  mbn_net_segment_boundary_depth(mbn_net *net, const void *labels_i32, void *depth_u8, double ratio, int d, int edge);
+/* The surface-distance score of the label maps of that same call ("score a segmentation by surface distance" above; found exactly as
+ * mbn_net_segment_score finds it): a uniform call is one mbn_surface_score_i32, an image call mbn_surface_score_ragged_i32 on the net's own ragged
+ * set. classes is the plan's; surf_u64 [classes][2][MBN_SURFACE_HEAD + bins] is added to; dist2_u32 (at the labels' element offsets) may be NULL.
+ * The mbn_surface handle is the net's: made on first use for max_batch images, the pixels of the call and the plan's classes, made again when a
+ * later call needs more, freed by mbn_net_destroy. MBN_EINVAL before any segment call; otherwise whatever mbn_surface_create and the score call
+ * answer. */
+int  mbn_net_segment_surface(mbn_net *net, const void *labels_i32, const void *truth, int truth_bytes, int bins, int edge, void *surf_u64,
+                             void *dist2_u32);
 /* The panoptic quality of the label maps of that same call ("score a segmentation by its regions" above; found exactly as mbn_net_segment_score
  * finds it) against `truth` (uint8 or int32, truth_bytes 1 or 4; in an image call at the labels' dst_offsets): mbn_components on the labels, the same
  * on the truth (classes the plan's, `connectivity` and `min_area` for both, a label or truth value outside [0, classes) belongs to no segment:

@@ -58,6 +58,12 @@
       mbn_panoptic_i32, the panoptic quality of --batch label maps of 375 x 500 against a truth (main_panoptic): 21 / 1000 classes, 25 x 25-block
       (the prediction shifted and with noise), random and constant inputs; the scoring call alone and the whole chain of two mbn_components_i32
       and the score, beside torch.unique of the (predicted, truth) pairs on the same buffers and numpy's after a download.
+
+  python tools/dense_bench.py --surface [--reps 7] [--steps 20] [--batch 32] [--torch-steps 2] [--torch-images 2] [--host-maps 2] [--no-torch] [--no-host]
+                              [--configs blocks,constant,random,far]
+      mbn_surface_score_i32, the surface-distance table of --batch label maps of 375 x 500 against a uint8 truth (main_surface): 21 / 1000
+      classes, 64 bins, shifted noisy 25 x 25 blocks, constant, random and far-apart inputs, beside torch.cdist between each class's contour
+      coordinates on the same buffers and scipy.ndimage.distance_transform_edt per class on the host, download included; equal tables required.
 """
 import argparse
 import json
@@ -1109,6 +1115,200 @@ def main_boundary(a):
     print(json.dumps(result))
 
 
+def surface_rows(d2, bins):
+    """the cells of one class and direction of a surface table from the int64 d2 of its matched queries (numpy), without n and unmatched"""
+    import math
+    row = np.zeros(4 + bins, np.uint64)
+    if len(d2):
+        row[2] = int(d2.max())
+        row[3] = sum(math.isqrt(int(v) << 16) for v in d2)
+        t = np.array([math.isqrt(int(v)) for v in d2], np.int64)
+        row[4:] = np.bincount(np.minimum(t + (t * t < d2), bins - 1), minlength=bins).astype(np.uint64)
+    return row
+
+
+def main_surface(a):
+    """--surface: mbn_surface_score_i32 on --batch maps of 375 x 500 (6 M pixels at 32), int32 labels against uint8 truth, 64 bins, edge 1, at 21 and
+    1000 classes. Inputs: blocks (25 x 25 blocks against the same blocks shifted by one pixel, 3 % of the prediction's pixels redrawn: what a label
+    map looks like), constant (no contour but the frame), random (every pixel is a contour pixel) and far (class 1 is a strip of 40 columns at the
+    far left of the labels and at the far right of the truth: every one of its queries walks 420 rings or more, the worst case of an uncapped search).
+    Per cell, on the SAME device buffers:
+      kernel  the call (three kernels), table cleared once in front (it accumulates); with dist2 and without
+      torch   per map and class the contour coordinates of both sides (eight shifted compares), torch.cdist between them (exact mode), the row
+              minima both ways, squared and rounded, and the table's cells from them; on the first --torch-images maps, scaled to the batch
+      host    what a user has without the call: the download of both maps, then per class present the contour (mask & ~binary_erosion) and
+              scipy.ndimage.distance_transform_edt of the other side's complement read at the queries; on the first --host-maps maps, scaled
+    Both yardsticks' tables are compared with the kernel's on their maps. Each kernel figure is the median over the repetitions of `steps`
+    back-to-back calls between two stream marks; the runs are kept. floor_ms: 21 bytes a pixel over 8 TB/s (pass A reads 5 and writes the two
+    contour maps, 8; pass B reads those 8 once as queries; what the search reads beyond that comes from the cache when the match is near)."""
+    pkg = import_package()
+    torch = None
+    if not a.no_torch:
+        import torch
+        assert torch.cuda.is_available(), "the yardstick needs torch on the same GPU"
+    import time
+    n, H, W, bins, edge = a.batch, 375, 500, 64, 1
+    pix = n * H * W
+    rng = np.random.default_rng(0)
+    result = {"batch": n, "pixels": pix, "bins": bins, "edge": edge, "bytes_per_pixel": 21, "floor_ms": round(1e3 * 21.0 * pix / HBM_BYTES_PER_S, 4)}
+
+    def host_table(h_lab, h_tr, classes):
+        from scipy import ndimage
+        surf = np.zeros((classes, 2, 4 + bins), np.uint64)
+        el = np.ones((3, 3))
+        for lab, tr in zip(h_lab, h_tr):
+            maps = (lab.astype(np.int64), tr.astype(np.int64))
+            for c in np.union1d(np.unique(maps[0]), np.unique(maps[1])):
+                if not 0 <= c < classes:
+                    continue
+                cont = [(m == c) & ~ndimage.binary_erosion(m == c, structure=el, border_value=0) for m in maps]
+                for k in range(2):
+                    q = int(cont[k].sum())
+                    surf[c, k, 0] += np.uint64(q)
+                    if not q:
+                        continue
+                    if not cont[1 - k].any():
+                        surf[c, k, 1] += np.uint64(q)
+                        continue
+                    d2 = np.rint(ndimage.distance_transform_edt(~cont[1 - k]) ** 2).astype(np.int64)[cont[k]]
+                    row = surface_rows(d2, bins)
+                    surf[c, k, 2] = max(surf[c, k, 2], row[2])
+                    surf[c, k, 3] += row[3]
+                    surf[c, k, 4:] += row[4:]
+        return surf
+
+    def torch_table(t_lab, t_tr, classes, k_maps):
+        surf = torch.zeros((classes, 2, 4 + bins), dtype=torch.int64, device="cuda")
+
+        def contour(m):
+            p = torch.nn.functional.pad(m, (1, 1, 1, 1), value=-7)
+            out = torch.zeros_like(m, dtype=torch.bool)
+            for dr in range(3):
+                for dc in range(3):
+                    out |= p[dr:dr + H, dc:dc + W] != m
+            return out
+
+        def isqrt(v):
+            t = v.double().sqrt().floor().long()
+            t = torch.where(t * t > v, t - 1, t)
+            return torch.where((t + 1) * (t + 1) <= v, t + 1, t)
+
+        for i in range(k_maps):
+            maps = (t_lab[i].long(), t_tr[i].long())
+            cont = [contour(m) for m in maps]
+            present = torch.unique(torch.cat([maps[0][cont[0]], maps[1][cont[1]]]))
+            for c in present.tolist():
+                if not 0 <= c < classes:
+                    continue
+                pts = [torch.nonzero(cont[k] & (maps[k] == c)).double() for k in range(2)]
+                for k in range(2):
+                    q = pts[k].shape[0]
+                    surf[c, k, 0] += q
+                    if not q:
+                        continue
+                    if not pts[1 - k].shape[0]:
+                        surf[c, k, 1] += q
+                        continue
+                    near = torch.cat([torch.cdist(pts[k][j:j + 2048], pts[1 - k], compute_mode="donot_use_mm_for_euclid_dist").min(1).values
+                                      for j in range(0, q, 2048)])
+                    d2 = (near.double() ** 2).round().long()
+                    surf[c, k, 2] = torch.maximum(surf[c, k, 2], d2.max())
+                    surf[c, k, 3] += isqrt(d2 << 16).sum()
+                    t = isqrt(d2)
+                    surf[c, k, 4:] += torch.bincount(torch.clamp(t + (t * t < d2).long(), max=bins - 1), minlength=bins)
+        return surf
+
+    with pkg.Context(0) as ctx:
+        for classes in (21, 1000):
+            tc = min(classes, 256)
+            yy, xx = np.mgrid[0:H, 0:W]
+            blocks = rng.integers(0, tc, (n, H // 25 + 1, W // 25 + 2))
+            shifted = blocks[:, yy // 25, (xx + 1) // 25].astype(np.int32)
+            noise = rng.random((n, H, W)) < 0.03
+            shifted[noise] = rng.integers(0, classes, int(noise.sum()))
+            far_l, far_t = np.zeros((n, H, W), np.int32), np.zeros((n, H, W), np.uint8)
+            far_l[:, :, :40], far_t[:, :, W - 40:] = 1, 1
+            inputs = {"blocks": (shifted, blocks[:, yy // 25, xx // 25].astype(np.uint8)),
+                      "constant": (np.full((n, H, W), classes - 1, np.int32), np.full((n, H, W), tc - 1, np.uint8)),
+                      "random": (rng.integers(0, classes, (n, H, W)).astype(np.int32), rng.integers(0, tc, (n, H, W)).astype(np.uint8)),
+                      "far": (far_l, far_t)}
+            inputs = {k: (np.ascontiguousarray(v[0]), np.ascontiguousarray(v[1])) for k, v in inputs.items()}
+            cells = classes * 2 * (4 + bins)
+            d_surf, d_d2 = ctx.alloc(cells * 8), ctx.alloc(pix * 4)
+            h = pkg.Surface(ctx, n, pix, classes)
+            for name, (lab, tr) in inputs.items():
+                if a.configs and name not in a.configs.split(","):
+                    continue
+                if name == "far" and classes != 21:
+                    continue
+                if torch is not None:
+                    t_lab, t_tr = torch.from_numpy(lab).cuda(), torch.from_numpy(tr).cuda()
+                    p_lab, p_tr = t_lab.data_ptr(), t_tr.data_ptr()
+                else:
+                    t_lab, t_tr = ctx.to_device(lab), ctx.to_device(tr)
+                    p_lab, p_tr = t_lab.ptr, t_tr.ptr
+
+                def table_of(k_maps):
+                    ctx.lib.mbn_memset(ctx.h, d_surf.ptr, 0, cells * 8)
+                    ctx.surface_score(h, d_surf.ptr, p_lab, p_tr, 1, classes, bins, k_maps, H, W, edge)
+                    ctx.sync()
+                    return d_surf.download((classes, 2, 4 + bins), np.uint64)
+
+                full = table_of(n)
+                out = {"queries": int(full[:, :, 0].sum()), "unmatched": int(full[:, :, 1].sum()), "max_d2": int(full[:, :, 2].max())}
+                k_host, k_torch = min(a.host_maps, n), min(a.torch_images, n)
+                if not a.no_host:
+                    t0 = time.perf_counter()
+                    h_lab, h_tr = np.empty((n, H, W), np.int32), np.empty((n, H, W), np.uint8)
+                    ctx.lib.mbn_download(ctx.h, h_lab.ctypes.data, p_lab, h_lab.nbytes)
+                    ctx.lib.mbn_download(ctx.h, h_tr.ctypes.data, p_tr, h_tr.nbytes)
+                    t_dl = time.perf_counter() - t0
+                    t0 = time.perf_counter()
+                    host = host_table(h_lab[:k_host], h_tr[:k_host], classes)
+                    out.update({"host_ms": round(1e3 * (t_dl + (time.perf_counter() - t0) * n / k_host), 1), "host_maps": k_host,
+                                "table_equal_host": bool(np.array_equal(host, table_of(k_host)))})
+                if torch is not None:
+                    want = torch_table(t_lab, t_tr, classes, k_torch)        # once in front: compared, and the allocator is warm
+                    out["table_equal_torch"] = bool(np.array_equal(want.cpu().numpy().astype(np.uint64), table_of(k_torch)))
+                    ts = []
+                    for _ in range(max(1, a.torch_steps)):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        torch_table(t_lab, t_tr, classes, k_torch)
+                        torch.cuda.synchronize()
+                        ts.append(1e3 * (time.perf_counter() - t0) * n / k_torch)
+                    out.update({"torch_ms": round(statistics.median(ts), 1), "torch_runs_ms": [round(v, 1) for v in ts], "torch_maps": k_torch})
+                for key, d2 in (("kernel", None), ("kernel_dist2", d_d2.ptr)):
+                    fn = lambda: ctx.surface_score(h, d_surf.ptr, p_lab, p_tr, 1, classes, bins, n, H, W, edge, dist2=d2)
+                    steps = 2 if name == "far" else a.steps
+                    marks_ms(ctx, fn, 1)
+                    ks = [marks_ms(ctx, fn, steps) for _ in range(a.reps)]
+                    k = statistics.median(ks)
+                    out.update({key + "_ms": round(k, 4), key + "_runs_ms": [round(v, 4) for v in ks]})
+                k = out["kernel_ms"]
+                out["share_of_hbm"] = round(21.0 * pix / (k * 1e-3) / HBM_BYTES_PER_S, 4)
+                if "host_ms" in out:
+                    out["host_over_kernel"] = round(out["host_ms"] / k, 1)
+                if "torch_ms" in out:
+                    out["torch_over_kernel"] = round(out["torch_ms"] / k, 1)
+                print("classes %4d %-8s: kernel %.4f ms (%.4f - %.4f, %.2f %% of 8 TB/s at 21 B/pixel), with dist2 %.4f ms; queries %d, unmatched %d, "
+                      "max_d2 %d; torch %s ms (equal %s)  host %s ms (equal %s)" %
+                      (classes, name, k, min(out["kernel_runs_ms"]), max(out["kernel_runs_ms"]), 100 * out["share_of_hbm"], out["kernel_dist2_ms"],
+                       out["queries"], out["unmatched"], out["max_d2"], out.get("torch_ms", "-"), out.get("table_equal_torch", "-"),
+                       out.get("host_ms", "-"), out.get("table_equal_host", "-")), flush=True)
+                result["classes_%d_%s" % (classes, name)] = out
+                if torch is not None:
+                    del t_lab, t_tr
+                    torch.cuda.empty_cache()
+                else:
+                    t_lab.free()
+                    t_tr.free()
+            h.close()
+            d_surf.free()
+            d_d2.free()
+    print(json.dumps(result))
+
+
 def pq_from_pairs(img, p, g, cnt, rec_p, n_p, rec_t, n_t, classes):
     """pq uint64 [classes][4] from the pair histogram of a batch: (img, p, g) unique with p >= 0, g = -1 over void truth, cnt pixels each. The match
     rule of include/mbn.h, "score a segmentation by its regions", vectorised; rec_*: int64 [batch][cap][8], n_*: [batch]"""
@@ -1300,9 +1500,12 @@ def main():
     ap.add_argument("--host-maps", type=int, default=2, help="--regions, --boundary: the maps the host yardstick really works on (its time is scaled to the batch)")
     ap.add_argument("--no-host", action="store_true", help="--regions, --boundary: skip the host yardstick")
     ap.add_argument("--calibration", action="store_true", help="time mbn_calibration_f32 beside mbn_confusion_i32 and torch instead: see main_calibration")
+    ap.add_argument("--surface", action="store_true", help="time mbn_surface_score_i32 beside torch.cdist and scipy's distance transform instead: see main_surface")
     a = ap.parse_args()
     if a.calibration:
         return main_calibration(a)
+    if a.surface:
+        return main_surface(a)
     if a.panoptic:
         return main_panoptic(a)
     if a.boundary:
