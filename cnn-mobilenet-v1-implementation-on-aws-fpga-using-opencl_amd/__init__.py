@@ -154,6 +154,12 @@ class Calibration(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("pixels", "answered", "abstained", "void_pixels", "accuracy", "mean_confidence", "ece", "mce", "aurc")]
 
 
+class Nll(C.Structure):
+    """mbn_nll: what mbn_nll_metrics derives from one temperature plane of an NLL table."""
+    _fields_ = [(n, C.c_double) for n in ("pixels", "scored", "void_pixels", "nll", "brier", "accuracy", "mean_class_nll", "mean_class_brier")] + \
+               [("classes_present", C.c_int)]
+
+
 class PanopticMetrics(C.Structure):
     """mbn_panoptic_metrics_t (include/mbn.h, "score a segmentation by its regions")"""
     _fields_ = [(n, C.c_double) for n in ("pq", "sq", "rq", "tp", "fp", "fn")] + [("classes_present", C.c_int32), ("reserved", C.c_int32)]
@@ -282,6 +288,12 @@ def _declare_host(lib):
     lib.mbn_calibration_envelope.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64]
     lib.mbn_calibration_metrics.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.POINTER(Calibration)] + [C.POINTER(C.c_double)] * 4
     lib.mbn_calibration_threshold.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_double, C.POINTER(C.c_float)] + [C.POINTER(C.c_double)] * 2
+    lib.mbn_resample_nll_envelope.argtypes = [C.c_int] * 6 + [C.POINTER(C.c_int32)] + [C.c_int] * 4
+    lib.mbn_resample_nll_ragged_check.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64]              # mbn_envelope.h, like the next
+    lib.mbn_nll_temps_check.argtypes = [C.POINTER(C.c_float), C.c_int]
+    lib.mbn_nll_metrics.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, C.POINTER(Nll)] + [C.POINTER(C.c_double)] * 2
+    lib.mbn_nll_best.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                 C.POINTER(C.c_int)]
     lib.mbn_components_envelope.argtypes = [C.c_int] * 7
     lib.mbn_components_tile.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.mbn_components_scratch_bytes.argtypes = [C.c_int, C.c_int64]
@@ -466,6 +478,9 @@ def load():
         lib.mbn_calibration_f32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, C.c_int64, vp]
         lib.mbn_calibration_ragged_f32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, vp]
         lib.mbn_net_segment_calibration.argtypes = [vp, vp, vp, vp, ci, ci, vp]
+        lib.mbn_resample_nll_f32.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, C.POINTER(C.c_int32), ci, ci, C.POINTER(C.c_float), ci, vp]
+        lib.mbn_resample_nll_ragged_f32.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, ci, C.POINTER(C.c_float), ci, vp]
+        lib.mbn_net_segment_nll.argtypes = [vp, vp, ci, C.POINTER(C.c_float), ci, vp, vp, vp, C.c_int64]
         lib.mbn_net_segment_topk_fit.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, C.c_float, ci]
         lib.mbn_net_segment_topk_images_fit.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, ci, ci, C.c_int64,
                                                         vp, C.POINTER(C.c_int64), vp, vp, C.c_float, ci]
@@ -914,6 +929,53 @@ def calibration_threshold(calib, bins, target_accuracy, lib=None):
     return p.value, cov.value, sel.value
 
 
+NLL_MAX_TEMPS = 8
+NLL_CAP = 32768.0
+NLL_ONE = 1 << 16                   # the fixed point of a table's NLL column (the Brier column: CALIBRATION_ONE)
+
+
+def _inv_temps(inv_temps):
+    """a host array of fp32 inverse temperatures as ctypes, and its length"""
+    v = [float(b) for b in inv_temps]
+    return (C.c_float * max(len(v), 1))(*v), len(v)
+
+
+def nll_envelope(batch, rows, cols, classes, in_rows, in_cols, rect, out_rows, out_cols, truth_bytes, temps, lib=None) -> int:
+    """mbn_resample_nll_envelope: the status mbn_resample_nll_f32 gives the shape, the window rect (None: the whole map), the truth and temps."""
+    return (lib or host_lib()).mbn_resample_nll_envelope(batch, rows, cols, classes, in_rows, in_cols, None if rect is None else _rect(rect),
+                                                         out_rows, out_cols, truth_bytes, temps)
+
+
+def _nll_table(table, classes, temps):
+    n = np.ascontiguousarray(table, dtype=np.uint64)
+    if n.size != temps * (classes + 1) * 4:
+        raise ValueError("the table has %d cells, classes = %d and temps = %d need %d" % (n.size, classes, temps, temps * (classes + 1) * 4))
+    return n
+
+
+def nll_metrics(table, classes, temps, j, lib=None):
+    """mbn_nll_metrics: (Nll, class_nll float64 [classes], class_brier float64 [classes]) of plane j of table, uint64 [temps][classes + 1][4]."""
+    n = _nll_table(table, classes, temps)
+    m, cn, cb = Nll(), np.empty(max(classes, 1), np.float64), np.empty(max(classes, 1), np.float64)
+    dp = C.POINTER(C.c_double)
+    _chk((lib or host_lib()).mbn_nll_metrics(n.ctypes.data_as(C.POINTER(C.c_uint64)), classes, temps, j, C.byref(m), cn.ctypes.data_as(dp),
+                                             cb.ctypes.data_as(dp)), "nll_metrics")
+    return m, cn, cb
+
+
+def nll_best(table, classes, inv_temps, lib=None):
+    """mbn_nll_best: (best index, refined inverse temperature, at_edge) of a table over the strictly ascending grid inv_temps; None when nothing
+    is scored (MBN_ENOTFOUND)."""
+    arr, temps = _inv_temps(inv_temps)
+    n = _nll_table(table, classes, temps)
+    best, beta, edge = C.c_int(), C.c_double(), C.c_int()
+    rc = (lib or host_lib()).mbn_nll_best(n.ctypes.data_as(C.POINTER(C.c_uint64)), classes, temps, arr, C.byref(best), C.byref(beta), C.byref(edge))
+    if rc == ENOTFOUND:
+        return None
+    _chk(rc, "nll_best")
+    return best.value, beta.value, edge.value
+
+
 COMPONENTS_MAX_REGIONS = 1 << 24
 
 
@@ -1271,6 +1333,22 @@ class Context:
         map. prob None with min_prob 0: the logit form. `score` may be None. min_prob / ignore_label act on plane 0 only."""
         _chk(self.lib.mbn_resample_topk_f32(self.h, labels, prob, score, logits, batch, rows, cols, classes, in_rows, in_cols,
                                             None if rect is None else _rect(rect), out_rows, out_cols, k, min_prob, ignore_label, stream),
+             self.last_error())
+
+    def resample_nll(self, table, nll, brier, logits, truth, truth_bytes, batch, rows, cols, classes, out_rows, out_cols, inv_temps, rect=None,
+                     in_rows=0, in_cols=0, stream=None):
+        """mbn_resample_nll_f32: table (uint64 [temps][classes + 1][4], device) += per truth class and inverse temperature the pixels, their NLL in
+        2^-16 and Brier score in 2^-24 fixed point and the pixels labelled correctly; nll / brier (fp32 [temps][batch][out_rows][out_cols], either
+        may be None) get the per-pixel values, -1 on void pixels. truth (uint8 or int32) is [batch][out_rows][out_cols]; inv_temps a host list."""
+        arr, temps = _inv_temps(inv_temps)
+        _chk(self.lib.mbn_resample_nll_f32(self.h, table, nll, brier, logits, truth, truth_bytes, batch, rows, cols, classes, in_rows, in_cols,
+                                           None if rect is None else _rect(rect), out_rows, out_cols, arr, temps, stream), self.last_error())
+
+    def resample_nll_ragged(self, readout, table, nll, brier, plane_stride, logits, truth, truth_bytes, inv_temps, stream=None):
+        """mbn_resample_nll_ragged_f32: the same over the maps of a RaggedReadout's set; temperature j of item i at j * plane_stride + dst_offset_i
+        elements of nll / brier, truth at the items' element offsets."""
+        arr, temps = _inv_temps(inv_temps)
+        _chk(self.lib.mbn_resample_nll_ragged_f32(readout.h, table, nll, brier, plane_stride, logits, truth, truth_bytes, arr, temps, stream),
              self.last_error())
 
     def topk_rank(self, ranks, labels, k, plane_stride, truth, truth_bytes, classes, count, stream=None):
@@ -1748,6 +1826,14 @@ class Net:
         """mbn_net_segment_calibration: calib (uint64 [bins + 1][4]) += the calibration table of the maps and probabilities the most recent successful
         segment call wrote (Context.calibration; the net's own set after an image call), with the plan's classes."""
         _chk(self.ctx.lib.mbn_net_segment_calibration(self.h, labels_ptr, prob_ptr, truth_ptr, truth_bytes, bins, calib_ptr), self.ctx.last_error())
+
+    def segment_nll(self, truth_ptr, truth_bytes, inv_temps, table_ptr, nll_ptr=None, brier_ptr=None, plane_stride=0):
+        """mbn_net_segment_nll: table (uint64 [temps][classes + 1][4]) += the NLL / Brier table of the probabilities of the most recent successful
+        segment call, read out again from the net's dense logits (Context.resample_nll; the net's own set after an image call, which reads
+        plane_stride). Raises EUNSUPPORTED after a views or slide call, EINVAL before any call."""
+        arr, temps = _inv_temps(inv_temps)
+        _chk(self.ctx.lib.mbn_net_segment_nll(self.h, truth_ptr, truth_bytes, arr, temps, table_ptr, nll_ptr, brier_ptr, plane_stride),
+             self.ctx.last_error())
 
     def resize_views(self, src_ptr, batch, in_rows, in_cols, scales, mirrors) -> int:
         """mbn_net_resize_views: uint8 sources [batch][in_rows][in_cols][3] -> the net's staging buffer, view-major: view k = fit_view(scales[k],

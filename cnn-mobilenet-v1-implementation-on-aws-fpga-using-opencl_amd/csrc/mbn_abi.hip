@@ -1056,6 +1056,54 @@ int mbn_resample_topk_ragged_f32(mbn_ragged_readout *r, void *labels_i32, void *
                         });
 }
 
+// What the two NLL read-outs share: the pointer and alignment checks and the temperatures (MBN_EINVAL) in front of the shape's limits, the spans
+// (`span` elements of truth and of one plane of each map, `plane` elements from plane to plane), the launch
+extern "C++" {
+template <typename Launch>
+static int nll_call(mbn_context *ctx, void *nll_u64, void *nll_f32, void *brier_f32, const void *logits, const void *truth, int truth_bytes,
+                    int classes, const float *inv_temps, int temps, int shape, double logits_bytes, double span, double plane, void *stream,
+                    Launch launch)
+{
+    if (!ctx || !nll_u64 || !logits || !truth || !inv_temps || shape == MBN_EINVAL) return MBN_EINVAL;
+    if ((uintptr_t)nll_u64 % 8 || ((uintptr_t)nll_f32 | (uintptr_t)brier_f32 | (uintptr_t)logits) % 4 || (truth_bytes == 4 && (uintptr_t)truth % 4))
+        return MBN_EINVAL;
+    if (mbn_nll_temps_check(inv_temps, temps) != MBN_OK) return MBN_EINVAL;
+    if (shape != MBN_OK) return shape;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    const double map_bytes = 4.0 * ((double)(temps - 1) * plane + span);
+    MBN_SPANS(ctx, { nll_u64, 32.0 * temps * (classes + 1), "nll table" }, { nll_f32, map_bytes, "nll map" }, { brier_f32, map_bytes, "brier map" },
+              { logits, logits_bytes, "nll logits" }, { truth, (double)truth_bytes * span, "nll truth" });
+    Scope sc(ctx, s);
+    return sc.finish(launch(s));
+}
+}   // extern "C++"
+
+int mbn_resample_nll_f32(mbn_context *ctx, void *nll_u64, void *nll_f32, void *brier_f32, const void *logits, const void *truth, int truth_bytes,
+                         int batch, int rows, int cols, int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols,
+                         const float *inv_temps, int temps, void *stream)
+{
+    const int shape = mbn_resample_nll_envelope(batch, rows, cols, classes, in_rows, in_cols, rect, out_rows, out_cols, truth_bytes, temps);
+    const double span = shape == MBN_OK ? (double)batch * out_rows * out_cols : 0.0;
+    return nll_call(ctx, nll_u64, nll_f32, brier_f32, logits, truth, truth_bytes, classes, inv_temps, temps, shape,
+                    4.0 * batch * rows * cols * classes, span, span, stream, [&](hipStream_t s) {
+                        return mbn_launch_f32_resample_nll(ctx, s, nll_u64, (float *)nll_f32, (float *)brier_f32, (const float *)logits, truth,
+                                                           truth_bytes, batch, rows, cols, classes, in_rows, in_cols, rect, out_rows, out_cols,
+                                                           inv_temps, temps);
+                    });
+}
+
+int mbn_resample_nll_ragged_f32(mbn_ragged_readout *r, void *nll_u64, void *nll_f32, void *brier_f32, int64_t plane_stride, const void *logits,
+                                const void *truth, int truth_bytes, const float *inv_temps, int temps, void *stream)
+{
+    if (!r || r->batch <= 0) return MBN_EINVAL;                  // no set: nothing to score
+    const int shape = mbn_resample_nll_ragged_check(r->classes, r->launch.span, truth_bytes, temps, plane_stride);
+    return nll_call(r->ctx, nll_u64, nll_f32, brier_f32, logits, truth, truth_bytes, r->classes, inv_temps, temps, shape,
+                    4.0 * r->batch * r->rows * r->cols * r->classes, (double)r->launch.span, (double)plane_stride, stream, [&](hipStream_t s) {
+                        return mbn_launch_f32_resample_nll_ragged(r, s, nll_u64, (float *)nll_f32, (float *)brier_f32, plane_stride,
+                                                                  (const float *)logits, truth, truth_bytes, inv_temps, temps);
+                    });
+}
+
 // What the two rank-score calls share: confusion_call's checks with the rank table and the k label planes
 extern "C++" {
 template <typename Launch>

@@ -928,7 +928,376 @@ void topk_launch(hipStream_t s, int batch, const mbn_resample_launch_t &l, TopkA
     hipLaunchKernelGGL(topk_kernels[k > 4][q != nullptr][vec], dim3((unsigned)l.tiles, (unsigned)batch), dim3(256), (size_t)l.lds_bytes, s, a);
 }
 
+// ---- NLL (mbn_resample_nll_f32, _ragged_f32; include/mbn.h, "score the probabilities"): the negative log-likelihood and the Brier score of every
+// output pixel's softmax distribution against a ground truth at the output resolution, at up to eight inverse temperatures in one pass, stored as
+// maps and added to the table [temps][classes + 1][4]. Kernels of their own on resample_tile's tile, under the top-k's conventions: one index /
+// weight rule (the window's), uniform and ragged in one kernel (a.set.head says which). What differs:
+//   passes  TWO over the class chunks. Pass 1 is the argmax loop itself (rs_reduce without PROB: best and label have the argmax read-out's bits).
+//           Pass 2 forms every v again (a launch of one chunk finds it still staged; more chunks are staged again) and, with d = v - best <= 0,
+//           adds e = exp2(d * k_j) to S[r][j] and e * e to Q[r][j] for every temperature j, k_j = fp32(beta_j * log2 e) from the host; the
+//           truth's own interpolant v_t is picked where c == t. Nothing overflows at beta = 16, and the lerps are shared by the temperatures
+//   state   T is a template CAPACITY (1, 4 or 8), as the top-k's K: the loops over the temperatures are unrolled with a uniform guard, so the
+//           4 x T x 2 accumulators are indexed at compile time only and stay in registers. The operations of one temperature are written once
+//           (nl_diff, nl_term, nl_score), contraction off: its bits do not depend on the capacity or on the other temperatures
+//   table   64-bit integer atomics, aggregated per wave: the lanes that hold one truth class elect the first of them, which adds the wave's
+//           count, both fixed-point sums and the correct count once per temperature (mbn_f32_calibration.hip's election, here over a lane's four
+//           rows). Label maps are coherent, so a wave holds one to three classes as a rule; after NL_LEADERS rounds what is left adds on its own.
+//           Every lane of a workgroup stays to the end for it (no early return of the lanes past the image)
+struct NllArgs {
+    unsigned long long *table;
+    float *nll, *brier;      // either may be null
+    const float *logits;
+    const uint8_t *truth;    // element 0 of the truth, uint8 or int32
+    int truth_bytes;
+    int rows, cols, classes;
+    int out_rows, out_cols, tiles_x;      // uniform form
+    int fy, fx, ch;
+    int temps;               // 1 .. T
+    long long plane;         // elements from temperature j to j + 1 of the two maps
+    int in_rows, in_cols;    // the network input the windows lie in (a plain set: rows, cols)
+    int wx, wy, wiw, wih;    // uniform form: the window
+    mbn_label_set set;       // ragged form (mbn_label_set.h), else a null head
+    float beta[MBN_NLL_MAX_TEMPS], k2[MBN_NLL_MAX_TEMPS];      // beta_j and fp32(beta_j * log2 e)
+};
+
+constexpr int NL_LEADERS = 4;             // distinct truth classes a wave aggregates
+
+// d = v - best for the exponent: <= 0 under a finite best. A NaN v (a padding class among them) gives -3e38, whose term is exp2(-inf) = 0 exactly
+__device__ __forceinline__ float nl_diff(float v, float best)
+{
+#pragma clang fp contract(off)
+    return __builtin_fmaxf(v - best, -3.0e38f);
+}
+
+// e = exp(beta d) as exp2(d * k): one product, v_exp_f32 (a result below 2^-126 may flush to 0, against S >= 1)
+__device__ __forceinline__ float nl_term(float d, float k)
+{
+#pragma clang fp contract(off)
+    return __builtin_amdgcn_exp2f(d * k);
+}
+
+// the stored (nll, brier) of one pixel at one temperature from its sums, its truth's interpolant vt (NaN: none was picked) and best
+__device__ __forceinline__ void nl_score(float S, float Q, float vt, float best, float beta, float k, float *nll, float *brier)
+{
+#pragma clang fp contract(off)
+    const bool have = vt > -__builtin_inff();                                                  // not for a NaN, not for -inf
+    const float inv = 1.0f / S;
+    const float xt = beta * (vt - best);
+    const float et = have ? nl_term(nl_diff(vt, best), k) : 0.0f;                               // the term the sums hold for the truth
+    float n = have ? __builtin_amdgcn_logf(S) * 0.693147180559945309f - xt : MBN_NLL_CAP;       // v_log_f32 is log2; S >= 1 is normal
+    const float p = et * inv, q = (Q * inv) * inv;
+    float b = (1.0f - 2.0f * p) + q;
+    if (!(__builtin_fabsf(best) < __builtin_inff())) { n = MBN_NLL_CAP; b = 1.0f; }             // nothing won, or a +inf winner
+    *nll = __builtin_fminf(__builtin_fmaxf(n, 0.0f), MBN_NLL_CAP);
+    *brier = __builtin_fminf(__builtin_fmaxf(b, 0.0f), 2.0f);
+}
+
+// the sum of v over the 64 lanes of a wave; every lane of the wave is active (the caller)
+__device__ __forceinline__ unsigned long long nl_wave_sum(unsigned long long v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, d, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), d, 64);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+
+// pass 2 over one staged chunk: rs_reduce's products and sums in the same order, then per temperature the two sums
+template <int T, bool CROSS>
+__device__ __forceinline__ void nl_reduce(const float *(&p)[3][2], int cn4, int c0, float wx0, float wx1, const float (&wy0)[RS_ROWS],
+                                          const float (&wy1)[RS_ROWS], const bool (&up)[RS_ROWS], const float (&best)[RS_ROWS], const int (&t)[RS_ROWS],
+                                          const NllArgs &a, float (&vt)[RS_ROWS], float (&S)[RS_ROWS][T], float (&Q)[RS_ROWS][T])
+{
+    constexpr int NT = CROSS ? 3 : 2;
+    for (int c = 0; c < cn4; c += 4) {
+        f4 v0[NT], v1[NT];
+        float d[RS_ROWS][4];
+#pragma unroll
+        for (int j = 0; j < NT; j++) {
+            v0[j] = *reinterpret_cast<const f4 *>(p[j][0] + c);
+            v1[j] = *reinterpret_cast<const f4 *>(p[j][1] + c);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            float h[NT];
+#pragma unroll
+            for (int j = 0; j < NT; j++) h[j] = rs_lerp(v0[j][k], wx0, v1[j][k], wx1);      // horizontal first
+#pragma unroll
+            for (int r = 0; r < RS_ROWS; r++) {
+                const float ta = CROSS && up[r] ? h[1] : h[0], tb = CROSS && up[r] ? h[NT - 1] : h[1];
+                const float v = rs_lerp(ta, wy0[r], tb, wy1[r]);                            // then vertical
+                if (c0 + c + k == t[r]) vt[r] = v;
+                d[r][k] = nl_diff(v, best[r]);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < T; j++) {
+            if (j >= a.temps) break;
+            const float kj = a.k2[j];
+#pragma unroll
+            for (int r = 0; r < RS_ROWS; r++) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+#pragma clang fp contract(off)
+                    const float e = nl_term(d[r][k], kj);
+                    S[r][j] += e;                                                           // ascending class order
+                    Q[r][j] += e * e;
+                }
+            }
+        }
+    }
+}
+
+// what one key (a truth class, or `classes`: void) adds to plane j of the table: n pixels, `right` of them labelled correctly, the fixed-point sums
+__device__ __forceinline__ void nl_add(const NllArgs &a, int j, int key, unsigned n, unsigned right, unsigned long long qn, unsigned long long qb)
+{
+    unsigned long long *row = a.table + ((size_t)j * (size_t)(a.classes + 1) + (size_t)key) * 4;
+    atomicAdd(row, (unsigned long long)n);
+    if (key == a.classes) return;                                                           // void: the count alone
+    if (qn) atomicAdd(row + 1, qn);
+    if (qb) atomicAdd(row + 2, qb);
+    if (right) atomicAdd(row + 3, (unsigned long long)right);
+}
+
+template <int T, bool VEC>
+__global__ __launch_bounds__(256) void resample_nll_f32(const NllArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_rs[];
+    const int tid = threadIdx.x;
+    // ---- this workgroup's image: its output size, its place in a plane, its windows and its tile (resample_topk_f32's)
+    int H = a.out_rows, W = a.out_cols, tiles_x = a.tiles_x;
+    size_t dst = (size_t)blockIdx.y * ((size_t)a.out_rows * a.out_cols);                          // 64-bit bases, 32-bit offsets inside a map
+    RsWindow wy = { a.in_rows, a.wy, a.wih }, wx = { a.in_cols, a.wx, a.wiw };
+    if (a.set.head) {
+        // a replay of a captured launch after another set: the items are no longer the ones its grid, LDS and spans were checked for
+        if (mbn_label_set_stale(a.set) || (int)blockIdx.y >= a.set.head->batch) return;
+        const mbn_label_item *at = mbn_label_set_item(a.set, (int)blockIdx.y);
+        const mbn_label_item it = *at;
+        H = it.rows; W = it.cols;
+        dst = (size_t)it.dst_offset;
+        tiles_x = (W + RS_TILE - 1) / RS_TILE;
+        if (a.set.item_bytes == (int)sizeof(mbn_label_window_item)) {
+            const mbn_label_window_item wi = *(const mbn_label_window_item *)at;
+            wy.b = wi.y; wy.l = wi.ih; wx.b = wi.x; wx.l = wi.iw;
+        }
+    }
+    const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
+    if (ty >= (H + RS_TILE - 1) / RS_TILE) return;                                              // ragged: past this image's tiles
+    const float *__restrict__ src = a.logits + (size_t)blockIdx.y * ((size_t)a.rows * a.cols * a.classes);
+
+    // ---- resample_tile's lane state under the window rule
+    const int ld = a.ch + 4, nv = a.fy * a.fx;
+    int ybase, xbase;
+    float unused;
+    rs_coord<true>(RS_TILE * ty, a.rows, H, wy, &ybase, &unused);
+    rs_coord<true>(RS_TILE * tx, a.cols, W, wx, &xbase, &unused);
+    const int ox = RS_TILE * tx + (tid & 31), oy0 = RS_TILE * ty + RS_ROWS * (tid >> 5);
+    const bool active = ox < W && oy0 < H;
+    int x0, ya = 0;
+    float wx1, wy1[RS_ROWS], wy0[RS_ROWS];
+    bool up[RS_ROWS];
+    rs_coord<true>(min(ox, W - 1), a.cols, W, wx, &x0, &wx1);
+    const float wx0 = 1.0f - wx1;
+#pragma unroll
+    for (int r = 0; r < RS_ROWS; r++) {
+        int r0;
+        rs_coord<true>(min(oy0 + r, H - 1), a.rows, H, wy, &r0, &wy1[r]);
+        wy0[r] = 1.0f - wy1[r];
+        if (r == 0) ya = r0;
+        up[r] = r0 != ya;                     // r0 is ya or ya + 1: four rows span less than one coarse row
+    }
+    const bool cross = __ballot(up[1] || up[2] || up[3]) != 0;
+    // inside the staged block by construction; the clamps keep every read inside the launch's LDS whatever the arguments
+    const int last_y = a.rows - 1, last_x = a.cols - 1;
+    const int sx0 = min(max(x0 - xbase, 0), a.fx - 1), sx1 = min(max(min(x0 + 1, last_x) - xbase, 0), a.fx - 1);
+    const float *p[3][2];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const int sy = min(max(min(ya + j, last_y) - ybase, 0), a.fy - 1);
+        p[j][0] = s_rs + (sy * a.fx + sx0) * ld;
+        p[j][1] = s_rs + (sy * a.fx + sx1) * ld;
+    }
+
+    // ---- the truth of the lane's pixels: a class, `classes` for a void pixel, -1 where the lane has no pixel (past the image)
+    const unsigned out = (unsigned)(oy0 * W + ox);        // 32-bit inside an image: its map is below 2^31 bytes
+    int t[RS_ROWS];
+#pragma unroll
+    for (int r = 0; r < RS_ROWS; r++) {
+        t[r] = -1;
+        if (active && oy0 + r < H) {
+            const size_t e = dst + out + (unsigned)(r * W);
+            const int v = a.truth_bytes == 1 ? (int)a.truth[e] : ((const int32_t *)a.truth)[e];
+            t[r] = (unsigned)v < (unsigned)a.classes ? v : a.classes;
+        }
+    }
+
+    // ---- pass 1: the argmax loop
+    float best[RS_ROWS], ref[RS_ROWS], sum[RS_ROWS];      // ref, sum: rs_reduce's PROB state, unused
+    int label[RS_ROWS];
+#pragma unroll
+    for (int r = 0; r < RS_ROWS; r++) { best[r] = ref[r] = -__builtin_inff(); sum[r] = 0.0f; label[r] = 0; }
+    for (int c0 = 0; c0 < a.classes; c0 += a.ch) {
+        const int cn = min(a.ch, a.classes - c0), cn4 = (cn + 3) & ~3;
+        rs_stage<VEC>(s_rs, src, ybase, xbase, a.fx, nv, ld, a.cols, a.classes, last_y, last_x, c0, cn, cn4, tid);
+        __syncthreads();
+        if (active) {
+            if (cross) rs_reduce<true, false>(p, cn4, c0, wx0, wx1, wy0, wy1, up, best, label, ref, sum);
+            else rs_reduce<false, false>(p, cn4, c0, wx0, wx1, wy0, wy1, up, best, label, ref, sum);
+        }
+        if (a.classes > a.ch) __syncthreads();            // one chunk: it stays staged for pass 2
+    }
+
+    // ---- pass 2: the sums of every temperature under the final best
+    float S[RS_ROWS][T], Q[RS_ROWS][T], vt[RS_ROWS];
+#pragma unroll
+    for (int r = 0; r < RS_ROWS; r++) {
+        vt[r] = __builtin_nanf("");
+#pragma unroll
+        for (int j = 0; j < T; j++) S[r][j] = Q[r][j] = 0.0f;
+    }
+    for (int c0 = 0; c0 < a.classes; c0 += a.ch) {
+        const int cn = min(a.ch, a.classes - c0), cn4 = (cn + 3) & ~3;
+        if (a.classes > a.ch) {
+            rs_stage<VEC>(s_rs, src, ybase, xbase, a.fx, nv, ld, a.cols, a.classes, last_y, last_x, c0, cn, cn4, tid);
+            __syncthreads();
+        }
+        if (active) {
+            if (cross) nl_reduce<T, true>(p, cn4, c0, wx0, wx1, wy0, wy1, up, best, t, a, vt, S, Q);
+            else nl_reduce<T, false>(p, cn4, c0, wx0, wx1, wy0, wy1, up, best, t, a, vt, S, Q);
+        }
+        if (a.classes > a.ch) __syncthreads();
+    }
+
+    // ---- the scores, the maps (a void pixel: -1) and the fixed-point terms of the table, from the values stored
+    unsigned qn[RS_ROWS][T], qb[RS_ROWS][T];
+#pragma unroll
+    for (int j = 0; j < T; j++) {
+        if (j >= a.temps) break;
+        float *__restrict__ nll = a.nll ? a.nll + (size_t)j * (size_t)a.plane + dst : nullptr;
+        float *__restrict__ brier = a.brier ? a.brier + (size_t)j * (size_t)a.plane + dst : nullptr;
+#pragma unroll
+        for (int r = 0; r < RS_ROWS; r++) {
+            float n, b;
+            nl_score(S[r][j], Q[r][j], vt[r], best[r], a.beta[j], a.k2[j], &n, &b);
+            qn[r][j] = (unsigned)(n * 65536.0f);                                            // exact: powers of two; at most 2^31 and 2^25
+            qb[r][j] = (unsigned)(b * 16777216.0f);
+            if (t[r] < 0) continue;
+            const bool scored = t[r] < a.classes;
+            if (nll) nll[out + (unsigned)(r * W)] = scored ? n : -1.0f;
+            if (brier) brier[out + (unsigned)(r * W)] = scored ? b : -1.0f;
+        }
+    }
+
+    // ---- the table: every lane of the wave is here; one add per distinct truth class and temperature, by the first lane that still holds one
+    unsigned todo = 0;
+#pragma unroll
+    for (int r = 0; r < RS_ROWS; r++) todo |= (unsigned)(t[r] >= 0) << r;
+    for (int it = 0; it < NL_LEADERS; it++) {
+        int mine = -1;
+#pragma unroll
+        for (int r = RS_ROWS - 1; r >= 0; r--)
+            if (todo >> r & 1u) mine = t[r];
+        const unsigned long long pending = __ballot(mine >= 0);
+        if (!pending) break;
+        const int first = __ffsll((long long)pending) - 1;
+        const int lead = __builtin_amdgcn_readlane(mine, first);
+        unsigned match = 0, counts = 0;                    // counts: the lane's pixels of the class, and in the high half the correct ones
+#pragma unroll
+        for (int r = 0; r < RS_ROWS; r++) {
+            if ((todo >> r & 1u) && t[r] == lead) {
+                match |= 1u << r;
+                counts += 1u + ((unsigned)(label[r] == lead) << 16);
+            }
+        }
+        const unsigned long long both = nl_wave_sum(counts);                                // at most 256 each
+        const bool leader = (int)__lane_id() == first;
+#pragma unroll
+        for (int j = 0; j < T; j++) {
+            if (j >= a.temps) break;
+            unsigned long long sn = 0, sb = 0;
+            if (lead != a.classes) {
+#pragma unroll
+                for (int r = 0; r < RS_ROWS; r++) {
+                    if (match >> r & 1u) { sn += qn[r][j]; sb += qb[r][j]; }
+                }
+                sn = nl_wave_sum(sn);
+                sb = nl_wave_sum(sb);
+            }
+            if (leader) nl_add(a, j, lead, (unsigned)both & 0xffffu, (unsigned)(both >> 16) & 0xffffu, sn, sb);
+        }
+        todo &= ~match;
+    }
+    // what is left after the rounds (a wave with many classes): every pixel on its own
+#pragma unroll
+    for (int r = 0; r < RS_ROWS; r++) {
+        if (!(todo >> r & 1u)) continue;
+#pragma unroll
+        for (int j = 0; j < T; j++) {
+            if (j >= a.temps) break;
+            nl_add(a, j, t[r], 1u, (unsigned)(label[r] == t[r]), qn[r][j], qb[r][j]);
+        }
+    }
+}
+
+// the six NLL kernels by [capacity: 1, 4, 8][vec]
+typedef void (*NllKernel)(const NllArgs);
+const NllKernel nll_kernels[3][2] = { { resample_nll_f32<1, false>, resample_nll_f32<1, true> },
+                                      { resample_nll_f32<4, false>, resample_nll_f32<4, true> },
+                                      { resample_nll_f32<8, false>, resample_nll_f32<8, true> } };
+
+void nll_launch(hipStream_t s, int batch, const mbn_resample_launch_t &l, NllArgs &a, void *table, float *nll, float *brier, int64_t plane,
+                const float *logits, const void *truth, int truth_bytes, int rows, int cols, int classes, const float *inv_temps, int temps)
+{
+    a.table = (unsigned long long *)table; a.nll = nll; a.brier = brier; a.plane = plane;
+    a.logits = logits; a.truth = (const uint8_t *)truth; a.truth_bytes = truth_bytes;
+    a.rows = rows; a.cols = cols; a.classes = classes;
+    a.fy = l.fy; a.fx = l.fx; a.ch = l.ch;
+    a.temps = temps;
+    for (int j = 0; j < temps; j++) {
+        a.beta[j] = inv_temps[j];
+        a.k2[j] = (float)((double)inv_temps[j] * 1.44269504088896341);                      // one rounding
+    }
+    const bool vec = ((uintptr_t)logits % 16) == 0 && (classes % 4) == 0;
+    hipLaunchKernelGGL(nll_kernels[temps > 4 ? 2 : temps > 1][vec], dim3((unsigned)l.tiles, (unsigned)batch), dim3(256), (size_t)l.lds_bytes, s, a);
+}
+
 }   // namespace
+
+// rect = null: the whole map, the window (0, 0, cols, rows) of a rows x cols input. The shape is inside mbn_resample_nll_envelope, the temperatures
+// inside mbn_nll_temps_check and the pointers checked (the caller); nll / brier may be null
+int mbn_launch_f32_resample_nll(mbn_context *, hipStream_t s, void *table, float *nll, float *brier, const float *logits, const void *truth,
+                                int truth_bytes, int batch, int rows, int cols, int classes, int in_rows, int in_cols, const int32_t *rect,
+                                int out_rows, int out_cols, const float *inv_temps, int temps)
+{
+    const int32_t full[4] = { 0, 0, cols, rows };
+    if (!rect) { rect = full; in_rows = rows; in_cols = cols; }
+    mbn_resample_launch_t l = { 0, 0, 0, 0, 0, 0 };
+    mbn_resample_window_plan(rows, cols, in_rows, in_cols, rect, out_rows, out_cols, &l);
+    NllArgs a = {};
+    a.out_rows = out_rows; a.out_cols = out_cols;
+    a.tiles_x = (out_cols + RS_TILE - 1) / RS_TILE;
+    a.in_rows = in_rows; a.in_cols = in_cols;
+    a.wx = rect[0]; a.wy = rect[1]; a.wiw = rect[2]; a.wih = rect[3];
+    nll_launch(s, batch, l, a, table, nll, brier, (int64_t)batch * out_rows * out_cols, logits, truth, truth_bytes, rows, cols, classes, inv_temps,
+               temps);
+    return MBN_OK;
+}
+
+// the handle has a batch, plane_stride covers the set's span, the temperatures and the pointers are checked and the spans fit (the caller)
+int mbn_launch_f32_resample_nll_ragged(mbn_ragged_readout *r, hipStream_t s, void *table, float *nll, float *brier, int64_t plane_stride,
+                                       const float *logits, const void *truth, int truth_bytes, const float *inv_temps, int temps)
+{
+    NllArgs a = {};
+    a.tiles_x = 1;                                              // unused: a workgroup takes its image's own
+    // a plain set's items are the full window of a rows x cols input (what its check planned them as)
+    a.in_rows = r->window ? r->in_rows : r->rows; a.in_cols = r->window ? r->in_cols : r->cols;
+    a.wx = 0; a.wy = 0; a.wiw = a.in_cols; a.wih = a.in_rows;
+    a.set = mbn_ragged_readout_view(r);
+    nll_launch(s, r->batch, r->launch, a, table, nll, brier, plane_stride, logits, truth, truth_bytes, r->rows, r->cols, r->classes, inv_temps, temps);
+    mbn_ragged_readout_mark_done(r, s);
+    return MBN_OK;
+}
 
 // rect = null: the whole map, the window (0, 0, cols, rows) of a rows x cols input. The shape is inside mbn_resample_topk_envelope and the pointers
 // are non-null multiples of 4 (the caller has checked both). q = null: the logit form, no exponential

@@ -370,6 +370,14 @@ int mbn_launch_f32_resample_topk(mbn_context *ctx, hipStream_t s, int32_t *label
                                  const mbn_readout_prob *q);
 int mbn_launch_f32_resample_topk_ragged(mbn_ragged_readout *r, hipStream_t s, int32_t *labels, float *score, const float *logits, int k,
                                         int64_t plane_stride, const mbn_readout_prob *q);
+// the NLL / Brier read-out (mbn_resample_nll_*): table [temps][classes + 1][4] uint64 +=, nll / brier (either may be null) temperature-major,
+// temperature j at j * plane elements (uniform: plane = batch * out_rows * out_cols; ragged: plane_stride); truth at the maps' element offsets.
+// The shape is inside mbn_resample_nll_envelope / mbn_resample_nll_ragged_check and inv_temps (host) inside mbn_nll_temps_check
+int mbn_launch_f32_resample_nll(mbn_context *ctx, hipStream_t s, void *table, float *nll, float *brier, const float *logits, const void *truth,
+                                int truth_bytes, int batch, int rows, int cols, int classes, int in_rows, int in_cols, const int32_t *rect,
+                                int out_rows, int out_cols, const float *inv_temps, int temps);
+int mbn_launch_f32_resample_nll_ragged(mbn_ragged_readout *r, hipStream_t s, void *table, float *nll, float *brier, int64_t plane_stride,
+                                       const float *logits, const void *truth, int truth_bytes, const float *inv_temps, int temps);
 // rank score (mbn_i32_topk_rank.hip): ranks [classes + 1][k + 1] uint64 += per truth row the rank at which the truth is among the k label planes
 // (plane j at j * plane_stride elements). The arguments are inside mbn_topk_rank_envelope and the pointers checked
 int mbn_launch_i32_topk_rank(mbn_context *ctx, hipStream_t s, void *ranks, const void *labels, int k, int64_t plane_stride, const void *truth,

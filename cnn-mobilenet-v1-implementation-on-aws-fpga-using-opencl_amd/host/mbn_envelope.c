@@ -351,6 +351,38 @@ int mbn_resample_topk_ragged_check(int classes, int64_t span, int k, int64_t pla
     return topk_planes(classes, k, plane_stride, MBN_OK);
 }
 
+/* what the two NLL forms share: the truth's width and the temperatures in front of the shape's own answer, then the classes and the planes */
+static int nll_planes(int classes, int truth_bytes, int temps, int64_t plane, int shape)
+{
+    if ((truth_bytes != 1 && truth_bytes != 4) || temps < 1 || temps > MBN_NLL_MAX_TEMPS || shape == MBN_EINVAL) return MBN_EINVAL;
+    if (shape != MBN_OK) return shape;
+    if (classes > MBN_CONFUSION_MAX_CLASSES) return MBN_EUNSUPPORTED;
+    return plane > MBN_TOPK_MAX_ELEMENTS / temps ? MBN_EUNSUPPORTED : MBN_OK;
+}
+
+int mbn_resample_nll_envelope(int batch, int rows, int cols, int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols,
+                              int truth_bytes, int temps)
+{
+    const int shape = rect ? mbn_resample_window_envelope(batch, rows, cols, classes, in_rows, in_cols, rect, out_rows, out_cols)
+                           : mbn_resample_argmax_envelope(batch, rows, cols, classes, out_rows, out_cols);
+    return nll_planes(classes, truth_bytes, temps, shape == MBN_OK ? (int64_t)batch * out_rows * out_cols : 0, shape);
+}
+
+int mbn_resample_nll_ragged_check(int classes, int64_t span, int truth_bytes, int temps, int64_t plane_stride)
+{
+    if (classes < 1 || span < 1 || plane_stride < span) return MBN_EINVAL;
+    return nll_planes(classes, truth_bytes, temps, plane_stride, MBN_OK);
+}
+
+/* a beta the NLL read-out takes: finite and in [1/16, 16] (a NaN fails both compares) */
+int mbn_nll_temps_check(const float *inv_temps, int temps)
+{
+    if (!inv_temps || temps < 1 || temps > MBN_NLL_MAX_TEMPS) return MBN_EINVAL;
+    for (int j = 0; j < temps; j++)
+        if (!(inv_temps[j] >= 0.0625f && inv_temps[j] <= 16.0f)) return MBN_EINVAL;
+    return MBN_OK;
+}
+
 static long lmin(long a, long b) { return a < b ? a : b; }
 
 int mbn_i8_pw_plan(long m, int cin, int op_size, int num_cus, int operands_on_16, int out_f32, mbn_i8_pw_plan_t *p)

@@ -149,6 +149,13 @@ int mbn_resample_slide_plan(int rows, int cols, const mbn_slide *s, int out_rows
  * MBN_EUNSUPPORTED for k * plane_stride above the same limit. The launch is the set's own (mbn_resample_window_plan / the handle's) */
 #define MBN_TOPK_MAX_ELEMENTS ((int64_t)1 << 40)
 int mbn_resample_topk_ragged_check(int classes, int64_t span, int k, int64_t plane_stride);
+/* mbn_resample_nll_f32 (its envelope is declared in mbn.h too): MBN_EINVAL for truth_bytes other than 1 / 4, temps outside 1..MBN_NLL_MAX_TEMPS and
+ * whatever the envelope of the same form calls MBN_EINVAL (rect given: mbn_resample_window_envelope, NULL: mbn_resample_argmax_envelope); else that
+ * envelope's MBN_EUNSUPPORTED; else MBN_EUNSUPPORTED for classes > MBN_CONFUSION_MAX_CLASSES or temps planes above MBN_TOPK_MAX_ELEMENTS elements.
+ * mbn_resample_nll_ragged_check: the ragged form's part, for a set that reaches `span` elements: MBN_EINVAL for plane_stride < span, then as above.
+ * mbn_nll_temps_check: MBN_EINVAL for a NULL array, temps out of range or a beta that is NaN, infinite or outside [1/16, 16] */
+int mbn_resample_nll_ragged_check(int classes, int64_t span, int truth_bytes, int temps, int64_t plane_stride);
+int mbn_nll_temps_check(const float *inv_temps, int temps);
 /* rank score (mbn_i32_topk_rank.hip, host/mbn_score.c; mbn_topk_metrics is declared in mbn.h). mbn_topk_rank_envelope: MBN_EINVAL for k outside
  * 1..MBN_TOPK_MAX, plane_stride < count or whatever mbn_confusion_envelope calls MBN_EINVAL, else its MBN_EUNSUPPORTED, and MBN_EUNSUPPORTED for
  * k * plane_stride above MBN_TOPK_MAX_ELEMENTS. mbn_topk_rank_form: MBN_CONFUSION_FORM_LDS while a workgroup's table of (classes + 1) * (k + 1)

@@ -13,7 +13,13 @@ struct mbn_seg_maps {
     int64_t count;                  /* the pixels of all maps */
     int topk;                       /* 0, or the k of a top-k call: the maps are plane 0 of k rank-major planes, */
     int64_t plane_stride;           /* this many elements apart */
+    /* which read-out geometry turned net->seg.dense_logits into the maps (mbn_net_segment_nll reads the logits again): the whole map or the
+     * letterbox rectangle of a uniform call (the factor path: the whole map at out = factor x map, bit-equal), the net's ragged set, or several
+     * presentations of an image (views, slide), which no single read-out of the logits reproduces */
+    int geometry;                   /* MBN_SEG_GEOM_* */
+    int32_t rect[4];                /* MBN_SEG_GEOM_RECT: (x, y, iw, ih) of the network input */
 };
+enum { MBN_SEG_GEOM_WHOLE = 0, MBN_SEG_GEOM_RECT = 1, MBN_SEG_GEOM_SET = 2, MBN_SEG_GEOM_MANY = 3 };
 
 /* the segmentation state of a net: everything here is made on first use and freed by mbn_net_seg_release */
 struct mbn_net_seg {

@@ -423,7 +423,10 @@ static int segment_run(mbn_net *net, const seg_call *c)
     /* (5) the record */
     if (c->path != P_IMAGES) pixels = (int64_t)batch * rows * cols;    /* (an image call has rows = cols = 0, and the pixels of its items) */
     net->seg.last = (struct mbn_seg_maps){ c->path == P_IMAGES ? MBN_SEG_RAGGED : MBN_SEG_UNIFORM, batch, rows, cols, classes, pixels, c->topk,
-                                           c->path == P_IMAGES ? c->plane_stride : pixels };
+                                           c->path == P_IMAGES ? c->plane_stride : pixels,
+                                           c->path == P_IMAGES ? MBN_SEG_GEOM_SET : c->path == P_VIEWS || c->path == P_SLIDE ? MBN_SEG_GEOM_MANY
+                                           : rect ? MBN_SEG_GEOM_RECT : MBN_SEG_GEOM_WHOLE,
+                                           { rect ? rect[0] : 0, rect ? rect[1] : 0, rect ? rect[2] : 0, rect ? rect[3] : 0 } };
     return MBN_OK;
 }
 
@@ -560,6 +563,25 @@ int mbn_net_segment_calibration(mbn_net *net, const void *labels_i32, const void
     if (m->kind == MBN_SEG_RAGGED)
         return mbn_calibration_ragged_f32(net->seg.readout, calib_u64, labels_i32, prob_f32, truth, truth_bytes, m->classes, bins, NULL);
     return mbn_calibration_f32(net->ctx, calib_u64, labels_i32, prob_f32, truth, truth_bytes, m->classes, bins, m->count, NULL);
+}
+
+/* NLL and Brier score of the last call's probabilities: the read-out of net->seg.dense_logits once more, under the geometry the call used, with
+ * the truth in the class loop. The factor path's maps are the plain kernel's at out = factor x map bit for bit, so the whole-map call serves it */
+int mbn_net_segment_nll(mbn_net *net, const void *truth, int truth_bytes, const float *inv_temps, int temps, void *nll_u64, void *nll_f32,
+                        void *brier_f32, int64_t plane_stride)
+{
+    const struct mbn_seg_maps *m = last_maps(net);
+    if (!m) return MBN_EINVAL;
+    if (m->geometry == MBN_SEG_GEOM_MANY) return MBN_EUNSUPPORTED;     /* several presentations of an image: another probability model */
+    const void *logits = net->seg.dense_logits;
+    if (m->geometry == MBN_SEG_GEOM_SET)
+        return mbn_resample_nll_ragged_f32(net->seg.readout, nll_u64, nll_f32, brier_f32, plane_stride, logits, truth, truth_bytes, inv_temps, temps, NULL);
+    const mbn_layer_desc *feat, *fc;
+    const int rc = mbn_net_dense_layers(net, &feat, &fc);
+    if (rc != MBN_OK) return rc;
+    return mbn_resample_nll_f32(net->ctx, nll_u64, nll_f32, brier_f32, logits, truth, truth_bytes, m->batch, feat->out_rows, feat->out_cols, m->classes,
+                                net->plan.layer[0].in_rows, net->plan.layer[0].in_cols, m->geometry == MBN_SEG_GEOM_RECT ? m->rect : NULL, m->rows,
+                                m->cols, inv_temps, temps, NULL);
 }
 
 /* the net's one mbn_components handle holds at least the maps m */

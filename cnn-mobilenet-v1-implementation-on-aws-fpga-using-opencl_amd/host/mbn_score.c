@@ -212,3 +212,82 @@ int mbn_calibration_threshold(const uint64_t *calib, int bins, double target_acc
     }
     return MBN_ENOTFOUND;
 }
+
+/* ---- score the probabilities (include/mbn.h, "score the probabilities"): the NLL, the Brier score and the accuracy of one temperature plane of
+ * the table mbn_resample_nll_f32 adds to, and the plane of a temperature grid with the smallest NLL */
+static int nll_table_check(const uint64_t *nll_u64, int classes, int temps)
+{
+    if (!nll_u64 || classes < 1 || temps < 1 || temps > MBN_NLL_MAX_TEMPS) return MBN_EINVAL;
+    return classes > MBN_CONFUSION_MAX_CLASSES ? MBN_EUNSUPPORTED : MBN_OK;
+}
+
+/* cell (t, col) of plane j as a double: exact below 2^53 */
+static double nll_cell(const uint64_t *nll_u64, int classes, int j, int t, int col)
+{
+    return (double)nll_u64[((size_t)j * ((size_t)classes + 1) + (size_t)t) * 4 + (size_t)col];
+}
+
+int mbn_nll_metrics(const uint64_t *nll_u64, int classes, int temps, int j, mbn_nll *m, double *class_nll, double *class_brier)
+{
+    const int rc = nll_table_check(nll_u64, classes, temps);
+    if (rc == MBN_EINVAL || !m || j < 0 || j >= temps) return MBN_EINVAL;
+    if (rc != MBN_OK) return rc;
+    const double one16 = 65536.0, one24 = 16777216.0;               /* the fixed points of columns 1 and 2 */
+    /* sums of integers in doubles: exact below 2^53 */
+    double scored = 0.0, nll = 0.0, brier = 0.0, right = 0.0, mean_nll = 0.0, mean_brier = 0.0;
+    int present = 0;
+    for (int t = 0; t < classes; t++) {                             /* ascending class order */
+        const double n = nll_cell(nll_u64, classes, j, t, 0), a = nll_cell(nll_u64, classes, j, t, 1), b = nll_cell(nll_u64, classes, j, t, 2);
+        scored += n; nll += a; brier += b;
+        right += nll_cell(nll_u64, classes, j, t, 3);
+        const double cn = n > 0.0 ? a / (n * one16) : (double)NAN, cb = n > 0.0 ? b / (n * one24) : (double)NAN;
+        if (class_nll) class_nll[t] = cn;
+        if (class_brier) class_brier[t] = cb;
+        if (n > 0.0) { present++; mean_nll += cn; mean_brier += cb; }
+    }
+    m->scored = scored;
+    m->void_pixels = nll_cell(nll_u64, classes, j, classes, 0);
+    m->pixels = scored + m->void_pixels;
+    m->nll = scored > 0.0 ? nll / (scored * one16) : 0.0;
+    m->brier = scored > 0.0 ? brier / (scored * one24) : 0.0;
+    m->accuracy = scored > 0.0 ? right / scored : 0.0;
+    m->mean_class_nll = present ? mean_nll / (double)present : 0.0;
+    m->mean_class_brier = present ? mean_brier / (double)present : 0.0;
+    m->classes_present = present;
+    return MBN_OK;
+}
+
+int mbn_nll_best(const uint64_t *nll_u64, int classes, int temps, const float *inv_temps, int *best, double *inv_temp, int *at_edge)
+{
+    const int rc = nll_table_check(nll_u64, classes, temps);
+    if (rc == MBN_EINVAL || !inv_temps || !best) return MBN_EINVAL;
+    for (int j = 0; j < temps; j++)
+        if (!(inv_temps[j] > 0.0f) || isinf(inv_temps[j]) || (j > 0 && !(inv_temps[j] > inv_temps[j - 1]))) return MBN_EINVAL;
+    if (rc != MBN_OK) return rc;
+    /* the integer sums of column 1 (they fit: the device's 64-bit cells did), and what plane 0 scored */
+    uint64_t sum[MBN_NLL_MAX_TEMPS], scored = 0;
+    for (int t = 0; t < classes; t++) scored += nll_u64[(size_t)t * 4];
+    if (!scored) return MBN_ENOTFOUND;
+    int b = 0;
+    for (int j = 0; j < temps; j++) {
+        sum[j] = 0;
+        for (int t = 0; t < classes; t++) sum[j] += nll_u64[((size_t)j * ((size_t)classes + 1) + (size_t)t) * 4 + 1];
+        if (sum[j] < sum[b]) b = j;                                 /* strict: the lowest index on a tie */
+    }
+    double beta = (double)inv_temps[b];
+    if (b > 0 && b + 1 < temps) {
+        const double x0 = log((double)inv_temps[b - 1]), x1 = log((double)inv_temps[b]), x2 = log((double)inv_temps[b + 1]);
+        const double y0 = (double)sum[b - 1], y1 = (double)sum[b], y2 = (double)sum[b + 1];
+        const double s01 = (y1 - y0) / (x1 - x0), s12 = (y2 - y1) / (x2 - x1), a = (s12 - s01) / (x2 - x0);
+        if (a > 0.0) {
+            double x = 0.5 * (x0 + x1) - s01 / (2.0 * a);
+            if (x < x0) x = x0;
+            if (x > x2) x = x2;
+            beta = exp(x);
+        }
+    }
+    *best = b;
+    if (inv_temp) *inv_temp = beta;
+    if (at_edge) *at_edge = temps > 1 && (b == 0 || b == temps - 1);
+    return MBN_OK;
+}

@@ -49,6 +49,12 @@
  *   min_confidence=... coverage=... selective_accuracy=...  (min_confidence=none when no threshold of the table reaches it). With
  *   --min-confidence P > 0 the thresholded labels are what is scored: the pixels below P are in the abstained count and in no bin's accuracy.
  *   Works with --segment-topk, --tta-* and --slide like the other scores
+ *   --nll [--temperatures T1,T2,...] (with --segment-source and --truth; up to 8 distinct T, each in [1/16, 16], default 1; else usage status 2; not
+ *   with --segment-topk, --tta-* or --slide): are the probabilities worth anything as a whole. The NLL / Brier table of the softmax distribution of
+ *   the same call at every temperature, read out again from the net's logits with the truth in the class loop (mbn_net_segment_nll); behind the
+ *   calibration line one line per temperature, in descending T, and one for the best of them (mbn_nll_metrics, mbn_nll_best):
+ *   nll: temperature=... scored=... void=... nll=... brier=... mean_class_nll=... accuracy=...
+ *   nll_best: temperature=... refined_temperature=... at_edge=0|1   (temperature=none when nothing is scored)
  *   --regions [--connectivity 4|8] [--min-area N] [--max-regions M] (with --segment-source; defaults 4, 1, 256): the connected regions of every label
  *   map, found on the device (mbn_net_segment_regions). Per image one line `regions: image <n> count <k>` (k is the true count, even above M), then
  *   for each of its first min(k, M) regions `region <i> class <c> area <a> box <r0> <c0> <r1> <c1>` (rows first, both corners inside the box), in
@@ -633,6 +639,66 @@ static int score_calibration(mbn_context *ctx, mbn_net *net, void *d_labels, voi
     return 0;
 }
 
+/* --nll [--temperatures T1,T2,...]: what the command line asked for; temps = 0: nothing (set once by main). inv[j] = 1 / T_j, ascending */
+static struct { int temps; float temperature[MBN_NLL_MAX_TEMPS], inv[MBN_NLL_MAX_TEMPS]; } g_nll = { 0, { 0 }, { 0 } };
+
+/* --temperatures: up to MBN_NLL_MAX_TEMPS comma-separated T, each with 1 / T in [1/16, 16]; kept in descending T, so that 1 / T ascends as
+ * mbn_nll_best asks. 0 on success */
+static int parse_temperatures(const char *s)
+{
+    int n = 0;
+    while (*s) {
+        char *end;
+        const double t = strtod(s, &end);
+        if (end == s || n == MBN_NLL_MAX_TEMPS || !(t >= 0.0625 && t <= 16.0) || (*end && *end != ',')) return 1;
+        g_nll.temperature[n++] = (float)t;
+        s = *end ? end + 1 : end;
+        if (*end && !*s) return 1;                               /* a trailing comma */
+    }
+    for (int i = 1; i < n; i++)                                  /* insertion sort, T descending; equal temperatures are refused */
+        for (int j = i; j > 0 && g_nll.temperature[j] > g_nll.temperature[j - 1]; j--) {
+            const float v = g_nll.temperature[j];
+            g_nll.temperature[j] = g_nll.temperature[j - 1];
+            g_nll.temperature[j - 1] = v;
+        }
+    for (int i = 0; i < n; i++) {
+        g_nll.inv[i] = 1.0f / g_nll.temperature[i];
+        if (i > 0 && !(g_nll.inv[i] > g_nll.inv[i - 1])) return 1;
+    }
+    g_nll.temps = n;
+    return n == 0;
+}
+
+/* --truth with --nll: the NLL / Brier table of the probabilities of the same call, read out again from the net's logits (mbn_net_segment_nll):
+ * one nll: line per temperature and one nll_best: line */
+static int score_nll(mbn_context *ctx, mbn_net *net, void *d_truth, int tb, int classes, size_t pixels)
+{
+    const int temps = g_nll.temps;
+    const size_t bytes = (size_t)temps * ((size_t)classes + 1) * 4 * sizeof(uint64_t);
+    uint64_t *table = malloc(bytes);
+    if (!table) return 1;
+    void *d_table;
+    CHECK(mbn_alloc(ctx, bytes, &d_table));
+    CHECK(mbn_memset(ctx, d_table, 0, bytes));
+    CHECK(mbn_net_segment_nll(net, d_truth, tb, g_nll.inv, temps, d_table, NULL, NULL, (int64_t)pixels));
+    CHECK(mbn_download(ctx, table, d_table, bytes));
+    CHECK(mbn_free(ctx, d_table));
+    for (int j = 0; j < temps; j++) {
+        mbn_nll m;
+        CHECK(mbn_nll_metrics(table, classes, temps, j, &m, NULL, NULL));
+        printf("nll: temperature=%.9g scored=%.0f void=%.0f nll=%.17g brier=%.17g mean_class_nll=%.17g accuracy=%.17g\n", (double)g_nll.temperature[j],
+               m.scored, m.void_pixels, m.nll, m.brier, m.mean_class_nll, m.accuracy);
+    }
+    int best = 0, at_edge = 0;
+    double inv = 0.0;
+    const int rc = mbn_nll_best(table, classes, temps, g_nll.inv, &best, &inv, &at_edge);
+    if (rc == MBN_OK) printf("nll_best: temperature=%.9g refined_temperature=%.17g at_edge=%d\n", (double)g_nll.temperature[best], 1.0 / inv, at_edge);
+    else if (rc == MBN_ENOTFOUND) printf("nll_best: temperature=none refined_temperature=nan at_edge=0\n");      /* nothing scored */
+    else CHECK(rc);
+    free(table);
+    return 0;
+}
+
 /* --surface [--surface-bins N] [--surface-tolerance T] [--surface-percentile P] [--surface-edge 0|1] [--surface-map out.pgm]: what the command line
  * asked for; on = 0: nothing (set once by main) */
 static struct { int on, bins, tolerance, edge; double percentile; const char *map; } g_surface = { 0, 64, 2, 1, 95.0, NULL };
@@ -735,6 +801,10 @@ static int score_truth(mbn_context *ctx, mbn_net *net, const char **truths, int 
            m.valid, m.void_pixels, m.abstained, m.classes_present, m.pixel_accuracy, m.mean_accuracy, m.miou, m.fw_iou);
     if (g_calibration.bins) {
         const int bad = score_calibration(ctx, net, d_labels, d_prob, d_truth, tb);
+        if (bad) return bad;
+    }
+    if (g_nll.temps) {
+        const int bad = score_nll(ctx, net, d_truth, tb, classes, pixels);
         if (bad) return bad;
     }
     if (bo->on) {
@@ -1062,7 +1132,8 @@ int main(int argc, char **argv)
     int fit = MBN_FIT_CROP, filter = MBN_FILTER_BILINEAR;
     int pad_rgb[3] = { 0, 0, 0 }, src_h0 = 0, src_w0 = 0;              /* src_h0 x src_w0: image 0 as it was resized (0: it was not) */
     float crop_fraction = 1.0f, min_conf = 0.0f;
-    int have_min_conf = 0, have_ignore = 0, ignore_label = -1, have_topk = 0, segment_topk = 0, have_calibration = 0, calibration_bins = 0;
+    int have_min_conf = 0, have_ignore = 0, ignore_label = -1, have_topk = 0, segment_topk = 0, have_calibration = 0, calibration_bins = 0, have_nll = 0;
+    const char *temperatures = NULL;
     const char *tta = NULL, *slide_arg = NULL, *slide_stride_arg = NULL;
     int fit_given = 0, slide[4] = { 0, 0, 0, 0 }, slide_tiles = 0;      /* slide: tile rows, tile columns, stride rows, stride columns */
     region_opts regions = { 0, 4, 1, 256 };
@@ -1105,6 +1176,8 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--truth") && i + 1 < argc) truths[n_truth++] = argv[++i];
         else if (!strcmp(argv[i], "--calibration") && i + 1 < argc) { calibration_bins = atoi(argv[++i]); have_calibration = 1; }
         else if (!strcmp(argv[i], "--target-accuracy") && i + 1 < argc) { g_calibration.target = atof(argv[++i]); g_calibration.have_target = 1; }
+        else if (!strcmp(argv[i], "--nll")) have_nll = 1;
+        else if (!strcmp(argv[i], "--temperatures") && i + 1 < argc) temperatures = argv[++i];
         else if (!strcmp(argv[i], "--regions")) regions.on = 1;
         else if (!strcmp(argv[i], "--panoptic")) panoptic.on = 1;
         else if (!strcmp(argv[i], "--boundary-ratio") && i + 1 < argc) { boundary.ratio = atof(argv[++i]); boundary.on |= 1; }
@@ -1136,11 +1209,13 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--literal")) literal = 1;
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
-            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--segment-topk K] [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]] [--slide TH[xTW] [--slide-stride SH[xSW]]] [--truth F.pgm ...] [--calibration BINS [--target-accuracy A]] [--regions [--connectivity 4|8] [--min-area N] [--max-regions M]] [--boundary-ratio R | --boundary-d N [--boundary-edge 0|1] [--boundary-map OUT.pgm]] [--panoptic [--connectivity 4|8] [--min-area N]] [--surface [--surface-bins N] [--surface-tolerance T] [--surface-percentile P] [--surface-edge 0|1] [--surface-map OUT.pgm]]] [--segment-confidence OUT.pgm] "
+            fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--segment-topk K] [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]] [--slide TH[xTW] [--slide-stride SH[xSW]]] [--truth F.pgm ...] [--calibration BINS [--target-accuracy A]] [--nll [--temperatures T1,T2,...]] [--regions [--connectivity 4|8] [--min-area N] [--max-regions M]] [--boundary-ratio R | --boundary-d N [--boundary-edge 0|1] [--boundary-map OUT.pgm]] [--panoptic [--connectivity 4|8] [--min-area N]] [--surface [--surface-bins N] [--surface-tolerance T] [--surface-percentile P] [--surface-edge 0|1] [--surface-map OUT.pgm]]] [--segment-confidence OUT.pgm] "
                             "[--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n"
                             "  --calibration BINS [--target-accuracy A]: with --segment-confidence and --truth, one calibration: line (reliability table "
                             "in BINS bins, ECE, MCE, AURC) and the smallest --min-confidence that reaches accuracy A; with --min-confidence P > 0 the "
-                            "thresholded labels are scored, the pixels below P count as abstained\n", argv[0]);
+                            "thresholded labels are scored, the pixels below P count as abstained\n"
+                            "  --nll [--temperatures T1,T2,...]: with --truth, one nll: line per temperature (NLL, Brier score, mean-class NLL of the softmax "
+                            "distribution scaled by 1 / T; default 1) and one nll_best: line (the T with the smallest NLL, refined, at_edge)\n", argv[0]);
             return 2;
         }
     }
@@ -1219,6 +1294,17 @@ int main(int argc, char **argv)
             return 2;
         }
         g_calibration.bins = calibration_bins;
+    }
+    if (have_nll || temperatures) {
+        if (!have_nll || !segment_src || n_truth == 0 || have_topk || tta || tta_flip || slide_arg) {
+            fprintf(stderr, "--nll [--temperatures T1,T2,...] needs --segment-source and --truth and does not go with --segment-topk, --tta-scales or "
+                            "--slide (several presentations of an image are another probability model); --temperatures needs --nll\n");
+            return 2;
+        }
+        if (parse_temperatures(temperatures ? temperatures : "1")) {
+            fprintf(stderr, "bad --temperatures: 1 to %d distinct comma-separated values, each in [1/16, 16]\n", MBN_NLL_MAX_TEMPS);
+            return 2;
+        }
     }
     if (boundary.on || boundary_flags || boundary.map) {
         const int both = boundary.on == 3, none = boundary.on == 0;

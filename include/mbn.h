@@ -749,6 +749,87 @@ int mbn_calibration_metrics(const uint64_t *calib, int bins, mbn_calibration *m,
                             double *selective_accuracy);
 int mbn_calibration_threshold(const uint64_t *calib, int bins, double target_accuracy, float *min_prob, double *coverage,
                               double *selective_accuracy);
+/* Score the probabilities: negative log-likelihood and Brier score of the WHOLE softmax distribution of every output pixel against a ground truth,
+ * at up to eight temperatures in one pass. ECE (above) says whether the winner's confidence is honest; these two proper scoring
+ * rules say whether the distribution is, and the NLL is what a temperature is fitted on (Guo et al. 2017). The read-out takes the truth INTO the
+ * class loop: the tensor [out_rows][out_cols][classes] is never formed. Normative (tests/dense_nll_ref.py is the float64 form):
+ *   Interpolants. For an output pixel, v_c, best and label are exactly the interpolants, maximum and argmax of mbn_resample_argmax_f32; with a
+ *     rect (a window set) those of mbn_resample_argmax_window_f32. (The kernel evaluates the window rule throughout, as the top-k read-out does: a
+ *     NULL rect is the window (0, 0, cols, rows) of a rows x cols input, bit for bit the plain rule.)
+ *   Truth. t is the pixel's truth at the OUTPUT resolution, [batch][out_rows][out_cols] (ragged: at the items' dst_offsets), uint8 (truth_bytes
+ *     = 1) or int32 (4). A value outside [0, classes) is VOID, as in mbn_confusion_i32.
+ *   Temperatures. inv_temps[j], j < temps, is a HOST array of fp32 inverse temperatures beta_j = 1 / T_j; 1 <= temps <= MBN_NLL_MAX_TEMPS; each
+ *     beta_j is finite and in [1/16, 16]. It is read at the call and travels in the kernel's arguments.
+ *   Scores. Per temperature, in real arithmetic on the fp32 v_c and the fp32 beta:
+ *       x_c = beta (v_c - best);  e_c = exp(x_c), 0 for a NaN v_c;  S = sum_c e_c;  Q = sum_c e_c^2;
+ *       nll = log S - x_t;        brier = 1 - 2 e_t / S + Q / S^2        (= sum_c (p_c - [c == t])^2 with p_c = e_c / S).
+ *     best not finite (the prob = 0 case of "segment with confidence"): nll = MBN_NLL_CAP, brier = 1. v_t a NaN or -inf under a finite best:
+ *     nll = MBN_NLL_CAP, brier = 1 + Q / S^2. The stored nll is clamped to [0, MBN_NLL_CAP], the stored brier to [0, 2]. The NLL is formed in the
+ *     log domain: it stays finite where p_t underflows (a ramp of 65 logit units at beta = 16 gives about 1040, not the cap).
+ *   Outputs. nll_f32 and brier_f32 are optional, independent of each other, on 4 bytes; each holds `temps` planes, temperature-major:
+ *     [temps][batch][out_rows][out_cols]; ragged: plane j of item i at j * plane_stride + dst_offset_i ELEMENTS, plane_stride at least the set's
+ *     span (the rule of the top-k planes), nothing between the maps written. A void pixel stores -1.0f in both; no scored pixel can.
+ *     nll_u64 is required: uint64 [temps][classes + 1][4] on 8 bytes, ADDED to (the caller clears it, mbn_memset). A scored pixel adds to row t
+ *     of EVERY plane j: 1 to column 0, trunc(nll * 2^16) to column 1, trunc(brier * 2^24) to column 2 and (label == t) to column 3, nll and
+ *     brier being the fp32 values the kernel stores (or would store) for plane j: both products are exact in fp32. A void pixel adds 1 to
+ *     [j][classes][0] and nothing else. Column 1 cannot wrap below 2^33 pixels (2^31 a pixel at the cap), column 2 below 2^39.
+ *   Determinism. A pixel's values do not depend on the launch and everything after the quantisation is integer: the table and the maps are the
+ *     same bytes at every planning CU count and on graph replay.
+ *   Independence. The arithmetic of temperature j does not depend on temps, on the other entries or on the instantiation that serves the call:
+ *     plane j of a call with 8 temperatures equals the single plane of a call with beta_j alone, bit for bit.
+ *   Tolerance. The maps are fp32 and NOT bit-pinned against the reference (the float64 evaluation of the formulas on the fp32 v_c). Outside the
+ *     capped cases, as ABSOLUTE errors:  |nll - ref| <= (classes + 200 + 4 |x_t|) * 2^-24,   |brier - ref| <= 4 (classes + 200) * 2^-24.
+ *     Derivation for the implementation (csrc/mbn_f32_resample.hip, NLL): two passes, the second with the FINAL best, so every d = v_c - best is
+ *     <= 0 and nothing overflows at beta = 16. e_c = exp2(d * k), k = fp32(beta * log2 e) formed on the host: the subtraction, the rounding of k
+ *     and the product each put at most |x_c| * 2^-24 (natural units) into the exponent of a term that weighs e^x (|x| e^x < 1 for x <= 0), 3
+ *     units a term at most; exp2 within 2 ulp; a sequential fp32 sum of non-negative terms, classes - 1 roundings: S is relative-exact within
+ *     (classes + 5) * 2^-24, far inside the classes + 200 of "segment with confidence". Q's terms carry twice the exponent error plus one
+ *     rounding of the square: within (classes + 9) * 2^-24. log turns the relative error of S into an absolute one, plus log2's 1 ulp and the
+ *     product by ln 2 on a value of at most ln classes < 9: under classes + 25 units. x_t = beta * (v_t - best) is one subtraction and one
+ *     product: 1.5 |x_t| units; the last subtraction rounds at the size of nll <= |x_t| + ln classes: another |x_t| / 2 + 5 units. In all under
+ *     (classes + 30 + 2 |x_t|) * 2^-24: the bound above with room. Brier is three terms of magnitude at most 2: 2 e_t / S (the error of e_t, of
+ *     S and of 1 / S, times 2), Q / S^2 (Q's error and S's twice) and two additions: under 4 (classes + 20) * 2^-24. A term below 2^-126 may be
+ *     flushed to 0 by the exponential: an absolute 2^-126 a class against S >= 1.
+ *   mbn_resample_nll_f32         logits [batch][rows][cols][classes]; rect = NULL is the whole map, as in mbn_resample_topk_f32 (in_rows and
+ *                                in_cols are then not read). ONE kernel, asynchronous on `stream` (NULL: the context's), capturable as one node
+ *   mbn_resample_nll_ragged_f32  the maps of a ragged set, after either kind of set. ONE kernel; it keeps the generation rule: a captured
+ *                                launch replayed after a later set adds nothing and writes nothing; the next set waits for it
+ * MBN_EINVAL: NULL ctx / nll_u64 / logits / truth / inv_temps, nll_u64 off 8 bytes, a map or the logits off 4, an int32 truth off 4 (a uint8
+ * truth may be any byte pointer), truth_bytes not 1 or 4, temps outside 1..MBN_NLL_MAX_TEMPS, a beta that is NaN, infinite or outside [1/16, 16],
+ * whatever the argmax (NULL rect) or window call of the same shape calls MBN_EINVAL, plane_stride below the set's span, a handle without a set, or
+ * an undersized tracked buffer (mbn_alloc's bounds rule: the table spans temps * (classes + 1) * 32 bytes, a map (temps - 1) * plane + span
+ * elements, truth span elements). MBN_EUNSUPPORTED: outside the envelope of that argmax or window call, classes > MBN_CONFUSION_MAX_CLASSES, or
+ * temps * plane above 2^40 elements (mbn_resample_topk_ragged_check's limit). An MBN_EINVAL goes in front of an MBN_EUNSUPPORTED. Nothing is
+ * launched or written on a refusal. mbn_resample_nll_envelope answers the shape part of the uniform call; pure host.
+ *   mbn_nll_metrics  pure C in doubles, exact for cells below 2^53; plane j of the table. scored = the sum of column 0 over the class rows;
+ *     void_pixels = [j][classes][0]; pixels = scored + void_pixels; nll = (sum of column 1) / (scored * 2^16); brier = (sum of column 2) /
+ *     (scored * 2^24); accuracy = (sum of column 3) / scored; all three 0 when nothing is scored. class_nll and class_brier are [classes] or NULL:
+ *     the same ratios of one row, NaN for a class with an empty row; classes_present counts the others and mean_class_nll / mean_class_brier
+ *     are the means over them in ascending class order (0 when there are none). Every ratio is one division of exact integers.
+ *     MBN_EINVAL: NULL table or m, classes < 1, temps outside 1..MBN_NLL_MAX_TEMPS, j outside [0, temps); MBN_EUNSUPPORTED: classes >
+ *     MBN_CONFUSION_MAX_CLASSES.
+ *   mbn_nll_best     which plane of a temperature grid has the smallest NLL. inv_temps must be strictly ascending (and positive, finite), else
+ *     MBN_EINVAL. *best = the plane with the smallest INTEGER sum of column 1 over the class rows, the lowest index on a tie; MBN_ENOTFOUND
+ *     (nothing written) when plane 0 scored nothing. *at_edge = 1 when temps > 1 and best is the first or last plane: the caller should widen
+ *     the grid. *inv_temp = beta_best, refined when best is interior and the parabola through the three points (x_i, y_i) = (ln beta_i, sum_i),
+ *     i = best - 1, best, best + 1, opens upward: with s01 = (y1 - y0) / (x1 - x0), s12 = (y2 - y1) / (x2 - x1) and a = (s12 - s01) /
+ *     (x2 - x0) > 0 the vertex is x* = (x0 + x1) / 2 - s01 / (2 a) (unequal spacing allowed), clamped to [x0, x2], and *inv_temp = exp(x*).
+ *     inv_temp and at_edge may be NULL. The other statuses are mbn_nll_metrics'. */
+#define MBN_NLL_MAX_TEMPS 8
+#define MBN_NLL_CAP 32768.0f
+typedef struct mbn_nll {
+    double pixels, scored, void_pixels, nll, brier, accuracy, mean_class_nll, mean_class_brier;
+    int classes_present;
+} mbn_nll;
+int mbn_resample_nll_f32(mbn_context *ctx, void *nll_u64, void *nll_f32, void *brier_f32, const void *logits, const void *truth, int truth_bytes,
+                         int batch, int rows, int cols, int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols,
+                         const float *inv_temps, int temps, void *stream);
+int mbn_resample_nll_ragged_f32(mbn_ragged_readout *r, void *nll_u64, void *nll_f32, void *brier_f32, int64_t plane_stride, const void *logits,
+                                const void *truth, int truth_bytes, const float *inv_temps, int temps, void *stream);
+int mbn_resample_nll_envelope(int batch, int rows, int cols, int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols,
+                              int truth_bytes, int temps);
+int mbn_nll_metrics(const uint64_t *nll_u64, int classes, int temps, int j, mbn_nll *m, double *class_nll, double *class_brier);
+int mbn_nll_best(const uint64_t *nll_u64, int classes, int temps, const float *inv_temps, int *best, double *inv_temp, int *at_edge);
 /* Regions of a label map: connected-component labelling of the int32 maps the read-outs above write, on the device.
  * Normative (tests/components_ref.py is the numpy form; everything is integer, so the result is a function of the input alone: the same bytes at
  * every planning CU count, in both forms, on every run and on graph replay). For one image L [rows][cols] and classes >= 1:
@@ -1619,6 +1700,16 @@ int  mbn_net_segment_topk_score(mbn_net *net, const void *labels_i32, const void
  * whether the last call wrote one. MBN_EINVAL before any segment call. Otherwise whatever the calibration call answers. */
 int  mbn_net_segment_calibration(mbn_net *net, const void *labels_i32, const void *prob_f32, const void *truth, int truth_bytes, int bins,
                                  void *calib_u64);
+/* The NLL and Brier score of that same call's probabilities ("score the probabilities" above): the dense logits of the most recent successful
+ * segment call are still in the net, and this reads them out once more under the geometry that call used, with `truth` (at the labels' element
+ * offsets) in the class loop: mbn_resample_nll_f32 for a uniform call (whole map, or the letterbox rectangle of a pad fit; after mbn_net_segment
+ * the whole-map call at out = factor x map, whose interpolants are that call's bit for bit), mbn_resample_nll_ragged_f32 on the net's own set for
+ * an image call (plane_stride in elements; a uniform call does not read it: its planes are batch * rows * cols apart). The logits are valid until
+ * the next segment call (or mbn_net_forward_dense into them). MBN_EINVAL before any segment call; MBN_EUNSUPPORTED after a views or slide call:
+ * those logits are several presentations of an image, and averaging them is another probability model. Otherwise whatever the NLL call answers;
+ * a refused call leaves the table and the record as they were. */
+int  mbn_net_segment_nll(mbn_net *net, const void *truth, int truth_bytes, const float *inv_temps, int temps, void *nll_u64, void *nll_f32,
+                         void *brier_f32, int64_t plane_stride);
 /* The regions of the label maps of that same call ("regions of a label map" above; found exactly as mbn_net_segment_score finds it): a uniform
  * call is one mbn_components_i32 over [batch][out_rows][out_cols], an image call mbn_components_ragged_i32 on the net's own ragged set. classes is
  * the plan's. The net owns one mbn_components handle, sized for the call on first use, made again when a later call needs more, freed by

@@ -64,6 +64,12 @@
       mbn_surface_score_i32, the surface-distance table of --batch label maps of 375 x 500 against a uint8 truth (main_surface): 21 / 1000
       classes, 64 bins, shifted noisy 25 x 25 blocks, constant, random and far-apart inputs, beside torch.cdist between each class's contour
       coordinates on the same buffers and scipy.ndimage.distance_transform_edt per class on the host, download included; equal tables required.
+
+  python tools/dense_bench.py --nll [--reps 7] [--steps 20] [--batch 32] [--torch-steps 2] [--no-torch]
+      mbn_resample_nll_f32, the NLL / Brier read-out with a temperature grid (main_nll): --batch maps to 375 x 500 from the 28 x 28 and the
+      14 x 14 map against a uint8 truth of 25 x 25 blocks, 21 and 1000 classes, 1, 4 and 8 temperatures, beside mbn_resample_argmax_f32 and
+      mbn_resample_softmax_f32 on the same buffers and torch's interpolate -> log_softmax -> nll_loss plus the Brier expression at 1 and 8
+      temperatures.
 """
 import argparse
 import json
@@ -341,6 +347,111 @@ def main_prob(a):
                                                       "torch_over_softmax": round(t / result["plain_from_%d" % hw_]["softmax"]["kernel_ms"], 2)})
                 print("torch three-pass from %d: %.2f ms" % (hw_, t), flush=True)
         rd.close()
+    print(json.dumps(result))
+
+
+def nll_work(batch, h, w, classes, pix, temps):
+    """(bytes, vector issue slots) of the NLL read-out: two passes of resample_work's upper count of lerps (the second without the compare's two
+    selects but with the truth's compare and select and the subtract and max of d), and per temperature a multiply, one v_exp_f32 at two slots,
+    an add, a multiply and an add; 8 bytes of maps per pixel and temperature and the truth's byte"""
+    bytes_, ops = resample_work(batch, h, w, classes, pix)
+    return bytes_ - 8.0 * pix + pix * (1.0 + 8.0 * temps), 2 * ops + pix * classes * (2.0 + 6.0 * temps)
+
+
+def main_nll(a):
+    """--nll: the NLL / Brier read-out, --batch images of random logits (sigma 3) to 375 x 500 from the 28 x 28 and the 14 x 14 map, 21 and 1000
+    classes, against a uint8 truth of 25 x 25 blocks. Per shape, alternating within every repetition, on the same buffers:
+      argmax, softmax   mbn_resample_argmax_f32 (labels + score) and mbn_resample_softmax_f32 (labels + score + prob): the two kernels whose sum
+                        the NLL call at one temperature is expected to cost
+      nll_1, _4, _8     mbn_resample_nll_f32 with both maps and the table at 1, 4 and 8 temperatures (the three capacities)
+      torch_1, _8       the yardstick: interpolate(size=(375, 500)) -> log_softmax(beta v) -> nll_loss, and the Brier expression
+                        1 - 2 p_t + sum p^2, per temperature, on the same buffers, in slices of 8 images
+    Each figure is the median over the repetitions of `steps` back-to-back calls between two stream marks, with the range of the rounds."""
+    pkg = import_package()
+    torch = None
+    if not a.no_torch:
+        import torch
+        assert torch.cuda.is_available(), "the yardstick needs torch on the same GPU"
+    n, rng = a.batch, np.random.default_rng(0)
+    H, W = 375, 500
+    grid = [0.25, 0.35, 0.5, 0.7, 1.0, 1.4, 2.0, 4.0]
+    betas = {1: [1.0], 4: grid[2:6], 8: grid}
+    result = {"batch": n}
+    with pkg.Context(0) as ctx:
+        d_lab, d_sc, d_pr = ctx.alloc(n * H * W * 4), ctx.alloc(n * H * W * 4), ctx.alloc(n * H * W * 4)
+        d_nll, d_brier = ctx.alloc(8 * n * H * W * 4), ctx.alloc(8 * n * H * W * 4)
+        for classes in (21, 1000):
+            blocks = rng.integers(0, min(classes, 255), (n, (H + 24) // 25, (W + 24) // 25)).astype(np.uint8)
+            truth = np.ascontiguousarray(np.repeat(np.repeat(blocks, 25, axis=1), 25, axis=2)[:, :H, :W])
+            d_tab = ctx.to_device(np.zeros(8 * (classes + 1) * 4, np.uint64))
+            if torch is not None:
+                t_truth = torch.from_numpy(truth).cuda()
+                truth_ptr = t_truth.data_ptr()
+            else:
+                d_truth = ctx.to_device(truth)
+                truth_ptr = d_truth.ptr
+            for hw_ in (28, 14):
+                x = (3.0 * rng.standard_normal((n, hw_, hw_, classes))).astype(np.float32)
+                if torch is not None:
+                    t = torch.from_numpy(x).cuda()
+                    p, keep = t.data_ptr(), t
+                else:
+                    keep = ctx.to_device(x)
+                    p = keep.ptr
+                runs = {"argmax": lambda: ctx.resample_argmax(d_lab.ptr, d_sc.ptr, p, n, hw_, hw_, classes, H, W),
+                        "softmax": lambda: ctx.resample_softmax(d_lab.ptr, d_pr.ptr, d_sc.ptr, p, n, hw_, hw_, classes, H, W)}
+                for temps, b in betas.items():
+                    runs["nll_%d" % temps] = lambda b=b: ctx.resample_nll(d_tab.ptr, d_nll.ptr, d_brier.ptr, p, truth_ptr, 1, n, hw_, hw_, classes, H, W, b)
+                times = {k: [] for k in runs}
+                t_times = {1: [], 8: []}
+                for f in runs.values():
+                    marks_ms(ctx, f, 3)
+                for _ in range(a.reps):
+                    for k, f in runs.items():
+                        times[k].append(marks_ms(ctx, f, a.steps))
+                    for temps in (1, 8) if torch is not None else ():
+                        ctx.sync()
+                        nchw = keep.permute(0, 3, 1, 2)
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+                        def route(temps=temps):
+                            for i in range(0, n, 8):
+                                v = torch.nn.functional.interpolate(nchw[i:i + 8], size=(H, W), mode="bilinear", align_corners=False)
+                                tt = t_truth[i:i + 8].long()
+                                for beta in betas[temps]:
+                                    logp = torch.log_softmax(v * beta, dim=1)
+                                    nll = torch.nn.functional.nll_loss(logp, tt, reduction="none")
+                                    brier = 1.0 - 2.0 * torch.exp(-nll) + torch.exp(2.0 * logp).sum(1)
+                                    del logp, nll, brier
+                        route()
+                        e0.record()
+                        for _ in range(a.torch_steps):
+                            route()
+                        e1.record()
+                        torch.cuda.synchronize()
+                        t_times[temps].append(e0.elapsed_time(e1) / a.torch_steps)
+                out = {}
+                for k, ts in times.items():
+                    m = statistics.median(ts)
+                    out[k] = {"kernel_ms": round(m, 4), "kernel_runs_ms": [round(v, 4) for v in ts], "range_ms": [round(min(ts), 4), round(max(ts), 4)]}
+                    if k.startswith("nll_"):
+                        work = nll_work(n, hw_, hw_, classes, n * H * W, int(k[4:]))
+                        out[k].update({"kernel_frac_of_8TBps": round(work[0] / HBM_BYTES_PER_S / (m / 1e3), 4),
+                                       "kernel_frac_of_valu_rate": round(work[1] / VALU_LANE_OPS_PER_S / (m / 1e3), 4)})
+                out["nll_1_over_argmax_plus_softmax"] = round(out["nll_1"]["kernel_ms"] / (out["argmax"]["kernel_ms"] + out["softmax"]["kernel_ms"]), 3)
+                out["ms_per_further_temperature"] = round((out["nll_8"]["kernel_ms"] - out["nll_1"]["kernel_ms"]) / 7, 4)
+                for temps, ts in t_times.items():
+                    if ts:
+                        m = statistics.median(ts)
+                        out["torch_%d" % temps] = {"ms": round(m, 4), "runs_ms": [round(v, 4) for v in ts],
+                                                   "over_nll": round(m / out["nll_%d" % temps]["kernel_ms"], 2)}
+                name = "classes_%d_from_%d" % (classes, hw_)
+                result[name] = out
+                print("%-22s argmax %.4f  softmax %.4f  nll_1 %.4f  nll_4 %.4f  nll_8 %.4f ms  (nll_1 / (argmax + softmax) %.3f, %.4f ms a further "
+                      "temperature)%s" % (name, out["argmax"]["kernel_ms"], out["softmax"]["kernel_ms"], out["nll_1"]["kernel_ms"], out["nll_4"]["kernel_ms"],
+                                          out["nll_8"]["kernel_ms"], out["nll_1_over_argmax_plus_softmax"], out["ms_per_further_temperature"],
+                                          "".join("  torch_%d %.2f ms" % (k, out["torch_%d" % k]["ms"]) for k in (1, 8) if "torch_%d" % k in out)), flush=True)
+                del keep
     print(json.dumps(result))
 
 
@@ -1501,7 +1612,10 @@ def main():
     ap.add_argument("--no-host", action="store_true", help="--regions, --boundary: skip the host yardstick")
     ap.add_argument("--calibration", action="store_true", help="time mbn_calibration_f32 beside mbn_confusion_i32 and torch instead: see main_calibration")
     ap.add_argument("--surface", action="store_true", help="time mbn_surface_score_i32 beside torch.cdist and scipy's distance transform instead: see main_surface")
+    ap.add_argument("--nll", action="store_true", help="time mbn_resample_nll_f32 beside the argmax and softmax read-outs and torch instead: see main_nll")
     a = ap.parse_args()
+    if a.nll:
+        return main_nll(a)
     if a.calibration:
         return main_calibration(a)
     if a.surface:
