@@ -1,7 +1,7 @@
 /*
  * mbn_oracle.c — CPU restatement of kernel.cl (LITERAL mode) and of the fp32 MobileNet-V1 the metric
- * measures (F32 mode). TEST INFRASTRUCTURE ONLY — see mbn_oracle.h. PARITY UNPINNED (no reference
- * fixtures exist); pinned by hand-derived known-answer vectors in tests/golden/.
+ * measures (F32 mode). TEST INFRASTRUCTURE ONLY — see mbn_oracle.h for what pins it: the LITERAL
+ * functions by kernel.cl's own compiled text (tests/test_kernel_cl_cpu.py), the rest by hand-derived known-answer vectors.
  *
  * Written from the semantics of /root/reference/kernel.cl and the layer table of
  * /root/reference/MobileNet.c; no reference source is copied. Every function carries the lines it follows.

@@ -1,6 +1,6 @@
 """ctypes/numpy front-end of the CPU oracle (oracle/mbn_oracle.c). TEST INFRASTRUCTURE ONLY.
 
-PARITY UNPINNED: see oracle/mbn_oracle.h. Only tests/, __graft_entry__.smoke() and bench.py's
+What pins it, and what does not: see oracle/mbn_oracle.h. Only tests/, __graft_entry__.smoke() and bench.py's
 cpu_baseline leg may import this module; the product never does.
 """
 from __future__ import annotations
@@ -73,22 +73,32 @@ def _f32(a):
 
 # ----------------------------------------------------------------------------- LITERAL
 
+def _out(out, size):
+    """The output buffer: zeros, or a copy of the caller's prefill (an NDRange smaller than the plane leaves cells unwritten)."""
+    if out is None:
+        return np.zeros(size, np.uint8)
+    o = np.array(out, dtype=np.uint8).reshape(-1)
+    if o.size != size:
+        raise ValueError("out has %d bytes, the call's output has %d" % (o.size, size))
+    return o
+
+
 def lit_convolute(inp_r, inp_g, inp_b, filt, rows, cols, filtersize, stride, op_size, quirks=QUIRKS_KERNEL_CL,
-                  g0=0, g1=0):
+                  g0=0, g1=0, out=None):
     """kernel.cl:2-60. planes: uint8 [rows*cols]; filt int32 [op_size][3][k][k]. Returns uint8 [op_size][orow][ocol]."""
     r, g, b, f = _u8(inp_r), _u8(inp_g), _u8(inp_b), _i32(filt)
     plane = (rows // 2) * (cols // 2) if quirks & Q_LITERAL_INDEX else (rows // stride) * (cols // stride)
-    out = np.zeros(op_size * plane, np.uint8)
+    out = _out(out, op_size * plane)
     lib().orc_lit_convolute(_p(out), _p(r), _p(g), _p(b), _p(f), rows, cols, filtersize, stride, op_size,
                             C.c_uint(quirks), g0, g1)
     return out
 
 
 def lit_depthwise(inp, filt, rows, cols, filtersize, stride, op_size, in_rows=0, in_cols=0,
-                  quirks=QUIRKS_KERNEL_CL, g0=0, g1=0):
+                  quirks=QUIRKS_KERNEL_CL, g0=0, g1=0, out=None):
     """kernel.cl:62-92. inp uint8 [C][in_rows][in_cols]; filt int32 [C][k][k]. Returns uint8 [C*rows*cols]."""
     i, f = _u8(inp), _i32(filt)
-    out = np.zeros(op_size * rows * cols, np.uint8)
+    out = _out(out, op_size * rows * cols)
     lib().orc_lit_depthwise(_p(out), _p(i), _p(f), rows, cols, filtersize, stride, op_size, in_rows, in_cols,
                             C.c_uint(quirks), g0, g1)
     return out
@@ -103,8 +113,13 @@ def lit_pointwise(inp, filt, rows, cols, filtersize, op_size, quirks=QUIRKS_KERN
 
 
 def lit_pool(inp, rows, cols, filtersize, op_size, quirks=QUIRKS_KERNEL_CL):
-    """kernel.cl:116-132 (work-item (0,0))."""
+    """kernel.cl:116-132 (work-item (0,0)). filtersize^2 > rows*cols would run kernel.cl:126 past the plane (and, in the last
+    channel, past the buffer): refused like the C-ABI's mbn_pool does (MBN_EINVAL)."""
+    if rows <= 0 or cols <= 0 or op_size <= 0 or filtersize <= 0 or filtersize * filtersize > rows * cols:
+        raise ValueError("lit_pool: filtersize^2 = %d exceeds the %d x %d plane" % (filtersize * filtersize, rows, cols))
     i = _u8(inp)
+    if i.size < rows * cols * op_size:
+        raise ValueError("lit_pool: input has %d bytes, op_size planes have %d" % (i.size, rows * cols * op_size))
     out = np.zeros(op_size, np.uint8)
     lib().orc_lit_pool(_p(out), _p(i), rows, cols, filtersize, op_size, C.c_uint(quirks))
     return out

@@ -1,5 +1,5 @@
-"""Pins the CPU oracle (oracle/mbn_oracle.c). The reference has no tests or golden vectors, so the
-oracle is "parity unpinned" by the reference; what pins it here is:
+"""Pins the CPU oracle (oracle/mbn_oracle.c). The reference has no tests or golden vectors; its kernel.cl, compiled
+for the CPU, pins the LITERAL functions in tests/test_kernel_cl_cpu.py. What pins the oracle here, for every mode and quirk set, is:
   1. hand-derived known-answer vectors from the text of kernel.cl (tests/golden/kat_literal.json),
   2. an independent numpy formulation of the same semantics on seeded random inputs,
   3. torch.nn.functional.conv2d (an independent implementation, not the reference) for the fp32 mode at every
