@@ -440,11 +440,14 @@ __global__ __launch_bounds__(256) void softmax_f32(float *__restrict__ probs, in
     __shared__ int s_idx[4];
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float *l = logits + (long)n * classes;
+    // the total order of the top-k passes below (value descending, index ascending; a NaN is never taken), so that argmax == topk_idx[0] on every
+    // row, also on one without a finite maximum: all -inf gives index 0; nothing but NaN has no winner, stored as -1. `k < am` only ever holds
+    // for the first -inf of a lane: on a row with a value above -inf the scan takes exactly what a strict '>' alone takes.
     float mx = -INFINITY;
     int am = 0x7fffffff;
     for (int k = tid; k < classes; k += 256) {
         float v = l[k];
-        if (v > mx) { mx = v; am = k; }
+        if (v > mx || (v == mx && k < am)) { mx = v; am = k; }
     }
     for (int d = 32; d >= 1; d >>= 1) {
         float ov = __shfl_xor(mx, d, 64);
@@ -465,7 +468,7 @@ __global__ __launch_bounds__(256) void softmax_f32(float *__restrict__ probs, in
     sum = s_val[0] + s_val[1] + s_val[2] + s_val[3];
     if (probs)
         for (int k = tid; k < classes; k += 256) probs[(long)n * classes + k] = expf(l[k] - mx) / sum;
-    if (argmax && tid == 0) argmax[n] = am;
+    if (argmax && tid == 0) argmax[n] = am != 0x7fffffff ? am : -1;
 }
 
 // softmax + top-k per image (k <= 8): one workgroup per image. The k winners are found by k block-wide arg-max passes

@@ -351,7 +351,17 @@ int mbn_tail_resident_bf16(mbn_context *ctx, void *out, const void *in, const mb
                            void *stream);
 
 /* Classifier tail on device, fp32 (replaces the host loop MobileNet.c:2771-2792):
- * probs[n][k] = softmax(logits[n][:]) and argmax[n] (0-based). probs or argmax may be NULL. */
+ * probs[n][k] = softmax(logits[n][:]) and argmax[n] (0-based). probs or argmax may be NULL.
+ * Rows without a finite maximum — the contract of mbn_softmax_f32, mbn_softmax_topk_f32 and mbn_classifier_tail_fused (tests/test_readout_gpu.py):
+ *   order     the ranking is the total order (value descending, index ascending) over the entries that are not NaN: -inf entries rank last, in
+ *             index order; a NaN is never ranked. argmax[n] is topk_idx[n][0] of the same row in every case.
+ *   indices   every index written lies in [0, classes) or is -1. -1 ("no such winner") fills the slots past the ranked entries: classes < k,
+ *             or fewer than k entries that are not NaN. A row of nothing but NaN has argmax -1; a row of nothing but -inf has argmax 0 and
+ *             top-k 0, 1, 2, ...
+ *   probs     a -inf entry of a row whose maximum is finite has probability exactly 0. A row whose maximum is not finite (all -inf, or a +inf
+ *             in it) or that holds a NaN anywhere gets NaN for EVERY probability, winners' included (never a number that looks like one);
+ *             the probability stored beside an index of -1 is 0.
+ *   rows      a row is read and written by itself: the other rows of the batch are the same bytes whatever this one holds. */
 int mbn_softmax_f32(mbn_context *ctx, void *probs, void *argmax_i32, const void *logits, int batch,
                     int classes, void *stream);
 
@@ -367,7 +377,8 @@ int mbn_dwpw_fused_bf16(mbn_context *ctx, void *out, const void *in, const void 
 /* softmax + top-k on device: for every image the k <= 8 most probable classes, most probable first
  * (ties -> lowest index), topk_idx [batch][k] int32 (0-based, -1 when classes < k) and topk_prob [batch][k] fp32;
  * probs (may be NULL) additionally receives the full [batch][classes] distribution. Only 2k values per image have to
- * cross PCIe instead of the 1000 logits of MobileNet.c:2744 + the host exp loop :2771-2792. */
+ * cross PCIe instead of the 1000 logits of MobileNet.c:2744 + the host exp loop :2771-2792. NaN, -inf and +inf entries: the contract
+ * stated at mbn_softmax_f32 above. */
 int mbn_softmax_topk_f32(mbn_context *ctx, void *probs, void *topk_idx_i32, void *topk_prob_f32, const void *logits,
                          int batch, int classes, int k, void *stream);
 /* Dense head read-out (segmentation; the reference has none: its only read-out is MobileNet.c:2771-2792 over 1000 pooled logits): bilinear upsample of
@@ -1110,7 +1121,8 @@ int mbn_pool_fc(mbn_context *ctx, void *logits, const void *in, const void *fc_w
  * `pointwise` launch with its blocking read-back of 1000 logits, the host softmax loop :2771-2779 and the host arg-max :2781-2792): global
  * average pool -> FC + bias -> softmax -> top-k, results identical to mbn_pool_fc followed by mbn_softmax_topk_f32 bit for bit. The class
  * range that finishes last (a second arrival counter in the workspace) reads the complete logits back and normalises / ranks them. Same
- * workspace and envelope as mbn_pool_fc, plus classes <= 1024; `logits` [batch][classes] stay readable, `probs` may be NULL.
+ * workspace and envelope as mbn_pool_fc, plus classes <= 1024; `logits` [batch][classes] stay readable, `probs` may be NULL. Rows of logits
+ * without a finite maximum: the contract stated at mbn_softmax_f32, the same bytes as mbn_softmax_topk_f32 there too.
  * Measured on MI355X (profiles/r04/h_classifier_tail_one_launch.txt): see there — at 1...4 images the tail is launch-latency bound and the
  * one launch is offered as an option, not taken by default. */
 int mbn_classifier_tail_fused(mbn_context *ctx, void *topk_idx_i32, void *topk_prob_f32, void *probs, void *logits, const void *in, const void *fc_w,
