@@ -294,6 +294,8 @@ def _declare_host(lib):
     lib.mbn_nll_metrics.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, C.POINTER(Nll)] + [C.POINTER(C.c_double)] * 2
     lib.mbn_nll_best.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                  C.POINTER(C.c_int)]
+    lib.mbn_guided_lut.argtypes = [C.c_float, C.POINTER(C.c_float)]
+    lib.mbn_guide_reduce_envelope.argtypes = [C.c_int] * 4                                                       # mbn_envelope.h
     lib.mbn_components_envelope.argtypes = [C.c_int] * 7
     lib.mbn_components_tile.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.mbn_components_scratch_bytes.argtypes = [C.c_int, C.c_int64]
@@ -461,6 +463,9 @@ def load():
         lib.mbn_net_segment_prob_images_fit.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, ci, vp,
                                                         C.POINTER(C.c_int64), vp, C.c_float, ci]
         lib.mbn_net_segment_images.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, vp, C.POINTER(C.c_int64), vp]
+        lib.mbn_resample_guided_f32.argtypes = [vp] * 8 + [ci] * 6 + [C.POINTER(C.c_int32), ci, ci, C.c_float, ci, vp]
+        lib.mbn_guide_reduce_u8.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]
+        lib.mbn_net_segment_guided_fit.argtypes = [vp, vp, ci, ci, ci, ci, C.c_float, vp, vp, vp, C.c_float, ci]
         lib.mbn_resample_ensemble_f32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(View), ci, ci, ci, C.c_float, ci, vp]
         lib.mbn_resample_slide_f32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, C.POINTER(Slide), ci, ci, C.c_float, ci, vp]
         lib.mbn_net_resize_tiles.argtypes = [vp, vp, ci, ci, ci, C.POINTER(Slide), C.POINTER(vp)]
@@ -800,6 +805,21 @@ def resample_ragged_window_check(rows, cols, classes, in_rows, in_cols, items, l
     rc = (lib or host_lib()).mbn_resample_ragged_window_check(rows, cols, classes, in_rows, in_cols, arr, len(arr),
                                                               (C.c_int64 * (2 * max(len(arr), 1)))(), C.byref(l))
     return rc, l
+
+
+GUIDED_LUT = 766
+
+
+def guided_lut(sigma, lib=None) -> np.ndarray:
+    """mbn_guided_lut: the 766 float32 range weights of resample_guided, lut[d] = max(exp(-d^2 / (2 sigma^2)), 2^-60) (upload them to the device)."""
+    lut = np.zeros(GUIDED_LUT, np.float32)
+    _chk((lib or host_lib()).mbn_guided_lut(sigma, lut.ctypes.data_as(C.POINTER(C.c_float))), "guided_lut")
+    return lut
+
+
+def guide_reduce_envelope(batch, in_rows, in_cols, stride, lib=None) -> int:
+    """mbn_guide_reduce_envelope: the status Context.guide_reduce gives the sizes and the stride."""
+    return (lib or host_lib()).mbn_guide_reduce_envelope(batch, in_rows, in_cols, stride)
 
 
 def softmax_readout_check(have_prob, min_prob, lib=None) -> int:
@@ -1308,6 +1328,21 @@ class Context:
         _chk(self.lib.mbn_resample_softmax_window_f32(self.h, labels, prob, score, logits, batch, rows, cols, classes, in_rows, in_cols, _rect(rect),
                                                       out_rows, out_cols, min_prob, ignore_label, None), self.last_error())
 
+    def guide_reduce(self, guide_lo, canvas, batch, in_rows, in_cols, stride):
+        """mbn_guide_reduce_u8: uint8 canvas [batch][in_rows][in_cols][3] -> guide_lo [batch][in_rows / stride][in_cols / stride][3], the rounded
+        mean of every stride x stride block per channel: the low-resolution guide of resample_guided."""
+        _chk(self.lib.mbn_guide_reduce_u8(self.h, guide_lo, canvas, batch, in_rows, in_cols, stride, None), self.last_error())
+
+    def resample_guided(self, labels, prob, score, logits, guide_lo, guide_hi, lut, batch, rows, cols, classes, out_rows, out_cols, in_rows=0,
+                        in_cols=0, rect=None, min_prob=0.0, ignore_label=0):
+        """mbn_resample_guided_f32: the read-out to out_rows x out_cols with the bilinear weights scaled by lut[colour distance] between guide_hi
+        (uint8 [batch][out_rows][out_cols][3], the source image) and guide_lo (uint8 [batch][rows][cols][3]) and normalised: joint bilateral
+        upsampling + argmax in one kernel. lut: guided_lut(sigma) on the device. rect = (x, y, iw, ih) of the in_rows x in_cols input, or None for
+        the whole map. prob None with min_prob 0: the argmax form; `score` may be None."""
+        _chk(self.lib.mbn_resample_guided_f32(self.h, labels, prob, score, logits, guide_lo, guide_hi, lut, batch, rows, cols, classes, in_rows, in_cols,
+                                              None if rect is None else _rect(rect), out_rows, out_cols, min_prob, ignore_label, None),
+             self.last_error())
+
     def resample_ensemble(self, labels, prob, score, logits, batch, rows, cols, classes, in_rows, in_cols, view_list, out_rows, out_cols,
                           min_prob=0.0, ignore_label=0, n_views=None):
         """mbn_resample_ensemble_f32: ONE read-out of the views in view_list (View objects or (x, y, iw, ih, mirror)) over view-major logits
@@ -1771,6 +1806,12 @@ class Net:
         """mbn_net_segment_fit: uint8 sources [batch][in_rows][in_cols][3] -> resize_input(fit), forward_dense and the read-out to the source size:
         labels (and scores) [batch][in_rows][in_cols]. FIT_STRETCH or FIT_PAD (the window read-out of fit_pad's rectangle). Needs set_input_u8()."""
         _chk(self.ctx.lib.mbn_net_segment_fit(self.h, src_ptr, batch, in_rows, in_cols, fit, labels_ptr, score_ptr), self.ctx.last_error())
+
+    def segment_guided_fit(self, src_ptr, batch, in_rows, in_cols, fit, sigma, labels_ptr, prob_ptr=None, score_ptr=None, min_prob=0.0, ignore_label=0):
+        """mbn_net_segment_guided_fit: segment_fit (FIT_STRETCH or FIT_PAD) with the guided read-out (Context.resample_guided): the source image is
+        guide_hi, the block means of the resized canvas guide_lo, the table guided_lut(sigma). prob None with min_prob 0: the argmax form."""
+        _chk(self.ctx.lib.mbn_net_segment_guided_fit(self.h, src_ptr, batch, in_rows, in_cols, fit, sigma, labels_ptr, prob_ptr, score_ptr, min_prob,
+                                                     ignore_label), self.ctx.last_error())
 
     def segment_images_fit(self, src_ptr, offsets, rows, cols, fit, labels_ptr, dst_offsets, score_ptr=None):
         """mbn_net_segment_images_fit: segment_images under FIT_STRETCH or FIT_PAD (one ragged window read-out, each image's own rectangle)."""

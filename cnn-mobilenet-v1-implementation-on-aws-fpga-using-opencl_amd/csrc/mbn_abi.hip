@@ -958,6 +958,44 @@ int mbn_resample_slide_f32(mbn_context *ctx, void *labels_i32, void *prob_f32, v
                         });
 }
 
+// The guided read-out: readout_call's order (pointers, the softmax arguments, the shape, the spans) with the three operands of its own
+int mbn_resample_guided_f32(mbn_context *ctx, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, const void *guide_lo_u8,
+                            const void *guide_hi_u8, const void *lut_f32, int batch, int rows, int cols, int classes, int in_rows, int in_cols,
+                            const int32_t rect[4], int out_rows, int out_cols, float min_prob, int ignore_label, void *stream)
+{
+    if (!ctx || !labels_i32 || !logits || !guide_lo_u8 || !guide_hi_u8 || !lut_f32) return MBN_EINVAL;
+    if (((uintptr_t)labels_i32 | (uintptr_t)score_f32 | (uintptr_t)logits | (uintptr_t)prob_f32 | (uintptr_t)lut_f32) % 4) return MBN_EINVAL;
+    // no prob map and no threshold: the argmax form (a NaN threshold is not 0: the softmax check refuses it)
+    const mbn_readout_prob prob = { (float *)prob_f32, min_prob, ignore_label };
+    const mbn_readout_prob *q = prob_f32 || !(min_prob == 0.0f) ? &prob : nullptr;
+    if (q && mbn_softmax_readout_check(q->prob != nullptr, q->min_prob) != MBN_OK) return MBN_EINVAL;
+    const int shape = rect ? mbn_resample_window_envelope(batch, rows, cols, classes, in_rows, in_cols, rect, out_rows, out_cols)
+                           : mbn_resample_argmax_envelope(batch, rows, cols, classes, out_rows, out_cols);
+    if (shape != MBN_OK) return shape;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    const double out = 4.0 * batch * out_rows * out_cols;
+    MBN_SPANS(ctx, { logits, 4.0 * batch * rows * cols * classes, "guided read-out logits" }, { labels_i32, out, "guided read-out labels" },
+              { score_f32, out, "guided read-out score" }, { prob_f32, out, "guided read-out prob" },
+              { guide_lo_u8, 3.0 * batch * rows * cols, "guided read-out guide_lo" }, { guide_hi_u8, 3.0 * batch * out_rows * out_cols, "guided read-out guide_hi" },
+              { lut_f32, 4.0 * MBN_GUIDED_LUT, "guided read-out lut" });
+    Scope sc(ctx, s);
+    return sc.finish(mbn_launch_f32_resample_guided(ctx, s, (int32_t *)labels_i32, (float *)score_f32, (const float *)logits, (const uint8_t *)guide_lo_u8,
+                                                    (const uint8_t *)guide_hi_u8, (const float *)lut_f32, batch, rows, cols, classes, in_rows, in_cols,
+                                                    rect, out_rows, out_cols, q));
+}
+
+int mbn_guide_reduce_u8(mbn_context *ctx, void *guide_lo_u8, const void *canvas_u8, int batch, int in_rows, int in_cols, int S, void *stream)
+{
+    if (!ctx || !guide_lo_u8 || !canvas_u8) return MBN_EINVAL;
+    const int shape = mbn_guide_reduce_envelope(batch, in_rows, in_cols, S);
+    if (shape != MBN_OK) return shape;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    MBN_SPANS(ctx, { canvas_u8, 3.0 * batch * in_rows * in_cols, "guide_reduce canvas" },
+              { guide_lo_u8, 3.0 * batch * (in_rows / S) * (in_cols / S), "guide_reduce guide_lo" });
+    Scope sc(ctx, s);
+    return sc.finish(mbn_launch_u8_guide_reduce(ctx, s, (uint8_t *)guide_lo_u8, (const uint8_t *)canvas_u8, batch, in_rows, in_cols, S));
+}
+
 int mbn_ragged_readout_create(mbn_context *ctx, int max_batch, mbn_ragged_readout **r)
 {
     if (!ctx || !r) return MBN_EINVAL;

@@ -378,6 +378,13 @@ int mbn_launch_f32_resample_nll(mbn_context *ctx, hipStream_t s, void *table, fl
                                 int out_rows, int out_cols, const float *inv_temps, int temps);
 int mbn_launch_f32_resample_nll_ragged(mbn_ragged_readout *r, hipStream_t s, void *table, float *nll, float *brier, int64_t plane_stride,
                                        const float *logits, const void *truth, int truth_bytes, const float *inv_temps, int temps);
+// the guided read-out (mbn_f32_guided.hip; mbn_resample_guided_f32): the bilinear read-out's geometry, envelope and plan with the four weights of a
+// pixel scaled by lut[colour distance between guide_hi's pixel and guide_lo's neighbour] and normalised. rect and q as above. The reduce: guide_lo
+// [batch][in_rows / S][in_cols / S][3] = the rounded block means of canvas [batch][in_rows][in_cols][3], inside mbn_guide_reduce_envelope
+int mbn_launch_f32_resample_guided(mbn_context *ctx, hipStream_t s, int32_t *labels, float *score, const float *logits, const uint8_t *guide_lo,
+                                   const uint8_t *guide_hi, const float *lut, int batch, int rows, int cols, int classes, int in_rows, int in_cols,
+                                   const int32_t *rect, int out_rows, int out_cols, const mbn_readout_prob *q);
+int mbn_launch_u8_guide_reduce(mbn_context *ctx, hipStream_t s, uint8_t *guide_lo, const uint8_t *canvas, int batch, int in_rows, int in_cols, int S);
 // rank score (mbn_i32_topk_rank.hip): ranks [classes + 1][k + 1] uint64 += per truth row the rank at which the truth is among the k label planes
 // (plane j at j * plane_stride elements). The arguments are inside mbn_topk_rank_envelope and the pointers checked
 int mbn_launch_i32_topk_rank(mbn_context *ctx, hipStream_t s, void *ranks, const void *labels, int k, int64_t plane_stride, const void *truth,

@@ -98,6 +98,11 @@ int mbn_resample_window_envelope(int batch, int rows, int cols, int classes, int
 /* mbn_resample_plan for a window: widens *l likewise, with the window's footprint. The full window gives exactly mbn_resample_plan's answer */
 void mbn_resample_window_plan(int rows, int cols, int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols,
                               mbn_resample_launch_t *l);
+/* mbn_resample_guided_f32 has no envelope of its own: its shape is mbn_resample_window_envelope's (a NULL rect: mbn_resample_argmax_envelope's) and
+ * its launch mbn_resample_window_plan's, with the footprint's fy * fx * 3 colour bytes (rounded up to 4) behind lds_bytes.
+ * mbn_guide_reduce_u8: MBN_EINVAL for a non-positive size, S < 1 or S not a divisor of both sides; else MBN_EUNSUPPORTED for a batch above 65535, a
+ * side above MBN_RESAMPLE_MAX_OUT or S above 2048 (a block's sum of 255 S^2 is kept in 32 bits) */
+int mbn_guide_reduce_envelope(int batch, int in_rows, int in_cols, int S);
 /* mbn_resample_ragged_check for the items of mbn_ragged_readout_set_window: the same statuses, overlap sort and scratch, every item under
  * mbn_resample_window_envelope with its own rectangle; *l is written only when the batch is accepted */
 int mbn_resample_ragged_window_check(int rows, int cols, int classes, int in_rows, int in_cols, const mbn_label_window_item *items, int batch,

@@ -25,6 +25,9 @@ enum { MBN_SEG_GEOM_WHOLE = 0, MBN_SEG_GEOM_RECT = 1, MBN_SEG_GEOM_SET = 2, MBN_
 struct mbn_net_seg {
     void *dense_logits;             /* [max_batch][h][w][classes] fp32: the dense head's output, what every read-out reads */
     void *resize_buf;               /* the staging buffer: [max_batch][rows][cols][3] uint8, the resized images of every resize call */
+    void *guide_lo;                 /* mbn_net_segment_guided_fit: [max_batch][h][w][3] uint8, the block means of the staged canvases, */
+    void *guided_lut;               /* and the device table of range weights, MBN_GUIDED_LUT floats, made for */
+    float guided_sigma;             /* this sigma (the last call's) */
     int resize_filter;              /* mbn_net_set_resize_filter: MBN_FILTER_* of every resizer (MBN_FILTER_BILINEAR until it is called) */
     uint8_t pad_color[3];           /* mbn_net_set_pad_color: the border of MBN_FIT_PAD, R, G, B (black until it is called) */
     mbn_resizer *resizer;           /* mbn_net_resize_input: the resizer of the geometry below, rebuilt when it changes */

@@ -260,6 +260,8 @@ typedef struct seg_call {
     int tile[2], stride[2];                             /* P_SLIDE: rows, cols */
     int topk;                                           /* P_FIT, P_IMAGES: 0, or the k of the top-k read-out: labels, score and prob hold k planes, */
     int64_t plane_stride;                               /* for P_IMAGES this many elements apart */
+    int guided;                                         /* P_FIT: the guided read-out (mbn_resample_guided_f32) with the table of sigma, */
+    float sigma;                                        /* the source as guide_hi and the block means of the staged canvas as guide_lo */
 } seg_call;
 
 /* The net's read-out set from the items of an image call: each image's map at its own size, through its letterbox window under MBN_FIT_PAD. The set
@@ -302,6 +304,33 @@ static int dense_forward(mbn_net *net, const mbn_layer_desc *feat, const mbn_lay
     return mbn_net_forward_dense(net, images, net->seg.dense_logits, batch);
 }
 
+/* What a guided call adds to the staging: the coarse guide of the staged canvases, [max_batch][h][w][3] uint8, and the device table, both made on
+ * first use; lut = the table of a sigma the kept one was not made for (NULL: keep it). The upload waits for the read-out that may still read the table. */
+static int guide_stage(mbn_net *net, const void *canvas, int batch, int h, int w, const float *lut, float sigma)
+{
+    struct mbn_net_seg *s = &net->seg;
+    const mbn_layer_desc *in = &net->plan.layer[0];
+    int rc = MBN_OK;
+    if (!s->guide_lo) {
+        rc = mbn_alloc(net->ctx, (size_t)net->max_batch * h * w * 3, &s->guide_lo);
+        if (rc != MBN_OK) { s->guide_lo = NULL; return rc; }
+    }
+    if (lut) {
+        void *table = s->guided_lut;
+        if (!table) rc = mbn_alloc(net->ctx, sizeof(float) * MBN_GUIDED_LUT, &table);
+        if (rc == MBN_OK) rc = mbn_sync(net->ctx);
+        if (rc == MBN_OK) rc = mbn_upload(net->ctx, table, lut, sizeof(float) * MBN_GUIDED_LUT);
+        if (rc != MBN_OK) {                                            /* no table is kept: the next call makes it again */
+            if (table) mbn_free(net->ctx, table);
+            s->guided_lut = NULL;
+            return rc;
+        }
+        s->guided_lut = table;
+        s->guided_sigma = sigma;
+    }
+    return mbn_guide_reduce_u8(net->ctx, s->guide_lo, canvas, batch, in->in_rows, in->in_cols, in->in_rows / h, NULL);
+}
+
 /* Every segment call. The order is the contract: (1) everything that can refuse, and nothing before the end of it touches the device, a kept
  * handle or the record, so a refused call leaves all three as they were; (2) the staging; (3) ONE forward pass, on n_images; (4) the read-out;
  * (5) the record the consumers read, only after a read-out that succeeded. The cases of a switch are what is a path's own. */
@@ -309,6 +338,9 @@ static int segment_run(mbn_net *net, const seg_call *c)
 {
     if (!net || !c->src || !c->labels) return MBN_EINVAL;
     if (c->path >= P_FIT && !net->input_u8) return MBN_EINVAL;         /* the staged images are uint8: the net must take them as such */
+    float lut[MBN_GUIDED_LUT];                                         /* a guided call with another sigma than the kept table's: the new table */
+    const int new_lut = c->guided && !(net->seg.guided_lut && net->seg.guided_sigma == c->sigma);
+    if (new_lut && mbn_guided_lut(c->sigma, lut) != MBN_OK) return MBN_EINVAL;
     const readout_prob *q = c->q;
     if (q && ((uintptr_t)q->prob % 4 || mbn_softmax_readout_check(q->prob != NULL, q->min_prob) != MBN_OK)) return MBN_EINVAL;
     const int in_rows = net->plan.layer[0].in_rows, in_cols = net->plan.layer[0].in_cols, batch = c->batch;
@@ -357,6 +389,8 @@ static int segment_run(mbn_net *net, const seg_call *c)
             if (rc == MBN_OK) rc = mbn_resample_window_envelope(batch, h, w, classes, in_rows, in_cols, rect, rows, cols);
         } else if (mbn_resample_argmax_envelope(batch, h, w, classes, rows, cols) != MBN_OK)
             rc = MBN_EUNSUPPORTED;                                     /* every size is positive here: what the plain shape can miss is a limit */
+        /* the coarse guide is the block mean over the plan's output stride: an integer, the same on both axes */
+        if (rc == MBN_OK && c->guided && (in_rows % h || in_cols % w || in_rows / h != in_cols / w)) rc = MBN_EUNSUPPORTED;
         if (rc == MBN_OK && c->topk) rc = mbn_resample_topk_envelope(batch, h, w, classes, in_rows, in_cols, rect, rows, cols, c->topk);
         break;
     case P_IMAGES:
@@ -384,6 +418,7 @@ static int segment_run(mbn_net *net, const seg_call *c)
     case P_VIEWS:  rc = resize_views(net, c->src, batch, rows, cols, c->scales, views, c->n_views, &images); break;
     case P_SLIDE:  rc = resize_tiles(net, c->src, batch, rows, cols, &slide, &images); break;
     }
+    if (rc == MBN_OK && c->guided) rc = guide_stage(net, images, batch, h, w, new_lut ? lut : NULL, c->sigma);
     if (rc == MBN_OK) rc = dense_forward(net, feat, fc, images, n_images);
     if (rc != MBN_OK) return rc;
     /* (4) the read-out: the one place that chooses among the public read-out calls */
@@ -408,7 +443,10 @@ static int segment_run(mbn_net *net, const seg_call *c)
         rc = mbn_resample_slide_f32(net->ctx, c->labels, prob, c->score, logits, batch, h, w, classes, &slide, rows, cols, min_prob, ignore, NULL);
         break;
     default:
-        if (c->topk)
+        if (c->guided)
+            rc = mbn_resample_guided_f32(net->ctx, c->labels, prob, c->score, logits, net->seg.guide_lo, c->src, net->seg.guided_lut, batch, h, w, classes,
+                                         in_rows, in_cols, rect, rows, cols, min_prob, ignore, NULL);
+        else if (c->topk)
             rc = mbn_resample_topk_f32(net->ctx, c->labels, prob, c->score, logits, batch, h, w, classes, in_rows, in_cols, rect, rows, cols, c->topk,
                                        min_prob, ignore, NULL);
         else if (q && rect)
@@ -425,7 +463,7 @@ static int segment_run(mbn_net *net, const seg_call *c)
     net->seg.last = (struct mbn_seg_maps){ c->path == P_IMAGES ? MBN_SEG_RAGGED : MBN_SEG_UNIFORM, batch, rows, cols, classes, pixels, c->topk,
                                            c->path == P_IMAGES ? c->plane_stride : pixels,
                                            c->path == P_IMAGES ? MBN_SEG_GEOM_SET : c->path == P_VIEWS || c->path == P_SLIDE ? MBN_SEG_GEOM_MANY
-                                           : rect ? MBN_SEG_GEOM_RECT : MBN_SEG_GEOM_WHOLE,
+                                           : c->guided ? MBN_SEG_GEOM_MANY : rect ? MBN_SEG_GEOM_RECT : MBN_SEG_GEOM_WHOLE,
                                            { rect ? rect[0] : 0, rect ? rect[1] : 0, rect ? rect[2] : 0, rect ? rect[3] : 0 } };
     return MBN_OK;
 }
@@ -461,6 +499,15 @@ int mbn_net_segment_prob_fit(mbn_net *net, const void *src_u8, int batch, int in
 {
     const readout_prob q = { prob_f32, min_prob, ignore_label };
     const seg_call c = { .path = P_FIT, .src = src_u8, .labels = labels_i32, .q = &q, .batch = batch, .rows = in_rows, .cols = in_cols, .fit = fit };
+    return segment_run(net, &c);
+}
+
+int mbn_net_segment_guided_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, float sigma, void *labels_i32,
+                               void *prob_f32, void *score_f32, float min_prob, int ignore_label)
+{
+    const readout_prob given = { prob_f32, min_prob, ignore_label };
+    const seg_call c = { .path = P_FIT, .src = src_u8, .labels = labels_i32, .score = score_f32, .q = softmax_form(prob_f32, min_prob) ? &given : NULL,
+                         .batch = batch, .rows = in_rows, .cols = in_cols, .fit = fit, .guided = 1, .sigma = sigma };
     return segment_run(net, &c);
 }
 
@@ -782,6 +829,8 @@ void mbn_net_seg_release(mbn_net *net)
     struct mbn_net_seg *s = &net->seg;
     if (s->dense_logits) mbn_free(net->ctx, s->dense_logits);
     if (s->resize_buf) mbn_free(net->ctx, s->resize_buf);
+    if (s->guide_lo) mbn_free(net->ctx, s->guide_lo);
+    if (s->guided_lut) mbn_free(net->ctx, s->guided_lut);
     if (s->resizer) mbn_resizer_destroy(s->resizer);
     if (s->ragged) mbn_ragged_resizer_destroy(s->ragged);
     for (int i = 0; i < MBN_ENSEMBLE_MAX_VIEWS; i++)

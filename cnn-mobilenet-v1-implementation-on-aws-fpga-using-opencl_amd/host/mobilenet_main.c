@@ -31,6 +31,10 @@
  *   is shown to the network at every scale (0 < S <= 1: the letterbox shrunk about the centre of the input), with --tta-flip also mirrored, and ONE
  *   read-out averages the views' logits. The views are (S1, plain), (S1, mirrored), (S2, plain), ... in that order, 8 at most (else usage status 2);
  *   --segment-confidence, --min-confidence and --ignore-label work as without it
+ *   --guided SIGMA (with ONE --ppm, --segment-source and --fit stretch or --fit pad; SIGMA finite and > 0): the read-out along the image's edges,
+ *   mbn_net_segment_guided_fit: the bilinear weights of every pixel are scaled by exp(-d^2 / (2 SIGMA^2)), d the L1 colour distance between the pixel
+ *   of the --ppm file itself and the block mean of what the network saw. --segment-confidence, --min-confidence, --ignore-label, --truth and the
+ *   scoring flags work as without it; not with --segment-topk, --tta-scales, --slide or --nll: usage status 2
  *   --slide TH[xTW] [--slide-stride SH[xSW]] (with ONE --ppm and --segment-source; rows x columns): sliding-window segmentation,
  *   mbn_net_segment_slide: overlapping TH x TW crops of the image, each stretched to the network's input, and ONE read-out that averages the crops'
  *   logits where they overlap. The default stride is (2 * tile + 2) / 3 per axis. The fit is the stretch: with --fit pad or --fit crop, or with
@@ -882,8 +886,8 @@ static int write_confidence_map(const char *path, const float *prob, int rows, i
  * ro->on (--regions): the regions of every map are printed first; with --min-area > 1 the cleaned maps take the place of the maps from there on.
  * n_truth > 0 (--truth, one per image): the maps are scored against them on the device before anything is written */
 static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int n_ppm, const char *path, int classes, int fit, const char *conf_path,
-                          float min_conf, int ignore, const float *scales, const int32_t *mirrors, int n_views, const int *slide, const char **truths,
-                          int n_truth, const region_opts *ro, const boundary_opts *bo, const panoptic_opts *po)
+                          float min_conf, int ignore, const float *scales, const int32_t *mirrors, int n_views, const int *slide, float guided,
+                          const char **truths, int n_truth, const region_opts *ro, const boundary_opts *bo, const panoptic_opts *po)
 {
     int64_t *offs = malloc(sizeof(int64_t) * (size_t)n_ppm), *dst = malloc(sizeof(int64_t) * (size_t)n_ppm);
     int32_t *hs = malloc(sizeof(int32_t) * (size_t)n_ppm), *ws = malloc(sizeof(int32_t) * (size_t)n_ppm);
@@ -911,7 +915,12 @@ static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int
     CHECK(mbn_alloc(ctx, sizeof(int) * pixels, &d_labels));
     CHECK(mbn_upload(ctx, d_src, all, total));
     if (!(min_conf > 0.0f)) ignore = -1;                        /* --min-confidence 0 replaces nothing: the argmax read-out, unless a map is asked for */
-    if (slide) {
+    if (guided > 0.0f) {
+        if (conf_path) CHECK(mbn_alloc(ctx, sizeof(float) * pixels, &d_prob));
+        CHECK(mbn_net_segment_guided_fit(net, d_src, 1, hs[0], ws[0], fit, guided, d_labels, d_prob, NULL, ignore >= 0 ? min_conf : 0.0f,
+                                         ignore >= 0 ? ignore : 0));
+        printf("segment: guided by the source image, sigma %g\n", (double)guided);
+    } else if (slide) {
         if (conf_path) CHECK(mbn_alloc(ctx, sizeof(float) * pixels, &d_prob));
         CHECK(mbn_net_segment_slide(net, d_src, 1, hs[0], ws[0], slide[0], slide[1], slide[2], slide[3], d_labels, d_prob, NULL,
                                     ignore >= 0 ? min_conf : 0.0f, ignore >= 0 ? ignore : 0));
@@ -1132,7 +1141,8 @@ int main(int argc, char **argv)
     int fit = MBN_FIT_CROP, filter = MBN_FILTER_BILINEAR;
     int pad_rgb[3] = { 0, 0, 0 }, src_h0 = 0, src_w0 = 0;              /* src_h0 x src_w0: image 0 as it was resized (0: it was not) */
     float crop_fraction = 1.0f, min_conf = 0.0f;
-    int have_min_conf = 0, have_ignore = 0, ignore_label = -1, have_topk = 0, segment_topk = 0, have_calibration = 0, calibration_bins = 0, have_nll = 0;
+    int have_min_conf = 0, have_ignore = 0, ignore_label = -1, have_topk = 0, segment_topk = 0, have_calibration = 0, calibration_bins = 0, have_nll = 0, have_guided = 0;
+    float guided = 0.0f;
     const char *temperatures = NULL;
     const char *tta = NULL, *slide_arg = NULL, *slide_stride_arg = NULL;
     int fit_given = 0, slide[4] = { 0, 0, 0, 0 }, slide_tiles = 0;      /* slide: tile rows, tile columns, stride rows, stride columns */
@@ -1166,6 +1176,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--segment") && i + 1 < argc) segment = argv[++i];
         else if (!strcmp(argv[i], "--segment-source") && i + 1 < argc) segment_src = argv[++i];
         else if (!strcmp(argv[i], "--segment-confidence") && i + 1 < argc) segment_conf = argv[++i];
+        else if (!strcmp(argv[i], "--guided") && i + 1 < argc) { guided = (float)atof(argv[++i]); have_guided = 1; }
         else if (!strcmp(argv[i], "--segment-topk") && i + 1 < argc) { segment_topk = atoi(argv[++i]); have_topk = 1; }
         else if (!strcmp(argv[i], "--min-confidence") && i + 1 < argc) { min_conf = (float)atof(argv[++i]); have_min_conf = 1; }
         else if (!strcmp(argv[i], "--ignore-label") && i + 1 < argc) { ignore_label = atoi(argv[++i]); have_ignore = 1; }
@@ -1266,6 +1277,12 @@ int main(int argc, char **argv)
         fprintf(stderr, "--segment-topk K (1 <= K <= %d) needs one --ppm and --segment-source with --fit stretch or --fit pad; it goes with "
                         "--segment-confidence, --min-confidence / --ignore-label and --truth, not with --tta-scales, --slide, --regions, --panoptic or "
                         "--boundary-*\n", MBN_TOPK_MAX);
+        return 2;
+    }
+    if (have_guided && (!(guided > 0.0f) || guided > 3.0e38f || !segment_src || n_ppm != 1 || have_topk || tta || tta_flip || slide_arg || have_nll)) {
+        fprintf(stderr, "--guided SIGMA (finite, > 0) needs one --ppm and --segment-source with --fit stretch or --fit pad; it goes with "
+                        "--segment-confidence, --min-confidence / --ignore-label, --truth and the scoring flags, not with --segment-topk, --tta-scales, "
+                        "--slide or --nll\n");
         return 2;
     }
     if (tta || tta_flip) {
@@ -1516,7 +1533,7 @@ int main(int argc, char **argv)
         if (bad) return bad;
     } else if (segment_src || segment_conf) {
         const int bad = segment_source(ctx, net, ppms, n_ppm, segment_src, classes, fit, segment_conf, min_conf, have_ignore ? ignore_label : -1,
-                                       view_scales, view_mirrors, n_views, slide_tiles ? slide : NULL, truths, n_truth, &regions, &boundary, &panoptic);
+                                       view_scales, view_mirrors, n_views, slide_tiles ? slide : NULL, guided, truths, n_truth, &regions, &boundary, &panoptic);
         if (bad) return bad;
     }
     mbn_net_destroy(net);

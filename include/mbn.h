@@ -841,6 +841,47 @@ int mbn_resample_nll_envelope(int batch, int rows, int cols, int classes, int in
                               int truth_bytes, int temps);
 int mbn_nll_metrics(const uint64_t *nll_u64, int classes, int temps, int j, mbn_nll *m, double *class_nll, double *class_brier);
 int mbn_nll_best(const uint64_t *nll_u64, int classes, int temps, const float *inv_temps, int *best, double *inv_temp, int *at_edge);
+/* Segment along the image's edges: the read-out to any output size with the bilinear weights GUIDED by the source image, joint bilateral upsampling
+ * (Kopf et al. 2007). The bilinear read-outs above place an object's boundary by the spatial weights alone, up to half a coarse
+ * cell (16 input pixels at output stride 32) from the edge the image shows. Here each of the four coarse neighbours also gets a RANGE weight that
+ * falls with the colour difference between the output pixel in the source image and the neighbour's colour in a low-resolution copy of what the
+ * network saw. The weights do not depend on the class: one kernel (mbn_f32_guided.hip), [out_rows][out_cols][classes] never in memory.
+ * Inputs: logits fp32 [batch][rows][cols][classes]; guide_hi_u8 [batch][out_rows][out_cols][3], the source image; guide_lo_u8
+ * [batch][rows][cols][3]; lut_f32, MBN_GUIDED_LUT = 766 fp32 values ON THE DEVICE; rect[4] with in_rows, in_cols, the window of
+ * mbn_resample_argmax_window_f32, or NULL for the whole map (in_rows, in_cols are then not read).
+ * Normative (tests/dense_guided_ref.py reproduces it bit for bit in numpy):
+ *   Indices and spatial weights. Per output pixel (oy, ox): (i0y, w1y) and (i0x, w1x) exactly as mbn_resample_argmax_f32 gives them, with a rect
+ *     exactly as mbn_resample_argmax_window_f32 does; i1 = min(i0 + 1, n - 1); w0 = 1.0f - w1. Neighbour (j, k) in {0,1}^2 is (iy_j, ix_k).
+ *   Range weight. d_jk = |dR| + |dG| + |dB| between guide_hi at (oy, ox) and guide_lo at (iy_j, ix_k): an integer in 0..765; g_jk = lut[d_jk].
+ *   Combination. Every product, sum and quotient is one fp32 operation that rounds on its own (no contraction):
+ *       a_jk = (wy_j * wx_k) * g_jk;   A = ((a00 + a01) + a10) + a11;   b_jk = a_jk / A   (the correctly rounded fp32 quotient);
+ *       v_c  = (b00 * x00_c + b01 * x01_c) + (b10 * x10_c + b11 * x11_c)                   (x_jk: the logits of neighbour (j, k)).
+ *     A zero weight still multiplies (0 * inf is a NaN, as in the bilinear read-out).
+ *   Argmax, score, prob. Classes in ascending order, class c taken iff v_c > best (strict); a NaN never wins; a pixel where nothing wins is label 0
+ *     with score -inf. score = the winning v. prob (optional) is the softmax probability of the winner over the v_c, with the formula, the min_prob /
+ *     ignore_label rule and the error bound stated for mbn_resample_softmax_f32 above ((classes + 200) * 2^-24 relative, 0 exactly where the best
+ *     is not finite). prob_f32 = NULL with min_prob = 0 is the argmax form; score_f32 may be NULL.
+ *   The table. mbn_guided_lut(sigma, lut) fills lut[d] = max((float)exp(-(double)d * d / (2 sigma^2)), 2^-60), d = 0..765, on the HOST (it is part of
+ *     libmbn_host.so; copy it to the device). lut[0] = 1. MBN_EINVAL unless sigma is finite and > 0, or for a NULL lut. The floor keeps A > 0 for
+ *     every input: one of the four wy * wx is at least 1/4 and 2^-60 * 2^-48 is still a normal fp32 number, so there is no zero sum to define. Any
+ *     766 positive values may be given instead; the kernel only looks them up.
+ *   The low-resolution guide. mbn_guide_reduce_u8 writes guide_lo_u8 [batch][in_rows / S][in_cols / S][3] from the network's input canvas_u8
+ *     [batch][in_rows][in_cols][3]: each channel of a coarse cell is the rounded mean of its S x S block, (sum + S * S / 2) / (S * S) in integers.
+ *     S is the plan's output stride. MBN_EINVAL unless S >= 1 divides both sides (and for a NULL pointer or a non-positive size); MBN_EUNSUPPORTED for
+ *     a side above 16384, S above 2048 or a batch above 65535. Under a letterbox the border cells carry the pad colour, so their logits are
+ *     down-weighted for every image pixel that does not look like the pad: that is intended, the network saw no image there.
+ * With a flat guide (every g equal) the b_jk are the bilinear weights up to the roundings of the combination: the labels are the bilinear
+ * read-out's wherever the top two classes differ by more than the tolerance (16 * 2^-24 * max|x|; tests/dense_guided_ref.py derives it).
+ * The envelope, the size limits and their statuses are those of mbn_resample_argmax_window_f32 (out >= 4 x coarse on both axes under the window;
+ * a NULL rect: those of mbn_resample_argmax_f32). MBN_EINVAL: NULL labels / logits / guide_lo / guide_hi / lut; labels, score, prob, logits or lut
+ * off 4 bytes (the guides: any byte pointer); min_prob outside [0, 1]. Nothing is launched on a refusal. The mbn_alloc bounds rule applies to every
+ * operand. Each call is ONE kernel and may be captured as one kernel node. */
+#define MBN_GUIDED_LUT 766
+int mbn_guided_lut(float sigma, float lut[MBN_GUIDED_LUT]);
+int mbn_guide_reduce_u8(mbn_context *ctx, void *guide_lo_u8, const void *canvas_u8, int batch, int in_rows, int in_cols, int S, void *stream);
+int mbn_resample_guided_f32(mbn_context *ctx, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, const void *guide_lo_u8,
+                            const void *guide_hi_u8, const void *lut_f32, int batch, int rows, int cols, int classes, int in_rows, int in_cols,
+                            const int32_t rect[4], int out_rows, int out_cols, float min_prob, int ignore_label, void *stream);
 /* Regions of a label map: connected-component labelling of the int32 maps the read-outs above write, on the device.
  * Normative (tests/components_ref.py is the numpy form; everything is integer, so the result is a function of the input alone: the same bytes at
  * every planning CU count, in both forms, on every run and on graph replay). For one image L [rows][cols] and classes >= 1:
@@ -1648,6 +1689,18 @@ int  mbn_net_segment_prob_fit(mbn_net *net, const void *src_u8, int batch, int i
                               float min_prob, int ignore_label);
 int  mbn_net_segment_prob_images_fit(mbn_net *net, const void *src_u8, const int64_t *offsets, const int32_t *rows, const int32_t *cols, int batch,
                                      int fit, void *labels_i32, const int64_t *dst_offsets, void *prob_f32, float min_prob, int ignore_label);
+/* Segment along the image's edges (mbn_resample_guided_f32 above): mbn_net_segment_fit with the guided read-out, the source image itself as
+ * guide_hi. Everything that can refuse is checked first (what mbn_net_segment_fit and the softmax calls refuse; sigma not finite or not > 0:
+ * MBN_EINVAL; a plan whose map does not divide its input by one integer stride on both axes: MBN_EUNSUPPORTED). Then mbn_net_resize_input with
+ * `fit`, mbn_guide_reduce_u8 of the staging buffer it returns with S = the plan's output stride, mbn_net_forward_dense, and ONE
+ * mbn_resample_guided_f32 to in_rows x in_cols: the whole map under MBN_FIT_STRETCH, mbn_fit_pad's rectangle under MBN_FIT_PAD (the border cells
+ * carry the pad colour and are down-weighted for every pixel that does not look like it). labels_i32, prob_f32 (may be NULL) and score_f32 (may be
+ * NULL) [batch][in_rows][in_cols]; prob_f32 = NULL with min_prob = 0 is the argmax form. The net keeps the coarse guide ([max_batch][h][w][3]) and
+ * the device table of the last sigma (another sigma waits for the stream and uploads a new table); both are freed by mbn_net_destroy. Every dtype
+ * the dense head runs in. The call is recorded as the net's most recent successful segment call: mbn_net_segment_score, _regions, _boundary_*,
+ * _surface, _panoptic and _calibration work on its maps unchanged (mbn_net_segment_nll does not: no bilinear read-out of the logits gives these maps). */
+int  mbn_net_segment_guided_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, float sigma, void *labels_i32,
+                                void *prob_f32, void *score_f32, float min_prob, int ignore_label);
 /* Segment with runners-up (mbn_resample_topk_f32 above): mbn_net_segment_prob_fit / _prob_images_fit, step for step, with the top-k read-out, in every
  * dtype those serve. labels_i32, prob_f32 and score_f32 are rank-major: [k][batch][in_rows][in_cols] for the uniform call; for the image call rank j
  * of image i at j * plane_stride + dst_offsets[i] (plane_stride in elements, at least max(dst_offsets + rows * cols)). prob_f32 = NULL with

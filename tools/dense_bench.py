@@ -350,6 +350,70 @@ def main_prob(a):
     print(json.dumps(result))
 
 
+def guided_work(batch, h, w, classes, pix, prob):
+    """(bytes, vector issue slots) of the guided read-out: the logits and the coarse guide once, 3 bytes of guide_hi and 8 (12 with prob) bytes of
+    output per pixel; per pixel and class four products, three sums, one compare and two selects (the two selects of a row that crosses a coarse
+    row are not counted: an under-count by up to 2 of 10), with prob the softmax sum's slots of prob_work"""
+    return (4.0 * batch * h * w * classes + 3.0 * batch * h * w + (15.0 if prob else 11.0) * pix,
+            pix * classes * (10.0 + (6.0 + 5.0 / 4 if prob else 0.0)))
+
+
+def main_guided(a):
+    """--guided: mbn_resample_guided_f32 beside the bilinear window read-outs, --batch maps of random logits (sigma 3) to 375 x 500 through
+    mbn_fit_pad's rectangle of a 224 x 224 input, from the 28 x 28 and the 14 x 14 map, 1000 and 21 classes, without and with prob. guide_hi is
+    random uint8, guide_lo the block mean of a random canvas, the table mbn_guided_lut(24). Per shape, alternating within every repetition on the
+    same buffers: the window kernel (argmax / softmax), then the guided kernel. Each figure is the median over the repetitions of `steps`
+    back-to-back calls between two stream marks; the runs are kept, the spread is (max - min) / median of a name's own repetitions."""
+    pkg = import_package()
+    n, rng = a.batch, np.random.default_rng(0)
+    H, W = 375, 500
+    rect = tuple(pkg.fit_pad(H, W, RES, RES))
+    result = {"batch": n, "rect": list(rect), "sigma": 24.0}
+    with pkg.Context(0) as ctx:
+        d_lab, d_sc, d_pr = (ctx.alloc(n * H * W * 4) for _ in range(3))
+        d_hi = ctx.to_device(rng.integers(0, 256, (n, H, W, 3), dtype=np.uint8))
+        d_canvas = ctx.to_device(rng.integers(0, 256, (n, RES, RES, 3), dtype=np.uint8))
+        d_lut = ctx.to_device(pkg.guided_lut(24.0))
+        runs = []
+        for classes in (CLASSES, 21):
+            for hw_ in (28, 14):
+                d_x = ctx.to_device((3.0 * rng.standard_normal((n, hw_, hw_, classes))).astype(np.float32))
+                d_lo = ctx.alloc(n * hw_ * hw_ * 3)
+                ctx.guide_reduce(d_lo.ptr, d_canvas.ptr, n, RES, RES, RES // hw_)
+                g = (d_x.ptr, n, hw_, hw_, classes)
+                for prob in (False, True):
+                    pr = d_pr.ptr if prob else None
+                    base = (lambda g=g: ctx.resample_softmax_window(d_lab.ptr, d_pr.ptr, d_sc.ptr, *g, RES, RES, rect, H, W)) if prob else \
+                           (lambda g=g: ctx.resample_argmax_window(d_lab.ptr, d_sc.ptr, *g, RES, RES, rect, H, W))
+                    guided = lambda g=g, pr=pr, lo=d_lo.ptr: ctx.resample_guided(d_lab.ptr, pr, d_sc.ptr, g[0], lo, d_hi.ptr, d_lut.ptr, *g[1:], H, W,
+                                                                                 RES, RES, rect)
+                    runs.append(("from_%d_classes_%d_%s" % (hw_, classes, "softmax" if prob else "argmax"), base, guided, (hw_, classes, prob)))
+        times = {(name, k): [] for name, _, _, _ in runs for k in ("bilinear", "guided")}
+        for _, base, guided, _ in runs:
+            marks_ms(ctx, base, 3)
+            marks_ms(ctx, guided, 3)
+        for _ in range(a.reps):
+            for name, base, guided, _ in runs:
+                times[(name, "bilinear")].append(marks_ms(ctx, base, a.steps))
+                times[(name, "guided")].append(marks_ms(ctx, guided, a.steps))
+        for name, _, _, (hw_, classes, prob) in runs:
+            pix, out = n * H * W, {}
+            work = {"bilinear": prob_work(n, hw_, hw_, classes, pix) if prob else resample_work(n, hw_, hw_, classes, pix),
+                    "guided": guided_work(n, hw_, hw_, classes, pix, prob)}
+            for k in ("bilinear", "guided"):
+                ts = times[(name, k)]
+                m = statistics.median(ts)
+                out[k] = {"kernel_ms": round(m, 4), "kernel_runs_ms": [round(v, 4) for v in ts], "spread": round((max(ts) - min(ts)) / m, 4),
+                          "kernel_frac_of_8TBps": round(work[k][0] / HBM_BYTES_PER_S / (m / 1e3), 4),
+                          "kernel_frac_of_valu_rate": round(work[k][1] / VALU_LANE_OPS_PER_S / (m / 1e3), 4)}
+            out["guided_over_bilinear"] = round(out["guided"]["kernel_ms"] / out["bilinear"]["kernel_ms"], 3)
+            result[name] = out
+            print("%-32s bilinear %.4f ms (spread %.1f %%)  guided %.4f ms (spread %.1f %%, %.1f %% of the VALU rate, %.1f %% of 8 TB/s)  ratio %.3f"
+                  % (name, out["bilinear"]["kernel_ms"], 100 * out["bilinear"]["spread"], out["guided"]["kernel_ms"], 100 * out["guided"]["spread"],
+                     100 * out["guided"]["kernel_frac_of_valu_rate"], 100 * out["guided"]["kernel_frac_of_8TBps"], out["guided_over_bilinear"]), flush=True)
+    print(json.dumps(result))
+
+
 def nll_work(batch, h, w, classes, pix, temps):
     """(bytes, vector issue slots) of the NLL read-out: two passes of resample_work's upper count of lerps (the second without the compare's two
     selects but with the truth's compare and select and the subtract and max of d), and per temperature a multiply, one v_exp_f32 at two slots,
@@ -1613,7 +1677,10 @@ def main():
     ap.add_argument("--calibration", action="store_true", help="time mbn_calibration_f32 beside mbn_confusion_i32 and torch instead: see main_calibration")
     ap.add_argument("--surface", action="store_true", help="time mbn_surface_score_i32 beside torch.cdist and scipy's distance transform instead: see main_surface")
     ap.add_argument("--nll", action="store_true", help="time mbn_resample_nll_f32 beside the argmax and softmax read-outs and torch instead: see main_nll")
+    ap.add_argument("--guided", action="store_true", help="time mbn_resample_guided_f32 beside the bilinear window read-outs instead: see main_guided")
     a = ap.parse_args()
+    if a.guided:
+        return main_guided(a)
     if a.nll:
         return main_nll(a)
     if a.calibration:
