@@ -3,42 +3,13 @@
 // the source resolution", is the normative statement of the arithmetic). mbn_f32_dense.hip is the integer-factor sibling and stays mbn_net_segment's:
 // its structure rests on the factor (a lane's four rows share one patch, a tile owns (P+1)^2 vectors on a grid shifted by S/2); neither holds here.
 //
-// The resampled tensor [out_rows][out_cols][classes] is never formed in memory. A workgroup of 256 lanes owns a 32 x 32 output tile (unshifted: tile
-// (ty, tx) starts at output (32 ty, 32 tx)). The envelope's ratio (out >= 4 x coarse on both axes) bounds what a tile touches: along an axis the
-// source span of 32 outputs is 31 n / N < 8, so i0 takes at most floor(31 n / N) + 2 values and i1 one more: MBN_RESAMPLE_FOOT(n, N) <= 10 coarse
-// rows / columns, fy x fx class vectors. The launch's dynamic LDS holds exactly that footprint (6 x 6 at ratio 8, 10 x 10 only at ratio 4).
-//   stage   per class chunk the fy x fx vectors go from global memory to LDS once (16-byte loads when `logits` is on 16 bytes and classes % 4 == 0,
-//           else dword loads; classes past the end are staged as NaN, which never wins). Vector (j, i) is coarse row min(ybase + j, rows - 1),
-//           column min(xbase + i, cols - 1), ybase / xbase = i0 of the tile's first output row / column;
-//   reduce  a lane owns one output column and four consecutive output rows. Four rows span 3 n / N < 1 of the source, so their i0 is ya or ya + 1
-//           and they touch at most the three coarse rows ya, ya + 1, ya + 2 (clamped). Per class the lane forms the three horizontal interpolants
-//           t0, t1, t2 of its column once; row r takes (t0, t1) or (t1, t2) by a per-row select and keeps a running (best, label) in registers.
-//           A wave neither of whose two row groups crosses a coarse row (a group crosses with probability about 3 n / N; none does at an integer
-//           factor, where i0 steps at multiples of 4) takes the loop without t2 and without the selects: the same products and sums.
-// Classes are visited in ascending order with a strict compare, which IS the definition, so there is no cross-lane reduction. Borders are no special
-// case: every lane evaluates the normative index / weight rule for its own pixel, the weight's quotient in fp64 rounded once to fp32.
-// Every product and sum rounds on its own: contraction into FMA is switched off where they are formed (the build contracts by default).
-// The class chunk is the launch's (MBN_RESAMPLE_CH): 128 while the footprint still leaves eight workgroups on a CU's 160 KB, else 64.
-// The uniform and the ragged form share the tile body; they differ in where a workgroup finds its image's (out_rows, out_cols, destination).
-// WIN (mbn_resample_argmax_window_f32, mbn_ragged_readout_set_window): the outputs resample a rectangle of the network's input, the letterbox's
-// inner image, instead of the whole map. Only the index / weight rule differs (rs_axis_win: 64-bit integers, still one fp64 division per axis
-// coordinate, once per lane in front of the class loop); the footprint bound holds with n / N replaced by l n / (N R) (host/mbn_envelope.h), so
-// stage, reduce, the cross ballot, the store and the LDS layout are the same code. The other instantiations compile to what they were without it.
-// On the host the whole map is the window that covers the whole input (host/mbn_envelope.c: one envelope, one plan), and here one launch entry
-// takes an optional rectangle. The device keeps both rules: the window rule's 64-bit divisions cost 0.6-0.7 % at equal footprint (profiles/LOG.md,
-// "Through the letterbox"), so WIN stays a compile-time parameter and a null rectangle launches the plain kernels.
-// PROB (mbn_resample_softmax_f32, _window_f32, _ragged_f32; include/mbn.h, "segment with confidence"): the same tile body also keeps the softmax
-// denominator of each of the lane's four pixels and writes prob = 1 / sum_c exp(v_c - best) beside the label; labels and scores are the argmax
-// instantiations' bit for bit (the same v, the same compare). The sum is ONE pass with a LAZY reference: per row a reference `ref` and
-// sum = sum_c exp(v_c - ref). Per four classes the row's maximum m of the four is compared with ref: more than RS_MARGIN = 16 above it, m becomes
-// the reference and the old sum is rescaled by exp(ref - m) < e^-16; then the four add exp(v - ref). So every v seen is at most 16 above ref,
-// best - ref stays in [0, 16], ref is itself a v seen (its term is exp(0) = 1: sum >= 1), and a part of the sum that went through k rescales
-// weighs below classes * e^(-16 (k - 1)) of it: only the first rescale of a part counts, and an ascending ramp costs one rescale per 16 units of
-// logit instead of one per class. That is what keeps the error bound of include/mbn.h for every input. The alternative, a second pass with the
-// final best, stages every chunk and forms every interpolant twice: about 10 plain VALU per pixel and class on top of the same exp, against
-// about 7 issue slots here (subtract, max, multiply, add, v_exp_f32 at two slots, and a quarter of the group's three maxima, subtract and
-// compare). prob = exp(best - ref) / sum at the end, 0 when best is not finite. A NaN v (the padding classes of the dword path among them) is
-// dropped by the maxima, and its difference is replaced by -200 by a max that drops the NaN: it adds exp(-200) = 0, exactly.
+// The tile all of this file's kernels run on (a 32 x 32 output tile per workgroup, one column and four rows per lane, an fy x fx footprint staged per
+// class chunk), the index / weight rule, the stage pass, the lerps, the lazy-reference softmax sum and the store are mbn_readout_tile.h's, described
+// there with WIN and PROB. The uniform and the ragged form share the tile body; they differ in where a workgroup finds its image's (out_rows,
+// out_cols, destination).
+// WIN (mbn_resample_argmax_window_f32, mbn_ragged_readout_set_window): on the host the whole map is the window that covers the whole input
+// (host/mbn_envelope.c: one envelope, one plan), and here one launch entry takes an optional rectangle; a null rectangle launches the plain kernels.
+// PROB (mbn_resample_softmax_f32, _window_f32, _ragged_f32): the same tile body also writes prob beside the label.
 // ENSEMBLE (mbn_resample_ensemble_f32; include/mbn.h, "segment with test-time augmentation"): K views read out as one map, kernels of their own on
 // the same tile, stage pass, lerps, softmax sum and store; described where they stand, behind rs_launch.
 // SLIDE (mbn_resample_slide_f32; include/mbn.h, "segment by sliding window"): a grid of overlapping tiles read out as one map, the ensemble's sibling
@@ -48,14 +19,12 @@
 #include "mbn_internal.h"
 #include "mbn_device.h"
 #include "mbn_label_set.h"
+#include "mbn_readout_tile.h"
 
 #include <new>
 #include <type_traits>
 
 namespace {
-
-constexpr int RS_TILE = MBN_RESAMPLE_TILE;   // output tile side of a workgroup
-constexpr int RS_ROWS = 4;                   // output rows of a lane
 
 struct ResampleArgs {
     int *labels;
@@ -79,154 +48,19 @@ struct ResampleArgs {
     int ignore_label;
 };
 
-constexpr float RS_MARGIN = 16.0f;           // the lazy reference moves when a logit exceeds it by more than this
-
-// a window of the network's input along one axis: [b, b + l) of the R pixels the n coarse samples cover
-struct RsWindow {
-    int R, b, l;
-};
-
-// a * wa + b * wb with three roundings
-__device__ __forceinline__ float rs_lerp(float a, float wa, float b, float wb)
-{
-#pragma clang fp contract(off)
-    const float p = a * wa, q = b * wb;
-    return p + q;
-}
-
-// the normative index / weight rule for output coordinate o of an axis with n coarse samples and N outputs: i0 and the weight of i1
-__device__ __forceinline__ void rs_axis(int o, int n, int N, int *i0, float *w1)
-{
-    const int num = max((2 * o + 1) * n - N, 0), den = 2 * N;
-    *i0 = num / den;
-    *w1 = (float)((double)(num % den) / (double)den);       // fp64 quotient, rounded once
-}
-
-// The same for a window (include/mbn.h, "segment through the letterbox"): output o of N sits at input coordinate b + (o + 1/2) l / N. 64-bit integers
-// (num < 2^46, den <= 2^29 inside the envelope: both exact in fp64); evaluated once per lane and axis coordinate, outside the class loop.
-__device__ __forceinline__ void rs_axis_win(int o, int n, int N, const RsWindow &w, int *i0, float *w1)
-{
-    const int64_t num = max((int64_t)(2 * o + 1) * w.l * n + 2 * (int64_t)w.b * n * N - (int64_t)N * w.R, (int64_t)0), den = 2 * (int64_t)N * w.R;
-    const int64_t q = num / den;
-    *i0 = (int)q;
-    *w1 = (float)((double)(num - q * den) / (double)den);   // fp64 quotient, rounded once
-}
-
-template <bool WIN>
-__device__ __forceinline__ void rs_coord(int o, int n, int N, const RsWindow &w, int *i0, float *w1)
-{
-    if (WIN) rs_axis_win(o, n, N, w, i0, w1);
-    else rs_axis(o, n, N, i0, w1);
-}
-
-// exp(d) for the softmax sum: d <= RS_MARGIN, -inf gives 0. One multiply and v_exp_f32 (1 ulp; a result below 2^-126 may flush to 0, far below
-// the bound against a sum of at least 1).
-__device__ __forceinline__ float rs_exp(float d) { return __builtin_amdgcn_exp2f(d * 1.44269504088896341f); }
-
-// The lazy-reference softmax sum (the file's head) of a lane's four rows over one group of four classes, vv[r][k] = row r's v of the group's class k:
-// the ensemble kernels' copy of what rs_reduce does in place. rs_reduce keeps its own text because the sixteen kernels built from it are pinned to
-// the registers they had before the ensemble existed, and calling this from there moved the softmax ones from 102 to 98 VGPRs
-__device__ __forceinline__ void rs_softmax_group(const float (&vv)[RS_ROWS][4], float (&ref)[RS_ROWS], float (&sum)[RS_ROWS])
-{
-#pragma clang fp contract(off)                      // the same operations in every instantiation: a pixel's prob does not depend on the kernel
-#pragma unroll
-    for (int r = 0; r < RS_ROWS; r++) {
-        // the reference moves at most once per four classes, to their maximum m (the maxima drop NaNs; an all-NaN m fails the compare, and
-        // so does -inf - -inf): everything seen so far is then at most RS_MARGIN above ref, the four included
-        const float m = __builtin_fmaxf(__builtin_fmaxf(vv[r][0], vv[r][1]), __builtin_fmaxf(vv[r][2], vv[r][3]));
-        if (m - ref[r] > RS_MARGIN) { sum[r] *= rs_exp(ref[r] - m); ref[r] = m; }
-#pragma unroll
-        for (int k = 0; k < 4; k++) sum[r] += rs_exp(__builtin_fmaxf(vv[r][k] - ref[r], -200.0f));     // a NaN difference adds exp(-200) = 0
-    }
-}
-
-// The reduce pass of one staged chunk of cn4 classes for a lane's four rows. CROSS: some row of the wave interpolates between (ya + 1, ya + 2), so
-// the third interpolant and the per-row selects are needed; otherwise every row of the wave uses (t0, t1) and neither is formed. The same products
-// and sums in the same order either way. PROB: each row's lazy reference and softmax sum follow v (the file's head); untouched otherwise.
+// The reduce pass of one staged chunk of cn4 classes for a lane's four rows: every interpolant meets the strict compare. PROB: each row's lazy
+// reference and softmax sum follow v; untouched otherwise.
 template <bool CROSS, bool PROB>
-__device__ __forceinline__ void rs_reduce(const float *(&p)[3][2], int cn4, int c0, float wx0, float wx1, const float (&wy0)[RS_ROWS],
-                                          const float (&wy1)[RS_ROWS], const bool (&up)[RS_ROWS], float (&best)[RS_ROWS], int (&label)[RS_ROWS],
+__device__ __forceinline__ void rs_reduce(const float *s_x, const RsLane &n, int cn4, int c0, float (&best)[RS_ROWS], int (&label)[RS_ROWS],
                                           float (&ref)[RS_ROWS], float (&sum)[RS_ROWS])
 {
-    constexpr int NT = CROSS ? 3 : 2;
     for (int c = 0; c < cn4; c += 4) {
-        f4 v0[NT], v1[NT];
         float vv[RS_ROWS][4];                                                               // PROB: the four classes' v of each row
-#pragma unroll
-        for (int j = 0; j < NT; j++) {
-            v0[j] = *reinterpret_cast<const f4 *>(p[j][0] + c);
-            v1[j] = *reinterpret_cast<const f4 *>(p[j][1] + c);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            float t[NT];
-#pragma unroll
-            for (int j = 0; j < NT; j++) t[j] = rs_lerp(v0[j][k], wx0, v1[j][k], wx1);      // horizontal first
-#pragma unroll
-            for (int r = 0; r < RS_ROWS; r++) {
-                const float ta = CROSS && up[r] ? t[1] : t[0], tb = CROSS && up[r] ? t[NT - 1] : t[1];
-                const float v = rs_lerp(ta, wy0[r], tb, wy1[r]);                            // then vertical
-                if (v > best[r]) { best[r] = v; label[r] = c0 + c + k; }
-                if (PROB) vv[r][k] = v;
-            }
-        }
-        if (PROB) {
-#pragma clang fp contract(off)                      // the same operations in every instantiation: a pixel's prob does not depend on the kernel
-#pragma unroll
-            for (int r = 0; r < RS_ROWS; r++) {
-                // the reference moves at most once per four classes, to their maximum m (the maxima drop NaNs; an all-NaN m fails the compare, and
-                // so does -inf - -inf): everything seen so far is then at most RS_MARGIN above ref, the four included
-                const float m = __builtin_fmaxf(__builtin_fmaxf(vv[r][0], vv[r][1]), __builtin_fmaxf(vv[r][2], vv[r][3]));
-                if (m - ref[r] > RS_MARGIN) { sum[r] *= rs_exp(ref[r] - m); ref[r] = m; }
-#pragma unroll
-                for (int k = 0; k < 4; k++) sum[r] += rs_exp(__builtin_fmaxf(vv[r][k] - ref[r], -200.0f));     // a NaN difference adds exp(-200) = 0
-            }
-        }
-    }
-}
-
-// The stage pass of one class chunk (classes c0 .. c0 + cn - 1, cn4 = cn rounded up to 4): the nv = fy x fx vectors of one image's map, from
-// (ybase, xbase) on and clamped to the map, go to s_x, ld floats apart. VEC: 16-byte loads; else dword loads, the classes past cn staged as NaN
-template <bool VEC>
-__device__ __forceinline__ void rs_stage(float *s_x, const float *__restrict__ src, int ybase, int xbase, int fx, int nv, int ld, int cols, int classes,
-                                         int last_y, int last_x, int c0, int cn, int cn4, int tid)
-{
-    if (VEC) {
-        const int q = cn4 >> 2;                  // classes % 4 == 0: cn4 == cn
-        for (int e = tid; e < nv * q; e += 256) {
-            const int v = e / q, c = (e - v * q) << 2;
-            const int ry = min(ybase + v / fx, last_y), rx = min(xbase + v % fx, last_x);
-            *reinterpret_cast<f4 *>(s_x + v * ld + c) = *reinterpret_cast<const f4 *>(src + (unsigned)((ry * cols + rx) * classes + c0 + c));
-        }
-    } else {
-        const float nan = __builtin_nanf("");
-        for (int e = tid; e < nv * cn4; e += 256) {
-            const int v = e / cn4, c = e - v * cn4;
-            const int ry = min(ybase + v / fx, last_y), rx = min(xbase + v % fx, last_x);
-            s_x[v * ld + c] = c < cn ? src[(unsigned)((ry * cols + rx) * classes + c0 + c)] : nan;
-        }
-    }
-}
-
-// What an active lane stores for its column ox and rows oy0 .. oy0 + 3 (those inside the H x W map): the label, the score (may be null) and, PROB,
-// the probability (may be null) with the threshold on the value stored
-template <bool PROB>
-__device__ __forceinline__ void rs_store(int *__restrict__ labels, float *__restrict__ score, float *__restrict__ prob, int H, int W, int oy0, int ox,
-                                         const float (&best)[RS_ROWS], int (&label)[RS_ROWS], const float (&ref)[RS_ROWS],
-                                         const float (&sum)[RS_ROWS], float min_prob, int ignore_label)
-{
-    const unsigned out = (unsigned)(oy0 * W + ox);        // 32-bit inside an image: its map is below 2^31 bytes
-#pragma unroll
-    for (int r = 0; r < RS_ROWS; r++) {
-        if (oy0 + r >= H) break;
-        if (PROB) {
-            // a finite best has a finite ref <= best <= ref + RS_MARGIN and a sum >= 1 that holds best's own term: 0 < pr <= 1
-            const float pr = __builtin_fabsf(best[r]) < __builtin_inff() ? rs_exp(best[r] - ref[r]) / sum[r] : 0.0f;
-            if (pr < min_prob) label[r] = ignore_label;                                     // strict, on the value stored below
-            if (prob) prob[out + (unsigned)(r * W)] = pr;
-        }
-        labels[out + (unsigned)(r * W)] = label[r];
-        if (score) score[out + (unsigned)(r * W)] = best[r];
+        rs_interp<CROSS>(s_x, n.off, c, n.wx0, n.wx1, n.wy0, n.wy1, n.up, [&](int r, int k, float v) __attribute__((always_inline)) {
+            if (v > best[r]) { best[r] = v; label[r] = c0 + c + k; }
+            if (PROB) vv[r][k] = v;
+        });
+        if (PROB) rs_softmax_group(vv, ref, sum);
     }
 }
 
@@ -241,40 +75,8 @@ __device__ __forceinline__ void resample_tile(const ResampleArgs &a, const float
     const int tid = threadIdx.x;
     const int ld = a.ch + 4;                  // 16-byte aligned rows, consecutive vectors 4 banks apart
     const int nv = a.fy * a.fx;
-    int ybase, xbase;
-    float unused;
-    rs_coord<WIN>(RS_TILE * ty, a.rows, H, wy, &ybase, &unused);
-    rs_coord<WIN>(RS_TILE * tx, a.cols, W, wx, &xbase, &unused);
-
-    // this lane's pixels: column ox, rows oy0 .. oy0 + 3 (a coordinate past the image is evaluated at the last one and not stored)
-    const int ox = RS_TILE * tx + (tid & 31), oy0 = RS_TILE * ty + RS_ROWS * (tid >> 5);
-    const bool active = ox < W && oy0 < H;
-    int x0, ya = 0;
-    float wx1, wy1[RS_ROWS], wy0[RS_ROWS];
-    bool up[RS_ROWS];                         // row r interpolates between (ya + 1, ya + 2) instead of (ya, ya + 1)
-    rs_coord<WIN>(min(ox, W - 1), a.cols, W, wx, &x0, &wx1);
-    const float wx0 = 1.0f - wx1;
-#pragma unroll
-    for (int r = 0; r < RS_ROWS; r++) {
-        int r0;
-        rs_coord<WIN>(min(oy0 + r, H - 1), a.rows, H, wy, &r0, &wy1[r]);
-        wy0[r] = 1.0f - wy1[r];
-        if (r == 0) ya = r0;
-        up[r] = r0 != ya;                     // r0 is ya or ya + 1: four rows span less than one coarse row
-    }
-    // the same for every lane of the wave (its two groups of rows): at ratio r about 3 / r of the groups cross a coarse row
-    const bool cross = __ballot(up[1] || up[2] || up[3]) != 0;
-    // LDS word offsets of the six vectors: rows ya, min(ya + 1, rows - 1), min(ya + 2, rows - 1) x columns x0, min(x0 + 1, cols - 1). The slots are
-    // inside the staged block by construction; the clamps cost nothing and keep every read inside the launch's LDS whatever the arguments.
-    const int last_y = a.rows - 1, last_x = a.cols - 1;
-    const int sx0 = min(max(x0 - xbase, 0), a.fx - 1), sx1 = min(max(min(x0 + 1, last_x) - xbase, 0), a.fx - 1);
-    const float *p[3][2];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        const int sy = min(max(min(ya + j, last_y) - ybase, 0), a.fy - 1);
-        p[j][0] = s_x + (sy * a.fx + sx0) * ld;
-        p[j][1] = s_x + (sy * a.fx + sx1) * ld;
-    }
+    RsLane n;
+    rs_lane<WIN>(n, a.rows, a.cols, a.fy, a.fx, ld, H, W, ty, tx, wy, wx);
 
     float best[RS_ROWS], ref[RS_ROWS], sum[RS_ROWS];      // ref, sum: the PROB instantiations' lazy reference and softmax sum
     int label[RS_ROWS];
@@ -284,17 +86,17 @@ __device__ __forceinline__ void resample_tile(const ResampleArgs &a, const float
     for (int c0 = 0; c0 < a.classes; c0 += a.ch) {
         const int cn = min(a.ch, a.classes - c0), cn4 = (cn + 3) & ~3;
         // ---- stage: nv vectors x cn4 classes
-        rs_stage<VEC>(s_x, src, ybase, xbase, a.fx, nv, ld, a.cols, a.classes, last_y, last_x, c0, cn, cn4, tid);
+        rs_stage<VEC>(s_x, src, n.ybase, n.xbase, a.fx, nv, ld, a.cols, a.classes, a.rows - 1, a.cols - 1, c0, cn, cn4, tid);
         __syncthreads();
         // ---- reduce
-        if (active) {
-            if (cross) rs_reduce<true, PROB>(p, cn4, c0, wx0, wx1, wy0, wy1, up, best, label, ref, sum);
-            else rs_reduce<false, PROB>(p, cn4, c0, wx0, wx1, wy0, wy1, up, best, label, ref, sum);
+        if (n.active) {
+            if (n.cross) rs_reduce<true, PROB>(s_x, n, cn4, c0, best, label, ref, sum);
+            else rs_reduce<false, PROB>(s_x, n, cn4, c0, best, label, ref, sum);
         }
         __syncthreads();
     }
-    if (!active) return;
-    rs_store<PROB>(labels, score, prob, H, W, oy0, ox, best, label, ref, sum, a.min_prob, a.ignore_label);
+    if (!n.active) return;
+    rs_store<PROB>(labels, score, prob, H, W, n.oy0, n.ox, best, label, ref, sum, a.min_prob, a.ignore_label);
 }
 
 template <bool VEC, bool WIN, bool PROB>
@@ -376,24 +178,10 @@ const RsKernel rs_kernels[2][2][2][2] = {
         { resample_softmax_ragged_f32<false, true>, resample_softmax_ragged_f32<true, true> } } },
 };
 
-// What every form's launch carries: the buffers, the coarse map, the launch's plan, the network input a window lies in (WIN) and q, the softmax
-// read-out's extras (null for the argmax read-out). The form adds its own: the output size and rectangle, or the handle's items.
-ResampleArgs rs_args(int32_t *labels, float *score, const float *logits, int rows, int cols, int classes, const mbn_resample_launch_t &l, int in_rows,
-                     int in_cols, const mbn_readout_prob *q)
-{
-    ResampleArgs a = {};
-    a.labels = labels; a.score = score; a.logits = logits;
-    a.rows = rows; a.cols = cols; a.classes = classes;
-    a.fy = l.fy; a.fx = l.fx; a.ch = l.ch;
-    a.in_rows = in_rows; a.in_cols = in_cols;
-    if (q) { a.prob = q->prob; a.min_prob = q->min_prob; a.ignore_label = q->ignore_label; }
-    return a;
-}
-
 void rs_launch(bool ragged, bool prob, bool win, int batch, const mbn_resample_launch_t &l, hipStream_t s, const ResampleArgs &a)
 {
-    const bool vec = ((uintptr_t)a.logits % 16) == 0 && (a.classes % 4) == 0;
-    hipLaunchKernelGGL(rs_kernels[ragged][prob][win][vec], dim3((unsigned)l.tiles, (unsigned)batch), dim3(256), (size_t)l.lds_bytes, s, a);
+    hipLaunchKernelGGL(rs_kernels[ragged][prob][win][rs_vec(a.logits, a.classes)], dim3((unsigned)l.tiles, (unsigned)batch), dim3(256),
+                       (size_t)l.lds_bytes, s, a);
 }
 
 // ---- ENSEMBLE (mbn_resample_ensemble_f32; include/mbn.h, "segment with test-time augmentation"): K views of the same images, each a window of the
@@ -429,7 +217,9 @@ struct EnsView {
     bool cross;              // some row of the wave has a bit set in this view
 };
 
-// adds one view's interpolants of the four classes at c to the lane's sums (first: they ARE the sums); rs_reduce's products and sums
+// adds one view's interpolants of the four classes at c to the lane's sums (first: they ARE the sums): rs_interp's reads, products and sums. Its own
+// text, and the ensemble its own lane state per view: through rs_interp the K = 7 VEC kernels spill a register that they do not spill here, and
+// on the shared lane helpers the K = 2 and K = 3 argmax kernels measured 0.8 % slower (profiles/LOG.md, "One tile header")
 template <bool CROSS>
 __device__ __forceinline__ void ens_add(const float *s_x, const EnsView &e, int c, bool first, float (&s)[RS_ROWS][4])
 {
@@ -635,9 +425,8 @@ __global__ __launch_bounds__(256) void resample_slide_f32(const SlideArgs a)
         float unused;
         rs_axis(px.o0 - t0, a.cols, a.s.tile_cols, &xbase[kx], &unused);
         rs_axis(oxc - t0, a.cols, a.s.tile_cols, &x0, &wx1[kx]);
-        // inside the tile's staged block by construction; the clamps keep every read inside the launch's LDS whatever the arguments
-        col[kx][0] = (kx * nv + min(max(x0 - xbase[kx], 0), a.fx - 1)) * ld;
-        col[kx][1] = (kx * nv + min(max(min(x0 + 1, last_x) - xbase[kx], 0), a.fx - 1)) * ld;
+        col[kx][0] = (kx * nv + rs_slot(x0, xbase[kx], a.fx)) * ld;
+        col[kx][1] = (kx * nv + rs_slot(min(x0 + 1, last_x), xbase[kx], a.fx)) * ld;
     }
     // per tile row: the footprint's first coarse row, the four rows' weights and up bits, the LDS offsets of the three coarse rows
     int ybase[SL_K], row[SL_K][3];
@@ -649,18 +438,14 @@ __global__ __launch_bounds__(256) void resample_slide_f32(const SlideArgs a)
         const int t0 = a.s.y[py.k0 + (ky < py.K ? ky : 0)];
         int ya = 0;
         float unused;
+        bool u[RS_ROWS];
         rs_axis(py.o0 - t0, a.rows, a.s.tile_rows, &ybase[ky], &unused);
+        cross[ky] = rs_rows<false>(oy0 - t0, y_end - 1 - t0, a.rows, a.s.tile_rows, RsWindow{ 0, 0, 0 }, &ya, wy1[ky], u);       // the plain rule reads no window
         up[ky] = 0;
 #pragma unroll
-        for (int r = 0; r < RS_ROWS; r++) {
-            int r0;
-            rs_axis(min(oy0 + r, y_end - 1) - t0, a.rows, a.s.tile_rows, &r0, &wy1[ky][r]);
-            if (r == 0) ya = r0;
-            up[ky] |= (unsigned)(r0 != ya) << r;      // r0 is ya or ya + 1: four rows span less than one coarse row
-        }
-        cross[ky] = __ballot(up[ky] != 0) != 0;
+        for (int r = 0; r < RS_ROWS; r++) up[ky] |= (unsigned)u[r] << r;
 #pragma unroll
-        for (int j = 0; j < 3; j++) row[ky][j] = (ky * px.K * nv + min(max(min(ya + j, last_y) - ybase[ky], 0), a.fy - 1) * a.fx) * ld;
+        for (int j = 0; j < 3; j++) row[ky][j] = (ky * px.K * nv + rs_slot(min(ya + j, last_y), ybase[ky], a.fy) * a.fx) * ld;
     }
     const float inv = a.inv[py.K * px.K];
     const float *tiles = a.logits + (img * (size_t)(a.s.ny * a.s.nx) + (size_t)(py.k0 * a.s.nx + px.k0)) * lmap;      // the piece's first tile
@@ -772,7 +557,9 @@ __device__ __forceinline__ void tk_insert(float (&val)[K], int (&lab)[K], float 
     if (v > val[0]) { val[0] = v; lab[0] = c; }
 }
 
-// rs_reduce with the K slots in the place of (best, label); the same products and sums in the same order, the softmax sum by rs_softmax_group
+// rs_reduce with the K slots in the place of (best, label); the same products and sums in the same order, the softmax sum by rs_softmax_group.
+// This family keeps its own lane state and loop: on the shared ones it measured 1 - 5 % slower at equal register counts (profiles/LOG.md, "One
+// tile header")
 template <int K, bool CROSS, bool PROB>
 __device__ __forceinline__ void tk_reduce(const float *(&p)[3][2], int cn4, int c0, float wx0, float wx1, const float (&wy0)[RS_ROWS],
                                           const float (&wy1)[RS_ROWS], const bool (&up)[RS_ROWS], float (&val)[RS_ROWS][K], int (&lab)[RS_ROWS][K],
@@ -919,13 +706,10 @@ const TopkKernel topk_kernels[2][2][2] = {
 void topk_launch(hipStream_t s, int batch, const mbn_resample_launch_t &l, TopkArgs &a, const float *logits, int rows, int cols, int classes, int k,
                  int64_t plane, int32_t *labels, float *score, const mbn_readout_prob *q)
 {
-    a.labels = labels; a.score = score; a.logits = logits;
-    a.rows = rows; a.cols = cols; a.classes = classes;
-    a.fy = l.fy; a.fx = l.fx; a.ch = l.ch;
+    rs_fill(a, labels, score, logits, rows, cols, classes, l, q);
     a.k = k; a.plane = plane;
-    if (q) { a.prob = q->prob; a.min_prob = q->min_prob; a.ignore_label = q->ignore_label; }
-    const bool vec = ((uintptr_t)logits % 16) == 0 && (classes % 4) == 0;
-    hipLaunchKernelGGL(topk_kernels[k > 4][q != nullptr][vec], dim3((unsigned)l.tiles, (unsigned)batch), dim3(256), (size_t)l.lds_bytes, s, a);
+    hipLaunchKernelGGL(topk_kernels[k > 4][q != nullptr][rs_vec(logits, classes)], dim3((unsigned)l.tiles, (unsigned)batch), dim3(256),
+                       (size_t)l.lds_bytes, s, a);
 }
 
 // ---- NLL (mbn_resample_nll_f32, _ragged_f32; include/mbn.h, "score the probabilities"): the negative log-likelihood and the Brier score of every
@@ -1003,34 +787,17 @@ __device__ __forceinline__ unsigned long long nl_wave_sum(unsigned long long v)
     return v;
 }
 
-// pass 2 over one staged chunk: rs_reduce's products and sums in the same order, then per temperature the two sums
+// pass 2 over one staged chunk: rs_reduce's interpolants, then per temperature the two sums
 template <int T, bool CROSS>
-__device__ __forceinline__ void nl_reduce(const float *(&p)[3][2], int cn4, int c0, float wx0, float wx1, const float (&wy0)[RS_ROWS],
-                                          const float (&wy1)[RS_ROWS], const bool (&up)[RS_ROWS], const float (&best)[RS_ROWS], const int (&t)[RS_ROWS],
+__device__ __forceinline__ void nl_reduce(const float *s_x, const RsLane &n, int cn4, int c0, const float (&best)[RS_ROWS], const int (&t)[RS_ROWS],
                                           const NllArgs &a, float (&vt)[RS_ROWS], float (&S)[RS_ROWS][T], float (&Q)[RS_ROWS][T])
 {
-    constexpr int NT = CROSS ? 3 : 2;
     for (int c = 0; c < cn4; c += 4) {
-        f4 v0[NT], v1[NT];
         float d[RS_ROWS][4];
-#pragma unroll
-        for (int j = 0; j < NT; j++) {
-            v0[j] = *reinterpret_cast<const f4 *>(p[j][0] + c);
-            v1[j] = *reinterpret_cast<const f4 *>(p[j][1] + c);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            float h[NT];
-#pragma unroll
-            for (int j = 0; j < NT; j++) h[j] = rs_lerp(v0[j][k], wx0, v1[j][k], wx1);      // horizontal first
-#pragma unroll
-            for (int r = 0; r < RS_ROWS; r++) {
-                const float ta = CROSS && up[r] ? h[1] : h[0], tb = CROSS && up[r] ? h[NT - 1] : h[1];
-                const float v = rs_lerp(ta, wy0[r], tb, wy1[r]);                            // then vertical
-                if (c0 + c + k == t[r]) vt[r] = v;
-                d[r][k] = nl_diff(v, best[r]);
-            }
-        }
+        rs_interp<CROSS>(s_x, n.off, c, n.wx0, n.wx1, n.wy0, n.wy1, n.up, [&](int r, int k, float v) __attribute__((always_inline)) {
+            if (c0 + c + k == t[r]) vt[r] = v;
+            d[r][k] = nl_diff(v, best[r]);
+        });
 #pragma unroll
         for (int j = 0; j < T; j++) {
             if (j >= a.temps) break;
@@ -1085,39 +852,12 @@ __global__ __launch_bounds__(256) void resample_nll_f32(const NllArgs a)
     const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
     if (ty >= (H + RS_TILE - 1) / RS_TILE) return;                                              // ragged: past this image's tiles
     const float *__restrict__ src = a.logits + (size_t)blockIdx.y * ((size_t)a.rows * a.cols * a.classes);
-
-    // ---- resample_tile's lane state under the window rule
     const int ld = a.ch + 4, nv = a.fy * a.fx;
-    int ybase, xbase;
-    float unused;
-    rs_coord<true>(RS_TILE * ty, a.rows, H, wy, &ybase, &unused);
-    rs_coord<true>(RS_TILE * tx, a.cols, W, wx, &xbase, &unused);
-    const int ox = RS_TILE * tx + (tid & 31), oy0 = RS_TILE * ty + RS_ROWS * (tid >> 5);
-    const bool active = ox < W && oy0 < H;
-    int x0, ya = 0;
-    float wx1, wy1[RS_ROWS], wy0[RS_ROWS];
-    bool up[RS_ROWS];
-    rs_coord<true>(min(ox, W - 1), a.cols, W, wx, &x0, &wx1);
-    const float wx0 = 1.0f - wx1;
-#pragma unroll
-    for (int r = 0; r < RS_ROWS; r++) {
-        int r0;
-        rs_coord<true>(min(oy0 + r, H - 1), a.rows, H, wy, &r0, &wy1[r]);
-        wy0[r] = 1.0f - wy1[r];
-        if (r == 0) ya = r0;
-        up[r] = r0 != ya;                     // r0 is ya or ya + 1: four rows span less than one coarse row
-    }
-    const bool cross = __ballot(up[1] || up[2] || up[3]) != 0;
-    // inside the staged block by construction; the clamps keep every read inside the launch's LDS whatever the arguments
     const int last_y = a.rows - 1, last_x = a.cols - 1;
-    const int sx0 = min(max(x0 - xbase, 0), a.fx - 1), sx1 = min(max(min(x0 + 1, last_x) - xbase, 0), a.fx - 1);
-    const float *p[3][2];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        const int sy = min(max(min(ya + j, last_y) - ybase, 0), a.fy - 1);
-        p[j][0] = s_rs + (sy * a.fx + sx0) * ld;
-        p[j][1] = s_rs + (sy * a.fx + sx1) * ld;
-    }
+    RsLane n;
+    rs_lane<true>(n, a.rows, a.cols, a.fy, a.fx, ld, H, W, ty, tx, wy, wx);
+    const int ox = n.ox, oy0 = n.oy0;
+    const bool active = n.active;
 
     // ---- the truth of the lane's pixels: a class, `classes` for a void pixel, -1 where the lane has no pixel (past the image)
     const unsigned out = (unsigned)(oy0 * W + ox);        // 32-bit inside an image: its map is below 2^31 bytes
@@ -1139,11 +879,11 @@ __global__ __launch_bounds__(256) void resample_nll_f32(const NllArgs a)
     for (int r = 0; r < RS_ROWS; r++) { best[r] = ref[r] = -__builtin_inff(); sum[r] = 0.0f; label[r] = 0; }
     for (int c0 = 0; c0 < a.classes; c0 += a.ch) {
         const int cn = min(a.ch, a.classes - c0), cn4 = (cn + 3) & ~3;
-        rs_stage<VEC>(s_rs, src, ybase, xbase, a.fx, nv, ld, a.cols, a.classes, last_y, last_x, c0, cn, cn4, tid);
+        rs_stage<VEC>(s_rs, src, n.ybase, n.xbase, a.fx, nv, ld, a.cols, a.classes, last_y, last_x, c0, cn, cn4, tid);
         __syncthreads();
         if (active) {
-            if (cross) rs_reduce<true, false>(p, cn4, c0, wx0, wx1, wy0, wy1, up, best, label, ref, sum);
-            else rs_reduce<false, false>(p, cn4, c0, wx0, wx1, wy0, wy1, up, best, label, ref, sum);
+            if (n.cross) rs_reduce<true, false>(s_rs, n, cn4, c0, best, label, ref, sum);
+            else rs_reduce<false, false>(s_rs, n, cn4, c0, best, label, ref, sum);
         }
         if (a.classes > a.ch) __syncthreads();            // one chunk: it stays staged for pass 2
     }
@@ -1159,12 +899,12 @@ __global__ __launch_bounds__(256) void resample_nll_f32(const NllArgs a)
     for (int c0 = 0; c0 < a.classes; c0 += a.ch) {
         const int cn = min(a.ch, a.classes - c0), cn4 = (cn + 3) & ~3;
         if (a.classes > a.ch) {
-            rs_stage<VEC>(s_rs, src, ybase, xbase, a.fx, nv, ld, a.cols, a.classes, last_y, last_x, c0, cn, cn4, tid);
+            rs_stage<VEC>(s_rs, src, n.ybase, n.xbase, a.fx, nv, ld, a.cols, a.classes, last_y, last_x, c0, cn, cn4, tid);
             __syncthreads();
         }
         if (active) {
-            if (cross) nl_reduce<T, true>(p, cn4, c0, wx0, wx1, wy0, wy1, up, best, t, a, vt, S, Q);
-            else nl_reduce<T, false>(p, cn4, c0, wx0, wx1, wy0, wy1, up, best, t, a, vt, S, Q);
+            if (n.cross) nl_reduce<T, true>(s_rs, n, cn4, c0, best, t, a, vt, S, Q);
+            else nl_reduce<T, false>(s_rs, n, cn4, c0, best, t, a, vt, S, Q);
         }
         if (a.classes > a.ch) __syncthreads();
     }
@@ -1258,8 +998,8 @@ void nll_launch(hipStream_t s, int batch, const mbn_resample_launch_t &l, NllArg
         a.beta[j] = inv_temps[j];
         a.k2[j] = (float)((double)inv_temps[j] * 1.44269504088896341);                      // one rounding
     }
-    const bool vec = ((uintptr_t)logits % 16) == 0 && (classes % 4) == 0;
-    hipLaunchKernelGGL(nll_kernels[temps > 4 ? 2 : temps > 1][vec], dim3((unsigned)l.tiles, (unsigned)batch), dim3(256), (size_t)l.lds_bytes, s, a);
+    hipLaunchKernelGGL(nll_kernels[temps > 4 ? 2 : temps > 1][rs_vec(logits, classes)], dim3((unsigned)l.tiles, (unsigned)batch), dim3(256),
+                       (size_t)l.lds_bytes, s, a);
 }
 
 }   // namespace
@@ -1275,10 +1015,7 @@ int mbn_launch_f32_resample_nll(mbn_context *, hipStream_t s, void *table, float
     mbn_resample_launch_t l = { 0, 0, 0, 0, 0, 0 };
     mbn_resample_window_plan(rows, cols, in_rows, in_cols, rect, out_rows, out_cols, &l);
     NllArgs a = {};
-    a.out_rows = out_rows; a.out_cols = out_cols;
-    a.tiles_x = (out_cols + RS_TILE - 1) / RS_TILE;
-    a.in_rows = in_rows; a.in_cols = in_cols;
-    a.wx = rect[0]; a.wy = rect[1]; a.wiw = rect[2]; a.wih = rect[3];
+    rs_fill_uniform(a, out_rows, out_cols, in_rows, in_cols, rect);
     nll_launch(s, batch, l, a, table, nll, brier, (int64_t)batch * out_rows * out_cols, logits, truth, truth_bytes, rows, cols, classes, inv_temps,
                temps);
     return MBN_OK;
@@ -1310,10 +1047,7 @@ int mbn_launch_f32_resample_topk(mbn_context *, hipStream_t s, int32_t *labels, 
     mbn_resample_launch_t l = { 0, 0, 0, 0, 0, 0 };
     mbn_resample_window_plan(rows, cols, in_rows, in_cols, rect, out_rows, out_cols, &l);
     TopkArgs a = {};
-    a.out_rows = out_rows; a.out_cols = out_cols;
-    a.tiles_x = (out_cols + RS_TILE - 1) / RS_TILE;
-    a.in_rows = in_rows; a.in_cols = in_cols;
-    a.wx = rect[0]; a.wy = rect[1]; a.wiw = rect[2]; a.wih = rect[3];
+    rs_fill_uniform(a, out_rows, out_cols, in_rows, in_cols, rect);
     topk_launch(s, batch, l, a, logits, rows, cols, classes, k, (int64_t)batch * out_rows * out_cols, labels, score, q);
     return MBN_OK;
 }
@@ -1343,18 +1077,15 @@ int mbn_launch_f32_resample_slide(mbn_context *, hipStream_t s, int32_t *labels,
     const int rc = mbn_resample_slide_plan(rows, cols, plan, out_rows, out_cols, &l);
     if (rc != MBN_OK) return rc;
     SlideArgs a = {};
-    a.labels = labels; a.score = score; a.logits = logits;
-    a.rows = rows; a.cols = cols; a.classes = classes;
+    rs_fill(a, labels, score, logits, rows, cols, classes, l, q);
     a.out_rows = out_rows; a.out_cols = out_cols;
-    a.fy = l.fy; a.fx = l.fx; a.ch = l.ch;
-    if (q) { a.prob = q->prob; a.min_prob = q->min_prob; a.ignore_label = q->ignore_label; }
     for (int k = 1; k < 10; k++) a.inv[k] = 1.0f / (float)k;
     a.s = *plan;
     int32_t kmax;
     a.cells_y = mbn_slide_cells(plan->y, plan->ny, plan->tile_rows, a.edge_y, a.pieces_y, &kmax);
     a.cells_x = mbn_slide_cells(plan->x, plan->nx, plan->tile_cols, a.edge_x, a.pieces_x, &kmax);
-    const bool vec = ((uintptr_t)logits % 16) == 0 && (classes % 4) == 0;
-    hipLaunchKernelGGL(slide_kernels[q != nullptr][vec], dim3((unsigned)l.tiles, (unsigned)batch), dim3(256), (size_t)l.lds_bytes, s, a);
+    hipLaunchKernelGGL(slide_kernels[q != nullptr][rs_vec(logits, classes)], dim3((unsigned)l.tiles, (unsigned)batch), dim3(256), (size_t)l.lds_bytes,
+                       s, a);
     return MBN_OK;
 }
 
@@ -1367,17 +1098,15 @@ int mbn_launch_f32_resample_ensemble(mbn_context *, hipStream_t s, int32_t *labe
     const int rc = mbn_resample_ensemble_plan(rows, cols, in_rows, in_cols, views, n_views, out_rows, out_cols, &l);
     if (rc != MBN_OK) return rc;
     EnsembleArgs a = {};
-    a.labels = labels; a.score = score; a.logits = logits;
-    a.rows = rows; a.cols = cols; a.classes = classes; a.batch = batch;
+    rs_fill(a, labels, score, logits, rows, cols, classes, l, q);
+    a.batch = batch;
     a.out_rows = out_rows; a.out_cols = out_cols;
     a.tiles_x = (out_cols + RS_TILE - 1) / RS_TILE;
-    a.fy = l.fy; a.fx = l.fx; a.ch = l.ch;
     a.in_rows = in_rows; a.in_cols = in_cols;
     a.inv_k = 1.0f / (float)n_views;
-    if (q) { a.prob = q->prob; a.min_prob = q->min_prob; a.ignore_label = q->ignore_label; }
     for (int k = 0; k < n_views; k++) a.views[k] = views[k];
-    const bool vec = ((uintptr_t)logits % 16) == 0 && (classes % 4) == 0;
-    hipLaunchKernelGGL(ens_kernels[n_views - 1][q != nullptr][vec], dim3((unsigned)l.tiles, (unsigned)batch), dim3(256), (size_t)l.lds_bytes, s, a);
+    hipLaunchKernelGGL(ens_kernels[n_views - 1][q != nullptr][rs_vec(logits, classes)], dim3((unsigned)l.tiles, (unsigned)batch), dim3(256),
+                       (size_t)l.lds_bytes, s, a);
     return MBN_OK;
 }
 
@@ -1390,10 +1119,9 @@ int mbn_launch_f32_resample_argmax(mbn_context *, hipStream_t s, int32_t *labels
     mbn_resample_launch_t l = { 0, 0, 0, 0, 0, 0 };
     if (rect) mbn_resample_window_plan(rows, cols, in_rows, in_cols, rect, out_rows, out_cols, &l);
     else mbn_resample_plan(rows, cols, out_rows, out_cols, &l);
-    ResampleArgs a = rs_args(labels, score, logits, rows, cols, classes, l, in_rows, in_cols, q);
-    a.out_rows = out_rows; a.out_cols = out_cols;
-    a.tiles_x = (out_cols + RS_TILE - 1) / RS_TILE;
-    if (rect) { a.wx = rect[0]; a.wy = rect[1]; a.wiw = rect[2]; a.wih = rect[3]; }
+    ResampleArgs a = {};
+    rs_fill(a, labels, score, logits, rows, cols, classes, l, q);
+    rs_fill_uniform(a, out_rows, out_cols, in_rows, in_cols, rect);
     rs_launch(false, q != nullptr, rect != nullptr, batch, l, s, a);
     return MBN_OK;
 }
@@ -1461,8 +1189,10 @@ int mbn_ragged_readout_plan(mbn_ragged_readout *r, hipStream_t s, int rows, int 
 int mbn_launch_f32_resample_argmax_ragged(mbn_ragged_readout *r, hipStream_t s, int32_t *labels, float *score, const float *logits,
                                           const mbn_readout_prob *q)
 {
-    ResampleArgs a = rs_args(labels, score, logits, r->rows, r->cols, r->classes, r->launch, r->in_rows, r->in_cols, q);
+    ResampleArgs a = {};
+    rs_fill(a, labels, score, logits, r->rows, r->cols, r->classes, r->launch, q);
     a.tiles_x = 1;                                              // unused: a workgroup takes its image's own
+    a.in_rows = r->in_rows; a.in_cols = r->in_cols;
     a.head = (const mbn_label_set_head *)r->dev;
     a.items = (const mbn_label_item *)(a.head + 1);
     a.witems = (const mbn_label_window_item *)(a.head + 1);     // the last set decides which of the two the block holds
