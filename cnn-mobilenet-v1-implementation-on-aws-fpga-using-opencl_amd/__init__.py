@@ -296,6 +296,8 @@ def _declare_host(lib):
                                  C.POINTER(C.c_int)]
     lib.mbn_guided_lut.argtypes = [C.c_float, C.POINTER(C.c_float)]
     lib.mbn_guide_reduce_envelope.argtypes = [C.c_int] * 4                                                       # mbn_envelope.h
+    lib.mbn_class_groups_layout.argtypes = [C.c_int, C.c_int] + [C.POINTER(C.c_int32)] * 3 + [C.POINTER(C.c_int)]
+    lib.mbn_resample_groups_envelope.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float]
     lib.mbn_components_envelope.argtypes = [C.c_int] * 7
     lib.mbn_components_tile.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.mbn_components_scratch_bytes.argtypes = [C.c_int, C.c_int64]
@@ -466,6 +468,10 @@ def load():
         lib.mbn_resample_guided_f32.argtypes = [vp] * 8 + [ci] * 6 + [C.POINTER(C.c_int32), ci, ci, C.c_float, ci, vp]
         lib.mbn_guide_reduce_u8.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]
         lib.mbn_net_segment_guided_fit.argtypes = [vp, vp, ci, ci, ci, ci, C.c_float, vp, vp, vp, C.c_float, ci]
+        lib.mbn_class_groups_create.argtypes = [vp, ci, ci, C.POINTER(C.c_int32), C.POINTER(vp)]
+        lib.mbn_class_groups_destroy.argtypes = [vp]
+        lib.mbn_resample_groups_f32.argtypes = [vp] * 6 + [ci] * 6 + [C.POINTER(C.c_int32), ci, ci, C.c_float, ci, vp]
+        lib.mbn_net_segment_groups_fit.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, C.c_float, ci]
         lib.mbn_resample_ensemble_f32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(View), ci, ci, ci, C.c_float, ci, vp]
         lib.mbn_resample_slide_f32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, C.POINTER(Slide), ci, ci, C.c_float, ci, vp]
         lib.mbn_net_resize_tiles.argtypes = [vp, vp, ci, ci, ci, C.POINTER(Slide), C.POINTER(vp)]
@@ -820,6 +826,24 @@ def guided_lut(sigma, lib=None) -> np.ndarray:
 def guide_reduce_envelope(batch, in_rows, in_cols, stride, lib=None) -> int:
     """mbn_guide_reduce_envelope: the status Context.guide_reduce gives the sizes and the stride."""
     return (lib or host_lib()).mbn_guide_reduce_envelope(batch, in_rows, in_cols, stride)
+
+
+def class_groups_layout(group_of, groups, lib=None):
+    """mbn_class_groups_layout: (status, slot_class, quad_group) of the grouping group_of [classes] (-1: the class is left out): the order the
+    group read-out walks, every non-empty group padded to four slots with -1; quad_group[q] = the group that ends with quad q, else -1."""
+    g = np.ascontiguousarray(group_of, np.int32)
+    room = max(g.size + 3 * max(int(groups), 0), 4)
+    slot_class, quad_group, slots = np.full(room, -2, np.int32), np.full(room // 4 + 1, -2, np.int32), C.c_int(0)
+    i32 = C.POINTER(C.c_int32)
+    rc = (lib or host_lib()).mbn_class_groups_layout(g.size, groups, g.ctypes.data_as(i32), slot_class.ctypes.data_as(i32),
+                                                     quad_group.ctypes.data_as(i32), C.byref(slots))
+    return rc, slot_class[:slots.value], quad_group[:slots.value // 4]
+
+
+def resample_groups_envelope(batch, rows, cols, classes, group_classes, in_rows, in_cols, rect, out_rows, out_cols, min_prob=0.0, lib=None) -> int:
+    """mbn_resample_groups_envelope: the status Context.resample_groups gives the shape, the handle's class count and min_prob."""
+    return (lib or host_lib()).mbn_resample_groups_envelope(batch, rows, cols, classes, group_classes, in_rows, in_cols,
+                                                            None if rect is None else _rect(rect), out_rows, out_cols, min_prob)
 
 
 def softmax_readout_check(have_prob, min_prob, lib=None) -> int:
@@ -1343,6 +1367,15 @@ class Context:
                                               None if rect is None else _rect(rect), out_rows, out_cols, min_prob, ignore_label, None),
              self.last_error())
 
+    def resample_groups(self, groups, labels, prob, score, logits, batch, rows, cols, classes, out_rows, out_cols, in_rows=0, in_cols=0, rect=None,
+                        min_prob=0.0, ignore_label=0):
+        """mbn_resample_groups_f32: the read-out to out_rows x out_cols whose labels are the groups of `groups` (a ClassGroups): per pixel the group
+        whose members' softmax probabilities sum highest, prob = that sum, score = its log-sum-exp. rect = (x, y, iw, ih) of the in_rows x in_cols
+        input, or None for the whole map. `prob` and `score` may be None."""
+        _chk(self.lib.mbn_resample_groups_f32(self.h, groups.h, labels, prob, score, logits, batch, rows, cols, classes, in_rows, in_cols,
+                                              None if rect is None else _rect(rect), out_rows, out_cols, min_prob, ignore_label, None),
+             self.last_error())
+
     def resample_ensemble(self, labels, prob, score, logits, batch, rows, cols, classes, in_rows, in_cols, view_list, out_rows, out_cols,
                           min_prob=0.0, ignore_label=0, n_views=None):
         """mbn_resample_ensemble_f32: ONE read-out of the views in view_list (View objects or (x, y, iw, ih, mirror)) over view-major logits
@@ -1591,6 +1624,24 @@ class RaggedReadout:
             self.h = None
 
 
+class ClassGroups:
+    """mbn_class_groups_create: a grouping of the plan's classes on the device, group_of [classes] with values in -1 .. groups - 1 (-1: the class
+    is left out of the softmax). Context.resample_groups and Net.segment_groups_fit take it; close() or the context's shutdown frees it."""
+
+    def __init__(self, ctx: Context, group_of, groups):
+        self.ctx = ctx
+        g = np.ascontiguousarray(group_of, np.int32)
+        self.classes, self.groups = g.size, int(groups)
+        h = C.c_void_p()
+        _chk(ctx.lib.mbn_class_groups_create(ctx.h, g.size, groups, g.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(h)), ctx.last_error())
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.mbn_class_groups_destroy(self.h)
+            self.h = None
+
+
 class Resizer:
     """mbn_resizer_create_filter / mbn_resize_u8: uint8 HWC images [batch][in_rows][in_cols][3] -> [batch][out_rows][out_cols][3], Pillow's 8-bit
     resize of `box` = (left, upper, right, lower) (None = the whole image) under `filter` (FILTER_*, bilinear by default), byte for byte. One
@@ -1811,6 +1862,12 @@ class Net:
         """mbn_net_segment_guided_fit: segment_fit (FIT_STRETCH or FIT_PAD) with the guided read-out (Context.resample_guided): the source image is
         guide_hi, the block means of the resized canvas guide_lo, the table guided_lut(sigma). prob None with min_prob 0: the argmax form."""
         _chk(self.ctx.lib.mbn_net_segment_guided_fit(self.h, src_ptr, batch, in_rows, in_cols, fit, sigma, labels_ptr, prob_ptr, score_ptr, min_prob,
+                                                     ignore_label), self.ctx.last_error())
+
+    def segment_groups_fit(self, groups, src_ptr, batch, in_rows, in_cols, fit, labels_ptr, prob_ptr=None, score_ptr=None, min_prob=0.0, ignore_label=0):
+        """mbn_net_segment_groups_fit: segment_prob_fit (FIT_STRETCH or FIT_PAD) with the group read-out of `groups` (a ClassGroups made for the
+        plan's classes). The scoring calls that follow work on group labels with `groups.groups` classes; segment_nll refuses."""
+        _chk(self.ctx.lib.mbn_net_segment_groups_fit(self.h, groups.h, src_ptr, batch, in_rows, in_cols, fit, labels_ptr, prob_ptr, score_ptr, min_prob,
                                                      ignore_label), self.ctx.last_error())
 
     def segment_images_fit(self, src_ptr, offsets, rows, cols, fit, labels_ptr, dst_offsets, score_ptr=None):

@@ -220,6 +220,7 @@ int mbn_shutdown(mbn_context *ctx)
     for (mbn_resizer *r : ctx->resizers) mbn_resizer_release(r);
     for (mbn_ragged_resizer *r : ctx->ragged_resizers) mbn_ragged_resizer_release(r);
     for (mbn_ragged_readout *r : ctx->ragged_readouts) mbn_ragged_readout_release(r);
+    for (mbn_class_groups *g : ctx->class_groups) mbn_class_groups_release(g);
     ctx->allocs.clear();
     for (hipEvent_t e : ctx->pool) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->marks) (void)hipEventDestroy(e);
@@ -994,6 +995,59 @@ int mbn_guide_reduce_u8(mbn_context *ctx, void *guide_lo_u8, const void *canvas_
               { guide_lo_u8, 3.0 * batch * (in_rows / S) * (in_cols / S), "guide_reduce guide_lo" });
     Scope sc(ctx, s);
     return sc.finish(mbn_launch_u8_guide_reduce(ctx, s, (uint8_t *)guide_lo_u8, (const uint8_t *)canvas_u8, batch, in_rows, in_cols, S));
+}
+
+int mbn_class_groups_create(mbn_context *ctx, int classes, int groups, const int32_t *group_of, mbn_class_groups **g)
+{
+    if (!ctx || !g) return MBN_EINVAL;
+    *g = nullptr;
+    if (!group_of) return MBN_EINVAL;
+    const int rc = mbn_class_groups_build(ctx, classes, groups, group_of, g);      // the layout's own statuses first
+    if (rc != MBN_OK) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->class_groups.push_back(*g);
+    return MBN_OK;
+}
+
+int mbn_class_groups_destroy(mbn_class_groups *g)
+{
+    if (!g) return MBN_OK;
+    mbn_context *ctx = g->ctx;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        for (auto it = ctx->class_groups.begin(); it != ctx->class_groups.end(); ++it)
+            if (*it == g) { ctx->class_groups.erase(it); break; }
+    }
+    (void)hipSetDevice(ctx->device);
+    MBN_HIP_TRY(ctx, hipDeviceSynchronize());                    // its last launch, whatever the stream
+    mbn_class_groups_release(g);
+    return MBN_OK;
+}
+
+int mbn_class_groups_info(const mbn_class_groups *g, const mbn_context *ctx, int *classes, int *groups)
+{
+    if (!g || g->ctx != ctx) return MBN_EINVAL;
+    if (classes) *classes = g->classes;
+    if (groups) *groups = g->groups;
+    return MBN_OK;
+}
+
+// The group read-out: the checks of readout_call in its order (pointers, min_prob, the shape, the spans); prob may be NULL at any min_prob
+int mbn_resample_groups_f32(mbn_context *ctx, const mbn_class_groups *g, void *labels_i32, void *prob_f32, void *score_f32, const void *logits,
+                            int batch, int rows, int cols, int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols,
+                            float min_prob, int ignore_label, void *stream)
+{
+    if (!ctx || !g || g->ctx != ctx || !labels_i32 || !logits) return MBN_EINVAL;
+    if (((uintptr_t)labels_i32 | (uintptr_t)score_f32 | (uintptr_t)logits | (uintptr_t)prob_f32) % 4) return MBN_EINVAL;
+    const int shape = mbn_resample_groups_envelope(batch, rows, cols, classes, g->classes, in_rows, in_cols, rect, out_rows, out_cols, min_prob);
+    if (shape != MBN_OK) return shape;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    const double out = 4.0 * batch * out_rows * out_cols;
+    MBN_SPANS(ctx, { logits, 4.0 * batch * rows * cols * classes, "group read-out logits" }, { labels_i32, out, "group read-out labels" },
+              { score_f32, out, "group read-out score" }, { prob_f32, out, "group read-out prob" });
+    Scope sc(ctx, s);
+    return sc.finish(mbn_launch_f32_resample_groups(ctx, s, g, (int32_t *)labels_i32, (float *)prob_f32, (float *)score_f32, (const float *)logits,
+                                                    batch, rows, cols, in_rows, in_cols, rect, out_rows, out_cols, min_prob, ignore_label));
 }
 
 int mbn_ragged_readout_create(mbn_context *ctx, int max_batch, mbn_ragged_readout **r)

@@ -67,6 +67,14 @@ struct mbn_ragged_readout {
     hipEvent_t done = nullptr;                   // behind the last upload or launch: the next set waits for it
 };
 
+// mbn_class_groups_create's handle (mbn_f32_groups.hip): the layout of one grouping on the device, uploaded once
+struct mbn_class_groups {
+    mbn_context *ctx = nullptr;
+    int classes = 0, groups = 0;
+    int slots = 0, first_group = 0;              // of mbn_class_groups_layout; the lowest non-empty group
+    void *dev = nullptr;                         // int32 slot_class [slots], then quad_group [slots / 4]
+};
+
 // A scratch handle: device memory for the kernels of one family of calls, allocated once for up to max_batch images and `capacity` of the
 // family's unit. mbn_scratch_create / _destroy (mbn_abi.hip) serve every family; the public types stay distinct
 struct mbn_scratch {
@@ -113,6 +121,7 @@ struct mbn_context {
     std::vector<mbn_resizer *> resizers;         // live mbn_resizer_create handles (mbn_shutdown frees the stragglers)
     std::vector<mbn_ragged_resizer *> ragged_resizers;   // live mbn_ragged_resizer_create handles, likewise
     std::vector<mbn_ragged_readout *> ragged_readouts;   // live mbn_ragged_readout_create handles, likewise
+    std::vector<mbn_class_groups *> class_groups;        // live mbn_class_groups_create handles, likewise
     mbn_scratch_list scratches;                  // live mbn_components_create / mbn_panoptic_create handles (freed with the context)
     std::mutex mu;
     std::map<uintptr_t, size_t> allocs;          // buffers handed out by mbn_alloc: base address -> bytes (ordered: mbn_span_check
@@ -385,6 +394,13 @@ int mbn_launch_f32_resample_guided(mbn_context *ctx, hipStream_t s, int32_t *lab
                                    const uint8_t *guide_hi, const float *lut, int batch, int rows, int cols, int classes, int in_rows, int in_cols,
                                    const int32_t *rect, int out_rows, int out_cols, const mbn_readout_prob *q);
 int mbn_launch_u8_guide_reduce(mbn_context *ctx, hipStream_t s, uint8_t *guide_lo, const uint8_t *canvas, int batch, int in_rows, int in_cols, int S);
+// the group read-out (mbn_f32_groups.hip; mbn_resample_groups_f32): the handle's tables, and the launch inside mbn_resample_groups_envelope with
+// the pointers checked. rect as above; prob and score may be null
+int mbn_class_groups_build(mbn_context *ctx, int classes, int groups, const int32_t *group_of, mbn_class_groups **g);
+void mbn_class_groups_release(mbn_class_groups *g);
+int mbn_launch_f32_resample_groups(mbn_context *ctx, hipStream_t s, const mbn_class_groups *g, int32_t *labels, float *prob, float *score,
+                                   const float *logits, int batch, int rows, int cols, int in_rows, int in_cols, const int32_t *rect, int out_rows,
+                                   int out_cols, float min_prob, int ignore_label);
 // rank score (mbn_i32_topk_rank.hip): ranks [classes + 1][k + 1] uint64 += per truth row the rank at which the truth is among the k label planes
 // (plane j at j * plane_stride elements). The arguments are inside mbn_topk_rank_envelope and the pointers checked
 int mbn_launch_i32_topk_rank(mbn_context *ctx, hipStream_t s, void *ranks, const void *labels, int k, int64_t plane_stride, const void *truth,

@@ -145,6 +145,16 @@ void mbn_resample_plan(int rows, int cols, int out_rows, int out_cols, mbn_resam
     mbn_resample_window_plan(rows, cols, rows, cols, full, out_rows, out_cols, l);
 }
 
+int mbn_resample_groups_envelope(int batch, int rows, int cols, int classes, int group_classes, int in_rows, int in_cols, const int32_t rect[4],
+                                 int out_rows, int out_cols, float min_prob)
+{
+    if (!(min_prob >= 0.0f && min_prob <= 1.0f)) return MBN_EINVAL;                             /* a NaN fails both compares */
+    const int shape = rect ? mbn_resample_window_envelope(batch, rows, cols, classes, in_rows, in_cols, rect, out_rows, out_cols)
+                           : mbn_resample_argmax_envelope(batch, rows, cols, classes, out_rows, out_cols);
+    if (shape == MBN_EINVAL || classes != group_classes) return MBN_EINVAL;
+    return shape;
+}
+
 int mbn_resample_ensemble_envelope(int batch, int rows, int cols, int classes, int in_rows, int in_cols, const mbn_view *views, int n_views,
                                    int out_rows, int out_cols)
 {

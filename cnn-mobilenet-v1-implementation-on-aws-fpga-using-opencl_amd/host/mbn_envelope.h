@@ -103,6 +103,11 @@ void mbn_resample_window_plan(int rows, int cols, int in_rows, int in_cols, cons
  * mbn_guide_reduce_u8: MBN_EINVAL for a non-positive size, S < 1 or S not a divisor of both sides; else MBN_EUNSUPPORTED for a batch above 65535, a
  * side above MBN_RESAMPLE_MAX_OUT or S above 2048 (a block's sum of 255 S^2 is kept in 32 bits) */
 int mbn_guide_reduce_envelope(int batch, int in_rows, int in_cols, int S);
+/* mbn_resample_groups_f32: MBN_EINVAL for min_prob outside [0, 1] or NaN, for what the window envelope (rect = NULL: the plain one) calls
+ * MBN_EINVAL, and for classes other than group_classes, the class count the handle was made for; else that envelope's status. The launch is
+ * mbn_resample_window_plan's (mbn_resample_plan's), its chunk counted in slots of the layout instead of classes */
+int mbn_resample_groups_envelope(int batch, int rows, int cols, int classes, int group_classes, int in_rows, int in_cols, const int32_t rect[4],
+                                 int out_rows, int out_cols, float min_prob);
 /* mbn_resample_ragged_check for the items of mbn_ragged_readout_set_window: the same statuses, overlap sort and scratch, every item under
  * mbn_resample_window_envelope with its own rectangle; *l is written only when the batch is accepted */
 int mbn_resample_ragged_window_check(int rows, int cols, int classes, int in_rows, int in_cols, const mbn_label_window_item *items, int batch,

@@ -262,6 +262,7 @@ typedef struct seg_call {
     int64_t plane_stride;                               /* for P_IMAGES this many elements apart */
     int guided;                                         /* P_FIT: the guided read-out (mbn_resample_guided_f32) with the table of sigma, */
     float sigma;                                        /* the source as guide_hi and the block means of the staged canvas as guide_lo */
+    const mbn_class_groups *groups;                     /* P_FIT: the group read-out (mbn_resample_groups_f32) of this handle; q is always given */
 } seg_call;
 
 /* The net's read-out set from the items of an image call: each image's map at its own size, through its letterbox window under MBN_FIT_PAD. The set
@@ -342,7 +343,9 @@ static int segment_run(mbn_net *net, const seg_call *c)
     const int new_lut = c->guided && !(net->seg.guided_lut && net->seg.guided_sigma == c->sigma);
     if (new_lut && mbn_guided_lut(c->sigma, lut) != MBN_OK) return MBN_EINVAL;
     const readout_prob *q = c->q;
-    if (q && ((uintptr_t)q->prob % 4 || mbn_softmax_readout_check(q->prob != NULL, q->min_prob) != MBN_OK)) return MBN_EINVAL;
+    int group_classes = 0, n_groups = 0;                               /* a group call: its prob map may be missing at any threshold */
+    if (c->groups && mbn_class_groups_info(c->groups, net->ctx, &group_classes, &n_groups) != MBN_OK) return MBN_EINVAL;
+    if (q && ((uintptr_t)q->prob % 4 || mbn_softmax_readout_check(q->prob != NULL || c->groups, q->min_prob) != MBN_OK)) return MBN_EINVAL;
     const int in_rows = net->plan.layer[0].in_rows, in_cols = net->plan.layer[0].in_cols, batch = c->batch;
     const int rows = c->path == P_INPUT ? in_rows : c->rows, cols = c->path == P_INPUT ? in_cols : c->cols;
     const int aligned = (((uintptr_t)c->labels | (uintptr_t)c->score | (uintptr_t)(q ? q->prob : NULL)) % 4) == 0;
@@ -391,6 +394,7 @@ static int segment_run(mbn_net *net, const seg_call *c)
             rc = MBN_EUNSUPPORTED;                                     /* every size is positive here: what the plain shape can miss is a limit */
         /* the coarse guide is the block mean over the plan's output stride: an integer, the same on both axes */
         if (rc == MBN_OK && c->guided && (in_rows % h || in_cols % w || in_rows / h != in_cols / w)) rc = MBN_EUNSUPPORTED;
+        if (rc == MBN_OK && c->groups && group_classes != classes) rc = MBN_EINVAL;
         if (rc == MBN_OK && c->topk) rc = mbn_resample_topk_envelope(batch, h, w, classes, in_rows, in_cols, rect, rows, cols, c->topk);
         break;
     case P_IMAGES:
@@ -443,7 +447,10 @@ static int segment_run(mbn_net *net, const seg_call *c)
         rc = mbn_resample_slide_f32(net->ctx, c->labels, prob, c->score, logits, batch, h, w, classes, &slide, rows, cols, min_prob, ignore, NULL);
         break;
     default:
-        if (c->guided)
+        if (c->groups)
+            rc = mbn_resample_groups_f32(net->ctx, c->groups, c->labels, prob, c->score, logits, batch, h, w, classes, in_rows, in_cols, rect, rows, cols,
+                                         min_prob, ignore, NULL);
+        else if (c->guided)
             rc = mbn_resample_guided_f32(net->ctx, c->labels, prob, c->score, logits, net->seg.guide_lo, c->src, net->seg.guided_lut, batch, h, w, classes,
                                          in_rows, in_cols, rect, rows, cols, min_prob, ignore, NULL);
         else if (c->topk)
@@ -460,10 +467,11 @@ static int segment_run(mbn_net *net, const seg_call *c)
     if (rc != MBN_OK) return rc;
     /* (5) the record */
     if (c->path != P_IMAGES) pixels = (int64_t)batch * rows * cols;    /* (an image call has rows = cols = 0, and the pixels of its items) */
-    net->seg.last = (struct mbn_seg_maps){ c->path == P_IMAGES ? MBN_SEG_RAGGED : MBN_SEG_UNIFORM, batch, rows, cols, classes, pixels, c->topk,
+    /* (a group call's labels are groups: its consumers size their tables by them, and no read-out of the logits per class gives its maps) */
+    net->seg.last = (struct mbn_seg_maps){ c->path == P_IMAGES ? MBN_SEG_RAGGED : MBN_SEG_UNIFORM, batch, rows, cols, c->groups ? n_groups : classes, pixels, c->topk,
                                            c->path == P_IMAGES ? c->plane_stride : pixels,
                                            c->path == P_IMAGES ? MBN_SEG_GEOM_SET : c->path == P_VIEWS || c->path == P_SLIDE ? MBN_SEG_GEOM_MANY
-                                           : c->guided ? MBN_SEG_GEOM_MANY : rect ? MBN_SEG_GEOM_RECT : MBN_SEG_GEOM_WHOLE,
+                                           : c->guided || c->groups ? MBN_SEG_GEOM_MANY : rect ? MBN_SEG_GEOM_RECT : MBN_SEG_GEOM_WHOLE,
                                            { rect ? rect[0] : 0, rect ? rect[1] : 0, rect ? rect[2] : 0, rect ? rect[3] : 0 } };
     return MBN_OK;
 }
@@ -508,6 +516,16 @@ int mbn_net_segment_guided_fit(mbn_net *net, const void *src_u8, int batch, int 
     const readout_prob given = { prob_f32, min_prob, ignore_label };
     const seg_call c = { .path = P_FIT, .src = src_u8, .labels = labels_i32, .score = score_f32, .q = softmax_form(prob_f32, min_prob) ? &given : NULL,
                          .batch = batch, .rows = in_rows, .cols = in_cols, .fit = fit, .guided = 1, .sigma = sigma };
+    return segment_run(net, &c);
+}
+
+int mbn_net_segment_groups_fit(mbn_net *net, const mbn_class_groups *groups, const void *src_u8, int batch, int in_rows, int in_cols, int fit,
+                               void *labels_i32, void *prob_f32, void *score_f32, float min_prob, int ignore_label)
+{
+    if (!groups) return MBN_EINVAL;
+    const readout_prob given = { prob_f32, min_prob, ignore_label };
+    const seg_call c = { .path = P_FIT, .src = src_u8, .labels = labels_i32, .score = score_f32, .q = &given, .batch = batch, .rows = in_rows,
+                         .cols = in_cols, .fit = fit, .groups = groups };
     return segment_run(net, &c);
 }
 

@@ -35,6 +35,11 @@
  *   mbn_net_segment_guided_fit: the bilinear weights of every pixel are scaled by exp(-d^2 / (2 SIGMA^2)), d the L1 colour distance between the pixel
  *   of the --ppm file itself and the block mean of what the network saw. --segment-confidence, --min-confidence, --ignore-label, --truth and the
  *   scoring flags work as without it; not with --segment-topk, --tta-scales, --slide or --nll: usage status 2
+ *   --class-groups FILE (with ONE --ppm, --segment-source and --fit stretch or --fit pad): the labels are GROUPS of the plan's classes,
+ *   mbn_net_segment_groups_fit: per pixel the group whose members' softmax probabilities sum highest. FILE is text, one integer per class in class
+ *   order: the class's group, 0 .. groups - 1 (groups = the largest value + 1, at most 4096), or -1 to leave the class out of the softmax. The PGM's
+ *   maxval follows the groups; --segment-confidence (the group's probability), --min-confidence, --ignore-label, --truth and the scoring flags work as
+ *   without it, on group labels; not with --guided, --segment-topk, --tta-scales / --tta-flip, --slide or --nll: usage status 2
  *   --slide TH[xTW] [--slide-stride SH[xSW]] (with ONE --ppm and --segment-source; rows x columns): sliding-window segmentation,
  *   mbn_net_segment_slide: overlapping TH x TW crops of the image, each stretched to the network's input, and ONE read-out that averages the crops'
  *   logits where they overlap. The default stride is (2 * tile + 2) / 3 per axis. The fit is the stretch: with --fit pad or --fit crop, or with
@@ -887,7 +892,7 @@ static int write_confidence_map(const char *path, const float *prob, int rows, i
  * n_truth > 0 (--truth, one per image): the maps are scored against them on the device before anything is written */
 static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int n_ppm, const char *path, int classes, int fit, const char *conf_path,
                           float min_conf, int ignore, const float *scales, const int32_t *mirrors, int n_views, const int *slide, float guided,
-                          const char **truths, int n_truth, const region_opts *ro, const boundary_opts *bo, const panoptic_opts *po)
+                          const mbn_class_groups *groups, int n_groups, const char **truths, int n_truth, const region_opts *ro, const boundary_opts *bo, const panoptic_opts *po)
 {
     int64_t *offs = malloc(sizeof(int64_t) * (size_t)n_ppm), *dst = malloc(sizeof(int64_t) * (size_t)n_ppm);
     int32_t *hs = malloc(sizeof(int32_t) * (size_t)n_ppm), *ws = malloc(sizeof(int32_t) * (size_t)n_ppm);
@@ -915,7 +920,13 @@ static int segment_source(mbn_context *ctx, mbn_net *net, const char **ppms, int
     CHECK(mbn_alloc(ctx, sizeof(int) * pixels, &d_labels));
     CHECK(mbn_upload(ctx, d_src, all, total));
     if (!(min_conf > 0.0f)) ignore = -1;                        /* --min-confidence 0 replaces nothing: the argmax read-out, unless a map is asked for */
-    if (guided > 0.0f) {
+    if (groups) {
+        if (conf_path) CHECK(mbn_alloc(ctx, sizeof(float) * pixels, &d_prob));
+        CHECK(mbn_net_segment_groups_fit(net, groups, d_src, 1, hs[0], ws[0], fit, d_labels, d_prob, NULL, ignore >= 0 ? min_conf : 0.0f,
+                                         ignore >= 0 ? ignore : 0));
+        printf("segment: %d classes read out as %d groups\n", classes, n_groups);
+        classes = n_groups;                                     /* the maps hold group labels from here on */
+    } else if (guided > 0.0f) {
         if (conf_path) CHECK(mbn_alloc(ctx, sizeof(float) * pixels, &d_prob));
         CHECK(mbn_net_segment_guided_fit(net, d_src, 1, hs[0], ws[0], fit, guided, d_labels, d_prob, NULL, ignore >= 0 ? min_conf : 0.0f,
                                          ignore >= 0 ? ignore : 0));
@@ -1144,7 +1155,7 @@ int main(int argc, char **argv)
     int have_min_conf = 0, have_ignore = 0, ignore_label = -1, have_topk = 0, segment_topk = 0, have_calibration = 0, calibration_bins = 0, have_nll = 0, have_guided = 0;
     float guided = 0.0f;
     const char *temperatures = NULL;
-    const char *tta = NULL, *slide_arg = NULL, *slide_stride_arg = NULL;
+    const char *tta = NULL, *slide_arg = NULL, *slide_stride_arg = NULL, *groups_path = NULL;
     int fit_given = 0, slide[4] = { 0, 0, 0, 0 }, slide_tiles = 0;      /* slide: tile rows, tile columns, stride rows, stride columns */
     region_opts regions = { 0, 4, 1, 256 };
     int region_flags = 0;                                       /* --connectivity, --min-area or --max-regions seen */
@@ -1176,6 +1187,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--segment") && i + 1 < argc) segment = argv[++i];
         else if (!strcmp(argv[i], "--segment-source") && i + 1 < argc) segment_src = argv[++i];
         else if (!strcmp(argv[i], "--segment-confidence") && i + 1 < argc) segment_conf = argv[++i];
+        else if (!strcmp(argv[i], "--class-groups") && i + 1 < argc) groups_path = argv[++i];
         else if (!strcmp(argv[i], "--guided") && i + 1 < argc) { guided = (float)atof(argv[++i]); have_guided = 1; }
         else if (!strcmp(argv[i], "--segment-topk") && i + 1 < argc) { segment_topk = atoi(argv[++i]); have_topk = 1; }
         else if (!strcmp(argv[i], "--min-confidence") && i + 1 < argc) { min_conf = (float)atof(argv[++i]); have_min_conf = 1; }
@@ -1282,6 +1294,12 @@ int main(int argc, char **argv)
     if (have_guided && (!(guided > 0.0f) || guided > 3.0e38f || !segment_src || n_ppm != 1 || have_topk || tta || tta_flip || slide_arg || have_nll)) {
         fprintf(stderr, "--guided SIGMA (finite, > 0) needs one --ppm and --segment-source with --fit stretch or --fit pad; it goes with "
                         "--segment-confidence, --min-confidence / --ignore-label, --truth and the scoring flags, not with --segment-topk, --tta-scales, "
+                        "--slide or --nll\n");
+        return 2;
+    }
+    if (groups_path && (!segment_src || n_ppm != 1 || have_guided || have_topk || tta || tta_flip || slide_arg || have_nll)) {
+        fprintf(stderr, "--class-groups FILE needs one --ppm and --segment-source with --fit stretch or --fit pad; it goes with --segment-confidence, "
+                        "--min-confidence / --ignore-label, --truth and the scoring flags, not with --guided, --segment-topk, --tta-scales / --tta-flip, "
                         "--slide or --nll\n");
         return 2;
     }
@@ -1527,15 +1545,32 @@ int main(int argc, char **argv)
             printf("segment: image 0 is the %d x %d rectangle at (%d, %d) of the label map (wide x high, left, upper); the rest labels the border\n", rect[2],
                    rect[3], rect[0], rect[1]);
     }
+    mbn_class_groups *class_groups = NULL;
+    int n_groups = 0;
+    if (groups_path) {                                          /* one integer per class; the handle refuses what the layout refuses */
+        int32_t *group_of = malloc(sizeof(int32_t) * (size_t)classes);
+        FILE *f = fopen(groups_path, "r");
+        int c = 0, extra = 0;
+        if (!group_of) return 1;
+        while (f && c < classes && fscanf(f, "%d", &group_of[c]) == 1) { if (group_of[c] >= n_groups) n_groups = group_of[c] + 1; c++; }
+        const int more = f && fscanf(f, "%d", &extra) == 1;
+        if (f) fclose(f);
+        if (!f || c != classes || more || mbn_class_groups_create(ctx, classes, n_groups, group_of, &class_groups) != MBN_OK) {
+            fprintf(stderr, "--class-groups %s: not a text file of %d integers in -1 .. 4095 with at least one that is not -1\n", groups_path, classes);
+            return 2;
+        }
+        free(group_of);
+    }
     if (have_topk) {
         const int bad = segment_source_topk(ctx, net, ppm, segment_src, classes, fit, segment_topk, segment_conf, min_conf, have_ignore ? ignore_label : -1,
                                             n_truth ? truths[0] : NULL);
         if (bad) return bad;
     } else if (segment_src || segment_conf) {
         const int bad = segment_source(ctx, net, ppms, n_ppm, segment_src, classes, fit, segment_conf, min_conf, have_ignore ? ignore_label : -1,
-                                       view_scales, view_mirrors, n_views, slide_tiles ? slide : NULL, guided, truths, n_truth, &regions, &boundary, &panoptic);
+                                       view_scales, view_mirrors, n_views, slide_tiles ? slide : NULL, guided, class_groups, n_groups, truths, n_truth, &regions, &boundary, &panoptic);
         if (bad) return bad;
     }
+    mbn_class_groups_destroy(class_groups);
     mbn_net_destroy(net);
     mbn_weights_free(&w);
     mbn_shutdown(ctx);

@@ -882,6 +882,65 @@ int mbn_guide_reduce_u8(mbn_context *ctx, void *guide_lo_u8, const void *canvas_
 int mbn_resample_guided_f32(mbn_context *ctx, void *labels_i32, void *prob_f32, void *score_f32, const void *logits, const void *guide_lo_u8,
                             const void *guide_hi_u8, const void *lut_f32, int batch, int rows, int cols, int classes, int in_rows, int in_cols,
                             const int32_t rect[4], int out_rows, int out_cols, float min_prob, int ignore_label, void *stream);
+/* Segment by class groups: the read-out to any output size whose labels are GROUPS of the plan's classes: for every output pixel
+ * the group whose members' softmax probabilities sum highest, with that sum. With the 1000 ImageNet classes of the usual weights the argmax label is
+ * a dog breed or a car make; "dog / cat / vehicle / person / rest" is a grouping, and the arg-max remapped is NOT its answer (118 breeds at 0.5 %
+ * each lose to one sofa at 2 %). One kernel (mbn_f32_groups.hip); neither [out_rows][out_cols][classes] nor a per-group plane is in memory.
+ * The grouping. group_of [classes] int32: g in 0 .. groups - 1 puts class c in group g; -1 leaves it out of the numerator AND the denominator (the
+ *   probabilities renormalise over the KEPT classes; to keep a class in the denominator give it a "rest" group). A group without a class is never a
+ *   label. mbn_class_groups_layout (host, libmbn_host.so) writes the order the kernel walks: groups ascending, classes ascending inside a group,
+ *   every non-empty group padded to a multiple of four SLOTS with slot_class = -1; quad_group[q] = g when slots 4q .. 4q + 3 are the last of group
+ *   g, else -1; *slots <= classes + 3 * groups, the room slot_class needs (quad_group a quarter of it). MBN_EINVAL: a NULL pointer, classes or
+ *   groups <= 0, a value outside -1 .. groups - 1, no kept class; else MBN_EUNSUPPORTED: groups > MBN_CONFUSION_MAX_CLASSES (the maps are made to
+ *   be scored). mbn_class_groups_create checks the same and uploads the two tables once (MBN_ENOMEM, MBN_EDEVICE as mbn_alloc); the handle belongs
+ *   to the context, may serve any number of calls on any stream, and is freed by mbn_class_groups_destroy (which waits for the device) or by
+ *   mbn_shutdown.
+ * Normative (tests/dense_groups_ref.py evaluates it in float64 on the fp32 interpolants):
+ *   Interpolants. The v_c of a pixel are bit for bit those of mbn_resample_argmax_window_f32 for rect, of mbn_resample_argmax_f32 for rect = NULL
+ *     (in_rows, in_cols are then not read). K = the kept classes whose v_c is not NaN (a NaN adds nothing anywhere), m = max over K of v_c.
+ *   Sums. S_g = sum over the members c in K of group g of exp(v_c - m); T = sum_g S_g. The label is the lowest g with S_g = max S (a group without
+ *     members is not a candidate); prob = S_label / T; score = m + ln(S_label), the winning group's log-sum-exp: a "group logit" on the scale of
+ *     the v_c, what the score of the other read-outs is for a group of one class.
+ *   Not finite. If m is not finite (+inf, or no kept v above -inf): prob = 0 exactly, score = m (-inf when K is empty), label = the lowest
+ *     non-empty group. It falls under any positive min_prob, as in the softmax call.
+ *   Threshold. The stored label is ignore_label iff the stored prob < min_prob (strict, on the fp32 value written). min_prob in [0, 1], else
+ *     MBN_EINVAL; prob_f32 and score_f32 may each be NULL at any min_prob: there is no argmax-only sibling to confuse the call with.
+ *   Tolerance. prob, score and (at near ties) the label are NOT bit-pinned: they rest on v_exp_f32 sums. The kernel keeps per pixel ONE lazy
+ *     reference (the RS_MARGIN = 16 rule of the softmax call) for three sums: the open group, the closed groups' total, the best closed group; a
+ *     move of the reference rescales all three by the same factor. In units of 2^-24 relative, with L = ln(classes * groups):
+ *       - every term goes through at most classes + groups additions of non-negative values (its group's, then one per closed group);
+ *       - a term exp(d), d = v - ref <= 16: the subtraction and the log2(e) pre-multiply err by 2.5 |d| in the exponent, v_exp_f32 by 2 more and
+ *         the add by 1. For d > 0 that is 2.5 * 16 + 3. For d < 0 the softmax call argues |d| e^d < 1 against a sum >= 1; here the sum that must
+ *         stay accurate is a SUB-sum, S_label >= T / groups >= 1 / groups under the final reference, and the |d|-weighted mean over its terms is at
+ *         most 2 L (terms below e^-L weigh under L / groups together). So a term costs at most T1 = 2.5 * (16 + 2 L) + 3;
+ *       - a rescale by exp(-x), x > 16, errs by 2.5 x + 3 on a part that afterwards weighs at most classes * e^(16 - x) under the new reference,
+ *         that is classes * groups * e^(16 - x) of S_label: x * min(1, classes * groups * e^(16 - x)) <= 16 + L, so R1 = 2.5 * (16 + L) + 3 per
+ *         rescale. "Only the first rescale of a part counts" holds for the whole sum because a part that went through k rescales is below
+ *         classes * e^(-16 (k - 1)) of it. Of S_label the same part may be classes * groups * e^(-16 (k - 1)): it can still be ALL of the winning
+ *         group while k <= K1 = 1 + ceil(L / 16) (2 up to classes * groups = e^16 = 8.8e6, never above 3 below e^32), and from there on falls by
+ *         e^-16 per rescale, less than one more R1 for all further ones together. A winning group has therefore gone through at most K1 rescales
+ *         that count: (K1 + 1) * R1.
+ *       A = classes + groups + T1 + (K1 + 1) * R1 bounds S_label and T alike, and with the division
+ *           |prob - ref| <= (2 A + 1) * 2^-24 * ref       (classes 1000, groups 21: A = 1318, 1.6e-4; classes 5, groups 3: A = 214, 2.6e-5)
+ *       score is ABSOLUTE: ln(S_label) inherits 1.01 A; v_log_f32 (1 ulp) and the ln 2 multiply add 3 units of |ln S_label| <= 16 + L, the final
+ *       add one unit of |score| <= |m| + 16 + L:
+ *           |score - ref| <= (1.01 A + 4 * (16 + L) + |m| + 16) * 2^-24
+ *     The reference is the float64 evaluation on the fp32 v_c. Labels are equal wherever the two largest S_g differ by more than a factor
+ *     1 + (4 A + 2) * 2^-24 (the tests hold their inputs to 1 + 2^-10 and then require EVERY label equal).
+ * groups = classes with group_of[c] = c gives mbn_resample_softmax_f32's labels (near ties aside) and its prob within the two bounds.
+ * The envelope, pointer, alignment, byte and batch limits and their statuses are those of mbn_resample_softmax_window_f32 (rect = NULL: of
+ * mbn_resample_softmax_f32); `classes` must be the handle's and the handle this context's, else MBN_EINVAL; mbn_resample_groups_envelope
+ * (host/mbn_envelope.h) is the pure form of the shape check. Nothing is launched on a refusal; the mbn_alloc bounds rule applies to every operand.
+ * The call is ONE kernel and may be captured as one kernel node. */
+typedef struct mbn_class_groups mbn_class_groups;
+int mbn_class_groups_layout(int classes, int groups, const int32_t *group_of, int32_t *slot_class, int32_t *quad_group, int *slots);
+int mbn_class_groups_create(mbn_context *ctx, int classes, int groups, const int32_t *group_of, mbn_class_groups **g);
+int mbn_class_groups_destroy(mbn_class_groups *g);
+/* the class and group counts a handle was made for (either pointer may be NULL); MBN_EINVAL for a NULL handle or one of another context than ctx */
+int mbn_class_groups_info(const mbn_class_groups *g, const mbn_context *ctx, int *classes, int *groups);
+int mbn_resample_groups_f32(mbn_context *ctx, const mbn_class_groups *g, void *labels_i32, void *prob_f32, void *score_f32, const void *logits,
+                            int batch, int rows, int cols, int classes, int in_rows, int in_cols, const int32_t rect[4], int out_rows, int out_cols,
+                            float min_prob, int ignore_label, void *stream);
 /* Regions of a label map: connected-component labelling of the int32 maps the read-outs above write, on the device.
  * Normative (tests/components_ref.py is the numpy form; everything is integer, so the result is a function of the input alone: the same bytes at
  * every planning CU count, in both forms, on every run and on graph replay). For one image L [rows][cols] and classes >= 1:
@@ -1701,6 +1760,14 @@ int  mbn_net_segment_prob_images_fit(mbn_net *net, const void *src_u8, const int
  * _surface, _panoptic and _calibration work on its maps unchanged (mbn_net_segment_nll does not: no bilinear read-out of the logits gives these maps). */
 int  mbn_net_segment_guided_fit(mbn_net *net, const void *src_u8, int batch, int in_rows, int in_cols, int fit, float sigma, void *labels_i32,
                                 void *prob_f32, void *score_f32, float min_prob, int ignore_label);
+/* Segment by class groups (mbn_resample_groups_f32 above): mbn_net_segment_prob_fit, step for step, with the group read-out of `groups` (a handle
+ * of the net's context made for the plan's class count, else MBN_EINVAL). Every check comes before the resize and the forward pass;
+ * MBN_FIT_STRETCH reads out the whole map, MBN_FIT_PAD mbn_fit_pad's rectangle, MBN_FIT_CROP is MBN_EUNSUPPORTED. labels_i32, prob_f32 (may be
+ * NULL) and score_f32 (may be NULL) [batch][in_rows][in_cols]. Every dtype the dense head runs in. The call is recorded as the net's most recent
+ * successful segment call WITH classes = the handle's groups: mbn_net_segment_score, _regions, _boundary_*, _surface, _panoptic and _calibration
+ * run on group labels with group-sized tables, unchanged. mbn_net_segment_nll refuses such a record (MBN_EINVAL): its table is per fine class. */
+int  mbn_net_segment_groups_fit(mbn_net *net, const mbn_class_groups *groups, const void *src_u8, int batch, int in_rows, int in_cols, int fit,
+                                void *labels_i32, void *prob_f32, void *score_f32, float min_prob, int ignore_label);
 /* Segment with runners-up (mbn_resample_topk_f32 above): mbn_net_segment_prob_fit / _prob_images_fit, step for step, with the top-k read-out, in every
  * dtype those serve. labels_i32, prob_f32 and score_f32 are rank-major: [k][batch][in_rows][in_cols] for the uniform call; for the image call rank j
  * of image i at j * plane_stride + dst_offsets[i] (plane_stride in elements, at least max(dst_offsets + rows * cols)). prob_f32 = NULL with

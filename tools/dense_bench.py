@@ -25,6 +25,9 @@
       mbn_resample_softmax_f32 / _window_f32 / _ragged_f32, the read-out with confidence (main_prob): each beside the argmax kernel of the same
       form on the same buffers, alternating in one process, and torch's three-pass interpolate(size=...).softmax(1).max(1).
 
+  python tools/dense_bench.py --groups [--reps 7] [--steps 20] [--batch 32] [--torch-steps 2] [--no-torch]
+      mbn_resample_groups_f32 (1000 classes into 21 groups) beside the softmax window read-out and the torch route it replaces (main_groups).
+
   python tools/dense_bench.py --topk [--reps 7] [--steps 20] [--batch 32] [--torch-steps 2] [--no-torch]
       mbn_resample_topk_f32, the read-out with runners-up (main_topk): k = 1, 5, 8, with and without prob, on random logits and on the ascending
       ramp (the worst case), beside the softmax and argmax kernels on the same buffers and torch's interpolate(...).softmax(1).topk(k).
@@ -411,6 +414,73 @@ def main_guided(a):
             print("%-32s bilinear %.4f ms (spread %.1f %%)  guided %.4f ms (spread %.1f %%, %.1f %% of the VALU rate, %.1f %% of 8 TB/s)  ratio %.3f"
                   % (name, out["bilinear"]["kernel_ms"], 100 * out["bilinear"]["spread"], out["guided"]["kernel_ms"], 100 * out["guided"]["spread"],
                      100 * out["guided"]["kernel_frac_of_valu_rate"], 100 * out["guided"]["kernel_frac_of_8TBps"], out["guided_over_bilinear"]), flush=True)
+    print(json.dumps(result))
+
+
+def main_groups(a):
+    """--groups: mbn_resample_groups_f32 beside mbn_resample_softmax_window_f32 in the same process: 1000 classes into 21 groups (c % 21), --batch
+    maps of random logits (sigma 3) to 375 x 500 through mbn_fit_pad's rectangle of a 224 x 224 input, from the 28 x 28 and the 14 x 14 map,
+    alternating within every repetition on the same buffers. And the route the call replaces, torch-ROCm on the same buffer: interpolate ->
+    softmax -> index_add over the groups -> max, in slices of 8 images. Each figure is the median over the repetitions of `steps` back-to-back
+    calls between two stream marks; the runs are kept, the spread is (max - min) / median of a name's own repetitions."""
+    pkg = import_package()
+    torch = None
+    if not a.no_torch:
+        import torch
+        assert torch.cuda.is_available(), "the yardstick needs torch on the same GPU"
+    n, rng, groups = a.batch, np.random.default_rng(0), 21
+    H, W = 375, 500
+    rect = tuple(pkg.fit_pad(H, W, RES, RES))
+    group_of = np.arange(CLASSES) % groups
+    result = {"batch": n, "rect": list(rect), "classes": CLASSES, "groups": groups}
+    with pkg.Context(0) as ctx:
+        cg = pkg.ClassGroups(ctx, group_of, groups)
+        d_lab, d_sc, d_pr = (ctx.alloc(n * H * W * 4) for _ in range(3))
+        maps = {}
+        for hw_ in (28, 14):
+            x = (3.0 * rng.standard_normal((n, hw_, hw_, CLASSES))).astype(np.float32)
+            keep = torch.from_numpy(x).cuda() if torch is not None else ctx.to_device(x)
+            maps[hw_] = (keep.data_ptr() if torch is not None else keep.ptr, keep)
+        runs = [(hw_, lambda p=maps[hw_][0], hw_=hw_: ctx.resample_softmax_window(d_lab.ptr, d_pr.ptr, d_sc.ptr, p, n, hw_, hw_, CLASSES, RES, RES, rect, H, W),
+                 lambda p=maps[hw_][0], hw_=hw_: ctx.resample_groups(cg, d_lab.ptr, d_pr.ptr, d_sc.ptr, p, n, hw_, hw_, CLASSES, H, W, RES, RES, rect))
+                for hw_ in (28, 14)]
+        times = {(hw_, k): [] for hw_, _, _ in runs for k in ("softmax", "groups", "torch")}
+        for _, soft, grp in runs:
+            marks_ms(ctx, soft, 3)
+            marks_ms(ctx, grp, 3)
+        for _ in range(a.reps):
+            for hw_, soft, grp in runs:
+                times[(hw_, "softmax")].append(marks_ms(ctx, soft, a.steps))
+                times[(hw_, "groups")].append(marks_ms(ctx, grp, a.steps))
+            for hw_ in (28, 14) if torch is not None else ():
+                ctx.sync()
+                nchw, index = maps[hw_][1].permute(0, 3, 1, 2), torch.from_numpy(group_of).cuda()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+                def host_route():
+                    for i in range(0, n, 8):
+                        p = torch.nn.functional.interpolate(nchw[i:i + 8], size=(H, W), mode="bilinear", align_corners=False).softmax(1)
+                        torch.zeros((p.shape[0], groups, H, W), device=p.device).index_add_(1, index, p).max(1)
+                host_route()
+                e0.record()
+                for _ in range(a.torch_steps):
+                    host_route()
+                e1.record()
+                torch.cuda.synchronize()
+                times[(hw_, "torch")].append(e0.elapsed_time(e1) / a.torch_steps)
+        for hw_, _, _ in runs:
+            out = {}
+            for k in ("softmax", "groups", "torch"):
+                ts = times[(hw_, k)]
+                if ts:
+                    m = statistics.median(ts)
+                    out[k] = {"kernel_ms": round(m, 4), "kernel_runs_ms": [round(v, 4) for v in ts], "spread": round((max(ts) - min(ts)) / m, 4)}
+            out["groups_over_softmax"] = round(out["groups"]["kernel_ms"] / out["softmax"]["kernel_ms"], 3)
+            result["from_%d" % hw_] = out
+            print("from_%d  softmax window %.4f ms (spread %.1f %%)  groups %.4f ms (spread %.1f %%)  ratio %.3f  torch %s ms"
+                  % (hw_, out["softmax"]["kernel_ms"], 100 * out["softmax"]["spread"], out["groups"]["kernel_ms"], 100 * out["groups"]["spread"],
+                     out["groups_over_softmax"], out["torch"]["kernel_ms"] if "torch" in out else "-"), flush=True)
+        cg.close()
     print(json.dumps(result))
 
 
@@ -1677,10 +1747,13 @@ def main():
     ap.add_argument("--calibration", action="store_true", help="time mbn_calibration_f32 beside mbn_confusion_i32 and torch instead: see main_calibration")
     ap.add_argument("--surface", action="store_true", help="time mbn_surface_score_i32 beside torch.cdist and scipy's distance transform instead: see main_surface")
     ap.add_argument("--nll", action="store_true", help="time mbn_resample_nll_f32 beside the argmax and softmax read-outs and torch instead: see main_nll")
+    ap.add_argument("--groups", action="store_true", help="time mbn_resample_groups_f32 beside the softmax window read-out instead: see main_groups")
     ap.add_argument("--guided", action="store_true", help="time mbn_resample_guided_f32 beside the bilinear window read-outs instead: see main_guided")
     a = ap.parse_args()
     if a.guided:
         return main_guided(a)
+    if a.groups:
+        return main_groups(a)
     if a.nll:
         return main_nll(a)
     if a.calibration:
