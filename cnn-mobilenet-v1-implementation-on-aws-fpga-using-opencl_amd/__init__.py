@@ -298,6 +298,11 @@ def _declare_host(lib):
     lib.mbn_guide_reduce_envelope.argtypes = [C.c_int] * 4                                                       # mbn_envelope.h
     lib.mbn_class_groups_layout.argtypes = [C.c_int, C.c_int] + [C.POINTER(C.c_int32)] * 3 + [C.POINTER(C.c_int)]
     lib.mbn_resample_groups_envelope.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float]
+    lib.mbn_similarity_envelope.argtypes = [C.c_int] * 4
+    lib.mbn_embed_envelope.argtypes = [C.c_int] * 3
+    lib.mbn_similarity_tile.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int]                # mbn.h
+    lib.mbn_similarity_workspace_bytes.argtypes = [C.c_int] * 4
+    lib.mbn_similarity_workspace_bytes.restype = C.c_size_t
     lib.mbn_components_envelope.argtypes = [C.c_int] * 7
     lib.mbn_components_tile.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.mbn_components_scratch_bytes.argtypes = [C.c_int, C.c_int64]
@@ -442,6 +447,11 @@ def load():
         lib.mbn_blocks_resident_bf16.argtypes = [vp, vp, vp, C.POINTER(BlockParams), ci, ci, ci, ci, ci, vp]
         lib.mbn_tail_resident_bf16.argtypes = [vp, vp, vp, C.POINTER(BlockParams), ci, ci, ci, ci, ci, vp]
         lib.mbn_softmax_topk_f32.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, vp]
+        lib.mbn_similarity_topk_f32.argtypes = [vp] * 7 + [ci] * 4 + [vp, vp]
+        lib.mbn_row_inv_norm_f32.argtypes = [vp, vp, vp, ci, ci, vp]
+        lib.mbn_embed_rows.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp]
+        lib.mbn_net_embed.argtypes = [vp, vp, ci, vp, vp]
+        lib.mbn_net_nearest.argtypes = [vp, vp, ci, vp, vp, ci, ci, vp, vp]
         lib.mbn_classifier_tail.argtypes = [vp] * 9 + [ci] * 6 + [vp]
         lib.mbn_upsample_argmax_f32.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
         lib.mbn_net_forward_dense.argtypes = [vp, vp, vp, ci]
@@ -844,6 +854,23 @@ def resample_groups_envelope(batch, rows, cols, classes, group_classes, in_rows,
     """mbn_resample_groups_envelope: the status Context.resample_groups gives the shape, the handle's class count and min_prob."""
     return (lib or host_lib()).mbn_resample_groups_envelope(batch, rows, cols, classes, group_classes, in_rows, in_cols,
                                                             None if rect is None else _rect(rect), out_rows, out_cols, min_prob)
+
+
+def similarity_envelope(Q, G, D, k, lib=None) -> int:
+    """mbn_similarity_envelope: the status (OK, EINVAL or EUNSUPPORTED) Context.similarity_topk gives the shape."""
+    return (lib or host_lib()).mbn_similarity_envelope(Q, G, D, k)
+
+
+def similarity_tile(Q, D, lib=None):
+    """mbn_similarity_tile: (q_tile, g_tile), the queries and gallery rows of one work unit of the search; a function of Q and D alone."""
+    qt, gt = C.c_int(), C.c_int()
+    _chk((lib or host_lib()).mbn_similarity_tile(C.byref(qt), C.byref(gt), Q, D), "similarity_tile")
+    return qt.value, gt.value
+
+
+def similarity_workspace_bytes(Q, G, D, k, lib=None) -> int:
+    """mbn_similarity_workspace_bytes: the device memory Context.similarity_topk needs as `workspace` (0: a shape it refuses)."""
+    return (lib or host_lib()).mbn_similarity_workspace_bytes(Q, G, D, k)
 
 
 def softmax_readout_check(have_prob, min_prob, lib=None) -> int:
@@ -1376,6 +1403,21 @@ class Context:
                                               None if rect is None else _rect(rect), out_rows, out_cols, min_prob, ignore_label, None),
              self.last_error())
 
+    def similarity_topk(self, topk_idx, topk_score, queries, gallery, Q, G, D, k, workspace, q_scale=None, g_scale=None):
+        """mbn_similarity_topk_f32: per query row the k best rows of gallery [G][D] under (queries . gallery) * q_scale * g_scale, best first
+        (ties: the lowest index), topk_idx [Q][k] int32 (-1 past the ranked entries) and topk_score [Q][k] fp32. Device pointers; workspace of
+        similarity_workspace_bytes(Q, G, D, k). Inverse norms (row_inv_norm) as scales give the cosine."""
+        _chk(self.lib.mbn_similarity_topk_f32(self.h, topk_idx, topk_score, queries, gallery, q_scale, g_scale, Q, G, D, k, workspace, None),
+             self.last_error())
+
+    def row_inv_norm(self, out, x, N, D):
+        """mbn_row_inv_norm_f32: out[n] = 1 / sqrt(sum of squares of row n of x [N][D] fp32); 0 for a row of zeros."""
+        _chk(self.lib.mbn_row_inv_norm_f32(self.h, out, x, N, D, None), self.last_error())
+
+    def embed_rows(self, out_f32, inv_norm, rows, dtype, N, D):
+        """mbn_embed_rows: rows [N][D] stored as fp32 or bf16 (DT_F32 / DT_BF16) -> out_f32 [N][D] and inv_norm [N] (may be None), one pass."""
+        _chk(self.lib.mbn_embed_rows(self.h, out_f32, inv_norm, rows, dtype, N, D, None), self.last_error())
+
     def resample_ensemble(self, labels, prob, score, logits, batch, rows, cols, classes, in_rows, in_cols, view_list, out_rows, out_cols,
                           min_prob=0.0, ignore_label=0, n_views=None):
         """mbn_resample_ensemble_f32: ONE read-out of the views in view_list (View objects or (x, y, iw, ih, mirror)) over view-major logits
@@ -1830,6 +1872,14 @@ class Net:
 
     def classify(self, images_dev, batch, k, topk_idx_dev, topk_prob_dev):
         _chk(self.ctx.lib.mbn_net_classify(self.h, images_dev, batch, k, topk_idx_dev, topk_prob_dev), self.ctx.last_error())
+
+    def embed(self, images_dev, batch, emb_dev, inv_norm_dev=None):
+        """mbn_net_embed: the pooled vector of every image (the layer in front of the FC) as fp32 rows emb [batch][D], and their inverse norms."""
+        _chk(self.ctx.lib.mbn_net_embed(self.h, images_dev, batch, emb_dev, inv_norm_dev), self.ctx.last_error())
+
+    def nearest(self, images_dev, batch, gallery_dev, G, k, idx_dev, score_dev, g_scale_dev=None):
+        """mbn_net_nearest: embed, then the k gallery rows [G][D] nearest by cosine per image (g_scale: the gallery's inverse norms, None = 1)."""
+        _chk(self.ctx.lib.mbn_net_nearest(self.h, images_dev, batch, gallery_dev, g_scale_dev, G, k, idx_dev, score_dev), self.ctx.last_error())
 
     def forward_dense(self, images_ptr, out_ptr, batch):
         """The FC at every pixel of the map in front of the pool: out [batch][h][w][classes] fp32 (mbn_net_forward_dense)."""

@@ -850,6 +850,45 @@ int mbn_softmax_topk_f32(mbn_context *ctx, void *probs, void *topk_idx_i32, void
                                                  (const float *)logits, batch, classes, k));
 }
 
+// Nearest neighbours (mbn_f32_similarity.hip): the statuses in mbn.h's order — null and misaligned-by-4 first, then the envelope, then the 16-byte rule
+int mbn_similarity_topk_f32(mbn_context *ctx, void *topk_idx_i32, void *topk_score_f32, const void *queries, const void *gallery,
+                            const void *q_scale, const void *g_scale, int Q, int G, int D, int k, void *workspace, void *stream)
+{
+    if (!ctx || !topk_idx_i32 || !topk_score_f32 || !queries || !gallery || !workspace) return MBN_EINVAL;
+    if (((uintptr_t)topk_idx_i32 | (uintptr_t)topk_score_f32 | (uintptr_t)q_scale | (uintptr_t)g_scale) % 4) return MBN_EINVAL;
+    const int shape = mbn_similarity_envelope(Q, G, D, k);
+    if (shape != MBN_OK) return shape;
+    if (((uintptr_t)queries | (uintptr_t)gallery | (uintptr_t)workspace) % 16) return MBN_EUNSUPPORTED;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    MBN_SPANS(ctx, { queries, 4.0 * Q * D, "similarity queries" }, { gallery, 4.0 * G * D, "similarity gallery" },
+              { q_scale, 4.0 * Q, "similarity q_scale" }, { g_scale, 4.0 * G, "similarity g_scale" },
+              { topk_idx_i32, 4.0 * Q * k, "similarity idx" }, { topk_score_f32, 4.0 * Q * k, "similarity score" },
+              { workspace, (double)mbn_similarity_workspace_bytes(Q, G, D, k), "similarity workspace" });
+    Scope sc(ctx, s);
+    return sc.finish(mbn_launch_f32_similarity_topk(ctx, s, (int32_t *)topk_idx_i32, (float *)topk_score_f32, (const float *)queries,
+                                                    (const float *)gallery, (const float *)q_scale, (const float *)g_scale, Q, G, D, k, workspace));
+}
+
+int mbn_embed_rows(mbn_context *ctx, void *out_f32, void *inv_norm, const void *in, int dtype, int N, int D, void *stream)
+{
+    if (!ctx || !in || (!out_f32 && !inv_norm)) return MBN_EINVAL;
+    if ((uintptr_t)inv_norm % 4) return MBN_EINVAL;
+    const int shape = mbn_embed_envelope(N, D, dtype);
+    if (shape != MBN_OK) return shape;
+    const double esz = dtype == MBN_DT_BF16 ? 2.0 : 4.0;
+    if ((uintptr_t)out_f32 % 16 || (uintptr_t)in % (dtype == MBN_DT_BF16 ? 8 : 16)) return MBN_EUNSUPPORTED;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    MBN_SPANS(ctx, { in, esz * N * D, "embed rows in" }, { out_f32, 4.0 * N * D, "embed rows out" }, { inv_norm, 4.0 * N, "embed rows inv_norm" });
+    Scope sc(ctx, s);
+    return sc.finish(mbn_launch_rows_norm(ctx, s, (float *)out_f32, (float *)inv_norm, in, dtype, N, D));
+}
+
+int mbn_row_inv_norm_f32(mbn_context *ctx, void *out, const void *x, int N, int D, void *stream)
+{
+    if (!out) return MBN_EINVAL;
+    return mbn_embed_rows(ctx, nullptr, out, x, MBN_DT_F32, N, D, stream);
+}
+
 int mbn_upsample_argmax_f32(mbn_context *ctx, void *labels_i32, void *score_f32, const void *logits, int batch, int rows, int cols, int classes,
                             int factor, void *stream)
 {

@@ -401,6 +401,12 @@ void mbn_class_groups_release(mbn_class_groups *g);
 int mbn_launch_f32_resample_groups(mbn_context *ctx, hipStream_t s, const mbn_class_groups *g, int32_t *labels, float *prob, float *score,
                                    const float *logits, int batch, int rows, int cols, int in_rows, int in_cols, const int32_t *rect, int out_rows,
                                    int out_cols, float min_prob, int ignore_label);
+// nearest neighbours (mbn_f32_similarity.hip): the fused similarity GEMM + top-k and its chunk merge, two launches on s, inside
+// mbn_similarity_envelope with `workspace` of mbn_similarity_workspace_bytes; the row pass of mbn_row_inv_norm_f32 / mbn_embed_rows inside
+// mbn_embed_envelope (out or inv_norm may be null). Pointers checked by the callers
+int mbn_launch_f32_similarity_topk(mbn_context *ctx, hipStream_t s, int32_t *idx, float *score, const float *queries, const float *gallery,
+                                   const float *q_scale, const float *g_scale, int Q, int G, int D, int k, void *workspace);
+int mbn_launch_rows_norm(mbn_context *ctx, hipStream_t s, float *out, float *inv_norm, const void *in, int dtype, int N, int D);
 // rank score (mbn_i32_topk_rank.hip): ranks [classes + 1][k + 1] uint64 += per truth row the rank at which the truth is among the k label planes
 // (plane j at j * plane_stride elements). The arguments are inside mbn_topk_rank_envelope and the pointers checked
 int mbn_launch_i32_topk_rank(mbn_context *ctx, hipStream_t s, void *ranks, const void *labels, int k, int64_t plane_stride, const void *truth,

@@ -108,6 +108,12 @@ int mbn_guide_reduce_envelope(int batch, int in_rows, int in_cols, int S);
  * mbn_resample_window_plan's (mbn_resample_plan's), its chunk counted in slots of the layout instead of classes */
 int mbn_resample_groups_envelope(int batch, int rows, int cols, int classes, int group_classes, int in_rows, int in_cols, const int32_t rect[4],
                                  int out_rows, int out_cols, float min_prob);
+/* mbn_similarity_topk_f32 (host/mbn_similarity.c): MBN_EINVAL for a non-positive size or k outside 1 .. MBN_SIMILARITY_MAX_K; else MBN_EUNSUPPORTED
+ * for D off 4, below 4 or above MBN_SIMILARITY_MAX_D, for Q * D * 4 >= 2^31, for G * D * 4 >= 2^32 and for 2^31 work units or more (ceil(Q / q_tile) * ceil(G / g_tile) of mbn_similarity_tile) */
+int mbn_similarity_envelope(int Q, int G, int D, int k);
+/* mbn_row_inv_norm_f32 (dtype MBN_DT_F32) and mbn_embed_rows: MBN_EINVAL for a non-positive size; else MBN_EUNSUPPORTED for a dtype other than
+ * fp32 and bf16, for D off 4 or above MBN_SIMILARITY_MAX_D */
+int mbn_embed_envelope(int N, int D, int dtype);
 /* mbn_resample_ragged_check for the items of mbn_ragged_readout_set_window: the same statuses, overlap sort and scratch, every item under
  * mbn_resample_window_envelope with its own rectangle; *l is written only when the batch is accepted */
 int mbn_resample_ragged_window_check(int rows, int cols, int classes, int in_rows, int in_cols, const mbn_label_window_item *items, int batch,

@@ -95,6 +95,9 @@ int mbn_net_destroy(mbn_net *net)
     if (net->graph) mbn_graph_destroy(net->ctx, net->graph);
     if (net->logits_buf) mbn_free(net->ctx, net->logits_buf);
     if (net->dense_feat) mbn_free(net->ctx, net->dense_feat);
+    if (net->embed_raw) mbn_free(net->ctx, net->embed_raw);
+    if (net->near_emb) mbn_free(net->ctx, net->near_emb);
+    if (net->near_ws) mbn_free(net->ctx, net->near_ws);
     if (net->poolfc_ws) mbn_free(net->ctx, net->poolfc_ws);
     mbn_net_seg_release(net);
     for (int j = 0; j < 8; j++)
@@ -797,6 +800,48 @@ int mbn_net_classify(mbn_net *net, const void *images, int batch, int k, void *t
     int rc = forward_impl(net, images, net->logits_buf, batch, 0, NULL, 0);
     if (rc != MBN_OK) return rc;
     return mbn_softmax_topk_f32(net->ctx, NULL, topk_idx_i32, topk_prob_f32, net->logits_buf, batch, fc->out_ch, k, NULL);
+}
+
+/* Feature extractor: layers 1 .. pool into the net's own buffer (bf16 mode stores bf16 there), then the rows widened and their inverse norms */
+int mbn_net_embed(mbn_net *net, const void *images, int batch, void *emb_f32, void *inv_norm_f32)
+{
+    if (!net || !images || !emb_f32 || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
+    const int pool = net->plan.n_layers - 1;                  /* 1-based index of the layer in front of the FC */
+    if (net->dtype == MBN_DT_I8 || pool < 1 || net->plan.layer[pool - 1].kind != MBN_L_POOL) return MBN_EUNSUPPORTED;
+    const int D = net->plan.layer[pool - 1].out_ch;
+    int rc = MBN_OK;
+    if (!net->embed_raw) rc = mbn_alloc(net->ctx, (size_t)net->max_batch * D * sizeof(float), &net->embed_raw);
+    if (rc == MBN_OK) rc = forward_impl(net, images, net->embed_raw, batch, pool, NULL, 0);
+    void *rows = NULL;
+    if (rc == MBN_OK) rc = mbn_net_layer_output(net, pool, &rows, NULL);
+    if (rc != MBN_OK) return rc;
+    return mbn_embed_rows(net->ctx, emb_f32, inv_norm_f32, rows, net->dtype, batch, D, NULL);
+}
+
+int mbn_net_nearest(mbn_net *net, const void *images, int batch, const void *gallery_f32, const void *g_scale_f32, int G, int k, void *idx_i32,
+                    void *score_f32)
+{
+    if (!net || !images || !gallery_f32 || !idx_i32 || !score_f32 || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
+    const int pool = net->plan.n_layers - 1;
+    if (net->dtype == MBN_DT_I8 || pool < 1 || net->plan.layer[pool - 1].kind != MBN_L_POOL) return MBN_EUNSUPPORTED;
+    const int D = net->plan.layer[pool - 1].out_ch;
+    int rc = mbn_similarity_envelope(batch, G, D, k);
+    if (rc != MBN_OK) return rc;
+    const size_t emb_bytes = (size_t)net->max_batch * D * sizeof(float);       /* the rows (a multiple of 16 bytes), then their inverse norms */
+    if (!net->near_emb) rc = mbn_alloc(net->ctx, emb_bytes + (size_t)net->max_batch * sizeof(float), &net->near_emb);
+    const size_t need = mbn_similarity_workspace_bytes(batch, G, D, k);
+    if (rc == MBN_OK && need > net->near_ws_bytes) {          /* grown on demand; mbn_free waits for the launches that use the old one */
+        if (net->near_ws) mbn_free(net->ctx, net->near_ws);
+        net->near_ws = NULL;
+        net->near_ws_bytes = 0;
+        rc = mbn_alloc(net->ctx, need, &net->near_ws);
+        if (rc == MBN_OK) net->near_ws_bytes = need;
+    }
+    if (rc != MBN_OK) return rc;
+    void *inv = (char *)net->near_emb + emb_bytes;
+    rc = mbn_net_embed(net, images, batch, net->near_emb, inv);
+    if (rc != MBN_OK) return rc;
+    return mbn_similarity_topk_f32(net->ctx, idx_i32, score_f32, net->near_emb, gallery_f32, inv, g_scale_f32, batch, G, D, k, net->near_ws, NULL);
 }
 
 /* the dense head's layers: *feat = the layer in front of the pool, *fc = the FC; MBN_EUNSUPPORTED for a plan that does not end in pool, FC */

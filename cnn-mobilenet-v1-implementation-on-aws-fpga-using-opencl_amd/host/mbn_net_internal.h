@@ -95,6 +95,10 @@ struct mbn_net {
     void *keep_buf[MBN_MAX_LAYERS];
     void *logits_buf;          /* mbn_net_classify: [max_batch][classes] fp32 */
     void *dense_feat;          /* mbn_net_forward_dense: the activation in front of the pool, [max_batch][h][w][channels] at fp32 size */
+    void *embed_raw;           /* mbn_net_embed: the pool's output in the current mode, [max_batch][channels] at fp32 size */
+    void *near_emb;            /* mbn_net_nearest: [max_batch][channels] fp32 rows, then [max_batch] inverse norms */
+    void *near_ws;             /* ... and the search's workspace, grown on demand */
+    size_t near_ws_bytes;
     void *poolfc_ws;           /* workspace of mbn_pool_fc (1...4 images: pool + FC in one launch), allocated and zeroed at creation */
     size_t poolfc_ws_bytes;
     int fuse_tail;             /* mbn_net_set_fuse_tail (default 0) */

@@ -1229,6 +1229,50 @@ int mbn_classifier_tail_fused(mbn_context *ctx, void *topk_idx_i32, void *topk_p
                               const void *fc_bias, int batch, int rows, int cols, int channels, int classes, int k, void *workspace,
                               size_t workspace_bytes, void *stream);
 
+/* Nearest neighbours: the network as a feature extractor (csrc/mbn_f32_similarity.hip, host/mbn_similarity.c). The reference stops
+ * at the 1000 classes; a MobileNet behind a C-ABI is used as often for its pooled vector (layer 28), compared with a gallery of stored vectors.
+ * mbn_similarity_topk_f32 gives the k best gallery rows per query in one fused pass: an fp32 MFMA GEMM whose epilogue is a running top-k. The
+ * product [Q][G] is never in memory, and 2k values per query cross PCIe.
+ *   queries [Q][D] fp32, gallery [G][D] fp32, q_scale NULL or [Q] fp32, g_scale NULL or [G] fp32;
+ *   topk_idx [Q][k] int32, topk_score [Q][k] fp32, best first; workspace: mbn_similarity_workspace_bytes(Q, G, D, k) bytes. Device pointers.
+ * The arithmetic, normative:
+ *   dot[q][g] = sum_d queries[q][d] * gallery[g][d] on v_mfma_f32_32x32x2_f32, in a d order and grouping that are FIXED by D alone: the sum runs
+ *       over t = 0 .. ceil(D / 32) - 1, g = 0..3, s = 0..3, one instruction adding the two products at d = 32 t + 8 g + s and at d + 4 to the
+ *       accumulator (elements past D are zeros on both sides). It does not depend on Q, G, the tile or gallery chunk a pair falls in, or the
+ *       planning CU count. Such a sum is not an fmaf chain (mbn_f32_pw.hip), so this header gives a bound and not bits. With u = 2^-24: each of
+ *       the D products is rounded at most once, and on its way into the result a product passes at most D additions (two per instruction that
+ *       follows, whatever the order inside one), each rounding once; adding a zero is exact. A term so carries at most D + 1 factors (1 + e),
+ *       |e| <= u, and (1 + u)^(D+1) - 1 <= (D + 2) u for every D of the envelope (only the first instruction's terms pass all D additions), so
+ *           |dot - dot64| <= (D + 2) * 2^-24 * sum_d |q_d * g_d|                        (absent underflow; dot64 = the exact sum)
+ *   score = fmul(fmul(dot, q_scale[q]), g_scale[g]), in that order; a NULL scale skips its multiply. Inverse norms give the cosine, NULL / NULL
+ *       the inner product; a squared-distance ranking (g_scale = -1 on pre-combined norms) is left to callers. Two more roundings:
+ *           |score - score64| <= (D + 4) * 2^-24 * |q_scale * g_scale| * sum_d |q_d * g_d|
+ *   ranking: the total order of mbn_softmax_f32's contract: score descending, gallery index ascending; a NaN score is never ranked; -inf ranks
+ *       last in index order; the slots past the ranked entries (G < k, or fewer than k scores that are not NaN) hold index -1 and score 0.
+ *   rows: a query is answered by itself: the other rows' bytes do not depend on it.
+ * A pair's score bits and the order are both independent of how the gallery is split among workgroups, so the output bytes are the same at every
+ * planning CU count (mbn_set_planning_cus) and on every replay of a captured graph (two kernels on `stream`, nothing else).
+ * NULL ctx / outputs / queries / gallery / workspace, a non-positive size, k outside 1 .. 8, outputs or scales off 4 bytes: MBN_EINVAL. D off 4,
+ * below 4 or above 4096, Q * D * 4 >= 2^31, G * D * 4 >= 2^32 (larger galleries: a follow-up, the kernel already addresses each 128-row panel
+ * from a 64-bit base), ceil(Q / q_tile) * ceil(G / g_tile) >= 2^31 work units, queries / gallery / workspace off 16 bytes: MBN_EUNSUPPORTED.
+ *   mbn_similarity_tile             the constants of a launch: q_tile queries x g_tile gallery rows per work unit (a function of Q and D alone)
+ *   mbn_similarity_workspace_bytes  ceil(G / g_tile) * Q * k * 8; 0 for arguments outside the envelope
+ *   mbn_row_inv_norm_f32   out[n] = 1 / sqrt(sum_d x[n][d]^2), one wave per row with 16-byte loads; a row of zeros gives 0, so its scores are 0
+ *       and not NaN. The sum is an fmaf chain per lane and a fold of 64 partial sums: at most D roundings on non-negative terms, then a
+ *       correctly rounded sqrt (halves the sum's relative error, adds u) and a correctly rounded division (adds u):
+ *           |out - out64| <= (D + 4) * 2^-24 * out64        (D / 2 + 2 to first order; absent overflow and underflow of the sum)
+ *   mbn_embed_rows         rows stored as fp32 (MBN_DT_F32) or bf16 (MBN_DT_BF16), a layer-28 output in either mode, to out_f32 [N][D] (exact)
+ *       and inv_norm (may be NULL) as above, in one pass. MBN_DT_I8: MBN_EUNSUPPORTED (the activation scale would be needed: a follow-up).
+ *   Both: D % 4 == 0, D <= 4096, x / in / out_f32 on 16 bytes (bf16 in: 8), else MBN_EUNSUPPORTED; NULL or a non-positive size: MBN_EINVAL. */
+#define MBN_SIMILARITY_MAX_K 8
+#define MBN_SIMILARITY_MAX_D 4096
+int mbn_similarity_tile(int *q_tile, int *g_tile, int Q, int D);
+size_t mbn_similarity_workspace_bytes(int Q, int G, int D, int k);
+int mbn_similarity_topk_f32(mbn_context *ctx, void *topk_idx_i32, void *topk_score_f32, const void *queries, const void *gallery,
+                            const void *q_scale, const void *g_scale, int Q, int G, int D, int k, void *workspace, void *stream);
+int mbn_row_inv_norm_f32(mbn_context *ctx, void *out, const void *x, int N, int D, void *stream);
+int mbn_embed_rows(mbn_context *ctx, void *out_f32, void *inv_norm, const void *in, int dtype, int N, int D, void *stream);
+
 /* Input front-end on device: uint8 HWC [N][rows][cols][3] -> fp32 NHWC x*scale+bias
  * (Keras MobileNet preprocessing is scale=1/127.5, bias=-1). */
 int mbn_normalize_u8_to_f32(mbn_context *ctx, void *out_f32, const void *in_u8, size_t count, float scale,
@@ -1691,6 +1735,17 @@ int  mbn_net_forward(mbn_net *net, const void *images, void *logits, int batch, 
  * net's own logits buffer): topk_idx [batch][k] int32, topk_prob [batch][k] fp32, device pointers. What MobileNet.c:2744-2792
  * does with a 1000-byte D2H and a host loop, with 2k values per image to download. */
 int  mbn_net_classify(mbn_net *net, const void *images, int batch, int k, void *topk_idx_i32, void *topk_prob_f32);
+/* The network as a feature extractor ("Nearest neighbours" above). P = the pool in front of the FC (layer 28), D its channels.
+ *   mbn_net_embed    mbn_net_forward(net, images, ., batch, P) into a buffer of the net, then mbn_embed_rows from mbn_net_layer_output(net, P):
+ *                    emb_f32 [batch][D] fp32 and inv_norm (may be NULL) [batch], device pointers, in fp32 and bf16 mode.
+ *   mbn_net_nearest  mbn_net_embed into buffers of the net, then mbn_similarity_topk_f32 with q_scale = those inverse norms: the k best rows
+ *                    of gallery [G][D] fp32 per image, idx [batch][k] int32 and score [batch][k] fp32 (the cosine when g_scale [G] holds the
+ *                    gallery's inverse norms; NULL: the gallery rows are taken as normalised). The workspace is the net's, grown on demand.
+ * MBN_EUNSUPPORTED in I8 mode (the activation scale would be needed: a follow-up) and for a plan without the pool in front of its last layer;
+ * otherwise the statuses of the calls named. */
+int  mbn_net_embed(mbn_net *net, const void *images, int batch, void *emb_f32, void *inv_norm_f32);
+int  mbn_net_nearest(mbn_net *net, const void *images, int batch, const void *gallery_f32, const void *g_scale_f32, int G, int k, void *idx_i32,
+                     void *score_f32);
 /* Dense head (fully-convolutional MobileNet-V1; with a trained 1x1 conv_preds a DeepLab-style head): the classifier applied at EVERY pixel of the
  * last feature map instead of its average. For a plan whose last two layers are the pool and the FC (every plan of mbn_plan_build*), F = the layer
  * in front of the pool (27), h x w its output map:
