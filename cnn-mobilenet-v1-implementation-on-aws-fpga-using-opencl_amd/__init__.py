@@ -303,6 +303,11 @@ def _declare_host(lib):
     lib.mbn_similarity_tile.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int]                # mbn.h
     lib.mbn_similarity_workspace_bytes.argtypes = [C.c_int] * 4
     lib.mbn_similarity_workspace_bytes.restype = C.c_size_t
+    lib.mbn_similarity_envelope_bf16.argtypes = [C.c_int] * 4
+    lib.mbn_embed_envelope_bf16.argtypes = [C.c_int] * 3
+    lib.mbn_similarity_tile_bf16.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int]           # mbn.h
+    lib.mbn_similarity_workspace_bytes_bf16.argtypes = [C.c_int] * 4
+    lib.mbn_similarity_workspace_bytes_bf16.restype = C.c_size_t
     lib.mbn_components_envelope.argtypes = [C.c_int] * 7
     lib.mbn_components_tile.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.mbn_components_scratch_bytes.argtypes = [C.c_int, C.c_int64]
@@ -452,6 +457,10 @@ def load():
         lib.mbn_embed_rows.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp]
         lib.mbn_net_embed.argtypes = [vp, vp, ci, vp, vp]
         lib.mbn_net_nearest.argtypes = [vp, vp, ci, vp, vp, ci, ci, vp, vp]
+        lib.mbn_similarity_topk_bf16.argtypes = [vp] * 7 + [ci] * 4 + [vp, vp]
+        lib.mbn_embed_rows_bf16.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp]
+        lib.mbn_net_embed_bf16.argtypes = [vp, vp, ci, vp, vp]
+        lib.mbn_net_nearest_bf16.argtypes = [vp, vp, ci, vp, vp, ci, ci, vp, vp]
         lib.mbn_classifier_tail.argtypes = [vp] * 9 + [ci] * 6 + [vp]
         lib.mbn_upsample_argmax_f32.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
         lib.mbn_net_forward_dense.argtypes = [vp, vp, vp, ci]
@@ -871,6 +880,23 @@ def similarity_tile(Q, D, lib=None):
 def similarity_workspace_bytes(Q, G, D, k, lib=None) -> int:
     """mbn_similarity_workspace_bytes: the device memory Context.similarity_topk needs as `workspace` (0: a shape it refuses)."""
     return (lib or host_lib()).mbn_similarity_workspace_bytes(Q, G, D, k)
+
+
+def similarity_envelope_bf16(Q, G, D, k, lib=None) -> int:
+    """mbn_similarity_envelope_bf16: the status Context.similarity_topk_bf16 gives the shape (D % 8, G * D * 2 < 2^32)."""
+    return (lib or host_lib()).mbn_similarity_envelope_bf16(Q, G, D, k)
+
+
+def similarity_tile_bf16(Q, D, lib=None):
+    """mbn_similarity_tile_bf16: (q_tile, g_tile) of one work unit of the search on a bf16 gallery; a function of Q and D alone."""
+    qt, gt = C.c_int(), C.c_int()
+    _chk((lib or host_lib()).mbn_similarity_tile_bf16(C.byref(qt), C.byref(gt), Q, D), "similarity_tile_bf16")
+    return qt.value, gt.value
+
+
+def similarity_workspace_bytes_bf16(Q, G, D, k, lib=None) -> int:
+    """mbn_similarity_workspace_bytes_bf16: the device memory Context.similarity_topk_bf16 needs as `workspace` (0: a shape it refuses)."""
+    return (lib or host_lib()).mbn_similarity_workspace_bytes_bf16(Q, G, D, k)
 
 
 def softmax_readout_check(have_prob, min_prob, lib=None) -> int:
@@ -1418,6 +1444,17 @@ class Context:
         """mbn_embed_rows: rows [N][D] stored as fp32 or bf16 (DT_F32 / DT_BF16) -> out_f32 [N][D] and inv_norm [N] (may be None), one pass."""
         _chk(self.lib.mbn_embed_rows(self.h, out_f32, inv_norm, rows, dtype, N, D, None), self.last_error())
 
+    def similarity_topk_bf16(self, topk_idx, topk_score, queries, gallery_bf16, Q, G, D, k, workspace, q_scale=None, g_scale=None):
+        """mbn_similarity_topk_bf16: similarity_topk on a gallery [G][D] stored as bf16; the fp32 queries are split exactly into three bf16 planes.
+        workspace of similarity_workspace_bytes_bf16(Q, G, D, k); D % 8 == 0."""
+        _chk(self.lib.mbn_similarity_topk_bf16(self.h, topk_idx, topk_score, queries, gallery_bf16, q_scale, g_scale, Q, G, D, k, workspace, None),
+             self.last_error())
+
+    def embed_rows_bf16(self, out_bf16, inv_norm, rows, dtype, N, D):
+        """mbn_embed_rows_bf16: rows [N][D] stored as fp32 or bf16 -> out_bf16 [N][D] bf16 (round to nearest even) and inv_norm [N] of the ROUNDED
+        rows (either may be None): what a bf16 gallery stores."""
+        _chk(self.lib.mbn_embed_rows_bf16(self.h, out_bf16, inv_norm, rows, dtype, N, D, None), self.last_error())
+
     def resample_ensemble(self, labels, prob, score, logits, batch, rows, cols, classes, in_rows, in_cols, view_list, out_rows, out_cols,
                           min_prob=0.0, ignore_label=0, n_views=None):
         """mbn_resample_ensemble_f32: ONE read-out of the views in view_list (View objects or (x, y, iw, ih, mirror)) over view-major logits
@@ -1873,13 +1910,17 @@ class Net:
     def classify(self, images_dev, batch, k, topk_idx_dev, topk_prob_dev):
         _chk(self.ctx.lib.mbn_net_classify(self.h, images_dev, batch, k, topk_idx_dev, topk_prob_dev), self.ctx.last_error())
 
-    def embed(self, images_dev, batch, emb_dev, inv_norm_dev=None):
-        """mbn_net_embed: the pooled vector of every image (the layer in front of the FC) as fp32 rows emb [batch][D], and their inverse norms."""
-        _chk(self.ctx.lib.mbn_net_embed(self.h, images_dev, batch, emb_dev, inv_norm_dev), self.ctx.last_error())
+    def embed(self, images_dev, batch, emb_dev, inv_norm_dev=None, gallery_dtype=DT_F32):
+        """mbn_net_embed: the pooled vector of every image (the layer in front of the FC) as fp32 rows emb [batch][D], and their inverse norms.
+        gallery_dtype=DT_BF16 (mbn_net_embed_bf16): bf16 rows, as a bf16 gallery stores them, and the inverse norms of those."""
+        fn = self.ctx.lib.mbn_net_embed_bf16 if gallery_dtype == DT_BF16 else self.ctx.lib.mbn_net_embed
+        _chk(fn(self.h, images_dev, batch, emb_dev, inv_norm_dev), self.ctx.last_error())
 
-    def nearest(self, images_dev, batch, gallery_dev, G, k, idx_dev, score_dev, g_scale_dev=None):
-        """mbn_net_nearest: embed, then the k gallery rows [G][D] nearest by cosine per image (g_scale: the gallery's inverse norms, None = 1)."""
-        _chk(self.ctx.lib.mbn_net_nearest(self.h, images_dev, batch, gallery_dev, g_scale_dev, G, k, idx_dev, score_dev), self.ctx.last_error())
+    def nearest(self, images_dev, batch, gallery_dev, G, k, idx_dev, score_dev, g_scale_dev=None, gallery_dtype=DT_F32):
+        """mbn_net_nearest: embed, then the k gallery rows [G][D] nearest by cosine per image (g_scale: the gallery's inverse norms, None = 1).
+        gallery_dtype=DT_BF16 (mbn_net_nearest_bf16): the gallery is stored as bf16."""
+        fn = self.ctx.lib.mbn_net_nearest_bf16 if gallery_dtype == DT_BF16 else self.ctx.lib.mbn_net_nearest
+        _chk(fn(self.h, images_dev, batch, gallery_dev, g_scale_dev, G, k, idx_dev, score_dev), self.ctx.last_error())
 
     def forward_dense(self, images_ptr, out_ptr, batch):
         """The FC at every pixel of the map in front of the pool: out [batch][h][w][classes] fp32 (mbn_net_forward_dense)."""

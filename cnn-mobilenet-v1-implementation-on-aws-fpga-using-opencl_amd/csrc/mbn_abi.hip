@@ -889,6 +889,39 @@ int mbn_row_inv_norm_f32(mbn_context *ctx, void *out, const void *x, int N, int 
     return mbn_embed_rows(ctx, nullptr, out, x, MBN_DT_F32, N, D, stream);
 }
 
+// ... on a bf16 gallery (mbn_bf16_similarity.hip): the same order of statuses
+int mbn_similarity_topk_bf16(mbn_context *ctx, void *topk_idx_i32, void *topk_score_f32, const void *queries, const void *gallery_bf16,
+                             const void *q_scale, const void *g_scale, int Q, int G, int D, int k, void *workspace, void *stream)
+{
+    if (!ctx || !topk_idx_i32 || !topk_score_f32 || !queries || !gallery_bf16 || !workspace) return MBN_EINVAL;
+    if (((uintptr_t)topk_idx_i32 | (uintptr_t)topk_score_f32 | (uintptr_t)q_scale | (uintptr_t)g_scale) % 4) return MBN_EINVAL;
+    const int shape = mbn_similarity_envelope_bf16(Q, G, D, k);
+    if (shape != MBN_OK) return shape;
+    if (((uintptr_t)queries | (uintptr_t)gallery_bf16 | (uintptr_t)workspace) % 16) return MBN_EUNSUPPORTED;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    MBN_SPANS(ctx, { queries, 4.0 * Q * D, "similarity queries" }, { gallery_bf16, 2.0 * G * D, "similarity bf16 gallery" },
+              { q_scale, 4.0 * Q, "similarity q_scale" }, { g_scale, 4.0 * G, "similarity g_scale" },
+              { topk_idx_i32, 4.0 * Q * k, "similarity idx" }, { topk_score_f32, 4.0 * Q * k, "similarity score" },
+              { workspace, (double)mbn_similarity_workspace_bytes_bf16(Q, G, D, k), "similarity bf16 workspace" });
+    Scope sc(ctx, s);
+    return sc.finish(mbn_launch_bf16_similarity_topk(ctx, s, (int32_t *)topk_idx_i32, (float *)topk_score_f32, (const float *)queries, gallery_bf16,
+                                                     (const float *)q_scale, (const float *)g_scale, Q, G, D, k, workspace));
+}
+
+int mbn_embed_rows_bf16(mbn_context *ctx, void *out_bf16, void *inv_norm, const void *in, int dtype, int N, int D, void *stream)
+{
+    if (!ctx || !in || (!out_bf16 && !inv_norm)) return MBN_EINVAL;
+    if ((uintptr_t)inv_norm % 4) return MBN_EINVAL;
+    const int shape = mbn_embed_envelope_bf16(N, D, dtype);
+    if (shape != MBN_OK) return shape;
+    const double esz = dtype == MBN_DT_BF16 ? 2.0 : 4.0;
+    if (((uintptr_t)out_bf16 | (uintptr_t)in) % 16) return MBN_EUNSUPPORTED;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    MBN_SPANS(ctx, { in, esz * N * D, "embed rows in" }, { out_bf16, 2.0 * N * D, "embed rows bf16 out" }, { inv_norm, 4.0 * N, "embed rows inv_norm" });
+    Scope sc(ctx, s);
+    return sc.finish(mbn_launch_rows_pack_bf16(ctx, s, out_bf16, (float *)inv_norm, in, dtype, N, D));
+}
+
 int mbn_upsample_argmax_f32(mbn_context *ctx, void *labels_i32, void *score_f32, const void *logits, int batch, int rows, int cols, int classes,
                             int factor, void *stream)
 {

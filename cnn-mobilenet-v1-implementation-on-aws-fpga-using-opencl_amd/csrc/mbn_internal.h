@@ -407,6 +407,12 @@ int mbn_launch_f32_resample_groups(mbn_context *ctx, hipStream_t s, const mbn_cl
 int mbn_launch_f32_similarity_topk(mbn_context *ctx, hipStream_t s, int32_t *idx, float *score, const float *queries, const float *gallery,
                                    const float *q_scale, const float *g_scale, int Q, int G, int D, int k, void *workspace);
 int mbn_launch_rows_norm(mbn_context *ctx, hipStream_t s, float *out, float *inv_norm, const void *in, int dtype, int N, int D);
+// ... on a bf16 gallery (mbn_bf16_similarity.hip): the query split, the fused bf16 MFMA GEMM + top-k and the chunk merge, three launches on s,
+// inside mbn_similarity_envelope_bf16 with `workspace` of mbn_similarity_workspace_bytes_bf16; the packing pass of mbn_embed_rows_bf16 inside
+// mbn_embed_envelope_bf16 (out or inv_norm may be null). Pointers checked by the callers
+int mbn_launch_bf16_similarity_topk(mbn_context *ctx, hipStream_t s, int32_t *idx, float *score, const float *queries, const void *gallery,
+                                    const float *q_scale, const float *g_scale, int Q, int G, int D, int k, void *workspace);
+int mbn_launch_rows_pack_bf16(mbn_context *ctx, hipStream_t s, void *out, float *inv_norm, const void *in, int dtype, int N, int D);
 // rank score (mbn_i32_topk_rank.hip): ranks [classes + 1][k + 1] uint64 += per truth row the rank at which the truth is among the k label planes
 // (plane j at j * plane_stride elements). The arguments are inside mbn_topk_rank_envelope and the pointers checked
 int mbn_launch_i32_topk_rank(mbn_context *ctx, hipStream_t s, void *ranks, const void *labels, int k, int64_t plane_stride, const void *truth,

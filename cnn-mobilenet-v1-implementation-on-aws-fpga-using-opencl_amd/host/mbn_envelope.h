@@ -114,6 +114,12 @@ int mbn_similarity_envelope(int Q, int G, int D, int k);
 /* mbn_row_inv_norm_f32 (dtype MBN_DT_F32) and mbn_embed_rows: MBN_EINVAL for a non-positive size; else MBN_EUNSUPPORTED for a dtype other than
  * fp32 and bf16, for D off 4 or above MBN_SIMILARITY_MAX_D */
 int mbn_embed_envelope(int N, int D, int dtype);
+/* mbn_similarity_topk_bf16: as mbn_similarity_envelope with D off 8 (MBN_EUNSUPPORTED) in place of D off 4 and G * D * 2 >= 2^32 in place of
+ * G * D * 4 >= 2^32, the work units counted with mbn_similarity_tile_bf16. mbn_embed_rows_bf16: as mbn_embed_envelope with D off 8 */
+int mbn_similarity_envelope_bf16(int Q, int G, int D, int k);
+int mbn_embed_envelope_bf16(int N, int D, int dtype);
+/* where the queries' split image starts in the workspace of mbn_similarity_topk_bf16 (a multiple of 16; 0 outside the envelope) */
+size_t mbn_similarity_split_offset_bf16(int Q, int G, int D, int k);
 /* mbn_resample_ragged_check for the items of mbn_ragged_readout_set_window: the same statuses, overlap sort and scratch, every item under
  * mbn_resample_window_envelope with its own rectangle; *l is written only when the batch is accepted */
 int mbn_resample_ragged_window_check(int rows, int cols, int classes, int in_rows, int in_cols, const mbn_label_window_item *items, int batch,

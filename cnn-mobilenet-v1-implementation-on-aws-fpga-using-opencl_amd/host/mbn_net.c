@@ -802,10 +802,11 @@ int mbn_net_classify(mbn_net *net, const void *images, int batch, int k, void *t
     return mbn_softmax_topk_f32(net->ctx, NULL, topk_idx_i32, topk_prob_f32, net->logits_buf, batch, fc->out_ch, k, NULL);
 }
 
-/* Feature extractor: layers 1 .. pool into the net's own buffer (bf16 mode stores bf16 there), then the rows widened and their inverse norms */
-int mbn_net_embed(mbn_net *net, const void *images, int batch, void *emb_f32, void *inv_norm_f32)
+/* Feature extractor: layers 1 .. pool into the net's own buffer (bf16 mode stores bf16 there), then the rows widened (out_dtype MBN_DT_F32) or
+ * packed to bf16 (MBN_DT_BF16) and their inverse norms */
+static int net_embed(mbn_net *net, const void *images, int batch, void *emb, void *inv_norm_f32, int out_dtype)
 {
-    if (!net || !images || !emb_f32 || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
+    if (!net || !images || !emb || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
     const int pool = net->plan.n_layers - 1;                  /* 1-based index of the layer in front of the FC */
     if (net->dtype == MBN_DT_I8 || pool < 1 || net->plan.layer[pool - 1].kind != MBN_L_POOL) return MBN_EUNSUPPORTED;
     const int D = net->plan.layer[pool - 1].out_ch;
@@ -815,21 +816,34 @@ int mbn_net_embed(mbn_net *net, const void *images, int batch, void *emb_f32, vo
     void *rows = NULL;
     if (rc == MBN_OK) rc = mbn_net_layer_output(net, pool, &rows, NULL);
     if (rc != MBN_OK) return rc;
-    return mbn_embed_rows(net->ctx, emb_f32, inv_norm_f32, rows, net->dtype, batch, D, NULL);
+    if (out_dtype == MBN_DT_BF16) return mbn_embed_rows_bf16(net->ctx, emb, inv_norm_f32, rows, net->dtype, batch, D, NULL);
+    return mbn_embed_rows(net->ctx, emb, inv_norm_f32, rows, net->dtype, batch, D, NULL);
 }
 
-int mbn_net_nearest(mbn_net *net, const void *images, int batch, const void *gallery_f32, const void *g_scale_f32, int G, int k, void *idx_i32,
-                    void *score_f32)
+int mbn_net_embed(mbn_net *net, const void *images, int batch, void *emb_f32, void *inv_norm_f32)
 {
-    if (!net || !images || !gallery_f32 || !idx_i32 || !score_f32 || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
+    return net_embed(net, images, batch, emb_f32, inv_norm_f32, MBN_DT_F32);
+}
+
+int mbn_net_embed_bf16(mbn_net *net, const void *images, int batch, void *emb_bf16, void *inv_norm_f32)
+{
+    return net_embed(net, images, batch, emb_bf16, inv_norm_f32, MBN_DT_BF16);
+}
+
+/* the queries are fp32 rows in either case; gallery_dtype chooses the search */
+static int net_nearest(mbn_net *net, const void *images, int batch, const void *gallery, int gallery_dtype, const void *g_scale_f32, int G, int k,
+                       void *idx_i32, void *score_f32)
+{
+    if (!net || !images || !gallery || !idx_i32 || !score_f32 || batch <= 0 || batch > net->max_batch) return MBN_EINVAL;
     const int pool = net->plan.n_layers - 1;
     if (net->dtype == MBN_DT_I8 || pool < 1 || net->plan.layer[pool - 1].kind != MBN_L_POOL) return MBN_EUNSUPPORTED;
     const int D = net->plan.layer[pool - 1].out_ch;
-    int rc = mbn_similarity_envelope(batch, G, D, k);
+    const int bf16 = gallery_dtype == MBN_DT_BF16;
+    int rc = bf16 ? mbn_similarity_envelope_bf16(batch, G, D, k) : mbn_similarity_envelope(batch, G, D, k);
     if (rc != MBN_OK) return rc;
     const size_t emb_bytes = (size_t)net->max_batch * D * sizeof(float);       /* the rows (a multiple of 16 bytes), then their inverse norms */
     if (!net->near_emb) rc = mbn_alloc(net->ctx, emb_bytes + (size_t)net->max_batch * sizeof(float), &net->near_emb);
-    const size_t need = mbn_similarity_workspace_bytes(batch, G, D, k);
+    const size_t need = bf16 ? mbn_similarity_workspace_bytes_bf16(batch, G, D, k) : mbn_similarity_workspace_bytes(batch, G, D, k);
     if (rc == MBN_OK && need > net->near_ws_bytes) {          /* grown on demand; mbn_free waits for the launches that use the old one */
         if (net->near_ws) mbn_free(net->ctx, net->near_ws);
         net->near_ws = NULL;
@@ -841,7 +855,20 @@ int mbn_net_nearest(mbn_net *net, const void *images, int batch, const void *gal
     void *inv = (char *)net->near_emb + emb_bytes;
     rc = mbn_net_embed(net, images, batch, net->near_emb, inv);
     if (rc != MBN_OK) return rc;
-    return mbn_similarity_topk_f32(net->ctx, idx_i32, score_f32, net->near_emb, gallery_f32, inv, g_scale_f32, batch, G, D, k, net->near_ws, NULL);
+    if (bf16) return mbn_similarity_topk_bf16(net->ctx, idx_i32, score_f32, net->near_emb, gallery, inv, g_scale_f32, batch, G, D, k, net->near_ws, NULL);
+    return mbn_similarity_topk_f32(net->ctx, idx_i32, score_f32, net->near_emb, gallery, inv, g_scale_f32, batch, G, D, k, net->near_ws, NULL);
+}
+
+int mbn_net_nearest(mbn_net *net, const void *images, int batch, const void *gallery_f32, const void *g_scale_f32, int G, int k, void *idx_i32,
+                    void *score_f32)
+{
+    return net_nearest(net, images, batch, gallery_f32, MBN_DT_F32, g_scale_f32, G, k, idx_i32, score_f32);
+}
+
+int mbn_net_nearest_bf16(mbn_net *net, const void *images, int batch, const void *gallery_bf16, const void *g_scale_f32, int G, int k,
+                         void *idx_i32, void *score_f32)
+{
+    return net_nearest(net, images, batch, gallery_bf16, MBN_DT_BF16, g_scale_f32, G, k, idx_i32, score_f32);
 }
 
 /* the dense head's layers: *feat = the layer in front of the pool, *fc = the FC; MBN_EUNSUPPORTED for a plan that does not end in pool, FC */

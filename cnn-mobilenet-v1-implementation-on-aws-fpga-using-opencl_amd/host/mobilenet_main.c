@@ -44,6 +44,9 @@
  *   several) is APPENDED to FILE, D little-endian floats per row, so runs over a folder build a gallery. --gallery FILE --nearest K (together,
  *   1 <= K <= 8, else usage status 2): FILE is such a file, G = its size / 4D rows; prints per image the K rows nearest by cosine, index and
  *   cosine (mbn_row_inv_norm_f32 on the gallery, then mbn_net_nearest). A file that is not whole rows of D floats: status 2
+ *   --embed-dtype bf16 / --gallery-dtype bf16 (f32: the default; anything else: usage status 2): FILE holds D bf16 values per row, the upper halves
+ *   of the floats rounded to nearest even (mbn_net_embed_bf16 writes them, mbn_embed_rows_bf16 gives the stored rows' norms, mbn_net_nearest_bf16
+ *   searches them): half the file and half the device memory of the gallery
  *   --slide TH[xTW] [--slide-stride SH[xSW]] (with ONE --ppm and --segment-source; rows x columns): sliding-window segmentation,
  *   mbn_net_segment_slide: overlapping TH x TW crops of the image, each stretched to the network's input, and ONE read-out that averages the crops'
  *   logits where they overlap. The default stride is (2 * tile + 2) / 3 per axis. The fit is the stretch: with --fit pad or --fit crop, or with
@@ -1147,31 +1150,34 @@ static int filter_of(const char *name)
 /* --embed-out FILE: the pooled vector of each of the first n images (mbn_net_embed) appended to FILE as D little-endian floats per row.
  * --gallery FILE --nearest K: FILE is such a file (G = its size / 4D); the K rows nearest by cosine per image (mbn_net_nearest with the gallery's
  * inverse norms from mbn_row_inv_norm_f32). 0, 1 for a device error, 2 for a file that cannot be written or is not whole rows of D floats */
-static int embed_and_nearest(mbn_context *ctx, mbn_net *net, const void *d_images, int n, int D, const char *embed_out, const char *gallery_path, int k)
+static int embed_and_nearest(mbn_context *ctx, mbn_net *net, const void *d_images, int n, int D, const char *embed_out, int embed_bf16,
+                             const char *gallery_path, int gallery_bf16, int k)
 {
     void *d_emb = NULL;
     if (embed_out) {
-        float *emb = malloc(sizeof(float) * (size_t)n * D);
+        const size_t esz = embed_bf16 ? 2 : sizeof(float);
+        void *emb = malloc(esz * (size_t)n * D);
         FILE *f = fopen(embed_out, "ab");
         if (!emb || !f) { fprintf(stderr, "--embed-out %s: cannot append\n", embed_out); return 2; }
-        CHECK(mbn_alloc(ctx, sizeof(float) * (size_t)n * D, &d_emb));
-        CHECK(mbn_net_embed(net, d_images, n, d_emb, NULL));
-        CHECK(mbn_download(ctx, emb, d_emb, sizeof(float) * (size_t)n * D));
+        CHECK(mbn_alloc(ctx, esz * (size_t)n * D, &d_emb));
+        if (embed_bf16) CHECK(mbn_net_embed_bf16(net, d_images, n, d_emb, NULL));
+        else CHECK(mbn_net_embed(net, d_images, n, d_emb, NULL));
+        CHECK(mbn_download(ctx, emb, d_emb, esz * (size_t)n * D));
         CHECK(mbn_free(ctx, d_emb));
-        const int bad = fwrite(emb, sizeof(float) * (size_t)D, (size_t)n, f) != (size_t)n;
+        const int bad = fwrite(emb, esz * (size_t)D, (size_t)n, f) != (size_t)n;
         if (fclose(f) || bad) { fprintf(stderr, "--embed-out %s: short write\n", embed_out); return 2; }
-        printf("embed: %d row%s of %d floats appended to %s\n", n, n == 1 ? "" : "s", D, embed_out);
+        printf("embed: %d row%s of %d %s appended to %s\n", n, n == 1 ? "" : "s", D, embed_bf16 ? "bf16 values" : "floats", embed_out);
         free(emb);
     }
     if (!gallery_path) return 0;
     FILE *f = fopen(gallery_path, "rb");
     long bytes = -1;
     if (f && !fseek(f, 0, SEEK_END)) bytes = ftell(f);
-    const size_t row = sizeof(float) * (size_t)D;
-    float *g = bytes > 0 && bytes % (long)row == 0 ? malloc((size_t)bytes) : NULL;
+    const size_t row = (gallery_bf16 ? 2 : sizeof(float)) * (size_t)D;
+    void *g = bytes > 0 && bytes % (long)row == 0 ? malloc((size_t)bytes) : NULL;
     if (g) rewind(f);
     if (!g || fread(g, 1, (size_t)bytes, f) != (size_t)bytes || bytes / (long)row > 0x7fffffffL) {
-        fprintf(stderr, "--gallery %s: not a readable file of whole rows of %d floats\n", gallery_path, D);
+        fprintf(stderr, "--gallery %s: not a readable file of whole rows of %d %s\n", gallery_path, D, gallery_bf16 ? "bf16 values" : "floats");
         return 2;
     }
     fclose(f);
@@ -1186,8 +1192,13 @@ static int embed_and_nearest(mbn_context *ctx, mbn_net *net, const void *d_image
     CHECK(mbn_alloc(ctx, sizeof(sc), &d_sc));
     CHECK(mbn_upload(ctx, d_g, g, (size_t)bytes));
     free(g);
-    CHECK(mbn_row_inv_norm_f32(ctx, d_gs, d_g, G, D, NULL));
-    CHECK(mbn_net_nearest(net, d_images, n, d_g, d_gs, G, k, d_idx, d_sc));
+    if (gallery_bf16) {
+        CHECK(mbn_embed_rows_bf16(ctx, NULL, d_gs, d_g, MBN_DT_BF16, G, D, NULL));
+        CHECK(mbn_net_nearest_bf16(net, d_images, n, d_g, d_gs, G, k, d_idx, d_sc));
+    } else {
+        CHECK(mbn_row_inv_norm_f32(ctx, d_gs, d_g, G, D, NULL));
+        CHECK(mbn_net_nearest(net, d_images, n, d_g, d_gs, G, k, d_idx, d_sc));
+    }
     CHECK(mbn_download(ctx, idx, d_idx, sizeof(int32_t) * (size_t)n * k));
     CHECK(mbn_download(ctx, sc, d_sc, sizeof(float) * (size_t)n * k));
     for (int i = 0; i < n; i++) {
@@ -1219,7 +1230,7 @@ int main(int argc, char **argv)
     const char *temperatures = NULL;
     const char *tta = NULL, *slide_arg = NULL, *slide_stride_arg = NULL, *groups_path = NULL;
     const char *embed_out = NULL, *gallery_path = NULL;
-    int nearest_k = 0, have_nearest = 0;
+    int nearest_k = 0, have_nearest = 0, embed_bf16 = 0, gallery_bf16 = 0, bad_dtype = 0;
     int fit_given = 0, slide[4] = { 0, 0, 0, 0 }, slide_tiles = 0;     /* slide: tile rows, tile columns, stride rows, stride columns */
     region_opts regions = { 0, 4, 1, 256 };
     int region_flags = 0;                                       /* --connectivity, --min-area or --max-regions seen */
@@ -1255,6 +1266,11 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--embed-out") && i + 1 < argc) embed_out = argv[++i];
         else if (!strcmp(argv[i], "--gallery") && i + 1 < argc) gallery_path = argv[++i];
         else if (!strcmp(argv[i], "--nearest") && i + 1 < argc) { nearest_k = atoi(argv[++i]); have_nearest = 1; }
+        else if ((!strcmp(argv[i], "--embed-dtype") || !strcmp(argv[i], "--gallery-dtype")) && i + 1 < argc) {
+            int *bf16 = argv[i][2] == 'e' ? &embed_bf16 : &gallery_bf16;
+            *bf16 = !strcmp(argv[++i], "bf16");
+            if (!*bf16 && strcmp(argv[i], "f32")) bad_dtype = 1;
+        }
         else if (!strcmp(argv[i], "--guided") && i + 1 < argc) { guided = (float)atof(argv[++i]); have_guided = 1; }
         else if (!strcmp(argv[i], "--segment-topk") && i + 1 < argc) { segment_topk = atoi(argv[++i]); have_topk = 1; }
         else if (!strcmp(argv[i], "--min-confidence") && i + 1 < argc) { min_conf = (float)atof(argv[++i]); have_min_conf = 1; }
@@ -1300,7 +1316,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--ref-args")) ref_args = 1;
         else {
             fprintf(stderr, "usage: %s [--h5 F | --synthetic SEED | --literal] [--ppm F ... [--fit crop|stretch|pad] [--crop-fraction F] [--pad-color R,G,B] [--filter nearest|box|bilinear|hamming|bicubic|lanczos]] [--batch N] [--res R | RxC] [--alpha A] [--output-stride 32|16|8] [--segment OUT.pgm] [--segment-source OUT.pgm [--segment-topk K] [--min-confidence P --ignore-label L] [--tta-scales S1,S2,... [--tta-flip]] [--slide TH[xTW] [--slide-stride SH[xSW]]] [--truth F.pgm ...] [--calibration BINS [--target-accuracy A]] [--nll [--temperatures T1,T2,...]] [--regions [--connectivity 4|8] [--min-area N] [--max-regions M]] [--boundary-ratio R | --boundary-d N [--boundary-edge 0|1] [--boundary-map OUT.pgm]] [--panoptic [--connectivity 4|8] [--min-area N]] [--surface [--surface-bins N] [--surface-tolerance T] [--surface-percentile P] [--surface-edge 0|1] [--surface-map OUT.pgm]]] [--segment-confidence OUT.pgm] "
-                            "[--embed-out FILE] [--gallery FILE --nearest K] [--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n"
+                            "[--embed-out FILE [--embed-dtype f32|bf16]] [--gallery FILE --nearest K [--gallery-dtype f32|bf16]] [--gpus G [--steps K] [--warmup W] [--streams S] [--pw-emul 6] [--verify]]\n"
                             "  --calibration BINS [--target-accuracy A]: with --segment-confidence and --truth, one calibration: line (reliability table "
                             "in BINS bins, ECE, MCE, AURC) and the smallest --min-confidence that reaches accuracy A; with --min-confidence P > 0 the "
                             "thresholded labels are scored, the pixels below P count as abstained\n"
@@ -1314,6 +1330,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "--gallery FILE and --nearest K (1 <= K <= %d) come together\n", MBN_SIMILARITY_MAX_K);
         return 2;
     }
+    if (bad_dtype) { fprintf(stderr, "--embed-dtype and --gallery-dtype take f32 or bf16\n"); return 2; }
     if (n_ppm > 1 && n_ppm > batch) { fprintf(stderr, "%d --ppm files need --batch %d at least\n", n_ppm, n_ppm); return 2; }
     if (n_ppm > 1 && (filter == MBN_FILTER_HAMMING || filter == MBN_FILTER_LANCZOS)) {
         fprintf(stderr, "--filter %s with several --ppm: the ragged resize forms its weights on the device, which has no sin / cos bit-equal to the host's; "
@@ -1602,7 +1619,8 @@ int main(int argc, char **argv)
     printf("\n");
     for (int n = 0; n_ppm > 1 && n < n_ppm; n++) printf("top-1 of image %d (%s): %d (%f)\n", n, ppms[n], arg[n * topk] + 1, probs[n * topk]);
     if (embed_out || gallery_path) {
-        const int bad = embed_and_nearest(ctx, net, d_u8, n_ppm > 1 ? n_ppm : 1, w.plan.layer[w.plan.n_layers - 2].out_ch, embed_out, gallery_path, nearest_k);
+        const int bad = embed_and_nearest(ctx, net, d_u8, n_ppm > 1 ? n_ppm : 1, w.plan.layer[w.plan.n_layers - 2].out_ch, embed_out, embed_bf16, gallery_path,
+                                          gallery_bf16, nearest_k);
         if (bad) return bad;
     }
     if (segment) {

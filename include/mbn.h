@@ -1272,6 +1272,49 @@ int mbn_similarity_topk_f32(mbn_context *ctx, void *topk_idx_i32, void *topk_sco
                             const void *q_scale, const void *g_scale, int Q, int G, int D, int k, void *workspace, void *stream);
 int mbn_row_inv_norm_f32(mbn_context *ctx, void *out, const void *x, int N, int D, void *stream);
 int mbn_embed_rows(mbn_context *ctx, void *out_f32, void *inv_norm, const void *in, int dtype, int N, int D, void *stream);
+/* ... on a gallery stored in 16 bits (csrc/mbn_bf16_similarity.hip): mbn_similarity_topk_bf16 is the same search with
+ *   gallery [G][D] bf16 (the upper 16 bits of an fp32 value, as the bf16 mode stores activations; g~ below is its value), queries [Q][D] fp32.
+ * It halves the gallery's memory and the bytes of a small-Q search, and puts the product on v_mfma_f32_32x32x16_bf16. Everything not named here
+ * (scales, outputs, ranking, rows, the byte equality at every planning CU count and on graph replay; three kernels on `stream`) is as above.
+ * The arithmetic, normative:
+ *   queries lose nothing: each element is split as x = h + m + l, h = bf16(x), m = bf16(x - h), l = bf16(x - h - m), round to nearest even
+ *       (csrc/mbn_x6.h), which is exact for x = 0 and for 2^-110 <= |x| < 2^127. Outside that range: below 2^-110, m or l may fall under the
+ *       normal bf16 range and be rounded there or flushed: x is taken with an absolute error below 2^-126; from 2^127, h may round to infinity, and an infinite or NaN element
+ *       gives a NaN plane (x - h): the query's scores are then infinite or NaN, and a NaN score is never ranked.
+ *   dot[q][g]: a bf16 x bf16 product has 16 significant bits and is EXACT in fp32, so dot is a sum of 3 D exact products, accumulated in fp32 by
+ *       v_mfma_f32_32x32x16_bf16 in an order FIXED by D alone: k steps s = 0 .. ceil(D / 16) - 1 in ascending d; per k step three instructions on
+ *       the one accumulator, the query planes in the order l, m, h; an instruction adds the 16 products of its plane at d = 16 s .. 16 s + 15 (the
+ *       gallery past D is zeros). It does not depend on Q, G, the tile or gallery chunk a pair falls in, or the planning CU count.
+ *   The model of the instruction this bound assumes: it forms its 16 products exactly and adds them and the accumulator in SOME order with at
+ *       most 16 roundings, one per addition, each of relative size at most u = 2^-24 of that addition's result (an addition of zero is exact).
+ *       A sum of all 17 terms rounded once, or partial sums of 2, 4 or 8 products rounded on the way, are inside it; a unit that truncates
+ *       instead of rounding (relative 2^-23 per addition) is not.
+ *       With N = 3 * 16 * ceil(D / 16) <= 3 D + 24 additions in all, a product carries at most N factors (1 + e), |e| <= u, and
+ *       (1 + u)^N - 1 <= N u (1 + N u) <= 1.00074 N u for every D of the envelope. The sum of the planes' magnitudes is at most
+ *       |x| (1 + 2^-9 + 2^-9 (1 + 2^-9) + 2^-17) <= |x| (1 + 2^-7), and the planes' exact sum is q . g~. So
+ *           |dot - dot64| <= 1.00074 (1 + 2^-7) (3 D + 24) 2^-24 sum_d |q_d g~_d|        (absent underflow; dot64 = the exact q . g~)
+ *   score = fmul(fmul(dot, q_scale[q]), g_scale[g]) as above: two more roundings, (1 + delta)(1 + u)^2 - 1 <= delta + 2.01 u. With
+ *       1.00074 * 1.0078125 * (3 D + 24) + 2.01 <= (3 D + 26)(1 + 2^-6) = B(D):
+ *           |score - score64| <= B(D) * 2^-24 * |q_scale * g_scale| * sum_d |q_d * g~_d|,   B(D) = (3 D + 26) * 1.015625
+ *       score64 = the float64 product of the fp32 queries with the STORED gallery g~ and the scales; what rounding the gallery to bf16 costs
+ *       (2^-9 relative per element) is the caller's choice and not in this bound.
+ *   ranking: the same total order. A NaN in a gallery row makes that row's every score NaN: the row is never ranked.
+ * Statuses: those of mbn_similarity_topk_f32 with three differences: D % 8 != 0 is MBN_EUNSUPPORTED (D = 4 included); the gallery pointer sits on
+ * 16 bytes like the queries and the workspace; the gallery's limit is G * D * 2 < 2^32.
+ *   mbn_similarity_tile_bf16             q_tile x g_tile of a work unit of this kernel (a function of Q and D alone)
+ *   mbn_similarity_workspace_bytes_bf16  ceil(G / g_tile) * Q * k * 8 rounded up to 16, plus the queries' split image Q * 3 * D * 2; 0 outside the envelope
+ *   mbn_embed_rows_bf16    packs a gallery: rows stored as fp32 (MBN_DT_F32) or bf16 (MBN_DT_BF16) to out_bf16 [N][D] bf16, fp32 rounded to nearest
+ *       even (a NaN stays a NaN, beyond the bf16 range: infinity), and inv_norm (either may be NULL, not both) = 1 / sqrt(sum of squares) of the
+ *       ROUNDED row, so a stored row's cosine with itself is 1 within the two bounds: |inv_norm - inv_norm64(g~)| <= (D + 4) 2^-24 inv_norm64, as
+ *       mbn_row_inv_norm_f32. D % 8 == 0, D <= 4096, in / out_bf16 on 16 bytes, fp32 or bf16 (MBN_DT_I8: a follow-up), else MBN_EUNSUPPORTED;
+ *       NULL or a non-positive size: MBN_EINVAL.
+ * Follow-ups: fp8 or int8 galleries (a scale per row and another instruction; the bound changes kind), squared distances (a fused add of the
+ * norms in the epilogue), k above 8 (the lists leave the registers), galleries beyond 2^32 bytes (the panels' bases are 64-bit already). */
+int mbn_similarity_tile_bf16(int *q_tile, int *g_tile, int Q, int D);
+size_t mbn_similarity_workspace_bytes_bf16(int Q, int G, int D, int k);
+int mbn_similarity_topk_bf16(mbn_context *ctx, void *topk_idx_i32, void *topk_score_f32, const void *queries, const void *gallery_bf16,
+                             const void *q_scale, const void *g_scale, int Q, int G, int D, int k, void *workspace, void *stream);
+int mbn_embed_rows_bf16(mbn_context *ctx, void *out_bf16, void *inv_norm, const void *in, int dtype, int N, int D, void *stream);
 
 /* Input front-end on device: uint8 HWC [N][rows][cols][3] -> fp32 NHWC x*scale+bias
  * (Keras MobileNet preprocessing is scale=1/127.5, bias=-1). */
@@ -1746,6 +1789,14 @@ int  mbn_net_classify(mbn_net *net, const void *images, int batch, int k, void *
 int  mbn_net_embed(mbn_net *net, const void *images, int batch, void *emb_f32, void *inv_norm_f32);
 int  mbn_net_nearest(mbn_net *net, const void *images, int batch, const void *gallery_f32, const void *g_scale_f32, int G, int k, void *idx_i32,
                      void *score_f32);
+/* ... with a bf16 gallery, in fp32 and bf16 mode (MBN_DT_I8: MBN_EUNSUPPORTED, as above):
+ *   mbn_net_embed_bf16    as mbn_net_embed with mbn_embed_rows_bf16: emb_bf16 [batch][D] bf16, the rows a gallery stores, and inv_norm (may be
+ *                         NULL) of the stored rows.
+ *   mbn_net_nearest_bf16  mbn_net_embed into buffers of the net (fp32 queries and their inverse norms), then mbn_similarity_topk_bf16 on
+ *                         gallery_bf16 [G][D] bf16. */
+int  mbn_net_embed_bf16(mbn_net *net, const void *images, int batch, void *emb_bf16, void *inv_norm_f32);
+int  mbn_net_nearest_bf16(mbn_net *net, const void *images, int batch, const void *gallery_bf16, const void *g_scale_f32, int G, int k,
+                          void *idx_i32, void *score_f32);
 /* Dense head (fully-convolutional MobileNet-V1; with a trained 1x1 conv_preds a DeepLab-style head): the classifier applied at EVERY pixel of the
  * last feature map instead of its average. For a plan whose last two layers are the pool and the FC (every plan of mbn_plan_build*), F = the layer
  * in front of the pool (27), h x w its output map:
